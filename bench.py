@@ -9,10 +9,15 @@ reference CPU matcher).  With --gpus N every rank holds a replica of the map and
 one collective of the path -- an RCCL all-gather of the [B,3] poses -- is double buffered and asynchronous.
 
 OUTPUT.  The LAST stdout line of rank 0 is ONE compact JSON object (< 4 KB, `compact_line`; tests/test_bench_line.py): the
-driver's contract keys, `roofline` and `cpu_baseline`, and `details` = the path of the file that holds the full record
-(gpurun_out/bench_details*.json, or $HSM_BENCH_DETAILS).  Round 4 printed the full record as the line -- 24.6 KB -- and the
-driver could not parse it.
+driver's contract keys (`metric`, `value`, `unit`, `ms_per_step` = wall-clock ms of one timed step, `higher_is_better`, `dtype`,
+...).  A PLAIN run (`--gpus 1 --steps K --warmup W`) does what that figure needs and nothing else: inputs, map, warm-up, ONE
+timed region of exactly K steps, the line.  `--dump-outputs DIR` then writes what the last timed step computed (DIR/pose.npy
+[B,3] and DIR/covariance.npy [B,9], float32; the inputs are generated from fixed seeds, so two builds compare output for output).
 
+--full adds what the benchmark measures beside the headline figure; the line then also carries `roofline` and `cpu_baseline`,
+and `details` = the path of the file that holds the full record (`$HSM_BENCH_DETAILS`, else `details_file` in
+hsm_bench/common.py):
+  timing        the median of --repeats (5) timed regions of K steps, and a sustained region of --sustain-s seconds
   roofline      the dominant kernel, one HIP event pair on its stream around the timed region.  `bound` names what binds
                 it -- VALU instruction issue -- and achieved / peak / frac are wave64 VALU instructions per second
                 against 1024 SIMDs x 2.4 GHz / 2 cycles, from counters collected IN THIS RUN: bench.py re-executes itself
@@ -24,18 +29,19 @@ driver could not parse it.
   cpu_baseline  the reference CPU matcher (oracle/_ref, else the oracle port) on the SAME map and scans, single thread
                 (the reference is single threaded), ~12 s of matching, plus the GPU-vs-CPU pose deviation on a 512-scan
                 sample and the fraction of bit-identical poses.  Runs on a host thread WHILE the counter passes run in
-                child processes, so the default run takes ~15 s on the GPU box.
+                child processes; then the all-cores CPU leg.
   fast_mode     (details file; `fast_mode_value` in the line) the same launch with HSM_PARITY_FAST (tree summation, opt-in)
+  gather_legs   (N > 1) the other ways of exchanging the poses, same launches, labelled
 
---all-configs adds to the DETAILS file: the same batch from SURVEY 8(d)'s start errors, HSM_PARITY_RELAXED, the all-cores CPU
-leg, the 3-level pyramid leg, independent batches on 4 streams, and compact child runs of the other BASELINE configs
-(configs[0], [1], [3] share, [4] replica), each with its own counter passes (~80 s).
+--all-configs (implies --full) adds to the DETAILS file: the same batch from SURVEY 8(d)'s start errors, HSM_PARITY_RELAXED,
+the 3-level pyramid leg, independent batches on 4 streams, and compact child runs of the other BASELINE configs (configs[0],
+[1], [3] share, [4] replica), each with its own counter passes (~80 s).
 
 --workload config2|config3pyr|config4|config5 measures one of the other BASELINE configs (latency of a single scan, 3-level
 batch, 4096^2 pyramid, dense 16k-beam match+update loop) on its own, same output convention.  config3pyr / config4 / config5
 also run with --gpus N: config4 is configs[3] itself at N = 8 (4096 scans per GPU on the 3-level 4096^2 pyramid, all-gather
 of the poses); config5 is configs[4] (replicated pyramid: rank 0 matches, pose + scan are broadcast, every rank replays the
-update, the maps are compared across ranks at the end).
+update, the maps are compared across ranks at the end).  Without --full they run as with --no-pmc --no-cpu --no-exact.
 """
 from __future__ import annotations
 
@@ -101,19 +107,25 @@ def main():
                          "CUs from its one generation of workgroups (+45 us for that launch): measured with the real nccl backend, us per "
                          "step = 103 / 65.5 / 62.0 for buckets of 1 / 8 / >= the region's steps, 59.6 without any gather, 58.5 at N = 1")
     ap.add_argument("--sustain-s", type=float, default=6.0,
-                    help="N = 1: seconds of back-to-back headline launches timed as ONE region after the K-step regions (the sustained "
+                    help="--full, N = 1: seconds of back-to-back headline launches timed as ONE region after the K-step regions (the sustained "
                          "clock, and long enough for a 5-second device monitor to see the GPU busy); 0 = skip")
     ap.add_argument("--no-pipelined", action="store_true", help="skip the multi-stream leg")
     ap.add_argument("--compact", action="store_true",
-                    help="extra workloads: the short form the default run embeds (fewer steps, smaller CPU samples)")
+                    help="extra workloads: the short form --all-configs embeds (fewer steps, smaller CPU samples)")
     ap.add_argument("--no-configs", action="store_true", help="(--all-configs) skip the legs for the other BASELINE configs")
-    ap.add_argument("--all-configs", "--full", dest="all_configs", action="store_true",
-                    help="the long run: 8(d)-start leg, relaxed leg, all-cores CPU leg, pyramid, pipelined and the other BASELINE configs, all into "
-                         "the details file (the default run keeps the headline, its counters, the fast-mode leg and the 1-thread CPU baseline: ~45 s)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: median of --repeats regions, sustained region, counter passes and roofline, fast-mode "
+                         "leg, CPU baselines (1 thread and all cores), N > 1 gather legs, details file (~45 s).  Off: the timed steps only")
+    ap.add_argument("--all-configs", dest="all_configs", action="store_true",
+                    help="the long run (implies --full): 8(d)-start leg, relaxed leg, pyramid, pipelined and the other BASELINE configs, all into "
+                         "the details file")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed: DIR/pose.npy [B,3], DIR/covariance.npy [B,9] (float32)")
     ap.add_argument("--no-relaxed", action="store_true", help="skip the HSM_PARITY_RELAXED leg")
     ap.add_argument("--leg", default=None, choices=["pmc", "pyramid", "pipelined", "gentle"],
-                    help="internal: a leg of the default run executed in a child process")
-    ap.add_argument("--repeats", type=int, default=5, help="timed regions of --steps launches each; the median one is reported (timed_regions keeps all)")
+                    help="internal: a leg of a --full run executed in a child process")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of --steps launches each; the median one is reported (timed_regions keeps all).  Default 5 with --full, else 1")
     ap.add_argument("--prewarm-ms", type=float, default=40.0,
                     help="untimed launches for this long before the warm-up steps of every timed run (engine clock settling)")
     ap.add_argument("--starts", default="headline", choices=["headline", "gentle"], help="internal (--leg pmc): start errors of the counter pass")
@@ -124,6 +136,15 @@ def main():
     ap.add_argument("--workload", default="config3", choices=sorted(WORKLOADS),
                     help="config3 = the headline (BASELINE configs[2]); others are the extra configs")
     args = ap.parse_args()
+    args.full = args.full or args.all_configs
+    if args.leg is None and not args.full:
+        # a plain run: set-up, warm-up, the timed steps, the line -- the legs beside the headline figure belong to --full
+        args.no_cpu = args.no_pmc = args.no_exact = args.no_relaxed = True
+        args.sustain_s = 0.0
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    if args.dump_outputs and (args.workload != "config3" or args.group > 0 or args.leg is not None):
+        ap.error("--dump-outputs writes the headline workload's outputs (--workload config3, no --group)")
     if args.steps is None:
         args.steps = 200 if args.workload == "config3" and args.leg != "pyramid" else 30
         if args.workload != "config3" and (args.compact or args.leg == "pmc"):

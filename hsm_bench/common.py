@@ -172,15 +172,20 @@ def emit_pending():
         emit(_PENDING.pop())
 
 
-def emit(out: dict):
+def emit(out: dict, details: bool = True):
     """Top-level result: full record -> details file, compact record -> the LAST stdout line.  A child leg of another bench.py
-    (run_child sets HSM_BENCH_CHILD=1) prints its full record for the parent to embed."""
+    (run_child sets HSM_BENCH_CHILD=1) prints its full record for the parent to embed.  details=False (a plain headline run):
+    no details file unless HSM_BENCH_DETAILS names one."""
     if _DEFER_EMIT:
         _PENDING.append(out)
         return
     flush_c_stdio()
     if os.environ.get("HSM_BENCH_CHILD") == "1":
         print(json.dumps(out))
+        return
+    if not details and not os.environ.get("HSM_BENCH_DETAILS"):
+        sys.stdout.flush()
+        print(compact_line(out, None), flush=True)
         return
     path = details_file(out)
     rel = None
@@ -193,6 +198,26 @@ def emit(out: dict):
         rel = f"(not written: {e})"
     sys.stdout.flush()
     print(compact_line(out, rel), flush=True)
+
+
+DUMP_LIMIT = 64 << 20  # bytes, all arrays of one --dump-outputs together
+
+
+def dump_outputs(directory: str, **arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, as the timed path returned it (float32 / float64).  Arrays whose rows
+    together exceed DUMP_LIMIT are cut to the same fixed, seeded sample of rows (kept as DIR/sample_rows.npy)."""
+    os.makedirs(directory, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    rows = None
+    if total > DUMP_LIMIT:
+        n = next(iter(arrays.values())).shape[0]
+        keep = max(1, int(DUMP_LIMIT // (total / n + 8)))  # (+ 8 B per row: the row index)
+        rows = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        np.save(os.path.join(directory, "sample_rows.npy"), rows.astype(np.float64))
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a if rows is None else a[rows])
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(directory, f"{name}.npy"), a)
 
 
 def make_inputs(rank: int, batch: int, n_build: int = 200):

@@ -11,8 +11,8 @@ import time
 import numpy as np
 
 from . import common
-from .common import (BATCH_PER_GPU, MAP_SIZE, N_BEAMS, RESOLUTION, algorithmic_bytes_per_iteration, emit, flush_c_stdio, make_inputs,
-                     multi_rank_record, pose_stats)
+from .common import (BATCH_PER_GPU, MAP_SIZE, N_BEAMS, RESOLUTION, algorithmic_bytes_per_iteration, dump_outputs, emit, flush_c_stdio,
+                     make_inputs, multi_rank_record, pose_stats)
 from .cpu import config1_plumbing, cpu_baseline, cpu_baseline_all_cores
 from .extra import extra_workload
 from .group import group_child_from_rank0
@@ -65,7 +65,7 @@ def headline(args):
         return
 
     B = args.batch
-    if args.leg is None and world == 1 and "HSM_BENCH_INPUT_CACHE" not in os.environ:
+    if args.full and args.leg is None and world == 1 and "HSM_BENCH_INPUT_CACHE" not in os.environ:
         # the child legs of this run load the inputs this process generates (make_inputs)
         import atexit
         import shutil
@@ -345,9 +345,11 @@ def headline(args):
     headline_ranks = getattr(run, "ranks", None)
     headline_gather = getattr(run, "gather_mode", "none")
     gpu_pose = d_pose.cpu().numpy().copy()
+    if args.dump_outputs and rank == 0:  # what a caller of the timed path receives from its last step
+        dump_outputs(args.dump_outputs, pose=gpu_pose, covariance=d_cov.cpu().numpy())
     cfg = matcher.last_launch_config()
     gather_legs = None
-    if multi:
+    if multi and args.full:
         # beside the contract line (one gather per batched match), labelled: the bucketed RCCL collective of round 5, a collective per
         # match, and no exchange at all -- same launches, same timing bracket (a leg that fails leaves its error, not the line)
         gather_legs = {}
@@ -403,7 +405,7 @@ def headline(args):
         fast_leg = (dtf, kf, d_pose.cpu().numpy().copy(), matcher.last_launch_config(), getattr(run, "regions", None), getattr(run, "sclk_hz", None))
         matcher.set_parity(capi.PARITY_AUTO)
     # the 1-thread CPU baseline runs on a host thread WHILE the counter passes run in child processes (the C loop releases the
-    # GIL; the box has far more cores than the two need): the default run stays within ~45 s of wall clock
+    # GIL; the box has far more cores than the two need): a --full run stays within ~45 s of wall clock
     cpu_box = {}
     cpu_thread = None
     if single and not args.no_cpu:
@@ -426,9 +428,11 @@ def headline(args):
     if cpu_thread is not None:
         cpu_thread.join()
     pmc = (pmc_all or {}).get(kernel_name)
-    rf = roofline_block(kernel_name, kern_ms, bytes_per_launch, N_BEAMS, its, B, pmc, pmc_err, clock_hz,
-                        sclk_hz=headline_sclk, committed_profile="r06")
-    if cfg.get("parity_effective") == "exact":
+    rf = None
+    if args.full:
+        rf = roofline_block(kernel_name, kern_ms, bytes_per_launch, N_BEAMS, its, B, pmc, pmc_err, clock_hz,
+                            sclk_hz=headline_sclk, committed_profile="r06")
+    if rf is not None and cfg.get("parity_effective") == "exact":
         rf["what_binds"] = ("VALU instruction issue plus the serial chain jobs of the reference's summation order (gn_match_exact.h): one "
                             "workgroup barrier per 64-beam round, a 64-deep dependent fp32 chain behind it; texels and endpoints "
                             "served from L2 / LDS / VGPRs; not HBM, not MFMA")
@@ -447,8 +451,9 @@ def headline(args):
                    "kernel": cfg},
         "matchdata_per_s": total * args.steps / dt,
         "timed_regions": regions,
-        "roofline": rf,
     }
+    if rf is not None:
+        out["roofline"] = rf
     if sustained:
         out["sustained"] = sustained
     if multi:
@@ -458,15 +463,17 @@ def headline(args):
                                    "none": "no exchange"}[headline_gather]
         if _direct.get("note"):
             out["config"]["gather"] += " -- FALLBACK: " + _direct["note"][:300]
-        out["gather_legs"] = gather_legs
+        if gather_legs is not None:
+            out["gather_legs"] = gather_legs
         if args.all_configs and not args.no_group and os.environ.get("HSM_BENCH_SHARE_GPU") != "1":
             # the C++ single-process group over the same devices, RCCL gather and peer gather (child of rank 0)
             rec = group_child_from_rank0(args, world, dist)
             if rank == 0:
                 out["group_cpp"] = rec
-    conv = np.abs(gpu_pose.astype(np.float64) - truth.astype(np.float64))
-    out["convergence"] = {"median_abs_err_xy_m": float(np.median(conv[:, :2])),
-                          "median_abs_err_theta_rad": float(np.median(conv[:, 2]))}
+    if args.full:
+        conv = np.abs(gpu_pose.astype(np.float64) - truth.astype(np.float64))
+        out["convergence"] = {"median_abs_err_xy_m": float(np.median(conv[:, :2])),
+                              "median_abs_err_theta_rad": float(np.median(conv[:, 2]))}
 
     exact_pose = gpu_pose if cfg.get("parity_effective") == "exact" else None
     full = bool(args.all_configs)
@@ -534,13 +541,16 @@ def headline(args):
         matcher.close()
         del matcher
         torch.cuda.empty_cache()
-        extra = ["--compact"] + (["--no-cpu"] if args.no_cpu else []) + (["--no-pmc"] if args.no_pmc else []) + \
+        extra = ["--compact", "--full"] + (["--no-cpu"] if args.no_cpu else []) + (["--no-pmc"] if args.no_pmc else []) + \
             (["--pmc-dump", args.pmc_dump] if args.pmc_dump else [])
         cf = {"configs[0]": config1_plumbing(capi) if not args.no_cpu else None}
         for key, wl in (("configs[1]", "config2"), ("configs[3] (one GPU's share)", "config4"), ("configs[4] (one replica)", "config5")):
             cf[key] = run_child(["--workload", wl] + extra, timeout_s=400)
         out["configs"] = cf
-    if not full and single:
+    if not args.full and single:
+        out["not_run"] = ("the repeated regions, sustained region, counter passes, roofline, fast-mode and CPU legs: `bench.py --full`; "
+                          "the gentle-start, relaxed, pyramid, pipelined and other-config legs: `bench.py --all-configs`")
+    elif not full and single:
         out["not_run"] = "the gentle-start, relaxed, pyramid, pipelined and other-config legs: `bench.py --all-configs` (details file)"
     if multi:
         dist.barrier()
@@ -549,4 +559,4 @@ def headline(args):
         if rank == 0:
             time.sleep(1.0)  # the other ranks exit now (and flush whatever their libraries still hold): the line comes last
     if rank == 0:
-        emit(out)
+        emit(out, details=args.full)

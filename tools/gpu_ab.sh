@@ -11,7 +11,7 @@ for wl in ${2:-config3}; do
  for rep in 1 2; do
   for v in $1; do
     if [ $v != base ]; then export HSM_LIB=$ROOT/hector_slam_amd/lib/variants/libhector_mi355_$v.so; else unset HSM_LIB; fi
-    python bench.py --workload $wl --no-cpu --no-exact --no-pmc --no-pyramid --steps ${STEPS:-100} > $OUT/${wl}_$v.json 2>$OUT/${wl}_$v.err
+    python bench.py --full --workload $wl --no-cpu --no-exact --no-pmc --no-pyramid --steps ${STEPS:-100} > $OUT/${wl}_$v.json 2>$OUT/${wl}_$v.err
     python - <<PY
 import json
 try:

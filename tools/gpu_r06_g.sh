@@ -10,5 +10,5 @@ HSM_HYPOTHESIS_EXAMPLES=${HSM_HYPOTHESIS_EXAMPLES:-30} HSM_PARITY_STATS=$OUT/par
 tail -16 "$OUT/pytest.log"
 echo "== smoke"; timeout 300 python __graft_entry__.py smoke 2>&1 | tail -1 | cut -c1-200
 echo "== driver bench command"; S=$(date +%s)
-HSM_BENCH_DETAILS=$OUT/bench_driver_like_details.json timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --pmc-dump "$OUT/pmc" > "$OUT/bench_driver_like.out" 2> "$OUT/bench_driver_like.err"; echo "bench rc=$? ($(( $(date +%s) - S )) s)"
+HSM_BENCH_DETAILS=$OUT/bench_driver_like_details.json timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 --pmc-dump "$OUT/pmc" > "$OUT/bench_driver_like.out" 2> "$OUT/bench_driver_like.err"; echo "bench rc=$? ($(( $(date +%s) - S )) s)"
 tail -1 "$OUT/bench_driver_like.out"

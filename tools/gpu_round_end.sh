@@ -11,7 +11,7 @@ HSM_HYPOTHESIS_EXAMPLES=60 HSM_PARITY_STATS=$OUT/parity_stats.jsonl timeout 1800
 tail -14 "$OUT/pytest.log"
 echo "== smoke"; timeout 300 python __graft_entry__.py smoke 2>&1 | tail -1 | cut -c1-200
 echo "== driver bench command"; S=$(date +%s)
-HSM_BENCH_DETAILS=$OUT/bench_driver_like_details.json timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --pmc-dump "$OUT/pmc_driver_like" > "$OUT/bench_driver_like.out" 2> "$OUT/bench_driver_like.err"; echo "bench rc=$? ($(( $(date +%s) - S )) s)"
+HSM_BENCH_DETAILS=$OUT/bench_driver_like_details.json timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 --pmc-dump "$OUT/pmc_driver_like" > "$OUT/bench_driver_like.out" 2> "$OUT/bench_driver_like.err"; echo "bench rc=$? ($(( $(date +%s) - S )) s)"
 python - "$OUT/bench_driver_like.out" <<'PY'
 import json, sys
 last = open(sys.argv[1]).read().strip().splitlines()[-1]
@@ -19,7 +19,7 @@ d = json.loads(last)
 print("LINE bytes", len(last)); print(last)
 PY
 echo "== same command under rocprofv3 --kernel-trace --stats"; S=$(date +%s)
-( cd /tmp && export TMPDIR=/tmp && HSM_BENCH_DETAILS=$OUT/bench_details_under_rocprof.json timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python $ROOT/bench.py --gpus 1 --steps 20 --warmup 5 --no-pmc --no-cpu > "$OUT/bench_under_rocprof.out" 2> "$OUT/stats.err" ); echo "rc=$? ($(( $(date +%s) - S )) s)"
+( cd /tmp && export TMPDIR=/tmp && HSM_BENCH_DETAILS=$OUT/bench_details_under_rocprof.json timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python $ROOT/bench.py --full --gpus 1 --steps 20 --warmup 5 --no-pmc --no-cpu > "$OUT/bench_under_rocprof.out" 2> "$OUT/stats.err" ); echo "rc=$? ($(( $(date +%s) - S )) s)"
 python - "$OUT" <<'PY'
 import csv, glob, os, shutil, sys
 out = sys.argv[1]
@@ -42,8 +42,8 @@ for k, v in (d.get("configs") or {}).items():
     print(k, "value", v.get("value"), "ms", v.get("ms_per_step"), "match/update", v.get("match_ms"), v.get("update_ms"), "fast", (v.get("fast_mode") or {}).get("ms_per_step"), "err", v.get("error"))
 PY
 echo "== multi-rank path on this box: one rank with a process group (nccl), two ranks sharing the device (self-launched), the C++ group"; S=$(date +%s)
-HSM_BENCH_FORCE_DIST=1 HSM_BENCH_DETAILS=$OUT/bench_one_rank_nccl_group_details.json timeout 600 python bench.py --gpus 1 --steps 200 --warmup 10 --no-pmc --no-cpu > "$OUT/bench_one_rank_nccl_group.out" 2> "$OUT/bench_one_rank_nccl_group.err"; echo "rc=$?"; tail -1 "$OUT/bench_one_rank_nccl_group.out" | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('direct gather per match', d['ms_per_step'], d.get('gather_legs'))"
-HSM_BENCH_SHARE_GPU=1 HSM_BENCH_DETAILS=$OUT/bench_two_ranks_one_device_details.json timeout 600 python bench.py --gpus 2 --steps 100 --warmup 10 --no-pmc --no-cpu > "$OUT/bench_two_ranks_one_device.out" 2> "$OUT/bench_two_ranks_one_device.err"; echo "rc=$?"; tail -1 "$OUT/bench_two_ranks_one_device.out" | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('2 ranks', d['ms_per_step'], d.get('gather_legs'))"
+HSM_BENCH_FORCE_DIST=1 HSM_BENCH_DETAILS=$OUT/bench_one_rank_nccl_group_details.json timeout 600 python bench.py --full --gpus 1 --steps 200 --warmup 10 --no-pmc --no-cpu > "$OUT/bench_one_rank_nccl_group.out" 2> "$OUT/bench_one_rank_nccl_group.err"; echo "rc=$?"; tail -1 "$OUT/bench_one_rank_nccl_group.out" | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('direct gather per match', d['ms_per_step'], d.get('gather_legs'))"
+HSM_BENCH_SHARE_GPU=1 HSM_BENCH_DETAILS=$OUT/bench_two_ranks_one_device_details.json timeout 600 python bench.py --full --gpus 2 --steps 100 --warmup 10 --no-pmc --no-cpu > "$OUT/bench_two_ranks_one_device.out" 2> "$OUT/bench_two_ranks_one_device.err"; echo "rc=$?"; tail -1 "$OUT/bench_two_ranks_one_device.out" | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('2 ranks', d['ms_per_step'], d.get('gather_legs'))"
 timeout 600 python bench.py --group 2 --steps 50 > "$OUT/bench_group2.out" 2> "$OUT/bench_group2.err"; echo "rc=$? ($(( $(date +%s) - S )) s)"
 echo "== node loop, default mode, 30000 scans"; S=$(date +%s)
 timeout 900 python tools/node_loop_parity.py 30000 --parity auto > "$OUT/node_loop_parity_default_30000.json" 2> "$OUT/node_loop.err"; echo "rc=$? ($(( $(date +%s) - S )) s)"; cut -c1-400 "$OUT/node_loop_parity_default_30000.json"
