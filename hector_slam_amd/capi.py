@@ -75,6 +75,9 @@ SIGNATURES = {
     "hsm_synchronize": (_i, [_vp]),
     "hsm_match_ingested": (_i, [_vp, _f32p, _f32p, _f32p]),
     "hsm_update_by_ingested": (_i, [_vp, _f32p]),
+    "hsm_match_batch_ranges_device": (_i, [_vp, _i, _vp, _vp, _i, _f, _f, _f, _f, _f, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "hsm_match_batch_ranges_workspace": (C.c_size_t, [_i, _i]),
+    "hsm_match_batch_ranges": (_i, [_vp, _i, _vp, _vp, _i, _f, _f, _f, _f, _f, _vp, _vp, _vp]),
     "hsm_occupancy_grid": (_i, [_vp, _i, _vp]),
     "hsm_ray_distances": (_i, [_vp, _i, _f, _f, _f, _i, _f32p, _f32p, _f32p, _f32p]),
     "hsm_likelihood_states": (_i, [_vp, _i, _i, _f32p, _vp, _i, _f32p]),
@@ -177,6 +180,12 @@ def shard_bounds(total: int, rank: int, world: int) -> tuple[int, int]:
     b, e = C.c_int(0), C.c_int(0)
     _check(load_library().hsm_shard_bounds(int(total), int(rank), int(world), C.byref(b), C.byref(e)), "hsm_shard_bounds")
     return b.value, e.value
+
+
+def match_batch_ranges_workspace(batch: int, n: int) -> int:
+    """bytes of the caller-owned workspace hsm_match_batch_ranges_device needs for `batch` scans of n beams (0: sizes it refuses);
+    host arithmetic, no device needed"""
+    return int(load_library().hsm_match_batch_ranges_workspace(int(batch), int(n)))
 
 
 def _check(rc: int, what: str):
@@ -521,6 +530,37 @@ class MapRepMultiMap:
         _check(self._lib.hsm_match_batch_device(self._h, batch, d_begin, d_pts, d_offsets or None, shared_n,
                                                 d_out_pose, d_out_cov or None, stream or None),
                "hsm_match_batch_device")
+
+    def match_batch_ranges(self, begin_world, ranges, angle_min, angle_increment, range_min, range_max, scale_to_map=None,
+                           want_cov=True):
+        """B raw LaserScans of one geometry (``ranges`` [B, n]) -> (pose [B, 3], cov [B, 9] or None, counts [B]): the node's
+        rosLaserScanToDataContainer and matchData per scan, converted and matched on the device.  Host arrays in/out."""
+        b = np.ascontiguousarray(begin_world, np.float32).reshape(-1, 3)
+        r = np.ascontiguousarray(ranges, np.float32)
+        B = b.shape[0]
+        if r.ndim != 2 or r.shape[0] != B:
+            raise ValueError("ranges must be [B, n] with B = len(begin_world)")
+        n = r.shape[1]
+        out = np.empty_like(b)
+        cov = np.zeros((B, 9), np.float32) if want_cov else None
+        counts = np.empty(B, np.int32)
+        s = self.getScaleToMap() if scale_to_map is None else scale_to_map
+        _check(self._lib.hsm_match_batch_ranges(self._h, B, b.ctypes.data, r.ctypes.data if r.size else None, n, angle_min,
+                                                angle_increment, range_min, range_max, s, out.ctypes.data,
+                                                None if cov is None else cov.ctypes.data, counts.ctypes.data),
+               "hsm_match_batch_ranges")
+        return out, cov, counts
+
+    def match_batch_ranges_device(self, batch, d_begin, d_ranges, n, angle_min, angle_increment, range_min, range_max,
+                                  scale_to_map, d_out_pose, d_out_cov, d_out_counts, d_workspace, workspace_bytes, stream=0):
+        """Raw device pointers (ints), asynchronous on ``stream`` (a hipStream_t value); the workspace is the caller's
+        (match_batch_ranges_workspace(batch, n) bytes)."""
+        _check(self._lib.hsm_match_batch_ranges_device(self._h, batch, d_begin, d_ranges or None, n, angle_min, angle_increment,
+                                                       range_min, range_max, scale_to_map, d_out_pose, d_out_cov or None,
+                                                       d_out_counts or None, d_workspace, workspace_bytes, stream or None),
+               "hsm_match_batch_ranges_device")
+
+    match_batch_ranges_workspace = staticmethod(match_batch_ranges_workspace)
 
     def match_batch_device_gather(self, batch, d_begin, d_pts, d_offsets, shared_n, d_out_pose, d_out_cov, exchange, first_row, lag,
                                   d_out_all, stream=0):

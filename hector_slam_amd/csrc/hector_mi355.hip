@@ -33,6 +33,8 @@ const char* ncclGetErrorString(ncclResult_t result);
 ncclResult_t ncclGetVersion(int* version);
 }
 #endif
+#include <limits.h>
+#include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -901,6 +903,8 @@ void hsm_destroy(hsm_ctx* h) {
   TEARDOWN(log, hipFree(h->d_ranges));
   TEARDOWN(log, hipFree(h->d_trig));
   TEARDOWN(log, hipFree(h->d_ingest));
+  for (hsm_ctx::RangesGeometry& g : h->ranges_geoms) TEARDOWN(log, hipFree(g.d));
+  TEARDOWN(log, hipFree(h->d_rbatch));
   TEARDOWN(log, hipFree(h->d_occ));
   if (h->h_scan_pinned) TEARDOWN(log, hipHostFree(h->h_scan_pinned));
   if (h->evt_updates) TEARDOWN(log, hipEventDestroy(h->evt_updates));
@@ -1670,6 +1674,19 @@ static int finish_ingest(hsm_ctx* h, float* out_pts_xy, int* out_n) {
   return HSM_OK;
 }
 
+// the node's running fp32 angle and its float cos/sin (HectorMappingRos.cpp:487,502,505): sensor constants, evaluated on the
+// host exactly as the node does, as (cos, sin) pairs -- the table of hsm_ingest_laser_scan and hsm_match_batch_ranges_device
+static std::vector<float> node_scan_trig(int n, float angle_min, float angle_increment) {
+  std::vector<float> t(2 * (size_t)n);
+  float angle = angle_min;
+  for (int i = 0; i < n; ++i) {
+    t[2 * i] = cosf(angle);
+    t[2 * i + 1] = sinf(angle);
+    angle += angle_increment;
+  }
+  return t;
+}
+
 int hsm_ingest_laser_scan(hsm_ctx* h, const float* ranges, int n, float angle_min, float angle_increment,
                           float range_min, float range_max, float scale_to_map, float* out_pts_xy, int* out_n) {
   if (!h) return fail(HSM_ERR_INVALID, "null context");
@@ -1679,15 +1696,7 @@ int hsm_ingest_laser_scan(hsm_ctx* h, const float* ranges, int n, float angle_mi
   if (int rc = select_device(h)) return rc;
   if (int rc = ensure_ingest_capacity(h, n)) return rc;
   if (h->trig_kind != 0 || h->trig_n != n || h->trig_a0 != angle_min || h->trig_inc != angle_increment) {
-    // the node's running fp32 angle and its float cos/sin (HectorMappingRos.cpp:487,502,505): sensor
-    // constants, evaluated once per geometry on the host exactly as the node does
-    std::vector<float> t(2 * (size_t)n);
-    float angle = angle_min;
-    for (int i = 0; i < n; ++i) {
-      t[2 * i] = cosf(angle);
-      t[2 * i + 1] = sinf(angle);
-      angle += angle_increment;
-    }
+    const std::vector<float> t = node_scan_trig(n, angle_min, angle_increment);
     if (n > 0) HIP_TRY(hipMemcpy(h->d_trig, t.data(), (size_t)n * sizeof(float2), hipMemcpyHostToDevice));
     h->trig_kind = 0;
     h->trig_n = n;
@@ -1797,6 +1806,171 @@ int hsm_update_by_ingested(hsm_ctx* h, const float pose_world[3]) {
   static const float dummy[2] = {0.0f, 0.0f};
   const float* hp = h->ingest_n > 0 ? h->h_ingest.data() : dummy;
   return update_impl(h, pose_world, hp, h->ingest_n, h->ingest_origo, h->d_ingest);
+}
+
+// ---- B raw scans of one sensor geometry: ingestion kernels + the batched matcher, one stream-ordered sequence ----
+
+namespace {
+
+// workspace of hsm_match_batch_ranges_device, byte offsets: counts[B] | offsets[B + 1] | copy of the ranges[B * n] |
+// endpoints[max(B * n, 1)], each region 256-byte aligned.  The endpoint region keeps one element when every scan is empty:
+// the matcher clamps an empty scan's loads to element 0 (gn_match_exact.h).  false = sizes the entry refuses.
+struct RangesLayout {
+  size_t counts, offsets, copy, pts, total;
+};
+
+bool ranges_layout(int batch, int n, RangesLayout* L) {
+  if (batch < 0 || n < 0 || n > HSM_MAX_UPDATE_BEAMS || (size_t)batch * (size_t)n > (size_t)INT_MAX) return false;
+  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t bn = (size_t)batch * (size_t)n;
+  L->counts = 0;
+  L->offsets = L->counts + al((size_t)batch * sizeof(int));
+  L->copy = L->offsets + al(((size_t)batch + 1) * sizeof(int));
+  L->pts = L->copy + al(bn * sizeof(float));
+  L->total = L->pts + al((bn > 0 ? bn : 1) * sizeof(float2));
+  return true;
+}
+
+}  // namespace
+
+size_t hsm_match_batch_ranges_workspace(int batch, int n) {
+  RangesLayout L;
+  return ranges_layout(batch, n, &L) ? L.total : 0;
+}
+
+// true where `p` is device memory (hipMalloc / a torch allocation), which the compaction may read a second time; false for
+// pinned host memory (and anything the runtime does not know), which is read once and copied into the workspace
+static bool is_device_memory(const void* p) {
+  hipPointerAttribute_t a;
+  if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+    (void)hipGetLastError();  // (the failed query's own error: not left for the next launch check)
+    return false;
+  }
+  return a.type == hipMemoryTypeDevice && !a.isManaged;
+}
+
+// ranges_on_device: 1 = d_ranges is known to be device memory, -1 = ask the runtime
+static int match_batch_ranges_nolock(hsm_ctx* h, int batch, const float* d_begin_world, const float* d_ranges, int n,
+                                     float angle_min, float angle_increment, float range_min, float range_max,
+                                     float scale_to_map, float* d_out_pose, float* d_out_cov, int* d_out_counts,
+                                     void* d_workspace, size_t workspace_bytes, void* stream, int ranges_on_device = -1) {
+  if (batch < 0 || n < 0 || !d_begin_world || !d_out_pose || !d_workspace || (batch > 0 && n > 0 && !d_ranges))
+    return fail(HSM_ERR_INVALID, "hsm_match_batch_ranges_device: bad argument");
+  RangesLayout L;
+  if (!ranges_layout(batch, n, &L))
+    return fail(HSM_ERR_TOO_LARGE, "hsm_match_batch_ranges_device: n > HSM_MAX_UPDATE_BEAMS or batch * n > INT_MAX");
+  if (workspace_bytes < L.total || ((uintptr_t)d_workspace & 7u) != 0)
+    return fail(HSM_ERR_INVALID, "hsm_match_batch_ranges_device: workspace smaller than hsm_match_batch_ranges_workspace(batch, n) "
+                                 "or not 8-byte aligned");
+  if (batch == 0) return HSM_OK;
+  if (int rc = select_device(h)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const float2* trig = nullptr;
+  if (n > 0) {
+    unsigned a0_bits, inc_bits;
+    memcpy(&a0_bits, &angle_min, sizeof a0_bits);
+    memcpy(&inc_bits, &angle_increment, sizeof inc_bits);
+    for (const hsm_ctx::RangesGeometry& g : h->ranges_geoms)
+      if (g.n == n && g.a0_bits == a0_bits && g.inc_bits == inc_bits) trig = g.d;
+    if (!trig) {
+      // a new table is an allocation and a copy: not while the caller captures the stream into a graph (nothing is enqueued).
+      // The copy goes on the caller's stream, not the null stream, and waits for that stream only
+      hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+      if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+        return fail(HSM_ERR_INVALID, "hsm_match_batch_ranges_device: sensor geometry not seen before while the stream is being "
+                                     "captured (no allocation under capture: make one call with this geometry before capturing)");
+      const std::vector<float> t = node_scan_trig(n, angle_min, angle_increment);
+      float2* d = nullptr;
+      HIP_TRY(hipMalloc((void**)&d, (size_t)n * sizeof(float2)));
+      hipError_t e = hipMemcpyAsync(d, t.data(), (size_t)n * sizeof(float2), hipMemcpyHostToDevice, s);
+      if (e == hipSuccess) e = hipStreamSynchronize(s);  // (`t` is a host temporary)
+      if (e != hipSuccess) {
+        (void)hipFree(d);
+        return fail(HSM_ERR_HIP, "hsm_match_batch_ranges_device: sensor table upload", e);
+      }
+      h->ranges_geoms.push_back({n, a0_bits, inc_bits, d});
+      trig = d;
+    }
+  }
+  char* ws = (char*)d_workspace;
+  int* counts = reinterpret_cast<int*>(ws + L.counts);
+  int* offsets = reinterpret_cast<int*>(ws + L.offsets);
+  // pinned host ranges cross the link once (the compaction reads the workspace copy); device ranges are read twice instead
+  const bool on_device = n > 0 && (ranges_on_device == 1 || (ranges_on_device < 0 && is_device_memory(d_ranges)));
+  float* copy = on_device ? nullptr : reinterpret_cast<float*>(ws + L.copy);
+  float2* pts = reinterpret_cast<float2*>(ws + L.pts);
+  const float maxRangeForContainer = range_max - 0.1f;  // HectorMappingRos.cpp:493, on the host as in hsm_ingest_laser_scan
+  const int blocks = (batch - 1) / kRangesScansPerBlock + 1;
+  hipLaunchKernelGGL(ranges_gate_count_kernel, dim3(blocks), dim3(256), 0, s, d_ranges, batch, n, range_min,
+                     maxRangeForContainer, copy, counts);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(ranges_offsets_kernel, dim3(1), dim3(1024), 0, s, counts, batch, offsets, d_out_counts);
+  HIP_TRY(hipGetLastError());
+  if (n > 0) {
+    // (however the beams are read, scan b writes below offsets[b] + n <= batch * n: inside the endpoint region)
+    hipLaunchKernelGGL(ranges_compact_kernel, dim3(blocks), dim3(256), 0, s, copy ? copy : d_ranges, trig, batch, n, range_min,
+                       maxRangeForContainer, scale_to_map, offsets, pts);
+    HIP_TRY(hipGetLastError());
+  }
+  // n is a true bound of every scan's length after the gate
+  return match_batch_device_nolock(h, batch, d_begin_world, reinterpret_cast<const float*>(pts), offsets, n, d_out_pose,
+                                   d_out_cov, stream, n);
+}
+
+int hsm_match_batch_ranges_device(hsm_ctx* h, int batch, const float* d_begin_world, const float* d_ranges, int n,
+                                  float angle_min, float angle_increment, float range_min, float range_max,
+                                  float scale_to_map, float* d_out_pose, float* d_out_cov, int* d_out_counts,
+                                  void* d_workspace, size_t workspace_bytes, void* stream) {
+  if (!h) return fail(HSM_ERR_INVALID, "null context");
+  std::lock_guard<std::mutex> lk(h->mu);
+  return match_batch_ranges_nolock(h, batch, d_begin_world, d_ranges, n, angle_min, angle_increment, range_min, range_max,
+                                   scale_to_map, d_out_pose, d_out_cov, d_out_counts, d_workspace, workspace_bytes, stream);
+}
+
+int hsm_match_batch_ranges(hsm_ctx* h, int batch, const float* begin_world, const float* ranges, int n, float angle_min,
+                           float angle_increment, float range_min, float range_max, float scale_to_map, float* out_pose,
+                           float* out_cov, int* out_counts) {
+  if (!h) return fail(HSM_ERR_INVALID, "null context");
+  if (batch < 0 || n < 0 || !begin_world || !out_pose || (batch > 0 && n > 0 && !ranges))
+    return fail(HSM_ERR_INVALID, "hsm_match_batch_ranges: bad argument");
+  RangesLayout L;
+  if (!ranges_layout(batch, n, &L))
+    return fail(HSM_ERR_TOO_LARGE, "hsm_match_batch_ranges: n > HSM_MAX_UPDATE_BEAMS or batch * n > INT_MAX");
+  if (batch == 0) return HSM_OK;
+  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t b_begin = (size_t)batch * 3 * sizeof(float), b_cov = (size_t)batch * 9 * sizeof(float);
+  const size_t b_counts = (size_t)batch * sizeof(int), b_ranges = (size_t)batch * n * sizeof(float);
+  // device block: start poses | poses | covariances | counts | raw ranges | workspace
+  const size_t o_pose = al(b_begin), o_cov = o_pose + al(b_begin), o_counts = o_cov + al(b_cov);
+  const size_t o_ranges = o_counts + al(b_counts), o_ws = o_ranges + al(b_ranges), need = o_ws + L.total;
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (int rc = select_device(h)) return rc;
+  if (need > h->d_rbatch_cap) {
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (h->d_rbatch) HIP_TRY(hipFree(h->d_rbatch));
+    h->d_rbatch = nullptr;
+    h->d_rbatch_cap = 0;
+    HIP_TRY(hipMalloc(&h->d_rbatch, need));
+    h->d_rbatch_cap = need;
+  }
+  char* base = (char*)h->d_rbatch;
+  float* d_begin = (float*)base;
+  float* d_pose = (float*)(base + o_pose);
+  float* d_cov = (float*)(base + o_cov);
+  int* d_counts = (int*)(base + o_counts);
+  float* d_ranges = (float*)(base + o_ranges);
+  HIP_TRY(hipMemcpyAsync(d_begin, begin_world, b_begin, hipMemcpyHostToDevice, h->stream));
+  if (b_ranges) HIP_TRY(hipMemcpyAsync(d_ranges, ranges, b_ranges, hipMemcpyHostToDevice, h->stream));
+  if (out_cov) HIP_TRY(hipMemcpyAsync(d_cov, out_cov, b_cov, hipMemcpyHostToDevice, h->stream));  // in/out (empty scans)
+  if (int rc = match_batch_ranges_nolock(h, batch, d_begin, d_ranges, n, angle_min, angle_increment, range_min, range_max,
+                                         scale_to_map, d_pose, out_cov ? d_cov : nullptr, d_counts, base + o_ws, L.total,
+                                         h->stream, 1))
+    return rc;
+  HIP_TRY(hipMemcpyAsync(out_pose, d_pose, b_begin, hipMemcpyDeviceToHost, h->stream));
+  if (out_cov) HIP_TRY(hipMemcpyAsync(out_cov, d_cov, b_cov, hipMemcpyDeviceToHost, h->stream));
+  if (out_counts) HIP_TRY(hipMemcpyAsync(out_counts, d_counts, b_counts, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return HSM_OK;
 }
 
 static int ensure_batch_bytes(hsm_ctx* h, size_t need) {

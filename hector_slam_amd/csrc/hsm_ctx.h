@@ -152,6 +152,16 @@ struct hsm_ctx {
   int ingest_n = -1;                // -1 = nothing ingested yet
   float trig_a0 = 0.f, trig_inc = 0.f;
   int trig_n = -1;
+  // sensor geometries of hsm_match_batch_ranges*: one immutable float2 table per (n, angle_min bits, angle_increment bits),
+  // never rewritten and freed by hsm_destroy only (a queued or captured launch may read it any time before)
+  struct RangesGeometry {
+    int n;
+    unsigned a0_bits, inc_bits;
+    float2* d;
+  };
+  std::vector<RangesGeometry> ranges_geoms;
+  void* d_rbatch = nullptr;  // hsm_match_batch_ranges: start poses, results, counts and the workspace of its device call
+  size_t d_rbatch_cap = 0;
   signed char* d_occ = nullptr;     // occupancy export staging
   size_t d_occ_cap = 0;
   unsigned coop_bar_base = 0;   // value the grid-barrier counter has when the next cooperative launch starts

@@ -1102,6 +1102,85 @@ __global__ void __launch_bounds__(1024) ingest_laser_scan_kernel(const float* __
   if (threadIdx.x == 0) *out_n = base;
 }
 
+// The same conversion for B scans of one sensor geometry (hsm_match_batch_ranges_device): ranges[b * n + i] -> the CSR input
+// of the batched matcher, in three launches on the caller's stream.
+//   gate/count  one wavefront per scan: the range gate above, counts[b] = sum of the ballots' popcounts.  Ranges in host
+//               memory (pinned, device-accessible) are copied into the workspace on the way, so they cross the link once and the
+//               compaction reads the copy; ranges in device memory are read again by the compaction (copy == nullptr)
+//   offsets     one workgroup: exclusive scan of counts into offsets[B + 1], 1024 scans per pass, any B
+//   compact     one wavefront per scan: the kept beams in beam order at offsets[b] + rank, with the arithmetic of
+//               ingest_laser_scan_kernel operation for operation (scale first, then the two products)
+constexpr int kRangesScansPerBlock = 4;  // 256 threads
+
+__global__ void __launch_bounds__(256) ranges_gate_count_kernel(const float* __restrict__ ranges, int batch, int n,
+                                                                 float range_min, float max_range_for_container,
+                                                                 float* __restrict__ copy, int* __restrict__ counts) {
+  const int lane = threadIdx.x & 63;
+  const long long b = (long long)blockIdx.x * kRangesScansPerBlock + (threadIdx.x >> 6);  // (no int overflow for batch near INT_MAX)
+  if (b >= batch) return;  // (uniform per wavefront)
+  const size_t row = (size_t)b * n;
+  int c = 0;
+  for (int i0 = 0; i0 < n; i0 += 64) {
+    const int i = i0 + lane;
+    const float dist = i < n ? ranges[row + i] : 0.0f;
+    if (copy != nullptr && i < n) copy[row + i] = dist;
+    c += __popcll(__ballot((i < n) && (dist > range_min) && (dist < max_range_for_container)));
+  }
+  if (lane == 0) counts[b] = c;
+}
+
+__global__ void __launch_bounds__(1024) ranges_offsets_kernel(const int* __restrict__ counts, int batch,
+                                                              int* __restrict__ offsets, int* __restrict__ out_counts) {
+  __shared__ int wave_sum[16];
+  __shared__ int carry;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (threadIdx.x == 0) carry = 0;
+  __syncthreads();
+  for (long long b0 = 0; b0 < batch; b0 += 1024) {
+    const long long b = b0 + threadIdx.x;
+    const int c = b < batch ? counts[b] : 0;
+    if (out_counts != nullptr && b < batch) out_counts[b] = c;
+    int x = c;  // inclusive scan inside the wavefront
+    for (int d = 1; d < 64; d <<= 1) {
+      const int y = __shfl_up(x, d);
+      if (lane >= d) x += y;
+    }
+    if (lane == 63) wave_sum[wave] = x;
+    __syncthreads();
+    int base = carry;
+    for (int w = 0; w < wave; ++w) base += wave_sum[w];
+    if (b < batch) offsets[b] = base + x - c;
+    __syncthreads();                              // every thread has read `carry`
+    if (threadIdx.x == 1023) carry = base + x;    // the last thread's inclusive sum: everything up to this pass's end
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) offsets[batch] = carry;
+}
+
+__global__ void __launch_bounds__(256) ranges_compact_kernel(const float* __restrict__ ranges, const float2* __restrict__ trig,
+                                                              int batch, int n, float range_min, float max_range_for_container,
+                                                              float scale_to_map, const int* __restrict__ offsets,
+                                                              float2* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const long long b = (long long)blockIdx.x * kRangesScansPerBlock + (threadIdx.x >> 6);
+  if (b >= batch) return;
+  const float* __restrict__ r = ranges + (size_t)b * n;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  int pos = offsets[b];
+  for (int i0 = 0; i0 < n; i0 += 64) {
+    const int i = i0 + lane;
+    float dist = i < n ? r[i] : 0.0f;
+    const bool keep = (i < n) && (dist > range_min) && (dist < max_range_for_container);
+    const unsigned long long m = __ballot(keep);
+    if (keep) {
+      dist *= scale_to_map;
+      const float2 cs = trig[i];
+      out[pos + __popcll(m & below)] = make_float2(cs.x * dist, cs.y * dist);
+    }
+    pos += __popcll(m);
+  }
+}
+
 // rosPointCloudToDataContainer (HectorMappingRos.cpp:509-542), optionally preceded by
 // laser_geometry's projectLaser (the node's default path, :273-282; third party, algorithm stated in
 // include/hector_mi355/capi.h): one pass, ordered compaction like the kernel above.  tf arithmetic is fp64

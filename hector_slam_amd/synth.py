@@ -8,11 +8,15 @@ reaches the matcher (hector_mapping/src/HectorMappingRos.cpp:483-507,
 ``rosLaserScanToDataContainer``: keep ``range_min < r < range_max - 0.1``,
 endpoint = (cos(a) r s, sin(a) r s) with s = scaleToMap, all fp32).
 
-Pure numpy, no GPU, no oracle: this module only produces inputs.
+Pure numpy (plus the C library's cosf / sinf for the node's sensor table), no GPU, no oracle: this module only
+produces inputs.
 """
 from __future__ import annotations
 
+import ctypes
+import ctypes.util
 import dataclasses
+import functools
 import math
 
 import numpy as np
@@ -98,6 +102,51 @@ def scan_to_points(ranges: np.ndarray, angles: np.ndarray, scale_to_map: float,
     pts[:, 0] = np.cos(a).astype(np.float32) * r
     pts[:, 1] = np.sin(a).astype(np.float32) * r
     return pts
+
+
+@functools.lru_cache(maxsize=16)
+def _node_trig(n: int, a0_bits: int, inc_bits: int) -> np.ndarray:
+    libm = ctypes.CDLL(ctypes.util.find_library("m"))
+    cosf, sinf = libm.cosf, libm.sinf
+    for f in (cosf, sinf):
+        f.restype, f.argtypes = ctypes.c_float, [ctypes.c_float]
+    inc = np.array([inc_bits], np.uint32).view(np.float32)[0]
+    angle = np.array([a0_bits], np.uint32).view(np.float32)[0]
+    t = np.empty((n, 2), np.float32)
+    for i in range(n):
+        t[i] = cosf(float(angle)), sinf(float(angle))
+        angle = np.float32(angle + inc)
+    t.setflags(write=False)
+    return t
+
+
+def node_scan_trig(n: int, angle_min: float, angle_increment: float) -> np.ndarray:
+    """(cos, sin) per beam as the node evaluates them: the C library's float cosf / sinf of the running fp32 angle
+    (HectorMappingRos.cpp:487,502,505); [n, 2] float32, read-only"""
+    bits = np.array([angle_min, angle_increment], np.float32).view(np.uint32)
+    return _node_trig(int(n), int(bits[0]), int(bits[1]))
+
+
+def ranges_to_csr(ranges: np.ndarray, angle_min: float, angle_increment: float, range_min: float, range_max: float,
+                  scale_to_map: float):
+    """rosLaserScanToDataContainer (HectorMappingRos.cpp:483-507) for B scans of one geometry, ranges [B, n], laid out as
+    the batched matcher's CSR input: (counts [B] int32, offsets [B + 1] int32, endpoints [total, 2] float32, level-0 cell
+    units, each scan's kept beams in beam order).  fp32 throughout: keep iff range_min < r < range_max - 0.1f (NaN and
+    +-inf fail both), then r * scale_to_map, then (cos * r, sin * r)."""
+    r = np.ascontiguousarray(ranges, np.float32)
+    B, n = r.shape
+    with np.errstate(invalid="ignore"):
+        keep = (r > np.float32(range_min)) & (r < np.float32(np.float32(range_max) - np.float32(0.1)))
+    counts = keep.sum(1).astype(np.int32)
+    offsets = np.zeros(B + 1, np.int32)
+    np.cumsum(counts, out=offsets[1:])
+    t = node_scan_trig(n, angle_min, angle_increment)
+    rows, beams = np.nonzero(keep)  # row-major: scan by scan, beams in order
+    d = r[rows, beams] * np.float32(scale_to_map)
+    pts = np.empty((d.shape[0], 2), np.float32)
+    pts[:, 0] = t[beams, 0] * d
+    pts[:, 1] = t[beams, 1] * d
+    return counts, offsets, pts
 
 
 def make_scan(world: World, pose, n_beams: int, scale_to_map: float, rng: np.random.Generator | None,

@@ -26,6 +26,8 @@
 #ifndef HECTOR_MI355_CAPI_H
 #define HECTOR_MI355_CAPI_H
 
+#include <stddef.h>
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -357,6 +359,42 @@ int hsm_ingest_laser_scan_tf(hsm_ctx* h, const float* ranges, int n, float angle
                              float sqr_laser_min_dist, float sqr_laser_max_dist, float laser_z_min,
                              float laser_z_max, float scale_to_map, float* out_pts_xy, int* out_n,
                              float out_origo[2]);
+/* replaces: rosLaserScanToDataContainer (HectorMappingRos.cpp:483-507) followed by MapRepMultiMap::matchData
+ *           (HSL/slam_main/MapRepMultiMap.h:116-132), for B raw scans of ONE sensor geometry at once (extension: the
+ *           node converts and matches one scan per callback).  Per scan the result is bit for bit what the node's
+ *           conversion (the gate, scale and products of hsm_ingest_laser_scan) and a matchData of that container give
+ *           (default mode; HSM_PARITY_FAST: what hsm_match_batch_device gives on that container).
+ * DEVICE pointers (or device-accessible pinned host memory for d_ranges):
+ *   d_begin_world  [B*3]    d_ranges [B*n] LaserScan.ranges[] of scan b at b*n.  Pinned host memory is read exactly once
+ *                  (the first kernel copies it into the workspace); device memory is read by the gate and again by the
+ *                  compaction.  Either way not after the call's kernels have run
+ *   d_out_pose     [B*3]    d_out_cov [B*9] or NULL (in/out)    d_out_counts [B] or NULL: beams each scan kept
+ *   d_workspace    caller-owned, at least hsm_match_batch_ranges_workspace(B, n) bytes, 8-byte aligned; holds the CSR
+ *                  container (counts, int32 offsets, endpoints) until the match has run -- one workspace per stream in flight
+ * The (cos, sin) table of the geometry (n, angle_min, angle_increment; keyed on their bit patterns) is evaluated on the
+ * host with the node's running fp32 angle, uploaded once and kept until hsm_destroy.  A geometry not seen before while
+ * `stream` is being captured into a graph returns HSM_ERR_INVALID and enqueues nothing (no allocation under capture: one
+ * call with that geometry before capturing).  A new geometry allocates its table and copies it on `stream`, then waits for
+ * `stream`: do not introduce one while another thread captures in the global capture mode.
+ * `stream` is a hipStream_t (NULL = default stream); the call is asynchronous with the ordering contract of
+ * hsm_match_batch_device: behind every map update queued so far, the next update behind it.  Conversion and match are
+ * one stream-ordered sequence on the device, no host round trip between them.
+ * A scan that keeps no beam returns its start pose and leaves its covariance untouched (ScanMatcher.h:68,189).
+ * HSM_ERR_INVALID: null pointer, batch < 0, n < 0, workspace too small; HSM_ERR_TOO_LARGE: n > HSM_MAX_UPDATE_BEAMS
+ * or batch * n > INT_MAX.  Nothing is launched in either case. */
+int hsm_match_batch_ranges_device(hsm_ctx* h, int batch, const float* d_begin_world, const float* d_ranges, int n,
+                                  float angle_min, float angle_increment, float range_min, float range_max,
+                                  float scale_to_map, float* d_out_pose, float* d_out_cov, int* d_out_counts,
+                                  void* d_workspace, size_t workspace_bytes, void* stream);
+/* bytes of hsm_match_batch_ranges_device's workspace for `batch` scans of n beams; 0 for sizes the entry refuses.
+ * Host arithmetic only: callable without a device. */
+size_t hsm_match_batch_ranges_workspace(int batch, int n);
+/* the same with HOST pointers (begin_world [B*3], ranges [B*n], out_pose [B*3], out_cov [B*9] or NULL (in/out),
+ * out_counts [B] or NULL): copies 4 B per beam in, one device call on the context's stream, results out; synchronous.
+ * The workspace is the context's own. */
+int hsm_match_batch_ranges(hsm_ctx* h, int batch, const float* begin_world, const float* ranges, int n,
+                           float angle_min, float angle_increment, float range_min, float range_max, float scale_to_map,
+                           float* out_pose, float* out_cov, int* out_counts);
 /* hsm_match / hsm_update_by_scan on the ingested scan (no endpoint upload; origo as ingested) */
 int hsm_match_ingested(hsm_ctx* h, const float begin_world[3], float out_pose_world[3], float cov[9]);
 int hsm_update_by_ingested(hsm_ctx* h, const float pose_world[3]);
