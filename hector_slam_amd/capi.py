@@ -129,6 +129,7 @@ SIGNATURES = {
     "hsm_debug_set_coop_barrier": (_i, [_vp, C.c_uint]),
     "hsm_debug_set_coop_mute": (_i, [_vp, _i]),
     "hsm_debug_coop_fallbacks": (_i, [_vp]),
+    "hsm_debug_set_schedule": (_i, [_vp, _i, _i]),
     "hsm_debug_spec_stats": (_i, [_vp, _i, _vp]),
     "hsm_debug_marks_nonzero": (_i, [_vp, _i, _vp]),
     "hsm_debug_sincos": (_i, [_vp, _i, _f32p, _f32p, _f32p]),
@@ -640,6 +641,21 @@ class MapRepMultiMap:
 
     def debug_coop_fallbacks(self):
         return int(self._lib.hsm_debug_coop_fallbacks(self._h))
+
+    def debug_set_schedule(self, level, gn_steps=1):
+        """batched entries run `level` only, with `gn_steps` GN steps (1 + maxIterations); level < 0 restores the schedule"""
+        _check(self._lib.hsm_debug_set_schedule(self._h, int(level), int(gn_steps)), "hsm_debug_set_schedule")
+
+    def match_trace(self, begin_world, pts, origo=_ZERO2):
+        """matchData with the hook trace: (pose, cov, trace [steps, 12]) -- per GN step the map-frame estimate after the
+        step [3] and the H of that step [9], column major (hsm_match_trace)"""
+        a, p, n = _pts(pts)
+        steps_cap = self.gn_iterations_per_match()
+        trace = np.zeros((steps_cap, 12), np.float32)
+        out, cov, steps = np.empty(3, np.float32), np.zeros(9, np.float32), C.c_int()
+        _check(self._lib.hsm_match_trace(self._h, _v(begin_world, 3), p, n, _v(origo, 2), out, cov, trace.reshape(-1),
+                                         steps_cap, C.byref(steps)), "hsm_match_trace")
+        return out, cov, trace[:steps.value]
 
     def match_level(self, level, begin_world, pts_level, max_iter, cov=None):
         a, p, n = _pts(pts_level)

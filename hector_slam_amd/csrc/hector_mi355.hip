@@ -372,8 +372,10 @@ int launch_match_mode(hsm_ctx* h, const MatchParams& P, int max_n, hipStream_t s
 }
 
 // the schedule of MapRepMultiMap::matchData (MapRepMultiMap.h:116-132): coarse levels
-// maxIterations = 3, level 0 maxIterations = 5, each plus the unconditional first step
-void fill_schedule(const hsm_ctx* h, MatchParams& P) {
+// maxIterations = 3, level 0 maxIterations = 5, each plus the unconditional first step.  `batched`: the batched entries, where
+// the test hook hsm_debug_set_schedule may restrict the schedule to one level (every level's view stays filled: the batch
+// order reads level 0's)
+void fill_schedule(const hsm_ctx* h, MatchParams& P, bool batched = false) {
   const int nl = (int)h->levels.size();
   for (int l = 0; l < nl; ++l) {
     // static_cast<float>(1.0 / pow(2.0, level)) -- a power of two, exact in fp32
@@ -382,6 +384,10 @@ void fill_schedule(const hsm_ctx* h, MatchParams& P) {
   }
   P.first_level = nl - 1;
   P.last_level = 0;
+  if (batched && h->sched_level >= 0 && h->sched_level < nl) {
+    P.lv[h->sched_level].gn_steps = h->sched_steps;
+    P.first_level = P.last_level = h->sched_level;
+  }
 }
 
 int valid_level(const hsm_ctx* h, int level) {
@@ -1028,7 +1034,7 @@ static int match_batch_device_nolock(hsm_ctx* h, int batch, const float* d_begin
   if (int rc = select_device(h)) return rc;
   MatchParams P;
   memset(&P, 0, sizeof P);
-  fill_schedule(h, P);
+  fill_schedule(h, P, true);
   P.batch = batch;
   P.begin_world = d_begin_world;
   P.pts = reinterpret_cast<const float2*>(d_pts_xy);
@@ -2884,6 +2890,16 @@ int hsm_debug_set_coop_mute(hsm_ctx* h, int block_plus_one) {
   if (!h) return fail(HSM_ERR_INVALID, "null context");
   std::lock_guard<std::mutex> lk(h->mu);
   h->coop_mute_block = block_plus_one;
+  return HSM_OK;
+}
+
+int hsm_debug_set_schedule(hsm_ctx* h, int level, int gn_steps) {
+  if (!h) return fail(HSM_ERR_INVALID, "null context");
+  if (level >= (int)h->levels.size() || (level >= 0 && gn_steps < 1))
+    return fail(HSM_ERR_INVALID, "hsm_debug_set_schedule: level out of range or gn_steps < 1");
+  std::lock_guard<std::mutex> lk(h->mu);
+  h->sched_level = level < 0 ? -1 : level;
+  h->sched_steps = level < 0 ? 0 : gn_steps;
   return HSM_OK;
 }
 

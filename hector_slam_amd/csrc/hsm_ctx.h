@@ -186,6 +186,8 @@ struct hsm_ctx {
   bool relaxed = false;   // HSM_PARITY_RELAXED: contracted multiply-adds in the throughput kernel (gn_match_cached_kernel<.., RELAXED>)
   int last_cfg[6] = {0, 0, 0, 0, 0, 0};
   int coop_mute_block = 0;      // hsm_debug_set_coop_mute (test hook)
+  int sched_level = -1;         // hsm_debug_set_schedule (test hook): batched entries run `sched_level` only, -1 = the full schedule
+  int sched_steps = 0;          //   ... with this many GN steps
   bool exact_spec = false;       // env HSM_EXACT_SPEC=1: one-workgroup-per-scan launches in exact order take the speculative-carry form (gn_match_spec.h:
                                  // the same bits; measured SLOWER than the literal chains on one CU -- DESIGN.md 8 -- hence opt-in)
   bool exact_spec1 = false;      // env HSM_EXACT_SPEC1=1: ONE scan of up to 2048 beams (hsm_match) in exact order takes the on-chip speculative-carry form

@@ -464,6 +464,9 @@ int hsm_debug_spec_stats(hsm_ctx* h, int enable, unsigned long long out[4]);
  * one-workgroup matcher; hsm_debug_coop_fallbacks() counts how often it had to. */
 int hsm_debug_set_coop_mute(hsm_ctx* h, int block_plus_one);
 int hsm_debug_coop_fallbacks(hsm_ctx* h);
+/* test hook: batched entries (hsm_match_batch, hsm_match_batch_device and the ranges entries) restrict matchData to `level`
+ * with `gn_steps` steps (1 + maxIterations); level < 0 restores the schedule.  Single-scan entries are not affected. */
+int hsm_debug_set_schedule(hsm_ctx* h, int level, int gn_steps);
 /* device sincosf of n angles (glibc's algorithm, csrc/libm_exact.h) -- numerics test hook */
 int hsm_debug_sincos(hsm_ctx* h, int n, const float* x, float* s, float* c);
 /* device expf(x) and getGridProbability(x) = e/(e+1) of n values -- numerics test hook */

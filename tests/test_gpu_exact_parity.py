@@ -576,3 +576,63 @@ def test_likelihood_residual_and_sigma_point_covariance_bit_identical(capi, orac
             om, ow, ol = o.covariance_for_poses(lvl, poses, pts * f)
             assert same(lh, ol), (lvl, q)
             assert same(cm, om) and same(cw, ow), (lvl, q)
+
+
+@pytest.mark.parametrize("form", ["cached", "split-tail", "dense", "spec"])
+def test_schedule_hook_batches_are_bit_identical(capi, oracle_mod, pyramid_scene, kind, form, monkeypatch):
+    """hsm_debug_set_schedule on the reference-order batch forms: one level, gn_steps = 1, 2 and 5, every scan's pose and
+    covariance bit-identical to oracle.match_level(level, ..., gn_steps - 1) -- the hook leaves the default path alone, and
+    the exact batch kernels run schedules the full matchData never gives them.  Forms: gn_match_exact_cached_kernel (its
+    four-per-CU generations and its chain-wavefront form; the split-tail launch of 4097 scans) and the dense forms
+    gn_match_exact_dense_kernel / gn_match_spec_kernel (HSM_EXACT_DENSE_MIN lowered, HSM_EXACT_SPEC=1)"""
+    from hector_slam_amd import synth
+    sc = pyramid_scene
+    o = make_oracle(oracle_mod, kind, sc)
+    if form in ("dense", "spec"):
+        monkeypatch.setenv("HSM_EXACT_DENSE_MIN", "1920")
+    if form == "spec":
+        monkeypatch.setenv("HSM_EXACT_SPEC", "1")
+    g = exact_gpu(capi, sc, o)
+    rng = np.random.default_rng(91)
+    nq = len(sc.query_scans)
+    s = float(np.float32(1.0) / np.float32(sc.resolution))
+    if form == "cached":
+        batches = [[int(n) for n in rng.integers(300, 1081, 37)] + [0, 1, 64, 65], [700] * 4096]
+    elif form == "split-tail":
+        batches = [[int(n) for n in rng.integers(400, 1081, 4097)]]
+    else:
+        batches = [[2000, 2500, 1920]]
+    kernels = set()
+    for sizes in batches:
+        scans, init = [], []
+        for j, n in enumerate(sizes):
+            if form in ("dense", "spec"):
+                pts = synth.make_scan(sc.world, sc.query_truth[j % nq], n, s, rng, pad_to_full=True)
+            else:
+                full = sc.query_scans[j % nq]
+                n = min(n, full.shape[0])
+                pts = full[np.sort(rng.choice(full.shape[0], n, replace=False))] if n else np.zeros((0, 2), np.float32)
+            scans.append(np.ascontiguousarray(pts, np.float32))
+            init.append(sc.query_init[j % nq] + (rng.uniform(-0.05, 0.05, 3) * [1, 1, 0.2]).astype(np.float32))
+        init = np.asarray(init, np.float32)
+        pts, offs = synth.pack_scans(scans)
+        for lvl, steps in ((0, 1), (1, 2), (0, 5)) if len(sizes) < 1000 else ((0, 1), (2, 5)):
+            g.debug_set_schedule(lvl, steps)
+            pg, cg = g.match_batch(init, pts, offs)
+            cfg = g.last_launch_config()
+            kernels.add(cfg["kernel"])
+            assert cfg["parity_effective"] == "exact", cfg
+            f = np.float32(1.0 / 2 ** lvl)
+            for j in range(len(scans)):
+                po, co = o.match_level(lvl, init[j], scans[j] * f, steps - 1)
+                assert same(pg[j], po) and (scans[j].shape[0] == 0 or same(cg[j], co)), (form, lvl, steps, j, pg[j], po)
+    g.debug_set_schedule(-1)
+    k = min(8, len(scans))
+    pf, _ = g.match_batch(init[:k], *synth.pack_scans(scans[:k]))  # the hook released: the full schedule again
+    for j in range(k):
+        assert same(pf[j], o.match(init[j], scans[j])[0]), j
+    want = {"cached": {"gn_match_exact_cached_kernel", "gn_match_exact_cached_kernel (chain wavefront)"},
+            "split-tail": {"gn_match_exact_cached_kernel + its chain-wavefront form for the last, part-filled generation"},
+            "dense": {"gn_match_exact_dense_kernel"}, "spec": {"gn_match_spec_kernel"}}[form]
+    assert kernels == want, kernels
+    g.close()

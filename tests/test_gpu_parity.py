@@ -1536,3 +1536,159 @@ def test_two_caller_streams_are_each_ordered_against_updates(capi, pyramid_scene
     for lvl in range(sc.levels):
         la, lb = ref.download_level(lvl), dut.download_level(lvl)
         assert np.array_equal(bits(la[0]), bits(lb[0])) and np.array_equal(la[1], lb[1])
+
+
+# ---------------------------------------------------------------- one GN evaluation of every fast form against float64
+# H and dTr of ONE evaluation against the float64 sums of the reference's per-beam terms (tests/gn_f64.py), within the
+# rounding bound of each form's addition depth d.  The pose bars above cannot see a lost or doubled beam (one beam of a
+# 1081-beam scan moves the reference's own pose by ~1e-5 m); these can: every scan is built so that dropping any one
+# non-zero beam moves an entry beyond twice the bound (the margin printed per case, asserted on the CPU by
+# tests/test_gn_f64_reference.py).  Every case asserts the launch it took first, so a routing change cannot quietly
+# test another kernel.
+import gn_cases  # noqa: E402
+import gn_f64  # noqa: E402
+
+
+def _bpl_rule(n, wps):
+    """launch_match_w: the beams-per-lane instantiation a launch of scans of up to n beams takes"""
+    per_lane = -(-n // (64 * wps))
+    if per_lane > 17:
+        return 0
+    for b in ((2,) if wps == 1 else ()) + (3, 5, 9):
+        if per_lane <= b:
+            return b
+    return 17
+
+
+def _expect_cfg(cfg, want, what):
+    got = {k: cfg[k] for k in want}
+    assert got == want, f"{what}: launch {cfg} is not the form under test {want}"
+
+
+def _check_eval(Hg, ev, d, what, start_map=None, end_map=None):
+    """H entry by entry (bitwise symmetric); dTr through the step where H is regular.  Returns (H fraction, stepped)"""
+    frac = gn_f64.check_H(Hg, ev, d, what)
+    stepped = False
+    if end_map is not None and int(ev.nonzero().sum()) >= 3 and Hg[0, 0] != 0 and Hg[1, 1] != 0:
+        stepped = gn_f64.check_step(Hg, start_map, end_map, ev, d, what)
+    return frac, stepped
+
+
+@pytest.mark.parametrize("case", gn_cases.BATCH_CASES, ids=[c["id"] for c in gn_cases.BATCH_CASES])
+def test_fast_batch_form_one_step_against_float64(capi, case, monkeypatch):
+    """batched forms of launch_match_t / launch_match_w / launch_match_by_width, one GN step on one level through
+    hsm_debug_set_schedule: cov = H at the start pose, pose = start + clamp(H^-1 dTr)"""
+    from hector_slam_amd import synth
+    for k, v in case.get("env", {}).items():
+        monkeypatch.setenv(k, v)
+    if case.get("order"):
+        monkeypatch.setenv("HSM_BATCH_ORDER_MIN", "1")
+    w, init, scans, evs = gn_cases.batch_inputs(case)
+    lay = capi.LAYOUT_QUAD if case["layout"] == "quad" else capi.LAYOUT_PLANE
+    g = w.gpu(capi, layout=lay, waves_per_scan=case["wps"])
+    relaxed = case.get("parity") == "relaxed"
+    if relaxed:
+        g.set_parity(capi.PARITY_RELAXED)
+    if case.get("order") == "morton":
+        g.set_batch_order(capi.ORDER_MORTON)
+    lvl = case["level"]
+    g.debug_set_schedule(lvl, 1)
+    up = np.float32(2.0 ** lvl)  # the batch carries level-0 endpoints; the kernel scales them by 2^-level (exact)
+    if case.get("shared"):
+        pose, cov = g.match_batch(init, scans[0] * up)
+    else:
+        pts, offs = synth.pack_scans([s * up for s in scans])
+        pose, cov = g.match_batch(init, pts, offs)
+    cfg = g.last_launch_config()
+    _expect_cfg(cfg, case["expect"], case["id"])
+    if case.get("order"):
+        assert g.last_launch_sorted(), "the batch was meant to run through a permutation"
+    worst, stepped, margin, failures = 0.0, 0, np.inf, []
+    for j, pts_j in enumerate(scans):
+        n = pts_j.shape[0]
+        if n == 0:
+            assert np.array_equal(bits(pose[j]), bits(init[j])), j
+            continue
+        ev = evs[j][0]
+        d = gn_cases.batch_depth(case, n)
+        margin = min(margin, gn_f64.min_margin(ev, d))
+        start = w.o.map_coords_pose(lvl, init[j])
+        end = g.getMapCoordsPose(lvl, pose[j])
+        try:
+            f, s = _check_eval(cov[j].reshape(3, 3).T, ev, d, f"{case['id']} scan {j} (n={n}, d={d})", start, end)
+        except AssertionError as e:
+            failures.append(str(e))
+            continue
+        worst, stepped = max(worst, f), stepped + s
+    g.debug_set_schedule(-1)
+    g.close()
+    assert not failures, f"{len(failures)} of {len(scans)} scans:\n" + "\n".join(failures)
+    assert stepped >= len(scans) // 2, stepped
+    print(f"{case['id']}: {cfg['kernel']} W={cfg['waves_per_scan']} block={cfg['block']} bpl={cfg['beams_per_lane']}: "
+          f"worst |H - H64| = {worst:.3f} of the bound, single-beam margin {margin:.2f}, {stepped} steps checked")
+
+
+@pytest.mark.parametrize("W,n", gn_cases.SINGLE_CASES)
+def test_fast_single_scan_teams_one_step_against_float64(capi, W, n):
+    """match_level(max_iter = 0) on gn_match_kernel<W, SPB, L, BPL>: W = 1 .. 16, n = 64 W k +- 1 and n < 64"""
+    w, p0, pts, ev = gn_cases.single_inputs(W, n)
+    g = w.gpu(capi, waves_per_scan=W)
+    pose, cov = g.match_level(0, p0, pts, 0)
+    _expect_cfg(g.last_launch_config(), dict(kernel="gn_match_kernel", waves_per_scan=W, block=64 * W * (4 if W == 1 else 1),
+                                             beams_per_lane=_bpl_rule(n, W), texel_cache=False), f"W={W} n={n}")
+    d = gn_f64.depth_team(n, W)
+    f, s = _check_eval(cov.reshape(3, 3).T, ev, d, f"W={W} n={n} d={d}", w.o.map_coords_pose(0, p0), g.getMapCoordsPose(0, pose))
+    g.close()
+    print(f"team W={W} n={n} d={d}: {f:.3f} of the bound, margin {gn_f64.min_margin(ev, d):.2f}, step checked {s}")
+
+
+@pytest.mark.parametrize("tagged", ["1", "0"])
+@pytest.mark.parametrize("n", gn_cases.COOP_SIZES)
+def test_fast_coop_matcher_one_step_against_float64(capi, n, tagged, monkeypatch):
+    """gn_match_coop_kernel (single scans >= 4096 beams): K = 16, 64 workgroups, several beams per lane at 20000; the
+    tagged exchange and the counter barrier (HSM_COOP_TAGGED=0)"""
+    monkeypatch.setenv("HSM_COOP_TAGGED", tagged)
+    w, p0, pts, ev = gn_cases.coop_inputs(n)
+    g = w.gpu(capi)
+    pose, cov = g.match_level(0, p0, pts, 0)
+    K = gn_f64.coop_workgroups(n)
+    cfg = g.last_launch_config()
+    assert cfg["kernel"] == "gn_match_coop_kernel" and cfg["waves_per_scan"] < 0 and cfg["grid"] == K and cfg["block"] == 256, cfg
+    d = gn_f64.depth_coop(n, K)
+    f, s = _check_eval(cov.reshape(3, 3).T, ev, d, f"coop n={n} K={K} d={d}", w.o.map_coords_pose(0, p0), g.getMapCoordsPose(0, pose))
+    assert g.debug_coop_fallbacks() == 0
+    g.close()
+    print(f"coop n={n} K={K} d={d} tagged={tagged}: {f:.3f} of the bound, margin {gn_f64.min_margin(ev, d):.2f}, step checked {s}")
+
+
+def test_fast_trace_every_step_against_float64(capi):
+    """hsm_match_trace on a one-level map: every step's H against the float64 H at the estimate the trace reports for the
+    step before (the start pose for the first)"""
+    w, p0, pts, ev0 = gn_cases.trace_inputs()
+    g = w.gpu(capi)
+    pose, cov, trace = g.match_trace(p0, pts)
+    cfg = g.last_launch_config()
+    W = cfg["waves_per_scan"]
+    _expect_cfg(cfg, dict(kernel="gn_match_kernel", block=64 * W * (4 if W == 1 else 1), beams_per_lane=_bpl_rule(pts.shape[0], W),
+                          texel_cache=False), "trace")
+    assert trace.shape[0] == 6 and np.array_equal(bits(trace[-1, 3:]), bits(cov))
+    d = gn_f64.depth_team(pts.shape[0], W)
+    est = w.o.map_coords_pose(0, p0)
+    for k in range(trace.shape[0]):
+        ev = ev0 if k == 0 else gn_f64.Eval64(w.o, 0, est, pts, w.kind)
+        gn_f64.check_H(trace[k, 3:].reshape(3, 3).T, ev, d, f"trace step {k}")
+        est = trace[k, :3].copy()
+    g.close()
+
+
+@pytest.mark.parametrize("n,lvl", gn_cases.EVAL_CASES)
+def test_fast_eval_kernel_against_float64(capi, n, lvl):
+    """hsm_hessian_derivs in the fast mode (gn_eval_kernel: 1024 lanes, wave tree, 16 wave partials in order)"""
+    w, p0, pts, ev = gn_cases.eval_inputs(n, lvl)
+    g = w.gpu(capi)
+    pm = w.o.map_coords_pose(lvl, p0)
+    H, dtr = g.hessian_derivs(lvl, pm, pts)
+    d = gn_f64.depth_eval(n)
+    gn_f64.check_H(H, ev, d, f"eval n={n} L{lvl}")
+    gn_f64.check_dtr(dtr, ev, d, f"eval n={n} L{lvl}")
+    g.close()
