@@ -130,6 +130,7 @@ SIGNATURES = {
     "hsm_debug_set_coop_mute": (_i, [_vp, _i]),
     "hsm_debug_coop_fallbacks": (_i, [_vp]),
     "hsm_debug_set_schedule": (_i, [_vp, _i, _i]),
+    "hsm_debug_batch_order": (_i, [_vp, _i, _vp, _vp, _vp]),
     "hsm_debug_spec_stats": (_i, [_vp, _i, _vp]),
     "hsm_debug_marks_nonzero": (_i, [_vp, _i, _vp]),
     "hsm_debug_sincos": (_i, [_vp, _i, _f32p, _f32p, _f32p]),
@@ -645,6 +646,10 @@ class MapRepMultiMap:
     def debug_set_schedule(self, level, gn_steps=1):
         """batched entries run `level` only, with `gn_steps` GN steps (1 + maxIterations); level < 0 restores the schedule"""
         _check(self._lib.hsm_debug_set_schedule(self._h, int(level), int(gn_steps)), "hsm_debug_set_schedule")
+
+    def debug_batch_order(self, batch, d_begin, d_perm_out, stream=0):
+        """the batch-order sort alone, raw device pointers (ints), asynchronous on ``stream``: d_perm_out[slot] = scan"""
+        _check(self._lib.hsm_debug_batch_order(self._h, int(batch), d_begin, d_perm_out, stream or None), "hsm_debug_batch_order")
 
     def match_trace(self, begin_world, pts, origo=_ZERO2):
         """matchData with the hook trace: (pose, cov, trace [steps, 12]) -- per GN step the map-frame estimate after the

@@ -290,18 +290,30 @@ int launch_match_exact_dense(hsm_ctx* h, const MatchParams& P0, int max_n, hipSt
   // from it).  The shift rule accepts ~97 % of the segments of real chains, but on ONE CU the form is bound by what it moves
   // (16 k texel lines + 1.2 MB of products per GN step through one L1) and by a lone workgroup's ~2 us per dependent load: 2.8 ms
   // per 16 k-beam match against 0.9 for the literal chain below (profiles/r06/README.md).
-  if (h->exact_spec && P.n_bound > 0 && max_n <= P.n_bound) {
+  // The product scratch is the launching stream's own (two streams' launches would write the same rows at once).  A launch into a
+  // graph capture takes the literal form below, which needs no scratch: a graph never reads a block that an eager launch grows
+  // (frees), and nothing is allocated or synchronised while the caller captures.  So does a ninth stream.
+  hsm_ctx::SpecScratch* sb = nullptr;
+  if (h->exact_spec && P.n_bound > 0 && max_n <= P.n_bound && !stream_capturing(stream)) {
+    for (hsm_ctx::SpecScratch& b : h->spec_scratch)
+      if (b.s == stream) sb = &b;
+    if (!sb && h->spec_scratch.size() < 8) {
+      h->spec_scratch.push_back({stream, nullptr, 0});
+      sb = &h->spec_scratch.back();
+    }
+  }
+  if (sb) {
     const size_t stride = spec_scratch_float4s_bound(P.n_bound);  // enough for every n <= n_bound
     const size_t need = stride * (size_t)P.batch;
-    if (need > h->spec_scratch_cap) {
-      HIP_TRY(hipStreamSynchronize(stream));  // (a launch in flight may still read the old block)
-      if (h->d_spec_scratch) HIP_TRY(hipFree(h->d_spec_scratch));
-      h->d_spec_scratch = nullptr;
-      h->spec_scratch_cap = 0;
-      HIP_TRY(hipMalloc((void**)&h->d_spec_scratch, need * sizeof(float4)));
-      h->spec_scratch_cap = need;
+    if (need > sb->cap) {
+      HIP_TRY(hipStreamSynchronize(stream));  // (a launch of this stream in flight may still read the old block)
+      if (sb->d) HIP_TRY(hipFree(sb->d));
+      sb->d = nullptr;
+      sb->cap = 0;
+      HIP_TRY(hipMalloc((void**)&sb->d, need * sizeof(float4)));
+      sb->cap = need;
     }
-    P.spec_scratch = h->d_spec_scratch;
+    P.spec_scratch = sb->d;
     P.spec_stride = (unsigned)stride;
     P.spec_stats = h->d_spec_stats;
     if (h->layout == kLayoutPlane)
@@ -692,6 +704,12 @@ int select_device(const hsm_ctx* h) {
 // every writer of the map queues behind a batch match that a caller-owned stream may still be running, and
 // bumps the epoch the next such match orders itself behind
 int order_after_foreign_match(hsm_ctx* h) {
+  // Refused, before anything is queued, while a caller's stream that this context has matched on is being captured into a graph:
+  // a marker recorded on that stream would go into the capture, and the context's stream, waiting for it, would join the capture.
+  for (const hsm_ctx::ForeignStream& f : h->foreign)
+    if (stream_capturing(f.s))
+      return fail(HSM_ERR_INVALID, "map update while a caller's stream that this context matches on is being captured into a graph: "
+                                   "end the capture first (the caller orders replays against updates)");
   for (hsm_ctx::ForeignStream& f : h->foreign) {
     if (!f.pending) continue;
     // everything the caller has queued on that stream up to now (a superset of our matches); the wait captures
@@ -892,7 +910,7 @@ void hsm_destroy(hsm_ctx* h) {
   if (h->copy_stream) TEARDOWN(log, hipStreamSynchronize(h->copy_stream));
   for (Level& L : h->levels) free_level(L, log);
   TEARDOWN(log, hipFree(h->d_scan));
-  TEARDOWN(log, hipFree(h->d_spec_scratch));
+  for (hsm_ctx::SpecScratch& b : h->spec_scratch) TEARDOWN(log, hipFree(b.d));
   for (hsm_ctx::PermBuf& b : h->perm_bufs) TEARDOWN(log, hipFree(b.d));
   TEARDOWN(log, hipFree(h->d_spec_stats));
   TEARDOWN(log, hipFree(h->d_beam_recs));
@@ -1066,6 +1084,19 @@ static int match_batch_device_nolock(hsm_ctx* h, int batch, const float* d_begin
   if (!fs) {
     h->foreign.push_back({s, 0ull, false});
     fs = &h->foreign.back();
+  }
+  if (stream_capturing(s)) {
+    // A launch into a graph capture runs at the caller's replays, not now: it neither records that the stream is ordered behind
+    // the updates nor leaves a marker for the next update (either would describe work only the graph holds).  The updates queued
+    // so far are waited for on the host instead -- a wait node on an event recorded outside the capture would order the graph
+    // but not the stream's later eager launches.  Later updates and the replays are ordered by the caller; while the capture
+    // lasts, updates are refused (order_after_foreign_match).
+    hipStreamCaptureMode mode = hipStreamCaptureModeRelaxed;
+    HIP_TRY(hipThreadExchangeStreamCaptureMode(&mode));
+    const hipError_t e = hipStreamSynchronize(h->stream);
+    (void)hipThreadExchangeStreamCaptureMode(&mode);
+    if (e != hipSuccess) return fail(HSM_ERR_HIP, "hsm_match_batch_device: waiting for the queued map updates at capture", e);
+    return launch_match(h, P, hint, s);
   }
 #if !defined(HSM_EXP_NO_XSTREAM_ORDER)  // (negative control of test_queued_updates_are_ordered_against_caller_streams)
   if (fs->ordered_epoch != h->upd_epoch) {  // THIS stream has not been ordered behind the latest map writes yet
@@ -2901,6 +2932,14 @@ int hsm_debug_set_schedule(hsm_ctx* h, int level, int gn_steps) {
   h->sched_level = level < 0 ? -1 : level;
   h->sched_steps = level < 0 ? 0 : gn_steps;
   return HSM_OK;
+}
+
+int hsm_debug_batch_order(hsm_ctx* h, int batch, const float* d_begin_world, int* d_perm_out, void* stream) {
+  if (!h) return fail(HSM_ERR_INVALID, "null context");
+  if (batch < 1 || !d_begin_world || !d_perm_out) return fail(HSM_ERR_INVALID, "hsm_debug_batch_order: bad argument");
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (int rc = select_device(h)) return rc;
+  return hsm_host::launch_batch_order(h, d_begin_world, batch, d_perm_out, h->batch_order == HSM_ORDER_AUTO, (hipStream_t)stream);
 }
 
 int hsm_debug_spec_stats(hsm_ctx* h, int enable, unsigned long long out[4]) {

@@ -66,6 +66,19 @@ struct Level {
 };
 
 
+
+// true while the caller captures `s` into a graph (the null stream never is): what is launched then runs at the caller's replays,
+// so it may neither read nor change per-stream state that eager launches rewrite or free
+inline bool stream_capturing(hipStream_t s) {
+  if (s == nullptr) return false;
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(s, &cs) != hipSuccess) {
+    (void)hipGetLastError();  // (a stream the caller destroyed: not capturing)
+    return false;
+  }
+  return cs != hipStreamCaptureStatusNone;
+}
+
 }  // namespace hsm_host
 
 using hsm_host::Level;
@@ -207,8 +220,14 @@ struct hsm_ctx {
   };
   std::vector<PermBuf> perm_bufs;
   bool last_sorted = false;
-  float* d_spec_scratch = nullptr;   // gn_match_spec_kernel: products of every beam, [batch][stride] float4s
-  size_t spec_scratch_cap = 0;       // float4s
+  // gn_match_spec_kernel: products of every beam, [batch][stride] float4s -- one block per stream that has launched the form
+  // (launches on one stream are ordered; a ninth stream, and any launch into a graph capture, take the literal dense form)
+  struct SpecScratch {
+    hipStream_t s;
+    float* d;
+    size_t cap;  // float4s
+  };
+  std::vector<SpecScratch> spec_scratch;
   SpecStats* d_spec_stats = nullptr; // hsm_debug_spec_stats
   bool exact_dense = true;       // env HSM_EXACT_DENSE=0: dense scans in exact order keep the 16-wavefront team form (gn_match_kernel<16,...,EXACT>)
   int exact_dense_min = 4096;
@@ -233,7 +252,11 @@ int launch_match_exact_cached_forms(hsm_ctx* h, const hsm::MatchParams& P, int m
 // match_teams.hip: `wps` wavefronts per scan (1, 2, 4, 8, 16), either summation order; the one-wavefront exact form goes on to
 // launch_match_exact_cached_forms where that applies
 // MatchParams::perm for this launch where hsm_set_batch_order asks for it (a sort kernel on `stream` in front of the matcher)
+// (a launch into a graph capture keeps the caller's order: no graph ever reads a stream's permutation buffer)
 int ensure_batch_perm(hsm_ctx* h, hsm::MatchParams& P, hipStream_t stream);
+// batch_order_kernel on `stream`: perm[slot] = scan for `batch` start poses, with level 0's transform (hsm_debug_batch_order too)
+int launch_batch_order(hsm_ctx* h, const float* begin_world, int batch, int* perm, bool detect, hipStream_t stream);
 int launch_match_by_width(hsm_ctx* h, const hsm::MatchParams& P, int max_n, hipStream_t stream, bool exact, int wps);
+
 
 }  // namespace hsm_host

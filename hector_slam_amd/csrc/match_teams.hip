@@ -128,10 +128,25 @@ namespace hsm_host {
 
 #define HIP_TRY HSM_HIP_TRY
 
+int launch_batch_order(hsm_ctx* h, const float* begin_world, int batch, int* perm, bool detect, hipStream_t stream) {
+  // 64 tiles span the longer edge of level 0
+  const Level& L0 = h->levels[0];
+  int shift = 0;
+  while ((64 << shift) < (L0.sx > L0.sy ? L0.sx : L0.sy)) ++shift;
+  hipLaunchKernelGGL(batch_order_kernel, dim3(1), dim3(1024), 0, stream, L0.mapTworld, shift, begin_world, batch, perm, detect ? 1 : 0);
+  HIP_TRY(hipGetLastError());
+  return HSM_OK;
+}
+
 int ensure_batch_perm(hsm_ctx* h, MatchParams& P, hipStream_t stream) {
   if (P.perm != nullptr || P.begin_world == nullptr || P.batch < h->batch_order_min) return HSM_OK;
   const bool automatic = h->batch_order == HSM_ORDER_AUTO;
   if (h->batch_order != HSM_ORDER_MORTON && !(automatic && h->levels[0].cells() > ((size_t)1 << 23))) return HSM_OK;
+  // A launch into a graph capture keeps the caller's order and leaves the stream's permutation as it is.  Its sort would run at
+  // the replays only, while the host state below would claim it had run now (an eager launch of that size would then reuse a
+  // buffer that holds another batch's permutation); and a graph that read the buffer would read it after an eager launch had
+  // rewritten it or, growing it, freed it.
+  if (stream_capturing(stream)) return HSM_OK;
   hsm_ctx::PermBuf* pb = nullptr;
   for (hsm_ctx::PermBuf& b : h->perm_bufs)
     if (b.s == stream) pb = &b;
@@ -141,9 +156,6 @@ int ensure_batch_perm(hsm_ctx* h, MatchParams& P, hipStream_t stream) {
     pb = &h->perm_bufs.back();
   }
   if (pb->cap < (size_t)P.batch) {
-    // (no allocation while the caller captures this stream into a graph: such a launch keeps the caller's order)
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (stream != nullptr && hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return HSM_OK;
     if (pb->d) HIP_TRY(hipFree(pb->d));  // (hipFree waits for the device: no launch still reads it)
     pb->d = nullptr, pb->cap = 0, pb->batch = 0;
     const size_t cap = ((size_t)P.batch + 4095) / 4096 * 4096;
@@ -156,12 +168,7 @@ int ensure_batch_perm(hsm_ctx* h, MatchParams& P, hipStream_t stream) {
     h->last_sorted = true;
     return HSM_OK;
   }
-  // 64 tiles span the longer edge of level 0
-  const Level& L0 = h->levels[0];
-  int shift = 0;
-  while ((64 << shift) < (L0.sx > L0.sy ? L0.sx : L0.sy)) ++shift;
-  hipLaunchKernelGGL(batch_order_kernel, dim3(1), dim3(1024), 0, stream, P.lv[0].mapTworld, shift, P.begin_world, P.batch, pb->d, automatic ? 1 : 0);
-  HIP_TRY(hipGetLastError());
+  if (int rc = launch_batch_order(h, P.begin_world, P.batch, pb->d, automatic, stream)) return rc;
   pb->batch = P.batch, pb->used = 1;
   P.perm = pb->d;
   h->last_sorted = true;

@@ -163,6 +163,14 @@ int hsm_match_trace(hsm_ctx* h, const float begin_world[3], const float* pts_xy,
  * `stream` is a hipStream_t (NULL = default stream); the call is asynchronous.  The library orders it behind
  * every map update queued on the context so far, and the next map update behind it (events; no host wait),
  * per caller stream: matches may be in flight on several caller-owned streams at once.
+ * Graph capture (hipStreamBeginCapture on `stream`, e.g. torch.cuda.graph): the call records kernel launches
+ * only, and allocates nothing.  At capture time the host waits for the map updates queued so far, so every replay
+ * sees them.  A captured launch orders nothing else: the caller orders each replay against later updates
+ * (hsm_synchronize before replaying, or their own events).  While a stream that this context has matched on is
+ * being captured, every map update (hsm_update_by_scan and its kin, hsm_upload_level, hsm_reset) fails with
+ * HSM_ERR_INVALID and queues nothing.  Captured launches keep the caller's batch order and take the literal
+ * reference-order form where HSM_EXACT_SPEC=1 would speculate: no graph reads per-stream buffers that
+ * eager launches rewrite or free.  Results are the same bits.
  * Does not touch the retained-scan state. */
 int hsm_match_batch_device(hsm_ctx* h, int batch, const float* d_begin_world,
                            const float* d_pts_xy, const int* d_scan_offsets, int shared_n,
@@ -467,6 +475,10 @@ int hsm_debug_coop_fallbacks(hsm_ctx* h);
 /* test hook: batched entries (hsm_match_batch, hsm_match_batch_device and the ranges entries) restrict matchData to `level`
  * with `gn_steps` steps (1 + maxIterations); level < 0 restores the schedule.  Single-scan entries are not affected. */
 int hsm_debug_set_schedule(hsm_ctx* h, int level, int gn_steps);
+/* test hook: the sort that hsm_set_batch_order puts in front of a batch, alone: d_perm_out[slot] = scan for `batch` start poses
+ * (DEVICE pointers, asynchronous on `stream`), by the 64 x 64 level-0 tile of each start pose in Morton order; with
+ * HSM_ORDER_AUTO its map-order detection may return the identity.  Runs whatever the map size and batch size; no other effect. */
+int hsm_debug_batch_order(hsm_ctx* h, int batch, const float* d_begin_world, int* d_perm_out, void* stream);
 /* device sincosf of n angles (glibc's algorithm, csrc/libm_exact.h) -- numerics test hook */
 int hsm_debug_sincos(hsm_ctx* h, int n, const float* x, float* s, float* c);
 /* device expf(x) and getGridProbability(x) = e/(e+1) of n values -- numerics test hook */

@@ -336,8 +336,8 @@ def test_batch_order_environment_word(capi, monkeypatch):
 
 def test_batched_matches_can_be_captured_in_a_hip_graph(capi, oracle_mod):
     """hsm_match_batch_device on a caller's stream is kernel launches only: a loop of batched matches can be captured into a hipGraph
-    (torch.cuda.CUDAGraph on ROCm) and replayed -- same poses bit for bit, in the default mode and in Morton order (whose sort kernel
-    and permutation buffer belong to the stream: allocated by the warm-up launch, not during the capture)"""
+    (torch.cuda.CUDAGraph on ROCm) and replayed -- same poses bit for bit, in the default mode and with Morton order set (a captured
+    launch keeps the caller's order: no graph reads the stream's permutation buffer, which eager launches rewrite or free)"""
     import torch
     from hector_slam_amd import synth
     sc = synth.make_scene(n_beams=1081, map_size=1024, levels=3, resolution=0.05, n_build=60, n_query=4096, room=(40.0, 30.0), seed=21)
