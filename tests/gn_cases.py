@@ -20,11 +20,13 @@ RES = 0.05
 class World:
     """a random multi-level map in the CPU oracle; gpu() makes a context holding the same levels"""
 
-    def __init__(self, kind: str, size: int, levels: int, seed: int):
+    def __init__(self, kind: str, size: int, levels: int, seed: int, size_y: int | None = None):
+        """size_y: the map's height where it differs from its width (None: a square map, the random numbers of before)"""
         from oracle import pyoracle
         pyoracle.build()
         self.kind, self.size, self.levels = kind, size, levels
-        self.o = pyoracle.Oracle(kind, RES, size, size, levels)
+        self.size_y = size if size_y is None else size_y
+        self.o = pyoracle.Oracle(kind, RES, size, self.size_y, levels)
         rng = np.random.default_rng(seed)
         self.lv = []
         for lvl in range(levels):
@@ -45,7 +47,7 @@ class World:
 
     def gpu(self, capi, **kw):
         kw.setdefault("parity", capi.PARITY_FAST)
-        g = capi.MapRepMultiMap(RES, self.size, self.size, self.levels, **kw)
+        g = capi.MapRepMultiMap(RES, self.size, self.size_y, self.levels, **kw)
         for lvl in range(self.levels):
             g.upload_level(lvl, *self.lv[lvl])
         return g
@@ -175,6 +177,24 @@ for W in (2, 4, 8, 16):
         BATCH_CASES.append(dict(id=f"team{W}x{bpl}", world="pyr", level=0 if W <= 4 else 1, wps=W, layout="quad" if W != 4 else "plane",
                                 sizes=[n, n - 2 * T if bpl else n - T] + ([n - 1] if W <= 4 else []), expect=_plain(W, bpl, 1)))
 
+# rectangular maps: the texel-cache forms on a wide and a tall pyramid (an axis swap reads the wrong texels on one of the two),
+# and the large-map forms on a map whose width alone sets the batch sort's tile shift
+for wname in ("wide", "tall"):
+    for lvl in (0, 2):
+        for lay in ("quad", "plane"):
+            BATCH_CASES += [
+                dict(id=f"cached4x17-{lay}-L{lvl}-{wname}", world=wname, level=lvl, wps=1, layout=lay,
+                     sizes=[1000, 700, 577, 1088, 901] * 2 + [1088, 640, 1001], expect=_cached(17)),
+                dict(id=f"cached4x9-{lay}-L{lvl}-{wname}", world=wname, level=lvl, wps=1, layout=lay,
+                     sizes=[500, 321, 576, 400] * 2 + [576, 333, 449], expect=_cached(9)),
+            ]
+BATCH_CASES += [
+    dict(id="cached8x17-bigwide", world="bigwide", level=0, wps=1, layout="quad", sizes=[1000, 1088, 700] * 4 + [900] * 5,
+         expect=_cached(17, 8)),
+    dict(id="cached8x17-bigwide-auto", world="bigwide", level=0, wps=1, layout="quad", order="auto-interleaved", sizes=[1000] * 41,
+         expect=_cached(17, 8)),
+]
+
 
 def batch_depth(case, n):
     return gn_f64.depth_team(n, case["wps"])
@@ -195,6 +215,12 @@ def world(name: str, kind: str = "ho") -> World:
             _WORLDS[key] = World(kind, 512, 3, seed=2024)
         elif name == "flat1":
             _WORLDS[key] = World(kind, 384, 1, seed=77)
+        elif name == "wide":  # rectangles: 640 x 192 / 320 x 96 / 160 x 48, and the transpose
+            _WORLDS[key] = World(kind, 640, 3, seed=640, size_y=192)
+        elif name == "tall":
+            _WORLDS[key] = World(kind, 192, 3, seed=192, size_y=640)
+        elif name == "bigwide":  # 8192 x 1040 > 2^23 cells: the large-map forms, a batch-sort tile shift set by the width alone
+            _WORLDS[key] = World(kind, 8192, 1, seed=8192, size_y=1040)
         else:  # "big": 4096^2 level 0 = 2^24 cells (> 2^23: the large-map forms)
             _WORLDS[key] = World(kind, 4096, 1, seed=4096)
     return _WORLDS[key]
@@ -230,19 +256,23 @@ def batch_inputs(case, kind: str = "ho"):
     return w, np.asarray(init, np.float32), scans, evs
 
 
-def single_inputs(W: int, n: int, kind: str = "ho"):
+def _world_seed(name):
+    return [] if name == "pyr" else [ord(ch) for ch in name]
+
+
+def single_inputs(W: int, n: int, kind: str = "ho", world_name: str = "pyr"):
     """one scan for match_level(0, ..., max_iter = 0) on W waves: (world, init world pose, level-0 scan, Eval64)"""
-    w = world("pyr", kind)
-    rng = np.random.default_rng([W, n, 1])
+    w = world(world_name, kind)
+    rng = np.random.default_rng([W, n, 1] + _world_seed(world_name))
     p0 = w.start_pose(0, rng, theta=0.0 if n % 2 else float(rng.uniform(-2.5, 2.5)))
     pts, evs = make_scan(w, 0, p0, n, lambda m: gn_f64.depth_team(m, W), rng)
     return w, p0, pts, evs[0]
 
 
-def coop_inputs(n: int, kind: str = "ho"):
+def coop_inputs(n: int, kind: str = "ho", world_name: str = "pyr"):
     """one dense scan for the cooperative matcher (match_level on level 0)"""
-    w = world("pyr", kind)
-    rng = np.random.default_rng([n, 2])
+    w = world(world_name, kind)
+    rng = np.random.default_rng([n, 2] + _world_seed(world_name))
     p0 = w.start_pose(0, rng, theta=float(rng.uniform(-2.5, 2.5)))
     pts, evs = make_scan(w, 0, p0, n, lambda m: gn_f64.depth_coop(m, gn_f64.coop_workgroups(m)), rng)
     return w, p0, pts, evs[0]
@@ -257,13 +287,20 @@ def trace_inputs(n: int = 1081, kind: str = "ho"):
     return w, p0, pts, evs[0]
 
 
-def eval_inputs(n: int, level: int, kind: str = "ho"):
+def eval_inputs(n: int, level: int, kind: str = "ho", world_name: str = "pyr"):
     """one scan for hsm_hessian_derivs (gn_eval_kernel)"""
-    w = world("pyr", kind)
-    rng = np.random.default_rng([n, level, 4])
+    w = world(world_name, kind)
+    rng = np.random.default_rng([n, level, 4] + _world_seed(world_name))
     p0 = w.start_pose(level, rng, theta=float(rng.uniform(-2.5, 2.5)))
     pts, evs = make_scan(w, level, p0, n, gn_f64.depth_eval, rng)
     return w, p0, pts, evs[0]
 
 
 EVAL_CASES = [(37, 0), (1081, 0), (1024, 1), (5000, 2)]
+
+# the single-scan forms on rectangles, each case naming its world: team widths (match_level, max_iter = 0), the cooperative
+# matcher, gn_eval_kernel on the coarsest level of the wide pyramid
+RECT_SINGLE_CASES = [("wide", 1, 1081), ("tall", 2, 64 * 2 * 3 + 1), ("wide", 4, 64 * 4 * 2 - 1), ("tall", 8, 1081),
+                     ("wide", 16, 64 * 16 * 3 + 1), ("tall", 16, 37)]
+RECT_COOP_CASES = [("tall", 16384)]
+RECT_EVAL_CASES = [("wide", 2000, 2)]

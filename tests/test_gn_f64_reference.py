@@ -89,6 +89,41 @@ def test_trace_and_eval_cases_see_every_beam():
         assert mm > 1.0, (n, lvl, mm)
 
 
+@pytest.mark.parametrize("world,W,n", gn_cases.RECT_SINGLE_CASES)
+def test_rect_single_scan_cases_see_every_beam(world, W, n):
+    w, _, pts, ev = gn_cases.single_inputs(W, n, world_name=world)
+    assert w.size != w.size_y
+    mm = gn_f64.min_margin(ev, gn_f64.depth_team(n, W))
+    assert pts.shape[0] == n and mm > 1.0, mm
+    print(f"team W={W} n={n} on {world}: margin {mm:.2f}")
+
+
+@pytest.mark.parametrize("world,n", gn_cases.RECT_COOP_CASES)
+def test_rect_coop_cases_see_every_beam(world, n):
+    _, _, pts, ev = gn_cases.coop_inputs(n, world_name=world)
+    mm = gn_f64.min_margin(ev, gn_f64.depth_coop(n, gn_f64.coop_workgroups(n)))
+    assert pts.shape[0] == n and mm > 1.0, mm
+
+
+@pytest.mark.parametrize("world,n,lvl", gn_cases.RECT_EVAL_CASES)
+def test_rect_eval_cases_see_every_beam(world, n, lvl):
+    _, _, pts, ev = gn_cases.eval_inputs(n, lvl, world_name=world)
+    mm = gn_f64.min_margin(ev, gn_f64.depth_eval(n))
+    assert pts.shape[0] == n and mm > 1.0, mm
+
+
+def test_rect_worlds_are_rectangular_and_square_worlds_unchanged():
+    """the rectangular worlds hold sx != sy on every level (the oracle's own geometry); a square World draws the random
+    numbers it drew before size_y existed"""
+    for name, (sx, sy) in (("wide", (640, 192)), ("tall", (192, 640)), ("bigwide", (8192, 1040))):
+        w = gn_cases.world(name)
+        for lvl in range(w.levels):
+            assert w.o.level_info(lvl)[:2] == (sx >> lvl, sy >> lvl) and w.lv[lvl][0].shape == (sy >> lvl, sx >> lvl)
+    w = gn_cases.World("ho", 64, 2, seed=5)
+    rng = np.random.default_rng(5)
+    for lvl in range(2):
+        assert np.array_equal(w.lv[lvl][0], rng.uniform(-2.5, 2.5, (64 >> lvl, 64 >> lvl)).astype(np.float32))
+
 @pytest.mark.parametrize("case", [c for c in gn_cases.BATCH_CASES if c["id"] in ("cached4x17-quad-L0", "cached4x9-plane-L2", "plain1x4x0-L0")],
                          ids=lambda c: c["id"])
 def test_step_check_accepts_the_oracles_own_step(case):

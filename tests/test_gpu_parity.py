@@ -1692,3 +1692,44 @@ def test_fast_eval_kernel_against_float64(capi, n, lvl):
     gn_f64.check_H(H, ev, d, f"eval n={n} L{lvl}")
     gn_f64.check_dtr(dtr, ev, d, f"eval n={n} L{lvl}")
     g.close()
+
+
+# the same single-scan checks on rectangular maps (gn_cases "wide" 640 x 192 / "tall" 192 x 640 pyramids): each case names its world
+@pytest.mark.parametrize("world,W,n", gn_cases.RECT_SINGLE_CASES)
+def test_fast_single_scan_teams_on_rectangles_one_step_against_float64(capi, world, W, n):
+    w, p0, pts, ev = gn_cases.single_inputs(W, n, world_name=world)
+    g = w.gpu(capi, waves_per_scan=W)
+    assert g.level_info(0)[:2] == (w.size, w.size_y)
+    pose, cov = g.match_level(0, p0, pts, 0)
+    _expect_cfg(g.last_launch_config(), dict(kernel="gn_match_kernel", waves_per_scan=W, block=64 * W * (4 if W == 1 else 1),
+                                             beams_per_lane=_bpl_rule(n, W), texel_cache=False), f"{world} W={W} n={n}")
+    d = gn_f64.depth_team(n, W)
+    f, s = _check_eval(cov.reshape(3, 3).T, ev, d, f"{world} W={W} n={n} d={d}", w.o.map_coords_pose(0, p0), g.getMapCoordsPose(0, pose))
+    g.close()
+    print(f"team W={W} n={n} on {world} d={d}: {f:.3f} of the bound, margin {gn_f64.min_margin(ev, d):.2f}, step checked {s}")
+
+
+@pytest.mark.parametrize("world,n", gn_cases.RECT_COOP_CASES)
+def test_fast_coop_matcher_on_rectangles_one_step_against_float64(capi, world, n):
+    w, p0, pts, ev = gn_cases.coop_inputs(n, world_name=world)
+    g = w.gpu(capi)
+    pose, cov = g.match_level(0, p0, pts, 0)
+    K = gn_f64.coop_workgroups(n)
+    cfg = g.last_launch_config()
+    assert cfg["kernel"] == "gn_match_coop_kernel" and cfg["waves_per_scan"] < 0 and cfg["grid"] == K and cfg["block"] == 256, cfg
+    d = gn_f64.depth_coop(n, K)
+    _check_eval(cov.reshape(3, 3).T, ev, d, f"coop {world} n={n} K={K} d={d}", w.o.map_coords_pose(0, p0), g.getMapCoordsPose(0, pose))
+    assert g.debug_coop_fallbacks() == 0
+    g.close()
+
+
+@pytest.mark.parametrize("world,n,lvl", gn_cases.RECT_EVAL_CASES)
+def test_fast_eval_kernel_on_rectangles_against_float64(capi, world, n, lvl):
+    w, p0, pts, ev = gn_cases.eval_inputs(n, lvl, world_name=world)
+    g = w.gpu(capi)
+    pm = w.o.map_coords_pose(lvl, p0)
+    H, dtr = g.hessian_derivs(lvl, pm, pts)
+    d = gn_f64.depth_eval(n)
+    gn_f64.check_H(H, ev, d, f"eval {world} n={n} L{lvl}")
+    gn_f64.check_dtr(dtr, ev, d, f"eval {world} n={n} L{lvl}")
+    g.close()

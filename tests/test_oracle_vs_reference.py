@@ -4,8 +4,10 @@ the private Eigen/tf stand-in).  Every comparison is BIT-EXACT (integer/index wo
 import os
 import numpy as np
 import pytest
+from hypothesis import HealthCheck, given, seed, settings
 
-from conftest import bits, make_oracle
+import rect_cases
+from conftest import bits, make_oracle, oracle_kinds
 
 
 
@@ -157,10 +159,9 @@ def test_util_helpers(oracle_mod):
 
 
 def test_randomised_geometries_restatement_equals_reference(oracle_mod):
-    """odd map sizes, non-square maps are not supported by the constructor (sizeX, sizeY passed separately but the
-    reference squares nothing) -- so: odd sizes, 1..4 levels, off-centre start coordinates, random update factors,
-    rooms larger than the map (beams ending outside): restatement == reference, bit for bit.  (Poses that make H
-    singular are avoided on purpose: the reference then casts a NaN coordinate to an index and segfaults.)"""
+    """odd square map sizes (rectangular maps: the two tests after this one), 1..4 levels, off-centre start coordinates,
+    random update factors, rooms larger than the map (beams ending outside): restatement == reference, bit for bit.  (Poses
+    that make H singular are avoided on purpose: the reference then casts a NaN coordinate to an index and segfaults.)"""
     if not oracle_mod.available("hr"):
         pytest.skip("oracle/_ref not built")
     from hector_slam_amd import synth
@@ -206,6 +207,61 @@ def test_randomised_geometries_restatement_equals_reference(oracle_mod):
             a, b = o["ho"].download_level(lvl), o["hr"].download_level(lvl)
             assert np.array_equal(a[0].view(np.uint32), b[0].view(np.uint32)) and np.array_equal(a[1], b[1]), (trial, lvl)
             assert np.array_equal(o["ho"].occupancy_grid(lvl), o["hr"].occupancy_grid(lvl))
+
+
+def test_rectangular_geometries_restatement_equals_reference(oracle_mod):
+    """the processor loop of the test above on the rectangular maps of tests/rect_cases.py (wide / tall, sx % 4 != 0, strips
+    whose coarsest level is 6 cells across), each with its transpose: proc_update with a laser origin, one
+    map_without_matching step, rooms larger than the map -- poses, covariances, every level and the occupancy grids
+    bit-identical.  The restatement runs first on every step and must not read the map at a NaN coordinate (the reference
+    would crash there), so every step of every geometry is compared."""
+    if not oracle_mod.available("hr"):
+        pytest.skip("oracle/_ref not built")
+    import rect_cases
+    from hector_slam_amd import synth
+    for gi, (sx, sy, levels) in enumerate(rect_cases.SMALL):
+        rng = np.random.default_rng([sx, sy, levels])
+        res = rect_cases.RES
+        start = (float(rng.uniform(0.35, 0.65)), float(rng.uniform(0.35, 0.65)))
+        free, occ = float(rng.uniform(0.3, 0.49)), float(rng.uniform(0.55, 0.95))
+        grow = 1.15 if gi % 2 else 0.8
+        n_beams = (1081, 4096)[gi % 2]
+        world, poses, scans = rect_cases.scene(sx, sy, 12, n_beams, seed=sx * 7 + sy, res=res, grow=grow)
+        o = {k: oracle_mod.Oracle(k, res, sx, sy, levels, start) for k in ("ho", "hr")}
+        for k in o:
+            o[k].set_update_factor_free(free)
+            o[k].set_update_factor_occupied(occ)
+            o[k].proc_set_thresholds(0.02, 0.02)
+        hint = {k: poses[0].copy() for k in o}
+        for t in range(12):
+            origo = rng.uniform(-2, 2, 2).astype(np.float32)
+            last = {}
+            for k in ("ho", "hr"):
+                o[k].proc_update(scans[t], hint[k], origo=origo, map_without_matching=(t == 5))
+                last[k] = o[k].proc_last_pose()
+                assert o["ho"].undefined_reads() == 0, (sx, sy, t)
+            assert np.array_equal(bits(last["ho"][0]), bits(last["hr"][0])), (sx, sy, t)
+            assert np.array_equal(bits(last["ho"][1]), bits(last["hr"][1])), (sx, sy, t)
+            step = poses[min(t + 1, 11)] - poses[t]
+            for k in o:
+                hint[k] = last[k][0] + step
+        for lvl in range(levels):
+            a, b = o["ho"].download_level(lvl), o["hr"].download_level(lvl)
+            assert a[0].shape == (sy >> lvl, sx >> lvl)
+            assert np.array_equal(bits(a[0]), bits(b[0])) and np.array_equal(a[1], b[1]), (sx, sy, lvl)
+            assert np.array_equal(o["ho"].occupancy_grid(lvl), o["hr"].occupancy_grid(lvl))
+        _, ui = o["ho"].download_level(0)
+        assert (ui >= 0).sum() > 100, (sx, sy)  # the loop did map something
+
+
+@pytest.mark.skipif("hr" not in oracle_kinds(), reason="oracle/_ref not built")
+@seed(rect_cases.RECT_SEED)
+@settings(max_examples=20, deadline=None, database=None, suppress_health_check=list(HealthCheck))
+@given(g=rect_cases.rect_geometry())
+def test_rectangular_property_restatement_equals_reference(oracle_mod, g):
+    """independent size_x / size_y (tests/rect_cases.py rect_geometry): the restatement equals the reference headers on every
+    pose, covariance and map of a short SLAM loop.  The GPU test of tests/test_gpu_rect_maps.py draws the same examples."""
+    rect_cases.run_loop(g, rect_cases.oracle_impl(oracle_mod, "ho"), rect_cases.oracle_impl(oracle_mod, "hr"))
 
 
 def test_dense_fans_on_and_beyond_the_map_borders_restatement_equals_reference(oracle_mod):
