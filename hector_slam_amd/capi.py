@@ -80,6 +80,10 @@ SIGNATURES = {
     "hsm_match_batch_ranges": (_i, [_vp, _i, _vp, _vp, _i, _f, _f, _f, _f, _f, _vp, _vp, _vp]),
     "hsm_occupancy_grid": (_i, [_vp, _i, _vp]),
     "hsm_ray_distances": (_i, [_vp, _i, _f, _f, _f, _i, _f32p, _f32p, _f32p, _f32p]),
+    "hsm_score_batch_device": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "hsm_select_best_device": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "hsm_match_score_batch_device": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    "hsm_match_score_batch": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp]),
     "hsm_likelihood_states": (_i, [_vp, _i, _i, _f32p, _vp, _i, _f32p]),
     "hsm_residual_states": (_i, [_vp, _i, _i, _f32p, _vp, _i, _f32p]),
     "hsm_covariance_for_poses": (_i, [_vp, _i, _i, _f32p, _vp, _i, _f32p, _f32p, _f32p]),
@@ -532,6 +536,66 @@ class MapRepMultiMap:
         _check(self._lib.hsm_match_batch_device(self._h, batch, d_begin, d_pts, d_offsets or None, shared_n,
                                                 d_out_pose, d_out_cov or None, stream or None),
                "hsm_match_batch_device")
+
+    def score_batch_device(self, level, batch, d_poses_world, d_pts, d_offsets, shared_n, d_out_likelihood, d_out_residual=0,
+                           stream=0):
+        """Raw device pointers (ints), asynchronous on ``stream``: likelihood / residual of ``batch`` WORLD poses on ``level``."""
+        _check(self._lib.hsm_score_batch_device(self._h, level, batch, d_poses_world or None, d_pts or None, d_offsets or None,
+                                                shared_n, d_out_likelihood or None, d_out_residual or None, stream or None),
+               "hsm_score_batch_device")
+
+    def select_best_device(self, groups, d_group_offsets, group_size, d_scores, d_poses_world, d_out_index, d_out_score=0,
+                           d_out_pose_world=0, stream=0):
+        """Raw device pointers: per group the index of the highest score (NaN never wins, ties -> lowest index, none -> -1)."""
+        _check(self._lib.hsm_select_best_device(self._h, groups, d_group_offsets or None, group_size, d_scores or None,
+                                                d_poses_world or None, d_out_index or None, d_out_score or None,
+                                                d_out_pose_world or None, stream or None), "hsm_select_best_device")
+
+    def match_score_batch_device(self, batch, d_begin, d_pts, d_offsets, shared_n, d_out_pose, d_out_cov, score_level,
+                                 d_out_likelihood, d_out_residual=0, groups=0, d_group_offsets=0, group_size=0, d_out_index=0,
+                                 d_out_score=0, d_out_best_pose=0, stream=0):
+        """match_batch_device -> score_batch_device -> (groups > 0) select_best_device as one call on ``stream``."""
+        _check(self._lib.hsm_match_score_batch_device(
+            self._h, batch, d_begin or None, d_pts or None, d_offsets or None, shared_n, d_out_pose or None, d_out_cov or None,
+            score_level, d_out_likelihood or None, d_out_residual or None, groups, d_group_offsets or None, group_size,
+            d_out_index or None, d_out_score or None, d_out_best_pose or None, stream or None), "hsm_match_score_batch_device")
+
+    def score_batch(self, level, poses_world, pts, offsets=None):
+        """(likelihood, residual) of WORLD poses on ``level``; ``offsets`` None = every pose against the one scan ``pts``.
+        Host arrays in and out, through torch device buffers on the current stream."""
+        w = torch.as_tensor(np.ascontiguousarray(poses_world, np.float32).reshape(-1, 3)).cuda()
+        a, _, n = _pts(pts)
+        d_pts = torch.as_tensor(a).cuda()
+        d_offs = None if offsets is None else torch.as_tensor(np.ascontiguousarray(offsets, np.int32)).cuda()
+        out = torch.empty((2, w.shape[0]), dtype=torch.float32, device="cuda")
+        self.score_batch_device(level, w.shape[0], w.data_ptr(), d_pts.data_ptr() if n else 0,
+                                0 if d_offs is None else d_offs.data_ptr(), n if d_offs is None else 0, out[0].data_ptr(),
+                                out[1].data_ptr(), torch.cuda.current_stream().cuda_stream)
+        lh, res = out.cpu().numpy()
+        return lh.copy(), res.copy()
+
+    def match_score_batch(self, begin_world, pts, offsets=None, score_level=0, group_size=None, group_offsets=None, want_cov=True):
+        """hsm_match_score_batch: host arrays in/out.  Returns a dict: pose [B,3], cov [B,9] or None, likelihood [B], residual [B],
+        and -- with ``group_size`` or ``group_offsets`` -- best_index [G], best_score [G], best_pose [G,3] (NaN where a group
+        has no winner)."""
+        b = np.ascontiguousarray(begin_world, np.float32).reshape(-1, 3)
+        B = b.shape[0]
+        a, p, n = _pts(pts)
+        offs = None if offsets is None else np.ascontiguousarray(offsets, np.int32)
+        goffs = None if group_offsets is None else np.ascontiguousarray(group_offsets, np.int32)
+        G = 0 if group_size is None and goffs is None else (goffs.size - 1 if goffs is not None else (B // group_size if group_size else 0))
+        r = {"pose": np.empty_like(b), "cov": np.zeros((B, 9), np.float32) if want_cov else None,
+             "likelihood": np.empty(B, np.float32), "residual": np.empty(B, np.float32)}
+        if G:
+            r.update(best_index=np.empty(G, np.int32), best_score=np.empty(G, np.float32),
+                     best_pose=np.full((G, 3), np.nan, np.float32))
+        _check(self._lib.hsm_match_score_batch(
+            self._h, B, b.ctypes.data, p, None if offs is None else offs.ctypes.data, n if offs is None else 0,
+            r["pose"].ctypes.data, r["cov"].ctypes.data if want_cov else None, score_level, r["likelihood"].ctypes.data,
+            r["residual"].ctypes.data, G, None if goffs is None else goffs.ctypes.data, group_size or 0,
+            r["best_index"].ctypes.data if G else None, r["best_score"].ctypes.data if G else None,
+            r["best_pose"].ctypes.data if G else None), "hsm_match_score_batch")
+        return r
 
     def match_batch_ranges(self, begin_world, ranges, angle_min, angle_increment, range_min, range_max, scale_to_map=None,
                            want_cov=True):

@@ -1043,6 +1043,52 @@ int hsm_last_launch_config(const hsm_ctx* h, int cfg[5]) {
   return HSM_OK;
 }
 
+// Orders a launch on `s` that READS the map (a batched match, a batched score) against the map updates, which are queued on the
+// context's own stream.  *mark = the stream's record where the launch has to be remembered for the next update
+// (`(*mark)->pending = true` once it is queued), nullptr where nothing is to be remembered (the context's own stream; a capture).
+static int order_map_reader(hsm_ctx* h, hipStream_t s, const char* who, hsm_ctx::ForeignStream** mark) {
+  *mark = nullptr;
+  if (s == h->stream) return HSM_OK;
+  // A caller-owned stream is not ordered against the context's own one, on which map updates are queued
+  // (hsm_update_by_scan returns before they ran): order the launch behind the updates queued so far, and
+  // leave a marker the next update waits for, so that it does not rewrite the map under a running reader.
+  hsm_ctx::ForeignStream* fs = nullptr;
+  for (hsm_ctx::ForeignStream& f : h->foreign)
+    if (f.s == s) fs = &f;
+  if (!fs) {
+    h->foreign.push_back({s, 0ull, false});
+    fs = &h->foreign.back();
+  }
+  if (stream_capturing(s)) {
+    // A launch into a graph capture runs at the caller's replays, not now: it neither records that the stream is ordered behind
+    // the updates nor leaves a marker for the next update (either would describe work only the graph holds).  The updates queued
+    // so far are waited for on the host instead -- a wait node on an event recorded outside the capture would order the graph
+    // but not the stream's later eager launches.  Later updates and the replays are ordered by the caller; while the capture
+    // lasts, updates are refused (order_after_foreign_match).
+    hipStreamCaptureMode mode = hipStreamCaptureModeRelaxed;
+    HIP_TRY(hipThreadExchangeStreamCaptureMode(&mode));
+    const hipError_t e = hipStreamSynchronize(h->stream);
+    (void)hipThreadExchangeStreamCaptureMode(&mode);
+    if (e != hipSuccess) {
+      const std::string what = std::string(who) + ": waiting for the queued map updates at capture";
+      return fail(HSM_ERR_HIP, what.c_str(), e);
+    }
+    return HSM_OK;
+  }
+#if !defined(HSM_EXP_NO_XSTREAM_ORDER)  // (negative control of test_queued_updates_are_ordered_against_caller_streams)
+  if (fs->ordered_epoch != h->upd_epoch) {  // THIS stream has not been ordered behind the latest map writes yet
+    if (!h->evt_updates) HIP_TRY(hipEventCreateWithFlags(&h->evt_updates, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(h->evt_updates, h->stream));
+    HIP_TRY(hipStreamWaitEvent(s, h->evt_updates, 0));
+    fs->ordered_epoch = h->upd_epoch;
+  }
+#endif
+  // no marker here (an event record between back-to-back launches costs 2-3 us of kernel time each): the
+  // next writer of the map records one on every stream with a pending reader (order_after_foreign_match)
+  *mark = fs;
+  return HSM_OK;
+}
+
 static int match_batch_device_nolock(hsm_ctx* h, int batch, const float* d_begin_world, const float* d_pts_xy,
                                      const int* d_scan_offsets, int shared_n, float* d_out_pose,
                                      float* d_out_cov, void* stream, int n_bound = 0, const ExchangeFused* xp = nullptr) {
@@ -1074,42 +1120,10 @@ static int match_batch_device_nolock(hsm_ctx* h, int batch, const float* d_begin
   // scans longer than the hint (the beams beyond the register/LDS-resident ones stream from memory).
   const int hint = shared_n > 0 ? shared_n : 1081;
   hipStream_t s = (hipStream_t)stream;
-  if (s == h->stream) return launch_match(h, P, hint, s);
-  // A caller-owned stream is not ordered against the context's own one, on which map updates are queued
-  // (hsm_update_by_scan returns before they ran): order the match behind the updates queued so far, and
-  // leave a marker the next update waits for, so that it does not rewrite the map under a running match.
   hsm_ctx::ForeignStream* fs = nullptr;
-  for (hsm_ctx::ForeignStream& f : h->foreign)
-    if (f.s == s) fs = &f;
-  if (!fs) {
-    h->foreign.push_back({s, 0ull, false});
-    fs = &h->foreign.back();
-  }
-  if (stream_capturing(s)) {
-    // A launch into a graph capture runs at the caller's replays, not now: it neither records that the stream is ordered behind
-    // the updates nor leaves a marker for the next update (either would describe work only the graph holds).  The updates queued
-    // so far are waited for on the host instead -- a wait node on an event recorded outside the capture would order the graph
-    // but not the stream's later eager launches.  Later updates and the replays are ordered by the caller; while the capture
-    // lasts, updates are refused (order_after_foreign_match).
-    hipStreamCaptureMode mode = hipStreamCaptureModeRelaxed;
-    HIP_TRY(hipThreadExchangeStreamCaptureMode(&mode));
-    const hipError_t e = hipStreamSynchronize(h->stream);
-    (void)hipThreadExchangeStreamCaptureMode(&mode);
-    if (e != hipSuccess) return fail(HSM_ERR_HIP, "hsm_match_batch_device: waiting for the queued map updates at capture", e);
-    return launch_match(h, P, hint, s);
-  }
-#if !defined(HSM_EXP_NO_XSTREAM_ORDER)  // (negative control of test_queued_updates_are_ordered_against_caller_streams)
-  if (fs->ordered_epoch != h->upd_epoch) {  // THIS stream has not been ordered behind the latest map writes yet
-    if (!h->evt_updates) HIP_TRY(hipEventCreateWithFlags(&h->evt_updates, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(h->evt_updates, h->stream));
-    HIP_TRY(hipStreamWaitEvent(s, h->evt_updates, 0));
-    fs->ordered_epoch = h->upd_epoch;
-  }
-#endif
+  if (int rc = order_map_reader(h, s, "hsm_match_batch_device", &fs)) return rc;
   if (int rc = launch_match(h, P, hint, s)) return rc;
-  // no marker here (an event record between back-to-back launches costs 2-3 us of kernel time each): the
-  // next writer of the map records one on every stream with a pending match (order_after_foreign_match)
-  fs->pending = true;
+  if (fs) fs->pending = true;
   return HSM_OK;
 }
 
@@ -1142,19 +1156,173 @@ int hsm_match_batch_device_gather(hsm_ctx* h, int batch, const float* d_begin_wo
   return hsm_exchange_post_wait(x, d_out_pose, first_row, batch, lag, d_out_all, stream);
 }
 
-int hsm_match_batch(hsm_ctx* h, int batch, const float* begin_world, const float* pts_xy,
-                    const int* scan_offsets, int shared_n, float* out_pose, float* out_cov) {
+// The weighting step behind a batched match: B (world pose, scan) pairs scored on `level` in one launch of score_batch_kernel
+// (gn_match.h).  A reader of the map like the batched match, so ordered like it (order_map_reader); no workspace, no state.
+static int score_batch_device_nolock(hsm_ctx* h, int level, int batch, const float* d_poses_world, const float* d_pts_xy,
+                                     const int* d_scan_offsets, int shared_n, float* d_out_likelihood,
+                                     float* d_out_residual, void* stream) {
+  if (int rc = valid_level(h, level)) return rc;
+  if (batch < 0 || (!d_out_likelihood && !d_out_residual) || (!d_scan_offsets && shared_n < 0) ||
+      (batch > 0 && (!d_poses_world || (!d_pts_xy && !d_scan_offsets && shared_n > 0))))
+    return fail(HSM_ERR_INVALID, "hsm_score_batch_device: bad argument");
+  if (batch == 0) return HSM_OK;
+  if (int rc = select_device(h)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  hsm_ctx::ForeignStream* fs = nullptr;
+  if (int rc = order_map_reader(h, s, "hsm_score_batch_device", &fs)) return rc;
+  const float factor = (float)(1.0 / pow(2.0, (double)level));
+  const LevelView v = level_view(h->levels[level], factor, 1);
+  const bool exact = wants_exact(h);
+  const int grid = (batch + 3) / 4;
+#define HSM_LAUNCH_SCORE(LAY, EX)                                                                                        \
+  hipLaunchKernelGGL((score_batch_kernel<LAY, EX>), dim3(grid), dim3(256), 0, s, v, d_poses_world, batch,                \
+                     reinterpret_cast<const float2*>(d_pts_xy), d_scan_offsets, d_scan_offsets ? 0 : shared_n,           \
+                     d_out_likelihood, d_out_residual)
+  if (h->layout == kLayoutPlane) {
+    if (exact) HSM_LAUNCH_SCORE(kLayoutPlane, true); else HSM_LAUNCH_SCORE(kLayoutPlane, false);
+  } else {
+    if (exact) HSM_LAUNCH_SCORE(kLayoutQuad, true); else HSM_LAUNCH_SCORE(kLayoutQuad, false);
+  }
+#undef HSM_LAUNCH_SCORE
+  HIP_TRY(hipGetLastError());
+  if (fs) fs->pending = true;
+  h->last_kernel = "score_batch_kernel";
+  h->last_parity = exact ? HSM_PARITY_EXACT : (h->relaxed ? HSM_PARITY_RELAXED : HSM_PARITY_FAST);
+  return HSM_OK;
+}
+
+int hsm_score_batch_device(hsm_ctx* h, int level, int batch, const float* d_poses_world, const float* d_pts_xy,
+                           const int* d_scan_offsets, int shared_n, float* d_out_likelihood, float* d_out_residual,
+                           void* stream) {
   if (!h) return fail(HSM_ERR_INVALID, "null context");
-  if (batch < 0 || !begin_world || !out_pose) return fail(HSM_ERR_INVALID, "hsm_match_batch: bad argument");
+  std::lock_guard<std::mutex> lk(h->mu);
+  return score_batch_device_nolock(h, level, batch, d_poses_world, d_pts_xy, d_scan_offsets, shared_n, d_out_likelihood,
+                                   d_out_residual, stream);
+}
+
+// Groups of at most this many entries (or, with CSR groups whose sizes only the device knows, launches of at least this many
+// groups) take one wavefront per group, the others one workgroup per group.  Either shape gives the same result.
+constexpr int kSelectWaveGroupMax = 1024;
+
+// reads no map: stream order is all it needs
+static int select_best_device_nolock(hsm_ctx* h, int groups, const int* d_group_offsets, int group_size, const float* d_scores,
+                                     const float* d_poses_world, int* d_out_index, float* d_out_score,
+                                     float* d_out_pose_world, void* stream) {
+  if (groups < 0 || (!d_group_offsets && group_size < 0) || !d_out_index || (d_out_pose_world && !d_poses_world) ||
+      (!d_scores && groups > 0 && (d_group_offsets || group_size > 0)) ||
+      (!d_group_offsets && groups > 0 && (long long)groups * group_size > INT_MAX))
+    return fail(HSM_ERR_INVALID, "hsm_select_best_device: bad argument");
+  if (groups == 0) return HSM_OK;
+  if (int rc = select_device(h)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const bool wave_per_group = d_group_offsets ? groups >= kSelectWaveGroupMax : group_size <= kSelectWaveGroupMax;
+  if (wave_per_group)
+    hipLaunchKernelGGL((select_best_kernel<true>), dim3((groups + 3) / 4), dim3(256), 0, s, groups, d_group_offsets, group_size,
+                       d_scores, d_poses_world, d_out_index, d_out_score, d_out_pose_world);
+  else
+    hipLaunchKernelGGL((select_best_kernel<false>), dim3(groups), dim3(256), 0, s, groups, d_group_offsets, group_size,
+                       d_scores, d_poses_world, d_out_index, d_out_score, d_out_pose_world);
+  HIP_TRY(hipGetLastError());
+  return HSM_OK;
+}
+
+int hsm_select_best_device(hsm_ctx* h, int groups, const int* d_group_offsets, int group_size, const float* d_scores,
+                           const float* d_poses_world, int* d_out_index, float* d_out_score, float* d_out_pose_world,
+                           void* stream) {
+  if (!h) return fail(HSM_ERR_INVALID, "null context");
+  std::lock_guard<std::mutex> lk(h->mu);
+  return select_best_device_nolock(h, groups, d_group_offsets, group_size, d_scores, d_poses_world, d_out_index, d_out_score,
+                                   d_out_pose_world, stream);
+}
+
+// match -> score at the matched poses -> (groups > 0) the winner of every group, queued on `stream` under one lock.  Every
+// argument is checked before the first launch, so a bad one queues nothing.
+static int match_score_batch_device_nolock(hsm_ctx* h, int batch, const float* d_begin_world, const float* d_pts_xy,
+                                           const int* d_scan_offsets, int shared_n, float* d_out_pose, float* d_out_cov,
+                                           int score_level, float* d_out_likelihood, float* d_out_residual, int groups,
+                                           const int* d_group_offsets, int group_size, int* d_out_index, float* d_out_score,
+                                           float* d_out_best_pose, void* stream, int n_bound = 0) {
+  if (int rc = valid_level(h, score_level)) return rc;
+  if (batch < 0 || !d_begin_world || !d_out_pose || (!d_scan_offsets && shared_n < 0) || (!d_out_likelihood && !d_out_residual) ||
+      (batch > 0 && !d_pts_xy && !d_scan_offsets && shared_n > 0) || groups < 0 ||
+      (groups > 0 && (!d_out_likelihood || !d_out_index || (!d_group_offsets && (group_size < 0 || (long long)groups * group_size > batch)))))
+    return fail(HSM_ERR_INVALID, "hsm_match_score_batch_device: bad argument");
+  if (int rc = match_batch_device_nolock(h, batch, d_begin_world, d_pts_xy, d_scan_offsets, shared_n, d_out_pose, d_out_cov, stream, n_bound))
+    return rc;
+  // the sizing hint of a CSR match means nothing to the score: its kernel reads every scan's length from the offsets
+  if (int rc = score_batch_device_nolock(h, score_level, batch, d_out_pose, d_pts_xy, d_scan_offsets, d_scan_offsets ? 0 : shared_n,
+                                         d_out_likelihood, d_out_residual, stream))
+    return rc;
+  if (groups == 0) return HSM_OK;
+  return select_best_device_nolock(h, groups, d_group_offsets, group_size, d_out_likelihood, d_out_pose, d_out_index, d_out_score,
+                                   d_out_best_pose, stream);
+}
+
+int hsm_match_score_batch_device(hsm_ctx* h, int batch, const float* d_begin_world, const float* d_pts_xy,
+                                 const int* d_scan_offsets, int shared_n, float* d_out_pose, float* d_out_cov, int score_level,
+                                 float* d_out_likelihood, float* d_out_residual, int groups, const int* d_group_offsets,
+                                 int group_size, int* d_out_index, float* d_out_score, float* d_out_best_pose, void* stream) {
+  if (!h) return fail(HSM_ERR_INVALID, "null context");
+  std::lock_guard<std::mutex> lk(h->mu);
+  return match_score_batch_device_nolock(h, batch, d_begin_world, d_pts_xy, d_scan_offsets, shared_n, d_out_pose, d_out_cov,
+                                         score_level, d_out_likelihood, d_out_residual, groups, d_group_offsets, group_size,
+                                         d_out_index, d_out_score, d_out_best_pose, stream);
+}
+
+// what hsm_match_score_batch asks for on top of hsm_match_batch (host pointers)
+struct BatchScoreReq {
+  int level;
+  float* out_lh;
+  float* out_res;  // may be null
+  int groups;      // 0: no ranking
+  const int* group_offsets;
+  int group_size;
+  int* out_index;
+  float* out_score;      // may be null
+  float* out_best_pose;  // may be null; in/out (a group without a winner keeps the caller's values)
+};
+
+// hsm_match_batch, and with `sr` hsm_match_score_batch: host arrays in, one device call on the context's stream, results out
+static int match_batch_host(hsm_ctx* h, int batch, const float* begin_world, const float* pts_xy, const int* scan_offsets,
+                            int shared_n, float* out_pose, float* out_cov, const BatchScoreReq* sr, const char* who) {
+  if (!h) return fail(HSM_ERR_INVALID, "null context");
+  if (batch < 0 || !begin_world || !out_pose) return fail(HSM_ERR_INVALID, who);
+  const int G = sr ? sr->groups : 0;
+  if (sr) {
+    if (int rc = valid_level(h, sr->level)) return rc;
+    if (!sr->out_lh || G < 0 || (G > 0 && (!sr->out_index || (!sr->group_offsets && (sr->group_size < 0 || (long long)G * sr->group_size > batch)))))
+      return fail(HSM_ERR_INVALID, who);
+    if (G > 0 && sr->group_offsets)
+      for (int g = 0; g < G; ++g)
+        if (sr->group_offsets[g] < 0 || sr->group_offsets[g] > sr->group_offsets[g + 1] || sr->group_offsets[g + 1] > batch)
+          return fail(HSM_ERR_INVALID, who);
+  }
   if (batch == 0) return HSM_OK;
   const size_t total = scan_offsets ? (size_t)scan_offsets[batch] : (size_t)(shared_n > 0 ? shared_n : 0);
-  if (total > 0 && !pts_xy) return fail(HSM_ERR_INVALID, "hsm_match_batch: pts_xy is null");
+  if (total > 0 && !pts_xy) return fail(HSM_ERR_INVALID, who);
   const size_t b_begin = (size_t)batch * 3 * sizeof(float);
   const size_t b_pts = total * 2 * sizeof(float);
   const size_t b_offs = scan_offsets ? ((size_t)batch + 1) * sizeof(int) : 0;
   const size_t b_pose = b_begin, b_cov = (size_t)batch * 9 * sizeof(float);
   auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t need = al(b_begin) + al(b_pts) + al(b_offs) + al(b_pose) + al(b_cov);
+  // the score's and the ranking's arrays, one block behind the match's own: likelihood | residual | group offsets | winner
+  // index | winner score | winner pose
+  const size_t b_lh = sr ? (size_t)batch * sizeof(float) : 0, b_res = sr && sr->out_res ? b_lh : 0;
+  const size_t b_goffs = G > 0 && sr->group_offsets ? ((size_t)G + 1) * sizeof(int) : 0;
+  const size_t b_idx = (size_t)G * sizeof(int), b_bscore = G > 0 && sr->out_score ? (size_t)G * sizeof(float) : 0;
+  const size_t b_bpose = G > 0 && sr->out_best_pose ? (size_t)G * 3 * sizeof(float) : 0;
+  const size_t o_res = al(b_lh), o_goffs = o_res + al(b_res), o_idx = o_goffs + al(b_goffs), o_bscore = o_idx + al(b_idx);
+  const size_t o_bpose = o_bscore + al(b_bscore), b_extra = o_bpose + al(b_bpose);
+  // the launches behind the copies in: x = the device address of that block
+  auto launch = [&](const float* d_begin, const float* d_pts, const int* d_offs, int n_or_hint, float* d_pose, float* d_cov,
+                    char* x, int n_bound) {
+    if (!sr) return match_batch_device_nolock(h, batch, d_begin, d_pts, d_offs, n_or_hint, d_pose, d_cov, h->stream, n_bound);
+    return match_score_batch_device_nolock(h, batch, d_begin, d_pts, d_offs, n_or_hint, d_pose, d_cov, sr->level, (float*)x,
+                                           b_res ? (float*)(x + o_res) : nullptr, G, b_goffs ? (const int*)(x + o_goffs) : nullptr,
+                                           sr->group_size, (int*)(x + o_idx), b_bscore ? (float*)(x + o_bscore) : nullptr,
+                                           b_bpose ? (float*)(x + o_bpose) : nullptr, h->stream, n_bound);
+  };
+  const size_t need = al(b_begin) + al(b_pts) + al(b_offs) + al(b_pose) + al(b_cov) + b_extra;
   std::lock_guard<std::mutex> lk(h->mu);
   if (int rc = select_device(h)) return rc;
   if (!scan_offsets) {
@@ -1163,7 +1331,9 @@ int hsm_match_batch(hsm_ctx* h, int batch, const float* begin_world, const float
     // start pose once and writes its result once, so they cross PCIe exactly once without a copy command in front of or behind the
     // launch -- and only the scan (which every wavefront reads) is copied to the device.  4096 hypotheses of a 1081-beam scan:
     // one 8.6 KB copy + the launch, against three copies, the launch and two more copies of the general path below.
-    const size_t hb = al(b_begin) + al(b_pose) + al(b_cov) + al(b_pts);
+    // (With a score behind the match, its wavefront reads the matched pose back once and writes 4 or 8 bytes; the ranking reads
+    // every likelihood once.)
+    const size_t hb0 = al(b_begin) + al(b_pose) + al(b_cov) + al(b_pts), hb = hb0 + b_extra;
     if (hb > h->h_hyp_cap) {
       HIP_TRY(hipStreamSynchronize(h->stream));
       if (h->h_hyp_pinned) HIP_TRY(hipHostFree(h->h_hyp_pinned));
@@ -1177,20 +1347,29 @@ int hsm_match_batch(hsm_ctx* h, int batch, const float* begin_world, const float
     float* hp_pose = (float*)(hp + al(b_begin));
     float* hp_cov = (float*)(hp + al(b_begin) + al(b_pose));
     float* hp_pts = (float*)(hp + al(b_begin) + al(b_pose) + al(b_cov));
+    char* hx = hp + hb0;
     memcpy(hp_begin, begin_world, b_begin);
     if (out_cov) memcpy(hp_cov, out_cov, b_cov);  // in/out: an empty scan leaves the caller's matrices untouched (ScanMatcher.h:68,189)
     if (b_pts) memcpy(hp_pts, pts_xy, b_pts);
+    if (b_goffs) memcpy(hx + o_goffs, sr->group_offsets, b_goffs);
+    if (b_bpose) memcpy(hx + o_bpose, sr->out_best_pose, b_bpose);
     char* dp = nullptr;
     HIP_TRY(hipHostGetDevicePointer((void**)&dp, hp, 0));
     if (int rc = ensure_scan_capacity(h->d_scan, h->d_scan_cap, total)) return rc;
     if (b_pts) HIP_TRY(hipMemcpyAsync(h->d_scan, hp_pts, b_pts, hipMemcpyHostToDevice, h->stream));
-    if (int rc = match_batch_device_nolock(h, batch, (const float*)dp, (const float*)h->d_scan, nullptr, shared_n > 0 ? shared_n : 0,
-                                           (float*)(dp + al(b_begin)), out_cov ? (float*)(dp + al(b_begin) + al(b_pose)) : nullptr,
-                                           h->stream))
+    if (int rc = launch((const float*)dp, (const float*)h->d_scan, nullptr, shared_n > 0 ? shared_n : 0, (float*)(dp + al(b_begin)),
+                        out_cov ? (float*)(dp + al(b_begin) + al(b_pose)) : nullptr, dp + hb0, 0))
       return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));
     memcpy(out_pose, hp_pose, b_pose);
     if (out_cov) memcpy(out_cov, hp_cov, b_cov);
+    if (sr) {
+      memcpy(sr->out_lh, hx, b_lh);
+      if (b_res) memcpy(sr->out_res, hx + o_res, b_res);
+      if (b_idx) memcpy(sr->out_index, hx + o_idx, b_idx);
+      if (b_bscore) memcpy(sr->out_score, hx + o_bscore, b_bscore);
+      if (b_bpose) memcpy(sr->out_best_pose, hx + o_bpose, b_bpose);
+    }
     return HSM_OK;
   }
   if (need > h->d_batch_cap) {
@@ -1206,10 +1385,13 @@ int hsm_match_batch(hsm_ctx* h, int batch, const float* begin_world, const float
   int* d_offs = scan_offsets ? (int*)(base + al(b_begin) + al(b_pts)) : nullptr;
   float* d_pose = (float*)(base + al(b_begin) + al(b_pts) + al(b_offs));
   float* d_cov = (float*)(base + al(b_begin) + al(b_pts) + al(b_offs) + al(b_pose));
+  char* dx = base + al(b_begin) + al(b_pts) + al(b_offs) + al(b_pose) + al(b_cov);
   HIP_TRY(hipMemcpyAsync(d_begin, begin_world, b_begin, hipMemcpyHostToDevice, h->stream));
   if (b_pts) HIP_TRY(hipMemcpyAsync(d_pts, pts_xy, b_pts, hipMemcpyHostToDevice, h->stream));
   if (d_offs) HIP_TRY(hipMemcpyAsync(d_offs, scan_offsets, b_offs, hipMemcpyHostToDevice, h->stream));
   if (out_cov) HIP_TRY(hipMemcpyAsync(d_cov, out_cov, b_cov, hipMemcpyHostToDevice, h->stream));  // in/out
+  if (b_goffs) HIP_TRY(hipMemcpyAsync(dx + o_goffs, sr->group_offsets, b_goffs, hipMemcpyHostToDevice, h->stream));
+  if (b_bpose) HIP_TRY(hipMemcpyAsync(dx + o_bpose, sr->out_best_pose, b_bpose, hipMemcpyHostToDevice, h->stream));  // in/out
   int hint = shared_n;
   if (scan_offsets) {
     hint = 0;
@@ -1218,13 +1400,34 @@ int hsm_match_batch(hsm_ctx* h, int batch, const float* begin_world, const float
       if (ni > hint) hint = ni;
     }
   }
-  if (int rc = match_batch_device_nolock(h, batch, d_begin, d_pts, d_offs, hint, d_pose,
-                                         out_cov ? d_cov : nullptr, h->stream, scan_offsets ? hint : 0))
-    return rc;
+  if (int rc = launch(d_begin, d_pts, d_offs, hint, d_pose, out_cov ? d_cov : nullptr, dx, scan_offsets ? hint : 0)) return rc;
   HIP_TRY(hipMemcpyAsync(out_pose, d_pose, b_pose, hipMemcpyDeviceToHost, h->stream));
   if (out_cov) HIP_TRY(hipMemcpyAsync(out_cov, d_cov, b_cov, hipMemcpyDeviceToHost, h->stream));
+  if (sr) {
+    HIP_TRY(hipMemcpyAsync(sr->out_lh, dx, b_lh, hipMemcpyDeviceToHost, h->stream));
+    if (b_res) HIP_TRY(hipMemcpyAsync(sr->out_res, dx + o_res, b_res, hipMemcpyDeviceToHost, h->stream));
+    if (b_idx) HIP_TRY(hipMemcpyAsync(sr->out_index, dx + o_idx, b_idx, hipMemcpyDeviceToHost, h->stream));
+    if (b_bscore) HIP_TRY(hipMemcpyAsync(sr->out_score, dx + o_bscore, b_bscore, hipMemcpyDeviceToHost, h->stream));
+    if (b_bpose) HIP_TRY(hipMemcpyAsync(sr->out_best_pose, dx + o_bpose, b_bpose, hipMemcpyDeviceToHost, h->stream));
+  }
   HIP_TRY(hipStreamSynchronize(h->stream));
   return HSM_OK;
+}
+
+int hsm_match_batch(hsm_ctx* h, int batch, const float* begin_world, const float* pts_xy,
+                    const int* scan_offsets, int shared_n, float* out_pose, float* out_cov) {
+  return match_batch_host(h, batch, begin_world, pts_xy, scan_offsets, shared_n, out_pose, out_cov, nullptr,
+                          "hsm_match_batch: bad argument");
+}
+
+int hsm_match_score_batch(hsm_ctx* h, int batch, const float* begin_world, const float* pts_xy, const int* scan_offsets,
+                          int shared_n, float* out_pose, float* out_cov, int score_level, float* out_likelihood,
+                          float* out_residual, int groups, const int* group_offsets, int group_size, int* out_index,
+                          float* out_score, float* out_best_pose) {
+  const BatchScoreReq sr = {score_level, out_likelihood, out_residual, groups, group_offsets, group_size, out_index, out_score,
+                            out_best_pose};
+  return match_batch_host(h, batch, begin_world, pts_xy, scan_offsets, shared_n, out_pose, out_cov, &sr,
+                          "hsm_match_score_batch: bad argument");
 }
 
 // Largest scan the matcher keeps entirely in registers (16 waves x 64 lanes x 17 beams): such a scan is

@@ -416,6 +416,63 @@ int hsm_likelihood_states(hsm_ctx* h, int level, int batch, const float* states_
  * sum_i (1 - M_i), same arguments as hsm_likelihood_states. */
 int hsm_residual_states(hsm_ctx* h, int level, int batch, const float* states_map, const float* pts_xy, int n,
                         float* out_residual);
+/* ---- scoring and ranking a batch of pose hypotheses on the device (extension: the reference scores one state per call) ----
+ * replaces: OccGridMapUtil::getLikelihoodForState / getResidualForState (HSL/map/OccGridMapUtil.h:184-221) at
+ *           GridMapBase::getMapCoordsPose(pose) (HSL/map/GridMapBase.h:235-239), for B (pose, scan) pairs at once: the
+ *           weighting step behind hsm_match_batch_device.  DEVICE pointers:
+ *   d_poses_world  [B*3] WORLD poses -- what hsm_match_batch_device writes to d_out_pose; converted to the map frame of
+ *                  `level` in the kernel
+ *   d_pts_xy, d_scan_offsets, shared_n   as in hsm_match_batch_device (CSR offsets in points, or NULL = every hypothesis looks
+ *                  at the one scan d_pts_xy[0 .. shared_n); with offsets shared_n is ignored).  Level-0 units, scaled by
+ *                  (float)(1 / 2^level) in the kernel (DataContainer::setFrom)
+ *   d_out_likelihood [B] = 1 - residual / (float)n       d_out_residual [B] = sum_i (1 - M_i); either may be NULL, not both.
+ *                  A scan of 0 beams: residual +0, likelihood NaN (1 - 0/0, as the reference computes it)
+ * HSM_PARITY_AUTO / _EXACT: the residual is summed in the reference's beam order, both outputs are bit-identical to the
+ * reference for every hypothesis.  HSM_PARITY_FAST / _RELAXED: lane-strided partial sums + tree, as hsm_likelihood_states.
+ * hsm_last_launch_parity / hsm_last_launch_kernel ("score_batch_kernel") report the launch.
+ * Ordering, capture and locking: the contract of hsm_match_batch_device, through the same bookkeeping.  Asynchronous on
+ * `stream` (a hipStream_t, NULL = default stream); ordered behind every map update queued on the context so far and the next
+ * update behind it, per caller stream.  Under graph capture the call records one kernel launch and allocates nothing; at
+ * capture time the host waits for the updates queued so far; the caller orders the replays against later updates; while a
+ * stream this context has scored or matched on is being captured, every map update fails with HSM_ERR_INVALID and queues
+ * nothing.  The call needs no workspace and keeps no per-stream or per-context device state.  It does not touch the retained
+ * or the ingested scan.
+ * HSM_ERR_INVALID (nothing launched): NULL context, level out of range, batch < 0, both outputs NULL, shared_n < 0 without
+ * offsets, NULL poses, NULL points for a shared scan of shared_n > 0.  batch == 0: HSM_OK. */
+int hsm_score_batch_device(hsm_ctx* h, int level, int batch, const float* d_poses_world, const float* d_pts_xy,
+                           const int* d_scan_offsets, int shared_n, float* d_out_likelihood, float* d_out_residual,
+                           void* stream);
+/* no reference counterpart: the best hypothesis of every group (one group per physical scan / robot; one group of all
+ * hypotheses is the particle-filter case).  DEVICE pointers:
+ *   d_group_offsets [G+1] CSR offsets into d_scores, or NULL = G groups of group_size consecutive entries
+ *   d_scores        what hsm_score_batch_device wrote (any floats)      d_poses_world [*3] or NULL
+ *   d_out_index [G] index, into the whole score array, of the group's highest score.  A NaN never wins; among equal scores
+ *                   (compared as floats: +0 == -0) the LOWEST index wins; an empty or all-NaN group gives -1
+ *   d_out_score [G] or NULL: that score, NaN for -1
+ *   d_out_pose_world [G*3] or NULL (needs d_poses_world): that hypothesis's pose, copied bit for bit; untouched for -1
+ * The result is a function of the scores alone: the reduction runs on the pair (score, index), uses no atomics and does not
+ * depend on the launch shape.  Reads no map, so it is ordered by `stream` only; asynchronous, allocates nothing, capturable.
+ * HSM_ERR_INVALID: NULL context, groups < 0, NULL d_out_index, group_size < 0 without offsets, NULL scores where there are
+ * entries, d_out_pose_world without d_poses_world.  groups == 0: HSM_OK. */
+int hsm_select_best_device(hsm_ctx* h, int groups, const int* d_group_offsets, int group_size, const float* d_scores,
+                           const float* d_poses_world, int* d_out_index, float* d_out_score, float* d_out_pose_world,
+                           void* stream);
+/* hsm_match_batch_device, then hsm_score_batch_device of its d_out_pose on score_level into d_out_likelihood / d_out_residual,
+ * then -- groups > 0 -- hsm_select_best_device over d_out_likelihood and d_out_pose into d_out_index / d_out_score /
+ * d_out_best_pose: queued on `stream` under ONE lock of the context, no host wait in between; the same bits as the three calls.
+ * All arguments are checked before the first launch (groups > 0 needs d_out_likelihood and d_out_index, and groups * group_size
+ * <= batch without group offsets). */
+int hsm_match_score_batch_device(hsm_ctx* h, int batch, const float* d_begin_world, const float* d_pts_xy,
+                                 const int* d_scan_offsets, int shared_n, float* d_out_pose, float* d_out_cov, int score_level,
+                                 float* d_out_likelihood, float* d_out_residual, int groups, const int* d_group_offsets,
+                                 int group_size, int* d_out_index, float* d_out_score, float* d_out_best_pose, void* stream);
+/* the same with HOST pointers, built like hsm_match_batch (copies in, the chain on the context's stream, copies out;
+ * synchronous).  out_cov, out_residual, out_score and out_best_pose may be NULL; out_best_pose is in/out (a group without a
+ * winner keeps the caller's values); group offsets are checked against batch. */
+int hsm_match_score_batch(hsm_ctx* h, int batch, const float* begin_world, const float* pts_xy, const int* scan_offsets,
+                          int shared_n, float* out_pose, float* out_cov, int score_level, float* out_likelihood,
+                          float* out_residual, int groups, const int* group_offsets, int group_size, int* out_index,
+                          float* out_score, float* out_best_pose);
 /* replaces: OccGridMapUtil::getCovarianceForPose (HSL/map/OccGridMapUtil.h:106-160) and
  * getCovMatrixWorldCoords (:162-188) for `batch` MAP-frame poses of `level`: seven sigma points per pose
  * (x +- 1.5 cells, y +- 1.5 cells, angle +- 0.05 rad, the pose), likelihood-weighted sample covariance.

@@ -200,11 +200,44 @@ public:
                       const std::vector<const DataContainer*>& scans, std::vector<Eigen::Vector3f>& posesOut,
                       std::vector<Eigen::Matrix3f>* covOut = 0)
   {
+    matchBatchImpl(beginEstimatesWorld, scans, posesOut, covOut, -1, 0, 0, 0);
+  }
+
+  // ---- extension: matchDataBatch plus the weighting step -- likelihoodsOut[i] = OccGridMapUtil::getLikelihoodForState at the
+  // matched pose i on `scoreLevel` (NaN for an empty scan) -- and, with groupSize > 0 and bestIndexOut, the winner of every group
+  // of groupSize consecutive hypotheses: the index of its highest likelihood (ties: the lowest index; a NaN never wins; -1 if
+  // the group has none).  One device call (hsm_match_score_batch): the poses do not come back to the host in between.
+  void matchDataBatchScored(const std::vector<Eigen::Vector3f>& beginEstimatesWorld,
+                            const std::vector<const DataContainer*>& scans, std::vector<Eigen::Vector3f>& posesOut,
+                            std::vector<float>& likelihoodsOut, std::vector<Eigen::Matrix3f>* covOut = 0, int scoreLevel = 0,
+                            int groupSize = 0, std::vector<int>* bestIndexOut = 0)
+  {
+    matchBatchImpl(beginEstimatesWorld, scans, posesOut, covOut, scoreLevel, &likelihoodsOut, groupSize, bestIndexOut);
+  }
+
+  hsm_ctx* getDeviceContext() { return ctx; }
+
+protected:
+  // scoreLevel < 0: hsm_match_batch; else hsm_match_score_batch
+  void matchBatchImpl(const std::vector<Eigen::Vector3f>& beginEstimatesWorld,
+                      const std::vector<const DataContainer*>& scans, std::vector<Eigen::Vector3f>& posesOut,
+                      std::vector<Eigen::Matrix3f>* covOut, int scoreLevel, std::vector<float>* likelihoodsOut, int groupSize,
+                      std::vector<int>* bestIndexOut)
+  {
     const int B = static_cast<int>(beginEstimatesWorld.size());
     posesOut.resize(B);
+    const int groups = (scoreLevel >= 0 && bestIndexOut && groupSize > 0) ? B / groupSize : 0;
+    if (likelihoodsOut) {
+      likelihoodsOut->assign(static_cast<size_t>(B), 0.0f);
+    }
+    if (bestIndexOut) {
+      bestIndexOut->assign(static_cast<size_t>(groups), -1);
+    }
     if (B == 0) {
       return;
     }
+    float* lh = likelihoodsOut ? &(*likelihoodsOut)[0] : 0;
+    int* best = groups > 0 ? &(*bestIndexOut)[0] : 0;
     std::vector<float> begin(3 * static_cast<size_t>(B)), pose(3 * static_cast<size_t>(B)), cov;
     bool shared = true;  // every hypothesis looks at the same container: the particle-filter case
     for (int i = 0; i < B; ++i) {
@@ -226,7 +259,12 @@ public:
         pts[2 * static_cast<size_t>(j)] = p[0];
         pts[2 * static_cast<size_t>(j) + 1] = p[1];
       }
-      hsm_match_batch(ctx, B, &begin[0], pts.empty() ? 0 : &pts[0], 0, n, &pose[0], covOut ? &cov[0] : 0);
+      if (scoreLevel < 0) {
+        hsm_match_batch(ctx, B, &begin[0], pts.empty() ? 0 : &pts[0], 0, n, &pose[0], covOut ? &cov[0] : 0);
+      } else {
+        hsm_match_score_batch(ctx, B, &begin[0], pts.empty() ? 0 : &pts[0], 0, n, &pose[0], covOut ? &cov[0] : 0, scoreLevel, lh,
+                              0, groups, 0, groupSize, best, 0, 0);
+      }
     } else {
       std::vector<int> offsets(static_cast<size_t>(B) + 1, 0);
       for (int i = 0; i < B; ++i) {
@@ -241,7 +279,12 @@ public:
           pts[2 * (static_cast<size_t>(offsets[i]) + j) + 1] = p[1];
         }
       }
-      hsm_match_batch(ctx, B, &begin[0], pts.empty() ? 0 : &pts[0], &offsets[0], 0, &pose[0], covOut ? &cov[0] : 0);
+      if (scoreLevel < 0) {
+        hsm_match_batch(ctx, B, &begin[0], pts.empty() ? 0 : &pts[0], &offsets[0], 0, &pose[0], covOut ? &cov[0] : 0);
+      } else {
+        hsm_match_score_batch(ctx, B, &begin[0], pts.empty() ? 0 : &pts[0], &offsets[0], 0, &pose[0], covOut ? &cov[0] : 0,
+                              scoreLevel, lh, 0, groups, 0, groupSize, best, 0, 0);
+      }
     }
     for (int i = 0; i < B; ++i) {
       posesOut[i] = Eigen::Vector3f(pose[3 * i], pose[3 * i + 1], pose[3 * i + 2]);
@@ -258,9 +301,6 @@ public:
     }
   }
 
-  hsm_ctx* getDeviceContext() { return ctx; }
-
-protected:
   // bring the host mirror of `level` up to date: fetch-and-clear the union of the cell boxes the updates
   // touched since the last refresh, download it as the reference's AoS
   // cells, and bump the update counter like OccGridMapBase::updateByScan does (OccGridMapBase.h:164)
