@@ -68,6 +68,8 @@ SIGNATURES = {
     "hsm_match_batch": (_i, [_vp, _i, _f32p, _vp, _vp, _i, _f32p, _vp]),
     "hsm_update_by_scan": (_i, [_vp, _f32p, _vp, _i, _f32p]),
     "hsm_update_by_scan_level": (_i, [_vp, _i, _f32p, _vp, _i, _f32p]),
+    "hsm_update_by_scans_device": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "hsm_update_by_scans": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp]),
     "hsm_ingest_laser_scan": (_i, [_vp, _vp, _i, _f, _f, _f, _f, _f, _vp, C.POINTER(_i)]),
     "hsm_ingest_point_cloud": (_i, [_vp, _vp, _i, _vp, _f, _f, _f, _f, _f, _vp, C.POINTER(_i), _vp]),
     "hsm_ingest_laser_scan_tf": (_i, [_vp, _vp, _i, _f, _f, _f, _f, C.c_double, _vp, _f, _f, _f, _f, _f, _vp,
@@ -559,6 +561,23 @@ class MapRepMultiMap:
             self._h, batch, d_begin or None, d_pts or None, d_offsets or None, shared_n, d_out_pose or None, d_out_cov or None,
             score_level, d_out_likelihood or None, d_out_residual or None, groups, d_group_offsets or None, group_size,
             d_out_index or None, d_out_score or None, d_out_best_pose or None, stream or None), "hsm_match_score_batch_device")
+
+    def update_by_scans_device(self, count, d_poses_world, d_pts, d_offsets, shared_n, max_beams=0, origo=None, stream=0):
+        """Raw device pointers (ints): integrate ``count`` posed scans in order, queued on the context's stream behind what
+        ``stream`` holds now.  No host wait, no download: the poses may be a batched matcher's output."""
+        o = None if origo is None else _v(origo, 2)
+        _check(self._lib.hsm_update_by_scans_device(self._h, count, d_poses_world or None, d_pts or None, d_offsets or None,
+                                                    shared_n, max_beams, None if o is None else o.ctypes.data, stream or None),
+               "hsm_update_by_scans_device")
+
+    def update_by_scans(self, poses_world, pts, offsets=None, origo=None):
+        """Host arrays: a map from a log of posed scans in one call.  ``offsets`` None = every pose integrates the one scan ``pts``."""
+        w = np.ascontiguousarray(poses_world, np.float32).reshape(-1, 3)
+        a, p, n = _pts(pts)
+        offs = None if offsets is None else np.ascontiguousarray(offsets, np.int32)
+        o = None if origo is None else _v(origo, 2)
+        _check(self._lib.hsm_update_by_scans(self._h, w.shape[0], w.ctypes.data, p, None if offs is None else offs.ctypes.data,
+                                             n if offs is None else 0, None if o is None else o.ctypes.data), "hsm_update_by_scans")
 
     def score_batch(self, level, poses_world, pts, offsets=None):
         """(likelihood, residual) of WORLD poses on ``level``; ``offsets`` None = every pose against the one scan ``pts``.

@@ -728,6 +728,68 @@ int order_after_foreign_match(hsm_ctx* h) {
   return HSM_OK;
 }
 
+// Device-side updates (hsm_update_by_scans_device) leave their cell boxes on the device: the host never sees their poses.  Whoever
+// needs Level::bbox / Level::dirty -- the box getters, and every host-side writer of them -- first waits for the context's stream
+// and merges slot 0 (the running dirty boxes) and slot 1 (the last scan's boxes) of d_upd_boxes: one 256-byte copy.  Callers test
+// upd_boxes_outstanding themselves, so a context that never took a device-side update pays one branch.
+int merge_device_boxes(hsm_ctx* h) {
+  if (int rc = select_device(h)) return rc;
+  int host[2 * kMaxLevels * 4];
+  HIP_TRY(hipMemcpyAsync(host, h->d_upd_boxes, sizeof host, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  hipLaunchKernelGGL(update_boxes_clear_kernel, dim3(1), dim3(64), 0, h->stream, h->d_upd_boxes, kMaxLevels);
+  HIP_TRY(hipGetLastError());
+  for (size_t l = 0; l < h->levels.size(); ++l) {
+    Level& L = h->levels[l];
+    const int* run = host + 4 * l;
+    const int* last = host + 4 * (kMaxLevels + l);
+    if (last[2] >= last[0]) {
+      for (int k = 0; k < 4; ++k) L.bbox[k] = last[k];
+    } else {
+      L.bbox[0] = L.bbox[1] = 0;
+      L.bbox[2] = L.bbox[3] = -1;
+    }
+    if (run[2] < run[0]) continue;
+    if (L.dirty[2] < L.dirty[0]) {
+      for (int k = 0; k < 4; ++k) L.dirty[k] = run[k];
+    } else {
+      if (run[0] < L.dirty[0]) L.dirty[0] = run[0];
+      if (run[1] < L.dirty[1]) L.dirty[1] = run[1];
+      if (run[2] > L.dirty[2]) L.dirty[2] = run[2];
+      if (run[3] > L.dirty[3]) L.dirty[3] = run[3];
+    }
+  }
+  h->upd_boxes_outstanding = false;
+  return HSM_OK;
+}
+
+// the UpdateBatch blocks and cell boxes of `count` scans (hsm_ctx::d_upd_batches / d_upd_boxes)
+int ensure_update_scans(hsm_ctx* h, size_t count) {
+  if (h->d_upd_boxes && count <= h->upd_scans_cap) return HSM_OK;
+  if (h->upd_boxes_outstanding)  // the running boxes live in the block that is about to go
+    if (int rc = merge_device_boxes(h)) return rc;
+  if (h->d_upd_batches) HIP_TRY(hipFree(h->d_upd_batches));  // (frees wait for the queued work that still reads the old blocks)
+  if (h->d_upd_boxes) HIP_TRY(hipFree(h->d_upd_boxes));
+  h->d_upd_batches = nullptr;
+  h->d_upd_boxes = nullptr;
+  h->upd_scans_cap = 0;
+  const size_t want = count < 64 ? 64 : count + count / 2;
+  HIP_TRY(hipMalloc((void**)&h->d_upd_batches, want * sizeof(UpdateBatch)));
+  HIP_TRY(hipMalloc((void**)&h->d_upd_boxes, (want + 2) * kMaxLevels * 4 * sizeof(int)));
+  hipLaunchKernelGGL(update_boxes_clear_kernel, dim3(1), dim3(64), 0, h->stream, h->d_upd_boxes, 2 * kMaxLevels);
+  HIP_TRY(hipGetLastError());
+  h->upd_scans_cap = want;
+  return HSM_OK;
+}
+
+// the key planes of a whole level back to zero: the key generation of a device-side update wrapped.  The WHOLE level, not the
+// rows that carry keys: those rows are known on the device only, and a wrap is one scan in 4095.
+int clear_key_planes(hsm_ctx* h, Level& L) {
+  HIP_TRY(hipMemsetAsync(L.d_key_occ, 0, L.cells() * sizeof(unsigned int), h->stream));
+  HIP_TRY(hipMemsetAsync(L.d_key_free, 0, key_free_cells(L.sx, L.sy) * sizeof(unsigned int), h->stream));
+  return HSM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -933,6 +995,10 @@ void hsm_destroy(hsm_ctx* h) {
   if (h->h_scan_pinned) TEARDOWN(log, hipHostFree(h->h_scan_pinned));
   if (h->evt_updates) TEARDOWN(log, hipEventDestroy(h->evt_updates));
   if (h->evt_foreign) TEARDOWN(log, hipEventDestroy(h->evt_foreign));
+  if (h->evt_inputs) TEARDOWN(log, hipEventDestroy(h->evt_inputs));
+  TEARDOWN(log, hipFree(h->d_upd_batches));
+  TEARDOWN(log, hipFree(h->d_upd_boxes));
+  TEARDOWN(log, hipFree(h->d_upd_stage));
   if (h->h_small) TEARDOWN(log, hipHostFree(h->h_small));
   for (int k = 0; k < 2; ++k) {
     if (h->h_upd_pinned[k]) TEARDOWN(log, hipHostFree(h->h_upd_pinned[k]));
@@ -950,6 +1016,8 @@ int hsm_reset(hsm_ctx* h) {
   if (!h) return fail(HSM_ERR_INVALID, "null context");
   std::lock_guard<std::mutex> lk(h->mu);
   if (int rc = select_device(h)) return rc;
+  if (h->upd_boxes_outstanding)
+    if (int rc = merge_device_boxes(h)) return rc;
   if (int rc = order_after_foreign_match(h)) return rc;
   for (Level& L : h->levels) {
     if (int rc = fill_level(h, L)) return rc;
@@ -1742,6 +1810,8 @@ int hsm_update_by_scan(hsm_ctx* h, const float pose_world[3], const float* pts_x
 static int update_impl(hsm_ctx* h, const float pose_world[3], const float* pts_xy, int n, const float origo[2],
                        const float2* d_prestaged) {
   if (int rc = select_device(h)) return rc;
+  if (h->upd_boxes_outstanding)  // this update rewrites Level::bbox: the boxes of device-side updates go in first
+    if (int rc = merge_device_boxes(h)) return rc;
   if (int rc = order_after_foreign_match(h)) return rc;
   const float zero[2] = {0.0f, 0.0f};
   const float* o = origo ? origo : zero;
@@ -1859,6 +1929,8 @@ int hsm_update_by_scan_level(hsm_ctx* h, int level, const float pose_world[3], c
     return fail(HSM_ERR_INVALID, "hsm_update_by_scan_level: bad argument");
   std::lock_guard<std::mutex> lk(h->mu);
   if (int rc = select_device(h)) return rc;
+  if (h->upd_boxes_outstanding)
+    if (int rc = merge_device_boxes(h)) return rc;
   if (int rc = order_after_foreign_match(h)) return rc;
   const float zero[2] = {0.0f, 0.0f};
   if (int rc = ensure_scan_capacity(h->d_scan, h->d_scan_cap, (size_t)n)) return rc;
@@ -1876,6 +1948,159 @@ int hsm_update_by_scan_level(hsm_ctx* h, int level, const float pose_world[3], c
   update_applied(h, batch, prep);
   HIP_TRY(hipStreamSynchronize(h->stream));
   return HSM_OK;
+}
+
+// `count` posed scans that are on the device, integrated in order by stream-ordered launches only: one update_prep_kernel, then
+// a mark and an apply launch per scan (map_update.h "posed scans that are already on the device").  The host supplies what it can
+// compute without the poses: per level the counters and the key generation before the call, from which scan k's follow.
+static int update_by_scans_device_nolock(hsm_ctx* h, int count, const float* d_poses_world, const float* d_pts_xy,
+                                         const int* d_scan_offsets, int shared_n, int max_beams, const float origo[2],
+                                         hipStream_t stream) {
+  if (count < 0 || max_beams < 0 || (count > 0 && !d_poses_world) || (!d_scan_offsets && shared_n < 0) ||
+      (count > 0 && !d_scan_offsets && shared_n > 0 && !d_pts_xy))
+    return fail(HSM_ERR_INVALID, "hsm_update_by_scans_device: bad argument");
+  if (!d_scan_offsets && shared_n > HSM_MAX_UPDATE_BEAMS)
+    return fail(HSM_ERR_TOO_LARGE, "hsm_update_by_scans_device: more than HSM_MAX_UPDATE_BEAMS beams");
+  if (count == 0) return HSM_OK;
+  if (int rc = select_device(h)) return rc;
+  // the rule of every map update: refused, before anything is queued, while a stream this call would touch is being captured
+  if (stream_capturing(stream))
+    return fail(HSM_ERR_INVALID, "hsm_update_by_scans_device: `stream` is being captured into a graph (map updates are not captured)");
+  if (int rc = order_after_foreign_match(h)) return rc;  // (refuses the same way for the streams this context has matched on)
+  if (int rc = ensure_update_scans(h, (size_t)count)) return rc;
+  if (stream != h->stream) {  // the inputs are complete where the caller's stream stands now
+    if (!h->evt_inputs) HIP_TRY(hipEventCreateWithFlags(&h->evt_inputs, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(h->evt_inputs, stream));
+    HIP_TRY(hipStreamWaitEvent(h->stream, h->evt_inputs, 0));
+  }
+  const int nlev = (int)h->levels.size();
+  UpdatePrepParams A;
+  memset(&A, 0, sizeof A);
+  A.nlev = nlev;
+  A.count = count;
+  A.poses_world = d_poses_world;
+  A.pts = reinterpret_cast<const float2*>(d_pts_xy);
+  A.offsets = d_scan_offsets;
+  A.shared_n = shared_n;
+  A.out = h->d_upd_batches;
+  A.boxes = h->d_upd_boxes;
+  size_t max_cells = 0;
+  for (int l = 0; l < nlev; ++l) {
+    Level& L = h->levels[l];
+    if (L.marks_pending)
+      if (int rc = scrub_marks(h, L)) return rc;
+    UpdatePrepLevel& V = A.lv[l];
+    const float factor = (float)(1.0 / pow(2.0, (double)l));
+    V.lv = level_rw(L);
+    V.mapTworld = L.mapTworld;
+    V.pt_scale = factor;
+    V.origo_x = l == 0 ? (origo ? origo[0] : 0.0f) : (origo ? origo[0] : 0.0f) * factor;  // setFrom, DataPointContainer.h:48
+    V.origo_y = l == 0 ? (origo ? origo[1] : 0.0f) : (origo ? origo[1] : 0.0f) * factor;
+    V.log_odds_free = L.log_odds_free;
+    V.log_odds_occ = L.log_odds_occ;
+    V.serial0 = L.serial;
+    V.update_index0 = L.curr_update_index;
+    if (L.cells() > max_cells) max_cells = L.cells();
+  }
+  hipLaunchKernelGGL(update_prep_kernel, dim3((unsigned)count), dim3(64), 0, h->stream, A);
+  HIP_TRY(hipGetLastError());
+  // launch shapes from the hint alone: the mark grid strides over the scan's real beam count, the apply grid over the scan's
+  // box -- sized for the whole level, its blocks return after one scalar load where the box is empty or small
+  const int hint = max_beams > 0 ? max_beams : 1081;
+  const unsigned occ_blocks = (unsigned)((hint + 255) / 256), free_blocks = (unsigned)((hint + 3) / 4);
+  const unsigned apply_blocks = (unsigned)grid_for(max_cells);
+  const bool scatter = h->layout == kLayoutQuad;
+  for (int l = 0; l < nlev; ++l) h->levels[l].marks_pending = true;  // until every apply pass is queued (scrub_marks)
+  for (int k = 0; k < count; ++k) {
+    for (int l = 0; l < nlev; ++l) {
+      Level& L = h->levels[l];
+      // The key generation advances once per scan and level, empty scan or not (the host cannot see n_k; a generation spent on
+      // an empty scan is harmless).  Where it wraps, the key planes are cleared between the two scans concerned.
+      if (L.serial == kSerialMax) {
+        if (int rc = clear_key_planes(h, L)) return rc;
+        L.serial = 0;
+      }
+      ++L.serial;
+    }
+    int* scan_boxes = h->d_upd_boxes + (size_t)update_box_slot(k, count) * kMaxLevels * 4;
+    hipLaunchKernelGGL(update_mark_scan_kernel, dim3(occ_blocks + free_blocks, (unsigned)nlev), dim3(256), 0, h->stream,
+                       h->d_upd_batches + k, occ_blocks, scan_boxes, h->d_upd_boxes);
+    if (scatter)
+      hipLaunchKernelGGL(update_apply_scan_kernel<true>, dim3(apply_blocks, (unsigned)nlev), dim3(256), 0, h->stream,
+                         h->d_upd_batches + k, scan_boxes);
+    else
+      hipLaunchKernelGGL(update_apply_scan_kernel<false>, dim3(apply_blocks, (unsigned)nlev), dim3(256), 0, h->stream,
+                         h->d_upd_batches + k, scan_boxes);
+    HIP_TRY(hipGetLastError());
+  }
+  for (int l = 0; l < nlev; ++l) {
+    Level& L = h->levels[l];
+    L.marks_pending = false;
+    // OccGridMapBase.h:123-124, :167 and setUpdated() (GridMapBase.h:343), `count` times: an empty container counts, too
+    L.curr_mark_free = L.curr_update_index + 3 * (count - 1) + 1;
+    L.curr_mark_occ = L.curr_update_index + 3 * (count - 1) + 2;
+    L.curr_update_index += 3 * count;
+    L.last_update_index += count;
+    L.key_rows[0] = 0;  // which rows carry keys of this generation is known on the device only: the next wrap of a host-side
+    L.key_rows[1] = L.sy - 1;  // update clears the whole level
+  }
+  h->upd_boxes_outstanding = true;
+  h->queued_update = h->async_update;
+  if (!h->async_update) HIP_TRY(hipStreamSynchronize(h->stream));
+  return HSM_OK;
+}
+
+int hsm_update_by_scans_device(hsm_ctx* h, int count, const float* d_poses_world, const float* d_pts_xy,
+                               const int* d_scan_offsets, int shared_n, int max_beams, const float origo[2], void* stream) {
+  if (!h) return fail(HSM_ERR_INVALID, "null context");
+  std::lock_guard<std::mutex> lk(h->mu);
+  return update_by_scans_device_nolock(h, count, d_poses_world, d_pts_xy, d_scan_offsets, shared_n, max_beams, origo,
+                                       static_cast<hipStream_t>(stream));
+}
+
+int hsm_update_by_scans(hsm_ctx* h, int count, const float* poses_world, const float* pts_xy, const int* scan_offsets,
+                        int shared_n, const float origo[2]) {
+  if (!h) return fail(HSM_ERR_INVALID, "null context");
+  if (count < 0 || (count > 0 && !poses_world) || (!scan_offsets && shared_n < 0))
+    return fail(HSM_ERR_INVALID, "hsm_update_by_scans: bad argument");
+  if (count == 0) return HSM_OK;
+  size_t total = scan_offsets ? 0 : (size_t)shared_n;
+  int longest = scan_offsets ? 0 : shared_n;
+  if (scan_offsets) {
+    for (int k = 0; k < count; ++k) {
+      if (scan_offsets[k] < 0 || scan_offsets[k + 1] < scan_offsets[k])
+        return fail(HSM_ERR_INVALID, "hsm_update_by_scans: scan_offsets must start at >= 0 and not decrease");
+      if (scan_offsets[k + 1] - scan_offsets[k] > longest) longest = scan_offsets[k + 1] - scan_offsets[k];
+    }
+    total = (size_t)scan_offsets[count];
+  }
+  if (total > 0 && !pts_xy) return fail(HSM_ERR_INVALID, "hsm_update_by_scans: pts_xy is null");
+  if (longest > HSM_MAX_UPDATE_BEAMS) return fail(HSM_ERR_TOO_LARGE, "hsm_update_by_scans: more than HSM_MAX_UPDATE_BEAMS beams");
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (int rc = select_device(h)) return rc;
+  for (const hsm_ctx::ForeignStream& f : h->foreign)  // refused before the copies are queued (order_after_foreign_match)
+    if (stream_capturing(f.s))
+      return fail(HSM_ERR_INVALID, "hsm_update_by_scans: a caller's stream that this context matches on is being captured into a graph");
+  // one staging block: end points | poses | offsets (the copies are queued on the context's stream, in front of the update)
+  const size_t pts_bytes = (total * sizeof(float2) + 255) & ~(size_t)255, pose_bytes = ((size_t)count * 3 * sizeof(float) + 255) & ~(size_t)255;
+  const size_t need = pts_bytes + pose_bytes + ((size_t)count + 1) * sizeof(int);
+  if (need > h->d_upd_stage_cap) {
+    if (h->d_upd_stage) HIP_TRY(hipFree(h->d_upd_stage));
+    h->d_upd_stage = nullptr;
+    h->d_upd_stage_cap = 0;
+    HIP_TRY(hipMalloc(&h->d_upd_stage, need + need / 2));
+    h->d_upd_stage_cap = need + need / 2;
+  }
+  char* base = static_cast<char*>(h->d_upd_stage);
+  float* d_pts = reinterpret_cast<float*>(base);
+  float* d_poses = reinterpret_cast<float*>(base + pts_bytes);
+  int* d_offs = reinterpret_cast<int*>(base + pts_bytes + pose_bytes);
+  if (total > 0) HIP_TRY(hipMemcpyAsync(d_pts, pts_xy, total * sizeof(float2), hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(d_poses, poses_world, (size_t)count * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  if (scan_offsets)
+    HIP_TRY(hipMemcpyAsync(d_offs, scan_offsets, ((size_t)count + 1) * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  return update_by_scans_device_nolock(h, count, d_poses, d_pts, scan_offsets ? d_offs : nullptr, shared_n, longest, origo,
+                                       h->stream);
 }
 
 // device buffers of the ingestion entries: raw input (3 floats per element covers ranges and Point32
@@ -2983,6 +3208,8 @@ int hsm_upload_level(hsm_ctx* h, int level, const float* logodds, const int* upd
   std::lock_guard<std::mutex> lk(h->mu);
   if (int rc = select_device(h)) return rc;
   Level& L = h->levels[level];
+  if (h->upd_boxes_outstanding)
+    if (int rc = merge_device_boxes(h)) return rc;
   if (int rc = order_after_foreign_match(h)) return rc;
   HIP_TRY(hipStreamSynchronize(h->stream));
   if (logodds) HIP_TRY(hipMemcpy(L.d_logodds, logodds, L.cells() * sizeof(float), hipMemcpyHostToDevice));
@@ -3033,6 +3260,12 @@ int hsm_download_cells(hsm_ctx* h, int level, int x0, int y0, int x1, int y1, vo
 }
 int hsm_last_update_bbox(const hsm_ctx* h, int level, int bbox[4]) {
   if (int rc = valid_level(h, level)) return rc;
+  if (h->upd_boxes_outstanding) {  // a device-side update since the last look: wait for it and fetch its boxes
+    hsm_ctx* m = const_cast<hsm_ctx*>(h);
+    std::lock_guard<std::mutex> lk(m->mu);
+    if (m->upd_boxes_outstanding)
+      if (int rc = merge_device_boxes(m)) return rc;
+  }
   for (int i = 0; i < 4; ++i) bbox[i] = h->levels[level].bbox[i];
   return HSM_OK;
 }
@@ -3040,6 +3273,8 @@ int hsm_take_dirty_bbox(hsm_ctx* h, int level, int bbox[4]) {
   if (int rc = valid_level(h, level)) return rc;
   if (!bbox) return fail(HSM_ERR_INVALID, "hsm_take_dirty_bbox: bbox is null");
   std::lock_guard<std::mutex> lk(h->mu);
+  if (h->upd_boxes_outstanding)
+    if (int rc = merge_device_boxes(h)) return rc;
   Level& L = h->levels[level];
   for (int i = 0; i < 4; ++i) bbox[i] = L.dirty[i];
   L.dirty[0] = L.dirty[1] = 0;

@@ -17,6 +17,7 @@
 
 namespace hsm {
 struct BeamRec;  // map_update.h (its kernels are not templates: only hector_mi355.hip includes that header)
+struct UpdateBatch;
 }
 
 namespace hsm_host {
@@ -83,6 +84,7 @@ inline bool stream_capturing(hipStream_t s) {
 
 using hsm_host::Level;
 using hsm::BeamRec;
+using hsm::UpdateBatch;
 using hsm::SpecStats;
 using hsm::kLayoutQuad;
 
@@ -110,6 +112,15 @@ struct hsm_ctx {
   int scatter_texels_max = 1 << 30; // quad layout: scans below this write the texels from the apply pass (env HSM_SCATTER_TEXELS_MAX, 0 = never)
   BeamRec* d_beam_recs = nullptr;   // dense scans: per-beam records of all levels (map_update.h BeamRec), [levels][cap]
   size_t beam_recs_cap = 0;         // beams per level
+  // hsm_update_by_scans_device: one UpdateBatch and one cell box per level for every scan of a call, filled on the device
+  // (map_update.h update_prep_kernel); grown outside capture.  boxes: slot 0 the levels' running dirty boxes, slot 1 the last scan's
+  UpdateBatch* d_upd_batches = nullptr;
+  int* d_upd_boxes = nullptr;
+  size_t upd_scans_cap = 0;
+  bool upd_boxes_outstanding = false;  // device-side updates since the host last merged their boxes into Level::bbox / dirty
+  hipEvent_t evt_inputs = nullptr;     // the caller's stream at hsm_update_by_scans_device: its inputs are complete
+  void* d_upd_stage = nullptr;         // hsm_update_by_scans: poses, offsets and end points of the host arrays
+  size_t d_upd_stage_cap = 0;
   float2* h_upd_pinned[2] = {nullptr, nullptr};
   size_t h_upd_cap[2] = {0, 0};
   hipEvent_t upd_evt[2] = {nullptr, nullptr};

@@ -414,15 +414,16 @@ __global__ void __launch_bounds__(256) update_mark_kernel(const UpdateBatch B, u
 // corner of -- component 0 of texel (x,y), 1 of (x-1,y), 2 of (x,y-1), 3 of (x-1,y-1), with update_texels_kernel's
 // edge replication at the last column / row -- so the texel pass and its launch disappear.  Every texel component
 // has exactly one writer (the thread of its cell), untouched components keep their value: same bits as the rebuild.
+// The body of update_apply_kernel and of update_apply_scan_kernel; grid-stride: `first` is this thread's first cell of the
+// box, `stride` the number of threads in the grid (computed by the kernels, where blockDim is a compile-time-uniform read).
 template <bool SCATTER_TEXELS>
-__global__ void __launch_bounds__(256) update_apply_kernel(const UpdateBatch B) {
-  const UpdateParams& P = B.lv[blockIdx.y];
+__device__ __forceinline__ void apply_box(const UpdateParams& P, size_t first, size_t stride) {
   if (P.x1 < P.x0) return;  // this level has nothing to apply
   const bool aligned = (P.lv.sx & 63) == 0;
   const int bx0 = aligned ? (P.x0 & ~63) : P.x0;
   const int w = aligned ? ((P.x1 | 63) - bx0 + 1) : (P.x1 - P.x0 + 1), h = P.y1 - P.y0 + 1;
   const size_t n = (size_t)w * h;
-  for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < n; t += (size_t)gridDim.x * blockDim.x) {
+  for (size_t t = first; t < n; t += stride) {
     const int x = bx0 + (int)(t % (size_t)w), y = P.y0 + (int)(t / (size_t)w);
     const size_t c = (size_t)y * P.lv.sx + x;
     const unsigned int kf = P.lv.key_free[key_free_index(P.lv, (unsigned int)x, (unsigned int)y)];
@@ -476,6 +477,11 @@ __global__ void __launch_bounds__(256) update_apply_kernel(const UpdateBatch B) 
       if (lastx && lasty) put(x, y, 3);
     }
   }
+}
+
+template <bool SCATTER_TEXELS>
+__global__ void __launch_bounds__(256) update_apply_kernel(const UpdateBatch B) {
+  apply_box<SCATTER_TEXELS>(B.lv[blockIdx.y], blockIdx.x * (size_t)blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x);
 }
 
 
@@ -942,6 +948,191 @@ __global__ void __launch_bounds__(256) update_texels_kernel(const UpdateBatch B)
         make_float4(p[(size_t)y * P.lv.sx + x], p[(size_t)y * P.lv.sx + xn], p[(size_t)yn * P.lv.sx + x],
                     p[(size_t)yn * P.lv.sx + xn]);
   }
+}
+
+// ---- posed scans that are already on the device (hsm_update_by_scans_device) ---------------------------------------------
+// The host knows neither a scan's pose nor its length, so everything prepare_level() / level_bbox() derive from them on the
+// host is derived here:
+//   update_prep_kernel        one launch per call, one wavefront per scan (lane = level): scan k's UpdateBatch, in a
+//                             context-owned device array, from d_poses_world[k] -- the fp32 expressions of prepare_level()
+//   update_mark_scan_kernel   update_mark_kernel's two block kinds on that UpdateBatch, read through a pointer (wave-uniform
+//                             address: scalar loads); the grid is sized by the caller's hint and strides over the scan's real
+//                             beam count.  Its end-cell blocks also reduce the scan's cell box (DPP min / max per wavefront,
+//                             one lane's atomicMin / atomicMax) into the scan's box and the level's running dirty box.
+//   update_apply_scan_kernel  apply_box() over that box, in a grid sized for the whole level (the host cannot size it by a
+//                             box it never sees); a later launch on the same stream, so the box is complete.
+// Keyed form for every scan length (correct for any length; the byte-map form needs per-beam records sized by the host).
+//
+// A cell box on the device: {x0, y0, x1, y1}, inclusive; empty = {INT_MAX, INT_MAX, -1, -1}, the identity of the atomics.
+constexpr int kBoxEmptyLo = 0x7fffffff, kBoxEmptyHi = -1;
+
+struct UpdatePrepLevel {
+  LevelRW lv;
+  Affine2 mapTworld;
+  float pt_scale;                 // 2^-level: DataContainer::setFrom (DataPointContainer.h:46-58)
+  float origo_x, origo_y;         // the container's origo on this level (setFrom :48)
+  float log_odds_free, log_odds_occ;
+  unsigned int serial0;           // the level's key generation before the call: scan k takes ((serial0 + k) % kSerialMax) + 1
+  int update_index0;              // currUpdateIndex before the call: scan k marks with update_index0 + 3 k + 1 / + 2
+};
+
+struct UpdatePrepParams {
+  UpdatePrepLevel lv[kMaxLevels];
+  int nlev, count;
+  const float* poses_world;  // [count * 3]
+  const float2* pts;
+  const int* offsets;        // [count + 1] CSR offsets in points, or nullptr: every pose integrates pts[0 .. shared_n)
+  int shared_n;
+  UpdateBatch* out;          // [count]
+  int* boxes;                // [(count + 2) * kMaxLevels * 4]: slot 0 the running dirty boxes, slot 1 the LAST scan's, 2 + k scan k's
+};
+
+// the box slot of scan k of a call of `count` scans (the last scan's sits where the host finds it without knowing count)
+__host__ __device__ __forceinline__ int update_box_slot(int k, int count) { return k == count - 1 ? 1 : 2 + k; }
+
+__global__ void __launch_bounds__(64) update_prep_kernel(const UpdatePrepParams A) {
+  const int k = blockIdx.x, l = threadIdx.x;
+  if (l >= A.nlev) return;
+  const UpdatePrepLevel& V = A.lv[l];
+  UpdateParams P;
+  P.lv = V.lv;
+  const float px = A.poses_world[3 * k], py = A.poses_world[3 * k + 1], th = A.poses_world[3 * k + 2];
+  float mx, my;
+  affine_apply(V.mapTworld, px, py, mx, my);  // getMapCoordsPose
+  // Translation2f(mapPose.xy) * Rotation2Df(mapPose.theta): glibc's sinf / cosf (the pair sincosf returns, libm_exact.h)
+  float sinA, cosA;
+  libm::sincosf_glibc<false>(th, sinA, cosA);
+  P.pose.l00 = cosA;
+  P.pose.l01 = -sinA;
+  P.pose.l10 = sinA;
+  P.pose.l11 = cosA;
+  P.pose.t0 = mx;
+  P.pose.t1 = my;
+  float bx, by;
+  affine_apply(P.pose, V.origo_x, V.origo_y, bx, by);
+  bx += 0.5f;
+  by += 0.5f;
+  // x86's truncating conversion makes a NaN or out-of-range begin coordinate INT_MIN, which fails the map test of every beam;
+  // this device's makes a NaN 0, a VALID cell.  beam_line()'s finite-range test, applied to the begin cell: what it rejects is
+  // outside the map in the reference too, and (-1, -1) drops every beam the same way.
+  const bool finite = bx > -2.0f && bx < (float)V.lv.sx + 2.0f && by > -2.0f && by < (float)V.lv.sy + 2.0f;
+  P.bx = finite ? (int)bx : -1;
+  P.by = finite ? (int)by : -1;
+  int first = 0, n = A.shared_n;
+  if (A.offsets) {
+    first = A.offsets[k];
+    n = A.offsets[k + 1] - first;
+  }
+  if (n < 0 || n > (int)kBeamMask) n = 0;  // (more beams than the key's index field holds: integrated as an empty scan)
+  P.pts = A.pts + first;
+  P.n = n;
+  P.pt_scale = V.pt_scale;
+  P.serial = (V.serial0 + (unsigned int)k) % kSerialMax + 1u;
+  P.log_odds_free = V.log_odds_free;
+  P.log_odds_occ = V.log_odds_occ;
+  P.mark_free = V.update_index0 + 3 * k + 1;  // currMarkFreeIndex / currMarkOccIndex, OccGridMapBase.h:123-124
+  P.mark_occ = V.update_index0 + 3 * k + 2;
+  P.x0 = P.y0 = kBoxEmptyLo;  // (the passes take the box from A.boxes)
+  P.x1 = P.y1 = kBoxEmptyHi;
+  P.recs = nullptr;
+  UpdateBatch& B = A.out[k];
+  B.lv[l] = P;
+  if (l == 0) B.nlev = A.nlev;
+  int* box = A.boxes + ((size_t)update_box_slot(k, A.count) * kMaxLevels + l) * 4;
+  box[0] = box[1] = kBoxEmptyLo;
+  box[2] = box[3] = kBoxEmptyHi;
+}
+
+template <int CTRL>
+__device__ __forceinline__ int dpp_i32(int v) {
+  return __builtin_amdgcn_update_dpp(v, v, CTRL, 0xf, 0xf, false);
+}
+// min / max over the wavefront, in every lane (all 64 lanes active): the 16-lane rows by DPP, the four rows by readlane
+__device__ __forceinline__ int wave_min_i32(int v) {
+  v = min(v, dpp_i32<0xB1>(v));   // quad_perm [1,0,3,2]
+  v = min(v, dpp_i32<0x4E>(v));   // quad_perm [2,3,0,1]
+  v = min(v, dpp_i32<0x141>(v));  // row_half_mirror
+  v = min(v, dpp_i32<0x140>(v));  // row_mirror
+  return min(min(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
+             min(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
+}
+__device__ __forceinline__ int wave_max_i32(int v) {
+  v = max(v, dpp_i32<0xB1>(v));
+  v = max(v, dpp_i32<0x4E>(v));
+  v = max(v, dpp_i32<0x141>(v));
+  v = max(v, dpp_i32<0x140>(v));
+  return max(max(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
+             max(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
+}
+
+// The cell box of everything beams [block * 256, block * 256 + 256) of the scan can touch: the hull of the end cells of its
+// non-skipped beams and the begin cell (a Bresenham line stays inside the box of its end points) -- every cell a mark pass
+// writes to, so the apply pass over it clears every mark.  level_bbox() on the host also counts beams that end IN the begin
+// cell (skipped, OccGridMapBase.h:158): its box is this one, or the begin cell alone where this one is empty.
+// Called by all 64 lanes of every wavefront.
+__device__ __forceinline__ void mark_box_block(const UpdateParams& P, unsigned int block, int* scan_box, int* run_box) {
+  const int beam = block * blockDim.x + threadIdx.x;
+  int x0 = kBoxEmptyLo, y0 = kBoxEmptyLo, x1 = kBoxEmptyHi, y1 = kBoxEmptyHi;
+  if (beam < P.n) {
+    const BeamLine b = beam_line(P, beam);
+    if (b.valid) {
+      x0 = x1 = b.x1;
+      y0 = y1 = b.y1;
+    }
+  }
+  x1 = wave_max_i32(x1);
+  if (x1 < 0) return;  // wave-uniform: no beam of this wavefront ends inside the map
+  x0 = min(wave_min_i32(x0), P.bx);
+  y0 = min(wave_min_i32(y0), P.by);
+  x1 = max(x1, P.bx);
+  y1 = max(wave_max_i32(y1), P.by);
+  if ((threadIdx.x & 63) == 0) {
+    atomicMin(&scan_box[0], x0);
+    atomicMin(&scan_box[1], y0);
+    atomicMax(&scan_box[2], x1);
+    atomicMax(&scan_box[3], y1);
+    atomicMin(&run_box[0], x0);
+    atomicMin(&run_box[1], y0);
+    atomicMax(&run_box[2], x1);
+    atomicMax(&run_box[3], y1);
+  }
+}
+
+// gridDim.x = occ_blocks + free_blocks, sized by the caller's hint: the first occ_blocks workgroups of a row mark end cells and
+// reduce the box, 256 beams a turn, the others walk lines, 4 beams a turn, until the scan's real beam count is covered
+__global__ void __launch_bounds__(256) update_mark_scan_kernel(const UpdateBatch* __restrict__ B, unsigned int occ_blocks,
+                                                               int* scan_boxes, int* run_boxes) {
+  const UpdateParams P = B->lv[blockIdx.y];
+  if (P.n <= 0) return;
+  if (blockIdx.x < occ_blocks) {
+    const unsigned int turns = ((unsigned int)P.n + 255u) / 256u;
+    for (unsigned int b = blockIdx.x; b < turns; b += occ_blocks) {
+      mark_occ_block(P, b);
+      mark_box_block(P, b, scan_boxes + 4 * blockIdx.y, run_boxes + 4 * blockIdx.y);
+    }
+  } else {
+    const unsigned int free_blocks = gridDim.x - occ_blocks, turns = ((unsigned int)P.n + 3u) / 4u;
+    for (unsigned int b = blockIdx.x - occ_blocks; b < turns; b += free_blocks) mark_free_block<true>(P, b);
+  }
+}
+
+template <bool SCATTER_TEXELS>
+__global__ void __launch_bounds__(256) update_apply_scan_kernel(const UpdateBatch* __restrict__ B,
+                                                                const int* __restrict__ scan_boxes) {
+  const int4 box = *reinterpret_cast<const int4*>(scan_boxes + 4 * blockIdx.y);
+  if (box.z < box.x) return;  // nothing of this scan on this level
+  UpdateParams P = B->lv[blockIdx.y];
+  P.x0 = box.x;
+  P.y0 = box.y;
+  P.x1 = box.z;
+  P.y1 = box.w;
+  apply_box<SCATTER_TEXELS>(P, blockIdx.x * (size_t)blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x);
+}
+
+// the running dirty boxes of all levels back to empty (after the host has merged them)
+__global__ void update_boxes_clear_kernel(int* boxes, int n_boxes) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < 4 * n_boxes) boxes[i] = (i & 3) < 2 ? kBoxEmptyLo : kBoxEmptyHi;
 }
 
 // test hook (hsm_debug_marks_nonzero): the dense update's byte map and the keyed update's end-cell bitmap must be ALL ZERO

@@ -197,6 +197,42 @@ int hsm_synchronize(hsm_ctx* h);
 int hsm_update_by_scan_level(hsm_ctx* h, int level, const float pose_world[3],
                              const float* pts_level_xy, int n, const float origo_level[2]);
 
+/* replaces: for k = 0 .. count-1, in order: MapRepMultiMap::updateByScan(container_k, pose_k)
+ *           (HSL/slam_main/MapRepMultiMap.h:134-147 -> OccGridMapBase::updateByScan, HSL/map/OccGridMapBase.h:121-260),
+ *           with level l seeing container_k through DataContainer::setFrom(container_k, 1 / 2^l)
+ *           (DataPointContainer.h:46-58) -- what the reference does whenever updateByScan follows the matchData
+ *           of the same scan, which is always in HectorSlamProcessor::update (HectorSlamProcessor.h:78-94).
+ * Poses and scans stay where the batched matchers leave them.  DEVICE pointers:
+ *   d_poses_world  [count*3] WORLD poses, e.g. d_out_pose of hsm_match_batch_device or d_out_best_pose of
+ *                  hsm_match_score_batch_device.  A NaN, infinite or far-away pose changes no cell (every beam fails the
+ *                  reference's map test) and still counts as an update.
+ *   d_pts_xy, d_scan_offsets, shared_n   as in hsm_match_batch_device: CSR offsets [count+1] in points, or NULL = every pose
+ *                  integrates the one scan d_pts_xy[0 .. shared_n).  A scan of 0 beams counts as an update, like an empty
+ *                  container in the reference (OccGridMapBase.h:123-167); a CSR scan of more than HSM_MAX_UPDATE_BEAMS
+ *                  beams is integrated as an empty one.
+ *   max_beams      a sizing HINT (typical beams per scan, 0 = unknown -> 1081): it selects launch shapes only -- a longer
+ *                  scan is integrated correctly, just more slowly
+ *   origo          HOST, the containers' origo (NULL = 0,0)
+ * The host never learns a pose or a scan's length: one preparation launch, then two launches per scan, on the context's own
+ * stream like every map writer.  `stream` is the caller's stream on which the inputs were produced (NULL = default stream):
+ * the call records an event there and the context's stream waits for it; the update queues behind batched matches that
+ * still read the map, and every hsm_* map reader queued later, on any stream, is ordered behind the update.  The inputs
+ * must stay unchanged until the update has run: overwriting them from such later hsm_* calls needs no extra
+ * synchronisation, any other writer waits (hsm_synchronize).  Returns when everything is queued.
+ * HSM_ERR_INVALID, nothing queued: count < 0, max_beams < 0, a NULL pointer where data is needed, shared_n < 0 without
+ * offsets, or `stream` / a stream this context has matched on is being captured into a graph (updates are not captured).
+ * count == 0: HSM_OK.  hsm_update_index advances by count on every level.  Does not touch the retained or the ingested
+ * scan.  hsm_last_update_bbox / hsm_take_dirty_bbox called afterwards wait for the update (the boxes are computed on the
+ * device): on level 0 the box of the host path, on coarse levels a tighter one that still holds every changed cell.
+ * Not replayed by hsm_group_*. */
+int hsm_update_by_scans_device(hsm_ctx* h, int count, const float* d_poses_world, const float* d_pts_xy,
+                               const int* d_scan_offsets, int shared_n, int max_beams, const float origo[2],
+                               void* stream);
+/* same with host arrays (copies in, then the same device path; returns when queued, the arrays may be reused at once):
+ * builds a map from a log of posed scans in one call.  HSM_ERR_TOO_LARGE: a scan of more than HSM_MAX_UPDATE_BEAMS beams. */
+int hsm_update_by_scans(hsm_ctx* h, int count, const float* poses_world, const float* pts_xy,
+                        const int* scan_offsets, int shared_n, const float origo[2]);
+
 /* ---- single-process multi-GPU group (extension; the reference has no multi-device path) ------------------
  * One replica of the pyramid per listed device (a device may be listed more than once).  Batched matching is
  * sharded contiguously over the replicas, one PERSISTENT host thread per replica (created with the group), each
