@@ -147,7 +147,9 @@ int hsm_match(hsm_ctx* h, const float begin_world[3], const float* pts_xy, int n
  * (ScanMatcher.h:100-110: drawArrow(estimate) and addHessianMatrix(H) per loop iteration).
  * trace[12*k .. 12*k+11] = {map-frame estimate after step k [3], H used by step k [9] col-major},
  * steps in schedule order (coarsest level first; 4 per coarse level, 6 on level 0).
- * *steps_written = number of records (0 for an empty scan). */
+ * *steps_written = number of records (0 for an empty scan).
+ * trace_cap_steps < hsm_gn_iterations_per_match() (6 + 4 * (levels - 1), 34 on 8 levels): HSM_ERR_INVALID, no match is run
+ * and nothing is written, *steps_written included. */
 int hsm_match_trace(hsm_ctx* h, const float begin_world[3], const float* pts_xy, int n,
                     const float origo[2], float out_pose_world[3], float cov[9], float* trace,
                     int trace_cap_steps, int* steps_written);
@@ -366,7 +368,8 @@ int hsm_download_rows(hsm_ctx* h, int level, int y0, int y1, float* logodds_rows
  * refresh behind getGridMap() */
 int hsm_download_cells(hsm_ctx* h, int level, int x0, int y0, int x1, int y1, void* dst_cells,
                        int dst_pitch_cells);
-/* cell bounding box {x0, y0, x1, y1} (inclusive) touched by the last update of `level`;
+/* cell bounding box {x0, y0, x1, y1} (inclusive) touched by the last update of `level`: the last SCAN integrated, so after
+ * hsm_update_by_scans* of several scans the box of the last of them only (hsm_take_dirty_bbox covers the whole call);
  * x1 < x0 when nothing was touched */
 int hsm_last_update_bbox(const hsm_ctx* h, int level, int bbox[4]);
 /* union of the cell boxes touched on `level` since the previous call (reset/upload mark the whole level),

@@ -212,6 +212,66 @@ def test_dropin_matches_reference_node_loop(tmp_path, pyramid_scene, hooks):
                 assert np.array_equal(x, y)
 
 
+@pytest.fixture(scope="module")
+def deep_scene():
+    """1081 beams, a 6-level pyramid 1024 / 512 / ... / 32 over a 40 m x 30 m room"""
+    from hector_slam_amd import synth
+    return synth.make_scene(n_beams=1081, map_size=1024, levels=6, resolution=0.05, n_build=40, n_query=4, room=(40.0, 30.0), seed=606)
+
+
+@needs_ref
+def test_reference_driver_six_levels_matches_oracle(tmp_path, oracle_mod, deep_scene):
+    """the reference driver with numDepth = 6 on a 1024^2 map == the oracle's HectorSlamProcessor loop, which reads the map at
+    no NaN coordinate on it: the CPU pin of the run below"""
+    sc, steps = deep_scene, 12
+    scen, out = str(tmp_path / "s.bin"), str(tmp_path / "o.bin")
+    o = make_oracle(oracle_mod, "ho", sc, build=False)
+    o.proc_set_thresholds(0.05, 0.02)
+    origo = np.array([0.3, -0.1], np.float32) * np.float32(sc.scale_to_map)
+    last, poses = np.zeros(3, np.float32), []
+    for t in range(steps):
+        hint = sc.build_poses[0] if t == 0 else (sc.build_poses[t] - sc.build_poses[t - 1]) + last
+        o.proc_update(sc.build_scans[t], hint.astype(np.float32), origo=origo, map_without_matching=(t == 7))
+        last, _ = o.proc_last_pose()
+        poses.append(last)
+    assert o.undefined_reads() == 0 and np.isfinite(poses).all()
+    write_scenario(scen, sc, steps, hooks=False)
+    run(REF_BIN, scen, out)
+    r = read_output(out, steps)
+    assert np.array_equal(np.stack(poses).view(np.uint32), r["pose"].view(np.uint32))
+    assert len(r["grids"]) == 6 and (r["grids"][5]["sx"], r["grids"][5]["sy"]) == (32, 32)
+    for lvl in range(6):
+        lo, _ = o.download_level(lvl)
+        assert np.array_equal(lo.view(np.uint32), r["grids"][lvl]["val"].view(np.uint32)) and (lo != 0).any(), lvl
+
+
+@pytest.mark.gpu
+def test_dropin_six_levels_on_a_1024_map(tmp_path, deep_scene):
+    """numDepth = 6 through the facade, which forwards it untouched (only 3 had ever been run): poses, covariances, the batched
+    extension, all six grids and every record the draw / debug hooks saw (20 Hessians per match) carry the reference's bits"""
+    if not (os.path.exists(GPU_BIN) and os.path.exists(REF_BIN)):
+        pytest.skip("oracle/_ref/slam_driver_{ref,mi355} not prebuilt (run __graft_entry__.build() where "
+                    "/root/reference exists)")
+    sc, steps = deep_scene, 12
+    scen = str(tmp_path / "s.bin")
+    write_scenario(scen, sc, steps, hooks=1)
+    run(REF_BIN, scen, str(tmp_path / "ref.bin"))
+    assert "MI355X resident" in run(GPU_BIN, scen, str(tmp_path / "gpu.bin"))
+    r, g = read_output(str(tmp_path / "ref.bin"), steps), read_output(str(tmp_path / "gpu.bin"), steps)
+    same = lambda a, b: np.array_equal(np.ascontiguousarray(a, np.float32).view(np.uint32), np.ascontiguousarray(b, np.float32).view(np.uint32))  # noqa: E731
+    assert np.isfinite(r["pose"]).all()
+    assert same(r["pose"], g["pose"]) and same(r["cov"], g["cov"]) and same(r["batch"], g["batch"])
+    assert len(g["grids"]) == len(r["grids"]) == 6
+    for a, b in zip(r["grids"], g["grids"]):
+        assert (a["sx"], a["sy"], a["cell"], a["update_index"]) == (b["sx"], b["sy"], b["cell"], b["update_index"])
+        assert same(a["val"], b["val"]) and np.array_equal(a["occ"], b["occ"]) and (a["val"] != 0).any()
+    ca, cb = parse_log(r["log"]), parse_log(g["log"])
+    assert [t for t, _ in ca] == [t for t, _ in cb]
+    assert sum(1 for t, _ in ca if t == 8) == (steps - 1) * (3 * 5 + 5)  # (per match 3 on each coarse level, 5 on level 0; one step maps without matching)
+    for (t, x), (_, y) in zip(ca, cb):
+        assert np.array_equal(x, y), (t, x, y)
+
+
 @pytest.mark.gpu
 def test_dropin_dense_scans(tmp_path):
     """8192-beam scans through the C++ facade (the standalone driver runs on the system HIP runtime, not torch's): in the

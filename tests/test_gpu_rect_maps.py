@@ -477,6 +477,17 @@ def test_create_validation_is_symmetric(capi, oracle_mod, kind):
         _, ui = ref.o.download_level(2)
         assert ui.shape == (sy >> 2, sx >> 2) and (ui >= 0).any()
         g.close()
+    # the level count: 8 at most, and no level below 2 cells on either axis
+    with pytest.raises(capi.HsmError, match="bad map geometry"):
+        capi.MapRepMultiMap(RES, 4096, 4096, 9)
+    for sx, sy in ((255, 255), (256, 255), (255, 256)):
+        with pytest.raises(capi.HsmError, match="too many levels"):
+            capi.MapRepMultiMap(RES, sx, sy, 8)
+    g = new_ctx(capi, 256, 511, 8)
+    o = oracle_mod.Oracle(kind, RES, 256, 511, 8)
+    assert [g.level_info(l) for l in range(8)] == [o.level_info(l) for l in range(8)]
+    assert g.level_info(7)[:2] == (2, 3) and g.getMapLevels() == 8
+    g.close()
 
 
 # ------------------------------------------------------------------------------------------------ h. the seeded property

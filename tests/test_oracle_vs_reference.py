@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 from hypothesis import HealthCheck, given, seed, settings
 
+import deep_cases
 import rect_cases
 from conftest import bits, make_oracle, oracle_kinds
 
@@ -252,6 +253,59 @@ def test_rectangular_geometries_restatement_equals_reference(oracle_mod):
             assert np.array_equal(o["ho"].occupancy_grid(lvl), o["hr"].occupancy_grid(lvl))
         _, ui = o["ho"].download_level(0)
         assert (ui >= 0).sum() > 100, (sx, sy)  # the loop did map something
+
+
+@pytest.mark.parametrize("geom", deep_cases.GEOMETRIES + [deep_cases.LARGE], ids=deep_cases.gid)
+def test_deep_pyramids_restatement_equals_reference(oracle_mod, geom):
+    """the cases of tests/deep_cases.py (6 to 8 levels, coarsest levels of 64 x 64 down to 2 x 2 cells, the 4096^2 map: the very
+    scenes the GPU tests run, build counts included): the case is usable (deep_cases.check: no empty level, a regular H on the levels of 16 cells or more, no map read
+    at a NaN coordinate -- the restatement goes first everywhere, the reference would crash there), and restatement == reference
+    headers on the built map's planes, match, match_many, the per-level chain, and every level after each update of the SLAM loop
+    the GPU test runs"""
+    if not oracle_mod.available("hr"):
+        pytest.skip("oracle/_ref not built")
+    from hector_slam_amd import synth
+    case = deep_cases.case(geom)
+    deep_cases.check(oracle_mod, case)
+    assert case.undefined_reads == 0
+    L = case.levels
+    ho, hr = (deep_cases.built_oracle(oracle_mod, k, case) for k in ("ho", "hr"))
+
+    def same_maps(what):
+        for lvl in range(L):
+            a, b = ho.download_level(lvl), hr.download_level(lvl)
+            assert a[0].shape == (geom[1] >> lvl, geom[0] >> lvl)
+            assert np.array_equal(bits(a[0]), bits(b[0])) and np.array_equal(a[1], b[1]), (geom, what, lvl)
+            assert np.array_equal(ho.occupancy_grid(lvl), hr.occupancy_grid(lvl)), (geom, what, lvl)
+            assert ho.level_info(lvl) == hr.level_info(lvl)
+
+    same_maps("built")
+    pts, offs = synth.pack_scans(case.query_scans)
+    pm = ho.match_many(case.query_init, pts, offs)
+    assert ho.undefined_reads() == 0
+    assert np.array_equal(bits(pm), bits(hr.match_many(case.query_init, pts, offs)))
+    for q, (init, sc) in enumerate(zip(case.query_init, case.query_scans)):
+        (po, co), (pr, cr) = ho.match(init, sc, case.origo), hr.match(init, sc, case.origo)
+        assert np.array_equal(bits(po), bits(pr)) and np.array_equal(bits(co), bits(cr)), (geom, q)
+        po, _ = ho.match(init, sc)
+        assert np.array_equal(bits(po), bits(pm[q])), (geom, q)
+        chain, _, _ = deep_cases.level_chain(ho, init, sc, L)
+        for lvl, start, p, it in chain[:: 1 if q < 2 else L]:
+            at = ho.map_coords_pose(lvl, start)
+            assert np.array_equal(bits(at), bits(hr.map_coords_pose(lvl, start)))
+            (Ho, do), (Hr, dr) = ho.hessian_derivs(lvl, at, p), hr.hessian_derivs(lvl, at, p)
+            assert np.array_equal(bits(Ho), bits(Hr)) and np.array_equal(bits(do), bits(dr)), (geom, q, lvl)
+            for j in (0, it):
+                (a, ca), (b, cb) = ho.match_level(lvl, start, p, j), hr.match_level(lvl, start, p, j)
+                assert np.array_equal(bits(a), bits(b)) and np.array_equal(bits(ca), bits(cb)), (geom, q, lvl, j)
+    steps_o = deep_cases.slam_loop(ho, case)
+    assert ho.undefined_reads() == 0
+    for t, (hint, sc, og, p, c) in enumerate(steps_o):
+        pr, cr = hr.match(hint, sc, og)
+        assert np.array_equal(bits(p), bits(pr)) and np.array_equal(bits(c), bits(cr)), (geom, t)
+        hr.update_by_scan(pr, sc, og)
+        hr.on_map_updated()
+    same_maps("after the loop")
 
 
 @pytest.mark.skipif("hr" not in oracle_kinds(), reason="oracle/_ref not built")

@@ -44,7 +44,7 @@ def run_loop(g, make_a, make_b, steps=8, make_guard=None):
     (hypothesis.assume) instead of taking the test process down with it"""
     from hector_slam_amd import synth
     size, levels, res = g["size"], g["levels"], g["res"]
-    while (size >> (levels - 1)) < 8:
+    while (size >> (levels - 1)) < 2:  # (hsm_create's own limit: a coarsest level of 2 x 2 cells)
         levels -= 1
     ext = size * res
     world = synth.World.make(ext * g["grow"], ext * g["grow"] * 0.75, n_boxes=3, seed=g["seed"], keep_clear=0.5)
@@ -93,7 +93,7 @@ def run_loop(g, make_a, make_b, steps=8, make_guard=None):
 # runs are exactly the ones the CPU pin (restatement == reference headers) ran here first.
 dense_geometry = st.fixed_dictionaries({
     "size": st.sampled_from([64, 128, 192, 256, 320]),
-    "levels": st.integers(1, 3),
+    "levels": st.integers(1, 6),
     "res": st.sampled_from([0.05, 0.1]),
     "start": st.tuples(st.floats(-0.04, 1.04), st.floats(-0.04, 1.04)),
     "free": st.floats(0.3, 0.49),
@@ -188,7 +188,7 @@ def test_gpu_dense_update_equals_reference_at_the_borders(oracle_mod, g):
 # scans and fragments included) and holds every pose and covariance of the batch to the reference's bits.
 batch_geometry = st.fixed_dictionaries({
     "size": st.sampled_from([64, 128, 200, 256, 512]),
-    "levels": st.integers(1, 3),
+    "levels": st.integers(1, 6),
     "res": st.sampled_from([0.05, 0.1]),
     "start": st.tuples(st.floats(0.3, 0.7), st.floats(0.3, 0.7)),
     "free": st.floats(0.3, 0.49),
@@ -201,13 +201,11 @@ batch_geometry = st.fixed_dictionaries({
 })
 
 
-@pytest.mark.gpu
-@settings(max_examples=GPU_EXAMPLES or 60, deadline=None, derandomize=True, suppress_health_check=list(HealthCheck))
-@given(g=batch_geometry)
-def test_gpu_default_mode_batches_equal_reference_for_random_geometries(oracle_mod, g):
-    from hector_slam_amd import capi, synth
+def batch_example(g):
+    """the inputs of a batch_geometry example, from its seed alone: (levels, build poses, build scans, query scans, hints)"""
+    from hector_slam_amd import synth
     size, levels, res = g["size"], g["levels"], g["res"]
-    while (size >> (levels - 1)) < 8:
+    while (size >> (levels - 1)) < 2:  # (hsm_create's own limit: a coarsest level of 2 x 2 cells)
         levels -= 1
     ext = size * res
     world = synth.World.make(ext * g["grow"], ext * g["grow"] * 0.75, n_boxes=3, seed=g["seed"], keep_clear=0.5)
@@ -216,6 +214,51 @@ def test_gpu_default_mode_batches_equal_reference_for_random_geometries(oracle_m
     poses = synth.loop_trajectory(world, n_build + B, frac=0.25).astype(np.float32)
     rng = np.random.default_rng(g["seed"])
     scans = [synth.make_scan(world, p, g["beams"], s, rng, range_max=min(30.0, ext)) for p in poses]
+    query, init = [], []
+    for q in range(B):
+        sc = scans[n_build + q]
+        if g["ragged"] and sc.shape[0] > 0:
+            n = int(rng.choice([0, 1, 7, 64, 65, sc.shape[0] // 2, sc.shape[0]]))
+            sc = sc[np.sort(rng.choice(sc.shape[0], size=min(n, sc.shape[0]), replace=False))]
+        query.append(np.ascontiguousarray(sc, np.float32))
+        init.append(poses[n_build + q] + np.array([rng.uniform(-0.05, 0.05), rng.uniform(-0.05, 0.05), rng.uniform(-0.02, 0.02)], np.float32))
+    return levels, poses[:n_build], scans[:n_build], query, np.stack(init).astype(np.float32)
+
+
+@pytest.mark.skipif("hr" not in oracle_kinds(), reason="oracle/_ref/libhector_ref.so not built (needs /root/reference)")
+@settings(max_examples=60, deadline=None, derandomize=True, suppress_health_check=list(HealthCheck))
+@given(g=batch_geometry)
+def test_restatement_equals_reference_for_random_batches(oracle_mod, g):
+    """the CPU pin of the batch property below (the same derandomised examples, 1 to 6 levels, coarsest levels down to 2 cells):
+    the maps after the build scans and every scan's matchData, restatement == reference headers; the restatement goes first, and
+    an example on which the reference would read its grid at a NaN coordinate is discarded there as it is on the GPU"""
+    levels, bposes, bscans, query, init = batch_example(g)
+    ho, hr = (oracle_impl(oracle_mod, k)(g["res"], g["size"], levels, g["start"], g["free"], g["occ"]) for k in ("ho", "hr"))
+    zero = np.zeros(2, np.float32)
+    for p, sc in zip(bposes, bscans):
+        ho["update"](p, sc, zero)
+        hr["update"](p, sc, zero)
+    for lvl in range(levels):
+        la, lb = ho["level"](lvl), hr["level"](lvl)
+        assert np.array_equal(bits(la[0]), bits(lb[0])) and np.array_equal(la[1], lb[1]), (g, lvl)
+    for q in range(len(query)):
+        po, co = ho["match"](init[q], query[q], zero)
+        assume(not reference_undefined(ho))
+        pr, cr = hr["match"](init[q], query[q], zero)
+        if not np.isfinite(po).all():
+            assert np.array_equal(np.isnan(po), np.isnan(pr)), (g, q)
+            continue
+        assert np.array_equal(bits(po), bits(pr)) and np.array_equal(bits(co), bits(cr)), (g, q)
+
+
+@pytest.mark.gpu
+@settings(max_examples=GPU_EXAMPLES or 60, deadline=None, derandomize=True, suppress_health_check=list(HealthCheck))
+@given(g=batch_geometry)
+def test_gpu_default_mode_batches_equal_reference_for_random_geometries(oracle_mod, g):
+    from hector_slam_amd import capi, synth
+    size, res = g["size"], g["res"]
+    levels, bposes, bscans, query, init = batch_example(g)
+    B = g["batch"]
     m = capi.MapRepMultiMap(res, size, size, levels, g["start"])
     assert m.parity() == capi.PARITY_AUTO
     kind = oracle_kinds()[-1]
@@ -225,22 +268,13 @@ def test_gpu_default_mode_batches_equal_reference_for_random_geometries(oracle_m
     m.setUpdateFactorFree(g["free"])
     m.setUpdateFactorOccupied(g["occ"])
     zero = np.zeros(2, np.float32)
-    for t in range(n_build):
-        m.updateByScan(scans[t], poses[t])
+    for p, sc in zip(bposes, bscans):
+        m.updateByScan(sc, p)
         for o in impls:
-            o["update"](poses[t], scans[t], zero)
+            o["update"](p, sc, zero)
     for lvl in range(levels):
         la, lb = m.download_level(lvl), impls[-1]["level"](lvl)
         assert np.array_equal(bits(la[0]), bits(lb[0])) and np.array_equal(la[1], lb[1]), (g, lvl)
-    query, init = [], []
-    for q in range(B):
-        sc = scans[n_build + q]
-        if g["ragged"] and sc.shape[0] > 0:
-            n = int(rng.choice([0, 1, 7, 64, 65, sc.shape[0] // 2, sc.shape[0]]))
-            sc = sc[np.sort(rng.choice(sc.shape[0], size=min(n, sc.shape[0]), replace=False))]
-        query.append(np.ascontiguousarray(sc, np.float32))
-        init.append(poses[n_build + q] + np.array([rng.uniform(-0.05, 0.05), rng.uniform(-0.05, 0.05), rng.uniform(-0.02, 0.02)], np.float32))
-    init = np.stack(init).astype(np.float32)
     pts, offs = synth.pack_scans(query)
     pose, cov = m.match_batch(init, pts, offs)
     cfg = m.last_launch_config()
