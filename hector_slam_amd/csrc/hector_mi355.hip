@@ -193,23 +193,6 @@ int rebuild_probability(hsm_ctx* h, Level& L) {
   return HSM_OK;
 }
 
-// Teardown never stops at a failing call (everything else still has to be released), but it must not swallow one either: HIP
-// keeps the last failure per thread, and the next hipGetLastError() of an unrelated call -- the launch check of the next
-// hsm_create on this thread -- would report it as its own.  The first failing call is kept for hsm_last_error(), the runtime's
-// per-thread state is cleared at the end (hsm_destroy).
-struct TeardownLog {
-  std::string first;
-  void note(const char* what, hipError_t e) {
-    if (e == hipSuccess || !first.empty()) return;
-    first = std::string(what) + ": " + hipGetErrorString(e);
-  }
-};
-#define TEARDOWN(log, expr) \
-  do {                      \
-    hipError_t e__ = (expr); \
-    if (log) (log)->note(#expr, e__); \
-  } while (0)
-
 void free_level(Level& L, TeardownLog* log = nullptr) {
   TEARDOWN(log, hipFree(L.d_logodds));
   TEARDOWN(log, hipFree(L.d_update_index));
@@ -220,17 +203,6 @@ void free_level(Level& L, TeardownLog* log = nullptr) {
   TEARDOWN(log, hipFree(L.d_occ_bits));
   TEARDOWN(log, hipFree(L.d_free_bytes));
   L = Level();
-}
-
-int ensure_scan_capacity(float2*& buf, size_t& cap, size_t n) {
-  if (n <= cap) return HSM_OK;
-  if (buf) HIP_TRY(hipFree(buf));
-  buf = nullptr;
-  cap = 0;
-  size_t want = n < 4096 ? 4096 : n + n / 2;
-  HIP_TRY(hipMalloc((void**)&buf, want * sizeof(float2)));
-  cap = want;
-  return HSM_OK;
 }
 
 // waves per scan: enough wavefronts to fill 256 CUs x 4 SIMDs x several waves, but never
@@ -298,22 +270,16 @@ int launch_match_exact_dense(hsm_ctx* h, const MatchParams& P0, int max_n, hipSt
     for (hsm_ctx::SpecScratch& b : h->spec_scratch)
       if (b.s == stream) sb = &b;
     if (!sb && h->spec_scratch.size() < 8) {
-      h->spec_scratch.push_back({stream, nullptr, 0});
+      h->spec_scratch.push_back({stream, {}});
       sb = &h->spec_scratch.back();
     }
   }
   if (sb) {
     const size_t stride = spec_scratch_float4s_bound(P.n_bound);  // enough for every n <= n_bound
     const size_t need = stride * (size_t)P.batch;
-    if (need > sb->cap) {
-      HIP_TRY(hipStreamSynchronize(stream));  // (a launch of this stream in flight may still read the old block)
-      if (sb->d) HIP_TRY(hipFree(sb->d));
-      sb->d = nullptr;
-      sb->cap = 0;
-      HIP_TRY(hipMalloc((void**)&sb->d, need * sizeof(float4)));
-      sb->cap = need;
-    }
-    P.spec_scratch = sb->d;
+    if (!sb->d.holds(need)) HIP_TRY(hipStreamSynchronize(stream));  // (a launch of this stream in flight may still read the old block)
+    if (int rc = sb->d.reserve(need)) return rc;
+    P.spec_scratch = (float*)sb->d.p;
     P.spec_stride = (unsigned)stride;
     P.spec_stats = h->d_spec_stats;
     if (h->layout == kLayoutPlane)
@@ -610,15 +576,10 @@ int launch_update_mark(hsm_ctx* h, UpdateBatch& batch) {
   const unsigned ny = (unsigned)batch.nlev;
   if (use_dense_bits(h, batch, max_n)) {
     // per-beam records: written by the end-cell pass, read by the line walk (one block of max_n records per level)
-    if ((size_t)max_n > h->beam_recs_cap) {
-      if (h->d_beam_recs) HIP_TRY(hipFree(h->d_beam_recs));  // (frees wait for the queued work that still reads the old block)
-      h->d_beam_recs = nullptr;
-      h->beam_recs_cap = 0;
-      const size_t want = (size_t)max_n + (size_t)max_n / 2;
-      HIP_TRY(hipMalloc((void**)&h->d_beam_recs, want * HSM_MAX_LEVELS * sizeof(BeamRec)));
-      h->beam_recs_cap = want;
-    }
-    for (int i = 0; i < batch.nlev; ++i) batch.lv[i].recs = h->d_beam_recs + (size_t)i * h->beam_recs_cap;
+    if (!h->d_beam_recs.holds((size_t)max_n * HSM_MAX_LEVELS))
+      if (int rc = h->d_beam_recs.reserve(grown_capacity((size_t)max_n, kHalfMore) * HSM_MAX_LEVELS)) return rc;
+    const size_t per_level = h->d_beam_recs.count() / HSM_MAX_LEVELS;
+    for (int i = 0; i < batch.nlev; ++i) batch.lv[i].recs = h->d_beam_recs + (size_t)i * per_level;
     hipLaunchKernelGGL(update_mark_occ_dense_kernel, dim3((max_n + 255) / 256, ny), dim3(256), 0, h->stream, batch);
     // x extent a multiple of 8: workgroup b of every level then runs on XCD b % 8 (the kernel's beam -> XCD mapping)
     hipLaunchKernelGGL(update_mark_free_dense_kernel, dim3(mark_dense_blocks(max_n), ny), dim3(256), 0, h->stream, batch);
@@ -765,20 +726,16 @@ int merge_device_boxes(hsm_ctx* h) {
 
 // the UpdateBatch blocks and cell boxes of `count` scans (hsm_ctx::d_upd_batches / d_upd_boxes)
 int ensure_update_scans(hsm_ctx* h, size_t count) {
-  if (h->d_upd_boxes && count <= h->upd_scans_cap) return HSM_OK;
+  if (h->d_upd_boxes && h->d_upd_batches.holds(count)) return HSM_OK;
   if (h->upd_boxes_outstanding)  // the running boxes live in the block that is about to go
     if (int rc = merge_device_boxes(h)) return rc;
-  if (h->d_upd_batches) HIP_TRY(hipFree(h->d_upd_batches));  // (frees wait for the queued work that still reads the old blocks)
-  if (h->d_upd_boxes) HIP_TRY(hipFree(h->d_upd_boxes));
-  h->d_upd_batches = nullptr;
-  h->d_upd_boxes = nullptr;
-  h->upd_scans_cap = 0;
-  const size_t want = count < 64 ? 64 : count + count / 2;
-  HIP_TRY(hipMalloc((void**)&h->d_upd_batches, want * sizeof(UpdateBatch)));
-  HIP_TRY(hipMalloc((void**)&h->d_upd_boxes, (want + 2) * kMaxLevels * 4 * sizeof(int)));
+  if (int rc = h->d_upd_boxes.drop()) return rc;  // (both go before either comes back: the box block stands for the pair)
+  if (int rc = h->d_upd_batches.drop()) return rc;
+  const size_t want = grown_capacity(count, {64, 50});
+  if (int rc = h->d_upd_batches.reserve(want)) return rc;
+  if (int rc = h->d_upd_boxes.reserve((want + 2) * kMaxLevels * 4)) return rc;
   hipLaunchKernelGGL(update_boxes_clear_kernel, dim3(1), dim3(64), 0, h->stream, h->d_upd_boxes, 2 * kMaxLevels);
   HIP_TRY(hipGetLastError());
-  h->upd_scans_cap = want;
   return HSM_OK;
 }
 
@@ -971,39 +928,17 @@ void hsm_destroy(hsm_ctx* h) {
   if (h->stream) TEARDOWN(log, hipStreamSynchronize(h->stream));
   if (h->copy_stream) TEARDOWN(log, hipStreamSynchronize(h->copy_stream));
   for (Level& L : h->levels) free_level(L, log);
-  TEARDOWN(log, hipFree(h->d_scan));
-  for (hsm_ctx::SpecScratch& b : h->spec_scratch) TEARDOWN(log, hipFree(b.d));
-  for (hsm_ctx::PermBuf& b : h->perm_bufs) TEARDOWN(log, hipFree(b.d));
-  TEARDOWN(log, hipFree(h->d_spec_stats));
-  TEARDOWN(log, hipFree(h->d_beam_recs));
-  TEARDOWN(log, hipFree(h->d_retained));
-  TEARDOWN(log, hipFree(h->d_retained_alt));
-  if (h->copy_evt) TEARDOWN(log, hipEventDestroy(h->copy_evt));
-  if (h->copy_stream) TEARDOWN(log, hipStreamDestroy(h->copy_stream));
-  if (h->h_copy_pinned) TEARDOWN(log, hipHostFree(h->h_copy_pinned));
-  TEARDOWN(log, hipFree(h->d_small));
-  TEARDOWN(log, hipFree(h->d_batch));
-  if (h->h_hyp_pinned) TEARDOWN(log, hipHostFree(h->h_hyp_pinned));
-  TEARDOWN(log, hipFree(h->d_cells));
-  TEARDOWN(log, hipFree(h->d_partials));
-  TEARDOWN(log, hipFree(h->d_ranges));
-  TEARDOWN(log, hipFree(h->d_trig));
-  TEARDOWN(log, hipFree(h->d_ingest));
+  for (GrowBuf* b : h->bufs) b->release(log);  // every grow-on-demand block of the context (hsm_ctx.h)
+  for (hsm_ctx::SpecScratch& b : h->spec_scratch) b.d.release(log);
+  for (hsm_ctx::PermBuf& b : h->perm_bufs) b.d.release(log);
   for (hsm_ctx::RangesGeometry& g : h->ranges_geoms) TEARDOWN(log, hipFree(g.d));
-  TEARDOWN(log, hipFree(h->d_rbatch));
-  TEARDOWN(log, hipFree(h->d_occ));
-  if (h->h_scan_pinned) TEARDOWN(log, hipHostFree(h->h_scan_pinned));
-  if (h->evt_updates) TEARDOWN(log, hipEventDestroy(h->evt_updates));
-  if (h->evt_foreign) TEARDOWN(log, hipEventDestroy(h->evt_foreign));
-  if (h->evt_inputs) TEARDOWN(log, hipEventDestroy(h->evt_inputs));
-  TEARDOWN(log, hipFree(h->d_upd_batches));
-  TEARDOWN(log, hipFree(h->d_upd_boxes));
-  TEARDOWN(log, hipFree(h->d_upd_stage));
+  TEARDOWN(log, hipFree(h->d_spec_stats));
+  TEARDOWN(log, hipFree(h->d_small));
+  TEARDOWN(log, hipFree(h->d_partials));
   if (h->h_small) TEARDOWN(log, hipHostFree(h->h_small));
-  for (int k = 0; k < 2; ++k) {
-    if (h->h_upd_pinned[k]) TEARDOWN(log, hipHostFree(h->h_upd_pinned[k]));
-    if (h->upd_evt[k]) TEARDOWN(log, hipEventDestroy(h->upd_evt[k]));
-  }
+  for (hipEvent_t e : {h->copy_evt, h->evt_updates, h->evt_foreign, h->evt_inputs, h->upd_evt[0], h->upd_evt[1]})
+    if (e) TEARDOWN(log, hipEventDestroy(e));
+  if (h->copy_stream) TEARDOWN(log, hipStreamDestroy(h->copy_stream));
   if (h->stream) TEARDOWN(log, hipStreamDestroy(h->stream));
   delete h;
   if (!log_.first.empty()) {
@@ -1368,29 +1303,27 @@ static int match_batch_host(hsm_ctx* h, int batch, const float* begin_world, con
   if (batch == 0) return HSM_OK;
   const size_t total = scan_offsets ? (size_t)scan_offsets[batch] : (size_t)(shared_n > 0 ? shared_n : 0);
   if (total > 0 && !pts_xy) return fail(HSM_ERR_INVALID, who);
-  const size_t b_begin = (size_t)batch * 3 * sizeof(float);
-  const size_t b_pts = total * 2 * sizeof(float);
-  const size_t b_offs = scan_offsets ? ((size_t)batch + 1) * sizeof(int) : 0;
-  const size_t b_pose = b_begin, b_cov = (size_t)batch * 9 * sizeof(float);
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  // the score's and the ranking's arrays, one block behind the match's own: likelihood | residual | group offsets | winner
-  // index | winner score | winner pose
-  const size_t b_lh = sr ? (size_t)batch * sizeof(float) : 0, b_res = sr && sr->out_res ? b_lh : 0;
-  const size_t b_goffs = G > 0 && sr->group_offsets ? ((size_t)G + 1) * sizeof(int) : 0;
-  const size_t b_idx = (size_t)G * sizeof(int), b_bscore = G > 0 && sr->out_score ? (size_t)G * sizeof(float) : 0;
-  const size_t b_bpose = G > 0 && sr->out_best_pose ? (size_t)G * 3 * sizeof(float) : 0;
-  const size_t o_res = al(b_lh), o_goffs = o_res + al(b_res), o_idx = o_goffs + al(b_goffs), o_bscore = o_idx + al(b_idx);
-  const size_t o_bpose = o_bscore + al(b_bscore), b_extra = o_bpose + al(b_bpose);
-  // the launches behind the copies in: x = the device address of that block
-  auto launch = [&](const float* d_begin, const float* d_pts, const int* d_offs, int n_or_hint, float* d_pose, float* d_cov,
-                    char* x, int n_bound) {
-    if (!sr) return match_batch_device_nolock(h, batch, d_begin, d_pts, d_offs, n_or_hint, d_pose, d_cov, h->stream, n_bound);
-    return match_score_batch_device_nolock(h, batch, d_begin, d_pts, d_offs, n_or_hint, d_pose, d_cov, sr->level, (float*)x,
-                                           b_res ? (float*)(x + o_res) : nullptr, G, b_goffs ? (const int*)(x + o_goffs) : nullptr,
-                                           sr->group_size, (int*)(x + o_idx), b_bscore ? (float*)(x + o_bscore) : nullptr,
-                                           b_bpose ? (float*)(x + o_bpose) : nullptr, h->stream, n_bound);
+  BatchBytes b = {};  // (stage_layout.h: the match's own arrays, and behind them the score's and the ranking's)
+  b.begin = (size_t)batch * 3 * sizeof(float);
+  b.pts = total * 2 * sizeof(float);
+  b.offs = scan_offsets ? ((size_t)batch + 1) * sizeof(int) : 0;
+  b.cov = (size_t)batch * 9 * sizeof(float);
+  b.lh = sr ? (size_t)batch * sizeof(float) : 0, b.res = sr && sr->out_res ? b.lh : 0;
+  b.goffs = G > 0 && sr->group_offsets ? ((size_t)G + 1) * sizeof(int) : 0;
+  b.idx = (size_t)G * sizeof(int), b.bscore = G > 0 && sr->out_score ? (size_t)G * sizeof(float) : 0;
+  b.bpose = G > 0 && sr->out_best_pose ? (size_t)G * 3 * sizeof(float) : 0;
+  const BatchLayout L = batch_layout(b, !scan_offsets);
+  // the launches behind the copies in: x = the device address of the block
+  auto launch = [&](char* x, const float* d_pts, const int* d_offs, int n_or_hint, int n_bound) {
+    float* d_pose = (float*)(x + L.pose);
+    float* d_cov = out_cov ? (float*)(x + L.cov) : nullptr;
+    if (!sr) return match_batch_device_nolock(h, batch, (const float*)x, d_pts, d_offs, n_or_hint, d_pose, d_cov, h->stream, n_bound);
+    return match_score_batch_device_nolock(h, batch, (const float*)x, d_pts, d_offs, n_or_hint, d_pose, d_cov, sr->level,
+                                           (float*)(x + L.lh), b.res ? (float*)(x + L.res) : nullptr, G,
+                                           b.goffs ? (const int*)(x + L.goffs) : nullptr, sr->group_size, (int*)(x + L.idx),
+                                           b.bscore ? (float*)(x + L.bscore) : nullptr,
+                                           b.bpose ? (float*)(x + L.bpose) : nullptr, h->stream, n_bound);
   };
-  const size_t need = al(b_begin) + al(b_pts) + al(b_offs) + al(b_pose) + al(b_cov) + b_extra;
   std::lock_guard<std::mutex> lk(h->mu);
   if (int rc = select_device(h)) return rc;
   if (!scan_offsets) {
@@ -1401,82 +1334,55 @@ static int match_batch_host(hsm_ctx* h, int batch, const float* begin_world, con
     // one 8.6 KB copy + the launch, against three copies, the launch and two more copies of the general path below.
     // (With a score behind the match, its wavefront reads the matched pose back once and writes 4 or 8 bytes; the ranking reads
     // every likelihood once.)
-    const size_t hb0 = al(b_begin) + al(b_pose) + al(b_cov) + al(b_pts), hb = hb0 + b_extra;
-    if (hb > h->h_hyp_cap) {
-      HIP_TRY(hipStreamSynchronize(h->stream));
-      if (h->h_hyp_pinned) HIP_TRY(hipHostFree(h->h_hyp_pinned));
-      h->h_hyp_pinned = nullptr;
-      h->h_hyp_cap = 0;
-      HIP_TRY(hipHostMalloc(&h->h_hyp_pinned, hb + hb / 2, hipHostMallocMapped));
-      h->h_hyp_cap = hb + hb / 2;
-    }
-    char* hp = (char*)h->h_hyp_pinned;
-    float* hp_begin = (float*)hp;
-    float* hp_pose = (float*)(hp + al(b_begin));
-    float* hp_cov = (float*)(hp + al(b_begin) + al(b_pose));
-    float* hp_pts = (float*)(hp + al(b_begin) + al(b_pose) + al(b_cov));
-    char* hx = hp + hb0;
-    memcpy(hp_begin, begin_world, b_begin);
-    if (out_cov) memcpy(hp_cov, out_cov, b_cov);  // in/out: an empty scan leaves the caller's matrices untouched (ScanMatcher.h:68,189)
-    if (b_pts) memcpy(hp_pts, pts_xy, b_pts);
-    if (b_goffs) memcpy(hx + o_goffs, sr->group_offsets, b_goffs);
-    if (b_bpose) memcpy(hx + o_bpose, sr->out_best_pose, b_bpose);
+    if (!h->h_hyp_pinned.holds(L.total)) HIP_TRY(hipStreamSynchronize(h->stream));
+    if (int rc = h->h_hyp_pinned.reserve(L.total, kHalfMore)) return rc;
+    char* hp = h->h_hyp_pinned;
+    memcpy(hp, begin_world, b.begin);
+    if (out_cov) memcpy(hp + L.cov, out_cov, b.cov);  // in/out: an empty scan leaves the caller's matrices untouched (ScanMatcher.h:68,189)
+    if (b.pts) memcpy(hp + L.pts, pts_xy, b.pts);
+    if (b.goffs) memcpy(hp + L.goffs, sr->group_offsets, b.goffs);
+    if (b.bpose) memcpy(hp + L.bpose, sr->out_best_pose, b.bpose);
     char* dp = nullptr;
     HIP_TRY(hipHostGetDevicePointer((void**)&dp, hp, 0));
-    if (int rc = ensure_scan_capacity(h->d_scan, h->d_scan_cap, total)) return rc;
-    if (b_pts) HIP_TRY(hipMemcpyAsync(h->d_scan, hp_pts, b_pts, hipMemcpyHostToDevice, h->stream));
-    if (int rc = launch((const float*)dp, (const float*)h->d_scan, nullptr, shared_n > 0 ? shared_n : 0, (float*)(dp + al(b_begin)),
-                        out_cov ? (float*)(dp + al(b_begin) + al(b_pose)) : nullptr, dp + hb0, 0))
-      return rc;
+    if (int rc = h->d_scan.reserve(total, kScanGrowth)) return rc;
+    if (b.pts) HIP_TRY(hipMemcpyAsync(h->d_scan, hp + L.pts, b.pts, hipMemcpyHostToDevice, h->stream));
+    if (int rc = launch(dp, (const float*)h->d_scan.p, nullptr, shared_n > 0 ? shared_n : 0, 0)) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));
-    memcpy(out_pose, hp_pose, b_pose);
-    if (out_cov) memcpy(out_cov, hp_cov, b_cov);
+    memcpy(out_pose, hp + L.pose, b.begin);
+    if (out_cov) memcpy(out_cov, hp + L.cov, b.cov);
     if (sr) {
-      memcpy(sr->out_lh, hx, b_lh);
-      if (b_res) memcpy(sr->out_res, hx + o_res, b_res);
-      if (b_idx) memcpy(sr->out_index, hx + o_idx, b_idx);
-      if (b_bscore) memcpy(sr->out_score, hx + o_bscore, b_bscore);
-      if (b_bpose) memcpy(sr->out_best_pose, hx + o_bpose, b_bpose);
+      memcpy(sr->out_lh, hp + L.lh, b.lh);
+      if (b.res) memcpy(sr->out_res, hp + L.res, b.res);
+      if (b.idx) memcpy(sr->out_index, hp + L.idx, b.idx);
+      if (b.bscore) memcpy(sr->out_score, hp + L.bscore, b.bscore);
+      if (b.bpose) memcpy(sr->out_best_pose, hp + L.bpose, b.bpose);
     }
     return HSM_OK;
   }
-  if (need > h->d_batch_cap) {
-    if (h->d_batch) HIP_TRY(hipFree(h->d_batch));
-    h->d_batch = nullptr;
-    h->d_batch_cap = 0;
-    HIP_TRY(hipMalloc(&h->d_batch, need));
-    h->d_batch_cap = need;
+  if (int rc = h->d_batch.reserve(L.total)) return rc;
+  char* base = h->d_batch;
+  const float* d_pts = (const float*)(base + L.pts);
+  const int* d_offs = (const int*)(base + L.offs);  // (scan_offsets is not null here)
+  HIP_TRY(hipMemcpyAsync(base, begin_world, b.begin, hipMemcpyHostToDevice, h->stream));
+  if (b.pts) HIP_TRY(hipMemcpyAsync(base + L.pts, pts_xy, b.pts, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(base + L.offs, scan_offsets, b.offs, hipMemcpyHostToDevice, h->stream));
+  if (out_cov) HIP_TRY(hipMemcpyAsync(base + L.cov, out_cov, b.cov, hipMemcpyHostToDevice, h->stream));  // in/out
+  if (b.goffs) HIP_TRY(hipMemcpyAsync(base + L.goffs, sr->group_offsets, b.goffs, hipMemcpyHostToDevice, h->stream));
+  if (b.bpose) HIP_TRY(hipMemcpyAsync(base + L.bpose, sr->out_best_pose, b.bpose, hipMemcpyHostToDevice, h->stream));  // in/out
+  int hint = 0;
+  for (int i = 0; i < batch; ++i) {
+    const int ni = scan_offsets[i + 1] - scan_offsets[i];
+    if (ni > hint) hint = ni;
   }
-  char* base = (char*)h->d_batch;
-  float* d_begin = (float*)base;
-  float* d_pts = (float*)(base + al(b_begin));
-  int* d_offs = scan_offsets ? (int*)(base + al(b_begin) + al(b_pts)) : nullptr;
-  float* d_pose = (float*)(base + al(b_begin) + al(b_pts) + al(b_offs));
-  float* d_cov = (float*)(base + al(b_begin) + al(b_pts) + al(b_offs) + al(b_pose));
-  char* dx = base + al(b_begin) + al(b_pts) + al(b_offs) + al(b_pose) + al(b_cov);
-  HIP_TRY(hipMemcpyAsync(d_begin, begin_world, b_begin, hipMemcpyHostToDevice, h->stream));
-  if (b_pts) HIP_TRY(hipMemcpyAsync(d_pts, pts_xy, b_pts, hipMemcpyHostToDevice, h->stream));
-  if (d_offs) HIP_TRY(hipMemcpyAsync(d_offs, scan_offsets, b_offs, hipMemcpyHostToDevice, h->stream));
-  if (out_cov) HIP_TRY(hipMemcpyAsync(d_cov, out_cov, b_cov, hipMemcpyHostToDevice, h->stream));  // in/out
-  if (b_goffs) HIP_TRY(hipMemcpyAsync(dx + o_goffs, sr->group_offsets, b_goffs, hipMemcpyHostToDevice, h->stream));
-  if (b_bpose) HIP_TRY(hipMemcpyAsync(dx + o_bpose, sr->out_best_pose, b_bpose, hipMemcpyHostToDevice, h->stream));  // in/out
-  int hint = shared_n;
-  if (scan_offsets) {
-    hint = 0;
-    for (int i = 0; i < batch; ++i) {
-      const int ni = scan_offsets[i + 1] - scan_offsets[i];
-      if (ni > hint) hint = ni;
-    }
-  }
-  if (int rc = launch(d_begin, d_pts, d_offs, hint, d_pose, out_cov ? d_cov : nullptr, dx, scan_offsets ? hint : 0)) return rc;
-  HIP_TRY(hipMemcpyAsync(out_pose, d_pose, b_pose, hipMemcpyDeviceToHost, h->stream));
-  if (out_cov) HIP_TRY(hipMemcpyAsync(out_cov, d_cov, b_cov, hipMemcpyDeviceToHost, h->stream));
+  if (int rc = launch(base, d_pts, d_offs, hint, hint)) return rc;
+  HIP_TRY(hipMemcpyAsync(out_pose, base + L.pose, b.begin, hipMemcpyDeviceToHost, h->stream));
+  if (out_cov) HIP_TRY(hipMemcpyAsync(out_cov, base + L.cov, b.cov, hipMemcpyDeviceToHost, h->stream));
   if (sr) {
-    HIP_TRY(hipMemcpyAsync(sr->out_lh, dx, b_lh, hipMemcpyDeviceToHost, h->stream));
-    if (b_res) HIP_TRY(hipMemcpyAsync(sr->out_res, dx + o_res, b_res, hipMemcpyDeviceToHost, h->stream));
-    if (b_idx) HIP_TRY(hipMemcpyAsync(sr->out_index, dx + o_idx, b_idx, hipMemcpyDeviceToHost, h->stream));
-    if (b_bscore) HIP_TRY(hipMemcpyAsync(sr->out_score, dx + o_bscore, b_bscore, hipMemcpyDeviceToHost, h->stream));
-    if (b_bpose) HIP_TRY(hipMemcpyAsync(sr->out_best_pose, dx + o_bpose, b_bpose, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(sr->out_lh, base + L.lh, b.lh, hipMemcpyDeviceToHost, h->stream));
+    if (b.res) HIP_TRY(hipMemcpyAsync(sr->out_res, base + L.res, b.res, hipMemcpyDeviceToHost, h->stream));
+    if (b.idx) HIP_TRY(hipMemcpyAsync(sr->out_index, base + L.idx, b.idx, hipMemcpyDeviceToHost, h->stream));
+    if (b.bscore) HIP_TRY(hipMemcpyAsync(sr->out_score, base + L.bscore, b.bscore, hipMemcpyDeviceToHost, h->stream));
+    if (b.bpose) HIP_TRY(hipMemcpyAsync(sr->out_best_pose, base + L.bpose, b.bpose, hipMemcpyDeviceToHost, h->stream));
   }
   HIP_TRY(hipStreamSynchronize(h->stream));
   return HSM_OK;
@@ -1665,25 +1571,18 @@ static bool scan_is_read_once(const hsm_ctx* h, int n) {
 
 // stage a host scan where the matcher can read it: pinned mapped host memory when it will be read
 // once (register resident), device memory otherwise
-static int stage_scan(hsm_ctx* h, const float* pts_xy, int n, float2*& d_buf, size_t& d_cap, const float2** out) {
+static int stage_scan(hsm_ctx* h, const float* pts_xy, int n, Buf<float2>& d_buf, const float2** out) {
   // (a dense scan for the multi-workgroup matcher is re-read every GN step: it must live in device memory)
   // (and so does the exact-order form)
   if (scan_is_read_once(h, n)) {
-    if (!h->h_scan_pinned || (size_t)n > h->h_scan_pinned_cap) {  // (also the empty first scan of a fresh context)
-      if (h->h_scan_pinned) HIP_TRY(hipHostFree(h->h_scan_pinned));
-      h->h_scan_pinned = nullptr;
-      h->h_scan_pinned_cap = 0;
-      const size_t want = n < 4096 ? 4096 : (size_t)n + n / 2;
-      HIP_TRY(hipHostMalloc((void**)&h->h_scan_pinned, want * sizeof(float2), hipHostMallocMapped));
-      h->h_scan_pinned_cap = want;
-    }
+    if (int rc = h->h_scan_pinned.reserve(n > 0 ? n : 1, kScanGrowth)) return rc;  // (1: also the empty first scan of a fresh context)
     if (n > 0) memcpy(h->h_scan_pinned, pts_xy, (size_t)n * sizeof(float2));
     float2* dev = nullptr;
     HIP_TRY(hipHostGetDevicePointer((void**)&dev, h->h_scan_pinned, 0));
     *out = dev;
     return HSM_OK;
   }
-  if (int rc = ensure_scan_capacity(d_buf, d_cap, (size_t)n)) return rc;
+  if (int rc = d_buf.reserve((size_t)n, kScanGrowth)) return rc;
   if (n > 0) HIP_TRY(hipMemcpyAsync(d_buf, pts_xy, (size_t)n * sizeof(float2), hipMemcpyHostToDevice, h->stream));
   *out = d_buf;
   return HSM_OK;
@@ -1702,17 +1601,9 @@ static int stage_scan_overlapped(hsm_ctx* h, const float* pts_xy, int n, const f
     HIP_TRY(hipEventCreateWithFlags(&h->copy_evt, hipEventDisableTiming));
   }
   std::swap(h->d_retained, h->d_retained_alt);
-  std::swap(h->d_retained_cap, h->d_retained_alt_cap);
-  if (int rc = ensure_scan_capacity(h->d_retained, h->d_retained_cap, (size_t)n)) return rc;
-  if ((size_t)n > h->h_copy_pinned_cap) {
-    HIP_TRY(hipStreamSynchronize(h->copy_stream));
-    if (h->h_copy_pinned) HIP_TRY(hipHostFree(h->h_copy_pinned));
-    h->h_copy_pinned = nullptr;
-    h->h_copy_pinned_cap = 0;
-    const size_t want = (size_t)n + (size_t)n / 2;
-    HIP_TRY(hipHostMalloc((void**)&h->h_copy_pinned, want * sizeof(float2), hipHostMallocDefault));
-    h->h_copy_pinned_cap = want;
-  }
+  if (int rc = h->d_retained.reserve((size_t)n, kScanGrowth)) return rc;
+  if (!h->h_copy_pinned.holds((size_t)n)) HIP_TRY(hipStreamSynchronize(h->copy_stream));
+  if (int rc = h->h_copy_pinned.reserve((size_t)n, kHalfMore)) return rc;
   memcpy(h->h_copy_pinned, pts_xy, (size_t)n * sizeof(float2));
   HIP_TRY(hipMemcpyAsync(h->d_retained, h->h_copy_pinned, (size_t)n * sizeof(float2), hipMemcpyHostToDevice, h->copy_stream));
   HIP_TRY(hipEventRecord(h->copy_evt, h->copy_stream));
@@ -1765,7 +1656,7 @@ static int match_impl(hsm_ctx* h, const float begin_world[3], const float* pts_x
     // hipStreamQuery costs half of what the overlap gains: 0.1855 against 0.179 ms per configs[4] step)
     if (to_device && h->overlap_upload && n > 0 && h->queued_update) {
       if (int rc = stage_scan_overlapped(h, pts_xy, n, &pts)) return rc;
-    } else if (int rc = stage_scan(h, pts_xy, n, h->d_retained, h->d_retained_cap, &pts)) {
+    } else if (int rc = stage_scan(h, pts_xy, n, h->d_retained, &pts)) {
       return rc;
     }
   }
@@ -1786,7 +1677,7 @@ int hsm_match_level(hsm_ctx* h, int level, const float begin_world[3], const flo
   std::lock_guard<std::mutex> lk(h->mu);
   if (int rc = select_device(h)) return rc;
   const float2* pts = nullptr;
-  if (int rc = stage_scan(h, pts_level_xy, n, h->d_scan, h->d_scan_cap, &pts)) return rc;
+  if (int rc = stage_scan(h, pts_level_xy, n, h->d_scan, &pts)) return rc;
   MatchParams P;
   memset(&P, 0, sizeof P);
   P.lv[level] = level_view(h->levels[level], 1.0f, 1 + max_iterations);
@@ -1835,14 +1726,7 @@ static int update_impl(hsm_ctx* h, const float pose_world[3], const float* pts_x
       HIP_TRY(hipEventSynchronize(h->upd_evt[slot]));
       h->upd_busy[slot] = false;
     }
-    if ((size_t)n > h->h_upd_cap[slot]) {
-      if (h->h_upd_pinned[slot]) HIP_TRY(hipHostFree(h->h_upd_pinned[slot]));
-      h->h_upd_pinned[slot] = nullptr;
-      h->h_upd_cap[slot] = 0;
-      const size_t want = n < 4096 ? 4096 : (size_t)n + n / 2;
-      HIP_TRY(hipHostMalloc((void**)&h->h_upd_pinned[slot], want * sizeof(float2), hipHostMallocMapped));
-      h->h_upd_cap[slot] = want;
-    }
+    if (int rc = h->h_upd_pinned[slot].reserve((size_t)n, kScanGrowth)) return rc;
     if (!h->upd_evt[slot]) HIP_TRY(hipEventCreateWithFlags(&h->upd_evt[slot], hipEventDisableTiming));
     if (n > 0) memcpy(h->h_upd_pinned[slot], pts_xy, (size_t)n * sizeof(float2));
     if (n <= h->update_zero_copy_max) {
@@ -1850,13 +1734,13 @@ static int update_impl(hsm_ctx* h, const float pose_world[3], const float* pts_x
       if (n > 0) HIP_TRY(hipHostGetDevicePointer((void**)&dev, h->h_upd_pinned[slot], 0));
       d_level0 = n > 0 ? dev : h->d_scan;
     } else {
-      if (int rc = ensure_scan_capacity(h->d_scan, h->d_scan_cap, (size_t)n)) return rc;
+      if (int rc = h->d_scan.reserve((size_t)n, kScanGrowth)) return rc;
       HIP_TRY(hipMemcpyAsync(h->d_scan, h->h_upd_pinned[slot], (size_t)n * sizeof(float2), hipMemcpyHostToDevice,
                              h->stream));
       d_level0 = h->d_scan;
     }
   } else if (!d_level0) {
-    if (int rc = ensure_scan_capacity(h->d_scan, h->d_scan_cap, (size_t)n)) return rc;
+    if (int rc = h->d_scan.reserve((size_t)n, kScanGrowth)) return rc;
     if (n > 0)
       HIP_TRY(hipMemcpyAsync(h->d_scan, pts_xy, (size_t)n * sizeof(float2), hipMemcpyHostToDevice, h->stream));
     d_level0 = h->d_scan;
@@ -1879,7 +1763,7 @@ static int update_impl(hsm_ctx* h, const float pose_world[3], const float* pts_x
       coarse_same_container = h->retained_origo[0] == o[0] && h->retained_origo[1] == o[1];
     } else {
       if (rn > 0 && !h->d_retained_current) {
-        if (int rc = ensure_scan_capacity(h->d_retained, h->d_retained_cap, (size_t)rn)) return rc;
+        if (int rc = h->d_retained.reserve((size_t)rn, kScanGrowth)) return rc;
         HIP_TRY(hipMemcpyAsync(h->d_retained, h->retained_pts.data(), (size_t)rn * sizeof(float2),
                                hipMemcpyHostToDevice, h->stream));
         h->d_retained_current = true;
@@ -1933,7 +1817,7 @@ int hsm_update_by_scan_level(hsm_ctx* h, int level, const float pose_world[3], c
     if (int rc = merge_device_boxes(h)) return rc;
   if (int rc = order_after_foreign_match(h)) return rc;
   const float zero[2] = {0.0f, 0.0f};
-  if (int rc = ensure_scan_capacity(h->d_scan, h->d_scan_cap, (size_t)n)) return rc;
+  if (int rc = h->d_scan.reserve((size_t)n, kScanGrowth)) return rc;
   if (n > 0)
     HIP_TRY(hipMemcpyAsync(h->d_scan, pts_level_xy, (size_t)n * sizeof(float2), hipMemcpyHostToDevice, h->stream));
   UpdateBatch batch;
@@ -2082,19 +1966,14 @@ int hsm_update_by_scans(hsm_ctx* h, int count, const float* poses_world, const f
     if (stream_capturing(f.s))
       return fail(HSM_ERR_INVALID, "hsm_update_by_scans: a caller's stream that this context matches on is being captured into a graph");
   // one staging block: end points | poses | offsets (the copies are queued on the context's stream, in front of the update)
-  const size_t pts_bytes = (total * sizeof(float2) + 255) & ~(size_t)255, pose_bytes = ((size_t)count * 3 * sizeof(float) + 255) & ~(size_t)255;
-  const size_t need = pts_bytes + pose_bytes + ((size_t)count + 1) * sizeof(int);
-  if (need > h->d_upd_stage_cap) {
-    if (h->d_upd_stage) HIP_TRY(hipFree(h->d_upd_stage));
-    h->d_upd_stage = nullptr;
-    h->d_upd_stage_cap = 0;
-    HIP_TRY(hipMalloc(&h->d_upd_stage, need + need / 2));
-    h->d_upd_stage_cap = need + need / 2;
-  }
-  char* base = static_cast<char*>(h->d_upd_stage);
-  float* d_pts = reinterpret_cast<float*>(base);
-  float* d_poses = reinterpret_cast<float*>(base + pts_bytes);
-  int* d_offs = reinterpret_cast<int*>(base + pts_bytes + pose_bytes);
+  Carver c;
+  const size_t o_pts = c.take(total * sizeof(float2)), o_poses = c.take((size_t)count * 3 * sizeof(float));
+  const size_t o_offs = c.take(((size_t)count + 1) * sizeof(int));
+  if (int rc = h->d_upd_stage.reserve(c.total(), kHalfMore)) return rc;
+  char* base = h->d_upd_stage;
+  float* d_pts = reinterpret_cast<float*>(base + o_pts);
+  float* d_poses = reinterpret_cast<float*>(base + o_poses);
+  int* d_offs = reinterpret_cast<int*>(base + o_offs);
   if (total > 0) HIP_TRY(hipMemcpyAsync(d_pts, pts_xy, total * sizeof(float2), hipMemcpyHostToDevice, h->stream));
   HIP_TRY(hipMemcpyAsync(d_poses, poses_world, (size_t)count * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
   if (scan_offsets)
@@ -2107,24 +1986,16 @@ int hsm_update_by_scans(hsm_ctx* h, int count, const float* poses_world, const f
 // clouds; the int behind it is the survivor count), the sensor-geometry table (16 B per beam covers the
 // float2 and the double2 variant) and the container
 static int ensure_ingest_capacity(hsm_ctx* h, int n) {
-  if (h->d_ranges && (size_t)n <= h->ingest_cap) return HSM_OK;
-  (void)hipFree(h->d_ranges);
-  (void)hipFree(h->d_trig);
-  (void)hipFree(h->d_ingest);
-  h->d_ranges = nullptr;
-  h->d_trig = nullptr;
-  h->d_ingest = nullptr;
-  h->ingest_cap = 0;
+  if (h->d_ingest && h->d_ingest.holds((size_t)n)) return HSM_OK;
+  if (int rc = h->d_ingest.drop()) return rc;  // (first: it stands for the trio)
   h->trig_n = -1;
-  const size_t want = n < 2048 ? 2048 : (size_t)n + n / 2;
-  HIP_TRY(hipMalloc((void**)&h->d_ranges, 3 * want * sizeof(float) + sizeof(int)));
-  HIP_TRY(hipMalloc((void**)&h->d_trig, want * sizeof(double2)));
-  HIP_TRY(hipMalloc((void**)&h->d_ingest, want * sizeof(float2)));
-  h->ingest_cap = want;
-  return HSM_OK;
+  const size_t want = grown_capacity((size_t)n, {2048, 50});
+  if (int rc = h->d_ranges.reserve(3 * want + 1)) return rc;  // (+ the survivor count, an int)
+  if (int rc = h->d_trig.reserve(want)) return rc;
+  return h->d_ingest.reserve(want);
 }
 
-static int* ingest_count_ptr(hsm_ctx* h) { return reinterpret_cast<int*>(h->d_ranges + 3 * h->ingest_cap); }
+static int* ingest_count_ptr(hsm_ctx* h) { return reinterpret_cast<int*>(h->d_ranges + 3 * h->d_ingest.count()); }
 
 // fetch the survivor count + the container the kernel on h->stream just produced
 static int finish_ingest(hsm_ctx* h, float* out_pts_xy, int* out_n) {
@@ -2171,7 +2042,7 @@ int hsm_ingest_laser_scan(hsm_ctx* h, const float* ranges, int n, float angle_mi
   if (n > 0) HIP_TRY(hipMemcpyAsync(h->d_ranges, ranges, (size_t)n * sizeof(float), hipMemcpyHostToDevice, h->stream));
   const float maxRangeForContainer = range_max - 0.1f;  // :493
   hipLaunchKernelGGL(ingest_laser_scan_kernel, dim3(1), dim3(1024), 0, h->stream, h->d_ranges,
-                     reinterpret_cast<const float2*>(h->d_trig), n, range_min, maxRangeForContainer, scale_to_map,
+                     reinterpret_cast<const float2*>(h->d_trig.p), n, range_min, maxRangeForContainer, scale_to_map,
                      h->d_ingest, ingest_count_ptr(h));
   HIP_TRY(hipGetLastError());
   h->ingest_origo[0] = h->ingest_origo[1] = 0.0f;  // dataContainer.setOrigo(Vector2f::Zero()), :491
@@ -2248,7 +2119,7 @@ int hsm_ingest_laser_scan_tf(hsm_ctx* h, const float* ranges, int n, float angle
   if (n > 0) HIP_TRY(hipMemcpyAsync(h->d_ranges, ranges, (size_t)n * sizeof(float), hipMemcpyHostToDevice, h->stream));
   CloudIngestParams P{};
   P.ranges = h->d_ranges;
-  P.unit = reinterpret_cast<const double2*>(h->d_trig);
+  P.unit = h->d_trig;
   P.n = n;
   P.range_min = range_min;
   P.range_cutoff = range_cutoff < 0 ? (double)range_max : range_cutoff;
@@ -2275,30 +2146,7 @@ int hsm_update_by_ingested(hsm_ctx* h, const float pose_world[3]) {
 
 // ---- B raw scans of one sensor geometry: ingestion kernels + the batched matcher, one stream-ordered sequence ----
 
-namespace {
-
-// workspace of hsm_match_batch_ranges_device, byte offsets: counts[B] | offsets[B + 1] | copy of the ranges[B * n] |
-// endpoints[max(B * n, 1)], each region 256-byte aligned.  The endpoint region keeps one element when every scan is empty:
-// the matcher clamps an empty scan's loads to element 0 (gn_match_exact.h).  false = sizes the entry refuses.
-struct RangesLayout {
-  size_t counts, offsets, copy, pts, total;
-};
-
-bool ranges_layout(int batch, int n, RangesLayout* L) {
-  if (batch < 0 || n < 0 || n > HSM_MAX_UPDATE_BEAMS || (size_t)batch * (size_t)n > (size_t)INT_MAX) return false;
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t bn = (size_t)batch * (size_t)n;
-  L->counts = 0;
-  L->offsets = L->counts + al((size_t)batch * sizeof(int));
-  L->copy = L->offsets + al(((size_t)batch + 1) * sizeof(int));
-  L->pts = L->copy + al(bn * sizeof(float));
-  L->total = L->pts + al((bn > 0 ? bn : 1) * sizeof(float2));
-  return true;
-}
-
-}  // namespace
-
-size_t hsm_match_batch_ranges_workspace(int batch, int n) {
+size_t hsm_match_batch_ranges_workspace(int batch, int n) {  // (the layout: stage_layout.h)
   RangesLayout L;
   return ranges_layout(batch, n, &L) ? L.total : 0;
 }
@@ -2402,24 +2250,18 @@ int hsm_match_batch_ranges(hsm_ctx* h, int batch, const float* begin_world, cons
   if (!ranges_layout(batch, n, &L))
     return fail(HSM_ERR_TOO_LARGE, "hsm_match_batch_ranges: n > HSM_MAX_UPDATE_BEAMS or batch * n > INT_MAX");
   if (batch == 0) return HSM_OK;
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
   const size_t b_begin = (size_t)batch * 3 * sizeof(float), b_cov = (size_t)batch * 9 * sizeof(float);
   const size_t b_counts = (size_t)batch * sizeof(int), b_ranges = (size_t)batch * n * sizeof(float);
   // device block: start poses | poses | covariances | counts | raw ranges | workspace
-  const size_t o_pose = al(b_begin), o_cov = o_pose + al(b_begin), o_counts = o_cov + al(b_cov);
-  const size_t o_ranges = o_counts + al(b_counts), o_ws = o_ranges + al(b_ranges), need = o_ws + L.total;
+  Carver c;
+  const size_t o_begin = c.take(b_begin), o_pose = c.take(b_begin), o_cov = c.take(b_cov), o_counts = c.take(b_counts);
+  const size_t o_ranges = c.take(b_ranges), o_ws = c.take(L.total);
   std::lock_guard<std::mutex> lk(h->mu);
   if (int rc = select_device(h)) return rc;
-  if (need > h->d_rbatch_cap) {
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (h->d_rbatch) HIP_TRY(hipFree(h->d_rbatch));
-    h->d_rbatch = nullptr;
-    h->d_rbatch_cap = 0;
-    HIP_TRY(hipMalloc(&h->d_rbatch, need));
-    h->d_rbatch_cap = need;
-  }
-  char* base = (char*)h->d_rbatch;
-  float* d_begin = (float*)base;
+  if (!h->d_rbatch.holds(c.total())) HIP_TRY(hipStreamSynchronize(h->stream));
+  if (int rc = h->d_rbatch.reserve(c.total())) return rc;
+  char* base = h->d_rbatch;
+  float* d_begin = (float*)(base + o_begin);
   float* d_pose = (float*)(base + o_pose);
   float* d_cov = (float*)(base + o_cov);
   int* d_counts = (int*)(base + o_counts);
@@ -2438,16 +2280,6 @@ int hsm_match_batch_ranges(hsm_ctx* h, int batch, const float* begin_world, cons
   return HSM_OK;
 }
 
-static int ensure_batch_bytes(hsm_ctx* h, size_t need) {
-  if (need <= h->d_batch_cap) return HSM_OK;
-  if (h->d_batch) HIP_TRY(hipFree(h->d_batch));
-  h->d_batch = nullptr;
-  h->d_batch_cap = 0;
-  HIP_TRY(hipMalloc(&h->d_batch, need));
-  h->d_batch_cap = need;
-  return HSM_OK;
-}
-
 static int score_states(hsm_ctx* h, int level, int batch, const float* states_map, const float* pts_xy, int n,
                         float* out_lh, float* out_residual, const char* who) {
   if (int rc = valid_level(h, level)) return rc;
@@ -2456,10 +2288,10 @@ static int score_states(hsm_ctx* h, int level, int batch, const float* states_ma
   if (batch == 0) return HSM_OK;
   std::lock_guard<std::mutex> lk(h->mu);
   if (int rc = select_device(h)) return rc;
-  if (int rc = ensure_scan_capacity(h->d_scan, h->d_scan_cap, (size_t)n)) return rc;
+  if (int rc = h->d_scan.reserve((size_t)n, kScanGrowth)) return rc;
   if (n > 0) HIP_TRY(hipMemcpyAsync(h->d_scan, pts_xy, (size_t)n * sizeof(float2), hipMemcpyHostToDevice, h->stream));
-  if (int rc = ensure_batch_bytes(h, (size_t)batch * 5 * sizeof(float))) return rc;
-  float* d_states = (float*)h->d_batch;
+  if (int rc = h->d_batch.reserve((size_t)batch * 5 * sizeof(float))) return rc;
+  float* d_states = (float*)h->d_batch.p;
   float* d_lh = d_states + 3 * (size_t)batch;
   float* d_res = d_lh + (size_t)batch;
   HIP_TRY(hipMemcpyAsync(d_states, states_map, (size_t)batch * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
@@ -2503,10 +2335,10 @@ int hsm_covariance_for_poses(hsm_ctx* h, int level, int batch, const float* pose
   if (batch == 0) return HSM_OK;
   std::lock_guard<std::mutex> lk(h->mu);
   if (int rc = select_device(h)) return rc;
-  if (int rc = ensure_scan_capacity(h->d_scan, h->d_scan_cap, (size_t)n)) return rc;
+  if (int rc = h->d_scan.reserve((size_t)n, kScanGrowth)) return rc;
   if (n > 0) HIP_TRY(hipMemcpyAsync(h->d_scan, pts_xy, (size_t)n * sizeof(float2), hipMemcpyHostToDevice, h->stream));
-  if (int rc = ensure_batch_bytes(h, (size_t)batch * (3 + 9 + 9 + 7) * sizeof(float))) return rc;
-  float* d_poses = (float*)h->d_batch;
+  if (int rc = h->d_batch.reserve((size_t)batch * (3 + 9 + 9 + 7) * sizeof(float))) return rc;
+  float* d_poses = (float*)h->d_batch.p;
   float* d_map = d_poses + 3 * (size_t)batch;
   float* d_world = d_map + 9 * (size_t)batch;
   float* d_lh7 = d_world + 9 * (size_t)batch;
@@ -2542,15 +2374,8 @@ int hsm_ray_distances(hsm_ctx* h, int level, float origin_x, float origin_y, flo
   if (n == 0) return HSM_OK;
   std::lock_guard<std::mutex> lk(h->mu);
   if (int rc = select_device(h)) return rc;
-  const size_t need = (size_t)n * 7 * sizeof(float);  // begin[2] end[2] dist[1] hit[2]
-  if (need > h->d_batch_cap) {
-    if (h->d_batch) HIP_TRY(hipFree(h->d_batch));
-    h->d_batch = nullptr;
-    h->d_batch_cap = 0;
-    HIP_TRY(hipMalloc(&h->d_batch, need));
-    h->d_batch_cap = need;
-  }
-  float* d = (float*)h->d_batch;
+  if (int rc = h->d_batch.reserve((size_t)n * 7 * sizeof(float))) return rc;  // begin[2] end[2] dist[1] hit[2]
+  float* d = (float*)h->d_batch.p;
   RayQueryParams P;
   const Level& L = h->levels[level];
   P.logodds = L.d_logodds;
@@ -2584,13 +2409,7 @@ int hsm_occupancy_grid(hsm_ctx* h, int level, signed char* out) {
   std::lock_guard<std::mutex> lk(h->mu);
   if (int rc = select_device(h)) return rc;
   Level& L = h->levels[level];
-  if (L.cells() > h->d_occ_cap) {
-    (void)hipFree(h->d_occ);
-    h->d_occ = nullptr;
-    h->d_occ_cap = 0;
-    HIP_TRY(hipMalloc((void**)&h->d_occ, L.cells()));
-    h->d_occ_cap = L.cells();
-  }
+  if (int rc = h->d_occ.reserve(L.cells())) return rc;
   hipLaunchKernelGGL(occupancy_grid_kernel, dim3(grid_for(L.cells() / 4)), dim3(256), 0, h->stream, L.d_logodds,
                      L.cells(), h->d_occ);
   HIP_TRY(hipGetLastError());
@@ -2687,16 +2506,14 @@ struct hsm_group {
   std::vector<hsm_ctx*> members;
   std::vector<std::unique_ptr<GroupWorker>> workers;  // workers[r - 1] serves replica r
   // device-resident gather (hsm_group_match_batch_device): per replica a result block on ITS device and an event
-  std::vector<float*> d_pose, d_cov;
-  std::vector<size_t> d_cap;  // scans
+  std::vector<Buf<float>> d_pose, d_cov;  // (d_cov is allocated last: it holding 9 n floats says both serve n scans)
   std::vector<hipEvent_t> evt;
   // the gather itself: RCCL over the group's devices (one communicator per replica, ncclCommInitAll on first use), or
   // peer copies.  gather_pref = what was asked for (hsm_group_set_gather / env HSM_GROUP_GATHER), gather_mode = what runs.
   int gather_pref = HSM_GATHER_AUTO, gather_mode = HSM_GATHER_AUTO;
   bool force_p2p = false;  // hsm_group_debug_force_p2p: every shard, the root's too, through grouped ncclSend / ncclRecv
   std::vector<ncclComm_t> comms;
-  std::vector<float*> d_all_pose, d_all_cov;  // all-gather receive blocks of the replicas other than the root
-  std::vector<size_t> d_all_cap;              // floats of pose block (cov block: 3x)
+  std::vector<Buf<float>> d_all_pose, d_all_cov;  // all-gather receive blocks of the replicas other than the root (likewise)
   std::string gather_note;                    // why AUTO settled on peer copies, if it did
   // HSM_GATHER_DIRECT: one mailbox exchange per replica (pose_exchange.hip), re-made when the gathered row count changes
   std::vector<hsm_exchange*> xpose, xcov;
@@ -2837,13 +2654,8 @@ int hsm_group_create(float map_resolution, int size_x, int size_y, unsigned leve
     GroupWorker* w = g->workers.back().get();
     w->th = std::thread(group_worker_main, w);
   }
-  g->d_pose.assign((size_t)n_devices, nullptr);
-  g->d_cov.assign((size_t)n_devices, nullptr);
-  g->d_cap.assign((size_t)n_devices, 0);
+  for (std::vector<Buf<float>>* v : {&g->d_pose, &g->d_cov, &g->d_all_pose, &g->d_all_cov}) v->resize((size_t)n_devices);
   g->evt.assign((size_t)n_devices, nullptr);
-  g->d_all_pose.assign((size_t)n_devices, nullptr);
-  g->d_all_cov.assign((size_t)n_devices, nullptr);
-  g->d_all_cap.assign((size_t)n_devices, 0);
   if (const char* env = getenv("HSM_GROUP_GATHER")) {
     if (strcmp(env, "rccl") == 0) g->gather_pref = HSM_GATHER_RCCL;
     else if (strcmp(env, "peer") == 0) g->gather_pref = HSM_GATHER_PEER;
@@ -2916,15 +2728,9 @@ void hsm_group_destroy(hsm_group* g) {
   TeardownLog log_, *log = &log_;  // (as hsm_destroy: name the first failing call, leave no error behind for the next caller)
   for (size_t r = 0; r < g->members.size(); ++r) {
     if (g->members[r]) TEARDOWN(log, hipSetDevice(g->members[r]->device));
-    if (r < g->d_all_pose.size()) {
-      TEARDOWN(log, hipFree(g->d_all_pose[r]));
-      TEARDOWN(log, hipFree(g->d_all_cov[r]));
-    }
-    if (r < g->d_pose.size()) {
-      TEARDOWN(log, hipFree(g->d_pose[r]));
-      TEARDOWN(log, hipFree(g->d_cov[r]));
-      if (g->evt[r]) TEARDOWN(log, hipEventDestroy(g->evt[r]));
-    }
+    for (std::vector<Buf<float>>* v : {&g->d_pose, &g->d_cov, &g->d_all_pose, &g->d_all_cov})
+      if (r < v->size()) (*v)[r].release(log);
+    if (r < g->evt.size() && g->evt[r]) TEARDOWN(log, hipEventDestroy(g->evt[r]));
   }
   for (hsm_ctx* h : g->members) hsm_destroy(h);
   delete g;
@@ -3022,25 +2828,17 @@ int hsm_group_match_batch_device(hsm_group* g, const int* counts, const float* c
     std::lock_guard<std::mutex> lk(h->mu);
     if (int rc2 = select_device(h)) return rc2;
     if (!g->evt[(size_t)r]) HIP_TRY(hipEventCreateWithFlags(&g->evt[(size_t)r], hipEventDisableTiming));
-    if (((rccl && equal) || direct) && r != root && total * 3 > g->d_all_cap[(size_t)r]) {  // all-gather receive blocks of a non-root replica
-      (void)hipFree(g->d_all_pose[(size_t)r]);
-      (void)hipFree(g->d_all_cov[(size_t)r]);
-      g->d_all_pose[(size_t)r] = g->d_all_cov[(size_t)r] = nullptr;
-      g->d_all_cap[(size_t)r] = 0;
-      HIP_TRY(hipMalloc((void**)&g->d_all_pose[(size_t)r], total * 3 * sizeof(float)));
-      HIP_TRY(hipMalloc((void**)&g->d_all_cov[(size_t)r], total * 9 * sizeof(float)));
-      g->d_all_cap[(size_t)r] = total * 3;
-    }
+    // a pair of result blocks for `rows` scans: the covariance block goes first and comes back last
+    auto reserve_pair = [](Buf<float>& pose, Buf<float>& cov, size_t rows) -> int {
+      if (cov.holds(rows * 9)) return HSM_OK;
+      if (int rc2 = cov.drop()) return rc2;
+      if (int rc2 = pose.replace(rows * 3 * sizeof(float))) return rc2;
+      return cov.reserve(rows * 9);
+    };
+    if (((rccl && equal) || direct) && r != root)  // all-gather receive blocks of a non-root replica
+      if (int rc2 = reserve_pair(g->d_all_pose[(size_t)r], g->d_all_cov[(size_t)r], total)) return rc2;
     if (n > 0) {
-      if (n > g->d_cap[(size_t)r]) {
-        (void)hipFree(g->d_pose[(size_t)r]);
-        (void)hipFree(g->d_cov[(size_t)r]);
-        g->d_pose[(size_t)r] = g->d_cov[(size_t)r] = nullptr;
-        g->d_cap[(size_t)r] = 0;
-        HIP_TRY(hipMalloc((void**)&g->d_pose[(size_t)r], n * 3 * sizeof(float)));
-        HIP_TRY(hipMalloc((void**)&g->d_cov[(size_t)r], n * 9 * sizeof(float)));
-        g->d_cap[(size_t)r] = n;
-      }
+      if (int rc2 = reserve_pair(g->d_pose[(size_t)r], g->d_cov[(size_t)r], n)) return rc2;
       if (int rc2 = match_batch_device_nolock(h, (int)n, d_begin_world[r], d_pts_xy[r],
                                               d_scan_offsets ? d_scan_offsets[r] : nullptr, shared_n, g->d_pose[(size_t)r],
                                               d_out_cov_all ? g->d_cov[(size_t)r] : nullptr, h->stream))
@@ -3243,15 +3041,9 @@ int hsm_download_cells(hsm_ctx* h, int level, int x0, int y0, int x1, int y1, vo
     return fail(HSM_ERR_INVALID, "hsm_download_cells: bad rectangle");
   const int w = x1 - x0 + 1, hgt = y1 - y0 + 1;
   const size_t need = (size_t)w * hgt * 8;
-  if (need > h->d_cells_cap) {
-    if (h->d_cells) HIP_TRY(hipFree(h->d_cells));
-    h->d_cells = nullptr;
-    h->d_cells_cap = 0;
-    HIP_TRY(hipMalloc(&h->d_cells, need + need / 2));
-    h->d_cells_cap = need + need / 2;
-  }
+  if (int rc = h->d_cells.reserve(need, kHalfMore)) return rc;
   hipLaunchKernelGGL(pack_cells_kernel, dim3(grid_for((size_t)w * hgt)), dim3(256), 0, h->stream, level_rw(L), x0, y0, w,
-                     hgt, reinterpret_cast<int2*>(h->d_cells));
+                     hgt, reinterpret_cast<int2*>(h->d_cells.p));
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpy2DAsync(dst_cells, (size_t)dst_pitch_cells * 8, h->d_cells, (size_t)w * 8, (size_t)w * 8, hgt,
                            hipMemcpyDeviceToHost, h->stream));
@@ -3297,7 +3089,7 @@ int hsm_hessian_derivs(hsm_ctx* h, int level, const float pose_map[3], const flo
   if (!pose_map || n < 0 || (n > 0 && !pts) || !H || !dTr) return fail(HSM_ERR_INVALID, "bad argument");
   std::lock_guard<std::mutex> lk(h->mu);
   if (int rc = select_device(h)) return rc;
-  if (int rc = ensure_scan_capacity(h->d_scan, h->d_scan_cap, (size_t)n)) return rc;
+  if (int rc = h->d_scan.reserve((size_t)n, kScanGrowth)) return rc;
   if (n > 0) HIP_TRY(hipMemcpyAsync(h->d_scan, pts, (size_t)n * sizeof(float2), hipMemcpyHostToDevice, h->stream));
   const LevelView v = level_view(h->levels[level], 1.0f, 1);
   float* d_out = h->d_small + 16;
@@ -3328,7 +3120,7 @@ int hsm_eval_beams(hsm_ctx* h, int level, const float pose_map[3], const float* 
   if (n == 0) return HSM_OK;
   std::lock_guard<std::mutex> lk(h->mu);
   if (int rc = select_device(h)) return rc;
-  if (int rc = ensure_scan_capacity(h->d_scan, h->d_scan_cap, (size_t)n * 3)) return rc;  // pts + float4 out
+  if (int rc = h->d_scan.reserve((size_t)n * 3, kScanGrowth)) return rc;  // pts + float4 out
   HIP_TRY(hipMemcpyAsync(h->d_scan, pts, (size_t)n * sizeof(float2), hipMemcpyHostToDevice, h->stream));
   float4* d_out = reinterpret_cast<float4*>(h->d_scan + (((size_t)n + 1) & ~(size_t)1));
   const LevelView v = level_view(h->levels[level], 1.0f, 1);

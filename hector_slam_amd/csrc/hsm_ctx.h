@@ -14,6 +14,7 @@
 #include "gn_match.h"
 #include "hector_mi355/capi.h"
 #include "hsm_host.h"
+#include "stage_layout.h"
 
 namespace hsm {
 struct BeamRec;  // map_update.h (its kernels are not templates: only hector_mi355.hip includes that header)
@@ -66,7 +67,68 @@ struct Level {
   }
 };
 
+// Teardown never stops at a failing call (everything else still has to be released), but it must not swallow one either: HIP
+// keeps the last failure per thread, and the next hipGetLastError() of an unrelated call -- the launch check of the next
+// hsm_create on this thread -- would report it as its own.  The first failing call is kept for hsm_last_error(), the runtime's
+// per-thread state is cleared at the end (hsm_destroy).
+struct TeardownLog {
+  std::string first;
+  void note(const char* what, hipError_t e) {
+    if (e == hipSuccess || !first.empty()) return;
+    first = std::string(what) + ": " + hipGetErrorString(e);
+  }
+};
+#define TEARDOWN(log, expr) \
+  do {                      \
+    hipError_t e__ = (expr); \
+    if (log) (log)->note(#expr, e__); \
+  } while (0)
 
+// One block that grows on demand and never shrinks: device memory, pinned host memory, or pinned host memory the device reads
+// and writes in place.  Growing REPLACES the block (the contents go, and a free waits for queued work that still reads it), so
+// a caller that must wait for a stream first, or has state tied to the old block, asks holds() before it reserves.
+enum BufKind : unsigned char { kBufDevice, kBufPinned, kBufPinnedMapped };
+
+struct GrowBuf {
+  void* p = nullptr;
+  size_t bytes = 0;
+  BufKind kind = kBufDevice;
+  hipError_t free_block() { return kind == kBufDevice ? hipFree(p) : hipHostFree(p); }
+  int drop() {  // (a failing free leaves the block as it was)
+    if (p) HSM_HIP_TRY(free_block());
+    p = nullptr;
+    bytes = 0;
+    return HSM_OK;
+  }
+  int replace(size_t want_bytes) {  // null and empty after a failure
+    if (int rc = drop()) return rc;
+    if (kind == kBufDevice)
+      HSM_HIP_TRY(hipMalloc(&p, want_bytes));
+    else
+      HSM_HIP_TRY(hipHostMalloc(&p, want_bytes, kind == kBufPinned ? hipHostMallocDefault : hipHostMallocMapped));
+    bytes = want_bytes;
+    return HSM_OK;
+  }
+  void release(TeardownLog* log) {
+    if (p) TEARDOWN(log, free_block());
+    p = nullptr;
+    bytes = 0;
+  }
+};
+
+// ... of elements T (char: a block carved by the byte).  `owner`: the list its context releases at teardown (hsm_ctx::bufs)
+template <class T>
+struct Buf : GrowBuf {
+  Buf() = default;
+  explicit Buf(std::vector<GrowBuf*>* owner, BufKind k = kBufDevice) {
+    kind = k;
+    owner->push_back(this);
+  }
+  operator T*() const { return static_cast<T*>(p); }
+  size_t count() const { return bytes / sizeof(T); }
+  bool holds(size_t n) const { return n * sizeof(T) <= bytes; }
+  int reserve(size_t n, Growth g = kExact) { return holds(n) ? HSM_OK : replace(grown_capacity(n, g) * sizeof(T)); }
+};
 
 // true while the caller captures `s` into a graph (the null stream never is): what is launched then runs at the caller's replays,
 // so it may neither read nor change per-stream state that eager launches rewrite or free
@@ -88,13 +150,15 @@ using hsm::UpdateBatch;
 using hsm::SpecStats;
 using hsm::kLayoutQuad;
 
+using hsm_host::Buf;
+using hsm_host::kBufPinned;
+using hsm_host::kBufPinnedMapped;
+
 struct hsm_ctx {
+  std::vector<hsm_host::GrowBuf*> bufs;  // every Buf member below enrols here as it is constructed: hsm_destroy releases these
   int device = 0;
   int layout = kLayoutQuad;
   int wps_override = 0;
-  // updateByScan returns when its kernels are QUEUED (env HSM_ASYNC_UPDATE=0: wait for them): everything
-  // that reads the map afterwards is ordered behind them on `stream`.  Host endpoints are staged in one of
-  // two pinned blocks, each guarded by the event of the update that last read it.
   bool texel_cache = true;          // env HSM_TEXEL_CACHE=0: plain gn_match_kernel for throughput launches too
   // ordering between the context's stream (updates) and caller-owned streams (hsm_match_batch_device):
   // per caller stream the update epoch it has been ordered behind, and whether it may still run a match
@@ -106,23 +170,22 @@ struct hsm_ctx {
   std::vector<ForeignStream> foreign;
   unsigned long long upd_epoch = 1;
   hipEvent_t evt_updates = nullptr, evt_foreign = nullptr;
+  // updateByScan returns when its kernels are QUEUED (env HSM_ASYNC_UPDATE=0: wait for them): everything
+  // that reads the map afterwards is ordered behind them on `stream`.  Host endpoints are staged in one of
+  // two pinned blocks (h_upd_pinned), each guarded by the event of the update that last read it.
   bool async_update = true;
   int update_zero_copy_max = 4096;  // env HSM_UPDATE_ZEROCOPY_MAX
   int merged_mark_max = 4096;       // scans below this take the one-launch mark pass (env HSM_MERGED_MARK_MAX, 0 = never)
   int scatter_texels_max = 1 << 30; // quad layout: scans below this write the texels from the apply pass (env HSM_SCATTER_TEXELS_MAX, 0 = never)
-  BeamRec* d_beam_recs = nullptr;   // dense scans: per-beam records of all levels (map_update.h BeamRec), [levels][cap]
-  size_t beam_recs_cap = 0;         // beams per level
+  Buf<BeamRec> d_beam_recs{&bufs};  // dense scans: per-beam records of all levels (map_update.h BeamRec), [HSM_MAX_LEVELS][count() / HSM_MAX_LEVELS]
   // hsm_update_by_scans_device: one UpdateBatch and one cell box per level for every scan of a call, filled on the device
   // (map_update.h update_prep_kernel); grown outside capture.  boxes: slot 0 the levels' running dirty boxes, slot 1 the last scan's
-  UpdateBatch* d_upd_batches = nullptr;
-  int* d_upd_boxes = nullptr;
-  size_t upd_scans_cap = 0;
+  Buf<UpdateBatch> d_upd_batches{&bufs};
+  Buf<int> d_upd_boxes{&bufs};  // allocated last: non-null = both blocks serve d_upd_batches.count() scans
   bool upd_boxes_outstanding = false;  // device-side updates since the host last merged their boxes into Level::bbox / dirty
   hipEvent_t evt_inputs = nullptr;     // the caller's stream at hsm_update_by_scans_device: its inputs are complete
-  void* d_upd_stage = nullptr;         // hsm_update_by_scans: poses, offsets and end points of the host arrays
-  size_t d_upd_stage_cap = 0;
-  float2* h_upd_pinned[2] = {nullptr, nullptr};
-  size_t h_upd_cap[2] = {0, 0};
+  Buf<char> d_upd_stage{&bufs};        // hsm_update_by_scans: poses, offsets and end points of the host arrays
+  Buf<float2> h_upd_pinned[2] = {Buf<float2>{&bufs, kBufPinnedMapped}, Buf<float2>{&bufs, kBufPinnedMapped}};
   hipEvent_t upd_evt[2] = {nullptr, nullptr};
   bool upd_busy[2] = {false, false};
   int upd_slot = 0;
@@ -132,46 +195,39 @@ struct hsm_ctx {
   mutable std::mutex mu;
   hipStream_t stream = nullptr;
   // single-scan staging (device) + pinned result
-  float2* d_scan = nullptr;
-  size_t d_scan_cap = 0;
-  float* d_small = nullptr;   // begin pose[3] | out pose[3] | out cov[9] | eval[12]
+  Buf<float2> d_scan{&bufs};
+  float* d_small = nullptr;   // layout: top of this header
   float* h_small = nullptr;   // pinned mirror of d_small
   // retained scan = MapRepMultiMap::dataContainers (level-0 units; scaled by 2^-l on use)
   std::vector<float> retained_pts;
   float retained_origo[2] = {0.f, 0.f};
   bool retained_valid = false;  // false until the first match (reference: empty containers)
-  float2* d_retained = nullptr;
-  size_t d_retained_cap = 0;
+  Buf<float2> d_retained{&bufs};
   bool d_retained_current = false;
   // the upload of a dense scan for matchData runs on its own stream, into the OTHER of two device buffers, from a pinned
   // staging block: it overlaps the update kernels still queued on `stream` (which read the buffer of the scan before)
   // instead of waiting behind them; the match kernel waits for the copy's event (stage_scan_overlapped)
-  float2* d_retained_alt = nullptr;
-  size_t d_retained_alt_cap = 0;
+  Buf<float2> d_retained_alt{&bufs};
   hipStream_t copy_stream = nullptr;
   hipEvent_t copy_evt = nullptr;
-  float2* h_copy_pinned = nullptr;
-  size_t h_copy_pinned_cap = 0;
+  Buf<float2> h_copy_pinned{&bufs, kBufPinned};
   bool overlap_upload = true;  // env HSM_OVERLAP_UPLOAD=0: the copy is queued on `stream` as before
   bool queued_update = false;  // an asynchronous updateByScan was queued on `stream` since the host last saw it drained
   // batch staging for the host-pointer convenience entry
-  void* d_batch = nullptr;
-  size_t d_batch_cap = 0;
+  Buf<char> d_batch{&bufs};
   // ... and for its shared-scan form (pose hypotheses of ONE scan): start poses, results and the scan in pinned, device-mapped host
   // memory -- the kernel reads each start pose once and writes each result once, straight over PCIe, no copy command either way
-  void* h_hyp_pinned = nullptr;
-  size_t h_hyp_cap = 0;
+  Buf<char> h_hyp_pinned{&bufs, kBufPinnedMapped};
   // single-scan fast path: endpoints staged in pinned, device-mapped host memory and read by the
   // matcher ONCE (they stay in VGPRs); results written by the kernel straight into h_small
-  float2* h_scan_pinned = nullptr;
-  size_t h_scan_pinned_cap = 0;
+  Buf<float2> h_scan_pinned{&bufs, kBufPinnedMapped};
   // ingested scan (hsm_ingest_laser_scan): device container + host copy, sensor trig table cache
-  float* d_ranges = nullptr;
-  void* d_trig = nullptr;           // float2 (running-angle table) or double2 (laser_geometry unit vectors)
+  // (the three blocks hold d_ingest.count() beams; d_ranges: 3 floats per beam and the survivor count behind them)
+  Buf<float> d_ranges{&bufs};
+  Buf<double2> d_trig{&bufs};       // float2 (running-angle table) or double2 (laser_geometry unit vectors)
   int trig_kind = -1;
   float ingest_origo[2] = {0.f, 0.f};
-  float2* d_ingest = nullptr;
-  size_t ingest_cap = 0;
+  Buf<float2> d_ingest{&bufs};      // allocated last: non-null = the trio is complete
   std::vector<float> h_ingest;      // endpoints as the matcher/updater see them (host copy)
   int ingest_n = -1;                // -1 = nothing ingested yet
   float trig_a0 = 0.f, trig_inc = 0.f;
@@ -184,16 +240,13 @@ struct hsm_ctx {
     float2* d;
   };
   std::vector<RangesGeometry> ranges_geoms;
-  void* d_rbatch = nullptr;  // hsm_match_batch_ranges: start poses, results, counts and the workspace of its device call
-  size_t d_rbatch_cap = 0;
-  signed char* d_occ = nullptr;     // occupancy export staging
-  size_t d_occ_cap = 0;
+  Buf<char> d_rbatch{&bufs};  // hsm_match_batch_ranges: start poses, results, counts and the workspace of its device call
+  Buf<signed char> d_occ{&bufs};    // occupancy export staging
   unsigned coop_bar_base = 0;   // value the grid-barrier counter has when the next cooperative launch starts
   float* d_partials = nullptr;  // [2][64][9] per-workgroup partial sums of gn_match_coop_kernel
   int coop_min_beams = 4096;    // single scans at least this long take the multi-workgroup matcher (env HSM_COOP_MIN)
   bool coop_tagged = true;      // env HSM_COOP_TAGGED=0: the counter grid barrier instead of the tagged-record exchange
-  void* d_cells = nullptr;  // interleaved {logodds, updateIndex} staging for hsm_download_cells
-  size_t d_cells_cap = 0;
+  Buf<char> d_cells{&bufs};  // interleaved {logodds, updateIndex} staging for hsm_download_cells
   int bpl_override = -1;  // 0 = force the memory loop (env HSM_BPL=0), -1 = auto
   int exact_batch_form = 2;      // env HSM_EXACT_BATCH: 0 = the one-wavefront-per-scan exact form for batches, too; 1 = producer / chain workgroups on maps <= 2^23 cells only (the rule until the <8,2> shape); 2 = on every map
   int xcd_chunk_exact = 0;       // env HSM_XCD_CHUNK_EXACT: the same for the exact-order texel-cache form (0 = contiguous eighths, its default)
@@ -224,8 +277,7 @@ struct hsm_ctx {
                                  // results; an old one only groups the scans by where they were)
   struct PermBuf {
     hipStream_t s;
-    int* d;
-    size_t cap;
+    Buf<int> d;  // (not enrolled: hsm_destroy walks perm_bufs)
     int batch;  // the batch size the permutation in `d` was computed for (0: none)
     int used;   // launches it has served
   };
@@ -235,16 +287,15 @@ struct hsm_ctx {
   // (launches on one stream are ordered; a ninth stream, and any launch into a graph capture, take the literal dense form)
   struct SpecScratch {
     hipStream_t s;
-    float* d;
-    size_t cap;  // float4s
+    Buf<float4> d;  // (not enrolled: hsm_destroy walks spec_scratch)
   };
   std::vector<SpecScratch> spec_scratch;
   SpecStats* d_spec_stats = nullptr; // hsm_debug_spec_stats
   bool exact_dense = true;       // env HSM_EXACT_DENSE=0: dense scans in exact order keep the 16-wavefront team form (gn_match_kernel<16,...,EXACT>)
-  int exact_dense_min = 4096;
+  int exact_dense_min = 4096;    // env HSM_EXACT_DENSE_MIN: beams from which the producers-ahead-of-the-chain form takes over
   int compute_units = 256;   // of this device (hsm_create)
   int exact_split_tail = 1;  // env HSM_EXACT_SPLIT_TAIL=0: one launch however the batch divides into generations
-  int exact_chain_wave = 1;  // env HSM_EXACT_CHAIN_WAVE=0: no chain-only wavefront, teams of wavefronts for batches below 4096 scans (rounds 3-4)    // env HSM_EXACT_DENSE_MIN: beams from which the producers-ahead-of-the-chain form takes over
+  int exact_chain_wave = 1;  // env HSM_EXACT_CHAIN_WAVE=0: no chain-only wavefront, teams of wavefronts for batches below 4096 scans (rounds 3-4)
   const char* last_kernel = "";  // name of the matcher kernel the last launch used (hsm_last_launch_kernel)
   unsigned coop_fallbacks = 0;  // dense single-scan matches re-run on one workgroup after an exchange timeout (match_single)
   // ... and the back-off that follows: after a timeout the multi-workgroup form is skipped for the next coop_skip matches (1, 2, 4, ...

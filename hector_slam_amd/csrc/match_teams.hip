@@ -152,16 +152,11 @@ int ensure_batch_perm(hsm_ctx* h, MatchParams& P, hipStream_t stream) {
     if (b.s == stream) pb = &b;
   if (!pb) {
     if (h->perm_bufs.size() >= 8) return HSM_OK;  // (a ninth stream keeps the caller's order)
-    h->perm_bufs.push_back({stream, nullptr, 0, 0, 0});
+    h->perm_bufs.push_back({stream, {}, 0, 0});
     pb = &h->perm_bufs.back();
   }
-  if (pb->cap < (size_t)P.batch) {
-    if (pb->d) HIP_TRY(hipFree(pb->d));  // (hipFree waits for the device: no launch still reads it)
-    pb->d = nullptr, pb->cap = 0, pb->batch = 0;
-    const size_t cap = ((size_t)P.batch + 4095) / 4096 * 4096;
-    HIP_TRY(hipMalloc((void**)&pb->d, cap * sizeof(int)));
-    pb->cap = cap;
-  }
+  if (!pb->d.holds((size_t)P.batch)) pb->batch = 0;  // (the permutation goes with the block; the free waits for launches that read it)
+  if (int rc = pb->d.reserve(((size_t)P.batch + 4095) / 4096 * 4096)) return rc;  // multiples of 4096 ints
   if (pb->batch == P.batch && pb->used < h->batch_order_refresh) {  // the permutation of an earlier launch of this stream
     ++pb->used;
     P.perm = pb->d;
