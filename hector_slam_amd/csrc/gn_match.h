@@ -46,11 +46,8 @@
 // sums + tree instead of one sequential chain).  sinf/cosf/expf are glibc's algorithms
 // operation for operation (libm_exact.h): identical bits.
 #pragma once
-// Measured variants that are not shipped (the two-wave texel-cache form, per-wave time stamps) only compile with
-// -DHSM_EXPERIMENTS; the default library holds the shipped forms alone.
 #include <type_traits>
 #include <hip/hip_runtime.h>
-#include <hip/hip_cooperative_groups.h>
 
 #include "libm_exact.h"
 #include "pose_exchange.h"
@@ -60,17 +57,6 @@ namespace hsm {
 constexpr int kMaxLevels = 8;
 constexpr int kLayoutQuad = 1;
 constexpr int kLayoutPlane = 2;
-// HSM_PIPELINE=1 issues the gather of beam k+1 before beam k is consumed; HSM_UNROLL=n gathers n beams
-// back to back before consuming them.  Measured on MI355X (profiles/r01/README.md): one beam at a
-// time is fastest (372 M it/s; pipelined 358; chunks of 2 / 4 / 6 / 9: 359 / 342 / 340 / 309) --
-// the four waves per SIMD already interleave, extra texels in flight only cost registers.
-#ifndef HSM_PIPELINE
-#define HSM_PIPELINE 0
-#endif
-#ifndef HSM_UNROLL
-#define HSM_UNROLL 1
-#endif
-constexpr int kUnroll = HSM_UNROLL;  // texel gathers a lane keeps in flight (register-resident form)
 
 // Eigen::Affine2f as the reference builds it: 2x2 linear (column major) + translation.
 struct Affine2 {
@@ -79,11 +65,11 @@ struct Affine2 {
 
 // read-only view of one pyramid level for the matcher
 struct LevelView {
-  const float4* quad;  // texels {P00,P10,P01,P11}, tiled (quad_index), + one all-zero texel at quad_texels
+  const float4* quad;  // texels {P00,P10,P01,P11}, row major (quad_index), + one all-zero texel at quad_texels
   const float* prob;   // [sy*sx] plain probability plane (row major) + sx+2 zero cells
   int sx, sy;
   int tiles_x;         // quad tiles per row = ceil(sx / 4)
-  int quad_texels;     // tiles_x * ceil(sy / 2) * 8
+  int quad_texels;     // sx * sy
   float limx, limy;    // dims - 2  (MapDimensionProperties.h:70-74)
   Affine2 mapTworld;   // GridMapBase.h:272
   Affine2 worldTmap;   // GridMapBase.h:279
@@ -184,12 +170,8 @@ __device__ __forceinline__ void exchange_wait_unpack(const ExchangeFused& X, int
 //     batch), so contiguous eighths leave whole XCDs with the slow stretches; chunks keep an XCD's working set
 //     compact (16 workgroups = 64 consecutive scans) and give every XCD a sample of the whole batch (2048^2 headline:
 //     49.2 vs 50.5 us).
-// Bijective for any grid.  -DHSM_XCD_SWIZZLE=0 keeps the hardware order.
-#ifndef HSM_XCD_SWIZZLE
-#define HSM_XCD_SWIZZLE 1
-#endif
+// Bijective for any grid.
 __device__ __forceinline__ int xcd_block(int b, int nblocks, int chunk) {
-#if HSM_XCD_SWIZZLE
   int base = 0;
   if (chunk > 0) {
     const int main_blocks = nblocks / (8 * chunk) * (8 * chunk);
@@ -202,11 +184,6 @@ __device__ __forceinline__ int xcd_block(int b, int nblocks, int chunk) {
   const int rb = b - base, rn = nblocks - base;
   const int xcd = rb & 7, idx = rb >> 3, q = rn >> 3, r = rn & 7;
   return base + xcd * q + (xcd < r ? xcd : r) + idx;
-#else
-  (void)nblocks;
-  (void)chunk;
-  return b;
-#endif
 }
 
 // The lane index, recomputed where it is used (two v_mbcnt) instead of being carried in a VGPR from the top of a
@@ -217,28 +194,16 @@ __device__ __forceinline__ int lane_id_now() {
   return l;
 }
 
-// Texel address of cell (x, y) in the quad plane.
-// HSM_QUAD_TILE == 0 (default): row major, index = y*sizeX + x like the reference's grid -- one
-//   v_mad_u32_u24 per beam.
-// HSM_QUAD_TILE == 1: 4x2-cell tiles (= eight 16-byte texels = one 128-byte line), Morton order
-//   inside (x0, y0, x1), which cuts the cache-line requests of a gather along a wall by about a
-//   third but costs five more integer VALU ops per beam.  Measured on MI355X the matcher is
-//   VALU-issue bound and both variants run at the same speed (profiles/r01/kernel_ab_tile.jsonl),
-//   so the simpler one is the default; the switch is kept for maps that outgrow the L2.
-#ifndef HSM_QUAD_TILE
-#define HSM_QUAD_TILE 0
-#endif
+// Texel address of cell (x, y) in the quad plane: row major, index = y*sizeX + x like the reference's grid -- one
+// v_mad_u32_u24 per beam.  (Measured against 4x2-cell Morton tiles, which cut the cache-line requests of a gather along a
+// wall by about a third but cost five more integer VALU ops per beam: the matcher is VALU-issue bound and both run at
+// the same speed, profiles/r01/kernel_ab_tile.jsonl.)
 __host__ __device__ __forceinline__ unsigned quad_index(unsigned x, unsigned y, int tiles_x, int sx) {
-#if HSM_QUAD_TILE
-  (void)sx;
-  return ((((y >> 1) * (unsigned)tiles_x) + (x >> 2)) << 3) | ((x & 2) << 1) | ((y & 1) << 1) | (x & 1);
-#else
   (void)tiles_x;
 #if defined(__HIP_DEVICE_COMPILE__)
   return __umul24(y, (unsigned)sx) + x;
 #else
   return y * (unsigned)sx + x;
-#endif
 #endif
 }
 
@@ -255,15 +220,7 @@ __device__ __forceinline__ void affine_apply(const Affine2& a, float x, float y,
 // them into); the latency forms let the optimiser hoist them out of the 14-step chain
 template <bool PIN = false>
 __device__ __forceinline__ void sincos_f32(float th, float& s, float& c) {
-#if defined(HSM_EXPERIMENTS) && defined(HSM_EXP_FAST_SINCOS)
-  // what-if build (NOT parity-safe): the hardware's v_sin_f32 / v_cos_f32 -- two instructions -- instead of glibc's binary64
-  // evaluation.  An upper bound on what any restructuring of the bit-exact sincosf can buy per Gauss-Newton step
-  // (round-3 verdict item 7; profiles/r04/README.md)
-  s = __sinf(th);
-  c = __cosf(th);
-#else
   libm::sincosf_glibc<PIN>(th, s, c);
-#endif
 }
 
 // util::normalize_angle (HSL/util/UtilFunctions.h:37-49): double fmod, float result
@@ -325,30 +282,21 @@ struct BeamSample {
 // dM/dx = dM/dy = -0 and M = 0, so every product added to H and dTr is +-0 and the running fp32
 // sums are unchanged bit for bit -- the same outcome as the reference's explicit zeros, without a
 // branch or three selects per beam.  The matcher is VALU-issue bound (profiles/r01), so the test
-// itself is written for instruction count: v_med3_f32 clamps the coordinate into [0, dims-2]; the
-// beam is outside exactly when the clamp changed it (x < 0 or x > dims-2, as in the reference),
-// and the clamped value doubles as the finite stand-in coordinate of an outside beam.  A NaN
-// coordinate never equals its clamp, so it counts as outside (the reference would index the map
-// with (int)NaN there and crash).  v_fract_f32(x) == x - (float)(int)x exactly for 0 <= x < 2^23.
-// Bounds test of one map coordinate pair.  HSM_BOUNDS_BITS=1 (default): 0 <= x <= lim on the BIT PATTERNS -- for
+// itself is written for instruction count.  A beam is outside when x < 0 or x > dims-2, as in the
+// reference; a NaN coordinate counts as outside too (the reference would index the map with (int)NaN
+// there and crash).  v_fract_f32(x) == x - (float)(int)x exactly for 0 <= x < 2^23.
+// Bounds test of one map coordinate pair: 0 <= x <= lim on the BIT PATTERNS -- for
 // x >= +0 the unsigned pattern of an fp32 value is monotonic in the value, every negative value (sign bit set) and
 // every NaN compares above any non-negative limit, so `bits(x) <= bits(lim)` is the whole test in ONE v_cmp_le_u32
-// per axis (the clamp form costs v_med3 + v_cmp_neq per axis).  The one value the pattern test would judge
+// per axis (a clamp with v_med3 costs that + v_cmp_neq per axis).  The one value the pattern test would judge
 // differently is -0.0 (inside for the reference: -0.0 < 0 is false); c = e + r is -0.0 only if e AND r are -0.0,
 // and the callers pass e + 0.0f (wave-uniform, once per GN step; changes no other sum), so it cannot occur.
 // Outside beams keep their raw coordinate: v_cvt_i32_f32 saturates and v_fract_f32 of a finite value is finite,
 // which is all the all-zero texel needs to yield +-0 products.
-#ifndef HSM_BOUNDS_BITS
-#define HSM_BOUNDS_BITS 1
-#endif
 // the estimate's map coordinates as the beam loop adds them to the rotated endpoints: -0.0 -> +0.0 (see above; for
 // every other value x + 0.0f == x, and (+0.0) + r == (-0.0) + r unless r is -0.0 too)
 __device__ __forceinline__ f2 step_origin(float ex, float ey) {
-#if HSM_BOUNDS_BITS
   return f2{ex + 0.0f, ey + 0.0f};
-#else
-  return f2{ex, ey};
-#endif
 }
 
 struct CellCoord {
@@ -359,23 +307,12 @@ struct CellCoord {
 
 __device__ __forceinline__ CellCoord cell_coord(const LevelRegs& L, f2 c) {
   CellCoord q;
-#if HSM_BOUNDS_BITS
   q.oob = (int)(__float_as_uint(c.x) > __float_as_uint(L.limx)) | (int)(__float_as_uint(c.y) > __float_as_uint(L.limy));
   const float sx_ = c.x, sy_ = c.y;
-#else
-  const float sx_ = __builtin_amdgcn_fmed3f(c.x, 0.0f, L.limx);
-  const float sy_ = __builtin_amdgcn_fmed3f(c.y, 0.0f, L.limy);
-  q.oob = (sx_ != c.x) | (sy_ != c.y);
-#endif
-#if HSM_BOUNDS_BITS
   // truncation, OccGridMapUtil.h:295.  The instruction itself (saturating, defined for every input) rather than a
   // C++ cast, whose result is undefined for the raw coordinate of an outside beam.
   asm("v_cvt_i32_f32 %0, %1" : "=v"(q.ix) : "v"(sx_));
   asm("v_cvt_i32_f32 %0, %1" : "=v"(q.iy) : "v"(sy_));
-#else
-  q.ix = (unsigned)(int)sx_;  // truncation, OccGridMapUtil.h:295
-  q.iy = (unsigned)(int)sy_;
-#endif
   q.fx = __builtin_amdgcn_fractf(sx_);  // :298
   q.fy = __builtin_amdgcn_fractf(sy_);
   return q;
@@ -614,10 +551,6 @@ __device__ __forceinline__ float wave_allreduce(float v) {
 // the single register that is left.  25 instructions + 9 v_readlane_b32 (the totals end up in SGPRs, identical in
 // every lane) instead of 90.  Level order 32, 16, row_mirror, row_half_mirror, lane^2, lane^1 -- the same pairing
 // tree for all nine values.
-#ifndef HSM_REDUCE_FOLD
-#define HSM_REDUCE_FOLD 1
-#endif
-
 __device__ __forceinline__ float fold_swap32(float a, float b) {  // lanes 0..31: a[i] + a[i+32];  32..63: b[i-32] + b[i]
   const auto r = __builtin_amdgcn_permlane32_swap(__float_as_int(a), __float_as_int(b), false, false);
   return __int_as_float(r[0]) + __int_as_float(r[1]);
@@ -627,7 +560,7 @@ __device__ __forceinline__ float fold_swap16(float a, float b) {  // rows 0, 2: 
   return __int_as_float(r[0]) + __int_as_float(r[1]);
 }
 
-__device__ __forceinline__ void wave_allreduce9_folded(Acc9& a) {
+__device__ __forceinline__ void wave_allreduce9(Acc9& a) {
   // level 32 and level 16: the totals over the four rows, per column of 16
   const float a0 = fold_swap32(a.d01.x, a.d01.y);  // rows 0,1: dTr0   rows 2,3: dTr1
   const float a1 = fold_swap32(a.d2, a.hd.x);      //           dTr2             H00
@@ -666,22 +599,6 @@ __device__ __forceinline__ void wave_allreduce9_folded(Acc9& a) {
   a.h22 = lane_value(40);
   a.hr.x = lane_value(56);
   a.hr.y = lane_value(4);
-}
-
-__device__ __forceinline__ void wave_allreduce9(Acc9& a) {
-#if HSM_REDUCE_FOLD
-  wave_allreduce9_folded(a);
-  return;
-#endif
-  a.d01.x = wave_allreduce(a.d01.x);
-  a.d01.y = wave_allreduce(a.d01.y);
-  a.d2 = wave_allreduce(a.d2);
-  a.hd.x = wave_allreduce(a.hd.x);
-  a.hd.y = wave_allreduce(a.hd.y);
-  a.h22 = wave_allreduce(a.h22);
-  a.h01 = wave_allreduce(a.h01);
-  a.hr.x = wave_allreduce(a.hr.x);
-  a.hr.y = wave_allreduce(a.hr.y);
 }
 
 // team-wide totals: wave all-reduce, then (WPS > 1) LDS staging of the per-wave partials; every thread of the team
@@ -786,12 +703,8 @@ __global__ void __launch_bounds__(64 * WPS * SPB, ((EXACT && SPB == 1 && (WPS ==
   __shared__ __attribute__((aligned(16))) float red[2][9][WPS < 4 ? 4 : WPS];
   // exact order: [team][term][beam]; single-scan teams of up to four wavefronts stage a whole GROUP of rounds (kXGroup x T beams,
   // 46 KB at four wavefronts) and sum it in one go, the others round by round
-#ifndef HSM_XTEAM8  // experiment: an eight-wavefront team stages its THREE rounds (1536 beams, 55 KB) together as well
-#define HSM_XTEAM8 0
-#endif
-  constexpr bool kTeam8 = HSM_XTEAM8 != 0 && EXACT && SPB == 1 && T == 512;
-  constexpr int kXGroup = kTeam8 ? 3 : kExactGroupRounds;
-  constexpr int kXStaged = (EXACT && SPB == 1 && (T <= 256 || kTeam8)) ? kXGroup : 1;  // rounds staged together
+  constexpr int kXGroup = kExactGroupRounds;
+  constexpr int kXStaged = (EXACT && SPB == 1 && T <= 256) ? kXGroup : 1;  // rounds staged together
   constexpr int kXRowLen = kXStaged * T;
   __shared__ float stage[EXACT ? SPB * 9 * (kXRowLen + kExactPad) : 1];
   const int lane = threadIdx.x & 63;
@@ -888,34 +801,16 @@ __global__ void __launch_bounds__(64 * WPS * SPB, ((EXACT && SPB == 1 && (WPS ==
       acc.zero();
       const f2 e2 = step_origin(ex, ey), cs = f2{cosRot, sinRot}, sc = f2{sinRot, cosRot};
       if (in_regs) {
-#if HSM_PIPELINE
-        // Software pipeline of depth one (experiment switch): the texel gather of beam k+1 is issued
-        // BEFORE beam k is consumed.  The accumulation order stays k = 0, 1, 2 ... so the bits equal
-        // the memory loop's.
-        BeamRot rot_cur, rot_nxt;
-        BeamSample cur = beam_fetch<LAYOUT>(R, e2, cs, sc, pt[0], rot_cur), nxt;
-#pragma unroll
-        for (int k = 0; k < NREG; ++k) {
-          if (k + 1 < NREG) nxt = beam_fetch<LAYOUT>(R, e2, cs, sc, pt[k + 1], rot_nxt);
-          beam_finish(cur, rot_cur, acc);
-          // Pin: the accumulators are final here ("+v") and no later gather may be hoisted above
-          // this point ("memory") -- exactly one texel in flight while one is being consumed.
-          asm volatile(""
-                       : "+v"(acc.d01), "+v"(acc.d2), "+v"(acc.hd), "+v"(acc.h22), "+v"(acc.h01), "+v"(acc.hr)
-                       :
-                       : "memory");
-          cur = nxt;
-          rot_cur = rot_nxt;
-        }
-#else
-        // chunks of kUnroll beams: issue all gathers of a chunk, then consume them in beam order
+        // chunks of kChunk beams: issue all gathers of a chunk, then consume them in beam order
         // (the accumulation order stays k = 0, 1, 2 ... so the bits equal the memory loop's)
-        // Throughput launches (one wave per scan, 4 waves per SIMD): one beam at a time is fastest.
+        // Throughput launches (one wave per scan, 4 waves per SIMD): one beam at a time is fastest -- the four waves
+        // per SIMD already interleave, extra texels in flight only cost registers (372 M it/s; a one-deep software
+        // pipeline 358; chunks of 2 / 4 / 6 / 9: 359 / 342 / 340 / 309, profiles/r01/README.md).
         // Latency launches (WPS > 1 is only chosen when the batch cannot fill the chip, typically one wave
         // per SIMD): nobody else hides the L2 latency, so the lane's gathers are issued in chunks before the
         // first is consumed -- all of them up to 5 beams per lane (single 1081-beam scan: kernel 31.5 -> 25 us),
         // else 4 at a time (16k-beam scan on 16 waves: 170 / 155 / 173 us for chunks of 1 / 4 / 9).
-        constexpr int kChunk = WPS > 1 ? (NREG <= 5 ? NREG : 4) : kUnroll;
+        constexpr int kChunk = WPS > 1 ? (NREG <= 5 ? NREG : 4) : 1;
 #pragma unroll
         for (int k0 = 0; k0 < NREG; k0 += kChunk) {
           BeamSample smp[kChunk];
@@ -931,13 +826,12 @@ __global__ void __launch_bounds__(64 * WPS * SPB, ((EXACT && SPB == 1 && (WPS ==
           }
           // Pin the chunk: the accumulators must be final here ("+v") and no later gather may be
           // hoisted above this point ("memory").  Without it the compiler issues all BPL gathers
-          // first and spills their results; with it at most kUnroll texels are in flight per lane.
+          // first and spills their results; with it at most kChunk texels are in flight per lane.
           asm volatile(""
                        : "+v"(acc.d01), "+v"(acc.d2), "+v"(acc.hd), "+v"(acc.h22), "+v"(acc.h01), "+v"(acc.hr)
                        :
                        : "memory");
         }
-#endif
       } else if (EXACT) {
         float run = 0.0f;
         float* st = stage + team * 9 * (kXRowLen + kExactPad);
@@ -1213,23 +1107,9 @@ __global__ void __launch_bounds__(1024) gn_match_exact_dense_kernel(const MatchP
 // arithmetic on the same texel values in the same order as gn_match_kernel: identical bits.
 // One wave per scan, no trace.  The gathers run ONE beam ahead of their use (measured, profiles/r02/README.md: one
 // ahead 57.1 us on the headline workload, two ahead 58.3 at 128 VGPRs, chunks of 3 without a pipeline 58.4).
-// Compile-time switches of the measured variants (each A/B in profiles/r02/README.md):
-#ifndef HSM_ASM_GATHER   // counted waits for the masked texel gathers (see locate())
-#define HSM_ASM_GATHER 1
-#endif
-#ifndef HSM_LDS_AHEAD    // endpoint of beam k+2 read from LDS while beam k is consumed
-#define HSM_LDS_AHEAD 1
-#endif
-#ifndef HSM_ZERO_VGPR
-#define HSM_ZERO_VGPR 1
-#endif
-
-#ifndef HSM_GATHER_ALWAYS  // 1: every beam issues its (masked) gather with lane 0 enabled -- static load counts, no branches; measured neutral (49.5 / 95.7 / 133 us either way), off
-#define HSM_GATHER_ALWAYS 0
-#endif
-#ifndef HSM_PEEL_FIRST   // first GN step takes the endpoints from their load registers (see the kernel)
-#define HSM_PEEL_FIRST 1
-#endif
+// What the kernel does on top of that, each measured against the form without it in profiles/r02/README.md: counted waits
+// for the masked texel gathers (see locate()), the endpoint of beam k+2 read from LDS while beam k is consumed, the zero
+// texel's offset pinned in a VGPR, the first GN step taking the endpoints from their load registers.
 #ifndef HSM_EP_AHEAD     // endpoint loads in flight ahead of the beam being located in the peeled step
 #define HSM_EP_AHEAD 4
 #endif
@@ -1284,9 +1164,8 @@ struct __attribute__((packed, aligned(4))) CellPair {
   float a, b;
 };
 
-// WPS = 2 (experimental, HSM_CACHED_WPS2): TWO waves per scan, beam i in thread i mod 128 of the pair like
-// gn_match_kernel<2,1> (identical bits), nine beams per lane = 92 VGPRs = five waves per SIMD: a 4096-scan launch is
-// 8192 waves on 5120 slots, so late workgroups start as early ones finish.
+// WPS: one wavefront per scan is the only form (the parameter stays for the kernels' names; two wavefronts per scan were
+// measured in profiles/r02/README.md).
 //
 // RELAXED (HSM_PARITY_RELAXED, opt-in): the same expressions with their multiply-add pairs CONTRACTED -- the rotation, the
 // bilinear blend written as two lerps on the differences the gradient needs anyway, the blends of the differences, rotDeriv
@@ -1295,21 +1174,15 @@ struct __attribute__((packed, aligned(4))) CellPair {
 // per pair); the mode's bar is north_star's tolerance (1e-4 m / 1e-4 rad on the pose), measured at full size against the
 // reference (tests/test_gpu_full_size.py, bench.py), not bit-exactness of the terms.
 template <int SPB, int BPL, int LAYOUT = kLayoutQuad, int WPS = 1, bool RELAXED = false>
-__global__ void __launch_bounds__(64 * SPB * WPS, WPS > 1 ? 5 : 4) gn_match_cached_kernel(const MatchParams P) {
-  static_assert(!RELAXED || (LAYOUT == kLayoutQuad && WPS == 1), "the tolerance mode exists for the throughput form only");
-  static_assert(WPS == 1 || SPB == 1, "a pair of waves owns its workgroup (one barrier per GN step)");
-  constexpr int T = 64 * WPS;  // lanes per scan
-  __shared__ f2 lds_pts[SPB * WPS][BPL][64];
-  __shared__ __attribute__((aligned(16))) float red[2][9][WPS < 4 ? 4 : WPS];
+__global__ void __launch_bounds__(64 * SPB, 4) gn_match_cached_kernel(const MatchParams P) {
+  static_assert(WPS == 1, "one wavefront per scan");
+  static_assert(!RELAXED || LAYOUT == kLayoutQuad, "the tolerance mode exists for the throughput form only");
+  constexpr int T = 64;  // lanes per scan
+  __shared__ f2 lds_pts[SPB][BPL][64];
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
-  const int wit = __builtin_amdgcn_readfirstlane(wave % WPS);  // wave in team
-  int red_buf = 0;
   // wave-uniform: kept in an SGPR (and with it the pose / covariance addresses, which live across the whole kernel)
-  const int slot = __builtin_amdgcn_readfirstlane(xcd_block((int)blockIdx.x, (int)gridDim.x, P.xcd_chunk) * SPB + wave / WPS);
-#if defined(HSM_EXPERIMENTS) && defined(HSM_EXP_TIMESTAMPS)
-  const unsigned long long ts_entry = wall_clock64();
-#endif
+  const int slot = __builtin_amdgcn_readfirstlane(xcd_block((int)blockIdx.x, (int)gridDim.x, P.xcd_chunk) * SPB + wave);
   if (slot >= P.batch) return;
   // (MatchParams::perm: the batch in Morton order of its start poses -- neighbours in the launch are neighbours in the map)
   const int scan = P.perm != nullptr ? __builtin_amdgcn_readfirstlane(P.perm[slot]) : slot;
@@ -1321,7 +1194,7 @@ __global__ void __launch_bounds__(64 * SPB * WPS, WPS > 1 ? 5 : 4) gn_match_cach
   }
   float pw0 = P.begin_world[3 * scan + 0], pw1 = P.begin_world[3 * scan + 1], pw2 = P.begin_world[3 * scan + 2];
   if (n == 0) {
-    if (lane == 0 && wit == 0) {
+    if (lane == 0) {
       P.out_pose[3 * scan + 0] = pw0;
       P.out_pose[3 * scan + 1] = pw1;
       P.out_pose[3 * scan + 2] = pw2;
@@ -1332,7 +1205,7 @@ __global__ void __launch_bounds__(64 * SPB * WPS, WPS > 1 ? 5 : 4) gn_match_cach
   f2(*mine)[64] = lds_pts[wave];
   // Endpoint staging.  Every wave of a launch starts at the same time and needs its 8.6 KB of endpoints first: 35 MB for
   // 4096 scans, 6.5 us during which no wave has anything to compute if all endpoints are staged before the first GN
-  // step (measured per wave with HSM_EXP_TIMESTAMPS, profiles/r02/README.md).  So the FIRST GN step of the first level
+  // step (measured with per-wave time stamps, profiles/r02/README.md).  So the FIRST GN step of the first level
   // is peeled (kPeel): its beam k takes its endpoint straight from the register of a load issued kEpAhead beams
   // earlier and writes it to LDS for the later steps, so the arithmetic and the texel gathers of step one run while
   // the endpoints are still streaming in.  All loads of that step -- endpoints and (unmasked: every lane gathers in a
@@ -1340,7 +1213,7 @@ __global__ void __launch_bounds__(64 * SPB * WPS, WPS > 1 ? 5 : 4) gn_match_cach
   // the position of every load in the wave's issue order, hence how many younger loads may still be in flight when a
   // given one is needed.  Out-of-range lanes read the scan's last endpoint (exec stays full, so every load is issued
   // and the counts are static) and are replaced by the padding value.
-  constexpr bool kPeel = LAYOUT == kLayoutQuad && HSM_ASM_GATHER && HSM_PEEL_FIRST;
+  constexpr bool kPeel = LAYOUT == kLayoutQuad;
   constexpr int kEpAhead = HSM_EP_AHEAD < BPL ? HSM_EP_AHEAD : BPL - 1;
   static_assert(BPL <= 31, "PeelSchedule holds 32 positions per load kind");
   constexpr PeelSchedule kSched = peel_schedule(BPL, kEpAhead);
@@ -1349,15 +1222,11 @@ __global__ void __launch_bounds__(64 * SPB * WPS, WPS > 1 ? 5 : 4) gn_match_cach
   if (!peel) {
 #pragma unroll
     for (int k = 0; k < BPL; ++k) {
-      const int i = lane + 64 * wit + k * T;
+      const int i = lane + k * T;
       const float2 q = i < n ? pts[i] : make_float2(1.0e30f, 1.0e30f);  // padding: see gn_match_kernel
       mine[k][lane] = f2{q.x, q.y};
     }
   }
-#if defined(HSM_EXPERIMENTS) && defined(HSM_EXP_TIMESTAMPS)  // experiment (tools/exp_wave_timeline.py): per-wave start / end stamps of the 100 MHz clock
-  const unsigned long long ts_begin = wall_clock64();
-  const unsigned long long sc_begin = __builtin_readcyclecounter();  // shader clock (s_memtime)
-#endif
   f4v tq[BPL];
   unsigned toff[BPL];
   Acc9 acc;
@@ -1381,9 +1250,7 @@ __global__ void __launch_bounds__(64 * SPB * WPS, WPS > 1 ? 5 : 4) gn_match_cach
     }
     // byte offset of the all-zero texel, pinned in a VGPR (as an SGPR it costs a v_mov per beam in front of the select)
     unsigned zero_off = (unsigned)R.zero_index << (LAYOUT == kLayoutQuad ? 4 : 2);
-#if HSM_ZERO_VGPR
     asm volatile("" : "+v"(zero_off));
-#endif
     // one GN step; FIRST = the peeled step (compile-time)
     const bool wg_sync = __builtin_amdgcn_readfirstlane(P.wg_sync) != 0;
     auto gn_step = [&](auto FIRST, int it) {
@@ -1392,7 +1259,7 @@ __global__ void __launch_bounds__(64 * SPB * WPS, WPS > 1 ? 5 : 4) gn_match_cach
       // stays at the load (hoisted out of the level loop, 17 offsets would sit in VGPRs for the whole kernel).
       f2 pq[kFirst ? BPL : 1];
       auto endpoint_issue = [&](int k) {
-        int i = min((int)lane_id_now() + 64 * wit + T * k, n - 1);
+        int i = min((int)lane_id_now() + T * k, n - 1);
         asm volatile("" : "+v"(i));
         const unsigned byte_off = (unsigned)i << 3;
         asm volatile("global_load_dwordx2 %0, %1, %2" : "=v"(pq[kFirst ? k : 0]) : "v"(byte_off), "s"(pts) : "memory");
@@ -1400,7 +1267,7 @@ __global__ void __launch_bounds__(64 * SPB * WPS, WPS > 1 ? 5 : 4) gn_match_cach
       if (kFirst) {
         // clock probe, begin stamps (see the end of the kernel): here, at the top of the peeled step, no texel is live
         // yet -- the same block at the kernel's entry made the register allocator spill
-        if (P.clock_probe != nullptr && scan == 0 && wit == 0 && lane_id_now() == 0) {
+        if (P.clock_probe != nullptr && scan == 0 && lane_id_now() == 0) {
           P.clock_probe[0] = __builtin_readcyclecounter();
           P.clock_probe[1] = wall_clock64();
         }
@@ -1439,7 +1306,7 @@ __global__ void __launch_bounds__(64 * SPB * WPS, WPS > 1 ? 5 : 4) gn_match_cach
           toff[k] = off;
           return ~0ull;
         }
-        if (LAYOUT == kLayoutQuad && HSM_ASM_GATHER) {
+        if (LAYOUT == kLayoutQuad) {
           // The masked gather as ONE instruction sequence under the wave's own control.  The compiler's form of
           // `if (off != toff[k]) load` waits with vmcnt(0) before the PREVIOUS beam is consumed -- it cannot count
           // loads that sit behind a branch -- which puts the gather just issued on the critical path and defeats the
@@ -1447,22 +1314,9 @@ __global__ void __launch_bounds__(64 * SPB * WPS, WPS > 1 ? 5 : 4) gn_match_cach
           // moved, wave-uniform) and texel_ready() waits for exactly the load it needs.  No C++ control flow: the
           // compiler sees straight-line code and keeps tq[k] where it is (it does not know about the asynchronous
           // write; texel_ready(k) is ordered before every read of tq[k] through its "+v" operand).
+          // (Letting lane 0 re-read its texel at every beam, so that the load and wait counts are static and both branches
+          // go, measured neutral here: 49.5 / 95.7 / 133 us either way, profiles/r02/README.md.)
           unsigned long long moved, saved;
-#if HSM_GATHER_ALWAYS
-          // lane 0 always re-reads its texel (same value: the map does not change under the kernel), so every beam
-          // issues exactly ONE load and the waits are static -- no branch around the load, none around the wait
-          asm volatile(
-              "v_cmp_ne_u32 vcc, %[o], %[to]\n\t"
-              "s_or_b32 vcc_lo, vcc_lo, 1\n\t"
-              "s_and_saveexec_b64 %[sv], vcc\n\t"
-              "global_load_dwordx4 %[t], %[o], %[b]\n\t"
-              "v_mov_b32 %[to], %[o]\n\t"
-              "s_mov_b64 exec, %[sv]"
-              : [t] "+v"(tq[k]), [to] "+v"(toff[k]), [sv] "=&s"(saved)
-              : [o] "v"(off), [b] "s"(R.quad)
-              : "vcc", "scc", "memory");
-          moved = ~0ull;
-#else
           asm volatile(
               "v_cmp_ne_u32 vcc, %[o], %[to]\n\t"
               "s_mov_b64 %[mv], vcc\n\t"
@@ -1475,7 +1329,6 @@ __global__ void __launch_bounds__(64 * SPB * WPS, WPS > 1 ? 5 : 4) gn_match_cach
               : [t] "+v"(tq[k]), [to] "+v"(toff[k]), [sv] "=&s"(saved), [mv] "=&s"(moved)
               : [o] "v"(off), [b] "s"(R.quad)
               : "vcc", "scc", "memory");
-#endif
           return moved;
         }
         if (off != toff[k]) {
@@ -1496,11 +1349,9 @@ __global__ void __launch_bounds__(64 * SPB * WPS, WPS > 1 ? 5 : 4) gn_match_cach
       // beam k's texel has landed.  `next_moved` = the mask returned by the locate() of the only gather that may have
       // been issued after beam k's (wave-uniform): loads return in order, so with it in flight vmcnt(1) is enough.
       auto texel_ready = [&](int k, unsigned long long next_moved, bool has_next) {
-        if (!(LAYOUT == kLayoutQuad && HSM_ASM_GATHER)) return;
+        if (LAYOUT != kLayoutQuad) return;
         if (kFirst) {  // static schedule: everything issued after beam k's gather may still be in flight
           wait_vmcnt((has_next ? kSched.posG[k + 1] + 1 : kSched.total) - kSched.posG[k] - 1, tq[k]);
-        } else if (has_next && HSM_GATHER_ALWAYS) {
-          asm volatile("s_waitcnt vmcnt(1)" : "+v"(tq[k]) : : "memory");
         } else if (has_next) {
           asm volatile(
               "s_cmp_eq_u64 %[m], 0\n\t"
@@ -1520,7 +1371,7 @@ __global__ void __launch_bounds__(64 * SPB * WPS, WPS > 1 ? 5 : 4) gn_match_cach
       // peeled step: endpoint k from its load register (padding lanes replaced), scaled for this level, into LDS
       auto endpoint_take = [&](int k) -> f2 {
         wait_vmcnt(kSched.posG[k] - kSched.posE[k] - 1, pq[k]);  // beam k's gather is the next load in issue order
-        const bool pad = (int)lane_id_now() + 64 * wit + T * k >= n;
+        const bool pad = (int)lane_id_now() + T * k >= n;
         const f2 p = f2{(pad ? 1.0e30f : pq[k].x) * ps, (pad ? 1.0e30f : pq[k].y) * ps};
         mine[k][lane] = p;
         return p;
@@ -1559,7 +1410,7 @@ __global__ void __launch_bounds__(64 * SPB * WPS, WPS > 1 ? 5 : 4) gn_match_cach
       // Software pipeline: the texel gather of beam k+1 is ISSUED before beam k is consumed, so a gather has the
       // arithmetic of a whole beam (and the other waves' share of the SIMD) to land in.  The gathers write the beams'
       // own cache registers, so the only extra state in flight is the next beam's (rot, fx, fy); the endpoint of beam
-      // k+2 is read from LDS before beam k+1 is located (HSM_LDS_AHEAD), so the LDS latency is off the chain too.
+      // k+2 is read from LDS before beam k+1 is located, so the LDS latency is off the chain too.
       // Same arithmetic in the same beam order: identical bits.
       {
         BeamRot rc, rn;
@@ -1579,8 +1430,8 @@ __global__ void __launch_bounds__(64 * SPB * WPS, WPS > 1 ? 5 : 4) gn_match_cach
             if (k + 1 < BPL) next_moved = locate(k + 1, endpoint_take(k + 1), rn, fxn, fyn);
           } else {
             const f2 p_cur = p_next;
-            if (HSM_LDS_AHEAD && k + 2 < BPL) p_next = mine[k + 2][lane];
-            if (k + 1 < BPL) next_moved = locate(k + 1, HSM_LDS_AHEAD ? p_cur : mine[k + 1][lane], rn, fxn, fyn);
+            if (k + 2 < BPL) p_next = mine[k + 2][lane];
+            if (k + 1 < BPL) next_moved = locate(k + 1, p_cur, rn, fxn, fyn);
           }
           // large maps (MatchParams::wg_sync): the four waves of a workgroup -- consecutive scans, whose beam k ends in
           // the same or neighbouring cells -- locate beam k together, so the texel lines one of them pulls in are still
@@ -1600,18 +1451,13 @@ __global__ void __launch_bounds__(64 * SPB * WPS, WPS > 1 ? 5 : 4) gn_match_cach
       }
       // a scan longer than the 64 * BPL cached beams (BPL comes from a host-side length HINT): the rest streams
       // from memory like gn_match_kernel's loop, in the same per-lane order (wave-uniform trip count)
-      for (int i = T * BPL + (n > T * BPL ? lane_id_now() + 64 * wit : 0); i < n; i += T) {
+      for (int i = T * BPL + (n > T * BPL ? lane_id_now() : 0); i < n; i += T) {
         const float2 p = pts[i];
         BeamRot r;
         const BeamSample b = beam_fetch<LAYOUT>(R, e2, cs, sc, f2{p.x * ps, p.y * ps}, r);
         beam_finish(b, r, acc);
       }
-      if (WPS > 1) {
-        team_allreduce9<WPS>(acc, red, red_buf, wit, lane_id_now());
-        red_buf ^= 1;
-      } else {
-        wave_allreduce9(acc);
-      }
+      wave_allreduce9(acc);
       gn_solve_and_step(acc, ex, ey, eth);
     };
     int it = 0;
@@ -1624,195 +1470,24 @@ __global__ void __launch_bounds__(64 * SPB * WPS, WPS > 1 ? 5 : 4) gn_match_cach
     affine_apply(L.worldTmap, ex, ey, pw0, pw1);
     pw2 = eth;
   }
-  if (lane_id_now() == 0 && wit == 0) {
+  if (lane_id_now() == 0) {
     P.out_pose[3 * scan + 0] = pw0;
     P.out_pose[3 * scan + 1] = pw1;
     P.out_pose[3 * scan + 2] = pw2;
     if (P.out_cov) {
       float* c = P.out_cov + 9 * scan;
-#if defined(HSM_EXPERIMENTS) && defined(HSM_EXP_TIMESTAMPS)  // the stamps and the wave's placement overwrite the covariance
-      const unsigned long long ts_end = wall_clock64();
-      const unsigned long long sc_end = __builtin_readcyclecounter();
-      unsigned hwid, xcc;
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-      unsigned* u = reinterpret_cast<unsigned*>(c);
-      u[0] = (unsigned)ts_begin; u[1] = (unsigned)(ts_begin >> 32); u[2] = (unsigned)ts_end; u[3] = (unsigned)(ts_end >> 32);
-      u[4] = hwid; u[5] = xcc; u[6] = blockIdx.x; u[7] = (unsigned)(ts_begin - ts_entry); u[8] = (unsigned)(sc_end - sc_begin);
-#else
       c[0] = acc.hd.x; c[1] = acc.h01; c[2] = acc.hr.x;
       c[3] = acc.h01; c[4] = acc.hd.y; c[5] = acc.hr.y;
       c[6] = acc.hr.x; c[7] = acc.hr.y; c[8] = acc.h22;
-#endif
     }
   }
   // clock probe (bench.py: what clock does the kernel actually get?): the wave of scan 0 stamps the shader-clock counter
   // (s_memtime) and the 100 MHz wall clock at the top of its first GN step and here, as its last act; the ratio of the
   // two differences is the clock it ran at.  (Stamps of different launches cannot be compared: the wave lands on
   // different CUs, whose shader-clock counters are not aligned.)
-  if (P.clock_probe != nullptr && scan == 0 && wit == 0 && lane_id_now() == 0) {
+  if (P.clock_probe != nullptr && scan == 0 && lane_id_now() == 0) {
     P.clock_probe[2] = __builtin_readcyclecounter();
     P.clock_probe[3] = wall_clock64();
-  }
-}
-
-// ---- HSM_PARITY_EXACT for batches: wave-specialised -----------------------------------------------------------------
-// In exact_round() nine lanes of a wavefront run the nine sequential chains while the other 55 idle: 64 dependent adds
-// (+ the LDS traffic) per 64 beams, about as much issue time as the beam arithmetic itself.  A batch has many scans, so
-// this form lets ONE consumer wavefront run the chains of SEVEN scans side by side -- lane 9 j + t adds term t of scan
-// j -- while seven producer wavefronts (one scan each) compute the products: the chain cost per scan drops 7x and it
-// overlaps the producers' arithmetic.  Per round of 64 beams every producer writes its 9 x 64 products into its slice
-// of a double-buffered LDS stage and the workgroup meets at one barrier; the consumer then sums round r while the
-// producers already compute round r + 1 (buffer reuse is safe: the consumer reaches barrier r + 1 only after chain r).
-// After the last round the consumer publishes the 7 x 9 totals; every producer picks up its nine and solves.  The
-// round count is the workgroup's longest scan (shorter scans pad with +-0 products, which leave a sum unchanged).
-// Summation order per scan: beam 0 .. n-1, one fp32 chain per term -- the reference's (OccGridMapUtil.h:76-98), so the
-// results are bit-identical to gn_match_kernel<..., EXACT> and to the reference.
-// Workgroup shape <NPROD producers, NCONS consumers>: a consumer wavefront runs the chains of NPROD / NCONS <= 7 scans.
-// <7, 1> fills the consumer (63 chain lanes); <8, 2> makes a 4096-scan batch 512 workgroups = exactly two per CU --
-// with <7, 1> it is 586 workgroups, 74 of the 256 CUs get three of them and the launch lasts as long as those.
-constexpr int kExactScans = 7;  // <7, 1>: producers per workgroup; 7 x 9 = 63 chain lanes in the consumer wavefront
-
-#ifndef HSM_EXACT_DEEP  // <8, 2> shape: two texel gathers in flight per producer (needs > 64 VGPRs: 5 waves per SIMD)
-#define HSM_EXACT_DEEP 1
-#endif
-template <int LAYOUT, int NPROD = kExactScans, int NCONS = 1>
-__global__ void __launch_bounds__(64 * (NPROD + NCONS), (NPROD == 8 && HSM_EXACT_DEEP) ? 5 : 8)
-gn_match_exact_batch_kernel(const MatchParams P) {
-  constexpr bool kDeep = NPROD == 8 && HSM_EXACT_DEEP;
-  constexpr int kExactScans = NPROD;  // shadows the namespace constant: scans (= producer wavefronts) per workgroup
-  constexpr int SPC = NPROD / NCONS;  // scans per consumer wavefront
-  static_assert(NPROD % NCONS == 0 && SPC <= 7, "a consumer wavefront has 64 lanes for 9 chains per scan");
-  constexpr int ROW = 64 + kExactPad;
-  __shared__ float stage[2][kExactScans][9][ROW];
-  __shared__ float tot[kExactScans][9];
-  __shared__ int nmax_s;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const bool consumer = wave >= kExactScans;
-  const int scan = __builtin_amdgcn_readfirstlane((int)blockIdx.x * kExactScans + wave);
-  const bool active = !consumer && scan < P.batch;
-  int beg = 0, n = 0;
-  float pw0 = 0.0f, pw1 = 0.0f, pw2 = 0.0f;
-  if (active) {
-    n = P.shared_n;
-    if (P.offsets) {
-      beg = P.offsets[scan];
-      n = P.offsets[scan + 1] - beg;
-    }
-    pw0 = P.begin_world[3 * scan + 0];
-    pw1 = P.begin_world[3 * scan + 1];
-    pw2 = P.begin_world[3 * scan + 2];
-  }
-  const float b0 = pw0, b1 = pw1, b2 = pw2;  // an empty scan passes its start estimate through untouched (ScanMatcher.h:68,189)
-  if (threadIdx.x == 0) nmax_s = 0;
-  __syncthreads();
-  if (lane == 0 && n > 0) atomicMax(&nmax_s, n);
-  __syncthreads();
-  const int rounds = (nmax_s + 63) >> 6;  // workgroup-uniform
-  if (rounds == 0) {                      // nothing but empty scans
-    if (active && lane == 0) {
-      P.out_pose[3 * scan + 0] = b0;
-      P.out_pose[3 * scan + 1] = b1;
-      P.out_pose[3 * scan + 2] = b2;
-    }
-    return;
-  }
-  const float2* __restrict__ pts = P.pts + beg;
-  Acc9 acc;
-  acc.zero();
-  for (int l = P.first_level; l >= P.last_level; --l) {
-    const LevelView& L = P.lv[l];
-    float ex, ey, eth;
-    affine_apply(L.mapTworld, pw0, pw1, ex, ey);
-    eth = pw2;
-    const float ps = L.pt_scale;
-    const int gn_steps = L.gn_steps;
-    const LevelRegs R = level_regs<LAYOUT>(L);
-    for (int it = 0; it < gn_steps; ++it) {
-      if (consumer) {
-        float run = 0.0f;
-        const int jl = lane / 9, t = lane - 9 * jl;  // lanes >= 9 * SPC idle
-        const int j = (wave - kExactScans) * SPC + (jl < SPC ? jl : 0);
-        for (int r = 0; r < rounds; ++r) {
-          __syncthreads();  // the producers' products of round r are in stage[r & 1]
-          if (lane < 9 * SPC) {
-            const float* row = &stage[r & 1][j][t][0];
-#pragma unroll 4
-            for (int q = 0; q < 64; q += 4) {
-              const float4 v = *reinterpret_cast<const float4*>(row + q);
-              run += v.x;
-              run += v.y;
-              run += v.z;
-              run += v.w;
-            }
-          }
-        }
-        if (lane < 9 * SPC) tot[j][t] = run;
-        __syncthreads();  // totals published
-      } else {
-        float sinRot, cosRot;
-        sincos_f32(eth, sinRot, cosRot);
-        const f2 e2 = step_origin(ex, ey), cs = f2{cosRot, sinRot}, sc = f2{sinRot, cosRot};
-        // two-deep software pipeline: the endpoint of round r + 2 and the texel of round r + 1 are in flight while
-        // the products of round r are computed, so the barrier of a round does not wait for a memory round trip
-        const float2 pad = make_float2(1.0e30f, 1.0e30f);  // padding: exact +-0 products
-        float2 p_next = lane < n ? pts[lane] : pad;
-        BeamRot rot_next, rot_next2;
-        BeamSample b_next = beam_fetch<LAYOUT>(R, e2, cs, sc, f2{p_next.x * ps, p_next.y * ps}, rot_next), b_next2 = b_next;
-        p_next = 64 + lane < n ? pts[64 + lane] : pad;
-        if (kDeep) {  // three-deep: texels of rounds r + 1 and r + 2 and the endpoint of round r + 3 in flight
-          b_next2 = beam_fetch<LAYOUT>(R, e2, cs, sc, f2{p_next.x * ps, p_next.y * ps}, rot_next2);
-          p_next = 128 + lane < n ? pts[128 + lane] : pad;
-        }
-        for (int r = 0; r < rounds; ++r) {
-          const BeamSample b = b_next;
-          const BeamRot rot = rot_next;
-          if (kDeep) {
-            b_next = b_next2;
-            rot_next = rot_next2;
-            if (r + 2 < rounds) {
-              b_next2 = beam_fetch<LAYOUT>(R, e2, cs, sc, f2{p_next.x * ps, p_next.y * ps}, rot_next2);
-              const int i3 = ((r + 3) << 6) + lane;
-              p_next = i3 < n ? pts[i3] : pad;
-            }
-          } else if (r + 1 < rounds) {
-            b_next = beam_fetch<LAYOUT>(R, e2, cs, sc, f2{p_next.x * ps, p_next.y * ps}, rot_next);
-            const int i2 = ((r + 2) << 6) + lane;
-            p_next = i2 < n ? pts[i2] : pad;
-          }
-          float pr[9];
-          beam_products(b, rot, pr);
-          float* st = &stage[r & 1][wave][0][lane];
-#pragma unroll
-          for (int t = 0; t < 9; ++t) st[t * ROW] = pr[t];
-          __syncthreads();
-        }
-        __syncthreads();  // the consumer has published the totals
-        const float* tt = &tot[wave][0];
-        acc.d01 = f2{tt[0], tt[1]}; acc.d2 = tt[2];
-        acc.hd = f2{tt[3], tt[4]}; acc.h22 = tt[5];
-        acc.h01 = tt[6]; acc.hr = f2{tt[7], tt[8]};
-        gn_solve_and_step(acc, ex, ey, eth);
-      }
-    }
-    if (!consumer) {
-      eth = normalize_angle(eth);
-      affine_apply(L.worldTmap, ex, ey, pw0, pw1);
-      pw2 = eth;
-    }
-  }
-  if (active && lane == 0) {
-    const bool empty = n == 0;
-    P.out_pose[3 * scan + 0] = empty ? b0 : pw0;
-    P.out_pose[3 * scan + 1] = empty ? b1 : pw1;
-    P.out_pose[3 * scan + 2] = empty ? b2 : pw2;
-    if (P.out_cov && !empty) {
-      float* c = P.out_cov + 9 * scan;
-      c[0] = acc.hd.x; c[1] = acc.h01; c[2] = acc.hr.x;
-      c[3] = acc.h01; c[4] = acc.hd.y; c[5] = acc.hr.y;
-      c[6] = acc.hr.x; c[7] = acc.hr.y; c[8] = acc.h22;
-    }
   }
 }
 
@@ -1827,11 +1502,8 @@ gn_match_exact_batch_kernel(const MatchParams P) {
 // buffered by step parity: one grid sync per step.
 // Grid barrier of the cooperative matcher: one monotonically increasing device-memory counter (the host passes
 // its value at launch, so it is never reset), one agent-scope release increment per workgroup and an acquire
-// spin by thread 0 -- 2-3 us per GN step cheaper than cooperative_groups' grid.sync() (HSM_COOP_BARRIER=0
-// selects that one).  All K workgroups are co-resident: the launch is still a cooperative launch.
-#ifndef HSM_COOP_BARRIER
-#define HSM_COOP_BARRIER 1
-#endif
+// spin by thread 0 -- 2-3 us per GN step cheaper than cooperative_groups' grid.sync().  All K workgroups are co-resident:
+// the launch is still a cooperative launch.
 // TAGGED (default since round 3; env HSM_COOP_TAGGED=0 selects the counter barrier at run time): no grid barrier at all --
 // tagged 16-byte records, see the kernel.  That exchange relies on a 16-byte sc0 sc1 store being observed untorn, which is
 // documented behaviour of gfx942 / gfx950 only:
@@ -1853,10 +1525,6 @@ __device__ __forceinline__ void coop_barrier(unsigned* counter, unsigned target)
 template <int LAYOUT, bool TAGGED = true>
 __global__ void __launch_bounds__(256) gn_match_coop_kernel(const MatchParams P, float* __restrict__ partials,
                                                             unsigned* __restrict__ bar_counter, unsigned bar_base) {
-#if !HSM_COOP_BARRIER
-  namespace cg = cooperative_groups;
-  cg::grid_group grid = cg::this_grid();
-#endif
   __shared__ float red[4][9];
   __shared__ float tot[9];
   __shared__ int gave_up;  // the exchange timed out in this workgroup: leave (ordered by the barriers of the step)
@@ -1961,11 +1629,7 @@ __global__ void __launch_bounds__(256) gn_match_coop_kernel(const MatchParams P,
       } else {
       float* mine = partials + ((size_t)(step & 1) * K + blockIdx.x) * 9;
       if (threadIdx.x < 9) mine[threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
-#if HSM_COOP_BARRIER
       coop_barrier(bar_counter, bar_base + (unsigned)K * (unsigned)(step + 1));
-#else
-      grid.sync();
-#endif
       // every workgroup: the same K partials in the same order
       if (wave == 0) {
         const float* src = partials + ((size_t)(step & 1) * K + lane) * 9;

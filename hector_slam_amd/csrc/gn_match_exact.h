@@ -26,7 +26,7 @@
 //     Hence: everything that can be done by the producers in parallel is done there (the multiplications), the owner
 //     keeps a raised priority until its next row is staged, and the job itself is only reads + adds.
 //   Same arithmetic on the same texels in the same order as gn_match_kernel<.., EXACT>: identical bits.
-//   Against round 2's producer / chain-wavefront form (gn_match_exact_batch_kernel: endpoints streamed, no texel cache):
+//   Against round 2's producer / chain-wavefront form (endpoints streamed, no texel cache; since removed):
 //   66-69 vs 92 us on the 2048^2 headline batch, 141-143 vs 199 us on the 3-level batch, 156-162 vs 291 us on the 4096^2
 //   pyramid, whose gathers miss the L2.
 #pragma once
@@ -36,38 +36,24 @@ namespace hsm {
 
 constexpr int kXRow = 64 + kExactPad;  // floats per staged row: 16-byte aligned rows, chain lanes on distinct banks
 
-#ifndef HSM_XEARLY  // round 6: wavefronts run ahead of the round barriers so that the owner's interval holds only the job --
-                    // 2 = the balanced schedule (3 / 3 / 2 half-rows + job), 1 = the next owner produces two rows, 0 = round 3's schedule
-#define HSM_XEARLY 2
-#endif
 #ifndef HSM_XBPC  // cached rows of the 17-row instantiation (see the kernel)
 #define HSM_XBPC 15
 #endif
 #ifndef HSM_XBPC_MAIN  // ... of the four-producer form without a chain wavefront (the 4096-scan launch): the balanced schedule holds
-#define HSM_XBPC_MAIN (HSM_XEARLY == 2 ? 13 : HSM_XBPC)  // a row's nine products across a barrier, which 15 cached rows do not leave room for
+#define HSM_XBPC_MAIN 13  // a row's nine products across a barrier, which 15 cached rows do not leave room for
 #endif
 #ifndef HSM_XBPC_CW  // ... of the chain-wavefront form (five wavefronts per SIMD: 96 VGPRs)
 #define HSM_XBPC_CW 6
-#endif
-#ifndef HSM_XLDS_AHEAD
-#define HSM_XLDS_AHEAD 1
 #endif
 constexpr int kXRows = 9;  // staged rows per scan and round: the nine products of OccGridMapUtil.h:83-97
 #ifndef HSM_XOWNER_PRIO_P  // priority the job's owner keeps while it produces its next row (until the next barrier)
 #define HSM_XOWNER_PRIO_P 1
 #endif
-#ifndef HSM_XOWNER_SHIFT  // >= 0: the owner rotation of workgroup b starts at (b >> SHIFT) & 3 (workgroups of one CU out of phase)
+#ifndef HSM_XOWNER_SHIFT  // the owner rotation of workgroup b starts at (b >> SHIFT) & 3 (workgroups of one CU out of phase)
 #define HSM_XOWNER_SHIFT 8
-#endif
-#ifndef HSM_XPEEL  // the first GN step takes the endpoints from their load registers (gn_match_cached_kernel's peeled step)
-#define HSM_XPEEL 1
 #endif
 #ifndef HSM_XEP_AHEAD  // endpoint loads in flight ahead of the beam being located in that step
 #define HSM_XEP_AHEAD 2
-#endif
-#ifndef HSM_XGATHER_ALWAYS  // lane 0 re-reads its texel at every beam: exactly one load per beam, static waits, no branches
-                            // (four instructions less per row on the owner's path: ~1 us per launch, profiles/r03/README.md)
-#define HSM_XGATHER_ALWAYS 1
 #endif
 #ifndef HSM_XJOB_PRIO  // issue priority of a wavefront while it runs a chain job (the round's critical path)
 #define HSM_XJOB_PRIO 3
@@ -102,9 +88,9 @@ constexpr int kXRows = 9;  // staged rows per scan and round: the nine products 
   } while (0)
 #endif
 
-#ifndef HSM_XWGPRIO  // issue priority of a workgroup's producers by its dispatch order on the CU (blockIdx >> 8): the hardware arbitrates
-#define HSM_XWGPRIO 3  // by priority, then AGE, so the workgroup dispatched last to a CU loses every tie and ends last (profiles/r06).
-#endif                 // 0 = off; 1 = priority = order; 2 = (order + GN step) & 3: every workgroup is favoured in some steps; 3 = min(order, 2)
+// Issue priority of a workgroup's producers by its dispatch order on the CU (blockIdx >> 8), capped at 2: the hardware arbitrates
+// by priority, then AGE, so the workgroup dispatched last to a CU loses every tie and ends last.  (Measured against no priority,
+// priority = order and (order + GN step) & 3: profiles/r06.)
 __device__ __forceinline__ void set_prio_uniform(int p) {  // s_setprio takes an immediate
   if (p <= 0) __builtin_amdgcn_s_setprio(0);
   else if (p == 1) __builtin_amdgcn_s_setprio(1);
@@ -254,11 +240,10 @@ __global__ void __launch_bounds__(64 * (NS + (CW ? 1 : 0)), CW && 5 * BPC + 50 <
   // takes its endpoint from the register of a load issued kEpAhead beams earlier (and stores it, scaled for the level,
   // for the later steps), every lane gathers its texel (a level's first step), and all waits are counted from
   // peel_schedule()'s static issue order.
-  constexpr bool kPeel = HSM_XPEEL != 0;
   constexpr int kEpAhead = HSM_XEP_AHEAD < BPL ? HSM_XEP_AHEAD : BPL - 1;
   static_assert(BPL <= 31, "PeelSchedule holds 32 positions per load kind");
   constexpr PeelSchedule kSched = peel_schedule(BPL, kEpAhead);
-  const bool peel = kPeel && P.lv[P.first_level].gn_steps > 0;  // workgroup-uniform
+  const bool peel = P.lv[P.first_level].gn_steps > 0;  // workgroup-uniform
   if (!peel) {
 #pragma unroll
     for (int k = 0; k < BPL; ++k) {
@@ -276,7 +261,7 @@ __global__ void __launch_bounds__(64 * (NS + (CW ? 1 : 0)), CW && 5 * BPC + 50 <
   acc.zero();
   float reg_scale = 1.0f;
   int step_no = 0;
-  const int owner_phase = HSM_XOWNER_SHIFT >= 0 ? (int)((blockIdx.x >> (HSM_XOWNER_SHIFT >= 0 ? HSM_XOWNER_SHIFT : 0)) & 3u) : 0;
+  const int owner_phase = (int)((blockIdx.x >> HSM_XOWNER_SHIFT) & 3u);
   // LDS byte address of this wavefront's stage rows in buffer 0 (wave-uniform; a generic LDS pointer's low half)
   const unsigned st_wave = __builtin_amdgcn_readfirstlane((unsigned)(size_t)&stage[0][wave][0][0]);
   for (int l = P.first_level; l >= P.last_level; --l) {
@@ -342,7 +327,7 @@ __global__ void __launch_bounds__(64 * (NS + (CW ? 1 : 0)), CW && 5 * BPC + 50 <
       };
       // rotate, bounds test, cell offset, fractions; gather only in the lanes whose cell changed (gn_match_cached_kernel)
       f4v tu[2];  // texels of the uncached rows (k >= BPC), alternating
-      auto locate = [&](int k, f2 p, BeamRot& r, float& fx, float& fy) -> unsigned long long {
+      auto locate = [&](int k, f2 p, BeamRot& r, float& fx, float& fy) {
         r.r.x = cs.x * p.x - sc.x * p.y;
         r.r.y = cs.y * p.x + sc.y * p.y;
         const CellCoord q = cell_coord(R, f2{e2.x + r.r.x, e2.y + r.r.y});
@@ -353,16 +338,18 @@ __global__ void __launch_bounds__(64 * (NS + (CW ? 1 : 0)), CW && 5 * BPC + 50 <
         const unsigned off = q.oob ? zero_off : idx << 4;
         if (k >= BPC) {  // uncached row: every lane gathers
           asm volatile("global_load_dwordx4 %[t], %[o], %[b]" : [t] "=v"(tu[k & 1]) : [o] "v"(off), [b] "s"(R.quad) : "memory");
-          return ~0ull;
+          return;
         }
         const int kc = k < BPC ? k : 0;
         if (kFirst) {  // a level's first step: every lane gathers (toff[] holds no offset yet); one load, statically counted
           asm volatile("global_load_dwordx4 %[t], %[o], %[b]" : [t] "=v"(tq[kc]) : [o] "v"(off), [b] "s"(R.quad) : "memory");
           toff[kc] = off;
-          return ~0ull;
+          return;
         }
-        unsigned long long moved, saved;
-#if HSM_XGATHER_ALWAYS
+        // lane 0 re-reads its texel at every beam (same value: the map does not change under the kernel): exactly one load per
+        // beam, static waits, no branches (four instructions less per row on the owner's path than a gather that the whole
+        // wavefront may skip: ~1 us per launch, profiles/r03/README.md)
+        unsigned long long saved;
         asm volatile(
             "v_cmp_ne_u32 vcc, %[o], %[to]\n\t"
             "s_or_b32 vcc_lo, vcc_lo, 1\n\t"
@@ -373,40 +360,13 @@ __global__ void __launch_bounds__(64 * (NS + (CW ? 1 : 0)), CW && 5 * BPC + 50 <
             : [t] "+v"(tq[kc]), [to] "+v"(toff[kc]), [sv] "=&s"(saved)
             : [o] "v"(off), [b] "s"(R.quad)
             : "vcc", "scc", "memory");
-        return ~0ull;
-#endif
-        asm volatile(
-            "v_cmp_ne_u32 vcc, %[o], %[to]\n\t"
-            "s_mov_b64 %[mv], vcc\n\t"
-            "s_and_saveexec_b64 %[sv], vcc\n\t"
-            "s_cbranch_execz 1f\n\t"
-            "global_load_dwordx4 %[t], %[o], %[b]\n\t"
-            "v_mov_b32 %[to], %[o]\n\t"
-            "1:\n\t"
-            "s_mov_b64 exec, %[sv]"
-            : [t] "+v"(tq[kc]), [to] "+v"(toff[kc]), [sv] "=&s"(saved), [mv] "=&s"(moved)
-            : [o] "v"(off), [b] "s"(R.quad)
-            : "vcc", "scc", "memory");
-        return moved;
       };
-      auto texel_ready = [&](int k, unsigned long long next_moved, bool has_next) {
+      auto texel_ready = [&](int k, bool has_next) {
         f4v& tx = k < BPC ? tq[k < BPC ? k : 0] : tu[k & 1];
         if (kFirst) {  // static schedule: everything issued after beam k's gather may still be in flight
           wait_vmcnt((has_next ? kSched.posG[k + 1] + 1 : kSched.total) - kSched.posG[k] - 1, tx);
-        } else if (has_next && (k + 1 >= BPC || HSM_XGATHER_ALWAYS)) {  // the next row's gather is unconditional
+        } else if (has_next) {  // the next row's gather is unconditional: exactly one load behind beam k's
           asm volatile("s_waitcnt vmcnt(1)" : "+v"(tx) : : "memory");
-        } else if (has_next) {
-          asm volatile(
-              "s_cmp_eq_u64 %[m], 0\n\t"
-              "s_cbranch_scc1 1f\n\t"
-              "s_waitcnt vmcnt(1)\n\t"
-              "s_branch 2f\n\t"
-              "1:\n\t"
-              "s_waitcnt vmcnt(0)\n\t"
-              "2:"
-              : "+v"(tx)
-              : [m] "s"(next_moved)
-              : "scc", "memory");
         } else {
           asm volatile("s_waitcnt vmcnt(0)" : "+v"(tx) : : "memory");
         }
@@ -509,8 +469,8 @@ __global__ void __launch_bounds__(64 * (NS + (CW ? 1 : 0)), CW && 5 * BPC + 50 <
         }
       };
       const int wg_order = (int)((blockIdx.x >> 8) & 3u);
-      const int wg_prio = HSM_XWGPRIO == 1 ? wg_order : HSM_XWGPRIO == 2 ? ((wg_order + step_no) & 3) : HSM_XWGPRIO == 3 ? min(wg_order, 2) : 0;
-      if (HSM_XWGPRIO != 0 && !CW) set_prio_uniform(wg_prio);
+      const int wg_prio = min(wg_order, 2);
+      if (!CW) set_prio_uniform(wg_prio);
       // round k is staged: meet, then (one wavefront) run the chain jobs that are complete with it
       const int my_rounds =
           __builtin_amdgcn_readfirstlane((int)((unsigned)(wave + 64 * NS - (step_no + owner_phase) % NS) % (unsigned)NS));
@@ -529,15 +489,6 @@ __global__ void __launch_bounds__(64 * (NS + (CW ? 1 : 0)), CW && 5 * BPC + 50 <
         asm volatile("" : "+s"(mine_now));
         if ((int)((unsigned)k % (unsigned)NS) != mine_now) return;
         __builtin_amdgcn_s_setprio(HSM_XJOB_PRIO);
-#if defined(HSM_EXPERIMENTS) && defined(HSM_XWHATIF) && HSM_XWHATIF == 1  // timing experiment: every job runs twice (same sums: the second run starts from the first's input)
-        for (int j = j_lo; j < j_hi; ++j) {
-          const float keep = lane < NC ? runs[lane] : 0.0f;
-          chain_job(j, k);
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          if (lane < NC) runs[lane] = keep;
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        }
-#endif
         for (int j = j_lo; j < j_hi; ++j) chain_job(j, k);
         __builtin_amdgcn_s_setprio(HSM_XOWNER_PRIO_P);
         if (k < BPL) HSM_XT(k, 2);
@@ -545,18 +496,13 @@ __global__ void __launch_bounds__(64 * (NS + (CW ? 1 : 0)), CW && 5 * BPC + 50 <
       {
         BeamRot rc, rn;
         float fxc, fyc, fxn = 0.0f, fyn = 0.0f;
-        unsigned long long next_moved = 0ull;
-        constexpr bool kAhead = HSM_XLDS_AHEAD != 0 && !kFirst;
-        // (the first, peeled step keeps the rotating-owner schedule: measured slower with either early form -- all lanes gather, the
-        // endpoints stream from HBM, its waits are counted from a static issue order)
-#ifndef HSM_XEARLY_FIRST
-#define HSM_XEARLY_FIRST 0
-#endif
-        // (... and so does the 17-row form with fifteen cached rows, which has no registers left to hold a row across a barrier: the
-        // instantiation for maps that outgrow the L2s -- 4096^2 pyramid: 145 us with 15 cached rows and the rotating owner, 153 us
-        // with 13 and the balanced schedule, profiles/r06)
-        constexpr bool kBalanced = HSM_XEARLY == 2 && !CW && NCP == 64 && (!kFirst || HSM_XEARLY_FIRST != 0) && (BPL < 17 || BPC <= HSM_XBPC_MAIN);
-        constexpr bool kEarly = HSM_XEARLY == 1 && !CW && NCP == 64 && !kFirst;
+        constexpr bool kAhead = !kFirst;
+        // The balanced schedule (below) for the four-producer forms with one job per round.  The first, peeled step keeps the
+        // rotating-owner schedule: measured slower with the balanced one -- all lanes gather, the endpoints stream from HBM, its
+        // waits are counted from a static issue order.  And so does the 17-row form with fifteen cached rows, which has no
+        // registers left to hold a row across a barrier: the instantiation for maps that outgrow the L2s -- 4096^2 pyramid: 145 us
+        // with 15 cached rows and the rotating owner, 153 us with 13 and the balanced schedule, profiles/r06
+        constexpr bool kBalanced = !CW && NCP == 64 && !kFirst && (BPL < 17 || BPC <= HSM_XBPC_MAIN);
         f2 p_next = f2{0.0f, 0.0f};
         if (kAhead) p_next = endpoint(BPL > 1 ? 1 : 0);
         locate(0, endpoint(0), rc, fxc, fyc);
@@ -566,13 +512,10 @@ __global__ void __launch_bounds__(64 * (NS + (CW ? 1 : 0)), CW && 5 * BPC + 50 <
           if (kAhead) {  // endpoint of beam k+2 read from LDS before beam k+1 is located (two more VGPRs)
             const f2 p_cur = p_next;
             if (k + 2 < BPL) p_next = endpoint(k + 2);
-            if (k + 1 < BPL) next_moved = locate(k + 1, p_cur, rn, fxn, fyn);
+            if (k + 1 < BPL) locate(k + 1, p_cur, rn, fxn, fyn);
           } else {
-            if (k + 1 < BPL) next_moved = locate(k + 1, endpoint(k + 1), rn, fxn, fyn);
+            if (k + 1 < BPL) locate(k + 1, endpoint(k + 1), rn, fxn, fyn);
           }
-#if defined(HSM_EXPERIMENTS) && defined(HSM_XWHATIF) && HSM_XWHATIF == 2  // timing experiment: a second workgroup barrier per round
-          asm volatile("s_barrier" ::: "memory");
-#endif
           if (kBalanced) {
             // Round 6.  Where a round's time went (profiles/r06/README.md: s_memtime per round): the owner of round k's job ran it behind
             // barrier k and THEN produced its row k+1 -- job (~700 cycles) + production (~500) on every round's critical path, three
@@ -588,10 +531,9 @@ __global__ void __launch_bounds__(64 * (NS + (CW ? 1 : 0)), CW && 5 * BPC + 50 <
             asm volatile("" : "+s"(mine_now));  // (compared afresh in an SGPR at every round: see round_done)
             const int o = (int)((unsigned)(k + NS - mine_now) % (unsigned)NS);
             if (o == 3 && k >= 1) {
-              if (HSM_XWGPRIO == 0 && HSM_XOWNER_PRIO_P != 0) __builtin_amdgcn_s_setprio(0);
               asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
             }
-            texel_ready(k, next_moved, k + 1 < BPL);
+            texel_ready(k, k + 1 < BPL);
             const f4v& tx = k < BPC ? tq[k < BPC ? k : 0] : tu[k & 1];
             float pp[9];
             products(tx.x, tx.y, tx.z, tx.w, rc, fxc, fyc, pp);
@@ -599,13 +541,12 @@ __global__ void __launch_bounds__(64 * (NS + (CW ? 1 : 0)), CW && 5 * BPC + 50 <
               stage_write(k, pp);
               if (k == 0 && o == 1) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // (no job -1 to run)
             } else {  // o = 0, 1 with k >= 1: the products wait for barrier k-1
-              if (HSM_XWGPRIO == 0 && HSM_XOWNER_PRIO_P != 0) __builtin_amdgcn_s_setprio(0);
               asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
               stage_write(k, pp);
               if (o == 1) {
                 __builtin_amdgcn_s_setprio(HSM_XJOB_PRIO);
                 chain_job(k - 1, k - 1);
-                if (HSM_XWGPRIO != 0) set_prio_uniform(wg_prio); else __builtin_amdgcn_s_setprio(0);
+                set_prio_uniform(wg_prio);
                 asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
               }
             }
@@ -614,55 +555,11 @@ __global__ void __launch_bounds__(64 * (NS + (CW ? 1 : 0)), CW && 5 * BPC + 50 <
               if (o == 0) {
                 __builtin_amdgcn_s_setprio(HSM_XJOB_PRIO);
                 chain_job(k, k);
-                if (HSM_XWGPRIO != 0) set_prio_uniform(wg_prio); else __builtin_amdgcn_s_setprio(0);
-              }
-            }
-          } else if (kEarly) {
-            texel_ready(k, next_moved, k + 1 < BPL);
-            // Round 6.  The owner of round k's job used to run it behind barrier k and THEN produce its row k+1 -- job + production
-            // on every round's critical path, three wavefronts parked at barrier k+1 meanwhile (SQ_WAIT_ANY 0.53 of the wavefront
-            // cycles, profiles/r06/stall_table.txt).  Now the owner-to-be produces row k+1 BEFORE barrier k (its products wait in nine
-            // registers: stage buffer (k+1) % 2 is still being read by job k-1), so behind barrier k it only stages them and runs
-            // the job: an interval lasts max(job, two productions) instead of job + production.  Every wavefront still meets
-            // exactly one barrier per round; same products, same order of the additions.
-            const f4v& tx = k < BPC ? tq[k < BPC ? k : 0] : tu[k & 1];
-            float pp[9];
-            products(tx.x, tx.y, tx.z, tx.w, rc, fxc, fyc, pp);
-            int mine_now = my_rounds;
-            asm volatile("" : "+s"(mine_now));  // (compared afresh in an SGPR at every round: see round_done)
-            const bool own_k = (int)((unsigned)k % (unsigned)NS) == mine_now;
-            const bool own_km1 = k >= 1 && (int)((unsigned)(k + NS - 1) % (unsigned)NS) == mine_now;
-            if (own_km1) {  // row k was produced early: barrier k-1, stage it, job k-1, barrier k
-              if (HSM_XOWNER_PRIO_P != 0) __builtin_amdgcn_s_setprio(0);
-              HSM_XT(k - 1, 0);
-              asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-              HSM_XT(k - 1, 1);
-              stage_write(k, pp);
-              __builtin_amdgcn_s_setprio(HSM_XJOB_PRIO);
-              chain_job(k - 1, k - 1);
-              __builtin_amdgcn_s_setprio(0);
-              HSM_XT(k - 1, 2);
-              HSM_XT(k, 0);
-              asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-              HSM_XT(k, 1);
-            } else {
-              stage_write(k, pp);
-              if (own_k && k + 1 < BPL) {
-                __builtin_amdgcn_s_setprio(HSM_XOWNER_PRIO_P);  // no barrier here: this wavefront produces row k+1 first
-              } else {
-                HSM_XT(k, 0);
-                asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-                HSM_XT(k, 1);
-                if (own_k) {  // the last cached row is this wavefront's: nothing to produce ahead
-                  __builtin_amdgcn_s_setprio(HSM_XJOB_PRIO);
-                  chain_job(k, k);
-                  __builtin_amdgcn_s_setprio(0);
-                  HSM_XT(k, 2);
-                }
+                set_prio_uniform(wg_prio);
               }
             }
           } else {
-            texel_ready(k, next_moved, k + 1 < BPL);
+            texel_ready(k, k + 1 < BPL);
             {
               const f4v& tx = k < BPC ? tq[k < BPC ? k : 0] : tu[k & 1];
               produce(k, tx.x, tx.y, tx.z, tx.w, rc, fxc, fyc);
@@ -697,7 +594,7 @@ __global__ void __launch_bounds__(64 * (NS + (CW ? 1 : 0)), CW && 5 * BPC + 50 <
       ex = uniform_f32(ex), ey = uniform_f32(ey), eth = uniform_f32(eth);
     };
     int it = 0;
-    if (kPeel && peel_here) {
+    if (peel_here) {
       gn_step(std::true_type{});
       ++step_no;
       it = 1;

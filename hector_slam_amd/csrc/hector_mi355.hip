@@ -441,12 +441,8 @@ int prepare_level(hsm_ctx* h, UpdateBatch& batch, LevelPrep& prep, int level, co
       if (L.key_rows[1] >= L.key_rows[0]) {
         const size_t y0 = (size_t)L.key_rows[0], y1 = (size_t)L.key_rows[1];
         HIP_TRY(hipMemsetAsync(L.d_key_occ + y0 * L.sx, 0, (y1 - y0 + 1) * L.sx * sizeof(unsigned int), h->stream));
-#if HSM_KEYFREE_TILE
         const size_t row_words = (size_t)key_free_tiles_x(L.sx) * 32u;  // one row of 8x4-cell tiles
         HIP_TRY(hipMemsetAsync(L.d_key_free + (y0 >> 2) * row_words, 0, ((y1 >> 2) - (y0 >> 2) + 1) * row_words * sizeof(unsigned int), h->stream));
-#else
-        HIP_TRY(hipMemsetAsync(L.d_key_free + y0 * L.sx, 0, (y1 - y0 + 1) * L.sx * sizeof(unsigned int), h->stream));
-#endif
       }
       L.key_rows[0] = 0;
       L.key_rows[1] = -1;
@@ -557,14 +553,10 @@ void level_bbox(hsm_ctx* h, UpdateBatch& batch, LevelPrep& prep, const UpdatePar
 // dense scans (>= merged_mark_max beams) take the byte-map form of the update (map_update.h), on every map width since round 4;
 // env HSM_DENSE_BITS=0 keeps them on the keyed one-launch mark pass of the small scans
 bool use_dense_bits(const hsm_ctx* h, const UpdateBatch& batch, int max_n) {
-#if HSM_KEYFREE_TILE
   if (!h->dense_bits || max_n < h->merged_mark_max) return false;
   for (int i = 0; i < batch.nlev; ++i)
     if (batch.lv[i].lv.free_bytes == nullptr) return false;
   return true;
-#else
-  return false;
-#endif
 }
 
 // pass 1 of map_update.h for all levels of the batch (grid.y = level): needs no box
@@ -586,22 +578,10 @@ int launch_update_mark(hsm_ctx* h, UpdateBatch& batch) {
     HIP_TRY(hipGetLastError());
     return HSM_OK;
   }
-#if defined(HSM_EXPERIMENTS)
-  if (max_n >= h->merged_mark_max) {
-    // rounds 1-2: dense scans on two launches (end cells, then the line walk with plain tag stores where no beam ends);
-    // superseded by the byte-map form on every map width, kept for A/B builds
-    hipLaunchKernelGGL(update_mark_occ_kernel, dim3((max_n + 255) / 256, ny), dim3(256), 0, h->stream, batch);
-    hipLaunchKernelGGL(update_mark_free_kernel, dim3((max_n + 3) / 4, ny), dim3(256), 0, h->stream, batch);  // 4 beams (waves) per block
-    HIP_TRY(hipGetLastError());
-    return HSM_OK;
-  }
-#endif
-  {
-    // small scans (and HSM_DENSE_BITS=0): end-cell marks and line walks in ONE launch (keyed atomics, map_update.h) -- one
-    // dependent launch less
-    const unsigned occ_blocks = (unsigned)(max_n + 255) / 256;
-    hipLaunchKernelGGL(update_mark_kernel, dim3(occ_blocks + (max_n + 3) / 4, ny), dim3(256), 0, h->stream, batch, occ_blocks);
-  }
+  // small scans (and HSM_DENSE_BITS=0): end-cell marks and line walks in ONE launch (keyed atomics, map_update.h) -- one
+  // dependent launch less
+  const unsigned occ_blocks = (unsigned)(max_n + 255) / 256;
+  hipLaunchKernelGGL(update_mark_kernel, dim3(occ_blocks + (max_n + 3) / 4, ny), dim3(256), 0, h->stream, batch, occ_blocks);
   HIP_TRY(hipGetLastError());
   return HSM_OK;
 }
@@ -841,11 +821,6 @@ int hsm_create(float map_resolution, int size_x, int size_y, unsigned levels, fl
   if (const char* env = getenv("HSM_EXACT_CHAIN_WAVE")) h->exact_chain_wave = atoi(env);
   if (const char* env = getenv("HSM_EXACT_SPLIT_TAIL")) h->exact_split_tail = atoi(env);
   if (const char* env = getenv("HSM_WG_SYNC")) h->wg_sync = atoi(env) != 0;
-#if defined(HSM_EXPERIMENTS)  // switches of forms that only an experiment build holds
-  if (const char* env = getenv("HSM_EXACT_BATCH")) h->exact_batch_form = atoi(env);
-  if (const char* env = getenv("HSM_EXACT_SHAPE")) h->exact_shape = atoi(env);
-  if (const char* env = getenv("HSM_CACHED_WPS2")) h->cached_wps2 = atoi(env) != 0;
-#endif
   if (const char* env = getenv("HSM_SPB_LARGE")) h->spb_large = atoi(env) == 8 ? 8 : 4;
   if (const char* env = getenv("HSM_XCD_CHUNK")) h->xcd_chunk = atoi(env) > 0 ? atoi(env) : 0;
   if (const char* env = getenv("HSM_XCD_CHUNK_EXACT")) h->xcd_chunk_exact = atoi(env) > 0 ? atoi(env) : 0;
@@ -1078,14 +1053,13 @@ static int order_map_reader(hsm_ctx* h, hipStream_t s, const char* who, hsm_ctx:
     }
     return HSM_OK;
   }
-#if !defined(HSM_EXP_NO_XSTREAM_ORDER)  // (negative control of test_queued_updates_are_ordered_against_caller_streams)
+  // (what test_queued_updates_are_ordered_against_caller_streams holds)
   if (fs->ordered_epoch != h->upd_epoch) {  // THIS stream has not been ordered behind the latest map writes yet
     if (!h->evt_updates) HIP_TRY(hipEventCreateWithFlags(&h->evt_updates, hipEventDisableTiming));
     HIP_TRY(hipEventRecord(h->evt_updates, h->stream));
     HIP_TRY(hipStreamWaitEvent(s, h->evt_updates, 0));
     fs->ordered_epoch = h->upd_epoch;
   }
-#endif
   // no marker here (an event record between back-to-back launches costs 2-3 us of kernel time each): the
   // next writer of the map records one on every stream with a pending reader (order_after_foreign_match)
   *mark = fs;
@@ -1471,9 +1445,6 @@ static int match_single(hsm_ctx* h, MatchParams& P, const float begin_world[3], 
     // one beam per lane.  16 k beams, matchData us for K = 16 / 24 / 32 / 64 workgroups: 79.8 / 71 / 66-70 / 64 with round 2's grid
     // barrier; 70 (24) / 67-71 (31) / 76 (48) / 63-64 (64) with the tagged exchange (profiles/r03/README.md)
     int K = (n + 255) / 256;
-#if defined(HSM_EXPERIMENTS)
-    if (const char* env = getenv("HSM_COOP_K")) K = atoi(env);
-#endif
     if (K > 64) K = 64;
     if (K < 2) K = 2;
     float* partials = h->d_partials;

@@ -46,7 +46,7 @@ struct Level {
   unsigned int* d_key_free = nullptr;
   unsigned int* d_key_occ = nullptr;
   unsigned int* d_occ_bits = nullptr;
-  unsigned char* d_free_bytes = nullptr;  // dense scans: crossed-cell byte map in the key_free tiling (map_update.h)
+  unsigned char* d_free_bytes = nullptr;  // dense scans: crossed-cell byte map in 16 x 8-cell tiles (map_update.h)
   // GridMapLogOddsFunctions (GridMapLogOdds.h:200-203)
   float log_odds_free = 0.f, log_odds_occ = 0.f;
   // OccGridMapBase counters / GridMapBase::lastUpdateIndex
@@ -58,13 +58,7 @@ struct Level {
   bool marks_pending = false;     // a mark pass was queued on this level and its apply pass has not been (scrub_marks)
   size_t cells() const { return (size_t)sx * sy; }
   int tiles_x() const { return (sx + 3) / 4; }
-  int quad_texels() const {
-#if HSM_QUAD_TILE
-    return tiles_x() * ((sy + 1) / 2) * 8;
-#else
-    return sx * sy;
-#endif
-  }
+  int quad_texels() const { return sx * sy; }
 };
 
 // Teardown never stops at a failing call (everything else still has to be released), but it must not swallow one either: HIP
@@ -248,16 +242,13 @@ struct hsm_ctx {
   bool coop_tagged = true;      // env HSM_COOP_TAGGED=0: the counter grid barrier instead of the tagged-record exchange
   Buf<char> d_cells{&bufs};  // interleaved {logodds, updateIndex} staging for hsm_download_cells
   int bpl_override = -1;  // 0 = force the memory loop (env HSM_BPL=0), -1 = auto
-  int exact_batch_form = 2;      // env HSM_EXACT_BATCH: 0 = the one-wavefront-per-scan exact form for batches, too; 1 = producer / chain workgroups on maps <= 2^23 cells only (the rule until the <8,2> shape); 2 = on every map
   int xcd_chunk_exact = 0;       // env HSM_XCD_CHUNK_EXACT: the same for the exact-order texel-cache form (0 = contiguous eighths, its default)
   int xcd_chunk = 16;            // env HSM_XCD_CHUNK: workgroups per chunk of the chunked-cyclic batch mapping (0 = contiguous eighths)
   unsigned long long* clock_probe = nullptr;  // hsm_set_clock_probe
-  bool cached_wps2 = false;      // env HSM_CACHED_WPS2=1: with waves_per_scan = 2, batches use the two-wave texel-cache form (experimental)
   int spb_large = 8;             // env HSM_SPB_LARGE=4|8: scans per workgroup of the texel-cache matcher on maps > 2^23 cells
   int wg_sync = -1;              // env HSM_WG_SYNC=0|1: per-beam workgroup barrier of the texel-cache matcher (-1 = for maps > 2^23 cells)
-  int exact_shape = 0;           // env HSM_EXACT_SHAPE=7|8: producers per workgroup of the exact batch form (0 = by batch size)
   bool dense_bits = true;        // env HSM_DENSE_BITS=0: dense scans keep the keyed update (map_update.h)
-  bool exact_cached = true;      // env HSM_EXACT_CACHED=0: exact-mode batches keep round 2's producer / chain-wavefront form (gn_match.h)
+  bool exact_cached = true;      // env HSM_EXACT_CACHED=0: exact-mode batches take the one-wavefront-per-scan exact form (gn_match_kernel) instead of gn_match_exact.h's
   bool exact = false;     // HSM_PARITY_EXACT: H / dTr summed in the reference's beam order (gn_match.h exact_round)
   bool auto_parity = true;  // HSM_PARITY_AUTO (default): every entry point in the reference's summation order (auto_wants_exact)
   bool relaxed = false;   // HSM_PARITY_RELAXED: contracted multiply-adds in the throughput kernel (gn_match_cached_kernel<.., RELAXED>)

@@ -11,13 +11,14 @@
 //     is ((l + f) - f) [+ o] instead of l [+ o].  That rounding artefact is reproduced.
 //
 // Parallel formulation (bit-exact with the sequential reference):
-//   pass 1 "mark" (per beam), two launches: (a) every beam atomicMax'es
+//   pass 1 "mark" (per beam): (a) every beam atomicMax'es
 //       key = (scan serial << 20) | (0xFFFFF - beam index) into the occ-key plane at its end cell,
 //       which leaves the FIRST beam (lowest index) ending there; (b) one wavefront per beam, lane k
 //       owns Bresenham steps k, k+64, ... -- the cell of step i has a closed form (minor steps =
 //       floor((e0 + i*db)/da)), so no lane walks the line sequentially -- and tags every crossed
-//       cell in the free-key plane: a plain store of the serial where no beam ends, atomicMax of
-//       the key (lowest crossing beam index, needed for the revert artefact) where one does.
+//       cell in the free-key plane with an atomicMax of the key (lowest crossing beam index, needed
+//       for the revert artefact where a beam also ends).  Dense scans mark one byte per crossed
+//       cell instead (see below).
 //   pass 2 "apply" (per cell, DENSE over the bounding box of the scan):  every cell whose keys
 //       carry the current serial applies the reference's rule -- occupied if any beam ends there
 //       (after undoing the free update when a lower-indexed beam crossed it first), else free --
@@ -55,74 +56,44 @@ struct LevelRW {
   int kf_tiles_x;            // free-key tiles per row = key_free_tiles_x(sx): ceil(sx / 64) * 8   (key_free_index)
 };
 
-// The free-key plane is stored in 8x4-cell tiles (= one 128-byte line).  The line walk of update_mark_free_kernel
-// writes one 4-byte tag per visited cell: row major, a y-major beam touches a new cache line every step and an
+// The free-key plane is stored in 8x4-cell tiles (= one 128-byte line).  The line walk (mark_free_block)
+// writes one 4-byte key per visited cell: row major, a y-major beam touches a new cache line every step and an
 // x-major one every 32 steps; tiled, both touch a new line every 4..8 steps, and the lanes of a wave (64
-// consecutive steps of one beam) share lines either way.  HSM_KEYFREE_TILE=0: row major.
-#ifndef HSM_KEYFREE_TILE
-#define HSM_KEYFREE_TILE 1
-#endif
+// consecutive steps of one beam) share lines either way.
 // tiles per tile row, padded to whole 64-cell BLOCKS (8 tiles): the dense apply pass owns the marks of a 64 x 4-cell block as
 // 256 CONTIGUOUS bytes, so the last block of a row must not run into the next tile row -- with the padding the dense form
 // works for every map width (round 4; until then rows had to be a multiple of 64 cells)
 __host__ __device__ __forceinline__ int key_free_tiles_x(int sx) { return ((sx + 63) / 64) * 8; }
 __host__ __device__ __forceinline__ size_t key_free_cells(int sx, int sy) {
-#if HSM_KEYFREE_TILE
   return (size_t)key_free_tiles_x(sx) * (size_t)((sy + 3) / 4) * 32u;
-#else
-  return (size_t)sx * sy;
-#endif
 }
 __device__ __forceinline__ unsigned int key_free_index(const LevelRW& L, unsigned int x, unsigned int y) {
-#if HSM_KEYFREE_TILE
   return ((((y >> 2) * (unsigned int)L.kf_tiles_x) + (x >> 3)) << 5) | ((y & 3u) << 3) | (x & 7u);
-#else
-  return y * (unsigned int)L.sx + x;
-#endif
 }
 
-// The mark BYTES of the dense form (free_bytes): tiles of 16 x 8 cells = one 128-byte line each (HSM_MARK_TILE16=1, the default
-// since the end of round 4).  Until then they shared the free-key plane's 8 x 4-cell tiling (HSM_MARK_TILE16=0), in which a
-// 128-byte line of BYTES is four tiles side by side = 32 x 4 cells: the 64 steps of a line-walk iteration cross about
-// (dx / 32 + dy / 4 + 1) lines -- ~14.5 averaged over the beam directions of a 360-degree scan -- against (dx / 16 + dy / 8 + 1)
-// ~ 10 with the squarer tile.  The line walk is bound by exactly these scattered byte accesses (profiles/r04/README.md 5):
-// 65.2 -> 57.6 us on configs[4]; the apply pass, which now owns 32 x 8-cell blocks (two tiles = 256 contiguous mark bytes, its
-// plane accesses two 128-byte row segments per wavefront): 68.4 -> 65.1 us; update 0.144 -> 0.1355 ms, maps bit-identical
-// (profiles/r04/README.md 20).
-#ifndef HSM_MARK_TILE16
-#define HSM_MARK_TILE16 1
-#endif
+// The mark BYTES of the dense form (free_bytes): tiles of 16 x 8 cells = one 128-byte line each.  The 64 steps of a line-walk
+// iteration cross about (dx / 16 + dy / 8 + 1) lines -- ~10 averaged over the beam directions of a 360-degree scan -- and the
+// line walk is bound by exactly these scattered byte accesses (profiles/r04/README.md 5).  The apply pass owns 32 x 8-cell
+// blocks (two tiles = 256 contiguous mark bytes, its plane accesses two 128-byte row segments per wavefront).  (Measured
+// against the free-key plane's 8 x 4 tiling, where a line of bytes is 32 x 4 cells and an iteration crosses ~14.5 lines:
+// profiles/r04/README.md 20.)
 __host__ __device__ __forceinline__ int mark_tiles_x(int sx) { return ((sx + 31) / 32) * 2; }  // 16-cell tiles per row, whole 32-cell blocks
 __host__ __device__ __forceinline__ size_t mark_bytes(int sx, int sy) {
-#if HSM_MARK_TILE16
   return (size_t)mark_tiles_x(sx) * (size_t)((sy + 7) / 8) * 128u;
-#else
-  return key_free_cells(sx, sy);
-#endif
 }
 // One byte per 16 x 8 mark TILE behind the mark bytes: "a beam of the current scan ends in this tile" (set by the end-cell pass,
-// cleared by the apply pass; HSM_MARK_TILE_END=1, the default since the end of round 4).  The line walk had to read every mark
-// byte before storing to it -- to learn whether a beam ends in the cell (then the keyed atomicMax decides the revert artefact),
-// and to skip marks already set; that load, ~10 lines of a 67 MB plane per iteration, was a third of the walk.  Now it reads the
-// TILE's byte -- a 128 x smaller, cache-resident map, 1-4 lines per iteration -- and only in the ~1/6 of the tiles where it is set
-// the cell's own byte; everywhere else it stores its mark unread (an already set mark is stored again: same value).
+// cleared by the apply pass).  Without it the line walk has to read every mark byte before storing to it -- to learn whether a
+// beam ends in the cell (then the keyed atomicMax decides the revert artefact), and to skip marks already set; that load, ~10
+// lines of a 67 MB plane per iteration, was a third of the walk.  So it reads the TILE's byte -- a 128 x smaller, cache-resident
+// map, 1-4 lines per iteration -- and only in the ~1/6 of the tiles where it is set the cell's own byte; everywhere else it
+// stores its mark unread (an already set mark is stored again: same value).
 // configs[4]: line walk 57.5 -> 50.0 us, update 0.135 -> 0.127 ms (profiles/r04/README.md 21).
-#ifndef HSM_MARK_TILE_END
-#define HSM_MARK_TILE_END 1
-#endif
-#if HSM_MARK_TILE_END && !HSM_MARK_TILE16
-#error "the tile flags index the 16 x 8 mark tiles"
-#endif
 __host__ __device__ __forceinline__ size_t mark_tile_end_offset(int sx, int sy) { return mark_bytes(sx, sy) + 256; }
 __host__ __device__ __forceinline__ size_t mark_plane_bytes(int sx, int sy) {
-  return mark_bytes(sx, sy) + 256 + (HSM_MARK_TILE_END ? ((mark_bytes(sx, sy) / 128 + 3) & ~(size_t)3) + 256 : 0);
+  return mark_bytes(sx, sy) + 256 + ((mark_bytes(sx, sy) / 128 + 3) & ~(size_t)3) + 256;
 }
 __device__ __forceinline__ unsigned int mark_index(const LevelRW& L, unsigned int x, unsigned int y) {
-#if HSM_MARK_TILE16
   return ((((y >> 3) * (unsigned int)mark_tiles_x(L.sx)) + (x >> 4)) << 7) | ((y & 7u) << 4) | (x & 15u);
-#else
-  return key_free_index(L, x, y);
-#endif
 }
 
 // Key = (generation of the scan << kBeamBits) | (kBeamMask - beam index): atomicMax keeps the newest scan and, within
@@ -267,12 +238,6 @@ __device__ __forceinline__ void mark_occ_block(const UpdateParams& P, unsigned i
   if (head && valid) atomicOr(&P.lv.occ_bits[w], m);
 }
 
-#if defined(HSM_EXPERIMENTS)  // rounds 1-2: dense scans on the keyed planes in two launches (superseded by the byte-map form)
-__global__ void __launch_bounds__(256) update_mark_occ_kernel(const UpdateBatch B) {
-  mark_occ_block(B.lv[blockIdx.y], blockIdx.x);
-}
-#endif
-
 // dense scans: "a beam ends here" is bit 1 of the cell's mark byte instead of a bit of the row-major end-cell bitmap
 constexpr unsigned char kMarkCrossed = 1, kMarkEnd = 2;
 
@@ -308,34 +273,23 @@ __global__ void __launch_bounds__(256) update_mark_occ_dense_kernel(const Update
   if (valid && (lane == 0 || c_prev != c)) {  // of a run of adjacent lanes with the same end cell the first = lowest beam index
     atomicMax(&P.lv.key_occ[c], (P.serial << kBeamBits) | (kBeamMask - (unsigned int)beam));
     P.lv.free_bytes[kc] = kMarkEnd;
-#if HSM_MARK_TILE_END
     P.lv.free_bytes[mark_tile_end_offset(P.lv.sx, P.lv.sy) + (kc >> 7)] = 1;
-#endif
   }
 }
 
-// pass 1b: line cells (after 1a has completed).  WHICH beam crossed a cell first only matters
-// where some beam also ENDS (the free-then-occupied revert, OccGridMapBase.h:231-233); everywhere
-// else "some beam of this scan crossed it" is all the apply pass needs.  So a cell that is nobody's
-// end cell gets a plain store of the bare serial tag (all writers store the same word: a benign
-// race, and stores do not serialise in L2 the way same-address atomics do next to the sensor),
-// and only end cells -- a few thousand per scan -- take the atomicMax that keeps the lowest beam
-// index.  A cell is classified by the end-cell bitmap, which pass 1a finalised, so the two kinds of
-// access never mix on one word.
-//
-// KEYED = true (scans below 4096 beams, where the whole update is launch-latency bound): every crossed cell takes the
-// atomicMax of the full key, end cell or not, so the pass does not read the end-cell bitmap and no longer depends on
-// pass 1a -- both run in ONE launch (update_mark_kernel) and the update is one dependent launch shorter.  The apply
-// pass reads the same information either way (the serial tag; the beam index only where a beam ends).
-template <bool KEYED>
+// pass 1b: line cells.  WHICH beam crossed a cell first only matters where some beam also ENDS (the
+// free-then-occupied revert, OccGridMapBase.h:231-233); everywhere else "some beam of this scan crossed
+// it" is all the apply pass needs (the serial tag; the beam index only where a beam ends).  This walk
+// serves the scans below 4096 beams, where the whole update is launch-latency bound: every crossed cell
+// takes the atomicMax of the full key, end cell or not, so the pass does not read the end-cell bitmap and
+// does not depend on pass 1a -- both run in ONE launch (update_mark_kernel).
 __device__ __forceinline__ void mark_free_block(const UpdateParams& P, unsigned int block) {
   const int lane = threadIdx.x & 63;
   const int beam = block * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (beam >= P.n) return;
   const BeamLine b = beam_line(P, beam);
   if (!b.valid) return;
-  const unsigned int tag = P.serial << kBeamBits;
-  const unsigned int key = tag | (kBeamMask - (unsigned int)beam);
+  const unsigned int key = (P.serial << kBeamBits) | (kBeamMask - (unsigned int)beam);
   if ((unsigned int)lane >= b.abs_da) return;
   // Lane k visits steps k, k+64, ...: instead of one integer division per step (line_cell), carry the
   // quotient/remainder of (e0 + i*db) / da forward by the per-64-step increment -- two divisions per lane.
@@ -364,11 +318,7 @@ __device__ __forceinline__ void mark_free_block(const UpdateParams& P, unsigned 
       const int sa = b.offset_a > 0 ? (int)i : -(int)i, sb = b.offset_b > 0 ? (int)q : -(int)q;
       const unsigned int cx = (unsigned int)(P.bx + (x_major ? sa : sb)), cy = (unsigned int)(P.by + (x_major ? sb : sa));
       const unsigned int kc = key_free_index(P.lv, cx, cy);
-      if (KEYED || ((P.lv.occ_bits[c >> 5] >> (c & 31u)) & 1u)) {  // (the bitmap is 32x denser than the key plane: stays in L2)
-        atomicMax(&P.lv.key_free[kc], key);
-      } else {
-        P.lv.key_free[kc] = tag;
-      }
+      atomicMax(&P.lv.key_free[kc], key);
     }
     base += step_a;
     q += q64;
@@ -386,12 +336,6 @@ __device__ __forceinline__ void mark_free_block(const UpdateParams& P, unsigned 
   }
 }
 
-#if defined(HSM_EXPERIMENTS)
-__global__ void __launch_bounds__(256) update_mark_free_kernel(const UpdateBatch B) {
-  mark_free_block<false>(B.lv[blockIdx.y], blockIdx.x);
-}
-#endif
-
 // passes 1a + 1b of a SMALL scan in one launch: the first occ_blocks workgroups of a row mark the end cells, the rest
 // walk the lines with keyed atomics (no dependency between the two, see mark_free_block)
 __global__ void __launch_bounds__(256) update_mark_kernel(const UpdateBatch B, unsigned int occ_blocks) {
@@ -399,12 +343,12 @@ __global__ void __launch_bounds__(256) update_mark_kernel(const UpdateBatch B, u
   if (blockIdx.x < occ_blocks)
     mark_occ_block(P, blockIdx.x);
   else
-    mark_free_block<true>(P, blockIdx.x - occ_blocks);
+    mark_free_block(P, blockIdx.x - occ_blocks);
 }
 
 // dense over the box [x0..x1] x [y0..y1]: bresenhamCellFree / bresenhamCellOcc (OccGridMapBase.h:216-241)
 //
-// "A beam of THIS scan ends here" is the cell's bit in the end-cell bitmap (set by update_mark_occ_kernel,
+// "A beam of THIS scan ends here" is the cell's bit in the end-cell bitmap (set by mark_occ_block,
 // cleared here), so the occ-key plane is only read where the bit is set -- end cells are walls, and most of that
 // plane's cache lines are never touched by this pass.  The bitmap word is cleared by the lane of its first cell;
 // that is only safe when every reader of a word sits in the SAME wavefront (reads program-ordered before the
@@ -498,9 +442,9 @@ __global__ void __launch_bounds__(256) update_apply_kernel(const UpdateBatch B) 
 //     atomicOr per tile and lane -- lane k walking 8 consecutive steps -- was built first: 354 us against 110, every lane's
 //     accesses land in a different line.  The end-cell flag first lived in the row-major bitmap of the keyed path: up to 64
 //     lines per access for a y-major beam, and four more words per lane in the apply pass.)
-//   update_apply_dense_kernel: one wavefront per 64 x 4-cell block of the box (8 tiles = 256 contiguous bytes of the byte
+//   update_apply_dense_kernel: one wavefront per 32 x 8-cell block of the box (2 tiles = 256 contiguous bytes of the byte
 //     map).  It reads the block's bytes, skips the block when all are zero, applies the reference's rule to the marked
-//     cells row by row (coalesced 256-byte rows), and clears what it read -- the block has ONE owner, so there is no race
+//     cells row by row (coalesced 128-byte row segments), and clears what it read -- the block has ONE owner, so there is no race
 //     on the marks, and the byte map is all zero again between updates (no generation tag to wrap).  Untouched cells cost
 //     1 byte instead of 4 bytes + 1 bit.
 // Same cells, same rule, same order-dependent artefacts: the maps stay bit-identical to the reference.
@@ -540,8 +484,8 @@ __host__ __device__ __forceinline__ int mark_dense_blocks(int n) {  // workgroup
 
 // Tried in round 4 and dropped (profiles/r04/update_variants_kernel_us.txt, maps bit-identical in every variant): G = 2 / 4
 // beams side by side in one wavefront, 64 / G lanes each (the set-up amortised over G beams): 76.8 / 120 us against 72.1 --
-// the beams of a group differ in length and octant, so lanes idle and the loop diverges; without the duplicate suppression
-// (HSM_MARK_DEDUP=0): 104 us -- the per-step load only sees marks that have reached this XCD's L2, the predecessor test
+// the beams of a group differ in length and octant, so lanes idle and the loop diverges; without the duplicate suppression:
+// 104 us -- the per-step load only sees marks that have reached this XCD's L2, the predecessor test
 // needs no memory at all.
 __global__ void __launch_bounds__(256) update_mark_free_dense_kernel(const UpdateBatch B) {
   const UpdateParams& P = B.lv[blockIdx.y];
@@ -570,10 +514,7 @@ __global__ void __launch_bounds__(256) update_mark_free_dense_kernel(const Updat
   unsigned int q = small ? div_small(num0, da) : num0 / da;
   unsigned int r = num0 - q * da;
   // duplicate suppression against the previous beam (mark_free_block): valid, same octant
-#ifndef HSM_MARK_DEDUP
-#define HSM_MARK_DEDUP 1
-#endif
-  const bool dedup = HSM_MARK_DEDUP && rp.x != 0u && (rp.w & 7u) == oct;
+  const bool dedup = rp.x != 0u && (rp.w & 7u) == oct;
   const unsigned int pda = dedup ? rp.x : 0u;  // no step is "also the previous beam's" without dedup
   const unsigned int pden = dedup ? rp.x : 1u, pdb = rp.y;
   const unsigned int pnum0 = (pden >> 1) + (unsigned int)lane * pdb;
@@ -592,24 +533,14 @@ __global__ void __launch_bounds__(256) update_mark_free_dense_kernel(const Updat
   typedef __attribute__((address_space(1))) unsigned int gword;
   gbyte* const marks = (gbyte*)pinned_sgpr(P.lv.free_bytes);
   gword* const keys = (gword*)pinned_sgpr(P.lv.key_free);
-#if HSM_MARK_TILE16
   const unsigned int mtiles_x = pinned_sgpr((unsigned int)mark_tiles_x(P.lv.sx));
-#endif
   auto key_index = [&]() -> unsigned int {  // of the current cell, in the free-key plane
-#if HSM_KEYFREE_TILE
     return ((__umul24((unsigned int)cy >> 2, tiles_x) + ((unsigned int)cx >> 3)) << 5) | (((unsigned int)cy & 3u) << 3) |
            ((unsigned int)cx & 7u);  // == key_free_index(P.lv, cx, cy): rows of tiles and tiles per row are below 2^24
-#else
-    return key_free_index(P.lv, (unsigned int)cx, (unsigned int)cy);
-#endif
   };
   auto cell_index = [&]() -> unsigned int {  // of the current cell, in the mark-byte plane
-#if HSM_MARK_TILE16
     return ((__umul24((unsigned int)cy >> 3, mtiles_x) + ((unsigned int)cx >> 4)) << 7) | (((unsigned int)cy & 7u) << 4) |
            ((unsigned int)cx & 15u);  // == mark_index(P.lv, cx, cy)
-#else
-    return key_index();
-#endif
   };
   auto advance = [&]() {  // 64 steps on: the carries of both error accumulators
     q += q64;
@@ -636,203 +567,33 @@ __global__ void __launch_bounds__(256) update_mark_free_dense_kernel(const Updat
       marks[kc] = kMarkCrossed;
     }
   };
-#ifndef HSM_MARK_UNROLL  // 2: two steps (i, i + 64) per iteration with both byte loads in flight before either is acted on
-#define HSM_MARK_UNROLL 1
-#endif
-#if HSM_MARK_UNROLL == 2
-  for (unsigned int i = lane; i < da; i += 128) {
-    const bool need_a = !(i < pda && pq == q);
-    const unsigned int kc_a = cell_index(), kk_a = key_index();
-    advance();
-    const bool need_b = i + 64 < da && !(i + 64 < pda && pq == q);
-    const unsigned int kc_b = cell_index(), kk_b = key_index();
-    advance();
-    unsigned char m_a = kMarkCrossed, m_b = kMarkCrossed;  // "already marked": nothing to do
-    if (need_a) m_a = marks[kc_a];
-    if (need_b) m_b = marks[kc_b];
-    touch(kc_a, m_a, kk_a);
-    touch(kc_b, m_b, kk_b);
-  }
-#else
-#if HSM_MARK_TILE_END
+  // (two steps per iteration with both byte loads in flight before either is acted on: no gain, see above)
   const gbyte* const tile_end = (const gbyte*)pinned_sgpr(P.lv.free_bytes + mark_tile_end_offset(P.lv.sx, P.lv.sy));
-#endif
-#if defined(HSM_EXPERIMENTS) && defined(HSM_WHATIF_WALK)
-  // TIMING EXPERIMENTS ONLY (wrong maps): what a binned LDS tile rasteriser could gain on the walk (round-4 verdict, item 3).
-  //   1: no memory operation at all -- the walk's arithmetic alone;  2: the marks go to LDS bytes (ds_write_b8) instead of HBM
-  __shared__ unsigned char lds_marks[16384];
-  unsigned int sink = 0u;
-  for (unsigned int i = lane; i < da; i += 64) {
-    if (!(i < pda && pq == q)) {
-      const unsigned int kc = cell_index();
-      if (HSM_WHATIF_WALK == 2) lds_marks[kc & 16383u] = kMarkCrossed; else sink ^= kc;
-    }
-    advance();
-  }
-  if (sink == 0x9e3779b9u || (HSM_WHATIF_WALK == 2 && lds_marks[lane] == 77)) marks[0] = 1;  // (keeps the loop alive)
-  return;
-#endif
   for (unsigned int i = lane; i < da; i += 64) {  // abs_da free cells: steps 0 .. abs_da-1
     if (!(i < pda && pq == q)) {
       const unsigned int kc = cell_index();
-#if HSM_MARK_TILE_END
       if (tile_end[kc >> 7] == 0) {
         marks[kc] = kMarkCrossed;  // no beam ends in this tile: nothing to look at (an already set mark is stored again)
       } else {
+        // one byte load from the line the store goes to (the row-major end-cell bitmap cost a y-major beam 64 lines per access)
         touch(kc, marks[kc], key_index());
       }
-#else
-      // one byte load from the line the store goes to (the row-major end-cell bitmap cost a y-major beam 64 lines per access)
-      touch(kc, marks[kc], HSM_MARK_TILE16 ? key_index() : kc);
-#endif
     }
     advance();
   }
-#endif
 }
 
-// requires HSM_KEYFREE_TILE (the host checks): the box is widened to 64-column / 4-row boundaries; any map width (the tile
-// rows are padded to whole blocks, key_free_tiles_x)
-#ifndef HSM_APPLY_NT  // 1: the dense apply pass writes its three planes with non-temporal stores -- 12 bytes per touched cell that
-                      // nothing reads again before the next update; kept out of the L2 they leave it to the marks and the log-odds
-                      // rows (update 0.198 -> 0.178 ms on configs[4]; non-temporal LOADS of the rows or stores of the cleared marks
-                      // lose: 0.205 ms)
-#define HSM_APPLY_NT 1
-#endif
-#ifndef HSM_APPLY_BLOCKS  // 64 x 4-cell blocks a wavefront of the dense apply pass has in flight
-#define HSM_APPLY_BLOCKS 1
-#endif
-#if !HSM_MARK_TILE16
-template <bool SCATTER_TEXELS>
-__global__ void __launch_bounds__(256) update_apply_dense_kernel(const UpdateBatch B) {
-  const UpdateParams& P = B.lv[blockIdx.y];
-  if (P.x1 < P.x0) return;  // this level has nothing to apply
-  const int lane = threadIdx.x & 63;
-  const int bx0 = P.x0 & ~63, by0 = P.y0 & ~3;
-  const int nbx = ((P.x1 | 63) - bx0 + 1) >> 6, nby = (((P.y1 | 3) - by0) >> 2) + 1;
-  const int nblocks = nbx * nby;
-  const int waves = (int)((gridDim.x * blockDim.x) >> 6);
-  const int sx = P.lv.sx, sy = P.lv.sy;
-  // A wavefront's blocks are a chain of memory round trips (marks -> log-odds rows -> stores), a dozen blocks long, and the
-  // pass was waiting for them 84 % of the time (profiles/r03/README.md).  So the marks of the NEXT block are requested
-  // before this one is processed, and the rows of a block are all requested before the first is computed.
-  // the block's 256 mark bytes: lane l reads ONE dword of them (tile l / 8, row (l % 8) / 2, half l % 2)
-  auto marks_of = [&](int blk) -> unsigned int* {
-    const int X0 = bx0 + ((blk % nbx) << 6), Y0 = by0 + ((blk / nbx) << 2);
-    const unsigned int tile0 = (((unsigned int)(Y0 >> 2) * (unsigned int)P.lv.kf_tiles_x) + (unsigned int)(X0 >> 3)) << 5;  // byte index
-    return reinterpret_cast<unsigned int*>(P.lv.free_bytes + tile0) + lane;
-  };
-  // kApplyBlocks blocks per iteration: their rows are all in flight together (Little's law: 32 wavefronts per CU with
-  // four 256-byte rows each in flight sustain ~4 TB/s at this latency, which is what the one-block form measured)
-  constexpr int NBLK = HSM_APPLY_BLOCKS;
-  int blk = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6) * NBLK;
-  if (blk >= nblocks) return;
-  unsigned int fw_next[NBLK];
-#pragma unroll
-  for (int j = 0; j < NBLK; ++j) fw_next[j] = blk + j < nblocks ? *marks_of(blk + j) : 0u;
-  for (; blk < nblocks; blk += waves * NBLK) {
-    unsigned int fw[NBLK];
-    bool live[NBLK];
-#pragma unroll
-    for (int j = 0; j < NBLK; ++j) fw[j] = fw_next[j];
-#pragma unroll
-    for (int j = 0; j < NBLK; ++j) fw_next[j] = blk + waves * NBLK + j < nblocks ? *marks_of(blk + waves * NBLK + j) : 0u;
-    bool fre[NBLK][4], occ[NBLK][4];
-    float l[NBLK][4];
-    unsigned int ko[NBLK][4], kf[NBLK][4];
-    // phase 1: classify the four cells of this lane's column in every block and request what their update needs
-#pragma unroll
-    for (int j = 0; j < NBLK; ++j) {
-      live[j] = blk + j < nblocks && __ballot(fw[j] != 0u) != 0ull;  // wave-uniform: something of this scan in the block
-      if (!live[j]) continue;
-      const int X0 = bx0 + (((blk + j) % nbx) << 6), Y0 = by0 + (((blk + j) / nbx) << 2);
-      const int x = X0 + lane;
-      if (fw[j] != 0u) *marks_of(blk + j) = 0u;
-#pragma unroll
-      for (int dy = 0; dy < 4; ++dy) {
-        const int y = Y0 + dy;
-        const size_t c = (size_t)y * sx + x;
-        // the byte of cell (x, Y0 + dy): tile lane / 8, byte dy * 8 + lane % 8 = dword (lane & ~7) + 2 dy + (lane & 7) / 4, byte lane & 3
-        const unsigned int fwd = (unsigned int)__shfl((int)fw[j], (lane & ~7) + 2 * dy + ((lane & 7) >> 2));
-        const unsigned int mark = (fwd >> ((lane & 3) << 3)) & 0xffu;
-        occ[j][dy] = (mark & kMarkEnd) != 0u && y < sy && x < sx;  // (the widened box may reach past the map's last row / column:
-        fre[j][dy] = (mark & kMarkCrossed) != 0u && y < sy && x < sx;  //  no mark can sit there, cheap to insist)
-        l[j][dy] = 0.0f;
-        ko[j][dy] = kf[j][dy] = 0u;
-        if (fre[j][dy] || occ[j][dy]) l[j][dy] = P.lv.logodds[c];
-        if (occ[j][dy]) {
-          ko[j][dy] = P.lv.key_occ[c];
-          kf[j][dy] = P.lv.key_free[key_free_index(P.lv, (unsigned int)x, (unsigned int)y)];
-        }
-      }
-    }
-    // phase 2: the reference's rule, row by row (coalesced 256-byte rows)
-#pragma unroll
-    for (int j = 0; j < NBLK; ++j) {
-      if (!live[j]) continue;
-      const int X0 = bx0 + (((blk + j) % nbx) << 6), Y0 = by0 + (((blk + j) / nbx) << 2);
-      const int x = X0 + lane;
-#pragma unroll
-      for (int dy = 0; dy < 4; ++dy) {
-        const int y = Y0 + dy;
-        const size_t c = (size_t)y * sx + x;
-        bool is_occ = occ[j][dy], is_fre = fre[j][dy];
-        if (is_occ) {
-          is_occ = (ko[j][dy] >> kBeamBits) == P.serial;  // (a flag without this scan's key cannot occur; cheap to insist)
-          is_fre = (kf[j][dy] >> kBeamBits) == P.serial;
-        }
-        if (!is_fre && !is_occ) continue;
-        float lo = l[j][dy];
-        int stamp;
-        if (is_occ) {
-          // free-touched by an earlier beam of this scan: applied, then reverted (OccGridMapBase.h:231-233)
-          if (is_fre && (kBeamMask - (kf[j][dy] & kBeamMask)) < (kBeamMask - (ko[j][dy] & kBeamMask))) {
-            lo += P.log_odds_free;
-            lo -= P.log_odds_free;
-          }
-          if (lo < 50.0f) lo += P.log_odds_occ;  // updateSetOccupied
-          stamp = P.mark_occ;
-        } else {
-          lo += P.log_odds_free;                 // updateSetFree
-          stamp = P.mark_free;
-        }
-#if HSM_APPLY_NT
-        __builtin_nontemporal_store(lo, &P.lv.logodds[c]);
-        __builtin_nontemporal_store(stamp, &P.lv.update_index[c]);
-        const float p = grid_probability(lo);
-        __builtin_nontemporal_store(p, &P.lv.prob[c]);
-#else
-        P.lv.logodds[c] = lo;
-        P.lv.update_index[c] = stamp;
-        const float p = grid_probability(lo);
-        P.lv.prob[c] = p;
-#endif
-        if (SCATTER_TEXELS) {
-          float* q = reinterpret_cast<float*>(P.lv.quad);
-          const bool lastx = x == sx - 1, lasty = y == sy - 1;
-          auto put = [&](int tx, int ty, int comp) { q[4 * (size_t)quad_index(tx, ty, P.lv.tiles_x, sx) + comp] = p; };
-          put(x, y, 0);
-          if (x > 0) put(x - 1, y, 1);
-          if (lastx) put(x, y, 1);
-          if (y > 0) put(x, y - 1, 2);
-          if (lasty) put(x, y, 2);
-          if (x > 0 && y > 0) put(x - 1, y - 1, 3);
-          if (lastx && y > 0) put(x, y - 1, 3);
-          if (lasty && x > 0) put(x - 1, y, 3);
-          if (lastx && lasty) put(x, y, 3);
-        }
-      }
-    }
-  }
-}
-
-#endif  // !HSM_MARK_TILE16
-
-#if HSM_MARK_TILE16
-// HSM_MARK_TILE16: the dense apply pass on 32 x 8-cell blocks (two 16 x 8 mark tiles = 256 contiguous mark bytes, one dword
-// per lane).  Lane l works on column l % 32 of the block and on rows 2 i + l / 32 (i = 0 .. 3): every access of the log-odds /
-// stamp / probability planes is two 128-byte row segments per wavefront.  Otherwise update_apply_dense_kernel's block: skip
-// when no mark is set, the reference's rule on the marked cells, marks cleared; the next block's marks are requested first.
+// The dense apply pass: one wavefront per 32 x 8-cell block of the box (two 16 x 8 mark tiles = 256 contiguous mark bytes, one
+// dword per lane); the box is widened to block boundaries, any map width (the tile rows are padded to whole blocks).  A
+// wavefront's blocks are a chain of memory round trips (marks -> log-odds rows -> stores), a dozen blocks long, and the pass was
+// waiting for them 84 % of the time (profiles/r03/README.md).  So the marks of the NEXT block are requested before this one is
+// processed, and the rows of a block are all requested before the first is computed.
+// Lane l works on column l % 32 of the block and on rows 2 i + l / 32 (i = 0 .. 3): every access of the log-odds /
+// stamp / probability planes is two 128-byte row segments per wavefront.  A block is skipped when no mark is set; else the
+// reference's rule on the marked cells, marks cleared.  The three planes are written with non-temporal stores -- 12 bytes per
+// touched cell that nothing reads again before the next update; kept out of the L2 they leave it to the marks and the log-odds
+// rows (update 0.198 -> 0.178 ms on configs[4]; non-temporal LOADS of the rows or stores of the cleared marks lose: 0.205 ms).
+// (Measured against 64 x 4-cell blocks on the 8 x 4 tiling: profiles/r04/README.md 20.)
 template <bool SCATTER_TEXELS>
 __global__ void __launch_bounds__(256) update_apply_dense_kernel(const UpdateBatch B) {
   const UpdateParams& P = B.lv[blockIdx.y];
@@ -860,12 +621,10 @@ __global__ void __launch_bounds__(256) update_apply_dense_kernel(const UpdateBat
     const int X0 = bx0 + ((blk % nbx) << 5), Y0 = by0 + ((blk / nbx) << 3);
     const int x = X0 + xl;
     if (fw != 0u) *marks_of(blk) = 0u;
-#if HSM_MARK_TILE_END
     if (lane < 2) {
       const unsigned int t0 = (((unsigned int)(Y0 >> 3) * mtx) + (unsigned int)(X0 >> 4));
       P.lv.free_bytes[mark_tile_end_offset(sx, sy) + t0 + lane] = 0;
     }
-#endif
     bool fre[4], occ[4];
     float l[4];
     unsigned int ko[4], kf[4];
@@ -930,7 +689,6 @@ __global__ void __launch_bounds__(256) update_apply_dense_kernel(const UpdateBat
     }
   }
 }
-#endif
 
 // dense over the box grown by one cell towards -x/-y: texel (x,y) holds P of (x..x+1, y..y+1)
 __global__ void __launch_bounds__(256) update_texels_kernel(const UpdateBatch B) {
@@ -1112,7 +870,7 @@ __global__ void __launch_bounds__(256) update_mark_scan_kernel(const UpdateBatch
     }
   } else {
     const unsigned int free_blocks = gridDim.x - occ_blocks, turns = ((unsigned int)P.n + 3u) / 4u;
-    for (unsigned int b = blockIdx.x - occ_blocks; b < turns; b += free_blocks) mark_free_block<true>(P, b);
+    for (unsigned int b = blockIdx.x - occ_blocks; b < turns; b += free_blocks) mark_free_block(P, b);
   }
 }
 

@@ -255,37 +255,6 @@ int launch_match_exact(hsm_ctx* h, const MatchParams& P_in, int max_n, hipStream
     }
     return launch_match_exact_cached_forms(h, P, max_n, stream);
   }
-#if defined(HSM_EXPERIMENTS)
-  // round 2's exact batch form: producer wavefronts + chain wavefronts per workgroup (gn_match.h), env HSM_EXACT_CACHED=0.
-  // Measured (profiles/r02/README.md): 108 vs 122 us on the 2048^2 headline batch with the <7,1> shape, 92-97 us with <8,2>
-  // and two gathers in flight.  Not in the default library since round 4 (the texel-cache form above serves every quad
-  // batch; the plane layout takes the one-wavefront exact form below).
-  if (WPS == 1 && P.begin_world && !P.trace && h->exact_batch_form &&
-      (h->exact_batch_form == 2 || h->levels[0].cells() <= ((size_t)1 << 23))) {
-    const auto worst_cu = [&](int per_wg) { return ((P.batch + per_wg - 1) / per_wg + 255) / 256 * per_wg; };
-    int per_wg = worst_cu(8) < worst_cu(kExactScans) ? 8 : kExactScans;
-    if (h->exact_shape == 7 || h->exact_shape == 8) per_wg = h->exact_shape;
-    const int grid = (P.batch + per_wg - 1) / per_wg, block = per_wg == 8 ? 64 * 10 : 64 * (kExactScans + 1);
-    if (per_wg == 8) {
-      if (h->layout == kLayoutPlane)
-        hipLaunchKernelGGL((gn_match_exact_batch_kernel<kLayoutPlane, 8, 2>), dim3(grid), dim3(block), 0, stream, P);
-      else
-        hipLaunchKernelGGL((gn_match_exact_batch_kernel<kLayoutQuad, 8, 2>), dim3(grid), dim3(block), 0, stream, P);
-    } else if (h->layout == kLayoutPlane) {
-      hipLaunchKernelGGL((gn_match_exact_batch_kernel<kLayoutPlane>), dim3(grid), dim3(block), 0, stream, P);
-    } else {
-      hipLaunchKernelGGL((gn_match_exact_batch_kernel<kLayoutQuad>), dim3(grid), dim3(block), 0, stream, P);
-    }
-    HIP_TRY(hipGetLastError());
-    h->last_cfg[0] = h->layout;
-    h->last_cfg[1] = 1;
-    h->last_cfg[2] = block;
-    h->last_cfg[3] = grid;
-    h->last_cfg[4] = 0;
-    h->last_cfg[5] = 0;
-    return HSM_OK;
-  }
-#endif
   const int block = 64 * WPS * SPB;
   const int grid = (P.batch + SPB - 1) / SPB;
   if (h->layout == kLayoutPlane)
@@ -332,26 +301,7 @@ int launch_match_by_width(hsm_ctx* h, const MatchParams& P, int max_n, hipStream
         return per_lane <= 9 ? launch_match_t<1, 8, 9>(h, P, stream) : launch_match_t<1, 8, 17>(h, P, stream);
       return launch_match_w<1, 4>(h, P, max_n, stream, exact);
     }
-    case 2: {
-#if defined(HSM_EXPERIMENTS)
-      // experimental (HSM_CACHED_WPS2=1, explicit waves_per_scan = 2): the texel-cache form on a PAIR of waves per scan
-      // -- nine beams per lane, five waves per SIMD, 1.6 generations of waves for a 4096-scan launch (gn_match.h)
-      const int per_lane = (max_n + 127) / 128;
-      if (h->cached_wps2 && !exact && h->texel_cache && P.begin_world && !P.trace && h->bpl_override != 0 &&
-          h->layout == kLayoutQuad && per_lane > 0 && per_lane <= 9) {
-        hipLaunchKernelGGL((gn_match_cached_kernel<1, 9, kLayoutQuad, 2>), dim3(P.batch), dim3(128), 0, stream, P);
-        HIP_TRY(hipGetLastError());
-        h->last_cfg[0] = h->layout;
-        h->last_cfg[1] = 2;
-        h->last_cfg[2] = 128;
-        h->last_cfg[3] = P.batch;
-        h->last_cfg[4] = 9;
-        h->last_cfg[5] = 1;
-        return HSM_OK;
-      }
-#endif
-      return launch_match_w<2, 1>(h, P, max_n, stream, exact);
-    }
+    case 2: return launch_match_w<2, 1>(h, P, max_n, stream, exact);
     case 4: return launch_match_w<4, 1>(h, P, max_n, stream, exact);
     case 8: return launch_match_w<8, 1>(h, P, max_n, stream, exact);
     default: return launch_match_w<16, 1>(h, P, max_n, stream, exact);

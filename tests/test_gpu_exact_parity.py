@@ -131,8 +131,8 @@ def test_batch_ragged_bit_identical(capi, oracle_mod, pyramid_scene, kind, form,
     a small batch picks by itself ("auto"), the texel-cache exact form every quad-layout batch takes (gn_match_exact.h: every
     wavefront a producer, packed rotating chain jobs; 17 scans = two full workgroups and a partial one; "cached-tail" /
     "cached-long": scans four / nine rows longer than the 17 cached ones stream their tail rows), the plane layout (which has
-    no texel-cache exact form) and the one-wavefront-per-scan form (HSM_EXACT_CACHED=0).  Round 2's producer / chain-wavefront
-    form left the default library in round 4 (-DHSM_EXPERIMENTS).  Since round 5 a launch of at most 3072 scans -- this one --
+    no texel-cache exact form) and the one-wavefront-per-scan form (HSM_EXACT_CACHED=0).  (Round 2's producer / chain-wavefront
+    form is no longer in the sources: profiles/r02, profiles/r03.)  Since round 5 a launch of at most 3072 scans -- this one --
     takes the texel-cache form WITH a chain-only fifth wavefront per workgroup (block 320); ".../rotating-owner" switches it
     off (HSM_EXACT_CHAIN_WAVE=0): the form larger launches take, whose producers run the chain jobs in turn (block 256)"""
     from hector_slam_amd import synth
