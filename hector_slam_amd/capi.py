@@ -70,6 +70,11 @@ SIGNATURES = {
     "hsm_update_by_scan_level": (_i, [_vp, _i, _f32p, _vp, _i, _f32p]),
     "hsm_update_by_scans_device": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "hsm_update_by_scans": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp]),
+    "hsm_set_update_gate": (_i, [_vp, _f, _f]),
+    "hsm_reset_update_gate": (_i, [_vp]),
+    "hsm_update_gate_state": (_i, [_vp, _f32p, C.POINTER(C.c_longlong)]),
+    "hsm_update_by_scans_device_gated": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "hsm_slam_scans_device": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "hsm_ingest_laser_scan": (_i, [_vp, _vp, _i, _f, _f, _f, _f, _f, _vp, C.POINTER(_i)]),
     "hsm_ingest_point_cloud": (_i, [_vp, _vp, _i, _vp, _f, _f, _f, _f, _f, _vp, C.POINTER(_i), _vp]),
     "hsm_ingest_laser_scan_tf": (_i, [_vp, _vp, _i, _f, _f, _f, _f, C.c_double, _vp, _f, _f, _f, _f, _f, _vp,
@@ -570,6 +575,40 @@ class MapRepMultiMap:
                                                     shared_n, max_beams, None if o is None else o.ctypes.data, stream or None),
                "hsm_update_by_scans_device")
 
+    def set_update_gate(self, min_dist, min_angle):
+        """thresholds of the device-side movement gate (HectorSlamProcessor.h:62-63: 0.4 / 0.13)"""
+        _check(self._lib.hsm_set_update_gate(self._h, float(min_dist), float(min_angle)), "hsm_set_update_gate")
+
+    def reset_update_gate(self):
+        _check(self._lib.hsm_reset_update_gate(self._h), "hsm_reset_update_gate")
+
+    def update_gate_state(self):
+        """(lastMapUpdatePose [3], updates applied by gated calls since creation); waits for the queued work"""
+        pose, total = np.empty(3, np.float32), C.c_longlong(0)
+        _check(self._lib.hsm_update_gate_state(self._h, pose, C.byref(total)), "hsm_update_gate_state")
+        return pose, int(total.value)
+
+    def update_by_scans_device_gated(self, count, d_poses_world, d_pts, d_offsets, shared_n, max_beams=0, origo=None, d_force=0,
+                                     d_out_applied=0, stream=0):
+        """``update_by_scans_device`` behind the movement gate of HectorSlamProcessor::update: scan k is integrated where pose k
+        differs enough from the last integrated pose, or ``d_force[k]`` (device bytes) is set; ``d_out_applied`` (device int32
+        [count]) receives the decisions.  The host waits for nothing."""
+        o = None if origo is None else _v(origo, 2)
+        _check(self._lib.hsm_update_by_scans_device_gated(self._h, count, d_poses_world or None, d_pts or None, d_offsets or None,
+                                                          shared_n, max_beams, None if o is None else o.ctypes.data,
+                                                          d_force or None, d_out_applied or None, stream or None),
+               "hsm_update_by_scans_device_gated")
+
+    def slam_scans_device(self, count, d_start_pose, d_hint_deltas, d_pts, d_offsets, max_beams, origo, d_force, d_out_pose,
+                          d_out_cov=0, d_out_applied=0, stream=0):
+        """Raw device pointers (ints): HectorSlamProcessor::update for ``count`` scans in order -- match, gate, update -- queued
+        in one call; scan k's hint is scan k-1's pose (+ ``d_hint_deltas[k]``)."""
+        o = None if origo is None else _v(origo, 2)
+        _check(self._lib.hsm_slam_scans_device(self._h, count, d_start_pose or None, d_hint_deltas or None, d_pts or None,
+                                               d_offsets or None, max_beams, None if o is None else o.ctypes.data, d_force or None,
+                                               d_out_pose or None, d_out_cov or None, d_out_applied or None, stream or None),
+               "hsm_slam_scans_device")
+
     def update_by_scans(self, poses_world, pts, offsets=None, origo=None):
         """Host arrays: a map from a log of posed scans in one call.  ``offsets`` None = every pose integrates the one scan ``pts``."""
         w = np.ascontiguousarray(poses_world, np.float32).reshape(-1, 3)
@@ -950,10 +989,25 @@ class HectorSlamProcessor:
         fmax = np.finfo(np.float32).max
         self.lastMapUpdatePose = np.array([fmax, fmax, fmax], np.float32)
         self.lastScanMatchPose = np.zeros(3, np.float32)
-        self.mapRep.reset()
+        self.mapRep.reset()  # (hsm_reset: the device-side gate goes back to FLT_MAX with it)
+        self.mapRep.reset_update_gate()
 
     def setMapUpdateMinDistDiff(self, v): self.paramMinDistanceDiffForMapUpdate = np.float32(v)
     def setMapUpdateMinAngleDiff(self, v): self.paramMinAngleDiffForMapUpdate = np.float32(v)
+
+    def update_scans_device(self, count, d_start_pose, d_hint_deltas, d_pts, d_offsets, d_out_pose, d_out_cov=0,
+                            d_out_applied=0, d_force=0, max_beams=0, origo=None, stream=0):
+        """``update()`` for a log of ``count`` scans that are on the device (raw pointers as ints), queued in one call with
+        this processor's thresholds: nothing is waited for and nothing comes back to the host -- lastScanMatchPose /
+        lastMapUpdatePose of the device-side loop are read with ``device_state()``.  The host-side ``update()`` keeps its own
+        lastMapUpdatePose: drive one processor through one of the two."""
+        self.mapRep.set_update_gate(self.paramMinDistanceDiffForMapUpdate, self.paramMinAngleDiffForMapUpdate)
+        self.mapRep.slam_scans_device(count, d_start_pose, d_hint_deltas, d_pts, d_offsets, max_beams, origo, d_force,
+                                      d_out_pose, d_out_cov, d_out_applied, stream)
+
+    def device_state(self):
+        """(lastMapUpdatePose, updates applied) of the device-side loop; waits for it"""
+        return self.mapRep.update_gate_state()
     def setUpdateFactorFree(self, v): self.mapRep.setUpdateFactorFree(v)
     def setUpdateFactorOccupied(self, v): self.mapRep.setUpdateFactorOccupied(v)
     def getLastScanMatchPose(self): return self.lastScanMatchPose

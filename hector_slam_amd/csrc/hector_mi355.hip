@@ -727,6 +727,39 @@ int clear_key_planes(hsm_ctx* h, Level& L) {
   return HSM_OK;
 }
 
+// Gated updates (hsm_update_by_scans_device_gated, hsm_slam_scans_device) count the scans they integrate on the device: the
+// host never sees their decisions.  Whoever needs the levels' update counters on the host -- prepare_level, the ungated
+// hsm_update_by_scans_device, hsm_update_index, reset and upload -- first waits for the context's stream, fetches the count and
+// folds it in: OccGridMapBase.h:123-124, :167 and setUpdated() (GridMapBase.h:343) that many times.  Callers test
+// gate_outstanding themselves, so a context that never made a gated call pays one branch.  *state: the block as fetched.
+int fold_gate_counters(hsm_ctx* h, GateState* state = nullptr) {
+  if (int rc = select_device(h)) return rc;
+  GateState host;
+  HIP_TRY(hipMemcpyAsync(&host, h->d_gate, sizeof host, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (state) *state = host;
+  const int applied = host.pending;
+  if (applied > 0) {
+    HIP_TRY(hipMemsetAsync(&h->d_gate->pending, 0, sizeof(int), h->stream));  // ahead of every later gated call
+    for (Level& L : h->levels) {
+      L.curr_mark_free = L.curr_update_index + 3 * (applied - 1) + 1;
+      L.curr_mark_occ = L.curr_update_index + 3 * (applied - 1) + 2;
+      L.curr_update_index += 3 * applied;
+      L.last_update_index += applied;
+    }
+    h->gate_applied_total += applied;
+    if (state) state->pending = 0;
+  }
+  h->gate_outstanding = false;
+  return HSM_OK;
+}
+
+int reset_update_gate(hsm_ctx* h) {
+  hipLaunchKernelGGL(update_gate_reset_kernel, dim3(1), dim3(64), 0, h->stream, h->d_gate);
+  HIP_TRY(hipGetLastError());
+  return HSM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -843,6 +876,10 @@ int hsm_create(float map_resolution, int size_x, int size_y, unsigned levels, fl
   CREATE_TRY(hipHostMalloc((void**)&h->h_small, kSmallFloats * sizeof(float),
                            hipHostMallocMapped | hipHostMallocCoherent));
   memset(h->h_small, 0, kSmallFloats * sizeof(float));
+  CREATE_TRY(hipMalloc((void**)&h->d_gate, sizeof(GateState)));
+  CREATE_TRY(hipMemsetAsync(h->d_gate, 0, sizeof(GateState), h->stream));
+  hipLaunchKernelGGL(update_gate_reset_kernel, dim3(1), dim3(64), 0, h->stream, h->d_gate);
+  CREATE_TRY(hipGetLastError());
 
   // MapRepMultiMap ctor (MapRepMultiMap.h:48-72)
   int rx = size_x, ry = size_y;
@@ -910,8 +947,9 @@ void hsm_destroy(hsm_ctx* h) {
   TEARDOWN(log, hipFree(h->d_spec_stats));
   TEARDOWN(log, hipFree(h->d_small));
   TEARDOWN(log, hipFree(h->d_partials));
+  TEARDOWN(log, hipFree(h->d_gate));
   if (h->h_small) TEARDOWN(log, hipHostFree(h->h_small));
-  for (hipEvent_t e : {h->copy_evt, h->evt_updates, h->evt_foreign, h->evt_inputs, h->upd_evt[0], h->upd_evt[1]})
+  for (hipEvent_t e : {h->copy_evt, h->evt_updates, h->evt_foreign, h->evt_inputs, h->evt_slam_done, h->upd_evt[0], h->upd_evt[1]})
     if (e) TEARDOWN(log, hipEventDestroy(e));
   if (h->copy_stream) TEARDOWN(log, hipStreamDestroy(h->copy_stream));
   if (h->stream) TEARDOWN(log, hipStreamDestroy(h->stream));
@@ -928,7 +966,10 @@ int hsm_reset(hsm_ctx* h) {
   if (int rc = select_device(h)) return rc;
   if (h->upd_boxes_outstanding)
     if (int rc = merge_device_boxes(h)) return rc;
+  if (h->gate_outstanding)
+    if (int rc = fold_gate_counters(h)) return rc;
   if (int rc = order_after_foreign_match(h)) return rc;
+  if (int rc = reset_update_gate(h)) return rc;
   for (Level& L : h->levels) {
     if (int rc = fill_level(h, L)) return rc;
     L.dirty[0] = L.dirty[1] = 0;  // every cell changed: the whole level is dirty for host mirrors
@@ -1674,6 +1715,8 @@ static int update_impl(hsm_ctx* h, const float pose_world[3], const float* pts_x
   if (int rc = select_device(h)) return rc;
   if (h->upd_boxes_outstanding)  // this update rewrites Level::bbox: the boxes of device-side updates go in first
     if (int rc = merge_device_boxes(h)) return rc;
+  if (h->gate_outstanding)  // ... and numbers its update behind the ones gated calls applied
+    if (int rc = fold_gate_counters(h)) return rc;
   if (int rc = order_after_foreign_match(h)) return rc;
   const float zero[2] = {0.0f, 0.0f};
   const float* o = origo ? origo : zero;
@@ -1786,6 +1829,8 @@ int hsm_update_by_scan_level(hsm_ctx* h, int level, const float pose_world[3], c
   if (int rc = select_device(h)) return rc;
   if (h->upd_boxes_outstanding)
     if (int rc = merge_device_boxes(h)) return rc;
+  if (h->gate_outstanding)
+    if (int rc = fold_gate_counters(h)) return rc;
   if (int rc = order_after_foreign_match(h)) return rc;
   const float zero[2] = {0.0f, 0.0f};
   if (int rc = h->d_scan.reserve((size_t)n, kScanGrowth)) return rc;
@@ -1808,9 +1853,21 @@ int hsm_update_by_scan_level(hsm_ctx* h, int level, const float pose_world[3], c
 // `count` posed scans that are on the device, integrated in order by stream-ordered launches only: one update_prep_kernel, then
 // a mark and an apply launch per scan (map_update.h "posed scans that are already on the device").  The host supplies what it can
 // compute without the poses: per level the counters and the key generation before the call, from which scan k's follow.
+// `gate`: the gated entries.  update_gate_prep_kernel takes update_prep_kernel's place: it decides on the device which scans are
+// integrated and numbers them behind the updates earlier gated calls applied, so the levels' counters are not advanced here
+// (fold_gate_counters); a rejected scan's two launches return at once.
+struct GateCall {
+  const unsigned char* d_force = nullptr;
+  int* d_out_applied = nullptr;
+  bool slam = false;  // hsm_slam_scans_device's call for one scan: see UpdateGateParams
+  float* pose_io = nullptr;
+  float* cov_io = nullptr;
+  const float* next_delta = nullptr;
+};
+
 static int update_by_scans_device_nolock(hsm_ctx* h, int count, const float* d_poses_world, const float* d_pts_xy,
                                          const int* d_scan_offsets, int shared_n, int max_beams, const float origo[2],
-                                         hipStream_t stream) {
+                                         hipStream_t stream, const GateCall* gate = nullptr) {
   if (count < 0 || max_beams < 0 || (count > 0 && !d_poses_world) || (!d_scan_offsets && shared_n < 0) ||
       (count > 0 && !d_scan_offsets && shared_n > 0 && !d_pts_xy))
     return fail(HSM_ERR_INVALID, "hsm_update_by_scans_device: bad argument");
@@ -1822,6 +1879,8 @@ static int update_by_scans_device_nolock(hsm_ctx* h, int count, const float* d_p
   if (stream_capturing(stream))
     return fail(HSM_ERR_INVALID, "hsm_update_by_scans_device: `stream` is being captured into a graph (map updates are not captured)");
   if (int rc = order_after_foreign_match(h)) return rc;  // (refuses the same way for the streams this context has matched on)
+  if (!gate && h->gate_outstanding)  // scan k is update k behind EVERY earlier update: the ones gated calls applied go in first
+    if (int rc = fold_gate_counters(h)) return rc;
   if (int rc = ensure_update_scans(h, (size_t)count)) return rc;
   if (stream != h->stream) {  // the inputs are complete where the caller's stream stands now
     if (!h->evt_inputs) HIP_TRY(hipEventCreateWithFlags(&h->evt_inputs, hipEventDisableTiming));
@@ -1857,7 +1916,23 @@ static int update_by_scans_device_nolock(hsm_ctx* h, int count, const float* d_p
     V.update_index0 = L.curr_update_index;
     if (L.cells() > max_cells) max_cells = L.cells();
   }
-  hipLaunchKernelGGL(update_prep_kernel, dim3((unsigned)count), dim3(64), 0, h->stream, A);
+  if (gate) {
+    UpdateGateParams G;
+    memset(&G, 0, sizeof G);
+    G.prep = A;
+    G.state = h->d_gate;
+    G.min_dist = h->gate_min_dist;
+    G.min_angle = h->gate_min_angle;
+    G.force = gate->d_force;
+    G.out_applied = gate->d_out_applied;
+    G.slam = gate->slam ? 1 : 0;
+    G.pose_io = gate->pose_io;
+    G.cov_io = gate->cov_io;
+    G.next_delta = gate->next_delta;
+    hipLaunchKernelGGL(update_gate_prep_kernel, dim3(1), dim3(256), 0, h->stream, G);
+  } else {
+    hipLaunchKernelGGL(update_prep_kernel, dim3((unsigned)count), dim3(64), 0, h->stream, A);
+  }
   HIP_TRY(hipGetLastError());
   // launch shapes from the hint alone: the mark grid strides over the scan's real beam count, the apply grid over the scan's
   // box -- sized for the whole level, its blocks return after one scalar load where the box is empty or small
@@ -1891,17 +1966,107 @@ static int update_by_scans_device_nolock(hsm_ctx* h, int count, const float* d_p
   for (int l = 0; l < nlev; ++l) {
     Level& L = h->levels[l];
     L.marks_pending = false;
-    // OccGridMapBase.h:123-124, :167 and setUpdated() (GridMapBase.h:343), `count` times: an empty container counts, too
-    L.curr_mark_free = L.curr_update_index + 3 * (count - 1) + 1;
-    L.curr_mark_occ = L.curr_update_index + 3 * (count - 1) + 2;
-    L.curr_update_index += 3 * count;
-    L.last_update_index += count;
+    if (!gate) {
+      // OccGridMapBase.h:123-124, :167 and setUpdated() (GridMapBase.h:343), `count` times: an empty container counts, too
+      L.curr_mark_free = L.curr_update_index + 3 * (count - 1) + 1;
+      L.curr_mark_occ = L.curr_update_index + 3 * (count - 1) + 2;
+      L.curr_update_index += 3 * count;
+      L.last_update_index += count;
+    }
     L.key_rows[0] = 0;  // which rows carry keys of this generation is known on the device only: the next wrap of a host-side
     L.key_rows[1] = L.sy - 1;  // update clears the whole level
   }
   h->upd_boxes_outstanding = true;
+  if (gate) h->gate_outstanding = true;
   h->queued_update = h->async_update;
   if (!h->async_update) HIP_TRY(hipStreamSynchronize(h->stream));
+  return HSM_OK;
+}
+
+int hsm_set_update_gate(hsm_ctx* h, float min_dist, float min_angle) {
+  if (!h) return fail(HSM_ERR_INVALID, "null context");
+  std::lock_guard<std::mutex> lk(h->mu);
+  h->gate_min_dist = min_dist;
+  h->gate_min_angle = min_angle;
+  return HSM_OK;
+}
+
+int hsm_reset_update_gate(hsm_ctx* h) {
+  if (!h) return fail(HSM_ERR_INVALID, "null context");
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (int rc = select_device(h)) return rc;
+  return reset_update_gate(h);
+}
+
+int hsm_update_gate_state(hsm_ctx* h, float last_update_pose[3], long long* applied_total) {
+  if (!h) return fail(HSM_ERR_INVALID, "null context");
+  std::lock_guard<std::mutex> lk(h->mu);
+  GateState st;
+  if (int rc = fold_gate_counters(h, &st)) return rc;
+  if (last_update_pose)
+    for (int i = 0; i < 3; ++i) last_update_pose[i] = st.last_update_pose[i];
+  if (applied_total) *applied_total = h->gate_applied_total;
+  return HSM_OK;
+}
+
+int hsm_update_by_scans_device_gated(hsm_ctx* h, int count, const float* d_poses_world, const float* d_pts_xy,
+                                     const int* d_scan_offsets, int shared_n, int max_beams, const float origo[2],
+                                     const unsigned char* d_force, int* d_out_applied, void* stream) {
+  if (!h) return fail(HSM_ERR_INVALID, "null context");
+  std::lock_guard<std::mutex> lk(h->mu);
+  GateCall gate;
+  gate.d_force = d_force;
+  gate.d_out_applied = d_out_applied;
+  return update_by_scans_device_nolock(h, count, d_poses_world, d_pts_xy, d_scan_offsets, shared_n, max_beams, origo,
+                                       static_cast<hipStream_t>(stream), &gate);
+}
+
+// HectorSlamProcessor::update for a log of scans (HectorSlamProcessor.h:71-95), queued whole.  Everything runs on the context's
+// own stream -- the matches too, so a scan costs no event hop: the caller's stream is waited for once, in front, and waits once,
+// behind.  Per scan: the exact batch matcher on a batch of one, reading its hint from the gate's device block; then the gated
+// update of that one scan, whose gate launch also settles a forced scan's pose and covariance and leaves the next scan's hint.
+int hsm_slam_scans_device(hsm_ctx* h, int count, const float* d_start_pose, const float* d_hint_deltas, const float* d_pts_xy,
+                          const int* d_scan_offsets, int max_beams, const float origo[2], const unsigned char* d_force,
+                          float* d_out_pose, float* d_out_cov, int* d_out_applied, void* stream) {
+  if (!h) return fail(HSM_ERR_INVALID, "null context");
+  if (count < 0 || max_beams < 0 || (count > 0 && (!d_scan_offsets || !d_out_pose)))
+    return fail(HSM_ERR_INVALID, "hsm_slam_scans_device: bad argument");
+  if (count == 0) return HSM_OK;
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (int rc = select_device(h)) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (stream_capturing(s))
+    return fail(HSM_ERR_INVALID, "hsm_slam_scans_device: `stream` is being captured into a graph (map updates are not captured)");
+  for (const hsm_ctx::ForeignStream& f : h->foreign)  // refused before anything is queued (order_after_foreign_match)
+    if (stream_capturing(f.s))
+      return fail(HSM_ERR_INVALID, "hsm_slam_scans_device: a caller's stream that this context matches on is being captured into a graph");
+  if (s != h->stream) {  // the inputs are complete where the caller's stream stands now
+    if (!h->evt_inputs) HIP_TRY(hipEventCreateWithFlags(&h->evt_inputs, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(h->evt_inputs, s));
+    HIP_TRY(hipStreamWaitEvent(h->stream, h->evt_inputs, 0));
+  }
+  hipLaunchKernelGGL(slam_begin_kernel, dim3(1), dim3(64), 0, h->stream, h->d_gate, d_start_pose, d_hint_deltas);
+  HIP_TRY(hipGetLastError());
+  for (int k = 0; k < count; ++k) {
+    if (int rc = match_batch_device_nolock(h, 1, h->d_gate->hint, d_pts_xy, d_scan_offsets + k, max_beams, d_out_pose + 3 * (size_t)k,
+                                           d_out_cov ? d_out_cov + 9 * (size_t)k : nullptr, h->stream))
+      return rc;
+    GateCall gate;
+    gate.d_force = d_force ? d_force + k : nullptr;
+    gate.d_out_applied = d_out_applied ? d_out_applied + k : nullptr;
+    gate.slam = true;
+    gate.pose_io = d_out_pose + 3 * (size_t)k;
+    gate.cov_io = d_out_cov ? d_out_cov + 9 * (size_t)k : nullptr;
+    gate.next_delta = d_hint_deltas && k + 1 < count ? d_hint_deltas + 3 * (size_t)(k + 1) : nullptr;
+    if (int rc = update_by_scans_device_nolock(h, 1, gate.pose_io, d_pts_xy, d_scan_offsets + k, 0, max_beams, origo, h->stream,
+                                               &gate))
+      return rc;
+  }
+  if (s != h->stream) {  // the results are complete where the context's stream stands now
+    if (!h->evt_slam_done) HIP_TRY(hipEventCreateWithFlags(&h->evt_slam_done, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(h->evt_slam_done, h->stream));
+    HIP_TRY(hipStreamWaitEvent(s, h->evt_slam_done, 0));
+  }
   return HSM_OK;
 }
 
@@ -2958,6 +3123,8 @@ int hsm_world_coords_pose(const hsm_ctx* h, int level, const float m[3], float w
 int hsm_update_index(const hsm_ctx* h, int level) {
   if (valid_level(h, level)) return -1;
   std::lock_guard<std::mutex> lk(h->mu);  // read by the facade's publisher thread while the scan thread updates
+  if (h->gate_outstanding)  // gated updates since the last look: wait for them and fetch their count
+    if (fold_gate_counters(const_cast<hsm_ctx*>(h))) return -1;
   return h->levels[level].last_update_index;
 }
 
@@ -2979,6 +3146,8 @@ int hsm_upload_level(hsm_ctx* h, int level, const float* logodds, const int* upd
   Level& L = h->levels[level];
   if (h->upd_boxes_outstanding)
     if (int rc = merge_device_boxes(h)) return rc;
+  if (h->gate_outstanding)
+    if (int rc = fold_gate_counters(h)) return rc;
   if (int rc = order_after_foreign_match(h)) return rc;
   HIP_TRY(hipStreamSynchronize(h->stream));
   if (logodds) HIP_TRY(hipMemcpy(L.d_logodds, logodds, L.cells() * sizeof(float), hipMemcpyHostToDevice));

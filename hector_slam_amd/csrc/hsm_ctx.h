@@ -19,6 +19,7 @@
 namespace hsm {
 struct BeamRec;  // map_update.h (its kernels are not templates: only hector_mi355.hip includes that header)
 struct UpdateBatch;
+struct GateState;
 }
 
 namespace hsm_host {
@@ -178,6 +179,14 @@ struct hsm_ctx {
   Buf<int> d_upd_boxes{&bufs};  // allocated last: non-null = both blocks serve d_upd_batches.count() scans
   bool upd_boxes_outstanding = false;  // device-side updates since the host last merged their boxes into Level::bbox / dirty
   hipEvent_t evt_inputs = nullptr;     // the caller's stream at hsm_update_by_scans_device: its inputs are complete
+  // the movement gate of HectorSlamProcessor::update (update_gate.h; map_update.h update_gate_prep_kernel): its state and the
+  // count of updates it let through live on the device -- the host never learns a gated call's decisions.  Whoever needs
+  // Level's update counters on the host first waits for the stream and folds that count in (fold_gate_counters), like the boxes
+  hsm::GateState* d_gate = nullptr;
+  float gate_min_dist = 0.4f, gate_min_angle = 0.13f;  // HectorSlamProcessor.h:62-63 (hsm_set_update_gate)
+  bool gate_outstanding = false;       // gated calls since the host last folded their count into the levels' counters
+  long long gate_applied_total = 0;    // updates of gated calls folded so far, since hsm_create
+  hipEvent_t evt_slam_done = nullptr;  // the context's stream at the end of hsm_slam_scans_device: the caller's stream waits for it
   Buf<char> d_upd_stage{&bufs};        // hsm_update_by_scans: poses, offsets and end points of the host arrays
   Buf<float2> h_upd_pinned[2] = {Buf<float2>{&bufs, kBufPinnedMapped}, Buf<float2>{&bufs, kBufPinnedMapped}};
   hipEvent_t upd_evt[2] = {nullptr, nullptr};

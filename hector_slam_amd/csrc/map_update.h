@@ -36,6 +36,7 @@
 #include <hip/hip_runtime.h>
 
 #include "gn_match.h"
+#include "update_gate.h"
 
 namespace hsm {
 
@@ -748,13 +749,13 @@ struct UpdatePrepParams {
 // the box slot of scan k of a call of `count` scans (the last scan's sits where the host finds it without knowing count)
 __host__ __device__ __forceinline__ int update_box_slot(int k, int count) { return k == count - 1 ? 1 : 2 + k; }
 
-__global__ void __launch_bounds__(64) update_prep_kernel(const UpdatePrepParams A) {
-  const int k = blockIdx.x, l = threadIdx.x;
-  if (l >= A.nlev) return;
+// scan k's UpdateParams of level l and its (empty) box: points [first, first + n) of A.pts at `pose`, marked with
+// update_index0 + 3 * rank + 1 / + 2 (currMarkFreeIndex / currMarkOccIndex, OccGridMapBase.h:123-124)
+__device__ __forceinline__ void update_prep_scan_level(const UpdatePrepParams& A, int k, int l, float px, float py, float th,
+                                                       int first, int n, int rank) {
   const UpdatePrepLevel& V = A.lv[l];
   UpdateParams P;
   P.lv = V.lv;
-  const float px = A.poses_world[3 * k], py = A.poses_world[3 * k + 1], th = A.poses_world[3 * k + 2];
   float mx, my;
   affine_apply(V.mapTworld, px, py, mx, my);  // getMapCoordsPose
   // Translation2f(mapPose.xy) * Rotation2Df(mapPose.theta): glibc's sinf / cosf (the pair sincosf returns, libm_exact.h)
@@ -776,11 +777,6 @@ __global__ void __launch_bounds__(64) update_prep_kernel(const UpdatePrepParams 
   const bool finite = bx > -2.0f && bx < (float)V.lv.sx + 2.0f && by > -2.0f && by < (float)V.lv.sy + 2.0f;
   P.bx = finite ? (int)bx : -1;
   P.by = finite ? (int)by : -1;
-  int first = 0, n = A.shared_n;
-  if (A.offsets) {
-    first = A.offsets[k];
-    n = A.offsets[k + 1] - first;
-  }
   if (n < 0 || n > (int)kBeamMask) n = 0;  // (more beams than the key's index field holds: integrated as an empty scan)
   P.pts = A.pts + first;
   P.n = n;
@@ -788,8 +784,8 @@ __global__ void __launch_bounds__(64) update_prep_kernel(const UpdatePrepParams 
   P.serial = (V.serial0 + (unsigned int)k) % kSerialMax + 1u;
   P.log_odds_free = V.log_odds_free;
   P.log_odds_occ = V.log_odds_occ;
-  P.mark_free = V.update_index0 + 3 * k + 1;  // currMarkFreeIndex / currMarkOccIndex, OccGridMapBase.h:123-124
-  P.mark_occ = V.update_index0 + 3 * k + 2;
+  P.mark_free = V.update_index0 + 3 * rank + 1;
+  P.mark_occ = V.update_index0 + 3 * rank + 2;
   P.x0 = P.y0 = kBoxEmptyLo;  // (the passes take the box from A.boxes)
   P.x1 = P.y1 = kBoxEmptyHi;
   P.recs = nullptr;
@@ -799,6 +795,164 @@ __global__ void __launch_bounds__(64) update_prep_kernel(const UpdatePrepParams 
   int* box = A.boxes + ((size_t)update_box_slot(k, A.count) * kMaxLevels + l) * 4;
   box[0] = box[1] = kBoxEmptyLo;
   box[2] = box[3] = kBoxEmptyHi;
+}
+
+__global__ void __launch_bounds__(64) update_prep_kernel(const UpdatePrepParams A) {
+  const int k = blockIdx.x, l = threadIdx.x;
+  if (l >= A.nlev) return;
+  int first = 0, n = A.shared_n;
+  if (A.offsets) {
+    first = A.offsets[k];
+    n = A.offsets[k + 1] - first;
+  }
+  // every scan is integrated: scan k is update k of the call
+  update_prep_scan_level(A, k, l, A.poses_world[3 * k], A.poses_world[3 * k + 1], A.poses_world[3 * k + 2], first, n, k);
+}
+
+// ---- the movement gate in front of them (hsm_update_by_scans_device_gated, hsm_slam_scans_device) -------------------------------
+// HectorSlamProcessor::update (HectorSlamProcessor.h:71-95) integrates a scan only where util::poseDifferenceLargerThan(pose,
+// lastMapUpdatePose, ..) holds or the caller forces it, and lastMapUpdatePose follows every integrated scan: the decisions of a
+// call are SEQUENTIAL in k, and the host sees none of them.  So what the host derived per scan for the ungated entry -- "scan k is
+// update k" -- is derived here: ONE launch per call, one workgroup.  Lane 0 walks the scans, 256 a turn (update_gate.h's
+// gate_step, the text the CPU model test compiles), and leaves {integrated, rank, the coarse levels' points} per scan in LDS;
+// then all lanes fill the UpdateBatch blocks as update_prep_kernel does.  A rejected scan gets n = 0 on every level and an empty
+// box: update_mark_scan_kernel and update_apply_scan_kernel return after one scalar load.  The gate's state lives in a
+// per-context device block and is written with ordinary stores.
+struct GateState {
+  float last_update_pose[3];  // lastMapUpdatePose: FLT_MAX three times until a scan is integrated
+  int pending;                // updates that gated calls applied and the host has not yet folded into Level's counters
+  // hsm_slam_scans_device
+  float hint[3];              // start estimate of the next scan
+  int retained_first;         // the scan the coarse levels retain (matchData's setFrom, MapRepMultiMap.h:143): points
+  float last_pose[3];         // lastScanMatchPose                                   [retained_first, + retained_n) of this
+  int retained_n;             //                                                     call's d_pts_xy
+  float last_cov[9];          // lastScanMatchCov
+  int reserved[3];
+};
+
+struct UpdateGateParams {
+  UpdatePrepParams prep;
+  GateState* state;
+  float min_dist, min_angle;
+  const unsigned char* force;  // [count] map_without_matching per scan, or nullptr
+  int* out_applied;            // [count], or nullptr
+  // hsm_slam_scans_device's call for ONE scan (count == 1), behind its match:
+  int slam;
+  float* pose_io;              // [3] the matched pose; a forced scan takes its hint instead (written here)
+  float* cov_io;               // [9] the match's covariance, or nullptr; a forced scan keeps the last one (written here)
+  const float* next_delta;     // [3] added to the pose to give the next scan's hint, or nullptr: the pose itself
+};
+
+constexpr int kGateChunk = 256;
+
+__global__ void __launch_bounds__(256) update_gate_prep_kernel(const UpdateGateParams G) {
+  __shared__ int4 walk[kGateChunk];  // {integrated, rank, first point of the coarse levels' container, its length}
+  const UpdatePrepParams& A = G.prep;
+  GateWalk w;
+  gate_reset(w);
+  int ret_first = 0, ret_n = 0;
+  if (threadIdx.x == 0) {
+    w.last_update_pose[0] = G.state->last_update_pose[0];
+    w.last_update_pose[1] = G.state->last_update_pose[1];
+    w.last_update_pose[2] = G.state->last_update_pose[2];
+    w.applied = G.state->pending;
+    ret_first = G.state->retained_first;
+    ret_n = G.state->retained_n;
+  }
+  for (int k0 = 0; k0 < A.count; k0 += kGateChunk) {
+    const int chunk = min(kGateChunk, A.count - k0);
+    if (threadIdx.x == 0) {
+      for (int j = 0; j < chunk; ++j) {
+        const int k = k0 + j;
+        const bool force = G.force != nullptr && G.force[k] != 0;
+        int first = 0, n = A.shared_n;
+        if (A.offsets) {
+          first = A.offsets[k];
+          n = A.offsets[k + 1] - first;
+        }
+        float pose[3];
+        if (G.slam) {
+          // a forced scan skips the match (HectorSlamProcessor.h:75-80): its pose is its hint, the covariance stays, and the
+          // coarse levels keep the containers of the last matched scan
+          for (int i = 0; i < 3; ++i) pose[i] = force ? G.state->hint[i] : G.pose_io[3 * k + i];
+          if (force) {
+            for (int i = 0; i < 3; ++i) G.pose_io[3 * k + i] = pose[i];
+          } else {
+            ret_first = first;
+            ret_n = n;
+          }
+          if (G.cov_io) {
+            for (int i = 0; i < 9; ++i) {
+              if (force)
+                G.cov_io[9 * k + i] = G.state->last_cov[i];
+              else if (n > 0)  // (matchData leaves the covariance alone for an empty container, ScanMatcher.h:62-64)
+                G.state->last_cov[i] = G.cov_io[9 * k + i];
+            }
+          }
+          for (int i = 0; i < 3; ++i) {
+            G.state->last_pose[i] = pose[i];
+            G.state->hint[i] = G.next_delta ? pose[i] + G.next_delta[i] : pose[i];
+          }
+        } else {
+          for (int i = 0; i < 3; ++i) pose[i] = A.poses_world[3 * k + i];
+          ret_first = first;  // every level sees the scan itself, as in hsm_update_by_scans_device
+          ret_n = n;
+        }
+        int rank;
+        const bool go = gate_step(w, pose, force, G.min_dist, G.min_angle, &rank);
+        walk[j] = make_int4(go ? 1 : 0, rank, ret_first, ret_n);
+        if (G.out_applied) G.out_applied[k] = go ? 1 : 0;
+      }
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < chunk * A.nlev; t += blockDim.x) {
+      const int j = t / A.nlev, l = t - j * A.nlev, k = k0 + j;
+      const int4 d = walk[j];
+      int first = 0, n = A.shared_n;
+      if (A.offsets) {
+        first = A.offsets[k];
+        n = A.offsets[k + 1] - first;
+      }
+      if (l > 0) {
+        first = d.z;
+        n = d.w;
+      }
+      const float* pose = G.slam ? G.pose_io + 3 * k : A.poses_world + 3 * k;
+      update_prep_scan_level(A, k, l, pose[0], pose[1], pose[2], first, d.x ? n : 0, d.y);
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    G.state->last_update_pose[0] = w.last_update_pose[0];
+    G.state->last_update_pose[1] = w.last_update_pose[1];
+    G.state->last_update_pose[2] = w.last_update_pose[2];
+    G.state->pending = w.applied;
+    G.state->retained_first = ret_first;
+    G.state->retained_n = ret_n;
+  }
+}
+
+// lastMapUpdatePose back to FLT_MAX (hsm_reset_update_gate); `all`: lastScanMatchPose and the hint back to 0 as well
+// (HectorSlamProcessor::reset, HectorSlamProcessor.h:133-140).  The counters stay: the maps keep theirs.
+__global__ void update_gate_reset_kernel(GateState* state) {
+  if (threadIdx.x < 3) {
+    state->last_update_pose[threadIdx.x] = FLT_MAX;
+    state->last_pose[threadIdx.x] = 0.0f;
+    state->hint[threadIdx.x] = 0.0f;
+  }
+}
+
+// hsm_slam_scans_device, in front of the first scan of a call: its hint is the start pose -- or, where the caller gives none,
+// the last pose of the call before -- plus delta 0; the coarse levels' containers do not outlive the call that owned their points
+__global__ void slam_begin_kernel(GateState* state, const float* __restrict__ start_pose, const float* __restrict__ delta0) {
+  if (threadIdx.x < 3) {
+    const float p = start_pose ? start_pose[threadIdx.x] : state->last_pose[threadIdx.x];
+    state->hint[threadIdx.x] = delta0 ? p + delta0[threadIdx.x] : p;
+  }
+  if (threadIdx.x == 0) {
+    state->retained_first = 0;
+    state->retained_n = 0;
+  }
 }
 
 template <int CTRL>

@@ -1,0 +1,75 @@
+// update_gate.h -- the movement gate of HectorSlamProcessor::update (HSL/slam_main/HectorSlamProcessor.h:71-95): a scan is
+// integrated into the map only when its pose differs from the pose of the last integrated scan by more than a distance or an
+// angle, util::poseDifferenceLargerThan (HSL/util/UtilFunctions.h:73-92), or when the caller forces it (map_without_matching).
+// Plain C++ (no HIP header): the device's gate kernel (map_update.h) and the host compile the same text, and
+// tests/cpp/update_gate_model.cpp holds it to the CPU checkers with the host compiler alone (tests/test_update_gate_model.py).
+#pragma once
+#include <float.h>
+#include <math.h>
+
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define HSM_GATE_HD __host__ __device__
+#else
+#define HSM_GATE_HD
+#endif
+
+namespace hsm {
+
+// HectorSlamProcessor.h:62-63
+constexpr float kGateDefaultMinDist = 0.4f, kGateDefaultMinAngle = 0.13f;
+
+// util::poseDifferenceLargerThan in the reference's own mix of types:
+//   ((pose1.head<2>() - pose2.head<2>()).norm()) > distanceDiffThresh     fp32: sqrtf(dx * dx + dy * dy), the products and the sum
+//                                                                          each rounded (no contraction), the root correctly rounded
+//   angleDiff > M_PI / < -M_PI                                             the float against the DOUBLE constant
+//   angleDiff -= M_PI * 2.0f  /  += M_PI * 2.0f                            in double, rounded back to float
+//   abs(angleDiff) > angleDiffThresh                                       fp32
+// A NaN in any component compares false everywhere: "not larger".  Against (FLT_MAX, FLT_MAX, .) the squared distance
+// overflows to +inf: "larger".
+HSM_GATE_HD inline bool pose_difference_larger_than(const float pose1[3], const float pose2[3], float dist_thresh,
+                                                    float angle_thresh) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const float dx = pose1[0] - pose2[0];
+  const float dy = pose1[1] - pose2[1];
+  const float xx = dx * dx, yy = dy * dy;
+  const float sq = xx + yy;
+  if (sqrtf(sq) > dist_thresh) return true;
+  float angle_diff = pose1[2] - pose2[2];
+  const double pi = 3.14159265358979323846;  // M_PI
+  if ((double)angle_diff > pi) {
+    angle_diff = (float)((double)angle_diff - pi * 2.0);
+  } else if ((double)angle_diff < -pi) {
+    angle_diff = (float)((double)angle_diff + pi * 2.0);
+  }
+  return fabsf(angle_diff) > angle_thresh;
+}
+
+// What the gate remembers between scans: lastMapUpdatePose, FLT_MAX three times until the first scan is integrated
+// (HectorSlamProcessor.h:133-136 reset()), and how many scans it has let through.
+struct GateWalk {
+  float last_update_pose[3];
+  int applied;
+};
+
+HSM_GATE_HD inline void gate_reset(GateWalk& g) {
+  g.last_update_pose[0] = g.last_update_pose[1] = g.last_update_pose[2] = FLT_MAX;
+  g.applied = 0;
+}
+
+// One scan of HectorSlamProcessor::update's second half (:84-94): true = integrate it.  *rank = the number of scans integrated
+// before it since `g.applied` was last zeroed, which numbers its update (OccGridMapBase.h:123-124, :167).  A rejected scan
+// changes nothing.
+HSM_GATE_HD inline bool gate_step(GateWalk& g, const float pose[3], bool map_without_matching, float dist_thresh,
+                                  float angle_thresh, int* rank) {
+  *rank = g.applied;
+  if (!(pose_difference_larger_than(pose, g.last_update_pose, dist_thresh, angle_thresh) || map_without_matching)) return false;
+  g.last_update_pose[0] = pose[0];
+  g.last_update_pose[1] = pose[1];
+  g.last_update_pose[2] = pose[2];
+  ++g.applied;
+  return true;
+}
+
+}  // namespace hsm

@@ -235,6 +235,69 @@ int hsm_update_by_scans_device(hsm_ctx* h, int count, const float* d_poses_world
 int hsm_update_by_scans(hsm_ctx* h, int count, const float* poses_world, const float* pts_xy,
                         const int* scan_offsets, int shared_n, const float origo[2]);
 
+/* ---- the movement gate of HectorSlamProcessor::update, on the device ----------------------------------------------------
+ * replaces: the second half of HectorSlamProcessor::update (HSL/slam_main/HectorSlamProcessor.h:84-94):
+ *             if (util::poseDifferenceLargerThan(newPose, lastMapUpdatePose, minDist, minAngle) || map_without_matching)
+ *               { updateByScan; onMapUpdated; lastMapUpdatePose = newPose; }
+ *           with util::poseDifferenceLargerThan (HSL/util/UtilFunctions.h:73-92) in the reference's fp32 / fp64 mix.
+ * lastMapUpdatePose and the number of updates the gate has let through live in a per-context device block: the host learns
+ * neither a decision nor a pose.  A NaN compares false, so a NaN in x or y leaves the angle test alone to let the pose through,
+ * a NaN in theta the distance test, and an all-NaN pose is never "larger": it is not integrated and advances no counter (the
+ * ungated entry counts it as an update).  An infinite pose is integrated as an update that changes no cell.
+ *
+ * thresholds of the gate (paramMinDistanceDiffForMapUpdate / paramMinAngleDiffForMapUpdate; 0.4 / 0.13 after hsm_create,
+ * HectorSlamProcessor.h:62-63); they apply to the calls queued afterwards */
+int hsm_set_update_gate(hsm_ctx* h, float min_dist, float min_angle);
+/* lastMapUpdatePose = FLT_MAX three times (the next scan is integrated whatever its pose) and lastScanMatchPose = 0, as
+ * HectorSlamProcessor::reset leaves them (:133-140); also done by hsm_create and hsm_reset.  Stream-ordered: queued behind the
+ * gated calls made so far, no host wait.  The update counters of the maps stay. */
+int hsm_reset_update_gate(hsm_ctx* h);
+/* waits for the context's stream and fetches the gate's state: lastMapUpdatePose, and the number of updates gated calls have
+ * applied since hsm_create.  Either pointer may be NULL. */
+int hsm_update_gate_state(hsm_ctx* h, float last_update_pose[3], long long* applied_total);
+/* hsm_update_by_scans_device behind the gate: for k = 0 .. count-1, in order, scan k is integrated where the gate lets pose k
+ * through.  Arguments, stream rules, ordering and refusals of hsm_update_by_scans_device, plus
+ *   d_force        DEVICE [count] bytes, non-zero = map_without_matching: the scan is integrated whatever the gate says
+ *                  (and becomes lastMapUpdatePose).  NULL = none.
+ *   d_out_applied  DEVICE [count] ints, 1 = integrated, 0 = rejected.  May be NULL.
+ * One gate launch per call (the decisions are sequential: one lane walks them), then the two launches per scan of the
+ * ungated entry; those of a rejected scan return at once, and it changes no cell and no counter.  An integrated scan is marked
+ * with the update index that follows the last integrated one.  One key generation is spent per scan and level, integrated or
+ * not.  hsm_update_index and every host-side update called afterwards first wait for the stream to learn how many scans were
+ * integrated.  hsm_last_update_bbox afterwards: the box of the call's LAST scan, empty where that one was rejected.
+ * HSM_ERR_INVALID, nothing queued, while `stream` or a stream this context has matched on is being captured.
+ * Not built: capture into graphs, replay through hsm_group_*, the byte-map (dense) form of the update. */
+int hsm_update_by_scans_device_gated(hsm_ctx* h, int count, const float* d_poses_world, const float* d_pts_xy,
+                                     const int* d_scan_offsets, int shared_n, int max_beams, const float origo[2],
+                                     const unsigned char* d_force, int* d_out_applied, void* stream);
+/* replaces: for k = 0 .. count-1, in order: HectorSlamProcessor::update(container_k, hint_k, force_k)
+ *           (HSL/slam_main/HectorSlamProcessor.h:71-95): matchData, the gate, updateByScan -- a log of scans in ONE call that
+ *           returns when everything is queued.  The host waits for nothing and learns nothing.  DEVICE pointers:
+ *   d_start_pose   [3] hint of scan 0; NULL = lastScanMatchPose of the call before (0 after hsm_create / a reset)
+ *   d_hint_deltas  [count*3] or NULL.  hint_k = pose_(k-1) + delta_k componentwise in fp32 (hint_0 = start + delta_0), e.g.
+ *                  odometry increments; NULL = the pose is passed on unchanged, no addition.
+ *   d_pts_xy, d_scan_offsets   CSR scans as in hsm_match_batch_device ([count+1] offsets in points; required)
+ *   max_beams      sizing hint as in hsm_update_by_scans_device (0 = unknown -> 1081)
+ *   origo          HOST, the containers' origo (NULL = 0,0)
+ *   d_force        [count] bytes or NULL: a forced scan skips the match and takes its hint as its pose; its covariance row
+ *                  repeats lastScanMatchCov, and the coarse levels integrate the containers the last MATCHED scan left there,
+ *                  as the reference does (MapRepMultiMap.h:134-147).  Those containers do not outlive the call: a scan forced
+ *                  before the first matched scan of a call finds them empty, as the reference does before its first match.
+ *   d_out_pose     [count*3] lastScanMatchPose after each scan        d_out_cov [count*9] or NULL
+ *   d_out_applied  [count] ints or NULL: 1 = the scan was integrated
+ * An empty scan returns its hint as its pose, like matchData; its covariance row is what hsm_match_batch_device writes for
+ * an empty scan.  Per scan the call queues one match of one scan through hsm_match_batch_device's path, the gate launch, the
+ * mark and the apply launch, all on the context's stream: `stream` (the caller's, NULL = default stream) is waited for once in
+ * front -- the inputs must be complete there -- and waits once behind, so work queued on it afterwards sees every result.
+ * The gate's state persists on the device: two calls of 12 scans give what one call of 24 gives.
+ * HSM_ERR_INVALID, nothing queued: a bad argument, or `stream` / a stream this context has matched on is being captured.
+ * Does not touch the retained or the ingested scan.  Not built: capture into graphs, replay through hsm_group_*, the byte-map
+ * (dense) form of the update; the C++ facade's HectorSlamProcessor.h stays reference code and does not call this. */
+int hsm_slam_scans_device(hsm_ctx* h, int count, const float* d_start_pose, const float* d_hint_deltas,
+                          const float* d_pts_xy, const int* d_scan_offsets, int max_beams, const float origo[2],
+                          const unsigned char* d_force, float* d_out_pose, float* d_out_cov, int* d_out_applied,
+                          void* stream);
+
 /* ---- single-process multi-GPU group (extension; the reference has no multi-device path) ------------------
  * One replica of the pyramid per listed device (a device may be listed more than once).  Batched matching is
  * sharded contiguously over the replicas, one PERSISTENT host thread per replica (created with the group), each
