@@ -85,6 +85,10 @@ SIGNATURES = {
     "hsm_match_batch_ranges_device": (_i, [_vp, _i, _vp, _vp, _i, _f, _f, _f, _f, _f, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "hsm_match_batch_ranges_workspace": (C.c_size_t, [_i, _i]),
     "hsm_match_batch_ranges": (_i, [_vp, _i, _vp, _vp, _i, _f, _f, _f, _f, _f, _vp, _vp, _vp]),
+    "hsm_ingest_batch_ranges_tf_device": (_i, [_vp, _i, _vp, _i, _f, _f, _f, _f, C.c_double, _vp, _i, _f, _f, _f, _f, _f, _vp, _vp,
+                                               _vp, _vp, _vp]),
+    "hsm_match_batch_ranges_tf": (_i, [_vp, _i, _vp, _vp, _i, _f, _f, _f, _f, C.c_double, _vp, _i, _f, _f, _f, _f, _f, _vp, _vp,
+                                       _vp, _vp]),
     "hsm_occupancy_grid": (_i, [_vp, _i, _vp]),
     "hsm_ray_distances": (_i, [_vp, _i, _f, _f, _f, _i, _f32p, _f32p, _f32p, _f32p]),
     "hsm_score_batch_device": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
@@ -685,6 +689,47 @@ class MapRepMultiMap:
                "hsm_match_batch_ranges_device")
 
     match_batch_ranges_workspace = staticmethod(match_batch_ranges_workspace)
+
+    def ingest_batch_ranges_tf_device(self, batch, d_ranges, n, angle_min, angle_increment, range_min, range_max, range_cutoff,
+                                      d_tf_rows, shared_tf, sqr_laser_min_dist, sqr_laser_max_dist, laser_z_min, laser_z_max,
+                                      scale_to_map, d_out_pts, d_out_offsets, d_out_counts, d_out_origo=0, stream=0):
+        """Raw device pointers (ints), asynchronous on ``stream``: B raw scans + a laser->base transform per scan (``d_tf_rows``
+        [B, 12] doubles, or [12] with ``shared_tf``) through the node's default tf path -> the CSR container of the batched
+        entries (``d_out_pts`` [max(B*n, 1), 2], ``d_out_offsets`` [B+1], ``d_out_counts`` [B]) and the origos [B, 2]."""
+        _check(self._lib.hsm_ingest_batch_ranges_tf_device(
+            self._h, batch, d_ranges or None, n, angle_min, angle_increment, range_min, range_max, range_cutoff, d_tf_rows or None,
+            int(bool(shared_tf)), sqr_laser_min_dist, sqr_laser_max_dist, laser_z_min, laser_z_max, scale_to_map, d_out_pts or None,
+            d_out_offsets or None, d_out_counts or None, d_out_origo or None, stream or None), "hsm_ingest_batch_ranges_tf_device")
+
+    def match_batch_ranges_tf(self, begin_world, ranges, angle_min, angle_increment, range_min, range_max, range_cutoff, tf_rows,
+                              sqr_laser_min_dist, sqr_laser_max_dist, laser_z_min, laser_z_max, scale_to_map=None, want_cov=True,
+                              cov=None):
+        """B raw LaserScans of one geometry (``ranges`` [B, n]) through the node's default tf path (``tf_rows`` [B, 12], or [12]:
+        one transform for every scan), then matchData per scan -> (pose [B, 3], cov [B, 9] or None, counts [B], origo [B, 2]).
+        Host arrays in/out; ``cov`` presets the covariances (a scan that keeps no beam leaves its row untouched)."""
+        b = np.ascontiguousarray(begin_world, np.float32).reshape(-1, 3)
+        r = np.ascontiguousarray(ranges, np.float32)
+        B = b.shape[0]
+        if r.ndim != 2 or r.shape[0] != B:
+            raise ValueError("ranges must be [B, n] with B = len(begin_world)")
+        T = np.ascontiguousarray(tf_rows, np.float64)
+        shared = T.size == 12 and T.ndim == 1
+        if not shared and T.shape != (B, 12):
+            raise ValueError("tf_rows must be [12] or [B, 12]")
+        n = r.shape[1]
+        out = np.empty_like(b)
+        if want_cov:
+            cov = np.zeros((B, 9), np.float32) if cov is None else np.array(cov, np.float32).reshape(B, 9)
+        else:
+            cov = None
+        counts, origo = np.empty(B, np.int32), np.empty((B, 2), np.float32)
+        s = self.getScaleToMap() if scale_to_map is None else scale_to_map
+        _check(self._lib.hsm_match_batch_ranges_tf(self._h, B, b.ctypes.data, r.ctypes.data if r.size else None, n, angle_min,
+                                                   angle_increment, range_min, range_max, range_cutoff, T.ctypes.data,
+                                                   int(shared), sqr_laser_min_dist, sqr_laser_max_dist, laser_z_min, laser_z_max,
+                                                   s, out.ctypes.data, None if cov is None else cov.ctypes.data,
+                                                   counts.ctypes.data, origo.ctypes.data), "hsm_match_batch_ranges_tf")
+        return out, cov, counts, origo
 
     def match_batch_device_gather(self, batch, d_begin, d_pts, d_offsets, shared_n, d_out_pose, d_out_cov, exchange, first_row, lag,
                                   d_out_all, stream=0):

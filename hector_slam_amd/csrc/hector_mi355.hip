@@ -944,6 +944,7 @@ void hsm_destroy(hsm_ctx* h) {
   for (hsm_ctx::SpecScratch& b : h->spec_scratch) b.d.release(log);
   for (hsm_ctx::PermBuf& b : h->perm_bufs) b.d.release(log);
   for (hsm_ctx::RangesGeometry& g : h->ranges_geoms) TEARDOWN(log, hipFree(g.d));
+  for (hsm_ctx::RangesTfGeometry& g : h->ranges_tf_geoms) TEARDOWN(log, hipFree(g.d));
   TEARDOWN(log, hipFree(h->d_spec_stats));
   TEARDOWN(log, hipFree(h->d_small));
   TEARDOWN(log, hipFree(h->d_partials));
@@ -2159,6 +2160,18 @@ static std::vector<float> node_scan_trig(int n, float angle_min, float angle_inc
   return t;
 }
 
+// laser_geometry's unit vectors (getUnitVectors_): double cos/sin(angle_min + (double)i * angle_increment), cached per sensor
+// geometry there as well -- the table of hsm_ingest_laser_scan_tf and hsm_ingest_batch_ranges_tf_device
+static std::vector<double> laser_unit_vectors(int n, float angle_min, float angle_increment) {
+  std::vector<double> t(2 * (size_t)n);
+  const double a0 = angle_min, inc = angle_increment;
+  for (int i = 0; i < n; ++i) {
+    t[2 * i] = cos(a0 + (double)i * inc);
+    t[2 * i + 1] = sin(a0 + (double)i * inc);
+  }
+  return t;
+}
+
 int hsm_ingest_laser_scan(hsm_ctx* h, const float* ranges, int n, float angle_min, float angle_increment,
                           float range_min, float range_max, float scale_to_map, float* out_pts_xy, int* out_n) {
   if (!h) return fail(HSM_ERR_INVALID, "null context");
@@ -2238,14 +2251,7 @@ int hsm_ingest_laser_scan_tf(hsm_ctx* h, const float* ranges, int n, float angle
   if (int rc = select_device(h)) return rc;
   if (int rc = ensure_ingest_capacity(h, n)) return rc;
   if (h->trig_kind != 1 || h->trig_n != n || h->trig_a0 != angle_min || h->trig_inc != angle_increment) {
-    // laser_geometry's unit vectors (getUnitVectors_): double cos/sin(angle_min + (double)i * angle_increment),
-    // cached per sensor geometry there as well
-    std::vector<double> t(2 * (size_t)n);
-    const double a0 = angle_min, inc = angle_increment;
-    for (int i = 0; i < n; ++i) {
-      t[2 * i] = cos(a0 + (double)i * inc);
-      t[2 * i + 1] = sin(a0 + (double)i * inc);
-    }
+    const std::vector<double> t = laser_unit_vectors(n, angle_min, angle_increment);
     if (n > 0) HIP_TRY(hipMemcpy(h->d_trig, t.data(), (size_t)n * sizeof(double2), hipMemcpyHostToDevice));
     h->trig_kind = 1;
     h->trig_n = n;
@@ -2298,6 +2304,39 @@ static bool is_device_memory(const void* p) {
   return a.type == hipMemoryTypeDevice && !a.isManaged;
 }
 
+// the immutable per-geometry table of the batched conversions (hsm_ctx::RangesGeometry / RangesTfGeometry), keyed on
+// (n, angle_min bits, angle_increment bits): found, or evaluated by `make`, uploaded on `s` and kept until hsm_destroy
+extern "C++" template <class Geometry, class Value, class Make>
+static int ranges_geometry_table(std::vector<Geometry>& geoms, int n, float angle_min, float angle_increment, hipStream_t s,
+                                 const char* who, Make make, const Value** out) {
+  unsigned a0_bits, inc_bits;
+  memcpy(&a0_bits, &angle_min, sizeof a0_bits);
+  memcpy(&inc_bits, &angle_increment, sizeof inc_bits);
+  for (const Geometry& g : geoms)
+    if (g.n == n && g.a0_bits == a0_bits && g.inc_bits == inc_bits) {
+      *out = g.d;
+      return HSM_OK;
+    }
+  // a new table is an allocation and a copy: not while the caller captures the stream into a graph (nothing is enqueued).
+  // The copy goes on the caller's stream, not the null stream, and waits for that stream only
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+    return fail(HSM_ERR_INVALID, (std::string(who) + ": sensor geometry not seen before while the stream is being captured (no "
+                                  "allocation under capture: make one call with this geometry before capturing)").c_str());
+  const auto t = make(n, angle_min, angle_increment);
+  Value* d = nullptr;
+  HIP_TRY(hipMalloc((void**)&d, (size_t)n * sizeof(Value)));
+  hipError_t e = hipMemcpyAsync(d, t.data(), (size_t)n * sizeof(Value), hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);  // (`t` is a host temporary)
+  if (e != hipSuccess) {
+    (void)hipFree(d);
+    return fail(HSM_ERR_HIP, (std::string(who) + ": sensor table upload").c_str(), e);
+  }
+  geoms.push_back({n, a0_bits, inc_bits, d});
+  *out = d;
+  return HSM_OK;
+}
+
 // ranges_on_device: 1 = d_ranges is known to be device memory, -1 = ask the runtime
 static int match_batch_ranges_nolock(hsm_ctx* h, int batch, const float* d_begin_world, const float* d_ranges, int n,
                                      float angle_min, float angle_increment, float range_min, float range_max,
@@ -2315,32 +2354,10 @@ static int match_batch_ranges_nolock(hsm_ctx* h, int batch, const float* d_begin
   if (int rc = select_device(h)) return rc;
   hipStream_t s = (hipStream_t)stream;
   const float2* trig = nullptr;
-  if (n > 0) {
-    unsigned a0_bits, inc_bits;
-    memcpy(&a0_bits, &angle_min, sizeof a0_bits);
-    memcpy(&inc_bits, &angle_increment, sizeof inc_bits);
-    for (const hsm_ctx::RangesGeometry& g : h->ranges_geoms)
-      if (g.n == n && g.a0_bits == a0_bits && g.inc_bits == inc_bits) trig = g.d;
-    if (!trig) {
-      // a new table is an allocation and a copy: not while the caller captures the stream into a graph (nothing is enqueued).
-      // The copy goes on the caller's stream, not the null stream, and waits for that stream only
-      hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-      if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-        return fail(HSM_ERR_INVALID, "hsm_match_batch_ranges_device: sensor geometry not seen before while the stream is being "
-                                     "captured (no allocation under capture: make one call with this geometry before capturing)");
-      const std::vector<float> t = node_scan_trig(n, angle_min, angle_increment);
-      float2* d = nullptr;
-      HIP_TRY(hipMalloc((void**)&d, (size_t)n * sizeof(float2)));
-      hipError_t e = hipMemcpyAsync(d, t.data(), (size_t)n * sizeof(float2), hipMemcpyHostToDevice, s);
-      if (e == hipSuccess) e = hipStreamSynchronize(s);  // (`t` is a host temporary)
-      if (e != hipSuccess) {
-        (void)hipFree(d);
-        return fail(HSM_ERR_HIP, "hsm_match_batch_ranges_device: sensor table upload", e);
-      }
-      h->ranges_geoms.push_back({n, a0_bits, inc_bits, d});
-      trig = d;
-    }
-  }
+  if (n > 0)
+    if (int rc = ranges_geometry_table(h->ranges_geoms, n, angle_min, angle_increment, s, "hsm_match_batch_ranges_device",
+                                       node_scan_trig, &trig))
+      return rc;
   char* ws = (char*)d_workspace;
   int* counts = reinterpret_cast<int*>(ws + L.counts);
   int* offsets = reinterpret_cast<int*>(ws + L.offsets);
@@ -2412,6 +2429,133 @@ int hsm_match_batch_ranges(hsm_ctx* h, int batch, const float* begin_world, cons
   HIP_TRY(hipMemcpyAsync(out_pose, d_pose, b_begin, hipMemcpyDeviceToHost, h->stream));
   if (out_cov) HIP_TRY(hipMemcpyAsync(out_cov, d_cov, b_cov, hipMemcpyDeviceToHost, h->stream));
   if (out_counts) HIP_TRY(hipMemcpyAsync(out_counts, d_counts, b_counts, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return HSM_OK;
+}
+
+// ---- B raw scans and a transform per scan through the node's tf path: the CSR container of the batched entries ----
+
+// the context's part, under its lock: the device and the unit-vector table of the geometry (nullptr for n == 0)
+static int ranges_tf_unit_table(hsm_ctx* h, const char* who, int n, float angle_min, float angle_increment, hipStream_t s,
+                                const double2** unit) {
+  *unit = nullptr;
+  if (int rc = select_device(h)) return rc;
+  if (n == 0) return HSM_OK;
+  return ranges_geometry_table(h->ranges_tf_geoms, n, angle_min, angle_increment, s, who, laser_unit_vectors, unit);
+}
+
+// the three launches on `s`; they read nothing of the context
+static int launch_ingest_batch_ranges_tf(const double2* unit, int batch, const float* d_ranges, int n, float range_min,
+                                         float range_max, double range_cutoff, const double* d_tf_rows, int shared_tf,
+                                         float sqr_laser_min_dist, float sqr_laser_max_dist, float laser_z_min,
+                                         float laser_z_max, float scale_to_map, float* d_out_pts_xy, int* d_out_offsets,
+                                         int* d_out_counts, float* d_out_origo, hipStream_t s) {
+  RangesTfParams P{};
+  P.ranges = d_ranges;
+  P.unit = unit;
+  P.tf_rows = d_tf_rows;
+  P.batch = batch;
+  P.n = n;
+  P.shared_tf = shared_tf != 0;
+  P.range_min = range_min;
+  P.range_cutoff = range_cutoff < 0 ? (double)range_max : range_cutoff;
+  P.G = {sqr_laser_min_dist, sqr_laser_max_dist, laser_z_min, laser_z_max, scale_to_map};
+  const int blocks = (batch - 1) / kRangesScansPerBlock + 1;
+  hipLaunchKernelGGL(ranges_tf_gate_count_kernel, dim3(blocks), dim3(256), 0, s, P, d_out_counts,
+                     reinterpret_cast<float2*>(d_out_origo));
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(ranges_offsets_kernel, dim3(1), dim3(1024), 0, s, d_out_counts, batch, d_out_offsets, (int*)nullptr);
+  HIP_TRY(hipGetLastError());
+  if (n > 0) {
+    // (scan b writes below offsets[b] + n <= (b + 1) * n <= batch * n: inside the caller's endpoint array)
+    hipLaunchKernelGGL(ranges_tf_compact_kernel, dim3(blocks), dim3(256), 0, s, P, d_out_offsets,
+                       reinterpret_cast<float2*>(d_out_pts_xy));
+    HIP_TRY(hipGetLastError());
+  }
+  return HSM_OK;
+}
+
+// the argument checks the two entries share (pointers: the device entry's, or the host entry's before staging)
+static int check_batch_ranges_tf(const char* who, int batch, const void* ranges, int n, const void* tf_rows) {
+  if (batch < 0 || n < 0 || (batch > 0 && n > 0 && !ranges) || (batch > 0 && !tf_rows))
+    return fail(HSM_ERR_INVALID, (std::string(who) + ": bad argument").c_str());
+  if (n > HSM_MAX_UPDATE_BEAMS || (size_t)batch * (size_t)n > (size_t)INT_MAX)
+    return fail(HSM_ERR_TOO_LARGE, (std::string(who) + ": n > HSM_MAX_UPDATE_BEAMS or batch * n > INT_MAX").c_str());
+  return HSM_OK;
+}
+
+int hsm_ingest_batch_ranges_tf_device(hsm_ctx* h, int batch, const float* d_ranges, int n, float angle_min,
+                                      float angle_increment, float range_min, float range_max, double range_cutoff,
+                                      const double* d_tf_rows, int shared_tf, float sqr_laser_min_dist,
+                                      float sqr_laser_max_dist, float laser_z_min, float laser_z_max, float scale_to_map,
+                                      float* d_out_pts_xy, int* d_out_offsets, int* d_out_counts, float* d_out_origo,
+                                      void* stream) {
+  static const char who[] = "hsm_ingest_batch_ranges_tf_device";
+  if (!h) return fail(HSM_ERR_INVALID, "null context");
+  if (!d_out_pts_xy || !d_out_offsets || !d_out_counts || ((uintptr_t)d_tf_rows & 7u) != 0)
+    return fail(HSM_ERR_INVALID, "hsm_ingest_batch_ranges_tf_device: bad argument");
+  if (int rc = check_batch_ranges_tf(who, batch, d_ranges, n, d_tf_rows)) return rc;
+  if (batch == 0) return HSM_OK;
+  const hipStream_t s = (hipStream_t)stream;
+  const double2* unit = nullptr;
+  {
+    std::lock_guard<std::mutex> lk(h->mu);  // (for the geometry cache only)
+    if (int rc = ranges_tf_unit_table(h, who, n, angle_min, angle_increment, s, &unit)) return rc;
+  }
+  return launch_ingest_batch_ranges_tf(unit, batch, d_ranges, n, range_min, range_max, range_cutoff, d_tf_rows, shared_tf,
+                                       sqr_laser_min_dist, sqr_laser_max_dist, laser_z_min, laser_z_max, scale_to_map,
+                                       d_out_pts_xy, d_out_offsets, d_out_counts, d_out_origo, s);
+}
+
+int hsm_match_batch_ranges_tf(hsm_ctx* h, int batch, const float* begin_world, const float* ranges, int n, float angle_min,
+                              float angle_increment, float range_min, float range_max, double range_cutoff,
+                              const double* tf_rows, int shared_tf, float sqr_laser_min_dist, float sqr_laser_max_dist,
+                              float laser_z_min, float laser_z_max, float scale_to_map, float* out_pose, float* out_cov,
+                              int* out_counts, float* out_origo) {
+  static const char who[] = "hsm_match_batch_ranges_tf";
+  if (!h) return fail(HSM_ERR_INVALID, "null context");
+  if (!begin_world || !out_pose) return fail(HSM_ERR_INVALID, "hsm_match_batch_ranges_tf: bad argument");
+  if (int rc = check_batch_ranges_tf(who, batch, ranges, n, tf_rows)) return rc;
+  if (batch == 0) return HSM_OK;
+  const size_t bn = (size_t)batch * n;
+  const size_t b_begin = (size_t)batch * 3 * sizeof(float), b_cov = (size_t)batch * 9 * sizeof(float);
+  const size_t b_counts = (size_t)batch * sizeof(int), b_ranges = bn * sizeof(float);
+  const size_t b_tf = (shared_tf ? 1 : (size_t)batch) * 12 * sizeof(double), b_origo = (size_t)batch * 2 * sizeof(float);
+  // device block: transforms | start poses | poses | covariances | counts | origos | offsets | raw ranges | endpoints
+  Carver c;
+  const size_t o_tf = c.take(b_tf), o_begin = c.take(b_begin), o_pose = c.take(b_begin), o_cov = c.take(b_cov);
+  const size_t o_counts = c.take(b_counts), o_origo = c.take(b_origo), o_offs = c.take(b_counts + sizeof(int));
+  const size_t o_ranges = c.take(b_ranges), o_pts = c.take((bn > 0 ? bn : 1) * 2 * sizeof(float));
+  std::lock_guard<std::mutex> lk(h->mu);
+  const double2* unit = nullptr;
+  if (int rc = ranges_tf_unit_table(h, who, n, angle_min, angle_increment, h->stream, &unit)) return rc;
+  if (!h->d_rbatch.holds(c.total())) HIP_TRY(hipStreamSynchronize(h->stream));
+  if (int rc = h->d_rbatch.reserve(c.total())) return rc;
+  char* base = h->d_rbatch;
+  double* d_tf = (double*)(base + o_tf);
+  float* d_begin = (float*)(base + o_begin);
+  float* d_pose = (float*)(base + o_pose);
+  float* d_cov = (float*)(base + o_cov);
+  int* d_counts = (int*)(base + o_counts);
+  float* d_origo = (float*)(base + o_origo);
+  int* d_offs = (int*)(base + o_offs);
+  float* d_ranges = (float*)(base + o_ranges);
+  float* d_pts = (float*)(base + o_pts);
+  HIP_TRY(hipMemcpyAsync(d_tf, tf_rows, b_tf, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(d_begin, begin_world, b_begin, hipMemcpyHostToDevice, h->stream));
+  if (b_ranges) HIP_TRY(hipMemcpyAsync(d_ranges, ranges, b_ranges, hipMemcpyHostToDevice, h->stream));
+  if (out_cov) HIP_TRY(hipMemcpyAsync(d_cov, out_cov, b_cov, hipMemcpyHostToDevice, h->stream));  // in/out (empty scans)
+  if (int rc = launch_ingest_batch_ranges_tf(unit, batch, d_ranges, n, range_min, range_max, range_cutoff, d_tf, shared_tf,
+                                             sqr_laser_min_dist, sqr_laser_max_dist, laser_z_min, laser_z_max, scale_to_map,
+                                             d_pts, d_offs, d_counts, out_origo ? d_origo : nullptr, h->stream))
+    return rc;
+  // n is a true bound of every scan's length after the gates
+  if (int rc = match_batch_device_nolock(h, batch, d_begin, d_pts, d_offs, n, d_pose, out_cov ? d_cov : nullptr, h->stream, n))
+    return rc;
+  HIP_TRY(hipMemcpyAsync(out_pose, d_pose, b_begin, hipMemcpyDeviceToHost, h->stream));
+  if (out_cov) HIP_TRY(hipMemcpyAsync(out_cov, d_cov, b_cov, hipMemcpyDeviceToHost, h->stream));
+  if (out_counts) HIP_TRY(hipMemcpyAsync(out_counts, d_counts, b_counts, hipMemcpyDeviceToHost, h->stream));
+  if (out_origo) HIP_TRY(hipMemcpyAsync(out_origo, d_origo, b_origo, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   return HSM_OK;
 }

@@ -243,6 +243,13 @@ struct hsm_ctx {
     float2* d;
   };
   std::vector<RangesGeometry> ranges_geoms;
+  // the same for hsm_ingest_batch_ranges_tf_device / hsm_match_batch_ranges_tf: laser_geometry's double2 unit vectors
+  struct RangesTfGeometry {
+    int n;
+    unsigned a0_bits, inc_bits;
+    double2* d;
+  };
+  std::vector<RangesTfGeometry> ranges_tf_geoms;
   Buf<char> d_rbatch{&bufs};  // hsm_match_batch_ranges: start poses, results, counts and the workspace of its device call
   Buf<signed char> d_occ{&bufs};    // occupancy export staging
   unsigned coop_bar_base = 0;   // value the grid-barrier counter has when the next cooperative launch starts

@@ -1301,10 +1301,42 @@ struct CloudIngestParams {
   int* out_n;
 };
 
+// One beam of the tf path, the only statement of its arithmetic: the single-scan kernel and both passes of the batched
+// conversion call these two, so a count and a compaction cannot disagree and the entries cannot drift apart.  The fp64
+// products and sums stay separate operations (the build sets -ffp-contract=off: no FMA), in the node's order.
+// projectLaser: point = float((double)range * unit), kept when range < range_cutoff (double compare) && range >= range_min
+__device__ __forceinline__ bool project_laser_beam(float range, double2 unit, float range_min, double range_cutoff,
+                                                   float* px, float* py) {
+  const double r = (double)range;
+  *px = (float)(r * unit.x);
+  *py = (float)(r * unit.y);
+  return ((double)range < range_cutoff) && (range >= range_min);
+}
+
+struct CloudGates {
+  float sqr_min, sqr_max, z_min, z_max, scale;
+};
+
+// rosPointCloudToDataContainer's loop body (:519-540): true = the point is kept, *e = its endpoint.  T: rows [R | t]
+__device__ __forceinline__ bool cloud_point_endpoint(float px, float py, float pz, const double* __restrict__ T,
+                                                     const CloudGates& G, float2* e) {
+  const float dist_sqr = px * px + py * py;
+  if (!((dist_sqr > G.sqr_min) && (dist_sqr < G.sqr_max)) || ((px < 0.0f) && (dist_sqr < 0.50f))) return false;
+  const double vx = px, vy = py, vz = pz;
+  const double bx = (T[0] * vx + T[1] * vy + T[2] * vz) + T[3];
+  const double by = (T[4] * vx + T[5] * vy + T[6] * vz) + T[7];
+  const double bz = (T[8] * vx + T[9] * vy + T[10] * vz) + T[11];
+  const float zl = (float)(bz - T[11]);
+  if (!(zl > G.z_min && zl < G.z_max)) return false;
+  *e = make_float2((float)bx * G.scale, (float)by * G.scale);
+  return true;
+}
+
 __global__ void __launch_bounds__(1024) ingest_point_cloud_kernel(CloudIngestParams P) {
   __shared__ int wave_count[16];
   __shared__ int base;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const CloudGates G{P.sqr_min, P.sqr_max, P.z_min, P.z_max, P.scale};
   if (threadIdx.x == 0) base = 0;
   __syncthreads();
   for (int i0 = 0; i0 < P.n; i0 += 1024) {
@@ -1315,30 +1347,14 @@ __global__ void __launch_bounds__(1024) ingest_point_cloud_kernel(CloudIngestPar
       float px, py, pz;
       bool valid = true;
       if (P.ranges) {
-        const float range = P.ranges[i];
-        const double r = (double)range;
-        const double2 u = P.unit[i];
-        px = (float)(r * u.x);
-        py = (float)(r * u.y);
+        valid = project_laser_beam(P.ranges[i], P.unit[i], P.range_min, P.range_cutoff, &px, &py);
         pz = 0.0f;
-        valid = ((double)range < P.range_cutoff) && (range >= P.range_min);
       } else {
         px = P.pts_xyz[3 * (size_t)i];
         py = P.pts_xyz[3 * (size_t)i + 1];
         pz = P.pts_xyz[3 * (size_t)i + 2];
       }
-      const float dist_sqr = px * px + py * py;
-      if (valid && (dist_sqr > P.sqr_min) && (dist_sqr < P.sqr_max) && !((px < 0.0f) && (dist_sqr < 0.50f))) {
-        const double vx = px, vy = py, vz = pz;
-        const double bx = (P.T[0] * vx + P.T[1] * vy + P.T[2] * vz) + P.T[3];
-        const double by = (P.T[4] * vx + P.T[5] * vy + P.T[6] * vz) + P.T[7];
-        const double bz = (P.T[8] * vx + P.T[9] * vy + P.T[10] * vz) + P.T[11];
-        const float zl = (float)(bz - P.T[11]);
-        if (zl > P.z_min && zl < P.z_max) {
-          keep = true;
-          e = make_float2((float)bx * P.scale, (float)by * P.scale);
-        }
-      }
+      keep = valid && cloud_point_endpoint(px, py, pz, P.T, G, &e);
     }
     const unsigned long long m = __ballot(keep);
     if (lane == 0) wave_count[wave] = __popcll(m);
@@ -1355,6 +1371,81 @@ __global__ void __launch_bounds__(1024) ingest_point_cloud_kernel(CloudIngestPar
     __syncthreads();
   }
   if (threadIdx.x == 0) *P.out_n = base;
+}
+
+// The tf path for B scans of one sensor geometry (hsm_ingest_batch_ranges_tf_device): ranges[b * n + i] and a transform per
+// scan -> the CSR container of the batched entries, in the three-launch shape of the ranges_* kernels above.
+//   gate/count  one wavefront per scan: counts[b] = kept beams; lane 0 also writes the scan's origo (:517)
+//   offsets     ranges_offsets_kernel
+//   compact     one wavefront per scan: the kept beams in beam order at offsets[b] + rank
+// Both passes evaluate ranges_tf_beam, i.e. the two functions above; the second pass recomputes ~20 fp64 operations per beam
+// instead of reading back a staged 8 B per beam.  The twelve transform values of a scan are wave-uniform: the scan index is
+// made scalar, so they are fetched once per wavefront through the scalar cache and stay in SGPRs.
+struct RangesTfParams {
+  const float* ranges;    // [batch * n]
+  const double2* unit;    // [n] (cos, sin)(angle_min + (double)i * angle_increment)
+  const double* tf_rows;  // [batch][12], or [12] with shared_tf
+  int batch, n, shared_tf;
+  float range_min;
+  double range_cutoff;
+  CloudGates G;
+};
+
+__device__ __forceinline__ long long ranges_tf_scan_index() {  // wave-uniform, no int overflow for batch near INT_MAX
+  return (long long)blockIdx.x * kRangesScansPerBlock + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+}
+
+__device__ __forceinline__ void ranges_tf_load_rows(const RangesTfParams& P, long long b, double (&T)[12]) {
+  const double* __restrict__ t = P.tf_rows + (P.shared_tf ? (size_t)0 : (size_t)b * 12);
+#pragma unroll
+  for (int k = 0; k < 12; ++k) T[k] = t[k];
+}
+
+__device__ __forceinline__ bool ranges_tf_beam(const RangesTfParams& P, const float* __restrict__ r, int i,
+                                               const double (&T)[12], float2* e) {
+  if (i >= P.n) return false;
+  float px, py;
+  const bool valid = project_laser_beam(r[i], P.unit[i], P.range_min, P.range_cutoff, &px, &py);
+  return valid && cloud_point_endpoint(px, py, 0.0f, T, P.G, e);
+}
+
+__global__ void __launch_bounds__(256) ranges_tf_gate_count_kernel(const RangesTfParams P, int* __restrict__ counts,
+                                                                    float2* __restrict__ out_origo) {
+  const int lane = threadIdx.x & 63;
+  const long long b = ranges_tf_scan_index();
+  if (b >= P.batch) return;  // (uniform per wavefront)
+  double T[12];
+  ranges_tf_load_rows(P, b, T);
+  const float* __restrict__ r = P.ranges + (size_t)b * P.n;
+  int c = 0;
+  for (int i0 = 0; i0 < P.n; i0 += 64) {
+    float2 e;
+    c += __popcll(__ballot(ranges_tf_beam(P, r, i0 + lane, T, &e)));
+  }
+  if (lane == 0) {
+    counts[b] = c;
+    // dataContainer.setOrigo(Eigen::Vector2f(laserPos.x(), laserPos.y()) * scaleToMap)  (:517)
+    if (out_origo != nullptr) out_origo[b] = make_float2((float)T[3] * P.G.scale, (float)T[7] * P.G.scale);
+  }
+}
+
+__global__ void __launch_bounds__(256) ranges_tf_compact_kernel(const RangesTfParams P, const int* __restrict__ offsets,
+                                                                 float2* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const long long b = ranges_tf_scan_index();
+  if (b >= P.batch) return;
+  double T[12];
+  ranges_tf_load_rows(P, b, T);
+  const float* __restrict__ r = P.ranges + (size_t)b * P.n;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  int pos = offsets[b];  // (<= b * n: every count is at most n, so scan b stays below (b + 1) * n <= batch * n)
+  for (int i0 = 0; i0 < P.n; i0 += 64) {
+    float2 e;
+    const bool keep = ranges_tf_beam(P, r, i0 + lane, T, &e);
+    const unsigned long long m = __ballot(keep);
+    if (keep) out[pos + __popcll(m & below)] = e;
+    pos += __popcll(m);
+  }
 }
 
 // device expf / getGridProbability sweep for the parity tests

@@ -149,6 +149,69 @@ def ranges_to_csr(ranges: np.ndarray, angle_min: float, angle_increment: float, 
     return counts, offsets, pts
 
 
+@functools.lru_cache(maxsize=16)
+def _laser_units(n: int, a0_bits: int, inc_bits: int) -> np.ndarray:
+    a0, inc = (float(v) for v in np.array([a0_bits, inc_bits], np.uint32).view(np.float32))  # float -> double is exact
+    t = np.empty((n, 2), np.float64)
+    for i in range(n):
+        a = a0 + float(i) * inc  # fp64: a product, then a sum
+        t[i] = math.cos(a), math.sin(a)
+    t.setflags(write=False)
+    return t
+
+
+def laser_unit_vectors(n: int, angle_min: float, angle_increment: float) -> np.ndarray:
+    """laser_geometry's unit vectors: the C library's double cos / sin of angle_min + (double)i * angle_increment, the float
+    geometry widened to double; one math.cos / math.sin call per element (numpy's vectorised ones need not give the same
+    bits); [n, 2] float64, read-only"""
+    bits = np.array([angle_min, angle_increment], np.float32).view(np.uint32)
+    return _laser_units(int(n), int(bits[0]), int(bits[1]))
+
+
+def ranges_tf_to_csr(ranges: np.ndarray, angle_min: float, angle_increment: float, range_min: float, range_max: float,
+                     range_cutoff: float, tf_rows: np.ndarray, sqr_laser_min_dist: float, sqr_laser_max_dist: float,
+                     laser_z_min: float, laser_z_max: float, scale_to_map: float):
+    """The node's default ingestion (projectLaser, the laser -> base transform, rosPointCloudToDataContainer,
+    HectorMappingRos.cpp:257-282,509-542) for B scans of one geometry, ranges [B, n]; tf_rows [B, 12] float64 rows [R | t] per
+    scan, or [12] for every scan.  Returns (counts [B] int32, offsets [B + 1] int32, endpoints [total, 2] float32 in level-0
+    cell units, each scan's kept beams in beam order, origos [B, 2] float32).  Per beam, with the types the node has:
+      point   = float32(float64(range) * unit)               z = 0
+      valid   = float64(range) < cutoff and range >= range_min          (cutoff < 0 means range_max)
+      dist2   = x * x + y * y in float32, kept in (sqr_min, sqr_max) and not (x < 0 and dist2 < 0.5)
+      base    = (T0 * x + T1 * y + T2 * z) + T3 per row in float64, every product and sum rounded on its own
+      z gate  = float32(base_z - T11) in (z_min, z_max)
+      out     = float32(base_x) * scale, float32(base_y) * scale;   origo = float32(T3) * scale, float32(T7) * scale"""
+    f32, f64 = np.float32, np.float64
+    r = np.ascontiguousarray(ranges, f32)
+    B, n = r.shape
+    T = np.ascontiguousarray(tf_rows, f64)
+    T = np.broadcast_to(T, (B, 12)) if T.ndim == 1 else T.reshape(B, 12)
+    cutoff = f64(range_max if range_cutoff < 0 else range_cutoff)
+    u = laser_unit_vectors(n, angle_min, angle_increment)
+    scale = f32(scale_to_map)
+    with np.errstate(invalid="ignore", over="ignore"):
+        rd = r.astype(f64)
+        x, y = (rd * u[:, 0]).astype(f32), (rd * u[:, 1]).astype(f32)
+        keep = (rd < cutoff) & (r >= f32(range_min))
+        d2 = x * x + y * y
+        keep &= (d2 > f32(sqr_laser_min_dist)) & (d2 < f32(sqr_laser_max_dist)) & ~((x < f32(0)) & (d2 < f32(0.5)))
+        vx, vy, vz = x.astype(f64), y.astype(f64), np.zeros((B, n), f64)
+        t = [T[:, k:k + 1] for k in range(12)]
+        bx = ((t[0] * vx + t[1] * vy) + t[2] * vz) + t[3]
+        by = ((t[4] * vx + t[5] * vy) + t[6] * vz) + t[7]
+        bz = ((t[8] * vx + t[9] * vy) + t[10] * vz) + t[11]
+        zl = (bz - t[11]).astype(f32)
+        keep &= (zl > f32(laser_z_min)) & (zl < f32(laser_z_max))
+        ex, ey = bx.astype(f32) * scale, by.astype(f32) * scale
+    counts = keep.sum(1).astype(np.int32)
+    offsets = np.zeros(B + 1, np.int32)
+    np.cumsum(counts, out=offsets[1:])
+    rows, beams = np.nonzero(keep)  # row-major: scan by scan, beams in order
+    pts = np.stack([ex[rows, beams], ey[rows, beams]], 1).astype(f32).reshape(-1, 2)
+    origos = np.stack([T[:, 3].astype(f32) * scale, T[:, 7].astype(f32) * scale], 1)
+    return counts, offsets, pts, origos
+
+
 def make_scan(world: World, pose, n_beams: int, scale_to_map: float, rng: np.random.Generator | None,
               noise_sigma: float = 0.01, range_max: float = 30.0, pad_to_full: bool = False) -> np.ndarray:
     """One scan taken at ground-truth ``pose``; returns (n_valid, 2) fp32 endpoints.

@@ -505,6 +505,58 @@ size_t hsm_match_batch_ranges_workspace(int batch, int n);
 int hsm_match_batch_ranges(hsm_ctx* h, int batch, const float* begin_world, const float* ranges, int n,
                            float angle_min, float angle_increment, float range_min, float range_max, float scale_to_map,
                            float* out_pose, float* out_cov, int* out_counts);
+/* replaces: the node's DEFAULT ingestion (use_tf_scan_transformation, HectorMappingRos.cpp:82,:257-282) -- projectLaser,
+ *           the laser -> base_link transform and rosPointCloudToDataContainer (:509-542) -- for B raw scans of ONE sensor
+ *           geometry at once, each with its own transform (extension: the node converts one scan per callback; base_link
+ *           attitude from an IMU changes R every scan).  Per scan the container and its origo are bit for bit what
+ *           hsm_ingest_laser_scan_tf gives: point = float((double)range * (cos, sin)(angle_min + (double)i * angle_increment)),
+ *           kept when range < range_cutoff && range >= range_min (range_cutoff < 0 means range_max); x*x + y*y in
+ *           (sqr_laser_min_dist, sqr_laser_max_dist), x < 0 && dist_sqr < 0.5 dropped; the transform in fp64 without FMA;
+ *           base-frame z minus t_z in (laser_z_min, laser_z_max); endpoint = float(base x, y) * scale_to_map, kept beams in
+ *           beam order.  CONVERSION ONLY: reads no map, touches neither the retained nor the ingested scan.
+ * DEVICE pointers:
+ *   d_ranges       [B*n] LaserScan.ranges[] of scan b at b*n, device-accessible; read once by each of the two passes and not
+ *                  after the call's kernels have run
+ *   d_tf_rows      [B*12] doubles, rows [R | t] of scan b's laser -> base transform at b*12; with shared_tf != 0 one [12] block
+ *                  that every scan uses.  8-byte aligned
+ *   d_out_pts_xy   caller-owned, capacity max(B*n, 1) * 2 floats (the matcher clamps an empty scan's loads to element 0)
+ *   d_out_offsets  [B+1] int32 CSR offsets in points        d_out_counts [B] beams each scan kept; REQUIRED: it is the
+ *                  entry's only scratch
+ *   d_out_origo    [B*2] or NULL: origo of scan b = float(t_x, t_y) * scale_to_map (:517)
+ * The outputs are exactly the d_pts_xy / d_scan_offsets arguments of hsm_match_batch_device, hsm_score_batch_device,
+ * hsm_match_score_batch_device, hsm_update_by_scans_device[_gated] and hsm_slam_scans_device; pass n as shared_n / max_beams,
+ * it is a true bound of every scan's length.
+ * The unit-vector table of the geometry (n, angle_min, angle_increment; keyed on their bit patterns) is evaluated on the host
+ * with the double cos / sin that laser_geometry uses, uploaded once and kept until hsm_destroy.  A geometry not seen before
+ * while `stream` is being captured into a graph returns HSM_ERR_INVALID and enqueues nothing (no allocation under capture: one
+ * call with that geometry before capturing); a new geometry allocates its table, copies it on `stream` and waits for `stream`.
+ * With a known geometry a capture records three kernel launches and nothing is allocated.
+ * `stream` is a hipStream_t (NULL = default stream); the call is asynchronous and ordered by `stream` alone -- it waits for
+ * no map update and none waits for it.  The context lock is held for the geometry cache only.
+ * HSM_ERR_INVALID, nothing launched: NULL context, batch < 0, n < 0, NULL d_ranges with batch*n > 0, NULL d_tf_rows with
+ * batch > 0, NULL d_out_pts_xy / d_out_offsets / d_out_counts, an unseen geometry under capture.  HSM_ERR_TOO_LARGE:
+ * n > HSM_MAX_UPDATE_BEAMS or batch * n > INT_MAX.  batch == 0: HSM_OK, nothing written.
+ * Not built: per-scan origos in the update and slam entries -- they take one HOST origo, so a log whose transform translation
+ * is constant passes d_out_origo[0] (copied to the host) and a caller with a moving sensor mount splits the log; a fused
+ * conversion + match device entry with a workspace (this call and hsm_match_batch_device on one stream are the same
+ * launches); the C++ facade; hsm_group_*. */
+int hsm_ingest_batch_ranges_tf_device(hsm_ctx* h, int batch, const float* d_ranges, int n, float angle_min,
+                                      float angle_increment, float range_min, float range_max, double range_cutoff,
+                                      const double* d_tf_rows, int shared_tf, float sqr_laser_min_dist,
+                                      float sqr_laser_max_dist, float laser_z_min, float laser_z_max, float scale_to_map,
+                                      float* d_out_pts_xy, int* d_out_offsets, int* d_out_counts, float* d_out_origo,
+                                      void* stream);
+/* the same conversion followed by MapRepMultiMap::matchData (HSL/slam_main/MapRepMultiMap.h:116-132) per scan, with HOST
+ * pointers (begin_world [B*3], ranges [B*n], tf_rows [B*12] or [12] with shared_tf, out_pose [B*3], out_cov [B*9] or NULL
+ * (in/out), out_counts [B] or NULL, out_origo [B*2] or NULL): copies 4 B per beam and 96 B per scan in, runs the conversion and
+ * then hsm_match_batch_device's path on the context's stream, copies the results out; synchronous.  The staging block is the
+ * context's own.  The origo plays no part in a match (it is the update's); a scan that keeps no beam returns its start pose
+ * and leaves its covariance untouched (ScanMatcher.h:68,189).  Errors as above, and NULL begin_world / out_pose. */
+int hsm_match_batch_ranges_tf(hsm_ctx* h, int batch, const float* begin_world, const float* ranges, int n, float angle_min,
+                              float angle_increment, float range_min, float range_max, double range_cutoff,
+                              const double* tf_rows, int shared_tf, float sqr_laser_min_dist, float sqr_laser_max_dist,
+                              float laser_z_min, float laser_z_max, float scale_to_map, float* out_pose, float* out_cov,
+                              int* out_counts, float* out_origo);
 /* hsm_match / hsm_update_by_scan on the ingested scan (no endpoint upload; origo as ingested) */
 int hsm_match_ingested(hsm_ctx* h, const float begin_world[3], float out_pose_world[3], float cov[9]);
 int hsm_update_by_ingested(hsm_ctx* h, const float pose_world[3]);

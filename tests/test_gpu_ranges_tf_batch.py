@@ -1,0 +1,339 @@
+"""B raw LaserScans and a transform per scan through the node's default tf path on the device:
+hsm_ingest_batch_ranges_tf_device (device pointers, caller's stream) and hsm_match_batch_ranges_tf (host arrays).  The bar is
+the reference node compiled from its own source -- projectLaser + rosPointCloudToDataContainer per scan
+(`NodeRef.project_and_convert`), matchData on those containers, and scanCallback over a whole log -- bit for bit."""
+import numpy as np
+import pytest
+
+from conftest import bits, make_oracle
+import ranges_tf_cases as tc
+from test_node_rows import laser_scan_messages
+
+pytestmark = pytest.mark.gpu
+
+HSM_OK, HSM_ERR_INVALID, HSM_ERR_TOO_LARGE = 0, -1, -4
+
+
+@pytest.fixture(scope="module")
+def capi():
+    import torch
+    assert torch.cuda.is_available()
+    from hector_slam_amd import capi as m
+    m.load_library()
+    return m
+
+
+@pytest.fixture(scope="module")
+def ctx(capi):
+    g = capi.MapRepMultiMap(0.05, 256, 256, 2)
+    yield g
+    g.close()
+
+
+def dev(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+class Conv:
+    """device buffers of one hsm_ingest_batch_ranges_tf_device call, the outputs filled with sentinels"""
+
+    def __init__(self, ranges, T):
+        import torch
+        self.B, self.n = ranges.shape
+        self.shared = T.ndim == 1
+        self.ranges, self.T = dev(ranges.astype(np.float32)), dev(T.astype(np.float64))
+        self.pts = torch.full((max(self.B * self.n, 1), 2), -5.0, dtype=torch.float32, device="cuda")
+        self.offs = torch.full((self.B + 1,), -3, dtype=torch.int32, device="cuda")
+        self.counts = torch.full((self.B,), -1, dtype=torch.int32, device="cuda")
+        self.origo = torch.full((self.B, 2), -7.0, dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+
+    def launch(self, g, cutoff, ga, scale, stream=None, range_min=tc.RANGE_MIN):
+        import torch
+        s = stream if stream is not None else torch.cuda.current_stream()
+        g.ingest_batch_ranges_tf_device(self.B, self.ranges.data_ptr(), self.n, tc.A0, tc.INC, range_min, tc.RANGE_MAX, cutoff,
+                                        self.T.data_ptr(), self.shared, *ga, scale, self.pts.data_ptr(), self.offs.data_ptr(),
+                                        self.counts.data_ptr(), self.origo.data_ptr(), s.cuda_stream)
+
+    def result(self):
+        import torch
+        torch.cuda.synchronize()
+        return self.counts.cpu().numpy(), self.offs.cpu().numpy(), self.pts.cpu().numpy(), self.origo.cpu().numpy()
+
+    def untouched(self):
+        c, o, p, g = self.result()
+        return (c == -1).all() and (o == -3).all() and (p == -5.0).all() and (g == -7.0).all()
+
+
+def reference(oracle_mod, node, gates, ranges, cutoff, T, scale):
+    """the node per scan where oracle/_ref is built, else the numpy statement test_ranges_tf_batch_abi.py pins to it"""
+    if node is not None:
+        return tc.node_reference(node, ranges, cutoff, T, scale)[:4]
+    from hector_slam_amd import synth
+    print("NOTICE: oracle/_ref not built -- comparing against synth.ranges_tf_to_csr instead of the reference node")
+    return synth.ranges_tf_to_csr(ranges, tc.A0, tc.INC, tc.RANGE_MIN, tc.RANGE_MAX, cutoff, T, *tc.gate_args(gates), scale)
+
+
+def make_node(oracle_mod, gates):
+    return oracle_mod.NodeRef(*gates) if oracle_mod.available("node") else None
+
+
+def assert_container(got, want, what):
+    (gc, go, gp, gg), (wc, wo, wp, wg) = got, want
+    assert np.array_equal(gc, wc), (what, "counts", np.nonzero(gc != wc)[0][:8])
+    assert np.array_equal(go, wo), (what, "offsets")
+    total = int(wo[-1])
+    assert np.array_equal(bits(gp[:total]), bits(wp)), (what, "endpoints")
+    assert np.array_equal(bits(gg), bits(wg)), (what, "origos")
+
+
+# ---- 3: the conversion against the reference node -------------------------------------------------------------------------
+@pytest.mark.parametrize("gates", tc.NODE_GATES, ids=["default gates", "narrow gates"])
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 181, 1081])
+def test_conversion_equals_the_reference_node(capi, ctx, oracle_mod, n, gates):
+    """n around the 64-lane ballot, B around the four-scans-per-workgroup tail (1, 5, 257) and into the second pass of the
+    1024-wide offset scan (1025); a transform per scan and one for all; both cutoffs; inf / NaN / 0 in the ranges, a scan that
+    keeps nothing and one that keeps everything"""
+    node = make_node(oracle_mod, gates)
+    ga = tc.gate_args(gates)
+    scale = ctx.getScaleToMap()
+    rng = np.random.default_rng(1000 + n)
+    for B in (1, 5, 257, 1025):
+        r, per_scan = tc.batch(rng, B, n)
+        for T in (per_scan, tc.rigid_rows(rng)):
+            for cutoff in tc.CUTOFFS:
+                want = reference(oracle_mod, node, gates, r, cutoff, T, scale)
+                d = Conv(r, T)
+                d.launch(ctx, cutoff, ga, scale)
+                got = d.result()
+                assert_container(got, want, (n, B, T.ndim, cutoff))
+                if B > 2:
+                    assert got[0][tc.NOTHING] == 0 and got[0][tc.EVERYTHING] == n
+                assert (got[2][int(want[1][-1]):] == -5.0).all()  # nothing written behind the container
+    if node is not None:
+        node.close()
+
+
+# ---- 4: the single-scan entry ---------------------------------------------------------------------------------------------
+def test_conversion_equals_the_single_scan_entry(capi, ctx):
+    scale = ctx.getScaleToMap()
+    rng = np.random.default_rng(44)
+    ga = tc.gate_args(tc.NODE_GATES[0])
+    for B, n in ((5, 65), (9, 1081)):
+        r, T = tc.batch(rng, B, n)
+        for cutoff in tc.CUTOFFS:
+            d = Conv(r, T)
+            d.launch(ctx, cutoff, ga, scale)
+            counts, offs, pts, origo = d.result()
+            for b in range(B):
+                sp, so = ctx.ingest_laser_scan_tf(r[b], tc.A0, tc.INC, tc.RANGE_MIN, tc.RANGE_MAX, cutoff, T[b], *ga)
+                assert counts[b] == sp.shape[0], (n, cutoff, b)
+                assert np.array_equal(bits(pts[offs[b]:offs[b + 1]]), bits(sp)) and np.array_equal(bits(origo[b]), bits(so)), (n, b)
+            assert 0 < offs[-1] < B * n
+
+
+# ---- 5: conversion, then the batched matcher -------------------------------------------------------------------------------
+def mount_rows(rng):
+    """a sensor mount that moves a little from scan to scan (base_link attitude from an IMU): small roll / pitch / yaw and a
+    few centimetres of shift, 12 doubles [R | t]"""
+    r, p, y = rng.uniform(-0.03, 0.03), rng.uniform(-0.03, 0.03), rng.uniform(-0.02, 0.02)
+    cr, sr, cp, sp, cy, sy = np.cos(r), np.sin(r), np.cos(p), np.sin(p), np.cos(y), np.sin(y)
+    R = np.array([[cy * cp, cy * sp * sr - sy * cr, cy * sp * cr + sy * sr],
+                  [sy * cp, sy * sp * sr + cy * cr, sy * sp * cr - cy * sr],
+                  [-sp, cp * sr, cp * cr]])
+    return np.concatenate([R, rng.uniform(-0.05, 0.05, (3, 1))], 1).reshape(12)
+
+
+def test_match_of_the_converted_batch_equals_the_reference(capi, oracle_mod, pyramid_scene):
+    import torch
+    from hector_slam_amd import synth
+    if not (oracle_mod.available("node") and oracle_mod.available("hr")):
+        pytest.skip("oracle/_ref not built (no reference tree where the suite was built)")
+    sc = pyramid_scene
+    B, n = 257, 1081
+    g = capi.MapRepMultiMap(sc.resolution, sc.map_size, sc.map_size, sc.levels)
+    g.setUpdateFactorFree(0.4)
+    g.setUpdateFactorOccupied(0.9)
+    g.build_map(sc.build_poses, sc.build_scans)
+    o = make_oracle(oracle_mod, "hr", sc)
+    scale = g.getScaleToMap()
+    rng = np.random.default_rng(55)
+    truth = synth.loop_trajectory(sc.world, B, phase=0.37 * 2 * np.pi / 80).astype(np.float32)
+    init = synth.perturb_poses(truth, np.random.default_rng(56))
+    ang = synth.beam_angles(n)
+    a0, inc = float(ang[0]), float(np.float32(synth.SCAN_SHAPES[n][1]))
+    r = (np.stack([sc.world.raycast(p, ang) for p in truth]) + rng.normal(0.0, 0.01, (B, n))).astype(np.float32)
+    drop = rng.random(r.shape)
+    r[drop < 0.02] = np.inf
+    r[(drop >= 0.02) & (drop < 0.03)] = np.nan
+    r[3] = np.inf  # a scan that keeps no beam
+    T = np.stack([mount_rows(rng) for _ in range(B)])
+    node = oracle_mod.NodeRef(*tc.NODE_GATES[0])
+    ga = tc.gate_args(tc.NODE_GATES[0])
+    rp, rc, rn, ro = np.empty((B, 3), np.float32), np.full((B, 9), 7.0, np.float32), np.empty(B, np.int32), np.empty((B, 2), np.float32)
+    for b in range(B):
+        pts, ro[b], _ = node.project_and_convert(r[b], a0, inc, 0.4, 30.0, 30.0, T[b], scale)
+        rn[b] = pts.shape[0]
+        if rn[b]:
+            rp[b], rc[b] = o.match(init[b], pts, ro[b])
+        else:  # ScanMatcher.h:68,189: the start pose, the covariance untouched
+            rp[b] = init[b]
+    assert rn[3] == 0 and (np.delete(rn, 3) > 800).all() and len({tuple(bits(x)) for x in ro}) == B
+    # device: conversion, then hsm_match_batch_device on its outputs, one stream
+    d_r, d_T, d_init = dev(r), dev(T), dev(init)
+    d_pts = torch.empty((B * n, 2), dtype=torch.float32, device="cuda")
+    d_offs = torch.empty(B + 1, dtype=torch.int32, device="cuda")
+    d_counts = torch.empty(B, dtype=torch.int32, device="cuda")
+    d_origo = torch.empty((B, 2), dtype=torch.float32, device="cuda")
+    d_pose = torch.full((B, 3), -9.0, dtype=torch.float32, device="cuda")
+    d_cov = torch.full((B, 9), 7.0, dtype=torch.float32, device="cuda")
+    s = torch.cuda.current_stream().cuda_stream
+    g.ingest_batch_ranges_tf_device(B, d_r.data_ptr(), n, a0, inc, 0.4, 30.0, 30.0, d_T.data_ptr(), False, *ga, scale,
+                                    d_pts.data_ptr(), d_offs.data_ptr(), d_counts.data_ptr(), d_origo.data_ptr(), s)
+    g.match_batch_device(B, d_init.data_ptr(), d_pts.data_ptr(), d_offs.data_ptr(), n, d_pose.data_ptr(), d_cov.data_ptr(), s)
+    torch.cuda.synchronize()
+    pose, cov = d_pose.cpu().numpy(), d_cov.cpu().numpy()
+    assert g.last_launch_config()["parity_effective"] == "exact"
+    assert np.array_equal(d_counts.cpu().numpy(), rn) and np.array_equal(bits(d_origo.cpu().numpy()), bits(ro))
+    assert np.array_equal(bits(pose), bits(rp)), np.nonzero((bits(pose) != bits(rp)).any(1))[0][:8]
+    assert np.array_equal(bits(cov), bits(rc)), np.nonzero((bits(cov) != bits(rc)).any(1))[0][:8]
+    assert np.array_equal(bits(pose[3]), bits(init[3])) and (cov[3] == 7.0).all()
+    assert not np.array_equal(bits(np.delete(pose, 3, 0)), bits(np.delete(init, 3, 0)))
+    # the host entry: the same bits, counts and origos
+    hp, hc, hn, ho = g.match_batch_ranges_tf(init, r, a0, inc, 0.4, 30.0, 30.0, T, *ga, cov=np.full((B, 9), 7.0, np.float32))
+    assert np.array_equal(bits(hp), bits(rp)) and np.array_equal(bits(hc), bits(rc))
+    assert np.array_equal(hn, rn) and np.array_equal(bits(ho), bits(ro))
+    node.close()
+    g.close()
+
+
+# ---- 6: a whole log, the node's default path --------------------------------------------------------------------------------
+def test_whole_log_through_the_tf_path_equals_the_node(capi, oracle_mod):
+    import torch
+    if not oracle_mod.available("node"):
+        pytest.skip("oracle/_ref/libhector_node_ref.so not built (no reference tree where the suite was built)")
+    N = 25
+    scans, a0, inc = laser_scan_messages(N)
+    T = np.array([1, 0, 0, 0.12, 0, 1, 0, -0.05, 0, 0, 1, 0.3], np.float64)
+    node = oracle_mod.NodeRef(map_size=512, levels=3, resolution=0.05, update_dist_thresh=0.05, update_angle_thresh=0.02,
+                              laser_transform=T)
+    rp, rc = np.empty((N, 3), np.float32), np.empty((N, 9), np.float32)
+    for k, r in enumerate(scans):
+        rp[k], rc[k] = node.scan_callback(r, a0, inc, 0.4, 30.0)
+    cells, lo, _ = node.node_map()
+    g = capi.MapRepMultiMap(0.05, 512, 512, 3)
+    g.setUpdateFactorFree(0.4)
+    g.setUpdateFactorOccupied(0.9)
+    g.set_update_gate(0.05, 0.02)
+    n = scans[0].shape[0]
+    d = Conv(np.stack(scans), T)
+    s = torch.cuda.Stream()
+    g.ingest_batch_ranges_tf_device(N, d.ranges.data_ptr(), n, a0, inc, 0.4, 30.0, 30.0, d.T.data_ptr(), True,
+                                    np.float32(node.sqr_min), np.float32(node.sqr_max), -1.0, 1.0, g.getScaleToMap(),
+                                    d.pts.data_ptr(), d.offs.data_ptr(), d.counts.data_ptr(), d.origo.data_ptr(), s.cuda_stream)
+    s.synchronize()
+    origo = d.origo.cpu().numpy()
+    assert (bits(origo) == bits(origo[0])).all() and origo[0, 0] != 0  # one mount for the whole log
+    d_pose = torch.full((N, 3), -777.0, dtype=torch.float32, device="cuda")
+    d_cov = torch.full((N, 9), -777.0, dtype=torch.float32, device="cuda")
+    g.slam_scans_device(N, 0, 0, d.pts.data_ptr(), d.offs.data_ptr(), n, origo[0], 0, d_pose.data_ptr(), d_cov.data_ptr(), 0,
+                        s.cuda_stream)
+    s.synchronize()
+    pose, cov = d_pose.cpu().numpy(), d_cov.cpu().numpy()
+    assert np.array_equal(bits(pose), bits(rp)), np.nonzero((bits(pose) != bits(rp)).any(1))[0][:8]
+    assert np.array_equal(bits(cov), bits(rc)), np.nonzero((bits(cov) != bits(rc)).any(1))[0][:8]
+    g.synchronize()
+    assert np.array_equal(bits(g.download_level(0)[0]), bits(lo))
+    assert np.array_equal(g.occupancy_grid(0), cells) and (cells == 100).sum() > 200
+    print(f"whole log: {N} scans, final pose {pose[-1]}, {(cells == 100).sum()} occupied cells, identical to the node")
+    node.close()
+    g.close()
+
+
+# ---- 7: capture and validation ----------------------------------------------------------------------------------------------
+def test_capture_replays_and_refuses_an_unseen_geometry(capi, ctx):
+    import torch
+    scale = ctx.getScaleToMap()
+    rng = np.random.default_rng(77)
+    ga = tc.gate_args(tc.NODE_GATES[0])
+    B, n = 37, 181
+    r, T = tc.batch(rng, B, n)
+    r2 = tc.batch(rng, B, n)[0]
+    s = torch.cuda.Stream()
+    d = Conv(r, T)
+    d.launch(ctx, 30.0, ga, scale, s)  # eager: the geometry is known from here on
+    eager = d.result()
+    e = Conv(r2, T)
+    e.launch(ctx, 30.0, ga, scale, s)
+    eager2 = e.result()
+    assert not np.array_equal(eager[0], eager2[0])
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, stream=s):
+        d.launch(ctx, 30.0, ga, scale, s)
+    for ranges, want in ((r, eager), (r2, eager2), (r, eager)):  # the ranges buffer rewritten between replays
+        d.ranges.copy_(torch.from_numpy(ranges))
+        d.pts.fill_(-5.0)
+        d.offs.fill_(-3)
+        d.counts.fill_(-1)
+        d.origo.fill_(-7.0)
+        torch.cuda.synchronize()
+        graph.replay()
+        got = d.result()
+        assert all(np.array_equal(x.view(np.uint32), y.view(np.uint32)) for x, y in zip(got, want))
+    # a geometry not seen before, during a capture: refused, nothing recorded, the capture ends cleanly
+    new = Conv(tc.batch(rng, B, 900)[0], T)  # (no other call on this context uses 900 beams)
+    graph2 = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph2, stream=s):
+        rc = ctx._lib.hsm_ingest_batch_ranges_tf_device(ctx._h, B, new.ranges.data_ptr(), 900, tc.A0, tc.INC, tc.RANGE_MIN,
+                                                        tc.RANGE_MAX, 30.0, new.T.data_ptr(), 0, *ga, scale, new.pts.data_ptr(),
+                                                        new.offs.data_ptr(), new.counts.data_ptr(), new.origo.data_ptr(),
+                                                        s.cuda_stream)
+        msg = ctx._lib.hsm_last_error().decode()
+        d.launch(ctx, 30.0, ga, scale, s)
+    assert rc == HSM_ERR_INVALID and "captur" in msg, (rc, msg)
+    d.counts.fill_(-1)
+    torch.cuda.synchronize()
+    graph2.replay()
+    assert np.array_equal(d.result()[0], eager[0]) and new.untouched()
+
+
+def test_validation_leaves_outputs_untouched(capi, ctx):
+    import torch
+    scale = ctx.getScaleToMap()
+    rng = np.random.default_rng(78)
+    ga = tc.gate_args(tc.NODE_GATES[0])
+    r, T = tc.batch(rng, 4, 181)
+    d = Conv(r, T)
+    lib, s = ctx._lib, torch.cuda.current_stream().cuda_stream
+    null = object()
+
+    def call(batch=4, n=181, h=ctx._h, ranges=None, tf=None, pts=None, offs=None, counts=None):
+        p = lambda v, t: None if v is null else (t.data_ptr() if v is None else v)  # noqa: E731
+        return lib.hsm_ingest_batch_ranges_tf_device(h, batch, p(ranges, d.ranges), n, tc.A0, tc.INC, tc.RANGE_MIN, tc.RANGE_MAX, 30.0,
+                                                     p(tf, d.T), 0, *ga, scale, p(pts, d.pts), p(offs, d.offs), p(counts, d.counts),
+                                                     d.origo.data_ptr(), s)
+
+    assert call(h=None) == HSM_ERR_INVALID
+    assert call(batch=-1) == HSM_ERR_INVALID and call(n=-1) == HSM_ERR_INVALID
+    assert call(ranges=null) == HSM_ERR_INVALID and call(tf=null) == HSM_ERR_INVALID
+    assert call(pts=null) == HSM_ERR_INVALID and call(offs=null) == HSM_ERR_INVALID and call(counts=null) == HSM_ERR_INVALID
+    assert call(batch=4096, n=1048575) == HSM_ERR_TOO_LARGE   # B * n > INT_MAX
+    assert call(batch=1, n=1048576) == HSM_ERR_TOO_LARGE      # n > HSM_MAX_UPDATE_BEAMS
+    assert d.untouched()
+    assert call(batch=0) == HSM_OK and call(batch=0, ranges=null, tf=null) == HSM_OK
+    assert d.untouched()
+    assert call(n=0, ranges=null) == HSM_OK  # scans without beams: counts 0, offsets 0, the origos written
+    c, o, p, og = d.result()
+    assert (c == 0).all() and (o == 0).all() and (p == -5.0).all() and (og != -7.0).all()
+    d.launch(ctx, 30.0, ga, scale)  # the same buffers in a valid call
+    assert (d.result()[0][[0, 3]] > 0).all()
+    # the host entry refuses the same way and writes nothing
+    pose = np.full((4, 3), -9.0, np.float32)
+    init = np.zeros((4, 3), np.float32)
+    host = lambda batch, n, rp, tp: lib.hsm_match_batch_ranges_tf(ctx._h, batch, init.ctypes.data, rp, n, tc.A0, tc.INC, 0.1, 30.0,  # noqa: E731
+                                                                   30.0, tp, 0, *ga, scale, pose.ctypes.data, None, None, None)
+    assert host(4, 181, None, T.ctypes.data) == HSM_ERR_INVALID and host(4, 181, r.ctypes.data, None) == HSM_ERR_INVALID
+    assert host(-1, 181, r.ctypes.data, T.ctypes.data) == HSM_ERR_INVALID
+    assert host(1, 1048576, r.ctypes.data, T.ctypes.data) == HSM_ERR_TOO_LARGE
+    assert host(0, 181, None, None) == HSM_OK and (pose == -9.0).all()
