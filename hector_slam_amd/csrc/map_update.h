@@ -392,6 +392,8 @@ __device__ __forceinline__ void apply_box(const UpdateParams& P, size_t first, s
     int stamp;
     if (occ) {
       // free-touched by an earlier beam of this scan: applied, then reverted (:231-233)
+      // (in fp32 (l + f) - f == l unless l + f leaves l's binade, so this comparison shows in the bits only for cells just above
+      // -2, -4, -8 ...: tests/test_gpu_update_order.py puts cells there and runs scans in several beam orders)
       if (fre && (kBeamMask - (kf & kBeamMask)) < (kBeamMask - (ko & kBeamMask))) {
         l += P.log_odds_free;
         l -= P.log_odds_free;
@@ -659,6 +661,8 @@ __global__ void __launch_bounds__(256) update_apply_dense_kernel(const UpdateBat
       float lo = l[i];
       int stamp;
       if (is_occ) {
+        // crossed by a beam of lower index than the first that ends here: applied, then reverted (:231-233).  Visible in the bits
+        // only where lo + f leaves lo's binade (cells just above -2, -4, -8 ...): tests/test_gpu_update_order.py
         if (is_fre && (kBeamMask - (kf[i] & kBeamMask)) < (kBeamMask - (ko[i] & kBeamMask))) {
           lo += P.log_odds_free;
           lo -= P.log_odds_free;
