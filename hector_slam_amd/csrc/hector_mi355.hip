@@ -205,23 +205,6 @@ void free_level(Level& L, TeardownLog* log = nullptr) {
   L = Level();
 }
 
-// waves per scan: enough wavefronts to fill 256 CUs x 4 SIMDs x several waves, but never
-// more lanes than beams
-int choose_wps(const hsm_ctx* h, int batch, int max_n) {
-  if (h->wps_override > 0) return h->wps_override;
-  int wps = 1;
-  const long target_waves = (long)h->compute_units * 4 * 4;  // 4 waves per SIMD on every CU of THIS device (a partitioned device has fewer)
-  while (wps < 16 && (long)batch * wps < target_waves && 64 * wps < max_n) wps *= 2;
-  // ... but keep about five beams per lane: every extra wavefront adds LDS staging + a barrier to each
-  // of the 14 dependent GN steps, which costs more than the beam loop saves (single 1081-beam scan on
-  // MI355X: 72 / 58 / 53 / 61 / 79 us for 1 / 2 / 4 / 8 / 16 waves, profiles/r01/README.md)
-  int lat = 1;
-  while (lat < 16 && 64 * 5 * lat < max_n) lat *= 2;
-  return wps < lat ? wps : lat;
-}
-
-
-
 // HSM_PARITY_AUTO (the default): EVERY match -- batched, single scan, dense scan, and the likelihood / covariance / Hessian
 // entry points -- takes the reference's summation order: bit-identical to the reference CPU matcher on every entry point.
 // History: round 3 chose exact order only on maps of more than 2^23 cells (a rule fitted to BASELINE's own scenes); round 4's scene
@@ -231,122 +214,136 @@ int choose_wps(const hsm_ctx* h, int batch, int max_n) {
 // of 256 scans per family, of which the corridor family already failed (0.83 within 1e-4 m).  Round 5: the same argument holds for
 // one scan as for 4096, so the default does not try there either.  HSM_PARITY_FAST / _RELAXED stay opt-in for callers who trade
 // the guarantee for speed (profiles/r05/README.md has the prices: batch +34 % / +45 %, single 1081-beam scan ~35 vs ~95 us).
-// AUTO and HSM_PARITY_EXACT launch the same kernels today (launch_match treats them alike); the distinction kept in the API is one of
-// contract: AUTO promises the reference's BITS by whatever form delivers them, EXACT names the reference's order of additions.
-bool auto_wants_exact(const hsm_ctx* h, const MatchParams&) { return h->auto_parity; }
-// the effective summation order of the entry points that do not go through launch_match (staging decisions, likelihood,
-// covariance, Hessian probes)
+// AUTO and HSM_PARITY_EXACT launch the same kernels today; the distinction kept in the API is one of contract: AUTO promises the
+// reference's BITS by whatever form delivers them, EXACT names the reference's order of additions.
+// The effective order is an INPUT of the plan (MatchSite::exact) -- the context's flags are never changed by a launch
+// (hsm_parity() reads them without the mutex) -- and is recorded for hsm_last_launch_parity().
 bool wants_exact(const hsm_ctx* h) { return h->exact || h->auto_parity; }
 
+static_assert(hsm_plan::kQuad == kLayoutQuad && hsm_plan::kPlane == kLayoutPlane && hsm_plan::kExactGroupRounds == kExactGroupRounds &&
+                  hsm_plan::kDenseRound == kDenseRound && hsm_plan::kSpec1MaxBeams == kSpec1MaxBeams,
+              "match_plan.h restates gn_match.h / gn_match_spec.h");
+static_assert(hsm_plan::kParityFast == HSM_PARITY_FAST && hsm_plan::kParityExact == HSM_PARITY_EXACT && hsm_plan::kParityRelaxed == HSM_PARITY_RELAXED,
+              "match_plan.h restates capi.h");
 
-int launch_match_mode(hsm_ctx* h, const MatchParams& P, int max_n, hipStream_t stream, bool exact);
+using hsm_plan::Family;
+using hsm_plan::MatchSite;
+using hsm_plan::plan_match;
 
-// HSM_PARITY_AUTO: which launches take the reference's summation order (see auto_wants_exact).  The effective mode is an
-// ARGUMENT of the launch helpers -- the context's flags are never changed by a launch (hsm_parity() reads them without the
-// mutex) -- and is recorded for hsm_last_launch_parity().
-int launch_match(hsm_ctx* h, const MatchParams& P, int max_n, hipStream_t stream) {
-  const bool exact = h->exact || auto_wants_exact(h, P);
-  h->last_sorted = false;  // (the forms that take a permuted batch set it: ensure_batch_perm)
-  const int rc = launch_match_mode(h, P, max_n, stream, exact);
-  h->last_parity = exact ? HSM_PARITY_EXACT : (h->relaxed ? HSM_PARITY_RELAXED : HSM_PARITY_FAST);
-  return rc;
+// the site of a match launch (match_plan.h): the context's knobs and the call's shape.  The staging of a single scan and its
+// launch both come here, so that they plan the same form.  `stream`: only the opt-in speculative-carry form asks whether it is
+// being captured, so nobody else pays for the question.
+MatchSite match_site(const hsm_ctx* h, int batch, int max_n, int n_bound, bool batched, bool trace, hipStream_t stream) {
+  MatchSite s;
+  s.batch = batch, s.max_n = max_n, s.n_bound = n_bound;
+  s.exact = wants_exact(h), s.relaxed = h->relaxed, s.layout = h->layout;
+  s.batched = batched, s.trace = trace, s.clock_probe = h->clock_probe != nullptr;
+  s.capturing = h->exact_spec && stream_capturing(stream);
+  s.compute_units = h->compute_units, s.level0_cells = h->levels[0].cells();
+  s.wps_override = h->wps_override, s.bpl_override = h->bpl_override;
+  s.texel_cache = h->texel_cache, s.exact_cached = h->exact_cached;
+  s.exact_chain_wave = h->exact_chain_wave != 0, s.exact_split_tail = h->exact_split_tail != 0;
+  s.exact_dense = h->exact_dense, s.exact_dense_min = h->exact_dense_min;
+  s.exact_spec = h->exact_spec, s.exact_spec1 = h->exact_spec1;
+  s.spb_large = h->spb_large, s.coop_min_beams = h->coop_min_beams, s.coop_skip = h->coop_skip > 0;
+  return s;
+}
+MatchSite single_scan_site(const hsm_ctx* h, int n, bool trace = false) { return match_site(h, 1, n, n, false, trace, h->stream); }
+
+// what hsm_last_launch_config / _kernel / _parity report: the plan that was launched
+void record_launch(hsm_ctx* h, const MatchPlan& plan) {
+  for (int i = 0; i < 6; ++i) h->last_cfg[i] = plan.record[i];
+  h->last_kernel = plan.name;
+  h->last_parity = plan.parity;
 }
 
-// reference order, launches that cannot fill the chip with one wavefront per scan (single scans, small batches): one wavefront
-// adds, fifteen produce one round ahead of it (gn_match_exact_dense_kernel, gn_match.h) -- a 16 k-beam match of configs[4] in
-// 0.9 instead of 1.2 ms, the nine chains' own 16 384 x 14 x 8.5 cycles being 0.8
-int launch_match_exact_dense(hsm_ctx* h, const MatchParams& P0, int max_n, hipStream_t stream) {
-  MatchParams P = P0;
-  // Round 6, opt-in (HSM_EXACT_SPEC=1): the speculative-carry form (gn_match_spec.h) -- the same sums bit for bit, the chains cut
-  // into segments that run in parallel -- whenever the host knows a true bound of the scan lengths (its product scratch is sized
-  // from it).  The shift rule accepts ~97 % of the segments of real chains, but on ONE CU the form is bound by what it moves
-  // (16 k texel lines + 1.2 MB of products per GN step through one L1) and by a lone workgroup's ~2 us per dependent load: 2.8 ms
-  // per 16 k-beam match against 0.9 for the literal chain below (profiles/r06/README.md).
-  // The product scratch is the launching stream's own (two streams' launches would write the same rows at once).  A launch into a
-  // graph capture takes the literal form below, which needs no scratch: a graph never reads a block that an eager launch grows
-  // (frees), and nothing is allocated or synchronised while the caller captures.  So does a ninth stream.
-  hsm_ctx::SpecScratch* sb = nullptr;
-  if (h->exact_spec && P.n_bound > 0 && max_n <= P.n_bound && !stream_capturing(stream)) {
+// the one-workgroup-per-scan forms of this unit: Family::kExactDense, kSpec (gn_match.h, gn_match_spec.h: `batch` workgroups) and
+// kSpec1 (one scan)
+int launch_workgroup_form(hsm_ctx* h, MatchParams P, MatchPlan& plan, const MatchSite& site, hipStream_t stream) {
+  if (plan.family == Family::kSpec) {
+    // The product scratch is the launching stream's own (two streams' launches would write the same rows at once).  A launch into a
+    // graph capture was planned in the literal form, which needs no scratch: a graph never reads a block that an eager launch grows
+    // (frees), and nothing is allocated or synchronised while the caller captures.  A ninth stream falls to it here.
+    hsm_ctx::SpecScratch* sb = nullptr;
     for (hsm_ctx::SpecScratch& b : h->spec_scratch)
       if (b.s == stream) sb = &b;
     if (!sb && h->spec_scratch.size() < 8) {
       h->spec_scratch.push_back({stream, {}});
       sb = &h->spec_scratch.back();
     }
+    if (!sb) {
+      MatchSite literal = site;
+      literal.exact_spec = false;
+      plan = plan_match(literal);
+    } else {
+      const size_t stride = spec_scratch_float4s_bound(P.n_bound);  // enough for every n <= n_bound
+      const size_t need = stride * (size_t)P.batch;
+      if (!sb->d.holds(need)) HIP_TRY(hipStreamSynchronize(stream));  // (a launch of this stream in flight may still read the old block)
+      if (int rc = sb->d.reserve(need)) return rc;
+      P.spec_scratch = (float*)sb->d.p;
+      P.spec_stride = (unsigned)stride;
+      P.spec_stats = h->d_spec_stats;
+    }
   }
-  if (sb) {
-    const size_t stride = spec_scratch_float4s_bound(P.n_bound);  // enough for every n <= n_bound
-    const size_t need = stride * (size_t)P.batch;
-    if (!sb->d.holds(need)) HIP_TRY(hipStreamSynchronize(stream));  // (a launch of this stream in flight may still read the old block)
-    if (int rc = sb->d.reserve(need)) return rc;
-    P.spec_scratch = (float*)sb->d.p;
-    P.spec_stride = (unsigned)stride;
-    P.spec_stats = h->d_spec_stats;
-    if (h->layout == kLayoutPlane)
-      hipLaunchKernelGGL((gn_match_spec_kernel<kLayoutPlane>), dim3(P.batch), dim3(1024), 0, stream, P);
-    else
-      hipLaunchKernelGGL((gn_match_spec_kernel<kLayoutQuad>), dim3(P.batch), dim3(1024), 0, stream, P);
-    HIP_TRY(hipGetLastError());
-    h->last_cfg[0] = h->layout;
-    h->last_cfg[1] = 16;
-    h->last_cfg[2] = 1024;
-    h->last_cfg[3] = P.batch;
-    h->last_cfg[4] = 0;
-    h->last_cfg[5] = 0;
-    h->last_kernel = "gn_match_spec_kernel";
-    return HSM_OK;
-  }
-  if (h->layout == kLayoutPlane)
-    hipLaunchKernelGGL((gn_match_exact_dense_kernel<kLayoutPlane>), dim3(P.batch), dim3(1024), 0, stream, P);
-  else
-    hipLaunchKernelGGL((gn_match_exact_dense_kernel<kLayoutQuad>), dim3(P.batch), dim3(1024), 0, stream, P);
+#define HSM_LAUNCH_WG(KERNEL)                                                              \
+  do {                                                                                     \
+    if (plan.layout == kLayoutPlane)                                                       \
+      hipLaunchKernelGGL((KERNEL<kLayoutPlane>), dim3(plan.grid), dim3(plan.block), 0, stream, P); \
+    else                                                                                   \
+      hipLaunchKernelGGL((KERNEL<kLayoutQuad>), dim3(plan.grid), dim3(plan.block), 0, stream, P);  \
+  } while (0)
+  if (plan.family == Family::kSpec) HSM_LAUNCH_WG(gn_match_spec_kernel);
+  else if (plan.family == Family::kExactDense) HSM_LAUNCH_WG(gn_match_exact_dense_kernel);
+  else HSM_LAUNCH_WG(gn_match_spec1_kernel);
+#undef HSM_LAUNCH_WG
   HIP_TRY(hipGetLastError());
-  h->last_cfg[0] = h->layout;
-  h->last_cfg[1] = 16;
-  h->last_cfg[2] = 1024;
-  h->last_cfg[3] = P.batch;
-  h->last_cfg[4] = 0;
-  h->last_cfg[5] = 0;
-  h->last_kernel = "gn_match_exact_dense_kernel";
   return HSM_OK;
 }
 
-int launch_match_mode(hsm_ctx* h, const MatchParams& P, int max_n, hipStream_t stream, bool exact) {
-  int wps = choose_wps(h, P.batch, max_n);
-  // reference order, batches of scans of up to 17 beams per lane: ALWAYS one wavefront per scan with the texel cache
-  // (launch_match_exact).  Teams of wavefronts per scan -- what choose_wps picks below 4096 scans to fill the chip -- only
-  // produce faster, and production is not what bounds this form: the nine chains are.  Measured (tools/batch_size_sweep.py,
-  // level-0 batch of 1081-beam scans, us per launch, teams -> one wavefront per scan + chain wavefront): 16 scans 46.7 -> 36.3,
-  // 1024: 80.3 -> 37.1, 2048: 92.4 -> 39.3, 3072: 134.5 -> 48.6, 3584: 135.9 -> 60.7 (without the chain wavefront).
-  // (hsm_match's single scans stay on the team form: it stops its chain at the scan's last beam and keeps the endpoints in
-  // registers -- 1081 beams 94 vs 92 us per call, 720 beams 74 vs 90, 360 beams 51 vs 59 through the chain-wavefront form)
-  // Longer scans (rows beyond the seventeenth stream from memory in every step, one dependent round trip per row): still one
-  // wavefront per scan once the batch has more scans than the device has CUs -- 2162-beam scans, 1024 / 3072 per launch: 83 / 117 us
-  // against 154 / 258 for the teams; 3243 beams: 140 / 195 against 228 / 381; up to 256 scans the 16-wavefront teams are as fast
-  // or faster (110-121 against 122) -- and dense scans (>= exact_dense_min beams) keep their one-workgroup-per-scan form below.
-  if (exact && wps > 1 && h->wps_override == 0 && P.begin_world && !P.trace && h->layout == kLayoutQuad && h->bpl_override != 0 &&
-      h->exact_cached && h->exact_chain_wave &&
-      (max_n <= 17 * 64 || (P.batch > h->compute_units && !(h->exact_dense && max_n >= h->exact_dense_min))))
-    wps = 1;
-  if (exact && wps > 1 && h->wps_override == 0 && h->exact_dense && max_n >= h->exact_dense_min) return launch_match_exact_dense(h, P, max_n, stream);
-  // one scan of the node's size through hsm_match, reference order: the on-chip speculative-carry form (gn_match_spec.h)
-  if (exact && wps > 1 && h->wps_override == 0 && h->exact_spec1 && P.batch == 1 && !P.begin_world && P.n_bound > 0 && max_n <= P.n_bound &&
-      max_n <= kSpec1MaxBeams) {
-    if (h->layout == kLayoutPlane)
-      hipLaunchKernelGGL((gn_match_spec1_kernel<kLayoutPlane>), dim3(1), dim3(1024), 0, stream, P);
-    else
-      hipLaunchKernelGGL((gn_match_spec1_kernel<kLayoutQuad>), dim3(1), dim3(1024), 0, stream, P);
-    HIP_TRY(hipGetLastError());
-    h->last_cfg[0] = h->layout;
-    h->last_cfg[1] = 16;
-    h->last_cfg[2] = 1024;
-    h->last_cfg[3] = 1;
-    h->last_cfg[4] = 0;
-    h->last_cfg[5] = 0;
-    h->last_kernel = "gn_match_spec1_kernel";
-    return HSM_OK;
+// launches `plan` (any family but the cooperative one, which match_single launches itself) and records it
+int launch_plan(hsm_ctx* h, MatchParams P, const MatchSite& site, MatchPlan plan, hipStream_t stream) {
+  if (plan.wants_perm)
+    if (int rc = ensure_batch_perm(h, P, stream)) return rc;  // (hsm_set_batch_order)
+  int rc;
+  switch (plan.family) {
+    case Family::kExactDense:
+    case Family::kSpec:
+    case Family::kSpec1: rc = launch_workgroup_form(h, P, plan, site, stream); break;
+    case Family::kExactCached:
+    case Family::kExactCachedCw:
+      if (plan.tail_batch > 0) {
+        // the whole generations, and behind them the part-filled last one in its own launch
+        MatchParams A = P, B = P;
+        A.batch = P.batch - plan.tail_batch, B.batch = plan.tail_batch;
+        if (P.perm) {  // (a permuted batch: the second launch takes the rest of the permutation, its scan indices stay absolute)
+          B.perm = P.perm + A.batch;
+        } else {
+          B.begin_world = P.begin_world + 3 * (size_t)A.batch;
+          if (P.offsets) B.offsets = P.offsets + A.batch;  // (absolute offsets into pts: the pointer moves, pts stays)
+          B.out_pose = P.out_pose + 3 * (size_t)A.batch;
+          if (P.out_cov) B.out_cov = P.out_cov + 9 * (size_t)A.batch;
+        }
+        B.clock_probe = nullptr;  // (scan 0's probe belongs to the first launch)
+        A.xp.world = 0;           // (neither part carries the pose exchange: plan_split_part)
+        B.xp.world = 0;
+        rc = launch_exact_cached_form(h, A, hsm_plan::plan_split_part(site, plan.tail_batch, false), stream);
+        if (rc == HSM_OK) rc = launch_exact_cached_form(h, B, hsm_plan::plan_split_part(site, plan.tail_batch, true), stream);
+      } else {
+        rc = launch_exact_cached_form(h, P, plan, stream);
+      }
+      break;
+    default: rc = launch_team_form(h, P, plan, stream); break;
   }
-  return launch_match_by_width(h, P, max_n, stream, exact, wps);
+  if (rc == HSM_OK) record_launch(h, plan);
+  return rc;
+}
+
+int launch_match(hsm_ctx* h, const MatchParams& P, int max_n, hipStream_t stream) {
+  h->last_sorted = false;  // (the forms that take a permuted batch set it: ensure_batch_perm)
+  MatchSite site = match_site(h, P.batch, max_n, P.n_bound, P.begin_world != nullptr, P.trace != nullptr, stream);
+  site.exchange = P.xp.world > 0, site.exchange_wait_blocks = P.xp.wait_blocks;
+  site.coop_skip = true;  // (the cooperative form is match_single's to launch: here its scan goes to one workgroup)
+  return launch_plan(h, P, site, plan_match(site), stream);
 }
 
 // the schedule of MapRepMultiMap::matchData (MapRepMultiMap.h:116-132): coarse levels
@@ -1131,8 +1128,9 @@ static int match_batch_device_nolock(hsm_ctx* h, int batch, const float* d_begin
   h->fused_exchange_done = false;
   // workgroup -> XCD mapping (gn_match.h, xcd_block): chunks dealt to the XCDs in turn balance the data-dependent
   // per-scan time; maps whose touched region outgrows the L2s keep one contiguous eighth of the batch per XCD
-  P.xcd_chunk = h->levels[0].cells() <= ((size_t)1 << 23) ? h->xcd_chunk : 0;
-  P.wg_sync = h->wg_sync >= 0 ? h->wg_sync : (h->levels[0].cells() > ((size_t)1 << 23) ? 1 : 0);
+  const bool outgrows = hsm_plan::level0_outgrows_l2(h->levels[0].cells());
+  P.xcd_chunk = outgrows ? 0 : h->xcd_chunk;
+  P.wg_sync = h->wg_sync >= 0 ? h->wg_sync : (outgrows ? 1 : 0);
   P.clock_probe = h->clock_probe;
   // per-scan length is only known on the device for CSR input; shared_n doubles as the sizing HINT there
   // (callers pass the typical beams per scan, 0 = unknown).  It only picks the kernel form: every form handles
@@ -1420,11 +1418,6 @@ int hsm_match_score_batch(hsm_ctx* h, int batch, const float* begin_world, const
                           "hsm_match_score_batch: bad argument");
 }
 
-// Largest scan the matcher keeps entirely in registers (16 waves x 64 lanes x 17 beams): such a scan is
-// read exactly once per match, so the kernel can fetch it directly from pinned host memory over PCIe
-// and the host entry needs no H2D copy at all.
-constexpr int kMaxRegisterResidentBeams = 16 * 64 * 17;
-
 // One scan on the levels selected in P.  `pts` is a device-accessible pointer (device memory or pinned
 // mapped host memory), level-0 units.  Latency path of the ROS node: ONE kernel launch and one stream
 // synchronise -- the start estimate travels in the kernel arguments and the kernel writes pose, H and
@@ -1475,20 +1468,19 @@ static int match_single(hsm_ctx* h, MatchParams& P, const float begin_world[3], 
   P.err_flag = reinterpret_cast<unsigned*>(hs_dev + kErrFlagOff);
   P.coop_mute_block = h->coop_mute_block;
   P.clock_probe = h->clock_probe;
-  bool coop_now = n >= h->coop_min_beams && h->wps_override == 0 && !wants_exact(h);
-  if (coop_now && h->coop_skip > 0) {  // backing off after an exchange timeout: this match goes straight to the one-workgroup form
+  // which form: the site the scan was staged for (stage_scan), now with the trace
+  MatchSite site = single_scan_site(h, n, trace_steps > 0);
+  site.coop_skip = false;
+  MatchPlan plan = plan_match(site);
+  if (plan.family == Family::kCoop && h->coop_skip > 0) {  // backing off after an exchange timeout: this match goes straight to the one-workgroup form
     --h->coop_skip;
-    coop_now = false;
+    site.coop_skip = true;
+    plan = plan_match(site);
   }
-  const bool coop_tried = coop_now;
-  if (coop_now) {
-    // one dense scan: spread it over K workgroups of one cooperative launch (gn_match.h); the exact-order
-    // form keeps the scan on one workgroup -- its nine summation chains are sequential anyway
-    // one beam per lane.  16 k beams, matchData us for K = 16 / 24 / 32 / 64 workgroups: 79.8 / 71 / 66-70 / 64 with round 2's grid
-    // barrier; 70 (24) / 67-71 (31) / 76 (48) / 63-64 (64) with the tagged exchange (profiles/r03/README.md)
-    int K = (n + 255) / 256;
-    if (K > 64) K = 64;
-    if (K < 2) K = 2;
+  const bool coop_tried = plan.family == Family::kCoop;
+  if (coop_tried) {
+    // one dense scan spread over K workgroups of one launch (match_plan.h has the measurements)
+    const int K = plan.grid;
     float* partials = h->d_partials;
     unsigned* bar_counter = reinterpret_cast<unsigned*>(h->d_partials + 2 * 64 * 12);
     unsigned bar_base = h->coop_bar_base;
@@ -1516,20 +1508,14 @@ static int match_single(hsm_ctx* h, MatchParams& P, const float begin_world[3], 
       unsigned steps = 0;
       for (int l = P.first_level; l >= P.last_level; --l) steps += (unsigned)P.lv[l].gn_steps;
       h->coop_bar_base += (unsigned)K * steps;  // one arrival per workgroup per GN step
-      h->last_cfg[0] = h->layout;
-      h->last_cfg[1] = -K;  // negative: K cooperating workgroups instead of waves per scan
-      h->last_cfg[2] = 256;
-      h->last_cfg[3] = K;
-      h->last_cfg[4] = 0;
-      h->last_kernel = "gn_match_coop_kernel";
-      h->last_parity = HSM_PARITY_FAST;
+      record_launch(h, plan);
     } else {
       // the runtime could not guarantee co-residency (device busy with other work): the one-workgroup
       // matcher computes the same thing on one CU
       (void)hipGetLastError();
       if (int rc = launch_match(h, P, n, h->stream)) return rc;
     }
-  } else if (int rc = launch_match(h, P, n, h->stream)) {
+  } else if (int rc = launch_match(h, P, n, h->stream)) {  // (plans the same site again, with the cooperative form ruled out)
     return rc;
   }
   if (int rc = wait_single_scan(h, seq)) return rc;
@@ -1567,27 +1553,10 @@ static int match_single(hsm_ctx* h, MatchParams& P, const float begin_world[3], 
   return HSM_OK;
 }
 
-// Does the matcher read the endpoints of a single n-beam scan exactly ONCE?  Then they can stay in pinned, device-mapped host
-// memory (no H2D copy command in front of the kernel); otherwise -- re-read in every GN step -- they must live in device memory.
-//   tree summation: the register-resident forms (BPL > 0), unless the multi-workgroup dense matcher takes the scan;
-//   reference order (round 5): the team form keeps a scan of at most kExactGroupRounds rounds in registers across all levels and
-//     steps (gn_match_kernel: xq_resident) -- every single scan below the dense threshold --, the producers-ahead form a scan of
-//     at most two of its rounds
-static bool scan_is_read_once(const hsm_ctx* h, int n) {
-  if (!wants_exact(h))
-    return n <= kMaxRegisterResidentBeams && h->bpl_override != 0 && (n < h->coop_min_beams || h->wps_override != 0);
-  const int wps = choose_wps(h, 1, n);
-  if (wps > 1 && h->wps_override == 0 && h->exact_dense && n >= h->exact_dense_min)
-    return !h->exact_spec && n <= 2 * kDenseRound;  // (the speculative-carry form re-reads the endpoints in every GN step)
-  return n <= kExactGroupRounds * 64 * wps;
-}
-
-// stage a host scan where the matcher can read it: pinned mapped host memory when it will be read
-// once (register resident), device memory otherwise
+// stage a host scan where the matcher can read it: pinned mapped host memory when the form planned for it reads it once
+// (MatchPlan::reads_scan_once: no H2D copy command in front of the kernel), device memory otherwise
 static int stage_scan(hsm_ctx* h, const float* pts_xy, int n, Buf<float2>& d_buf, const float2** out) {
-  // (a dense scan for the multi-workgroup matcher is re-read every GN step: it must live in device memory)
-  // (and so does the exact-order form)
-  if (scan_is_read_once(h, n)) {
+  if (plan_match(single_scan_site(h, n)).reads_scan_once) {
     if (int rc = h->h_scan_pinned.reserve(n > 0 ? n : 1, kScanGrowth)) return rc;  // (1: also the empty first scan of a fresh context)
     if (n > 0) memcpy(h->h_scan_pinned, pts_xy, (size_t)n * sizeof(float2));
     float2* dev = nullptr;
@@ -1663,7 +1632,7 @@ static int match_impl(hsm_ctx* h, const float begin_world[3], const float* pts_x
   const float2* pts = d_prestaged;
   if (!pts) {
     // (the same rule as stage_scan's: scans the matcher reads once stay in pinned host memory)
-    const bool to_device = !scan_is_read_once(h, n);
+    const bool to_device = !plan_match(single_scan_site(h, n)).reads_scan_once;
     // ... and only behind an update that was queued and not waited for (the match + update loop): on an idle stream the
     // extra hop through the copy stream's event costs ~10 us of latency and hides nothing (asking the runtime with
     // hipStreamQuery costs half of what the overlap gains: 0.1855 against 0.179 ms per configs[4] step)

@@ -14,6 +14,7 @@
 #include "gn_match.h"
 #include "hector_mi355/capi.h"
 #include "hsm_host.h"
+#include "match_plan.h"
 #include "stage_layout.h"
 
 namespace hsm {
@@ -266,9 +267,9 @@ struct hsm_ctx {
   bool dense_bits = true;        // env HSM_DENSE_BITS=0: dense scans keep the keyed update (map_update.h)
   bool exact_cached = true;      // env HSM_EXACT_CACHED=0: exact-mode batches take the one-wavefront-per-scan exact form (gn_match_kernel) instead of gn_match_exact.h's
   bool exact = false;     // HSM_PARITY_EXACT: H / dTr summed in the reference's beam order (gn_match.h exact_round)
-  bool auto_parity = true;  // HSM_PARITY_AUTO (default): every entry point in the reference's summation order (auto_wants_exact)
+  bool auto_parity = true;  // HSM_PARITY_AUTO (default): every entry point in the reference's summation order (wants_exact)
   bool relaxed = false;   // HSM_PARITY_RELAXED: contracted multiply-adds in the throughput kernel (gn_match_cached_kernel<.., RELAXED>)
-  int last_cfg[6] = {0, 0, 0, 0, 0, 0};
+  int last_cfg[6] = {0, 0, 0, 0, 0, 0};  // MatchPlan::record of the last match launch (record_launch)
   int coop_mute_block = 0;      // hsm_debug_set_coop_mute (test hook)
   int sched_level = -1;         // hsm_debug_set_schedule (test hook): batched entries run `sched_level` only, -1 = the full schedule
   int sched_steps = 0;          //   ... with this many GN steps
@@ -315,17 +316,20 @@ struct hsm_ctx {
 
 namespace hsm_host {
 
-// match_exact_cached.hip: reference order, batches, one wavefront per scan with the texel cache (by scan length and by how many
-// workgroups the launch leaves a CU)
-int launch_match_exact_cached_forms(hsm_ctx* h, const hsm::MatchParams& P, int max_n, hipStream_t stream);
-// match_teams.hip: `wps` wavefronts per scan (1, 2, 4, 8, 16), either summation order; the one-wavefront exact form goes on to
-// launch_match_exact_cached_forms where that applies
-// MatchParams::perm for this launch where hsm_set_batch_order asks for it (a sort kernel on `stream` in front of the matcher)
-// (a launch into a graph capture keeps the caller's order: no graph ever reads a stream's permutation buffer)
-int ensure_batch_perm(hsm_ctx* h, hsm::MatchParams& P, hipStream_t stream);
-// batch_order_kernel on `stream`: perm[slot] = scan for `batch` start poses, with level 0's transform (hsm_debug_batch_order too)
-int launch_batch_order(hsm_ctx* h, const float* begin_world, int batch, int* perm, bool detect, hipStream_t stream);
-int launch_match_by_width(hsm_ctx* h, const hsm::MatchParams& P, int max_n, hipStream_t stream, bool exact, int wps);
+using hsm_plan::MatchPlan;
 
+// Which form a launch takes is decided once, in match_plan.h (plan_match), by launch_match of hector_mi355.hip, which also
+// keeps the launch record; the other two units only map a plan to their instantiations and launch it.
+// match_exact_cached.hip: reference order, batches, one wavefront per scan with the texel cache (Family::kExactCached, kExactCachedCw)
+int launch_exact_cached_form(hsm_ctx* h, hsm::MatchParams P, const MatchPlan& plan, hipStream_t stream);
+// match_teams.hip: `plan.wps` wavefronts per scan (1, 2, 4, 8, 16), either summation order, and the fast texel-cache form
+// (Family::kTeam, kTeamExact, kCached)
+int launch_team_form(hsm_ctx* h, const hsm::MatchParams& P, const MatchPlan& plan, hipStream_t stream);
+// match_teams.hip: MatchParams::perm for this launch where hsm_set_batch_order asks for it (a sort kernel on `stream` in front of
+// the matcher); a launch into a graph capture keeps the caller's order: no graph ever reads a stream's permutation buffer
+int ensure_batch_perm(hsm_ctx* h, hsm::MatchParams& P, hipStream_t stream);
+// match_teams.hip: batch_order_kernel on `stream`: perm[slot] = scan for `batch` start poses, with level 0's transform
+// (hsm_debug_batch_order too)
+int launch_batch_order(hsm_ctx* h, const float* begin_world, int batch, int* perm, bool detect, hipStream_t stream);
 
 }  // namespace hsm_host

@@ -141,7 +141,7 @@ int launch_batch_order(hsm_ctx* h, const float* begin_world, int batch, int* per
 int ensure_batch_perm(hsm_ctx* h, MatchParams& P, hipStream_t stream) {
   if (P.perm != nullptr || P.begin_world == nullptr || P.batch < h->batch_order_min) return HSM_OK;
   const bool automatic = h->batch_order == HSM_ORDER_AUTO;
-  if (h->batch_order != HSM_ORDER_MORTON && !(automatic && h->levels[0].cells() > ((size_t)1 << 23))) return HSM_OK;
+  if (h->batch_order != HSM_ORDER_MORTON && !(automatic && hsm_plan::level0_outgrows_l2(h->levels[0].cells()))) return HSM_OK;
   // A launch into a graph capture keeps the caller's order and leaves the stream's permutation as it is.  Its sort would run at
   // the replays only, while the host state below would claim it had run now (an eager launch of that size would then reuse a
   // buffer that holds another batch's permutation); and a graph that read the buffer would read it after an eager launch had
@@ -172,140 +172,68 @@ int ensure_batch_perm(hsm_ctx* h, MatchParams& P, hipStream_t stream) {
 
 namespace {
 
+using hsm_plan::Family;
+
+// gn_match_kernel<WPS, SPB, ., BPL>, and for one-wavefront teams of 9 or 17 beams per lane the fast texel-cache form next to it
 template <int WPS, int SPB, int BPL>
-int launch_match_t(hsm_ctx* h, const MatchParams& P_in, hipStream_t stream) {
-  const MatchParams& P = P_in;
-  const int block = 64 * WPS * SPB;
-  const int grid = (P.batch + SPB - 1) / SPB;
+void launch_team(const MatchParams& P, const MatchPlan& plan, hipStream_t stream) {
+  const dim3 grid(plan.grid), block(plan.block);
   if constexpr (WPS == 1 && (BPL == 9 || BPL == 17)) {
-    // throughput launches of long scans: the texel-cache form (gn_match.h)
-    if (h->texel_cache && P.begin_world && !P.trace) {
-      MatchParams P = P_in;  // (hsm_set_batch_order: the launch takes its scans through a permutation)
-      if (int rc = ensure_batch_perm(h, P, stream)) return rc;
-      if (h->layout == kLayoutQuad && h->relaxed)
-        hipLaunchKernelGGL((gn_match_cached_kernel<SPB, BPL, kLayoutQuad, 1, true>), dim3(grid), dim3(block), 0, stream, P);
-      else if (h->layout == kLayoutQuad)
-        hipLaunchKernelGGL((gn_match_cached_kernel<SPB, BPL, kLayoutQuad>), dim3(grid), dim3(block), 0, stream, P);
+    if (plan.family == Family::kCached) {
+      if (plan.relaxed)
+        hipLaunchKernelGGL((gn_match_cached_kernel<SPB, BPL, kLayoutQuad, 1, true>), grid, block, 0, stream, P);
+      else if (plan.layout == kLayoutQuad)
+        hipLaunchKernelGGL((gn_match_cached_kernel<SPB, BPL, kLayoutQuad>), grid, block, 0, stream, P);
       else
-        hipLaunchKernelGGL((gn_match_cached_kernel<SPB, BPL, kLayoutPlane>), dim3(grid), dim3(block), 0, stream, P);
-      HIP_TRY(hipGetLastError());
-      h->last_cfg[0] = h->layout;
-      h->last_cfg[1] = WPS;
-      h->last_cfg[2] = block;
-      h->last_cfg[3] = grid;
-      h->last_cfg[4] = BPL;
-      h->last_cfg[5] = 1;
-      h->last_kernel = "gn_match_cached_kernel";
-      return HSM_OK;
+        hipLaunchKernelGGL((gn_match_cached_kernel<SPB, BPL, kLayoutPlane>), grid, block, 0, stream, P);
+      return;
     }
   }
-  h->last_cfg[5] = 0;
-  h->last_kernel = "gn_match_kernel";
-  if (h->layout == kLayoutPlane)
-    hipLaunchKernelGGL((gn_match_kernel<WPS, SPB, kLayoutPlane, BPL>), dim3(grid), dim3(block), 0, stream, P);
+  if (plan.layout == kLayoutPlane)
+    hipLaunchKernelGGL((gn_match_kernel<WPS, SPB, kLayoutPlane, BPL>), grid, block, 0, stream, P);
   else
-    hipLaunchKernelGGL((gn_match_kernel<WPS, SPB, kLayoutQuad, BPL>), dim3(grid), dim3(block), 0, stream, P);
-  HIP_TRY(hipGetLastError());
-  h->last_cfg[0] = h->layout;
-  h->last_cfg[1] = WPS;
-  h->last_cfg[2] = block;
-  h->last_cfg[3] = grid;
-  h->last_cfg[4] = BPL;
-  return HSM_OK;
+    hipLaunchKernelGGL((gn_match_kernel<WPS, SPB, kLayoutQuad, BPL>), grid, block, 0, stream, P);
+}
+
+// gn_match_kernel<WPS, SPB, ., 0, EXACT>: the reference's summation order, endpoints streamed
+template <int WPS, int SPB>
+void launch_team_exact(const MatchParams& P, const MatchPlan& plan, hipStream_t stream) {
+  if (plan.layout == kLayoutPlane)
+    hipLaunchKernelGGL((gn_match_kernel<WPS, SPB, kLayoutPlane, 0, true>), dim3(plan.grid), dim3(plan.block), 0, stream, P);
+  else
+    hipLaunchKernelGGL((gn_match_kernel<WPS, SPB, kLayoutQuad, 0, true>), dim3(plan.grid), dim3(plan.block), 0, stream, P);
 }
 
 template <int WPS, int SPB>
-int launch_match_exact(hsm_ctx* h, const MatchParams& P_in, int max_n, hipStream_t stream) {
-  MatchParams P = P_in;
-  // throughput launches of the quad layout: every wavefront a producer with the texel cache, four scans per workgroup, one
-  // 36-lane chain job per round behind the round's barrier (gn_match_exact.h).  Measured against round 2's producer /
-  // chain-wavefront form (profiles/r03/README.md): 66-69 vs 92 us on the 2048^2 headline batch, 141-143 vs 199 us on the
-  // 3-level batch, 156-162 vs 291 us on the 4096^2 pyramid.  Scans longer than 17 beams per lane stream their tail rows.
-  if (WPS == 1 && P.begin_world && !P.trace && h->layout == kLayoutQuad && h->bpl_override != 0 && h->exact_cached) {
-    if (int rc = ensure_batch_perm(h, P, stream)) return rc;  // (hsm_set_batch_order)
-    // More than one generation of workgroups (four per CU) with a remainder that the chain-wavefront form takes: the whole
-    // generations go out in round 3's form, the remainder behind them in its own launch -- 5000 scans: 57 + 36 us instead of the
-    // 104 a single launch takes (its last, part-filled generation runs ~47 us in the rotating-owner form).
-    const int groups = (P.batch + 3) / 4, full = 4 * h->compute_units, rest = groups % full;
-    if (h->exact_chain_wave && h->exact_split_tail && groups > full && rest > 0 &&
-        (rest <= 2 * h->compute_units || (rest <= 3 * h->compute_units && h->levels[0].cells() <= ((size_t)1 << 23)))) {
-      MatchParams A = P, B = P;
-      A.batch = (groups - rest) * 4;
-      B.batch = P.batch - A.batch;
-      if (P.perm) {  // (a permuted batch: the second launch takes the rest of the permutation, its scan indices stay absolute)
-        B.perm = P.perm + A.batch;
-      } else {
-        B.begin_world = P.begin_world + 3 * (size_t)A.batch;
-        if (P.offsets) B.offsets = P.offsets + A.batch;  // (absolute offsets into pts: the pointer moves, pts stays)
-        B.out_pose = P.out_pose + 3 * (size_t)A.batch;
-        if (P.out_cov) B.out_cov = P.out_cov + 9 * (size_t)A.batch;
-      }
-      B.clock_probe = nullptr;  // (scan 0's probe belongs to the first launch)
-      // (a launch that carries the pose exchange: the part-filled last generation runs in a chain-wavefront form, which does not --
-      // so the whole step is left to the stand-alone exchange kernel behind both launches)
-      A.xp.world = 0;
-      B.xp.world = 0;
-      if (int rc = launch_match_exact_cached_forms(h, A, max_n, stream)) return rc;
-      const int grid_a = h->last_cfg[3];
-      if (int rc = launch_match_exact_cached_forms(h, B, max_n, stream)) return rc;
-      h->last_cfg[2] = 256;  // (hsm_last_launch_config describes the first launch; its grid counts both)
-      h->last_cfg[3] += grid_a;
-      h->last_kernel = "gn_match_exact_cached_kernel + its chain-wavefront form for the last, part-filled generation";
-      return HSM_OK;
-    }
-    return launch_match_exact_cached_forms(h, P, max_n, stream);
-  }
-  const int block = 64 * WPS * SPB;
-  const int grid = (P.batch + SPB - 1) / SPB;
-  if (h->layout == kLayoutPlane)
-    hipLaunchKernelGGL((gn_match_kernel<WPS, SPB, kLayoutPlane, 0, true>), dim3(grid), dim3(block), 0, stream, P);
-  else
-    hipLaunchKernelGGL((gn_match_kernel<WPS, SPB, kLayoutQuad, 0, true>), dim3(grid), dim3(block), 0, stream, P);
-  HIP_TRY(hipGetLastError());
-  h->last_cfg[0] = h->layout;
-  h->last_cfg[1] = WPS;
-  h->last_cfg[2] = block;
-  h->last_cfg[3] = grid;
-  h->last_cfg[4] = 0;
-  h->last_cfg[5] = 0;
-  h->last_kernel = "gn_match_kernel (exact order)";
-  return HSM_OK;
-}
-
-template <int WPS, int SPB>
-int launch_match_w(hsm_ctx* h, const MatchParams& P, int max_n, hipStream_t stream, bool exact) {
-  if (exact) return launch_match_exact<WPS, SPB>(h, P, max_n, stream);
-  const int per_lane = (max_n + 64 * WPS - 1) / (64 * WPS);
-  if (h->bpl_override == 0 || per_lane > 17) return launch_match_t<WPS, SPB, 0>(h, P, stream);
-  // (two beams per lane: only one-wavefront teams get there by themselves -- choose_wps keeps ~5 beams per lane -- so wider
-  // teams, reachable through an explicit waves_per_scan only, share the three-beam instantiation)
-  if constexpr (WPS == 1)
-    if (per_lane <= 2) return launch_match_t<WPS, SPB, 2>(h, P, stream);
-  if (per_lane <= 3) return launch_match_t<WPS, SPB, 3>(h, P, stream);
-  if (per_lane <= 5) return launch_match_t<WPS, SPB, 5>(h, P, stream);
-  if (per_lane <= 9) return launch_match_t<WPS, SPB, 9>(h, P, stream);
-  return launch_match_t<WPS, SPB, 17>(h, P, stream);
+void launch_team_w(const MatchParams& P, const MatchPlan& plan, hipStream_t stream) {
+  if (plan.family == Family::kTeamExact) return launch_team_exact<WPS, SPB>(P, plan, stream);
+  if (plan.bpl == 0) return launch_team<WPS, SPB, 0>(P, plan, stream);
+  if constexpr (WPS == 1)  // (two beams per lane: one-wavefront teams only, match_plan.h)
+    if (plan.bpl == 2) return launch_team<WPS, SPB, 2>(P, plan, stream);
+  if (plan.bpl == 3) return launch_team<WPS, SPB, 3>(P, plan, stream);
+  if (plan.bpl == 5) return launch_team<WPS, SPB, 5>(P, plan, stream);
+  if (plan.bpl == 9) return launch_team<WPS, SPB, 9>(P, plan, stream);
+  return launch_team<WPS, SPB, 17>(P, plan, stream);
 }
 
 }  // namespace
 
-int launch_match_by_width(hsm_ctx* h, const MatchParams& P, int max_n, hipStream_t stream, bool exact, int wps) {
-  switch (wps) {
-    case 1: {
-      // maps whose touched region outgrows the L2s: EIGHT consecutive scans per workgroup instead of four -- with the
-      // per-beam workgroup barrier (MatchParams::wg_sync) eight waves share the texel lines in the CU's L1 (4096^2
-      // pyramid: 132.8 -> 129.1 us; 16 per workgroup: 133 us; no effect on the 2048^2 workloads, which keep four)
-      const int per_lane = (max_n + 63) / 64;
-      if (h->spb_large == 8 && h->levels[0].cells() > ((size_t)1 << 23) && !exact && h->texel_cache && P.begin_world &&
-          !P.trace && h->bpl_override != 0 && per_lane > 5 && per_lane <= 17)
-        return per_lane <= 9 ? launch_match_t<1, 8, 9>(h, P, stream) : launch_match_t<1, 8, 17>(h, P, stream);
-      return launch_match_w<1, 4>(h, P, max_n, stream, exact);
-    }
-    case 2: return launch_match_w<2, 1>(h, P, max_n, stream, exact);
-    case 4: return launch_match_w<4, 1>(h, P, max_n, stream, exact);
-    case 8: return launch_match_w<8, 1>(h, P, max_n, stream, exact);
-    default: return launch_match_w<16, 1>(h, P, max_n, stream, exact);
+// the plan's team form or fast texel-cache form (match_plan.h: plan_team) -> its instantiation
+int launch_team_form(hsm_ctx*, const MatchParams& P, const MatchPlan& plan, hipStream_t stream) {
+  switch (plan.wps) {
+    case 1:
+      if (plan.spb == 8)
+        plan.bpl == 9 ? launch_team<1, 8, 9>(P, plan, stream) : launch_team<1, 8, 17>(P, plan, stream);
+      else
+        launch_team_w<1, 4>(P, plan, stream);
+      break;
+    case 2: launch_team_w<2, 1>(P, plan, stream); break;
+    case 4: launch_team_w<4, 1>(P, plan, stream); break;
+    case 8: launch_team_w<8, 1>(P, plan, stream); break;
+    default: launch_team_w<16, 1>(P, plan, stream); break;
   }
+  HIP_TRY(hipGetLastError());
+  return HSM_OK;
 }
 
 }  // namespace hsm_host
