@@ -69,12 +69,20 @@ SIGNATURES = {
     "hsm_update_by_scan": (_i, [_vp, _f32p, _vp, _i, _f32p]),
     "hsm_update_by_scan_level": (_i, [_vp, _i, _f32p, _vp, _i, _f32p]),
     "hsm_update_by_scans_device": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "hsm_update_by_scans_device_origos": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "hsm_update_by_scans": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp]),
     "hsm_set_update_gate": (_i, [_vp, _f, _f]),
     "hsm_reset_update_gate": (_i, [_vp]),
     "hsm_update_gate_state": (_i, [_vp, _f32p, C.POINTER(C.c_longlong)]),
     "hsm_update_by_scans_device_gated": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "hsm_update_by_scans_device_gated_origos": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "hsm_slam_scans_device": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "hsm_slam_scans_device_origos": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "hsm_slam_ranges_tf_device": (_i, [_vp, _i, _vp, _vp, _vp, _i, _f, _f, _f, _f, C.c_double, _vp, _i, _f, _f, _f, _f, _f, _vp,
+                                       _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "hsm_slam_ranges_tf_workspace": (C.c_size_t, [_i, _i]),
+    "hsm_slam_ranges_tf": (_i, [_vp, _i, _vp, _vp, _vp, _i, _f, _f, _f, _f, C.c_double, _vp, _i, _f, _f, _f, _f, _f, _vp, _vp,
+                                _vp, _vp, _vp, _vp]),
     "hsm_ingest_laser_scan": (_i, [_vp, _vp, _i, _f, _f, _f, _f, _f, _vp, C.POINTER(_i)]),
     "hsm_ingest_point_cloud": (_i, [_vp, _vp, _i, _vp, _f, _f, _f, _f, _f, _vp, C.POINTER(_i), _vp]),
     "hsm_ingest_laser_scan_tf": (_i, [_vp, _vp, _i, _f, _f, _f, _f, C.c_double, _vp, _f, _f, _f, _f, _f, _vp,
@@ -612,6 +620,75 @@ class MapRepMultiMap:
                                                d_offsets or None, max_beams, None if o is None else o.ctypes.data, d_force or None,
                                                d_out_pose or None, d_out_cov or None, d_out_applied or None, stream or None),
                "hsm_slam_scans_device")
+
+    def update_by_scans_device_origos(self, count, d_poses_world, d_pts, d_offsets, shared_n, max_beams=0, d_origos=0, stream=0):
+        """``update_by_scans_device`` with one origo per scan on the device (``d_origos`` float32 [count, 2], 0 = 0,0)."""
+        _check(self._lib.hsm_update_by_scans_device_origos(self._h, count, d_poses_world or None, d_pts or None, d_offsets or None,
+                                                           shared_n, max_beams, d_origos or None, stream or None),
+               "hsm_update_by_scans_device_origos")
+
+    def update_by_scans_device_gated_origos(self, count, d_poses_world, d_pts, d_offsets, shared_n, max_beams=0, d_origos=0,
+                                            d_force=0, d_out_applied=0, stream=0):
+        """``update_by_scans_device_gated`` with one origo per scan on the device."""
+        _check(self._lib.hsm_update_by_scans_device_gated_origos(self._h, count, d_poses_world or None, d_pts or None,
+                                                                 d_offsets or None, shared_n, max_beams, d_origos or None,
+                                                                 d_force or None, d_out_applied or None, stream or None),
+               "hsm_update_by_scans_device_gated_origos")
+
+    def slam_scans_device_origos(self, count, d_start_pose, d_hint_deltas, d_pts, d_offsets, max_beams, d_origos, d_force,
+                                 d_out_pose, d_out_cov=0, d_out_applied=0, stream=0):
+        """``slam_scans_device`` with one origo per scan on the device: a forced scan's coarse levels integrate the points
+        and the origo of the last matched scan, as the reference does."""
+        _check(self._lib.hsm_slam_scans_device_origos(self._h, count, d_start_pose or None, d_hint_deltas or None, d_pts or None,
+                                                      d_offsets or None, max_beams, d_origos or None, d_force or None,
+                                                      d_out_pose or None, d_out_cov or None, d_out_applied or None,
+                                                      stream or None), "hsm_slam_scans_device_origos")
+
+    @staticmethod
+    def slam_ranges_tf_workspace(count, n):
+        """bytes of the workspace of ``slam_ranges_tf_device`` (0 for sizes it refuses); host arithmetic only"""
+        return int(load_library().hsm_slam_ranges_tf_workspace(int(count), int(n)))
+
+    def slam_ranges_tf_device(self, count, d_start_pose, d_hint_deltas, d_ranges, n, angle_min, angle_increment, range_min,
+                              range_max, range_cutoff, d_tf_rows, shared_tf, sqr_laser_min_dist, sqr_laser_max_dist, laser_z_min,
+                              laser_z_max, scale_to_map, d_force, d_out_pose, d_out_cov, d_out_applied, d_out_counts, d_workspace,
+                              workspace_bytes, stream=0):
+        """Raw device pointers (ints): a log of raw scans and a transform per scan through the node's tf conversion and the
+        whole HectorSlamProcessor::update loop, queued in one call; the host waits for nothing."""
+        _check(self._lib.hsm_slam_ranges_tf_device(
+            self._h, count, d_start_pose or None, d_hint_deltas or None, d_ranges or None, n, angle_min, angle_increment, range_min,
+            range_max, range_cutoff, d_tf_rows or None, int(bool(shared_tf)), sqr_laser_min_dist, sqr_laser_max_dist, laser_z_min,
+            laser_z_max, scale_to_map, d_force or None, d_out_pose or None, d_out_cov or None, d_out_applied or None,
+            d_out_counts or None, d_workspace or None, workspace_bytes, stream or None), "hsm_slam_ranges_tf_device")
+
+    def slam_ranges_tf(self, start_pose, hint_deltas, ranges, angle_min, angle_increment, range_min, range_max, range_cutoff,
+                       tf_rows, sqr_laser_min_dist, sqr_laser_max_dist, laser_z_min, laser_z_max, scale_to_map=None, force=None,
+                       cov=None):
+        """Host arrays: ``ranges`` [count, n] and ``tf_rows`` [count, 12] (or [12]: one transform for every scan) through the
+        one-call entry -> dict(pose [count, 3], cov [count, 9], applied, counts [count], origo [count, 2]); synchronous.
+        ``cov`` presets the covariances (a scan that keeps no beam leaves its row untouched)."""
+        r = np.ascontiguousarray(ranges, np.float32)
+        if r.ndim != 2:
+            raise ValueError("ranges must be [count, n]")
+        count, n = r.shape
+        T = np.ascontiguousarray(tf_rows, np.float64)
+        shared = T.size == 12 and T.ndim == 1
+        if not shared and T.shape != (count, 12):
+            raise ValueError("tf_rows must be [12] or [count, 12]")
+        sp = None if start_pose is None else _v(start_pose, 3)
+        dl = None if hint_deltas is None else np.ascontiguousarray(hint_deltas, np.float32).reshape(count, 3)
+        fo = None if force is None else np.ascontiguousarray(force, np.uint8).reshape(count)
+        out = {"pose": np.empty((count, 3), np.float32),
+               "cov": np.zeros((count, 9), np.float32) if cov is None else np.array(cov, np.float32).reshape(count, 9),
+               "applied": np.empty(count, np.int32), "counts": np.empty(count, np.int32), "origo": np.empty((count, 2), np.float32)}
+        s = self.getScaleToMap() if scale_to_map is None else scale_to_map
+        _check(self._lib.hsm_slam_ranges_tf(
+            self._h, count, None if sp is None else sp.ctypes.data, None if dl is None else dl.ctypes.data,
+            r.ctypes.data if r.size else None, n, angle_min, angle_increment, range_min, range_max, range_cutoff, T.ctypes.data,
+            int(shared), sqr_laser_min_dist, sqr_laser_max_dist, laser_z_min, laser_z_max, s, None if fo is None else fo.ctypes.data,
+            out["pose"].ctypes.data, out["cov"].ctypes.data, out["applied"].ctypes.data, out["counts"].ctypes.data,
+            out["origo"].ctypes.data), "hsm_slam_ranges_tf")
+        return out
 
     def update_by_scans(self, poses_world, pts, offsets=None, origo=None):
         """Host arrays: a map from a log of posed scans in one call.  ``offsets`` None = every pose integrates the one scan ``pts``."""

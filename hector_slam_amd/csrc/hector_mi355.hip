@@ -1837,17 +1837,18 @@ struct GateCall {
 
 static int update_by_scans_device_nolock(hsm_ctx* h, int count, const float* d_poses_world, const float* d_pts_xy,
                                          const int* d_scan_offsets, int shared_n, int max_beams, const float origo[2],
-                                         hipStream_t stream, const GateCall* gate = nullptr) {
+                                         hipStream_t stream, const GateCall* gate = nullptr, const float* d_origos = nullptr,
+                                         const char* who = "hsm_update_by_scans_device") {  // the entry the caller used, for the error text
   if (count < 0 || max_beams < 0 || (count > 0 && !d_poses_world) || (!d_scan_offsets && shared_n < 0) ||
-      (count > 0 && !d_scan_offsets && shared_n > 0 && !d_pts_xy))
-    return fail(HSM_ERR_INVALID, "hsm_update_by_scans_device: bad argument");
+      (count > 0 && !d_scan_offsets && shared_n > 0 && !d_pts_xy) || ((uintptr_t)d_origos & 7u) != 0)  // (origos: float2 loads)
+    return fail(HSM_ERR_INVALID, (std::string(who) + ": bad argument").c_str());
   if (!d_scan_offsets && shared_n > HSM_MAX_UPDATE_BEAMS)
-    return fail(HSM_ERR_TOO_LARGE, "hsm_update_by_scans_device: more than HSM_MAX_UPDATE_BEAMS beams");
+    return fail(HSM_ERR_TOO_LARGE, (std::string(who) + ": more than HSM_MAX_UPDATE_BEAMS beams").c_str());
   if (count == 0) return HSM_OK;
   if (int rc = select_device(h)) return rc;
   // the rule of every map update: refused, before anything is queued, while a stream this call would touch is being captured
   if (stream_capturing(stream))
-    return fail(HSM_ERR_INVALID, "hsm_update_by_scans_device: `stream` is being captured into a graph (map updates are not captured)");
+    return fail(HSM_ERR_INVALID, (std::string(who) + ": `stream` is being captured into a graph (map updates are not captured)").c_str());
   if (int rc = order_after_foreign_match(h)) return rc;  // (refuses the same way for the streams this context has matched on)
   if (!gate && h->gate_outstanding)  // scan k is update k behind EVERY earlier update: the ones gated calls applied go in first
     if (int rc = fold_gate_counters(h)) return rc;
@@ -1866,6 +1867,7 @@ static int update_by_scans_device_nolock(hsm_ctx* h, int count, const float* d_p
   A.pts = reinterpret_cast<const float2*>(d_pts_xy);
   A.offsets = d_scan_offsets;
   A.shared_n = shared_n;
+  A.origos = reinterpret_cast<const float2*>(d_origos);  // per scan, on the device: the host pair below is then not read
   A.out = h->d_upd_batches;
   A.boxes = h->d_upd_boxes;
   size_t max_cells = 0;
@@ -1979,42 +1981,66 @@ int hsm_update_gate_state(hsm_ctx* h, float last_update_pose[3], long long* appl
   return HSM_OK;
 }
 
-int hsm_update_by_scans_device_gated(hsm_ctx* h, int count, const float* d_poses_world, const float* d_pts_xy,
-                                     const int* d_scan_offsets, int shared_n, int max_beams, const float origo[2],
-                                     const unsigned char* d_force, int* d_out_applied, void* stream) {
+static int update_by_scans_device_gated_impl(hsm_ctx* h, int count, const float* d_poses_world, const float* d_pts_xy,
+                                             const int* d_scan_offsets, int shared_n, int max_beams, const float origo[2],
+                                             const float* d_origos, const unsigned char* d_force, int* d_out_applied,
+                                             void* stream, const char* who) {
   if (!h) return fail(HSM_ERR_INVALID, "null context");
   std::lock_guard<std::mutex> lk(h->mu);
   GateCall gate;
   gate.d_force = d_force;
   gate.d_out_applied = d_out_applied;
   return update_by_scans_device_nolock(h, count, d_poses_world, d_pts_xy, d_scan_offsets, shared_n, max_beams, origo,
-                                       static_cast<hipStream_t>(stream), &gate);
+                                       static_cast<hipStream_t>(stream), &gate, d_origos, who);
 }
 
-// HectorSlamProcessor::update for a log of scans (HectorSlamProcessor.h:71-95), queued whole.  Everything runs on the context's
-// own stream -- the matches too, so a scan costs no event hop: the caller's stream is waited for once, in front, and waits once,
-// behind.  Per scan: the exact batch matcher on a batch of one, reading its hint from the gate's device block; then the gated
-// update of that one scan, whose gate launch also settles a forced scan's pose and covariance and leaves the next scan's hint.
-int hsm_slam_scans_device(hsm_ctx* h, int count, const float* d_start_pose, const float* d_hint_deltas, const float* d_pts_xy,
-                          const int* d_scan_offsets, int max_beams, const float origo[2], const unsigned char* d_force,
-                          float* d_out_pose, float* d_out_cov, int* d_out_applied, void* stream) {
-  if (!h) return fail(HSM_ERR_INVALID, "null context");
-  if (count < 0 || max_beams < 0 || (count > 0 && (!d_scan_offsets || !d_out_pose)))
-    return fail(HSM_ERR_INVALID, "hsm_slam_scans_device: bad argument");
-  if (count == 0) return HSM_OK;
-  std::lock_guard<std::mutex> lk(h->mu);
-  if (int rc = select_device(h)) return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
+int hsm_update_by_scans_device_gated(hsm_ctx* h, int count, const float* d_poses_world, const float* d_pts_xy,
+                                     const int* d_scan_offsets, int shared_n, int max_beams, const float origo[2],
+                                     const unsigned char* d_force, int* d_out_applied, void* stream) {
+  return update_by_scans_device_gated_impl(h, count, d_poses_world, d_pts_xy, d_scan_offsets, shared_n, max_beams, origo, nullptr,
+                                           d_force, d_out_applied, stream, "hsm_update_by_scans_device");
+}
+
+int hsm_update_by_scans_device_gated_origos(hsm_ctx* h, int count, const float* d_poses_world, const float* d_pts_xy,
+                                            const int* d_scan_offsets, int shared_n, int max_beams, const float* d_origos,
+                                            const unsigned char* d_force, int* d_out_applied, void* stream) {
+  return update_by_scans_device_gated_impl(h, count, d_poses_world, d_pts_xy, d_scan_offsets, shared_n, max_beams, nullptr,
+                                           d_origos, d_force, d_out_applied, stream, "hsm_update_by_scans_device_gated_origos");
+}
+
+// the refusals of a scan-log call, before anything is queued: `s` or a stream this context has matched on is being captured
+static int slam_refuse_capture(hsm_ctx* h, hipStream_t s, const char* who) {
   if (stream_capturing(s))
-    return fail(HSM_ERR_INVALID, "hsm_slam_scans_device: `stream` is being captured into a graph (map updates are not captured)");
-  for (const hsm_ctx::ForeignStream& f : h->foreign)  // refused before anything is queued (order_after_foreign_match)
+    return fail(HSM_ERR_INVALID, (std::string(who) + ": `stream` is being captured into a graph (map updates are not captured)").c_str());
+  for (const hsm_ctx::ForeignStream& f : h->foreign)  // (order_after_foreign_match)
     if (stream_capturing(f.s))
-      return fail(HSM_ERR_INVALID, "hsm_slam_scans_device: a caller's stream that this context matches on is being captured into a graph");
-  if (s != h->stream) {  // the inputs are complete where the caller's stream stands now
-    if (!h->evt_inputs) HIP_TRY(hipEventCreateWithFlags(&h->evt_inputs, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(h->evt_inputs, s));
-    HIP_TRY(hipStreamWaitEvent(h->stream, h->evt_inputs, 0));
-  }
+      return fail(HSM_ERR_INVALID, (std::string(who) + ": a caller's stream that this context matches on is being captured into a graph").c_str());
+  return HSM_OK;
+}
+
+// the context's stream behind the caller's (the inputs are complete where `s` stands now) ...
+static int slam_wait_for_caller(hsm_ctx* h, hipStream_t s) {
+  if (s == h->stream) return HSM_OK;
+  if (!h->evt_inputs) HIP_TRY(hipEventCreateWithFlags(&h->evt_inputs, hipEventDisableTiming));
+  HIP_TRY(hipEventRecord(h->evt_inputs, s));
+  HIP_TRY(hipStreamWaitEvent(h->stream, h->evt_inputs, 0));
+  return HSM_OK;
+}
+
+// ... and the caller's behind the context's (the results are complete where the context's stream stands now)
+static int slam_caller_waits(hsm_ctx* h, hipStream_t s) {
+  if (s == h->stream) return HSM_OK;
+  if (!h->evt_slam_done) HIP_TRY(hipEventCreateWithFlags(&h->evt_slam_done, hipEventDisableTiming));
+  HIP_TRY(hipEventRecord(h->evt_slam_done, h->stream));
+  HIP_TRY(hipStreamWaitEvent(s, h->evt_slam_done, 0));
+  return HSM_OK;
+}
+
+// the loop itself, on the context's stream: `origo` the host pair for every scan, or `d_origos` [count*2] on the device
+static int slam_scans_queue(hsm_ctx* h, int count, const float* d_start_pose, const float* d_hint_deltas, const float* d_pts_xy,
+                            const int* d_scan_offsets, int max_beams, const float origo[2], const float* d_origos,
+                            const unsigned char* d_force, float* d_out_pose, float* d_out_cov, int* d_out_applied,
+                            const char* update_who) {
   hipLaunchKernelGGL(slam_begin_kernel, dim3(1), dim3(64), 0, h->stream, h->d_gate, d_start_pose, d_hint_deltas);
   HIP_TRY(hipGetLastError());
   for (int k = 0; k < count; ++k) {
@@ -2029,15 +2055,49 @@ int hsm_slam_scans_device(hsm_ctx* h, int count, const float* d_start_pose, cons
     gate.cov_io = d_out_cov ? d_out_cov + 9 * (size_t)k : nullptr;
     gate.next_delta = d_hint_deltas && k + 1 < count ? d_hint_deltas + 3 * (size_t)(k + 1) : nullptr;
     if (int rc = update_by_scans_device_nolock(h, 1, gate.pose_io, d_pts_xy, d_scan_offsets + k, 0, max_beams, origo, h->stream,
-                                               &gate))
+                                               &gate, d_origos ? d_origos + 2 * (size_t)k : nullptr, update_who))
       return rc;
   }
-  if (s != h->stream) {  // the results are complete where the context's stream stands now
-    if (!h->evt_slam_done) HIP_TRY(hipEventCreateWithFlags(&h->evt_slam_done, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(h->evt_slam_done, h->stream));
-    HIP_TRY(hipStreamWaitEvent(s, h->evt_slam_done, 0));
-  }
   return HSM_OK;
+}
+
+// HectorSlamProcessor::update for a log of scans (HectorSlamProcessor.h:71-95), queued whole.  Everything runs on the context's
+// own stream -- the matches too, so a scan costs no event hop: the caller's stream is waited for once, in front, and waits once,
+// behind.  Per scan: the exact batch matcher on a batch of one, reading its hint from the gate's device block; then the gated
+// update of that one scan, whose gate launch also settles a forced scan's pose and covariance and leaves the next scan's hint.
+static int slam_scans_device_impl(hsm_ctx* h, const char* who, int count, const float* d_start_pose, const float* d_hint_deltas,
+                                  const float* d_pts_xy, const int* d_scan_offsets, int max_beams, const float origo[2],
+                                  const float* d_origos, const unsigned char* d_force, float* d_out_pose, float* d_out_cov,
+                                  int* d_out_applied, void* stream) {
+  if (!h) return fail(HSM_ERR_INVALID, "null context");
+  if (count < 0 || max_beams < 0 || (count > 0 && (!d_scan_offsets || !d_out_pose)) || ((uintptr_t)d_origos & 7u) != 0)
+    return fail(HSM_ERR_INVALID, (std::string(who) + ": bad argument").c_str());
+  if (count == 0) return HSM_OK;
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (int rc = select_device(h)) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (int rc = slam_refuse_capture(h, s, who)) return rc;
+  if (int rc = slam_wait_for_caller(h, s)) return rc;
+  if (int rc = slam_scans_queue(h, count, d_start_pose, d_hint_deltas, d_pts_xy, d_scan_offsets, max_beams, origo, d_origos,
+                                d_force, d_out_pose, d_out_cov, d_out_applied,
+                                d_origos ? who : "hsm_update_by_scans_device"))  // (the parent entry keeps its texts)
+    return rc;
+  return slam_caller_waits(h, s);
+}
+
+int hsm_slam_scans_device(hsm_ctx* h, int count, const float* d_start_pose, const float* d_hint_deltas, const float* d_pts_xy,
+                          const int* d_scan_offsets, int max_beams, const float origo[2], const unsigned char* d_force,
+                          float* d_out_pose, float* d_out_cov, int* d_out_applied, void* stream) {
+  return slam_scans_device_impl(h, "hsm_slam_scans_device", count, d_start_pose, d_hint_deltas, d_pts_xy, d_scan_offsets, max_beams,
+                                origo, nullptr, d_force, d_out_pose, d_out_cov, d_out_applied, stream);
+}
+
+int hsm_slam_scans_device_origos(hsm_ctx* h, int count, const float* d_start_pose, const float* d_hint_deltas,
+                                 const float* d_pts_xy, const int* d_scan_offsets, int max_beams, const float* d_origos,
+                                 const unsigned char* d_force, float* d_out_pose, float* d_out_cov, int* d_out_applied,
+                                 void* stream) {
+  return slam_scans_device_impl(h, "hsm_slam_scans_device_origos", count, d_start_pose, d_hint_deltas, d_pts_xy, d_scan_offsets,
+                                max_beams, nullptr, d_origos, d_force, d_out_pose, d_out_cov, d_out_applied, stream);
 }
 
 int hsm_update_by_scans_device(hsm_ctx* h, int count, const float* d_poses_world, const float* d_pts_xy,
@@ -2046,6 +2106,15 @@ int hsm_update_by_scans_device(hsm_ctx* h, int count, const float* d_poses_world
   std::lock_guard<std::mutex> lk(h->mu);
   return update_by_scans_device_nolock(h, count, d_poses_world, d_pts_xy, d_scan_offsets, shared_n, max_beams, origo,
                                        static_cast<hipStream_t>(stream));
+}
+
+int hsm_update_by_scans_device_origos(hsm_ctx* h, int count, const float* d_poses_world, const float* d_pts_xy,
+                                      const int* d_scan_offsets, int shared_n, int max_beams, const float* d_origos,
+                                      void* stream) {
+  if (!h) return fail(HSM_ERR_INVALID, "null context");
+  std::lock_guard<std::mutex> lk(h->mu);
+  return update_by_scans_device_nolock(h, count, d_poses_world, d_pts_xy, d_scan_offsets, shared_n, max_beams, nullptr,
+                                       static_cast<hipStream_t>(stream), nullptr, d_origos, "hsm_update_by_scans_device_origos");
 }
 
 int hsm_update_by_scans(hsm_ctx* h, int count, const float* poses_world, const float* pts_xy, const int* scan_offsets,
@@ -2418,7 +2487,8 @@ static int launch_ingest_batch_ranges_tf(const double2* unit, int batch, const f
                                          float range_max, double range_cutoff, const double* d_tf_rows, int shared_tf,
                                          float sqr_laser_min_dist, float sqr_laser_max_dist, float laser_z_min,
                                          float laser_z_max, float scale_to_map, float* d_out_pts_xy, int* d_out_offsets,
-                                         int* d_out_counts, float* d_out_origo, hipStream_t s) {
+                                         int* d_out_counts, float* d_out_origo, hipStream_t s,
+                                         int* d_counts_copy = nullptr) {  // a second copy of the counts, by the offsets pass
   RangesTfParams P{};
   P.ranges = d_ranges;
   P.unit = unit;
@@ -2433,7 +2503,7 @@ static int launch_ingest_batch_ranges_tf(const double2* unit, int batch, const f
   hipLaunchKernelGGL(ranges_tf_gate_count_kernel, dim3(blocks), dim3(256), 0, s, P, d_out_counts,
                      reinterpret_cast<float2*>(d_out_origo));
   HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(ranges_offsets_kernel, dim3(1), dim3(1024), 0, s, d_out_counts, batch, d_out_offsets, (int*)nullptr);
+  hipLaunchKernelGGL(ranges_offsets_kernel, dim3(1), dim3(1024), 0, s, d_out_counts, batch, d_out_offsets, d_counts_copy);
   HIP_TRY(hipGetLastError());
   if (n > 0) {
     // (scan b writes below offsets[b] + n <= (b + 1) * n <= batch * n: inside the caller's endpoint array)
@@ -2525,6 +2595,121 @@ int hsm_match_batch_ranges_tf(hsm_ctx* h, int batch, const float* begin_world, c
   if (out_cov) HIP_TRY(hipMemcpyAsync(out_cov, d_cov, b_cov, hipMemcpyDeviceToHost, h->stream));
   if (out_counts) HIP_TRY(hipMemcpyAsync(out_counts, d_counts, b_counts, hipMemcpyDeviceToHost, h->stream));
   if (out_origo) HIP_TRY(hipMemcpyAsync(out_origo, d_origo, b_origo, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return HSM_OK;
+}
+
+// ---- a raw scan log through the tf conversion and the whole SLAM loop, one call ----
+
+size_t hsm_slam_ranges_tf_workspace(int count, int n) {  // (the layout: stage_layout.h)
+  SlamRangesTfLayout L;
+  return slam_ranges_tf_layout(count, n, &L) ? L.total : 0;
+}
+
+// The conversion's three launches and the loop of hsm_slam_scans_device_origos, all on the context's stream and under its lock;
+// `s` is waited for once in front and waits once behind.  Every check comes before the first launch; a geometry not seen before is
+// uploaded (on the context's stream, which is waited for) before anything is queued.
+static int slam_ranges_tf_nolock(hsm_ctx* h, const char* who, int count, const float* d_start_pose, const float* d_hint_deltas,
+                                 const float* d_ranges, int n, float angle_min, float angle_increment, float range_min,
+                                 float range_max, double range_cutoff, const double* d_tf_rows, int shared_tf,
+                                 float sqr_laser_min_dist, float sqr_laser_max_dist, float laser_z_min, float laser_z_max,
+                                 float scale_to_map, const unsigned char* d_force, float* d_out_pose, float* d_out_cov,
+                                 int* d_out_applied, int* d_out_counts, void* d_workspace, size_t workspace_bytes, hipStream_t s) {
+  SlamRangesTfLayout L;
+  if (!slam_ranges_tf_layout(count, n, &L)) return fail(HSM_ERR_TOO_LARGE, (std::string(who) + ": n > HSM_MAX_UPDATE_BEAMS or count * n > INT_MAX").c_str());
+  if (!d_workspace || workspace_bytes < L.total || ((uintptr_t)d_workspace & 7u) != 0)
+    return fail(HSM_ERR_INVALID, (std::string(who) + ": workspace smaller than hsm_slam_ranges_tf_workspace(count, n) or not 8-byte aligned").c_str());
+  if (int rc = select_device(h)) return rc;
+  if (int rc = slam_refuse_capture(h, s, who)) return rc;
+  const double2* unit = nullptr;
+  if (int rc = ranges_tf_unit_table(h, who, n, angle_min, angle_increment, h->stream, &unit)) return rc;
+  if (int rc = slam_wait_for_caller(h, s)) return rc;
+  char* ws = (char*)d_workspace;
+  float* pts = reinterpret_cast<float*>(ws + L.pts);
+  int* offsets = reinterpret_cast<int*>(ws + L.offsets);
+  float* origos = reinterpret_cast<float*>(ws + L.origos);
+  if (int rc = launch_ingest_batch_ranges_tf(unit, count, d_ranges, n, range_min, range_max, range_cutoff, d_tf_rows, shared_tf,
+                                             sqr_laser_min_dist, sqr_laser_max_dist, laser_z_min, laser_z_max, scale_to_map, pts,
+                                             offsets, reinterpret_cast<int*>(ws + L.counts), origos, h->stream, d_out_counts))
+    return rc;
+  // n is a true bound of every scan's length after the gates
+  if (int rc = slam_scans_queue(h, count, d_start_pose, d_hint_deltas, pts, offsets, n, nullptr, origos, d_force, d_out_pose,
+                                d_out_cov, d_out_applied, who))
+    return rc;
+  return slam_caller_waits(h, s);
+}
+
+int hsm_slam_ranges_tf_device(hsm_ctx* h, int count, const float* d_start_pose, const float* d_hint_deltas, const float* d_ranges,
+                              int n, float angle_min, float angle_increment, float range_min, float range_max, double range_cutoff,
+                              const double* d_tf_rows, int shared_tf, float sqr_laser_min_dist, float sqr_laser_max_dist,
+                              float laser_z_min, float laser_z_max, float scale_to_map, const unsigned char* d_force,
+                              float* d_out_pose, float* d_out_cov, int* d_out_applied, int* d_out_counts, void* d_workspace,
+                              size_t workspace_bytes, void* stream) {
+  static const char who[] = "hsm_slam_ranges_tf_device";
+  if (!h) return fail(HSM_ERR_INVALID, "null context");
+  if ((count > 0 && !d_out_pose) || ((uintptr_t)d_tf_rows & 7u) != 0)
+    return fail(HSM_ERR_INVALID, "hsm_slam_ranges_tf_device: bad argument");
+  if (int rc = check_batch_ranges_tf(who, count, d_ranges, n, d_tf_rows)) return rc;
+  if (count == 0) return HSM_OK;
+  std::lock_guard<std::mutex> lk(h->mu);
+  return slam_ranges_tf_nolock(h, who, count, d_start_pose, d_hint_deltas, d_ranges, n, angle_min, angle_increment, range_min,
+                               range_max, range_cutoff, d_tf_rows, shared_tf, sqr_laser_min_dist, sqr_laser_max_dist, laser_z_min,
+                               laser_z_max, scale_to_map, d_force, d_out_pose, d_out_cov, d_out_applied, d_out_counts, d_workspace,
+                               workspace_bytes, static_cast<hipStream_t>(stream));
+}
+
+int hsm_slam_ranges_tf(hsm_ctx* h, int count, const float* start_pose, const float* hint_deltas, const float* ranges, int n,
+                       float angle_min, float angle_increment, float range_min, float range_max, double range_cutoff,
+                       const double* tf_rows, int shared_tf, float sqr_laser_min_dist, float sqr_laser_max_dist, float laser_z_min,
+                       float laser_z_max, float scale_to_map, const unsigned char* force, float* out_pose, float* out_cov,
+                       int* out_applied, int* out_counts, float* out_origo) {
+  static const char who[] = "hsm_slam_ranges_tf";
+  if (!h) return fail(HSM_ERR_INVALID, "null context");
+  if (count > 0 && !out_pose) return fail(HSM_ERR_INVALID, "hsm_slam_ranges_tf: bad argument");
+  if (int rc = check_batch_ranges_tf(who, count, ranges, n, tf_rows)) return rc;
+  if (count == 0) return HSM_OK;
+  SlamRangesTfLayout L;
+  slam_ranges_tf_layout(count, n, &L);  // (the sizes passed check_batch_ranges_tf)
+  const size_t b3 = (size_t)count * 3 * sizeof(float), b_cov = (size_t)count * 9 * sizeof(float);
+  const size_t b_int = (size_t)count * sizeof(int), b_ranges = (size_t)count * n * sizeof(float);
+  const size_t b_tf = (shared_tf ? 1 : (size_t)count) * 12 * sizeof(double), b_origo = (size_t)count * 2 * sizeof(float);
+  // device block: transforms | start pose | hint deltas | force | poses | covariances | applied | counts | raw ranges | workspace
+  Carver c;
+  const size_t o_tf = c.take(b_tf), o_start = c.take(3 * sizeof(float)), o_deltas = c.take(b3), o_force = c.take((size_t)count);
+  const size_t o_pose = c.take(b3), o_cov = c.take(b_cov), o_applied = c.take(b_int), o_counts = c.take(b_int);
+  const size_t o_ranges = c.take(b_ranges), o_ws = c.take(L.total);
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (int rc = select_device(h)) return rc;
+  if (int rc = slam_refuse_capture(h, h->stream, who)) return rc;  // (before the copies are queued)
+  if (!h->d_rbatch.holds(c.total())) HIP_TRY(hipStreamSynchronize(h->stream));
+  if (int rc = h->d_rbatch.reserve(c.total())) return rc;
+  char* base = h->d_rbatch;
+  double* d_tf = (double*)(base + o_tf);
+  float* d_start = (float*)(base + o_start);
+  float* d_deltas = (float*)(base + o_deltas);
+  unsigned char* d_force = (unsigned char*)(base + o_force);
+  float* d_pose = (float*)(base + o_pose);
+  float* d_cov = (float*)(base + o_cov);
+  int* d_applied = (int*)(base + o_applied);
+  int* d_counts = (int*)(base + o_counts);
+  float* d_ranges = (float*)(base + o_ranges);
+  HIP_TRY(hipMemcpyAsync(d_tf, tf_rows, b_tf, hipMemcpyHostToDevice, h->stream));
+  if (start_pose) HIP_TRY(hipMemcpyAsync(d_start, start_pose, 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  if (hint_deltas) HIP_TRY(hipMemcpyAsync(d_deltas, hint_deltas, b3, hipMemcpyHostToDevice, h->stream));
+  if (force) HIP_TRY(hipMemcpyAsync(d_force, force, (size_t)count, hipMemcpyHostToDevice, h->stream));
+  if (b_ranges) HIP_TRY(hipMemcpyAsync(d_ranges, ranges, b_ranges, hipMemcpyHostToDevice, h->stream));
+  if (out_cov) HIP_TRY(hipMemcpyAsync(d_cov, out_cov, b_cov, hipMemcpyHostToDevice, h->stream));  // in/out (empty scans)
+  if (int rc = slam_ranges_tf_nolock(h, who, count, start_pose ? d_start : nullptr, hint_deltas ? d_deltas : nullptr, d_ranges, n,
+                                     angle_min, angle_increment, range_min, range_max, range_cutoff, d_tf, shared_tf,
+                                     sqr_laser_min_dist, sqr_laser_max_dist, laser_z_min, laser_z_max, scale_to_map,
+                                     force ? d_force : nullptr, d_pose, out_cov ? d_cov : nullptr, out_applied ? d_applied : nullptr,
+                                     out_counts ? d_counts : nullptr, base + o_ws, L.total, h->stream))
+    return rc;
+  HIP_TRY(hipMemcpyAsync(out_pose, d_pose, b3, hipMemcpyDeviceToHost, h->stream));
+  if (out_cov) HIP_TRY(hipMemcpyAsync(out_cov, d_cov, b_cov, hipMemcpyDeviceToHost, h->stream));
+  if (out_applied) HIP_TRY(hipMemcpyAsync(out_applied, d_applied, b_int, hipMemcpyDeviceToHost, h->stream));
+  if (out_counts) HIP_TRY(hipMemcpyAsync(out_counts, d_counts, b_int, hipMemcpyDeviceToHost, h->stream));
+  if (out_origo) HIP_TRY(hipMemcpyAsync(out_origo, base + o_ws + L.origos, b_origo, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   return HSM_OK;
 }

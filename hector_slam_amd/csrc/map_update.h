@@ -746,6 +746,8 @@ struct UpdatePrepParams {
   const float2* pts;
   const int* offsets;        // [count + 1] CSR offsets in points, or nullptr: every pose integrates pts[0 .. shared_n)
   int shared_n;
+  const float2* origos;      // [count] the containers' origos in level-0 cell units, level l sees origos[k] * 2^-l (setFrom :48);
+                             // or nullptr: the host pair UpdatePrepLevel::origo_x/y for every scan
   UpdateBatch* out;          // [count]
   int* boxes;                // [(count + 2) * kMaxLevels * 4]: slot 0 the running dirty boxes, slot 1 the LAST scan's, 2 + k scan k's
 };
@@ -754,9 +756,11 @@ struct UpdatePrepParams {
 __host__ __device__ __forceinline__ int update_box_slot(int k, int count) { return k == count - 1 ? 1 : 2 + k; }
 
 // scan k's UpdateParams of level l and its (empty) box: points [first, first + n) of A.pts at `pose`, marked with
-// update_index0 + 3 * rank + 1 / + 2 (currMarkFreeIndex / currMarkOccIndex, OccGridMapBase.h:123-124)
+// update_index0 + 3 * rank + 1 / + 2 (currMarkFreeIndex / currMarkOccIndex, OccGridMapBase.h:123-124).  `origo`: with
+// A.origos, the level-0 origo of the container this level integrates (the scan's own, or the retained scan's on the coarse
+// levels of a forced scan); not read otherwise.
 __device__ __forceinline__ void update_prep_scan_level(const UpdatePrepParams& A, int k, int l, float px, float py, float th,
-                                                       int first, int n, int rank) {
+                                                       int first, int n, int rank, float2 origo) {
   const UpdatePrepLevel& V = A.lv[l];
   UpdateParams P;
   P.lv = V.lv;
@@ -771,8 +775,12 @@ __device__ __forceinline__ void update_prep_scan_level(const UpdatePrepParams& A
   P.pose.l11 = cosA;
   P.pose.t0 = mx;
   P.pose.t1 = my;
+  // setFrom's origo * factor (DataPointContainer.h:48): one fp32 multiply per component, level 0 takes the origo as it is --
+  // the expression the host evaluates for the pair it passes
+  const float ox = A.origos == nullptr ? V.origo_x : (l == 0 ? origo.x : origo.x * V.pt_scale);
+  const float oy = A.origos == nullptr ? V.origo_y : (l == 0 ? origo.y : origo.y * V.pt_scale);
   float bx, by;
-  affine_apply(P.pose, V.origo_x, V.origo_y, bx, by);
+  affine_apply(P.pose, ox, oy, bx, by);
   bx += 0.5f;
   by += 0.5f;
   // x86's truncating conversion makes a NaN or out-of-range begin coordinate INT_MIN, which fails the map test of every beam;
@@ -810,7 +818,8 @@ __global__ void __launch_bounds__(64) update_prep_kernel(const UpdatePrepParams 
     n = A.offsets[k + 1] - first;
   }
   // every scan is integrated: scan k is update k of the call
-  update_prep_scan_level(A, k, l, A.poses_world[3 * k], A.poses_world[3 * k + 1], A.poses_world[3 * k + 2], first, n, k);
+  const float2 origo = A.origos ? A.origos[k] : make_float2(0.0f, 0.0f);
+  update_prep_scan_level(A, k, l, A.poses_world[3 * k], A.poses_world[3 * k + 1], A.poses_world[3 * k + 2], first, n, k, origo);
 }
 
 // ---- the movement gate in front of them (hsm_update_by_scans_device_gated, hsm_slam_scans_device) -------------------------------
@@ -831,8 +840,10 @@ struct GateState {
   float last_pose[3];         // lastScanMatchPose                                   [retained_first, + retained_n) of this
   int retained_n;             //                                                     call's d_pts_xy
   float last_cov[9];          // lastScanMatchCov
-  int reserved[3];
+  float retained_origo[2];    // the retained scan's origo, level-0 cell units (setFrom copies it with the points, :48); read
+  int reserved[1];            // only by calls that carry per-scan origos
 };
+static_assert(sizeof(GateState) == 24 * 4, "GateState: six 16-byte rows");
 
 struct UpdateGateParams {
   UpdatePrepParams prep;
@@ -851,17 +862,21 @@ constexpr int kGateChunk = 256;
 
 __global__ void __launch_bounds__(256) update_gate_prep_kernel(const UpdateGateParams G) {
   __shared__ int4 walk[kGateChunk];  // {integrated, rank, first point of the coarse levels' container, its length}
+  __shared__ float2 walk_origo[kGateChunk];  // that container's origo (per-scan origos only)
   const UpdatePrepParams& A = G.prep;
   GateWalk w;
   gate_reset(w);
-  int ret_first = 0, ret_n = 0;
+  GateRetained ret;
+  gate_retained_reset(ret);
   if (threadIdx.x == 0) {
     w.last_update_pose[0] = G.state->last_update_pose[0];
     w.last_update_pose[1] = G.state->last_update_pose[1];
     w.last_update_pose[2] = G.state->last_update_pose[2];
     w.applied = G.state->pending;
-    ret_first = G.state->retained_first;
-    ret_n = G.state->retained_n;
+    ret.first = G.state->retained_first;
+    ret.n = G.state->retained_n;
+    ret.origo[0] = G.state->retained_origo[0];
+    ret.origo[1] = G.state->retained_origo[1];
   }
   for (int k0 = 0; k0 < A.count; k0 += kGateChunk) {
     const int chunk = min(kGateChunk, A.count - k0);
@@ -874,17 +889,15 @@ __global__ void __launch_bounds__(256) update_gate_prep_kernel(const UpdateGateP
           first = A.offsets[k];
           n = A.offsets[k + 1] - first;
         }
+        const float2 own = A.origos ? A.origos[k] : make_float2(0.0f, 0.0f);
         float pose[3];
         if (G.slam) {
           // a forced scan skips the match (HectorSlamProcessor.h:75-80): its pose is its hint, the covariance stays, and the
           // coarse levels keep the containers of the last matched scan
           for (int i = 0; i < 3; ++i) pose[i] = force ? G.state->hint[i] : G.pose_io[3 * k + i];
-          if (force) {
+          if (force)
             for (int i = 0; i < 3; ++i) G.pose_io[3 * k + i] = pose[i];
-          } else {
-            ret_first = first;
-            ret_n = n;
-          }
+          gate_retain_step(ret, force, first, n, own.x, own.y);
           if (G.cov_io) {
             for (int i = 0; i < 9; ++i) {
               if (force)
@@ -899,12 +912,12 @@ __global__ void __launch_bounds__(256) update_gate_prep_kernel(const UpdateGateP
           }
         } else {
           for (int i = 0; i < 3; ++i) pose[i] = A.poses_world[3 * k + i];
-          ret_first = first;  // every level sees the scan itself, as in hsm_update_by_scans_device
-          ret_n = n;
+          gate_retain_step(ret, false, first, n, own.x, own.y);  // every level sees the scan itself, as in hsm_update_by_scans_device
         }
         int rank;
         const bool go = gate_step(w, pose, force, G.min_dist, G.min_angle, &rank);
-        walk[j] = make_int4(go ? 1 : 0, rank, ret_first, ret_n);
+        walk[j] = make_int4(go ? 1 : 0, rank, ret.first, ret.n);
+        walk_origo[j] = make_float2(ret.origo[0], ret.origo[1]);
         if (G.out_applied) G.out_applied[k] = go ? 1 : 0;
       }
     }
@@ -917,12 +930,14 @@ __global__ void __launch_bounds__(256) update_gate_prep_kernel(const UpdateGateP
         first = A.offsets[k];
         n = A.offsets[k + 1] - first;
       }
+      float2 origo = A.origos ? A.origos[k] : make_float2(0.0f, 0.0f);
       if (l > 0) {
         first = d.z;
         n = d.w;
+        origo = walk_origo[j];
       }
       const float* pose = G.slam ? G.pose_io + 3 * k : A.poses_world + 3 * k;
-      update_prep_scan_level(A, k, l, pose[0], pose[1], pose[2], first, d.x ? n : 0, d.y);
+      update_prep_scan_level(A, k, l, pose[0], pose[1], pose[2], first, d.x ? n : 0, d.y, origo);
     }
     __syncthreads();
   }
@@ -931,8 +946,10 @@ __global__ void __launch_bounds__(256) update_gate_prep_kernel(const UpdateGateP
     G.state->last_update_pose[1] = w.last_update_pose[1];
     G.state->last_update_pose[2] = w.last_update_pose[2];
     G.state->pending = w.applied;
-    G.state->retained_first = ret_first;
-    G.state->retained_n = ret_n;
+    G.state->retained_first = ret.first;
+    G.state->retained_n = ret.n;
+    G.state->retained_origo[0] = ret.origo[0];
+    G.state->retained_origo[1] = ret.origo[1];
   }
 }
 
@@ -956,6 +973,7 @@ __global__ void slam_begin_kernel(GateState* state, const float* __restrict__ st
   if (threadIdx.x == 0) {
     state->retained_first = 0;
     state->retained_n = 0;
+    state->retained_origo[0] = state->retained_origo[1] = 0.0f;
   }
 }
 

@@ -49,6 +49,25 @@ inline bool ranges_layout(int batch, int n, RangesLayout* L) {
   return true;
 }
 
+// workspace of hsm_slam_ranges_tf_device, byte offsets: counts[count] | offsets[count + 1] | origos[count * 2] |
+// endpoints[max(count * n, 1)] -- the outputs of the tf conversion, which the scan loop reads where they lie.  false = sizes the
+// entry refuses (those of the conversion).
+struct SlamRangesTfLayout {
+  size_t counts, offsets, origos, pts, total;
+};
+
+inline bool slam_ranges_tf_layout(int count, int n, SlamRangesTfLayout* L) {
+  if (count < 0 || n < 0 || n > HSM_MAX_UPDATE_BEAMS || (size_t)count * (size_t)n > (size_t)INT_MAX) return false;
+  const size_t cn = (size_t)count * (size_t)n;
+  Carver c;
+  L->counts = c.take((size_t)count * sizeof(int));
+  L->offsets = c.take(((size_t)count + 1) * sizeof(int));
+  L->origos = c.take((size_t)count * 2 * sizeof(float));
+  L->pts = c.take((cn > 0 ? cn : 1) * 2 * sizeof(float));
+  L->total = c.total();
+  return true;
+}
+
 // staging block of hsm_match_batch / hsm_match_score_batch.  Sizes in bytes, 0 for an array the call does not have (pose = begin).
 struct BatchBytes {
   size_t begin, pts, offs, cov;

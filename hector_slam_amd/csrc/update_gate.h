@@ -72,4 +72,30 @@ HSM_GATE_HD inline bool gate_step(GateWalk& g, const float pose[3], bool map_wit
   return true;
 }
 
+// What the coarse levels integrate (MapRepMultiMap.h:127,143): level 0 takes the scan's own container, level l >= 1 takes
+// dataContainers[l-1], the copy matchData's setFrom made of the last MATCHED scan -- its points AND its origo
+// (DataPointContainer.h:46-58).  Points [first, first + n) of the call's end points; origo in level-0 cell units, scaled by
+// 2^-l where a level uses it.  n == 0 until a scan of the call has been matched.
+struct GateRetained {
+  int first, n;
+  float origo[2];
+};
+
+HSM_GATE_HD inline void gate_retained_reset(GateRetained& r) {
+  r.first = r.n = 0;
+  r.origo[0] = r.origo[1] = 0.0f;
+}
+
+// One scan of HectorSlamProcessor::update's first half (:75-80) as the coarse levels see it: a scan that is matched (an empty
+// one too: setFrom runs before the matcher looks at the size) replaces the retained container, whether or not the gate lets it
+// through afterwards; a forced scan (`keeps`: the SLAM loop's map_without_matching) skips matchData and leaves it alone.
+// Where no matcher runs (the gated update at given poses) every scan replaces it: every level sees the scan itself.
+HSM_GATE_HD inline void gate_retain_step(GateRetained& r, bool keeps, int first, int n, float origo_x, float origo_y) {
+  if (keeps) return;
+  r.first = first;
+  r.n = n;
+  r.origo[0] = origo_x;
+  r.origo[1] = origo_y;
+}
+
 }  // namespace hsm

@@ -230,6 +230,18 @@ int hsm_update_by_scan_level(hsm_ctx* h, int level, const float pose_world[3],
 int hsm_update_by_scans_device(hsm_ctx* h, int count, const float* d_poses_world, const float* d_pts_xy,
                                const int* d_scan_offsets, int shared_n, int max_beams, const float origo[2],
                                void* stream);
+/* the same with one origo PER SCAN, on the device: a sensor whose mount moves against base_link (the node's tf path sets the
+ * container's origo from the laser -> base_link translation of every scan, HectorMappingRos.cpp:517).
+ *   d_origos       DEVICE [count*2] floats, scan k's origo in level-0 cell units, e.g. d_out_origo of
+ *                  hsm_ingest_batch_ranges_tf_device; level l sees d_origos[k] * 2^-l (DataPointContainer.h:48).  NULL = 0,0
+ *                  for every scan.  8-byte aligned (HSM_ERR_INVALID otherwise).  Complete on `stream` and unchanged until the
+ *                  update has run, like the other inputs.
+ * The origo is the begin cell of every Bresenham line of the scan (OccGridMapBase.h:134-137).  A NaN or infinite origo drops
+ * every beam of that scan, which still counts as an update, like a NaN pose.  With every pair equal to X the call is, bit for
+ * bit, hsm_update_by_scans_device with the host origo X; launches, ordering, refusals and counters are that entry's. */
+int hsm_update_by_scans_device_origos(hsm_ctx* h, int count, const float* d_poses_world, const float* d_pts_xy,
+                                      const int* d_scan_offsets, int shared_n, int max_beams, const float* d_origos,
+                                      void* stream);
 /* same with host arrays (copies in, then the same device path; returns when queued, the arrays may be reused at once):
  * builds a map from a log of posed scans in one call.  HSM_ERR_TOO_LARGE: a scan of more than HSM_MAX_UPDATE_BEAMS beams. */
 int hsm_update_by_scans(hsm_ctx* h, int count, const float* poses_world, const float* pts_xy,
@@ -266,10 +278,16 @@ int hsm_update_gate_state(hsm_ctx* h, float last_update_pose[3], long long* appl
  * not.  hsm_update_index and every host-side update called afterwards first wait for the stream to learn how many scans were
  * integrated.  hsm_last_update_bbox afterwards: the box of the call's LAST scan, empty where that one was rejected.
  * HSM_ERR_INVALID, nothing queued, while `stream` or a stream this context has matched on is being captured.
+ * A moving sensor mount passes its origos per scan through hsm_update_by_scans_device_gated_origos.
  * Not built: capture into graphs, replay through hsm_group_*, the byte-map (dense) form of the update. */
 int hsm_update_by_scans_device_gated(hsm_ctx* h, int count, const float* d_poses_world, const float* d_pts_xy,
                                      const int* d_scan_offsets, int shared_n, int max_beams, const float origo[2],
                                      const unsigned char* d_force, int* d_out_applied, void* stream);
+/* the same with d_origos as in hsm_update_by_scans_device_origos (DEVICE [count*2], NULL = 0,0): every level integrates scan k
+ * at its own origo.  Everything else is hsm_update_by_scans_device_gated's. */
+int hsm_update_by_scans_device_gated_origos(hsm_ctx* h, int count, const float* d_poses_world, const float* d_pts_xy,
+                                            const int* d_scan_offsets, int shared_n, int max_beams, const float* d_origos,
+                                            const unsigned char* d_force, int* d_out_applied, void* stream);
 /* replaces: for k = 0 .. count-1, in order: HectorSlamProcessor::update(container_k, hint_k, force_k)
  *           (HSL/slam_main/HectorSlamProcessor.h:71-95): matchData, the gate, updateByScan -- a log of scans in ONE call that
  *           returns when everything is queued.  The host waits for nothing and learns nothing.  DEVICE pointers:
@@ -291,12 +309,22 @@ int hsm_update_by_scans_device_gated(hsm_ctx* h, int count, const float* d_poses
  * front -- the inputs must be complete there -- and waits once behind, so work queued on it afterwards sees every result.
  * The gate's state persists on the device: two calls of 12 scans give what one call of 24 gives.
  * HSM_ERR_INVALID, nothing queued: a bad argument, or `stream` / a stream this context has matched on is being captured.
- * Does not touch the retained or the ingested scan.  Not built: capture into graphs, replay through hsm_group_*, the byte-map
- * (dense) form of the update; the C++ facade's HectorSlamProcessor.h stays reference code and does not call this. */
+ * Does not touch the retained or the ingested scan.  A moving sensor mount passes its origos per scan through
+ * hsm_slam_scans_device_origos.  Not built: capture into graphs, replay through hsm_group_*, the byte-map (dense) form of the
+ * update; the C++ facade's HectorSlamProcessor.h stays reference code and does not call this. */
 int hsm_slam_scans_device(hsm_ctx* h, int count, const float* d_start_pose, const float* d_hint_deltas,
                           const float* d_pts_xy, const int* d_scan_offsets, int max_beams, const float origo[2],
                           const unsigned char* d_force, float* d_out_pose, float* d_out_cov, int* d_out_applied,
                           void* stream);
+/* the same with d_origos as in hsm_update_by_scans_device_origos (DEVICE [count*2], NULL = 0,0).  The origo belongs to the
+ * container, so the reference's rule for a forced scan holds for it too: level 0 integrates the forced scan at its OWN origo,
+ * levels >= 1 integrate the points AND the origo of the last MATCHED scan (setFrom copies both, MapRepMultiMap.h:127,143).
+ * The retained origo lives in the gate's device block next to the retained scan; like it, it does not outlive the call.
+ * Everything else is hsm_slam_scans_device's. */
+int hsm_slam_scans_device_origos(hsm_ctx* h, int count, const float* d_start_pose, const float* d_hint_deltas,
+                                 const float* d_pts_xy, const int* d_scan_offsets, int max_beams, const float* d_origos,
+                                 const unsigned char* d_force, float* d_out_pose, float* d_out_cov, int* d_out_applied,
+                                 void* stream);
 
 /* ---- single-process multi-GPU group (extension; the reference has no multi-device path) ------------------
  * One replica of the pyramid per listed device (a device may be listed more than once).  Batched matching is
@@ -524,8 +552,8 @@ int hsm_match_batch_ranges(hsm_ctx* h, int batch, const float* begin_world, cons
  *                  entry's only scratch
  *   d_out_origo    [B*2] or NULL: origo of scan b = float(t_x, t_y) * scale_to_map (:517)
  * The outputs are exactly the d_pts_xy / d_scan_offsets arguments of hsm_match_batch_device, hsm_score_batch_device,
- * hsm_match_score_batch_device, hsm_update_by_scans_device[_gated] and hsm_slam_scans_device; pass n as shared_n / max_beams,
- * it is a true bound of every scan's length.
+ * hsm_match_score_batch_device, hsm_update_by_scans_device[_gated][_origos] and hsm_slam_scans_device[_origos]; pass n as
+ * shared_n / max_beams, it is a true bound of every scan's length, and d_out_origo as d_origos of the *_origos entries.
  * The unit-vector table of the geometry (n, angle_min, angle_increment; keyed on their bit patterns) is evaluated on the host
  * with the double cos / sin that laser_geometry uses, uploaded once and kept until hsm_destroy.  A geometry not seen before
  * while `stream` is being captured into a graph returns HSM_ERR_INVALID and enqueues nothing (no allocation under capture: one
@@ -536,10 +564,8 @@ int hsm_match_batch_ranges(hsm_ctx* h, int batch, const float* begin_world, cons
  * HSM_ERR_INVALID, nothing launched: NULL context, batch < 0, n < 0, NULL d_ranges with batch*n > 0, NULL d_tf_rows with
  * batch > 0, NULL d_out_pts_xy / d_out_offsets / d_out_counts, an unseen geometry under capture.  HSM_ERR_TOO_LARGE:
  * n > HSM_MAX_UPDATE_BEAMS or batch * n > INT_MAX.  batch == 0: HSM_OK, nothing written.
- * Not built: per-scan origos in the update and slam entries -- they take one HOST origo, so a log whose transform translation
- * is constant passes d_out_origo[0] (copied to the host) and a caller with a moving sensor mount splits the log; a fused
- * conversion + match device entry with a workspace (this call and hsm_match_batch_device on one stream are the same
- * launches); the C++ facade; hsm_group_*. */
+ * Not built: a fused conversion + match device entry with a workspace (this call and hsm_match_batch_device on one stream are
+ * the same launches; conversion + the whole scan loop in one call is hsm_slam_ranges_tf_device); the C++ facade; hsm_group_*. */
 int hsm_ingest_batch_ranges_tf_device(hsm_ctx* h, int batch, const float* d_ranges, int n, float angle_min,
                                       float angle_increment, float range_min, float range_max, double range_cutoff,
                                       const double* d_tf_rows, int shared_tf, float sqr_laser_min_dist,
@@ -557,6 +583,43 @@ int hsm_match_batch_ranges_tf(hsm_ctx* h, int batch, const float* begin_world, c
                               const double* tf_rows, int shared_tf, float sqr_laser_min_dist, float sqr_laser_max_dist,
                               float laser_z_min, float laser_z_max, float scale_to_map, float* out_pose, float* out_cov,
                               int* out_counts, float* out_origo);
+/* replaces: the node's scan callback for a LOG of raw scans (HectorMappingRos.cpp:257-282 + HectorSlamProcessor.h:71-95) --
+ *           hsm_ingest_batch_ranges_tf_device for the whole log, then hsm_slam_scans_device_origos on what it wrote, in ONE
+ *           call: raw ranges and a transform per scan in; poses, covariances, decisions and the map out.  The host waits for
+ *           nothing and learns nothing in between -- not a count, not an origo.
+ * Arguments as in the two entries (DEVICE pointers; d_start_pose / d_hint_deltas / d_force / d_out_cov / d_out_applied /
+ * d_out_counts may be NULL as there; d_out_counts [count] = beams each scan kept).  A scan that keeps no beam returns its hint
+ * as its pose, its covariance row is what hsm_match_batch_device writes for an empty scan.
+ *   d_workspace    caller-owned, 8-byte aligned, hsm_slam_ranges_tf_workspace(count, n) bytes: the conversion's counts, CSR
+ *                  offsets, origos and end points; the update reads them, so it stays unchanged until the call's work has run
+ * `stream` (the caller's, NULL = default stream) is waited for once in front -- the inputs must be complete there -- and waits
+ * once behind; the conversion's three launches and the loop's launches all go on the context's stream.  Ordering against
+ * other hsm_* calls is hsm_slam_scans_device's.  The geometry-table rules of hsm_ingest_batch_ranges_tf_device apply: a geometry
+ * not seen before is uploaded before anything is queued (that one call waits for the context's stream).
+ * Every argument is checked before the first launch.  HSM_ERR_INVALID, nothing queued: count < 0, n < 0, NULL d_out_pose,
+ * NULL d_ranges with count*n > 0, NULL or misaligned d_tf_rows, a workspace that is NULL, misaligned or too small, `stream` / a
+ * stream this context has matched on is being captured (updates are not captured; so an unseen geometry under capture is
+ * refused, too).  HSM_ERR_TOO_LARGE: n > HSM_MAX_UPDATE_BEAMS or count * n > INT_MAX.  count == 0: HSM_OK, nothing written.
+ * Not built: capture into graphs, replay through hsm_group_*, the byte-map (dense) form of the update, the non-tf conversion
+ * (rosLaserScanToDataContainer: its origo is always 0,0 -- hsm_match_batch_ranges_device's conversion and
+ * hsm_slam_scans_device cover it in two calls); the C++ facade's HectorSlamProcessor.h stays reference code. */
+int hsm_slam_ranges_tf_device(hsm_ctx* h, int count, const float* d_start_pose, const float* d_hint_deltas,
+                              const float* d_ranges, int n, float angle_min, float angle_increment, float range_min,
+                              float range_max, double range_cutoff, const double* d_tf_rows, int shared_tf,
+                              float sqr_laser_min_dist, float sqr_laser_max_dist, float laser_z_min, float laser_z_max,
+                              float scale_to_map, const unsigned char* d_force, float* d_out_pose, float* d_out_cov,
+                              int* d_out_applied, int* d_out_counts, void* d_workspace, size_t workspace_bytes, void* stream);
+/* bytes of that workspace (0 for sizes the entry refuses).  Host arithmetic only: callable without a device. */
+size_t hsm_slam_ranges_tf_workspace(int count, int n);
+/* the same with HOST pointers (start_pose [3] or NULL, hint_deltas [count*3] or NULL, ranges [count*n], tf_rows [count*12] or
+ * [12] with shared_tf, force [count] or NULL, out_pose [count*3], out_cov [count*9] or NULL (in/out), out_applied [count] or
+ * NULL, out_counts [count] or NULL, out_origo [count*2] or NULL): copies 4 B per beam and 96 B per scan in, makes the one
+ * device call on the context's stream, copies the results out; synchronous.  The staging block is the context's own. */
+int hsm_slam_ranges_tf(hsm_ctx* h, int count, const float* start_pose, const float* hint_deltas, const float* ranges, int n,
+                       float angle_min, float angle_increment, float range_min, float range_max, double range_cutoff,
+                       const double* tf_rows, int shared_tf, float sqr_laser_min_dist, float sqr_laser_max_dist,
+                       float laser_z_min, float laser_z_max, float scale_to_map, const unsigned char* force, float* out_pose,
+                       float* out_cov, int* out_applied, int* out_counts, float* out_origo);
 /* hsm_match / hsm_update_by_scan on the ingested scan (no endpoint upload; origo as ingested) */
 int hsm_match_ingested(hsm_ctx* h, const float begin_world[3], float out_pose_world[3], float cov[9]);
 int hsm_update_by_ingested(hsm_ctx* h, const float pose_world[3]);

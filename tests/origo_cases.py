@@ -1,0 +1,182 @@
+"""Inputs, references and non-vacuity guards shared by the tests of the per-scan origo entries
+(hsm_update_by_scans_device_origos, hsm_update_by_scans_device_gated_origos, hsm_slam_scans_device_origos) and of the one-call
+raw-log entry (hsm_slam_ranges_tf_device): test_origos_abi.py, test_origo_reference.py on the CPU, test_gpu_update_scans_origos.py
+and test_gpu_slam_ranges_tf.py on the device.
+
+The log: the first 24 of the 1081-beam build scans of the 16 m x 12 m room (seed 2024), on a 512 x 512 (or 500 x 360) 3-level
+map at 0.05 m; hint_k = pose_(k-1) + delta_k in fp32.  One origo per scan, drawn from +-0.3 m of mount translation: +-6 cells on
+level 0, +-1.5 cells on level 2, so the begin cell of the Bresenham lines differs between scans on every level."""
+import functools
+
+import numpy as np
+
+RES = 0.05
+LEVELS = 3
+N = 24
+GEOMS = {"square": (512, 512), "rect": (500, 360)}
+THRESHOLDS = {"default": (0.4, 0.13), "wide": (1.0, 0.3)}
+FLT_MAX = np.finfo(np.float32).max
+ZERO2 = np.zeros(2, np.float32)
+SCALE_TO_MAP = np.float32(1.0 / RES)  # GridMapBase::getScaleToMap
+
+
+@functools.lru_cache(maxsize=1)
+def trajectory():
+    from hector_slam_amd import synth
+    sc = synth.make_scene(n_beams=1081, map_size=512, levels=LEVELS, resolution=RES, n_build=64, n_query=8, room=(16.0, 12.0), seed=2024)
+    sc.poses = np.ascontiguousarray(sc.build_poses[:N], np.float32)
+    sc.scans = [np.ascontiguousarray(s, np.float32) for s in sc.build_scans[:N]]
+    sc.deltas = np.zeros((N, 3), np.float32)
+    sc.deltas[1:] = sc.poses[1:] - sc.poses[:-1]
+    # the origo of a container as the node sets it: float(t_x, t_y) * scaleToMap (HectorMappingRos.cpp:517)
+    t = np.random.default_rng(517).uniform(-0.3, 0.3, (N, 2))
+    sc.origos = np.ascontiguousarray(t.astype(np.float32) * SCALE_TO_MAP, np.float32)
+    return sc
+
+
+def force_mask():
+    """forced scans (map_without_matching): the first scan of the log -- the coarse containers are still empty --, and two
+    that follow a matched scan of another origo"""
+    f = np.zeros(N, np.uint8)
+    f[[0, 7, 15]] = 1
+    return f
+
+
+def new_refs(oracle_mod, geom="square", kinds=None):
+    from conftest import oracle_kinds
+    sx, sy = GEOMS[geom]
+    refs = {}
+    for kind in (kinds or oracle_kinds()):
+        o = oracle_mod.Oracle(kind, RES, sx, sy, LEVELS)
+        o.set_update_factor_free(0.4)
+        o.set_update_factor_occupied(0.9)
+        refs[kind] = o
+    return refs
+
+
+def ref_update(o, pose, pts, origo):
+    """one scan on every level of a checker: update_by_scan_level(l, pose, pts * 2^-l, origo * 2^-l), as setFrom scales both"""
+    for lvl in range(LEVELS):
+        f = np.float32(1.0 / 2.0 ** lvl)
+        o.update_by_scan_level(lvl, pose, np.asarray(pts, np.float32).reshape(-1, 2) * f, np.asarray(origo, np.float32) * f)
+    o.on_map_updated()
+
+
+class Gate:
+    """the Python loop over the checker's predicate: lastMapUpdatePose and the count"""
+
+    def __init__(self, checker, thresholds):
+        self.o, self.thr, self.last, self.count = checker, thresholds, np.float32([FLT_MAX] * 3), 0
+
+    def step(self, pose, forced=False):
+        go = self.o.pose_difference_larger_than(pose, self.last, self.thr[0], self.thr[1]) or bool(forced)
+        if go:
+            self.last, self.count = np.asarray(pose, np.float32).copy(), self.count + 1
+        return go
+
+    def walk(self, poses, force=None):
+        return np.array([self.step(p, force is not None and force[k]) for k, p in enumerate(np.asarray(poses, np.float32).reshape(-1, 3))])
+
+
+def reference_loop(o, thresholds, scans, origos, start, deltas, force=None):
+    """HectorSlamProcessor::update per scan on a checker -> (poses, covs, flags); origos [n, 2] or one pair for every scan"""
+    o.proc_set_thresholds(*thresholds)
+    gate = Gate(o, thresholds)
+    origos = np.broadcast_to(np.asarray(origos, np.float32), (len(scans), 2))
+    poses, covs, flags = [], [], []
+    pose = np.asarray(start, np.float32).copy()
+    for k, pts in enumerate(scans):
+        hint = (pose + deltas[k]).astype(np.float32) if deltas is not None else pose
+        forced = bool(force is not None and force[k])
+        o.proc_update(pts, hint, origos[k], forced)
+        pose, cov = o.proc_last_pose()
+        flags.append(gate.step(pose, forced))
+        poses.append(pose.copy())
+        covs.append(cov.copy())
+    return np.array(poses), np.array(covs), np.array(flags)
+
+
+def assert_gate_is_exercised(flags, what):
+    flags = np.asarray(flags, bool)
+    assert flags.sum() >= 6 and (~flags).sum() >= 6, (what, "the reference must both integrate and reject at least 6 scans", flags.astype(int))
+
+
+def level_planes(o):
+    return [o.download_level(lvl)[0].copy() for lvl in range(LEVELS)]
+
+
+@functools.lru_cache(maxsize=4)
+def _origo_dependence(kind):
+    from oracle import pyoracle
+    from conftest import bits
+    sc = trajectory()
+    out = {}
+    for name, thr in THRESHOLDS.items():
+        planes = []
+        for origos in (sc.origos, sc.origos[0]):
+            o = new_refs(pyoracle, kinds=[kind])[kind]
+            _, _, flags = reference_loop(o, thr, sc.scans, origos, sc.poses[0], sc.deltas)
+            planes.append(level_planes(o))
+            if kind == "ho":
+                assert o.undefined_reads() == 0
+            o.close()
+            if origos is sc.origos:
+                out[name] = flags
+        out[name + " differing cells"] = [int((bits(a) != bits(b)).sum()) for a, b in zip(*planes)]
+    return out
+
+
+def assert_the_reference_depends_on_the_origo(kind):
+    """The non-vacuity guard of every test here: on these inputs the checker's final log-odds planes differ on EVERY level between
+    the log with its per-scan origos and the log with origo[0] for every scan, and at both threshold pairs its gate integrates
+    and rejects at least 6 of the 24 scans.  Computed once per checker kind."""
+    r = _origo_dependence(kind)
+    for name in THRESHOLDS:
+        assert_gate_is_exercised(r[name], (kind, name))
+        assert all(c > 0 for c in r[name + " differing cells"]), (kind, name, r[name + " differing cells"])
+    return r
+
+
+# ---- raw scans and a moving mount ------------------------------------------------------------------------------------------------
+NODE_GATES0 = (0.4, 30.0, -1.0, 1.0)  # tests/test_node_rows.py NODE_GATES[0]: the node's default laser_min/max_dist, z gates
+
+
+def gate_args(gates=NODE_GATES0):
+    return (np.float32(gates[0] * gates[0]), np.float32(gates[1] * gates[1]), gates[2], gates[3])
+
+
+def moving_mount(rng):
+    """mount_rows of test_gpu_ranges_tf_batch.py with the translation drawn from +-0.3 m: small roll / pitch / yaw, 12 doubles
+    [R | t] -> (rows, (t_x, t_y, yaw))"""
+    r, p, y = rng.uniform(-0.03, 0.03), rng.uniform(-0.03, 0.03), rng.uniform(-0.02, 0.02)
+    cr, sr, cp, sp, cy, sy = np.cos(r), np.sin(r), np.cos(p), np.sin(p), np.cos(y), np.sin(y)
+    R = np.array([[cy * cp, cy * sp * sr - sy * cr, cy * sp * cr + sy * sr],
+                  [sy * cp, sy * sp * sr + cy * cr, sy * sp * cr - cy * sr],
+                  [-sp, cp * sr, cp * cr]])
+    t = np.array([rng.uniform(-0.3, 0.3), rng.uniform(-0.3, 0.3), rng.uniform(-0.05, 0.05)])
+    return np.concatenate([R, t[:, None]], 1).reshape(12), (t[0], t[1], y)
+
+
+@functools.lru_cache(maxsize=1)
+def raw_log():
+    """24 raw 1081-beam scans taken from the laser's place on its moving mount (1 cm noise, 2 % inf, 1 % NaN, one scan that
+    keeps no beam) -> (ranges [24, 1081], tf rows [24, 12], angle_min, angle_increment)"""
+    from hector_slam_amd import synth
+    sc = trajectory()
+    rng = np.random.default_rng(9)
+    n = 1081
+    ang = synth.beam_angles(n)
+    a0, inc = float(ang[0]), float(np.float32(synth.SCAN_SHAPES[n][1]))
+    rows, ranges = [], []
+    for p in sc.poses.astype(np.float64):
+        T, (tx, ty, yaw) = moving_mount(rng)
+        c, s = np.cos(p[2]), np.sin(p[2])
+        laser = np.array([p[0] + c * tx - s * ty, p[1] + s * tx + c * ty, p[2] + yaw])
+        rows.append(T)
+        ranges.append(sc.world.raycast(laser, ang))
+    r = (np.stack(ranges) + rng.normal(0.0, 0.01, (N, n))).astype(np.float32)
+    drop = rng.random(r.shape)
+    r[drop < 0.02] = np.inf
+    r[(drop >= 0.02) & (drop < 0.03)] = np.nan
+    r[5] = np.inf  # a scan that keeps no beam
+    return r, np.stack(rows), a0, inc

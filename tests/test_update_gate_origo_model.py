@@ -1,0 +1,112 @@
+"""What each level integrates when the scans of a log carry an origo each (hector_slam_amd/csrc/update_gate.h: gate_step and
+gate_retain_step, the text the device's gate kernel runs in one lane), on the CPU: tests/cpp/update_gate_origo_model.cpp compiles
+the header with the host compiler alone and walks a log of matched, forced and rejected scans with distinct origos.  Per scan
+the (first point, length, origo) of level 0 and of the coarse levels must equal a Python restatement of the reference:
+matchData copies the scan into dataContainers[l-1] -- points and origo, DataContainer::setFrom -- for every scan that is
+matched (MapRepMultiMap.h:127), a forced scan skips matchData (HectorSlamProcessor.h:75-80), and updateByScan gives level 0 the
+scan's own container and level l >= 1 dataContainers[l-1] (MapRepMultiMap.h:143).  Integers and copied floats: no tolerance."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FLT_MAX = np.finfo(np.float32).max
+REC = np.dtype([("pose", np.float32, 3), ("force", np.int32), ("first", np.int32), ("n", np.int32), ("origo", np.float32, 2)])
+SRC = [("first", np.int32), ("n", np.int32), ("origo", np.float32, 2)]
+OUT = np.dtype([("applied", np.int32), ("rank", np.int32), ("fine", SRC), ("coarse", SRC)])
+
+
+@pytest.fixture(scope="module")
+def model(tmp_path_factory):
+    exe = tmp_path_factory.mktemp("gate_origo") / "update_gate_origo_model"
+    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "hector_slam_amd", "csrc"),
+                    os.path.join(ROOT, "tests", "cpp", "update_gate_origo_model.cpp"), "-o", str(exe)], check=True)
+    return exe
+
+
+def run(model, tmp_path, thresholds, slam, rec):
+    src, dst = tmp_path / "log.bin", tmp_path / "out.bin"
+    with open(src, "wb") as f:
+        f.write(np.float32(thresholds).tobytes())
+        f.write(np.int32(slam).tobytes())
+        f.write(rec.tobytes())
+    subprocess.run([str(model), str(src), str(dst)], check=True)
+    out = np.fromfile(dst, OUT)
+    assert out.size == rec.size
+    return out
+
+
+def larger(p1, p2, dist, angle):
+    """util::poseDifferenceLargerThan for the finite, unwrapped poses of this log (tests/test_update_gate_model.py holds the
+    header's predicate to the checkers on everything else)"""
+    d = np.float32(p1) - np.float32(p2)
+    with np.errstate(over="ignore"):
+        if np.sqrt(np.float32(d[0] * d[0]) + np.float32(d[1] * d[1])) > np.float32(dist):
+            return True
+    return bool(abs(d[2]) > np.float32(angle))
+
+
+def reference_walk(rec, thresholds, slam):
+    """HectorSlamProcessor::update over the log -> per scan (applied, rank, level 0's container, the coarse levels')"""
+    containers = (0, 0, (0.0, 0.0))  # dataContainers[l-1] before the first matchData: empty
+    last, count, rows = np.float32([FLT_MAX] * 3), 0, []
+    for r in rec:
+        own = (int(r["first"]), int(r["n"]), (float(r["origo"][0]), float(r["origo"][1])))
+        forced = bool(r["force"])
+        if not (slam and forced):
+            containers = own  # :127, setFrom: the points and the origo
+        go = larger(r["pose"], last, *thresholds) or forced
+        rows.append((go, count, own, containers))
+        if go:
+            last, count = r["pose"].copy(), count + 1
+    return rows
+
+
+def make_log():
+    """forced first in the call; matched and rejected scans; a forced scan straight after a matched one with another origo;
+    an empty matched scan followed by a forced one; two forced scans in a row"""
+    n = 16
+    rec = np.zeros(n, REC)
+    rng = np.random.default_rng(3)
+    lens = rng.integers(900, 1081, n)
+    rec["n"] = lens
+    rec["n"][9] = 0  # an empty scan that is matched ...
+    rec["first"] = np.concatenate([[0], np.cumsum(rec["n"])[:-1]])
+    rec["origo"] = (rng.uniform(-0.3, 0.3, (n, 2)).astype(np.float32) * np.float32(20.0))
+    step = np.float32([0.3, 0.02, 0.01])
+    rec["pose"] = np.cumsum(np.tile(step, (n, 1)), axis=0, dtype=np.float32)
+    rec["force"][[0, 4, 10, 13, 14]] = 1  # ... 10: forced right behind the empty matched scan 9
+    return rec
+
+
+@pytest.mark.parametrize("slam", [1, 0])
+@pytest.mark.parametrize("thresholds", [(0.4, 0.13), (1.0, 0.3)])
+def test_per_level_containers_equal_the_reference_rule(model, tmp_path, thresholds, slam):
+    rec = make_log()
+    assert len({tuple(o) for o in rec["origo"].view(np.uint32)}) == rec.size, "the origos must be distinct"
+    out = run(model, tmp_path, thresholds, slam, rec)
+    want = reference_walk(rec, thresholds, slam)
+    for k, (o, (go, rank, own, cont)) in enumerate(zip(out, want)):
+        assert bool(o["applied"]) == go and o["rank"] == rank, (k, o, go, rank)
+        for name, src in (("fine", own), ("coarse", cont)):
+            got = o[name]
+            assert got["first"] == src[0] and got["n"] == (src[1] if go else 0), (k, name, got, src)
+            assert np.array_equal(got["origo"].view(np.uint32), np.float32(src[2]).view(np.uint32)), (k, name, got, src)
+    flags = out["applied"].astype(bool)
+    forced = rec["force"].astype(bool)  # matched-and-integrated, forced and rejected scans all occur
+    assert (flags & ~forced).any() and forced.sum() == 5 and (~flags).sum() >= 3, flags.astype(int)
+    if slam:
+        # forced first in the call: the coarse levels find an empty container
+        assert flags[0] and out["coarse"]["n"][0] == 0 and out["fine"]["n"][0] == rec["n"][0]
+        # forced straight after a matched scan: level 0 its own origo, the coarse levels the matched scan's -- and they differ
+        for k in (4, 14):
+            prev = k - 1 if not rec["force"][k - 1] else k - 2
+            assert np.array_equal(out["coarse"]["origo"][k], rec["origo"][prev]) and out["coarse"]["first"][k] == rec["first"][prev]
+            assert not np.array_equal(out["coarse"]["origo"][k], out["fine"]["origo"][k])
+        # the empty matched scan 9 replaced the container: forced scan 10 integrates nothing on the coarse levels, at 9's origo
+        assert flags[10] and out["coarse"]["n"][10] == 0 and np.array_equal(out["coarse"]["origo"][10], rec["origo"][9])
+        assert out["fine"]["n"][10] == rec["n"][10] > 0
+    else:
+        assert np.array_equal(out["coarse"]["origo"], out["fine"]["origo"]) and np.array_equal(out["coarse"]["first"], out["fine"]["first"])

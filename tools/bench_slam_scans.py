@@ -8,6 +8,14 @@ costs the queued form its gate launch and two launches that return at once, and 
 Prints one JSON line per threshold pair: medians, all repetitions, how many scans were integrated, and whether the two routes
 produced the same poses, decisions and maps.  Ends itself after --time-limit seconds.
 
+A third leg starts from RAW ranges (the node's tf path), at the thresholds (0.4, 0.13), one more JSON line:
+  (a) a fixed mount the way the entries before hsm_slam_ranges_tf_device compose it: hsm_ingest_batch_ranges_tf_device, a stream
+      wait, the D2H copy of one origo, hsm_slam_scans_device with that host origo;
+  (b) the one-call entry hsm_slam_ranges_tf_device on the same log (one shared transform);
+  (c) a MOVING mount (a transform per scan) through the one-call entry, against the per-scan host loop
+      hsm_ingest_laser_scan_tf + hsm_match_ingested + host gate + hsm_update_by_ingested.
+(b) and (c) are skipped, with a note in the line, where the library does not have the entry.
+
   python tools/bench_slam_scans.py [--reps 5] [--profile-steps N]
 
 --profile-steps N: no timing, N queued calls and nothing else -- the run to put under `rocprofv3 --kernel-trace --stats`.
@@ -108,8 +116,111 @@ def main():
                           "queued_median": round(float(np.median(qv)), 2), "host_loop_median": round(float(np.median(hv)), 2),
                           "poses_bit_identical": same_poses, "decisions_equal": same_flags, "maps_bit_identical": bool(same_maps),
                           "final_error_m": round(float(np.linalg.norm(host_poses[-1, :2] - poses[-1, :2])), 4)}), flush=True)
+    if not args.profile_steps:
+        raw_leg(args, capi, synth, torch, sc, poses, deltas, processor, wall)
     a.mapRep.close()
     b.mapRep.close()
+
+
+def raw_leg(args, capi, synth, torch, sc, poses, deltas, processor, wall):
+    thr = THRESHOLDS[0]
+    dev = torch.device("cuda", 0)
+    t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)  # noqa: E731
+    rng = np.random.default_rng(14)
+    ang = synth.beam_angles(BEAMS)
+    a0, inc = float(ang[0]), float(np.float32(synth.SCAN_SHAPES[BEAMS][1]))
+    gates = (np.float32(0.4 * 0.4), np.float32(30.0 * 30.0), -1.0, 1.0)  # the node's defaults
+    fixed = np.array([1, 0, 0, 0.12, 0, 1, 0, -0.05, 0, 0, 1, 0.3], np.float64)
+    moving = np.tile(np.eye(3, 4).reshape(12), (SCANS, 1))
+    moving[:, [3, 7]] = rng.uniform(-0.3, 0.3, (SCANS, 2))
+
+    def ranges_from(tx, ty):  # the laser sits at pose (+) (t_x, t_y)
+        c, s_ = np.cos(poses[:, 2].astype(np.float64)), np.sin(poses[:, 2].astype(np.float64))
+        lp = np.stack([poses[:, 0] + c * tx - s_ * ty, poses[:, 1] + s_ * tx + c * ty, poses[:, 2]], 1)
+        return np.stack([sc.world.raycast(p, ang) for p in lp]).astype(np.float32)
+
+    r_fixed, r_moving = ranges_from(fixed[3], fixed[7]), ranges_from(moving[:, 3], moving[:, 7])
+    procs = [processor() for _ in range(4)]  # (a), (b), (c) one call, (c) host loop
+    for p in procs:
+        p.setMapUpdateMinDistDiff(thr[0])
+        p.setMapUpdateMinAngleDiff(thr[1])
+    scale = procs[0].mapRep.getScaleToMap()
+    s = torch.cuda.Stream()
+    d_start, d_deltas = t(poses[0]), t(deltas)
+    d_rf, d_rm, d_tf, d_tm = t(r_fixed), t(r_moving), t(fixed), t(moving)
+    d_pts = torch.empty((SCANS * BEAMS, 2), dtype=torch.float32, device=dev)
+    d_offs = torch.empty(SCANS + 1, dtype=torch.int32, device=dev)
+    d_counts = torch.empty(SCANS, dtype=torch.int32, device=dev)
+    d_origo = torch.empty((SCANS, 2), dtype=torch.float32, device=dev)
+    out = [{"pose": torch.zeros((SCANS, 3), dtype=torch.float32, device=dev), "applied": torch.zeros(SCANS, dtype=torch.int32, device=dev)}
+           for _ in range(3)]
+    have = hasattr(capi.MapRepMultiMap, "slam_ranges_tf_device")
+    d_ws = torch.empty(capi.MapRepMultiMap.slam_ranges_tf_workspace(SCANS, BEAMS), dtype=torch.uint8, device=dev) if have else None
+    s.synchronize()
+
+    def composed():  # (a)
+        m = procs[0].mapRep
+        m.reset_update_gate()
+        m.set_update_gate(*thr)
+        m.ingest_batch_ranges_tf_device(SCANS, d_rf.data_ptr(), BEAMS, a0, inc, 0.4, 30.0, 30.0, d_tf.data_ptr(), True, *gates, scale,
+                                        d_pts.data_ptr(), d_offs.data_ptr(), d_counts.data_ptr(), d_origo.data_ptr(), s.cuda_stream)
+        s.synchronize()
+        origo = d_origo[0].cpu().numpy()
+        m.slam_scans_device(SCANS, d_start.data_ptr(), d_deltas.data_ptr(), d_pts.data_ptr(), d_offs.data_ptr(), BEAMS, origo, 0,
+                            out[0]["pose"].data_ptr(), 0, out[0]["applied"].data_ptr(), s.cuda_stream)
+        m.synchronize()
+
+    def one_call(which, d_r, d_t, shared):  # (b), (c)
+        m = procs[which].mapRep
+        m.reset_update_gate()
+        m.set_update_gate(*thr)
+        m.slam_ranges_tf_device(SCANS, d_start.data_ptr(), d_deltas.data_ptr(), d_r.data_ptr(), BEAMS, a0, inc, 0.4, 30.0, 30.0,
+                                d_t.data_ptr(), shared, *gates, scale, 0, out[which]["pose"].data_ptr(), 0, out[which]["applied"].data_ptr(),
+                                0, d_ws.data_ptr(), d_ws.numel(), s.cuda_stream)
+        m.synchronize()
+
+    host_poses, host_applied = np.zeros((SCANS, 3), np.float32), np.zeros(SCANS, np.int32)
+    fmax = np.finfo(np.float32).max
+
+    def host_loop():  # (c)'s yardstick: one scan per call, the gate on the host
+        m = procs[3].mapRep
+        last, pose, cov = np.array([fmax, fmax, fmax], np.float32), poses[0].copy(), None
+        for k in range(SCANS):
+            m.ingest_laser_scan_tf(r_moving[k], a0, inc, 0.4, 30.0, 30.0, moving[k], *gates)
+            pose, cov = m.match_ingested((pose + deltas[k]).astype(np.float32), cov)
+            go = capi.pose_difference_larger_than(pose, last, thr[0], thr[1])
+            if go:
+                m.update_by_ingested(pose)
+                m.onMapUpdated()
+                last = pose.copy()
+            host_poses[k], host_applied[k] = pose, int(go)
+        m.synchronize()
+
+    legs = {"a_composed": composed, "c_host_loop": host_loop}
+    if have:
+        legs["b_one_call"] = lambda: one_call(1, d_rf, d_tf, True)
+        legs["c_one_call"] = lambda: one_call(2, d_rm, d_tm, False)
+    for fn in legs.values():  # warm-up: allocations, geometry tables, first launches
+        fn()
+    times = {k: [] for k in legs}
+    for _ in range(args.reps):
+        for k, fn in legs.items():
+            times[k].append(wall(fn) / SCANS)
+    line = {"case": f"raw ranges, {SCANS} x {BEAMS}-beam scans, {LEVELS}-level {MAP}^2, thresholds {thr}", "reps": args.reps}
+    for k, v in times.items():
+        line[k + "_us_per_scan"] = [round(x, 2) for x in v]
+        line[k + "_median"] = round(float(np.median(v)), 2)
+    line["a_spread"] = round(float(max(times["a_composed"]) - min(times["a_composed"])), 2)
+    if have:
+        same = lambda x, y: bool(np.array_equal(x.cpu().numpy().view(np.uint32), y.cpu().numpy().view(np.uint32)))  # noqa: E731
+        line["b_equals_a"] = same(out[0]["pose"], out[1]["pose"]) and same(out[0]["applied"], out[1]["applied"])
+        line["c_equals_host_loop"] = bool(np.array_equal(out[2]["pose"].cpu().numpy().view(np.uint32), host_poses.view(np.uint32)) and
+                                          np.array_equal(out[2]["applied"].cpu().numpy(), host_applied))
+    else:
+        line["note"] = "this library has no hsm_slam_ranges_tf_device: legs (b) and (c) one-call skipped"
+    print(json.dumps(line), flush=True)
+    for p in procs:
+        p.mapRep.close()
 
 
 if __name__ == "__main__":
