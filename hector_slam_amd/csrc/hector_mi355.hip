@@ -95,6 +95,13 @@ namespace {
     if (e__ != hipSuccess) return fail(HSM_ERR_HIP, #expr, e__); \
   } while (0)
 
+// fail() for code several entries share: the text is "<who><text>", `who` the entry the caller used
+int fail_at(int code, const char* who, const char* text, hipError_t e = hipSuccess) {
+  char buf[512];
+  snprintf(buf, sizeof buf, "%s%s", who, text);
+  return fail(code, buf, e);
+}
+
 }  // namespace
 
 
@@ -1086,10 +1093,7 @@ static int order_map_reader(hsm_ctx* h, hipStream_t s, const char* who, hsm_ctx:
     HIP_TRY(hipThreadExchangeStreamCaptureMode(&mode));
     const hipError_t e = hipStreamSynchronize(h->stream);
     (void)hipThreadExchangeStreamCaptureMode(&mode);
-    if (e != hipSuccess) {
-      const std::string what = std::string(who) + ": waiting for the queued map updates at capture";
-      return fail(HSM_ERR_HIP, what.c_str(), e);
-    }
+    if (e != hipSuccess) return fail_at(HSM_ERR_HIP, who, ": waiting for the queued map updates at capture", e);
     return HSM_OK;
   }
   // (what test_queued_updates_are_ordered_against_caller_streams holds)
@@ -1835,39 +1839,59 @@ struct GateCall {
   const float* next_delta = nullptr;
 };
 
-static int update_by_scans_device_nolock(hsm_ctx* h, int count, const float* d_poses_world, const float* d_pts_xy,
-                                         const int* d_scan_offsets, int shared_n, int max_beams, const float origo[2],
-                                         hipStream_t stream, const GateCall* gate = nullptr, const float* d_origos = nullptr,
-                                         const char* who = "hsm_update_by_scans_device") {  // the entry the caller used, for the error text
-  if (count < 0 || max_beams < 0 || (count > 0 && !d_poses_world) || (!d_scan_offsets && shared_n < 0) ||
-      (count > 0 && !d_scan_offsets && shared_n > 0 && !d_pts_xy) || ((uintptr_t)d_origos & 7u) != 0)  // (origos: float2 loads)
-    return fail(HSM_ERR_INVALID, (std::string(who) + ": bad argument").c_str());
-  if (!d_scan_offsets && shared_n > HSM_MAX_UPDATE_BEAMS)
-    return fail(HSM_ERR_TOO_LARGE, (std::string(who) + ": more than HSM_MAX_UPDATE_BEAMS beams").c_str());
+// The posed scans of an update call, filled once by the entry and passed down: CSR scans (`d_offsets`) or one scan of `shared_n`
+// beams at every pose; `origo` the host pair for every scan (null: zero) or `d_origos` [count * 2] on the device.  The first six
+// fields are in the order of the C ABI: an entry initialises them with braces and names the rest.
+struct PosedScans {
+  int count = 0;
+  const float* d_poses = nullptr;
+  const float* d_pts = nullptr;
+  const int* d_offsets = nullptr;
+  int shared_n = 0, max_beams = 0;
+  const float* origo = nullptr;
+  const float* d_origos = nullptr;
+  const GateCall* gate = nullptr;                   // the gated entries
+  const char* who = "hsm_update_by_scans_device";  // the entry the caller used, for the error texts
+};
+
+// the context's stream behind the caller's: the inputs are complete where `s` stands now
+static int wait_for_caller_inputs(hsm_ctx* h, hipStream_t s) {
+  if (s == h->stream) return HSM_OK;
+  if (!h->evt_inputs) HIP_TRY(hipEventCreateWithFlags(&h->evt_inputs, hipEventDisableTiming));
+  HIP_TRY(hipEventRecord(h->evt_inputs, s));
+  HIP_TRY(hipStreamWaitEvent(h->stream, h->evt_inputs, 0));
+  return HSM_OK;
+}
+
+static int update_by_scans_device_nolock(hsm_ctx* h, const PosedScans& S, hipStream_t stream) {
+  const int count = S.count;
+  const GateCall* gate = S.gate;
+  const float* origo = S.origo;
+  if (count < 0 || S.max_beams < 0 || (count > 0 && !S.d_poses) || (!S.d_offsets && S.shared_n < 0) ||
+      (count > 0 && !S.d_offsets && S.shared_n > 0 && !S.d_pts) || ((uintptr_t)S.d_origos & 7u) != 0)  // (origos: float2 loads)
+    return fail_at(HSM_ERR_INVALID, S.who, ": bad argument");
+  if (!S.d_offsets && S.shared_n > HSM_MAX_UPDATE_BEAMS)
+    return fail_at(HSM_ERR_TOO_LARGE, S.who, ": more than HSM_MAX_UPDATE_BEAMS beams");
   if (count == 0) return HSM_OK;
   if (int rc = select_device(h)) return rc;
   // the rule of every map update: refused, before anything is queued, while a stream this call would touch is being captured
   if (stream_capturing(stream))
-    return fail(HSM_ERR_INVALID, (std::string(who) + ": `stream` is being captured into a graph (map updates are not captured)").c_str());
+    return fail_at(HSM_ERR_INVALID, S.who, ": `stream` is being captured into a graph (map updates are not captured)");
   if (int rc = order_after_foreign_match(h)) return rc;  // (refuses the same way for the streams this context has matched on)
   if (!gate && h->gate_outstanding)  // scan k is update k behind EVERY earlier update: the ones gated calls applied go in first
     if (int rc = fold_gate_counters(h)) return rc;
   if (int rc = ensure_update_scans(h, (size_t)count)) return rc;
-  if (stream != h->stream) {  // the inputs are complete where the caller's stream stands now
-    if (!h->evt_inputs) HIP_TRY(hipEventCreateWithFlags(&h->evt_inputs, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(h->evt_inputs, stream));
-    HIP_TRY(hipStreamWaitEvent(h->stream, h->evt_inputs, 0));
-  }
+  if (int rc = wait_for_caller_inputs(h, stream)) return rc;
   const int nlev = (int)h->levels.size();
   UpdatePrepParams A;
   memset(&A, 0, sizeof A);
   A.nlev = nlev;
   A.count = count;
-  A.poses_world = d_poses_world;
-  A.pts = reinterpret_cast<const float2*>(d_pts_xy);
-  A.offsets = d_scan_offsets;
-  A.shared_n = shared_n;
-  A.origos = reinterpret_cast<const float2*>(d_origos);  // per scan, on the device: the host pair below is then not read
+  A.poses_world = S.d_poses;
+  A.pts = reinterpret_cast<const float2*>(S.d_pts);
+  A.offsets = S.d_offsets;
+  A.shared_n = S.shared_n;
+  A.origos = reinterpret_cast<const float2*>(S.d_origos);  // per scan, on the device: the host pair below is then not read
   A.out = h->d_upd_batches;
   A.boxes = h->d_upd_boxes;
   size_t max_cells = 0;
@@ -1908,7 +1932,7 @@ static int update_by_scans_device_nolock(hsm_ctx* h, int count, const float* d_p
   HIP_TRY(hipGetLastError());
   // launch shapes from the hint alone: the mark grid strides over the scan's real beam count, the apply grid over the scan's
   // box -- sized for the whole level, its blocks return after one scalar load where the box is empty or small
-  const int hint = max_beams > 0 ? max_beams : 1081;
+  const int hint = S.max_beams > 0 ? S.max_beams : 1081;
   const unsigned occ_blocks = (unsigned)((hint + 255) / 256), free_blocks = (unsigned)((hint + 3) / 4);
   const unsigned apply_blocks = (unsigned)grid_for(max_cells);
   const bool scatter = h->layout == kLayoutQuad;
@@ -1981,53 +2005,65 @@ int hsm_update_gate_state(hsm_ctx* h, float last_update_pose[3], long long* appl
   return HSM_OK;
 }
 
-static int update_by_scans_device_gated_impl(hsm_ctx* h, int count, const float* d_poses_world, const float* d_pts_xy,
-                                             const int* d_scan_offsets, int shared_n, int max_beams, const float origo[2],
-                                             const float* d_origos, const unsigned char* d_force, int* d_out_applied,
-                                             void* stream, const char* who) {
+// what the four device entries share: the context's lock around the update
+static int update_by_scans_device_locked(hsm_ctx* h, const PosedScans& S, void* stream) {
   if (!h) return fail(HSM_ERR_INVALID, "null context");
   std::lock_guard<std::mutex> lk(h->mu);
-  GateCall gate;
-  gate.d_force = d_force;
-  gate.d_out_applied = d_out_applied;
-  return update_by_scans_device_nolock(h, count, d_poses_world, d_pts_xy, d_scan_offsets, shared_n, max_beams, origo,
-                                       static_cast<hipStream_t>(stream), &gate, d_origos, who);
+  return update_by_scans_device_nolock(h, S, static_cast<hipStream_t>(stream));
+}
+
+int hsm_update_by_scans_device(hsm_ctx* h, int count, const float* d_poses_world, const float* d_pts_xy,
+                               const int* d_scan_offsets, int shared_n, int max_beams, const float origo[2], void* stream) {
+  PosedScans S{count, d_poses_world, d_pts_xy, d_scan_offsets, shared_n, max_beams};
+  S.origo = origo;
+  return update_by_scans_device_locked(h, S, stream);
+}
+
+int hsm_update_by_scans_device_origos(hsm_ctx* h, int count, const float* d_poses_world, const float* d_pts_xy,
+                                      const int* d_scan_offsets, int shared_n, int max_beams, const float* d_origos,
+                                      void* stream) {
+  PosedScans S{count, d_poses_world, d_pts_xy, d_scan_offsets, shared_n, max_beams};
+  S.d_origos = d_origos;
+  S.who = "hsm_update_by_scans_device_origos";
+  return update_by_scans_device_locked(h, S, stream);
 }
 
 int hsm_update_by_scans_device_gated(hsm_ctx* h, int count, const float* d_poses_world, const float* d_pts_xy,
                                      const int* d_scan_offsets, int shared_n, int max_beams, const float origo[2],
                                      const unsigned char* d_force, int* d_out_applied, void* stream) {
-  return update_by_scans_device_gated_impl(h, count, d_poses_world, d_pts_xy, d_scan_offsets, shared_n, max_beams, origo, nullptr,
-                                           d_force, d_out_applied, stream, "hsm_update_by_scans_device");
+  GateCall gate;
+  gate.d_force = d_force;
+  gate.d_out_applied = d_out_applied;
+  PosedScans S{count, d_poses_world, d_pts_xy, d_scan_offsets, shared_n, max_beams};
+  S.origo = origo;
+  S.gate = &gate;  // (the texts stay the ungated entry's)
+  return update_by_scans_device_locked(h, S, stream);
 }
 
 int hsm_update_by_scans_device_gated_origos(hsm_ctx* h, int count, const float* d_poses_world, const float* d_pts_xy,
                                             const int* d_scan_offsets, int shared_n, int max_beams, const float* d_origos,
                                             const unsigned char* d_force, int* d_out_applied, void* stream) {
-  return update_by_scans_device_gated_impl(h, count, d_poses_world, d_pts_xy, d_scan_offsets, shared_n, max_beams, nullptr,
-                                           d_origos, d_force, d_out_applied, stream, "hsm_update_by_scans_device_gated_origos");
+  GateCall gate;
+  gate.d_force = d_force;
+  gate.d_out_applied = d_out_applied;
+  PosedScans S{count, d_poses_world, d_pts_xy, d_scan_offsets, shared_n, max_beams};
+  S.d_origos = d_origos;
+  S.gate = &gate;
+  S.who = "hsm_update_by_scans_device_gated_origos";
+  return update_by_scans_device_locked(h, S, stream);
 }
 
 // the refusals of a scan-log call, before anything is queued: `s` or a stream this context has matched on is being captured
 static int slam_refuse_capture(hsm_ctx* h, hipStream_t s, const char* who) {
   if (stream_capturing(s))
-    return fail(HSM_ERR_INVALID, (std::string(who) + ": `stream` is being captured into a graph (map updates are not captured)").c_str());
+    return fail_at(HSM_ERR_INVALID, who, ": `stream` is being captured into a graph (map updates are not captured)");
   for (const hsm_ctx::ForeignStream& f : h->foreign)  // (order_after_foreign_match)
     if (stream_capturing(f.s))
-      return fail(HSM_ERR_INVALID, (std::string(who) + ": a caller's stream that this context matches on is being captured into a graph").c_str());
+      return fail_at(HSM_ERR_INVALID, who, ": a caller's stream that this context matches on is being captured into a graph");
   return HSM_OK;
 }
 
-// the context's stream behind the caller's (the inputs are complete where `s` stands now) ...
-static int slam_wait_for_caller(hsm_ctx* h, hipStream_t s) {
-  if (s == h->stream) return HSM_OK;
-  if (!h->evt_inputs) HIP_TRY(hipEventCreateWithFlags(&h->evt_inputs, hipEventDisableTiming));
-  HIP_TRY(hipEventRecord(h->evt_inputs, s));
-  HIP_TRY(hipStreamWaitEvent(h->stream, h->evt_inputs, 0));
-  return HSM_OK;
-}
-
-// ... and the caller's behind the context's (the results are complete where the context's stream stands now)
+// the caller's stream behind the context's (the results are complete where the context's stream stands now)
 static int slam_caller_waits(hsm_ctx* h, hipStream_t s) {
   if (s == h->stream) return HSM_OK;
   if (!h->evt_slam_done) HIP_TRY(hipEventCreateWithFlags(&h->evt_slam_done, hipEventDisableTiming));
@@ -2036,27 +2072,50 @@ static int slam_caller_waits(hsm_ctx* h, hipStream_t s) {
   return HSM_OK;
 }
 
-// the loop itself, on the context's stream: `origo` the host pair for every scan, or `d_origos` [count*2] on the device
-static int slam_scans_queue(hsm_ctx* h, int count, const float* d_start_pose, const float* d_hint_deltas, const float* d_pts_xy,
-                            const int* d_scan_offsets, int max_beams, const float origo[2], const float* d_origos,
-                            const unsigned char* d_force, float* d_out_pose, float* d_out_cov, int* d_out_applied,
-                            const char* update_who) {
-  hipLaunchKernelGGL(slam_begin_kernel, dim3(1), dim3(64), 0, h->stream, h->d_gate, d_start_pose, d_hint_deltas);
+// The scan log of a SLAM call, all on the device: what steers the loop and where its results go.  Scan k's share of every array
+// is sliced here and nowhere else.  (Fields in the order the entries initialise them with braces.)
+struct ScanLog {
+  int count = 0;
+  const float* d_start_pose = nullptr;
+  const float* d_hint_deltas = nullptr;  // [count * 3] or null
+  const unsigned char* d_force = nullptr;  // [count] or null
+  float* d_out_pose = nullptr;             // [count * 3]
+  float* d_out_cov = nullptr;              // [count * 9] or null
+  int* d_out_applied = nullptr;            // [count] or null
+  int* d_out_counts = nullptr;             // [count] or null: the raw-scan entries' survivors per scan
+  float* pose(int k) const { return d_out_pose + 3 * (size_t)k; }
+  float* cov(int k) const { return d_out_cov ? d_out_cov + 9 * (size_t)k : nullptr; }
+  GateCall gate(int k) const {  // scan k's gated update: it settles the scan's pose and covariance and leaves the next scan's hint
+    GateCall g;
+    g.d_force = d_force ? d_force + k : nullptr;
+    g.d_out_applied = d_out_applied ? d_out_applied + k : nullptr;
+    g.slam = true;
+    g.pose_io = pose(k);
+    g.cov_io = cov(k);
+    g.next_delta = d_hint_deltas && k + 1 < count ? d_hint_deltas + 3 * (size_t)(k + 1) : nullptr;
+    return g;
+  }
+};
+
+// the loop itself, on the context's stream.  `scans`: the log's CSR end points, beam hint, origo(s) and the name its updates
+// report under (count, poses and gate are the loop's to set)
+static int slam_scans_queue(hsm_ctx* h, const ScanLog& log, const PosedScans& scans) {
+  hipLaunchKernelGGL(slam_begin_kernel, dim3(1), dim3(64), 0, h->stream, h->d_gate, log.d_start_pose, log.d_hint_deltas);
   HIP_TRY(hipGetLastError());
-  for (int k = 0; k < count; ++k) {
-    if (int rc = match_batch_device_nolock(h, 1, h->d_gate->hint, d_pts_xy, d_scan_offsets + k, max_beams, d_out_pose + 3 * (size_t)k,
-                                           d_out_cov ? d_out_cov + 9 * (size_t)k : nullptr, h->stream))
+  GateCall gate;
+  PosedScans one = scans;
+  one.count = 1;
+  one.shared_n = 0;
+  one.gate = &gate;
+  for (int k = 0; k < log.count; ++k) {
+    if (int rc = match_batch_device_nolock(h, 1, h->d_gate->hint, scans.d_pts, scans.d_offsets + k, scans.max_beams, log.pose(k),
+                                           log.cov(k), h->stream))
       return rc;
-    GateCall gate;
-    gate.d_force = d_force ? d_force + k : nullptr;
-    gate.d_out_applied = d_out_applied ? d_out_applied + k : nullptr;
-    gate.slam = true;
-    gate.pose_io = d_out_pose + 3 * (size_t)k;
-    gate.cov_io = d_out_cov ? d_out_cov + 9 * (size_t)k : nullptr;
-    gate.next_delta = d_hint_deltas && k + 1 < count ? d_hint_deltas + 3 * (size_t)(k + 1) : nullptr;
-    if (int rc = update_by_scans_device_nolock(h, 1, gate.pose_io, d_pts_xy, d_scan_offsets + k, 0, max_beams, origo, h->stream,
-                                               &gate, d_origos ? d_origos + 2 * (size_t)k : nullptr, update_who))
-      return rc;
+    gate = log.gate(k);
+    one.d_poses = gate.pose_io;
+    one.d_offsets = scans.d_offsets + k;
+    one.d_origos = scans.d_origos ? scans.d_origos + 2 * (size_t)k : nullptr;
+    if (int rc = update_by_scans_device_nolock(h, one, h->stream)) return rc;
   }
   return HSM_OK;
 }
@@ -2065,56 +2124,39 @@ static int slam_scans_queue(hsm_ctx* h, int count, const float* d_start_pose, co
 // own stream -- the matches too, so a scan costs no event hop: the caller's stream is waited for once, in front, and waits once,
 // behind.  Per scan: the exact batch matcher on a batch of one, reading its hint from the gate's device block; then the gated
 // update of that one scan, whose gate launch also settles a forced scan's pose and covariance and leaves the next scan's hint.
-static int slam_scans_device_impl(hsm_ctx* h, const char* who, int count, const float* d_start_pose, const float* d_hint_deltas,
-                                  const float* d_pts_xy, const int* d_scan_offsets, int max_beams, const float origo[2],
-                                  const float* d_origos, const unsigned char* d_force, float* d_out_pose, float* d_out_cov,
-                                  int* d_out_applied, void* stream) {
+static int slam_scans_device_impl(hsm_ctx* h, const char* who, const ScanLog& log, PosedScans scans, void* stream) {
   if (!h) return fail(HSM_ERR_INVALID, "null context");
-  if (count < 0 || max_beams < 0 || (count > 0 && (!d_scan_offsets || !d_out_pose)) || ((uintptr_t)d_origos & 7u) != 0)
-    return fail(HSM_ERR_INVALID, (std::string(who) + ": bad argument").c_str());
-  if (count == 0) return HSM_OK;
+  if (log.count < 0 || scans.max_beams < 0 || (log.count > 0 && (!scans.d_offsets || !log.d_out_pose)) ||
+      ((uintptr_t)scans.d_origos & 7u) != 0)
+    return fail_at(HSM_ERR_INVALID, who, ": bad argument");
+  if (log.count == 0) return HSM_OK;
   std::lock_guard<std::mutex> lk(h->mu);
   if (int rc = select_device(h)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (int rc = slam_refuse_capture(h, s, who)) return rc;
-  if (int rc = slam_wait_for_caller(h, s)) return rc;
-  if (int rc = slam_scans_queue(h, count, d_start_pose, d_hint_deltas, d_pts_xy, d_scan_offsets, max_beams, origo, d_origos,
-                                d_force, d_out_pose, d_out_cov, d_out_applied,
-                                d_origos ? who : "hsm_update_by_scans_device"))  // (the parent entry keeps its texts)
-    return rc;
+  if (int rc = wait_for_caller_inputs(h, s)) return rc;
+  if (scans.d_origos) scans.who = who;  // (the parent entry's updates keep hsm_update_by_scans_device's texts)
+  if (int rc = slam_scans_queue(h, log, scans)) return rc;
   return slam_caller_waits(h, s);
 }
 
 int hsm_slam_scans_device(hsm_ctx* h, int count, const float* d_start_pose, const float* d_hint_deltas, const float* d_pts_xy,
                           const int* d_scan_offsets, int max_beams, const float origo[2], const unsigned char* d_force,
                           float* d_out_pose, float* d_out_cov, int* d_out_applied, void* stream) {
-  return slam_scans_device_impl(h, "hsm_slam_scans_device", count, d_start_pose, d_hint_deltas, d_pts_xy, d_scan_offsets, max_beams,
-                                origo, nullptr, d_force, d_out_pose, d_out_cov, d_out_applied, stream);
+  PosedScans scans{count, nullptr, d_pts_xy, d_scan_offsets, 0, max_beams};
+  scans.origo = origo;
+  const ScanLog log{count, d_start_pose, d_hint_deltas, d_force, d_out_pose, d_out_cov, d_out_applied};
+  return slam_scans_device_impl(h, "hsm_slam_scans_device", log, scans, stream);
 }
 
 int hsm_slam_scans_device_origos(hsm_ctx* h, int count, const float* d_start_pose, const float* d_hint_deltas,
                                  const float* d_pts_xy, const int* d_scan_offsets, int max_beams, const float* d_origos,
                                  const unsigned char* d_force, float* d_out_pose, float* d_out_cov, int* d_out_applied,
                                  void* stream) {
-  return slam_scans_device_impl(h, "hsm_slam_scans_device_origos", count, d_start_pose, d_hint_deltas, d_pts_xy, d_scan_offsets,
-                                max_beams, nullptr, d_origos, d_force, d_out_pose, d_out_cov, d_out_applied, stream);
-}
-
-int hsm_update_by_scans_device(hsm_ctx* h, int count, const float* d_poses_world, const float* d_pts_xy,
-                               const int* d_scan_offsets, int shared_n, int max_beams, const float origo[2], void* stream) {
-  if (!h) return fail(HSM_ERR_INVALID, "null context");
-  std::lock_guard<std::mutex> lk(h->mu);
-  return update_by_scans_device_nolock(h, count, d_poses_world, d_pts_xy, d_scan_offsets, shared_n, max_beams, origo,
-                                       static_cast<hipStream_t>(stream));
-}
-
-int hsm_update_by_scans_device_origos(hsm_ctx* h, int count, const float* d_poses_world, const float* d_pts_xy,
-                                      const int* d_scan_offsets, int shared_n, int max_beams, const float* d_origos,
-                                      void* stream) {
-  if (!h) return fail(HSM_ERR_INVALID, "null context");
-  std::lock_guard<std::mutex> lk(h->mu);
-  return update_by_scans_device_nolock(h, count, d_poses_world, d_pts_xy, d_scan_offsets, shared_n, max_beams, nullptr,
-                                       static_cast<hipStream_t>(stream), nullptr, d_origos, "hsm_update_by_scans_device_origos");
+  PosedScans scans{count, nullptr, d_pts_xy, d_scan_offsets, 0, max_beams};
+  scans.d_origos = d_origos;
+  const ScanLog log{count, d_start_pose, d_hint_deltas, d_force, d_out_pose, d_out_cov, d_out_applied};
+  return slam_scans_device_impl(h, "hsm_slam_scans_device_origos", log, scans, stream);
 }
 
 int hsm_update_by_scans(hsm_ctx* h, int count, const float* poses_world, const float* pts_xy, const int* scan_offsets,
@@ -2140,21 +2182,15 @@ int hsm_update_by_scans(hsm_ctx* h, int count, const float* poses_world, const f
   for (const hsm_ctx::ForeignStream& f : h->foreign)  // refused before the copies are queued (order_after_foreign_match)
     if (stream_capturing(f.s))
       return fail(HSM_ERR_INVALID, "hsm_update_by_scans: a caller's stream that this context matches on is being captured into a graph");
-  // one staging block: end points | poses | offsets (the copies are queued on the context's stream, in front of the update)
-  Carver c;
-  const size_t o_pts = c.take(total * sizeof(float2)), o_poses = c.take((size_t)count * 3 * sizeof(float));
-  const size_t o_offs = c.take(((size_t)count + 1) * sizeof(int));
-  if (int rc = h->d_upd_stage.reserve(c.total(), kHalfMore)) return rc;
+  // one staging block (the copies are queued on the context's stream, in front of the update)
+  const UpdateScansStage st = update_scans_stage(count, total, poses_world, pts_xy, scan_offsets);
+  if (int rc = h->d_upd_stage.reserve(st.plan.total(), kHalfMore)) return rc;
   char* base = h->d_upd_stage;
-  float* d_pts = reinterpret_cast<float*>(base + o_pts);
-  float* d_poses = reinterpret_cast<float*>(base + o_poses);
-  int* d_offs = reinterpret_cast<int*>(base + o_offs);
-  if (total > 0) HIP_TRY(hipMemcpyAsync(d_pts, pts_xy, total * sizeof(float2), hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(d_poses, poses_world, (size_t)count * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  if (scan_offsets)
-    HIP_TRY(hipMemcpyAsync(d_offs, scan_offsets, ((size_t)count + 1) * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  return update_by_scans_device_nolock(h, count, d_poses, d_pts, scan_offsets ? d_offs : nullptr, shared_n, longest, origo,
-                                       h->stream);
+  if (int rc = stage_copy_in(st.plan, base, h->stream)) return rc;
+  PosedScans S{count, staged<float>(base, st.poses), staged<float>(base, st.pts),
+                             staged<int>(base, st.offs, scan_offsets), shared_n, longest};
+  S.origo = origo;
+  return update_by_scans_device_nolock(h, S, h->stream);
 }
 
 // device buffers of the ingestion entries: raw input (3 floats per element covers ranges and Point32
@@ -2359,8 +2395,8 @@ static int ranges_geometry_table(std::vector<Geometry>& geoms, int n, float angl
   // The copy goes on the caller's stream, not the null stream, and waits for that stream only
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-    return fail(HSM_ERR_INVALID, (std::string(who) + ": sensor geometry not seen before while the stream is being captured (no "
-                                  "allocation under capture: make one call with this geometry before capturing)").c_str());
+    return fail_at(HSM_ERR_INVALID, who, ": sensor geometry not seen before while the stream is being captured (no "
+                                         "allocation under capture: make one call with this geometry before capturing)");
   const auto t = make(n, angle_min, angle_increment);
   Value* d = nullptr;
   HIP_TRY(hipMalloc((void**)&d, (size_t)n * sizeof(Value)));
@@ -2368,7 +2404,7 @@ static int ranges_geometry_table(std::vector<Geometry>& geoms, int n, float angl
   if (e == hipSuccess) e = hipStreamSynchronize(s);  // (`t` is a host temporary)
   if (e != hipSuccess) {
     (void)hipFree(d);
-    return fail(HSM_ERR_HIP, (std::string(who) + ": sensor table upload").c_str(), e);
+    return fail_at(HSM_ERR_HIP, who, ": sensor table upload", e);
   }
   geoms.push_back({n, a0_bits, inc_bits, d});
   *out = d;
@@ -2441,71 +2477,61 @@ int hsm_match_batch_ranges(hsm_ctx* h, int batch, const float* begin_world, cons
   if (!ranges_layout(batch, n, &L))
     return fail(HSM_ERR_TOO_LARGE, "hsm_match_batch_ranges: n > HSM_MAX_UPDATE_BEAMS or batch * n > INT_MAX");
   if (batch == 0) return HSM_OK;
-  const size_t b_begin = (size_t)batch * 3 * sizeof(float), b_cov = (size_t)batch * 9 * sizeof(float);
-  const size_t b_counts = (size_t)batch * sizeof(int), b_ranges = (size_t)batch * n * sizeof(float);
-  // device block: start poses | poses | covariances | counts | raw ranges | workspace
-  Carver c;
-  const size_t o_begin = c.take(b_begin), o_pose = c.take(b_begin), o_cov = c.take(b_cov), o_counts = c.take(b_counts);
-  const size_t o_ranges = c.take(b_ranges), o_ws = c.take(L.total);
+  const RangesStage st = ranges_stage(batch, n, L.total, begin_world, ranges, out_pose, out_cov, out_counts);
   std::lock_guard<std::mutex> lk(h->mu);
   if (int rc = select_device(h)) return rc;
-  if (!h->d_rbatch.holds(c.total())) HIP_TRY(hipStreamSynchronize(h->stream));
-  if (int rc = h->d_rbatch.reserve(c.total())) return rc;
+  if (!h->d_rbatch.holds(st.plan.total())) HIP_TRY(hipStreamSynchronize(h->stream));
+  if (int rc = h->d_rbatch.reserve(st.plan.total())) return rc;
   char* base = h->d_rbatch;
-  float* d_begin = (float*)(base + o_begin);
-  float* d_pose = (float*)(base + o_pose);
-  float* d_cov = (float*)(base + o_cov);
-  int* d_counts = (int*)(base + o_counts);
-  float* d_ranges = (float*)(base + o_ranges);
-  HIP_TRY(hipMemcpyAsync(d_begin, begin_world, b_begin, hipMemcpyHostToDevice, h->stream));
-  if (b_ranges) HIP_TRY(hipMemcpyAsync(d_ranges, ranges, b_ranges, hipMemcpyHostToDevice, h->stream));
-  if (out_cov) HIP_TRY(hipMemcpyAsync(d_cov, out_cov, b_cov, hipMemcpyHostToDevice, h->stream));  // in/out (empty scans)
-  if (int rc = match_batch_ranges_nolock(h, batch, d_begin, d_ranges, n, angle_min, angle_increment, range_min, range_max,
-                                         scale_to_map, d_pose, out_cov ? d_cov : nullptr, d_counts, base + o_ws, L.total,
+  if (int rc = stage_copy_in(st.plan, base, h->stream)) return rc;
+  if (int rc = match_batch_ranges_nolock(h, batch, staged<float>(base, st.begin), staged<float>(base, st.ranges), n, angle_min,
+                                         angle_increment, range_min, range_max, scale_to_map, staged<float>(base, st.pose),
+                                         staged<float>(base, st.cov, out_cov), staged<int>(base, st.counts), base + st.ws, L.total,
                                          h->stream, 1))
     return rc;
-  HIP_TRY(hipMemcpyAsync(out_pose, d_pose, b_begin, hipMemcpyDeviceToHost, h->stream));
-  if (out_cov) HIP_TRY(hipMemcpyAsync(out_cov, d_cov, b_cov, hipMemcpyDeviceToHost, h->stream));
-  if (out_counts) HIP_TRY(hipMemcpyAsync(out_counts, d_counts, b_counts, hipMemcpyDeviceToHost, h->stream));
+  if (int rc = stage_copy_out(st.plan, base, h->stream)) return rc;
   HIP_TRY(hipStreamSynchronize(h->stream));
   return HSM_OK;
 }
 
 // ---- B raw scans and a transform per scan through the node's tf path: the CSR container of the batched entries ----
 
-// the context's part, under its lock: the device and the unit-vector table of the geometry (nullptr for n == 0)
-static int ranges_tf_unit_table(hsm_ctx* h, const char* who, int n, float angle_min, float angle_increment, hipStream_t s,
-                                const double2** unit) {
-  *unit = nullptr;
-  if (int rc = select_device(h)) return rc;
-  if (n == 0) return HSM_OK;
-  return ranges_geometry_table(h->ranges_tf_geoms, n, angle_min, angle_increment, s, who, laser_unit_vectors, unit);
-}
-
-// the three launches on `s`; they read nothing of the context
-static int launch_ingest_batch_ranges_tf(const double2* unit, int batch, const float* d_ranges, int n, float range_min,
-                                         float range_max, double range_cutoff, const double* d_tf_rows, int shared_tf,
-                                         float sqr_laser_min_dist, float sqr_laser_max_dist, float laser_z_min,
-                                         float laser_z_max, float scale_to_map, float* d_out_pts_xy, int* d_out_offsets,
-                                         int* d_out_counts, float* d_out_origo, hipStream_t s,
-                                         int* d_counts_copy = nullptr) {  // a second copy of the counts, by the offsets pass
+// The tf conversion of `P.batch` raw scans is carried as the kernels' own RangesTfParams: the entry fills everything but `unit`
+// (the values in the order of the C ABI; the host-array entries put the staged `ranges` and `tf_rows` in once they have them),
+// ranges_tf_unit_table completes it.
+static RangesTfParams ranges_tf_params(int batch, const float* ranges, int n, float range_min, float range_max, double range_cutoff,
+                                       const double* tf_rows, int shared_tf, const CloudGates& gates) {
   RangesTfParams P{};
-  P.ranges = d_ranges;
-  P.unit = unit;
-  P.tf_rows = d_tf_rows;
+  P.ranges = ranges;
+  P.tf_rows = tf_rows;
   P.batch = batch;
   P.n = n;
   P.shared_tf = shared_tf != 0;
   P.range_min = range_min;
-  P.range_cutoff = range_cutoff < 0 ? (double)range_max : range_cutoff;
-  P.G = {sqr_laser_min_dist, sqr_laser_max_dist, laser_z_min, laser_z_max, scale_to_map};
-  const int blocks = (batch - 1) / kRangesScansPerBlock + 1;
+  P.range_cutoff = range_cutoff < 0 ? (double)range_max : range_cutoff;  // projectLaser's cutoff: range_max where none is given
+  P.G = gates;
+  return P;
+}
+
+// the context's part, under its lock: the device and the unit-vector table of the geometry (nullptr for n == 0)
+static int ranges_tf_unit_table(hsm_ctx* h, const char* who, RangesTfParams& P, float angle_min, float angle_increment,
+                                hipStream_t s) {
+  P.unit = nullptr;
+  if (int rc = select_device(h)) return rc;
+  if (P.n == 0) return HSM_OK;
+  return ranges_geometry_table(h->ranges_tf_geoms, P.n, angle_min, angle_increment, s, who, laser_unit_vectors, &P.unit);
+}
+
+// the three launches on `s`; they read nothing of the context.  d_counts_copy: a second copy of the counts, by the offsets pass
+static int launch_ingest_batch_ranges_tf(const RangesTfParams& P, float* d_out_pts_xy, int* d_out_offsets, int* d_out_counts,
+                                         float* d_out_origo, hipStream_t s, int* d_counts_copy = nullptr) {
+  const int blocks = (P.batch - 1) / kRangesScansPerBlock + 1;
   hipLaunchKernelGGL(ranges_tf_gate_count_kernel, dim3(blocks), dim3(256), 0, s, P, d_out_counts,
                      reinterpret_cast<float2*>(d_out_origo));
   HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(ranges_offsets_kernel, dim3(1), dim3(1024), 0, s, d_out_counts, batch, d_out_offsets, d_counts_copy);
+  hipLaunchKernelGGL(ranges_offsets_kernel, dim3(1), dim3(1024), 0, s, d_out_counts, P.batch, d_out_offsets, d_counts_copy);
   HIP_TRY(hipGetLastError());
-  if (n > 0) {
+  if (P.n > 0) {
     // (scan b writes below offsets[b] + n <= (b + 1) * n <= batch * n: inside the caller's endpoint array)
     hipLaunchKernelGGL(ranges_tf_compact_kernel, dim3(blocks), dim3(256), 0, s, P, d_out_offsets,
                        reinterpret_cast<float2*>(d_out_pts_xy));
@@ -2514,12 +2540,12 @@ static int launch_ingest_batch_ranges_tf(const double2* unit, int batch, const f
   return HSM_OK;
 }
 
-// the argument checks the two entries share (pointers: the device entry's, or the host entry's before staging)
-static int check_batch_ranges_tf(const char* who, int batch, const void* ranges, int n, const void* tf_rows) {
-  if (batch < 0 || n < 0 || (batch > 0 && n > 0 && !ranges) || (batch > 0 && !tf_rows))
-    return fail(HSM_ERR_INVALID, (std::string(who) + ": bad argument").c_str());
-  if (n > HSM_MAX_UPDATE_BEAMS || (size_t)batch * (size_t)n > (size_t)INT_MAX)
-    return fail(HSM_ERR_TOO_LARGE, (std::string(who) + ": n > HSM_MAX_UPDATE_BEAMS or batch * n > INT_MAX").c_str());
+// the argument checks the entries share (pointers: the device entry's, or the host entry's before staging)
+static int check_batch_ranges_tf(const char* who, const RangesTfParams& P) {
+  if (P.batch < 0 || P.n < 0 || (P.batch > 0 && P.n > 0 && !P.ranges) || (P.batch > 0 && !P.tf_rows))
+    return fail_at(HSM_ERR_INVALID, who, ": bad argument");
+  if (P.n > HSM_MAX_UPDATE_BEAMS || (size_t)P.batch * (size_t)P.n > (size_t)INT_MAX)
+    return fail_at(HSM_ERR_TOO_LARGE, who, ": n > HSM_MAX_UPDATE_BEAMS or batch * n > INT_MAX");
   return HSM_OK;
 }
 
@@ -2533,17 +2559,16 @@ int hsm_ingest_batch_ranges_tf_device(hsm_ctx* h, int batch, const float* d_rang
   if (!h) return fail(HSM_ERR_INVALID, "null context");
   if (!d_out_pts_xy || !d_out_offsets || !d_out_counts || ((uintptr_t)d_tf_rows & 7u) != 0)
     return fail(HSM_ERR_INVALID, "hsm_ingest_batch_ranges_tf_device: bad argument");
-  if (int rc = check_batch_ranges_tf(who, batch, d_ranges, n, d_tf_rows)) return rc;
+  RangesTfParams P = ranges_tf_params(batch, d_ranges, n, range_min, range_max, range_cutoff, d_tf_rows, shared_tf,
+                                      {sqr_laser_min_dist, sqr_laser_max_dist, laser_z_min, laser_z_max, scale_to_map});
+  if (int rc = check_batch_ranges_tf(who, P)) return rc;
   if (batch == 0) return HSM_OK;
   const hipStream_t s = (hipStream_t)stream;
-  const double2* unit = nullptr;
   {
     std::lock_guard<std::mutex> lk(h->mu);  // (for the geometry cache only)
-    if (int rc = ranges_tf_unit_table(h, who, n, angle_min, angle_increment, s, &unit)) return rc;
+    if (int rc = ranges_tf_unit_table(h, who, P, angle_min, angle_increment, s)) return rc;
   }
-  return launch_ingest_batch_ranges_tf(unit, batch, d_ranges, n, range_min, range_max, range_cutoff, d_tf_rows, shared_tf,
-                                       sqr_laser_min_dist, sqr_laser_max_dist, laser_z_min, laser_z_max, scale_to_map,
-                                       d_out_pts_xy, d_out_offsets, d_out_counts, d_out_origo, s);
+  return launch_ingest_batch_ranges_tf(P, d_out_pts_xy, d_out_offsets, d_out_counts, d_out_origo, s);
 }
 
 int hsm_match_batch_ranges_tf(hsm_ctx* h, int batch, const float* begin_world, const float* ranges, int n, float angle_min,
@@ -2554,47 +2579,30 @@ int hsm_match_batch_ranges_tf(hsm_ctx* h, int batch, const float* begin_world, c
   static const char who[] = "hsm_match_batch_ranges_tf";
   if (!h) return fail(HSM_ERR_INVALID, "null context");
   if (!begin_world || !out_pose) return fail(HSM_ERR_INVALID, "hsm_match_batch_ranges_tf: bad argument");
-  if (int rc = check_batch_ranges_tf(who, batch, ranges, n, tf_rows)) return rc;
+  RangesTfParams P = ranges_tf_params(batch, ranges, n, range_min, range_max, range_cutoff, tf_rows, shared_tf,
+                                      {sqr_laser_min_dist, sqr_laser_max_dist, laser_z_min, laser_z_max, scale_to_map});
+  if (int rc = check_batch_ranges_tf(who, P)) return rc;
   if (batch == 0) return HSM_OK;
-  const size_t bn = (size_t)batch * n;
-  const size_t b_begin = (size_t)batch * 3 * sizeof(float), b_cov = (size_t)batch * 9 * sizeof(float);
-  const size_t b_counts = (size_t)batch * sizeof(int), b_ranges = bn * sizeof(float);
-  const size_t b_tf = (shared_tf ? 1 : (size_t)batch) * 12 * sizeof(double), b_origo = (size_t)batch * 2 * sizeof(float);
-  // device block: transforms | start poses | poses | covariances | counts | origos | offsets | raw ranges | endpoints
-  Carver c;
-  const size_t o_tf = c.take(b_tf), o_begin = c.take(b_begin), o_pose = c.take(b_begin), o_cov = c.take(b_cov);
-  const size_t o_counts = c.take(b_counts), o_origo = c.take(b_origo), o_offs = c.take(b_counts + sizeof(int));
-  const size_t o_ranges = c.take(b_ranges), o_pts = c.take((bn > 0 ? bn : 1) * 2 * sizeof(float));
+  const RangesTfStage st = ranges_tf_stage(batch, n, shared_tf != 0, tf_rows, begin_world, ranges, out_pose, out_cov, out_counts,
+                                           out_origo);
   std::lock_guard<std::mutex> lk(h->mu);
-  const double2* unit = nullptr;
-  if (int rc = ranges_tf_unit_table(h, who, n, angle_min, angle_increment, h->stream, &unit)) return rc;
-  if (!h->d_rbatch.holds(c.total())) HIP_TRY(hipStreamSynchronize(h->stream));
-  if (int rc = h->d_rbatch.reserve(c.total())) return rc;
+  if (int rc = ranges_tf_unit_table(h, who, P, angle_min, angle_increment, h->stream)) return rc;
+  if (!h->d_rbatch.holds(st.plan.total())) HIP_TRY(hipStreamSynchronize(h->stream));
+  if (int rc = h->d_rbatch.reserve(st.plan.total())) return rc;
   char* base = h->d_rbatch;
-  double* d_tf = (double*)(base + o_tf);
-  float* d_begin = (float*)(base + o_begin);
-  float* d_pose = (float*)(base + o_pose);
-  float* d_cov = (float*)(base + o_cov);
-  int* d_counts = (int*)(base + o_counts);
-  float* d_origo = (float*)(base + o_origo);
-  int* d_offs = (int*)(base + o_offs);
-  float* d_ranges = (float*)(base + o_ranges);
-  float* d_pts = (float*)(base + o_pts);
-  HIP_TRY(hipMemcpyAsync(d_tf, tf_rows, b_tf, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(d_begin, begin_world, b_begin, hipMemcpyHostToDevice, h->stream));
-  if (b_ranges) HIP_TRY(hipMemcpyAsync(d_ranges, ranges, b_ranges, hipMemcpyHostToDevice, h->stream));
-  if (out_cov) HIP_TRY(hipMemcpyAsync(d_cov, out_cov, b_cov, hipMemcpyHostToDevice, h->stream));  // in/out (empty scans)
-  if (int rc = launch_ingest_batch_ranges_tf(unit, batch, d_ranges, n, range_min, range_max, range_cutoff, d_tf, shared_tf,
-                                             sqr_laser_min_dist, sqr_laser_max_dist, laser_z_min, laser_z_max, scale_to_map,
-                                             d_pts, d_offs, d_counts, out_origo ? d_origo : nullptr, h->stream))
+  P.ranges = staged<float>(base, st.ranges);
+  P.tf_rows = staged<double>(base, st.tf);
+  float* d_pts = staged<float>(base, st.pts);
+  int* d_offs = staged<int>(base, st.offs);
+  if (int rc = stage_copy_in(st.plan, base, h->stream)) return rc;
+  if (int rc = launch_ingest_batch_ranges_tf(P, d_pts, d_offs, staged<int>(base, st.counts), staged<float>(base, st.origo, out_origo),
+                                             h->stream))
     return rc;
   // n is a true bound of every scan's length after the gates
-  if (int rc = match_batch_device_nolock(h, batch, d_begin, d_pts, d_offs, n, d_pose, out_cov ? d_cov : nullptr, h->stream, n))
+  if (int rc = match_batch_device_nolock(h, batch, staged<float>(base, st.begin), d_pts, d_offs, n, staged<float>(base, st.pose),
+                                         staged<float>(base, st.cov, out_cov), h->stream, n))
     return rc;
-  HIP_TRY(hipMemcpyAsync(out_pose, d_pose, b_begin, hipMemcpyDeviceToHost, h->stream));
-  if (out_cov) HIP_TRY(hipMemcpyAsync(out_cov, d_cov, b_cov, hipMemcpyDeviceToHost, h->stream));
-  if (out_counts) HIP_TRY(hipMemcpyAsync(out_counts, d_counts, b_counts, hipMemcpyDeviceToHost, h->stream));
-  if (out_origo) HIP_TRY(hipMemcpyAsync(out_origo, d_origo, b_origo, hipMemcpyDeviceToHost, h->stream));
+  if (int rc = stage_copy_out(st.plan, base, h->stream)) return rc;
   HIP_TRY(hipStreamSynchronize(h->stream));
   return HSM_OK;
 }
@@ -2609,33 +2617,25 @@ size_t hsm_slam_ranges_tf_workspace(int count, int n) {  // (the layout: stage_l
 // The conversion's three launches and the loop of hsm_slam_scans_device_origos, all on the context's stream and under its lock;
 // `s` is waited for once in front and waits once behind.  Every check comes before the first launch; a geometry not seen before is
 // uploaded (on the context's stream, which is waited for) before anything is queued.
-static int slam_ranges_tf_nolock(hsm_ctx* h, const char* who, int count, const float* d_start_pose, const float* d_hint_deltas,
-                                 const float* d_ranges, int n, float angle_min, float angle_increment, float range_min,
-                                 float range_max, double range_cutoff, const double* d_tf_rows, int shared_tf,
-                                 float sqr_laser_min_dist, float sqr_laser_max_dist, float laser_z_min, float laser_z_max,
-                                 float scale_to_map, const unsigned char* d_force, float* d_out_pose, float* d_out_cov,
-                                 int* d_out_applied, int* d_out_counts, void* d_workspace, size_t workspace_bytes, hipStream_t s) {
+static int slam_ranges_tf_nolock(hsm_ctx* h, const char* who, const ScanLog& log, RangesTfParams P, float angle_min,
+                                 float angle_increment, void* d_workspace, size_t workspace_bytes, hipStream_t s) {
   SlamRangesTfLayout L;
-  if (!slam_ranges_tf_layout(count, n, &L)) return fail(HSM_ERR_TOO_LARGE, (std::string(who) + ": n > HSM_MAX_UPDATE_BEAMS or count * n > INT_MAX").c_str());
+  if (!slam_ranges_tf_layout(P.batch, P.n, &L)) return fail_at(HSM_ERR_TOO_LARGE, who, ": n > HSM_MAX_UPDATE_BEAMS or count * n > INT_MAX");
   if (!d_workspace || workspace_bytes < L.total || ((uintptr_t)d_workspace & 7u) != 0)
-    return fail(HSM_ERR_INVALID, (std::string(who) + ": workspace smaller than hsm_slam_ranges_tf_workspace(count, n) or not 8-byte aligned").c_str());
+    return fail_at(HSM_ERR_INVALID, who, ": workspace smaller than hsm_slam_ranges_tf_workspace(count, n) or not 8-byte aligned");
   if (int rc = select_device(h)) return rc;
   if (int rc = slam_refuse_capture(h, s, who)) return rc;
-  const double2* unit = nullptr;
-  if (int rc = ranges_tf_unit_table(h, who, n, angle_min, angle_increment, h->stream, &unit)) return rc;
-  if (int rc = slam_wait_for_caller(h, s)) return rc;
+  if (int rc = ranges_tf_unit_table(h, who, P, angle_min, angle_increment, h->stream)) return rc;
+  if (int rc = wait_for_caller_inputs(h, s)) return rc;
   char* ws = (char*)d_workspace;
-  float* pts = reinterpret_cast<float*>(ws + L.pts);
-  int* offsets = reinterpret_cast<int*>(ws + L.offsets);
-  float* origos = reinterpret_cast<float*>(ws + L.origos);
-  if (int rc = launch_ingest_batch_ranges_tf(unit, count, d_ranges, n, range_min, range_max, range_cutoff, d_tf_rows, shared_tf,
-                                             sqr_laser_min_dist, sqr_laser_max_dist, laser_z_min, laser_z_max, scale_to_map, pts,
-                                             offsets, reinterpret_cast<int*>(ws + L.counts), origos, h->stream, d_out_counts))
-    return rc;
   // n is a true bound of every scan's length after the gates
-  if (int rc = slam_scans_queue(h, count, d_start_pose, d_hint_deltas, pts, offsets, n, nullptr, origos, d_force, d_out_pose,
-                                d_out_cov, d_out_applied, who))
+  PosedScans scans{P.batch, nullptr, staged<float>(ws, L.pts), staged<int>(ws, L.offsets), 0, P.n};
+  scans.d_origos = staged<float>(ws, L.origos);
+  scans.who = who;
+  if (int rc = launch_ingest_batch_ranges_tf(P, staged<float>(ws, L.pts), staged<int>(ws, L.offsets), staged<int>(ws, L.counts),
+                                             staged<float>(ws, L.origos), h->stream, log.d_out_counts))
     return rc;
+  if (int rc = slam_scans_queue(h, log, scans)) return rc;
   return slam_caller_waits(h, s);
 }
 
@@ -2649,13 +2649,14 @@ int hsm_slam_ranges_tf_device(hsm_ctx* h, int count, const float* d_start_pose, 
   if (!h) return fail(HSM_ERR_INVALID, "null context");
   if ((count > 0 && !d_out_pose) || ((uintptr_t)d_tf_rows & 7u) != 0)
     return fail(HSM_ERR_INVALID, "hsm_slam_ranges_tf_device: bad argument");
-  if (int rc = check_batch_ranges_tf(who, count, d_ranges, n, d_tf_rows)) return rc;
+  RangesTfParams P = ranges_tf_params(count, d_ranges, n, range_min, range_max, range_cutoff, d_tf_rows, shared_tf,
+                                      {sqr_laser_min_dist, sqr_laser_max_dist, laser_z_min, laser_z_max, scale_to_map});
+  if (int rc = check_batch_ranges_tf(who, P)) return rc;
   if (count == 0) return HSM_OK;
+  const ScanLog log{count, d_start_pose, d_hint_deltas, d_force, d_out_pose, d_out_cov, d_out_applied, d_out_counts};
   std::lock_guard<std::mutex> lk(h->mu);
-  return slam_ranges_tf_nolock(h, who, count, d_start_pose, d_hint_deltas, d_ranges, n, angle_min, angle_increment, range_min,
-                               range_max, range_cutoff, d_tf_rows, shared_tf, sqr_laser_min_dist, sqr_laser_max_dist, laser_z_min,
-                               laser_z_max, scale_to_map, d_force, d_out_pose, d_out_cov, d_out_applied, d_out_counts, d_workspace,
-                               workspace_bytes, static_cast<hipStream_t>(stream));
+  return slam_ranges_tf_nolock(h, who, log, P, angle_min, angle_increment, d_workspace, workspace_bytes,
+                               static_cast<hipStream_t>(stream));
 }
 
 int hsm_slam_ranges_tf(hsm_ctx* h, int count, const float* start_pose, const float* hint_deltas, const float* ranges, int n,
@@ -2666,50 +2667,33 @@ int hsm_slam_ranges_tf(hsm_ctx* h, int count, const float* start_pose, const flo
   static const char who[] = "hsm_slam_ranges_tf";
   if (!h) return fail(HSM_ERR_INVALID, "null context");
   if (count > 0 && !out_pose) return fail(HSM_ERR_INVALID, "hsm_slam_ranges_tf: bad argument");
-  if (int rc = check_batch_ranges_tf(who, count, ranges, n, tf_rows)) return rc;
+  RangesTfParams P = ranges_tf_params(count, ranges, n, range_min, range_max, range_cutoff, tf_rows, shared_tf,
+                                      {sqr_laser_min_dist, sqr_laser_max_dist, laser_z_min, laser_z_max, scale_to_map});
+  if (int rc = check_batch_ranges_tf(who, P)) return rc;
   if (count == 0) return HSM_OK;
   SlamRangesTfLayout L;
   slam_ranges_tf_layout(count, n, &L);  // (the sizes passed check_batch_ranges_tf)
-  const size_t b3 = (size_t)count * 3 * sizeof(float), b_cov = (size_t)count * 9 * sizeof(float);
-  const size_t b_int = (size_t)count * sizeof(int), b_ranges = (size_t)count * n * sizeof(float);
-  const size_t b_tf = (shared_tf ? 1 : (size_t)count) * 12 * sizeof(double), b_origo = (size_t)count * 2 * sizeof(float);
-  // device block: transforms | start pose | hint deltas | force | poses | covariances | applied | counts | raw ranges | workspace
-  Carver c;
-  const size_t o_tf = c.take(b_tf), o_start = c.take(3 * sizeof(float)), o_deltas = c.take(b3), o_force = c.take((size_t)count);
-  const size_t o_pose = c.take(b3), o_cov = c.take(b_cov), o_applied = c.take(b_int), o_counts = c.take(b_int);
-  const size_t o_ranges = c.take(b_ranges), o_ws = c.take(L.total);
+  const SlamRangesTfStage st = slam_ranges_tf_stage(count, n, shared_tf != 0, L, tf_rows, start_pose, hint_deltas, force, ranges,
+                                                    out_pose, out_cov, out_applied, out_counts, out_origo);
   std::lock_guard<std::mutex> lk(h->mu);
   if (int rc = select_device(h)) return rc;
   if (int rc = slam_refuse_capture(h, h->stream, who)) return rc;  // (before the copies are queued)
-  if (!h->d_rbatch.holds(c.total())) HIP_TRY(hipStreamSynchronize(h->stream));
-  if (int rc = h->d_rbatch.reserve(c.total())) return rc;
+  if (!h->d_rbatch.holds(st.plan.total())) HIP_TRY(hipStreamSynchronize(h->stream));
+  if (int rc = h->d_rbatch.reserve(st.plan.total())) return rc;
   char* base = h->d_rbatch;
-  double* d_tf = (double*)(base + o_tf);
-  float* d_start = (float*)(base + o_start);
-  float* d_deltas = (float*)(base + o_deltas);
-  unsigned char* d_force = (unsigned char*)(base + o_force);
-  float* d_pose = (float*)(base + o_pose);
-  float* d_cov = (float*)(base + o_cov);
-  int* d_applied = (int*)(base + o_applied);
-  int* d_counts = (int*)(base + o_counts);
-  float* d_ranges = (float*)(base + o_ranges);
-  HIP_TRY(hipMemcpyAsync(d_tf, tf_rows, b_tf, hipMemcpyHostToDevice, h->stream));
-  if (start_pose) HIP_TRY(hipMemcpyAsync(d_start, start_pose, 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  if (hint_deltas) HIP_TRY(hipMemcpyAsync(d_deltas, hint_deltas, b3, hipMemcpyHostToDevice, h->stream));
-  if (force) HIP_TRY(hipMemcpyAsync(d_force, force, (size_t)count, hipMemcpyHostToDevice, h->stream));
-  if (b_ranges) HIP_TRY(hipMemcpyAsync(d_ranges, ranges, b_ranges, hipMemcpyHostToDevice, h->stream));
-  if (out_cov) HIP_TRY(hipMemcpyAsync(d_cov, out_cov, b_cov, hipMemcpyHostToDevice, h->stream));  // in/out (empty scans)
-  if (int rc = slam_ranges_tf_nolock(h, who, count, start_pose ? d_start : nullptr, hint_deltas ? d_deltas : nullptr, d_ranges, n,
-                                     angle_min, angle_increment, range_min, range_max, range_cutoff, d_tf, shared_tf,
-                                     sqr_laser_min_dist, sqr_laser_max_dist, laser_z_min, laser_z_max, scale_to_map,
-                                     force ? d_force : nullptr, d_pose, out_cov ? d_cov : nullptr, out_applied ? d_applied : nullptr,
-                                     out_counts ? d_counts : nullptr, base + o_ws, L.total, h->stream))
-    return rc;
-  HIP_TRY(hipMemcpyAsync(out_pose, d_pose, b3, hipMemcpyDeviceToHost, h->stream));
-  if (out_cov) HIP_TRY(hipMemcpyAsync(out_cov, d_cov, b_cov, hipMemcpyDeviceToHost, h->stream));
-  if (out_applied) HIP_TRY(hipMemcpyAsync(out_applied, d_applied, b_int, hipMemcpyDeviceToHost, h->stream));
-  if (out_counts) HIP_TRY(hipMemcpyAsync(out_counts, d_counts, b_int, hipMemcpyDeviceToHost, h->stream));
-  if (out_origo) HIP_TRY(hipMemcpyAsync(out_origo, base + o_ws + L.origos, b_origo, hipMemcpyDeviceToHost, h->stream));
+  P.ranges = staged<float>(base, st.ranges);
+  P.tf_rows = staged<double>(base, st.tf);
+  const ScanLog log{count,
+                    staged<float>(base, st.start, start_pose),
+                    staged<float>(base, st.deltas, hint_deltas),
+                    staged<unsigned char>(base, st.force, force),
+                    staged<float>(base, st.pose),
+                    staged<float>(base, st.cov, out_cov),
+                    staged<int>(base, st.applied, out_applied),
+                    staged<int>(base, st.counts, out_counts)};
+  if (int rc = stage_copy_in(st.plan, base, h->stream)) return rc;
+  if (int rc = slam_ranges_tf_nolock(h, who, log, P, angle_min, angle_increment, base + st.ws, L.total, h->stream)) return rc;
+  if (int rc = stage_copy_out(st.plan, base, h->stream)) return rc;
   HIP_TRY(hipStreamSynchronize(h->stream));
   return HSM_OK;
 }

@@ -138,6 +138,31 @@ inline bool stream_capturing(hipStream_t s) {
   return cs != hipStreamCaptureStatusNone;
 }
 
+// The copies of a host-array entry's staging block (stage_layout.h StagePlan) whose regions start at `base`, queued on `s`:
+// every host array in, ahead of the entry's first launch ...
+inline int stage_copy_in(const StagePlan& st, char* base, hipStream_t s) {
+  for (int i = 0; i < st.n; ++i)
+    if (st.r[i].src && st.r[i].bytes)
+      HSM_HIP_TRY(hipMemcpyAsync(base + st.r[i].off, st.r[i].src, st.r[i].bytes, hipMemcpyHostToDevice, s));
+  return HSM_OK;
+}
+// ... and every result out, behind its last one (the entry then waits for `s` once)
+inline int stage_copy_out(const StagePlan& st, char* base, hipStream_t s) {
+  for (int i = 0; i < st.n; ++i)
+    if (st.r[i].dst && st.r[i].bytes)
+      HSM_HIP_TRY(hipMemcpyAsync(st.r[i].dst, base + st.r[i].off, st.r[i].bytes, hipMemcpyDeviceToHost, s));
+  return HSM_OK;
+}
+// the device address of a region; the three-argument form: null where the host array it stands for is absent
+template <class T>
+T* staged(char* base, size_t off) {
+  return reinterpret_cast<T*>(base + off);
+}
+template <class T>
+T* staged(char* base, size_t off, const void* host) {
+  return host ? reinterpret_cast<T*>(base + off) : nullptr;
+}
+
 }  // namespace hsm_host
 
 using hsm_host::Level;

@@ -2,6 +2,7 @@
 // 256-byte aligned regions of one allocation start.  Plain C++ (no HIP header): tests/cpp/stage_layout_check.cpp compiles it with
 // the host compiler and holds it to the written-out sums (tests/test_stage_layout.py).
 #pragma once
+#include <assert.h>
 #include <limits.h>
 #include <stddef.h>
 
@@ -95,6 +96,118 @@ inline BatchLayout batch_layout(const BatchBytes& b, bool pinned) {
   L.bpose = c.take(b.bpose);
   L.total = c.total();
   return L;
+}
+
+// The staging block of a host-array entry: its regions in the order they are carved, each with the host array that is copied
+// into it before the launches (src), the host array that receives it after them (dst), both (an in/out array) or neither (device
+// scratch).  A null array or an empty region is not copied; the copies are queued in the order of the list (hsm_ctx.h stage_copy_in /
+// stage_copy_out).
+struct StageRegion {
+  size_t off, bytes;
+  const void* src;
+  void* dst;
+};
+
+struct StagePlan {
+  static constexpr int kMaxRegions = 12;
+  StageRegion r[kMaxRegions];
+  int n = 0;
+  Carver c;
+  size_t add(size_t bytes, const void* src = nullptr, void* dst = nullptr) { return view(c.take(bytes), bytes, src, dst); }
+  // a copy into or out of part of a region carved before: it takes no room
+  size_t view(size_t off, size_t bytes, const void* src, void* dst) {
+    assert(n < kMaxRegions);
+    r[n++] = {off, bytes, src, dst};
+    return off;
+  }
+  size_t total() const { return c.total(); }
+};
+
+// hsm_update_by_scans (d_upd_stage): end points[total_pts] | poses[count * 3] | offsets[count + 1]
+struct UpdateScansStage {
+  StagePlan plan;
+  size_t pts, poses, offs;
+};
+
+inline UpdateScansStage update_scans_stage(int count, size_t total_pts, const float* poses, const float* pts, const int* offsets) {
+  UpdateScansStage s;
+  s.pts = s.plan.add(total_pts * 2 * sizeof(float), pts);
+  s.poses = s.plan.add((size_t)count * 3 * sizeof(float), poses);
+  s.offs = s.plan.add(((size_t)count + 1) * sizeof(int), offsets);
+  return s;
+}
+
+// hsm_match_batch_ranges (d_rbatch): start poses | poses | covariances | counts | raw ranges | the device call's workspace.
+// The covariances go in and out: the matcher leaves an empty scan's as it was.
+struct RangesStage {
+  StagePlan plan;
+  size_t begin, pose, cov, counts, ranges, ws;
+};
+
+inline RangesStage ranges_stage(int batch, int n, size_t ws_bytes, const float* begin, const float* ranges, float* out_pose,
+                                float* out_cov, int* out_counts) {
+  const size_t b3 = (size_t)batch * 3 * sizeof(float);
+  RangesStage s;
+  s.begin = s.plan.add(b3, begin);
+  s.pose = s.plan.add(b3, nullptr, out_pose);
+  s.cov = s.plan.add((size_t)batch * 9 * sizeof(float), nullptr, out_cov);
+  s.counts = s.plan.add((size_t)batch * sizeof(int), nullptr, out_counts);
+  s.ranges = s.plan.add((size_t)batch * (size_t)n * sizeof(float), ranges);
+  s.ws = s.plan.add(ws_bytes);
+  s.plan.view(s.cov, (size_t)batch * 9 * sizeof(float), out_cov, nullptr);  // (in as well, behind the other copies in)
+  return s;
+}
+
+// hsm_match_batch_ranges_tf (d_rbatch): transforms[batch or 1][12] | start poses | poses | covariances | counts | origos |
+// offsets[batch + 1] | raw ranges | endpoints[max(batch * n, 1)]
+struct RangesTfStage {
+  StagePlan plan;
+  size_t tf, begin, pose, cov, counts, origo, offs, ranges, pts;
+};
+
+inline RangesTfStage ranges_tf_stage(int batch, int n, bool shared_tf, const double* tf_rows, const float* begin,
+                                     const float* ranges, float* out_pose, float* out_cov, int* out_counts, float* out_origo) {
+  const size_t bn = (size_t)batch * (size_t)n, b3 = (size_t)batch * 3 * sizeof(float), b_int = (size_t)batch * sizeof(int);
+  RangesTfStage s;
+  s.tf = s.plan.add((shared_tf ? 1 : (size_t)batch) * 12 * sizeof(double), tf_rows);
+  s.begin = s.plan.add(b3, begin);
+  s.pose = s.plan.add(b3, nullptr, out_pose);
+  s.cov = s.plan.add((size_t)batch * 9 * sizeof(float), nullptr, out_cov);
+  s.counts = s.plan.add(b_int, nullptr, out_counts);
+  s.origo = s.plan.add((size_t)batch * 2 * sizeof(float), nullptr, out_origo);
+  s.offs = s.plan.add(b_int + sizeof(int));
+  s.ranges = s.plan.add(bn * sizeof(float), ranges);
+  s.pts = s.plan.add((bn > 0 ? bn : 1) * 2 * sizeof(float));
+  s.plan.view(s.cov, (size_t)batch * 9 * sizeof(float), out_cov, nullptr);  // (in as well, behind the other copies in)
+  return s;
+}
+
+// hsm_slam_ranges_tf (d_rbatch): transforms[count or 1][12] | start pose | hint deltas | force | poses | covariances | applied |
+// counts | raw ranges | the device call's workspace `L`, whose origos are copied out where they lie
+struct SlamRangesTfStage {
+  StagePlan plan;
+  size_t tf, start, deltas, force, pose, cov, applied, counts, ranges, ws;
+};
+
+inline SlamRangesTfStage slam_ranges_tf_stage(int count, int n, bool shared_tf, const SlamRangesTfLayout& L, const double* tf_rows,
+                                              const float* start_pose, const float* hint_deltas, const unsigned char* force,
+                                              const float* ranges, float* out_pose, float* out_cov, int* out_applied,
+                                              int* out_counts, float* out_origo) {
+  const size_t b3 = (size_t)count * 3 * sizeof(float), b_int = (size_t)count * sizeof(int);
+  SlamRangesTfStage s;
+  s.tf = s.plan.add((shared_tf ? 1 : (size_t)count) * 12 * sizeof(double), tf_rows);
+  s.start = s.plan.add(3 * sizeof(float), start_pose);
+  s.deltas = s.plan.add(b3, hint_deltas);
+  s.force = s.plan.add((size_t)count, force);
+  s.pose = s.plan.add(b3, nullptr, out_pose);
+  s.cov = s.plan.add((size_t)count * 9 * sizeof(float), nullptr, out_cov);
+  s.applied = s.plan.add(b_int, nullptr, out_applied);
+  s.counts = s.plan.add(b_int, nullptr, out_counts);
+  s.ranges = s.plan.add((size_t)count * (size_t)n * sizeof(float), ranges);
+  s.ws = s.plan.add(L.total);
+  s.plan.view(s.cov, (size_t)count * 9 * sizeof(float), out_cov, nullptr);  // (in as well, behind the other copies in)
+  s.plan.view(s.ws + L.origos, (size_t)count * 2 * sizeof(float), nullptr, out_origo);
+  return s;
 }
 
 }  // namespace hsm_host

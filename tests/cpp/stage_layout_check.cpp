@@ -1,7 +1,9 @@
 // stage_layout_check.cpp -- hector_slam_amd/csrc/stage_layout.h against the sums the host runtime wrote out by hand before
 // the header existed: the workspace of hsm_match_batch_ranges_device, the staging blocks of hsm_match_batch /
 // hsm_match_score_batch (device and pinned form; with and without score, residual, ranking and its optional arrays) and the
-// growth rule of every grow-on-demand buffer.  Every case is compared exactly; prints one JSON line, exits 1 on a mismatch.
+// growth rule of every grow-on-demand buffer; and the staging plans of the four host-array entries built on StagePlan
+// (hsm_update_by_scans, hsm_match_batch_ranges, hsm_match_batch_ranges_tf, hsm_slam_ranges_tf) against each entry's layout written
+// out term by term, with the copies a plan asks for.  Every case is compared exactly; prints one JSON line, exits 1 on a mismatch.
 #include <stdio.h>
 
 #include <vector>
@@ -98,6 +100,162 @@ static void check_growth(size_t n) {
   same(grown_capacity((n + 4095) / 4096 * 4096, kExact), (n + 4095) / 4096 * 4096, "multiples of 4096", n, 0, 0);
 }
 
+// ---- the staging plans of the host-array entries: offsets and totals written out term by term, as the entries carved them by hand
+// before StagePlan; and which regions are copied in and out (null array or empty region: no copy) ----
+static const float kF[1] = {0};  // any non-null host array
+static const double kD[1] = {0};
+static const int kI[1] = {0};
+static const unsigned char kU[1] = {0};
+
+// the copies of a plan: region `off` is copied in from `src` / out to `dst` over `bytes`, and nothing else is
+struct WantCopy {
+  size_t off, bytes;
+  const void* src;
+  const void* dst;
+};
+static void check_copies(const StagePlan& p, const std::vector<WantCopy>& want, const char* what, long long a, long long b, long long c) {
+  size_t in = 0, out = 0, want_in = 0, want_out = 0;
+  for (const WantCopy& w : want) {
+    const bool does_in = w.src && w.bytes, does_out = w.dst && w.bytes;
+    want_in += does_in;
+    want_out += does_out;
+    bool found_in = !does_in, found_out = !does_out;
+    for (int i = 0; i < p.n; ++i) {
+      const StageRegion& r = p.r[i];
+      if (does_in && r.src == w.src && r.off == w.off && r.bytes == w.bytes) found_in = true;
+      if (does_out && r.dst == w.dst && r.off == w.off && r.bytes == w.bytes) found_out = true;
+    }
+    same(found_in && found_out, true, what, a, b, c);
+  }
+  for (int i = 0; i < p.n; ++i) in += p.r[i].src && p.r[i].bytes, out += p.r[i].dst && p.r[i].bytes;
+  same(in, want_in, what, a, b, c);
+  same(out, want_out, what, a, b, c);
+}
+
+// flags: 1 pts, 2 offsets
+static void check_update_scans_stage(int count, size_t total, int flags) {
+  const float* pts = flags & 1 ? kF : nullptr;
+  const int* offsets = flags & 2 ? kI : nullptr;
+  const size_t b_pts = total * 2 * sizeof(float), b_poses = (size_t)count * 3 * sizeof(float), b_offs = ((size_t)count + 1) * sizeof(int);
+  const UpdateScansStage s = update_scans_stage(count, total, kF, pts, offsets);
+  same(s.pts, 0, "update stage pts", count, total, flags);
+  same(s.poses, al(b_pts), "update stage poses", count, total, flags);
+  same(s.offs, al(b_pts) + al(b_poses), "update stage offsets", count, total, flags);
+  same(s.plan.total(), al(b_pts) + al(b_poses) + al(b_offs), "update stage total", count, total, flags);
+  check_copies(s.plan, {{0, b_pts, pts, nullptr}, {al(b_pts), b_poses, kF, nullptr}, {al(b_pts) + al(b_poses), b_offs, offsets, nullptr}},
+               "update stage copies", count, total, flags);
+}
+
+// flags: 1 out_cov, 2 out_counts, 4 ranges
+static void check_ranges_stage(int batch, int n, int flags) {
+  RangesLayout L;
+  if (!ranges_layout(batch, n, &L)) return;
+  float cov[1], pose[1];
+  int counts[1];
+  float* out_cov = flags & 1 ? cov : nullptr;
+  int* out_counts = flags & 2 ? counts : nullptr;
+  const float* ranges = flags & 4 ? kF : nullptr;
+  const size_t b_begin = (size_t)batch * 3 * sizeof(float), b_cov = (size_t)batch * 9 * sizeof(float);
+  const size_t b_counts = (size_t)batch * sizeof(int), b_ranges = (size_t)batch * n * sizeof(float);
+  const size_t o_pose = al(b_begin), o_cov = al(b_begin) + al(b_begin), o_counts = al(b_begin) + al(b_begin) + al(b_cov);
+  const size_t o_ranges = al(b_begin) + al(b_begin) + al(b_cov) + al(b_counts);
+  const size_t o_ws = al(b_begin) + al(b_begin) + al(b_cov) + al(b_counts) + al(b_ranges);
+  const RangesStage s = ranges_stage(batch, n, L.total, kF, ranges, pose, out_cov, out_counts);
+  same(s.begin, 0, "ranges stage begin", batch, n, flags);
+  same(s.pose, o_pose, "ranges stage pose", batch, n, flags);
+  same(s.cov, o_cov, "ranges stage cov", batch, n, flags);
+  same(s.counts, o_counts, "ranges stage counts", batch, n, flags);
+  same(s.ranges, o_ranges, "ranges stage ranges", batch, n, flags);
+  same(s.ws, o_ws, "ranges stage workspace", batch, n, flags);
+  same(s.plan.total(), o_ws + al(L.total), "ranges stage total", batch, n, flags);
+  check_copies(s.plan, {{0, b_begin, kF, nullptr}, {o_pose, b_begin, nullptr, pose}, {o_cov, b_cov, out_cov, out_cov},
+                        {o_counts, b_counts, nullptr, out_counts}, {o_ranges, b_ranges, ranges, nullptr}},
+               "ranges stage copies", batch, n, flags);
+}
+
+// flags: 1 out_cov, 2 out_counts, 4 ranges, 8 out_origo, 16 shared_tf
+static void check_ranges_tf_stage(int batch, int n, int flags) {
+  if (batch < 0 || n < 0 || n > HSM_MAX_UPDATE_BEAMS || (size_t)batch * (size_t)n > (size_t)INT_MAX) return;
+  float cov[1], pose[1], origo[1];
+  int counts[1];
+  float* out_cov = flags & 1 ? cov : nullptr;
+  int* out_counts = flags & 2 ? counts : nullptr;
+  const float* ranges = flags & 4 ? kF : nullptr;
+  float* out_origo = flags & 8 ? origo : nullptr;
+  const bool shared_tf = flags & 16;
+  const size_t bn = (size_t)batch * n;
+  const size_t b_begin = (size_t)batch * 3 * sizeof(float), b_cov = (size_t)batch * 9 * sizeof(float);
+  const size_t b_counts = (size_t)batch * sizeof(int), b_ranges = bn * sizeof(float);
+  const size_t b_tf = (shared_tf ? 1 : (size_t)batch) * 12 * sizeof(double), b_origo = (size_t)batch * 2 * sizeof(float);
+  const size_t o_begin = al(b_tf), o_pose = al(b_tf) + al(b_begin), o_cov = al(b_tf) + al(b_begin) + al(b_begin);
+  const size_t o_counts = al(b_tf) + al(b_begin) + al(b_begin) + al(b_cov);
+  const size_t o_origo = al(b_tf) + al(b_begin) + al(b_begin) + al(b_cov) + al(b_counts);
+  const size_t o_offs = al(b_tf) + al(b_begin) + al(b_begin) + al(b_cov) + al(b_counts) + al(b_origo);
+  const size_t o_ranges = al(b_tf) + al(b_begin) + al(b_begin) + al(b_cov) + al(b_counts) + al(b_origo) + al(b_counts + sizeof(int));
+  const size_t o_pts = o_ranges + al(b_ranges);
+  const size_t total = o_pts + al((bn > 0 ? bn : 1) * 2 * sizeof(float));
+  const RangesTfStage s = ranges_tf_stage(batch, n, shared_tf, kD, kF, ranges, pose, out_cov, out_counts, out_origo);
+  same(s.tf, 0, "ranges tf stage tf", batch, n, flags);
+  same(s.begin, o_begin, "ranges tf stage begin", batch, n, flags);
+  same(s.pose, o_pose, "ranges tf stage pose", batch, n, flags);
+  same(s.cov, o_cov, "ranges tf stage cov", batch, n, flags);
+  same(s.counts, o_counts, "ranges tf stage counts", batch, n, flags);
+  same(s.origo, o_origo, "ranges tf stage origo", batch, n, flags);
+  same(s.offs, o_offs, "ranges tf stage offsets", batch, n, flags);
+  same(s.ranges, o_ranges, "ranges tf stage ranges", batch, n, flags);
+  same(s.pts, o_pts, "ranges tf stage pts", batch, n, flags);
+  same(s.plan.total(), total, "ranges tf stage total", batch, n, flags);
+  check_copies(s.plan, {{0, b_tf, kD, nullptr}, {o_begin, b_begin, kF, nullptr}, {o_pose, b_begin, nullptr, pose},
+                        {o_cov, b_cov, out_cov, out_cov}, {o_counts, b_counts, nullptr, out_counts},
+                        {o_origo, b_origo, nullptr, out_origo}, {o_ranges, b_ranges, ranges, nullptr}},
+               "ranges tf stage copies", batch, n, flags);
+}
+
+// flags: 1 out_cov, 2 out_counts, 4 ranges, 8 out_origo, 16 shared_tf, 32 start_pose, 64 hint_deltas, 128 force, 256 out_applied
+static void check_slam_ranges_tf_stage(int count, int n, int flags) {
+  SlamRangesTfLayout L;
+  if (!slam_ranges_tf_layout(count, n, &L)) return;
+  float cov[1], pose[1], origo[1];
+  int counts[1], applied[1];
+  float* out_cov = flags & 1 ? cov : nullptr;
+  int* out_counts = flags & 2 ? counts : nullptr;
+  const float* ranges = flags & 4 ? kF : nullptr;
+  float* out_origo = flags & 8 ? origo : nullptr;
+  const bool shared_tf = flags & 16;
+  const float* start = flags & 32 ? kF : nullptr;
+  const float* deltas = flags & 64 ? kF + 0 : nullptr;
+  const unsigned char* force = flags & 128 ? kU : nullptr;
+  int* out_applied = flags & 256 ? applied : nullptr;
+  const size_t b3 = (size_t)count * 3 * sizeof(float), b_cov = (size_t)count * 9 * sizeof(float);
+  const size_t b_int = (size_t)count * sizeof(int), b_ranges = (size_t)count * n * sizeof(float);
+  const size_t b_tf = (shared_tf ? 1 : (size_t)count) * 12 * sizeof(double), b_origo = (size_t)count * 2 * sizeof(float);
+  const size_t o_start = al(b_tf), o_deltas = al(b_tf) + al(3 * sizeof(float)), o_force = al(b_tf) + al(3 * sizeof(float)) + al(b3);
+  const size_t o_pose = al(b_tf) + al(3 * sizeof(float)) + al(b3) + al((size_t)count);
+  const size_t o_cov = al(b_tf) + al(3 * sizeof(float)) + al(b3) + al((size_t)count) + al(b3);
+  const size_t o_applied = al(b_tf) + al(3 * sizeof(float)) + al(b3) + al((size_t)count) + al(b3) + al(b_cov);
+  const size_t o_counts = al(b_tf) + al(3 * sizeof(float)) + al(b3) + al((size_t)count) + al(b3) + al(b_cov) + al(b_int);
+  const size_t o_ranges = al(b_tf) + al(3 * sizeof(float)) + al(b3) + al((size_t)count) + al(b3) + al(b_cov) + al(b_int) + al(b_int);
+  const size_t o_ws = o_ranges + al(b_ranges);
+  const SlamRangesTfStage s = slam_ranges_tf_stage(count, n, shared_tf, L, kD, start, deltas, force, ranges, pose, out_cov, out_applied,
+                                                   out_counts, out_origo);
+  same(s.tf, 0, "slam stage tf", count, n, flags);
+  same(s.start, o_start, "slam stage start", count, n, flags);
+  same(s.deltas, o_deltas, "slam stage deltas", count, n, flags);
+  same(s.force, o_force, "slam stage force", count, n, flags);
+  same(s.pose, o_pose, "slam stage pose", count, n, flags);
+  same(s.cov, o_cov, "slam stage cov", count, n, flags);
+  same(s.applied, o_applied, "slam stage applied", count, n, flags);
+  same(s.counts, o_counts, "slam stage counts", count, n, flags);
+  same(s.ranges, o_ranges, "slam stage ranges", count, n, flags);
+  same(s.ws, o_ws, "slam stage workspace", count, n, flags);
+  same(s.plan.total(), o_ws + al(L.total), "slam stage total", count, n, flags);
+  check_copies(s.plan, {{0, b_tf, kD, nullptr}, {o_start, 3 * sizeof(float), start, nullptr}, {o_deltas, b3, deltas, nullptr},
+                        {o_force, (size_t)count, force, nullptr}, {o_pose, b3, nullptr, pose}, {o_cov, b_cov, out_cov, out_cov},
+                        {o_applied, b_int, nullptr, out_applied}, {o_counts, b_int, nullptr, out_counts},
+                        {o_ranges, b_ranges, ranges, nullptr}, {o_ws + L.origos, b_origo, nullptr, out_origo}},
+               "slam stage copies", count, n, flags);
+}
+
 int main() {
   // sizes around the 256-byte multiples of every element size in play (4, 8, 12, 36 bytes), and the ends of the ranges
   std::vector<long long> sizes = {0, 1, 2, 3, 5, 7, 21, 22, 31, 32, 33, 63, 64, 65, 85, 86, 127, 128, 129, 255, 256, 257, 1023, 1024,
@@ -139,6 +297,18 @@ int main() {
           check_batch((size_t)bt, (size_t)pts, (size_t)G, flags, false);
           if (!(flags & 64)) check_batch((size_t)bt, (size_t)pts, (size_t)G, flags, true);
         }
+  // the staging plans: counts and n of 0 and 1, and one element either side of every 256-byte multiple an element size in play
+  // reaches (4-byte elements at 64, 8 at 32, 12 at 64, 36 at 64, 96 at 8, 1 at 256); every optional array present and absent
+  const std::vector<long long> stage_sizes = {0, 1, 2, 7, 8, 9, 21, 22, 31, 32, 33, 63, 64, 65, 127, 128, 129, 255, 256, 257, 1081};
+  for (long long cnt : stage_sizes) {
+    for (long long t : stage_sizes)
+      for (int flags = 0; flags < 4; ++flags) check_update_scans_stage((int)cnt, (size_t)t, flags);
+    for (long long n : stage_sizes) {
+      for (int flags = 0; flags < 8; ++flags) check_ranges_stage((int)cnt, (int)n, flags);
+      for (int flags = 0; flags < 32; ++flags) check_ranges_tf_stage((int)cnt, (int)n, flags);
+      for (int flags = 0; flags < 512; ++flags) check_slam_ranges_tf_stage((int)cnt, (int)n, flags);
+    }
+  }
   printf("{\"cases\": %lld, \"mismatches\": %lld}\n", cases, mismatches);
   return mismatches ? 1 : 0;
 }
