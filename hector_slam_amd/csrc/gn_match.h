@@ -387,7 +387,9 @@ struct Acc9 {
 //   rotDeriv (:87)          = (-s*px - c*py) * gx + (c*px - s*py) * gy
 // In IEEE arithmetic (-s)*py == -(s*py) and a + (-b) == a - b exactly, and round-to-nearest is
 // symmetric, so  c*px + (-s)*py == c*px - s*py == rx  and  -s*px - c*py == -(s*px + c*py) == -ry
-// BIT FOR BIT: the two products/one sum per component are computed once and reused.
+// BIT FOR BIT, but for the sign of an exact zero (s*px = +0, c*py = -0: -(+0) against -0 - (-0) = +0), which only an end point
+// with a -0.0 component produces and which no sum shows: every chain and partial sum starts at +0, and x + (+-0) == x.
+// The two products/one sum per component are computed once and reused.
 struct BeamRot {
   f2 r;  // (rx, ry)
 };
@@ -1751,6 +1753,9 @@ __global__ void gn_beam_terms_kernel(const LevelView L, const float2* __restrict
     t.M = gx = gy = 0.0f;
     rd = ((-sinRot * p.x - cosRot * p.y) * gx + (cosRot * p.x - sinRot * p.y) * gy);
   }
+  // a rotDeriv of exactly zero: the shared rotation (BeamRot) may give it the other SIGN than the source's expression (an end
+  // point with a -0.0 component: -(0 + -0) is -0, -0 - (-0) is +0).  No sum can show it, this hook can: report the source's
+  if (rd == 0.0f) rd = ((-sinRot * p.x - cosRot * p.y) * gx + (cosRot * p.x - sinRot * p.y) * gy);
   out[i] = make_float4(t.M, gx, gy, rd);
 }
 

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 from hypothesis import HealthCheck, given, seed, settings
 
+import border_cases
 import deep_cases
 import rect_cases
 from conftest import bits, make_oracle, oracle_kinds
@@ -57,7 +58,12 @@ def test_interp_with_derivatives(pair, pyramid_scene):
         s = pyramid_scene.map_size >> lvl
         c = rng.uniform(-3, s + 3, size=(4000, 2)).astype(np.float32)
         c[:8] = [[0, 0], [s - 2, s - 2], [s - 2, 0], [0, s - 2], [s - 1.999, 5], [-0.0, 3], [5, s - 2.0001], [s - 1, s - 1]]
+        # ... and the shared edge values (border_cases.axis_values: +-0, subnormals, lim +- 1 ulp, 2^23 + 0.5, +-1e30 ...), all pairs
+        v = border_cases.axis_values(s - 2)
+        edge = np.stack([np.repeat(v, v.size), np.tile(v, v.size)], 1)
+        c[8:8 + edge.shape[0]] = edge
         assert np.array_equal(bits(ho.interp(lvl, c)), bits(hr.interp(lvl, c)))
+        assert int((ho.interp(lvl, edge)[:, 0] != 0).sum()) > 0  # (this scene's border cells are unknown, 0.5: the edge values sample them)
 
 
 def test_hessian_derivs_and_match_level(pair, pyramid_scene):
