@@ -98,6 +98,10 @@ SIGNATURES = {
     "hsm_match_batch_ranges_tf": (_i, [_vp, _i, _vp, _vp, _i, _f, _f, _f, _f, C.c_double, _vp, _i, _f, _f, _f, _f, _f, _vp, _vp,
                                        _vp, _vp]),
     "hsm_occupancy_grid": (_i, [_vp, _i, _vp]),
+    "hsm_occupancy_grid_device": (_i, [_vp, _i, _vp, _vp]),
+    "hsm_occupancy_changes_device": (_i, [_vp, _i, _vp, _vp, _vp]),
+    "hsm_occupancy_changes": (_i, [_vp, _i, _vp, _i32p]),
+    "hsm_occupancy_restart": (_i, [_vp, _i]),
     "hsm_ray_distances": (_i, [_vp, _i, _f, _f, _f, _i, _f32p, _f32p, _f32p, _f32p]),
     "hsm_score_batch_device": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "hsm_select_best_device": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -535,6 +539,30 @@ class MapRepMultiMap:
         out = np.empty((sy, sx), np.int8)
         _check(self._lib.hsm_occupancy_grid(self._h, level, out.ctypes.data), "hsm_occupancy_grid")
         return out
+
+    def occupancy_grid_device(self, level, d_out, stream=0):
+        """Raw device pointer (int): the whole int8 grid of ``level`` into device memory, queued on the context's stream."""
+        _check(self._lib.hsm_occupancy_grid_device(self._h, level, d_out or None, stream or None), "hsm_occupancy_grid_device")
+
+    def occupancy_changes_device(self, level, d_grid, d_out_bbox=0, stream=0):
+        """Raw device pointers (ints): the cells of ``level`` that may have changed since its last export, into the caller's
+        persistent device grid; ``d_out_bbox`` (int32 [4]) receives the box, 0,0,-1,-1 when nothing changed.  No host wait."""
+        _check(self._lib.hsm_occupancy_changes_device(self._h, level, d_grid or None, d_out_bbox or None, stream or None),
+               "hsm_occupancy_changes_device")
+
+    def occupancy_changes(self, level, grid):
+        """The same into the caller's host grid (int8 [sy, sx], C-contiguous, updated in place) -> the box x0,y0,x1,y1."""
+        sx, sy, _, _ = self.level_info(level)
+        if not (isinstance(grid, np.ndarray) and grid.dtype == np.int8 and grid.shape == (sy, sx) and grid.flags.c_contiguous
+                and grid.flags.writeable):
+            raise ValueError("occupancy_changes: grid must be a writeable C-contiguous int8 array of shape (sy, sx)")
+        bb = np.empty(4, np.int32)
+        _check(self._lib.hsm_occupancy_changes(self._h, level, grid.ctypes.data, bb), "hsm_occupancy_changes")
+        return bb
+
+    def occupancy_restart(self, level=-1):
+        """the next occupancy_changes* of ``level`` (-1: every level) exports the whole level"""
+        _check(self._lib.hsm_occupancy_restart(self._h, level), "hsm_occupancy_restart")
 
     # ---- batched extension ---------------------------------------------------------------
     def match_batch(self, begin_world, pts, offsets=None, want_cov=True):

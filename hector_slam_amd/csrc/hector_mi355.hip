@@ -372,6 +372,27 @@ void fill_schedule(const hsm_ctx* h, MatchParams& P, bool batched = false) {
   }
 }
 
+// acc = the hull of acc and b ({x0, y0, x1, y1} inclusive, empty where x1 < x0); b is not empty
+void box_widen(int acc[4], const int b[4]) {
+  if (acc[2] < acc[0]) {
+    for (int k = 0; k < 4; ++k) acc[k] = b[k];
+    return;
+  }
+  if (b[0] < acc[0]) acc[0] = b[0];
+  if (b[1] < acc[1]) acc[1] = b[1];
+  if (b[2] > acc[2]) acc[2] = b[2];
+  if (b[3] > acc[3]) acc[3] = b[3];
+}
+
+// every cell of the level may have changed (create, reset, upload): host mirrors and the published grid take all of it
+void whole_level_changed(Level& L, bool mirror = true) {
+  const int all[4] = {0, 0, L.sx - 1, L.sy - 1};
+  for (int k = 0; k < 4; ++k) {
+    if (mirror) L.dirty[k] = all[k];
+    L.pub[k] = all[k];
+  }
+}
+
 int valid_level(const hsm_ctx* h, int level) {
   if (!h) return fail(HSM_ERR_INVALID, "null context");
   if (level < 0 || level >= (int)h->levels.size()) return fail(HSM_ERR_INVALID, "level out of range");
@@ -543,14 +564,8 @@ void level_bbox(hsm_ctx* h, UpdateBatch& batch, LevelPrep& prep, const UpdatePar
       if (L.bbox[1] < L.key_rows[0]) L.key_rows[0] = L.bbox[1];
       if (L.bbox[3] > L.key_rows[1]) L.key_rows[1] = L.bbox[3];
     }
-    if (L.dirty[2] < L.dirty[0]) {
-      for (int k = 0; k < 4; ++k) L.dirty[k] = L.bbox[k];
-    } else {
-      if (L.bbox[0] < L.dirty[0]) L.dirty[0] = L.bbox[0];
-      if (L.bbox[1] < L.dirty[1]) L.dirty[1] = L.bbox[1];
-      if (L.bbox[2] > L.dirty[2]) L.dirty[2] = L.bbox[2];
-      if (L.bbox[3] > L.dirty[3]) L.dirty[3] = L.bbox[3];
-    }
+    box_widen(L.dirty, L.bbox);
+    box_widen(L.pub, L.bbox);
   }
 }
 
@@ -694,15 +709,7 @@ int merge_device_boxes(hsm_ctx* h) {
       L.bbox[0] = L.bbox[1] = 0;
       L.bbox[2] = L.bbox[3] = -1;
     }
-    if (run[2] < run[0]) continue;
-    if (L.dirty[2] < L.dirty[0]) {
-      for (int k = 0; k < 4; ++k) L.dirty[k] = run[k];
-    } else {
-      if (run[0] < L.dirty[0]) L.dirty[0] = run[0];
-      if (run[1] < L.dirty[1]) L.dirty[1] = run[1];
-      if (run[2] > L.dirty[2]) L.dirty[2] = run[2];
-      if (run[3] > L.dirty[3]) L.dirty[3] = run[3];
-    }
+    if (run[2] >= run[0]) box_widen(L.dirty, run);
   }
   h->upd_boxes_outstanding = false;
   return HSM_OK;
@@ -884,6 +891,9 @@ int hsm_create(float map_resolution, int size_x, int size_y, unsigned levels, fl
   CREATE_TRY(hipMemsetAsync(h->d_gate, 0, sizeof(GateState), h->stream));
   hipLaunchKernelGGL(update_gate_reset_kernel, dim3(1), dim3(64), 0, h->stream, h->d_gate);
   CREATE_TRY(hipGetLastError());
+  CREATE_TRY(hipMalloc((void**)&h->d_pub_boxes, 3 * kMaxLevels * 4 * sizeof(int)));
+  hipLaunchKernelGGL(update_boxes_clear_kernel, dim3(1), dim3(64), 0, h->stream, h->d_pub_boxes, 2 * kMaxLevels);
+  CREATE_TRY(hipGetLastError());
 
   // MapRepMultiMap ctor (MapRepMultiMap.h:48-72)
   int rx = size_x, ry = size_y;
@@ -927,6 +937,8 @@ int hsm_create(float map_resolution, int size_x, int size_y, unsigned levels, fl
       hsm_destroy(h);
       return HSM_ERR_HIP;
     }
+    whole_level_changed(L, false);  // the first export of a level is all of it (a mirror starts from the same cleared map: not dirty)
+    CREATE_TRY(hipMemcpyAsync(h->d_pub_boxes + (2 * kMaxLevels + i) * 4, L.pub, sizeof L.pub, hipMemcpyHostToDevice, h->stream));
     rx /= 2;
     ry /= 2;
     map_resolution *= 2.0f;
@@ -953,6 +965,7 @@ void hsm_destroy(hsm_ctx* h) {
   TEARDOWN(log, hipFree(h->d_small));
   TEARDOWN(log, hipFree(h->d_partials));
   TEARDOWN(log, hipFree(h->d_gate));
+  TEARDOWN(log, hipFree(h->d_pub_boxes));
   if (h->h_small) TEARDOWN(log, hipHostFree(h->h_small));
   for (hipEvent_t e : {h->copy_evt, h->evt_updates, h->evt_foreign, h->evt_inputs, h->evt_slam_done, h->upd_evt[0], h->upd_evt[1]})
     if (e) TEARDOWN(log, hipEventDestroy(e));
@@ -977,9 +990,7 @@ int hsm_reset(hsm_ctx* h) {
   if (int rc = reset_update_gate(h)) return rc;
   for (Level& L : h->levels) {
     if (int rc = fill_level(h, L)) return rc;
-    L.dirty[0] = L.dirty[1] = 0;  // every cell changed: the whole level is dirty for host mirrors
-    L.dirty[2] = L.sx - 1;
-    L.dirty[3] = L.sy - 1;
+    whole_level_changed(L);
   }
   HIP_TRY(hipStreamSynchronize(h->stream));
   return HSM_OK;
@@ -1950,7 +1961,7 @@ static int update_by_scans_device_nolock(hsm_ctx* h, const PosedScans& S, hipStr
     }
     int* scan_boxes = h->d_upd_boxes + (size_t)update_box_slot(k, count) * kMaxLevels * 4;
     hipLaunchKernelGGL(update_mark_scan_kernel, dim3(occ_blocks + free_blocks, (unsigned)nlev), dim3(256), 0, h->stream,
-                       h->d_upd_batches + k, occ_blocks, scan_boxes, h->d_upd_boxes);
+                       h->d_upd_batches + k, occ_blocks, scan_boxes, h->d_upd_boxes, h->d_pub_boxes);
     if (scatter)
       hipLaunchKernelGGL(update_apply_scan_kernel<true>, dim3(apply_blocks, (unsigned)nlev), dim3(256), 0, h->stream,
                          h->d_upd_batches + k, scan_boxes);
@@ -2836,6 +2847,94 @@ int hsm_occupancy_grid(hsm_ctx* h, int level, signed char* out) {
   return HSM_OK;
 }
 
+// ---- the published grid on the device, and its changed cells only (map_update.h occupancy_box_kernel) ---------------------------
+constexpr unsigned kOccupancyBoxBlocks = 512;  // two workgroups per CU of a whole MI355X: the launch shape cannot depend on the box
+
+static int occupancy_export_refusals(hsm_ctx* h, const void* grid, hipStream_t s, const char* who) {
+  if (!grid) return fail_at(HSM_ERR_INVALID, who, ": the grid is null");
+  return slam_refuse_capture(h, s, who);
+}
+
+// occupancy_box_kernel over the box at `d_box` of level L, into a device grid of any alignment
+static int launch_occupancy_box(hsm_ctx* h, const Level& L, const int* d_box, signed char* d_grid) {
+  hipLaunchKernelGGL(occupancy_box_kernel, dim3(kOccupancyBoxBlocks), dim3(256), 0, h->stream, L.d_logodds, L.sx, d_box, d_grid,
+                     ((uintptr_t)d_grid & 3u) == 0 ? 1 : 0);
+  HIP_TRY(hipGetLastError());
+  return HSM_OK;
+}
+
+// The two launches of an export of `level`'s changed cells into d_grid; afterwards the level's publish box is empty on both
+// sides.  -> *d_box: where the exported box stands once the prep launch has run (until the level's next export).
+static int queue_occupancy_changes(hsm_ctx* h, int level, signed char* d_grid, int* d_out_bbox, const int** d_box) {
+  Level& L = h->levels[level];
+  OccupancyPrepParams A;
+  memset(&A, 0, sizeof A);
+  A.nlev = (int)h->levels.size();
+  A.pub_boxes = h->d_pub_boxes;
+  A.host_box[level] = make_int4(L.pub[0], L.pub[1], L.pub[2], L.pub[3]);
+  A.dims[level] = make_int2(L.sx, L.sy);
+  A.box_out[level] = h->d_pub_boxes + (kMaxLevels + level) * 4;
+  A.bbox_out[level] = d_out_bbox;
+  hipLaunchKernelGGL(occupancy_prep_kernel, dim3(1), dim3(64), 0, h->stream, A);
+  HIP_TRY(hipGetLastError());
+  L.pub[0] = L.pub[1] = 0;
+  L.pub[2] = L.pub[3] = -1;
+  *d_box = A.box_out[level];
+  return launch_occupancy_box(h, L, *d_box, d_grid);
+}
+
+int hsm_occupancy_grid_device(hsm_ctx* h, int level, signed char* d_out, void* stream) {
+  if (int rc = valid_level(h, level)) return rc;
+  std::lock_guard<std::mutex> lk(h->mu);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (int rc = occupancy_export_refusals(h, d_out, s, "hsm_occupancy_grid_device")) return rc;
+  if (int rc = select_device(h)) return rc;
+  if (int rc = wait_for_caller_inputs(h, s)) return rc;
+  if (int rc = launch_occupancy_box(h, h->levels[level], h->d_pub_boxes + (2 * kMaxLevels + level) * 4, d_out)) return rc;
+  return slam_caller_waits(h, s);
+}
+
+int hsm_occupancy_changes_device(hsm_ctx* h, int level, signed char* d_grid, int* d_out_bbox, void* stream) {
+  if (int rc = valid_level(h, level)) return rc;
+  std::lock_guard<std::mutex> lk(h->mu);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (int rc = occupancy_export_refusals(h, d_grid, s, "hsm_occupancy_changes_device")) return rc;
+  if (int rc = select_device(h)) return rc;
+  if (int rc = wait_for_caller_inputs(h, s)) return rc;
+  const int* d_box = nullptr;
+  if (int rc = queue_occupancy_changes(h, level, d_grid, d_out_bbox, &d_box)) return rc;
+  return slam_caller_waits(h, s);
+}
+
+int hsm_occupancy_changes(hsm_ctx* h, int level, signed char* grid, int bbox[4]) {
+  if (int rc = valid_level(h, level)) return rc;
+  if (!grid || !bbox) return fail(HSM_ERR_INVALID, "hsm_occupancy_changes: null argument");
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (int rc = select_device(h)) return rc;
+  Level& L = h->levels[level];
+  if (int rc = h->d_occ.reserve(L.cells())) return rc;
+  const int* d_box = nullptr;
+  if (int rc = queue_occupancy_changes(h, level, h->d_occ, nullptr, &d_box)) return rc;
+  HIP_TRY(hipMemcpyAsync(bbox, d_box, 4 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (bbox[2] < bbox[0]) return HSM_OK;  // nothing changed: `grid` stays as it is
+  const size_t first = (size_t)bbox[1] * L.sx + bbox[0];
+  HIP_TRY(hipMemcpy2DAsync(grid + first, (size_t)L.sx, h->d_occ + first, (size_t)L.sx, (size_t)(bbox[2] - bbox[0] + 1),
+                           (size_t)(bbox[3] - bbox[1] + 1), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return HSM_OK;
+}
+
+int hsm_occupancy_restart(hsm_ctx* h, int level) {
+  if (!h) return fail(HSM_ERR_INVALID, "null context");
+  if (level != -1)
+    if (int rc = valid_level(h, level)) return rc;
+  std::lock_guard<std::mutex> lk(h->mu);
+  for (int l = 0; l < (int)h->levels.size(); ++l)
+    if (level == -1 || l == level) whole_level_changed(h->levels[l], false);
+  return HSM_OK;
+}
+
 int hsm_retain_scan(hsm_ctx* h, const float* pts_xy, int n, const float origo[2]) {
   if (!h) return fail(HSM_ERR_INVALID, "null context");
   if (n < 0 || (n > 0 && !pts_xy)) return fail(HSM_ERR_INVALID, "hsm_retain_scan: bad argument");
@@ -3436,9 +3535,7 @@ int hsm_upload_level(hsm_ctx* h, int level, const float* logodds, const int* upd
   if (update_index)
     HIP_TRY(hipMemcpy(L.d_update_index, update_index, L.cells() * sizeof(int), hipMemcpyHostToDevice));
   if (int rc = rebuild_probability(h, L)) return rc;
-  L.dirty[0] = L.dirty[1] = 0;
-  L.dirty[2] = L.sx - 1;
-  L.dirty[3] = L.sy - 1;
+  whole_level_changed(L);
   HIP_TRY(hipStreamSynchronize(h->stream));
   return HSM_OK;
 }

@@ -56,6 +56,7 @@ struct Level {
   unsigned int serial = 0;  // key-plane generation (map_update.h)
   int bbox[4] = {0, 0, -1, -1};   // cell box touched by the last update
   int dirty[4] = {0, 0, -1, -1};  // union of those boxes since hsm_take_dirty_bbox was last called
+  int pub[4] = {0, 0, -1, -1};    // the host's share of the publish box: the same union since the level was last exported (hsm_occupancy_changes*)
   int key_rows[2] = {0, -1};      // rows that carry keys of the current key generation (union of the boxes since the planes were last cleared)
   bool marks_pending = false;     // a mark pass was queued on this level and its apply pass has not been (scrub_marks)
   size_t cells() const { return (size_t)sx * sy; }
@@ -205,6 +206,10 @@ struct hsm_ctx {
   Buf<int> d_upd_boxes{&bufs};  // allocated last: non-null = both blocks serve d_upd_batches.count() scans
   bool upd_boxes_outstanding = false;  // device-side updates since the host last merged their boxes into Level::bbox / dirty
   hipEvent_t evt_inputs = nullptr;     // the caller's stream at hsm_update_by_scans_device: its inputs are complete
+  // the published grid (map_update.h occupancy_prep_kernel), three rows of kMaxLevels boxes in a block of their own that no
+  // growing buffer replaces: the levels' publish boxes as device-side updates widen them (never fetched), the box of the export
+  // that was queued last on each level (its convert launch reads it), and the whole level as a box (written by hsm_create)
+  int* d_pub_boxes = nullptr;
   // the movement gate of HectorSlamProcessor::update (update_gate.h; map_update.h update_gate_prep_kernel): its state and the
   // count of updates it let through live on the device -- the host never learns a gated call's decisions.  Whoever needs
   // Level's update counters on the host first waits for the stream and folds that count in (fold_gate_counters), like the boxes

@@ -710,6 +710,39 @@ int hsm_ray_distances(hsm_ctx* h, int level, float origin_x, float origin_y, flo
  * (GridMapLogOdds.h:76-84): -1 unknown, 0 free (logOdds < 0), 100 occupied (logOdds > 0).
  * out: host, sx*sy bytes, row major. */
 int hsm_occupancy_grid(hsm_ctx* h, int level, signed char* out);
+/* replaces: the same loop with the grid left in DEVICE memory: d_out, sx*sy bytes, row major, any alignment.  Asynchronous:
+ * the conversion runs on the context's stream, behind every update queued so far and in front of every later one; `stream`
+ * (the caller's, NULL = default stream) is waited for once in front -- d_out may still be in use there -- and waits once
+ * behind, so work queued on it afterwards sees the grid.  The host waits for nothing.  Leaves the publish box of
+ * hsm_occupancy_changes* alone.  HSM_ERR_INVALID, nothing queued: a NULL context or grid, a level out of range, or `stream` /
+ * a stream this context has matched on is being captured into a graph.
+ * Not built: capture into graphs, replay through hsm_group_*, a C++ facade entry (the node's publishMap reads the host
+ * mirror). */
+int hsm_occupancy_grid_device(hsm_ctx* h, int level, signed char* d_out, void* stream);
+/* replaces: publishMap's cell loop (HectorMappingRos.cpp:435-481) restricted to the cells that can differ from the grid
+ *           published before: every level keeps a PUBLISH box, the hull of the cells whose log-odds may have changed since
+ *           the level was last exported -- widened by every update, on the host or on the device, and independent of the
+ *           mirror's box (hsm_take_dirty_bbox and these entries never consume each other's box).
+ *   d_grid      DEVICE, the caller's persistent sx*sy byte grid of this level, row major, any alignment.  Only cells inside
+ *               the exported box are written (-1 / 0 / 100 as above); every other byte keeps its value.
+ *   d_out_bbox  DEVICE, 4 ints, may be NULL: the exported box x0,y0,x1,y1 (inclusive), or 0,0,-1,-1 when nothing changed.
+ * After the call the level's publish box is empty.  The first export of a level is the whole level; so is the first after
+ * hsm_reset, hsm_upload_level or hsm_occupancy_restart.  A scan that a gated call rejected widens nothing.  The box is a
+ * hull: it holds every changed cell and may hold unchanged ones, which are written with the value they have.
+ * ONE consumer per level and context: whoever calls this (or hsm_occupancy_changes) for a level empties that level's box, so
+ * two grids fed from the same level would each miss the other's changes.
+ * Stream rules, ordering and refusals of hsm_occupancy_grid_device; a refused call leaves the publish box as it was.  The
+ * host never learns the box: one preparation launch of one wavefront, one conversion launch whose shape does not depend on it.
+ * Not built: capture into graphs, replay through hsm_group_*, a C++ facade entry. */
+int hsm_occupancy_changes_device(hsm_ctx* h, int level, signed char* d_grid, int* d_out_bbox, void* stream);
+/* the same into a HOST grid (sx*sy bytes, row major): converts into the context's staging grid, fetches the box and copies
+ * the box's rows and columns only (a 2-D copy at pitch sx); bbox[4] receives the box, 0,0,-1,-1 when nothing changed (then
+ * `grid` is not written).  Synchronous: waits for the context's stream.  Shares the level's publish box with
+ * hsm_occupancy_changes_device: one consumer per level. */
+int hsm_occupancy_changes(hsm_ctx* h, int level, signed char* grid, int bbox[4]);
+/* the next hsm_occupancy_changes* of `level` (-1 = every level) exports the whole level: for a consumer that lost or
+ * replaced its grid.  Host bookkeeping only, nothing is queued. */
+int hsm_occupancy_restart(hsm_ctx* h, int level);
 
 /* ---- parity / debug entry points (used by tests, not by the facade) ------------ */
 /* device probability plane p = e^l/(e^l+1) (GridMapLogOdds.h:163-166) */

@@ -1,0 +1,480 @@
+"""hsm_occupancy_changes_device / hsm_occupancy_changes / hsm_occupancy_grid_device / hsm_occupancy_restart on the MI355X: the
+published grid, exported for the cells that may have changed only, without a host wait.
+
+Yardstick for every grid: `Oracle.occupancy_grid(level)` of the CPU checkers ("hr": the unmodified reference, "ho": the
+restatement) driven through the same updates; hsm_occupancy_grid of the same context is a second witness.  Byte grids are
+compared for equality, boxes as integers: no tolerance anywhere.
+
+Every export goes through the untouched-cell check (`export`): the caller's grid is saved and overwritten with the poison byte
+55; after the call the cells inside the returned box hold only -1 / 0 / 100, the cells outside still hold 55, and restoring
+those from the saved copy must give exactly the full export.
+
+Shapes (tests/occupancy_cases.py): a 3-level pyramid of 100 x 76, 50 x 38 and 25 x 19 cells, scans of 16 - 181 beams.
+
+The cell of case 3: the issue behind these entries expected a cell that one scan marks free and the next occupied to hold a
+log-odds of exactly 0 at update factors 0.4 / 0.6.  In fp32 the two increments are -0.40546516 and 0.4054652, not each other's
+negative: both checkers leave 2.9802322e-08 in that cell and publish 100.  The case is kept as stated and held to the checkers;
+the pair 0.25 / 0.75, whose increments do cancel (-1.0986123 / 1.0986123), holds the property that was meant: a touched cell
+whose log-odds is exactly 0 exports -1 while its neighbours export 0 and 100.
+
+Nothing here provokes a device fault."""
+import numpy as np
+import pytest
+
+import occupancy_cases as oc
+from conftest import oracle_kinds
+
+pytestmark = pytest.mark.gpu
+
+HSM_ERR_INVALID = -1
+LEVELS = oc.LEVELS
+ZERO2 = np.zeros(2, np.float32)
+EMPTY = [0, 0, -1, -1]
+
+
+@pytest.fixture(scope="module")
+def capi():
+    import torch
+    assert torch.cuda.is_available(), "gpu-marked tests need a HIP device"
+    from hector_slam_amd import capi as m
+    m.load_library()
+    return m
+
+
+def dev(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
+
+
+def pack(scans):
+    offs = np.zeros(len(scans) + 1, np.int32)
+    offs[1:] = np.cumsum([len(s) for s in scans])
+    return np.ascontiguousarray(np.concatenate([np.asarray(s, np.float32).reshape(-1, 2) for s in scans]), np.float32), offs
+
+
+def new_ctx(capi, free=0.4, occ=0.9):
+    g = capi.MapRepMultiMap(oc.RES, oc.GEOM[0], oc.GEOM[1], LEVELS, startCoords=oc.START)
+    g.setUpdateFactorFree(free)
+    g.setUpdateFactorOccupied(occ)
+    return g
+
+
+def new_refs(oracle_mod, free=0.4, occ=0.9):
+    refs = {}
+    for kind in oracle_kinds():
+        o = oracle_mod.Oracle(kind, oc.RES, oc.GEOM[0], oc.GEOM[1], LEVELS, oc.START)
+        o.set_update_factor_free(free)
+        o.set_update_factor_occupied(occ)
+        refs[kind] = o
+    return refs
+
+
+def host_update(capi, g, pose, scan):
+    """the host path: hsm_retain_scan (what matchData leaves for the coarse levels) + hsm_update_by_scan"""
+    a = np.ascontiguousarray(scan, np.float32).reshape(-1, 2)
+    capi._check(g._lib.hsm_retain_scan(g._h, a.ctypes.data, a.shape[0], ZERO2), "hsm_retain_scan")
+    g.updateByScan(a, np.asarray(pose, np.float32), ZERO2)
+
+
+def ref_update(refs, poses, scans):
+    for o in refs.values():
+        o.build_map(np.asarray(poses, np.float32).reshape(-1, 3), scans)
+
+
+def box_mask(shape, box):
+    m = np.zeros(shape, bool)
+    if box[2] >= box[0]:
+        m[box[1]:box[3] + 1, box[0]:box[2] + 1] = True
+    return m
+
+
+def new_grids():
+    """a consumer's persistent grids, one per level; the content before the first export is arbitrary"""
+    return [np.full(oc.dims(l)[::-1], 7, np.int8) for l in range(LEVELS)]
+
+
+def export(g, lvl, grid, form):
+    """one export of level `lvl` into `grid` (int8 [sy, sx], updated in place) through the untouched-cell check -> the box"""
+    import torch
+    saved = grid.copy()
+    work = np.full_like(grid, oc.POISON)
+    if form == "host":
+        box = g.occupancy_changes(lvl, work)
+    else:
+        d, d_box = dev(work), torch.full((4,), -9, dtype=torch.int32, device="cuda:0")
+        g.occupancy_changes_device(lvl, d.data_ptr(), d_box.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        work, box = d.cpu().numpy(), d_box.cpu().numpy()  # (the caller's stream waits behind the export)
+    box = [int(v) for v in box]
+    sx, sy = oc.dims(lvl)
+    assert box == EMPTY or (0 <= box[0] <= box[2] < sx and 0 <= box[1] <= box[3] < sy), (lvl, form, box)
+    m = box_mask(grid.shape, box)
+    assert np.isin(work[m], (-1, 0, 100)).all(), (lvl, form, box, np.unique(work[m]))
+    assert (work[~m] == oc.POISON).all(), (lvl, form, box, "a cell outside the box was written", oc.hull_of((work != oc.POISON) & ~m))
+    grid[...] = np.where(m, work, saved)
+    return box
+
+
+def assert_grid(g, refs, lvl, grid, what):
+    for kind, o in refs.items():
+        want = o.occupancy_grid(lvl)
+        assert np.array_equal(grid, want), (what, kind, lvl, int((grid != want).sum()), oc.hull_of(grid != want))
+    assert np.array_equal(grid, g.occupancy_grid(lvl)), (what, "hsm_occupancy_grid", lvl)
+
+
+FORMS = ["host", "device"]
+
+
+# ---- 1: the first export is the whole level, an immediate second one is empty ---------------------------------------------------
+@pytest.mark.parametrize("form", FORMS)
+def test_first_export_is_the_whole_level_and_the_second_is_empty(capi, oracle_mod, form):
+    g, refs = new_ctx(capi), new_refs(oracle_mod)
+    pose, scan = oc.edge_scans()["odd x"]
+    host_update(capi, g, pose, scan)
+    ref_update(refs, [pose], [scan])
+    grids = new_grids()
+    for lvl in range(LEVELS):
+        sx, sy = oc.dims(lvl)
+        assert export(g, lvl, grids[lvl], form) == [0, 0, sx - 1, sy - 1]
+        assert_grid(g, refs, lvl, grids[lvl], "first export")
+        before = grids[lvl].copy()
+        assert export(g, lvl, grids[lvl], form) == EMPTY  # (the check inside: nothing was written)
+        assert np.array_equal(grids[lvl], before)
+    g.close()
+
+
+# ---- 2: host updates one at a time, scans that end on the map's edges --------------------------------------------------------
+@pytest.mark.parametrize("form", FORMS)
+def test_host_updates_on_the_edges_one_at_a_time(capi, oracle_mod, form):
+    g, refs = new_ctx(capi), new_refs(oracle_mod)
+    grids = new_grids()
+    for lvl in range(LEVELS):
+        export(g, lvl, grids[lvl], form)
+    cases = oc.edge_scans()
+    order = ["column 0", "odd x", "last column", "row 0", "last row", ("odd x", "column 0")]  # the last: two updates, one export
+    for step in order:
+        names = step if isinstance(step, tuple) else (step,)
+        since = [[] for _ in range(LEVELS)]
+        for name in names:
+            pose, scan = cases[name]
+            host_update(capi, g, pose, scan)
+            ref_update(refs, [pose], [scan])
+            for lvl in range(LEVELS):
+                since[lvl].append(g.last_update_bbox(lvl))
+        for lvl in range(LEVELS):
+            previous = grids[lvl].copy()
+            box = export(g, lvl, grids[lvl], form)
+            assert_grid(g, refs, lvl, grids[lvl], step)
+            assert oc.inside(box, oc.hull_of(grids[lvl] != previous)), (step, lvl, box, "a changed cell outside the box")
+            assert oc.inside(oc.union(since[lvl]), box), (step, lvl, box, oc.union(since[lvl]))
+    sx, sy = oc.dims(0)
+    touched = oc.hull_of(grids[0] != -1)
+    assert touched[0] == 0 and touched[1] == 0 and touched[2] == sx - 1 and touched[3] == sy - 1, touched  # the edges were reached
+    g.close()
+
+
+# ---- 3: a cell one scan marks free and the next occupied ---------------------------------------------------------------------------
+@pytest.mark.parametrize("form", FORMS)
+@pytest.mark.parametrize("factors", [(0.4, 0.6), (0.25, 0.75)], ids=["0.4_0.6", "0.25_0.75"])
+def test_cell_marked_free_then_occupied(capi, oracle_mod, factors, form):
+    g, refs = new_ctx(capi, *factors), new_refs(oracle_mod, *factors)
+    pose, first, second = oc.zero_cell_scans()
+    grids = new_grids()
+    for scan in (first, second):
+        host_update(capi, g, pose, scan)
+        ref_update(refs, [pose], [scan])
+        export(g, 0, grids[0], form)
+        assert_grid(g, refs, 0, grids[0], factors)
+    row = grids[0][30]
+    for o in refs.values():
+        lo = o.download_level(0)[0]
+        if factors == (0.25, 0.75):
+            assert lo[30, 50] == 0.0 and lo[30, 49] < 0 and lo[30, 51] < 0 and lo[30, 60] > 0  # free + occupied cancel exactly
+        else:
+            assert lo[30, 50] == np.float32(2.9802322e-08)  # the module docstring: they do not cancel in fp32
+    assert row[49] == 0 and row[51] == 0 and row[60] == 100 and row[61] == -1
+    assert row[50] == (-1 if factors == (0.25, 0.75) else 100)
+    g.close()
+
+
+# ---- 4: upload and reset ---------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("form", FORMS)
+def test_upload_of_special_values_and_reset(capi, oracle_mod, form):
+    g, refs = new_ctx(capi), new_refs(oracle_mod)
+    grids = new_grids()
+    for lvl in range(LEVELS):
+        export(g, lvl, grids[lvl], form)
+    planes, where = oc.special_planes()
+    for lvl in (1, 2, 0):
+        g.upload_level(lvl, *planes[lvl])
+        for o in refs.values():
+            o.upload_level(lvl, *planes[lvl])
+    for lvl in range(LEVELS):
+        sx, sy = oc.dims(lvl)
+        assert export(g, lvl, grids[lvl], form) == [0, 0, sx - 1, sy - 1]
+        assert [int(grids[lvl][y, x]) for y, x in where[lvl]] == [-1, -1, 100, 0]  # NaN, -0.0, +inf, -inf
+        assert np.array_equal(grids[lvl], np.where(planes[lvl][0] < 0, 0, np.where(planes[lvl][0] > 0, 100, -1)))
+        assert_grid(g, refs, lvl, grids[lvl], "upload")
+        assert export(g, lvl, grids[lvl], form) == EMPTY
+    g.reset()
+    for lvl in range(LEVELS):
+        sx, sy = oc.dims(lvl)
+        assert export(g, lvl, grids[lvl], form) == [0, 0, sx - 1, sy - 1]
+        assert (grids[lvl] == -1).all()
+    g.close()
+
+
+# ---- 5: the device path, no host query in between ------------------------------------------------------------------------------------
+def device_update(g, poses, scans, gated=False, stream=0):
+    """hsm_update_by_scans_device(_gated) on torch buffers -> the buffers (they must outlive the update)"""
+    pts, offs = pack(scans)
+    keep = [dev(np.asarray(poses, np.float32).reshape(-1, 3)), dev(pts), dev(offs)]
+    if gated:
+        g.update_by_scans_device_gated(len(scans), keep[0].data_ptr(), keep[1].data_ptr(), keep[2].data_ptr(), 0, 181, None, 0, 0, stream)
+    else:
+        g.update_by_scans_device(len(scans), keep[0].data_ptr(), keep[1].data_ptr(), keep[2].data_ptr(), 0, 181, None, stream)
+    return keep
+
+
+@pytest.mark.parametrize("form", FORMS)
+def test_device_updates_of_three_scans_then_export(capi, oracle_mod, form):
+    g, refs = new_ctx(capi), new_refs(oracle_mod)
+    grids = new_grids()
+    for lvl in range(LEVELS):
+        export(g, lvl, grids[lvl], form)
+    cases = oc.edge_scans()
+    poses, scans = zip(*[cases[n] for n in ("odd x", "row 0", "last column")])
+    keep = device_update(g, poses, scans)
+    ref_update(refs, poses, scans)
+    boxes = []
+    for lvl in range(LEVELS):
+        previous = grids[lvl].copy()
+        boxes.append(export(g, lvl, grids[lvl], form))
+        assert_grid(g, refs, lvl, grids[lvl], "three scans")
+        assert oc.inside(boxes[lvl], oc.hull_of(grids[lvl] != previous)), (lvl, boxes[lvl])
+    sx, sy = oc.dims(0)
+    assert boxes[0] != [0, 0, sx - 1, sy - 1]  # a box, not the whole level
+    # the mirror's boxes were not consumed by the exports, nor the other way round
+    for lvl in range(LEVELS):
+        assert [int(v) for v in g.take_dirty_bbox(lvl)] == boxes[lvl], (lvl, boxes[lvl])
+        assert export(g, lvl, grids[lvl], form) == EMPTY
+    del keep
+    g.close()
+
+
+def test_gated_call_with_a_rejected_scan_widens_nothing(capi, oracle_mod):
+    g, twin, refs = new_ctx(capi), new_ctx(capi), new_refs(oracle_mod)
+    cases = oc.edge_scans()
+    p0, s0 = cases["odd x"]
+    p1 = (p0 + np.float32([oc.RES, 0.0, 0.0])).astype(np.float32)  # one cell further: below the gate's 0.4 m / 0.13 rad
+    s1 = cases["column 0"][1]  # ... with a scan that would reach column 0 and rows 3 .. 72
+    far = (48.0, 36.0)  # 0.875 m and 0.625 m from the first pose: through the gate
+    p2, s2 = oc.world_pose(*far), oc.aimed_scan(far, np.stack([np.linspace(3.0, 96.0, 24), np.zeros(24)], 1))
+    poses, scans = [p0, p1, p2], [s0, s1, s2]
+    grids = new_grids()
+    for lvl in range(LEVELS):
+        export(g, lvl, grids[lvl], "device")
+    keep = device_update(g, poses, scans, gated=True)
+    ref_update(refs, [p0, p2], [s0, s2])
+    per_call = [[] for _ in range(LEVELS)]
+    keeps = []
+    for k in range(3):  # the twin: one call per scan, with a box query after each
+        keeps.append(device_update(twin, poses[k:k + 1], scans[k:k + 1], gated=True))
+        for lvl in range(LEVELS):
+            per_call[lvl].append([int(v) for v in twin.last_update_bbox(lvl)])
+    for lvl in range(LEVELS):
+        assert per_call[lvl][1] == EMPTY, "the twin's gate let the middle scan through"
+        assert per_call[lvl][0] != EMPTY and (lvl > 0 or per_call[lvl][2] != EMPTY), "the gate rejected a scan it was to let through"
+        box = export(g, lvl, grids[lvl], "device")
+        assert box == oc.union(per_call[lvl]), (lvl, box, per_call[lvl])
+        assert_grid(g, refs, lvl, grids[lvl], "gated")
+    assert grids[0][:, 0].tolist() == [-1] * oc.dims(0)[1] and oc.union(per_call[0])[0] > 0  # column 0 was never reached
+    del keep, keeps
+    g.close()
+    twin.close()
+
+
+def test_two_scan_logs_and_two_snapshots_queued_before_one_wait(capi, oracle_mod):
+    import torch
+    n, n1 = 8, 4
+    thresholds = (0.01, 0.01)
+    poses, scans = oc.room_scans(n)
+    deltas = np.zeros((n, 3), np.float32)
+    deltas[1:] = poses[1:] - poses[:-1]
+    g, refs = new_ctx(capi), new_refs(oracle_mod)
+    g.set_update_gate(*thresholds)
+    s = torch.cuda.Stream()
+    pts, offs = pack(scans)
+    lvls = range(LEVELS)
+    with torch.cuda.stream(s):
+        d = {"start": dev(poses[0]), "deltas": dev(deltas), "pts": dev(pts), "offs": dev(offs),
+             "pose": torch.full((n, 3), -777.0, device="cuda:0"), "applied": torch.full((n,), -7, dtype=torch.int32, device="cuda:0"),
+             "grid": [torch.full(oc.dims(l)[::-1], oc.POISON, dtype=torch.int8, device="cuda:0") for l in lvls],
+             "box": torch.full((2, LEVELS, 4), -9, dtype=torch.int32, device="cuda:0")}
+        snaps = []
+        for part, (k0, cnt) in enumerate([(0, n1), (n1, n - n1)]):
+            g.slam_scans_device(cnt, d["start"].data_ptr() if k0 == 0 else d["pose"][k0 - 1].data_ptr(), d["deltas"][k0:].data_ptr(),
+                                d["pts"].data_ptr(), d["offs"][k0:].data_ptr(), 181, None, 0, d["pose"][k0:].data_ptr(), 0,
+                                d["applied"][k0:].data_ptr(), s.cuda_stream)
+            for l in lvls:
+                g.occupancy_changes_device(l, d["grid"][l].data_ptr(), d["box"][part, l].data_ptr(), s.cuda_stream)
+            snaps.append([d["grid"][l].clone() for l in lvls])
+    s.synchronize()  # the one wait
+    applied = d["applied"].cpu().numpy()
+    boxes = d["box"].cpu().numpy()
+    for kind, o in refs.items():
+        o.proc_set_thresholds(*thresholds)
+        pose = poses[0].copy()
+        for k in range(n):
+            o.proc_update(scans[k], (pose + deltas[k]).astype(np.float32), ZERO2, False)
+            pose, _ = o.proc_last_pose()
+            assert np.array_equal(pose.view(np.uint32), d["pose"][k].cpu().numpy().view(np.uint32)), (kind, k)
+            if k + 1 in (n1, n):
+                part = 0 if k + 1 == n1 else 1
+                for l in lvls:
+                    got, want = snaps[part][l].cpu().numpy(), o.occupancy_grid(l)
+                    assert np.array_equal(got, want), (kind, "snapshot", part, l, int((got != want).sum()))
+        if kind == "ho":
+            assert o.undefined_reads() == 0
+    assert applied[:n1].sum() >= 2 and applied[n1:].sum() >= 2, applied
+    for l in lvls:
+        sx, sy = oc.dims(l)
+        assert boxes[0, l].tolist() == [0, 0, sx - 1, sy - 1]  # the first export of a level
+        changed = oc.hull_of(snaps[1][l].cpu().numpy() != snaps[0][l].cpu().numpy())
+        assert oc.inside(boxes[1, l].tolist(), changed), (l, boxes[1, l], changed)
+    assert boxes[1, 0].tolist() != [0, 0, oc.dims(0)[0] - 1, oc.dims(0)[1] - 1]
+    g.close()
+
+
+# ---- 6: the mirror's dirty box and the publish box are independent ------------------------------------------------------------------
+@pytest.mark.parametrize("form", FORMS)
+def test_take_dirty_bbox_and_the_export_do_not_consume_each_other(capi, oracle_mod, form):
+    g, twin, refs = new_ctx(capi), new_ctx(capi), new_refs(oracle_mod)
+    grids, twin_grids = new_grids(), new_grids()
+    for lvl in range(LEVELS):
+        export(g, lvl, grids[lvl], form)
+        export(twin, lvl, twin_grids[lvl], form)
+        g.take_dirty_bbox(lvl)
+        twin.take_dirty_bbox(lvl)
+    cases = oc.edge_scans()
+    (pa, sa), (pb, sb) = cases["odd x"], cases["last row"]
+    host_update(capi, g, pa, sa)
+    host_update(capi, twin, pa, sa)
+    keep = [device_update(c, [pb], [sb]) for c in (g, twin)]
+    ref_update(refs, [pa, pb], [sa, sb])
+    for lvl in range(LEVELS):
+        taken = [int(v) for v in g.take_dirty_bbox(lvl)]  # g: in front of the export; twin: behind it
+        box, twin_box = export(g, lvl, grids[lvl], form), export(twin, lvl, twin_grids[lvl], form)
+        assert box == twin_box and np.array_equal(grids[lvl], twin_grids[lvl]), (lvl, box, twin_box)
+        assert_grid(g, refs, lvl, grids[lvl], "dirty box taken first")
+        assert [int(v) for v in twin.take_dirty_bbox(lvl)] == taken, (lvl, taken, "the export emptied the mirror's box")
+        assert taken == box
+    del keep
+    g.close()
+    twin.close()
+
+
+# ---- 7: the whole level into device memory -------------------------------------------------------------------------------------------
+def test_grid_device_equals_the_host_export_and_leaves_the_box(capi, oracle_mod):
+    import torch
+    g, refs = new_ctx(capi), new_refs(oracle_mod)
+    grids = new_grids()
+    for lvl in range(LEVELS):
+        export(g, lvl, grids[lvl], "device")
+    pose, scan = oc.edge_scans()["odd x"]
+    host_update(capi, g, pose, scan)
+    ref_update(refs, [pose], [scan])
+    for lvl in range(LEVELS):
+        sx, sy = oc.dims(lvl)
+        for shift in (0, 1):  # a grid that starts on a 4-byte boundary, and one that does not
+            buf = torch.full((sx * sy + 8,), oc.POISON, dtype=torch.int8, device="cuda:0")
+            g.occupancy_grid_device(lvl, buf.data_ptr() + shift, torch.cuda.current_stream().cuda_stream)
+            got = buf.cpu().numpy()
+            assert (got[:shift] == oc.POISON).all() and (got[shift + sx * sy:] == oc.POISON).all(), (lvl, shift)
+            assert np.array_equal(got[shift:shift + sx * sy].reshape(sy, sx), g.occupancy_grid(lvl)), (lvl, shift)
+        for kind, o in refs.items():
+            assert np.array_equal(got[1:1 + sx * sy].reshape(sy, sx), o.occupancy_grid(lvl)), (kind, lvl)
+        box = export(g, lvl, grids[lvl], "device")
+        assert box == [int(v) for v in g.last_update_bbox(lvl)], (lvl, box)  # as the update left it
+    # the changed-cells export into a grid that starts off a 4-byte boundary
+    host_update(capi, g, *oc.edge_scans()["column 0"])
+    sx, sy = oc.dims(0)
+    buf = torch.full((sx * sy + 8,), oc.POISON, dtype=torch.int8, device="cuda:0")
+    d_box = torch.full((4,), -9, dtype=torch.int32, device="cuda:0")
+    g.occupancy_changes_device(0, buf.data_ptr() + 3, d_box.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    got, m = buf.cpu().numpy(), box_mask((sy, sx), d_box.cpu().numpy())
+    assert (got[:3] == oc.POISON).all() and (got[3 + sx * sy:] == oc.POISON).all()
+    assert np.array_equal(got[3:3 + sx * sy].reshape(sy, sx), np.where(m, g.occupancy_grid(0), oc.POISON))
+    # hsm_occupancy_restart: the next export is the whole level again
+    g.occupancy_restart(1)
+    assert export(g, 0, grids[0], "device") == EMPTY
+    assert export(g, 1, grids[1], "device") == [0, 0, oc.dims(1)[0] - 1, oc.dims(1)[1] - 1]
+    g.occupancy_restart()
+    for lvl in range(LEVELS):
+        assert export(g, lvl, grids[lvl], "host") == [0, 0, oc.dims(lvl)[0] - 1, oc.dims(lvl)[1] - 1]
+    g.close()
+
+
+# ---- 8: refusals ---------------------------------------------------------------------------------------------------------------------
+def test_refusals_queue_nothing_and_leave_the_box(capi, oracle_mod):
+    import torch
+    g, refs = new_ctx(capi), new_refs(oracle_mod)
+    grids = new_grids()
+    for lvl in range(LEVELS):
+        export(g, lvl, grids[lvl], "device")
+    pose, scan = oc.edge_scans()["odd x"]
+    host_update(capi, g, pose, scan)
+    ref_update(refs, [pose], [scan])
+    want_box = [int(v) for v in g.last_update_bbox(0)]
+    sx, sy = oc.dims(0)
+    d_grid = torch.full((sy, sx), oc.POISON, dtype=torch.int8, device="cuda:0")
+    d_box = torch.full((4,), -9, dtype=torch.int32, device="cuda:0")
+    host_grid, host_box = np.full((sy, sx), oc.POISON, np.int8), np.full(4, -9, np.int32)
+    lib, h = g._lib, g._h
+    calls = {
+        "grid_device: null context": lambda: lib.hsm_occupancy_grid_device(None, 0, d_grid.data_ptr(), None),
+        "grid_device: null grid": lambda: lib.hsm_occupancy_grid_device(h, 0, None, None),
+        "grid_device: level -1": lambda: lib.hsm_occupancy_grid_device(h, -1, d_grid.data_ptr(), None),
+        "grid_device: level 3": lambda: lib.hsm_occupancy_grid_device(h, LEVELS, d_grid.data_ptr(), None),
+        "changes_device: null context": lambda: lib.hsm_occupancy_changes_device(None, 0, d_grid.data_ptr(), d_box.data_ptr(), None),
+        "changes_device: null grid": lambda: lib.hsm_occupancy_changes_device(h, 0, None, d_box.data_ptr(), None),
+        "changes_device: level -1": lambda: lib.hsm_occupancy_changes_device(h, -1, d_grid.data_ptr(), d_box.data_ptr(), None),
+        "changes_device: level 3": lambda: lib.hsm_occupancy_changes_device(h, LEVELS, d_grid.data_ptr(), d_box.data_ptr(), None),
+        "changes: null context": lambda: lib.hsm_occupancy_changes(None, 0, host_grid.ctypes.data, host_box),
+        "changes: null grid": lambda: lib.hsm_occupancy_changes(h, 0, None, host_box),
+        "changes: level 3": lambda: lib.hsm_occupancy_changes(h, LEVELS, host_grid.ctypes.data, host_box),
+        "restart: null context": lambda: lib.hsm_occupancy_restart(None, 0),
+        "restart: level 3": lambda: lib.hsm_occupancy_restart(h, LEVELS),
+        "restart: level -2": lambda: lib.hsm_occupancy_restart(h, -2),
+    }
+    for what, call in calls.items():
+        assert call() == HSM_ERR_INVALID, what
+    # `stream` is being captured, and: a stream this context has matched on is being captured
+    s, other = torch.cuda.Stream(), torch.cuda.Stream()
+    with torch.cuda.stream(s):
+        b = dev(np.asarray([pose], np.float32))
+        p = dev(np.ascontiguousarray(scan, np.float32))
+        out = torch.zeros((1, 3), device="cuda:0")
+        g.match_batch_device(1, b.data_ptr(), p.data_ptr(), 0, len(scan), out.data_ptr(), 0, s.cuda_stream)  # s: a stream g has matched on
+        x = torch.zeros(8, device="cuda:0")
+    s.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, stream=s):
+        x.add_(1.0)
+        for st in (s, other):
+            for call in (lambda: g.occupancy_grid_device(0, d_grid.data_ptr(), st.cuda_stream),
+                         lambda: g.occupancy_changes_device(0, d_grid.data_ptr(), d_box.data_ptr(), st.cuda_stream)):
+                with pytest.raises(capi.HsmError) as e:
+                    call()
+                assert f"({HSM_ERR_INVALID})" in str(e.value) and "captur" in str(e.value), str(e.value)
+        x.add_(1.0)
+    torch.cuda.synchronize()
+    graph.replay()
+    torch.cuda.synchronize()
+    assert x.cpu().numpy().tolist() == [2.0] * 8  # the capture ended normally
+    # nothing was queued: no byte of either grid, no box
+    assert (d_grid.cpu().numpy() == oc.POISON).all() and d_box.cpu().numpy().tolist() == [-9] * 4
+    assert (host_grid == oc.POISON).all() and host_box.tolist() == [-9] * 4
+    # ... and the box is still there for the next call
+    assert export(g, 0, grids[0], "device") == want_box
+    assert_grid(g, refs, 0, grids[0], "after the refusals")
+    g.close()

@@ -1,0 +1,27 @@
+"""The row split of occupancy_box_kernel (hector_slam_amd/csrc/occupancy_rows.h: a ragged head, a body of 4-cell groups aligned
+on the GRID, a ragged tail) on the CPU: tests/cpp/occupancy_rows_check.cpp compiles the header with the host compiler alone and
+holds it to a byte-by-byte restatement for every box row 0 <= x0 <= x1 < 40 (clipped to the width) on 8 rows of grids 25, 38 and
+40 cells wide -- an odd width, an even one that is no multiple of 4, and a multiple of 4, so every phase of a row's first cell
+against the 4-cell alignment occurs.  Equality of byte grids: no tolerance."""
+import os
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def model(tmp_path_factory):
+    exe = tmp_path_factory.mktemp("occ_rows") / "occupancy_rows_check"
+    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "hector_slam_amd", "csrc"),
+                    os.path.join(ROOT, "tests", "cpp", "occupancy_rows_check.cpp"), "-o", str(exe)], check=True)
+    return exe
+
+
+@pytest.mark.parametrize("width", [25, 38, 40])
+def test_row_split_equals_the_byte_by_byte_restatement(model, width):
+    r = subprocess.run([str(model), str(width)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    m = min(width, 40)
+    assert r.stdout.split() == ["ok", str(8 * m * (m + 1) // 2)], r.stdout  # every (row, x0, x1) was checked
