@@ -1,6 +1,7 @@
 // hector_mi355.hip -- host runtime + C ABI (include/hector_mi355/capi.h) of the
 // MI355X-native hector_mapping scan matcher.  Kernels: gn_match.h, map_update.h; the batch / team matcher forms are
-// launched from match_exact_cached.hip and match_teams.hip (hsm_ctx.h says which unit holds what).
+// launched from match_exact_cached.hip and match_teams.hip, the probes and test hooks are in probes.hip, the multi-GPU group in
+// group.hip (hsm_ctx.h says which unit holds what).
 //
 // The context mirrors hectorslam::MapRepMultiMap (HSL/slam_main/MapRepMultiMap.h): a
 // pyramid of levels, each with its grid (log-odds + update stamps), its world<->map
@@ -9,30 +10,8 @@
 // host keeps only scalars.  There is no CPU compute path.
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off (see build.py).
-#include <dlfcn.h>
 #include <hip/hip_runtime.h>
 #include <math.h>
-// RCCL: declarations only -- librccl is dlopen'ed by the group entry points (rccl_api), never linked.  A ROCm install without
-// the RCCL development headers still builds the library: the handful of prototypes the group gather uses are then declared
-// here (the stable NCCL 2.x C API; values as in nccl.h).
-#if __has_include(<rccl/rccl.h>) && !defined(HSM_NO_RCCL_HEADER)
-#include <rccl/rccl.h>
-#else
-extern "C" {
-typedef struct ncclComm* ncclComm_t;
-typedef enum { ncclSuccess = 0 } ncclResult_t;
-typedef enum { ncclFloat = 7 } ncclDataType_t;
-ncclResult_t ncclCommInitAll(ncclComm_t* comm, int ndev, const int* devlist);
-ncclResult_t ncclCommDestroy(ncclComm_t comm);
-ncclResult_t ncclGroupStart(void);
-ncclResult_t ncclGroupEnd(void);
-ncclResult_t ncclAllGather(const void* sendbuff, void* recvbuff, size_t sendcount, ncclDataType_t datatype, ncclComm_t comm, hipStream_t stream);
-ncclResult_t ncclSend(const void* sendbuff, size_t count, ncclDataType_t datatype, int peer, ncclComm_t comm, hipStream_t stream);
-ncclResult_t ncclRecv(void* recvbuff, size_t count, ncclDataType_t datatype, int peer, ncclComm_t comm, hipStream_t stream);
-const char* ncclGetErrorString(ncclResult_t result);
-ncclResult_t ncclGetVersion(int* version);
-}
-#endif
 #include <limits.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -41,12 +20,8 @@ ncclResult_t ncclGetVersion(int* version);
 
 #include <atomic>
 #include <chrono>
-#include <condition_variable>
-#include <functional>
-#include <memory>
 #include <mutex>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "gn_match.h"
@@ -55,17 +30,6 @@ ncclResult_t ncclGetVersion(int* version);
 #include "hsm_ctx.h"
 #include "hsm_host.h"
 #include "map_update.h"
-
-namespace hsm {
-// device sin/cos sweep for the parity tests
-__global__ void sincos_debug_kernel(const float* __restrict__ x, int n, float* __restrict__ s,
-                                    float* __restrict__ c) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  sincos_f32(x[i], s[i], c[i]);
-}
-
-}  // namespace hsm
 
 namespace {
 
@@ -87,6 +51,8 @@ int hsm_host::fail(int code, const char* what, hipError_t e) {
   return code;
 }
 
+void hsm_host::set_error_text(const char* text) { g_last_error = text; }
+
 namespace {
 
 #define HIP_TRY(expr)                                         \
@@ -101,11 +67,6 @@ int fail_at(int code, const char* who, const char* text, hipError_t e = hipSucce
   snprintf(buf, sizeof buf, "%s%s", who, text);
   return fail(code, buf, e);
 }
-
-}  // namespace
-
-
-namespace {
 
 float prob_to_log_odds(float prob) {  // GridMapLogOdds.h:196-200 (float log overload)
   float odds = prob / (1.0f - prob);
@@ -138,10 +99,10 @@ void set_map_transformation(Level& L, float offx, float offy, float cell_length)
   L.worldTmap = w;
 }
 
-inline void affine_apply_host(const Affine2& a, float x, float y, float& ox, float& oy) {
-  ox = a.t0 + (a.l00 * x + a.l01 * y);
-  oy = a.t1 + (a.l10 * x + a.l11 * y);
-}
+}  // namespace
+
+// (declared in hsm_ctx.h: probes.hip uses these too)
+namespace hsm_host {
 
 LevelRW level_rw(const Level& L) {
   LevelRW v;
@@ -178,18 +139,11 @@ LevelView level_view(const Level& L, float pt_scale, int gn_steps) {
   return v;
 }
 
-int grid_for(size_t n, int block = 256) {
+int grid_for(size_t n, int block) {
   size_t g = (n + block - 1) / block;
   if (g > 256 * 8) g = 256 * 8;  // grid-stride the rest (guide, Guideline 11)
   if (g < 1) g = 1;
   return (int)g;
-}
-
-int fill_level(hsm_ctx* h, Level& L) {  // GridMapBase::clear + LogOddsCell::resetGridCell
-  hipLaunchKernelGGL(fill_level_kernel, dim3(grid_for(L.cells())), dim3(256), 0, h->stream, level_rw(L),
-                     0.0f, -1);
-  HIP_TRY(hipGetLastError());
-  return HSM_OK;
 }
 
 int rebuild_probability(hsm_ctx* h, Level& L) {
@@ -198,18 +152,6 @@ int rebuild_probability(hsm_ctx* h, Level& L) {
     hipLaunchKernelGGL(rebuild_quad_kernel, dim3(grid_for(L.cells())), dim3(256), 0, h->stream, level_rw(L));
   HIP_TRY(hipGetLastError());
   return HSM_OK;
-}
-
-void free_level(Level& L, TeardownLog* log = nullptr) {
-  TEARDOWN(log, hipFree(L.d_logodds));
-  TEARDOWN(log, hipFree(L.d_update_index));
-  TEARDOWN(log, hipFree(L.d_prob));
-  TEARDOWN(log, hipFree(L.d_quad));
-  TEARDOWN(log, hipFree(L.d_key_free));
-  TEARDOWN(log, hipFree(L.d_key_occ));
-  TEARDOWN(log, hipFree(L.d_occ_bits));
-  TEARDOWN(log, hipFree(L.d_free_bytes));
-  L = Level();
 }
 
 // HSM_PARITY_AUTO (the default): EVERY match -- batched, single scan, dense scan, and the likelihood / covariance / Hessian
@@ -226,6 +168,49 @@ void free_level(Level& L, TeardownLog* log = nullptr) {
 // The effective order is an INPUT of the plan (MatchSite::exact) -- the context's flags are never changed by a launch
 // (hsm_parity() reads them without the mutex) -- and is recorded for hsm_last_launch_parity().
 bool wants_exact(const hsm_ctx* h) { return h->exact || h->auto_parity; }
+
+// every cell of the level may have changed (create, reset, upload): host mirrors and the published grid take all of it
+void whole_level_changed(Level& L, bool mirror) {
+  const int all[4] = {0, 0, L.sx - 1, L.sy - 1};
+  for (int k = 0; k < 4; ++k) {
+    if (mirror) L.dirty[k] = all[k];
+    L.pub[k] = all[k];
+  }
+}
+
+int valid_level(const hsm_ctx* h, int level) {
+  if (!h) return fail(HSM_ERR_INVALID, "null context");
+  if (level < 0 || level >= (int)h->levels.size()) return fail(HSM_ERR_INVALID, "level out of range");
+  return HSM_OK;
+}
+
+int select_device(const hsm_ctx* h) {
+  HIP_TRY(hipSetDevice(h->device));
+  return HSM_OK;
+}
+
+}  // namespace hsm_host
+
+namespace {
+
+int fill_level(hsm_ctx* h, Level& L) {  // GridMapBase::clear + LogOddsCell::resetGridCell
+  hipLaunchKernelGGL(fill_level_kernel, dim3(grid_for(L.cells())), dim3(256), 0, h->stream, level_rw(L),
+                     0.0f, -1);
+  HIP_TRY(hipGetLastError());
+  return HSM_OK;
+}
+
+void free_level(Level& L, TeardownLog* log = nullptr) {
+  TEARDOWN(log, hipFree(L.d_logodds));
+  TEARDOWN(log, hipFree(L.d_update_index));
+  TEARDOWN(log, hipFree(L.d_prob));
+  TEARDOWN(log, hipFree(L.d_quad));
+  TEARDOWN(log, hipFree(L.d_key_free));
+  TEARDOWN(log, hipFree(L.d_key_occ));
+  TEARDOWN(log, hipFree(L.d_occ_bits));
+  TEARDOWN(log, hipFree(L.d_free_bytes));
+  L = Level();
+}
 
 static_assert(hsm_plan::kQuad == kLayoutQuad && hsm_plan::kPlane == kLayoutPlane && hsm_plan::kExactGroupRounds == kExactGroupRounds &&
                   hsm_plan::kDenseRound == kDenseRound && hsm_plan::kSpec1MaxBeams == kSpec1MaxBeams,
@@ -382,21 +367,6 @@ void box_widen(int acc[4], const int b[4]) {
   if (b[1] < acc[1]) acc[1] = b[1];
   if (b[2] > acc[2]) acc[2] = b[2];
   if (b[3] > acc[3]) acc[3] = b[3];
-}
-
-// every cell of the level may have changed (create, reset, upload): host mirrors and the published grid take all of it
-void whole_level_changed(Level& L, bool mirror = true) {
-  const int all[4] = {0, 0, L.sx - 1, L.sy - 1};
-  for (int k = 0; k < 4; ++k) {
-    if (mirror) L.dirty[k] = all[k];
-    L.pub[k] = all[k];
-  }
-}
-
-int valid_level(const hsm_ctx* h, int level) {
-  if (!h) return fail(HSM_ERR_INVALID, "null context");
-  if (level < 0 || level >= (int)h->levels.size()) return fail(HSM_ERR_INVALID, "level out of range");
-  return HSM_OK;
 }
 
 // OccGridMapBase::updateByScan on one level (OccGridMapBase.h:121-168), host side, in two steps so that the GPU can
@@ -656,10 +626,9 @@ void update_applied(hsm_ctx* h, const UpdateBatch& batch, const LevelPrep& prep)
   h->levels[prep.level].marks_pending = false;
 }
 
-int select_device(const hsm_ctx* h) {
-  HIP_TRY(hipSetDevice(h->device));
-  return HSM_OK;
-}
+}  // namespace
+
+namespace hsm_host {
 
 // every writer of the map queues behind a batch match that a caller-owned stream may still be running, and
 // bumps the epoch the next such match orders itself behind
@@ -715,6 +684,37 @@ int merge_device_boxes(hsm_ctx* h) {
   return HSM_OK;
 }
 
+// Gated updates (hsm_update_by_scans_device_gated, hsm_slam_scans_device) count the scans they integrate on the device: the
+// host never sees their decisions.  Whoever needs the levels' update counters on the host -- prepare_level, the ungated
+// hsm_update_by_scans_device, hsm_update_index, reset and upload -- first waits for the context's stream, fetches the count and
+// folds it in: OccGridMapBase.h:123-124, :167 and setUpdated() (GridMapBase.h:343) that many times.  Callers test
+// gate_outstanding themselves, so a context that never made a gated call pays one branch.  *state: the block as fetched.
+int fold_gate_counters(hsm_ctx* h, GateState* state) {
+  if (int rc = select_device(h)) return rc;
+  GateState host;
+  HIP_TRY(hipMemcpyAsync(&host, h->d_gate, sizeof host, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (state) *state = host;
+  const int applied = host.pending;
+  if (applied > 0) {
+    HIP_TRY(hipMemsetAsync(&h->d_gate->pending, 0, sizeof(int), h->stream));  // ahead of every later gated call
+    for (Level& L : h->levels) {
+      L.curr_mark_free = L.curr_update_index + 3 * (applied - 1) + 1;
+      L.curr_mark_occ = L.curr_update_index + 3 * (applied - 1) + 2;
+      L.curr_update_index += 3 * applied;
+      L.last_update_index += applied;
+    }
+    h->gate_applied_total += applied;
+    if (state) state->pending = 0;
+  }
+  h->gate_outstanding = false;
+  return HSM_OK;
+}
+
+}  // namespace hsm_host
+
+namespace {
+
 // the UpdateBatch blocks and cell boxes of `count` scans (hsm_ctx::d_upd_batches / d_upd_boxes)
 int ensure_update_scans(hsm_ctx* h, size_t count) {
   if (h->d_upd_boxes && h->d_upd_batches.holds(count)) return HSM_OK;
@@ -738,33 +738,6 @@ int clear_key_planes(hsm_ctx* h, Level& L) {
   return HSM_OK;
 }
 
-// Gated updates (hsm_update_by_scans_device_gated, hsm_slam_scans_device) count the scans they integrate on the device: the
-// host never sees their decisions.  Whoever needs the levels' update counters on the host -- prepare_level, the ungated
-// hsm_update_by_scans_device, hsm_update_index, reset and upload -- first waits for the context's stream, fetches the count and
-// folds it in: OccGridMapBase.h:123-124, :167 and setUpdated() (GridMapBase.h:343) that many times.  Callers test
-// gate_outstanding themselves, so a context that never made a gated call pays one branch.  *state: the block as fetched.
-int fold_gate_counters(hsm_ctx* h, GateState* state = nullptr) {
-  if (int rc = select_device(h)) return rc;
-  GateState host;
-  HIP_TRY(hipMemcpyAsync(&host, h->d_gate, sizeof host, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  if (state) *state = host;
-  const int applied = host.pending;
-  if (applied > 0) {
-    HIP_TRY(hipMemsetAsync(&h->d_gate->pending, 0, sizeof(int), h->stream));  // ahead of every later gated call
-    for (Level& L : h->levels) {
-      L.curr_mark_free = L.curr_update_index + 3 * (applied - 1) + 1;
-      L.curr_mark_occ = L.curr_update_index + 3 * (applied - 1) + 2;
-      L.curr_update_index += 3 * applied;
-      L.last_update_index += applied;
-    }
-    h->gate_applied_total += applied;
-    if (state) state->pending = 0;
-  }
-  h->gate_outstanding = false;
-  return HSM_OK;
-}
-
 int reset_update_gate(hsm_ctx* h) {
   hipLaunchKernelGGL(update_gate_reset_kernel, dim3(1), dim3(64), 0, h->stream, h->d_gate);
   HIP_TRY(hipGetLastError());
@@ -772,6 +745,87 @@ int reset_update_gate(hsm_ctx* h) {
 }
 
 }  // namespace
+
+// Orders a launch on `s` that READS the map (a batched match, a batched score) against the map updates, which are queued on the
+// context's own stream.  *mark = the stream's record where the launch has to be remembered for the next update
+// (`(*mark)->pending = true` once it is queued), nullptr where nothing is to be remembered (the context's own stream; a capture).
+static int order_map_reader(hsm_ctx* h, hipStream_t s, const char* who, hsm_ctx::ForeignStream** mark) {
+  *mark = nullptr;
+  if (s == h->stream) return HSM_OK;
+  // A caller-owned stream is not ordered against the context's own one, on which map updates are queued
+  // (hsm_update_by_scan returns before they ran): order the launch behind the updates queued so far, and
+  // leave a marker the next update waits for, so that it does not rewrite the map under a running reader.
+  hsm_ctx::ForeignStream* fs = nullptr;
+  for (hsm_ctx::ForeignStream& f : h->foreign)
+    if (f.s == s) fs = &f;
+  if (!fs) {
+    h->foreign.push_back({s, 0ull, false});
+    fs = &h->foreign.back();
+  }
+  if (stream_capturing(s)) {
+    // A launch into a graph capture runs at the caller's replays, not now: it neither records that the stream is ordered behind
+    // the updates nor leaves a marker for the next update (either would describe work only the graph holds).  The updates queued
+    // so far are waited for on the host instead -- a wait node on an event recorded outside the capture would order the graph
+    // but not the stream's later eager launches.  Later updates and the replays are ordered by the caller; while the capture
+    // lasts, updates are refused (order_after_foreign_match).
+    hipStreamCaptureMode mode = hipStreamCaptureModeRelaxed;
+    HIP_TRY(hipThreadExchangeStreamCaptureMode(&mode));
+    const hipError_t e = hipStreamSynchronize(h->stream);
+    (void)hipThreadExchangeStreamCaptureMode(&mode);
+    if (e != hipSuccess) return fail_at(HSM_ERR_HIP, who, ": waiting for the queued map updates at capture", e);
+    return HSM_OK;
+  }
+  // (what test_queued_updates_are_ordered_against_caller_streams holds)
+  if (fs->ordered_epoch != h->upd_epoch) {  // THIS stream has not been ordered behind the latest map writes yet
+    if (!h->evt_updates) HIP_TRY(hipEventCreateWithFlags(&h->evt_updates, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(h->evt_updates, h->stream));
+    HIP_TRY(hipStreamWaitEvent(s, h->evt_updates, 0));
+    fs->ordered_epoch = h->upd_epoch;
+  }
+  // no marker here (an event record between back-to-back launches costs 2-3 us of kernel time each): the
+  // next writer of the map records one on every stream with a pending reader (order_after_foreign_match)
+  *mark = fs;
+  return HSM_OK;
+}
+
+int hsm_host::match_batch_device_nolock(hsm_ctx* h, int batch, const float* d_begin_world, const float* d_pts_xy,
+                                        const int* d_scan_offsets, int shared_n, float* d_out_pose,
+                                        float* d_out_cov, void* stream, int n_bound, const ExchangeFused* xp) {
+  if (batch < 0 || !d_begin_world || !d_out_pose || (!d_scan_offsets && shared_n < 0))
+    return fail(HSM_ERR_INVALID, "hsm_match_batch_device: bad argument");
+  if (batch == 0) return HSM_OK;
+  if (int rc = select_device(h)) return rc;
+  MatchParams P;
+  memset(&P, 0, sizeof P);
+  fill_schedule(h, P, true);
+  P.batch = batch;
+  P.begin_world = d_begin_world;
+  P.pts = reinterpret_cast<const float2*>(d_pts_xy);
+  P.offsets = d_scan_offsets;
+  P.shared_n = shared_n;
+  P.out_pose = d_out_pose;
+  P.out_cov = d_out_cov;
+  // a true bound of the scan lengths, where the host has one: a shared scan's length, or what the caller computed from host offsets
+  P.n_bound = d_scan_offsets ? n_bound : shared_n;
+  if (xp) P.xp = *xp;
+  h->fused_exchange_done = false;
+  // workgroup -> XCD mapping (gn_match.h, xcd_block): chunks dealt to the XCDs in turn balance the data-dependent
+  // per-scan time; maps whose touched region outgrows the L2s keep one contiguous eighth of the batch per XCD
+  const bool outgrows = hsm_plan::level0_outgrows_l2(h->levels[0].cells());
+  P.xcd_chunk = outgrows ? 0 : h->xcd_chunk;
+  P.wg_sync = h->wg_sync >= 0 ? h->wg_sync : (outgrows ? 1 : 0);
+  P.clock_probe = h->clock_probe;
+  // per-scan length is only known on the device for CSR input; shared_n doubles as the sizing HINT there
+  // (callers pass the typical beams per scan, 0 = unknown).  It only picks the kernel form: every form handles
+  // scans longer than the hint (the beams beyond the register/LDS-resident ones stream from memory).
+  const int hint = shared_n > 0 ? shared_n : 1081;
+  hipStream_t s = (hipStream_t)stream;
+  hsm_ctx::ForeignStream* fs = nullptr;
+  if (int rc = order_map_reader(h, s, "hsm_match_batch_device", &fs)) return rc;
+  if (int rc = launch_match(h, P, hint, s)) return rc;
+  if (fs) fs->pending = true;
+  return HSM_OK;
+}
 
 extern "C" {
 
@@ -1078,87 +1132,6 @@ int hsm_last_launch_config(const hsm_ctx* h, int cfg[5]) {
   return HSM_OK;
 }
 
-// Orders a launch on `s` that READS the map (a batched match, a batched score) against the map updates, which are queued on the
-// context's own stream.  *mark = the stream's record where the launch has to be remembered for the next update
-// (`(*mark)->pending = true` once it is queued), nullptr where nothing is to be remembered (the context's own stream; a capture).
-static int order_map_reader(hsm_ctx* h, hipStream_t s, const char* who, hsm_ctx::ForeignStream** mark) {
-  *mark = nullptr;
-  if (s == h->stream) return HSM_OK;
-  // A caller-owned stream is not ordered against the context's own one, on which map updates are queued
-  // (hsm_update_by_scan returns before they ran): order the launch behind the updates queued so far, and
-  // leave a marker the next update waits for, so that it does not rewrite the map under a running reader.
-  hsm_ctx::ForeignStream* fs = nullptr;
-  for (hsm_ctx::ForeignStream& f : h->foreign)
-    if (f.s == s) fs = &f;
-  if (!fs) {
-    h->foreign.push_back({s, 0ull, false});
-    fs = &h->foreign.back();
-  }
-  if (stream_capturing(s)) {
-    // A launch into a graph capture runs at the caller's replays, not now: it neither records that the stream is ordered behind
-    // the updates nor leaves a marker for the next update (either would describe work only the graph holds).  The updates queued
-    // so far are waited for on the host instead -- a wait node on an event recorded outside the capture would order the graph
-    // but not the stream's later eager launches.  Later updates and the replays are ordered by the caller; while the capture
-    // lasts, updates are refused (order_after_foreign_match).
-    hipStreamCaptureMode mode = hipStreamCaptureModeRelaxed;
-    HIP_TRY(hipThreadExchangeStreamCaptureMode(&mode));
-    const hipError_t e = hipStreamSynchronize(h->stream);
-    (void)hipThreadExchangeStreamCaptureMode(&mode);
-    if (e != hipSuccess) return fail_at(HSM_ERR_HIP, who, ": waiting for the queued map updates at capture", e);
-    return HSM_OK;
-  }
-  // (what test_queued_updates_are_ordered_against_caller_streams holds)
-  if (fs->ordered_epoch != h->upd_epoch) {  // THIS stream has not been ordered behind the latest map writes yet
-    if (!h->evt_updates) HIP_TRY(hipEventCreateWithFlags(&h->evt_updates, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(h->evt_updates, h->stream));
-    HIP_TRY(hipStreamWaitEvent(s, h->evt_updates, 0));
-    fs->ordered_epoch = h->upd_epoch;
-  }
-  // no marker here (an event record between back-to-back launches costs 2-3 us of kernel time each): the
-  // next writer of the map records one on every stream with a pending reader (order_after_foreign_match)
-  *mark = fs;
-  return HSM_OK;
-}
-
-static int match_batch_device_nolock(hsm_ctx* h, int batch, const float* d_begin_world, const float* d_pts_xy,
-                                     const int* d_scan_offsets, int shared_n, float* d_out_pose,
-                                     float* d_out_cov, void* stream, int n_bound = 0, const ExchangeFused* xp = nullptr) {
-  if (batch < 0 || !d_begin_world || !d_out_pose || (!d_scan_offsets && shared_n < 0))
-    return fail(HSM_ERR_INVALID, "hsm_match_batch_device: bad argument");
-  if (batch == 0) return HSM_OK;
-  if (int rc = select_device(h)) return rc;
-  MatchParams P;
-  memset(&P, 0, sizeof P);
-  fill_schedule(h, P, true);
-  P.batch = batch;
-  P.begin_world = d_begin_world;
-  P.pts = reinterpret_cast<const float2*>(d_pts_xy);
-  P.offsets = d_scan_offsets;
-  P.shared_n = shared_n;
-  P.out_pose = d_out_pose;
-  P.out_cov = d_out_cov;
-  // a true bound of the scan lengths, where the host has one: a shared scan's length, or what the caller computed from host offsets
-  P.n_bound = d_scan_offsets ? n_bound : shared_n;
-  if (xp) P.xp = *xp;
-  h->fused_exchange_done = false;
-  // workgroup -> XCD mapping (gn_match.h, xcd_block): chunks dealt to the XCDs in turn balance the data-dependent
-  // per-scan time; maps whose touched region outgrows the L2s keep one contiguous eighth of the batch per XCD
-  const bool outgrows = hsm_plan::level0_outgrows_l2(h->levels[0].cells());
-  P.xcd_chunk = outgrows ? 0 : h->xcd_chunk;
-  P.wg_sync = h->wg_sync >= 0 ? h->wg_sync : (outgrows ? 1 : 0);
-  P.clock_probe = h->clock_probe;
-  // per-scan length is only known on the device for CSR input; shared_n doubles as the sizing HINT there
-  // (callers pass the typical beams per scan, 0 = unknown).  It only picks the kernel form: every form handles
-  // scans longer than the hint (the beams beyond the register/LDS-resident ones stream from memory).
-  const int hint = shared_n > 0 ? shared_n : 1081;
-  hipStream_t s = (hipStream_t)stream;
-  hsm_ctx::ForeignStream* fs = nullptr;
-  if (int rc = order_map_reader(h, s, "hsm_match_batch_device", &fs)) return rc;
-  if (int rc = launch_match(h, P, hint, s)) return rc;
-  if (fs) fs->pending = true;
-  return HSM_OK;
-}
-
 int hsm_match_batch_device(hsm_ctx* h, int batch, const float* d_begin_world, const float* d_pts_xy,
                            const int* d_scan_offsets, int shared_n, float* d_out_pose, float* d_out_cov,
                            void* stream) {
@@ -1206,16 +1179,11 @@ static int score_batch_device_nolock(hsm_ctx* h, int level, int batch, const flo
   const LevelView v = level_view(h->levels[level], factor, 1);
   const bool exact = wants_exact(h);
   const int grid = (batch + 3) / 4;
-#define HSM_LAUNCH_SCORE(LAY, EX)                                                                                        \
-  hipLaunchKernelGGL((score_batch_kernel<LAY, EX>), dim3(grid), dim3(256), 0, s, v, d_poses_world, batch,                \
-                     reinterpret_cast<const float2*>(d_pts_xy), d_scan_offsets, d_scan_offsets ? 0 : shared_n,           \
-                     d_out_likelihood, d_out_residual)
-  if (h->layout == kLayoutPlane) {
-    if (exact) HSM_LAUNCH_SCORE(kLayoutPlane, true); else HSM_LAUNCH_SCORE(kLayoutPlane, false);
-  } else {
-    if (exact) HSM_LAUNCH_SCORE(kLayoutQuad, true); else HSM_LAUNCH_SCORE(kLayoutQuad, false);
-  }
-#undef HSM_LAUNCH_SCORE
+  with_sampler_form(h, [&](auto lay, auto ex) {
+    hipLaunchKernelGGL((score_batch_kernel<lay(), ex()>), dim3(grid), dim3(256), 0, s, v, d_poses_world, batch,
+                       reinterpret_cast<const float2*>(d_pts_xy), d_scan_offsets, d_scan_offsets ? 0 : shared_n,
+                       d_out_likelihood, d_out_residual);
+  });
   HIP_TRY(hipGetLastError());
   if (fs) fs->pending = true;
   h->last_kernel = "score_batch_kernel";
@@ -2709,129 +2677,6 @@ int hsm_slam_ranges_tf(hsm_ctx* h, int count, const float* start_pose, const flo
   return HSM_OK;
 }
 
-static int score_states(hsm_ctx* h, int level, int batch, const float* states_map, const float* pts_xy, int n,
-                        float* out_lh, float* out_residual, const char* who) {
-  if (int rc = valid_level(h, level)) return rc;
-  if (batch < 0 || n < 0 || (batch > 0 && (!states_map || !(out_lh || out_residual))) || (n > 0 && !pts_xy))
-    return fail(HSM_ERR_INVALID, who);
-  if (batch == 0) return HSM_OK;
-  std::lock_guard<std::mutex> lk(h->mu);
-  if (int rc = select_device(h)) return rc;
-  if (int rc = h->d_scan.reserve((size_t)n, kScanGrowth)) return rc;
-  if (n > 0) HIP_TRY(hipMemcpyAsync(h->d_scan, pts_xy, (size_t)n * sizeof(float2), hipMemcpyHostToDevice, h->stream));
-  if (int rc = h->d_batch.reserve((size_t)batch * 5 * sizeof(float))) return rc;
-  float* d_states = (float*)h->d_batch.p;
-  float* d_lh = d_states + 3 * (size_t)batch;
-  float* d_res = d_lh + (size_t)batch;
-  HIP_TRY(hipMemcpyAsync(d_states, states_map, (size_t)batch * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  const float factor = (float)(1.0 / pow(2.0, (double)level));
-  const LevelView v = level_view(h->levels[level], factor, 1);
-  const int grid = (batch + 3) / 4;
-#define HSM_LAUNCH_LH(LAY, EX)                                                                                         \
-  hipLaunchKernelGGL((likelihood_kernel<LAY, EX>), dim3(grid), dim3(256), 0, h->stream, v, d_states, batch, h->d_scan, \
-                     n, factor, out_lh ? d_lh : nullptr, out_residual ? d_res : nullptr)
-  if (h->layout == kLayoutPlane) {
-    if (wants_exact(h)) HSM_LAUNCH_LH(kLayoutPlane, true); else HSM_LAUNCH_LH(kLayoutPlane, false);
-  } else {
-    if (wants_exact(h)) HSM_LAUNCH_LH(kLayoutQuad, true); else HSM_LAUNCH_LH(kLayoutQuad, false);
-  }
-#undef HSM_LAUNCH_LH
-  HIP_TRY(hipGetLastError());
-  if (out_lh) HIP_TRY(hipMemcpyAsync(out_lh, d_lh, (size_t)batch * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-  if (out_residual)
-    HIP_TRY(hipMemcpyAsync(out_residual, d_res, (size_t)batch * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  return HSM_OK;
-}
-
-int hsm_likelihood_states(hsm_ctx* h, int level, int batch, const float* states_map, const float* pts_xy, int n,
-                          float* out_lh) {
-  return score_states(h, level, batch, states_map, pts_xy, n, out_lh, nullptr, "hsm_likelihood_states: bad argument");
-}
-
-int hsm_residual_states(hsm_ctx* h, int level, int batch, const float* states_map, const float* pts_xy, int n,
-                        float* out_residual) {
-  return score_states(h, level, batch, states_map, pts_xy, n, nullptr, out_residual,
-                      "hsm_residual_states: bad argument");
-}
-
-int hsm_covariance_for_poses(hsm_ctx* h, int level, int batch, const float* poses_map, const float* pts_xy, int n,
-                             float* out_cov_map, float* out_cov_world, float* out_lh7) {
-  if (int rc = valid_level(h, level)) return rc;
-  if (batch < 0 || n < 0 || (batch > 0 && (!poses_map || !(out_cov_map || out_cov_world || out_lh7))) ||
-      (n > 0 && !pts_xy))
-    return fail(HSM_ERR_INVALID, "hsm_covariance_for_poses: bad argument");
-  if (batch == 0) return HSM_OK;
-  std::lock_guard<std::mutex> lk(h->mu);
-  if (int rc = select_device(h)) return rc;
-  if (int rc = h->d_scan.reserve((size_t)n, kScanGrowth)) return rc;
-  if (n > 0) HIP_TRY(hipMemcpyAsync(h->d_scan, pts_xy, (size_t)n * sizeof(float2), hipMemcpyHostToDevice, h->stream));
-  if (int rc = h->d_batch.reserve((size_t)batch * (3 + 9 + 9 + 7) * sizeof(float))) return rc;
-  float* d_poses = (float*)h->d_batch.p;
-  float* d_map = d_poses + 3 * (size_t)batch;
-  float* d_world = d_map + 9 * (size_t)batch;
-  float* d_lh7 = d_world + 9 * (size_t)batch;
-  HIP_TRY(hipMemcpyAsync(d_poses, poses_map, (size_t)batch * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  const float factor = (float)(1.0 / pow(2.0, (double)level));
-  const Level& Lv = h->levels[level];
-  const LevelView v = level_view(Lv, factor, 1);
-#define HSM_LAUNCH_COV(LAY, EX)                                                                                     \
-  hipLaunchKernelGGL((pose_covariance_kernel<LAY, EX>), dim3(batch), dim3(448), 0, h->stream, v, d_poses, batch, \
-                     h->d_scan, n, factor, Lv.cell_length, d_map, d_world, d_lh7)
-  if (h->layout == kLayoutPlane) {
-    if (wants_exact(h)) HSM_LAUNCH_COV(kLayoutPlane, true); else HSM_LAUNCH_COV(kLayoutPlane, false);
-  } else {
-    if (wants_exact(h)) HSM_LAUNCH_COV(kLayoutQuad, true); else HSM_LAUNCH_COV(kLayoutQuad, false);
-  }
-#undef HSM_LAUNCH_COV
-  HIP_TRY(hipGetLastError());
-  if (out_cov_map)
-    HIP_TRY(hipMemcpyAsync(out_cov_map, d_map, (size_t)batch * 9 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-  if (out_cov_world)
-    HIP_TRY(hipMemcpyAsync(out_cov_world, d_world, (size_t)batch * 9 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-  if (out_lh7)
-    HIP_TRY(hipMemcpyAsync(out_lh7, d_lh7, (size_t)batch * 7 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  return HSM_OK;
-}
-
-int hsm_ray_distances(hsm_ctx* h, int level, float origin_x, float origin_y, float resolution, int n,
-                      const float* begin_world_xy, const float* end_world_xy, float* out_dist, float* out_hit_xy) {
-  if (int rc = valid_level(h, level)) return rc;
-  if (n < 0 || (n > 0 && (!begin_world_xy || !end_world_xy || !out_dist)) || !(resolution > 0.0f))
-    return fail(HSM_ERR_INVALID, "hsm_ray_distances: bad argument");
-  if (n == 0) return HSM_OK;
-  std::lock_guard<std::mutex> lk(h->mu);
-  if (int rc = select_device(h)) return rc;
-  if (int rc = h->d_batch.reserve((size_t)n * 7 * sizeof(float))) return rc;  // begin[2] end[2] dist[1] hit[2]
-  float* d = (float*)h->d_batch.p;
-  RayQueryParams P;
-  const Level& L = h->levels[level];
-  P.logodds = L.d_logodds;
-  P.sx = L.sx;
-  P.sy = L.sy;
-  P.origin_x = origin_x;
-  P.origin_y = origin_y;
-  P.scale = resolution;
-  P.inv_scale = 1.0f / resolution;  // CoordinateTransformer::setTransforms, HectorMapTools.h:64
-  P.begin_world = reinterpret_cast<const float2*>(d);
-  P.end_world = reinterpret_cast<const float2*>(d + 2 * (size_t)n);
-  P.out_hit = reinterpret_cast<float2*>(d + 4 * (size_t)n);
-  P.out_dist = d + 6 * (size_t)n;
-  P.n = n;
-  HIP_TRY(hipMemcpyAsync(d, begin_world_xy, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(d + 2 * (size_t)n, end_world_xy, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  if (out_hit_xy)  // in/out: rays without a hit keep the caller's values
-    HIP_TRY(hipMemcpyAsync(d + 4 * (size_t)n, out_hit_xy, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(ray_distance_kernel, dim3((n + 3) / 4), dim3(256), 0, h->stream, P);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(out_dist, P.out_dist, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-  if (out_hit_xy)
-    HIP_TRY(hipMemcpyAsync(out_hit_xy, P.out_hit, (size_t)n * 2 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  return HSM_OK;
-}
-
 int hsm_occupancy_grid(hsm_ctx* h, int level, signed char* out) {
   if (int rc = valid_level(h, level)) return rc;
   if (!out) return fail(HSM_ERR_INVALID, "hsm_occupancy_grid: out is null");
@@ -2951,839 +2796,3 @@ int hsm_retain_scan(hsm_ctx* h, const float* pts_xy, int n, const float origo[2]
 
 }  // extern "C"
 
-// One persistent host thread per replica beyond the first (replica 0 runs on the calling thread): a job slot guarded by
-// a mutex + condition variable; threads live as long as the group, so a batched match costs no thread creation.
-struct GroupWorker {
-  std::thread th;
-  std::mutex m;
-  std::condition_variable cv;
-  std::function<int()> job;
-  bool has_job = false, done = false, quit = false;
-  int rc = HSM_OK;
-  std::string err;
-};
-
-// RCCL, loaded on first use: the single-GPU library keeps its dependency set (HIP / HSA / libc), and a process that never
-// gathers across devices never maps the 570 MB librccl.  In a process that has PyTorch-ROCm loaded the SONAME resolves to
-// the librccl torch already brought in (one RCCL, one HIP runtime); elsewhere to /opt/rocm/lib.
-struct RcclApi {
-  void* lib = nullptr;
-  decltype(&ncclCommInitAll) CommInitAll = nullptr;
-  decltype(&ncclCommDestroy) CommDestroy = nullptr;
-  decltype(&ncclGroupStart) GroupStart = nullptr;
-  decltype(&ncclGroupEnd) GroupEnd = nullptr;
-  decltype(&ncclAllGather) AllGather = nullptr;
-  decltype(&ncclSend) Send = nullptr;
-  decltype(&ncclRecv) Recv = nullptr;
-  decltype(&ncclGetErrorString) GetErrorString = nullptr;
-  decltype(&ncclGetVersion) GetVersion = nullptr;
-  std::string error;
-};
-
-static RcclApi* rccl_api() {
-  static RcclApi api;
-  static std::once_flag once;
-  std::call_once(once, [] {
-    for (const char* name : {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"}) {
-      api.lib = dlopen(name, RTLD_NOW | RTLD_LOCAL);
-      if (api.lib) break;
-    }
-    if (!api.lib) {
-      const char* e = dlerror();
-      api.error = std::string("dlopen(librccl.so.1): ") + (e ? e : "not found");
-      return;
-    }
-    bool ok = true;
-    auto sym = [&](const char* n) -> void* {
-      void* p = dlsym(api.lib, n);
-      if (!p) {
-        ok = false;
-        api.error = std::string("librccl: missing symbol ") + n;
-      }
-      return p;
-    };
-    api.CommInitAll = reinterpret_cast<decltype(api.CommInitAll)>(sym("ncclCommInitAll"));
-    api.CommDestroy = reinterpret_cast<decltype(api.CommDestroy)>(sym("ncclCommDestroy"));
-    api.GroupStart = reinterpret_cast<decltype(api.GroupStart)>(sym("ncclGroupStart"));
-    api.GroupEnd = reinterpret_cast<decltype(api.GroupEnd)>(sym("ncclGroupEnd"));
-    api.AllGather = reinterpret_cast<decltype(api.AllGather)>(sym("ncclAllGather"));
-    api.Send = reinterpret_cast<decltype(api.Send)>(sym("ncclSend"));
-    api.Recv = reinterpret_cast<decltype(api.Recv)>(sym("ncclRecv"));
-    api.GetErrorString = reinterpret_cast<decltype(api.GetErrorString)>(sym("ncclGetErrorString"));
-    api.GetVersion = reinterpret_cast<decltype(api.GetVersion)>(sym("ncclGetVersion"));
-    if (!ok) {
-      dlclose(api.lib);
-      api.lib = nullptr;
-    }
-  });
-  return &api;
-}
-
-struct hsm_group {
-  std::vector<hsm_ctx*> members;
-  std::vector<std::unique_ptr<GroupWorker>> workers;  // workers[r - 1] serves replica r
-  // device-resident gather (hsm_group_match_batch_device): per replica a result block on ITS device and an event
-  std::vector<Buf<float>> d_pose, d_cov;  // (d_cov is allocated last: it holding 9 n floats says both serve n scans)
-  std::vector<hipEvent_t> evt;
-  // the gather itself: RCCL over the group's devices (one communicator per replica, ncclCommInitAll on first use), or
-  // peer copies.  gather_pref = what was asked for (hsm_group_set_gather / env HSM_GROUP_GATHER), gather_mode = what runs.
-  int gather_pref = HSM_GATHER_AUTO, gather_mode = HSM_GATHER_AUTO;
-  bool force_p2p = false;  // hsm_group_debug_force_p2p: every shard, the root's too, through grouped ncclSend / ncclRecv
-  std::vector<ncclComm_t> comms;
-  std::vector<Buf<float>> d_all_pose, d_all_cov;  // all-gather receive blocks of the replicas other than the root (likewise)
-  std::string gather_note;                    // why AUTO settled on peer copies, if it did
-  // HSM_GATHER_DIRECT: one mailbox exchange per replica (pose_exchange.hip), re-made when the gathered row count changes
-  std::vector<hsm_exchange*> xpose, xcov;
-  size_t x_rows = 0;
-  std::mutex mu;  // one group call at a time
-};
-
-#define NCCL_TRY(api, expr)                                                                     \
-  do {                                                                                          \
-    ncclResult_t r__ = (expr);                                                                  \
-    if (r__ != ncclSuccess) {                                                                   \
-      char b__[384];                                                                            \
-      snprintf(b__, sizeof b__, "%s: %s", #expr, (api)->GetErrorString ? (api)->GetErrorString(r__) : "rccl error"); \
-      return fail(HSM_ERR_HIP, b__);                                                            \
-    }                                                                                           \
-  } while (0)
-
-// decide (once) how the group gathers: RCCL needs the library, distinct devices and a communicator per replica
-static int group_ensure_gather(hsm_group* g) {
-  if (g->gather_mode != HSM_GATHER_AUTO) return HSM_OK;
-  const int R = (int)g->members.size();
-  auto settle_peer = [&](const std::string& why) -> int {
-    if (g->gather_pref == HSM_GATHER_RCCL) return fail(HSM_ERR_HIP, ("hsm_group: RCCL gather requested but unavailable: " + why).c_str());
-    g->gather_note += why;
-    g->gather_mode = HSM_GATHER_PEER;
-    return HSM_OK;
-  };
-  if (g->gather_pref == HSM_GATHER_PEER) {
-    g->gather_mode = HSM_GATHER_PEER;
-    return HSM_OK;
-  }
-  std::vector<int> devs;
-  for (hsm_ctx* h : g->members) devs.push_back(h->device);
-  if (g->gather_pref == HSM_GATHER_AUTO || g->gather_pref == HSM_GATHER_DIRECT) {
-    // the device-side exchange needs every replica's kernels to store into every other replica's HBM: the same device, or
-    // peer access (xGMI on one node)
-    std::string why;
-    if (R > HSM_EXCHANGE_MAX_WORLD) why = "more replicas than HSM_EXCHANGE_MAX_WORLD";
-    for (int a = 0; a < R && why.empty(); ++a)
-      for (int b = 0; b < R && why.empty(); ++b) {
-        if (devs[a] == devs[b]) continue;
-        int can = 0;
-        if (hipDeviceCanAccessPeer(&can, devs[a], devs[b]) != hipSuccess || !can) {
-          (void)hipGetLastError();
-          why = "no peer access between devices " + std::to_string(devs[a]) + " and " + std::to_string(devs[b]);
-        }
-      }
-    if (why.empty()) {
-      g->gather_mode = HSM_GATHER_DIRECT;
-      return HSM_OK;
-    }
-    if (g->gather_pref == HSM_GATHER_DIRECT) return fail(HSM_ERR_HIP, ("hsm_group: direct gather requested but unavailable: " + why).c_str());
-    g->gather_note = "direct exchange unavailable (" + why + "); ";
-  }
-  for (int a = 0; a < R; ++a)
-    for (int b = a + 1; b < R; ++b)
-      if (devs[a] == devs[b]) return settle_peer("a device is listed more than once (one RCCL rank per device)");
-  RcclApi* api = rccl_api();
-  if (!api->lib) return settle_peer(api->error);
-  g->comms.assign((size_t)R, nullptr);
-  const ncclResult_t r = api->CommInitAll(g->comms.data(), R, devs.data());
-  if (r != ncclSuccess) {
-    g->comms.clear();
-    return settle_peer(std::string("ncclCommInitAll: ") + api->GetErrorString(r));
-  }
-  g->gather_mode = HSM_GATHER_RCCL;
-  return HSM_OK;
-}
-
-static void group_worker_main(GroupWorker* w) {
-  std::unique_lock<std::mutex> lk(w->m);
-  for (;;) {
-    w->cv.wait(lk, [w] { return w->has_job || w->quit; });
-    if (w->quit) return;
-    std::function<int()> job = std::move(w->job);
-    w->has_job = false;
-    lk.unlock();
-    const int rc = job();
-    std::string err = rc != HSM_OK ? hsm_last_error() : "";  // thread-local text: carry it to the caller's thread
-    lk.lock();
-    w->rc = rc;
-    w->err = std::move(err);
-    w->done = true;
-    w->cv.notify_all();
-  }
-}
-
-// run fn(replica index) on every replica concurrently; first non-zero status wins
-template <typename F>
-static int group_parallel(hsm_group* g, F fn) {
-  const int R = (int)g->members.size();
-  for (int r = 1; r < R; ++r) {
-    GroupWorker* w = g->workers[(size_t)r - 1].get();
-    std::lock_guard<std::mutex> lk(w->m);
-    w->job = [fn, r]() -> int { return fn(r); };
-    w->has_job = true;
-    w->done = false;
-    w->cv.notify_all();
-  }
-  int rc0 = fn(0);
-  int rc_out = rc0;
-  std::string err_out = rc0 != HSM_OK ? std::string(hsm_last_error()) : std::string();
-  for (int r = 1; r < R; ++r) {
-    GroupWorker* w = g->workers[(size_t)r - 1].get();
-    std::unique_lock<std::mutex> lk(w->m);
-    w->cv.wait(lk, [w] { return w->done; });
-    if (w->rc != HSM_OK && rc_out == HSM_OK) {
-      rc_out = w->rc;
-      err_out = w->err;
-    }
-  }
-  return rc_out == HSM_OK ? HSM_OK : fail(rc_out, err_out.c_str());
-}
-
-
-extern "C" {
-
-int hsm_group_create(float map_resolution, int size_x, int size_y, unsigned levels, float start_x, float start_y,
-                     const int* devices, int n_devices, hsm_group** out) {
-  if (!out || !devices || n_devices < 1) return fail(HSM_ERR_INVALID, "hsm_group_create: bad argument");
-  *out = nullptr;
-  hsm_group* g = new hsm_group();
-  for (int i = 0; i < n_devices; ++i) {
-    hsm_opts o;
-    o.device = devices[i];
-    o.layout = HSM_LAYOUT_AUTO;
-    o.waves_per_scan = 0;
-    hsm_ctx* h = nullptr;
-    const int rc = hsm_create(map_resolution, size_x, size_y, levels, start_x, start_y, &o, &h);
-    if (rc != HSM_OK) {
-      hsm_group_destroy(g);
-      return rc;
-    }
-    g->members.push_back(h);
-  }
-  for (int i = 1; i < n_devices; ++i) {
-    g->workers.emplace_back(new GroupWorker());
-    GroupWorker* w = g->workers.back().get();
-    w->th = std::thread(group_worker_main, w);
-  }
-  for (std::vector<Buf<float>>* v : {&g->d_pose, &g->d_cov, &g->d_all_pose, &g->d_all_cov}) v->resize((size_t)n_devices);
-  g->evt.assign((size_t)n_devices, nullptr);
-  if (const char* env = getenv("HSM_GROUP_GATHER")) {
-    if (strcmp(env, "rccl") == 0) g->gather_pref = HSM_GATHER_RCCL;
-    else if (strcmp(env, "peer") == 0) g->gather_pref = HSM_GATHER_PEER;
-    else if (strcmp(env, "direct") == 0) g->gather_pref = HSM_GATHER_DIRECT;
-    else if (strcmp(env, "auto") != 0) {
-      hsm_group_destroy(g);
-      return fail(HSM_ERR_INVALID, "hsm_group_create: HSM_GROUP_GATHER must be one of auto, direct, rccl, peer");
-    }
-  }
-  *out = g;
-  return HSM_OK;
-}
-
-int hsm_group_set_gather(hsm_group* g, int mode) {
-  if (!g) return fail(HSM_ERR_INVALID, "null group");
-  if (mode != HSM_GATHER_AUTO && mode != HSM_GATHER_PEER && mode != HSM_GATHER_RCCL && mode != HSM_GATHER_DIRECT)
-    return fail(HSM_ERR_INVALID, "hsm_group_set_gather: unknown mode");
-  std::lock_guard<std::mutex> glk(g->mu);
-  g->gather_pref = mode;
-  g->gather_note.clear();
-  if (mode == HSM_GATHER_PEER) {
-    g->gather_mode = HSM_GATHER_PEER;
-    return HSM_OK;
-  }
-  if (mode == HSM_GATHER_RCCL && !g->comms.empty()) {  // communicators, once made, are kept and reused
-    g->gather_mode = HSM_GATHER_RCCL;
-    return HSM_OK;
-  }
-  g->gather_mode = HSM_GATHER_AUTO;  // decide again
-  return mode == HSM_GATHER_AUTO ? HSM_OK : group_ensure_gather(g);
-}
-
-int hsm_group_debug_force_p2p(hsm_group* g, int on) {
-  if (!g) return fail(HSM_ERR_INVALID, "null group");
-  std::lock_guard<std::mutex> glk(g->mu);
-  g->force_p2p = on != 0;
-  return HSM_OK;
-}
-
-int hsm_group_gather_mode(hsm_group* g) {
-  if (!g) return HSM_GATHER_AUTO;
-  std::lock_guard<std::mutex> glk(g->mu);
-  if (group_ensure_gather(g) != HSM_OK) return HSM_GATHER_AUTO;
-  return g->gather_mode;
-}
-
-const char* hsm_group_gather_note(const hsm_group* g) { return g ? g->gather_note.c_str() : ""; }
-
-void hsm_group_destroy(hsm_group* g) {
-  if (!g) return;
-  for (auto& w : g->workers) {
-    {
-      std::lock_guard<std::mutex> lk(w->m);
-      w->quit = true;
-      w->cv.notify_all();
-    }
-    if (w->th.joinable()) w->th.join();
-  }
-  if (!g->comms.empty()) {
-    for (hsm_ctx* h : g->members) (void)hsm_synchronize(h);
-    RcclApi* api = rccl_api();
-    for (ncclComm_t c : g->comms)
-      if (c && api->CommDestroy) (void)api->CommDestroy(c);
-  }
-  if (!g->xpose.empty() || !g->xcov.empty()) {
-    for (hsm_ctx* h : g->members) (void)hsm_synchronize(h);
-    for (hsm_exchange* x : g->xpose) hsm_exchange_destroy(x);
-    for (hsm_exchange* x : g->xcov) hsm_exchange_destroy(x);
-  }
-  TeardownLog log_, *log = &log_;  // (as hsm_destroy: name the first failing call, leave no error behind for the next caller)
-  for (size_t r = 0; r < g->members.size(); ++r) {
-    if (g->members[r]) TEARDOWN(log, hipSetDevice(g->members[r]->device));
-    for (std::vector<Buf<float>>* v : {&g->d_pose, &g->d_cov, &g->d_all_pose, &g->d_all_cov})
-      if (r < v->size()) (*v)[r].release(log);
-    if (r < g->evt.size() && g->evt[r]) TEARDOWN(log, hipEventDestroy(g->evt[r]));
-  }
-  for (hsm_ctx* h : g->members) hsm_destroy(h);
-  delete g;
-  if (!log_.first.empty()) {
-    g_last_error = "hsm_group_destroy: " + log_.first;
-    (void)hipGetLastError();
-  }
-}
-
-int hsm_group_size(const hsm_group* g) { return g ? (int)g->members.size() : 0; }
-
-hsm_ctx* hsm_group_member(hsm_group* g, int i) {
-  return (g && i >= 0 && i < (int)g->members.size()) ? g->members[i] : nullptr;
-}
-
-int hsm_group_set_update_factors(hsm_group* g, float free_factor, float occupied_factor) {
-  if (!g) return fail(HSM_ERR_INVALID, "null group");
-  for (hsm_ctx* h : g->members) {
-    if (int rc = hsm_set_update_factor_free(h, free_factor)) return rc;
-    if (int rc = hsm_set_update_factor_occupied(h, occupied_factor)) return rc;
-  }
-  return HSM_OK;
-}
-
-int hsm_group_process_scan(hsm_group* g, const float hint_world[3], const float* pts_xy, int n, const float origo[2],
-                           int do_update, float out_pose_world[3], float cov[9]) {
-  if (!g || g->members.empty()) return fail(HSM_ERR_INVALID, "null group");
-  std::lock_guard<std::mutex> glk(g->mu);
-  if (int rc = hsm_match(g->members[0], hint_world, pts_xy, n, origo, out_pose_world, cov)) return rc;
-  if (!do_update) return HSM_OK;
-  return group_parallel(g, [&](int r) -> int {
-    hsm_ctx* h = g->members[r];
-    if (r != 0)
-      if (int rc = hsm_retain_scan(h, pts_xy, n, origo)) return rc;
-    return hsm_update_by_scan(h, out_pose_world, pts_xy, n, origo);
-  });
-}
-
-int hsm_group_match_batch_device(hsm_group* g, const int* counts, const float* const* d_begin_world,
-                                 const float* const* d_pts_xy, const int* const* d_scan_offsets, int shared_n, int root,
-                                 float* d_out_pose_all, float* d_out_cov_all) {
-  if (!g || g->members.empty()) return fail(HSM_ERR_INVALID, "null group");
-  const int R = (int)g->members.size();
-  if (!counts || !d_begin_world || !d_pts_xy || !d_out_pose_all || root < 0 || root >= R)
-    return fail(HSM_ERR_INVALID, "hsm_group_match_batch_device: bad argument");
-  std::lock_guard<std::mutex> glk(g->mu);
-  std::vector<size_t> first((size_t)R + 1, 0);
-  for (int r = 0; r < R; ++r) {
-    if (counts[r] < 0 || (counts[r] > 0 && (!d_begin_world[r] || !d_pts_xy[r])))
-      return fail(HSM_ERR_INVALID, "hsm_group_match_batch_device: bad shard");
-    first[(size_t)r + 1] = first[(size_t)r] + (size_t)counts[r];
-  }
-  const int root_dev = g->members[(size_t)root]->device;
-  if (int rc = group_ensure_gather(g)) return rc;
-  const bool rccl = g->gather_mode == HSM_GATHER_RCCL;
-  const bool direct = g->gather_mode == HSM_GATHER_DIRECT;
-  const size_t total = first[(size_t)R];
-  if (direct && total > 0) {
-    // Device-side exchange: one mailbox per replica for [total, 3] (+ one for [total, 9]), made when the gathered row count
-    // changes (a particle filter keeps its particle count; anything else pays a re-allocation here)
-    const bool want_cov = d_out_cov_all != nullptr;
-    if (g->x_rows != total || g->xpose.empty() || (want_cov && g->xcov.empty())) {
-      for (hsm_ctx* h : g->members)
-        if (int rc0 = hsm_synchronize(h)) return rc0;
-      const bool remake_pose = g->x_rows != total || g->xpose.empty();
-      auto make = [&](std::vector<hsm_exchange*>& xs, int cols) -> int {
-        for (hsm_exchange* x : xs) hsm_exchange_destroy(x);
-        xs.assign((size_t)R, nullptr);
-        for (int r = 0; r < R; ++r)
-          if (int rc0 = hsm_exchange_create(g->members[(size_t)r]->device, r, R, (int)total, cols, 2, &xs[(size_t)r])) return rc0;
-        for (int r = 0; r < R; ++r)
-          if (int rc0 = hsm_exchange_connect_local(xs[(size_t)r], xs.data())) return rc0;
-        return HSM_OK;
-      };
-      if (remake_pose) {
-        if (int rc0 = make(g->xpose, 3)) return rc0;
-        for (hsm_exchange* x : g->xcov) hsm_exchange_destroy(x);  // (shaped for the old row count)
-        g->xcov.clear();
-      }
-      if (want_cov && g->xcov.empty())
-        if (int rc0 = make(g->xcov, 9)) return rc0;
-      g->x_rows = total;
-    }
-  }
-  bool equal = counts[0] > 0;  // ncclAllGather wants the same count from every rank
-  for (int r = 1; r < R; ++r) equal = equal && counts[r] == counts[0];
-  const bool self_send = rccl && g->force_p2p;  // test hook: the send / receive form for every shard, the root's own included
-  if (self_send) equal = false;
-  // every replica: match its shard on its own stream.  Peer gather: push the poses (and H) to the root's device with a peer
-  // copy on the same stream -- 12 (+36) bytes per scan over xGMI, no host staging, no host wait.  RCCL gather: the
-  // collective is queued below, behind the match, on the same streams.
-  int rc = group_parallel(g, [&](int r) -> int {
-    hsm_ctx* h = g->members[(size_t)r];
-    const size_t n = (size_t)counts[r];
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (int rc2 = select_device(h)) return rc2;
-    if (!g->evt[(size_t)r]) HIP_TRY(hipEventCreateWithFlags(&g->evt[(size_t)r], hipEventDisableTiming));
-    // a pair of result blocks for `rows` scans: the covariance block goes first and comes back last
-    auto reserve_pair = [](Buf<float>& pose, Buf<float>& cov, size_t rows) -> int {
-      if (cov.holds(rows * 9)) return HSM_OK;
-      if (int rc2 = cov.drop()) return rc2;
-      if (int rc2 = pose.replace(rows * 3 * sizeof(float))) return rc2;
-      return cov.reserve(rows * 9);
-    };
-    if (((rccl && equal) || direct) && r != root)  // all-gather receive blocks of a non-root replica
-      if (int rc2 = reserve_pair(g->d_all_pose[(size_t)r], g->d_all_cov[(size_t)r], total)) return rc2;
-    if (n > 0) {
-      if (int rc2 = reserve_pair(g->d_pose[(size_t)r], g->d_cov[(size_t)r], n)) return rc2;
-      if (int rc2 = match_batch_device_nolock(h, (int)n, d_begin_world[r], d_pts_xy[r],
-                                              d_scan_offsets ? d_scan_offsets[r] : nullptr, shared_n, g->d_pose[(size_t)r],
-                                              d_out_cov_all ? g->d_cov[(size_t)r] : nullptr, h->stream))
-        return rc2;
-      if (direct) {
-        // (below, also for a replica without scans: every replica posts every epoch)
-      } else if (!rccl || (r == root && !equal && !self_send)) {  // (RCCL send/recv gather: the root's own shard is a local copy)
-        HIP_TRY(hipMemcpyPeerAsync(d_out_pose_all + 3 * first[(size_t)r], root_dev, g->d_pose[(size_t)r], h->device,
-                                   n * 3 * sizeof(float), h->stream));
-        if (d_out_cov_all)
-          HIP_TRY(hipMemcpyPeerAsync(d_out_cov_all + 9 * first[(size_t)r], root_dev, g->d_cov[(size_t)r], h->device,
-                                     n * 9 * sizeof(float), h->stream));
-      }
-    }
-    if (direct && total > 0) {
-      // ONE launch on this replica's stream, behind its match: store the shard's rows into every replica's mailbox and
-      // unpack all shards' rows as they arrive -- the root into the caller's arrays, the others into blocks the group
-      // keeps (every replica holds all poses afterwards: hsm_group_gathered).  No collective, no event, no host wait.
-      if (int rc2 = hsm_exchange_post_wait(g->xpose[(size_t)r], g->d_pose[(size_t)r], (int)first[(size_t)r], (int)n, 0,
-                                           r == root ? d_out_pose_all : g->d_all_pose[(size_t)r], h->stream))
-        return rc2;
-      if (d_out_cov_all)
-        if (int rc2 = hsm_exchange_post_wait(g->xcov[(size_t)r], g->d_cov[(size_t)r], (int)first[(size_t)r], (int)n, 0,
-                                             r == root ? d_out_cov_all : g->d_all_cov[(size_t)r], h->stream))
-          return rc2;
-      return HSM_OK;
-    }
-    if (!rccl) HIP_TRY(hipEventRecord(g->evt[(size_t)r], h->stream));
-    return HSM_OK;
-  });
-  if (rc != HSM_OK) return rc;
-  if (direct) return HSM_OK;
-  if (rccl) {
-    // ONE grouped collective over the group's communicators, each rank's part on its replica's stream (behind its match):
-    // equal shards -> ncclAllGather of [B/G, 3] (+ [B/G, 9]); the root receives straight into the caller's arrays, the
-    // other replicas into blocks the group keeps (every replica then holds all poses: hsm_group_gathered).  Unequal
-    // shards -> the same gather as grouped ncclSend / ncclRecv to the root.  The collective itself orders the root's
-    // stream behind every shard.
-    RcclApi* api = rccl_api();
-    NCCL_TRY(api, api->GroupStart());
-    ncclResult_t nr = ncclSuccess;
-    for (int r = 0; r < R && nr == ncclSuccess; ++r) {
-      hsm_ctx* h = g->members[(size_t)r];
-      const size_t n = (size_t)counts[r];
-      if (equal) {
-        nr = api->AllGather(g->d_pose[(size_t)r], r == root ? d_out_pose_all : g->d_all_pose[(size_t)r], n * 3, ncclFloat,
-                            g->comms[(size_t)r], h->stream);
-        if (nr == ncclSuccess && d_out_cov_all)
-          nr = api->AllGather(g->d_cov[(size_t)r], r == root ? d_out_cov_all : g->d_all_cov[(size_t)r], n * 9, ncclFloat,
-                              g->comms[(size_t)r], h->stream);
-      } else if ((r != root || self_send) && n > 0) {
-        hsm_ctx* hr = g->members[(size_t)root];
-        nr = api->Send(g->d_pose[(size_t)r], n * 3, ncclFloat, root, g->comms[(size_t)r], h->stream);
-        if (nr == ncclSuccess)
-          nr = api->Recv(d_out_pose_all + 3 * first[(size_t)r], n * 3, ncclFloat, r, g->comms[(size_t)root], hr->stream);
-        if (nr == ncclSuccess && d_out_cov_all) {
-          nr = api->Send(g->d_cov[(size_t)r], n * 9, ncclFloat, root, g->comms[(size_t)r], h->stream);
-          if (nr == ncclSuccess)
-            nr = api->Recv(d_out_cov_all + 9 * first[(size_t)r], n * 9, ncclFloat, r, g->comms[(size_t)root], hr->stream);
-        }
-      }
-    }
-    const ncclResult_t ne = api->GroupEnd();
-    if (nr != ncclSuccess) NCCL_TRY(api, nr);
-    NCCL_TRY(api, ne);
-    return HSM_OK;
-  }
-  // the root's stream waits for every shard: work queued on it afterwards (and hsm_synchronize on the root member) sees
-  // the complete gather
-  hsm_ctx* hr = g->members[(size_t)root];
-  std::lock_guard<std::mutex> lk(hr->mu);
-  if (int rc2 = select_device(hr)) return rc2;
-  for (int r = 0; r < R; ++r)
-    if (r != root) HIP_TRY(hipStreamWaitEvent(hr->stream, g->evt[(size_t)r], 0));
-  return HSM_OK;
-}
-
-const float* hsm_group_gathered(hsm_group* g, int replica, int want_cov) {
-  if (!g || replica < 0 || replica >= (int)g->d_all_pose.size()) return nullptr;
-  return want_cov ? g->d_all_cov[(size_t)replica] : g->d_all_pose[(size_t)replica];
-}
-
-int hsm_group_synchronize(hsm_group* g) {
-  if (!g) return fail(HSM_ERR_INVALID, "null group");
-  for (hsm_ctx* h : g->members)
-    if (int rc = hsm_synchronize(h)) return rc;
-  for (hsm_exchange* x : g->xpose)  // a gather whose rows did not all arrive says so here
-    if (int rc = hsm_exchange_status(x)) return rc;
-  for (hsm_exchange* x : g->xcov)
-    if (int rc = hsm_exchange_status(x)) return rc;
-  return HSM_OK;
-}
-
-// THE partitioning of a batch over G replicas (contiguous shards): the first total % world shards hold one
-// scan more.  One rule for both transports -- hsm_group_* (one process, a worker thread per device) and
-// hector_slam_amd/sharding.py (one process per device under torch.distributed, which calls this function).
-int hsm_shard_bounds(int total, int rank, int world, int* begin, int* end) {
-  if (total < 0 || world <= 0 || rank < 0 || rank >= world || !begin || !end) return fail(HSM_ERR_INVALID, "hsm_shard_bounds: bad argument");
-  const int base = total / world, rem = total % world;
-  *begin = rank * base + (rank < rem ? rank : rem);
-  *end = *begin + base + (rank < rem ? 1 : 0);
-  return HSM_OK;
-}
-
-int hsm_group_match_batch(hsm_group* g, int batch, const float* begin_world, const float* pts_xy,
-                          const int* scan_offsets, int shared_n, float* out_pose, float* out_cov) {
-  if (!g || g->members.empty()) return fail(HSM_ERR_INVALID, "null group");
-  if (batch < 0 || !begin_world || !out_pose) return fail(HSM_ERR_INVALID, "hsm_group_match_batch: bad argument");
-  const int R = (int)g->members.size();
-  std::lock_guard<std::mutex> glk(g->mu);
-  return group_parallel(g, [&](int r) -> int {
-    int b = 0, e = 0;
-    if (int rc = hsm_shard_bounds(batch, r, R, &b, &e)) return rc;
-    if (e == b) return HSM_OK;
-    if (!scan_offsets)  // pose hypotheses of ONE shared scan
-      return hsm_match_batch(g->members[r], e - b, begin_world + 3 * (size_t)b, pts_xy, nullptr, shared_n,
-                             out_pose + 3 * (size_t)b, out_cov ? out_cov + 9 * (size_t)b : nullptr);
-    std::vector<int> offs((size_t)(e - b) + 1);  // CSR offsets rebased to the shard
-    for (int i = b; i <= e; ++i) offs[(size_t)(i - b)] = scan_offsets[i] - scan_offsets[b];
-    return hsm_match_batch(g->members[r], e - b, begin_world + 3 * (size_t)b, pts_xy + 2 * (size_t)scan_offsets[b],
-                           offs.data(), 0, out_pose + 3 * (size_t)b, out_cov ? out_cov + 9 * (size_t)b : nullptr);
-  });
-}
-
-int hsm_level_info(const hsm_ctx* h, int level, int* sx, int* sy, float* cell, float* scale) {
-  if (int rc = valid_level(h, level)) return rc;
-  const Level& L = h->levels[level];
-  if (sx) *sx = L.sx;
-  if (sy) *sy = L.sy;
-  if (cell) *cell = L.cell_length;
-  if (scale) *scale = L.scale_to_map;
-  return HSM_OK;
-}
-int hsm_map_coords_pose(const hsm_ctx* h, int level, const float w[3], float m[3]) {
-  if (int rc = valid_level(h, level)) return rc;
-  affine_apply_host(h->levels[level].mapTworld, w[0], w[1], m[0], m[1]);
-  m[2] = w[2];
-  return HSM_OK;
-}
-int hsm_world_coords_pose(const hsm_ctx* h, int level, const float m[3], float w[3]) {
-  if (int rc = valid_level(h, level)) return rc;
-  affine_apply_host(h->levels[level].worldTmap, m[0], m[1], w[0], w[1]);
-  w[2] = m[2];
-  return HSM_OK;
-}
-int hsm_update_index(const hsm_ctx* h, int level) {
-  if (valid_level(h, level)) return -1;
-  std::lock_guard<std::mutex> lk(h->mu);  // read by the facade's publisher thread while the scan thread updates
-  if (h->gate_outstanding)  // gated updates since the last look: wait for them and fetch their count
-    if (fold_gate_counters(const_cast<hsm_ctx*>(h))) return -1;
-  return h->levels[level].last_update_index;
-}
-
-int hsm_download_level(hsm_ctx* h, int level, float* logodds, int* update_index) {
-  if (int rc = valid_level(h, level)) return rc;
-  std::lock_guard<std::mutex> lk(h->mu);
-  if (int rc = select_device(h)) return rc;
-  Level& L = h->levels[level];
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  if (logodds) HIP_TRY(hipMemcpy(logodds, L.d_logodds, L.cells() * sizeof(float), hipMemcpyDeviceToHost));
-  if (update_index)
-    HIP_TRY(hipMemcpy(update_index, L.d_update_index, L.cells() * sizeof(int), hipMemcpyDeviceToHost));
-  return HSM_OK;
-}
-int hsm_upload_level(hsm_ctx* h, int level, const float* logodds, const int* update_index) {
-  if (int rc = valid_level(h, level)) return rc;
-  std::lock_guard<std::mutex> lk(h->mu);
-  if (int rc = select_device(h)) return rc;
-  Level& L = h->levels[level];
-  if (h->upd_boxes_outstanding)
-    if (int rc = merge_device_boxes(h)) return rc;
-  if (h->gate_outstanding)
-    if (int rc = fold_gate_counters(h)) return rc;
-  if (int rc = order_after_foreign_match(h)) return rc;
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  if (logodds) HIP_TRY(hipMemcpy(L.d_logodds, logodds, L.cells() * sizeof(float), hipMemcpyHostToDevice));
-  if (update_index)
-    HIP_TRY(hipMemcpy(L.d_update_index, update_index, L.cells() * sizeof(int), hipMemcpyHostToDevice));
-  if (int rc = rebuild_probability(h, L)) return rc;
-  whole_level_changed(L);
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  return HSM_OK;
-}
-int hsm_download_rows(hsm_ctx* h, int level, int y0, int y1, float* rows) {
-  if (int rc = valid_level(h, level)) return rc;
-  std::lock_guard<std::mutex> lk(h->mu);
-  if (int rc = select_device(h)) return rc;
-  Level& L = h->levels[level];
-  if (y0 < 0 || y1 > L.sy || y0 > y1 || !rows) return fail(HSM_ERR_INVALID, "hsm_download_rows: bad row range");
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  if (y1 > y0)
-    HIP_TRY(hipMemcpy(rows, L.d_logodds + (size_t)y0 * L.sx, (size_t)(y1 - y0) * L.sx * sizeof(float),
-                      hipMemcpyDeviceToHost));
-  return HSM_OK;
-}
-int hsm_download_cells(hsm_ctx* h, int level, int x0, int y0, int x1, int y1, void* dst_cells, int dst_pitch_cells) {
-  if (int rc = valid_level(h, level)) return rc;
-  std::lock_guard<std::mutex> lk(h->mu);
-  if (int rc = select_device(h)) return rc;
-  Level& L = h->levels[level];
-  if (x0 < 0 || y0 < 0 || x1 >= L.sx || y1 >= L.sy || x1 < x0 || y1 < y0 || !dst_cells || dst_pitch_cells < x1 - x0 + 1)
-    return fail(HSM_ERR_INVALID, "hsm_download_cells: bad rectangle");
-  const int w = x1 - x0 + 1, hgt = y1 - y0 + 1;
-  const size_t need = (size_t)w * hgt * 8;
-  if (int rc = h->d_cells.reserve(need, kHalfMore)) return rc;
-  hipLaunchKernelGGL(pack_cells_kernel, dim3(grid_for((size_t)w * hgt)), dim3(256), 0, h->stream, level_rw(L), x0, y0, w,
-                     hgt, reinterpret_cast<int2*>(h->d_cells.p));
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy2DAsync(dst_cells, (size_t)dst_pitch_cells * 8, h->d_cells, (size_t)w * 8, (size_t)w * 8, hgt,
-                           hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  return HSM_OK;
-}
-int hsm_last_update_bbox(const hsm_ctx* h, int level, int bbox[4]) {
-  if (int rc = valid_level(h, level)) return rc;
-  if (h->upd_boxes_outstanding) {  // a device-side update since the last look: wait for it and fetch its boxes
-    hsm_ctx* m = const_cast<hsm_ctx*>(h);
-    std::lock_guard<std::mutex> lk(m->mu);
-    if (m->upd_boxes_outstanding)
-      if (int rc = merge_device_boxes(m)) return rc;
-  }
-  for (int i = 0; i < 4; ++i) bbox[i] = h->levels[level].bbox[i];
-  return HSM_OK;
-}
-int hsm_take_dirty_bbox(hsm_ctx* h, int level, int bbox[4]) {
-  if (int rc = valid_level(h, level)) return rc;
-  if (!bbox) return fail(HSM_ERR_INVALID, "hsm_take_dirty_bbox: bbox is null");
-  std::lock_guard<std::mutex> lk(h->mu);
-  if (h->upd_boxes_outstanding)
-    if (int rc = merge_device_boxes(h)) return rc;
-  Level& L = h->levels[level];
-  for (int i = 0; i < 4; ++i) bbox[i] = L.dirty[i];
-  L.dirty[0] = L.dirty[1] = 0;
-  L.dirty[2] = L.dirty[3] = -1;
-  return HSM_OK;
-}
-int hsm_download_prob(hsm_ctx* h, int level, float* prob) {
-  if (int rc = valid_level(h, level)) return rc;
-  std::lock_guard<std::mutex> lk(h->mu);
-  if (int rc = select_device(h)) return rc;
-  Level& L = h->levels[level];
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  HIP_TRY(hipMemcpy(prob, L.d_prob, L.cells() * sizeof(float), hipMemcpyDeviceToHost));
-  return HSM_OK;
-}
-
-int hsm_hessian_derivs(hsm_ctx* h, int level, const float pose_map[3], const float* pts, int n, float H[9],
-                       float dTr[3]) {
-  if (int rc = valid_level(h, level)) return rc;
-  if (!pose_map || n < 0 || (n > 0 && !pts) || !H || !dTr) return fail(HSM_ERR_INVALID, "bad argument");
-  std::lock_guard<std::mutex> lk(h->mu);
-  if (int rc = select_device(h)) return rc;
-  if (int rc = h->d_scan.reserve((size_t)n, kScanGrowth)) return rc;
-  if (n > 0) HIP_TRY(hipMemcpyAsync(h->d_scan, pts, (size_t)n * sizeof(float2), hipMemcpyHostToDevice, h->stream));
-  const LevelView v = level_view(h->levels[level], 1.0f, 1);
-  float* d_out = h->d_small + 16;
-  if (wants_exact(h)) {
-    if (h->layout == kLayoutPlane)
-      hipLaunchKernelGGL((gn_eval_kernel<kLayoutPlane, true>), dim3(1), dim3(1024), 0, h->stream, v, h->d_scan, n,
-                         pose_map[0], pose_map[1], pose_map[2], d_out);
-    else
-      hipLaunchKernelGGL((gn_eval_kernel<kLayoutQuad, true>), dim3(1), dim3(1024), 0, h->stream, v, h->d_scan, n,
-                         pose_map[0], pose_map[1], pose_map[2], d_out);
-  } else if (h->layout == kLayoutPlane)
-    hipLaunchKernelGGL((gn_eval_kernel<kLayoutPlane>), dim3(1), dim3(1024), 0, h->stream, v, h->d_scan, n,
-                       pose_map[0], pose_map[1], pose_map[2], d_out);
-  else
-    hipLaunchKernelGGL((gn_eval_kernel<kLayoutQuad>), dim3(1), dim3(1024), 0, h->stream, v, h->d_scan, n,
-                       pose_map[0], pose_map[1], pose_map[2], d_out);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(h->h_small + 16, d_out, 12 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  for (int i = 0; i < 9; ++i) H[i] = h->h_small[16 + i];
-  for (int i = 0; i < 3; ++i) dTr[i] = h->h_small[25 + i];
-  return HSM_OK;
-}
-
-int hsm_eval_beams(hsm_ctx* h, int level, const float pose_map[3], const float* pts, int n, float* out4) {
-  if (int rc = valid_level(h, level)) return rc;
-  if (!pose_map || n < 0 || (n > 0 && (!pts || !out4))) return fail(HSM_ERR_INVALID, "bad argument");
-  if (n == 0) return HSM_OK;
-  std::lock_guard<std::mutex> lk(h->mu);
-  if (int rc = select_device(h)) return rc;
-  if (int rc = h->d_scan.reserve((size_t)n * 3, kScanGrowth)) return rc;  // pts + float4 out
-  HIP_TRY(hipMemcpyAsync(h->d_scan, pts, (size_t)n * sizeof(float2), hipMemcpyHostToDevice, h->stream));
-  float4* d_out = reinterpret_cast<float4*>(h->d_scan + (((size_t)n + 1) & ~(size_t)1));
-  const LevelView v = level_view(h->levels[level], 1.0f, 1);
-  const int grid = (n + 255) / 256;
-  if (h->layout == kLayoutPlane)
-    hipLaunchKernelGGL((gn_beam_terms_kernel<kLayoutPlane>), dim3(grid), dim3(256), 0, h->stream, v, h->d_scan, n,
-                       pose_map[0], pose_map[1], pose_map[2], d_out);
-  else
-    hipLaunchKernelGGL((gn_beam_terms_kernel<kLayoutQuad>), dim3(grid), dim3(256), 0, h->stream, v, h->d_scan, n,
-                       pose_map[0], pose_map[1], pose_map[2], d_out);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(out4, d_out, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  return HSM_OK;
-}
-
-int hsm_debug_set_coop_barrier(hsm_ctx* h, unsigned value) {
-  if (!h) return fail(HSM_ERR_INVALID, "null context");
-  std::lock_guard<std::mutex> lk(h->mu);
-  if (int rc = select_device(h)) return rc;
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  HIP_TRY(hipMemcpy(h->d_partials + 2 * 64 * 12, &value, sizeof value, hipMemcpyHostToDevice));
-  h->coop_bar_base = value;
-  return HSM_OK;
-}
-
-int hsm_debug_set_coop_mute(hsm_ctx* h, int block_plus_one) {
-  if (!h) return fail(HSM_ERR_INVALID, "null context");
-  std::lock_guard<std::mutex> lk(h->mu);
-  h->coop_mute_block = block_plus_one;
-  return HSM_OK;
-}
-
-int hsm_debug_set_schedule(hsm_ctx* h, int level, int gn_steps) {
-  if (!h) return fail(HSM_ERR_INVALID, "null context");
-  if (level >= (int)h->levels.size() || (level >= 0 && gn_steps < 1))
-    return fail(HSM_ERR_INVALID, "hsm_debug_set_schedule: level out of range or gn_steps < 1");
-  std::lock_guard<std::mutex> lk(h->mu);
-  h->sched_level = level < 0 ? -1 : level;
-  h->sched_steps = level < 0 ? 0 : gn_steps;
-  return HSM_OK;
-}
-
-int hsm_debug_batch_order(hsm_ctx* h, int batch, const float* d_begin_world, int* d_perm_out, void* stream) {
-  if (!h) return fail(HSM_ERR_INVALID, "null context");
-  if (batch < 1 || !d_begin_world || !d_perm_out) return fail(HSM_ERR_INVALID, "hsm_debug_batch_order: bad argument");
-  std::lock_guard<std::mutex> lk(h->mu);
-  if (int rc = select_device(h)) return rc;
-  return hsm_host::launch_batch_order(h, d_begin_world, batch, d_perm_out, h->batch_order == HSM_ORDER_AUTO, (hipStream_t)stream);
-}
-
-int hsm_debug_spec_stats(hsm_ctx* h, int enable, unsigned long long out[4]) {
-  if (!h) return fail(HSM_ERR_INVALID, "null context");
-  std::lock_guard<std::mutex> lk(h->mu);
-  if (int rc = select_device(h)) return rc;
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  if (out) {
-    out[0] = out[1] = out[2] = out[3] = 0;
-    if (h->d_spec_stats) HIP_TRY(hipMemcpy(out, h->d_spec_stats, sizeof(SpecStats), hipMemcpyDeviceToHost));
-  }
-  if (enable && !h->d_spec_stats) HIP_TRY(hipMalloc((void**)&h->d_spec_stats, sizeof(SpecStats)));
-  if (h->d_spec_stats) HIP_TRY(hipMemset(h->d_spec_stats, 0, sizeof(SpecStats)));
-  if (!enable && h->d_spec_stats) {
-    HIP_TRY(hipFree(h->d_spec_stats));
-    h->d_spec_stats = nullptr;
-  }
-  return HSM_OK;
-}
-
-int hsm_debug_coop_fallbacks(hsm_ctx* h) {
-  if (!h) return 0;
-  std::lock_guard<std::mutex> lk(h->mu);
-  return (int)h->coop_fallbacks;
-}
-
-int hsm_debug_marks_nonzero(hsm_ctx* h, int level, unsigned long long out[2]) {
-  if (int rc = valid_level(h, level)) return rc;
-  if (!out) return fail(HSM_ERR_INVALID, "hsm_debug_marks_nonzero: out is null");
-  std::lock_guard<std::mutex> lk(h->mu);
-  if (int rc = select_device(h)) return rc;
-  Level& L = h->levels[level];
-  unsigned long long* d = nullptr;
-  HIP_TRY(hipMalloc((void**)&d, 2 * sizeof(unsigned long long)));
-  hipError_t e = hipMemsetAsync(d, 0, 2 * sizeof(unsigned long long), h->stream);
-  if (e == hipSuccess) {
-    const size_t nb = (mark_plane_bytes(L.sx, L.sy)) / 4, nw = (L.cells() + 31) / 32 + 1;
-    hipLaunchKernelGGL(count_nonzero_words_kernel, dim3(grid_for(nb)), dim3(256), 0, h->stream,
-                       reinterpret_cast<const unsigned int*>(L.d_free_bytes), nb, d);
-    hipLaunchKernelGGL(count_nonzero_words_kernel, dim3(grid_for(nw)), dim3(256), 0, h->stream, L.d_occ_bits, nw, d + 1);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(out, d, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  (void)hipFree(d);
-  if (e != hipSuccess) return fail(HSM_ERR_HIP, "hsm_debug_marks_nonzero", e);
-  return HSM_OK;
-}
-
-int hsm_debug_set_update_serial(hsm_ctx* h, int level, unsigned serial) {
-  if (int rc = valid_level(h, level)) return rc;
-  if (serial > kSerialMax) return fail(HSM_ERR_INVALID, "hsm_debug_set_update_serial: serial exceeds the key generation field");
-  std::lock_guard<std::mutex> lk(h->mu);
-  h->levels[level].serial = serial;
-  return HSM_OK;
-}
-
-int hsm_debug_expf(hsm_ctx* h, int n, const float* x, float* out_exp, float* out_prob) {
-  if (!h || n < 0 || (n > 0 && (!x || !out_exp || !out_prob))) return fail(HSM_ERR_INVALID, "hsm_debug_expf: bad argument");
-  if (n == 0) return HSM_OK;
-  std::lock_guard<std::mutex> lk(h->mu);
-  if (int rc = select_device(h)) return rc;
-  float* d = nullptr;
-  HIP_TRY(hipMalloc((void**)&d, 3 * (size_t)n * sizeof(float)));
-  hipError_t e = hipMemcpyAsync(d, x, (size_t)n * sizeof(float), hipMemcpyHostToDevice, h->stream);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(expf_debug_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, d, n, d + n, d + 2 * (size_t)n);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(out_exp, d + n, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(out_prob, d + 2 * (size_t)n, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  (void)hipFree(d);
-  if (e != hipSuccess) return fail(HSM_ERR_HIP, "hsm_debug_expf", e);
-  return HSM_OK;
-}
-
-int hsm_debug_sincos(hsm_ctx* h, int n, const float* x, float* s, float* c) {
-  if (!h || n < 0 || (n > 0 && (!x || !s || !c))) return fail(HSM_ERR_INVALID, "hsm_debug_sincos: bad argument");
-  if (n == 0) return HSM_OK;
-  std::lock_guard<std::mutex> lk(h->mu);
-  if (int rc = select_device(h)) return rc;
-  float* d = nullptr;
-  HIP_TRY(hipMalloc((void**)&d, 3 * (size_t)n * sizeof(float)));
-  hipError_t e = hipMemcpyAsync(d, x, (size_t)n * sizeof(float), hipMemcpyHostToDevice, h->stream);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(sincos_debug_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, d, n, d + n, d + 2 * (size_t)n);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(s, d + n, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(c, d + 2 * (size_t)n, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  (void)hipFree(d);
-  if (e != hipSuccess) return fail(HSM_ERR_HIP, "hsm_debug_sincos", e);
-  return HSM_OK;
-}
-
-}  // extern "C"

@@ -1,6 +1,10 @@
 // hsm_ctx.h -- the context of libhector_mi355.so as its translation units see it: the pyramid level, hsm_ctx, and the launch
 // entry points the units implement for each other.  Internal (not installed): the public boundary is include/hector_mi355/capi.h.
-//   hector_mi355.hip        host runtime + C ABI, update / node-row / probe kernels, the one-workgroup-per-scan matcher forms
+//   hector_mi355.hip        host runtime + C ABI of everything that is timed: matches, updates, scan loops, ingestion, occupancy
+//                           exports; update / node-row kernels, the one-workgroup-per-scan matcher forms
+//   probes.hip              the host-array probes (likelihood, covariance, ray distances, Hessian), level downloads and uploads,
+//                           the hsm_debug_* test hooks, and the kernels only these launch (probe_kernels.h)
+//   group.hip               the multi-GPU group (hsm_group_*, hsm_shard_bounds): host code only, librccl opened on demand
 //   match_exact_cached.hip  the exact-order texel-cache batch forms (gn_match_exact.h: the headline kernel and its chain-wavefront forms)
 //   match_teams.hip         the team forms (gn_match_kernel, 1..16 wavefronts per scan) and the fast texel-cache forms
 //   pose_exchange.hip       the device-side gather of sharded results
@@ -9,6 +13,7 @@
 
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "gn_match.h"
@@ -19,6 +24,7 @@
 
 namespace hsm {
 struct BeamRec;  // map_update.h (its kernels are not templates: only hector_mi355.hip includes that header)
+struct LevelRW;  // map_cells.h
 struct UpdateBatch;
 struct GateState;
 }
@@ -63,6 +69,11 @@ struct Level {
   int tiles_x() const { return (sx + 3) / 4; }
   int quad_texels() const { return sx * sy; }
 };
+
+inline void affine_apply_host(const Affine2& a, float x, float y, float& ox, float& oy) {
+  ox = a.t0 + (a.l00 * x + a.l01 * y);
+  oy = a.t1 + (a.l10 * x + a.l11 * y);
+}
 
 // Teardown never stops at a failing call (everything else still has to be released), but it must not swallow one either: HIP
 // keeps the last failure per thread, and the next hipGetLastError() of an unrelated call -- the launch check of the next
@@ -347,6 +358,36 @@ struct hsm_ctx {
 namespace hsm_host {
 
 using hsm_plan::MatchPlan;
+
+// hector_mi355.hip, for probes.hip and group.hip: the views of a level, the launch arithmetic, and what an entry does before it
+// reads or rewrites a level on the host (the definitions carry the comments)
+int valid_level(const hsm_ctx* h, int level);
+int select_device(const hsm_ctx* h);
+bool wants_exact(const hsm_ctx* h);
+int grid_for(size_t n, int block = 256);
+LevelRW level_rw(const Level& L);
+LevelView level_view(const Level& L, float pt_scale, int gn_steps);
+int rebuild_probability(hsm_ctx* h, Level& L);
+void whole_level_changed(Level& L, bool mirror = true);
+int order_after_foreign_match(hsm_ctx* h);
+int merge_device_boxes(hsm_ctx* h);
+int fold_gate_counters(hsm_ctx* h, GateState* state = nullptr);
+int match_batch_device_nolock(hsm_ctx* h, int batch, const float* d_begin_world, const float* d_pts_xy, const int* d_scan_offsets,
+                              int shared_n, float* d_out_pose, float* d_out_cov, void* stream, int n_bound = 0,
+                              const ExchangeFused* xp = nullptr);
+
+// f(layout, exact) with the context's texel layout and summation order as types (std::integral_constant<int, kLayout...>,
+// std::bool_constant): a generic lambda launches `kernel<layout(), exact()>` and the four sampler forms need no ladder.  A kernel
+// that samples in one order only ignores the second argument.
+template <class F>
+void with_sampler_form(const hsm_ctx* h, F&& f) {
+  const bool exact = wants_exact(h);
+  if (h->layout == kLayoutPlane) {
+    if (exact) f(std::integral_constant<int, kLayoutPlane>{}, std::true_type{}); else f(std::integral_constant<int, kLayoutPlane>{}, std::false_type{});
+  } else {
+    if (exact) f(std::integral_constant<int, kLayoutQuad>{}, std::true_type{}); else f(std::integral_constant<int, kLayoutQuad>{}, std::false_type{});
+  }
+}
 
 // Which form a launch takes is decided once, in match_plan.h (plan_match), by launch_match of hector_mi355.hip, which also
 // keeps the launch record; the other two units only map a plan to their instantiations and launch it.

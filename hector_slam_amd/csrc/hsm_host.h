@@ -7,6 +7,8 @@ namespace hsm_host {
 
 // records "<what>[: <hip error text>]" as this thread's hsm_last_error() and returns `code`
 int fail(int code, const char* what, hipError_t e = hipSuccess);
+// `text`, whole, as this thread's hsm_last_error()
+void set_error_text(const char* text);
 
 }  // namespace hsm_host
 

@@ -36,74 +36,11 @@
 #include <hip/hip_runtime.h>
 
 #include "gn_match.h"
+#include "map_cells.h"
 #include "occupancy_rows.h"
 #include "update_gate.h"
 
 namespace hsm {
-
-// read-write view of one level for the update path
-struct LevelRW {
-  float* logodds;         // LogOddsCell::logOddsVal plane
-  int* update_index;      // LogOddsCell::updateIndex plane
-  float* prob;            // p = e^l / (e^l + 1)
-  float4* quad;           // {P(x,y), P(x+1,y), P(x,y+1), P(x+1,y+1)}
-  unsigned int* key_free; // first free-touching beam of the current scan
-  unsigned int* key_occ;  // first end-cell beam of the current scan
-  unsigned int* occ_bits; // 1 bit per cell: "some beam of the current scan ends here" (set in pass 1a, cleared in pass 2)
-  unsigned char* free_bytes; // dense scans: 1 byte per cell "some beam of the current scan crosses this cell", in tiles of 16 x 8
-                             // cells (index = mark_index: a tile is one 128-byte line); set by update_mark_free_dense_kernel,
-                             // cleared by the dense apply pass
-  int sx, sy;
-  int tiles_x, quad_texels;  // tiled texel plane geometry (gn_match.h quad_index)
-  int kf_tiles_x;            // free-key tiles per row = key_free_tiles_x(sx): ceil(sx / 64) * 8   (key_free_index)
-};
-
-// The free-key plane is stored in 8x4-cell tiles (= one 128-byte line).  The line walk (mark_free_block)
-// writes one 4-byte key per visited cell: row major, a y-major beam touches a new cache line every step and an
-// x-major one every 32 steps; tiled, both touch a new line every 4..8 steps, and the lanes of a wave (64
-// consecutive steps of one beam) share lines either way.
-// tiles per tile row, padded to whole 64-cell BLOCKS (8 tiles): the dense apply pass owns the marks of a 64 x 4-cell block as
-// 256 CONTIGUOUS bytes, so the last block of a row must not run into the next tile row -- with the padding the dense form
-// works for every map width (round 4; until then rows had to be a multiple of 64 cells)
-__host__ __device__ __forceinline__ int key_free_tiles_x(int sx) { return ((sx + 63) / 64) * 8; }
-__host__ __device__ __forceinline__ size_t key_free_cells(int sx, int sy) {
-  return (size_t)key_free_tiles_x(sx) * (size_t)((sy + 3) / 4) * 32u;
-}
-__device__ __forceinline__ unsigned int key_free_index(const LevelRW& L, unsigned int x, unsigned int y) {
-  return ((((y >> 2) * (unsigned int)L.kf_tiles_x) + (x >> 3)) << 5) | ((y & 3u) << 3) | (x & 7u);
-}
-
-// The mark BYTES of the dense form (free_bytes): tiles of 16 x 8 cells = one 128-byte line each.  The 64 steps of a line-walk
-// iteration cross about (dx / 16 + dy / 8 + 1) lines -- ~10 averaged over the beam directions of a 360-degree scan -- and the
-// line walk is bound by exactly these scattered byte accesses (profiles/r04/README.md 5).  The apply pass owns 32 x 8-cell
-// blocks (two tiles = 256 contiguous mark bytes, its plane accesses two 128-byte row segments per wavefront).  (Measured
-// against the free-key plane's 8 x 4 tiling, where a line of bytes is 32 x 4 cells and an iteration crosses ~14.5 lines:
-// profiles/r04/README.md 20.)
-__host__ __device__ __forceinline__ int mark_tiles_x(int sx) { return ((sx + 31) / 32) * 2; }  // 16-cell tiles per row, whole 32-cell blocks
-__host__ __device__ __forceinline__ size_t mark_bytes(int sx, int sy) {
-  return (size_t)mark_tiles_x(sx) * (size_t)((sy + 7) / 8) * 128u;
-}
-// One byte per 16 x 8 mark TILE behind the mark bytes: "a beam of the current scan ends in this tile" (set by the end-cell pass,
-// cleared by the apply pass).  Without it the line walk has to read every mark byte before storing to it -- to learn whether a
-// beam ends in the cell (then the keyed atomicMax decides the revert artefact), and to skip marks already set; that load, ~10
-// lines of a 67 MB plane per iteration, was a third of the walk.  So it reads the TILE's byte -- a 128 x smaller, cache-resident
-// map, 1-4 lines per iteration -- and only in the ~1/6 of the tiles where it is set the cell's own byte; everywhere else it
-// stores its mark unread (an already set mark is stored again: same value).
-// configs[4]: line walk 57.5 -> 50.0 us, update 0.135 -> 0.127 ms (profiles/r04/README.md 21).
-__host__ __device__ __forceinline__ size_t mark_tile_end_offset(int sx, int sy) { return mark_bytes(sx, sy) + 256; }
-__host__ __device__ __forceinline__ size_t mark_plane_bytes(int sx, int sy) {
-  return mark_bytes(sx, sy) + 256 + ((mark_bytes(sx, sy) / 128 + 3) & ~(size_t)3) + 256;
-}
-__device__ __forceinline__ unsigned int mark_index(const LevelRW& L, unsigned int x, unsigned int y) {
-  return ((((y >> 3) * (unsigned int)mark_tiles_x(L.sx)) + (x >> 4)) << 7) | ((y & 7u) << 4) | (x & 15u);
-}
-
-// Key = (generation of the scan << kBeamBits) | (kBeamMask - beam index): atomicMax keeps the newest scan and, within
-// it, the LOWEST beam index.  20 bits of beam index (scans of up to 1 048 575 beams; the reference has no limit, and
-// neither has any sensor), 12 bits of generation: the key planes are cleared once every 4095 updates of a level.
-constexpr unsigned int kBeamBits = 20;
-constexpr unsigned int kBeamMask = (1u << kBeamBits) - 1u;
-constexpr unsigned int kSerialMax = (1u << (32 - kBeamBits)) - 1u;
 
 // What the dense line walk needs to know about ONE beam on ONE level -- the result of beam_line() and of the two divisions
 // of its per-64-steps increment.  Round 3's walk derived all of this per WAVEFRONT (one beam each, 64 lanes computing the same
@@ -131,28 +68,11 @@ struct UpdateParams {
   struct BeamRec* recs;     // dense scans: one record per beam of this level (update_mark_occ_dense_kernel -> the line walk)
 };
 
-// GridMapLogOddsFunctions::getGridProbability (GridMapLogOdds.h:163-166): exp(float) is glibc's expf
-// there; libm_exact.h reproduces it bit for bit
-__device__ __forceinline__ float grid_probability(float log_odds) {
-  const float odds = libm::expf_glibc(log_odds);
-  return odds / (odds + 1.0f);
-}
-
 // All levels of one updateByScan in ONE launch per pass: blockIdx.y selects the level (the levels are
 // independent maps, so they run concurrently and the small coarse levels hide behind level 0).
 struct UpdateBatch {
   UpdateParams lv[kMaxLevels];
   int nlev;
-};
-
-struct BeamLine {
-  bool valid;
-  int x1, y1;
-  unsigned int abs_da, abs_db;
-  int offset_a, offset_b;
-  unsigned int e0;
-  unsigned int start;
-  bool x_major;  // the major (per-step) axis is x
 };
 
 // geometry of beam i exactly as updateByScan / updateLineBresenhami derive it
@@ -195,13 +115,6 @@ __device__ __forceinline__ BeamLine beam_line(const UpdateParams& P, int i) {
   }
   b.e0 = b.abs_da / 2;
   return b;
-}
-
-// cell visited at Bresenham step i (0 = start cell), closed form of bresenham2D (:243-260):
-// after i major steps the error accumulator has crossed abs_da floor((e0 + i*db)/da) times.
-__device__ __forceinline__ unsigned int line_cell(const BeamLine& b, unsigned int i) {
-  const unsigned int minor = (b.e0 + i * b.abs_db) / b.abs_da;
-  return b.start + (unsigned int)((int)i * b.offset_a) + (unsigned int)((int)minor * b.offset_b);
 }
 
 // pass 1a: end cells.  One thread per beam: atomicMax leaves the FIRST beam that ends in a cell.
@@ -1076,20 +989,6 @@ __global__ void update_boxes_clear_kernel(int* boxes, int n_boxes) {
   if (i < 4 * n_boxes) boxes[i] = (i & 3) < 2 ? kBoxEmptyLo : kBoxEmptyHi;
 }
 
-// test hook (hsm_debug_marks_nonzero): the dense update's byte map and the keyed update's end-cell bitmap must be ALL ZERO
-// between updates (each apply pass clears what its mark passes set; map_update.h "dense scans"): count the non-zero words
-__global__ void __launch_bounds__(256) count_nonzero_words_kernel(const unsigned int* __restrict__ words, size_t n,
-                                                                  unsigned long long* __restrict__ out) {
-  unsigned int local = 0;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-    local += words[i] != 0u ? 1u : 0u;
-  const unsigned long long m = __ballot(local != 0u);
-  if (m == 0ull) return;
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) local += (unsigned int)__shfl_down((int)local, d);
-  if ((threadIdx.x & 63) == 0) atomicAdd(out, (unsigned long long)local);
-}
-
 // ---- whole-plane maintenance (create / reset / upload) ------------------------------
 __global__ void fill_level_kernel(LevelRW L, float logodds, int update_index) {
   const size_t n = (size_t)L.sx * L.sy;
@@ -1105,16 +1004,6 @@ __global__ void fill_level_kernel(LevelRW L, float logodds, int update_index) {
          i += (size_t)gridDim.x * blockDim.x) {
       L.quad[i] = make_float4(p, p, p, p);
     }
-  }
-}
-
-// rectangle (x0,y0,w,h) of the two SoA planes -> the reference's AoS LogOddsCell {float, int}
-__global__ void pack_cells_kernel(LevelRW L, int x0, int y0, int w, int h, int2* __restrict__ out) {
-  const size_t n = (size_t)w * h;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const int x = x0 + (int)(i % (size_t)w), y = y0 + (int)(i / (size_t)w);
-    const size_t c = (size_t)y * L.sx + x;
-    out[i] = make_int2(__float_as_int(L.logodds[c]), L.update_index[c]);
   }
 }
 
@@ -1225,63 +1114,6 @@ __global__ void __launch_bounds__(256) occupancy_box_kernel(const float* __restr
       for (int i = 0; i < r.tail_n; ++i) out[r.tail0 + i] = occupancy_value(logodds[r.tail0 + i]);
     }
   }
-}
-
-// f4: DistanceMeasurementProvider::getDist (hector_map_tools/.../HectorMapTools.h:133-234) for a batch of
-// rays, straight on the log-odds plane (a cell of the published grid is 100 <=> logOdds > 0).  One
-// wavefront per ray: lane k tests Bresenham steps k, k+64, ... through the closed form of the error
-// accumulator, a ballot finds the FIRST occupied step, and the search stops at that chunk -- the
-// sequential early-exit walk of the reference without walking sequentially.
-struct RayQueryParams {
-  const float* logodds;
-  int sx, sy;
-  float origin_x, origin_y, scale, inv_scale;  // CoordinateTransformer (:58-98)
-  const float2* begin_world;
-  const float2* end_world;
-  int n;
-  float* out_dist;
-  float2* out_hit;
-};
-
-__global__ void __launch_bounds__(256) ray_distance_kernel(const RayQueryParams P) {
-  const int lane = threadIdx.x & 63;
-  const int r = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  if (r >= P.n) return;
-  const float2 bw = P.begin_world[r], ew = P.end_world[r];
-  // getC2Coords(...).cast<int>(): ((world - origo) * inv_scale), truncated
-  const int x0 = (int)((bw.x - P.origin_x) * P.inv_scale), y0 = (int)((bw.y - P.origin_y) * P.inv_scale);
-  const int x1 = (int)((ew.x - P.origin_x) * P.inv_scale), y1 = (int)((ew.y - P.origin_y) * P.inv_scale);
-  float dist = -1.0f;
-  if (!((x0 < 0) || (x0 >= P.sx) || (y0 < 0) || (y0 >= P.sy)) && !((x1 < 0) || (x1 >= P.sx) || (y1 < 0) || (y1 >= P.sy))) {
-    const int dx = x1 - x0, dy = y1 - y0;
-    const unsigned int abs_dx = (unsigned int)(dx < 0 ? -dx : dx), abs_dy = (unsigned int)(dy < 0 ? -dy : dy);
-    const int offset_dx = dx > 0 ? 1 : -1;
-    const int offset_dy = (dy > 0 ? 1 : -1) * P.sx;
-    BeamLine b;
-    b.start = (unsigned int)(y0 * P.sx + x0);
-    if (abs_dx >= abs_dy) {
-      b.abs_da = abs_dx; b.abs_db = abs_dy; b.offset_a = offset_dx; b.offset_b = offset_dy;
-    } else {
-      b.abs_da = abs_dy; b.abs_db = abs_dx; b.offset_a = offset_dy; b.offset_b = offset_dx;
-    }
-    b.e0 = b.abs_da / 2;
-    const unsigned int end = b.abs_da < 5000u ? b.abs_da : 5000u;  // bresenham2D(..., max_length = 5000)
-    for (unsigned int i0 = 0; i0 < end; i0 += 64) {
-      const unsigned int i = i0 + lane;
-      const bool occ = i < end && P.logodds[line_cell(b, i)] > 0.0f;  // data[offset] == 100
-      const unsigned long long m = __ballot(occ);
-      if (m) {
-        const unsigned int ih = i0 + (unsigned int)__ffsll((long long)m) - 1u;
-        const unsigned int c = line_cell(b, ih);
-        const int ex = (int)(c % (unsigned int)P.sx), ey = (int)(c / (unsigned int)P.sx);
-        const float fx = (float)(x0 - ex), fy = (float)(y0 - ey);
-        dist = (float)(int)sqrtf(fx * fx + fy * fy);  // int distMap = (begin - end).cast<float>().norm()
-        if (lane == 0) P.out_hit[r] = make_float2(P.origin_x + ((float)ex * P.scale), P.origin_y + ((float)ey * P.scale));
-        break;
-      }
-    }
-  }
-  if (lane == 0) P.out_dist[r] = P.scale * dist;  // getC1Scale
 }
 
 // rosLaserScanToDataContainer (HectorMappingRos.cpp:483-507).  trig[i] = (cosf(angle_i), sinf(angle_i))
@@ -1564,14 +1396,6 @@ __global__ void __launch_bounds__(256) ranges_tf_compact_kernel(const RangesTfPa
     if (keep) out[pos + __popcll(m & below)] = e;
     pos += __popcll(m);
   }
-}
-
-// device expf / getGridProbability sweep for the parity tests
-__global__ void expf_debug_kernel(const float* __restrict__ x, int n, float* __restrict__ e, float* __restrict__ p) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  e[i] = libm::expf_glibc(x[i]);
-  p[i] = grid_probability(x[i]);
 }
 
 __global__ void rebuild_prob_kernel(LevelRW L) {

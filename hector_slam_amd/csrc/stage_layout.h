@@ -158,6 +158,56 @@ inline RangesStage ranges_stage(int batch, int n, size_t ws_bytes, const float* 
   return s;
 }
 
+// hsm_likelihood_states / hsm_residual_states (d_batch): end points[n] | states[batch * 3] | likelihoods[batch] | residuals[batch]
+struct ScoreStatesStage {
+  StagePlan plan;
+  size_t pts, states, lh, res;
+};
+
+inline ScoreStatesStage score_states_stage(int batch, int n, const float* states, const float* pts, float* out_lh, float* out_res) {
+  ScoreStatesStage s;
+  s.pts = s.plan.add((size_t)n * 2 * sizeof(float), pts);
+  s.states = s.plan.add((size_t)batch * 3 * sizeof(float), states);
+  s.lh = s.plan.add((size_t)batch * sizeof(float), nullptr, out_lh);
+  s.res = s.plan.add((size_t)batch * sizeof(float), nullptr, out_res);
+  return s;
+}
+
+// hsm_covariance_for_poses (d_batch): end points[n] | poses[batch * 3] | map-frame covariances[batch * 9] | world-frame
+// covariances[batch * 9] | the seven sigma-point likelihoods[batch * 7]
+struct PoseCovarianceStage {
+  StagePlan plan;
+  size_t pts, poses, cov_map, cov_world, lh7;
+};
+
+inline PoseCovarianceStage pose_covariance_stage(int batch, int n, const float* poses, const float* pts, float* out_cov_map,
+                                                 float* out_cov_world, float* out_lh7) {
+  PoseCovarianceStage s;
+  s.pts = s.plan.add((size_t)n * 2 * sizeof(float), pts);
+  s.poses = s.plan.add((size_t)batch * 3 * sizeof(float), poses);
+  s.cov_map = s.plan.add((size_t)batch * 9 * sizeof(float), nullptr, out_cov_map);
+  s.cov_world = s.plan.add((size_t)batch * 9 * sizeof(float), nullptr, out_cov_world);
+  s.lh7 = s.plan.add((size_t)batch * 7 * sizeof(float), nullptr, out_lh7);
+  return s;
+}
+
+// hsm_ray_distances (d_batch): ray begins[n * 2] | ray ends[n * 2] | distances[n] | hit points[n * 2].  The hit points go in and
+// out: a ray without a hit leaves the caller's values.
+struct RayDistancesStage {
+  StagePlan plan;
+  size_t begin, end, dist, hit;
+};
+
+inline RayDistancesStage ray_distances_stage(int n, const float* begin, const float* end, float* out_dist, float* out_hit) {
+  const size_t n2 = (size_t)n * 2 * sizeof(float);
+  RayDistancesStage s;
+  s.begin = s.plan.add(n2, begin);
+  s.end = s.plan.add(n2, end);
+  s.dist = s.plan.add((size_t)n * sizeof(float), nullptr, out_dist);
+  s.hit = s.plan.add(n2, out_hit, out_hit);
+  return s;
+}
+
 // hsm_match_batch_ranges_tf (d_rbatch): transforms[batch or 1][12] | start poses | poses | covariances | counts | origos |
 // offsets[batch + 1] | raw ranges | endpoints[max(batch * n, 1)]
 struct RangesTfStage {

@@ -1,11 +1,13 @@
 // stage_layout_check.cpp -- hector_slam_amd/csrc/stage_layout.h against the sums the host runtime wrote out by hand before
 // the header existed: the workspace of hsm_match_batch_ranges_device, the staging blocks of hsm_match_batch /
 // hsm_match_score_batch (device and pinned form; with and without score, residual, ranking and its optional arrays) and the
-// growth rule of every grow-on-demand buffer; and the staging plans of the four host-array entries built on StagePlan
-// (hsm_update_by_scans, hsm_match_batch_ranges, hsm_match_batch_ranges_tf, hsm_slam_ranges_tf) against each entry's layout written
-// out term by term, with the copies a plan asks for.  Every case is compared exactly; prints one JSON line, exits 1 on a mismatch.
+// growth rule of every grow-on-demand buffer; and the staging plans of the host-array entries built on StagePlan
+// (hsm_update_by_scans, hsm_match_batch_ranges, hsm_match_batch_ranges_tf, hsm_slam_ranges_tf, and the probes hsm_likelihood_states /
+// hsm_residual_states, hsm_covariance_for_poses, hsm_ray_distances) against each entry's layout written out term by term, with the
+// copies a plan asks for.  Every case is compared exactly; prints one JSON line, exits 1 on a mismatch.
 #include <stdio.h>
 
+#include <utility>
 #include <vector>
 
 #include "stage_layout.h"
@@ -256,6 +258,64 @@ static void check_slam_ranges_tf_stage(int count, int n, int flags) {
                "slam stage copies", count, n, flags);
 }
 
+// flags: 1 out_lh, 2 out_residual, 4 pts
+static void check_score_states_stage(int batch, int n, int flags) {
+  float lh[1], res[1];
+  float* out_lh = flags & 1 ? lh : nullptr;
+  float* out_res = flags & 2 ? res : nullptr;
+  const float* pts = flags & 4 ? kF : nullptr;
+  const size_t b_pts = (size_t)n * 2 * sizeof(float), b_states = (size_t)batch * 3 * sizeof(float), b_one = (size_t)batch * sizeof(float);
+  const ScoreStatesStage s = score_states_stage(batch, n, kF, pts, out_lh, out_res);
+  same(s.pts, 0, "score stage pts", batch, n, flags);
+  same(s.states, al(b_pts), "score stage states", batch, n, flags);
+  same(s.lh, al(b_pts) + al(b_states), "score stage likelihood", batch, n, flags);
+  same(s.res, al(b_pts) + al(b_states) + al(b_one), "score stage residual", batch, n, flags);
+  same(s.plan.total(), al(b_pts) + al(b_states) + al(b_one) + al(b_one), "score stage total", batch, n, flags);
+  check_copies(s.plan, {{0, b_pts, pts, nullptr}, {al(b_pts), b_states, kF, nullptr}, {al(b_pts) + al(b_states), b_one, nullptr, out_lh},
+                        {al(b_pts) + al(b_states) + al(b_one), b_one, nullptr, out_res}},
+               "score stage copies", batch, n, flags);
+}
+
+// flags: 1 out_cov_map, 2 out_cov_world, 4 out_lh7, 8 pts
+static void check_pose_covariance_stage(int batch, int n, int flags) {
+  float cm[1], cw[1], l7[1];
+  float* out_map = flags & 1 ? cm : nullptr;
+  float* out_world = flags & 2 ? cw : nullptr;
+  float* out_lh7 = flags & 4 ? l7 : nullptr;
+  const float* pts = flags & 8 ? kF : nullptr;
+  const size_t b_pts = (size_t)n * 2 * sizeof(float), b_poses = (size_t)batch * 3 * sizeof(float);
+  const size_t b_cov = (size_t)batch * 9 * sizeof(float), b_lh7 = (size_t)batch * 7 * sizeof(float);
+  const size_t o_poses = al(b_pts), o_map = al(b_pts) + al(b_poses), o_world = al(b_pts) + al(b_poses) + al(b_cov);
+  const size_t o_lh7 = al(b_pts) + al(b_poses) + al(b_cov) + al(b_cov);
+  const PoseCovarianceStage s = pose_covariance_stage(batch, n, kF, pts, out_map, out_world, out_lh7);
+  same(s.pts, 0, "covariance stage pts", batch, n, flags);
+  same(s.poses, o_poses, "covariance stage poses", batch, n, flags);
+  same(s.cov_map, o_map, "covariance stage map frame", batch, n, flags);
+  same(s.cov_world, o_world, "covariance stage world frame", batch, n, flags);
+  same(s.lh7, o_lh7, "covariance stage likelihoods", batch, n, flags);
+  same(s.plan.total(), o_lh7 + al(b_lh7), "covariance stage total", batch, n, flags);
+  check_copies(s.plan, {{0, b_pts, pts, nullptr}, {o_poses, b_poses, kF, nullptr}, {o_map, b_cov, nullptr, out_map},
+                        {o_world, b_cov, nullptr, out_world}, {o_lh7, b_lh7, nullptr, out_lh7}},
+               "covariance stage copies", batch, n, flags);
+}
+
+// flags: 1 out_hit (in and out)
+static void check_ray_distances_stage(int n, int flags) {
+  float dist[1], hit[1];
+  float* out_hit = flags & 1 ? hit : nullptr;
+  const size_t b2 = (size_t)n * 2 * sizeof(float), b1 = (size_t)n * sizeof(float);
+  const RayDistancesStage s = ray_distances_stage(n, kF, kF + 0, dist, out_hit);
+  same(s.begin, 0, "ray stage begin", n, flags, 0);
+  same(s.end, al(b2), "ray stage end", n, flags, 0);
+  same(s.dist, al(b2) + al(b2), "ray stage distances", n, flags, 0);
+  same(s.hit, al(b2) + al(b2) + al(b1), "ray stage hits", n, flags, 0);
+  same(s.plan.total(), al(b2) + al(b2) + al(b1) + al(b2), "ray stage total", n, flags, 0);
+  // (begin and end are one host array here: two copies in of it, told apart by their offsets)
+  check_copies(s.plan, {{0, b2, kF, nullptr}, {al(b2), b2, kF, nullptr}, {al(b2) + al(b2), b1, nullptr, dist},
+                        {al(b2) + al(b2) + al(b1), b2, out_hit, out_hit}},
+               "ray stage copies", n, flags, 0);
+}
+
 int main() {
   // sizes around the 256-byte multiples of every element size in play (4, 8, 12, 36 bytes), and the ends of the ranges
   std::vector<long long> sizes = {0, 1, 2, 3, 5, 7, 21, 22, 31, 32, 33, 63, 64, 65, 85, 86, 127, 128, 129, 255, 256, 257, 1023, 1024,
@@ -309,6 +369,13 @@ int main() {
       for (int flags = 0; flags < 512; ++flags) check_slam_ranges_tf_stage((int)cnt, (int)n, flags);
     }
   }
+  // the probes' plans: empty, one element, odd sizes below a 256-byte multiple, and sizes that cross one in every region
+  for (const auto& bn : {std::pair<int, int>{0, 0}, {1, 1}, {3, 7}, {65, 129}}) {
+    for (int flags = 0; flags < 8; ++flags) check_score_states_stage(bn.first, bn.second, flags);
+    for (int flags = 0; flags < 16; ++flags) check_pose_covariance_stage(bn.first, bn.second, flags);
+  }
+  for (int n : {0, 1, 65})
+    for (int flags = 0; flags < 2; ++flags) check_ray_distances_stage(n, flags);
   printf("{\"cases\": %lld, \"mismatches\": %lld}\n", cases, mismatches);
   return mismatches ? 1 : 0;
 }

@@ -7,6 +7,10 @@ check wins where two apply, and the entry name in every text, are what such a re
 Arguments are symbolic so that no address reaches the golden file: "D" a device buffer, "D+4" the same at an address 4 mod 8,
 "D+1" at an odd one, "H" a host array, "S" the test's stream, None a null pointer.  No pointer is ever dereferenced: every case
 refuses first.  Cases with capture=True run while "S" is being captured into a graph.
+
+The probes, downloads, test hooks and the device group joined the list before they moved out of the core translation unit (recorded
+again, all cases, from the commit before that move).  Their first argument is the context unless FIRST says otherwise; the override
+`ctx=None` passes a null context (or group) instead.
 """
 INT_MAX = 2**31 - 1
 MAX_BEAMS = 1048575  # HSM_MAX_UPDATE_BEAMS
@@ -54,6 +58,55 @@ ENTRIES = {
                            ("out_applied", None), ("out_counts", None), ("out_origo", None)],
 }
 
+# the entries that moved to probes.hip and group.hip
+_STATES = [("level", 0), ("batch", COUNT), ("states", "H"), ("pts", "H"), ("n", N)]
+_POSE_PTS = [("level", 0), ("pose", "H"), ("pts", "H"), ("n", N)]
+MOVED = {
+    "hsm_likelihood_states": _STATES + [("out", "H")],
+    "hsm_residual_states": _STATES + [("out", "H")],
+    "hsm_covariance_for_poses": _STATES + [("out_cov_map", "H"), ("out_cov_world", None), ("out_lh7", None)],
+    "hsm_ray_distances": [("level", 0), ("origin_x", 0.0), ("origin_y", 0.0), ("resolution", 0.05), ("n", N), ("begin", "H"),
+                          ("end", "H"), ("out_dist", "H"), ("out_hit", None)],
+    "hsm_hessian_derivs": _POSE_PTS + [("H", "H"), ("dTr", "H")],
+    "hsm_eval_beams": _POSE_PTS + [("out4", "H")],
+    "hsm_level_info": [("level", 0), ("sx", None), ("sy", None), ("cell", None), ("scale", None)],
+    "hsm_map_coords_pose": [("level", 0), ("w", "H"), ("m", "H")],
+    "hsm_world_coords_pose": [("level", 0), ("m", "H"), ("w", "H")],
+    "hsm_update_index": [("level", 0)],
+    "hsm_download_level": [("level", 0), ("logodds", None), ("update_index", None)],
+    "hsm_upload_level": [("level", 0), ("logodds", None), ("update_index", None)],
+    "hsm_download_rows": [("level", 0), ("y0", 0), ("y1", 1), ("rows", "H")],
+    "hsm_download_cells": [("level", 0), ("x0", 0), ("y0", 0), ("x1", 1), ("y1", 1), ("dst", "H"), ("pitch", 2)],
+    "hsm_last_update_bbox": [("level", 0), ("bbox", "H")],
+    "hsm_take_dirty_bbox": [("level", 0), ("bbox", "H")],
+    "hsm_download_prob": [("level", 0), ("prob", "H")],
+    "hsm_debug_set_coop_barrier": [("value", 0)],
+    "hsm_debug_set_coop_mute": [("block_plus_one", 0)],
+    "hsm_debug_set_schedule": [("level", -1), ("gn_steps", 0)],
+    "hsm_debug_batch_order": [("batch", COUNT), ("begin", "D"), ("perm", "D"), ("stream", "S")],
+    "hsm_debug_spec_stats": [("enable", 0), ("out", None)],
+    "hsm_debug_marks_nonzero": [("level", 0), ("out", "H")],
+    "hsm_debug_set_update_serial": [("level", 0), ("serial", 1)],
+    "hsm_debug_expf": [("n", N), ("x", "H"), ("out_a", "H"), ("out_b", "H")],
+    "hsm_debug_sincos": [("n", N), ("x", "H"), ("out_a", "H"), ("out_b", "H")],
+    "hsm_group_create": [("map_resolution", 0.05), ("size_x", 64), ("size_y", 64), ("levels", 1), ("start_x", 0.5), ("start_y", 0.5),
+                         ("devices", "H_ZERO_INT"), ("n_devices", 1), ("out", "H")],
+    "hsm_group_set_gather": [("mode", 0)],
+    "hsm_group_debug_force_p2p": [("on", 0)],
+    "hsm_group_set_update_factors": [("free", 0.4), ("occupied", 0.9)],
+    "hsm_group_process_scan": [("hint", "H"), ("pts", "H"), ("n", N), ("origo", None), ("do_update", 0), ("out_pose", "H"), ("cov", "H")],
+    "hsm_group_match_batch_device": [("counts", "H_ONE_INT"), ("begin", "H_PTR_D"), ("pts", "H_PTR_D"), ("offsets", None), ("shared_n", N),
+                                     ("root", 0), ("out_pose_all", "D"), ("out_cov_all", None)],
+    "hsm_group_synchronize": [],
+    "hsm_group_match_batch": [("batch", COUNT), ("begin", "H"), ("pts", "H"), ("offsets", None), ("shared_n", N), ("out_pose", "H"),
+                              ("out_cov", None)],
+    "hsm_shard_bounds": [("total", 10), ("rank", 0), ("world", 2), ("begin", "H"), ("end", "H")],
+}
+# what goes in front of an entry's parameters: the context (every entry not listed), the runner's one-device group, or nothing
+FIRST = {e: "group" for e in MOVED if e.startswith("hsm_group_")}
+FIRST.update({"hsm_group_create": None, "hsm_shard_bounds": None})
+_LEVELLED = [e for e, params in MOVED.items() if params and params[0][0] == "level" and e != "hsm_debug_set_schedule"]
+
 _UPDATES = [e for e in ENTRIES if e.startswith("hsm_update_by_scans_device")]
 _SLAM_SCANS = ["hsm_slam_scans_device", "hsm_slam_scans_device_origos"]
 _RANGES = ["hsm_match_batch_ranges", "hsm_match_batch_ranges_device"]
@@ -74,7 +127,8 @@ def cases():
         out.append((f"{entry}:{what}", entry, over, capture))
 
     for e in ENTRIES:
-        add("negative count", e, **{_count_name(e): -1})
+        if e not in MOVED:
+            add("negative count", e, **{_count_name(e): -1})
     for e in _UPDATES + _SLAM_SCANS:
         add("negative max_beams", e, max_beams=-5)
     for e in _RANGES + _TF_ENTRIES:
@@ -119,8 +173,87 @@ def cases():
         add("unseen geometry under capture", e, capture=True, **_UNSEEN)
     add("too many beams under capture", "hsm_update_by_scans_device", capture=True, offsets=None, shared_n=MAX_BEAMS + 1)
     add("short workspace under capture", "hsm_slam_ranges_tf_device", capture=True, workspace_bytes="WS_SLAM-1")
+    moved_cases(add)
     assert len({c[0] for c in out}) == len(out)
     return out
+
+
+def moved_cases(add):
+    """the refusals of the entries in MOVED: a null context, a level out of range, negative counts, each required pointer null"""
+    for e in MOVED:
+        if FIRST.get(e, "ctx"):
+            add("null context", e, ctx=None)
+    for e in _LEVELLED:
+        add("level below zero", e, level=-1)
+        add("level past the pyramid", e, level=2)
+    for e in ["hsm_likelihood_states", "hsm_residual_states", "hsm_covariance_for_poses"]:
+        add("negative batch", e, batch=-1)
+        add("negative n", e, n=-1)
+        add("null states", e, states=None)
+        add("null pts", e, pts=None)
+        add("no output", e, **{k: None for k, _ in MOVED[e] if k.startswith("out")})
+        add("negative batch and a level out of range", e, batch=-1, level=7)
+    add("negative n", "hsm_ray_distances", n=-1)
+    add("null begin", "hsm_ray_distances", begin=None)
+    add("null end", "hsm_ray_distances", end=None)
+    add("null out_dist", "hsm_ray_distances", out_dist=None)
+    add("resolution zero", "hsm_ray_distances", resolution=0.0)
+    add("resolution negative", "hsm_ray_distances", resolution=-0.05)
+    add("resolution NaN", "hsm_ray_distances", resolution=float("nan"))
+    for e in ["hsm_hessian_derivs", "hsm_eval_beams"]:
+        add("null pose", e, pose=None)
+        add("negative n", e, n=-1)
+        add("null pts", e, pts=None)
+    add("null H", "hsm_hessian_derivs", H=None)
+    add("null dTr", "hsm_hessian_derivs", dTr=None)
+    add("null out4", "hsm_eval_beams", out4=None)
+    add("negative first row", "hsm_download_rows", y0=-1)
+    add("last row past the map", "hsm_download_rows", y1=257)
+    add("rows that decrease", "hsm_download_rows", y0=2, y1=1)
+    add("null rows", "hsm_download_rows", rows=None)
+    add("negative corner", "hsm_download_cells", x0=-1)
+    add("corner past the map", "hsm_download_cells", y1=256)
+    add("corners that decrease", "hsm_download_cells", x0=2, x1=1)
+    add("null destination", "hsm_download_cells", dst=None)
+    add("pitch below the width", "hsm_download_cells", pitch=1)
+    add("null bbox", "hsm_take_dirty_bbox", bbox=None)
+    add("level past the pyramid", "hsm_debug_set_schedule", level=2, gn_steps=1)
+    add("no steps", "hsm_debug_set_schedule", level=0, gn_steps=0)
+    add("empty batch", "hsm_debug_batch_order", batch=0)
+    add("null start poses", "hsm_debug_batch_order", begin=None)
+    add("null permutation", "hsm_debug_batch_order", perm=None)
+    add("null out", "hsm_debug_marks_nonzero", out=None)
+    add("serial past the key generation field", "hsm_debug_set_update_serial", serial=4096)
+    for e in ["hsm_debug_expf", "hsm_debug_sincos"]:
+        add("negative n", e, n=-1)
+        add("null x", e, x=None)
+        add("null first output", e, out_a=None)
+        add("null second output", e, out_b=None)
+    add("null out", "hsm_group_create", out=None)
+    add("null devices", "hsm_group_create", devices=None)
+    add("no devices", "hsm_group_create", n_devices=0)
+    add("unknown mode", "hsm_group_set_gather", mode=17)
+    add("null counts", "hsm_group_match_batch_device", counts=None)
+    add("null start poses", "hsm_group_match_batch_device", begin=None)
+    add("null pts", "hsm_group_match_batch_device", pts=None)
+    add("null output", "hsm_group_match_batch_device", out_pose_all=None)
+    add("root below zero", "hsm_group_match_batch_device", root=-1)
+    add("root past the group", "hsm_group_match_batch_device", root=1)
+    add("negative shard", "hsm_group_match_batch_device", counts="H_NEGATIVE")
+    add("shard without start poses", "hsm_group_match_batch_device", begin="H_PTR_NULL")
+    add("shard without pts", "hsm_group_match_batch_device", pts="H_PTR_NULL")
+    add("negative batch", "hsm_group_match_batch", batch=-1)
+    add("null start poses", "hsm_group_match_batch", begin=None)
+    add("null output pose", "hsm_group_match_batch", out_pose=None)
+    add("negative total", "hsm_shard_bounds", total=-1)
+    add("no ranks", "hsm_shard_bounds", world=0)
+    add("rank below zero", "hsm_shard_bounds", rank=-1)
+    add("rank past the world", "hsm_shard_bounds", rank=2)
+    add("null begin", "hsm_shard_bounds", begin=None)
+    add("null end", "hsm_shard_bounds", end=None)
+
+
+ENTRIES.update(MOVED)
 
 
 class Runner:
@@ -138,21 +271,37 @@ class Runner:
         self.negative = np.int32([-1, 4, 8])
         self.stream = torch.cuda.Stream()
         assert self.dev.data_ptr() % 256 == 0
+        # the moved entries: every array argument as a bare address (the binding's array types take no null), and a group of one device
+        import ctypes as C
+        self.raw = C.CDLL(self.lib._name)
+        for entry in MOVED:
+            restype, argtypes = capi.SIGNATURES[entry]
+            fn = getattr(self.raw, entry)
+            fn.restype, fn.argtypes = restype, [a if a in (C.c_int, C.c_uint, C.c_float) else C.c_void_p for a in argtypes]
+        self.zero_int, self.one_int = np.int32([0]), np.int32([1])
+        self.ptr_d, self.ptr_null = np.uint64([self.dev.data_ptr()]), np.uint64([0])
+        self.group = C.c_void_p()
+        assert self.lib.hsm_group_create(0.05, 64, 64, 1, 0.5, 0.5, self.zero_int, 1, C.byref(self.group)) == 0
         self.values = {
             "D": self.dev.data_ptr(), "D+4": self.dev.data_ptr() + 4, "D+1": self.dev.data_ptr() + 1, "H": self.host.ctypes.data,
             "H_DECREASING": self.decreasing.ctypes.data, "H_NEGATIVE": self.negative.ctypes.data, "S": self.stream.cuda_stream,
             "WS_RANGES": int(self.lib.hsm_match_batch_ranges_workspace(COUNT, N)),
             "WS_SLAM": int(self.lib.hsm_slam_ranges_tf_workspace(COUNT, N)),
+            "H_ZERO_INT": self.zero_int.ctypes.data, "H_ONE_INT": self.one_int.ctypes.data, "H_PTR_D": self.ptr_d.ctypes.data,
+            "H_PTR_NULL": self.ptr_null.ctypes.data,
         }
         self.values["WS_RANGES-1"] = self.values["WS_RANGES"] - 1
         self.values["WS_SLAM-1"] = self.values["WS_SLAM"] - 1
         assert 0 < self.values["WS_SLAM"] <= self.dev.numel() and 0 < self.values["WS_RANGES"] <= self.dev.numel()
 
     def call(self, entry, over):
-        assert not set(over) - {k for k, _ in ENTRIES[entry]}, (entry, over)
+        assert not set(over) - {k for k, _ in ENTRIES[entry]} - {"ctx"}, (entry, over)
         args = [over.get(k, v) for k, v in ENTRIES[entry]]
         args = [self.values[a] if isinstance(a, str) else a for a in args]
-        rc = getattr(self.lib, entry)(self.g._h, *args)
+        first = FIRST.get(entry, "ctx")
+        if first:
+            args.insert(0, over.get("ctx", self.g._h if first == "ctx" else self.group))
+        rc = getattr(self.raw if entry in MOVED else self.lib, entry)(*args)
         return {"code": int(rc), "text": self.lib.hsm_last_error().decode() if rc != 0 else ""}
 
     def run(self, case_list):
@@ -172,5 +321,6 @@ class Runner:
         return got
 
     def close(self):
+        self.lib.hsm_group_destroy(self.group)
         self.g.synchronize()
         self.g.close()

@@ -1,5 +1,6 @@
 """The refusals of the scan-log, update and raw-scan entries on the MI355X, held to what the library answered before those entries
-were rewritten onto argument bundles: for every case of tests/refusal_cases.py the status code and the full hsm_last_error() text
+were rewritten onto argument bundles, and those of the probes, test hooks and group entries to what it answered before they moved
+out of the core translation unit: for every case of tests/refusal_cases.py the status code and the full hsm_last_error() text
 equal tests/golden/host_refusals.json (tests/tools/record_host_refusals.py) -- which check wins where two apply, and the entry each
 text names.  Nothing is queued by any case; the map is empty and stays so.
 """
