@@ -292,7 +292,8 @@ struct BeamSample {
 // differently is -0.0 (inside for the reference: -0.0 < 0 is false); c = e + r is -0.0 only if e AND r are -0.0,
 // and the callers pass e + 0.0f (wave-uniform, once per GN step; changes no other sum), so it cannot occur.
 // Outside beams keep their raw coordinate: v_cvt_i32_f32 saturates and v_fract_f32 of a finite value is finite,
-// which is all the all-zero texel needs to yield +-0 products.
+// which is all the all-zero texel needs to yield +-0 products.  (A coordinate is inf or NaN only when the estimate is: the
+// whole evaluation is then put right once, in gn_solve_and_step.)
 // the estimate's map coordinates as the beam loop adds them to the rotated endpoints: -0.0 -> +0.0 (see above; for
 // every other value x + 0.0f == x, and (+0.0) + r == (-0.0) + r unless r is -0.0 too)
 __device__ __forceinline__ f2 step_origin(float ex, float ey) {
@@ -634,7 +635,23 @@ __device__ __forceinline__ void team_allreduce9(Acc9& a, float (*red)[9][WPS < 4
 
 // H.inverse() * dTr as Eigen evaluates it (LU/InverseImpl.h cofactors * invdet, then a
 // coefficient-based product; 3-term sums are x0 + (x1 + x2)), ScanMatcher.h:201-217.
-__device__ __forceinline__ void gn_solve_and_step(const Acc9& a, float& ex, float& ey, float& eth) {
+//
+// A NON-FINITE estimate (a step that divided by a determinant of 0 or overflowed): every beam of the evaluation that filled `a`
+// was outside the map -- inf + r is beyond every limit for the reference too, and a NaN coordinate counts as outside
+// (cell_coord) -- so each must have contributed the reference's exact zeros for M and both gradients.  The all-zero texel
+// delivers them only through finite fractions, and v_fract_f32 of inf or NaN is NaN; instead of two selects per beam the
+// totals are put right here, once per step and wave-uniformly: the sums of +-0 products are +0, and the four sums that hold
+// rotDeriv are NaN where the angle itself is not finite (sinf / cosf of it are NaN: NaN * 0), +0 otherwise.  H(0,0) == 0 then
+// skips the step as the reference's own test does, and `a` (the covariance and the hook trace read it) says what was summed.
+__device__ __forceinline__ void gn_solve_and_step(Acc9& a, float& ex, float& ey, float& eth) {
+  const float rot_nf = eth - eth;  // +0 for a finite value, NaN for inf and NaN
+  if (((ex - ex) + (ey - ey)) + rot_nf != 0.0f) {
+    a.d01 = a.hd = f2{0.0f, 0.0f};
+    a.h01 = 0.0f;
+    a.hr = f2{rot_nf, rot_nf};
+    a.d2 = a.h22 = rot_nf;
+    return;
+  }
   if ((a.hd.x != 0.0f) && (a.hd.y != 0.0f)) {
     // symmetric H: m(r,c)
     const float m00 = a.hd.x, m01 = a.h01, m02 = a.hr.x;

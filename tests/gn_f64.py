@@ -32,6 +32,13 @@ a sum through at most `d` fp32 additions.  With p_i the exact products, the comp
   gn_eval_kernel  (hsm_hessian_derivs in the fast mode; 1024 lanes): ceil(n / 1024) + 6 + 15.
   the oracle's hessian_derivs (one sequential chain per term): d = n.
 
+Subnormal terms.  The relative bound assumes that a product rounds with a relative error of u, which holds only while the
+product is a normal fp32 number.  A product that underflows is rounded to a multiple of the smallest subnormal, s = 2^-149:
+an absolute error of up to s / 2 however small the product (sums of subnormals are exact, so the additions add nothing).  With
+n beams the sum is off by at most n s / 2 more; bound() adds the floor n s -- one subnormal ulp per addition -- to every entry
+that has a non-zero term.  On maps of young cells the floor is some 1e-42 next to bounds of 1e-6: it changes no verdict there.
+On aged maps (tests/aged_cases.py: probabilities of 1e-38 and below) it is the whole bound.
+
 The GPU tests compare H entry by entry with bound(); a kernel that loses or double-counts beam i moves an entry by
 |p_i|, which a test sees where |p_i| > 2 * bound (the bound is the rounding allowance on both sides).  beam_margin()
 is that ratio, and the test scans are chosen (gn_cases.make_scan) so that it exceeds 1 for every non-zero beam.
@@ -43,6 +50,7 @@ import math
 import numpy as np
 
 U = 2.0 ** -24
+SUBNORMAL_ULP = 2.0 ** -149  # the spacing of fp32 below 2^-126
 
 # entry order of the 12 sums: H as a row-major 3x3 (9, symmetric), then dTr (3)
 H_IDX = [(0, 0), (0, 1), (0, 2), (1, 0), (1, 1), (1, 2), (2, 0), (2, 1), (2, 2)]
@@ -156,7 +164,8 @@ class Eval64:
     def bound(self, d: int):
         """(H bound (3, 3), dTr bound (3,)) of an fp32 form with addition depth d"""
         gm = gamma(d + 1)
-        return gm * self.absH, gm * self.absd
+        floor = self.n * SUBNORMAL_ULP  # products that underflow: see "Subnormal terms" above
+        return gm * self.absH + np.where(self.absH > 0, floor, 0.0), gm * self.absd + np.where(self.absd > 0, floor, 0.0)
 
     def beam_margin(self, d: int):
         """per beam: max over the 12 entries of |p_ie| / (2 * allowance_e); inf-free, 0 for beams whose terms are all

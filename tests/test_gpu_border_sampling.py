@@ -177,7 +177,10 @@ def check_single(g, oracle_mod, kind, geom, case, expect_kernel=None):
             assert g.last_launch_config()["kernel"] == expect_kernel, (name, g.last_launch_config())
 
 
-@pytest.mark.parametrize("wps", [0, 1, 2, 4, 8, 16])
+WPS = [0, 1, 2, 4, 8, 16]  # 0: the width the library picks (shared with tests/test_gpu_aged_maps.py, like the batch form tables)
+
+
+@pytest.mark.parametrize("wps", WPS)
 @LAYOUTS
 @GEOMS
 def test_single_scan_matchers_for_every_team_width(capi, oracle_mod, kind, geom, layout, wps):
