@@ -409,6 +409,7 @@ int prepare_level(hsm_ctx* h, UpdateBatch& batch, LevelPrep& prep, int level, co
   prep.n = n;
   L.curr_mark_free = L.curr_update_index + 1;
   L.curr_mark_occ = L.curr_update_index + 2;
+  if (L.stamps_ahead()) batch.stamped = 1;  // a restored stamp >= this scan's free mark
   float mx, my;
   affine_apply_host(L.mapTworld, pose_world[0], pose_world[1], mx, my);  // getMapCoordsPose
   const float mth = pose_world[2];
@@ -592,19 +593,20 @@ int launch_update_apply(hsm_ctx* h, const UpdateBatch& batch) {
   if (use_dense_bits(h, batch, max_n)) {
     // one wavefront per block of 256 cells of the widened box (32 x 8 cells: two 16 x 8 mark tiles; map_update.h)
     const int g = grid_for(max_box / 4 + 4096);
-    if (h->layout == kLayoutQuad)
-      hipLaunchKernelGGL(update_apply_dense_kernel<true>, dim3(g, ny), dim3(256), 0, h->stream, batch);
-    else
-      hipLaunchKernelGGL(update_apply_dense_kernel<false>, dim3(g, ny), dim3(256), 0, h->stream, batch);
+    auto dense = h->layout == kLayoutQuad ? (batch.stamped ? update_apply_dense_kernel<true, true> : update_apply_dense_kernel<true, false>)
+                                          : (batch.stamped ? update_apply_dense_kernel<false, true> : update_apply_dense_kernel<false, false>);
+    hipLaunchKernelGGL(dense, dim3(g, ny), dim3(256), 0, h->stream, batch);
     HIP_TRY(hipGetLastError());
     return HSM_OK;
   }
   if (h->layout == kLayoutQuad && max_n < h->scatter_texels_max) {
     // the apply pass writes the texels itself: one dependent launch less for the launch-bound small scans (1081 beams,
     // 3 levels: complete 39 -> 34.5 us) and one dense pass less for the big ones (16 k beams on 8192^2: 0.51 -> 0.45 ms)
-    hipLaunchKernelGGL(update_apply_kernel<true>, dim3(grid_for(max_box), ny), dim3(256), 0, h->stream, batch);
+    auto apply = batch.stamped ? update_apply_kernel<true, true> : update_apply_kernel<true, false>;
+    hipLaunchKernelGGL(apply, dim3(grid_for(max_box), ny), dim3(256), 0, h->stream, batch);
   } else {
-    hipLaunchKernelGGL(update_apply_kernel<false>, dim3(grid_for(max_box), ny), dim3(256), 0, h->stream, batch);
+    auto apply = batch.stamped ? update_apply_kernel<false, true> : update_apply_kernel<false, false>;
+    hipLaunchKernelGGL(apply, dim3(grid_for(max_box), ny), dim3(256), 0, h->stream, batch);
     if (h->layout == kLayoutQuad)
       hipLaunchKernelGGL(update_texels_kernel, dim3(grid_for(max_box), ny), dim3(256), 0, h->stream, batch);
   }
@@ -1044,6 +1046,7 @@ int hsm_reset(hsm_ctx* h) {
   if (int rc = reset_update_gate(h)) return rc;
   for (Level& L : h->levels) {
     if (int rc = fill_level(h, L)) return rc;
+    L.uploaded_stamp_max = -1;  // every stamp is -1 again
     whole_level_changed(L);
   }
   HIP_TRY(hipStreamSynchronize(h->stream));
@@ -1714,6 +1717,7 @@ static int update_impl(hsm_ctx* h, const float pose_world[3], const float* pts_x
   }
   UpdateBatch batch;
   batch.nlev = 0;
+  batch.stamped = 0;
   LevelPrep prep[HSM_MAX_LEVELS];
   if (int rc = prepare_level(h, batch, prep[0], 0, pose_world, d_level0, pts_xy, n, 1.0f, o)) return rc;
   // coarse levels: the containers retained by the last matchData (MapRepMultiMap.h:143)
@@ -1791,6 +1795,7 @@ int hsm_update_by_scan_level(hsm_ctx* h, int level, const float pose_world[3], c
     HIP_TRY(hipMemcpyAsync(h->d_scan, pts_level_xy, (size_t)n * sizeof(float2), hipMemcpyHostToDevice, h->stream));
   UpdateBatch batch;
   batch.nlev = 0;
+  batch.stamped = 0;
   LevelPrep prep;
   if (int rc = prepare_level(h, batch, prep, level, pose_world, h->d_scan, pts_level_xy, n, 1.0f,
                              origo_level ? origo_level : zero))
@@ -1915,6 +1920,12 @@ static int update_by_scans_device_nolock(hsm_ctx* h, const PosedScans& S, hipStr
   const unsigned occ_blocks = (unsigned)((hint + 255) / 256), free_blocks = (unsigned)((hint + 3) / 4);
   const unsigned apply_blocks = (unsigned)grid_for(max_cells);
   const bool scatter = h->layout == kLayoutQuad;
+  // Restored stamps at or ahead of the first scan's free mark: the whole call takes the stamp-aware apply pass.  (A gated call
+  // whose predecessors' counts are still on the device sees a counter that lags: the test errs towards the stamp-aware form.)
+  bool stamped = false;
+  for (int l = 0; l < nlev; ++l) stamped |= h->levels[l].stamps_ahead();
+  auto apply_scan = scatter ? (stamped ? update_apply_scan_kernel<true, true> : update_apply_scan_kernel<true, false>)
+                            : (stamped ? update_apply_scan_kernel<false, true> : update_apply_scan_kernel<false, false>);
   for (int l = 0; l < nlev; ++l) h->levels[l].marks_pending = true;  // until every apply pass is queued (scrub_marks)
   for (int k = 0; k < count; ++k) {
     for (int l = 0; l < nlev; ++l) {
@@ -1930,12 +1941,7 @@ static int update_by_scans_device_nolock(hsm_ctx* h, const PosedScans& S, hipStr
     int* scan_boxes = h->d_upd_boxes + (size_t)update_box_slot(k, count) * kMaxLevels * 4;
     hipLaunchKernelGGL(update_mark_scan_kernel, dim3(occ_blocks + free_blocks, (unsigned)nlev), dim3(256), 0, h->stream,
                        h->d_upd_batches + k, occ_blocks, scan_boxes, h->d_upd_boxes, h->d_pub_boxes);
-    if (scatter)
-      hipLaunchKernelGGL(update_apply_scan_kernel<true>, dim3(apply_blocks, (unsigned)nlev), dim3(256), 0, h->stream,
-                         h->d_upd_batches + k, scan_boxes);
-    else
-      hipLaunchKernelGGL(update_apply_scan_kernel<false>, dim3(apply_blocks, (unsigned)nlev), dim3(256), 0, h->stream,
-                         h->d_upd_batches + k, scan_boxes);
+    hipLaunchKernelGGL(apply_scan, dim3(apply_blocks, (unsigned)nlev), dim3(256), 0, h->stream, h->d_upd_batches + k, scan_boxes);
     HIP_TRY(hipGetLastError());
   }
   for (int l = 0; l < nlev; ++l) {

@@ -59,6 +59,10 @@ struct Level {
   float log_odds_free = 0.f, log_odds_occ = 0.f;
   // OccGridMapBase counters / GridMapBase::lastUpdateIndex
   int curr_update_index = 0, curr_mark_occ = -1, curr_mark_free = -1, last_update_index = -1;
+  // the largest stamp hsm_upload_level last restored, -1 = none (hsm_reset).  While it is ahead of curr_update_index the
+  // apply passes run their stamp-aware form (map_update.h "stored stamps"); kernels only ever store stamps below the counter
+  int uploaded_stamp_max = -1;
+  bool stamps_ahead() const { return uploaded_stamp_max > curr_update_index; }
   unsigned int serial = 0;  // key-plane generation (map_update.h)
   int bbox[4] = {0, 0, -1, -1};   // cell box touched by the last update
   int dirty[4] = {0, 0, -1, -1};  // union of those boxes since hsm_take_dirty_bbox was last called

@@ -29,6 +29,16 @@
 // Keys of earlier scans are always smaller than the current ones, so the key planes never need
 // clearing (only when the 12-bit serial wraps, every 4095 updates).
 //
+// Stored stamps.  The reference's two cell rules test the cell's stored updateIndex against the scan's marks F = counter + 1
+// and O = counter + 2 (:218, :228).  Every stamp the kernels write lies below the counter of the next scan, so the tests always
+// pass and the apply passes need not read the plane -- until hsm_upload_level restores a level whose stamps are at or ahead of
+// the counter.  Then, with s the stamp in front of the scan: s >= O, nothing is written (log-odds, stamp, probability and
+// texels stay); s == F, a crossing writes nothing and an end applies unsetFree (l -= f, whether or not the scan crossed the
+// cell first), then the occupied update, stamp O; s < F, the rule above.  The apply passes have a STAMPED instantiation that
+// loads the stamp and does exactly that (the marks and bitmap words of skipped cells are cleared as for any other cell); the
+// host selects it per call while Level::uploaded_stamp_max is ahead of the level's counter, so the hot path never pays the
+// extra 4 B per touched cell (profiles/r16/README.md).  tests/test_gpu_restored_stamps.py.
+//
 // Traffic: mark = one 4-byte load (+ rarely an atomic) per visited cell; apply = 12 B
 // read + 12 B written per touched cell of the box; texels = 16 B written per cell of the box.
 // HBM/L2-bound integer/byte work, no MFMA.
@@ -73,6 +83,7 @@ struct UpdateParams {
 struct UpdateBatch {
   UpdateParams lv[kMaxLevels];
   int nlev;
+  int stamped;  // host-side batches: a level of the batch holds restored stamps at or ahead of its marks (the apply passes' STAMPED form)
 };
 
 // geometry of beam i exactly as updateByScan / updateLineBresenhami derive it
@@ -275,7 +286,8 @@ __global__ void __launch_bounds__(256) update_mark_kernel(const UpdateBatch B, u
 // has exactly one writer (the thread of its cell), untouched components keep their value: same bits as the rebuild.
 // The body of update_apply_kernel and of update_apply_scan_kernel; grid-stride: `first` is this thread's first cell of the
 // box, `stride` the number of threads in the grid (computed by the kernels, where blockDim is a compile-time-uniform read).
-template <bool SCATTER_TEXELS>
+// STAMPED (restored levels, see the header): the cell's stored stamp is read and the reference's tests on it are applied.
+template <bool SCATTER_TEXELS, bool STAMPED>
 __device__ __forceinline__ void apply_box(const UpdateParams& P, size_t first, size_t stride) {
   if (P.x1 < P.x0) return;  // this level has nothing to apply
   const bool aligned = (P.lv.sx & 63) == 0;
@@ -302,13 +314,22 @@ __device__ __forceinline__ void apply_box(const UpdateParams& P, size_t first, s
     }
     const bool fre = (kf >> kBeamBits) == P.serial;
     if (!fre && !occ) continue;
+    bool stored_free = false;  // the stored stamp IS this scan's free mark: no free update, unsetFree in front of the occupied one
+    if (STAMPED) {
+      const int s = P.lv.update_index[c];
+      if (s >= P.mark_occ) continue;  // :228 fails, and :218 with it: the cell stays as it is
+      stored_free = s == P.mark_free;
+      if (stored_free && !occ) continue;  // :218 fails
+    }
     float l = P.lv.logodds[c];
     int stamp;
     if (occ) {
       // free-touched by an earlier beam of this scan: applied, then reverted (:231-233)
       // (in fp32 (l + f) - f == l unless l + f leaves l's binade, so this comparison shows in the bits only for cells just above
       // -2, -4, -8 ...: tests/test_gpu_update_order.py puts cells there and runs scans in several beam orders)
-      if (fre && (kBeamMask - (kf & kBeamMask)) < (kBeamMask - (ko & kBeamMask))) {
+      if (stored_free) {
+        l -= P.log_odds_free;
+      } else if (fre && (kBeamMask - (kf & kBeamMask)) < (kBeamMask - (ko & kBeamMask))) {
         l += P.log_odds_free;
         l -= P.log_odds_free;
       }
@@ -340,9 +361,9 @@ __device__ __forceinline__ void apply_box(const UpdateParams& P, size_t first, s
   }
 }
 
-template <bool SCATTER_TEXELS>
+template <bool SCATTER_TEXELS, bool STAMPED>
 __global__ void __launch_bounds__(256) update_apply_kernel(const UpdateBatch B) {
-  apply_box<SCATTER_TEXELS>(B.lv[blockIdx.y], blockIdx.x * (size_t)blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x);
+  apply_box<SCATTER_TEXELS, STAMPED>(B.lv[blockIdx.y], blockIdx.x * (size_t)blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x);
 }
 
 
@@ -511,7 +532,7 @@ __global__ void __launch_bounds__(256) update_mark_free_dense_kernel(const Updat
 // touched cell that nothing reads again before the next update; kept out of the L2 they leave it to the marks and the log-odds
 // rows (update 0.198 -> 0.178 ms on configs[4]; non-temporal LOADS of the rows or stores of the cleared marks lose: 0.205 ms).
 // (Measured against 64 x 4-cell blocks on the 8 x 4 tiling: profiles/r04/README.md 20.)
-template <bool SCATTER_TEXELS>
+template <bool SCATTER_TEXELS, bool STAMPED>
 __global__ void __launch_bounds__(256) update_apply_dense_kernel(const UpdateBatch B) {
   const UpdateParams& P = B.lv[blockIdx.y];
   if (P.x1 < P.x0) return;
@@ -545,6 +566,7 @@ __global__ void __launch_bounds__(256) update_apply_dense_kernel(const UpdateBat
     bool fre[4], occ[4];
     float l[4];
     unsigned int ko[4], kf[4];
+    int st[4];  // STAMPED: the stored stamps
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int r = 2 * i + rh, y = Y0 + r;
@@ -556,7 +578,9 @@ __global__ void __launch_bounds__(256) update_apply_dense_kernel(const UpdateBat
       fre[i] = (mark & kMarkCrossed) != 0u && y < sy && x < sx;
       l[i] = 0.0f;
       ko[i] = kf[i] = 0u;
+      st[i] = -1;
       if (fre[i] || occ[i]) l[i] = P.lv.logodds[c];
+      if (STAMPED && (fre[i] || occ[i])) st[i] = P.lv.update_index[c];
       if (occ[i]) {
         ko[i] = P.lv.key_occ[c];
         kf[i] = P.lv.key_free[key_free_index(P.lv, (unsigned int)x, (unsigned int)y)];
@@ -572,12 +596,17 @@ __global__ void __launch_bounds__(256) update_apply_dense_kernel(const UpdateBat
         is_fre = (kf[i] >> kBeamBits) == P.serial;
       }
       if (!is_fre && !is_occ) continue;
+      // the stored stamp (apply_box): at or past the occupied mark the cell stays; equal to the free mark it takes no free update
+      const bool stored_free = STAMPED && st[i] == P.mark_free;
+      if (STAMPED && (st[i] >= P.mark_occ || (stored_free && !is_occ))) continue;
       float lo = l[i];
       int stamp;
       if (is_occ) {
         // crossed by a beam of lower index than the first that ends here: applied, then reverted (:231-233).  Visible in the bits
         // only where lo + f leaves lo's binade (cells just above -2, -4, -8 ...): tests/test_gpu_update_order.py
-        if (is_fre && (kBeamMask - (kf[i] & kBeamMask)) < (kBeamMask - (ko[i] & kBeamMask))) {
+        if (stored_free) {
+          lo -= P.log_odds_free;
+        } else if (is_fre && (kBeamMask - (kf[i] & kBeamMask)) < (kBeamMask - (ko[i] & kBeamMask))) {
           lo += P.log_odds_free;
           lo -= P.log_odds_free;
         }
@@ -970,7 +999,7 @@ __global__ void __launch_bounds__(256) update_mark_scan_kernel(const UpdateBatch
   }
 }
 
-template <bool SCATTER_TEXELS>
+template <bool SCATTER_TEXELS, bool STAMPED>
 __global__ void __launch_bounds__(256) update_apply_scan_kernel(const UpdateBatch* __restrict__ B,
                                                                 const int* __restrict__ scan_boxes) {
   const int4 box = *reinterpret_cast<const int4*>(scan_boxes + 4 * blockIdx.y);
@@ -980,7 +1009,7 @@ __global__ void __launch_bounds__(256) update_apply_scan_kernel(const UpdateBatc
   P.y0 = box.y;
   P.x1 = box.z;
   P.y1 = box.w;
-  apply_box<SCATTER_TEXELS>(P, blockIdx.x * (size_t)blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x);
+  apply_box<SCATTER_TEXELS, STAMPED>(P, blockIdx.x * (size_t)blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x);
 }
 
 // the running dirty boxes of all levels back to empty (after the host has merged them)

@@ -169,8 +169,13 @@ int hsm_upload_level(hsm_ctx* h, int level, const float* logodds, const int* upd
   if (int rc = order_after_foreign_match(h)) return rc;
   HIP_TRY(hipStreamSynchronize(h->stream));
   if (logodds) HIP_TRY(hipMemcpy(L.d_logodds, logodds, L.cells() * sizeof(float), hipMemcpyHostToDevice));
-  if (update_index)
+  if (update_index) {
     HIP_TRY(hipMemcpy(L.d_update_index, update_index, L.cells() * sizeof(int), hipMemcpyHostToDevice));
+    // the reference's cell rules read these stamps: while one is at or ahead of the counter the apply passes read them, too
+    int top = -1;
+    for (size_t i = 0; i < L.cells(); ++i) top = update_index[i] > top ? update_index[i] : top;
+    L.uploaded_stamp_max = top;
+  }
   if (int rc = rebuild_probability(h, L)) return rc;
   whole_level_changed(L);
   HIP_TRY(hipStreamSynchronize(h->stream));

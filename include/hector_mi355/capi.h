@@ -450,6 +450,13 @@ int hsm_world_coords_pose(const hsm_ctx* h, int level, const float map[3], float
 int hsm_update_index(const hsm_ctx* h, int level);
 /* whole level; either pointer may be NULL */
 int hsm_download_level(hsm_ctx* h, int level, float* logodds, int* update_index);
+/* hsm_upload_level replaces the planes and leaves the level's update counter (currUpdateIndex) where it is, as the reference's
+ * cells would be if written directly.  The reference's cell rules test each cell's stored stamp against the marks of the scan
+ * being integrated (counter + 1 / + 2, OccGridMapBase.h bresenhamCellFree / bresenhamCellOcc), and so do the kernels: a cell
+ * restored with a stamp at or ahead of the counter stays FROZEN -- no update touches it -- until the counter has passed its
+ * stamp (the counter advances by 3 per integrated scan); a stamp equal to a scan's free mark takes unsetFree in front of that
+ * scan's occupied update.  Restoring into the context the planes came from is exact.  To restore into another context and get
+ * live cells, upload stamps of -1, or hsm_reset and pass update_index == NULL (which keeps the stamps that are there). */
 int hsm_upload_level(hsm_ctx* h, int level, const float* logodds, const int* update_index);
 /* rows [y0, y1) of the log-odds plane only (cheap mirror refresh after an update) */
 int hsm_download_rows(hsm_ctx* h, int level, int y0, int y1, float* logodds_rows);
