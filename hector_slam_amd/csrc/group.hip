@@ -42,8 +42,6 @@ ncclResult_t ncclGetVersion(int* version);
 
 using namespace hsm_host;
 
-#define HIP_TRY HSM_HIP_TRY
-
 // One persistent host thread per replica beyond the first (replica 0 runs on the calling thread): a job slot guarded by
 // a mutex + condition variable; threads live as long as the group, so a batched match costs no thread creation.
 struct GroupWorker {

@@ -1,7 +1,10 @@
 // hsm_ctx.h -- the context of libhector_mi355.so as its translation units see it: the pyramid level, hsm_ctx, and the launch
 // entry points the units implement for each other.  Internal (not installed): the public boundary is include/hector_mi355/capi.h.
-//   hector_mi355.hip        host runtime + C ABI of everything that is timed: matches, updates, scan loops, ingestion, occupancy
-//                           exports; update / node-row kernels, the one-workgroup-per-scan matcher forms
+//   hector_mi355.hip        the core: host runtime + C ABI of matches, updates and scan loops; the update kernels
+//                           (map_update.h), the one-workgroup-per-scan matcher forms
+//   ingest.hip              raw sensor data: the LaserScan / point-cloud conversions of one scan and of batches, in front of
+//                           the core's match, update and SLAM loop (ingest_kernels.h)
+//   occupancy.hip           a level as the node's occupancy grid, whole or its changed cells only (occupancy_kernels.h)
 //   probes.hip              the host-array probes (likelihood, covariance, ray distances, Hessian), level downloads and uploads,
 //                           the hsm_debug_* test hooks, and the kernels only these launch (probe_kernels.h)
 //   group.hip               the multi-GPU group (hsm_group_*, hsm_shard_bounds): host code only, librccl opened on demand
@@ -107,7 +110,7 @@ struct GrowBuf {
   BufKind kind = kBufDevice;
   hipError_t free_block() { return kind == kBufDevice ? hipFree(p) : hipHostFree(p); }
   int drop() {  // (a failing free leaves the block as it was)
-    if (p) HSM_HIP_TRY(free_block());
+    if (p) HIP_TRY(free_block());
     p = nullptr;
     bytes = 0;
     return HSM_OK;
@@ -115,9 +118,9 @@ struct GrowBuf {
   int replace(size_t want_bytes) {  // null and empty after a failure
     if (int rc = drop()) return rc;
     if (kind == kBufDevice)
-      HSM_HIP_TRY(hipMalloc(&p, want_bytes));
+      HIP_TRY(hipMalloc(&p, want_bytes));
     else
-      HSM_HIP_TRY(hipHostMalloc(&p, want_bytes, kind == kBufPinned ? hipHostMallocDefault : hipHostMallocMapped));
+      HIP_TRY(hipHostMalloc(&p, want_bytes, kind == kBufPinned ? hipHostMallocDefault : hipHostMallocMapped));
     bytes = want_bytes;
     return HSM_OK;
   }
@@ -159,14 +162,14 @@ inline bool stream_capturing(hipStream_t s) {
 inline int stage_copy_in(const StagePlan& st, char* base, hipStream_t s) {
   for (int i = 0; i < st.n; ++i)
     if (st.r[i].src && st.r[i].bytes)
-      HSM_HIP_TRY(hipMemcpyAsync(base + st.r[i].off, st.r[i].src, st.r[i].bytes, hipMemcpyHostToDevice, s));
+      HIP_TRY(hipMemcpyAsync(base + st.r[i].off, st.r[i].src, st.r[i].bytes, hipMemcpyHostToDevice, s));
   return HSM_OK;
 }
 // ... and every result out, behind its last one (the entry then waits for `s` once)
 inline int stage_copy_out(const StagePlan& st, char* base, hipStream_t s) {
   for (int i = 0; i < st.n; ++i)
     if (st.r[i].dst && st.r[i].bytes)
-      HSM_HIP_TRY(hipMemcpyAsync(st.r[i].dst, base + st.r[i].off, st.r[i].bytes, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipMemcpyAsync(st.r[i].dst, base + st.r[i].off, st.r[i].bytes, hipMemcpyDeviceToHost, s));
   return HSM_OK;
 }
 // the device address of a region; the three-argument form: null where the host array it stands for is absent
@@ -221,7 +224,7 @@ struct hsm_ctx {
   Buf<int> d_upd_boxes{&bufs};  // allocated last: non-null = both blocks serve d_upd_batches.count() scans
   bool upd_boxes_outstanding = false;  // device-side updates since the host last merged their boxes into Level::bbox / dirty
   hipEvent_t evt_inputs = nullptr;     // the caller's stream at hsm_update_by_scans_device: its inputs are complete
-  // the published grid (map_update.h occupancy_prep_kernel), three rows of kMaxLevels boxes in a block of their own that no
+  // the published grid (occupancy_kernels.h occupancy_prep_kernel), three rows of kMaxLevels boxes in a block of their own that no
   // growing buffer replaces: the levels' publish boxes as device-side updates widen them (never fetched), the box of the export
   // that was queued last on each level (its convert launch reads it), and the whole level as a box (written by hsm_create)
   int* d_pub_boxes = nullptr;
@@ -363,8 +366,59 @@ namespace hsm_host {
 
 using hsm_plan::MatchPlan;
 
-// hector_mi355.hip, for probes.hip and group.hip: the views of a level, the launch arithmetic, and what an entry does before it
-// reads or rewrites a level on the host (the definitions carry the comments)
+// What a gated update adds to an update call (update_by_scans_device_nolock of hector_mi355.hip; map_update.h UpdateGateParams)
+struct GateCall {
+  const unsigned char* d_force = nullptr;
+  int* d_out_applied = nullptr;
+  bool slam = false;  // hsm_slam_scans_device's call for one scan: see UpdateGateParams
+  float* pose_io = nullptr;
+  float* cov_io = nullptr;
+  const float* next_delta = nullptr;
+};
+
+// The posed scans of an update call, filled once by the entry and passed down: CSR scans (`d_offsets`) or one scan of `shared_n`
+// beams at every pose; `origo` the host pair for every scan (null: zero) or `d_origos` [count * 2] on the device.  The first six
+// fields are in the order of the C ABI: an entry initialises them with braces and names the rest.
+struct PosedScans {
+  int count = 0;
+  const float* d_poses = nullptr;
+  const float* d_pts = nullptr;
+  const int* d_offsets = nullptr;
+  int shared_n = 0, max_beams = 0;
+  const float* origo = nullptr;
+  const float* d_origos = nullptr;
+  const GateCall* gate = nullptr;                   // the gated entries
+  const char* who = "hsm_update_by_scans_device";  // the entry the caller used, for the error texts
+};
+
+// The scan log of a SLAM call, all on the device: what steers the loop and where its results go.  Scan k's share of every array
+// is sliced here and nowhere else.  (Fields in the order the entries initialise them with braces.)
+struct ScanLog {
+  int count = 0;
+  const float* d_start_pose = nullptr;
+  const float* d_hint_deltas = nullptr;  // [count * 3] or null
+  const unsigned char* d_force = nullptr;  // [count] or null
+  float* d_out_pose = nullptr;             // [count * 3]
+  float* d_out_cov = nullptr;              // [count * 9] or null
+  int* d_out_applied = nullptr;            // [count] or null
+  int* d_out_counts = nullptr;             // [count] or null: the raw-scan entries' survivors per scan
+  float* pose(int k) const { return d_out_pose + 3 * (size_t)k; }
+  float* cov(int k) const { return d_out_cov ? d_out_cov + 9 * (size_t)k : nullptr; }
+  GateCall gate(int k) const {  // scan k's gated update: it settles the scan's pose and covariance and leaves the next scan's hint
+    GateCall g;
+    g.d_force = d_force ? d_force + k : nullptr;
+    g.d_out_applied = d_out_applied ? d_out_applied + k : nullptr;
+    g.slam = true;
+    g.pose_io = pose(k);
+    g.cov_io = cov(k);
+    g.next_delta = d_hint_deltas && k + 1 < count ? d_hint_deltas + 3 * (size_t)(k + 1) : nullptr;
+    return g;
+  }
+};
+
+// hector_mi355.hip, for the other units: the views of a level, the launch arithmetic, what an entry does before it reads or
+// rewrites a level on the host, the hand-over between a caller's stream and the context's around queued map updates, and the
+// device SLAM loop over a scan log (the definitions carry the comments)
 int valid_level(const hsm_ctx* h, int level);
 int select_device(const hsm_ctx* h);
 bool wants_exact(const hsm_ctx* h);
@@ -379,6 +433,10 @@ int fold_gate_counters(hsm_ctx* h, GateState* state = nullptr);
 int match_batch_device_nolock(hsm_ctx* h, int batch, const float* d_begin_world, const float* d_pts_xy, const int* d_scan_offsets,
                               int shared_n, float* d_out_pose, float* d_out_cov, void* stream, int n_bound = 0,
                               const ExchangeFused* xp = nullptr);
+int slam_refuse_capture(hsm_ctx* h, hipStream_t s, const char* who);
+int wait_for_caller_inputs(hsm_ctx* h, hipStream_t s);
+int slam_caller_waits(hsm_ctx* h, hipStream_t s);
+int slam_scans_queue(hsm_ctx* h, const ScanLog& log, const PosedScans& scans);
 
 // f(layout, exact) with the context's texel layout and summation order as types (std::integral_constant<int, kLayout...>,
 // std::bool_constant): a generic lambda launches `kernel<layout(), exact()>` and the four sampler forms need no ladder.  A kernel

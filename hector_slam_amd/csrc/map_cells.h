@@ -1,6 +1,6 @@
 // map_cells.h -- what every kernel that walks a level's cells shares: the read-write view of a level, the tilings of its key and
-// mark planes, the cell probability, and the closed form of a Bresenham line.  No kernel is defined here: map_update.h (the
-// core unit) and probe_kernels.h (probes.hip) both include it.
+// mark planes, the cell probability, the empty cell box, and the closed form of a Bresenham line.  No kernel is defined here:
+// map_update.h (the core unit), probe_kernels.h (probes.hip) and occupancy_kernels.h (occupancy.hip) all include it.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -78,6 +78,9 @@ __device__ __forceinline__ float grid_probability(float log_odds) {
   const float odds = libm::expf_glibc(log_odds);
   return odds / (odds + 1.0f);
 }
+
+// A cell box on the device: {x0, y0, x1, y1}, inclusive; empty = {INT_MAX, INT_MAX, -1, -1}, the identity of the atomics.
+constexpr int kBoxEmptyLo = 0x7fffffff, kBoxEmptyHi = -1;
 
 struct BeamLine {
   bool valid;

@@ -126,8 +126,6 @@ __global__ void __launch_bounds__(1024) batch_order_kernel(Affine2 mapTworld, in
 
 namespace hsm_host {
 
-#define HIP_TRY HSM_HIP_TRY
-
 int launch_batch_order(hsm_ctx* h, const float* begin_world, int batch, int* perm, bool detect, hipStream_t stream) {
   // 64 tiles span the longer edge of level 0
   const Level& L0 = h->levels[0];

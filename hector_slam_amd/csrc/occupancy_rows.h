@@ -1,4 +1,4 @@
-// occupancy_rows.h -- how occupancy_box_kernel (map_update.h) cuts one row of a cell box into a ragged head, a body of 4-cell
+// occupancy_rows.h -- how occupancy_box_kernel (occupancy_kernels.h) cuts one row of a cell box into a ragged head, a body of 4-cell
 // groups and a ragged tail, and publishMap's rule for one cell.  The groups are aligned on the GRID: a group starts at a flat
 // cell index (y * sx + x) that is a multiple of 4, where a 16-byte load of the log-odds plane and a 4-byte store into the byte
 // grid are aligned -- whatever column the box starts at, and on levels whose width is no multiple of 4 (the phase then changes

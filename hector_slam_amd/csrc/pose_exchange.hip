@@ -120,9 +120,9 @@ int exchange_launch(hsm_exchange* x, const float* d_rows, int first_row, int n_r
   const size_t wait_blocks = wait_epoch ? (x->lay.buffer_granules() + per_block - 1) / per_block : 0;
   const size_t grid = (size_t)A.post_blocks * (size_t)x->lay.world + wait_blocks;
   if (grid == 0) return HSM_OK;
-  HSM_HIP_TRY(hipSetDevice(x->device));
+  HIP_TRY(hipSetDevice(x->device));
   hipLaunchKernelGGL(pose_exchange_kernel, dim3((unsigned)grid), dim3(kExchangeBlock), 0, (hipStream_t)stream, A);
-  HSM_HIP_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return HSM_OK;
 }
 
@@ -142,8 +142,8 @@ int hsm_exchange_create(int device, int rank, int world, int total_rows, int col
   if (world < 1 || world > kExchangeMaxWorld || rank < 0 || rank >= world || total_rows < 1 || cols < 1 || depth < 2 ||
       (size_t)total_rows * (size_t)cols > ((size_t)1 << 28))
     return hsm_host::fail(HSM_ERR_INVALID, "hsm_exchange_create: bad argument (1 <= world <= 16, depth >= 2)");
-  if (device < 0) HSM_HIP_TRY(hipGetDevice(&device));
-  HSM_HIP_TRY(hipSetDevice(device));
+  if (device < 0) HIP_TRY(hipGetDevice(&device));
+  HIP_TRY(hipSetDevice(device));
   hsm_exchange* x = new hsm_exchange();
   x->device = device;
   x->rank = rank;
@@ -195,9 +195,9 @@ void hsm_exchange_destroy(hsm_exchange* x) {
 int hsm_exchange_handle(hsm_exchange* x, void* handle64) {
   if (!x || !handle64) return hsm_host::fail(HSM_ERR_INVALID, "hsm_exchange_handle: null argument");
   static_assert(sizeof(hipIpcMemHandle_t) == HSM_EXCHANGE_HANDLE_BYTES, "capi.h states the size of an IPC handle");
-  HSM_HIP_TRY(hipSetDevice(x->device));
+  HIP_TRY(hipSetDevice(x->device));
   hipIpcMemHandle_t h;
-  HSM_HIP_TRY(hipIpcGetMemHandle(&h, x->mailbox));
+  HIP_TRY(hipIpcGetMemHandle(&h, x->mailbox));
   memcpy(handle64, &h, sizeof h);
   return HSM_OK;
 }
@@ -206,13 +206,13 @@ int hsm_exchange_connect(hsm_exchange* x, const void* handles) {
   if (!x || (!handles && x->lay.world > 1)) return hsm_host::fail(HSM_ERR_INVALID, "hsm_exchange_connect: null argument");
   std::lock_guard<std::mutex> lk(x->mu);
   if (x->connected) return HSM_OK;
-  HSM_HIP_TRY(hipSetDevice(x->device));
+  HIP_TRY(hipSetDevice(x->device));
   for (int r = 0; r < x->lay.world; ++r) {
     if (r == x->rank) continue;
     hipIpcMemHandle_t h;
     memcpy(&h, (const char*)handles + (size_t)r * sizeof h, sizeof h);
     void* p = nullptr;
-    HSM_HIP_TRY(hipIpcOpenMemHandle(&p, h, hipIpcMemLazyEnablePeerAccess));
+    HIP_TRY(hipIpcOpenMemHandle(&p, h, hipIpcMemLazyEnablePeerAccess));
     x->peer[r] = (uint64_t*)p;
     x->opened[r] = true;
   }
@@ -223,7 +223,7 @@ int hsm_exchange_connect(hsm_exchange* x, const void* handles) {
 int hsm_exchange_connect_local(hsm_exchange* x, hsm_exchange* const* ranks) {
   if (!x || !ranks) return hsm_host::fail(HSM_ERR_INVALID, "hsm_exchange_connect_local: null argument");
   std::lock_guard<std::mutex> lk(x->mu);
-  HSM_HIP_TRY(hipSetDevice(x->device));
+  HIP_TRY(hipSetDevice(x->device));
   for (int r = 0; r < x->lay.world; ++r) {
     const hsm_exchange* o = ranks[r];
     if (!o || o->rank != r || o->lay.world != x->lay.world || o->lay.total_rows != x->lay.total_rows || o->lay.cols != x->lay.cols ||
@@ -232,7 +232,7 @@ int hsm_exchange_connect_local(hsm_exchange* x, hsm_exchange* const* ranks) {
     if (r == x->rank) continue;
     if (o->device != x->device) {
       int can = 0;
-      HSM_HIP_TRY(hipDeviceCanAccessPeer(&can, x->device, o->device));
+      HIP_TRY(hipDeviceCanAccessPeer(&can, x->device, o->device));
       if (!can) return hsm_host::fail(HSM_ERR_HIP, "hsm_exchange_connect_local: no peer access between the devices");
       const hipError_t e = hipDeviceEnablePeerAccess(o->device, 0);
       if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) return hsm_host::fail(HSM_ERR_HIP, "hipDeviceEnablePeerAccess", e);

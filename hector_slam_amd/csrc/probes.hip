@@ -16,8 +16,6 @@
 using namespace hsm;
 using namespace hsm_host;
 
-#define HIP_TRY HSM_HIP_TRY
-
 extern "C" {
 
 static int score_states(hsm_ctx* h, int level, int batch, const float* states_map, const float* pts_xy, int n,

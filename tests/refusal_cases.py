@@ -11,6 +11,9 @@ refuses first.  Cases with capture=True run while "S" is being captured into a g
 The probes, downloads, test hooks and the device group joined the list before they moved out of the core translation unit (recorded
 again, all cases, from the commit before that move).  Their first argument is the context unless FIRST says otherwise; the override
 `ctx=None` passes a null context (or group) instead.
+
+The single-scan conversions (INGEST) and one failing HIP status check joined it before raw-scan conversion and the occupancy
+exports moved to ingest.hip and occupancy.hip (recorded again, all cases, from the commit before that move).
 """
 INT_MAX = 2**31 - 1
 MAX_BEAMS = 1048575  # HSM_MAX_UPDATE_BEAMS
@@ -102,6 +105,12 @@ MOVED = {
                               ("out_cov", None)],
     "hsm_shard_bounds": [("total", 10), ("rank", 0), ("world", 2), ("begin", "H"), ("end", "H")],
 }
+# the single-scan conversions, which joined the list before they moved to ingest.hip
+INGEST = {
+    "hsm_ingest_laser_scan": [("ranges", "H"), ("n", N)] + _TF[:4] + [("scale_to_map", 20.0), ("out_pts", None), ("out_n", None)],
+    "hsm_ingest_laser_scan_tf": [("ranges", "H"), ("n", N)] + _TF + [("tf_rows", "H")] + _GATES + [("out_pts", None), ("out_n", None),
+                                                                                                 ("out_origo", None)],
+}
 # what goes in front of an entry's parameters: the context (every entry not listed), the runner's one-device group, or nothing
 FIRST = {e: "group" for e in MOVED if e.startswith("hsm_group_")}
 FIRST.update({"hsm_group_create": None, "hsm_shard_bounds": None})
@@ -127,7 +136,7 @@ def cases():
         out.append((f"{entry}:{what}", entry, over, capture))
 
     for e in ENTRIES:
-        if e not in MOVED:
+        if e not in MOVED and e not in INGEST:
             add("negative count", e, **{_count_name(e): -1})
     for e in _UPDATES + _SLAM_SCANS:
         add("negative max_beams", e, max_beams=-5)
@@ -174,6 +183,16 @@ def cases():
     add("too many beams under capture", "hsm_update_by_scans_device", capture=True, offsets=None, shared_n=MAX_BEAMS + 1)
     add("short workspace under capture", "hsm_slam_ranges_tf_device", capture=True, workspace_bytes="WS_SLAM-1")
     moved_cases(add)
+    for e in INGEST:
+        add("null context", e, ctx=None)
+        add("negative n", e, n=-1)
+        add("n above HSM_MAX_UPDATE_BEAMS", e, n=MAX_BEAMS + 1)
+        add("null ranges", e, ranges=None)
+    add("null tf_rows", "hsm_ingest_laser_scan_tf", tf_rows=None)
+    # The text of a failing HIP status check ("<the call as written>: <HIP's text>"), without a failing device: HIP keeps a thread's
+    # last failure until somebody asks for it, so a call of the CALLER's that HIP refused (an invalid device ordinal) is what the
+    # entry's launch check reports.  The one case that queues work: the conversion of an empty scan, which writes its count of 0.
+    add("launch check behind a failed HIP call of the caller's", "hsm_ingest_laser_scan", n=0, failed_hip_call_first=True)
     assert len({c[0] for c in out}) == len(out)
     return out
 
@@ -254,6 +273,7 @@ def moved_cases(add):
 
 
 ENTRIES.update(MOVED)
+ENTRIES.update(INGEST)
 
 
 class Runner:
@@ -295,13 +315,17 @@ class Runner:
         assert 0 < self.values["WS_SLAM"] <= self.dev.numel() and 0 < self.values["WS_RANGES"] <= self.dev.numel()
 
     def call(self, entry, over):
-        assert not set(over) - {k for k, _ in ENTRIES[entry]} - {"ctx"}, (entry, over)
+        assert not set(over) - {k for k, _ in ENTRIES[entry]} - {"ctx", "failed_hip_call_first"}, (entry, over)
         args = [over.get(k, v) for k, v in ENTRIES[entry]]
         args = [self.values[a] if isinstance(a, str) else a for a in args]
         first = FIRST.get(entry, "ctx")
         if first:
             args.insert(0, over.get("ctx", self.g._h if first == "ctx" else self.group))
+        if over.get("failed_hip_call_first"):  # (the library's own HIP runtime, on this thread)
+            assert self.raw.hipSetDevice(1 << 20) != 0
         rc = getattr(self.raw if entry in MOVED else self.lib, entry)(*args)
+        if over.get("failed_hip_call_first"):
+            self.raw.hipGetLastError()  # (nothing of it is left for the next launch check of this thread)
         return {"code": int(rc), "text": self.lib.hsm_last_error().decode() if rc != 0 else ""}
 
     def run(self, case_list):
