@@ -103,6 +103,9 @@ SIGNATURES = {
     "hsm_occupancy_changes": (_i, [_vp, _i, _vp, _i32p]),
     "hsm_occupancy_restart": (_i, [_vp, _i]),
     "hsm_ray_distances": (_i, [_vp, _i, _f, _f, _f, _i, _f32p, _f32p, _f32p, _f32p]),
+    "hsm_ray_distances_device": (_i, [_vp, _i, _f, _f, _f, _i, _vp, _vp, _vp, _vp, _vp]),
+    "hsm_cast_scans_device": (_i, [_vp, _i, _i, _vp, _vp, _i, _f, _vp, _vp, _vp]),
+    "hsm_cast_scans": (_i, [_vp, _i, _i, _vp, _vp, _i, _f, _vp, _vp]),
     "hsm_score_batch_device": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "hsm_select_best_device": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "hsm_match_score_batch_device": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp]),
@@ -532,6 +535,37 @@ class MapRepMultiMap:
             _check(self._lib.hsm_ray_distances(self._h, level, ox, oy, res, b.shape[0], b.reshape(-1), e.reshape(-1),
                                                dist, hit.reshape(-1)), "hsm_ray_distances")
         return dist, hit
+
+    def ray_distances_device(self, level, n, d_begin_world, d_end_world, d_out_dist, d_out_hit=0, origin_xy=None, resolution=None,
+                             stream=0):
+        """Raw device pointers (ints), asynchronous on ``stream``: ``ray_distances`` for ``n`` rays, on the level's own
+        metadata unless ``origin_xy`` / ``resolution`` say otherwise."""
+        ox, oy, res = self.map_metadata(level)
+        if origin_xy is not None:
+            ox, oy = origin_xy
+        if resolution is not None:
+            res = resolution
+        _check(self._lib.hsm_ray_distances_device(self._h, level, ox, oy, res, n, d_begin_world or None, d_end_world or None,
+                                                  d_out_dist or None, d_out_hit or None, stream or None),
+               "hsm_ray_distances_device")
+
+    def cast_scans_device(self, level, batch, d_poses_world, d_beam_angles, n, range_max, d_out_ranges, d_out_hit=0, stream=0):
+        """Raw device pointers (ints), asynchronous on ``stream``: the expected range of each of ``n`` beams (angles in the sensor
+        frame) from each of ``batch`` sensor poses on ``level``; -resolution where a beam hits nothing."""
+        _check(self._lib.hsm_cast_scans_device(self._h, level, batch, d_poses_world or None, d_beam_angles or None, n, range_max,
+                                               d_out_ranges or None, d_out_hit or None, stream or None), "hsm_cast_scans_device")
+
+    def cast_scans(self, level, poses_world, beam_angles, range_max):
+        """Host arrays: -> (ranges[B, n], hit[B, n, 2]; NaN where no hit)"""
+        p = np.ascontiguousarray(poses_world, np.float32).reshape(-1, 3)
+        a = np.ascontiguousarray(beam_angles, np.float32).reshape(-1)
+        B, n = p.shape[0], a.shape[0]
+        ranges = np.empty((B, n), np.float32)
+        hit = np.full((B, n, 2), np.nan, np.float32)
+        if B and n:
+            _check(self._lib.hsm_cast_scans(self._h, level, B, _addr(p), _addr(a), n, range_max, _addr(ranges), _addr(hit)),
+                   "hsm_cast_scans")
+        return ranges, hit
 
     def occupancy_grid(self, level=0):
         """publishMap's int8 grid: -1 unknown, 0 free, 100 occupied"""

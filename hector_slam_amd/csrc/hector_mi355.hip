@@ -769,10 +769,11 @@ int reset_update_gate(hsm_ctx* h) {
 
 }  // namespace
 
-// Orders a launch on `s` that READS the map (a batched match, a batched score) against the map updates, which are queued on the
-// context's own stream.  *mark = the stream's record where the launch has to be remembered for the next update
-// (`(*mark)->pending = true` once it is queued), nullptr where nothing is to be remembered (the context's own stream; a capture).
-static int order_map_reader(hsm_ctx* h, hipStream_t s, const char* who, hsm_ctx::ForeignStream** mark) {
+// Orders a launch on `s` that READS the map (a batched match, a batched score, the rays of rays.hip) against the map updates,
+// which are queued on the context's own stream.  *mark = the stream's record where the launch has to be remembered for the next
+// update (`(*mark)->pending = true` once it is queued), nullptr where nothing is to be remembered (the context's own stream; a
+// capture).
+int hsm_host::order_map_reader(hsm_ctx* h, hipStream_t s, const char* who, hsm_ctx::ForeignStream** mark) {
   *mark = nullptr;
   if (s == h->stream) return HSM_OK;
   // A caller-owned stream is not ordered against the context's own one, on which map updates are queued
@@ -944,6 +945,7 @@ int hsm_create(float map_resolution, int size_x, int size_y, unsigned levels, fl
   if (const char* env = getenv("HSM_WG_SYNC")) h->wg_sync = atoi(env) != 0;
   if (const char* env = getenv("HSM_SPB_LARGE")) h->spb_large = atoi(env) == 8 ? 8 : 4;
   if (const char* env = getenv("HSM_XCD_CHUNK")) h->xcd_chunk = atoi(env) > 0 ? atoi(env) : 0;
+  if (const char* env = getenv("HSM_CAST_FORM")) h->cast_form = !strcmp(env, "wave") ? 0 : (!strcmp(env, "lane") ? 1 : -1);
   if (const char* env = getenv("HSM_XCD_CHUNK_EXACT")) h->xcd_chunk_exact = atoi(env) > 0 ? atoi(env) : 0;
 
 #define CREATE_TRY(expr)                                   \

@@ -5,8 +5,10 @@
 //   ingest.hip              raw sensor data: the LaserScan / point-cloud conversions of one scan and of batches, in front of
 //                           the core's match, update and SLAM loop (ingest_kernels.h)
 //   occupancy.hip           a level as the node's occupancy grid, whole or its changed cells only (occupancy_kernels.h)
-//   probes.hip              the host-array probes (likelihood, covariance, ray distances, Hessian), level downloads and uploads,
+//   probes.hip              the host-array probes (likelihood, covariance, Hessian), level downloads and uploads,
 //                           the hsm_debug_* test hooks, and the kernels only these launch (probe_kernels.h)
+//   rays.hip                what a laser would see on a level: ray distances of arrays of rays (host or device pointers) and
+//                           expected scans cast from batches of poses (ray_kernels.h)
 //   group.hip               the multi-GPU group (hsm_group_*, hsm_shard_bounds): host code only, librccl opened on demand
 //   match_exact_cached.hip  the exact-order texel-cache batch forms (gn_match_exact.h: the headline kernel and its chain-wavefront forms)
 //   match_teams.hip         the team forms (gn_match_kernel, 1..16 wavefronts per scan) and the fast texel-cache forms
@@ -352,6 +354,7 @@ struct hsm_ctx {
   int compute_units = 256;   // of this device (hsm_create)
   int exact_split_tail = 1;  // env HSM_EXACT_SPLIT_TAIL=0: one launch however the batch divides into generations
   int exact_chain_wave = 1;  // env HSM_EXACT_CHAIN_WAVE=0: no chain-only wavefront, teams of wavefronts for batches below 4096 scans (rounds 3-4)
+  int cast_form = -1;            // env HSM_CAST_FORM=wave|lane: hsm_cast_scans* take that walk whatever the fan (-1 = by its length, rays.hip)
   const char* last_kernel = "";  // name of the matcher kernel the last launch used (hsm_last_launch_kernel)
   unsigned coop_fallbacks = 0;  // dense single-scan matches re-run on one workgroup after an exchange timeout (match_single)
   // ... and the back-off that follows: after a timeout the multi-workgroup form is skipped for the next coop_skip matches (1, 2, 4, ...
@@ -428,6 +431,7 @@ LevelView level_view(const Level& L, float pt_scale, int gn_steps);
 int rebuild_probability(hsm_ctx* h, Level& L);
 void whole_level_changed(Level& L, bool mirror = true);
 int order_after_foreign_match(hsm_ctx* h);
+int order_map_reader(hsm_ctx* h, hipStream_t s, const char* who, hsm_ctx::ForeignStream** mark);
 int merge_device_boxes(hsm_ctx* h);
 int fold_gate_counters(hsm_ctx* h, GateState* state = nullptr);
 int match_batch_device_nolock(hsm_ctx* h, int batch, const float* d_begin_world, const float* d_pts_xy, const int* d_scan_offsets,

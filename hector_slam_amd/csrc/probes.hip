@@ -1,8 +1,8 @@
 // probes.hip -- the entries of the C ABI (include/hector_mi355/capi.h) that look INTO a context and are never timed: the
-// host-array probes of the matcher's sums (likelihood, residual, covariance, Hessian, single beams), ray distances, a level's
-// planes down and up, its boxes, and the hsm_debug_* test hooks.  Each one ends in a wait for the context's stream.  The kernel
-// templates are gn_match.h's; the kernels nothing else launches are in probe_kernels.h.  What these entries need of the core
-// runtime (hector_mi355.hip) is declared in hsm_ctx.h.
+// host-array probes of the matcher's sums (likelihood, residual, covariance, Hessian, single beams), a level's planes down and
+// up, its boxes, and the hsm_debug_* test hooks.  Each one ends in a wait for the context's stream.  The kernel templates are
+// gn_match.h's; the kernels nothing else launches are in probe_kernels.h.  What these entries need of the core runtime
+// (hector_mi355.hip) is declared in hsm_ctx.h.  (Ray distances are in rays.hip.)
 #include <hip/hip_runtime.h>
 #include <math.h>
 
@@ -76,39 +76,6 @@ int hsm_covariance_for_poses(hsm_ctx* h, int level, int batch, const float* pose
                        batch, staged<float2>(base, st.pts), n, factor, Lv.cell_length, staged<float>(base, st.cov_map),
                        staged<float>(base, st.cov_world), staged<float>(base, st.lh7));
   });
-  HIP_TRY(hipGetLastError());
-  if (int rc = stage_copy_out(st.plan, base, h->stream)) return rc;
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  return HSM_OK;
-}
-
-int hsm_ray_distances(hsm_ctx* h, int level, float origin_x, float origin_y, float resolution, int n,
-                      const float* begin_world_xy, const float* end_world_xy, float* out_dist, float* out_hit_xy) {
-  if (int rc = valid_level(h, level)) return rc;
-  if (n < 0 || (n > 0 && (!begin_world_xy || !end_world_xy || !out_dist)) || !(resolution > 0.0f))
-    return fail(HSM_ERR_INVALID, "hsm_ray_distances: bad argument");
-  if (n == 0) return HSM_OK;
-  std::lock_guard<std::mutex> lk(h->mu);
-  if (int rc = select_device(h)) return rc;
-  const RayDistancesStage st = ray_distances_stage(n, begin_world_xy, end_world_xy, out_dist, out_hit_xy);
-  if (int rc = h->d_batch.reserve(st.plan.total())) return rc;
-  char* base = h->d_batch;
-  RayQueryParams P;
-  const Level& L = h->levels[level];
-  P.logodds = L.d_logodds;
-  P.sx = L.sx;
-  P.sy = L.sy;
-  P.origin_x = origin_x;
-  P.origin_y = origin_y;
-  P.scale = resolution;
-  P.inv_scale = 1.0f / resolution;  // CoordinateTransformer::setTransforms, HectorMapTools.h:64
-  P.begin_world = staged<float2>(base, st.begin);
-  P.end_world = staged<float2>(base, st.end);
-  P.out_hit = staged<float2>(base, st.hit);  // in/out: rays without a hit keep the caller's values
-  P.out_dist = staged<float>(base, st.dist);
-  P.n = n;
-  if (int rc = stage_copy_in(st.plan, base, h->stream)) return rc;
-  hipLaunchKernelGGL(ray_distance_kernel, dim3((n + 3) / 4), dim3(256), 0, h->stream, P);
   HIP_TRY(hipGetLastError());
   if (int rc = stage_copy_out(st.plan, base, h->stream)) return rc;
   HIP_TRY(hipStreamSynchronize(h->stream));

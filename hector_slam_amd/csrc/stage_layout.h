@@ -208,6 +208,23 @@ inline RayDistancesStage ray_distances_stage(int n, const float* begin, const fl
   return s;
 }
 
+// hsm_cast_scans (d_batch): sensor poses[batch * 3] | beam angles[n] | ranges[batch * n] | hit points[batch * n * 2].  The hit
+// points go in and out like hsm_ray_distances's; without the caller's array the region is not carved and the kernel gets none.
+struct CastScansStage {
+  StagePlan plan;
+  size_t poses, angles, ranges, hit;
+};
+
+inline CastScansStage cast_scans_stage(int batch, int n, const float* poses, const float* angles, float* out_ranges, float* out_hit) {
+  const size_t bn = (size_t)batch * (size_t)n;
+  CastScansStage s;
+  s.poses = s.plan.add((size_t)batch * 3 * sizeof(float), poses);
+  s.angles = s.plan.add((size_t)n * sizeof(float), angles);
+  s.ranges = s.plan.add(bn * sizeof(float), nullptr, out_ranges);
+  s.hit = s.plan.add(out_hit ? bn * 2 * sizeof(float) : 0, out_hit, out_hit);
+  return s;
+}
+
 // hsm_match_batch_ranges_tf (d_rbatch): transforms[batch or 1][12] | start poses | poses | covariances | counts | origos |
 // offsets[batch + 1] | raw ranges | endpoints[max(batch * n, 1)]
 struct RangesTfStage {

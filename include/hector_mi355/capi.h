@@ -713,6 +713,49 @@ int hsm_covariance_for_poses(hsm_ctx* h, int level, int batch, const float* pose
  * Host pointers; out_hit_xy may be NULL. */
 int hsm_ray_distances(hsm_ctx* h, int level, float origin_x, float origin_y, float resolution, int n,
                       const float* begin_world_xy, const float* end_world_xy, float* out_dist, float* out_hit_xy);
+/* ---- expected scans on the device-resident map (extension: the reference answers one ray per service call) ----
+ * hsm_ray_distances with DEVICE pointers, asynchronous on `stream`: the same kernel walk and, for every ray of finite
+ * coordinates, the same bits.  A ray with a non-finite end-point coordinate is "without a hit" here (-resolution, hit untouched);
+ * hsm_ray_distances leaves that case to the device's float -> int conversion.  d_out_hit_xy may be NULL.
+ * Ordering, capture and locking: the contract of hsm_score_batch_device, through the same bookkeeping -- reads the map only,
+ * needs no workspace, keeps no per-stream or per-context device state; ordered behind every map update queued on the context so
+ * far and the next update behind it; under graph capture one kernel launch and no allocation; the retained and the ingested scan
+ * are not touched.  hsm_last_launch_kernel: "ray_distance_kernel".
+ * HSM_ERR_INVALID (nothing launched): NULL context, level out of range, n < 0, NULL begin, end or distances where n > 0,
+ * resolution not > 0.  n == 0: HSM_OK.
+ * Not built: replay through hsm_group_*, a C++ facade entry. */
+int hsm_ray_distances_device(hsm_ctx* h, int level, float origin_x, float origin_y, float resolution, int n,
+                             const float* d_begin_world_xy, const float* d_end_world_xy, float* d_out_dist,
+                             float* d_out_hit_xy, void* stream);
+/* replaces: getDist for the n beams of a scan fan at each of `batch` sensor poses -- batch * n rays that never exist in memory.
+ * DEVICE pointers:
+ *   d_poses_world [batch*3]  the SENSOR's world pose (x, y, theta); the caller folds in any mount offset
+ *   d_beam_angles [n]        sensor frame, rad -- a table, so the caller decides how the angles were accumulated (the node adds
+ *                            angle_increment in fp32)
+ * Beam i of pose b, every operation fp32 and un-fused, in this order:
+ *   a = theta + beam_angles[i];  (s, c) = sincosf(a) (glibc's, bit for bit);
+ *   begin = (px, py);  end = (px + range_max * c, py + range_max * s);  getDist(begin, end)
+ * on the level's OWN OccupancyGrid metadata, computed once on the host in fp32: origin = getWorldCoords(0,0) - cell * 0.5f per
+ * axis, resolution = the cell length (HectorMappingRos.cpp:546-553).
+ *   d_out_ranges [batch*n]   [b*n+i] = resolution * (float)(int)|begin cell - hit cell|, or -resolution WITHOUT A HIT: no occupied
+ *                            cell among the steps walked, either end point outside the level (so a beam that leaves the map
+ *                            reports no hit even where it crosses a wall first -- the reference's behaviour at the map's edge),
+ *                            the walk's cap of 5000 steps (bresenham2D's max_length: an occupied cell further along is not
+ *                            seen), or a non-finite end-point coordinate (a non-finite pose)
+ *   d_out_hit_xy [batch*n*2] or NULL: the hit cell's world coordinates; left untouched for a ray without a hit
+ * One kernel launch in one of two shapes that give the same bits -- a lane per beam with 64 adjacent beams of a pose in a
+ * wavefront, or a wavefront per beam for fans of fewer than 32 beams; hsm_last_launch_kernel says which ("cast_scans_lane_kernel" /
+ * "cast_scans_wave_kernel"), env HSM_CAST_FORM=wave|lane at hsm_create forces one.
+ * Ordering, capture and locking: as hsm_ray_distances_device.
+ * HSM_ERR_INVALID (nothing launched): NULL context, level out of range, batch < 0, n < 0, batch * n > INT_MAX, range_max
+ * negative or non-finite, NULL poses, angles or ranges where batch * n > 0.  batch == 0 or n == 0: HSM_OK, nothing launched.
+ * Not built: replay through hsm_group_*, a C++ facade entry. */
+int hsm_cast_scans_device(hsm_ctx* h, int level, int batch, const float* d_poses_world, const float* d_beam_angles, int n,
+                          float range_max, float* d_out_ranges, float* d_out_hit_xy, void* stream);
+/* the same with HOST pointers: copies in, the kernel on the context's stream, copies out; synchronous.  out_hit_xy is in/out
+ * (a ray without a hit keeps the caller's values) and may be NULL. */
+int hsm_cast_scans(hsm_ctx* h, int level, int batch, const float* poses_world, const float* beam_angles, int n,
+                   float range_max, float* out_ranges, float* out_hit_xy);
 /* replaces: publishMap's cell loop (HectorMappingRos.cpp:449-468) with LogOddsCell::isFree/isOccupied
  * (GridMapLogOdds.h:76-84): -1 unknown, 0 free (logOdds < 0), 100 occupied (logOdds > 0).
  * out: host, sx*sy bytes, row major. */
