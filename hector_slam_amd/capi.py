@@ -151,6 +151,9 @@ SIGNATURES = {
     "hsm_download_cells": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i]),
     "hsm_last_update_bbox": (_i, [_vp, _i, _i32p]),
     "hsm_take_dirty_bbox": (_i, [_vp, _i, _i32p]),
+    "hsm_copy_map": (_i, [_vp, _vp]),
+    "hsm_copy_map_boxes": (_i, [_vp, _vp, _vp]),
+    "hsm_group_sync_maps": (_i, [_vp, _i, _vp]),
     "hsm_download_prob": (_i, [_vp, _i, _f32p]),
     "hsm_hessian_derivs": (_i, [_vp, _i, _f32p, _vp, _i, _f32p, _f32p]),
     "hsm_eval_beams": (_i, [_vp, _i, _f32p, _vp, _i, _vp]),
@@ -424,6 +427,17 @@ class MapRepMultiMap:
         bb = np.empty(4, np.int32)
         _check(self._lib.hsm_take_dirty_bbox(self._h, level, bb), "hsm_take_dirty_bbox")
         return bb
+
+    def copy_map_from(self, src, boxes=None):
+        """this context's pyramid becomes `src`'s, on the device (hsm_copy_map), or with boxes [levels, 4] = x0, y0, x1, y1
+        inclusive its cells inside one box per level (hsm_copy_map_boxes); queued, no host wait"""
+        if boxes is None:
+            _check(self._lib.hsm_copy_map(self._h, src._h), "hsm_copy_map")
+            return
+        bx = np.ascontiguousarray(boxes, np.int32).reshape(-1)
+        if bx.size != 4 * self.getMapLevels():
+            raise ValueError("boxes must hold x0, y0, x1, y1 for every level")
+        _check(self._lib.hsm_copy_map_boxes(self._h, src._h, bx.ctypes.data), "hsm_copy_map_boxes")
 
     def download_prob(self, level):
         sx, sy, _, _ = self.level_info(level)
@@ -1046,6 +1060,14 @@ class MapRepGroup:
 
     def synchronize(self):
         _check(self._lib.hsm_group_synchronize(self._g), "hsm_group_synchronize")
+
+    def sync_maps(self, from_, boxes=None):
+        """replica `from_`'s pyramid (boxes [levels, 4]: its cells inside one box per level) into every other replica, on the
+        device; asynchronous (synchronize() waits)"""
+        bx = None if boxes is None else np.ascontiguousarray(boxes, np.int32).reshape(-1)
+        if bx is not None and bx.size != 4 * self.member(0).getMapLevels():
+            raise ValueError("boxes must hold x0, y0, x1, y1 for every level")
+        _check(self._lib.hsm_group_sync_maps(self._g, from_, None if bx is None else bx.ctypes.data), "hsm_group_sync_maps")
 
     def set_gather(self, mode: int):
         """GATHER_AUTO / GATHER_DIRECT / GATHER_RCCL / GATHER_PEER for match_batch_device (DIRECT or RCCL asked for explicitly raise

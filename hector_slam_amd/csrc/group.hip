@@ -529,6 +529,21 @@ const float* hsm_group_gathered(hsm_group* g, int replica, int want_cov) {
   return want_cov ? g->d_all_cov[(size_t)replica] : g->d_all_pose[(size_t)replica];
 }
 
+// Replicas drift apart once one of them integrates scans through an entry the group does not replay (the device-resident
+// writers): replica `from`'s pyramid, or one cell box per level of it, into every other replica (map_copy.hip), each copy queued
+// by its replica's thread.
+int hsm_group_sync_maps(hsm_group* g, int from, const int* boxes) {
+  if (!g || g->members.empty()) return fail(HSM_ERR_INVALID, "null group");
+  const int R = (int)g->members.size();
+  if (from < 0 || from >= R) return fail(HSM_ERR_INVALID, "hsm_group_sync_maps: `from` is no replica of the group");
+  std::lock_guard<std::mutex> glk(g->mu);
+  hsm_ctx* src = g->members[(size_t)from];
+  return group_parallel(g, [&](int r) -> int {
+    if (r == from) return HSM_OK;
+    return boxes ? hsm_copy_map_boxes(g->members[(size_t)r], src, boxes) : hsm_copy_map(g->members[(size_t)r], src);
+  });
+}
+
 int hsm_group_synchronize(hsm_group* g) {
   if (!g) return fail(HSM_ERR_INVALID, "null group");
   for (hsm_ctx* h : g->members)

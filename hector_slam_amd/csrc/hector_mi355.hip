@@ -947,6 +947,7 @@ int hsm_create(float map_resolution, int size_x, int size_y, unsigned levels, fl
   if (const char* env = getenv("HSM_XCD_CHUNK")) h->xcd_chunk = atoi(env) > 0 ? atoi(env) : 0;
   if (const char* env = getenv("HSM_CAST_FORM")) h->cast_form = !strcmp(env, "wave") ? 0 : (!strcmp(env, "lane") ? 1 : -1);
   if (const char* env = getenv("HSM_XCD_CHUNK_EXACT")) h->xcd_chunk_exact = atoi(env) > 0 ? atoi(env) : 0;
+  if (const char* env = getenv("HSM_COPY_STAGE")) h->copy_stage = atoi(env) != 0;
 
 #define CREATE_TRY(expr)                                   \
   do {                                                     \
@@ -1046,7 +1047,8 @@ void hsm_destroy(hsm_ctx* h) {
   TEARDOWN(log, hipFree(h->d_gate));
   TEARDOWN(log, hipFree(h->d_pub_boxes));
   if (h->h_small) TEARDOWN(log, hipHostFree(h->h_small));
-  for (hipEvent_t e : {h->copy_evt, h->evt_updates, h->evt_foreign, h->evt_inputs, h->evt_slam_done, h->upd_evt[0], h->upd_evt[1]})
+  for (hipEvent_t e : {h->copy_evt, h->evt_updates, h->evt_foreign, h->evt_inputs, h->evt_slam_done, h->upd_evt[0], h->upd_evt[1],
+                       h->evt_copy_read, h->evt_copy_src})
     if (e) TEARDOWN(log, hipEventDestroy(e));
   if (h->copy_stream) TEARDOWN(log, hipStreamDestroy(h->copy_stream));
   if (h->stream) TEARDOWN(log, hipStreamDestroy(h->stream));

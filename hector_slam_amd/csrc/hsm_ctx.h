@@ -9,6 +9,8 @@
 //                           the hsm_debug_* test hooks, and the kernels only these launch (probe_kernels.h)
 //   rays.hip                what a laser would see on a level: ray distances of arrays of rays (host or device pointers) and
 //                           expected scans cast from batches of poses (ray_kernels.h)
+//   map_copy.hip            a pyramid, or one cell box per level, copied from another context's planes on the device
+//                           (map_copy_kernels.h; the box arithmetic: map_copy_box.h)
 //   group.hip               the multi-GPU group (hsm_group_*, hsm_shard_bounds): host code only, librccl opened on demand
 //   match_exact_cached.hip  the exact-order texel-cache batch forms (gn_match_exact.h: the headline kernel and its chain-wavefront forms)
 //   match_teams.hip         the team forms (gn_match_kernel, 1..16 wavefronts per scan) and the fast texel-cache forms
@@ -308,6 +310,12 @@ struct hsm_ctx {
   int coop_min_beams = 4096;    // single scans at least this long take the multi-workgroup matcher (env HSM_COOP_MIN)
   bool coop_tagged = true;      // env HSM_COOP_TAGGED=0: the counter grid barrier instead of the tagged-record exchange
   Buf<char> d_cells{&bufs};  // interleaved {logodds, updateIndex} staging for hsm_download_cells
+  // hsm_copy_map* (map_copy.hip).  As the destination: the staging patch of the cross-device route (4-byte elements, laid out by
+  // map_copy_box.h copy_patch_at), and the event on the own stream behind the last read of the source, which the source's
+  // stream waits for.  As the source: the event on the own stream the destination's stream waits for.
+  Buf<float> d_copy_patch{&bufs};
+  hipEvent_t evt_copy_read = nullptr, evt_copy_src = nullptr;
+  bool copy_stage = false;   // env HSM_COPY_STAGE=1: copies INTO this context take the staged route from the same device too
   int bpl_override = -1;  // 0 = force the memory loop (env HSM_BPL=0), -1 = auto
   int xcd_chunk_exact = 0;       // env HSM_XCD_CHUNK_EXACT: the same for the exact-order texel-cache form (0 = contiguous eighths, its default)
   int xcd_chunk = 16;            // env HSM_XCD_CHUNK: workgroups per chunk of the chunked-cyclic batch mapping (0 = contiguous eighths)

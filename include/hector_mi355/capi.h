@@ -384,6 +384,12 @@ int hsm_group_match_batch_device(hsm_group* g, const int* counts, const float* c
                                  float* d_out_pose_all, float* d_out_cov_all);
 /* wait for all queued work of every replica */
 int hsm_group_synchronize(hsm_group* g);
+/* Replica `from`'s pyramid into every other replica: hsm_copy_map (boxes == NULL: the whole pyramid) or hsm_copy_map_boxes with
+ * `boxes` [levels * 4, host], each queued by its replica's thread; returns when all are queued (hsm_group_synchronize waits).
+ * The remedy after entries the group does not replay -- once one replica has integrated scans through hsm_update_by_scans_device*
+ * or hsm_slam_*_device, pass the boxes of its hsm_take_dirty_bbox.  HSM_ERR_INVALID: a NULL group, `from` out of range, and what
+ * the copies refuse. */
+int hsm_group_sync_maps(hsm_group* g, int from, const int* boxes);
 /* hsm_match_batch over all replicas: scans [B*r/R, B*(r+1)/R) go to replica r */
 int hsm_group_match_batch(hsm_group* g, int batch, const float* begin_world, const float* pts_xy,
                           const int* scan_offsets, int shared_n, float* out_pose, float* out_cov);
@@ -473,6 +479,43 @@ int hsm_last_update_bbox(const hsm_ctx* h, int level, int bbox[4]);
 /* union of the cell boxes touched on `level` since the previous call (reset/upload mark the whole level),
  * then cleared: what a host mirror has to re-download.  x1 < x0 when nothing changed. */
 int hsm_take_dirty_bbox(hsm_ctx* h, int level, int bbox[4]);
+
+/* ---- a pyramid from one context into another, on the device ----------------------------------------------------------------
+ * replaces: GridMapBase's copy constructor and operator= (HSL/map/GridMapBase.h:173-205: the cells, the dimensions, the
+ * transforms and the update index), for a map that lives in HBM: fork a map per hypothesis, keep a checkpoint, roll an update
+ * back, bring the replicas of a group back in line.  No host trip and no host wait.
+ *
+ * hsm_copy_map: afterwards every level of `dst` is what it is in `src` -- the log-odds and the stamps; the probabilities (and,
+ * in the quad layout, the texels), bit for bit what a rebuild from those log-odds gives; the level's update counters
+ * (currUpdateIndex, currMarkOccIndex, currMarkFreeIndex, lastUpdateIndex) and whether restored stamps are still ahead of the
+ * counter, so a cell frozen in `src` (hsm_upload_level) is frozen in `dst`, and every later update gives the same bits in both.
+ * `dst` keeps what is its own: the update factors, the update gate's state, the retained and the ingested scan, parity, layout
+ * and batch-order settings.  Every level of `dst` is marked wholly changed, for hsm_take_dirty_bbox and for
+ * hsm_occupancy_changes*.
+ *
+ * hsm_copy_map_boxes: the same for the cells of ONE box per level, boxes[4 * level ..] = x0, y0, x1, y1 inclusive, in HOST
+ * memory; a level whose box is empty (x1 < x0) copies no cell.  The counters are copied as above.  The result is the full copy
+ * if -- and only if -- `dst` equalled `src` outside the boxes: the boxes hsm_take_dirty_bbox(src, level) has returned since the
+ * last copy into `dst` are such boxes.  In the quad layout the texels of each box grown by one cell towards lower x and y
+ * (clamped to the level) are refreshed: texel (x, y) holds P(x+1, y), P(x, y+1) and P(x+1, y+1) as well.  `dst`'s dirty box and
+ * publish box widen by each copied box.
+ *
+ * Ordering: the copy is QUEUED on `dst`'s stream and the call returns.  It reads `src` behind every update queued on `src` so
+ * far, and writes `dst` behind the batched matches callers' streams may still be running on `dst`; every later hsm_* call on
+ * `dst` is ordered behind it, and `src`'s stream -- so its next update -- is ordered behind the read.  If `src` has gated updates
+ * outstanding (hsm_update_by_scans_device_gated, hsm_slam_*), the call first WAITS for `src`'s stream to fetch their count;
+ * likewise for `dst`.  Two threads may copy in opposite directions (the contexts' locks are taken in address order).
+ *
+ * HSM_ERR_INVALID, nothing queued, nothing changed: a NULL context; dst == src; contexts that differ in level count, sizes,
+ * resolution, offsets or layout; a box that is not empty and reaches outside its level; boxes == NULL (hsm_copy_map_boxes); a
+ * caller's stream that either context has matched on being captured into a graph (copies are not captured, like every writer).
+ *
+ * Contexts on the same device: the kernel reads `src`'s planes directly.  On different devices the boxes' rows are first copied
+ * (hipMemcpy2DAsync, on `dst`'s stream) into a staging patch that `dst` owns and grows on demand, and the same kernel reads the
+ * patch.  HSM_COPY_STAGE=1 in the environment at `dst`'s hsm_create forces that route on one device as well, and that is the only
+ * way it has been exercised: the cross-device copy itself has not been run. */
+int hsm_copy_map(hsm_ctx* dst, hsm_ctx* src);
+int hsm_copy_map_boxes(hsm_ctx* dst, hsm_ctx* src, const int* boxes);
 
 /* ---- the rows either side of the path; reference = the ROS node,
  *      hector_mapping/src/HectorMappingRos.cpp.  Optional: the facade does not need them. ---- */

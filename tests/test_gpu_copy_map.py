@@ -1,0 +1,449 @@
+"""A pyramid, or one cell box per level, copied between contexts on the device (hsm_copy_map, hsm_copy_map_boxes,
+hsm_group_sync_maps) against the CPU checkers bit for bit: no tolerance anywhere in this file.
+
+3-level pyramids of 128 x 128 cells (0.1 m; a 10 m x 8 m synthetic room, 181-beam scans), both layouts, the library's default
+parity; one-level maps of 38 x 25 and 40 x 40 cells for the hand-made boxes (an even width that is no multiple of 4 with an odd
+height, and a multiple of 4); stamp_cases' restored levels for the stamps ahead of the counter.  The checkers' maps are built
+once per stage (so many scans of the scene's log) and shared.
+
+Every test runs on the direct route; the boxes and the shapes tests run again in a child process with HSM_COPY_STAGE=1, which
+sends every copy through the staging patch of the cross-device route (on one device).
+
+At the parent commit every test of this file fails: the entries do not exist."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import stamp_cases as sc
+from conftest import bits, oracle_kinds
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HSM_ERR_INVALID = -1
+LAYOUTS = pytest.mark.parametrize("layout", ("quad", "plane"))
+RES, SIZE, LEVELS = 0.1, 128, 3
+N_SRC, N_MORE, N_BOX, N_HYP = 12, 4, 3, 16
+ZERO3 = np.zeros(3, np.float32)
+
+
+@pytest.fixture(scope="module")
+def capi():
+    import torch
+    assert torch.cuda.is_available(), "gpu-marked tests need a HIP device"
+    from hector_slam_amd import capi as m
+    m.load_library()
+    return m
+
+
+@pytest.fixture(scope="module")
+def scene():
+    from hector_slam_amd import synth
+    return synth.make_scene(n_beams=181, map_size=SIZE, levels=LEVELS, resolution=RES, n_build=N_SRC + N_MORE + N_BOX, n_query=32,
+                            room=(10.0, 8.0), seed=515, range_max=30.0)
+
+
+@pytest.fixture(scope="module")
+def stages(scene, oracle_mod):
+    """stage(kind, n): the checker of `kind` after the first n scans of the scene's log -- built once, never changed afterwards"""
+    made = {}
+
+    def stage(kind, n):
+        if (kind, n) not in made:
+            o = oracle_mod.Oracle(kind, RES, SIZE, SIZE, LEVELS)
+            o.set_update_factor_free(0.4)
+            o.set_update_factor_occupied(0.9)
+            o.build_map(scene.build_poses[:n], scene.build_scans[:n])
+            made[(kind, n)] = o
+        return made[(kind, n)]
+    yield stage
+    for o in made.values():
+        o.close()
+
+
+def dev(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
+
+
+def pack(scans):
+    offs = np.zeros(len(scans) + 1, np.int32)
+    offs[1:] = np.cumsum([len(s) for s in scans])
+    return np.ascontiguousarray(np.concatenate(scans), np.float32), offs
+
+
+def new_ctx(capi, layout, sx=SIZE, sy=SIZE, levels=LEVELS, res=RES, free=0.4, occ=0.9):
+    g = capi.MapRepMultiMap(res, sx, sy, levels, layout=capi.LAYOUT_QUAD if layout == "quad" else capi.LAYOUT_PLANE)
+    g.setUpdateFactorFree(free)
+    g.setUpdateFactorOccupied(occ)
+    return g
+
+
+def single_update(capi, g, pose, pts):
+    """hsm_retain_scan (what matchData leaves for the coarse levels) + hsm_update_by_scan, which returns when it is queued"""
+    a = np.ascontiguousarray(pts, np.float32).reshape(-1, 2)
+    capi._check(g._lib.hsm_retain_scan(g._h, a.ctypes.data, a.shape[0], np.zeros(2, np.float32)), "hsm_retain_scan")
+    g.updateByScan(a, pose)
+
+
+def integrate(capi, g, scene, first, last):
+    for k in range(first, last):
+        single_update(capi, g, scene.build_poses[k], scene.build_scans[k])
+
+
+def state(g):
+    """per level (log-odds, stamps, probabilities, update index)"""
+    return [g.download_level(lvl) + (g.download_prob(lvl), g.getUpdateIndex(lvl)) for lvl in range(g.getMapLevels())]
+
+
+def assert_same_state(a, b, what):
+    for lvl, (x, y) in enumerate(zip(a, b)):
+        w = (what, "level", lvl)
+        assert np.array_equal(bits(x[0]), bits(y[0])), w + ("log odds", int((bits(x[0]) != bits(y[0])).sum()))
+        assert np.array_equal(x[1], y[1]), w + ("stamps", int((x[1] != y[1]).sum()))
+        assert np.array_equal(bits(x[2]), bits(y[2])), w + ("probabilities", int((bits(x[2]) != bits(y[2])).sum()))
+        assert x[3] == y[3], w + ("update index", x[3], y[3])
+
+
+def assert_state_is_checkers(om, st, checkers, n_updates, what):
+    """checkers: {kind: Oracle}; the probabilities against the checker's expf of its own log-odds"""
+    for lvl, (lo, ui, prob, idx) in enumerate(st):
+        for kind, o in checkers.items():
+            w = (what, kind, "level", lvl)
+            lo_o, ui_o = o.download_level(lvl)
+            assert np.array_equal(bits(lo), bits(lo_o)), w + ("log odds", int((bits(lo) != bits(lo_o)).sum()))
+            assert np.array_equal(ui, ui_o), w + ("stamps", int((ui != ui_o).sum()))
+            _, p = om.libm_expf(lo_o.reshape(-1), kind)
+            assert np.array_equal(bits(prob).reshape(-1), bits(p)), w + ("probabilities",)
+        assert idx == n_updates - 1, (what, lvl, "update index", idx, n_updates)
+
+
+def assert_matches_are_checkers(scene, got, checkers, what):
+    pose, cov = got
+    for kind, o in checkers.items():
+        for k in range(N_HYP):
+            po, co = o.match(scene.query_init[k], scene.query_scans[k])
+            assert np.array_equal(bits(pose[k]), bits(po)) and np.array_equal(bits(cov[k]), bits(co)), (what, kind, k, pose[k], po)
+
+
+def match_hypotheses(g, scene):
+    pts, offs = pack(scene.query_scans[:N_HYP])
+    return g.match_batch(scene.query_init[:N_HYP], pts, offs)
+
+
+def seam_points(sx, sy, box):
+    """map coordinates on the cells at x0-1, x0, x1, x1+1 (and likewise in y) of a box, inside the sampler's bounds, off the
+    cell centres so that all four corners of a texel weigh in"""
+    x0, y0, x1, y1 = box
+    xs = [x for x in (x0 - 1, x0, x1, x1 + 1) if 0 <= x <= sx - 2]
+    ys = [y for y in (y0 - 1, y0, y1, y1 + 1) if 0 <= y <= sy - 2]
+    along_y = np.unique(np.clip(np.linspace(y0 - 1, y1 + 1, 24).astype(int), 0, sy - 2))
+    along_x = np.unique(np.clip(np.linspace(x0 - 1, x1 + 1, 24).astype(int), 0, sx - 2))
+    pts = [(x + 0.3, y + 0.6) for x in xs for y in along_y] + [(x + 0.7, y + 0.2) for y in ys for x in along_x]
+    return np.ascontiguousarray(pts, np.float32)
+
+
+def whole_state_check(capi, om, scene, stages, src, dst, n, what):
+    """dst == src == the checkers after n scans: planes, probabilities, counters"""
+    checkers = {kind: stages(kind, n) for kind in oracle_kinds()}
+    s_dst, s_src = state(dst), state(src)
+    assert_same_state(s_dst, s_src, what)
+    assert_state_is_checkers(om, s_dst, checkers, n, what)
+    return checkers
+
+
+# ---- 1. clone ------------------------------------------------------------------------------------------------------------------------
+@LAYOUTS
+def test_clone_is_the_source_and_stays_it(capi, oracle_mod, scene, stages, layout):
+    src, dst = new_ctx(capi, layout), new_ctx(capi, layout)
+    integrate(capi, src, scene, 0, N_SRC)
+    dst.copy_map_from(src)  # queued behind the updates: nothing has waited for them
+    whole_state_check(capi, oracle_mod, scene, stages, src, dst, N_SRC, "clone")
+    for lvl in range(LEVELS):  # every level wholly changed, for the mirror and for the published grid
+        sx, sy, _, _ = dst.level_info(lvl)
+        assert dst.take_dirty_bbox(lvl).tolist() == [0, 0, sx - 1, sy - 1]
+        grid = np.full((sy, sx), 55, np.int8)
+        assert dst.occupancy_changes(lvl, grid).tolist() == [0, 0, sx - 1, sy - 1]
+        assert np.array_equal(grid, stages("ho", N_SRC).occupancy_grid(lvl)), lvl
+    for g in (src, dst):
+        integrate(capi, g, scene, N_SRC, N_SRC + N_MORE)
+    checkers = whole_state_check(capi, oracle_mod, scene, stages, src, dst, N_SRC + N_MORE, "clone + 4 scans")
+    got_src, got_dst = match_hypotheses(src, scene), match_hypotheses(dst, scene)
+    assert np.array_equal(bits(got_src[0]), bits(got_dst[0])) and np.array_equal(bits(got_src[1]), bits(got_dst[1]))
+    assert_matches_are_checkers(scene, got_dst, checkers, "clone + 4 scans")
+    src.close()
+    dst.close()
+
+
+# ---- 2. boxes ------------------------------------------------------------------------------------------------------------------------
+@LAYOUTS
+def test_boxes_form_ships_the_changed_cells(capi, oracle_mod, scene, stages, layout):
+    src, dst = new_ctx(capi, layout), new_ctx(capi, layout)
+    integrate(capi, src, scene, 0, N_SRC)
+    dst.copy_map_from(src)
+    grids = []
+    for lvl in range(LEVELS):  # empty the boxes of both
+        src.take_dirty_bbox(lvl)
+        dst.take_dirty_bbox(lvl)
+        sx, sy, _, _ = dst.level_info(lvl)
+        grids.append(np.full((sy, sx), 55, np.int8))
+        dst.occupancy_changes(lvl, grids[lvl])
+    integrate(capi, src, scene, N_SRC, N_SRC + N_BOX)
+    boxes = np.stack([src.take_dirty_bbox(lvl) for lvl in range(LEVELS)])
+    assert all(b[2] >= b[0] and b[3] >= b[1] for b in boxes), boxes
+    assert any((b[2] - b[0] + 1) * (b[3] - b[1] + 1) < (SIZE >> lvl) ** 2 for lvl, b in enumerate(boxes)), boxes
+    dst.copy_map_from(src, boxes)
+    n = N_SRC + N_BOX
+    checkers = whole_state_check(capi, oracle_mod, scene, stages, src, dst, n, "boxes")
+    # the texel seam: samples whose footprint straddles each box's edges
+    for lvl in range(LEVELS):
+        sx, sy, _, _ = dst.level_info(lvl)
+        pts = seam_points(sx, sy, [int(v) for v in boxes[lvl]])
+        got = dst.eval_beams(lvl, ZERO3, pts)
+        Hg, dg = dst.hessian_derivs(lvl, ZERO3, pts)
+        for kind, o in checkers.items():
+            assert np.array_equal(bits(got[:, :3]), bits(o.interp(lvl, pts))), (kind, lvl, "seam samples")
+            Ho, do = o.hessian_derivs(lvl, ZERO3, pts)
+            assert np.array_equal(bits(Hg), bits(Ho)) and np.array_equal(bits(dg), bits(do)), (kind, lvl, "seam H")
+    # dst's boxes hold the copied boxes, and its published grid becomes src's
+    for lvl in range(LEVELS):
+        assert dst.take_dirty_bbox(lvl).tolist() == boxes[lvl].tolist(), lvl
+        assert dst.occupancy_changes(lvl, grids[lvl]).tolist() == boxes[lvl].tolist(), lvl
+        assert np.array_equal(grids[lvl], stages("ho", n).occupancy_grid(lvl)), lvl
+    src.close()
+    dst.close()
+
+
+# ---- 3. shapes -----------------------------------------------------------------------------------------------------------------------
+def hand_boxes(sx, sy):
+    return {"corner 00": (0, 0, 2, 1), "corner x0": (sx - 3, 0, sx - 1, 2), "corner 0y": (0, sy - 2, 1, sy - 1),
+            "corner xy": (sx - 2, sy - 3, sx - 1, sy - 1), "one cell": (5, 7, 5, 7), "last cell": (sx - 1, sy - 1, sx - 1, sy - 1),
+            "full row": (0, 3, sx - 1, 3), "full rows": (0, 2, sx - 1, 6), "full column": (9, 0, 9, sy - 1),
+            "inner": (3, 2, 17, 11), "all but the rim": (1, 1, sx - 2, sy - 2), "whole level": (0, 0, sx - 1, sy - 1),
+            "empty": (0, 0, -1, -1), "empty, far": (2 ** 31 - 1, 2 ** 31 - 1, -1, -1)}
+
+
+def random_planes(rng, sx, sy):
+    lo = rng.uniform(-4.0, 4.0, (sy, sx)).astype(np.float32)
+    lo[rng.random((sy, sx)) < 0.2] = 0.0  # exact zeros: unknown cells
+    lo[rng.random((sy, sx)) < 0.05] = -0.0
+    ui = rng.integers(-1, 6, (sy, sx)).astype(np.int32)
+    return lo, ui
+
+
+@LAYOUTS
+@pytest.mark.parametrize("sx,sy", [(38, 25), (40, 40)])
+def test_shapes_form_hand_made_boxes(capi, layout, sx, sy):
+    rng = np.random.default_rng(100 * sx + sy)
+    src, dst, exp = (new_ctx(capi, layout, sx, sy, 1) for _ in range(3))
+    tiny = np.float32([[3.0, 0.2], [0.1, 3.0], [-3.0, 0.3]])
+    for _ in range(2):  # src's counters move; the upload leaves them where they are
+        single_update(capi, src, ZERO3, tiny)
+    src_lo, src_ui = random_planes(rng, sx, sy)
+    old_lo, old_ui = random_planes(rng, sx, sy)
+    src.upload_level(0, src_lo, src_ui)
+    assert src.getUpdateIndex(0) == 1 and dst.getUpdateIndex(0) == -1
+    cells = np.ascontiguousarray([(x + 0.25, y + 0.5) for y in range(sy - 1) for x in range(sx - 1)], np.float32)
+    for name, (x0, y0, x1, y1) in hand_boxes(sx, sy).items():
+        dst.upload_level(0, old_lo, old_ui)
+        dst.take_dirty_bbox(0)
+        dst.copy_map_from(src, np.int32([[x0, y0, x1, y1]]))
+        want_lo, want_ui = old_lo.copy(), old_ui.copy()
+        if x1 >= x0:
+            want_lo[y0:y1 + 1, x0:x1 + 1] = src_lo[y0:y1 + 1, x0:x1 + 1]
+            want_ui[y0:y1 + 1, x0:x1 + 1] = src_ui[y0:y1 + 1, x0:x1 + 1]
+        lo, ui = dst.download_level(0)
+        assert np.array_equal(bits(lo), bits(want_lo)) and np.array_equal(ui, want_ui), (name, "planes")
+        exp.upload_level(0, want_lo, want_ui)
+        assert np.array_equal(bits(dst.download_prob(0)), bits(exp.download_prob(0))), (name, "probabilities")
+        assert np.array_equal(bits(dst.eval_beams(0, ZERO3, cells)), bits(exp.eval_beams(0, ZERO3, cells))), (name, "samples")
+        assert dst.getUpdateIndex(0) == 1, (name, "counters")
+        assert dst.take_dirty_bbox(0).tolist() == ([x0, y0, x1, y1] if x1 >= x0 else [0, 0, -1, -1]), (name, "dirty box")
+        # the counters of an earlier copy are not what made this one pass
+        dst.copy_map_from(exp, np.int32([[0, 0, -1, -1]]))
+        assert dst.getUpdateIndex(0) == -1, name
+    # ... and an update after the copy marks with src's counters: both take the same scan to the same bits
+    dst.copy_map_from(src)
+    for g in (src, dst):
+        single_update(capi, g, ZERO3, tiny)
+    assert_same_state(state(dst), state(src), "an update after the copy")
+    for g in (src, dst, exp):
+        g.close()
+
+
+# ---- 4. the staged route -------------------------------------------------------------------------------------------------------------
+def test_staged_route_gives_the_same_bits():
+    """tests 2 and 3 again with HSM_COPY_STAGE=1: every copy goes through the staging patch"""
+    if os.environ.get("HSM_COPY_STAGE") == "1":
+        pytest.fail("the child run must not select this test")
+    env = dict(os.environ, HSM_COPY_STAGE="1")
+    r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider", os.path.abspath(__file__),
+                        "-k", "boxes_form or shapes_form"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-2000:]
+    assert "6 passed" in r.stdout, r.stdout[-2000:]
+
+
+# ---- 5. stamps ahead of the counter --------------------------------------------------------------------------------------------------
+@LAYOUTS
+@pytest.mark.parametrize("U", sc.COUNTERS)
+@pytest.mark.parametrize("geom", sc.GEOMETRIES, ids=sc.gid)
+def test_clone_of_restored_levels_freezes_the_same_cells(capi, oracle_mod, geom, U, layout):
+    src = new_ctx(capi, layout, geom[0], geom[1], geom[2], sc.RES, sc.FACTOR_FREE, sc.FACTOR_OCC)
+    dst = new_ctx(capi, layout, geom[0], geom[1], geom[2], sc.RES, sc.FACTOR_FREE, sc.FACTOR_OCC)
+    for _ in range(U // 3):
+        single_update(capi, src, sc.sensor_pose(geom), sc.warm_scan())
+    sc.upload(src, geom, U)
+    checkers = {kind: sc.restored_checker(oracle_mod, kind, geom, U) for kind in oracle_kinds()}
+    dst.copy_map_from(src)
+    assert_same_state(state(dst), state(src), "restored clone")
+    poses, scans = sc.batch(geom)
+    before = dst.download_level(0)
+    for pose, pts in zip(poses, scans):
+        for g in (src, dst):
+            single_update(capi, g, pose, pts)
+        for o in checkers.values():
+            sc.checker_update(o, pose, pts)
+    s_dst = state(dst)
+    assert_same_state(s_dst, state(src), "restored clone + batch")
+    assert_state_is_checkers(oracle_mod, s_dst, checkers, U // 3 + sc.BATCH, "restored clone + batch")
+    far = before[1] == sc.FAR  # frozen for the whole test, and the batch did change the cells around them
+    assert far.any() and np.array_equal(bits(s_dst[0][0][far]), bits(before[0][far])) and (s_dst[0][1] != before[1]).any()
+    for g in [src, dst] + list(checkers.values()):
+        g.close()
+
+
+# ---- 6. ordering ---------------------------------------------------------------------------------------------------------------------
+@LAYOUTS
+def test_copy_is_ordered_between_updates_and_matches(capi, scene, stages, layout):
+    """old match on dst || update on src -> copy -> new match on dst, queued back to back with no host wait"""
+    import torch
+    n_old = 6
+    src, dst = new_ctx(capi, layout), new_ctx(capi, layout)
+    integrate(capi, src, scene, 0, N_SRC)
+    integrate(capi, dst, scene, 0, n_old)
+    pts, offs = pack(scene.query_scans[:N_HYP])
+    reps = 64  # the match in flight: 1024 scans
+    big_pts, big_offs = pack(scene.query_scans[:N_HYP] * reps)
+    d = [dev(scene.query_init[:N_HYP]), dev(pts), dev(offs), dev(np.tile(scene.query_init[:N_HYP], (reps, 1))), dev(big_pts), dev(big_offs)]
+    out_old = [torch.full((N_HYP * reps, 3), -7.0, device="cuda:0"), torch.full((N_HYP * reps, 9), -7.0, device="cuda:0")]
+    out_new = [torch.full((N_HYP, 3), -7.0, device="cuda:0"), torch.full((N_HYP, 9), -7.0, device="cuda:0")]
+    s = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    for g in (src, dst):
+        g.synchronize()
+    dst.match_batch_device(N_HYP * reps, d[3].data_ptr(), d[4].data_ptr(), d[5].data_ptr(), 0, out_old[0].data_ptr(), out_old[1].data_ptr(),
+                           s.cuda_stream)
+    single_update(capi, src, scene.build_poses[N_SRC], scene.build_scans[N_SRC])
+    dst.copy_map_from(src)
+    dst.match_batch_device(N_HYP, d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), 0, out_new[0].data_ptr(), out_new[1].data_ptr(), s.cuda_stream)
+    s.synchronize()
+    old = (out_old[0].cpu().numpy(), out_old[1].cpu().numpy())
+    for r in range(reps):
+        assert np.array_equal(bits(old[0][r * N_HYP:(r + 1) * N_HYP]), bits(old[0][:N_HYP])), ("the match in flight", r)
+    assert_matches_are_checkers(scene, old, {k: stages(k, n_old) for k in oracle_kinds()}, "the match in flight sees the old map")
+    assert_matches_are_checkers(scene, (out_new[0].cpu().numpy(), out_new[1].cpu().numpy()),
+                                {k: stages(k, N_SRC + 1) for k in oracle_kinds()}, "the match behind the copy sees the updated map")
+    src.close()
+    dst.close()
+
+
+# ---- 7. refusals ---------------------------------------------------------------------------------------------------------------------
+def test_refusals_change_nothing(capi, scene):
+    import torch
+    src, dst = new_ctx(capi, "quad"), new_ctx(capi, "quad")
+    integrate(capi, src, scene, 0, 3)
+    integrate(capi, dst, scene, 3, 5)
+    others = {"a different size": new_ctx(capi, "quad", 64, 64, 3), "a different level count": new_ctx(capi, "quad", SIZE, SIZE, 2),
+              "a different layout": new_ctx(capi, "plane"), "a different resolution": new_ctx(capi, "quad", res=0.05)}
+    grids = {}
+    for name, g in (("src", src), ("dst", dst)):
+        for lvl in range(LEVELS):
+            g.take_dirty_bbox(lvl)
+            grids[name, lvl] = np.full((SIZE >> lvl, SIZE >> lvl), 55, np.int8)
+            g.occupancy_changes(lvl, grids[name, lvl])
+    before = {"src": state(src), "dst": state(dst)}
+    lib, ok = dst._lib, np.int32([[0, 0, 9, 9]] * LEVELS)
+
+    def refused(rc, text):
+        msg = lib.hsm_last_error().decode()
+        assert rc == HSM_ERR_INVALID and text in msg, (rc, msg, text)
+
+    refused(lib.hsm_copy_map(dst._h, dst._h), "same context")
+    refused(lib.hsm_copy_map_boxes(dst._h, dst._h, ok.ctypes.data), "same context")
+    for name, g in others.items():
+        refused(lib.hsm_copy_map(dst._h, g._h), "differ")
+        refused(lib.hsm_copy_map(g._h, src._h), "differ")
+        refused(lib.hsm_copy_map_boxes(dst._h, g._h, ok.ctypes.data), "differ")
+    for bad in ([-1, 0, 5, 5], [0, -1, 5, 5], [0, 0, SIZE, 5], [0, 0, 5, SIZE], [120, 120, 130, 125]):
+        refused(lib.hsm_copy_map_boxes(dst._h, src._h, np.int32([bad, [0, 0, 3, 3], [0, 0, -1, -1]]).ctypes.data), "outside")
+    refused(lib.hsm_copy_map_boxes(dst._h, src._h, np.int32([[0, 0, 3, 3], [0, 0, 3, 3], [0, 0, 3, SIZE >> 2]]).ctypes.data), "outside")
+    refused(lib.hsm_copy_map_boxes(dst._h, src._h, None), "boxes is null")
+    # a capture in progress on a stream dst has matched on
+    pts, offs = pack(scene.query_scans[:4])
+    d = [dev(scene.query_init[:4]), dev(pts), dev(offs), torch.zeros((4, 3), device="cuda:0")]
+    s = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    launch = lambda: dst.match_batch_device(4, d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), 0, d[3].data_ptr(), 0, s.cuda_stream)
+    launch()
+    s.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, stream=s):
+        launch()
+        rcs = [lib.hsm_copy_map(dst._h, src._h), lib.hsm_copy_map_boxes(dst._h, src._h, ok.ctypes.data), lib.hsm_copy_map(src._h, dst._h)]
+        msg = lib.hsm_last_error().decode()
+    assert rcs == [HSM_ERR_INVALID] * 3 and "captured" in msg, (rcs, msg)
+    torch.cuda.synchronize()
+    assert_same_state(state(src), before["src"], "src after the refusals")
+    assert_same_state(state(dst), before["dst"], "dst after the refusals")
+    for name, g in (("src", src), ("dst", dst)):
+        for lvl in range(LEVELS):
+            assert g.take_dirty_bbox(lvl)[2] < g.take_dirty_bbox(lvl)[0], (name, lvl, "dirty box")
+            bb = g.occupancy_changes(lvl, grids[name, lvl])
+            assert bb[2] < bb[0], (name, lvl, "publish box", bb)
+    dst.copy_map_from(src)  # ... and the capture over, the copy goes through
+    assert_same_state(state(dst), before["src"], "the copy after the capture")
+    for g in [src, dst] + list(others.values()):
+        g.close()
+
+
+# ---- 8. group ------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("form", ("whole", "boxes"))
+def test_group_replicas_alike_after_a_device_resident_update(capi, oracle_mod, scene, stages, form):
+    import torch
+    grp = capi.MapRepGroup(RES, SIZE, SIZE, LEVELS, [0, 0])
+    grp.set_update_factors(0.4, 0.9)
+    m0, m1 = grp.member(0), grp.member(1)
+    for lvl in range(LEVELS):
+        m0.take_dirty_bbox(lvl)
+    n = 4
+    pts, offs = pack(scene.build_scans[:n])
+    d = [dev(scene.build_poses[:n]), dev(pts), dev(offs)]
+    torch.cuda.synchronize()
+    m0.update_by_scans_device(n, d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), 0, max(len(x) for x in scene.build_scans[:n]), None,
+                              torch.cuda.current_stream().cuda_stream)
+    with pytest.raises(capi.HsmError):
+        grp.sync_maps(2)
+    with pytest.raises(capi.HsmError):
+        grp.sync_maps(-1)
+    if form == "whole":
+        grp.sync_maps(0)
+    else:
+        boxes = np.stack([m0.take_dirty_bbox(lvl) for lvl in range(LEVELS)])
+        assert all(b[2] >= b[0] for b in boxes), boxes
+        grp.sync_maps(0, boxes)
+    grp.synchronize()
+    checkers = {kind: stages(kind, n) for kind in oracle_kinds()}
+    s1 = state(m1)
+    assert_same_state(s1, state(m0), ("group", form))
+    assert_state_is_checkers(oracle_mod, s1, checkers, n, ("group", form))
+    q_pts, q_offs = pack(scene.query_scans)
+    pose, cov = grp.match_batch(scene.query_init, q_pts, q_offs)
+    assert len(pose) == 32
+    for kind, o in checkers.items():
+        for k in range(32):
+            po, co = o.match(scene.query_init[k], scene.query_scans[k])
+            assert np.array_equal(bits(pose[k]), bits(po)) and np.array_equal(bits(cov[k]), bits(co)), (form, kind, k, pose[k], po)
+    grp.close()
