@@ -109,6 +109,14 @@ SIGNATURES = {
     "hsm_score_batch_device": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "hsm_select_best_device": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "hsm_match_score_batch_device": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    "hsm_score_window_device": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "hsm_score_window": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "hsm_window_poses_device": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "hsm_select_topk_device": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "hsm_select_topk_workspace": (C.c_size_t, [_i, _i]),
+    "hsm_relocalize_device": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "hsm_relocalize_workspace": (C.c_size_t, [_i, _i]),
+    "hsm_relocalize": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "hsm_match_score_batch": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp]),
     "hsm_likelihood_states": (_i, [_vp, _i, _i, _f32p, _vp, _i, _f32p]),
     "hsm_residual_states": (_i, [_vp, _i, _i, _f32p, _vp, _i, _f32p]),
@@ -788,6 +796,75 @@ class MapRepMultiMap:
                                 out[1].data_ptr(), torch.cuda.current_stream().cuda_stream)
         lh, res = out.cpu().numpy()
         return lh.copy(), res.copy()
+
+    # ---- a window of poses around a DEVICE centre (capi.h "relocalisation"): step = (m, m, rad), half = three half-extents ----
+    @staticmethod
+    def window_count(half) -> int:
+        hx, hy, ht = (int(v) for v in half)
+        return 0 if min(hx, hy, ht) < 0 else (2 * hx + 1) * (2 * hy + 1) * (2 * ht + 1)
+
+    @staticmethod
+    def _window(step, half):
+        return (C.c_float * 3)(*[float(v) for v in step]), (C.c_int * 3)(*[int(v) for v in half])
+
+    @staticmethod
+    def select_topk_workspace(count, k) -> int:
+        return int(load_library().hsm_select_topk_workspace(int(count), int(k)))
+
+    @staticmethod
+    def relocalize_workspace(window_count, k) -> int:
+        return int(load_library().hsm_relocalize_workspace(int(window_count), int(k)))
+
+    def score_window_device(self, level, d_center, step, half, d_pts, n, d_out_likelihood, d_out_residual=0, stream=0):
+        """likelihood / residual of the scan at every pose of the window (device pointers as ints; asynchronous on ``stream``)."""
+        st, hf = self._window(step, half)
+        _check(self._lib.hsm_score_window_device(self._h, level, d_center or None, st, hf, d_pts or None, n,
+                                                 d_out_likelihood or None, d_out_residual or None, stream or None),
+               "hsm_score_window_device")
+
+    def score_window(self, level, center_world, step, half, pts):
+        """host arrays: (likelihood [W], residual [W])"""
+        c = np.ascontiguousarray(center_world, np.float32).reshape(3)
+        a, p, n = _pts(pts)
+        W = self.window_count(half)
+        st, hf = self._window(step, half)
+        lh, res = np.empty(max(W, 0), np.float32), np.empty(max(W, 0), np.float32)
+        _check(self._lib.hsm_score_window(self._h, level, c.ctypes.data, st, hf, p, n, lh.ctypes.data, res.ctypes.data),
+               "hsm_score_window")
+        return lh, res
+
+    def window_poses_device(self, d_center, step, half, d_index, count, d_out_pose, stream=0):
+        st, hf = self._window(step, half)
+        _check(self._lib.hsm_window_poses_device(self._h, d_center or None, st, hf, d_index or None, count, d_out_pose or None,
+                                                 stream or None), "hsm_window_poses_device")
+
+    def select_topk_device(self, count, d_scores, k, d_out_index, d_out_score, d_workspace, workspace_bytes, stream=0):
+        _check(self._lib.hsm_select_topk_device(self._h, count, d_scores or None, k, d_out_index or None, d_out_score or None,
+                                                d_workspace or None, workspace_bytes, stream or None), "hsm_select_topk_device")
+
+    def relocalize_device(self, search_level, d_center, step, half, k, d_pts, n, d_workspace, workspace_bytes, d_out_cand_pose,
+                          d_out_cand_cov, d_out_cand_likelihood, d_out_best_pose, d_out_best_score, d_out_best_index, stream=0):
+        """window score -> top k -> poses -> match -> score on level 0 -> winner, one call on ``stream`` (capi.h)."""
+        st, hf = self._window(step, half)
+        _check(self._lib.hsm_relocalize_device(
+            self._h, search_level, d_center or None, st, hf, k, d_pts or None, n, d_workspace or None, workspace_bytes,
+            d_out_cand_pose or None, d_out_cand_cov or None, d_out_cand_likelihood or None, d_out_best_pose or None,
+            d_out_best_score or None, d_out_best_index or None, stream or None), "hsm_relocalize_device")
+
+    def relocalize(self, search_level, center_world, step, half, k, pts, want_cov=True):
+        """hsm_relocalize: host arrays.  Returns a dict: cand_pose [k,3], cand_cov [k,9] or None, cand_likelihood [k], best_pose [3]
+        (NaN without a winner), best_score, best_index (the window index of the winner's start, -1 if none)."""
+        c = np.ascontiguousarray(center_world, np.float32).reshape(3)
+        a, p, n = _pts(pts)
+        st, hf = self._window(step, half)
+        r = {"cand_pose": np.empty((k, 3), np.float32), "cand_cov": np.zeros((k, 9), np.float32) if want_cov else None,
+             "cand_likelihood": np.empty(k, np.float32), "best_pose": np.full(3, np.nan, np.float32)}
+        bs, bi = np.empty(1, np.float32), np.empty(1, np.int32)
+        _check(self._lib.hsm_relocalize(self._h, search_level, c.ctypes.data, st, hf, k, p, n, r["cand_pose"].ctypes.data,
+                                        r["cand_cov"].ctypes.data if want_cov else None, r["cand_likelihood"].ctypes.data,
+                                        r["best_pose"].ctypes.data, bs.ctypes.data, bi.ctypes.data), "hsm_relocalize")
+        r.update(best_score=bs[0], best_index=int(bi[0]))
+        return r
 
     def match_score_batch(self, begin_world, pts, offsets=None, score_level=0, group_size=None, group_offsets=None, want_cov=True):
         """hsm_match_score_batch: host arrays in/out.  Returns a dict: pose [B,3], cov [B,9] or None, likelihood [B], residual [B],

@@ -946,6 +946,7 @@ int hsm_create(float map_resolution, int size_x, int size_y, unsigned levels, fl
   if (const char* env = getenv("HSM_SPB_LARGE")) h->spb_large = atoi(env) == 8 ? 8 : 4;
   if (const char* env = getenv("HSM_XCD_CHUNK")) h->xcd_chunk = atoi(env) > 0 ? atoi(env) : 0;
   if (const char* env = getenv("HSM_CAST_FORM")) h->cast_form = !strcmp(env, "wave") ? 0 : (!strcmp(env, "lane") ? 1 : -1);
+  if (const char* env = getenv("HSM_WINDOW_FORM")) h->window_form = !strcmp(env, "wave") ? 0 : (!strcmp(env, "lane") ? 1 : -1);
   if (const char* env = getenv("HSM_XCD_CHUNK_EXACT")) h->xcd_chunk_exact = atoi(env) > 0 ? atoi(env) : 0;
   if (const char* env = getenv("HSM_COPY_STAGE")) h->copy_stage = atoi(env) != 0;
 
@@ -1285,6 +1286,19 @@ static int match_score_batch_device_nolock(hsm_ctx* h, int batch, const float* d
   return select_best_device_nolock(h, groups, d_group_offsets, group_size, d_out_likelihood, d_out_pose, d_out_index, d_out_score,
                                    d_out_best_pose, stream);
 }
+
+}  // extern "C"
+
+int hsm_host::match_score_batch_chain_nolock(hsm_ctx* h, int batch, const float* d_begin_world, const float* d_pts_xy, int shared_n,
+                                             float* d_out_pose, float* d_out_cov, int score_level, float* d_out_likelihood,
+                                             int groups, int group_size, int* d_out_index, float* d_out_score,
+                                             float* d_out_best_pose, void* stream) {
+  return match_score_batch_device_nolock(h, batch, d_begin_world, d_pts_xy, nullptr, shared_n, d_out_pose, d_out_cov, score_level,
+                                         d_out_likelihood, nullptr, groups, nullptr, group_size, d_out_index, d_out_score,
+                                         d_out_best_pose, stream);
+}
+
+extern "C" {
 
 int hsm_match_score_batch_device(hsm_ctx* h, int batch, const float* d_begin_world, const float* d_pts_xy,
                                  const int* d_scan_offsets, int shared_n, float* d_out_pose, float* d_out_cov, int score_level,

@@ -363,6 +363,7 @@ struct hsm_ctx {
   int exact_split_tail = 1;  // env HSM_EXACT_SPLIT_TAIL=0: one launch however the batch divides into generations
   int exact_chain_wave = 1;  // env HSM_EXACT_CHAIN_WAVE=0: no chain-only wavefront, teams of wavefronts for batches below 4096 scans (rounds 3-4)
   int cast_form = -1;            // env HSM_CAST_FORM=wave|lane: hsm_cast_scans* take that walk whatever the fan (-1 = by its length, rays.hip)
+  int window_form = -1;          // env HSM_WINDOW_FORM=wave|lane: hsm_score_window* take that form whatever the window (-1 = by its size, window.hip)
   const char* last_kernel = "";  // name of the matcher kernel the last launch used (hsm_last_launch_kernel)
   unsigned coop_fallbacks = 0;  // dense single-scan matches re-run on one workgroup after an exchange timeout (match_single)
   // ... and the back-off that follows: after a timeout the multi-workgroup form is skipped for the next coop_skip matches (1, 2, 4, ...
@@ -445,6 +446,10 @@ int fold_gate_counters(hsm_ctx* h, GateState* state = nullptr);
 int match_batch_device_nolock(hsm_ctx* h, int batch, const float* d_begin_world, const float* d_pts_xy, const int* d_scan_offsets,
                               int shared_n, float* d_out_pose, float* d_out_cov, void* stream, int n_bound = 0,
                               const ExchangeFused* xp = nullptr);
+// the chain behind hsm_match_score_batch_device (match -> score -> winners), for hsm_relocalize_device of window.hip
+int match_score_batch_chain_nolock(hsm_ctx* h, int batch, const float* d_begin_world, const float* d_pts_xy, int shared_n,
+                                   float* d_out_pose, float* d_out_cov, int score_level, float* d_out_likelihood, int groups,
+                                   int group_size, int* d_out_index, float* d_out_score, float* d_out_best_pose, void* stream);
 int slam_refuse_capture(hsm_ctx* h, hipStream_t s, const char* who);
 int wait_for_caller_inputs(hsm_ctx* h, hipStream_t s);
 int slam_caller_waits(hsm_ctx* h, hipStream_t s);

@@ -1,0 +1,267 @@
+// window.hip -- the entries of the C ABI (include/hector_mi355/capi.h) that search a window of poses around a centre on the
+// device-resident map: the likelihood of one scan at every pose of the window (hsm_score_window_device, hsm_score_window), window
+// indices as poses (hsm_window_poses_device), the K best of an array of scores (hsm_select_topk_device) and the chain
+// window score -> top K -> poses -> match -> score on level 0 -> winner (hsm_relocalize_device, hsm_relocalize).  The kernels are
+// in window_kernels.h, the window's arithmetic and the workspace sizes in window_grid.h.  The scoring entries read the map like a
+// batched score and are ordered like one (order_map_reader of the core runtime, hector_mi355.hip).
+#include <hip/hip_runtime.h>
+#include <limits.h>
+#include <math.h>
+
+#include <mutex>
+
+#include "hector_mi355/capi.h"
+#include "hsm_ctx.h"
+#include "window_kernels.h"
+
+using namespace hsm;
+using namespace hsm_host;
+
+static_assert(HSM_MAX_TOPK == kMaxTopK, "capi.h and window_grid.h disagree on K");
+
+namespace {
+
+// Windows of at least this many hypotheses take a lane per hypothesis, smaller ones a wavefront per hypothesis (either gives the
+// same bits).  Measured (profiles/r20/, 1081 beams, level 0 of the 2048^2 pyramid, lane against wave): 1 089 hypotheses 119
+// against 21 us, 4 225: 119 against 23, 35 301: 120 against 93, 269 001: 234 against 585 -- a lane-per-hypothesis launch is never
+// shorter than one lane's walk over the whole scan (119 us), the wave form grows by 1.9 us per 1000 hypotheses; they meet near
+// 52 000, and this is the nearest power of two.
+constexpr long long kWindowLaneMin = 1ll << 16;
+
+bool window_lane_form(const hsm_ctx* h, long long W) {
+  if (h->window_form >= 0) return h->window_form == 1;
+  return W >= kWindowLaneMin;
+}
+
+// the refusals every window entry shares; *W: the window's size
+int window_refusals(const hsm_ctx* h, const float* d_center, const float step[3], const int half[3], const char* who, long long* W) {
+  if (!step || !half || !d_center) return fail_at(HSM_ERR_INVALID, who, ": null centre, steps or half-extents");
+  if (half[0] < 0 || half[1] < 0 || half[2] < 0) return fail_at(HSM_ERR_INVALID, who, ": negative half-extent");
+  for (int a = 0; a < 3; ++a)
+    if (!(fabsf(step[a]) <= 3.402823466e38f)) return fail_at(HSM_ERR_INVALID, who, ": non-finite step");
+  *W = window_count(half[0], half[1], half[2]);
+  if (*W > (long long)INT_MAX) return fail_at(HSM_ERR_INVALID, who, ": more than INT_MAX hypotheses");
+  (void)h;
+  return HSM_OK;
+}
+
+WindowGrid window_grid(const float step[3], const int half[3]) { return WindowGrid{half[0], half[1], half[2], step[0], step[1], step[2]}; }
+
+int score_window_refusals(const hsm_ctx* h, int level, const float* d_center, const float step[3], const int half[3],
+                          const void* pts, int n, const void* out_lh, const void* out_res, const char* who, long long* W) {
+  if (int rc = valid_level(h, level)) return rc;
+  if (int rc = window_refusals(h, d_center, step, half, who, W)) return rc;
+  if (n < 0 || (!out_lh && !out_res) || (n > 0 && !pts)) return fail_at(HSM_ERR_INVALID, who, ": bad argument");
+  return HSM_OK;
+}
+
+// one kernel on `s`; arguments checked, device selected, lock held
+int score_window_launch(hsm_ctx* h, int level, const float* d_center, const WindowGrid& G, int W, const float* d_pts, int n,
+                        float* d_out_lh, float* d_out_res, hipStream_t s) {
+  hsm_ctx::ForeignStream* fs = nullptr;
+  if (int rc = order_map_reader(h, s, "hsm_score_window_device", &fs)) return rc;
+  const float factor = (float)(1.0 / pow(2.0, (double)level));
+  const LevelView v = level_view(h->levels[level], factor, 1);
+  WindowParams P;
+  P.grid = G;
+  P.center = d_center;
+  P.count = W;
+  P.pts = reinterpret_cast<const float2*>(d_pts);
+  P.n = n;
+  P.out_lh = d_out_lh;
+  P.out_residual = d_out_res;
+  const bool lane = window_lane_form(h, W);
+  const unsigned grid = lane ? (unsigned)(((long long)W + 255) / 256) : (unsigned)(((long long)W + 3) / 4);
+  if (h->layout == kLayoutPlane) {
+    if (lane) hipLaunchKernelGGL((score_window_lane_kernel<kLayoutPlane>), dim3(grid), dim3(256), 0, s, v, P);
+    else hipLaunchKernelGGL((score_window_wave_kernel<kLayoutPlane>), dim3(grid), dim3(256), 0, s, v, P);
+  } else {
+    if (lane) hipLaunchKernelGGL((score_window_lane_kernel<kLayoutQuad>), dim3(grid), dim3(256), 0, s, v, P);
+    else hipLaunchKernelGGL((score_window_wave_kernel<kLayoutQuad>), dim3(grid), dim3(256), 0, s, v, P);
+  }
+  HIP_TRY(hipGetLastError());
+  if (fs) fs->pending = true;
+  h->last_kernel = lane ? "score_window_lane_kernel" : "score_window_wave_kernel";
+  h->last_parity = HSM_PARITY_EXACT;  // a lane (or lane 0) owns the whole chain: the reference's order in every mode
+  return HSM_OK;
+}
+
+int window_poses_launch(const WindowGrid& G, int W, const float* d_center, const int* d_index, int count, float* d_out_pose,
+                        hipStream_t s) {
+  hipLaunchKernelGGL(window_poses_kernel, dim3((unsigned)(((long long)count + 255) / 256)), dim3(256), 0, s, G, W, d_center, d_index,
+                     count, d_out_pose);
+  HIP_TRY(hipGetLastError());
+  return HSM_OK;
+}
+
+int select_topk_launch(int count, const float* d_scores, int k, int* d_out_index, float* d_out_score, void* d_workspace,
+                       hipStream_t s) {
+  const int slices = topk_slices(count);
+  float* cand_score = static_cast<float*>(d_workspace);
+  int* cand_index = reinterpret_cast<int*>(cand_score + (size_t)slices * k);
+  hipLaunchKernelGGL(topk_slice_kernel, dim3((slices + 3) / 4), dim3(256), 0, s, d_scores, count, k, slices, cand_score, cand_index);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(topk_merge_kernel, dim3(1), dim3(256), 0, s, cand_score, cand_index, slices * k, k, d_out_index, d_out_score);
+  HIP_TRY(hipGetLastError());
+  return HSM_OK;
+}
+
+int select_topk_refusals(int count, const void* scores, int k, const void* out_index, const void* ws, size_t ws_bytes) {
+  if (count < 0 || k < 1 || k > HSM_MAX_TOPK || !out_index || (count > 0 && !scores) || !ws ||
+      ws_bytes < topk_workspace_bytes(count, k) || ((size_t)ws & 3))
+    return fail(HSM_ERR_INVALID, "hsm_select_topk_device: bad argument");
+  return HSM_OK;
+}
+
+int relocalize_refusals(const hsm_ctx* h, int search_level, const float* d_center, const float step[3], const int half[3], int k,
+                        const void* pts, int n, const void* cand_pose, const void* cand_lh, const void* best_pose,
+                        const void* best_index, const char* who, long long* W) {
+  if (int rc = valid_level(h, search_level)) return rc;
+  if (int rc = window_refusals(h, d_center, step, half, who, W)) return rc;
+  if (n < 0 || (n > 0 && !pts) || k < 1 || k > HSM_MAX_TOPK || !cand_pose || !cand_lh || !best_pose || !best_index)
+    return fail_at(HSM_ERR_INVALID, who, ": bad argument");
+  return HSM_OK;
+}
+
+// the chain on `s`; arguments checked, device selected, lock held
+int relocalize_queue(hsm_ctx* h, int search_level, const float* d_center, const WindowGrid& G, int W, int k, const float* d_pts,
+                     int n, char* ws, float* d_cand_pose, float* d_cand_cov, float* d_cand_lh, float* d_best_pose,
+                     float* d_best_score, int* d_best_index, hipStream_t s) {
+  const RelocalizeLayout L = relocalize_layout(W, k);
+  float* scores = reinterpret_cast<float*>(ws + L.scores);
+  int* kindex = reinterpret_cast<int*>(ws + L.index);
+  float* kscore = reinterpret_cast<float*>(ws + L.kscore);
+  float* kpose = reinterpret_cast<float*>(ws + L.pose);
+  if (int rc = score_window_launch(h, search_level, d_center, G, W, d_pts, n, scores, nullptr, s)) return rc;
+  if (int rc = select_topk_launch(W, scores, k, kindex, kscore, ws + L.topk, s)) return rc;
+  if (int rc = window_poses_launch(G, W, d_center, kindex, k, kpose, s)) return rc;
+  if (int rc = match_score_batch_chain_nolock(h, k, kpose, d_pts, n, d_cand_pose, d_cand_cov, 0, d_cand_lh, 1, k, d_best_index,
+                                              d_best_score, d_best_pose, s))
+    return rc;
+  hipLaunchKernelGGL(window_best_index_kernel, dim3(1), dim3(64), 0, s, kindex, k, d_best_index);
+  HIP_TRY(hipGetLastError());
+  return HSM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t hsm_select_topk_workspace(int count, int k) { return topk_workspace_bytes(count, k); }
+
+size_t hsm_relocalize_workspace(int window_count, int k) { return relocalize_layout(window_count, k).total; }
+
+int hsm_score_window_device(hsm_ctx* h, int level, const float* d_center_world, const float step[3], const int half[3],
+                            const float* d_pts_xy, int n, float* d_out_likelihood, float* d_out_residual, void* stream) {
+  if (!h) return fail(HSM_ERR_INVALID, "null context");
+  long long W = 0;
+  if (int rc = score_window_refusals(h, level, d_center_world, step, half, d_pts_xy, n, d_out_likelihood, d_out_residual,
+                                     "hsm_score_window_device", &W))
+    return rc;
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (int rc = select_device(h)) return rc;
+  return score_window_launch(h, level, d_center_world, window_grid(step, half), (int)W, d_pts_xy, n, d_out_likelihood,
+                             d_out_residual, static_cast<hipStream_t>(stream));
+}
+
+int hsm_score_window(hsm_ctx* h, int level, const float center_world[3], const float step[3], const int half[3],
+                     const float* pts_xy, int n, float* out_likelihood, float* out_residual) {
+  if (!h) return fail(HSM_ERR_INVALID, "null context");
+  long long W = 0;
+  if (int rc = score_window_refusals(h, level, center_world, step, half, pts_xy, n, out_likelihood, out_residual,
+                                     "hsm_score_window", &W))
+    return rc;
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (int rc = select_device(h)) return rc;
+  StagePlan st;
+  const size_t c = st.add(3 * sizeof(float), center_world);
+  const size_t p = st.add((size_t)n * 2 * sizeof(float), pts_xy);
+  const size_t lh = st.add(out_likelihood ? (size_t)W * sizeof(float) : 0, nullptr, out_likelihood);
+  const size_t res = st.add(out_residual ? (size_t)W * sizeof(float) : 0, nullptr, out_residual);
+  if (int rc = h->d_batch.reserve(st.total())) return rc;
+  char* base = h->d_batch;
+  if (int rc = stage_copy_in(st, base, h->stream)) return rc;
+  if (int rc = score_window_launch(h, level, staged<float>(base, c), window_grid(step, half), (int)W, staged<float>(base, p), n,
+                                   staged<float>(base, lh, out_likelihood), staged<float>(base, res, out_residual), h->stream))
+    return rc;
+  if (int rc = stage_copy_out(st, base, h->stream)) return rc;
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return HSM_OK;
+}
+
+int hsm_window_poses_device(hsm_ctx* h, const float* d_center_world, const float step[3], const int half[3], const int* d_index,
+                            int count, float* d_out_pose, void* stream) {
+  if (!h) return fail(HSM_ERR_INVALID, "null context");
+  long long W = 0;
+  if (int rc = window_refusals(h, d_center_world, step, half, "hsm_window_poses_device", &W)) return rc;
+  if (count < 0 || (count > 0 && !d_out_pose) || (!d_index && count > W))
+    return fail(HSM_ERR_INVALID, "hsm_window_poses_device: bad argument");
+  if (count == 0) return HSM_OK;
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (int rc = select_device(h)) return rc;
+  return window_poses_launch(window_grid(step, half), (int)W, d_center_world, d_index, count, d_out_pose,
+                             static_cast<hipStream_t>(stream));
+}
+
+int hsm_select_topk_device(hsm_ctx* h, int count, const float* d_scores, int k, int* d_out_index, float* d_out_score,
+                           void* d_workspace, size_t workspace_bytes, void* stream) {
+  if (!h) return fail(HSM_ERR_INVALID, "null context");
+  if (int rc = select_topk_refusals(count, d_scores, k, d_out_index, d_workspace, workspace_bytes)) return rc;
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (int rc = select_device(h)) return rc;
+  return select_topk_launch(count, d_scores, k, d_out_index, d_out_score, d_workspace, static_cast<hipStream_t>(stream));
+}
+
+int hsm_relocalize_device(hsm_ctx* h, int search_level, const float* d_center_world, const float step[3], const int half[3], int k,
+                          const float* d_pts_xy, int n, void* d_workspace, size_t workspace_bytes, float* d_out_cand_pose,
+                          float* d_out_cand_cov, float* d_out_cand_likelihood, float* d_out_best_pose, float* d_out_best_score,
+                          int* d_out_best_index, void* stream) {
+  if (!h) return fail(HSM_ERR_INVALID, "null context");
+  long long W = 0;
+  if (int rc = relocalize_refusals(h, search_level, d_center_world, step, half, k, d_pts_xy, n, d_out_cand_pose,
+                                   d_out_cand_likelihood, d_out_best_pose, d_out_best_index, "hsm_relocalize_device", &W))
+    return rc;
+  if (!d_workspace || ((size_t)d_workspace & 7) || workspace_bytes < relocalize_layout(W, k).total)
+    return fail(HSM_ERR_INVALID, "hsm_relocalize_device: workspace missing, misaligned or too small");
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (int rc = select_device(h)) return rc;
+  return relocalize_queue(h, search_level, d_center_world, window_grid(step, half), (int)W, k, d_pts_xy, n,
+                          static_cast<char*>(d_workspace), d_out_cand_pose, d_out_cand_cov, d_out_cand_likelihood, d_out_best_pose,
+                          d_out_best_score, d_out_best_index, static_cast<hipStream_t>(stream));
+}
+
+int hsm_relocalize(hsm_ctx* h, int search_level, const float center_world[3], const float step[3], const int half[3], int k,
+                   const float* pts_xy, int n, float* out_cand_pose, float* out_cand_cov, float* out_cand_likelihood,
+                   float* out_best_pose, float* out_best_score, int* out_best_index) {
+  if (!h) return fail(HSM_ERR_INVALID, "null context");
+  long long W = 0;
+  if (int rc = relocalize_refusals(h, search_level, center_world, step, half, k, pts_xy, n, out_cand_pose, out_cand_likelihood,
+                                   out_best_pose, out_best_index, "hsm_relocalize", &W))
+    return rc;
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (int rc = select_device(h)) return rc;
+  StagePlan st;
+  const size_t k3 = (size_t)k * 3 * sizeof(float), k9 = (size_t)k * 9 * sizeof(float);
+  const size_t c = st.add(3 * sizeof(float), center_world);
+  const size_t p = st.add((size_t)n * 2 * sizeof(float), pts_xy);
+  const size_t ws = st.add(relocalize_layout(W, k).total);
+  const size_t pose = st.add(k3, nullptr, out_cand_pose);
+  const size_t cov = st.add(out_cand_cov ? k9 : 0, out_cand_cov, out_cand_cov);  // in/out: an empty scan leaves the caller's matrices
+  const size_t lh = st.add((size_t)k * sizeof(float), nullptr, out_cand_likelihood);
+  const size_t bpose = st.add(3 * sizeof(float), out_best_pose, out_best_pose);  // in/out: no winner keeps the caller's values
+  const size_t bscore = st.add(out_best_score ? sizeof(float) : 0, nullptr, out_best_score);
+  const size_t bidx = st.add(sizeof(int), nullptr, out_best_index);
+  if (int rc = h->d_batch.reserve(st.total())) return rc;
+  char* base = h->d_batch;
+  if (int rc = stage_copy_in(st, base, h->stream)) return rc;
+  if (int rc = relocalize_queue(h, search_level, staged<float>(base, c), window_grid(step, half), (int)W, k, staged<float>(base, p),
+                                n, base + ws, staged<float>(base, pose), staged<float>(base, cov, out_cand_cov),
+                                staged<float>(base, lh), staged<float>(base, bpose), staged<float>(base, bscore, out_best_score),
+                                staged<int>(base, bidx), h->stream))
+    return rc;
+  if (int rc = stage_copy_out(st, base, h->stream)) return rc;
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return HSM_OK;
+}
+
+}  // extern "C"

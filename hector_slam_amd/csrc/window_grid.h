@@ -1,0 +1,95 @@
+// window_grid.h -- a window of pose hypotheses around a centre (window.hip, window_kernels.h), stated once: how many hypotheses a
+// window holds, which (i, j, k) a window index stands for, and the fp32 pose of a hypothesis; and the bytes of the caller-owned
+// workspaces of the top-K selection and of hsm_relocalize_device.
+// Plain C++ (no HIP header): the kernels and the host compile the same text, and tests/cpp/window_grid_check.cpp prints it with
+// the host compiler alone (tests/test_window_model.py).
+#pragma once
+#include <limits.h>
+#include <stddef.h>
+
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define HSM_WIN_HD __host__ __device__
+#else
+#define HSM_WIN_HD
+#endif
+
+namespace hsm {
+
+// half-extents (>= 0) and steps (m, m, rad) of a window: (2hx+1)(2hy+1)(2ht+1) hypotheses, x fastest, then y, then theta
+struct WindowGrid {
+  int hx, hy, ht;
+  float step_x, step_y, step_t;
+};
+
+// the number of hypotheses; 0 for a negative half-extent, more than INT_MAX where the window is refused for its size
+HSM_WIN_HD inline long long window_count(int hx, int hy, int ht) {
+  if (hx < 0 || hy < 0 || ht < 0) return 0;
+  const long long nx = 2ll * hx + 1, ny = 2ll * hy + 1, nt = 2ll * ht + 1;
+  const long long cap = (long long)INT_MAX + 1;
+  if (nx > cap || ny > cap || nt > cap) return cap;
+  const long long xy = nx * ny;  // < 2^63
+  if (xy > cap) return cap;
+  const long long all = xy * nt;  // <= 2^31 * (2^32 - 1) < 2^63
+  return all > cap ? cap : all;
+}
+
+// w = (k * (2hy+1) + j) * (2hx+1) + i
+HSM_WIN_HD inline int window_index(const WindowGrid& g, int i, int j, int k) {
+  return (k * (2 * g.hy + 1) + j) * (2 * g.hx + 1) + i;
+}
+HSM_WIN_HD inline void window_ijk(const WindowGrid& g, int w, int& i, int& j, int& k) {
+  const int nx = 2 * g.hx + 1, ny = 2 * g.hy + 1;
+  const int row = w / nx;
+  i = w - row * nx;
+  k = row / ny;
+  j = row - k * ny;
+}
+
+// The pose of hypothesis (i, j, k) around the centre (cx, cy, ct): one int -> float conversion, one multiplication and one
+// addition per component, each rounded to fp32 (the library and the check are built with -ffp-contract=off: no fused
+// multiply-add).  The heading is not normalised.
+HSM_WIN_HD inline void window_pose_ijk(const WindowGrid& g, float cx, float cy, float ct, int i, int j, int k, float& x, float& y,
+                                       float& t) {
+  x = cx + (float)(i - g.hx) * g.step_x;
+  y = cy + (float)(j - g.hy) * g.step_y;
+  t = ct + (float)(k - g.ht) * g.step_t;
+}
+HSM_WIN_HD inline void window_pose(const WindowGrid& g, float cx, float cy, float ct, int w, float& x, float& y, float& t) {
+  int i, j, k;
+  window_ijk(g, w, i, j, k);
+  window_pose_ijk(g, cx, cy, ct, i, j, k, x, y, t);
+}
+
+// ---- the top-K selection's shape and workspace -------------------------------------------------------------------------------
+constexpr int kMaxTopK = 64;          // HSM_MAX_TOPK
+constexpr int kTopKSliceWaves = 256;  // wavefronts of the first launch at most: each leaves K candidates (score, index)
+
+// wavefronts the first launch uses for `count` scores: one per 64 scores, kTopKSliceWaves at most, one at least
+HSM_WIN_HD inline int topk_slices(int count) {
+  const int w = (count + 63) / 64;
+  return w < 1 ? 1 : (w > kTopKSliceWaves ? kTopKSliceWaves : w);
+}
+inline size_t round_up8(size_t b) { return (b + 7) & ~(size_t)7; }
+// candidates of every slice: K scores, then K indices, per slice.  0 for refused sizes
+inline size_t topk_workspace_bytes(int count, int k) {
+  if (count < 0 || k < 1 || k > kMaxTopK) return 0;
+  return round_up8((size_t)topk_slices(count) * (size_t)k * (sizeof(float) + sizeof(int)));
+}
+
+// hsm_relocalize_device: the W scores, the top-K candidates, K indices, K scores and K start poses, each region 8-byte aligned
+struct RelocalizeLayout {
+  size_t scores, topk, index, kscore, pose, total;
+};
+inline RelocalizeLayout relocalize_layout(long long W, int k) {
+  RelocalizeLayout L = {0, 0, 0, 0, 0, 0};
+  if (W < 1 || W > (long long)INT_MAX || k < 1 || k > kMaxTopK) return L;
+  L.scores = 0;
+  L.topk = round_up8((size_t)W * sizeof(float));
+  L.index = L.topk + topk_workspace_bytes((int)W, k);
+  L.kscore = L.index + round_up8((size_t)k * sizeof(int));
+  L.pose = L.kscore + round_up8((size_t)k * sizeof(float));
+  L.total = L.pose + round_up8((size_t)k * 3 * sizeof(float));
+  return L;
+}
+
+}  // namespace hsm

@@ -740,6 +740,83 @@ int hsm_match_score_batch(hsm_ctx* h, int batch, const float* begin_world, const
                           int shared_n, float* out_pose, float* out_cov, int score_level, float* out_likelihood,
                           float* out_residual, int groups, const int* group_offsets, int group_size, int* out_index,
                           float* out_score, float* out_best_pose);
+/* ---- relocalisation: one scan against a WINDOW of poses on the device map (extension: hector_mapping has no recovery once
+ * the matcher has left its basin) ----
+ * A window is a DEVICE centre d_center_world[3] (so that it can be the d_out_pose of a match or of hsm_slam_* without a host
+ * trip), HOST steps step[3] (m, m, rad; finite) and HOST half-extents half[3] >= 0.  It holds W = (2hx+1)(2hy+1)(2ht+1)
+ * hypotheses that never exist in memory; hypothesis w = (k*(2hy+1) + j)*(2hx+1) + i is, every operation fp32 and un-fused:
+ *   x = cx + (float)(i - hx) * step_x;   y = cy + (float)(j - hy) * step_y;   theta = ctheta + (float)(k - ht) * step_theta
+ * (theta is not normalised).
+ *
+ * hsm_score_window_device
+ * replaces: OccGridMapUtil::getLikelihoodForState / getResidualForState (HSL/map/OccGridMapUtil.h:184-221) at
+ *           GridMapBase::getMapCoordsPose(pose_w) for every pose of the window against ONE scan d_pts_xy[0 .. n) (level-0 units,
+ *           scaled by (float)(1 / 2^level) in the kernel).  d_out_likelihood [W] / d_out_residual [W]: either may be NULL, not
+ *           both; the same bits as hsm_score_batch_device in its reference-order mode gives on the written-out poses.  n == 0:
+ *           residual +0, likelihood NaN.
+ * One kernel launch in one of two forms that give the same bits -- a lane per hypothesis, each lane walking beams 0 .. n-1
+ * itself, or a wavefront per hypothesis (the shape of score_batch_kernel); the entry chooses by W, env HSM_WINDOW_FORM=lane|wave
+ * at hsm_create forces one, hsm_last_launch_kernel names the one that ran ("score_window_lane_kernel" /
+ * "score_window_wave_kernel").  The residual is summed in the reference's beam order in EVERY parity mode (a lane owns a whole
+ * chain, a tree sum would buy nothing): hsm_last_launch_parity reports HSM_PARITY_EXACT after this entry whatever hsm_set_parity
+ * asked for.
+ * Ordering, capture and locking: the contract of hsm_score_batch_device, through the same bookkeeping -- reads the map only,
+ * needs no workspace, keeps no state, one kernel node under capture.
+ * HSM_ERR_INVALID (nothing launched): NULL context, level out of range, a negative half-extent, W > INT_MAX, a non-finite step,
+ * n < 0, both outputs NULL, NULL centre, steps or half-extents, NULL points where n > 0.
+ * Not built: replay through hsm_group_*, a C++ facade entry, non-maximum suppression among candidates, a window per scan of a
+ * batch of different scans. */
+#define HSM_MAX_TOPK 64
+int hsm_score_window_device(hsm_ctx* h, int level, const float* d_center_world, const float step[3], const int half[3],
+                            const float* d_pts_xy, int n, float* d_out_likelihood, float* d_out_residual, void* stream);
+/* the same with HOST pointers (the centre too): copies in, the kernel on the context's stream, copies out; synchronous. */
+int hsm_score_window(hsm_ctx* h, int level, const float center_world[3], const float step[3], const int half[3],
+                     const float* pts_xy, int n, float* out_likelihood, float* out_residual);
+/* window indices as poses: d_out_pose[3c ..] = the world pose of hypothesis d_index[c], c < count, by the arithmetic above; an
+ * index of -1 or outside [0, W) writes three quiet NaNs.  d_index == NULL: indices 0 .. count-1 (count <= W), the window written
+ * out.  One small launch, ordered by `stream` alone (reads no map), capturable.  HSM_ERR_INVALID: NULL context, a bad window (as
+ * above), count < 0, NULL output where count > 0, count > W without indices. */
+int hsm_window_poses_device(hsm_ctx* h, const float* d_center_world, const float step[3], const int half[3], const int* d_index,
+                            int count, float* d_out_pose, void* stream);
+/* the K best of d_scores[0 .. count) in rank order, by the strict total order of hsm_select_best_device: a NaN never takes
+ * part, the higher score first, equal scores (+0 == -0) the lower index first.  d_out_index [k]; d_out_score [k] or NULL; where
+ * fewer than k entries take part the remaining places are -1 and NaN.  1 <= k <= HSM_MAX_TOPK.  The result is a function of the
+ * scores alone (no float atomics, no dependence on launch shape).  Two launches: slices of the array reduced to k candidates each
+ * in the caller-owned d_workspace of at least hsm_select_topk_workspace(count, k) bytes (4-byte aligned), merged by one workgroup.
+ * Nothing is allocated: capturable; reads no map: ordered by `stream` alone.
+ * Neighbouring cells of one peak can fill all k places: non-maximum suppression is not built.  One winner per heading slice is
+ * hsm_select_best_device with group_size = (2hx+1)(2hy+1) followed by hsm_window_poses_device.
+ * HSM_ERR_INVALID: NULL context, count < 0, k out of range, NULL indices, NULL scores where count > 0, a workspace that is NULL,
+ * misaligned or too small. */
+int hsm_select_topk_device(hsm_ctx* h, int count, const float* d_scores, int k, int* d_out_index, float* d_out_score,
+                           void* d_workspace, size_t workspace_bytes, void* stream);
+/* host arithmetic, callable without a device; a multiple of 8; 0 for refused sizes (count < 0, k out of range) */
+size_t hsm_select_topk_workspace(int count, int k);
+/* One call, everything queued on `stream` under one lock of the context, no host wait:
+ *   1. hsm_score_window_device on search_level (likelihoods into the workspace)     2. hsm_select_topk_device, k
+ *   3. hsm_window_poses_device of the k indices        4. hsm_match_score_batch_device on the k poses and the shared scan, with
+ *   score_level 0 and one group of k;  then d_out_best_index[0], the winner's place among the k, is replaced by the WINDOW index
+ *   its start came from (-1 if none).
+ * The same bits as the four public calls.  d_out_cand_pose [k*3] the refined poses, d_out_cand_cov [k*9] or NULL,
+ * d_out_cand_likelihood [k] on level 0, d_out_best_pose [3] (left as it is where there is no winner), d_out_best_score [1] or
+ * NULL, d_out_best_index [1].  Where fewer than k window scores take part the remaining starts are NaN poses: the matcher returns
+ * a non-finite pose for them, their likelihood is 0 (every beam outside the map) or NaN, and they lie behind every filled place,
+ * so they never win over one.  d_workspace: at least hsm_relocalize_workspace(W, k) bytes, 8-byte aligned.
+ * Every argument is checked before the first launch.  Ordering is hsm_match_batch_device's; capturable (a replay with a new
+ * centre or scan written into the same buffers gives the new answer); the retained and the ingested scan are not touched.
+ * HSM_ERR_INVALID: the refusals of hsm_score_window_device, k out of range, a NULL required output, a workspace that is NULL,
+ * misaligned or too small. */
+int hsm_relocalize_device(hsm_ctx* h, int search_level, const float* d_center_world, const float step[3], const int half[3], int k,
+                          const float* d_pts_xy, int n, void* d_workspace, size_t workspace_bytes, float* d_out_cand_pose,
+                          float* d_out_cand_cov, float* d_out_cand_likelihood, float* d_out_best_pose, float* d_out_best_score,
+                          int* d_out_best_index, void* stream);
+/* host arithmetic, callable without a device; a multiple of 8; 0 for refused sizes (window_count < 1, k out of range) */
+size_t hsm_relocalize_workspace(int window_count, int k);
+/* the same with HOST pointers, built like hsm_match_score_batch (copies in, the chain on the context's stream, copies out;
+ * synchronous).  out_cand_cov and out_best_score may be NULL; out_best_pose is in/out. */
+int hsm_relocalize(hsm_ctx* h, int search_level, const float center_world[3], const float step[3], const int half[3], int k,
+                   const float* pts_xy, int n, float* out_cand_pose, float* out_cand_cov, float* out_cand_likelihood,
+                   float* out_best_pose, float* out_best_score, int* out_best_index);
 /* replaces: OccGridMapUtil::getCovarianceForPose (HSL/map/OccGridMapUtil.h:106-160) and
  * getCovMatrixWorldCoords (:162-188) for `batch` MAP-frame poses of `level`: seven sigma points per pose
  * (x +- 1.5 cells, y +- 1.5 cells, angle +- 0.05 rad, the pose), likelihood-weighted sample covariance.
