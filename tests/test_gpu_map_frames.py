@@ -1,5 +1,6 @@
 """Every entry point against the reference on off-centre maps and odd cell sizes (cases: tests/frame_cases.py, pinned on the
 CPU by tests/test_frame_reference.py).
+(The cast, window and copy entries came after this file: tests/test_gpu_entry_geometries.py holds them to the same frames.)
 
 The map frame -- start coordinates and resolution -- reaches the device in a dozen places: mapTworld / worldTmap once per
 matcher form, the scorer, the per-level transforms of the device-side updates, the host update, the tile sort, the cell
