@@ -37,6 +37,7 @@ UNITS = {
     "probes.hip": _c("probes.hip", "probe_kernels.h", "map_cells.h") + _COMMON,
     "rays.hip": _c("rays.hip", "ray_kernels.h", "map_cells.h") + _COMMON,
     "map_copy.hip": _c("map_copy.hip", "map_copy_kernels.h", "map_copy_box.h", "occupancy_rows.h", "map_cells.h") + _COMMON,
+    "map_shift.hip": _c("map_shift.hip", "map_shift_kernels.h", "map_shift_plan.h", "map_copy_box.h", "occupancy_rows.h", "map_cells.h") + _COMMON,
     "window.hip": _c("window.hip", "window_kernels.h", "window_grid.h") + _COMMON,
     "group.hip": _c("group.hip") + _COMMON,
     "match_exact_cached.hip": _c("match_exact_cached.hip", "gn_match_exact.h") + _COMMON,

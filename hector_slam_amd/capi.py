@@ -162,6 +162,8 @@ SIGNATURES = {
     "hsm_copy_map": (_i, [_vp, _vp]),
     "hsm_copy_map_boxes": (_i, [_vp, _vp, _vp]),
     "hsm_group_sync_maps": (_i, [_vp, _i, _vp]),
+    "hsm_shift_map": (_i, [_vp, _f, _f, _vp]),
+    "hsm_map_start": (_i, [_vp, _f32p]),
     "hsm_download_prob": (_i, [_vp, _i, _f32p]),
     "hsm_hessian_derivs": (_i, [_vp, _i, _f32p, _vp, _i, _f32p, _f32p]),
     "hsm_eval_beams": (_i, [_vp, _i, _f32p, _vp, _i, _vp]),
@@ -446,6 +448,26 @@ class MapRepMultiMap:
         if bx.size != 4 * self.getMapLevels():
             raise ValueError("boxes must hold x0, y0, x1, y1 for every level")
         _check(self._lib.hsm_copy_map_boxes(self._h, src._h, bx.ctypes.data), "hsm_copy_map_boxes")
+
+    def map_start(self):
+        """the start coordinates the geometry currently derives from (hsm_map_start) -> float32 [2]"""
+        out = np.empty(2, np.float32)
+        _check(self._lib.hsm_map_start(self._h, out), "hsm_map_start")
+        return out
+
+    def start_for_shift(self, kx, ky):
+        """the start coordinates that move the window by (kx, ky) cells of the COARSEST level: float32(start + k * 2^(levels-1) / size)"""
+        sx, sy, _, _ = self.level_info(0)
+        m = 1 << (self.getMapLevels() - 1)
+        s = self.map_start().astype(np.float64)
+        return np.array([s[0] + kx * m / sx, s[1] + ky * m / sy]).astype(np.float32)
+
+    def shift_map(self, start):
+        """the window moves so that the geometry is hsm_create's for `start`; cell contents keep their world position
+        (hsm_shift_map); queued, no host wait -> level 0's displacement (dx, dy) in cells"""
+        d = np.zeros(2, np.int32)
+        _check(self._lib.hsm_shift_map(self._h, float(np.float32(start[0])), float(np.float32(start[1])), d.ctypes.data), "hsm_shift_map")
+        return int(d[0]), int(d[1])
 
     def download_prob(self, level):
         sx, sy, _, _ = self.level_info(level)

@@ -625,6 +625,10 @@ void update_applied(hsm_ctx* h, const UpdateBatch& batch, const LevelPrep& prep)
 
 namespace hsm_host {
 
+// for map_shift.hip: hsm_create's transforms of a level for other offsets, and the clear of marks a failed update left behind
+void set_level_transformation(Level& L, float offx, float offy, float cell_length) { set_map_transformation(L, offx, offy, cell_length); }
+int scrub_pending_marks(hsm_ctx* h, Level& L) { return scrub_marks(h, L); }
+
 // every writer of the map queues behind a batch match that a caller-owned stream may still be running, and
 // bumps the epoch the next such match orders itself behind
 int order_after_foreign_match(hsm_ctx* h) {
@@ -983,6 +987,8 @@ int hsm_create(float map_resolution, int size_x, int size_y, unsigned levels, fl
   const float total_y = map_resolution * (float)size_y;
   const float mid_offset_y = total_y * start_y;
   h->levels.resize(levels);
+  h->start[0] = start_x;
+  h->start[1] = start_y;
   for (unsigned i = 0; i < levels; ++i) {
     Level& L = h->levels[i];
     L.sx = rx;

@@ -11,6 +11,9 @@
 //                           expected scans cast from batches of poses (ray_kernels.h)
 //   map_copy.hip            a pyramid, or one cell box per level, copied from another context's planes on the device
 //                           (map_copy_kernels.h; the box arithmetic: map_copy_box.h)
+//   map_shift.hip           the window moved under the robot: every level's contents shifted by whole cells inside their own
+//                           planes, the geometry re-derived for other start coordinates (map_shift_kernels.h; the plan:
+//                           map_shift_plan.h)
 //   group.hip               the multi-GPU group (hsm_group_*, hsm_shard_bounds): host code only, librccl opened on demand
 //   match_exact_cached.hip  the exact-order texel-cache batch forms (gn_match_exact.h: the headline kernel and its chain-wavefront forms)
 //   match_teams.hip         the team forms (gn_match_kernel, 1..16 wavefronts per scan) and the fast texel-cache forms
@@ -248,6 +251,7 @@ struct hsm_ctx {
   bool spin_wait = true;       // single-scan matches: poll the kernel's completion word (env HSM_SPIN_WAIT=0: off)
   unsigned done_seq = 0;
   std::vector<hsm_host::Level> levels;
+  float start[2] = {0.5f, 0.5f};  // the start coordinates the levels' transforms derive from (hsm_create, hsm_shift_map)
   mutable std::mutex mu;
   hipStream_t stream = nullptr;
   // single-scan staging (device) + pinned result
@@ -439,6 +443,8 @@ LevelRW level_rw(const Level& L);
 LevelView level_view(const Level& L, float pt_scale, int gn_steps);
 int rebuild_probability(hsm_ctx* h, Level& L);
 void whole_level_changed(Level& L, bool mirror = true);
+void set_level_transformation(Level& L, float offx, float offy, float cell_length);
+int scrub_pending_marks(hsm_ctx* h, Level& L);
 int order_after_foreign_match(hsm_ctx* h);
 int order_map_reader(hsm_ctx* h, hipStream_t s, const char* who, hsm_ctx::ForeignStream** mark);
 int merge_device_boxes(hsm_ctx* h);

@@ -517,6 +517,42 @@ int hsm_take_dirty_bbox(hsm_ctx* h, int level, int bbox[4]);
 int hsm_copy_map(hsm_ctx* dst, hsm_ctx* src);
 int hsm_copy_map_boxes(hsm_ctx* dst, hsm_ctx* src, const int* boxes);
 
+/* ---- the map window moved under the robot, on the device -------------------------------------------------------------------
+ * The reference fixes a map's window at construction (MapRepMultiMap.h:48-72); a robot that reaches its edge loses its beams.
+ * hsm_shift_map moves the window so that the context's geometry becomes that of hsm_create(..., new_start_x, new_start_y): the
+ * same arithmetic on offsets derived from the new start coordinates (never accumulated: repeated moves do not drift), so the
+ * same bits in hsm_level_info, hsm_map_coords_pose and hsm_world_coords_pose.  Cell contents keep their WORLD position: on level
+ * l they move by d_l whole cells, cells that scroll in are cleared cells (log-odds 0, update index -1), cells that scroll out
+ * are gone; probabilities (and texels) are what a rebuild from the moved log-odds gives.  Afterwards the context is
+ * indistinguishable from one created with the new start coordinates into which the moved cells were loaded, except that it
+ * keeps its update counters, mark indices, restored-stamp state, update factors, parity mode, the update gate's state (a world
+ * pose) and the retained and ingested scans (sensor frame).  Every level is marked wholly changed for hsm_take_dirty_bbox and
+ * for hsm_occupancy_changes* (the host's and the device's share of the publish box); hsm_last_update_bbox is empty.
+ *
+ * Displacement: with off = (resolution * size) * start per axis as hsm_create computes it in fp32,
+ * d_0 = nearest integer of (off' - off) / cell_0 in double, and d_l = d_0 >> l.  shift_cells (may be NULL) receives level 0's
+ * {dx, dy}.  start + k * 2^(levels - 1) / size per axis moves the window by k cells of the coarsest level.
+ *
+ * HSM_ERR_INVALID, nothing queued, nothing changed: a NULL context; a start coordinate that is not finite; a move further than
+ * 1/64 cell of level 0 from a whole number of cells on either axis; a d_0 that is no multiple of 2^(levels - 1) on either axis;
+ * a caller's stream that the context has matched on being captured into a graph (a move is not captured, like every writer).
+ * A zero displacement with unchanged start coordinates is HSM_OK, queues nothing and changes nothing.
+ *
+ * Ordering: QUEUED on the context's stream behind every update queued so far and behind the batched matches callers' streams
+ * may still be running on the map; no host wait (except to fetch the box and gate counters device-side updates left on the
+ * device, as hsm_copy_map does).  The cells that survive travel through a staging block the context owns and grows on demand
+ * (shared with hsm_copy_map's staged route); the planes keep their addresses.
+ *
+ * Graphs: a graph captured from a match entry BEFORE a move carries the old transforms in its kernel arguments and would match
+ * in the old frame; capture it again after the move.
+ *
+ * Not covered: a group-wide move (the replicas of hsm_group_member can be moved one by one; hsm_group_sync_maps refuses
+ * replicas whose offsets differ), the C++ facade (its host mirrors assume the constructor's geometry), and following the robot
+ * automatically inside hsm_slam_scans_device. */
+int hsm_shift_map(hsm_ctx* h, float new_start_x, float new_start_y, int shift_cells[2]);
+/* the start coordinates the geometry currently derives from: hsm_create's, or the last accepted hsm_shift_map's */
+int hsm_map_start(const hsm_ctx* h, float start[2]);
+
 /* ---- the rows either side of the path; reference = the ROS node,
  *      hector_mapping/src/HectorMappingRos.cpp.  Optional: the facade does not need them. ---- */
 /* replaces: rosLaserScanToDataContainer (HectorMappingRos.cpp:483-507): raw LaserScan ranges ->

@@ -1,0 +1,120 @@
+"""The host-side plan of a window move (hector_slam_amd/csrc/map_shift_plan.h: the displacement of every level, the box of cells
+that survive in old and in new coordinates, the refusals) on the CPU: tests/cpp/shift_plan_check.cpp compiles the header with
+the host compiler alone, and every plan it prints is held to the numpy model of tests/shift_cases.py -- for every move of every
+map of the suite, for 2000 seeded random (size, levels, start, start') draws, and for the refusals.  Integers and bits: no tolerance."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import shift_cases as sc
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+F = np.float32
+
+
+@pytest.fixture(scope="module")
+def checker(tmp_path_factory):
+    exe = tmp_path_factory.mktemp("shift_plan") / "shift_plan_check"
+    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "hector_slam_amd", "csrc"),
+                    os.path.join(ROOT, "tests", "cpp", "shift_plan_check.cpp"), "-o", str(exe)], check=True)
+    return exe
+
+
+def fbits(x):
+    return int(np.array([x], F).view(np.uint32)[0])
+
+
+def run(checker, requests):
+    """requests: [(res, sx, sy, levels, old start, new start)] -> the checker's lines, split into ints"""
+    text = "".join("%d %d %d %d %d %d %d %d\n" % (fbits(r), sx, sy, lv, fbits(o[0]), fbits(o[1]), fbits(n[0]), fbits(n[1]))
+                   for r, sx, sy, lv, o, n in requests)
+    r = subprocess.run([str(checker)], input=text, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    lines = [[int(v) for v in line.split()] for line in r.stdout.splitlines()]
+    assert len(lines) == len(requests)
+    return lines
+
+
+def model_line(res, sx, sy, levels, old, new):
+    refusal, d0, lv = sc.plan_model(res, sx, sy, levels, old, new)
+    if refusal != sc.OK:
+        return [refusal]
+    same = bool(F(old[0]) == F(new[0]) and F(old[1]) == F(new[1]))
+    out = [refusal, d0[0], d0[1], int(d0 != (0, 0)), int(same), fbits(sc.offset(res, sx, new[0])), fbits(sc.offset(res, sy, new[1]))]
+    for dx, dy, a, b in lv:
+        out += [dx, dy, *a, *b]
+    return out
+
+
+def test_every_case_of_the_suite(checker):
+    reqs, names = [], []
+    for m in sc.MAPS:
+        for name in sc.SHIFT_NAMES:
+            new = sc.case_plan(m, name)[0]
+            reqs.append((m.resolution, m.geom[0], m.geom[1], m.geom[2], np.asarray(m.start, F), new))
+            names.append((m.id, name))
+    for got, req, name in zip(run(checker, reqs), reqs, names):
+        want = model_line(*req)
+        assert want[0] == sc.OK, (name, "the model refuses a case of the suite")
+        assert got == want, (name, got, want)
+        kx, ky = sc.shift_of(req[1:4], name[1])
+        top = req[3] - 1
+        assert (got[1], got[2]) == (kx << top, ky << top), (name, got[:3])   # the move the case asked for
+
+
+def random_requests(count=2000, seed=2101):
+    rng = np.random.default_rng(seed)
+    reqs = []
+    for i in range(count):
+        levels = int(rng.integers(1, 9))
+        sx, sy = (int(rng.integers(2 << (levels - 1), 3000)) for _ in range(2))
+        res = F(rng.choice([0.025, 0.03, 0.05, 0.07, 0.1, 0.125, 1.0]))
+        old = rng.uniform(-2.0, 2.0, 2).astype(F)
+        m = 1 << (levels - 1)
+        k = rng.integers(-40, 41, 2)
+        kind = i % 4   # 0, 1: a whole number of coarsest cells; 2: any whole number of level-0 cells; 3: anywhere
+        if kind == 2:
+            new = (old.astype(np.float64) + rng.integers(-300, 301, 2) / np.array([sx, sy])).astype(F)
+        elif kind == 3:
+            new = (old.astype(np.float64) + rng.uniform(-0.5, 0.5, 2)).astype(F)
+        else:
+            new = (old.astype(np.float64) + k * m / np.array([sx, sy])).astype(F)
+        reqs.append((res, sx, sy, levels, old, new))
+    return reqs
+
+
+def test_2000_random_draws(checker):
+    reqs = random_requests()
+    seen = set()
+    for got, req in zip(run(checker, reqs), reqs):
+        want = model_line(*req)
+        assert got == want, (req, got, want)
+        seen.add(got[0])
+    assert {sc.OK, sc.FRACTION, sc.NOT_MULTIPLE} <= seen, seen   # the draws reach acceptance and both arithmetic refusals
+
+
+def test_refusals(checker):
+    old = np.array([0.5, 0.5], F)
+    res, sx, sy, levels = F(0.05), 96, 40, 3
+    step = 4 / np.array([sx, sy])   # the start that moves by one coarsest cell
+    cases = [
+        ((old + [1 / sx, 0]).astype(F), sc.NOT_MULTIPLE),          # one level-0 cell: no multiple of 4
+        ((old + [0, 6 / sy]).astype(F), sc.NOT_MULTIPLE),
+        ((old + [step[0] * (1 + 1 / 128), 0]).astype(F), sc.FRACTION),   # 1/32 cell off a whole number
+        ((old + [0, step[1] * 0.125]).astype(F), sc.FRACTION),           # half a cell
+        ((old + [step[0] * (1 + 1 / 1024), 0]).astype(F), sc.OK),        # 1/256 cell: inside the bound
+        (np.array([np.nan, 0.5], F), sc.NON_FINITE),
+        (np.array([0.5, np.inf], F), sc.NON_FINITE),
+        (np.array([-np.inf, 0.5], F), sc.NON_FINITE),
+        (np.array([3.0e38, 0.5], F), sc.NON_FINITE),               # a finite start whose offset overflows
+        (np.array([1.0e12, 0.5], F), sc.TOO_FAR),
+        (old.copy(), sc.OK),
+    ]
+    reqs = [(res, sx, sy, levels, old, new) for new, _ in cases]
+    for got, req, (_, want_code) in zip(run(checker, reqs), reqs, cases):
+        assert got[0] == want_code, (req, got)
+        assert got == model_line(*req), (req, got)
+    same = run(checker, [(res, sx, sy, levels, old, old)])[0]
+    assert same[1:5] == [0, 0, 0, 1]   # zero displacement, nothing moves, the start is the same
