@@ -31,7 +31,8 @@ def _c(*names):
 # translation unit -> the files it includes (its own staleness test)
 _COMMON = _c("gn_match.h", "libm_exact.h", "hsm_host.h", "hsm_ctx.h", "match_plan.h", "stage_layout.h") + [_CAPI]
 UNITS = {
-    "hector_mi355.hip": _c("hector_mi355.hip", "gn_match_spec.h", "spec_chain.h", "map_update.h", "map_cells.h", "update_gate.h") + _COMMON,
+    "hector_mi355.hip": _c("hector_mi355.hip", "gn_match_spec.h", "spec_chain.h", "map_cells.h") + _COMMON,
+    "map_update.hip": _c("map_update.hip", "map_update.h", "map_cells.h", "update_gate.h") + _COMMON,
     "ingest.hip": _c("ingest.hip", "ingest_kernels.h") + _COMMON,
     "occupancy.hip": _c("occupancy.hip", "occupancy_kernels.h", "map_cells.h", "occupancy_rows.h") + _COMMON,
     "probes.hip": _c("probes.hip", "probe_kernels.h", "map_cells.h") + _COMMON,

@@ -1,9 +1,11 @@
 // hsm_ctx.h -- the context of libhector_mi355.so as its translation units see it: the pyramid level, hsm_ctx, and the launch
 // entry points the units implement for each other.  Internal (not installed): the public boundary is include/hector_mi355/capi.h.
-//   hector_mi355.hip        the core: host runtime + C ABI of matches, updates and scan loops; the update kernels
-//                           (map_update.h), the one-workgroup-per-scan matcher forms
+//   hector_mi355.hip        the core: the context's life cycle, the stream hand-over around map updates, every match entry and
+//                           the one-workgroup-per-scan matcher forms
+//   map_update.hip          every writer of the map by scans: the update entries, the movement gate, the device SLAM scan loop and
+//                           the level maintenance the other units reach through this header (map_update.h, update_gate.h)
 //   ingest.hip              raw sensor data: the LaserScan / point-cloud conversions of one scan and of batches, in front of
-//                           the core's match, update and SLAM loop (ingest_kernels.h)
+//                           the match, the update and the SLAM loop (ingest_kernels.h)
 //   occupancy.hip           a level as the node's occupancy grid, whole or its changed cells only (occupancy_kernels.h)
 //   probes.hip              the host-array probes (likelihood, covariance, Hessian), level downloads and uploads,
 //                           the hsm_debug_* test hooks, and the kernels only these launch (probe_kernels.h)
@@ -20,6 +22,7 @@
 //   pose_exchange.hip       the device-side gather of sharded results
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 
 #include <mutex>
 #include <string>
@@ -33,7 +36,8 @@
 #include "stage_layout.h"
 
 namespace hsm {
-struct BeamRec;  // map_update.h (its kernels are not templates: only hector_mi355.hip includes that header)
+struct BeamRec;  // map_update.h.  Its kernels are not templates, so map_update.hip includes that header (and update_gate.h behind
+                 // it) and no other unit does: whatever launches one of its kernels lives there
 struct LevelRW;  // map_cells.h
 struct UpdateBatch;
 struct GateState;
@@ -83,6 +87,9 @@ struct Level {
   int tiles_x() const { return (sx + 3) / 4; }
   int quad_texels() const { return sx * sy; }
 };
+
+// what brings level-0 end points to level l: static_cast<float>(1.0 / pow(2.0, level)) -- a power of two, exact in fp32
+inline float level_factor(int l) { return (float)(1.0 / pow(2.0, (double)l)); }
 
 inline void affine_apply_host(const Affine2& a, float x, float y, float& ox, float& oy) {
   ox = a.t0 + (a.l00 * x + a.l01 * y);
@@ -382,7 +389,7 @@ namespace hsm_host {
 
 using hsm_plan::MatchPlan;
 
-// What a gated update adds to an update call (update_by_scans_device_nolock of hector_mi355.hip; map_update.h UpdateGateParams)
+// What a gated update adds to an update call (update_by_scans_device_nolock of map_update.hip; map_update.h UpdateGateParams)
 struct GateCall {
   const unsigned char* d_force = nullptr;
   int* d_out_applied = nullptr;
@@ -432,23 +439,18 @@ struct ScanLog {
   }
 };
 
-// hector_mi355.hip, for the other units: the views of a level, the launch arithmetic, what an entry does before it reads or
-// rewrites a level on the host, the hand-over between a caller's stream and the context's around queued map updates, and the
-// device SLAM loop over a scan log (the definitions carry the comments)
+// hector_mi355.hip, for the other units: the views of a level, the launch arithmetic, and the hand-over between a caller's stream
+// and the context's around queued map updates (the definitions carry the comments)
 int valid_level(const hsm_ctx* h, int level);
 int select_device(const hsm_ctx* h);
 bool wants_exact(const hsm_ctx* h);
 int grid_for(size_t n, int block = 256);
 LevelRW level_rw(const Level& L);
 LevelView level_view(const Level& L, float pt_scale, int gn_steps);
-int rebuild_probability(hsm_ctx* h, Level& L);
 void whole_level_changed(Level& L, bool mirror = true);
 void set_level_transformation(Level& L, float offx, float offy, float cell_length);
-int scrub_pending_marks(hsm_ctx* h, Level& L);
 int order_after_foreign_match(hsm_ctx* h);
 int order_map_reader(hsm_ctx* h, hipStream_t s, const char* who, hsm_ctx::ForeignStream** mark);
-int merge_device_boxes(hsm_ctx* h);
-int fold_gate_counters(hsm_ctx* h, GateState* state = nullptr);
 int match_batch_device_nolock(hsm_ctx* h, int batch, const float* d_begin_world, const float* d_pts_xy, const int* d_scan_offsets,
                               int shared_n, float* d_out_pose, float* d_out_cov, void* stream, int n_bound = 0,
                               const ExchangeFused* xp = nullptr);
@@ -459,6 +461,15 @@ int match_score_batch_chain_nolock(hsm_ctx* h, int batch, const float* d_begin_w
 int slam_refuse_capture(hsm_ctx* h, hipStream_t s, const char* who);
 int wait_for_caller_inputs(hsm_ctx* h, hipStream_t s);
 int slam_caller_waits(hsm_ctx* h, hipStream_t s);
+// map_update.hip, for the other units: the level maintenance that launches map_update.h's kernels, what an entry does before it
+// reads or rewrites a level's boxes and counters on the host, and the device SLAM loop over a scan log
+int create_update_state(hsm_ctx* h);
+int fill_level(hsm_ctx* h, Level& L);
+int reset_update_gate(hsm_ctx* h);
+int rebuild_probability(hsm_ctx* h, Level& L);
+int scrub_pending_marks(hsm_ctx* h, Level& L);
+int merge_device_boxes(hsm_ctx* h);
+int fold_gate_counters(hsm_ctx* h, GateState* state = nullptr);
 int slam_scans_queue(hsm_ctx* h, const ScanLog& log, const PosedScans& scans);
 
 // f(layout, exact) with the context's texel layout and summation order as types (std::integral_constant<int, kLayout...>,

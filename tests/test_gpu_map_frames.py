@@ -374,7 +374,7 @@ def device_update(g, world, scans, form, origo=None):
 
 
 UPDATE_FORMS = ["hsm_update_by_scan", "hsm_update_by_scan/byte-map", "hsm_update_by_scans", "device", "device/byte-map", "origos", "gated"]
-HOST_FORMS = UPDATE_FORMS[:3]  # these reach the map through the host's transform (hector_mi355.hip), the others through update_prep_kernel
+HOST_FORMS = UPDATE_FORMS[:3]  # these reach the map through the host's transform (map_update.hip), the others through update_prep_kernel
 
 
 @pytest.mark.parametrize("form", UPDATE_FORMS)
