@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import concurrent.futures
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -21,30 +22,27 @@ import sys
 _PKG = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_PKG)
 _CSRC = os.path.join(_PKG, "csrc")
-_CAPI = os.path.join(_ROOT, "include", "hector_mi355", "capi.h")
+_INC = os.path.join(_ROOT, "include")
+_QUOTED = re.compile(r'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', re.M)
 
 
-def _c(*names):
-    return [os.path.join(_CSRC, n) for n in names]
+def _closure(path: str, seen: list[str]) -> list[str]:
+    """`path` and every file its quoted #include lines reach, each looked up in csrc/ and then in include/ (the -I order of the
+    build).  Lines inside an #if count as well: a superset only makes a unit rebuild once too often."""
+    if path not in seen:
+        seen.append(path)
+        with open(path) as f:
+            for name in _QUOTED.findall(f.read()):
+                hit = next((p for p in (os.path.join(_CSRC, name), os.path.join(_INC, name)) if os.path.exists(p)), None)
+                if hit:
+                    _closure(hit, seen)
+    return seen
 
 
-# translation unit -> the files it includes (its own staleness test)
-_COMMON = _c("gn_match.h", "libm_exact.h", "hsm_host.h", "hsm_ctx.h", "match_plan.h", "stage_layout.h") + [_CAPI]
-UNITS = {
-    "hector_mi355.hip": _c("hector_mi355.hip", "gn_match_spec.h", "spec_chain.h", "map_cells.h") + _COMMON,
-    "map_update.hip": _c("map_update.hip", "map_update.h", "map_cells.h", "update_gate.h") + _COMMON,
-    "ingest.hip": _c("ingest.hip", "ingest_kernels.h") + _COMMON,
-    "occupancy.hip": _c("occupancy.hip", "occupancy_kernels.h", "map_cells.h", "occupancy_rows.h") + _COMMON,
-    "probes.hip": _c("probes.hip", "probe_kernels.h", "map_cells.h") + _COMMON,
-    "rays.hip": _c("rays.hip", "ray_kernels.h", "map_cells.h") + _COMMON,
-    "map_copy.hip": _c("map_copy.hip", "map_copy_kernels.h", "map_copy_box.h", "occupancy_rows.h", "map_cells.h") + _COMMON,
-    "map_shift.hip": _c("map_shift.hip", "map_shift_kernels.h", "map_shift_plan.h", "map_copy_box.h", "occupancy_rows.h", "map_cells.h") + _COMMON,
-    "window.hip": _c("window.hip", "window_kernels.h", "window_grid.h") + _COMMON,
-    "group.hip": _c("group.hip") + _COMMON,
-    "match_exact_cached.hip": _c("match_exact_cached.hip", "gn_match_exact.h") + _COMMON,
-    "match_teams.hip": _c("match_teams.hip") + _COMMON,
-    "pose_exchange.hip": _c("pose_exchange.hip", "pose_exchange.h", "hsm_host.h") + [_CAPI],
-}
+# translation unit -> itself and the files it includes, directly or not (its own staleness test); the link order
+_UNIT_NAMES = ["hector_mi355.hip", "map_update.hip", "ingest.hip", "occupancy.hip", "probes.hip", "rays.hip", "map_copy.hip",
+               "map_shift.hip", "window.hip", "group.hip", "match_exact_cached.hip", "match_teams.hip", "pose_exchange.hip"]
+UNITS = {u: _closure(os.path.join(_CSRC, u), []) for u in _UNIT_NAMES}
 SRC = os.path.join(_CSRC, "hector_mi355.hip")
 DEPS = sorted({d for deps in UNITS.values() for d in deps})
 LIB = os.path.join(_PKG, "lib", "libhector_mi355.so")

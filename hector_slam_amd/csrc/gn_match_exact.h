@@ -1,6 +1,6 @@
 // gn_match_exact.h -- HSM_PARITY_EXACT for batches: the exact-order matcher with the texel cache (round 3).
 //
-// What it computes: the same coarse-to-fine Gauss-Newton match as gn_match.h, with the nine sums of
+// What it computes: the same coarse-to-fine Gauss-Newton match as gn_match_teams.h, with the nine sums of
 // OccGridMapUtil::getCompleteHessianDerivs (HSL/map/OccGridMapUtil.h:76-98) accumulated in the REFERENCE's order --
 // one fp32 chain per term, beam 0 .. n-1 -- so H, dTr, every GN step (ScanMatcher.h:194-221), the pose and the
 // covariance are bit-identical to the reference CPU matcher.
@@ -30,7 +30,12 @@
 //   66-69 vs 92 us on the 2048^2 headline batch, 141-143 vs 199 us on the 3-level batch, 156-162 vs 291 us on the 4096^2
 //   pyramid, whose gathers miss the L2.
 #pragma once
-#include "gn_match.h"
+#include <hip/hip_runtime.h>
+
+#include "beam_sample.h"
+#include "gn_step.h"
+#include "match_types.h"
+#include "texel_cache.h"
 
 namespace hsm {
 
@@ -373,7 +378,7 @@ __global__ void __launch_bounds__(64 * (NS + (CW ? 1 : 0)), CW && 5 * BPC + 50 <
       };
       // the four staged values of one beam (OccGridMapUtil.h:332-346 and :80-87), with the source's signs:
       //   gx = -((P00-P10)*xFacInv + (P01-P11)*fx) == (P10-P00)*xFacInv + (P11-P01)*fx   (negation commutes with rounding)
-      //   rotDeriv = (-ry)*gx + rx*gy == rx*gy - ry*gx,  (rx, ry) = R(theta) p shared with the transform (gn_match.h)
+      //   rotDeriv = (-ry)*gx + rx*gy == rx*gy - ry*gx,  (rx, ry) = R(theta) p shared with the transform (beam_sample.h)
       // the nine products of :83-97, one rounding each like the reference's; the chain lane only adds
       // (in two halves: the four terms of a beam -- gx, gy, funVal, rotDeriv -- are what a wavefront that runs ahead of a barrier keeps
       // in registers; the nine products are formed from them when the row is staged)
@@ -423,7 +428,7 @@ __global__ void __launch_bounds__(64 * (NS + (CW ? 1 : 0)), CW && 5 * BPC + 50 <
       };
       // the four staged values of one beam (OccGridMapUtil.h:332-346 and :80-87), with the source's signs:
       //   gx = -((P00-P10)*xFacInv + (P01-P11)*fx) == (P10-P00)*xFacInv + (P11-P01)*fx   (negation commutes with rounding)
-      //   rotDeriv = (-ry)*gx + rx*gy == rx*gy - ry*gx,  (rx, ry) = R(theta) p shared with the transform (gn_match.h)
+      //   rotDeriv = (-ry)*gx + rx*gy == rx*gy - ry*gx,  (rx, ry) = R(theta) p shared with the transform (beam_sample.h)
       auto produce = [&](int k, float i0, float i1, float i2, float i3, const BeamRot& r, float fx, float fy) {
         float pp[9];
         products(i0, i1, i2, i3, r, fx, fy, pp);

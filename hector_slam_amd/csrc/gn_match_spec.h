@@ -24,7 +24,11 @@
 // additions; candidates, summaries and the order of the atomics only decide how many segments are re-run.
 // Host model of phases C and D (same header, same arithmetic): tests/cpp/spec_chain_model.cpp, speculative_wave().
 #pragma once
-#include "gn_match.h"
+#include <hip/hip_runtime.h>
+
+#include "beam_sample.h"
+#include "gn_step.h"
+#include "match_types.h"
 #include "spec_chain.h"
 
 namespace hsm {

@@ -1,5 +1,5 @@
 // hector_mi355.hip -- host runtime + C ABI (include/hector_mi355/capi.h) of the
-// MI355X-native hector_mapping scan matcher: the context's life cycle and every match entry.  Kernels: gn_match.h; the batch / team
+// MI355X-native hector_mapping scan matcher: the context's life cycle and every match entry.  Kernels launched here: gn_match_dense.h, gn_match_spec.h, score_kernels.h; the batch / team
 // matcher forms are launched from match_exact_cached.hip and match_teams.hip, map updates and the scan loop are in map_update.hip, the
 // probes and test hooks in probes.hip, the multi-GPU group in group.hip, raw-scan conversion in ingest.hip, the occupancy exports in
 // occupancy.hip (hsm_ctx.h says which unit holds what).
@@ -25,12 +25,14 @@
 #include <string>
 #include <vector>
 
-#include "gn_match.h"
+#include "gn_match_dense.h"
 #include "gn_match_spec.h"
+#include "gn_step.h"
 #include "hector_mi355/capi.h"
 #include "hsm_ctx.h"
 #include "hsm_host.h"
 #include "map_cells.h"
+#include "score_kernels.h"
 
 namespace {
 
@@ -193,7 +195,7 @@ void free_level(Level& L, TeardownLog* log = nullptr) {
 
 static_assert(hsm_plan::kQuad == kLayoutQuad && hsm_plan::kPlane == kLayoutPlane && hsm_plan::kExactGroupRounds == kExactGroupRounds &&
                   hsm_plan::kDenseRound == kDenseRound && hsm_plan::kSpec1MaxBeams == kSpec1MaxBeams,
-              "match_plan.h restates gn_match.h / gn_match_spec.h");
+              "match_plan.h restates match_types.h / gn_step.h / gn_match_dense.h / gn_match_spec.h");
 static_assert(hsm_plan::kParityFast == HSM_PARITY_FAST && hsm_plan::kParityExact == HSM_PARITY_EXACT && hsm_plan::kParityRelaxed == HSM_PARITY_RELAXED,
               "match_plan.h restates capi.h");
 
@@ -228,7 +230,7 @@ void record_launch(hsm_ctx* h, const MatchPlan& plan) {
   h->last_parity = plan.parity;
 }
 
-// the one-workgroup-per-scan forms of this unit: Family::kExactDense, kSpec (gn_match.h, gn_match_spec.h: `batch` workgroups) and
+// the one-workgroup-per-scan forms of this unit: Family::kExactDense, kSpec (gn_match_dense.h, gn_match_spec.h: `batch` workgroups) and
 // kSpec1 (one scan)
 int launch_workgroup_form(hsm_ctx* h, MatchParams P, MatchPlan& plan, const MatchSite& site, hipStream_t stream) {
   if (plan.family == Family::kSpec) {
@@ -460,7 +462,7 @@ int hsm_host::match_batch_device_nolock(hsm_ctx* h, int batch, const float* d_be
   P.n_bound = d_scan_offsets ? n_bound : shared_n;
   if (xp) P.xp = *xp;
   h->fused_exchange_done = false;
-  // workgroup -> XCD mapping (gn_match.h, xcd_block): chunks dealt to the XCDs in turn balance the data-dependent
+  // workgroup -> XCD mapping (beam_sample.h, xcd_block): chunks dealt to the XCDs in turn balance the data-dependent
   // per-scan time; maps whose touched region outgrows the L2s keep one contiguous eighth of the batch per XCD
   const bool outgrows = hsm_plan::level0_outgrows_l2(h->levels[0].cells());
   P.xcd_chunk = outgrows ? 0 : h->xcd_chunk;
@@ -622,7 +624,7 @@ int hsm_create(float map_resolution, int size_x, int size_y, unsigned levels, fl
     CREATE_TRY(hipMalloc((void**)&L.d_logodds, n * sizeof(float)));
     CREATE_TRY(hipMalloc((void**)&L.d_update_index, n * sizeof(int)));
     // the samplers point out-of-map beams at an all-zero footprint stored BEHIND the planes
-    // (gn_match.h sample_fetch): one extra texel, resp. sizeX + 2 extra cells, zeroed once here
+    // (beam_sample.h sample_fetch): one extra texel, resp. sizeX + 2 extra cells, zeroed once here
     CREATE_TRY(hipMalloc((void**)&L.d_prob, (n + (size_t)rx + 2) * sizeof(float)));
     CREATE_TRY(hipMemsetAsync(L.d_prob + n, 0, ((size_t)rx + 2) * sizeof(float), h->stream));
     if (h->layout == kLayoutQuad) {
@@ -817,7 +819,7 @@ int hsm_match_batch_device_gather(hsm_ctx* h, int batch, const float* d_begin_wo
 }
 
 // The weighting step behind a batched match: B (world pose, scan) pairs scored on `level` in one launch of score_batch_kernel
-// (gn_match.h).  A reader of the map like the batched match, so ordered like it (order_map_reader); no workspace, no state.
+// (score_kernels.h).  A reader of the map like the batched match, so ordered like it (order_map_reader); no workspace, no state.
 static int score_batch_device_nolock(hsm_ctx* h, int level, int batch, const float* d_poses_world, const float* d_pts_xy,
                                      const int* d_scan_offsets, int shared_n, float* d_out_likelihood,
                                      float* d_out_residual, void* stream) {

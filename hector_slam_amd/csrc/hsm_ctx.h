@@ -1,7 +1,7 @@
 // hsm_ctx.h -- the context of libhector_mi355.so as its translation units see it: the pyramid level, hsm_ctx, and the launch
 // entry points the units implement for each other.  Internal (not installed): the public boundary is include/hector_mi355/capi.h.
 //   hector_mi355.hip        the core: the context's life cycle, the stream hand-over around map updates, every match entry and
-//                           the one-workgroup-per-scan matcher forms
+//                           the one-workgroup-per-scan matcher forms (gn_match_dense.h, gn_match_spec.h, score_kernels.h)
 //   map_update.hip          every writer of the map by scans: the update entries, the movement gate, the device SLAM scan loop and
 //                           the level maintenance the other units reach through this header (map_update.h, update_gate.h)
 //   ingest.hip              raw sensor data: the LaserScan / point-cloud conversions of one scan and of batches, in front of
@@ -18,8 +18,11 @@
 //                           map_shift_plan.h)
 //   group.hip               the multi-GPU group (hsm_group_*, hsm_shard_bounds): host code only, librccl opened on demand
 //   match_exact_cached.hip  the exact-order texel-cache batch forms (gn_match_exact.h: the headline kernel and its chain-wavefront forms)
-//   match_teams.hip         the team forms (gn_match_kernel, 1..16 wavefronts per scan) and the fast texel-cache forms
+//   match_teams.hip         the team forms (gn_match_teams.h: gn_match_kernel, 1..16 wavefronts per scan) and the fast texel-cache
+//                           forms (gn_match_cached.h)
 //   pose_exchange.hip       the device-side gather of sharded results
+// This header sees the matcher's TYPES only (match_types.h): a kernel header is included by the unit that launches its kernels,
+// the device primitives they share are in beam_sample.h, gn_step.h and texel_cache.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -29,10 +32,10 @@
 #include <type_traits>
 #include <vector>
 
-#include "gn_match.h"
 #include "hector_mi355/capi.h"
 #include "hsm_host.h"
 #include "match_plan.h"
+#include "match_types.h"
 #include "stage_layout.h"
 
 namespace hsm {
@@ -335,7 +338,7 @@ struct hsm_ctx {
   int wg_sync = -1;              // env HSM_WG_SYNC=0|1: per-beam workgroup barrier of the texel-cache matcher (-1 = for maps > 2^23 cells)
   bool dense_bits = true;        // env HSM_DENSE_BITS=0: dense scans keep the keyed update (map_update.h)
   bool exact_cached = true;      // env HSM_EXACT_CACHED=0: exact-mode batches take the one-wavefront-per-scan exact form (gn_match_kernel) instead of gn_match_exact.h's
-  bool exact = false;     // HSM_PARITY_EXACT: H / dTr summed in the reference's beam order (gn_match.h exact_round)
+  bool exact = false;     // HSM_PARITY_EXACT: H / dTr summed in the reference's beam order (gn_step.h exact_round)
   bool auto_parity = true;  // HSM_PARITY_AUTO (default): every entry point in the reference's summation order (wants_exact)
   bool relaxed = false;   // HSM_PARITY_RELAXED: contracted multiply-adds in the throughput kernel (gn_match_cached_kernel<.., RELAXED>)
   int last_cfg[6] = {0, 0, 0, 0, 0, 0};  // MatchPlan::record of the last match launch (record_launch)

@@ -5,7 +5,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "gn_match.h"
+#include "libm_exact.h"
 
 namespace hsm {
 
@@ -22,7 +22,7 @@ struct LevelRW {
                              // cells (index = mark_index: a tile is one 128-byte line); set by update_mark_free_dense_kernel,
                              // cleared by the dense apply pass
   int sx, sy;
-  int tiles_x, quad_texels;  // tiled texel plane geometry (gn_match.h quad_index)
+  int tiles_x, quad_texels;  // tiled texel plane geometry (beam_sample.h quad_index)
   int kf_tiles_x;            // free-key tiles per row = key_free_tiles_x(sx): ceil(sx / 64) * 8   (key_free_index)
 };
 

@@ -16,7 +16,6 @@
 
 #include <mutex>
 
-#include "gn_match.h"
 #include "hector_mi355/capi.h"
 #include "hsm_ctx.h"
 #include "map_copy_kernels.h"

@@ -16,9 +16,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "gn_match.h"
+#include "beam_sample.h"
 #include "map_cells.h"
 #include "map_copy_box.h"
+#include "match_types.h"
 
 namespace hsm {
 

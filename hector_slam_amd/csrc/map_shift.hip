@@ -22,7 +22,6 @@
 #include <cmath>
 #include <mutex>
 
-#include "gn_match.h"
 #include "hector_mi355/capi.h"
 #include "hsm_ctx.h"
 #include "map_shift_kernels.h"

@@ -45,8 +45,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "gn_match.h"
+#include "beam_sample.h"
+#include "libm_exact.h"
 #include "map_cells.h"
+#include "match_types.h"
 #include "update_gate.h"
 
 namespace hsm {

@@ -8,7 +8,7 @@
 namespace hsm_host {
 namespace {
 
-static_assert(hsm_plan::kQuad == kLayoutQuad && hsm_plan::kPlane == kLayoutPlane, "match_plan.h restates gn_match.h");
+static_assert(hsm_plan::kQuad == kLayoutQuad && hsm_plan::kPlane == kLayoutPlane, "match_plan.h restates match_types.h");
 static_assert(hsm_plan::kXbpc == HSM_XBPC && hsm_plan::kXbpcMain == HSM_XBPC_MAIN && hsm_plan::kXbpcCw == HSM_XBPC_CW,
               "match_plan.h restates gn_match_exact.h");
 

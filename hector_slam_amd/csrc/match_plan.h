@@ -8,7 +8,7 @@
 
 namespace hsm_plan {
 
-// what the kernels fix (static_asserts in the launch units hold these equal to gn_match.h / gn_match_spec.h)
+// what the kernels fix (static_asserts in the launch units hold these equal to match_types.h, gn_step.h, gn_match_dense.h and gn_match_spec.h)
 constexpr int kQuad = 1, kPlane = 2;                     // kLayoutQuad / kLayoutPlane
 constexpr int kExactGroupRounds = 5;                     // rounds the exact-order team form keeps in registers
 constexpr int kDenseRound = 64 * 15;                     // beams per round of the producers-ahead form
@@ -117,7 +117,7 @@ inline void plan_team(const MatchSite& s, MatchPlan& p, int wps, int spb, int bp
     p.family = Family::kTeamExact;
     finish(p, "gn_match_kernel (exact order)", false);
   } else if (wps == 1 && (bpl == 9 || bpl == 17) && s.texel_cache && throughput_launch(s)) {
-    // throughput launches of long scans: the texel-cache form (gn_match.h)
+    // throughput launches of long scans: the texel-cache form (gn_match_cached.h)
     p.family = Family::kCached;
     p.relaxed = s.layout == kQuad && s.relaxed;
     p.wants_perm = true;  // (hsm_set_batch_order: the launch takes its scans through a permutation)
@@ -235,7 +235,7 @@ inline MatchPlan plan_match(const MatchSite& s) {
 
   if (free_team && dense) {
     // reference order, launches that cannot fill the chip with one wavefront per scan (single scans, small batches): one wavefront
-    // adds, fifteen produce one round ahead of it (gn_match_exact_dense_kernel, gn_match.h) -- a 16 k-beam match of configs[4] in
+    // adds, fifteen produce one round ahead of it (gn_match_exact_dense_kernel, gn_match_dense.h) -- a 16 k-beam match of configs[4] in
     // 0.9 instead of 1.2 ms, the nine chains' own 16 384 x 14 x 8.5 cycles being 0.8
     // Round 6, opt-in (HSM_EXACT_SPEC=1): the speculative-carry form (gn_match_spec.h) -- the same sums bit for bit, the chains cut
     // into segments that run in parallel -- whenever the host knows a true bound of the scan lengths (its product scratch is sized

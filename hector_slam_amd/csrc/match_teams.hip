@@ -1,7 +1,9 @@
-// match_teams.hip -- launches of the team forms of the matcher (gn_match.h: gn_match_kernel on 1 .. 16 wavefronts per scan,
-// either summation order) and of the fast texel-cache forms (gn_match_cached_kernel).  About eighty instantiations: a
+// match_teams.hip -- launches of the team forms of the matcher (gn_match_teams.h: gn_match_kernel on 1 .. 16 wavefronts per scan,
+// either summation order) and of the fast texel-cache forms (gn_match_cached.h: gn_match_cached_kernel).  About eighty instantiations: a
 // translation unit of its own so that an edit elsewhere does not rebuild them.
-#include "gn_match.h"
+#include "beam_sample.h"
+#include "gn_match_cached.h"
+#include "gn_match_teams.h"
 #include "hsm_ctx.h"
 
 namespace hsm {

@@ -3,8 +3,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "gn_match.h"
 #include "map_cells.h"
+#include "match_types.h"
 #include "occupancy_rows.h"
 
 namespace hsm {

@@ -289,7 +289,7 @@ int hsm_exchange_post_wait(hsm_exchange* x, const float* d_rows, int first_row, 
 
 }  // extern "C"
 
-// ---- a matcher launch that carries the exchange itself (gn_match.h: exchange_post_pose / exchange_wait_unpack) ---------------------
+// ---- a matcher launch that carries the exchange itself (gn_step.h: exchange_post_pose / exchange_wait_unpack) ---------------------
 // begin: what post_wait would launch, as the arguments a matcher kernel needs (epochs NOT advanced yet); commit: the matcher
 // launch that took them has been queued on `stream`.  A matcher form that cannot carry them leaves the step to hsm_exchange_post_wait.
 int hsm_host::exchange_fused_begin(hsm_exchange* x, int first_row, int n_rows, int lag, float* d_out_all, hsm::ExchangeFused* out) {

@@ -1,10 +1,14 @@
-// probe_kernels.h -- the kernels that only the probes and test hooks launch (probes.hip).  They are not templates, so exactly one
-// translation unit may include this header.
+// probe_kernels.h -- the kernels that only the probes and test hooks launch (probes.hip): the test hooks of the map planes and of
+// libm_exact.h, one evaluation of the matcher's sums at a given pose, and the likelihood and covariance of map-frame poses.  Some
+// are not templates, so exactly one translation unit may include this header.
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "gn_match.h"
+#include "beam_sample.h"
+#include "gn_step.h"
+#include "libm_exact.h"
 #include "map_cells.h"
+#include "match_types.h"
 
 namespace hsm {
 
@@ -46,6 +50,224 @@ __global__ void sincos_debug_kernel(const float* __restrict__ x, int n, float* _
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   sincos_f32(x[i], s[i], c[i]);
+}
+
+// ---- parity / debug kernels: one evaluation at a given map-frame pose ------------
+// H, dTr of one getCompleteHessianDerivs call (same device functions as the matcher)
+template <int LAYOUT, bool EXACT = false>
+__global__ void __launch_bounds__(1024) gn_eval_kernel(const LevelView L, const float2* __restrict__ pts,
+                                                      int n, float ex, float ey, float eth,
+                                                      float* out12 /* H[9] col-major, dTr[3] */) {
+  __shared__ __attribute__((aligned(16))) float red[2][9][16];
+  __shared__ float stage[EXACT ? 9 * (1024 + kExactPad) : 1];
+  const int lane = threadIdx.x & 63;
+  const int wit = threadIdx.x >> 6;
+  float sinRot, cosRot;
+  sincos_f32(eth, sinRot, cosRot);
+  Acc9 acc;
+  acc.zero();
+  const LevelRegs R = level_regs<LAYOUT>(L);
+  if (EXACT) {
+    const f2 e2 = step_origin(ex, ey), cs = f2{cosRot, sinRot}, sc = f2{sinRot, cosRot};
+    float run = 0.0f;
+    for (int base = 0; base < n; base += 1024) {
+      const int i = base + (int)threadIdx.x;
+      const float2 p = i < n ? pts[i] : make_float2(1.0e30f, 1.0e30f);
+      BeamRot r;
+      const BeamSample b = beam_fetch<LAYOUT>(R, e2, cs, sc, f2{p.x, p.y}, r);
+      float pr[9];
+      beam_products(b, r, pr);
+      run = exact_round<1024>(pr, stage, (int)threadIdx.x, run, min(1024, n - base));
+    }
+    float* const redf = &red[0][0][0];
+    if (threadIdx.x < 9) redf[threadIdx.x] = run;
+    __syncthreads();
+    acc.d01 = f2{redf[0], redf[1]}; acc.d2 = redf[2];
+    acc.hd = f2{redf[3], redf[4]}; acc.h22 = redf[5];
+    acc.h01 = redf[6]; acc.hr = f2{redf[7], redf[8]};
+  } else {
+    for (int i = threadIdx.x; i < n; i += 1024) {
+      const float2 p = pts[i];
+      beam_accumulate<LAYOUT>(R, ex, ey, sinRot, cosRot, p.x, p.y, acc);
+    }
+    team_allreduce9<16>(acc, red, 0, wit, lane);
+  }
+  if (threadIdx.x == 0) {
+    out12[0] = acc.hd.x; out12[1] = acc.h01; out12[2] = acc.hr.x;
+    out12[3] = acc.h01; out12[4] = acc.hd.y; out12[5] = acc.hr.y;
+    out12[6] = acc.hr.x; out12[7] = acc.hr.y; out12[8] = acc.h22;
+    out12[9] = acc.d01.x; out12[10] = acc.d01.y; out12[11] = acc.d2;
+  }
+}
+
+// per-beam M, dM/dx, dM/dy, rotDeriv
+template <int LAYOUT>
+__global__ void gn_beam_terms_kernel(const LevelView L, const float2* __restrict__ pts, int n, float ex,
+                                     float ey, float eth, float4* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float sinRot, cosRot;
+  sincos_f32(eth, sinRot, cosRot);
+  Acc9 acc;
+  acc.zero();
+  BeamTerms t;
+  const float2 p = pts[i];
+  const LevelRegs R = level_regs<LAYOUT>(L);
+  float rd = beam_accumulate<LAYOUT>(R, ex, ey, sinRot, cosRot, p.x, p.y, acc, &t);
+  // out-of-map beams: the matcher's zero-texel trick yields dM = -0 where the reference returns
+  // literal +0 (same sums, different sign bit); report the reference's literal values here
+  const float cx = ex + (cosRot * p.x - sinRot * p.y), cy = ey + (sinRot * p.x + cosRot * p.y);
+  float gx = -t.G.x, gy = -t.G.y;
+  if ((cx < 0.0f) | (cx > R.limx) | (cy < 0.0f) | (cy > R.limy)) {
+    t.M = gx = gy = 0.0f;
+    rd = ((-sinRot * p.x - cosRot * p.y) * gx + (cosRot * p.x - sinRot * p.y) * gy);
+  }
+  // a rotDeriv of exactly zero: the shared rotation (BeamRot) may give it the other SIGN than the source's expression (an end
+  // point with a -0.0 component: -(0 + -0) is -0, -0 - (-0) is +0).  No sum can show it, this hook can: report the source's
+  if (rd == 0.0f) rd = ((-sinRot * p.x - cosRot * p.y) * gx + (cosRot * p.x - sinRot * p.y) * gy);
+  out[i] = make_float4(t.M, gx, gy, rd);
+}
+
+// ---- f3: pose likelihood for a batch of map-frame states against ONE scan --------
+// OccGridMapUtil::getLikelihoodForState (OccGridMapUtil.h:184-214): residual = sum_i (1 - M_i),
+// likelihood = 1 - residual / size, with M from interpMapValue (:233-285) -- the same bilinear sample
+// as the matcher without the gradient.  One wavefront per state, beams strided over the lanes, the
+// texel gather and the zero-texel treatment of out-of-map beams shared with the matcher (an
+// out-of-map beam reads M = 0, i.e. funval = 1, exactly the reference's `return 0.0f`).
+
+template <int LAYOUT, bool EXACT = false>
+__global__ void __launch_bounds__(256) likelihood_kernel(const LevelView L, const float* __restrict__ states,
+                                                         int batch, const float2* __restrict__ pts, int n,
+                                                         float pt_scale, float* __restrict__ out_lh,
+                                                         float* __restrict__ out_residual) {
+  __shared__ float rows[EXACT ? 4 : 1][EXACT ? 64 : 1];
+  const int lane = threadIdx.x & 63;
+  const int b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (b >= batch) return;
+  const float ex = states[3 * b], ey = states[3 * b + 1];
+  float sinRot, cosRot;
+  sincos_f32(states[3 * b + 2], sinRot, cosRot);
+  const LevelRegs R = level_regs<LAYOUT>(L);
+  const f2 e2 = step_origin(ex, ey), cs = f2{cosRot, sinRot}, sc = f2{sinRot, cosRot};
+  float residual = 0.0f;
+  if (EXACT) {
+    float* row = rows[(threadIdx.x >> 6) & 3];
+    for (int base = 0; base < n; base += 64) {  // wave-uniform trip count
+      const int i = base + lane;
+      // padding beyond the scan: funval = +0 (M is only ever 0 .. 1, so no sum is -0 and +0 changes nothing)
+      float funval = 0.0f;
+      if (i < n) {
+        const float2 p = pts[i];
+        BeamRot r;
+        const BeamSample s = beam_fetch<LAYOUT>(R, e2, cs, sc, f2{p.x * pt_scale, p.y * pt_scale}, r);
+        const float M = ((s.lo.x * s.X.x + s.lo.y * s.X.y) * (s.Y.x)) + ((s.hi.x * s.X.x + s.hi.y * s.X.y) * (s.Y.y));
+        funval = 1.0f - M;
+      }
+      residual = exact_residual_round(funval, row, lane, residual);
+    }
+  } else {
+    for (int i = lane; i < n; i += 64) {
+      const float2 p = pts[i];
+      BeamRot r;
+      const BeamSample s = beam_fetch<LAYOUT>(R, e2, cs, sc, f2{p.x * pt_scale, p.y * pt_scale}, r);
+      const float M = ((s.lo.x * s.X.x + s.lo.y * s.X.y) * (s.Y.x)) + ((s.hi.x * s.X.x + s.hi.y * s.X.y) * (s.Y.y));
+      residual += 1.0f - M;
+    }
+    residual = wave_allreduce(residual);
+  }
+  if (lane == 0) {
+    if (out_lh) out_lh[b] = 1 - (residual / (float)n);
+    if (out_residual) out_residual[b] = residual;  // getResidualForState (:205-221)
+  }
+}
+
+// OccGridMapUtil::getCovarianceForPose (HSL/map/OccGridMapUtil.h:106-160) + getCovMatrixWorldCoords
+// (:162-188): 7 sigma points around a MAP-frame pose (+-1.5 cells, +-0.05 rad, the pose itself), their
+// likelihoods weight a sample mean and a 3x3 sample covariance.  One workgroup per pose, wave w scores
+// sigma point w (same sampler as above), thread 0 does the 7-term statistics in the source's order.
+template <int LAYOUT, bool EXACT = false>
+__global__ void __launch_bounds__(448) pose_covariance_kernel(const LevelView L, const float* __restrict__ poses,
+                                                              int batch, const float2* __restrict__ pts, int n,
+                                                              float pt_scale, float cell_length,
+                                                              float* __restrict__ out_cov_map,
+                                                              float* __restrict__ out_cov_world,
+                                                              float* __restrict__ out_lh7) {
+  __shared__ float lh[7];
+  __shared__ float rows[EXACT ? 7 : 1][EXACT ? 64 : 1];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int b = blockIdx.x;
+  const float deltaTransX = 1.5f, deltaTransY = 1.5f, deltaAng = 0.05f;
+  const float x = poses[3 * b], y = poses[3 * b + 1], ang = poses[3 * b + 2];
+  float sp[7][3] = {{x + deltaTransX, y, ang}, {x - deltaTransX, y, ang}, {x, y + deltaTransY, ang},
+                    {x, y - deltaTransY, ang}, {x, y, ang + deltaAng},    {x, y, ang - deltaAng}, {x, y, ang}};
+  {
+    float ex = sp[0][0], ey = sp[0][1], ea = sp[0][2];
+#pragma unroll
+    for (int k = 1; k < 7; ++k)
+      if (w == k) ex = sp[k][0], ey = sp[k][1], ea = sp[k][2];
+    float sinRot, cosRot;
+    sincos_f32(ea, sinRot, cosRot);
+    const LevelRegs R = level_regs<LAYOUT>(L);
+    const f2 e2 = step_origin(ex, ey), cs = f2{cosRot, sinRot}, sc = f2{sinRot, cosRot};
+    float residual = 0.0f;
+    if (EXACT) {
+      for (int base = 0; base < n; base += 64) {
+        const int i = base + lane;
+        float funval = 0.0f;
+        if (i < n) {
+          const float2 p = pts[i];
+          BeamRot r;
+          const BeamSample s = beam_fetch<LAYOUT>(R, e2, cs, sc, f2{p.x * pt_scale, p.y * pt_scale}, r);
+          const float M = ((s.lo.x * s.X.x + s.lo.y * s.X.y) * (s.Y.x)) + ((s.hi.x * s.X.x + s.hi.y * s.X.y) * (s.Y.y));
+          funval = 1.0f - M;
+        }
+        residual = exact_residual_round(funval, rows[w], lane, residual);
+      }
+    } else {
+      for (int i = lane; i < n; i += 64) {
+        const float2 p = pts[i];
+        BeamRot r;
+        const BeamSample s = beam_fetch<LAYOUT>(R, e2, cs, sc, f2{p.x * pt_scale, p.y * pt_scale}, r);
+        const float M = ((s.lo.x * s.X.x + s.lo.y * s.X.y) * (s.Y.x)) + ((s.hi.x * s.X.x + s.hi.y * s.X.y) * (s.Y.y));
+        residual += 1.0f - M;
+      }
+      residual = wave_allreduce(residual);
+    }
+    if (lane == 0) lh[w] = 1 - (residual / (float)n);
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  // likelihoods.sum(): fixed-size 7-vector, unrolled halves (0..2) + (3..6)
+  const float sum = ((lh[0] + (lh[1] + lh[2])) + ((lh[3] + lh[4]) + (lh[5] + lh[6])));
+  const float invLhNormalizer = 1 / sum;
+  float mean[3] = {0.0f, 0.0f, 0.0f};
+  for (int i = 0; i < 7; ++i)
+    for (int r = 0; r < 3; ++r) mean[r] += sp[i][r] * lh[i];
+  for (int r = 0; r < 3; ++r) mean[r] *= invLhNormalizer;
+  float cov[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // column major
+  for (int i = 0; i < 7; ++i) {
+    const float d[3] = {sp[i][0] - mean[0], sp[i][1] - mean[1], sp[i][2] - mean[2]};
+    const float wgt = lh[i] * invLhNormalizer;
+    for (int c = 0; c < 3; ++c)
+      for (int r = 0; r < 3; ++r) cov[c * 3 + r] += wgt * (d[r] * d[c]);
+  }
+  if (out_lh7)
+    for (int i = 0; i < 7; ++i) out_lh7[7 * b + i] = lh[i];
+  if (out_cov_map)
+    for (int i = 0; i < 9; ++i) out_cov_map[9 * b + i] = cov[i];
+  if (out_cov_world) {
+    const float scaleTrans = cell_length, scaleTransSq = scaleTrans * scaleTrans;
+    float* W = out_cov_world + 9 * b;  // (r,c) at c*3+r
+    W[0] = cov[0] * scaleTransSq;
+    W[4] = cov[4] * scaleTransSq;
+    W[1] = cov[1] * scaleTransSq;  // (1,0)
+    W[3] = W[1];
+    W[2] = cov[2] * scaleTrans;  // (2,0)
+    W[6] = W[2];
+    W[5] = cov[5] * scaleTrans;  // (2,1)
+    W[7] = W[5];
+    W[8] = cov[8];
+  }
 }
 
 }  // namespace hsm

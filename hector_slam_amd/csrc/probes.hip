@@ -1,14 +1,13 @@
 // probes.hip -- the entries of the C ABI (include/hector_mi355/capi.h) that look INTO a context and are never timed: the
 // host-array probes of the matcher's sums (likelihood, residual, covariance, Hessian, single beams), a level's planes down and
-// up, its boxes, and the hsm_debug_* test hooks.  Each one ends in a wait for the context's stream.  The kernel templates are
-// gn_match.h's; the kernels nothing else launches are in probe_kernels.h.  What these entries need of the core runtime
+// up, its boxes, and the hsm_debug_* test hooks.  Each one ends in a wait for the context's stream.  Their kernels, which nothing else
+// launches, are in probe_kernels.h (sampler and sums: beam_sample.h, gn_step.h).  What these entries need of the core runtime
 // (hector_mi355.hip) is declared in hsm_ctx.h.  (Ray distances are in rays.hip.)
 #include <hip/hip_runtime.h>
 #include <math.h>
 
 #include <mutex>
 
-#include "gn_match.h"
 #include "hector_mi355/capi.h"
 #include "hsm_ctx.h"
 #include "probe_kernels.h"

@@ -19,7 +19,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "gn_match.h"
+#include "beam_sample.h"
 #include "map_cells.h"
 
 namespace hsm {

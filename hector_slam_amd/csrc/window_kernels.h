@@ -1,7 +1,11 @@
 // window_kernels.h -- the kernels of window.hip: the likelihood of ONE scan at every pose of a window that never exists in memory
 // (two forms with the same bits), window indices turned into poses, and the K best of an array of scores.
 #pragma once
-#include "gn_match.h"
+#include <hip/hip_runtime.h>
+
+#include "beam_sample.h"
+#include "gn_step.h"
+#include "match_types.h"
 #include "window_grid.h"
 
 namespace hsm {

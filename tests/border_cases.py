@@ -1,5 +1,5 @@
 """Inputs for the map-EDGE tests of the sampler every matcher, scorer and probe kernel shares (interpMapValueWithDerivatives,
-OccGridMapUtil.h:287-347; the kernels' copy of it is gn_match.h cell_coord / sample_fetch and the texel-cache re-gather of
+OccGridMapUtil.h:287-347; the kernels' copy of it is beam_sample.h cell_coord / sample_fetch and the texel-cache re-gather of
 gn_match_exact.h): map coordinates that land EXACTLY on 0, -0.0, a subnormal, an integer, dims - 2 and one ulp either side of it,
 far outside, and beams that cross the border between two Gauss-Newton steps -- on maps whose every cell, border cells and
 corners included, holds a value of its own, so that a sampler that reads the wrong border cell or lets a beam at lim + 1 ulp

@@ -11,7 +11,7 @@ a sum through at most `d` fp32 additions.  With p_i the exact products, the comp
     |s - sum p_i| <= gamma(d + 1) * sum |p_i|,      gamma(k) = k u / (1 - k u)
 (Higham, Accuracy and Stability of Numerical Algorithms, 2nd ed., 4.2: every term carries at most d + 1 factors
 (1 + delta)).  d is the longest chain of additions a single beam's product passes through, read off the kernel source
-(hector_slam_amd/csrc/gn_match.h):
+(hector_slam_amd/csrc/: gn_match_teams.h, gn_match_cached.h, gn_match_dense.h, probe_kernels.h; the reductions: gn_step.h):
 
   gn_match_kernel<W, SPB, L, BPL>  (team forms, T = 64 W lanes per scan): lane j adds the beams j, j + T, j + 2T, ...
       into its own accumulator (BPL register-resident beams, padding slots add exact zeros, beams beyond T * BPL stream
@@ -85,7 +85,7 @@ def _fma(a, b, c):
 
 
 def relaxed_factors(prob, pm, pts, s, c):
-    """(M, gx, gy, rotDeriv) as gn_match_cached_kernel<.., RELAXED = true> computes them (gn_match.h, `locate` and
+    """(M, gx, gy, rotDeriv) as gn_match_cached_kernel<.., RELAXED = true> computes them (gn_match_cached.h, `locate` and
     `consume`): the rotation, the bilinear blend as two lerps, the gradient blends and rotDeriv as contracted
     multiply-adds.  Its endpoint positions differ from the reference's in the last bit, so a beam within an ulp of a cell
     border may sample the neighbouring cell, whose source-literal gradient is another one: the reference's factors are
@@ -198,7 +198,7 @@ def check_dtr(dg, ev: Eval64, d: int, what: str):
 
 
 def solve32(H, b):
-    """the kernel's step, gn_solve_and_step (gn_match.h; Eigen's cofactor inverse, ScanMatcher.h:201-217) in numpy fp32 with
+    """the kernel's step, gn_solve_and_step (gn_step.h; Eigen's cofactor inverse, ScanMatcher.h:201-217) in numpy fp32 with
     the same operations in the same order: (s0, s1, s2 clamped to +-0.2) and |inverse| (3, 3) float64"""
     f = np.float32
     H = np.asarray(H, np.float32).reshape(3, 3)

@@ -3,7 +3,7 @@ tests/test_border_reference.py).
 
 All matcher, scorer and probe kernels share one beam loop -- rotate, add the estimate, bounds-test on the bit patterns, truncate
 with a saturating convert, v_fract, gather four texels; out-of-map beams read an all-zero texel, the texel-cache forms re-gather
-only where the effective offset changed (gn_match.h cell_coord / sample_fetch, gn_match_exact.h locate).  Here that loop meets
+only where the effective offset changed (beam_sample.h cell_coord / sample_fetch, gn_match_exact.h locate).  Here that loop meets
 coordinates exactly on 0, -0.0, subnormals, integers, dims - 2 and one ulp either side of it, and beams that cross the border
 between two Gauss-Newton steps, on maps whose border cells all differ.  Library default mode (the reference's summation order):
 every comparison is on uint32 views.  The opt-in fast forms are held to the float64 sums of tests/gn_f64.py with its bound.

@@ -4,7 +4,7 @@ step, the pose and the covariance -- on every scan, settled or not.
 What makes that possible: the per-beam products were bit-exact all along; sinf / cosf / expf
 are glibc's algorithms operation for operation (csrc/libm_exact.h); and in this mode the nine sums of
 getCompleteHessianDerivs (OccGridMapUtil.h:76-98) run in the reference's order, beam 0 .. n-1, as nine sequential
-fp32 chains (gn_match.h exact_round).  So no tolerance appears in this file: every comparison is on uint32 views.
+fp32 chains (gn_step.h exact_round).  So no tolerance appears in this file: every comparison is on uint32 views.
 
 Runs against both CPU checkers where oracle/_ref/libhector_ref.so is present: "ho" (restatement) and "hr" (the
 unmodified reference headers).

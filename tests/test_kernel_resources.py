@@ -183,7 +183,7 @@ def occupancies(asm):
 
 def designed_waves_per_simd(name):
     m = re.search(r"15gn_match_kernelILi(\d+)ELi(\d+)ELi\d+ELi\d+ELb([01])E", name)
-    if m:  # gn_match.h: four, except the exact-order teams of two / four wavefronts (a group of five rounds alive: three)
+    if m:  # gn_match_teams.h: four, except the exact-order teams of two / four wavefronts (a group of five rounds alive: three)
         wps, spb, exact = int(m.group(1)), int(m.group(2)), m.group(3) == "1"
         return 3 if (exact and spb == 1 and wps in (2, 4)) else 4
     m = re.search(r"22gn_match_cached_kernelILi\d+ELi\d+ELi\d+ELi(\d+)ELb[01]E", name)

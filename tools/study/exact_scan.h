@@ -2,7 +2,7 @@
 //
 // getCompleteHessianDerivs (OccGridMapUtil.h:76-98) adds the nine per-beam products to nine running fp32 sums in beam order;
 // the result depends on that order through the rounding of every partial sum, which is why HSM_PARITY_EXACT keeps nine
-// literal chains of dependent v_add_f32 (hector_slam_amd/csrc/gn_match.h exact_chain: 8.5 cycles per beam, the floor of that form).  This header
+// literal chains of dependent v_add_f32 (hector_slam_amd/csrc/gn_step.h exact_chain: 8.5 cycles per beam, the floor of that form).  This header
 // holds the element arithmetic of a form that produces the SAME bits without the dependent chain (round-4 verdict, item 1(ii)):
 //
 //   While the running sum s stays inside one binade [2^e, 2^(e+1)) every float in reach is a multiple of u = 2^(e-23), s = S*u
