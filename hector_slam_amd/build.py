@@ -40,8 +40,9 @@ def _closure(path: str, seen: list[str]) -> list[str]:
 
 
 # translation unit -> itself and the files it includes, directly or not (its own staleness test); the link order
-_UNIT_NAMES = ["hector_mi355.hip", "map_update.hip", "ingest.hip", "occupancy.hip", "probes.hip", "rays.hip", "map_copy.hip",
-               "map_shift.hip", "window.hip", "group.hip", "match_exact_cached.hip", "match_teams.hip", "pose_exchange.hip"]
+_UNIT_NAMES = ["hector_mi355.hip", "match.hip", "map_update.hip", "ingest.hip", "occupancy.hip", "probes.hip", "rays.hip",
+               "map_copy.hip", "map_shift.hip", "window.hip", "group.hip", "match_exact_cached.hip", "match_teams.hip",
+               "pose_exchange.hip"]
 UNITS = {u: _closure(os.path.join(_CSRC, u), []) for u in _UNIT_NAMES}
 SRC = os.path.join(_CSRC, "hector_mi355.hip")
 DEPS = sorted({d for deps in UNITS.values() for d in deps})

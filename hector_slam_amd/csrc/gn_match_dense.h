@@ -1,4 +1,4 @@
-// gn_match_dense.h -- the two forms of the matcher for ONE dense scan, launched by hector_mi355.hip only: the producers-ahead
+// gn_match_dense.h -- the two forms of the matcher for ONE dense scan, launched by match.hip only: the producers-ahead
 // form in the reference's summation order (gn_match_exact_dense_kernel) and the multi-workgroup form of HSM_PARITY_FAST
 // (gn_match_coop_kernel).  The design of the matcher as a whole: gn_match_teams.h.
 #pragma once

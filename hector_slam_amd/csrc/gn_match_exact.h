@@ -71,7 +71,7 @@ constexpr int kXRows = 9;  // staged rows per scan and round: the nine products 
 // CW (round 5): a CHAIN WAVEFRONT.  The workgroup gets one more wavefront (index NS) that produces nothing: it runs every
 // round's chain job, the running sums never leave its registers inside a GN step, and no producer carries a job on top of
 // its own row any more -- the round's critical path is max(job, production) instead of the owner's job + production.
-// Launched for batches that leave a CU at most THREE such workgroups (hector_mi355.hip, launch_match_exact): the dispatcher
+// Launched for batches that leave a CU at most THREE such workgroups (match_plan.h, plan_match): the dispatcher
 // places a workgroup only where every SIMD has room for ceil(5 / 4) = 2 of its wavefronts, so the third workgroup fits for
 // certain only if a SIMD holds six wavefronts -- 80 VGPRs, i.e. fewer rows with a cached texel (BPC = HSM_XBPC_CW) -- and
 // a fourth does not (tools/study/ubench_wg_placement.hip, profiles/r05/README.md 9); the launch bounds ask for five per SIMD

@@ -1,7 +1,7 @@
 // group.hip -- the multi-GPU group of the C ABI (include/hector_mi355/capi.h: hsm_group_*, hsm_shard_bounds): one context per
 // device, a worker thread per replica beyond the first, and the gather of the shards' results.  Host code only, no kernel of its
-// own: it reaches the core runtime (hector_mi355.hip) through the C ABI and through select_device, match_batch_device_nolock,
-// fail and set_error_text (hsm_ctx.h, hsm_host.h).
+// own: it reaches the core runtime (hector_mi355.hip) through the C ABI and through select_device, fail and set_error_text, and
+// the matcher (match.hip) through match_batch_device_nolock (hsm_ctx.h, hsm_host.h).
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 // RCCL: declarations only -- librccl is dlopen'ed by the group entry points (rccl_api), never linked.  A ROCm install without

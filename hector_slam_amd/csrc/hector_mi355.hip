@@ -1,6 +1,8 @@
-// hector_mi355.hip -- host runtime + C ABI (include/hector_mi355/capi.h) of the
-// MI355X-native hector_mapping scan matcher: the context's life cycle and every match entry.  Kernels launched here: gn_match_dense.h, gn_match_spec.h, score_kernels.h; the batch / team
-// matcher forms are launched from match_exact_cached.hip and match_teams.hip, map updates and the scan loop are in map_update.hip, the
+// hector_mi355.hip -- the core of the host runtime + C ABI (include/hector_mi355/capi.h) of the
+// MI355X-native hector_mapping scan matcher: the context's life cycle, its settings, the error text, the views of a level and the
+// stream hand-over around map updates.  Host code only: no kernel is launched here.  The match, score and select entries and the
+// plan of a matcher launch are in match.hip, the batch / team matcher forms in match_exact_cached.hip and match_teams.hip, map
+// updates and the scan loop in map_update.hip, the
 // probes and test hooks in probes.hip, the multi-GPU group in group.hip, raw-scan conversion in ingest.hip, the occupancy exports in
 // occupancy.hip (hsm_ctx.h says which unit holds what).
 //
@@ -13,26 +15,19 @@
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off (see build.py).
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <limits.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
-#include <atomic>
-#include <chrono>
 #include <mutex>
 #include <string>
 #include <vector>
 
-#include "gn_match_dense.h"
-#include "gn_match_spec.h"
-#include "gn_step.h"
 #include "hector_mi355/capi.h"
 #include "hsm_ctx.h"
 #include "hsm_host.h"
 #include "map_cells.h"
-#include "score_kernels.h"
 
 namespace {
 
@@ -193,147 +188,6 @@ void free_level(Level& L, TeardownLog* log = nullptr) {
   L = Level();
 }
 
-static_assert(hsm_plan::kQuad == kLayoutQuad && hsm_plan::kPlane == kLayoutPlane && hsm_plan::kExactGroupRounds == kExactGroupRounds &&
-                  hsm_plan::kDenseRound == kDenseRound && hsm_plan::kSpec1MaxBeams == kSpec1MaxBeams,
-              "match_plan.h restates match_types.h / gn_step.h / gn_match_dense.h / gn_match_spec.h");
-static_assert(hsm_plan::kParityFast == HSM_PARITY_FAST && hsm_plan::kParityExact == HSM_PARITY_EXACT && hsm_plan::kParityRelaxed == HSM_PARITY_RELAXED,
-              "match_plan.h restates capi.h");
-
-using hsm_plan::Family;
-using hsm_plan::MatchSite;
-using hsm_plan::plan_match;
-
-// the site of a match launch (match_plan.h): the context's knobs and the call's shape.  The staging of a single scan and its
-// launch both come here, so that they plan the same form.  `stream`: only the opt-in speculative-carry form asks whether it is
-// being captured, so nobody else pays for the question.
-MatchSite match_site(const hsm_ctx* h, int batch, int max_n, int n_bound, bool batched, bool trace, hipStream_t stream) {
-  MatchSite s;
-  s.batch = batch, s.max_n = max_n, s.n_bound = n_bound;
-  s.exact = wants_exact(h), s.relaxed = h->relaxed, s.layout = h->layout;
-  s.batched = batched, s.trace = trace, s.clock_probe = h->clock_probe != nullptr;
-  s.capturing = h->exact_spec && stream_capturing(stream);
-  s.compute_units = h->compute_units, s.level0_cells = h->levels[0].cells();
-  s.wps_override = h->wps_override, s.bpl_override = h->bpl_override;
-  s.texel_cache = h->texel_cache, s.exact_cached = h->exact_cached;
-  s.exact_chain_wave = h->exact_chain_wave != 0, s.exact_split_tail = h->exact_split_tail != 0;
-  s.exact_dense = h->exact_dense, s.exact_dense_min = h->exact_dense_min;
-  s.exact_spec = h->exact_spec, s.exact_spec1 = h->exact_spec1;
-  s.spb_large = h->spb_large, s.coop_min_beams = h->coop_min_beams, s.coop_skip = h->coop_skip > 0;
-  return s;
-}
-MatchSite single_scan_site(const hsm_ctx* h, int n, bool trace = false) { return match_site(h, 1, n, n, false, trace, h->stream); }
-
-// what hsm_last_launch_config / _kernel / _parity report: the plan that was launched
-void record_launch(hsm_ctx* h, const MatchPlan& plan) {
-  for (int i = 0; i < 6; ++i) h->last_cfg[i] = plan.record[i];
-  h->last_kernel = plan.name;
-  h->last_parity = plan.parity;
-}
-
-// the one-workgroup-per-scan forms of this unit: Family::kExactDense, kSpec (gn_match_dense.h, gn_match_spec.h: `batch` workgroups) and
-// kSpec1 (one scan)
-int launch_workgroup_form(hsm_ctx* h, MatchParams P, MatchPlan& plan, const MatchSite& site, hipStream_t stream) {
-  if (plan.family == Family::kSpec) {
-    // The product scratch is the launching stream's own (two streams' launches would write the same rows at once).  A launch into a
-    // graph capture was planned in the literal form, which needs no scratch: a graph never reads a block that an eager launch grows
-    // (frees), and nothing is allocated or synchronised while the caller captures.  A ninth stream falls to it here.
-    hsm_ctx::SpecScratch* sb = nullptr;
-    for (hsm_ctx::SpecScratch& b : h->spec_scratch)
-      if (b.s == stream) sb = &b;
-    if (!sb && h->spec_scratch.size() < 8) {
-      h->spec_scratch.push_back({stream, {}});
-      sb = &h->spec_scratch.back();
-    }
-    if (!sb) {
-      MatchSite literal = site;
-      literal.exact_spec = false;
-      plan = plan_match(literal);
-    } else {
-      const size_t stride = spec_scratch_float4s_bound(P.n_bound);  // enough for every n <= n_bound
-      const size_t need = stride * (size_t)P.batch;
-      if (!sb->d.holds(need)) HIP_TRY(hipStreamSynchronize(stream));  // (a launch of this stream in flight may still read the old block)
-      if (int rc = sb->d.reserve(need)) return rc;
-      P.spec_scratch = (float*)sb->d.p;
-      P.spec_stride = (unsigned)stride;
-      P.spec_stats = h->d_spec_stats;
-    }
-  }
-#define HSM_LAUNCH_WG(KERNEL)                                                              \
-  do {                                                                                     \
-    if (plan.layout == kLayoutPlane)                                                       \
-      hipLaunchKernelGGL((KERNEL<kLayoutPlane>), dim3(plan.grid), dim3(plan.block), 0, stream, P); \
-    else                                                                                   \
-      hipLaunchKernelGGL((KERNEL<kLayoutQuad>), dim3(plan.grid), dim3(plan.block), 0, stream, P);  \
-  } while (0)
-  if (plan.family == Family::kSpec) HSM_LAUNCH_WG(gn_match_spec_kernel);
-  else if (plan.family == Family::kExactDense) HSM_LAUNCH_WG(gn_match_exact_dense_kernel);
-  else HSM_LAUNCH_WG(gn_match_spec1_kernel);
-#undef HSM_LAUNCH_WG
-  HIP_TRY(hipGetLastError());
-  return HSM_OK;
-}
-
-// launches `plan` (any family but the cooperative one, which match_single launches itself) and records it
-int launch_plan(hsm_ctx* h, MatchParams P, const MatchSite& site, MatchPlan plan, hipStream_t stream) {
-  if (plan.wants_perm)
-    if (int rc = ensure_batch_perm(h, P, stream)) return rc;  // (hsm_set_batch_order)
-  int rc;
-  switch (plan.family) {
-    case Family::kExactDense:
-    case Family::kSpec:
-    case Family::kSpec1: rc = launch_workgroup_form(h, P, plan, site, stream); break;
-    case Family::kExactCached:
-    case Family::kExactCachedCw:
-      if (plan.tail_batch > 0) {
-        // the whole generations, and behind them the part-filled last one in its own launch
-        MatchParams A = P, B = P;
-        A.batch = P.batch - plan.tail_batch, B.batch = plan.tail_batch;
-        if (P.perm) {  // (a permuted batch: the second launch takes the rest of the permutation, its scan indices stay absolute)
-          B.perm = P.perm + A.batch;
-        } else {
-          B.begin_world = P.begin_world + 3 * (size_t)A.batch;
-          if (P.offsets) B.offsets = P.offsets + A.batch;  // (absolute offsets into pts: the pointer moves, pts stays)
-          B.out_pose = P.out_pose + 3 * (size_t)A.batch;
-          if (P.out_cov) B.out_cov = P.out_cov + 9 * (size_t)A.batch;
-        }
-        B.clock_probe = nullptr;  // (scan 0's probe belongs to the first launch)
-        A.xp.world = 0;           // (neither part carries the pose exchange: plan_split_part)
-        B.xp.world = 0;
-        rc = launch_exact_cached_form(h, A, hsm_plan::plan_split_part(site, plan.tail_batch, false), stream);
-        if (rc == HSM_OK) rc = launch_exact_cached_form(h, B, hsm_plan::plan_split_part(site, plan.tail_batch, true), stream);
-      } else {
-        rc = launch_exact_cached_form(h, P, plan, stream);
-      }
-      break;
-    default: rc = launch_team_form(h, P, plan, stream); break;
-  }
-  if (rc == HSM_OK) record_launch(h, plan);
-  return rc;
-}
-
-int launch_match(hsm_ctx* h, const MatchParams& P, int max_n, hipStream_t stream) {
-  h->last_sorted = false;  // (the forms that take a permuted batch set it: ensure_batch_perm)
-  MatchSite site = match_site(h, P.batch, max_n, P.n_bound, P.begin_world != nullptr, P.trace != nullptr, stream);
-  site.exchange = P.xp.world > 0, site.exchange_wait_blocks = P.xp.wait_blocks;
-  site.coop_skip = true;  // (the cooperative form is match_single's to launch: here its scan goes to one workgroup)
-  return launch_plan(h, P, site, plan_match(site), stream);
-}
-
-// the schedule of MapRepMultiMap::matchData (MapRepMultiMap.h:116-132): coarse levels
-// maxIterations = 3, level 0 maxIterations = 5, each plus the unconditional first step.  `batched`: the batched entries, where
-// the test hook hsm_debug_set_schedule may restrict the schedule to one level (every level's view stays filled: the batch
-// order reads level 0's)
-void fill_schedule(const hsm_ctx* h, MatchParams& P, bool batched = false) {
-  const int nl = (int)h->levels.size();
-  for (int l = 0; l < nl; ++l) P.lv[l] = level_view(h->levels[l], level_factor(l), l == 0 ? 6 : 4);
-  P.first_level = nl - 1;
-  P.last_level = 0;
-  if (batched && h->sched_level >= 0 && h->sched_level < nl) {
-    P.lv[h->sched_level].gn_steps = h->sched_steps;
-    P.first_level = P.last_level = h->sched_level;
-  }
-}
-
 }  // namespace
 
 namespace hsm_host {
@@ -438,45 +292,6 @@ int hsm_host::order_map_reader(hsm_ctx* h, hipStream_t s, const char* who, hsm_c
   // no marker here (an event record between back-to-back launches costs 2-3 us of kernel time each): the
   // next writer of the map records one on every stream with a pending reader (order_after_foreign_match)
   *mark = fs;
-  return HSM_OK;
-}
-
-int hsm_host::match_batch_device_nolock(hsm_ctx* h, int batch, const float* d_begin_world, const float* d_pts_xy,
-                                        const int* d_scan_offsets, int shared_n, float* d_out_pose,
-                                        float* d_out_cov, void* stream, int n_bound, const ExchangeFused* xp) {
-  if (batch < 0 || !d_begin_world || !d_out_pose || (!d_scan_offsets && shared_n < 0))
-    return fail(HSM_ERR_INVALID, "hsm_match_batch_device: bad argument");
-  if (batch == 0) return HSM_OK;
-  if (int rc = select_device(h)) return rc;
-  MatchParams P;
-  memset(&P, 0, sizeof P);
-  fill_schedule(h, P, true);
-  P.batch = batch;
-  P.begin_world = d_begin_world;
-  P.pts = reinterpret_cast<const float2*>(d_pts_xy);
-  P.offsets = d_scan_offsets;
-  P.shared_n = shared_n;
-  P.out_pose = d_out_pose;
-  P.out_cov = d_out_cov;
-  // a true bound of the scan lengths, where the host has one: a shared scan's length, or what the caller computed from host offsets
-  P.n_bound = d_scan_offsets ? n_bound : shared_n;
-  if (xp) P.xp = *xp;
-  h->fused_exchange_done = false;
-  // workgroup -> XCD mapping (beam_sample.h, xcd_block): chunks dealt to the XCDs in turn balance the data-dependent
-  // per-scan time; maps whose touched region outgrows the L2s keep one contiguous eighth of the batch per XCD
-  const bool outgrows = hsm_plan::level0_outgrows_l2(h->levels[0].cells());
-  P.xcd_chunk = outgrows ? 0 : h->xcd_chunk;
-  P.wg_sync = h->wg_sync >= 0 ? h->wg_sync : (outgrows ? 1 : 0);
-  P.clock_probe = h->clock_probe;
-  // per-scan length is only known on the device for CSR input; shared_n doubles as the sizing HINT there
-  // (callers pass the typical beams per scan, 0 = unknown).  It only picks the kernel form: every form handles
-  // scans longer than the hint (the beams beyond the register/LDS-resident ones stream from memory).
-  const int hint = shared_n > 0 ? shared_n : 1081;
-  hipStream_t s = (hipStream_t)stream;
-  hsm_ctx::ForeignStream* fs = nullptr;
-  if (int rc = order_map_reader(h, s, "hsm_match_batch_device", &fs)) return rc;
-  if (int rc = launch_match(h, P, hint, s)) return rc;
-  if (fs) fs->pending = true;
   return HSM_OK;
 }
 
@@ -789,541 +604,6 @@ int hsm_last_launch_config(const hsm_ctx* h, int cfg[5]) {
   return HSM_OK;
 }
 
-int hsm_match_batch_device(hsm_ctx* h, int batch, const float* d_begin_world, const float* d_pts_xy,
-                           const int* d_scan_offsets, int shared_n, float* d_out_pose, float* d_out_cov,
-                           void* stream) {
-  if (!h) return fail(HSM_ERR_INVALID, "null context");
-  std::lock_guard<std::mutex> lk(h->mu);
-  return match_batch_device_nolock(h, batch, d_begin_world, d_pts_xy, d_scan_offsets, shared_n, d_out_pose,
-                                   d_out_cov, stream);
-}
-
-int hsm_match_batch_device_gather(hsm_ctx* h, int batch, const float* d_begin_world, const float* d_pts_xy,
-                                  const int* d_scan_offsets, int shared_n, float* d_out_pose, float* d_out_cov,
-                                  hsm_exchange* x, int first_row, int lag, float* d_out_all, void* stream) {
-  if (!h || !x) return fail(HSM_ERR_INVALID, "null context / exchange");
-  if (batch <= 0) return fail(HSM_ERR_INVALID, "hsm_match_batch_device_gather: every rank posts a non-empty shard");
-  std::lock_guard<std::mutex> lk(h->mu);
-  // The exchange step of this match: carried by the matcher launch itself where the form can (the exact-order batch forms: every
-  // wavefront posts its pose from the kernel's epilogue, extra workgroups at the end of the grid unpack the epoch `lag` matches
-  // back -- no launch of its own, nothing between two matcher launches), else one launch of the stand-alone exchange kernel behind it.
-  ExchangeFused f;
-  if (int rc = hsm_host::exchange_fused_begin(x, first_row, batch, lag, d_out_all, &f)) return rc;
-  if (int rc = match_batch_device_nolock(h, batch, d_begin_world, d_pts_xy, d_scan_offsets, shared_n, d_out_pose, d_out_cov, stream, 0, &f))
-    return rc;
-  if (h->fused_exchange_done) {
-    hsm_host::exchange_fused_commit(x, f);
-    return HSM_OK;
-  }
-  return hsm_exchange_post_wait(x, d_out_pose, first_row, batch, lag, d_out_all, stream);
-}
-
-// The weighting step behind a batched match: B (world pose, scan) pairs scored on `level` in one launch of score_batch_kernel
-// (score_kernels.h).  A reader of the map like the batched match, so ordered like it (order_map_reader); no workspace, no state.
-static int score_batch_device_nolock(hsm_ctx* h, int level, int batch, const float* d_poses_world, const float* d_pts_xy,
-                                     const int* d_scan_offsets, int shared_n, float* d_out_likelihood,
-                                     float* d_out_residual, void* stream) {
-  if (int rc = valid_level(h, level)) return rc;
-  if (batch < 0 || (!d_out_likelihood && !d_out_residual) || (!d_scan_offsets && shared_n < 0) ||
-      (batch > 0 && (!d_poses_world || (!d_pts_xy && !d_scan_offsets && shared_n > 0))))
-    return fail(HSM_ERR_INVALID, "hsm_score_batch_device: bad argument");
-  if (batch == 0) return HSM_OK;
-  if (int rc = select_device(h)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  hsm_ctx::ForeignStream* fs = nullptr;
-  if (int rc = order_map_reader(h, s, "hsm_score_batch_device", &fs)) return rc;
-  const float factor = (float)(1.0 / pow(2.0, (double)level));
-  const LevelView v = level_view(h->levels[level], factor, 1);
-  const bool exact = wants_exact(h);
-  const int grid = (batch + 3) / 4;
-  with_sampler_form(h, [&](auto lay, auto ex) {
-    hipLaunchKernelGGL((score_batch_kernel<lay(), ex()>), dim3(grid), dim3(256), 0, s, v, d_poses_world, batch,
-                       reinterpret_cast<const float2*>(d_pts_xy), d_scan_offsets, d_scan_offsets ? 0 : shared_n,
-                       d_out_likelihood, d_out_residual);
-  });
-  HIP_TRY(hipGetLastError());
-  if (fs) fs->pending = true;
-  h->last_kernel = "score_batch_kernel";
-  h->last_parity = exact ? HSM_PARITY_EXACT : (h->relaxed ? HSM_PARITY_RELAXED : HSM_PARITY_FAST);
-  return HSM_OK;
-}
-
-int hsm_score_batch_device(hsm_ctx* h, int level, int batch, const float* d_poses_world, const float* d_pts_xy,
-                           const int* d_scan_offsets, int shared_n, float* d_out_likelihood, float* d_out_residual,
-                           void* stream) {
-  if (!h) return fail(HSM_ERR_INVALID, "null context");
-  std::lock_guard<std::mutex> lk(h->mu);
-  return score_batch_device_nolock(h, level, batch, d_poses_world, d_pts_xy, d_scan_offsets, shared_n, d_out_likelihood,
-                                   d_out_residual, stream);
-}
-
-// Groups of at most this many entries (or, with CSR groups whose sizes only the device knows, launches of at least this many
-// groups) take one wavefront per group, the others one workgroup per group.  Either shape gives the same result.
-constexpr int kSelectWaveGroupMax = 1024;
-
-// reads no map: stream order is all it needs
-static int select_best_device_nolock(hsm_ctx* h, int groups, const int* d_group_offsets, int group_size, const float* d_scores,
-                                     const float* d_poses_world, int* d_out_index, float* d_out_score,
-                                     float* d_out_pose_world, void* stream) {
-  if (groups < 0 || (!d_group_offsets && group_size < 0) || !d_out_index || (d_out_pose_world && !d_poses_world) ||
-      (!d_scores && groups > 0 && (d_group_offsets || group_size > 0)) ||
-      (!d_group_offsets && groups > 0 && (long long)groups * group_size > INT_MAX))
-    return fail(HSM_ERR_INVALID, "hsm_select_best_device: bad argument");
-  if (groups == 0) return HSM_OK;
-  if (int rc = select_device(h)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  const bool wave_per_group = d_group_offsets ? groups >= kSelectWaveGroupMax : group_size <= kSelectWaveGroupMax;
-  if (wave_per_group)
-    hipLaunchKernelGGL((select_best_kernel<true>), dim3((groups + 3) / 4), dim3(256), 0, s, groups, d_group_offsets, group_size,
-                       d_scores, d_poses_world, d_out_index, d_out_score, d_out_pose_world);
-  else
-    hipLaunchKernelGGL((select_best_kernel<false>), dim3(groups), dim3(256), 0, s, groups, d_group_offsets, group_size,
-                       d_scores, d_poses_world, d_out_index, d_out_score, d_out_pose_world);
-  HIP_TRY(hipGetLastError());
-  return HSM_OK;
-}
-
-int hsm_select_best_device(hsm_ctx* h, int groups, const int* d_group_offsets, int group_size, const float* d_scores,
-                           const float* d_poses_world, int* d_out_index, float* d_out_score, float* d_out_pose_world,
-                           void* stream) {
-  if (!h) return fail(HSM_ERR_INVALID, "null context");
-  std::lock_guard<std::mutex> lk(h->mu);
-  return select_best_device_nolock(h, groups, d_group_offsets, group_size, d_scores, d_poses_world, d_out_index, d_out_score,
-                                   d_out_pose_world, stream);
-}
-
-// match -> score at the matched poses -> (groups > 0) the winner of every group, queued on `stream` under one lock.  Every
-// argument is checked before the first launch, so a bad one queues nothing.
-static int match_score_batch_device_nolock(hsm_ctx* h, int batch, const float* d_begin_world, const float* d_pts_xy,
-                                           const int* d_scan_offsets, int shared_n, float* d_out_pose, float* d_out_cov,
-                                           int score_level, float* d_out_likelihood, float* d_out_residual, int groups,
-                                           const int* d_group_offsets, int group_size, int* d_out_index, float* d_out_score,
-                                           float* d_out_best_pose, void* stream, int n_bound = 0) {
-  if (int rc = valid_level(h, score_level)) return rc;
-  if (batch < 0 || !d_begin_world || !d_out_pose || (!d_scan_offsets && shared_n < 0) || (!d_out_likelihood && !d_out_residual) ||
-      (batch > 0 && !d_pts_xy && !d_scan_offsets && shared_n > 0) || groups < 0 ||
-      (groups > 0 && (!d_out_likelihood || !d_out_index || (!d_group_offsets && (group_size < 0 || (long long)groups * group_size > batch)))))
-    return fail(HSM_ERR_INVALID, "hsm_match_score_batch_device: bad argument");
-  if (int rc = match_batch_device_nolock(h, batch, d_begin_world, d_pts_xy, d_scan_offsets, shared_n, d_out_pose, d_out_cov, stream, n_bound))
-    return rc;
-  // the sizing hint of a CSR match means nothing to the score: its kernel reads every scan's length from the offsets
-  if (int rc = score_batch_device_nolock(h, score_level, batch, d_out_pose, d_pts_xy, d_scan_offsets, d_scan_offsets ? 0 : shared_n,
-                                         d_out_likelihood, d_out_residual, stream))
-    return rc;
-  if (groups == 0) return HSM_OK;
-  return select_best_device_nolock(h, groups, d_group_offsets, group_size, d_out_likelihood, d_out_pose, d_out_index, d_out_score,
-                                   d_out_best_pose, stream);
-}
-
-}  // extern "C"
-
-int hsm_host::match_score_batch_chain_nolock(hsm_ctx* h, int batch, const float* d_begin_world, const float* d_pts_xy, int shared_n,
-                                             float* d_out_pose, float* d_out_cov, int score_level, float* d_out_likelihood,
-                                             int groups, int group_size, int* d_out_index, float* d_out_score,
-                                             float* d_out_best_pose, void* stream) {
-  return match_score_batch_device_nolock(h, batch, d_begin_world, d_pts_xy, nullptr, shared_n, d_out_pose, d_out_cov, score_level,
-                                         d_out_likelihood, nullptr, groups, nullptr, group_size, d_out_index, d_out_score,
-                                         d_out_best_pose, stream);
-}
-
-extern "C" {
-
-int hsm_match_score_batch_device(hsm_ctx* h, int batch, const float* d_begin_world, const float* d_pts_xy,
-                                 const int* d_scan_offsets, int shared_n, float* d_out_pose, float* d_out_cov, int score_level,
-                                 float* d_out_likelihood, float* d_out_residual, int groups, const int* d_group_offsets,
-                                 int group_size, int* d_out_index, float* d_out_score, float* d_out_best_pose, void* stream) {
-  if (!h) return fail(HSM_ERR_INVALID, "null context");
-  std::lock_guard<std::mutex> lk(h->mu);
-  return match_score_batch_device_nolock(h, batch, d_begin_world, d_pts_xy, d_scan_offsets, shared_n, d_out_pose, d_out_cov,
-                                         score_level, d_out_likelihood, d_out_residual, groups, d_group_offsets, group_size,
-                                         d_out_index, d_out_score, d_out_best_pose, stream);
-}
-
-// what hsm_match_score_batch asks for on top of hsm_match_batch (host pointers)
-struct BatchScoreReq {
-  int level;
-  float* out_lh;
-  float* out_res;  // may be null
-  int groups;      // 0: no ranking
-  const int* group_offsets;
-  int group_size;
-  int* out_index;
-  float* out_score;      // may be null
-  float* out_best_pose;  // may be null; in/out (a group without a winner keeps the caller's values)
-};
-
-// hsm_match_batch, and with `sr` hsm_match_score_batch: host arrays in, one device call on the context's stream, results out
-static int match_batch_host(hsm_ctx* h, int batch, const float* begin_world, const float* pts_xy, const int* scan_offsets,
-                            int shared_n, float* out_pose, float* out_cov, const BatchScoreReq* sr, const char* who) {
-  if (!h) return fail(HSM_ERR_INVALID, "null context");
-  if (batch < 0 || !begin_world || !out_pose) return fail(HSM_ERR_INVALID, who);
-  const int G = sr ? sr->groups : 0;
-  if (sr) {
-    if (int rc = valid_level(h, sr->level)) return rc;
-    if (!sr->out_lh || G < 0 || (G > 0 && (!sr->out_index || (!sr->group_offsets && (sr->group_size < 0 || (long long)G * sr->group_size > batch)))))
-      return fail(HSM_ERR_INVALID, who);
-    if (G > 0 && sr->group_offsets)
-      for (int g = 0; g < G; ++g)
-        if (sr->group_offsets[g] < 0 || sr->group_offsets[g] > sr->group_offsets[g + 1] || sr->group_offsets[g + 1] > batch)
-          return fail(HSM_ERR_INVALID, who);
-  }
-  if (batch == 0) return HSM_OK;
-  const size_t total = scan_offsets ? (size_t)scan_offsets[batch] : (size_t)(shared_n > 0 ? shared_n : 0);
-  if (total > 0 && !pts_xy) return fail(HSM_ERR_INVALID, who);
-  BatchBytes b = {};  // (stage_layout.h: the match's own arrays, and behind them the score's and the ranking's)
-  b.begin = (size_t)batch * 3 * sizeof(float);
-  b.pts = total * 2 * sizeof(float);
-  b.offs = scan_offsets ? ((size_t)batch + 1) * sizeof(int) : 0;
-  b.cov = (size_t)batch * 9 * sizeof(float);
-  b.lh = sr ? (size_t)batch * sizeof(float) : 0, b.res = sr && sr->out_res ? b.lh : 0;
-  b.goffs = G > 0 && sr->group_offsets ? ((size_t)G + 1) * sizeof(int) : 0;
-  b.idx = (size_t)G * sizeof(int), b.bscore = G > 0 && sr->out_score ? (size_t)G * sizeof(float) : 0;
-  b.bpose = G > 0 && sr->out_best_pose ? (size_t)G * 3 * sizeof(float) : 0;
-  const BatchLayout L = batch_layout(b, !scan_offsets);
-  // the launches behind the copies in: x = the device address of the block
-  auto launch = [&](char* x, const float* d_pts, const int* d_offs, int n_or_hint, int n_bound) {
-    float* d_pose = (float*)(x + L.pose);
-    float* d_cov = out_cov ? (float*)(x + L.cov) : nullptr;
-    if (!sr) return match_batch_device_nolock(h, batch, (const float*)x, d_pts, d_offs, n_or_hint, d_pose, d_cov, h->stream, n_bound);
-    return match_score_batch_device_nolock(h, batch, (const float*)x, d_pts, d_offs, n_or_hint, d_pose, d_cov, sr->level,
-                                           (float*)(x + L.lh), b.res ? (float*)(x + L.res) : nullptr, G,
-                                           b.goffs ? (const int*)(x + L.goffs) : nullptr, sr->group_size, (int*)(x + L.idx),
-                                           b.bscore ? (float*)(x + L.bscore) : nullptr,
-                                           b.bpose ? (float*)(x + L.bpose) : nullptr, h->stream, n_bound);
-  };
-  std::lock_guard<std::mutex> lk(h->mu);
-  if (int rc = select_device(h)) return rc;
-  if (!scan_offsets) {
-    // Pose hypotheses of ONE scan (a particle filter's weighting step: BASELINE configs[2]): 12 bytes in and 12 (+36) bytes out
-    // per hypothesis.  The start poses and the results live in pinned, device-mapped host memory -- every wavefront reads its
-    // start pose once and writes its result once, so they cross PCIe exactly once without a copy command in front of or behind the
-    // launch -- and only the scan (which every wavefront reads) is copied to the device.  4096 hypotheses of a 1081-beam scan:
-    // one 8.6 KB copy + the launch, against three copies, the launch and two more copies of the general path below.
-    // (With a score behind the match, its wavefront reads the matched pose back once and writes 4 or 8 bytes; the ranking reads
-    // every likelihood once.)
-    if (!h->h_hyp_pinned.holds(L.total)) HIP_TRY(hipStreamSynchronize(h->stream));
-    if (int rc = h->h_hyp_pinned.reserve(L.total, kHalfMore)) return rc;
-    char* hp = h->h_hyp_pinned;
-    memcpy(hp, begin_world, b.begin);
-    if (out_cov) memcpy(hp + L.cov, out_cov, b.cov);  // in/out: an empty scan leaves the caller's matrices untouched (ScanMatcher.h:68,189)
-    if (b.pts) memcpy(hp + L.pts, pts_xy, b.pts);
-    if (b.goffs) memcpy(hp + L.goffs, sr->group_offsets, b.goffs);
-    if (b.bpose) memcpy(hp + L.bpose, sr->out_best_pose, b.bpose);
-    char* dp = nullptr;
-    HIP_TRY(hipHostGetDevicePointer((void**)&dp, hp, 0));
-    if (int rc = h->d_scan.reserve(total, kScanGrowth)) return rc;
-    if (b.pts) HIP_TRY(hipMemcpyAsync(h->d_scan, hp + L.pts, b.pts, hipMemcpyHostToDevice, h->stream));
-    if (int rc = launch(dp, (const float*)h->d_scan.p, nullptr, shared_n > 0 ? shared_n : 0, 0)) return rc;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    memcpy(out_pose, hp + L.pose, b.begin);
-    if (out_cov) memcpy(out_cov, hp + L.cov, b.cov);
-    if (sr) {
-      memcpy(sr->out_lh, hp + L.lh, b.lh);
-      if (b.res) memcpy(sr->out_res, hp + L.res, b.res);
-      if (b.idx) memcpy(sr->out_index, hp + L.idx, b.idx);
-      if (b.bscore) memcpy(sr->out_score, hp + L.bscore, b.bscore);
-      if (b.bpose) memcpy(sr->out_best_pose, hp + L.bpose, b.bpose);
-    }
-    return HSM_OK;
-  }
-  if (int rc = h->d_batch.reserve(L.total)) return rc;
-  char* base = h->d_batch;
-  const float* d_pts = (const float*)(base + L.pts);
-  const int* d_offs = (const int*)(base + L.offs);  // (scan_offsets is not null here)
-  HIP_TRY(hipMemcpyAsync(base, begin_world, b.begin, hipMemcpyHostToDevice, h->stream));
-  if (b.pts) HIP_TRY(hipMemcpyAsync(base + L.pts, pts_xy, b.pts, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(base + L.offs, scan_offsets, b.offs, hipMemcpyHostToDevice, h->stream));
-  if (out_cov) HIP_TRY(hipMemcpyAsync(base + L.cov, out_cov, b.cov, hipMemcpyHostToDevice, h->stream));  // in/out
-  if (b.goffs) HIP_TRY(hipMemcpyAsync(base + L.goffs, sr->group_offsets, b.goffs, hipMemcpyHostToDevice, h->stream));
-  if (b.bpose) HIP_TRY(hipMemcpyAsync(base + L.bpose, sr->out_best_pose, b.bpose, hipMemcpyHostToDevice, h->stream));  // in/out
-  int hint = 0;
-  for (int i = 0; i < batch; ++i) {
-    const int ni = scan_offsets[i + 1] - scan_offsets[i];
-    if (ni > hint) hint = ni;
-  }
-  if (int rc = launch(base, d_pts, d_offs, hint, hint)) return rc;
-  HIP_TRY(hipMemcpyAsync(out_pose, base + L.pose, b.begin, hipMemcpyDeviceToHost, h->stream));
-  if (out_cov) HIP_TRY(hipMemcpyAsync(out_cov, base + L.cov, b.cov, hipMemcpyDeviceToHost, h->stream));
-  if (sr) {
-    HIP_TRY(hipMemcpyAsync(sr->out_lh, base + L.lh, b.lh, hipMemcpyDeviceToHost, h->stream));
-    if (b.res) HIP_TRY(hipMemcpyAsync(sr->out_res, base + L.res, b.res, hipMemcpyDeviceToHost, h->stream));
-    if (b.idx) HIP_TRY(hipMemcpyAsync(sr->out_index, base + L.idx, b.idx, hipMemcpyDeviceToHost, h->stream));
-    if (b.bscore) HIP_TRY(hipMemcpyAsync(sr->out_score, base + L.bscore, b.bscore, hipMemcpyDeviceToHost, h->stream));
-    if (b.bpose) HIP_TRY(hipMemcpyAsync(sr->out_best_pose, base + L.bpose, b.bpose, hipMemcpyDeviceToHost, h->stream));
-  }
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  return HSM_OK;
-}
-
-int hsm_match_batch(hsm_ctx* h, int batch, const float* begin_world, const float* pts_xy,
-                    const int* scan_offsets, int shared_n, float* out_pose, float* out_cov) {
-  return match_batch_host(h, batch, begin_world, pts_xy, scan_offsets, shared_n, out_pose, out_cov, nullptr,
-                          "hsm_match_batch: bad argument");
-}
-
-int hsm_match_score_batch(hsm_ctx* h, int batch, const float* begin_world, const float* pts_xy, const int* scan_offsets,
-                          int shared_n, float* out_pose, float* out_cov, int score_level, float* out_likelihood,
-                          float* out_residual, int groups, const int* group_offsets, int group_size, int* out_index,
-                          float* out_score, float* out_best_pose) {
-  const BatchScoreReq sr = {score_level, out_likelihood, out_residual, groups, group_offsets, group_size, out_index, out_score,
-                            out_best_pose};
-  return match_batch_host(h, batch, begin_world, pts_xy, scan_offsets, shared_n, out_pose, out_cov, &sr,
-                          "hsm_match_score_batch: bad argument");
-}
-
-// One scan on the levels selected in P.  `pts` is a device-accessible pointer (device memory or pinned
-// mapped host memory), level-0 units.  Latency path of the ROS node: ONE kernel launch and one stream
-// synchronise -- the start estimate travels in the kernel arguments and the kernel writes pose, H and
-// the optional hook trace straight into the pinned h_small block.
-// Completion of a single-scan match.  The kernel's last act is a system-scope release store of `seq` into
-// the pinned result block, AFTER pose / cov / trace: polling that word returns the results a few
-// microseconds before the end-of-kernel signal would (the queue's completion interrupt path is most of
-// what hipStreamSynchronize waits for on a 25 us kernel).  Bounded: after 2 ms without the word the normal
-// stream synchronisation takes over, which also surfaces a faulted kernel.  Later work on the stream
-// stays ordered behind the kernel as usual.
-static int wait_single_scan(hsm_ctx* h, unsigned seq) {
-  if (h->spin_wait) {
-    volatile unsigned* flag = reinterpret_cast<volatile unsigned*>(h->h_small + kDoneFlagOff);
-    const auto t0 = std::chrono::steady_clock::now();
-    for (unsigned it = 1;; ++it) {
-      if (*flag == seq) {
-        std::atomic_thread_fence(std::memory_order_acquire);
-        return HSM_OK;
-      }
-      __builtin_ia32_pause();
-      if ((it & 0xfff) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
-    }
-  }
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  return HSM_OK;
-}
-
-static int match_single(hsm_ctx* h, MatchParams& P, const float begin_world[3], const float2* pts, int n,
-                        float out_pose_world[3], float cov[9], float* trace = nullptr, int trace_steps = 0) {
-  float* hs = h->h_small;
-  float* hs_dev = nullptr;
-  HIP_TRY(hipHostGetDevicePointer((void**)&hs_dev, hs, 0));
-  P.batch = 1;
-  P.begin_world = nullptr;
-  P.begin_inline[0] = begin_world[0];
-  P.begin_inline[1] = begin_world[1];
-  P.begin_inline[2] = begin_world[2];
-  P.pts = pts;
-  P.offsets = nullptr;
-  P.shared_n = n;
-  P.n_bound = n;
-  P.out_pose = hs_dev + 3;
-  P.out_cov = hs_dev + 6;
-  P.trace = trace_steps > 0 ? hs_dev + kTraceOff : nullptr;
-  const unsigned seq = ++h->done_seq;
-  P.done_flag = h->spin_wait ? reinterpret_cast<unsigned*>(hs_dev + kDoneFlagOff) : nullptr;
-  P.done_seq = seq;
-  P.err_flag = reinterpret_cast<unsigned*>(hs_dev + kErrFlagOff);
-  P.coop_mute_block = h->coop_mute_block;
-  P.clock_probe = h->clock_probe;
-  // which form: the site the scan was staged for (stage_scan), now with the trace
-  MatchSite site = single_scan_site(h, n, trace_steps > 0);
-  site.coop_skip = false;
-  MatchPlan plan = plan_match(site);
-  if (plan.family == Family::kCoop && h->coop_skip > 0) {  // backing off after an exchange timeout: this match goes straight to the one-workgroup form
-    --h->coop_skip;
-    site.coop_skip = true;
-    plan = plan_match(site);
-  }
-  const bool coop_tried = plan.family == Family::kCoop;
-  if (coop_tried) {
-    // one dense scan spread over K workgroups of one launch (match_plan.h has the measurements)
-    const int K = plan.grid;
-    float* partials = h->d_partials;
-    unsigned* bar_counter = reinterpret_cast<unsigned*>(h->d_partials + 2 * 64 * 12);
-    unsigned bar_base = h->coop_bar_base;
-    void* args[] = {(void*)&P, (void*)&partials, (void*)&bar_counter, (void*)&bar_base};
-    const void* fn = h->layout == kLayoutPlane ? (const void*)gn_match_coop_kernel<kLayoutPlane, false>
-                                                : (const void*)gn_match_coop_kernel<kLayoutQuad, false>;
-    // The tagged-record exchange (default) has no grid barrier: a workgroup that is not resident yet only delays the others'
-    // polls, which are bounded (a record that never arrives turns into an error return, err_flag) -- so it is an ORDINARY
-    // launch: K <= 64 workgroups of 256 lanes are co-resident on an idle 256-CU device, and on a busy one they become so as
-    // soon as other kernels retire.  (Round 3 launched it through hipLaunchCooperativeKernel: that goes through the
-    // device's cooperative queue -- a slower launch, and a process that has used it segfaults in the runtime's exit
-    // handlers when it runs under rocprofv3, profiles/r04/README.md.)  The counter-barrier form (HSM_COOP_TAGGED=0) spins
-    // without a bound and keeps the cooperative launch's co-residency guarantee.
-    hipError_t le;
-    if (h->coop_tagged) {
-      if (h->layout == kLayoutPlane)
-        hipLaunchKernelGGL((gn_match_coop_kernel<kLayoutPlane, true>), dim3(K), dim3(256), 0, h->stream, P, partials, bar_counter, bar_base);
-      else
-        hipLaunchKernelGGL((gn_match_coop_kernel<kLayoutQuad, true>), dim3(K), dim3(256), 0, h->stream, P, partials, bar_counter, bar_base);
-      le = hipGetLastError();
-    } else {
-      le = hipLaunchCooperativeKernel(fn, dim3(K), dim3(256), args, 0, h->stream);
-    }
-    if (le == hipSuccess) {
-      unsigned steps = 0;
-      for (int l = P.first_level; l >= P.last_level; --l) steps += (unsigned)P.lv[l].gn_steps;
-      h->coop_bar_base += (unsigned)K * steps;  // one arrival per workgroup per GN step
-      record_launch(h, plan);
-    } else {
-      // the runtime could not guarantee co-residency (device busy with other work): the one-workgroup
-      // matcher computes the same thing on one CU
-      (void)hipGetLastError();
-      if (int rc = launch_match(h, P, n, h->stream)) return rc;
-    }
-  } else if (int rc = launch_match(h, P, n, h->stream)) {  // (plans the same site again, with the cooperative form ruled out)
-    return rc;
-  }
-  if (int rc = wait_single_scan(h, seq)) return rc;
-  h->queued_update = false;  // the match kernel was the last thing on `stream`, and it has completed
-  if (*reinterpret_cast<volatile unsigned*>(hs + kErrFlagOff) == seq) {
-    // The multi-workgroup matcher's tagged exchange gave up waiting for a record: its K workgroups were not co-resident for
-    // ~2^22 polls (a device shared with another process, or a long kernel of another stream holding the CUs -- an ordinary
-    // launch carries no co-residency guarantee).  No pose was written.  The scan is matched again by the one-workgroup
-    // matcher, which needs no other workgroup to make progress -- same sums in a different tree, so the caller gets a pose
-    // within the fast mode's bar instead of an error (round-4 advisor); hsm_last_launch_config() then reports that form.
-    const unsigned seq2 = ++h->done_seq;
-    P.done_seq = seq2;
-    if (int rc = launch_match(h, P, n, h->stream)) return rc;
-    if (int rc = wait_single_scan(h, seq2)) return rc;
-    ++h->coop_fallbacks;
-    h->coop_backoff = h->coop_backoff ? (h->coop_backoff < 1024 ? 2 * h->coop_backoff : 1024) : 1;
-    h->coop_skip = h->coop_backoff;
-    {
-      char b[200];
-      snprintf(b, sizeof b, "hsm_match: the multi-workgroup matcher's exchange timed out (device shared or busy); re-ran on one workgroup, "
-               "skipping that form for the next %u dense matches", h->coop_skip);
-      g_last_error = b;  // (not an error return: the pose is valid; the text tells who asks why a match took long)
-    }
-    if (*reinterpret_cast<volatile unsigned*>(hs + kErrFlagOff) == seq2)
-      return fail(HSM_ERR_HIP, "hsm_match: exchange timeout flagged by the one-workgroup matcher (cannot happen: it has no exchange)");
-  }
-  else if (coop_tried)
-    h->coop_backoff = 0;  // an exchange completed: the device is ours again
-  for (int i = 0; i < trace_steps * 12; ++i) trace[i] = hs[kTraceOff + i];
-  out_pose_world[0] = hs[3];
-  out_pose_world[1] = hs[4];
-  out_pose_world[2] = hs[5];
-  if (n != 0 && cov)
-    for (int i = 0; i < 9; ++i) cov[i] = hs[6 + i];
-  return HSM_OK;
-}
-
-// stage a host scan where the matcher can read it: pinned mapped host memory when the form planned for it reads it once
-// (MatchPlan::reads_scan_once: no H2D copy command in front of the kernel), device memory otherwise
-static int stage_scan(hsm_ctx* h, const float* pts_xy, int n, Buf<float2>& d_buf, const float2** out) {
-  if (plan_match(single_scan_site(h, n)).reads_scan_once) {
-    if (int rc = h->h_scan_pinned.reserve(n > 0 ? n : 1, kScanGrowth)) return rc;  // (1: also the empty first scan of a fresh context)
-    if (n > 0) memcpy(h->h_scan_pinned, pts_xy, (size_t)n * sizeof(float2));
-    float2* dev = nullptr;
-    HIP_TRY(hipHostGetDevicePointer((void**)&dev, h->h_scan_pinned, 0));
-    *out = dev;
-    return HSM_OK;
-  }
-  if (int rc = d_buf.reserve((size_t)n, kScanGrowth)) return rc;
-  if (n > 0) HIP_TRY(hipMemcpyAsync(d_buf, pts_xy, (size_t)n * sizeof(float2), hipMemcpyHostToDevice, h->stream));
-  *out = d_buf;
-  return HSM_OK;
-}
-
-// The retained scan of matchData when it has to live in device memory (dense scans, exact order): uploaded on the copy
-// stream into the buffer the update kernels of the scan BEFORE are not reading, so that the copy runs while those kernels
-// still occupy `stream` (in a match + update loop the upload of scan t + 1 used to wait behind the update of scan t: ~10 us of
-// every configs[4] step).  Safe with two buffers: the kernels that read buffer A (match t, update t) are all ordered before
-// match t + 1 on `stream`, and hsm_match returns only when match t + 1 has completed -- so when the upload of scan t + 2 is
-// issued into A nothing reads it any more.  The staging block is pinned (a pageable hipMemcpyAsync would block the host
-// until everything queued on its stream has completed) and free again for the same reason.
-static int stage_scan_overlapped(hsm_ctx* h, const float* pts_xy, int n, const float2** out) {
-  if (!h->copy_stream) {
-    HIP_TRY(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreateWithFlags(&h->copy_evt, hipEventDisableTiming));
-  }
-  std::swap(h->d_retained, h->d_retained_alt);
-  if (int rc = h->d_retained.reserve((size_t)n, kScanGrowth)) return rc;
-  if (!h->h_copy_pinned.holds((size_t)n)) HIP_TRY(hipStreamSynchronize(h->copy_stream));
-  if (int rc = h->h_copy_pinned.reserve((size_t)n, kHalfMore)) return rc;
-  memcpy(h->h_copy_pinned, pts_xy, (size_t)n * sizeof(float2));
-  HIP_TRY(hipMemcpyAsync(h->d_retained, h->h_copy_pinned, (size_t)n * sizeof(float2), hipMemcpyHostToDevice, h->copy_stream));
-  HIP_TRY(hipEventRecord(h->copy_evt, h->copy_stream));
-  HIP_TRY(hipStreamWaitEvent(h->stream, h->copy_evt, 0));
-  *out = h->d_retained;
-  return HSM_OK;
-}
-
-// the containers of matchData: DataContainer::setFrom keeps scaled copies for the coarse levels (MapRepMultiMap.h:127);
-// here: one level-0 copy, scaled by 2^-level on use
-static void retain_scan(hsm_ctx* h, const float* pts_xy, int n, const float origo[2]) {
-  if (h->levels.size() <= 1) return;
-  h->retained_pts.assign(pts_xy, pts_xy + 2 * (size_t)n);
-  h->retained_origo[0] = origo ? origo[0] : 0.0f;
-  h->retained_origo[1] = origo ? origo[1] : 0.0f;
-  h->retained_valid = true;
-}
-
-static int match_impl(hsm_ctx* h, const float begin_world[3], const float* pts_xy, int n, const float origo[2],
-                      float out_pose_world[3], float cov[9], float* trace, int trace_steps,
-                      const float2* d_prestaged = nullptr);
-
-int hsm_match(hsm_ctx* h, const float begin_world[3], const float* pts_xy, int n, const float origo[2],
-              float out_pose_world[3], float cov[9]) {
-  return match_impl(h, begin_world, pts_xy, n, origo, out_pose_world, cov, nullptr, 0);
-}
-
-int hsm_match_trace(hsm_ctx* h, const float begin_world[3], const float* pts_xy, int n, const float origo[2],
-                    float out_pose_world[3], float cov[9], float* trace, int trace_cap_steps, int* steps_written) {
-  if (!h) return fail(HSM_ERR_INVALID, "null context");
-  const int steps = hsm_gn_iterations_per_match(h);
-  if (!trace || !steps_written || trace_cap_steps < steps)
-    return fail(HSM_ERR_INVALID, "hsm_match_trace: trace buffer smaller than hsm_gn_iterations_per_match()");
-  *steps_written = n > 0 ? steps : 0;
-  return match_impl(h, begin_world, pts_xy, n, origo, out_pose_world, cov, trace, n > 0 ? steps : 0);
-}
-
-static int match_impl(hsm_ctx* h, const float begin_world[3], const float* pts_xy, int n, const float origo[2],
-                      float out_pose_world[3], float cov[9], float* trace, int trace_steps,
-                      const float2* d_prestaged) {
-  if (!h) return fail(HSM_ERR_INVALID, "null context");
-  if (!begin_world || !out_pose_world || n < 0 || (n > 0 && !pts_xy))
-    return fail(HSM_ERR_INVALID, "hsm_match: bad argument");
-  std::lock_guard<std::mutex> lk(h->mu);
-  if (int rc = select_device(h)) return rc;
-  retain_scan(h, pts_xy, n, origo);
-  const float2* pts = d_prestaged;
-  if (!pts) {
-    // (the same rule as stage_scan's: scans the matcher reads once stay in pinned host memory)
-    const bool to_device = !plan_match(single_scan_site(h, n)).reads_scan_once;
-    // ... and only behind an update that was queued and not waited for (the match + update loop): on an idle stream the
-    // extra hop through the copy stream's event costs ~10 us of latency and hides nothing (asking the runtime with
-    // hipStreamQuery costs half of what the overlap gains: 0.1855 against 0.179 ms per configs[4] step)
-    if (to_device && h->overlap_upload && n > 0 && h->queued_update) {
-      if (int rc = stage_scan_overlapped(h, pts_xy, n, &pts)) return rc;
-    } else if (int rc = stage_scan(h, pts_xy, n, h->d_retained, &pts)) {
-      return rc;
-    }
-  }
-  // the device copy of the retained scan is (re)uploaded lazily by the next update when the
-  // matcher read the scan from pinned host memory
-  h->d_retained_current = h->levels.size() > 1 && pts == h->d_retained;
-  MatchParams P;
-  memset(&P, 0, sizeof P);
-  fill_schedule(h, P);
-  return match_single(h, P, begin_world, pts, n, out_pose_world, cov, trace, trace_steps);
-}
-
-int hsm_match_level(hsm_ctx* h, int level, const float begin_world[3], const float* pts_level_xy, int n,
-                    int max_iterations, float out_pose_world[3], float cov[9]) {
-  if (int rc = valid_level(h, level)) return rc;
-  if (!begin_world || !out_pose_world || n < 0 || max_iterations < 0 || (n > 0 && !pts_level_xy))
-    return fail(HSM_ERR_INVALID, "hsm_match_level: bad argument");
-  std::lock_guard<std::mutex> lk(h->mu);
-  if (int rc = select_device(h)) return rc;
-  const float2* pts = nullptr;
-  if (int rc = stage_scan(h, pts_level_xy, n, h->d_scan, &pts)) return rc;
-  MatchParams P;
-  memset(&P, 0, sizeof P);
-  P.lv[level] = level_view(h->levels[level], 1.0f, 1 + max_iterations);
-  P.first_level = level;
-  P.last_level = level;
-  return match_single(h, P, begin_world, pts, n, out_pose_world, cov);
-}
-
 int hsm_synchronize(hsm_ctx* h) {
   if (!h) return fail(HSM_ERR_INVALID, "null context");
   std::lock_guard<std::mutex> lk(h->mu);
@@ -1334,22 +614,4 @@ int hsm_synchronize(hsm_ctx* h) {
   return HSM_OK;
 }
 
-int hsm_match_ingested(hsm_ctx* h, const float begin_world[3], float out_pose_world[3], float cov[9]) {
-  if (!h) return fail(HSM_ERR_INVALID, "null context");
-  if (h->ingest_n < 0) return fail(HSM_ERR_INVALID, "hsm_match_ingested: no scan ingested");
-  static const float dummy[2] = {0.0f, 0.0f};
-  const float* hp = h->ingest_n > 0 ? h->h_ingest.data() : dummy;
-  return match_impl(h, begin_world, hp, h->ingest_n, h->ingest_origo, out_pose_world, cov, nullptr, 0, h->d_ingest);
-}
-
-int hsm_retain_scan(hsm_ctx* h, const float* pts_xy, int n, const float origo[2]) {
-  if (!h) return fail(HSM_ERR_INVALID, "null context");
-  if (n < 0 || (n > 0 && !pts_xy)) return fail(HSM_ERR_INVALID, "hsm_retain_scan: bad argument");
-  std::lock_guard<std::mutex> lk(h->mu);
-  retain_scan(h, pts_xy, n, origo);
-  h->d_retained_current = false;  // (never true on a one-level map)
-  return HSM_OK;
-}
-
 }  // extern "C"
-

@@ -1,7 +1,11 @@
 // hsm_ctx.h -- the context of libhector_mi355.so as its translation units see it: the pyramid level, hsm_ctx, and the launch
 // entry points the units implement for each other.  Internal (not installed): the public boundary is include/hector_mi355/capi.h.
-//   hector_mi355.hip        the core: the context's life cycle, the stream hand-over around map updates, every match entry and
-//                           the one-workgroup-per-scan matcher forms (gn_match_dense.h, gn_match_spec.h, score_kernels.h)
+//   hector_mi355.hip        the core: the context's life cycle and settings, the error text, the views of a level and the stream
+//                           hand-over around map updates: host code only, no kernel in its include closure
+//   match.hip               the matcher's front door: every match, score and select entry, the plan of a launch and its record,
+//                           the single-scan path, and the one-workgroup-per-scan and multi-workgroup matcher forms
+//                           (gn_match_dense.h, gn_match_spec.h, score_kernels.h); the other forms it dispatches to the two
+//                           match_* units below
 //   map_update.hip          every writer of the map by scans: the update entries, the movement gate, the device SLAM scan loop and
 //                           the level maintenance the other units reach through this header (map_update.h, update_gate.h)
 //   ingest.hip              raw sensor data: the LaserScan / point-cloud conversions of one scan and of batches, in front of
@@ -443,7 +447,7 @@ struct ScanLog {
 };
 
 // hector_mi355.hip, for the other units: the views of a level, the launch arithmetic, and the hand-over between a caller's stream
-// and the context's around queued map updates (the definitions carry the comments)
+// and the context's around queued map updates (the definitions carry the comments).  level_factor and stream_capturing are inline above
 int valid_level(const hsm_ctx* h, int level);
 int select_device(const hsm_ctx* h);
 bool wants_exact(const hsm_ctx* h);
@@ -454,16 +458,17 @@ void whole_level_changed(Level& L, bool mirror = true);
 void set_level_transformation(Level& L, float offx, float offy, float cell_length);
 int order_after_foreign_match(hsm_ctx* h);
 int order_map_reader(hsm_ctx* h, hipStream_t s, const char* who, hsm_ctx::ForeignStream** mark);
-int match_batch_device_nolock(hsm_ctx* h, int batch, const float* d_begin_world, const float* d_pts_xy, const int* d_scan_offsets,
-                              int shared_n, float* d_out_pose, float* d_out_cov, void* stream, int n_bound = 0,
-                              const ExchangeFused* xp = nullptr);
-// the chain behind hsm_match_score_batch_device (match -> score -> winners), for hsm_relocalize_device of window.hip
-int match_score_batch_chain_nolock(hsm_ctx* h, int batch, const float* d_begin_world, const float* d_pts_xy, int shared_n,
-                                   float* d_out_pose, float* d_out_cov, int score_level, float* d_out_likelihood, int groups,
-                                   int group_size, int* d_out_index, float* d_out_score, float* d_out_best_pose, void* stream);
 int slam_refuse_capture(hsm_ctx* h, hipStream_t s, const char* who);
 int wait_for_caller_inputs(hsm_ctx* h, hipStream_t s);
 int slam_caller_waits(hsm_ctx* h, hipStream_t s);
+// match.hip, for the other units: the batched match behind the raw-scan, group and scan-loop entries ...
+int match_batch_device_nolock(hsm_ctx* h, int batch, const float* d_begin_world, const float* d_pts_xy, const int* d_scan_offsets,
+                              int shared_n, float* d_out_pose, float* d_out_cov, void* stream, int n_bound = 0,
+                              const ExchangeFused* xp = nullptr);
+// ... and the chain behind hsm_match_score_batch_device (match -> score -> winners), for hsm_relocalize_device of window.hip
+int match_score_batch_chain_nolock(hsm_ctx* h, int batch, const float* d_begin_world, const float* d_pts_xy, int shared_n,
+                                   float* d_out_pose, float* d_out_cov, int score_level, float* d_out_likelihood, int groups,
+                                   int group_size, int* d_out_index, float* d_out_score, float* d_out_best_pose, void* stream);
 // map_update.hip, for the other units: the level maintenance that launches map_update.h's kernels, what an entry does before it
 // reads or rewrites a level's boxes and counters on the host, and the device SLAM loop over a scan log
 int create_update_state(hsm_ctx* h);
@@ -488,7 +493,7 @@ void with_sampler_form(const hsm_ctx* h, F&& f) {
   }
 }
 
-// Which form a launch takes is decided once, in match_plan.h (plan_match), by launch_match of hector_mi355.hip, which also
+// Which form a launch takes is decided once, in match_plan.h (plan_match), by launch_match of match.hip, which also
 // keeps the launch record; the other two units only map a plan to their instantiations and launch it.
 // match_exact_cached.hip: reference order, batches, one wavefront per scan with the texel cache (Family::kExactCached, kExactCachedCw)
 int launch_exact_cached_form(hsm_ctx* h, hsm::MatchParams P, const MatchPlan& plan, hipStream_t stream);

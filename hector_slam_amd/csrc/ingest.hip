@@ -1,7 +1,7 @@
 // ingest.hip -- the entries of the C ABI (include/hector_mi355/capi.h) that take RAW sensor data: one LaserScan or point cloud into
 // the context's scan container (hsm_ingest_*), batches of raw scans into the batched matcher (hsm_match_batch_ranges*,
 // hsm_ingest_batch_ranges_tf_device, hsm_match_batch_ranges_tf) and a raw scan log through the whole SLAM loop (hsm_slam_ranges_tf*).
-// The conversion kernels are in ingest_kernels.h; the match behind them stays in the core runtime (hector_mi355.hip), the update
+// The conversion kernels are in ingest_kernels.h; the match behind them is the matcher's front door's (match.hip), the update
 // and the loop in map_update.hip; hsm_ctx.h declares what these entries need of either.  hsm_match_ingested and
 // hsm_update_by_ingested, a match and an update that read the container, are there too.
 #include <hip/hip_runtime.h>

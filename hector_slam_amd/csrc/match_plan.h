@@ -1,6 +1,6 @@
 // match_plan.h -- which form of the matcher a launch takes: ONE decision, made on the host from plain values, before anything
-// is launched.  plan_match(site) holds every rule; the three launch units (hector_mi355.hip, match_teams.hip,
-// match_exact_cached.hip) map the plan to their instantiations, hector_mi355.hip records it (record_launch) and asks it where a
+// is launched.  plan_match(site) holds every rule; the three launch units (match.hip, match_teams.hip,
+// match_exact_cached.hip) map the plan to their instantiations, match.hip records it (record_launch) and asks it where a
 // single scan is staged (reads_scan_once).  Plain C++17, no HIP and no context: tests/cpp/match_plan_check.cpp runs it on the CPU
 // against the table of tests/golden/match_forms.json.  DESIGN.md "which form runs when" is this file in prose.
 #pragma once

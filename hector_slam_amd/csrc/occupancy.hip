@@ -1,7 +1,7 @@
 // occupancy.hip -- the entries of the C ABI (include/hector_mi355/capi.h) that export a level as the node's occupancy grid: the
 // whole level (hsm_occupancy_grid*) or the cells that changed since the level was last exported (hsm_occupancy_changes*,
-// hsm_occupancy_restart).  The kernels are in occupancy_kernels.h; the publish boxes they read are kept by the map updates of the
-// core runtime (hector_mi355.hip), which declares what these entries need of it in hsm_ctx.h.
+// hsm_occupancy_restart).  The kernels are in occupancy_kernels.h; the publish boxes they read are kept by the map updates
+// (map_update.hip); what these entries need of them and of the core runtime (hector_mi355.hip) is declared in hsm_ctx.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>

@@ -1,5 +1,5 @@
 // score_kernels.h -- the weighting and ranking of batches of pose hypotheses (score_batch_kernel, select_best_kernel), launched
-// by hector_mi355.hip only.  Sampler: beam_sample.h; the residual chain and the (score, index) order: gn_step.h.
+// by match.hip only.  Sampler: beam_sample.h; the residual chain and the (score, index) order: gn_step.h.
 #pragma once
 #include <hip/hip_runtime.h>
 

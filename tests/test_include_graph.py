@@ -18,18 +18,18 @@ CSRC = os.path.join(ROOT, "hector_slam_amd", "csrc")
 OWNERS = {
     "gn_match_teams.h": {"match_teams.hip"},
     "gn_match_cached.h": {"match_teams.hip"},
-    "gn_match_dense.h": {"hector_mi355.hip"},
-    "score_kernels.h": {"hector_mi355.hip"},
+    "gn_match_dense.h": {"match.hip"},
+    "score_kernels.h": {"match.hip"},
     "probe_kernels.h": {"probes.hip"},
     "gn_match_exact.h": {"match_exact_cached.hip"},
-    "gn_match_spec.h": {"hector_mi355.hip"},
+    "gn_match_spec.h": {"match.hip"},
 }
 # the kernel-free headers of the matcher: what the table says of them, as sets of units as well
-TWELVE = set(build.UNITS) - {"pose_exchange.hip"}
+ALL_BUT_EXCHANGE = set(build.UNITS) - {"pose_exchange.hip"}
 SHARED = {
     "texel_cache.h": {"match_teams.hip", "match_exact_cached.hip"},
-    "gn_step.h": {"match_teams.hip", "match_exact_cached.hip", "hector_mi355.hip", "window.hip", "probes.hip"},
-    "match_types.h": TWELVE,
+    "gn_step.h": {"match_teams.hip", "match_exact_cached.hip", "match.hip", "window.hip", "probes.hip"},
+    "match_types.h": ALL_BUT_EXCHANGE,
     "pose_exchange.h": set(build.UNITS),
 }
 
@@ -46,9 +46,9 @@ def _closure_of(name):
     return build._closure(os.path.join(CSRC, name), [])
 
 
-def test_thirteen_units_in_link_order():
-    assert list(build.UNITS) == ["hector_mi355.hip", "map_update.hip", "ingest.hip", "occupancy.hip", "probes.hip", "rays.hip",
-                                 "map_copy.hip", "map_shift.hip", "window.hip", "group.hip", "match_exact_cached.hip",
+def test_fourteen_units_in_link_order():
+    assert list(build.UNITS) == ["hector_mi355.hip", "match.hip", "map_update.hip", "ingest.hip", "occupancy.hip", "probes.hip",
+                                 "rays.hip", "map_copy.hip", "map_shift.hip", "window.hip", "group.hip", "match_exact_cached.hip",
                                  "match_teams.hip", "pose_exchange.hip"]
     for unit, deps in build.UNITS.items():
         assert deps[0] == os.path.join(CSRC, unit) and all(os.path.isabs(d) and os.path.isfile(d) for d in deps), unit
@@ -99,6 +99,18 @@ def test_exact_cached_unit_is_not_rebuilt_by_the_fast_kernels():
     deps = _names(build.UNITS["match_exact_cached.hip"])
     assert not deps & {"gn_match_cached.h", "gn_match_teams.h"}
     assert not _names(_closure_of("gn_match_exact.h")) & {"gn_match_cached.h", "gn_match_teams.h"}
+
+
+def test_core_unit_launches_no_kernel():
+    for path in _closure_of("hector_mi355.hip"):
+        assert "__global__" not in open(path).read(), path
+    core = open(os.path.join(CSRC, "hector_mi355.hip")).read()
+    assert "hipLaunchKernelGGL" not in core and "hipLaunchCooperativeKernel" not in core
+
+
+def test_matcher_front_door_does_not_see_the_kernels_it_dispatches_to():
+    deps = _names(build.UNITS["match.hip"])
+    assert not deps & {"map_update.h", "gn_match_exact.h", "gn_match_teams.h", "gn_match_cached.h"}
 
 
 def _compiler_deps(hipcc, unit):

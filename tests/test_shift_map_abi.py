@@ -38,7 +38,7 @@ def test_new_symbols_declared_bound_and_exported():
         assert callable(getattr(capi.MapRepMultiMap, method)), method
     unit = build.UNITS["map_shift.hip"]
     assert any(d.endswith("map_shift_kernels.h") for d in unit) and any(d.endswith("map_shift_plan.h") for d in unit)
-    assert len(build.UNITS) == 13
+    assert len(build.UNITS) == 14
 
 
 def test_header_with_the_new_entries_is_plain_c99(tmp_path):
