@@ -150,7 +150,7 @@ int grid_for(size_t n, int block) {
 // reference's BITS by whatever form delivers them, EXACT names the reference's order of additions.
 // The effective order is an INPUT of the plan (MatchSite::exact) -- the context's flags are never changed by a launch
 // (hsm_parity() reads them without the mutex) -- and is recorded for hsm_last_launch_parity().
-bool wants_exact(const hsm_ctx* h) { return h->exact || h->auto_parity; }
+bool wants_exact(const hsm_ctx* h) { return h->cfg.parity.exact || h->cfg.parity.auto_parity; }
 
 // every cell of the level may have changed (create, reset, upload): host mirrors and the published grid take all of it
 void whole_level_changed(Level& L, bool mirror) {
@@ -200,34 +200,34 @@ void set_level_transformation(Level& L, float offx, float offy, float cell_lengt
 int order_after_foreign_match(hsm_ctx* h) {
   // Refused, before anything is queued, while a caller's stream that this context has matched on is being captured into a graph:
   // a marker recorded on that stream would go into the capture, and the context's stream, waiting for it, would join the capture.
-  for (const hsm_ctx::ForeignStream& f : h->foreign)
+  for (const hsm_ctx::ForeignStream& f : h->order.foreign)
     if (stream_capturing(f.s))
       return fail(HSM_ERR_INVALID, "map update while a caller's stream that this context matches on is being captured into a graph: "
                                    "end the capture first (the caller orders replays against updates)");
-  for (hsm_ctx::ForeignStream& f : h->foreign) {
+  for (hsm_ctx::ForeignStream& f : h->order.foreign) {
     if (!f.pending) continue;
     // everything the caller has queued on that stream up to now (a superset of our matches); the wait captures
     // the event's state at this call, so one event serves all streams in turn
-    if (!h->evt_foreign) HIP_TRY(hipEventCreateWithFlags(&h->evt_foreign, hipEventDisableTiming));
-    if (hipEventRecord(h->evt_foreign, f.s) == hipSuccess) {
-      HIP_TRY(hipStreamWaitEvent(h->stream, h->evt_foreign, 0));
+    if (!h->order.evt_foreign) HIP_TRY(hipEventCreateWithFlags(&h->order.evt_foreign, hipEventDisableTiming));
+    if (hipEventRecord(h->order.evt_foreign, f.s) == hipSuccess) {
+      HIP_TRY(hipStreamWaitEvent(h->stream, h->order.evt_foreign, 0));
     } else {  // the caller destroyed the stream meanwhile: its work has been flushed or is covered by a device sync
       (void)hipGetLastError();
       HIP_TRY(hipDeviceSynchronize());
     }
     f.pending = false;
   }
-  if (h->foreign.size() > 16) h->foreign.clear();  // nothing pending any more: forget streams callers may have destroyed
-  ++h->upd_epoch;
+  if (h->order.foreign.size() > 16) h->order.foreign.clear();  // nothing pending any more: forget streams callers may have destroyed
+  ++h->order.upd_epoch;
   return HSM_OK;
 }
 
 // the context's stream behind the caller's: the inputs are complete where `s` stands now
 int wait_for_caller_inputs(hsm_ctx* h, hipStream_t s) {
   if (s == h->stream) return HSM_OK;
-  if (!h->evt_inputs) HIP_TRY(hipEventCreateWithFlags(&h->evt_inputs, hipEventDisableTiming));
-  HIP_TRY(hipEventRecord(h->evt_inputs, s));
-  HIP_TRY(hipStreamWaitEvent(h->stream, h->evt_inputs, 0));
+  if (!h->order.evt_inputs) HIP_TRY(hipEventCreateWithFlags(&h->order.evt_inputs, hipEventDisableTiming));
+  HIP_TRY(hipEventRecord(h->order.evt_inputs, s));
+  HIP_TRY(hipStreamWaitEvent(h->stream, h->order.evt_inputs, 0));
   return HSM_OK;
 }
 
@@ -235,7 +235,7 @@ int wait_for_caller_inputs(hsm_ctx* h, hipStream_t s) {
 int slam_refuse_capture(hsm_ctx* h, hipStream_t s, const char* who) {
   if (stream_capturing(s))
     return fail_at(HSM_ERR_INVALID, who, ": `stream` is being captured into a graph (map updates are not captured)");
-  for (const hsm_ctx::ForeignStream& f : h->foreign)  // (order_after_foreign_match)
+  for (const hsm_ctx::ForeignStream& f : h->order.foreign)  // (order_after_foreign_match)
     if (stream_capturing(f.s))
       return fail_at(HSM_ERR_INVALID, who, ": a caller's stream that this context matches on is being captured into a graph");
   return HSM_OK;
@@ -244,9 +244,9 @@ int slam_refuse_capture(hsm_ctx* h, hipStream_t s, const char* who) {
 // the caller's stream behind the context's (the results are complete where the context's stream stands now)
 int slam_caller_waits(hsm_ctx* h, hipStream_t s) {
   if (s == h->stream) return HSM_OK;
-  if (!h->evt_slam_done) HIP_TRY(hipEventCreateWithFlags(&h->evt_slam_done, hipEventDisableTiming));
-  HIP_TRY(hipEventRecord(h->evt_slam_done, h->stream));
-  HIP_TRY(hipStreamWaitEvent(s, h->evt_slam_done, 0));
+  if (!h->order.evt_slam_done) HIP_TRY(hipEventCreateWithFlags(&h->order.evt_slam_done, hipEventDisableTiming));
+  HIP_TRY(hipEventRecord(h->order.evt_slam_done, h->stream));
+  HIP_TRY(hipStreamWaitEvent(s, h->order.evt_slam_done, 0));
   return HSM_OK;
 }
 
@@ -263,11 +263,11 @@ int hsm_host::order_map_reader(hsm_ctx* h, hipStream_t s, const char* who, hsm_c
   // (hsm_update_by_scan returns before they ran): order the launch behind the updates queued so far, and
   // leave a marker the next update waits for, so that it does not rewrite the map under a running reader.
   hsm_ctx::ForeignStream* fs = nullptr;
-  for (hsm_ctx::ForeignStream& f : h->foreign)
+  for (hsm_ctx::ForeignStream& f : h->order.foreign)
     if (f.s == s) fs = &f;
   if (!fs) {
-    h->foreign.push_back({s, 0ull, false});
-    fs = &h->foreign.back();
+    h->order.foreign.push_back({s, 0ull, false});
+    fs = &h->order.foreign.back();
   }
   if (stream_capturing(s)) {
     // A launch into a graph capture runs at the caller's replays, not now: it neither records that the stream is ordered behind
@@ -283,11 +283,11 @@ int hsm_host::order_map_reader(hsm_ctx* h, hipStream_t s, const char* who, hsm_c
     return HSM_OK;
   }
   // (what test_queued_updates_are_ordered_against_caller_streams holds)
-  if (fs->ordered_epoch != h->upd_epoch) {  // THIS stream has not been ordered behind the latest map writes yet
-    if (!h->evt_updates) HIP_TRY(hipEventCreateWithFlags(&h->evt_updates, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(h->evt_updates, h->stream));
-    HIP_TRY(hipStreamWaitEvent(s, h->evt_updates, 0));
-    fs->ordered_epoch = h->upd_epoch;
+  if (fs->ordered_epoch != h->order.upd_epoch) {  // THIS stream has not been ordered behind the latest map writes yet
+    if (!h->order.evt_updates) HIP_TRY(hipEventCreateWithFlags(&h->order.evt_updates, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(h->order.evt_updates, h->stream));
+    HIP_TRY(hipStreamWaitEvent(s, h->order.evt_updates, 0));
+    fs->ordered_epoch = h->order.upd_epoch;
   }
   // no marker here (an event record between back-to-back launches costs 2-3 us of kernel time each): the
   // next writer of the map records one on every stream with a pending reader (order_after_foreign_match)
@@ -329,70 +329,11 @@ int hsm_create(float map_resolution, int size_x, int size_y, unsigned levels, fl
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) == hipSuccess && cus > 0) h->compute_units = cus;
   }
-  int layout = opts ? opts->layout : HSM_LAYOUT_AUTO;
-  if (layout == HSM_LAYOUT_AUTO) {
-    const char* env = getenv("HSM_LAYOUT");
-    layout = (env && strcmp(env, "plane") == 0) ? HSM_LAYOUT_PLANE : HSM_LAYOUT_QUAD;
-  }
-  h->layout = layout == HSM_LAYOUT_PLANE ? kLayoutPlane : kLayoutQuad;
-  int wps = opts ? opts->waves_per_scan : 0;
-  if (wps == 0) {
-    const char* env = getenv("HSM_WPS");
-    if (env) wps = atoi(env);
-  }
-  if (wps != 0 && wps != 1 && wps != 2 && wps != 4 && wps != 8 && wps != 16) {
+  const char* refusal = "";
+  if (int rc = parse_settings(opts, [](const char* name) -> const char* { return getenv(name); }, &h->cfg, &refusal)) {  // (settings.h)
     delete h;
-    return fail(HSM_ERR_INVALID, "hsm_create: waves_per_scan must be 0,1,2,4,8,16");
+    return fail(rc, refusal);
   }
-  h->wps_override = wps;
-  if (const char* env = getenv("HSM_BPL")) h->bpl_override = atoi(env) == 0 ? 0 : -1;
-  if (const char* env = getenv("HSM_COOP_MIN")) h->coop_min_beams = atoi(env);
-  if (const char* env = getenv("HSM_COOP_TAGGED")) h->coop_tagged = atoi(env) != 0;
-  if (const char* env = getenv("HSM_SPIN_WAIT")) h->spin_wait = atoi(env) != 0;
-  if (const char* env = getenv("HSM_ASYNC_UPDATE")) h->async_update = atoi(env) != 0;
-  if (const char* env = getenv("HSM_OVERLAP_UPLOAD")) h->overlap_upload = atoi(env) != 0;
-  if (const char* env = getenv("HSM_TEXEL_CACHE")) h->texel_cache = atoi(env) != 0;
-  if (const char* env = getenv("HSM_UPDATE_ZEROCOPY_MAX")) h->update_zero_copy_max = atoi(env);
-  if (const char* env = getenv("HSM_PARITY")) {
-    // only the four documented words change the mode; anything else ("Exact", "1", a typo) must not silently select the
-    // fast tree: the context is refused
-    const bool is_exact = strcmp(env, "exact") == 0, is_relaxed = strcmp(env, "relaxed") == 0, is_auto = strcmp(env, "auto") == 0;
-    if (!is_exact && !is_relaxed && !is_auto && strcmp(env, "fast") != 0) {
-      delete h;
-      return fail(HSM_ERR_INVALID, "hsm_create: HSM_PARITY must be one of auto, fast, exact, relaxed");
-    }
-    h->exact = is_exact;
-    h->relaxed = is_relaxed;
-    h->auto_parity = is_auto;
-  }
-  if (const char* env = getenv("HSM_BATCH_ORDER")) {
-    if (strcmp(env, "auto") == 0) h->batch_order = HSM_ORDER_AUTO;
-    else if (strcmp(env, "given") == 0) h->batch_order = HSM_ORDER_GIVEN;
-    else if (strcmp(env, "morton") == 0) h->batch_order = HSM_ORDER_MORTON;
-    else {
-      delete h;
-      return fail(HSM_ERR_INVALID, "hsm_create: HSM_BATCH_ORDER must be one of auto, given, morton");
-    }
-  }
-  if (const char* env = getenv("HSM_BATCH_ORDER_MIN")) h->batch_order_min = atoi(env);
-  if (const char* env = getenv("HSM_BATCH_ORDER_REFRESH")) h->batch_order_refresh = atoi(env) > 0 ? atoi(env) : 1;
-  if (const char* env = getenv("HSM_MERGED_MARK_MAX")) h->merged_mark_max = atoi(env);
-  if (const char* env = getenv("HSM_SCATTER_TEXELS_MAX")) h->scatter_texels_max = atoi(env);
-  if (const char* env = getenv("HSM_DENSE_BITS")) h->dense_bits = atoi(env) != 0;
-  if (const char* env = getenv("HSM_EXACT_CACHED")) h->exact_cached = atoi(env) != 0;
-  if (const char* env = getenv("HSM_EXACT_DENSE")) h->exact_dense = atoi(env) != 0;
-  if (const char* env = getenv("HSM_EXACT_SPEC")) h->exact_spec = atoi(env) != 0;
-  if (const char* env = getenv("HSM_EXACT_SPEC1")) h->exact_spec1 = atoi(env) != 0;
-  if (const char* env = getenv("HSM_EXACT_DENSE_MIN")) h->exact_dense_min = atoi(env);
-  if (const char* env = getenv("HSM_EXACT_CHAIN_WAVE")) h->exact_chain_wave = atoi(env);
-  if (const char* env = getenv("HSM_EXACT_SPLIT_TAIL")) h->exact_split_tail = atoi(env);
-  if (const char* env = getenv("HSM_WG_SYNC")) h->wg_sync = atoi(env) != 0;
-  if (const char* env = getenv("HSM_SPB_LARGE")) h->spb_large = atoi(env) == 8 ? 8 : 4;
-  if (const char* env = getenv("HSM_XCD_CHUNK")) h->xcd_chunk = atoi(env) > 0 ? atoi(env) : 0;
-  if (const char* env = getenv("HSM_CAST_FORM")) h->cast_form = !strcmp(env, "wave") ? 0 : (!strcmp(env, "lane") ? 1 : -1);
-  if (const char* env = getenv("HSM_WINDOW_FORM")) h->window_form = !strcmp(env, "wave") ? 0 : (!strcmp(env, "lane") ? 1 : -1);
-  if (const char* env = getenv("HSM_XCD_CHUNK_EXACT")) h->xcd_chunk_exact = atoi(env) > 0 ? atoi(env) : 0;
-  if (const char* env = getenv("HSM_COPY_STAGE")) h->copy_stage = atoi(env) != 0;
 
 #define CREATE_TRY(expr)                                   \
   do {                                                     \
@@ -406,12 +347,12 @@ int hsm_create(float map_resolution, int size_x, int size_y, unsigned levels, fl
 
   CREATE_TRY(hipSetDevice(h->device));
   CREATE_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-  CREATE_TRY(hipMalloc((void**)&h->d_small, kSmallFloats * sizeof(float)));
-  CREATE_TRY(hipMalloc((void**)&h->d_partials, 2 * 64 * 12 * sizeof(float) + 64));  // [2][64] records of 3 x {p,p,p,tag}; + the grid-barrier counter
-  CREATE_TRY(hipMemset(h->d_partials, 0, 2 * 64 * 12 * sizeof(float) + 64));
-  CREATE_TRY(hipHostMalloc((void**)&h->h_small, kSmallFloats * sizeof(float),
+  CREATE_TRY(hipMalloc((void**)&h->single.d_small, kSmallFloats * sizeof(float)));
+  CREATE_TRY(hipMalloc((void**)&h->single.d_partials, 2 * 64 * 12 * sizeof(float) + 64));  // [2][64] records of 3 x {p,p,p,tag}; + the grid-barrier counter
+  CREATE_TRY(hipMemset(h->single.d_partials, 0, 2 * 64 * 12 * sizeof(float) + 64));
+  CREATE_TRY(hipHostMalloc((void**)&h->single.h_small, kSmallFloats * sizeof(float),
                            hipHostMallocMapped | hipHostMallocCoherent));
-  memset(h->h_small, 0, kSmallFloats * sizeof(float));
+  memset(h->single.h_small, 0, kSmallFloats * sizeof(float));
   if (create_update_state(h) != HSM_OK) {  // (the gate's block and the publish boxes: map_update.hip)
     hsm_destroy(h);
     return HSM_ERR_HIP;
@@ -442,7 +383,7 @@ int hsm_create(float map_resolution, int size_x, int size_y, unsigned levels, fl
     // (beam_sample.h sample_fetch): one extra texel, resp. sizeX + 2 extra cells, zeroed once here
     CREATE_TRY(hipMalloc((void**)&L.d_prob, (n + (size_t)rx + 2) * sizeof(float)));
     CREATE_TRY(hipMemsetAsync(L.d_prob + n, 0, ((size_t)rx + 2) * sizeof(float), h->stream));
-    if (h->layout == kLayoutQuad) {
+    if (h->cfg.layout == kLayoutQuad) {
       // HSM_LAYOUT_PLANE samples the probability plane directly (4 gathers per beam) and keeps NO texel plane:
       // 16 B/cell less memory and one dense pass less per update -- the better trade for update-heavy use
       // (single dense scans); the quad layout is the better one for batched matching
@@ -462,7 +403,7 @@ int hsm_create(float map_resolution, int size_x, int size_y, unsigned levels, fl
       return HSM_ERR_HIP;
     }
     whole_level_changed(L, false);  // the first export of a level is all of it (a mirror starts from the same cleared map: not dirty)
-    CREATE_TRY(hipMemcpyAsync(h->d_pub_boxes + (2 * kMaxLevels + i) * 4, L.pub, sizeof L.pub, hipMemcpyHostToDevice, h->stream));
+    CREATE_TRY(hipMemcpyAsync(h->occ.d_pub_boxes + (2 * kMaxLevels + i) * 4, L.pub, sizeof L.pub, hipMemcpyHostToDevice, h->stream));
     rx /= 2;
     ry /= 2;
     map_resolution *= 2.0f;
@@ -478,23 +419,23 @@ void hsm_destroy(hsm_ctx* h) {
   TeardownLog log_, *log = &log_;
   TEARDOWN(log, hipSetDevice(h->device));
   if (h->stream) TEARDOWN(log, hipStreamSynchronize(h->stream));
-  if (h->copy_stream) TEARDOWN(log, hipStreamSynchronize(h->copy_stream));
+  if (h->single.copy_stream) TEARDOWN(log, hipStreamSynchronize(h->single.copy_stream));
   for (Level& L : h->levels) free_level(L, log);
   for (GrowBuf* b : h->bufs) b->release(log);  // every grow-on-demand block of the context (hsm_ctx.h)
-  for (hsm_ctx::SpecScratch& b : h->spec_scratch) b.d.release(log);
-  for (hsm_ctx::PermBuf& b : h->perm_bufs) b.d.release(log);
-  for (hsm_ctx::RangesGeometry& g : h->ranges_geoms) TEARDOWN(log, hipFree(g.d));
-  for (hsm_ctx::RangesTfGeometry& g : h->ranges_tf_geoms) TEARDOWN(log, hipFree(g.d));
-  TEARDOWN(log, hipFree(h->d_spec_stats));
-  TEARDOWN(log, hipFree(h->d_small));
-  TEARDOWN(log, hipFree(h->d_partials));
-  TEARDOWN(log, hipFree(h->d_gate));
-  TEARDOWN(log, hipFree(h->d_pub_boxes));
-  if (h->h_small) TEARDOWN(log, hipHostFree(h->h_small));
-  for (hipEvent_t e : {h->copy_evt, h->evt_updates, h->evt_foreign, h->evt_inputs, h->evt_slam_done, h->upd_evt[0], h->upd_evt[1],
-                       h->evt_copy_read, h->evt_copy_src})
+  for (hsm_ctx::SpecScratch& b : h->batch.spec_scratch) b.d.release(log);
+  for (hsm_ctx::PermBuf& b : h->batch.perm_bufs) b.d.release(log);
+  for (hsm_ctx::RangesGeometry& g : h->ingest.ranges_geoms) TEARDOWN(log, hipFree(g.d));
+  for (hsm_ctx::RangesTfGeometry& g : h->ingest.ranges_tf_geoms) TEARDOWN(log, hipFree(g.d));
+  TEARDOWN(log, hipFree(h->batch.d_spec_stats));
+  TEARDOWN(log, hipFree(h->single.d_small));
+  TEARDOWN(log, hipFree(h->single.d_partials));
+  TEARDOWN(log, hipFree(h->upd.d_gate));
+  TEARDOWN(log, hipFree(h->occ.d_pub_boxes));
+  if (h->single.h_small) TEARDOWN(log, hipHostFree(h->single.h_small));
+  for (hipEvent_t e : {h->single.copy_evt, h->order.evt_updates, h->order.evt_foreign, h->order.evt_inputs, h->order.evt_slam_done, h->upd.upd_evt[0], h->upd.upd_evt[1],
+                       h->copy.evt_copy_read, h->copy.evt_copy_src})
     if (e) TEARDOWN(log, hipEventDestroy(e));
-  if (h->copy_stream) TEARDOWN(log, hipStreamDestroy(h->copy_stream));
+  if (h->single.copy_stream) TEARDOWN(log, hipStreamDestroy(h->single.copy_stream));
   if (h->stream) TEARDOWN(log, hipStreamDestroy(h->stream));
   delete h;
   if (!log_.first.empty()) {
@@ -507,9 +448,9 @@ int hsm_reset(hsm_ctx* h) {
   if (!h) return fail(HSM_ERR_INVALID, "null context");
   std::lock_guard<std::mutex> lk(h->mu);
   if (int rc = select_device(h)) return rc;
-  if (h->upd_boxes_outstanding)
+  if (h->upd.upd_boxes_outstanding)
     if (int rc = merge_device_boxes(h)) return rc;
-  if (h->gate_outstanding)
+  if (h->upd.gate_outstanding)
     if (int rc = fold_gate_counters(h)) return rc;
   if (int rc = order_after_foreign_match(h)) return rc;
   if (int rc = reset_update_gate(h)) return rc;
@@ -544,41 +485,41 @@ int hsm_set_parity(hsm_ctx* h, int mode) {
   if (mode != HSM_PARITY_FAST && mode != HSM_PARITY_EXACT && mode != HSM_PARITY_RELAXED && mode != HSM_PARITY_AUTO)
     return fail(HSM_ERR_INVALID, "hsm_set_parity: unknown mode");
   std::lock_guard<std::mutex> lk(h->mu);
-  h->exact = mode == HSM_PARITY_EXACT;
-  h->relaxed = mode == HSM_PARITY_RELAXED;
-  h->auto_parity = mode == HSM_PARITY_AUTO;
+  h->cfg.parity.exact = mode == HSM_PARITY_EXACT;
+  h->cfg.parity.relaxed = mode == HSM_PARITY_RELAXED;
+  h->cfg.parity.auto_parity = mode == HSM_PARITY_AUTO;
   return HSM_OK;
 }
 int hsm_parity(const hsm_ctx* h) {
   if (!h) return HSM_PARITY_FAST;
-  return h->exact ? HSM_PARITY_EXACT : (h->relaxed ? HSM_PARITY_RELAXED : (h->auto_parity ? HSM_PARITY_AUTO : HSM_PARITY_FAST));
+  return h->cfg.parity.exact ? HSM_PARITY_EXACT : (h->cfg.parity.relaxed ? HSM_PARITY_RELAXED : (h->cfg.parity.auto_parity ? HSM_PARITY_AUTO : HSM_PARITY_FAST));
 }
 
-int hsm_last_launch_parity(const hsm_ctx* h) { return h ? h->last_parity : HSM_PARITY_FAST; }
+int hsm_last_launch_parity(const hsm_ctx* h) { return h ? h->last.last_parity : HSM_PARITY_FAST; }
 
 int hsm_set_batch_order(hsm_ctx* h, int order) {
   if (!h) return fail(HSM_ERR_INVALID, "null context");
   if (order != HSM_ORDER_GIVEN && order != HSM_ORDER_MORTON && order != HSM_ORDER_AUTO) return fail(HSM_ERR_INVALID, "hsm_set_batch_order: unknown order");
   std::lock_guard<std::mutex> lk(h->mu);
-  h->batch_order = order;
-  for (hsm_ctx::PermBuf& b : h->perm_bufs) b.batch = 0;
+  h->cfg.batch.batch_order = order;
+  for (hsm_ctx::PermBuf& b : h->batch.perm_bufs) b.batch = 0;
   return HSM_OK;
 }
 int hsm_set_batch_order_refresh(hsm_ctx* h, int launches) {
   if (!h) return fail(HSM_ERR_INVALID, "null context");
   if (launches < 1) return fail(HSM_ERR_INVALID, "hsm_set_batch_order_refresh: at least 1");
   std::lock_guard<std::mutex> lk(h->mu);
-  h->batch_order_refresh = launches;
-  for (hsm_ctx::PermBuf& b : h->perm_bufs) b.batch = 0;  // (the next launch computes a fresh one)
+  h->cfg.batch.batch_order_refresh = launches;
+  for (hsm_ctx::PermBuf& b : h->batch.perm_bufs) b.batch = 0;  // (the next launch computes a fresh one)
   return HSM_OK;
 }
-int hsm_batch_order(const hsm_ctx* h) { return h ? h->batch_order : HSM_ORDER_AUTO; }
-int hsm_last_launch_sorted(const hsm_ctx* h) { return h && h->last_sorted ? 1 : 0; }
+int hsm_batch_order(const hsm_ctx* h) { return h ? h->cfg.batch.batch_order : HSM_ORDER_AUTO; }
+int hsm_last_launch_sorted(const hsm_ctx* h) { return h && h->last.last_sorted ? 1 : 0; }
 
 int hsm_set_clock_probe(hsm_ctx* h, unsigned long long* d_stamps4) {
   if (!h) return fail(HSM_ERR_INVALID, "null context");
   std::lock_guard<std::mutex> lk(h->mu);
-  h->clock_probe = d_stamps4;
+  h->batch.clock_probe = d_stamps4;
   return HSM_OK;
 }
 
@@ -596,11 +537,11 @@ int hsm_device_info(const hsm_ctx* h, int info[4]) {
 int hsm_gn_iterations_per_match(const hsm_ctx* h) {
   return h ? 6 + 4 * ((int)h->levels.size() - 1) : 0;
 }
-const char* hsm_last_launch_kernel(const hsm_ctx* h) { return h ? h->last_kernel : ""; }
+const char* hsm_last_launch_kernel(const hsm_ctx* h) { return h ? h->last.last_kernel : ""; }
 int hsm_last_launch_config(const hsm_ctx* h, int cfg[5]) {
   if (!h || !cfg) return fail(HSM_ERR_INVALID, "null argument");
-  for (int i = 0; i < 5; ++i) cfg[i] = h->last_cfg[i];
-  if (h->last_cfg[5]) cfg[4] = -cfg[4];  // texel-cache form: endpoints in LDS, not VGPRs
+  for (int i = 0; i < 5; ++i) cfg[i] = h->last.last_cfg[i];
+  if (h->last.last_cfg[5]) cfg[4] = -cfg[4];  // texel-cache form: endpoints in LDS, not VGPRs
   return HSM_OK;
 }
 
@@ -609,8 +550,8 @@ int hsm_synchronize(hsm_ctx* h) {
   std::lock_guard<std::mutex> lk(h->mu);
   if (int rc = select_device(h)) return rc;
   HIP_TRY(hipStreamSynchronize(h->stream));
-  h->upd_busy[0] = h->upd_busy[1] = false;
-  h->queued_update = false;
+  h->upd.upd_busy[0] = h->upd.upd_busy[1] = false;
+  h->upd.queued_update = false;
   return HSM_OK;
 }
 

@@ -1,29 +1,32 @@
 // hsm_ctx.h -- the context of libhector_mi355.so as its translation units see it: the pyramid level, hsm_ctx, and the launch
 // entry points the units implement for each other.  Internal (not installed): the public boundary is include/hector_mi355/capi.h.
+// The units, and behind "=>" the members of hsm_ctx each one owns (tests/test_ctx_ownership.py has who else reaches into them):
 //   hector_mi355.hip        the core: the context's life cycle and settings, the error text, the views of a level and the stream
-//                           hand-over around map updates: host code only, no kernel in its include closure
+//                           hand-over around map updates: host code only, no kernel in its include closure  => cfg, order
 //   match.hip               the matcher's front door: every match, score and select entry, the plan of a launch and its record,
 //                           the single-scan path, and the one-workgroup-per-scan and multi-workgroup matcher forms
 //                           (gn_match_dense.h, gn_match_spec.h, score_kernels.h); the other forms it dispatches to the two
-//                           match_* units below
+//                           match_* units below  => single, batch, last, retained
 //   map_update.hip          every writer of the map by scans: the update entries, the movement gate, the device SLAM scan loop and
-//                           the level maintenance the other units reach through this header (map_update.h, update_gate.h)
+//                           the level maintenance the other units reach through this header (map_update.h, update_gate.h)  => upd
 //   ingest.hip              raw sensor data: the LaserScan / point-cloud conversions of one scan and of batches, in front of
-//                           the match, the update and the SLAM loop (ingest_kernels.h)
-//   occupancy.hip           a level as the node's occupancy grid, whole or its changed cells only (occupancy_kernels.h)
+//                           the match, the update and the SLAM loop (ingest_kernels.h)  => ingest
+//   occupancy.hip           a level as the node's occupancy grid, whole or its changed cells only (occupancy_kernels.h)  => occ
 //   probes.hip              the host-array probes (likelihood, covariance, Hessian), level downloads and uploads,
-//                           the hsm_debug_* test hooks, and the kernels only these launch (probe_kernels.h)
+//                           the hsm_debug_* test hooks, and the kernels only these launch (probe_kernels.h)  => d_cells
 //   rays.hip                what a laser would see on a level: ray distances of arrays of rays (host or device pointers) and
 //                           expected scans cast from batches of poses (ray_kernels.h)
 //   map_copy.hip            a pyramid, or one cell box per level, copied from another context's planes on the device
-//                           (map_copy_kernels.h; the box arithmetic: map_copy_box.h)
+//                           (map_copy_kernels.h; the box arithmetic: map_copy_box.h)  => copy
 //   map_shift.hip           the window moved under the robot: every level's contents shifted by whole cells inside their own
 //                           planes, the geometry re-derived for other start coordinates (map_shift_kernels.h; the plan:
 //                           map_shift_plan.h)
+//   window.hip              a window of poses around a centre scored on the device map, its K best, and the relocalisation chain
+//                           behind them (window_kernels.h; the window's arithmetic: window_grid.h)
 //   group.hip               the multi-GPU group (hsm_group_*, hsm_shard_bounds): host code only, librccl opened on demand
 //   match_exact_cached.hip  the exact-order texel-cache batch forms (gn_match_exact.h: the headline kernel and its chain-wavefront forms)
-//   match_teams.hip         the team forms (gn_match_teams.h: gn_match_kernel, 1..16 wavefronts per scan) and the fast texel-cache
-//                           forms (gn_match_cached.h)
+//   match_teams.hip         the team forms (gn_match_kernel, 1..16 wavefronts per scan: gn_match_teams.h) and the fast texel-cache
+//                           forms (gn_match_cached.h)  => batch's perm_bufs
 //   pose_exchange.hip       the device-side gather of sharded results
 // This header sees the matcher's TYPES only (match_types.h): a kernel header is included by the unit that launches its kernels,
 // the device primitives they share are in beam_sample.h, gn_step.h and texel_cache.h.
@@ -40,6 +43,7 @@
 #include "hsm_host.h"
 #include "match_plan.h"
 #include "match_types.h"
+#include "settings.h"
 #include "stage_layout.h"
 
 namespace hsm {
@@ -215,12 +219,27 @@ using hsm_host::Buf;
 using hsm_host::kBufPinned;
 using hsm_host::kBufPinnedMapped;
 
+// The context.  What every unit may use stands at the top; the rest is grouped into member structs by the unit that owns the state,
+// each under a comment that names it.  Which units reach into which member is pinned by tests/test_ctx_ownership.py: a new
+// cross-unit reach fails there until it is written into that table.  A member with Buf fields starts with the owner list, so that
+// its blocks enrol in hsm_ctx::bufs as they are constructed.
 struct hsm_ctx {
-  std::vector<hsm_host::GrowBuf*> bufs;  // every Buf member below enrols here as it is constructed: hsm_destroy releases these
+  using Bufs = std::vector<hsm_host::GrowBuf*>;
+  // ---- shared by every unit ----------------------------------------------------------------------------------------------------
+  Bufs bufs;  // every Buf member below enrols here as it is constructed: hsm_destroy releases these
   int device = 0;
-  int layout = kLayoutQuad;
-  int wps_override = 0;
-  bool texel_cache = true;          // env HSM_TEXEL_CACHE=0: plain gn_match_kernel for throughput launches too
+  int compute_units = 256;   // of this device (hsm_create)
+  hsm_host::Settings cfg;    // what hsm_opts and the environment set at hsm_create, and the hsm_set_* entries since (settings.h)
+  std::vector<hsm_host::Level> levels;
+  float start[2] = {0.5f, 0.5f};  // the start coordinates the levels' transforms derive from (hsm_create, hsm_shift_map)
+  mutable std::mutex mu;
+  hipStream_t stream = nullptr;
+  // scratch of whichever entry holds the mutex: single-scan staging (device) ...
+  Buf<float2> d_scan{&bufs};
+  // ... and batch staging for the host-pointer convenience entries
+  Buf<char> d_batch{&bufs};
+
+  // ---- hector_mi355.hip (the core) ---------------------------------------------------------------------------------------------
   // ordering between the context's stream (updates) and caller-owned streams (hsm_match_batch_device):
   // per caller stream the update epoch it has been ordered behind, and whether it may still run a match
   struct ForeignStream {
@@ -228,84 +247,116 @@ struct hsm_ctx {
     unsigned long long ordered_epoch;
     bool pending;
   };
-  std::vector<ForeignStream> foreign;
-  unsigned long long upd_epoch = 1;
-  hipEvent_t evt_updates = nullptr, evt_foreign = nullptr;
-  // updateByScan returns when its kernels are QUEUED (env HSM_ASYNC_UPDATE=0: wait for them): everything
-  // that reads the map afterwards is ordered behind them on `stream`.  Host endpoints are staged in one of
-  // two pinned blocks (h_upd_pinned), each guarded by the event of the update that last read it.
-  bool async_update = true;
-  int update_zero_copy_max = 4096;  // env HSM_UPDATE_ZEROCOPY_MAX
-  int merged_mark_max = 4096;       // scans below this take the one-launch mark pass (env HSM_MERGED_MARK_MAX, 0 = never)
-  int scatter_texels_max = 1 << 30; // quad layout: scans below this write the texels from the apply pass (env HSM_SCATTER_TEXELS_MAX, 0 = never)
-  Buf<BeamRec> d_beam_recs{&bufs};  // dense scans: per-beam records of all levels (map_update.h BeamRec), [HSM_MAX_LEVELS][count() / HSM_MAX_LEVELS]
-  // hsm_update_by_scans_device: one UpdateBatch and one cell box per level for every scan of a call, filled on the device
-  // (map_update.h update_prep_kernel); grown outside capture.  boxes: slot 0 the levels' running dirty boxes, slot 1 the last scan's
-  Buf<UpdateBatch> d_upd_batches{&bufs};
-  Buf<int> d_upd_boxes{&bufs};  // allocated last: non-null = both blocks serve d_upd_batches.count() scans
-  bool upd_boxes_outstanding = false;  // device-side updates since the host last merged their boxes into Level::bbox / dirty
-  hipEvent_t evt_inputs = nullptr;     // the caller's stream at hsm_update_by_scans_device: its inputs are complete
-  // the published grid (occupancy_kernels.h occupancy_prep_kernel), three rows of kMaxLevels boxes in a block of their own that no
-  // growing buffer replaces: the levels' publish boxes as device-side updates widen them (never fetched), the box of the export
-  // that was queued last on each level (its convert launch reads it), and the whole level as a box (written by hsm_create)
-  int* d_pub_boxes = nullptr;
-  // the movement gate of HectorSlamProcessor::update (update_gate.h; map_update.h update_gate_prep_kernel): its state and the
-  // count of updates it let through live on the device -- the host never learns a gated call's decisions.  Whoever needs
-  // Level's update counters on the host first waits for the stream and folds that count in (fold_gate_counters), like the boxes
-  hsm::GateState* d_gate = nullptr;
-  float gate_min_dist = 0.4f, gate_min_angle = 0.13f;  // HectorSlamProcessor.h:62-63 (hsm_set_update_gate)
-  bool gate_outstanding = false;       // gated calls since the host last folded their count into the levels' counters
-  long long gate_applied_total = 0;    // updates of gated calls folded so far, since hsm_create
-  hipEvent_t evt_slam_done = nullptr;  // the context's stream at the end of hsm_slam_scans_device: the caller's stream waits for it
-  Buf<char> d_upd_stage{&bufs};        // hsm_update_by_scans: poses, offsets and end points of the host arrays
-  Buf<float2> h_upd_pinned[2] = {Buf<float2>{&bufs, kBufPinnedMapped}, Buf<float2>{&bufs, kBufPinnedMapped}};
-  hipEvent_t upd_evt[2] = {nullptr, nullptr};
-  bool upd_busy[2] = {false, false};
-  int upd_slot = 0;
-  bool spin_wait = true;       // single-scan matches: poll the kernel's completion word (env HSM_SPIN_WAIT=0: off)
-  unsigned done_seq = 0;
-  std::vector<hsm_host::Level> levels;
-  float start[2] = {0.5f, 0.5f};  // the start coordinates the levels' transforms derive from (hsm_create, hsm_shift_map)
-  mutable std::mutex mu;
-  hipStream_t stream = nullptr;
-  // single-scan staging (device) + pinned result
-  Buf<float2> d_scan{&bufs};
-  float* d_small = nullptr;   // layout: top of this header
-  float* h_small = nullptr;   // pinned mirror of d_small
-  // retained scan = MapRepMultiMap::dataContainers (level-0 units; scaled by 2^-l on use)
-  std::vector<float> retained_pts;
-  float retained_origo[2] = {0.f, 0.f};
-  bool retained_valid = false;  // false until the first match (reference: empty containers)
-  Buf<float2> d_retained{&bufs};
-  bool d_retained_current = false;
-  // the upload of a dense scan for matchData runs on its own stream, into the OTHER of two device buffers, from a pinned
-  // staging block: it overlaps the update kernels still queued on `stream` (which read the buffer of the scan before)
-  // instead of waiting behind them; the match kernel waits for the copy's event (stage_scan_overlapped)
-  Buf<float2> d_retained_alt{&bufs};
-  hipStream_t copy_stream = nullptr;
-  hipEvent_t copy_evt = nullptr;
-  Buf<float2> h_copy_pinned{&bufs, kBufPinned};
-  bool overlap_upload = true;  // env HSM_OVERLAP_UPLOAD=0: the copy is queued on `stream` as before
-  bool queued_update = false;  // an asynchronous updateByScan was queued on `stream` since the host last saw it drained
-  // batch staging for the host-pointer convenience entry
-  Buf<char> d_batch{&bufs};
-  // ... and for its shared-scan form (pose hypotheses of ONE scan): start poses, results and the scan in pinned, device-mapped host
-  // memory -- the kernel reads each start pose once and writes each result once, straight over PCIe, no copy command either way
-  Buf<char> h_hyp_pinned{&bufs, kBufPinnedMapped};
-  // single-scan fast path: endpoints staged in pinned, device-mapped host memory and read by the
-  // matcher ONCE (they stay in VGPRs); results written by the kernel straight into h_small
-  Buf<float2> h_scan_pinned{&bufs, kBufPinnedMapped};
-  // ingested scan (hsm_ingest_laser_scan): device container + host copy, sensor trig table cache
-  // (the three blocks hold d_ingest.count() beams; d_ranges: 3 floats per beam and the survivor count behind them)
-  Buf<float> d_ranges{&bufs};
-  Buf<double2> d_trig{&bufs};       // float2 (running-angle table) or double2 (laser_geometry unit vectors)
-  int trig_kind = -1;
-  float ingest_origo[2] = {0.f, 0.f};
-  Buf<float2> d_ingest{&bufs};      // allocated last: non-null = the trio is complete
-  std::vector<float> h_ingest;      // endpoints as the matcher/updater see them (host copy)
-  int ingest_n = -1;                // -1 = nothing ingested yet
-  float trig_a0 = 0.f, trig_inc = 0.f;
-  int trig_n = -1;
+  struct Order {
+    std::vector<ForeignStream> foreign;
+    unsigned long long upd_epoch = 1;
+    hipEvent_t evt_updates = nullptr, evt_foreign = nullptr;
+    hipEvent_t evt_inputs = nullptr;     // the caller's stream at hsm_update_by_scans_device: its inputs are complete
+    hipEvent_t evt_slam_done = nullptr;  // the context's stream at the end of hsm_slam_scans_device: the caller's stream waits for it
+  } order;
+
+  // ---- match.hip: the single-scan path -----------------------------------------------------------------------------------------
+  struct Single {
+    Bufs* bufs;
+    float* d_small = nullptr;   // layout: top of this header
+    float* h_small = nullptr;   // pinned mirror of d_small
+    unsigned done_seq = 0;
+    // single-scan fast path: endpoints staged in pinned, device-mapped host memory and read by the
+    // matcher ONCE (they stay in VGPRs); results written by the kernel straight into h_small
+    Buf<float2> h_scan_pinned{bufs, kBufPinnedMapped};
+    // the upload of a dense scan for matchData runs on its own stream, into the OTHER of two device buffers, from a pinned
+    // staging block: it overlaps the update kernels still queued on `stream` (which read the buffer of the scan before)
+    // instead of waiting behind them; the match kernel waits for the copy's event (stage_scan_overlapped)
+    Buf<float2> d_retained_alt{bufs};
+    hipStream_t copy_stream = nullptr;
+    hipEvent_t copy_evt = nullptr;
+    Buf<float2> h_copy_pinned{bufs, kBufPinned};
+    unsigned coop_bar_base = 0;   // value the grid-barrier counter has when the next cooperative launch starts
+    float* d_partials = nullptr;  // [2][64][9] per-workgroup partial sums of gn_match_coop_kernel
+    int coop_mute_block = 0;      // hsm_debug_set_coop_mute (test hook)
+    unsigned coop_fallbacks = 0;  // dense single-scan matches re-run on one workgroup after an exchange timeout (match_single)
+    // ... and the back-off that follows: after a timeout the multi-workgroup form is skipped for the next coop_skip matches (1, 2, 4, ...
+    // up to 1024, reset by the first exchange that completes) -- on a device another process keeps busy every dense match would
+    // otherwise pay the full bounded wait, a host spin and a second launch (round-5 advisor)
+    unsigned coop_skip = 0, coop_backoff = 0;
+  } single{&bufs};
+
+  // ---- match.hip, match_teams.hip, match_exact_cached.hip: the batched entries --------------------------------------------------
+  // One permutation buffer per stream that has launched a sorted batch (launches on one stream are ordered; a ninth stream keeps the
+  // caller's order)
+  struct PermBuf {
+    hipStream_t s;
+    Buf<int> d;  // (not enrolled: hsm_destroy walks perm_bufs)
+    int batch;  // the batch size the permutation in `d` was computed for (0: none)
+    int used;   // launches it has served
+  };
+  // gn_match_spec_kernel: products of every beam, [batch][stride] float4s -- one block per stream that has launched the form
+  // (launches on one stream are ordered; a ninth stream, and any launch into a graph capture, take the literal dense form)
+  struct SpecScratch {
+    hipStream_t s;
+    Buf<float4> d;  // (not enrolled: hsm_destroy walks spec_scratch)
+  };
+  struct Batch {
+    Bufs* bufs;
+    // the shared-scan form of the host-pointer entry (pose hypotheses of ONE scan): start poses, results and the scan in pinned, device-mapped host
+    // memory -- the kernel reads each start pose once and writes each result once, straight over PCIe, no copy command either way
+    Buf<char> h_hyp_pinned{bufs, kBufPinnedMapped};
+    std::vector<PermBuf> perm_bufs;
+    std::vector<SpecScratch> spec_scratch;
+    SpecStats* d_spec_stats = nullptr; // hsm_debug_spec_stats
+    unsigned long long* clock_probe = nullptr;  // hsm_set_clock_probe
+    int sched_level = -1;         // hsm_debug_set_schedule (test hook): batched entries run `sched_level` only, -1 = the full schedule
+    int sched_steps = 0;          //   ... with this many GN steps
+    bool fused_exchange_done = false;  // the last launch_match carried MatchParams::xp itself (else the caller launches the exchange step)
+  } batch{&bufs};
+
+  // ---- the launch record: written by whichever unit launches a matcher or scorer (match.hip, match_teams.hip, rays.hip, window.hip) ----
+  struct Last {
+    int last_cfg[6] = {0, 0, 0, 0, 0, 0};  // MatchPlan::record of the last match launch (record_launch)
+    const char* last_kernel = "";  // name of the matcher kernel the last launch used (hsm_last_launch_kernel)
+    int last_parity = HSM_PARITY_FAST;  // the mode the last match launch actually ran in (hsm_last_launch_parity)
+    bool last_sorted = false;
+  } last;
+
+  // ---- the hand-over between matchData (match.hip) and updateByScan (map_update.hip) ---------------------------------------------
+  struct Retained {
+    Bufs* bufs;
+    // retained scan = MapRepMultiMap::dataContainers (level-0 units; scaled by 2^-l on use)
+    std::vector<float> retained_pts;
+    float retained_origo[2] = {0.f, 0.f};
+    bool retained_valid = false;  // false until the first match (reference: empty containers)
+    Buf<float2> d_retained{bufs};
+    bool d_retained_current = false;
+  } retained{&bufs};
+
+  // ---- map_update.hip -----------------------------------------------------------------------------------------------------------
+  struct Update {
+    Bufs* bufs;
+    Buf<BeamRec> d_beam_recs{bufs};  // dense scans: per-beam records of all levels (map_update.h BeamRec), [HSM_MAX_LEVELS][count() / HSM_MAX_LEVELS]
+    // hsm_update_by_scans_device: one UpdateBatch and one cell box per level for every scan of a call, filled on the device
+    // (map_update.h update_prep_kernel); grown outside capture.  boxes: slot 0 the levels' running dirty boxes, slot 1 the last scan's
+    Buf<UpdateBatch> d_upd_batches{bufs};
+    Buf<int> d_upd_boxes{bufs};  // allocated last: non-null = both blocks serve d_upd_batches.count() scans
+    bool upd_boxes_outstanding = false;  // device-side updates since the host last merged their boxes into Level::bbox / dirty
+    // the movement gate of HectorSlamProcessor::update (update_gate.h; map_update.h update_gate_prep_kernel): its state and the
+    // count of updates it let through live on the device -- the host never learns a gated call's decisions.  Whoever needs
+    // Level's update counters on the host first waits for the stream and folds that count in (fold_gate_counters), like the boxes
+    hsm::GateState* d_gate = nullptr;
+    float gate_min_dist = 0.4f, gate_min_angle = 0.13f;  // HectorSlamProcessor.h:62-63 (hsm_set_update_gate)
+    bool gate_outstanding = false;       // gated calls since the host last folded their count into the levels' counters
+    long long gate_applied_total = 0;    // updates of gated calls folded so far, since hsm_create
+    // updateByScan returns when its kernels are QUEUED (Settings::Update::async_update): everything
+    // that reads the map afterwards is ordered behind them on `stream`.  Host endpoints are staged in one of
+    // two pinned blocks (h_upd_pinned), each guarded by the event of the update that last read it.
+    Buf<char> d_upd_stage{bufs};        // hsm_update_by_scans: poses, offsets and end points of the host arrays
+    Buf<float2> h_upd_pinned[2] = {Buf<float2>{bufs, kBufPinnedMapped}, Buf<float2>{bufs, kBufPinnedMapped}};
+    hipEvent_t upd_evt[2] = {nullptr, nullptr};
+    bool upd_busy[2] = {false, false};
+    int upd_slot = 0;
+    bool queued_update = false;  // an asynchronous updateByScan was queued on `stream` since the host last saw it drained
+  } upd{&bufs};
+
+  // ---- ingest.hip ---------------------------------------------------------------------------------------------------------------
   // sensor geometries of hsm_match_batch_ranges*: one immutable float2 table per (n, angle_min bits, angle_increment bits),
   // never rewritten and freed by hsm_destroy only (a queued or captured launch may read it any time before)
   struct RangesGeometry {
@@ -313,83 +364,52 @@ struct hsm_ctx {
     unsigned a0_bits, inc_bits;
     float2* d;
   };
-  std::vector<RangesGeometry> ranges_geoms;
   // the same for hsm_ingest_batch_ranges_tf_device / hsm_match_batch_ranges_tf: laser_geometry's double2 unit vectors
   struct RangesTfGeometry {
     int n;
     unsigned a0_bits, inc_bits;
     double2* d;
   };
-  std::vector<RangesTfGeometry> ranges_tf_geoms;
-  Buf<char> d_rbatch{&bufs};  // hsm_match_batch_ranges: start poses, results, counts and the workspace of its device call
-  Buf<signed char> d_occ{&bufs};    // occupancy export staging
-  unsigned coop_bar_base = 0;   // value the grid-barrier counter has when the next cooperative launch starts
-  float* d_partials = nullptr;  // [2][64][9] per-workgroup partial sums of gn_match_coop_kernel
-  int coop_min_beams = 4096;    // single scans at least this long take the multi-workgroup matcher (env HSM_COOP_MIN)
-  bool coop_tagged = true;      // env HSM_COOP_TAGGED=0: the counter grid barrier instead of the tagged-record exchange
+  struct Ingest {
+    Bufs* bufs;
+    // ingested scan (hsm_ingest_laser_scan): device container + host copy, sensor trig table cache
+    // (the three blocks hold d_ingest.count() beams; d_ranges: 3 floats per beam and the survivor count behind them)
+    Buf<float> d_ranges{bufs};
+    Buf<double2> d_trig{bufs};       // float2 (running-angle table) or double2 (laser_geometry unit vectors)
+    int trig_kind = -1;
+    float ingest_origo[2] = {0.f, 0.f};
+    Buf<float2> d_ingest{bufs};      // allocated last: non-null = the trio is complete
+    std::vector<float> h_ingest;      // endpoints as the matcher/updater see them (host copy)
+    int ingest_n = -1;                // -1 = nothing ingested yet
+    float trig_a0 = 0.f, trig_inc = 0.f;
+    int trig_n = -1;
+    std::vector<RangesGeometry> ranges_geoms;
+    std::vector<RangesTfGeometry> ranges_tf_geoms;
+    Buf<char> d_rbatch{bufs};  // hsm_match_batch_ranges: start poses, results, counts and the workspace of its device call
+  } ingest{&bufs};
+
+  // ---- occupancy.hip ------------------------------------------------------------------------------------------------------------
+  struct Occupancy {
+    Bufs* bufs;
+    Buf<signed char> d_occ{bufs};    // occupancy export staging
+    // the published grid (occupancy_kernels.h occupancy_prep_kernel), three rows of kMaxLevels boxes in a block of their own that no
+    // growing buffer replaces: the levels' publish boxes as device-side updates widen them (never fetched), the box of the export
+    // that was queued last on each level (its convert launch reads it), and the whole level as a box (written by hsm_create)
+    int* d_pub_boxes = nullptr;
+  } occ{&bufs};
+
+  // ---- map_copy.hip, map_shift.hip ----------------------------------------------------------------------------------------------
+  struct Copy {
+    Bufs* bufs;
+    // hsm_copy_map* (map_copy.hip).  As the destination: the staging patch of the cross-device route (4-byte elements, laid out by
+    // map_copy_box.h copy_patch_at), and the event on the own stream behind the last read of the source, which the source's
+    // stream waits for.  As the source: the event on the own stream the destination's stream waits for.
+    Buf<float> d_copy_patch{bufs};
+    hipEvent_t evt_copy_read = nullptr, evt_copy_src = nullptr;
+  } copy{&bufs};
+
+  // ---- probes.hip ---------------------------------------------------------------------------------------------------------------
   Buf<char> d_cells{&bufs};  // interleaved {logodds, updateIndex} staging for hsm_download_cells
-  // hsm_copy_map* (map_copy.hip).  As the destination: the staging patch of the cross-device route (4-byte elements, laid out by
-  // map_copy_box.h copy_patch_at), and the event on the own stream behind the last read of the source, which the source's
-  // stream waits for.  As the source: the event on the own stream the destination's stream waits for.
-  Buf<float> d_copy_patch{&bufs};
-  hipEvent_t evt_copy_read = nullptr, evt_copy_src = nullptr;
-  bool copy_stage = false;   // env HSM_COPY_STAGE=1: copies INTO this context take the staged route from the same device too
-  int bpl_override = -1;  // 0 = force the memory loop (env HSM_BPL=0), -1 = auto
-  int xcd_chunk_exact = 0;       // env HSM_XCD_CHUNK_EXACT: the same for the exact-order texel-cache form (0 = contiguous eighths, its default)
-  int xcd_chunk = 16;            // env HSM_XCD_CHUNK: workgroups per chunk of the chunked-cyclic batch mapping (0 = contiguous eighths)
-  unsigned long long* clock_probe = nullptr;  // hsm_set_clock_probe
-  int spb_large = 8;             // env HSM_SPB_LARGE=4|8: scans per workgroup of the texel-cache matcher on maps > 2^23 cells
-  int wg_sync = -1;              // env HSM_WG_SYNC=0|1: per-beam workgroup barrier of the texel-cache matcher (-1 = for maps > 2^23 cells)
-  bool dense_bits = true;        // env HSM_DENSE_BITS=0: dense scans keep the keyed update (map_update.h)
-  bool exact_cached = true;      // env HSM_EXACT_CACHED=0: exact-mode batches take the one-wavefront-per-scan exact form (gn_match_kernel) instead of gn_match_exact.h's
-  bool exact = false;     // HSM_PARITY_EXACT: H / dTr summed in the reference's beam order (gn_step.h exact_round)
-  bool auto_parity = true;  // HSM_PARITY_AUTO (default): every entry point in the reference's summation order (wants_exact)
-  bool relaxed = false;   // HSM_PARITY_RELAXED: contracted multiply-adds in the throughput kernel (gn_match_cached_kernel<.., RELAXED>)
-  int last_cfg[6] = {0, 0, 0, 0, 0, 0};  // MatchPlan::record of the last match launch (record_launch)
-  int coop_mute_block = 0;      // hsm_debug_set_coop_mute (test hook)
-  int sched_level = -1;         // hsm_debug_set_schedule (test hook): batched entries run `sched_level` only, -1 = the full schedule
-  int sched_steps = 0;          //   ... with this many GN steps
-  bool exact_spec = false;       // env HSM_EXACT_SPEC=1: one-workgroup-per-scan launches in exact order take the speculative-carry form (gn_match_spec.h:
-                                 // the same bits; measured SLOWER than the literal chains on one CU -- DESIGN.md 8 -- hence opt-in)
-  bool exact_spec1 = false;      // env HSM_EXACT_SPEC1=1: ONE scan of up to 2048 beams (hsm_match) in exact order takes the on-chip speculative-carry form
-  // hsm_set_batch_order: launch order of a batch (texel-cache batch forms).  One permutation buffer per stream that has launched
-  // a sorted batch (launches on one stream are ordered; a ninth stream keeps the caller's order)
-  int batch_order = 2;           // HSM_ORDER_AUTO
-  int batch_order_min = 1024;    // env HSM_BATCH_ORDER_MIN: smaller batches keep the caller's order
-  int batch_order_refresh = 16;  // hsm_set_batch_order_refresh / env HSM_BATCH_ORDER_REFRESH: a stream's permutation serves that many
-                                 // launches of the same batch size before it is computed again (ANY permutation gives the same
-                                 // results; an old one only groups the scans by where they were)
-  struct PermBuf {
-    hipStream_t s;
-    Buf<int> d;  // (not enrolled: hsm_destroy walks perm_bufs)
-    int batch;  // the batch size the permutation in `d` was computed for (0: none)
-    int used;   // launches it has served
-  };
-  std::vector<PermBuf> perm_bufs;
-  bool last_sorted = false;
-  // gn_match_spec_kernel: products of every beam, [batch][stride] float4s -- one block per stream that has launched the form
-  // (launches on one stream are ordered; a ninth stream, and any launch into a graph capture, take the literal dense form)
-  struct SpecScratch {
-    hipStream_t s;
-    Buf<float4> d;  // (not enrolled: hsm_destroy walks spec_scratch)
-  };
-  std::vector<SpecScratch> spec_scratch;
-  SpecStats* d_spec_stats = nullptr; // hsm_debug_spec_stats
-  bool exact_dense = true;       // env HSM_EXACT_DENSE=0: dense scans in exact order keep the 16-wavefront team form (gn_match_kernel<16,...,EXACT>)
-  int exact_dense_min = 4096;    // env HSM_EXACT_DENSE_MIN: beams from which the producers-ahead-of-the-chain form takes over
-  int compute_units = 256;   // of this device (hsm_create)
-  int exact_split_tail = 1;  // env HSM_EXACT_SPLIT_TAIL=0: one launch however the batch divides into generations
-  int exact_chain_wave = 1;  // env HSM_EXACT_CHAIN_WAVE=0: no chain-only wavefront, teams of wavefronts for batches below 4096 scans (rounds 3-4)
-  int cast_form = -1;            // env HSM_CAST_FORM=wave|lane: hsm_cast_scans* take that walk whatever the fan (-1 = by its length, rays.hip)
-  int window_form = -1;          // env HSM_WINDOW_FORM=wave|lane: hsm_score_window* take that form whatever the window (-1 = by its size, window.hip)
-  const char* last_kernel = "";  // name of the matcher kernel the last launch used (hsm_last_launch_kernel)
-  unsigned coop_fallbacks = 0;  // dense single-scan matches re-run on one workgroup after an exchange timeout (match_single)
-  // ... and the back-off that follows: after a timeout the multi-workgroup form is skipped for the next coop_skip matches (1, 2, 4, ...
-  // up to 1024, reset by the first exchange that completes) -- on a device another process keeps busy every dense match would
-  // otherwise pay the full bounded wait, a host spin and a second launch (round-5 advisor)
-  unsigned coop_skip = 0, coop_backoff = 0;
-  bool fused_exchange_done = false;  // the last launch_match carried MatchParams::xp itself (else the caller launches the exchange step)
-  int last_parity = HSM_PARITY_FAST;  // the mode the last match launch actually ran in (hsm_last_launch_parity)
 };
 
 namespace hsm_host {
@@ -486,7 +506,7 @@ int slam_scans_queue(hsm_ctx* h, const ScanLog& log, const PosedScans& scans);
 template <class F>
 void with_sampler_form(const hsm_ctx* h, F&& f) {
   const bool exact = wants_exact(h);
-  if (h->layout == kLayoutPlane) {
+  if (h->cfg.layout == kLayoutPlane) {
     if (exact) f(std::integral_constant<int, kLayoutPlane>{}, std::true_type{}); else f(std::integral_constant<int, kLayoutPlane>{}, std::false_type{});
   } else {
     if (exact) f(std::integral_constant<int, kLayoutQuad>{}, std::true_type{}); else f(std::integral_constant<int, kLayoutQuad>{}, std::false_type{});

@@ -26,26 +26,26 @@ extern "C" {
 // clouds; the int behind it is the survivor count), the sensor-geometry table (16 B per beam covers the
 // float2 and the double2 variant) and the container
 static int ensure_ingest_capacity(hsm_ctx* h, int n) {
-  if (h->d_ingest && h->d_ingest.holds((size_t)n)) return HSM_OK;
-  if (int rc = h->d_ingest.drop()) return rc;  // (first: it stands for the trio)
-  h->trig_n = -1;
+  if (h->ingest.d_ingest && h->ingest.d_ingest.holds((size_t)n)) return HSM_OK;
+  if (int rc = h->ingest.d_ingest.drop()) return rc;  // (first: it stands for the trio)
+  h->ingest.trig_n = -1;
   const size_t want = grown_capacity((size_t)n, {2048, 50});
-  if (int rc = h->d_ranges.reserve(3 * want + 1)) return rc;  // (+ the survivor count, an int)
-  if (int rc = h->d_trig.reserve(want)) return rc;
-  return h->d_ingest.reserve(want);
+  if (int rc = h->ingest.d_ranges.reserve(3 * want + 1)) return rc;  // (+ the survivor count, an int)
+  if (int rc = h->ingest.d_trig.reserve(want)) return rc;
+  return h->ingest.d_ingest.reserve(want);
 }
 
-static int* ingest_count_ptr(hsm_ctx* h) { return reinterpret_cast<int*>(h->d_ranges + 3 * h->d_ingest.count()); }
+static int* ingest_count_ptr(hsm_ctx* h) { return reinterpret_cast<int*>(h->ingest.d_ranges + 3 * h->ingest.d_ingest.count()); }
 
 // fetch the survivor count + the container the kernel on h->stream just produced
 static int finish_ingest(hsm_ctx* h, float* out_pts_xy, int* out_n) {
   int m = 0;
   HIP_TRY(hipMemcpyAsync(&m, ingest_count_ptr(h), sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
-  h->h_ingest.resize(2 * (size_t)m);
-  if (m > 0) HIP_TRY(hipMemcpy(h->h_ingest.data(), h->d_ingest, (size_t)m * sizeof(float2), hipMemcpyDeviceToHost));
-  h->ingest_n = m;
-  if (out_pts_xy && m > 0) memcpy(out_pts_xy, h->h_ingest.data(), (size_t)m * sizeof(float2));
+  h->ingest.h_ingest.resize(2 * (size_t)m);
+  if (m > 0) HIP_TRY(hipMemcpy(h->ingest.h_ingest.data(), h->ingest.d_ingest, (size_t)m * sizeof(float2), hipMemcpyDeviceToHost));
+  h->ingest.ingest_n = m;
+  if (out_pts_xy && m > 0) memcpy(out_pts_xy, h->ingest.h_ingest.data(), (size_t)m * sizeof(float2));
   if (out_n) *out_n = m;
   return HSM_OK;
 }
@@ -79,13 +79,13 @@ static std::vector<double> laser_unit_vectors(int n, float angle_min, float angl
 // laser_unit_vectors' double pairs; evaluated by `make` and uploaded where the last call's kind or geometry was another
 extern "C++" template <class Make>
 static int ensure_sensor_table(hsm_ctx* h, int kind, int n, float angle_min, float angle_increment, Make make) {
-  if (h->trig_kind == kind && h->trig_n == n && h->trig_a0 == angle_min && h->trig_inc == angle_increment) return HSM_OK;
+  if (h->ingest.trig_kind == kind && h->ingest.trig_n == n && h->ingest.trig_a0 == angle_min && h->ingest.trig_inc == angle_increment) return HSM_OK;
   const auto t = make(n, angle_min, angle_increment);
-  if (n > 0) HIP_TRY(hipMemcpy(h->d_trig, t.data(), t.size() * sizeof t[0], hipMemcpyHostToDevice));
-  h->trig_kind = kind;
-  h->trig_n = n;
-  h->trig_a0 = angle_min;
-  h->trig_inc = angle_increment;
+  if (n > 0) HIP_TRY(hipMemcpy(h->ingest.d_trig, t.data(), t.size() * sizeof t[0], hipMemcpyHostToDevice));
+  h->ingest.trig_kind = kind;
+  h->ingest.trig_n = n;
+  h->ingest.trig_a0 = angle_min;
+  h->ingest.trig_inc = angle_increment;
   return HSM_OK;
 }
 
@@ -98,13 +98,13 @@ int hsm_ingest_laser_scan(hsm_ctx* h, const float* ranges, int n, float angle_mi
   if (int rc = select_device(h)) return rc;
   if (int rc = ensure_ingest_capacity(h, n)) return rc;
   if (int rc = ensure_sensor_table(h, 0, n, angle_min, angle_increment, node_scan_trig)) return rc;
-  if (n > 0) HIP_TRY(hipMemcpyAsync(h->d_ranges, ranges, (size_t)n * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  if (n > 0) HIP_TRY(hipMemcpyAsync(h->ingest.d_ranges, ranges, (size_t)n * sizeof(float), hipMemcpyHostToDevice, h->stream));
   const float maxRangeForContainer = range_max - 0.1f;  // :493
-  hipLaunchKernelGGL(ingest_laser_scan_kernel, dim3(1), dim3(1024), 0, h->stream, h->d_ranges,
-                     reinterpret_cast<const float2*>(h->d_trig.p), n, range_min, maxRangeForContainer, scale_to_map,
-                     h->d_ingest, ingest_count_ptr(h));
+  hipLaunchKernelGGL(ingest_laser_scan_kernel, dim3(1), dim3(1024), 0, h->stream, h->ingest.d_ranges,
+                     reinterpret_cast<const float2*>(h->ingest.d_trig.p), n, range_min, maxRangeForContainer, scale_to_map,
+                     h->ingest.d_ingest, ingest_count_ptr(h));
   HIP_TRY(hipGetLastError());
-  h->ingest_origo[0] = h->ingest_origo[1] = 0.0f;  // dataContainer.setOrigo(Vector2f::Zero()), :491
+  h->ingest.ingest_origo[0] = h->ingest.ingest_origo[1] = 0.0f;  // dataContainer.setOrigo(Vector2f::Zero()), :491
   return finish_ingest(h, out_pts_xy, out_n);
 }
 
@@ -118,16 +118,16 @@ static int ingest_cloud(hsm_ctx* h, CloudIngestParams& P, const double tf_rows[1
   P.z_min = z_min;
   P.z_max = z_max;
   P.scale = scale_to_map;
-  P.out = h->d_ingest;
+  P.out = h->ingest.d_ingest;
   P.out_n = ingest_count_ptr(h);
   hipLaunchKernelGGL(ingest_point_cloud_kernel, dim3(1), dim3(1024), 0, h->stream, P);
   HIP_TRY(hipGetLastError());
   // dataContainer.setOrigo(Eigen::Vector2f(laserPos.x(), laserPos.y()) * scaleToMap)  (:517)
-  h->ingest_origo[0] = (float)tf_rows[3] * scale_to_map;
-  h->ingest_origo[1] = (float)tf_rows[7] * scale_to_map;
+  h->ingest.ingest_origo[0] = (float)tf_rows[3] * scale_to_map;
+  h->ingest.ingest_origo[1] = (float)tf_rows[7] * scale_to_map;
   if (out_origo) {
-    out_origo[0] = h->ingest_origo[0];
-    out_origo[1] = h->ingest_origo[1];
+    out_origo[0] = h->ingest.ingest_origo[0];
+    out_origo[1] = h->ingest.ingest_origo[1];
   }
   return finish_ingest(h, out_pts_xy, out_n);
 }
@@ -142,9 +142,9 @@ int hsm_ingest_point_cloud(hsm_ctx* h, const float* pts_xyz, int n, const double
   if (int rc = select_device(h)) return rc;
   if (int rc = ensure_ingest_capacity(h, n)) return rc;
   if (n > 0)
-    HIP_TRY(hipMemcpyAsync(h->d_ranges, pts_xyz, 3 * (size_t)n * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->ingest.d_ranges, pts_xyz, 3 * (size_t)n * sizeof(float), hipMemcpyHostToDevice, h->stream));
   CloudIngestParams P{};
-  P.pts_xyz = h->d_ranges;
+  P.pts_xyz = h->ingest.d_ranges;
   P.n = n;
   return ingest_cloud(h, P, tf_rows, sqr_laser_min_dist, sqr_laser_max_dist, laser_z_min, laser_z_max, scale_to_map,
                       out_pts_xy, out_n, out_origo);
@@ -161,10 +161,10 @@ int hsm_ingest_laser_scan_tf(hsm_ctx* h, const float* ranges, int n, float angle
   if (int rc = select_device(h)) return rc;
   if (int rc = ensure_ingest_capacity(h, n)) return rc;
   if (int rc = ensure_sensor_table(h, 1, n, angle_min, angle_increment, laser_unit_vectors)) return rc;
-  if (n > 0) HIP_TRY(hipMemcpyAsync(h->d_ranges, ranges, (size_t)n * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  if (n > 0) HIP_TRY(hipMemcpyAsync(h->ingest.d_ranges, ranges, (size_t)n * sizeof(float), hipMemcpyHostToDevice, h->stream));
   CloudIngestParams P{};
-  P.ranges = h->d_ranges;
-  P.unit = h->d_trig;
+  P.ranges = h->ingest.d_ranges;
+  P.unit = h->ingest.d_trig;
   P.n = n;
   P.range_min = range_min;
   P.range_cutoff = range_cutoff < 0 ? (double)range_max : range_cutoff;
@@ -240,7 +240,7 @@ static int match_batch_ranges_nolock(hsm_ctx* h, int batch, const float* d_begin
   hipStream_t s = (hipStream_t)stream;
   const float2* trig = nullptr;
   if (n > 0)
-    if (int rc = ranges_geometry_table(h->ranges_geoms, n, angle_min, angle_increment, s, "hsm_match_batch_ranges_device",
+    if (int rc = ranges_geometry_table(h->ingest.ranges_geoms, n, angle_min, angle_increment, s, "hsm_match_batch_ranges_device",
                                        node_scan_trig, &trig))
       return rc;
   char* ws = (char*)d_workspace;
@@ -291,9 +291,9 @@ int hsm_match_batch_ranges(hsm_ctx* h, int batch, const float* begin_world, cons
   const RangesStage st = ranges_stage(batch, n, L.total, begin_world, ranges, out_pose, out_cov, out_counts);
   std::lock_guard<std::mutex> lk(h->mu);
   if (int rc = select_device(h)) return rc;
-  if (!h->d_rbatch.holds(st.plan.total())) HIP_TRY(hipStreamSynchronize(h->stream));
-  if (int rc = h->d_rbatch.reserve(st.plan.total())) return rc;
-  char* base = h->d_rbatch;
+  if (!h->ingest.d_rbatch.holds(st.plan.total())) HIP_TRY(hipStreamSynchronize(h->stream));
+  if (int rc = h->ingest.d_rbatch.reserve(st.plan.total())) return rc;
+  char* base = h->ingest.d_rbatch;
   if (int rc = stage_copy_in(st.plan, base, h->stream)) return rc;
   if (int rc = match_batch_ranges_nolock(h, batch, staged<float>(base, st.begin), staged<float>(base, st.ranges), n, angle_min,
                                          angle_increment, range_min, range_max, scale_to_map, staged<float>(base, st.pose),
@@ -330,7 +330,7 @@ static int ranges_tf_unit_table(hsm_ctx* h, const char* who, RangesTfParams& P, 
   P.unit = nullptr;
   if (int rc = select_device(h)) return rc;
   if (P.n == 0) return HSM_OK;
-  return ranges_geometry_table(h->ranges_tf_geoms, P.n, angle_min, angle_increment, s, who, laser_unit_vectors, &P.unit);
+  return ranges_geometry_table(h->ingest.ranges_tf_geoms, P.n, angle_min, angle_increment, s, who, laser_unit_vectors, &P.unit);
 }
 
 // the three launches on `s`; they read nothing of the context.  d_counts_copy: a second copy of the counts, by the offsets pass
@@ -398,9 +398,9 @@ int hsm_match_batch_ranges_tf(hsm_ctx* h, int batch, const float* begin_world, c
                                            out_origo);
   std::lock_guard<std::mutex> lk(h->mu);
   if (int rc = ranges_tf_unit_table(h, who, P, angle_min, angle_increment, h->stream)) return rc;
-  if (!h->d_rbatch.holds(st.plan.total())) HIP_TRY(hipStreamSynchronize(h->stream));
-  if (int rc = h->d_rbatch.reserve(st.plan.total())) return rc;
-  char* base = h->d_rbatch;
+  if (!h->ingest.d_rbatch.holds(st.plan.total())) HIP_TRY(hipStreamSynchronize(h->stream));
+  if (int rc = h->ingest.d_rbatch.reserve(st.plan.total())) return rc;
+  char* base = h->ingest.d_rbatch;
   P.ranges = staged<float>(base, st.ranges);
   P.tf_rows = staged<double>(base, st.tf);
   float* d_pts = staged<float>(base, st.pts);
@@ -489,9 +489,9 @@ int hsm_slam_ranges_tf(hsm_ctx* h, int count, const float* start_pose, const flo
   std::lock_guard<std::mutex> lk(h->mu);
   if (int rc = select_device(h)) return rc;
   if (int rc = slam_refuse_capture(h, h->stream, who)) return rc;  // (before the copies are queued)
-  if (!h->d_rbatch.holds(st.plan.total())) HIP_TRY(hipStreamSynchronize(h->stream));
-  if (int rc = h->d_rbatch.reserve(st.plan.total())) return rc;
-  char* base = h->d_rbatch;
+  if (!h->ingest.d_rbatch.holds(st.plan.total())) HIP_TRY(hipStreamSynchronize(h->stream));
+  if (int rc = h->ingest.d_rbatch.reserve(st.plan.total())) return rc;
+  char* base = h->ingest.d_rbatch;
   P.ranges = staged<float>(base, st.ranges);
   P.tf_rows = staged<double>(base, st.tf);
   const ScanLog log{count,

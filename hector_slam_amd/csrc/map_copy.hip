@@ -37,7 +37,7 @@ void widen(int acc[4], const CopyBox& b) {
 }
 
 bool same_geometry(const hsm_ctx* a, const hsm_ctx* b) {
-  if (a->levels.size() != b->levels.size() || a->layout != b->layout) return false;
+  if (a->levels.size() != b->levels.size() || a->cfg.layout != b->cfg.layout) return false;
   for (size_t l = 0; l < a->levels.size(); ++l) {
     const Level &A = a->levels[l], &B = b->levels[l];
     if (A.sx != B.sx || A.sy != B.sy || A.cell_length != B.cell_length || A.mapTworld.t0 != B.mapTworld.t0 ||
@@ -83,32 +83,32 @@ int copy_map(hsm_ctx* dst, hsm_ctx* src, const int* boxes, bool whole, const cha
   }
   // copies are not captured, like every writer of a map
   for (const hsm_ctx* h : {dst, src})
-    for (const hsm_ctx::ForeignStream& f : h->foreign)
+    for (const hsm_ctx::ForeignStream& f : h->order.foreign)
       if (stream_capturing(f.s))
         return fail_at(HSM_ERR_INVALID, who, ": a caller's stream that one of the contexts matches on is being captured into a graph");
 
   // the source's counters: gated updates keep theirs on the device until someone asks (this waits for the source's stream)
-  if (src->gate_outstanding)
+  if (src->upd.gate_outstanding)
     if (int rc = fold_gate_counters(src)) return rc;
   if (int rc = select_device(dst)) return rc;
-  if (dst->upd_boxes_outstanding)
+  if (dst->upd.upd_boxes_outstanding)
     if (int rc = merge_device_boxes(dst)) return rc;
-  if (dst->gate_outstanding)  // (what they still hold would be added to the counters copied below)
+  if (dst->upd.gate_outstanding)  // (what they still hold would be added to the counters copied below)
     if (int rc = fold_gate_counters(dst)) return rc;
-  const bool staged = dst->device != src->device || dst->copy_stage;
+  const bool staged = dst->device != src->device || dst->cfg.forms.copy_stage;
   if (staged && max_cells > 0)
-    if (int rc = dst->d_copy_patch.reserve(patch_elems, kHalfMore)) return rc;
+    if (int rc = dst->copy.d_copy_patch.reserve(patch_elems, kHalfMore)) return rc;
 
   if (max_cells > 0) {
     // a reader of the source: behind every update queued on its stream
     if (int rc = select_device(src)) return rc;
-    if (!src->evt_copy_src) HIP_TRY(hipEventCreateWithFlags(&src->evt_copy_src, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(src->evt_copy_src, src->stream));
+    if (!src->copy.evt_copy_src) HIP_TRY(hipEventCreateWithFlags(&src->copy.evt_copy_src, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(src->copy.evt_copy_src, src->stream));
     // a writer of the destination: behind the matches callers' streams may still be running on it
     if (int rc = select_device(dst)) return rc;
     if (int rc = order_after_foreign_match(dst)) return rc;
-    HIP_TRY(hipStreamWaitEvent(dst->stream, src->evt_copy_src, 0));
-    if (!dst->evt_copy_read) HIP_TRY(hipEventCreateWithFlags(&dst->evt_copy_read, hipEventDisableTiming));
+    HIP_TRY(hipStreamWaitEvent(dst->stream, src->copy.evt_copy_src, 0));
+    if (!dst->copy.evt_copy_read) HIP_TRY(hipEventCreateWithFlags(&dst->copy.evt_copy_read, hipEventDisableTiming));
     for (int l = 0; l < nlev; ++l) {
       const Level &D = dst->levels[l], &S = src->levels[l];
       MapCopyLevel& M = P.lv[l];
@@ -121,7 +121,7 @@ int copy_map(hsm_ctx* dst, hsm_ctx* src, const int* boxes, bool whole, const cha
       M.src_logodds = S.d_logodds;
       M.src_stamps = S.d_update_index;
       if (!staged || copy_box_empty(M.box)) continue;
-      float* base = dst->d_copy_patch;
+      float* base = dst->copy.d_copy_patch;
       const CopyBox& b = M.box;
       const size_t w = (size_t)(b.x1 - b.x0 + 1), rows = (size_t)(b.y1 - b.y0 + 1), at = (size_t)b.y0 * S.sx + b.x0;
       HIP_TRY(hipMemcpy2DAsync(base + patch[l].logodds, w * 4, S.d_logodds + at, (size_t)S.sx * 4, w * 4, rows, hipMemcpyDefault,
@@ -133,16 +133,16 @@ int copy_map(hsm_ctx* dst, hsm_ctx* src, const int* boxes, bool whole, const cha
     }
     const dim3 grid1((unsigned int)grid_for((size_t)max_turns * 64), (unsigned int)nlev);
     if (staged) {  // the source has been read once the patch is filled
-      HIP_TRY(hipEventRecord(dst->evt_copy_read, dst->stream));
+      HIP_TRY(hipEventRecord(dst->copy.evt_copy_read, dst->stream));
       hipLaunchKernelGGL(map_copy_cells_kernel<true>, grid1, dim3(256), 0, dst->stream, P);
     } else {
       hipLaunchKernelGGL(map_copy_cells_kernel<false>, grid1, dim3(256), 0, dst->stream, P);
-      HIP_TRY(hipEventRecord(dst->evt_copy_read, dst->stream));
+      HIP_TRY(hipEventRecord(dst->copy.evt_copy_read, dst->stream));
     }
     HIP_TRY(hipGetLastError());
     // the next writer of the source -- all of them queue on its stream -- behind that read
-    HIP_TRY(hipStreamWaitEvent(src->stream, dst->evt_copy_read, 0));
-    if (dst->layout == kLayoutQuad) {
+    HIP_TRY(hipStreamWaitEvent(src->stream, dst->copy.evt_copy_read, 0));
+    if (dst->cfg.layout == kLayoutQuad) {
       hipLaunchKernelGGL(map_copy_texels_kernel, dim3((unsigned int)grid_for(max_texels), (unsigned int)nlev), dim3(256), 0,
                          dst->stream, P);
       HIP_TRY(hipGetLastError());

@@ -57,7 +57,7 @@ int hsm_shift_map(hsm_ctx* h, float new_start_x, float new_start_y, int shift_ce
   const ShiftPlan plan = plan_map_shift(L0.cell_length, L0.sx, L0.sy, nlev, h->start, to);
   if (plan.refusal != kShiftOk) return fail_at(HSM_ERR_INVALID, who, refusal_text(plan.refusal));
   // a move is not captured, like every writer of a map
-  for (const hsm_ctx::ForeignStream& f : h->foreign)
+  for (const hsm_ctx::ForeignStream& f : h->order.foreign)
     if (stream_capturing(f.s))
       return fail_at(HSM_ERR_INVALID, who, ": a caller's stream that the context matches on is being captured into a graph");
   if (shift_cells) shift_cells[0] = plan.d0[0], shift_cells[1] = plan.d0[1];
@@ -65,9 +65,9 @@ int hsm_shift_map(hsm_ctx* h, float new_start_x, float new_start_y, int shift_ce
 
   if (plan.moves) {
     if (int rc = select_device(h)) return rc;
-    if (h->upd_boxes_outstanding)  // (their boxes are in old coordinates; the whole level is marked below)
+    if (h->upd.upd_boxes_outstanding)  // (their boxes are in old coordinates; the whole level is marked below)
       if (int rc = merge_device_boxes(h)) return rc;
-    if (h->gate_outstanding)
+    if (h->upd.gate_outstanding)
       if (int rc = fold_gate_counters(h)) return rc;
     MapShiftParams P = {};
     P.nlev = nlev;
@@ -88,7 +88,7 @@ int hsm_shift_map(hsm_ctx* h, float new_start_x, float new_start_y, int shift_ce
       if (st > stage_turns) stage_turns = st;
     }
     if (patch_elems > 0)  // grown here, outside any capture (refused above), before anything is queued
-      if (int rc = h->d_copy_patch.reserve(patch_elems, kHalfMore)) return rc;
+      if (int rc = h->copy.d_copy_patch.reserve(patch_elems, kHalfMore)) return rc;
     // a writer of the map: behind the matches callers' streams may still be running on it, and -- on the context's stream --
     // behind every update queued so far
     if (int rc = order_after_foreign_match(h)) return rc;
@@ -105,7 +105,7 @@ int hsm_shift_map(hsm_ctx* h, float new_start_x, float new_start_y, int shift_ce
       M.sy = L.sy;
       M.from = plan.lv[l].from;
       M.to = plan.lv[l].to;
-      float* base = h->d_copy_patch;
+      float* base = h->copy.d_copy_patch;
       M.st_logodds = base + patch[l].logodds;
       M.st_stamps = reinterpret_cast<int*>(base + patch[l].stamps);
     }
@@ -114,11 +114,11 @@ int hsm_shift_map(hsm_ctx* h, float new_start_x, float new_start_y, int shift_ce
                          h->stream, P);
     hipLaunchKernelGGL(map_shift_cells_kernel, dim3((unsigned int)grid_for((size_t)cell_turns * 64), (unsigned int)nlev), dim3(256), 0,
                        h->stream, P);
-    if (h->layout == kLayoutQuad)
+    if (h->cfg.layout == kLayoutQuad)
       hipLaunchKernelGGL(map_shift_texels_kernel, dim3((unsigned int)grid_for(max_cells), (unsigned int)nlev), dim3(256), 0, h->stream, P);
     HIP_TRY(hipGetLastError());
     // the device's share of the publish boxes: the whole level, from the row hsm_create wrote
-    HIP_TRY(hipMemcpyAsync(h->d_pub_boxes, h->d_pub_boxes + 2 * kMaxLevels * 4, (size_t)nlev * 4 * sizeof(int), hipMemcpyDeviceToDevice,
+    HIP_TRY(hipMemcpyAsync(h->occ.d_pub_boxes, h->occ.d_pub_boxes + 2 * kMaxLevels * 4, (size_t)nlev * 4 * sizeof(int), hipMemcpyDeviceToDevice,
                            h->stream));
   }
   for (int l = 0; l < nlev; ++l) {

@@ -44,18 +44,18 @@ int hsm_host::rebuild_probability(hsm_ctx* h, Level& L) {
 }
 
 int hsm_host::reset_update_gate(hsm_ctx* h) {
-  hipLaunchKernelGGL(update_gate_reset_kernel, dim3(1), dim3(64), 0, h->stream, h->d_gate);
+  hipLaunchKernelGGL(update_gate_reset_kernel, dim3(1), dim3(64), 0, h->stream, h->upd.d_gate);
   HIP_TRY(hipGetLastError());
   return HSM_OK;
 }
 
 // hsm_create's share of the update state: the gate's block, reset, and the publish boxes with their first two rows empty
 int hsm_host::create_update_state(hsm_ctx* h) {
-  HIP_TRY(hipMalloc((void**)&h->d_gate, sizeof(GateState)));
-  HIP_TRY(hipMemsetAsync(h->d_gate, 0, sizeof(GateState), h->stream));
+  HIP_TRY(hipMalloc((void**)&h->upd.d_gate, sizeof(GateState)));
+  HIP_TRY(hipMemsetAsync(h->upd.d_gate, 0, sizeof(GateState), h->stream));
   if (int rc = reset_update_gate(h)) return rc;
-  HIP_TRY(hipMalloc((void**)&h->d_pub_boxes, 3 * kMaxLevels * 4 * sizeof(int)));
-  hipLaunchKernelGGL(update_boxes_clear_kernel, dim3(1), dim3(64), 0, h->stream, h->d_pub_boxes, 2 * kMaxLevels);
+  HIP_TRY(hipMalloc((void**)&h->occ.d_pub_boxes, 3 * kMaxLevels * 4 * sizeof(int)));
+  hipLaunchKernelGGL(update_boxes_clear_kernel, dim3(1), dim3(64), 0, h->stream, h->occ.d_pub_boxes, 2 * kMaxLevels);
   HIP_TRY(hipGetLastError());
   return HSM_OK;
 }
@@ -82,9 +82,9 @@ int hsm_host::scrub_pending_marks(hsm_ctx* h, Level& L) {
 int hsm_host::merge_device_boxes(hsm_ctx* h) {
   if (int rc = select_device(h)) return rc;
   int host[2 * kMaxLevels * 4];
-  HIP_TRY(hipMemcpyAsync(host, h->d_upd_boxes, sizeof host, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(host, h->upd.d_upd_boxes, sizeof host, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
-  hipLaunchKernelGGL(update_boxes_clear_kernel, dim3(1), dim3(64), 0, h->stream, h->d_upd_boxes, kMaxLevels);
+  hipLaunchKernelGGL(update_boxes_clear_kernel, dim3(1), dim3(64), 0, h->stream, h->upd.d_upd_boxes, kMaxLevels);
   HIP_TRY(hipGetLastError());
   for (size_t l = 0; l < h->levels.size(); ++l) {
     Level& L = h->levels[l];
@@ -98,7 +98,7 @@ int hsm_host::merge_device_boxes(hsm_ctx* h) {
     }
     if (run[2] >= run[0]) box_widen(L.dirty, run);
   }
-  h->upd_boxes_outstanding = false;
+  h->upd.upd_boxes_outstanding = false;
   return HSM_OK;
 }
 
@@ -110,22 +110,22 @@ int hsm_host::merge_device_boxes(hsm_ctx* h) {
 int hsm_host::fold_gate_counters(hsm_ctx* h, GateState* state) {
   if (int rc = select_device(h)) return rc;
   GateState host;
-  HIP_TRY(hipMemcpyAsync(&host, h->d_gate, sizeof host, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(&host, h->upd.d_gate, sizeof host, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   if (state) *state = host;
   const int applied = host.pending;
   if (applied > 0) {
-    HIP_TRY(hipMemsetAsync(&h->d_gate->pending, 0, sizeof(int), h->stream));  // ahead of every later gated call
+    HIP_TRY(hipMemsetAsync(&h->upd.d_gate->pending, 0, sizeof(int), h->stream));  // ahead of every later gated call
     for (Level& L : h->levels) {
       L.curr_mark_free = L.curr_update_index + 3 * (applied - 1) + 1;
       L.curr_mark_occ = L.curr_update_index + 3 * (applied - 1) + 2;
       L.curr_update_index += 3 * applied;
       L.last_update_index += applied;
     }
-    h->gate_applied_total += applied;
+    h->upd.gate_applied_total += applied;
     if (state) state->pending = 0;
   }
-  h->gate_outstanding = false;
+  h->upd.gate_outstanding = false;
   return HSM_OK;
 }
 
@@ -295,7 +295,7 @@ void level_bbox(hsm_ctx* h, UpdateBatch& batch, LevelPrep& prep, const UpdatePar
 // dense scans (>= merged_mark_max beams) take the byte-map form of the update (map_update.h), on every map width since round 4;
 // env HSM_DENSE_BITS=0 keeps them on the keyed one-launch mark pass of the small scans
 bool use_dense_bits(const hsm_ctx* h, const UpdateBatch& batch, int max_n) {
-  if (!h->dense_bits || max_n < h->merged_mark_max) return false;
+  if (!h->cfg.upd.dense_bits || max_n < h->cfg.upd.merged_mark_max) return false;
   for (int i = 0; i < batch.nlev; ++i)
     if (batch.lv[i].lv.free_bytes == nullptr) return false;
   return true;
@@ -310,10 +310,10 @@ int launch_update_mark(hsm_ctx* h, UpdateBatch& batch) {
   const unsigned ny = (unsigned)batch.nlev;
   if (use_dense_bits(h, batch, max_n)) {
     // per-beam records: written by the end-cell pass, read by the line walk (one block of max_n records per level)
-    if (!h->d_beam_recs.holds((size_t)max_n * HSM_MAX_LEVELS))
-      if (int rc = h->d_beam_recs.reserve(grown_capacity((size_t)max_n, kHalfMore) * HSM_MAX_LEVELS)) return rc;
-    const size_t per_level = h->d_beam_recs.count() / HSM_MAX_LEVELS;
-    for (int i = 0; i < batch.nlev; ++i) batch.lv[i].recs = h->d_beam_recs + (size_t)i * per_level;
+    if (!h->upd.d_beam_recs.holds((size_t)max_n * HSM_MAX_LEVELS))
+      if (int rc = h->upd.d_beam_recs.reserve(grown_capacity((size_t)max_n, kHalfMore) * HSM_MAX_LEVELS)) return rc;
+    const size_t per_level = h->upd.d_beam_recs.count() / HSM_MAX_LEVELS;
+    for (int i = 0; i < batch.nlev; ++i) batch.lv[i].recs = h->upd.d_beam_recs + (size_t)i * per_level;
     hipLaunchKernelGGL(update_mark_occ_dense_kernel, dim3((max_n + 255) / 256, ny), dim3(256), 0, h->stream, batch);
     // x extent a multiple of 8: workgroup b of every level then runs on XCD b % 8 (the kernel's beam -> XCD mapping)
     hipLaunchKernelGGL(update_mark_free_dense_kernel, dim3(mark_dense_blocks(max_n), ny), dim3(256), 0, h->stream, batch);
@@ -345,13 +345,13 @@ int launch_update_apply(hsm_ctx* h, const UpdateBatch& batch) {
   if (use_dense_bits(h, batch, max_n)) {
     // one wavefront per block of 256 cells of the widened box (32 x 8 cells: two 16 x 8 mark tiles; map_update.h)
     const int g = grid_for(max_box / 4 + 4096);
-    auto dense = h->layout == kLayoutQuad ? (batch.stamped ? update_apply_dense_kernel<true, true> : update_apply_dense_kernel<true, false>)
+    auto dense = h->cfg.layout == kLayoutQuad ? (batch.stamped ? update_apply_dense_kernel<true, true> : update_apply_dense_kernel<true, false>)
                                           : (batch.stamped ? update_apply_dense_kernel<false, true> : update_apply_dense_kernel<false, false>);
     hipLaunchKernelGGL(dense, dim3(g, ny), dim3(256), 0, h->stream, batch);
     HIP_TRY(hipGetLastError());
     return HSM_OK;
   }
-  if (h->layout == kLayoutQuad && max_n < h->scatter_texels_max) {
+  if (h->cfg.layout == kLayoutQuad && max_n < h->cfg.upd.scatter_texels_max) {
     // the apply pass writes the texels itself: one dependent launch less for the launch-bound small scans (1081 beams,
     // 3 levels: complete 39 -> 34.5 us) and one dense pass less for the big ones (16 k beams on 8192^2: 0.51 -> 0.45 ms)
     auto apply = batch.stamped ? update_apply_kernel<true, true> : update_apply_kernel<true, false>;
@@ -359,7 +359,7 @@ int launch_update_apply(hsm_ctx* h, const UpdateBatch& batch) {
   } else {
     auto apply = batch.stamped ? update_apply_kernel<false, true> : update_apply_kernel<false, false>;
     hipLaunchKernelGGL(apply, dim3(grid_for(max_box), ny), dim3(256), 0, h->stream, batch);
-    if (h->layout == kLayoutQuad)
+    if (h->cfg.layout == kLayoutQuad)
       hipLaunchKernelGGL(update_texels_kernel, dim3(grid_for(max_box), ny), dim3(256), 0, h->stream, batch);
   }
   HIP_TRY(hipGetLastError());
@@ -384,9 +384,9 @@ void update_applied(hsm_ctx* h, const UpdateBatch& batch, const LevelPrep& prep)
 // first; it numbers its update behind the ones gated calls applied; and it queues behind a caller's batch match
 int begin_host_update(hsm_ctx* h) {
   if (int rc = select_device(h)) return rc;
-  if (h->upd_boxes_outstanding)
+  if (h->upd.upd_boxes_outstanding)
     if (int rc = merge_device_boxes(h)) return rc;
-  if (h->gate_outstanding)
+  if (h->upd.gate_outstanding)
     if (int rc = fold_gate_counters(h)) return rc;
   return order_after_foreign_match(h);
 }
@@ -419,30 +419,30 @@ int update_impl(hsm_ctx* h, const float pose_world[3], const float* pts_xy, int 
   // The usual flow updates with the scan that was just matched.  When the matcher put that scan into device memory (dense
   // scans, multi-level maps: d_retained) and the caller hands over the same endpoints, they are already where the update
   // kernels read them: no second upload (131 KB from pageable memory for a 16 k-beam scan, which the host waits for).
-  const int rn = h->retained_valid ? (int)(h->retained_pts.size() / 2) : 0;
-  auto same_as_retained = [&] { return rn == n && n > 0 && memcmp(h->retained_pts.data(), pts_xy, (size_t)n * sizeof(float2)) == 0; };
-  const bool same_as_matched = !d_level0 && h->d_retained_current && same_as_retained();
-  if (same_as_matched) d_level0 = h->d_retained;
-  if (!d_level0 && h->async_update) {
+  const int rn = h->retained.retained_valid ? (int)(h->retained.retained_pts.size() / 2) : 0;
+  auto same_as_retained = [&] { return rn == n && n > 0 && memcmp(h->retained.retained_pts.data(), pts_xy, (size_t)n * sizeof(float2)) == 0; };
+  const bool same_as_matched = !d_level0 && h->retained.d_retained_current && same_as_retained();
+  if (same_as_matched) d_level0 = h->retained.d_retained;
+  if (!d_level0 && h->cfg.upd.async_update) {
     // stage the endpoints in pinned memory (a pageable hipMemcpyAsync would block the host until the copy
     // -- and everything queued before it -- has completed); small scans are then read in place over PCIe
     // (each endpoint is read twice), dense ones copied to the device by a copy the host does not wait for
-    slot = h->upd_slot;
-    h->upd_slot ^= 1;
-    if (h->upd_busy[slot]) {
-      HIP_TRY(hipEventSynchronize(h->upd_evt[slot]));
-      h->upd_busy[slot] = false;
+    slot = h->upd.upd_slot;
+    h->upd.upd_slot ^= 1;
+    if (h->upd.upd_busy[slot]) {
+      HIP_TRY(hipEventSynchronize(h->upd.upd_evt[slot]));
+      h->upd.upd_busy[slot] = false;
     }
-    if (int rc = h->h_upd_pinned[slot].reserve((size_t)n, kScanGrowth)) return rc;
-    if (!h->upd_evt[slot]) HIP_TRY(hipEventCreateWithFlags(&h->upd_evt[slot], hipEventDisableTiming));
-    if (n > 0) memcpy(h->h_upd_pinned[slot], pts_xy, (size_t)n * sizeof(float2));
-    if (n <= h->update_zero_copy_max) {
+    if (int rc = h->upd.h_upd_pinned[slot].reserve((size_t)n, kScanGrowth)) return rc;
+    if (!h->upd.upd_evt[slot]) HIP_TRY(hipEventCreateWithFlags(&h->upd.upd_evt[slot], hipEventDisableTiming));
+    if (n > 0) memcpy(h->upd.h_upd_pinned[slot], pts_xy, (size_t)n * sizeof(float2));
+    if (n <= h->cfg.upd.update_zero_copy_max) {
       float2* dev = nullptr;
-      if (n > 0) HIP_TRY(hipHostGetDevicePointer((void**)&dev, h->h_upd_pinned[slot], 0));
+      if (n > 0) HIP_TRY(hipHostGetDevicePointer((void**)&dev, h->upd.h_upd_pinned[slot], 0));
       d_level0 = n > 0 ? dev : h->d_scan;
     } else {
       if (int rc = h->d_scan.reserve((size_t)n, kScanGrowth)) return rc;
-      HIP_TRY(hipMemcpyAsync(h->d_scan, h->h_upd_pinned[slot], (size_t)n * sizeof(float2), hipMemcpyHostToDevice,
+      HIP_TRY(hipMemcpyAsync(h->d_scan, h->upd.h_upd_pinned[slot], (size_t)n * sizeof(float2), hipMemcpyHostToDevice,
                              h->stream));
       d_level0 = h->d_scan;
     }
@@ -461,46 +461,46 @@ int update_impl(hsm_ctx* h, const float pose_world[3], const float* pts_xy, int 
   bool coarse_same_container = false;  // the usual flow: update with the container that was just matched
   if (h->levels.size() > 1) {
     const float2* d_coarse = nullptr;
-    if (same_as_matched || (!h->d_retained_current && same_as_retained())) {
+    if (same_as_matched || (!h->retained.d_retained_current && same_as_retained())) {
       d_coarse = d_level0;
-      coarse_same_container = h->retained_origo[0] == o[0] && h->retained_origo[1] == o[1];
+      coarse_same_container = h->retained.retained_origo[0] == o[0] && h->retained.retained_origo[1] == o[1];
     } else {
-      if (rn > 0 && !h->d_retained_current) {
-        if (int rc = h->d_retained.reserve((size_t)rn, kScanGrowth)) return rc;
-        HIP_TRY(hipMemcpyAsync(h->d_retained, h->retained_pts.data(), (size_t)rn * sizeof(float2),
+      if (rn > 0 && !h->retained.d_retained_current) {
+        if (int rc = h->retained.d_retained.reserve((size_t)rn, kScanGrowth)) return rc;
+        HIP_TRY(hipMemcpyAsync(h->retained.d_retained, h->retained.retained_pts.data(), (size_t)rn * sizeof(float2),
                                hipMemcpyHostToDevice, h->stream));
-        h->d_retained_current = true;
+        h->retained.d_retained_current = true;
       }
-      d_coarse = h->d_retained;  // read only after a possible (re)allocation above
+      d_coarse = h->retained.d_retained;  // read only after a possible (re)allocation above
     }
     for (size_t l = 1; l < h->levels.size(); ++l) {
       const float factor = level_factor((int)l);
-      const float ol[2] = {h->retained_origo[0] * factor, h->retained_origo[1] * factor};  // setFrom :48
-      if (int rc = prepare_level(h, batch, prep[l], (int)l, pose_world, d_coarse, h->retained_pts.data(), rn, factor, ol))
+      const float ol[2] = {h->retained.retained_origo[0] * factor, h->retained.retained_origo[1] * factor};  // setFrom :48
+      if (int rc = prepare_level(h, batch, prep[l], (int)l, pose_world, d_coarse, h->retained.retained_pts.data(), rn, factor, ol))
         return rc;
     }
   }
   if (int rc = mark_and_apply(h, batch, prep, (int)h->levels.size(), coarse_same_container)) return rc;
-  h->queued_update = h->async_update;
+  h->upd.queued_update = h->cfg.upd.async_update;
   if (slot >= 0) {
-    HIP_TRY(hipEventRecord(h->upd_evt[slot], h->stream));
-    h->upd_busy[slot] = true;
+    HIP_TRY(hipEventRecord(h->upd.upd_evt[slot], h->stream));
+    h->upd.upd_busy[slot] = true;
   }
-  if (!h->async_update) HIP_TRY(hipStreamSynchronize(h->stream));
+  if (!h->cfg.upd.async_update) HIP_TRY(hipStreamSynchronize(h->stream));
   return HSM_OK;
 }
 
 // the UpdateBatch blocks and cell boxes of `count` scans (hsm_ctx::d_upd_batches / d_upd_boxes)
 int ensure_update_scans(hsm_ctx* h, size_t count) {
-  if (h->d_upd_boxes && h->d_upd_batches.holds(count)) return HSM_OK;
-  if (h->upd_boxes_outstanding)  // the running boxes live in the block that is about to go
+  if (h->upd.d_upd_boxes && h->upd.d_upd_batches.holds(count)) return HSM_OK;
+  if (h->upd.upd_boxes_outstanding)  // the running boxes live in the block that is about to go
     if (int rc = merge_device_boxes(h)) return rc;
-  if (int rc = h->d_upd_boxes.drop()) return rc;  // (both go before either comes back: the box block stands for the pair)
-  if (int rc = h->d_upd_batches.drop()) return rc;
+  if (int rc = h->upd.d_upd_boxes.drop()) return rc;  // (both go before either comes back: the box block stands for the pair)
+  if (int rc = h->upd.d_upd_batches.drop()) return rc;
   const size_t want = grown_capacity(count, {64, 50});
-  if (int rc = h->d_upd_batches.reserve(want)) return rc;
-  if (int rc = h->d_upd_boxes.reserve((want + 2) * kMaxLevels * 4)) return rc;
-  hipLaunchKernelGGL(update_boxes_clear_kernel, dim3(1), dim3(64), 0, h->stream, h->d_upd_boxes, 2 * kMaxLevels);
+  if (int rc = h->upd.d_upd_batches.reserve(want)) return rc;
+  if (int rc = h->upd.d_upd_boxes.reserve((want + 2) * kMaxLevels * 4)) return rc;
+  hipLaunchKernelGGL(update_boxes_clear_kernel, dim3(1), dim3(64), 0, h->stream, h->upd.d_upd_boxes, 2 * kMaxLevels);
   HIP_TRY(hipGetLastError());
   return HSM_OK;
 }
@@ -526,7 +526,7 @@ int update_by_scans_device_nolock(hsm_ctx* h, const PosedScans& S, hipStream_t s
   if (stream_capturing(stream))
     return fail_at(HSM_ERR_INVALID, S.who, ": `stream` is being captured into a graph (map updates are not captured)");
   if (int rc = order_after_foreign_match(h)) return rc;  // (refuses the same way for the streams this context has matched on)
-  if (!gate && h->gate_outstanding)  // scan k is update k behind EVERY earlier update: the ones gated calls applied go in first
+  if (!gate && h->upd.gate_outstanding)  // scan k is update k behind EVERY earlier update: the ones gated calls applied go in first
     if (int rc = fold_gate_counters(h)) return rc;
   if (int rc = ensure_update_scans(h, (size_t)count)) return rc;
   if (int rc = wait_for_caller_inputs(h, stream)) return rc;
@@ -540,8 +540,8 @@ int update_by_scans_device_nolock(hsm_ctx* h, const PosedScans& S, hipStream_t s
   A.offsets = S.d_offsets;
   A.shared_n = S.shared_n;
   A.origos = reinterpret_cast<const float2*>(S.d_origos);  // per scan, on the device: the host pair below is then not read
-  A.out = h->d_upd_batches;
-  A.boxes = h->d_upd_boxes;
+  A.out = h->upd.d_upd_batches;
+  A.boxes = h->upd.d_upd_boxes;
   size_t max_cells = 0;
   for (int l = 0; l < nlev; ++l) {
     Level& L = h->levels[l];
@@ -564,9 +564,9 @@ int update_by_scans_device_nolock(hsm_ctx* h, const PosedScans& S, hipStream_t s
     UpdateGateParams G;
     memset(&G, 0, sizeof G);
     G.prep = A;
-    G.state = h->d_gate;
-    G.min_dist = h->gate_min_dist;
-    G.min_angle = h->gate_min_angle;
+    G.state = h->upd.d_gate;
+    G.min_dist = h->upd.gate_min_dist;
+    G.min_angle = h->upd.gate_min_angle;
     G.force = gate->d_force;
     G.out_applied = gate->d_out_applied;
     G.slam = gate->slam ? 1 : 0;
@@ -583,7 +583,7 @@ int update_by_scans_device_nolock(hsm_ctx* h, const PosedScans& S, hipStream_t s
   const int hint = S.max_beams > 0 ? S.max_beams : 1081;
   const unsigned occ_blocks = (unsigned)((hint + 255) / 256), free_blocks = (unsigned)((hint + 3) / 4);
   const unsigned apply_blocks = (unsigned)grid_for(max_cells);
-  const bool scatter = h->layout == kLayoutQuad;
+  const bool scatter = h->cfg.layout == kLayoutQuad;
   // Restored stamps at or ahead of the first scan's free mark: the whole call takes the stamp-aware apply pass.  (A gated call
   // whose predecessors' counts are still on the device sees a counter that lags: the test errs towards the stamp-aware form.)
   bool stamped = false;
@@ -603,10 +603,10 @@ int update_by_scans_device_nolock(hsm_ctx* h, const PosedScans& S, hipStream_t s
       }
       ++L.serial;
     }
-    int* scan_boxes = h->d_upd_boxes + (size_t)update_box_slot(k, count) * kMaxLevels * 4;
+    int* scan_boxes = h->upd.d_upd_boxes + (size_t)update_box_slot(k, count) * kMaxLevels * 4;
     hipLaunchKernelGGL(update_mark_scan_kernel, dim3(occ_blocks + free_blocks, (unsigned)nlev), dim3(256), 0, h->stream,
-                       h->d_upd_batches + k, occ_blocks, scan_boxes, h->d_upd_boxes, h->d_pub_boxes);
-    hipLaunchKernelGGL(apply_scan, dim3(apply_blocks, (unsigned)nlev), dim3(256), 0, h->stream, h->d_upd_batches + k, scan_boxes);
+                       h->upd.d_upd_batches + k, occ_blocks, scan_boxes, h->upd.d_upd_boxes, h->occ.d_pub_boxes);
+    hipLaunchKernelGGL(apply_scan, dim3(apply_blocks, (unsigned)nlev), dim3(256), 0, h->stream, h->upd.d_upd_batches + k, scan_boxes);
     HIP_TRY(hipGetLastError());
   }
   for (int l = 0; l < nlev; ++l) {
@@ -622,10 +622,10 @@ int update_by_scans_device_nolock(hsm_ctx* h, const PosedScans& S, hipStream_t s
     L.key_rows[0] = 0;  // which rows carry keys of this generation is known on the device only: the next wrap of a host-side
     L.key_rows[1] = L.sy - 1;  // update clears the whole level
   }
-  h->upd_boxes_outstanding = true;
-  if (gate) h->gate_outstanding = true;
-  h->queued_update = h->async_update;
-  if (!h->async_update) HIP_TRY(hipStreamSynchronize(h->stream));
+  h->upd.upd_boxes_outstanding = true;
+  if (gate) h->upd.gate_outstanding = true;
+  h->upd.queued_update = h->cfg.upd.async_update;
+  if (!h->cfg.upd.async_update) HIP_TRY(hipStreamSynchronize(h->stream));
   return HSM_OK;
 }
 
@@ -650,7 +650,7 @@ int update_by_scans_device_gated(hsm_ctx* h, PosedScans S, const unsigned char* 
 // the loop itself, on the context's stream.  `scans`: the log's CSR end points, beam hint, origo(s) and the name its updates
 // report under (count, poses and gate are the loop's to set)
 int hsm_host::slam_scans_queue(hsm_ctx* h, const ScanLog& log, const PosedScans& scans) {
-  hipLaunchKernelGGL(slam_begin_kernel, dim3(1), dim3(64), 0, h->stream, h->d_gate, log.d_start_pose, log.d_hint_deltas);
+  hipLaunchKernelGGL(slam_begin_kernel, dim3(1), dim3(64), 0, h->stream, h->upd.d_gate, log.d_start_pose, log.d_hint_deltas);
   HIP_TRY(hipGetLastError());
   GateCall gate;
   PosedScans one = scans;
@@ -658,7 +658,7 @@ int hsm_host::slam_scans_queue(hsm_ctx* h, const ScanLog& log, const PosedScans&
   one.shared_n = 0;
   one.gate = &gate;
   for (int k = 0; k < log.count; ++k) {
-    if (int rc = match_batch_device_nolock(h, 1, h->d_gate->hint, scans.d_pts, scans.d_offsets + k, scans.max_beams, log.pose(k),
+    if (int rc = match_batch_device_nolock(h, 1, h->upd.d_gate->hint, scans.d_pts, scans.d_offsets + k, scans.max_beams, log.pose(k),
                                            log.cov(k), h->stream))
       return rc;
     gate = log.gate(k);
@@ -701,11 +701,11 @@ int hsm_update_by_scan(hsm_ctx* h, const float pose_world[3], const float* pts_x
 
 int hsm_update_by_ingested(hsm_ctx* h, const float pose_world[3]) {
   if (!h) return fail(HSM_ERR_INVALID, "null context");
-  if (!pose_world || h->ingest_n < 0) return fail(HSM_ERR_INVALID, "hsm_update_by_ingested: no scan ingested");
+  if (!pose_world || h->ingest.ingest_n < 0) return fail(HSM_ERR_INVALID, "hsm_update_by_ingested: no scan ingested");
   std::lock_guard<std::mutex> lk(h->mu);
   static const float dummy[2] = {0.0f, 0.0f};
-  const float* hp = h->ingest_n > 0 ? h->h_ingest.data() : dummy;
-  return update_impl(h, pose_world, hp, h->ingest_n, h->ingest_origo, h->d_ingest);
+  const float* hp = h->ingest.ingest_n > 0 ? h->ingest.h_ingest.data() : dummy;
+  return update_impl(h, pose_world, hp, h->ingest.ingest_n, h->ingest.ingest_origo, h->ingest.d_ingest);
 }
 
 int hsm_update_by_scan_level(hsm_ctx* h, int level, const float pose_world[3], const float* pts_level_xy, int n,
@@ -734,8 +734,8 @@ int hsm_update_by_scan_level(hsm_ctx* h, int level, const float pose_world[3], c
 int hsm_set_update_gate(hsm_ctx* h, float min_dist, float min_angle) {
   if (!h) return fail(HSM_ERR_INVALID, "null context");
   std::lock_guard<std::mutex> lk(h->mu);
-  h->gate_min_dist = min_dist;
-  h->gate_min_angle = min_angle;
+  h->upd.gate_min_dist = min_dist;
+  h->upd.gate_min_angle = min_angle;
   return HSM_OK;
 }
 
@@ -753,7 +753,7 @@ int hsm_update_gate_state(hsm_ctx* h, float last_update_pose[3], long long* appl
   if (int rc = fold_gate_counters(h, &st)) return rc;
   if (last_update_pose)
     for (int i = 0; i < 3; ++i) last_update_pose[i] = st.last_update_pose[i];
-  if (applied_total) *applied_total = h->gate_applied_total;
+  if (applied_total) *applied_total = h->upd.gate_applied_total;
   return HSM_OK;
 }
 
@@ -829,13 +829,13 @@ int hsm_update_by_scans(hsm_ctx* h, int count, const float* poses_world, const f
   if (longest > HSM_MAX_UPDATE_BEAMS) return fail(HSM_ERR_TOO_LARGE, "hsm_update_by_scans: more than HSM_MAX_UPDATE_BEAMS beams");
   std::lock_guard<std::mutex> lk(h->mu);
   if (int rc = select_device(h)) return rc;
-  for (const hsm_ctx::ForeignStream& f : h->foreign)  // refused before the copies are queued (order_after_foreign_match)
+  for (const hsm_ctx::ForeignStream& f : h->order.foreign)  // refused before the copies are queued (order_after_foreign_match)
     if (stream_capturing(f.s))
       return fail(HSM_ERR_INVALID, "hsm_update_by_scans: a caller's stream that this context matches on is being captured into a graph");
   // one staging block (the copies are queued on the context's stream, in front of the update)
   const UpdateScansStage st = update_scans_stage(count, total, poses_world, pts_xy, scan_offsets);
-  if (int rc = h->d_upd_stage.reserve(st.plan.total(), kHalfMore)) return rc;
-  char* base = h->d_upd_stage;
+  if (int rc = h->upd.d_upd_stage.reserve(st.plan.total(), kHalfMore)) return rc;
+  char* base = h->upd.d_upd_stage;
   if (int rc = stage_copy_in(st.plan, base, h->stream)) return rc;
   PosedScans S{count, staged<float>(base, st.poses), staged<float>(base, st.pts),
                              staged<int>(base, st.offs, scan_offsets), shared_n, longest};

@@ -46,26 +46,22 @@ using hsm_plan::plan_match;
 // being captured, so nobody else pays for the question.
 MatchSite match_site(const hsm_ctx* h, int batch, int max_n, int n_bound, bool batched, bool trace, hipStream_t stream) {
   MatchSite s;
+  static_cast<hsm_plan::MatchKnobs&>(s) = h->cfg.match;
   s.batch = batch, s.max_n = max_n, s.n_bound = n_bound;
-  s.exact = wants_exact(h), s.relaxed = h->relaxed, s.layout = h->layout;
-  s.batched = batched, s.trace = trace, s.clock_probe = h->clock_probe != nullptr;
-  s.capturing = h->exact_spec && stream_capturing(stream);
+  s.exact = wants_exact(h), s.relaxed = h->cfg.parity.relaxed, s.layout = h->cfg.layout;
+  s.batched = batched, s.trace = trace, s.clock_probe = h->batch.clock_probe != nullptr;
+  s.capturing = h->cfg.match.exact_spec && stream_capturing(stream);
   s.compute_units = h->compute_units, s.level0_cells = h->levels[0].cells();
-  s.wps_override = h->wps_override, s.bpl_override = h->bpl_override;
-  s.texel_cache = h->texel_cache, s.exact_cached = h->exact_cached;
-  s.exact_chain_wave = h->exact_chain_wave != 0, s.exact_split_tail = h->exact_split_tail != 0;
-  s.exact_dense = h->exact_dense, s.exact_dense_min = h->exact_dense_min;
-  s.exact_spec = h->exact_spec, s.exact_spec1 = h->exact_spec1;
-  s.spb_large = h->spb_large, s.coop_min_beams = h->coop_min_beams, s.coop_skip = h->coop_skip > 0;
+  s.coop_skip = h->single.coop_skip > 0;
   return s;
 }
 MatchSite single_scan_site(const hsm_ctx* h, int n, bool trace = false) { return match_site(h, 1, n, n, false, trace, h->stream); }
 
 // what hsm_last_launch_config / _kernel / _parity report: the plan that was launched
 void record_launch(hsm_ctx* h, const MatchPlan& plan) {
-  for (int i = 0; i < 6; ++i) h->last_cfg[i] = plan.record[i];
-  h->last_kernel = plan.name;
-  h->last_parity = plan.parity;
+  for (int i = 0; i < 6; ++i) h->last.last_cfg[i] = plan.record[i];
+  h->last.last_kernel = plan.name;
+  h->last.last_parity = plan.parity;
 }
 
 // the one-workgroup-per-scan forms of this unit: Family::kExactDense, kSpec (gn_match_dense.h, gn_match_spec.h: `batch` workgroups) and
@@ -76,11 +72,11 @@ int launch_workgroup_form(hsm_ctx* h, MatchParams P, MatchPlan& plan, const Matc
     // graph capture was planned in the literal form, which needs no scratch: a graph never reads a block that an eager launch grows
     // (frees), and nothing is allocated or synchronised while the caller captures.  A ninth stream falls to it here.
     hsm_ctx::SpecScratch* sb = nullptr;
-    for (hsm_ctx::SpecScratch& b : h->spec_scratch)
+    for (hsm_ctx::SpecScratch& b : h->batch.spec_scratch)
       if (b.s == stream) sb = &b;
-    if (!sb && h->spec_scratch.size() < 8) {
-      h->spec_scratch.push_back({stream, {}});
-      sb = &h->spec_scratch.back();
+    if (!sb && h->batch.spec_scratch.size() < 8) {
+      h->batch.spec_scratch.push_back({stream, {}});
+      sb = &h->batch.spec_scratch.back();
     }
     if (!sb) {
       MatchSite literal = site;
@@ -93,7 +89,7 @@ int launch_workgroup_form(hsm_ctx* h, MatchParams P, MatchPlan& plan, const Matc
       if (int rc = sb->d.reserve(need)) return rc;
       P.spec_scratch = (float*)sb->d.p;
       P.spec_stride = (unsigned)stride;
-      P.spec_stats = h->d_spec_stats;
+      P.spec_stats = h->batch.d_spec_stats;
     }
   }
 #define HSM_LAUNCH_WG(KERNEL)                                                              \
@@ -150,7 +146,7 @@ int launch_plan(hsm_ctx* h, MatchParams P, const MatchSite& site, MatchPlan plan
 }
 
 int launch_match(hsm_ctx* h, const MatchParams& P, int max_n, hipStream_t stream) {
-  h->last_sorted = false;  // (the forms that take a permuted batch set it: ensure_batch_perm)
+  h->last.last_sorted = false;  // (the forms that take a permuted batch set it: ensure_batch_perm)
   MatchSite site = match_site(h, P.batch, max_n, P.n_bound, P.begin_world != nullptr, P.trace != nullptr, stream);
   site.exchange = P.xp.world > 0, site.exchange_wait_blocks = P.xp.wait_blocks;
   site.coop_skip = true;  // (the cooperative form is match_single's to launch: here its scan goes to one workgroup)
@@ -166,9 +162,9 @@ void fill_schedule(const hsm_ctx* h, MatchParams& P, bool batched = false) {
   for (int l = 0; l < nl; ++l) P.lv[l] = level_view(h->levels[l], level_factor(l), l == 0 ? 6 : 4);
   P.first_level = nl - 1;
   P.last_level = 0;
-  if (batched && h->sched_level >= 0 && h->sched_level < nl) {
-    P.lv[h->sched_level].gn_steps = h->sched_steps;
-    P.first_level = P.last_level = h->sched_level;
+  if (batched && h->batch.sched_level >= 0 && h->batch.sched_level < nl) {
+    P.lv[h->batch.sched_level].gn_steps = h->batch.sched_steps;
+    P.first_level = P.last_level = h->batch.sched_level;
   }
 }
 
@@ -194,13 +190,13 @@ int hsm_host::match_batch_device_nolock(hsm_ctx* h, int batch, const float* d_be
   // a true bound of the scan lengths, where the host has one: a shared scan's length, or what the caller computed from host offsets
   P.n_bound = d_scan_offsets ? n_bound : shared_n;
   if (xp) P.xp = *xp;
-  h->fused_exchange_done = false;
+  h->batch.fused_exchange_done = false;
   // workgroup -> XCD mapping (beam_sample.h, xcd_block): chunks dealt to the XCDs in turn balance the data-dependent
   // per-scan time; maps whose touched region outgrows the L2s keep one contiguous eighth of the batch per XCD
   const bool outgrows = hsm_plan::level0_outgrows_l2(h->levels[0].cells());
-  P.xcd_chunk = outgrows ? 0 : h->xcd_chunk;
-  P.wg_sync = h->wg_sync >= 0 ? h->wg_sync : (outgrows ? 1 : 0);
-  P.clock_probe = h->clock_probe;
+  P.xcd_chunk = outgrows ? 0 : h->cfg.batch.xcd_chunk;
+  P.wg_sync = h->cfg.batch.wg_sync >= 0 ? h->cfg.batch.wg_sync : (outgrows ? 1 : 0);
+  P.clock_probe = h->batch.clock_probe;
   // per-scan length is only known on the device for CSR input; shared_n doubles as the sizing HINT there
   // (callers pass the typical beams per scan, 0 = unknown).  It only picks the kernel form: every form handles
   // scans longer than the hint (the beams beyond the register/LDS-resident ones stream from memory).
@@ -237,7 +233,7 @@ int hsm_match_batch_device_gather(hsm_ctx* h, int batch, const float* d_begin_wo
   if (int rc = hsm_host::exchange_fused_begin(x, first_row, batch, lag, d_out_all, &f)) return rc;
   if (int rc = match_batch_device_nolock(h, batch, d_begin_world, d_pts_xy, d_scan_offsets, shared_n, d_out_pose, d_out_cov, stream, 0, &f))
     return rc;
-  if (h->fused_exchange_done) {
+  if (h->batch.fused_exchange_done) {
     hsm_host::exchange_fused_commit(x, f);
     return HSM_OK;
   }
@@ -269,8 +265,8 @@ static int score_batch_device_nolock(hsm_ctx* h, int level, int batch, const flo
   });
   HIP_TRY(hipGetLastError());
   if (fs) fs->pending = true;
-  h->last_kernel = "score_batch_kernel";
-  h->last_parity = exact ? HSM_PARITY_EXACT : (h->relaxed ? HSM_PARITY_RELAXED : HSM_PARITY_FAST);
+  h->last.last_kernel = "score_batch_kernel";
+  h->last.last_parity = exact ? HSM_PARITY_EXACT : (h->cfg.parity.relaxed ? HSM_PARITY_RELAXED : HSM_PARITY_FAST);
   return HSM_OK;
 }
 
@@ -427,9 +423,9 @@ static int match_batch_host(hsm_ctx* h, int batch, const float* begin_world, con
     // one 8.6 KB copy + the launch, against three copies, the launch and two more copies of the general path below.
     // (With a score behind the match, its wavefront reads the matched pose back once and writes 4 or 8 bytes; the ranking reads
     // every likelihood once.)
-    if (!h->h_hyp_pinned.holds(L.total)) HIP_TRY(hipStreamSynchronize(h->stream));
-    if (int rc = h->h_hyp_pinned.reserve(L.total, kHalfMore)) return rc;
-    char* hp = h->h_hyp_pinned;
+    if (!h->batch.h_hyp_pinned.holds(L.total)) HIP_TRY(hipStreamSynchronize(h->stream));
+    if (int rc = h->batch.h_hyp_pinned.reserve(L.total, kHalfMore)) return rc;
+    char* hp = h->batch.h_hyp_pinned;
     memcpy(hp, begin_world, b.begin);
     if (out_cov) memcpy(hp + L.cov, out_cov, b.cov);  // in/out: an empty scan leaves the caller's matrices untouched (ScanMatcher.h:68,189)
     if (b.pts) memcpy(hp + L.pts, pts_xy, b.pts);
@@ -508,8 +504,8 @@ int hsm_match_score_batch(hsm_ctx* h, int batch, const float* begin_world, const
 // stream synchronisation takes over, which also surfaces a faulted kernel.  Later work on the stream
 // stays ordered behind the kernel as usual.
 static int wait_single_scan(hsm_ctx* h, unsigned seq) {
-  if (h->spin_wait) {
-    volatile unsigned* flag = reinterpret_cast<volatile unsigned*>(h->h_small + kDoneFlagOff);
+  if (h->cfg.single.spin_wait) {
+    volatile unsigned* flag = reinterpret_cast<volatile unsigned*>(h->single.h_small + kDoneFlagOff);
     const auto t0 = std::chrono::steady_clock::now();
     for (unsigned it = 1;; ++it) {
       if (*flag == seq) {
@@ -526,7 +522,7 @@ static int wait_single_scan(hsm_ctx* h, unsigned seq) {
 
 static int match_single(hsm_ctx* h, MatchParams& P, const float begin_world[3], const float2* pts, int n,
                         float out_pose_world[3], float cov[9], float* trace = nullptr, int trace_steps = 0) {
-  float* hs = h->h_small;
+  float* hs = h->single.h_small;
   float* hs_dev = nullptr;
   HIP_TRY(hipHostGetDevicePointer((void**)&hs_dev, hs, 0));
   P.batch = 1;
@@ -541,18 +537,18 @@ static int match_single(hsm_ctx* h, MatchParams& P, const float begin_world[3], 
   P.out_pose = hs_dev + 3;
   P.out_cov = hs_dev + 6;
   P.trace = trace_steps > 0 ? hs_dev + kTraceOff : nullptr;
-  const unsigned seq = ++h->done_seq;
-  P.done_flag = h->spin_wait ? reinterpret_cast<unsigned*>(hs_dev + kDoneFlagOff) : nullptr;
+  const unsigned seq = ++h->single.done_seq;
+  P.done_flag = h->cfg.single.spin_wait ? reinterpret_cast<unsigned*>(hs_dev + kDoneFlagOff) : nullptr;
   P.done_seq = seq;
   P.err_flag = reinterpret_cast<unsigned*>(hs_dev + kErrFlagOff);
-  P.coop_mute_block = h->coop_mute_block;
-  P.clock_probe = h->clock_probe;
+  P.coop_mute_block = h->single.coop_mute_block;
+  P.clock_probe = h->batch.clock_probe;
   // which form: the site the scan was staged for (stage_scan), now with the trace
   MatchSite site = single_scan_site(h, n, trace_steps > 0);
   site.coop_skip = false;
   MatchPlan plan = plan_match(site);
-  if (plan.family == Family::kCoop && h->coop_skip > 0) {  // backing off after an exchange timeout: this match goes straight to the one-workgroup form
-    --h->coop_skip;
+  if (plan.family == Family::kCoop && h->single.coop_skip > 0) {  // backing off after an exchange timeout: this match goes straight to the one-workgroup form
+    --h->single.coop_skip;
     site.coop_skip = true;
     plan = plan_match(site);
   }
@@ -560,11 +556,11 @@ static int match_single(hsm_ctx* h, MatchParams& P, const float begin_world[3], 
   if (coop_tried) {
     // one dense scan spread over K workgroups of one launch (match_plan.h has the measurements)
     const int K = plan.grid;
-    float* partials = h->d_partials;
-    unsigned* bar_counter = reinterpret_cast<unsigned*>(h->d_partials + 2 * 64 * 12);
-    unsigned bar_base = h->coop_bar_base;
+    float* partials = h->single.d_partials;
+    unsigned* bar_counter = reinterpret_cast<unsigned*>(h->single.d_partials + 2 * 64 * 12);
+    unsigned bar_base = h->single.coop_bar_base;
     void* args[] = {(void*)&P, (void*)&partials, (void*)&bar_counter, (void*)&bar_base};
-    const void* fn = h->layout == kLayoutPlane ? (const void*)gn_match_coop_kernel<kLayoutPlane, false>
+    const void* fn = h->cfg.layout == kLayoutPlane ? (const void*)gn_match_coop_kernel<kLayoutPlane, false>
                                                 : (const void*)gn_match_coop_kernel<kLayoutQuad, false>;
     // The tagged-record exchange (default) has no grid barrier: a workgroup that is not resident yet only delays the others'
     // polls, which are bounded (a record that never arrives turns into an error return, err_flag) -- so it is an ORDINARY
@@ -574,8 +570,8 @@ static int match_single(hsm_ctx* h, MatchParams& P, const float begin_world[3], 
     // handlers when it runs under rocprofv3, profiles/r04/README.md.)  The counter-barrier form (HSM_COOP_TAGGED=0) spins
     // without a bound and keeps the cooperative launch's co-residency guarantee.
     hipError_t le;
-    if (h->coop_tagged) {
-      if (h->layout == kLayoutPlane)
+    if (h->cfg.single.coop_tagged) {
+      if (h->cfg.layout == kLayoutPlane)
         hipLaunchKernelGGL((gn_match_coop_kernel<kLayoutPlane, true>), dim3(K), dim3(256), 0, h->stream, P, partials, bar_counter, bar_base);
       else
         hipLaunchKernelGGL((gn_match_coop_kernel<kLayoutQuad, true>), dim3(K), dim3(256), 0, h->stream, P, partials, bar_counter, bar_base);
@@ -586,7 +582,7 @@ static int match_single(hsm_ctx* h, MatchParams& P, const float begin_world[3], 
     if (le == hipSuccess) {
       unsigned steps = 0;
       for (int l = P.first_level; l >= P.last_level; --l) steps += (unsigned)P.lv[l].gn_steps;
-      h->coop_bar_base += (unsigned)K * steps;  // one arrival per workgroup per GN step
+      h->single.coop_bar_base += (unsigned)K * steps;  // one arrival per workgroup per GN step
       record_launch(h, plan);
     } else {
       // the runtime could not guarantee co-residency (device busy with other work): the one-workgroup
@@ -598,31 +594,31 @@ static int match_single(hsm_ctx* h, MatchParams& P, const float begin_world[3], 
     return rc;
   }
   if (int rc = wait_single_scan(h, seq)) return rc;
-  h->queued_update = false;  // the match kernel was the last thing on `stream`, and it has completed
+  h->upd.queued_update = false;  // the match kernel was the last thing on `stream`, and it has completed
   if (*reinterpret_cast<volatile unsigned*>(hs + kErrFlagOff) == seq) {
     // The multi-workgroup matcher's tagged exchange gave up waiting for a record: its K workgroups were not co-resident for
     // ~2^22 polls (a device shared with another process, or a long kernel of another stream holding the CUs -- an ordinary
     // launch carries no co-residency guarantee).  No pose was written.  The scan is matched again by the one-workgroup
     // matcher, which needs no other workgroup to make progress -- same sums in a different tree, so the caller gets a pose
     // within the fast mode's bar instead of an error (round-4 advisor); hsm_last_launch_config() then reports that form.
-    const unsigned seq2 = ++h->done_seq;
+    const unsigned seq2 = ++h->single.done_seq;
     P.done_seq = seq2;
     if (int rc = launch_match(h, P, n, h->stream)) return rc;
     if (int rc = wait_single_scan(h, seq2)) return rc;
-    ++h->coop_fallbacks;
-    h->coop_backoff = h->coop_backoff ? (h->coop_backoff < 1024 ? 2 * h->coop_backoff : 1024) : 1;
-    h->coop_skip = h->coop_backoff;
+    ++h->single.coop_fallbacks;
+    h->single.coop_backoff = h->single.coop_backoff ? (h->single.coop_backoff < 1024 ? 2 * h->single.coop_backoff : 1024) : 1;
+    h->single.coop_skip = h->single.coop_backoff;
     {
       char b[200];
       snprintf(b, sizeof b, "hsm_match: the multi-workgroup matcher's exchange timed out (device shared or busy); re-ran on one workgroup, "
-               "skipping that form for the next %u dense matches", h->coop_skip);
+               "skipping that form for the next %u dense matches", h->single.coop_skip);
       set_error_text(b);  // (not an error return: the pose is valid; the text tells who asks why a match took long)
     }
     if (*reinterpret_cast<volatile unsigned*>(hs + kErrFlagOff) == seq2)
       return fail(HSM_ERR_HIP, "hsm_match: exchange timeout flagged by the one-workgroup matcher (cannot happen: it has no exchange)");
   }
   else if (coop_tried)
-    h->coop_backoff = 0;  // an exchange completed: the device is ours again
+    h->single.coop_backoff = 0;  // an exchange completed: the device is ours again
   for (int i = 0; i < trace_steps * 12; ++i) trace[i] = hs[kTraceOff + i];
   out_pose_world[0] = hs[3];
   out_pose_world[1] = hs[4];
@@ -636,10 +632,10 @@ static int match_single(hsm_ctx* h, MatchParams& P, const float begin_world[3], 
 // (MatchPlan::reads_scan_once: no H2D copy command in front of the kernel), device memory otherwise
 static int stage_scan(hsm_ctx* h, const float* pts_xy, int n, Buf<float2>& d_buf, const float2** out) {
   if (plan_match(single_scan_site(h, n)).reads_scan_once) {
-    if (int rc = h->h_scan_pinned.reserve(n > 0 ? n : 1, kScanGrowth)) return rc;  // (1: also the empty first scan of a fresh context)
-    if (n > 0) memcpy(h->h_scan_pinned, pts_xy, (size_t)n * sizeof(float2));
+    if (int rc = h->single.h_scan_pinned.reserve(n > 0 ? n : 1, kScanGrowth)) return rc;  // (1: also the empty first scan of a fresh context)
+    if (n > 0) memcpy(h->single.h_scan_pinned, pts_xy, (size_t)n * sizeof(float2));
     float2* dev = nullptr;
-    HIP_TRY(hipHostGetDevicePointer((void**)&dev, h->h_scan_pinned, 0));
+    HIP_TRY(hipHostGetDevicePointer((void**)&dev, h->single.h_scan_pinned, 0));
     *out = dev;
     return HSM_OK;
   }
@@ -657,19 +653,19 @@ static int stage_scan(hsm_ctx* h, const float* pts_xy, int n, Buf<float2>& d_buf
 // issued into A nothing reads it any more.  The staging block is pinned (a pageable hipMemcpyAsync would block the host
 // until everything queued on its stream has completed) and free again for the same reason.
 static int stage_scan_overlapped(hsm_ctx* h, const float* pts_xy, int n, const float2** out) {
-  if (!h->copy_stream) {
-    HIP_TRY(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreateWithFlags(&h->copy_evt, hipEventDisableTiming));
+  if (!h->single.copy_stream) {
+    HIP_TRY(hipStreamCreateWithFlags(&h->single.copy_stream, hipStreamNonBlocking));
+    HIP_TRY(hipEventCreateWithFlags(&h->single.copy_evt, hipEventDisableTiming));
   }
-  std::swap(h->d_retained, h->d_retained_alt);
-  if (int rc = h->d_retained.reserve((size_t)n, kScanGrowth)) return rc;
-  if (!h->h_copy_pinned.holds((size_t)n)) HIP_TRY(hipStreamSynchronize(h->copy_stream));
-  if (int rc = h->h_copy_pinned.reserve((size_t)n, kHalfMore)) return rc;
-  memcpy(h->h_copy_pinned, pts_xy, (size_t)n * sizeof(float2));
-  HIP_TRY(hipMemcpyAsync(h->d_retained, h->h_copy_pinned, (size_t)n * sizeof(float2), hipMemcpyHostToDevice, h->copy_stream));
-  HIP_TRY(hipEventRecord(h->copy_evt, h->copy_stream));
-  HIP_TRY(hipStreamWaitEvent(h->stream, h->copy_evt, 0));
-  *out = h->d_retained;
+  std::swap(h->retained.d_retained, h->single.d_retained_alt);
+  if (int rc = h->retained.d_retained.reserve((size_t)n, kScanGrowth)) return rc;
+  if (!h->single.h_copy_pinned.holds((size_t)n)) HIP_TRY(hipStreamSynchronize(h->single.copy_stream));
+  if (int rc = h->single.h_copy_pinned.reserve((size_t)n, kHalfMore)) return rc;
+  memcpy(h->single.h_copy_pinned, pts_xy, (size_t)n * sizeof(float2));
+  HIP_TRY(hipMemcpyAsync(h->retained.d_retained, h->single.h_copy_pinned, (size_t)n * sizeof(float2), hipMemcpyHostToDevice, h->single.copy_stream));
+  HIP_TRY(hipEventRecord(h->single.copy_evt, h->single.copy_stream));
+  HIP_TRY(hipStreamWaitEvent(h->stream, h->single.copy_evt, 0));
+  *out = h->retained.d_retained;
   return HSM_OK;
 }
 
@@ -677,10 +673,10 @@ static int stage_scan_overlapped(hsm_ctx* h, const float* pts_xy, int n, const f
 // here: one level-0 copy, scaled by 2^-level on use
 static void retain_scan(hsm_ctx* h, const float* pts_xy, int n, const float origo[2]) {
   if (h->levels.size() <= 1) return;
-  h->retained_pts.assign(pts_xy, pts_xy + 2 * (size_t)n);
-  h->retained_origo[0] = origo ? origo[0] : 0.0f;
-  h->retained_origo[1] = origo ? origo[1] : 0.0f;
-  h->retained_valid = true;
+  h->retained.retained_pts.assign(pts_xy, pts_xy + 2 * (size_t)n);
+  h->retained.retained_origo[0] = origo ? origo[0] : 0.0f;
+  h->retained.retained_origo[1] = origo ? origo[1] : 0.0f;
+  h->retained.retained_valid = true;
 }
 
 static int match_impl(hsm_ctx* h, const float begin_world[3], const float* pts_xy, int n, const float origo[2],
@@ -718,15 +714,15 @@ static int match_impl(hsm_ctx* h, const float begin_world[3], const float* pts_x
     // ... and only behind an update that was queued and not waited for (the match + update loop): on an idle stream the
     // extra hop through the copy stream's event costs ~10 us of latency and hides nothing (asking the runtime with
     // hipStreamQuery costs half of what the overlap gains: 0.1855 against 0.179 ms per configs[4] step)
-    if (to_device && h->overlap_upload && n > 0 && h->queued_update) {
+    if (to_device && h->cfg.single.overlap_upload && n > 0 && h->upd.queued_update) {
       if (int rc = stage_scan_overlapped(h, pts_xy, n, &pts)) return rc;
-    } else if (int rc = stage_scan(h, pts_xy, n, h->d_retained, &pts)) {
+    } else if (int rc = stage_scan(h, pts_xy, n, h->retained.d_retained, &pts)) {
       return rc;
     }
   }
   // the device copy of the retained scan is (re)uploaded lazily by the next update when the
   // matcher read the scan from pinned host memory
-  h->d_retained_current = h->levels.size() > 1 && pts == h->d_retained;
+  h->retained.d_retained_current = h->levels.size() > 1 && pts == h->retained.d_retained;
   MatchParams P;
   memset(&P, 0, sizeof P);
   fill_schedule(h, P);
@@ -752,10 +748,10 @@ int hsm_match_level(hsm_ctx* h, int level, const float begin_world[3], const flo
 
 int hsm_match_ingested(hsm_ctx* h, const float begin_world[3], float out_pose_world[3], float cov[9]) {
   if (!h) return fail(HSM_ERR_INVALID, "null context");
-  if (h->ingest_n < 0) return fail(HSM_ERR_INVALID, "hsm_match_ingested: no scan ingested");
+  if (h->ingest.ingest_n < 0) return fail(HSM_ERR_INVALID, "hsm_match_ingested: no scan ingested");
   static const float dummy[2] = {0.0f, 0.0f};
-  const float* hp = h->ingest_n > 0 ? h->h_ingest.data() : dummy;
-  return match_impl(h, begin_world, hp, h->ingest_n, h->ingest_origo, out_pose_world, cov, nullptr, 0, h->d_ingest);
+  const float* hp = h->ingest.ingest_n > 0 ? h->ingest.h_ingest.data() : dummy;
+  return match_impl(h, begin_world, hp, h->ingest.ingest_n, h->ingest.ingest_origo, out_pose_world, cov, nullptr, 0, h->ingest.d_ingest);
 }
 
 int hsm_retain_scan(hsm_ctx* h, const float* pts_xy, int n, const float origo[2]) {
@@ -763,7 +759,7 @@ int hsm_retain_scan(hsm_ctx* h, const float* pts_xy, int n, const float origo[2]
   if (n < 0 || (n > 0 && !pts_xy)) return fail(HSM_ERR_INVALID, "hsm_retain_scan: bad argument");
   std::lock_guard<std::mutex> lk(h->mu);
   retain_scan(h, pts_xy, n, origo);
-  h->d_retained_current = false;  // (never true on a one-level map)
+  h->retained.d_retained_current = false;  // (never true on a one-level map)
   return HSM_OK;
 }
 

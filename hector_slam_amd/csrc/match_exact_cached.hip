@@ -26,14 +26,14 @@ int launch_exact_cached_form(hsm_ctx* h, MatchParams P, const MatchPlan& plan, h
   if (cw) P.xp.world = 0;       // (the chain-wavefront forms do not carry it: the caller queues the stand-alone exchange kernel)
   if (plan.carries_exchange) {  // this launch carries the pose exchange: every scan posts its pose, the workgroups behind the matcher's own unpack
     P.xp.match_blocks = plan.grid - P.xp.wait_blocks;
-    h->fused_exchange_done = true;
+    h->batch.fused_exchange_done = true;
   }
   // workgroup -> XCD mapping: this form runs best with one contiguous eighth of the batch per XCD on every map size (2048^2
   // headline: 57.5 us against 58.3 with the fast form's chunks of 16 workgroups dealt in turn; chunks of 8 / 32: 58.4;
   // profiles/r04/exact_kernel_param_sweep.txt) -- its rounds are paced by barriers and chain jobs, not by how long a scan's
   // gathers take, so the load balancing the chunks buy the fast form is not needed and the compacter L2 footprint wins.
   // env HSM_XCD_CHUNK_EXACT=n restores chunks of n workgroups (of four scans).
-  P.xcd_chunk = h->xcd_chunk_exact;
+  P.xcd_chunk = h->cfg.batch.xcd_chunk_exact;
   const int bpl = plan.bpl, bpc = plan.bpc;
   if (bpl == 5) cw ? launch<5, 5, true>(P, plan, stream) : launch<5>(P, plan, stream);
   else if (bpl == 9) cw ? launch<9, 9, true>(P, plan, stream) : launch<9>(P, plan, stream);

@@ -33,8 +33,26 @@ constexpr int kXbpcCw = 6;
 #endif
 enum Parity { kParityFast = 0, kParityExact = 1, kParityRelaxed = 2 };  // HSM_PARITY_* (capi.h)
 
-// everything the decision reads
-struct MatchSite {
+// the matcher's knobs: fixed when the context is created (settings.h parse_settings, which names each one's env setting), the same
+// for every launch
+struct MatchKnobs {
+  int wps_override = 0;          // hsm_opts::waves_per_scan, else env HSM_WPS: 1, 2, 4, 8, 16 wavefronts per scan, 0 = choose_wps
+  int bpl_override = -1;         // 0 = force the memory loop (env HSM_BPL=0), -1 = auto
+  bool texel_cache = true;       // env HSM_TEXEL_CACHE=0: plain gn_match_kernel for throughput launches too
+  bool exact_cached = true;      // env HSM_EXACT_CACHED=0: exact-mode batches take the one-wavefront-per-scan exact form (gn_match_kernel) instead of gn_match_exact.h's
+  bool exact_chain_wave = true;  // env HSM_EXACT_CHAIN_WAVE=0: no chain-only wavefront, teams of wavefronts for batches below 4096 scans (rounds 3-4)
+  bool exact_split_tail = true;  // env HSM_EXACT_SPLIT_TAIL=0: one launch however the batch divides into generations
+  bool exact_dense = true;       // env HSM_EXACT_DENSE=0: dense scans in exact order keep the 16-wavefront team form (gn_match_kernel<16,...,EXACT>)
+  int exact_dense_min = 4096;    // env HSM_EXACT_DENSE_MIN: beams from which the producers-ahead-of-the-chain form takes over
+  bool exact_spec = false;       // env HSM_EXACT_SPEC=1: one-workgroup-per-scan launches in exact order take the speculative-carry form (gn_match_spec.h:
+                                 // the same bits; measured SLOWER than the literal chains on one CU -- DESIGN.md 8 -- hence opt-in)
+  bool exact_spec1 = false;      // env HSM_EXACT_SPEC1=1: ONE scan of up to 2048 beams (hsm_match) in exact order takes the on-chip speculative-carry form
+  int spb_large = 8;             // env HSM_SPB_LARGE=4|8: scans per workgroup of the texel-cache matcher on maps > 2^23 cells
+  int coop_min_beams = 4096;     // single scans at least this long take the multi-workgroup matcher (env HSM_COOP_MIN)
+};
+
+// everything the decision reads: the knobs and the launch's own shape
+struct MatchSite : MatchKnobs {
   int batch = 1;        // scans of the launch
   int max_n = 0;        // beams of the longest scan, or the caller's hint of it
   int n_bound = 0;      // a TRUE bound of the scan lengths where the host has one, else 0
@@ -49,12 +67,6 @@ struct MatchSite {
   int exchange_wait_blocks = 0;  // ... with this many workgroups behind the matcher's own
   int compute_units = 256;
   size_t level0_cells = 0;
-  // the knobs (hsm_create)
-  int wps_override = 0, bpl_override = -1;
-  bool texel_cache = true, exact_cached = true, exact_chain_wave = true, exact_split_tail = true, exact_dense = true;
-  int exact_dense_min = 4096;
-  bool exact_spec = false, exact_spec1 = false;
-  int spb_large = 8, coop_min_beams = 4096;
   bool coop_skip = false;  // the multi-workgroup form is backing off after an exchange timeout, or could not be launched
 };
 

@@ -139,34 +139,34 @@ int launch_batch_order(hsm_ctx* h, const float* begin_world, int batch, int* per
 }
 
 int ensure_batch_perm(hsm_ctx* h, MatchParams& P, hipStream_t stream) {
-  if (P.perm != nullptr || P.begin_world == nullptr || P.batch < h->batch_order_min) return HSM_OK;
-  const bool automatic = h->batch_order == HSM_ORDER_AUTO;
-  if (h->batch_order != HSM_ORDER_MORTON && !(automatic && hsm_plan::level0_outgrows_l2(h->levels[0].cells()))) return HSM_OK;
+  if (P.perm != nullptr || P.begin_world == nullptr || P.batch < h->cfg.batch.batch_order_min) return HSM_OK;
+  const bool automatic = h->cfg.batch.batch_order == HSM_ORDER_AUTO;
+  if (h->cfg.batch.batch_order != HSM_ORDER_MORTON && !(automatic && hsm_plan::level0_outgrows_l2(h->levels[0].cells()))) return HSM_OK;
   // A launch into a graph capture keeps the caller's order and leaves the stream's permutation as it is.  Its sort would run at
   // the replays only, while the host state below would claim it had run now (an eager launch of that size would then reuse a
   // buffer that holds another batch's permutation); and a graph that read the buffer would read it after an eager launch had
   // rewritten it or, growing it, freed it.
   if (stream_capturing(stream)) return HSM_OK;
   hsm_ctx::PermBuf* pb = nullptr;
-  for (hsm_ctx::PermBuf& b : h->perm_bufs)
+  for (hsm_ctx::PermBuf& b : h->batch.perm_bufs)
     if (b.s == stream) pb = &b;
   if (!pb) {
-    if (h->perm_bufs.size() >= 8) return HSM_OK;  // (a ninth stream keeps the caller's order)
-    h->perm_bufs.push_back({stream, {}, 0, 0});
-    pb = &h->perm_bufs.back();
+    if (h->batch.perm_bufs.size() >= 8) return HSM_OK;  // (a ninth stream keeps the caller's order)
+    h->batch.perm_bufs.push_back({stream, {}, 0, 0});
+    pb = &h->batch.perm_bufs.back();
   }
   if (!pb->d.holds((size_t)P.batch)) pb->batch = 0;  // (the permutation goes with the block; the free waits for launches that read it)
   if (int rc = pb->d.reserve(((size_t)P.batch + 4095) / 4096 * 4096)) return rc;  // multiples of 4096 ints
-  if (pb->batch == P.batch && pb->used < h->batch_order_refresh) {  // the permutation of an earlier launch of this stream
+  if (pb->batch == P.batch && pb->used < h->cfg.batch.batch_order_refresh) {  // the permutation of an earlier launch of this stream
     ++pb->used;
     P.perm = pb->d;
-    h->last_sorted = true;
+    h->last.last_sorted = true;
     return HSM_OK;
   }
   if (int rc = launch_batch_order(h, P.begin_world, P.batch, pb->d, automatic, stream)) return rc;
   pb->batch = P.batch, pb->used = 1;
   P.perm = pb->d;
-  h->last_sorted = true;
+  h->last.last_sorted = true;
   return HSM_OK;
 }
 

@@ -23,11 +23,11 @@ int hsm_occupancy_grid(hsm_ctx* h, int level, signed char* out) {
   std::lock_guard<std::mutex> lk(h->mu);
   if (int rc = select_device(h)) return rc;
   Level& L = h->levels[level];
-  if (int rc = h->d_occ.reserve(L.cells())) return rc;
+  if (int rc = h->occ.d_occ.reserve(L.cells())) return rc;
   hipLaunchKernelGGL(occupancy_grid_kernel, dim3(grid_for(L.cells() / 4)), dim3(256), 0, h->stream, L.d_logodds,
-                     L.cells(), h->d_occ);
+                     L.cells(), h->occ.d_occ);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(out, h->d_occ, L.cells(), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(out, h->occ.d_occ, L.cells(), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   return HSM_OK;
 }
@@ -55,10 +55,10 @@ static int queue_occupancy_changes(hsm_ctx* h, int level, signed char* d_grid, i
   OccupancyPrepParams A;
   memset(&A, 0, sizeof A);
   A.nlev = (int)h->levels.size();
-  A.pub_boxes = h->d_pub_boxes;
+  A.pub_boxes = h->occ.d_pub_boxes;
   A.host_box[level] = make_int4(L.pub[0], L.pub[1], L.pub[2], L.pub[3]);
   A.dims[level] = make_int2(L.sx, L.sy);
-  A.box_out[level] = h->d_pub_boxes + (kMaxLevels + level) * 4;
+  A.box_out[level] = h->occ.d_pub_boxes + (kMaxLevels + level) * 4;
   A.bbox_out[level] = d_out_bbox;
   hipLaunchKernelGGL(occupancy_prep_kernel, dim3(1), dim3(64), 0, h->stream, A);
   HIP_TRY(hipGetLastError());
@@ -75,7 +75,7 @@ int hsm_occupancy_grid_device(hsm_ctx* h, int level, signed char* d_out, void* s
   if (int rc = occupancy_export_refusals(h, d_out, s, "hsm_occupancy_grid_device")) return rc;
   if (int rc = select_device(h)) return rc;
   if (int rc = wait_for_caller_inputs(h, s)) return rc;
-  if (int rc = launch_occupancy_box(h, h->levels[level], h->d_pub_boxes + (2 * kMaxLevels + level) * 4, d_out)) return rc;
+  if (int rc = launch_occupancy_box(h, h->levels[level], h->occ.d_pub_boxes + (2 * kMaxLevels + level) * 4, d_out)) return rc;
   return slam_caller_waits(h, s);
 }
 
@@ -97,14 +97,14 @@ int hsm_occupancy_changes(hsm_ctx* h, int level, signed char* grid, int bbox[4])
   std::lock_guard<std::mutex> lk(h->mu);
   if (int rc = select_device(h)) return rc;
   Level& L = h->levels[level];
-  if (int rc = h->d_occ.reserve(L.cells())) return rc;
+  if (int rc = h->occ.d_occ.reserve(L.cells())) return rc;
   const int* d_box = nullptr;
-  if (int rc = queue_occupancy_changes(h, level, h->d_occ, nullptr, &d_box)) return rc;
+  if (int rc = queue_occupancy_changes(h, level, h->occ.d_occ, nullptr, &d_box)) return rc;
   HIP_TRY(hipMemcpyAsync(bbox, d_box, 4 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   if (bbox[2] < bbox[0]) return HSM_OK;  // nothing changed: `grid` stays as it is
   const size_t first = (size_t)bbox[1] * L.sx + bbox[0];
-  HIP_TRY(hipMemcpy2DAsync(grid + first, (size_t)L.sx, h->d_occ + first, (size_t)L.sx, (size_t)(bbox[2] - bbox[0] + 1),
+  HIP_TRY(hipMemcpy2DAsync(grid + first, (size_t)L.sx, h->occ.d_occ + first, (size_t)L.sx, (size_t)(bbox[2] - bbox[0] + 1),
                            (size_t)(bbox[3] - bbox[1] + 1), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   return HSM_OK;

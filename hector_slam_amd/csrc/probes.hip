@@ -105,7 +105,7 @@ int hsm_world_coords_pose(const hsm_ctx* h, int level, const float m[3], float w
 int hsm_update_index(const hsm_ctx* h, int level) {
   if (valid_level(h, level)) return -1;
   std::lock_guard<std::mutex> lk(h->mu);  // read by the facade's publisher thread while the scan thread updates
-  if (h->gate_outstanding)  // gated updates since the last look: wait for them and fetch their count
+  if (h->upd.gate_outstanding)  // gated updates since the last look: wait for them and fetch their count
     if (fold_gate_counters(const_cast<hsm_ctx*>(h))) return -1;
   return h->levels[level].last_update_index;
 }
@@ -126,9 +126,9 @@ int hsm_upload_level(hsm_ctx* h, int level, const float* logodds, const int* upd
   std::lock_guard<std::mutex> lk(h->mu);
   if (int rc = select_device(h)) return rc;
   Level& L = h->levels[level];
-  if (h->upd_boxes_outstanding)
+  if (h->upd.upd_boxes_outstanding)
     if (int rc = merge_device_boxes(h)) return rc;
-  if (h->gate_outstanding)
+  if (h->upd.gate_outstanding)
     if (int rc = fold_gate_counters(h)) return rc;
   if (int rc = order_after_foreign_match(h)) return rc;
   HIP_TRY(hipStreamSynchronize(h->stream));
@@ -177,10 +177,10 @@ int hsm_download_cells(hsm_ctx* h, int level, int x0, int y0, int x1, int y1, vo
 }
 int hsm_last_update_bbox(const hsm_ctx* h, int level, int bbox[4]) {
   if (int rc = valid_level(h, level)) return rc;
-  if (h->upd_boxes_outstanding) {  // a device-side update since the last look: wait for it and fetch its boxes
+  if (h->upd.upd_boxes_outstanding) {  // a device-side update since the last look: wait for it and fetch its boxes
     hsm_ctx* m = const_cast<hsm_ctx*>(h);
     std::lock_guard<std::mutex> lk(m->mu);
-    if (m->upd_boxes_outstanding)
+    if (m->upd.upd_boxes_outstanding)
       if (int rc = merge_device_boxes(m)) return rc;
   }
   for (int i = 0; i < 4; ++i) bbox[i] = h->levels[level].bbox[i];
@@ -190,7 +190,7 @@ int hsm_take_dirty_bbox(hsm_ctx* h, int level, int bbox[4]) {
   if (int rc = valid_level(h, level)) return rc;
   if (!bbox) return fail(HSM_ERR_INVALID, "hsm_take_dirty_bbox: bbox is null");
   std::lock_guard<std::mutex> lk(h->mu);
-  if (h->upd_boxes_outstanding)
+  if (h->upd.upd_boxes_outstanding)
     if (int rc = merge_device_boxes(h)) return rc;
   Level& L = h->levels[level];
   for (int i = 0; i < 4; ++i) bbox[i] = L.dirty[i];
@@ -217,16 +217,16 @@ int hsm_hessian_derivs(hsm_ctx* h, int level, const float pose_map[3], const flo
   if (int rc = h->d_scan.reserve((size_t)n, kScanGrowth)) return rc;
   if (n > 0) HIP_TRY(hipMemcpyAsync(h->d_scan, pts, (size_t)n * sizeof(float2), hipMemcpyHostToDevice, h->stream));
   const LevelView v = level_view(h->levels[level], 1.0f, 1);
-  float* d_out = h->d_small + 16;
+  float* d_out = h->single.d_small + 16;
   with_sampler_form(h, [&](auto lay, auto ex) {
     hipLaunchKernelGGL((gn_eval_kernel<lay(), ex()>), dim3(1), dim3(1024), 0, h->stream, v, h->d_scan, n,
                        pose_map[0], pose_map[1], pose_map[2], d_out);
   });
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(h->h_small + 16, d_out, 12 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(h->single.h_small + 16, d_out, 12 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
-  for (int i = 0; i < 9; ++i) H[i] = h->h_small[16 + i];
-  for (int i = 0; i < 3; ++i) dTr[i] = h->h_small[25 + i];
+  for (int i = 0; i < 9; ++i) H[i] = h->single.h_small[16 + i];
+  for (int i = 0; i < 3; ++i) dTr[i] = h->single.h_small[25 + i];
   return HSM_OK;
 }
 
@@ -256,15 +256,15 @@ int hsm_debug_set_coop_barrier(hsm_ctx* h, unsigned value) {
   std::lock_guard<std::mutex> lk(h->mu);
   if (int rc = select_device(h)) return rc;
   HIP_TRY(hipStreamSynchronize(h->stream));
-  HIP_TRY(hipMemcpy(h->d_partials + 2 * 64 * 12, &value, sizeof value, hipMemcpyHostToDevice));
-  h->coop_bar_base = value;
+  HIP_TRY(hipMemcpy(h->single.d_partials + 2 * 64 * 12, &value, sizeof value, hipMemcpyHostToDevice));
+  h->single.coop_bar_base = value;
   return HSM_OK;
 }
 
 int hsm_debug_set_coop_mute(hsm_ctx* h, int block_plus_one) {
   if (!h) return fail(HSM_ERR_INVALID, "null context");
   std::lock_guard<std::mutex> lk(h->mu);
-  h->coop_mute_block = block_plus_one;
+  h->single.coop_mute_block = block_plus_one;
   return HSM_OK;
 }
 
@@ -273,8 +273,8 @@ int hsm_debug_set_schedule(hsm_ctx* h, int level, int gn_steps) {
   if (level >= (int)h->levels.size() || (level >= 0 && gn_steps < 1))
     return fail(HSM_ERR_INVALID, "hsm_debug_set_schedule: level out of range or gn_steps < 1");
   std::lock_guard<std::mutex> lk(h->mu);
-  h->sched_level = level < 0 ? -1 : level;
-  h->sched_steps = level < 0 ? 0 : gn_steps;
+  h->batch.sched_level = level < 0 ? -1 : level;
+  h->batch.sched_steps = level < 0 ? 0 : gn_steps;
   return HSM_OK;
 }
 
@@ -283,7 +283,7 @@ int hsm_debug_batch_order(hsm_ctx* h, int batch, const float* d_begin_world, int
   if (batch < 1 || !d_begin_world || !d_perm_out) return fail(HSM_ERR_INVALID, "hsm_debug_batch_order: bad argument");
   std::lock_guard<std::mutex> lk(h->mu);
   if (int rc = select_device(h)) return rc;
-  return launch_batch_order(h, d_begin_world, batch, d_perm_out, h->batch_order == HSM_ORDER_AUTO, (hipStream_t)stream);
+  return launch_batch_order(h, d_begin_world, batch, d_perm_out, h->cfg.batch.batch_order == HSM_ORDER_AUTO, (hipStream_t)stream);
 }
 
 int hsm_debug_spec_stats(hsm_ctx* h, int enable, unsigned long long out[4]) {
@@ -293,13 +293,13 @@ int hsm_debug_spec_stats(hsm_ctx* h, int enable, unsigned long long out[4]) {
   HIP_TRY(hipStreamSynchronize(h->stream));
   if (out) {
     out[0] = out[1] = out[2] = out[3] = 0;
-    if (h->d_spec_stats) HIP_TRY(hipMemcpy(out, h->d_spec_stats, sizeof(SpecStats), hipMemcpyDeviceToHost));
+    if (h->batch.d_spec_stats) HIP_TRY(hipMemcpy(out, h->batch.d_spec_stats, sizeof(SpecStats), hipMemcpyDeviceToHost));
   }
-  if (enable && !h->d_spec_stats) HIP_TRY(hipMalloc((void**)&h->d_spec_stats, sizeof(SpecStats)));
-  if (h->d_spec_stats) HIP_TRY(hipMemset(h->d_spec_stats, 0, sizeof(SpecStats)));
-  if (!enable && h->d_spec_stats) {
-    HIP_TRY(hipFree(h->d_spec_stats));
-    h->d_spec_stats = nullptr;
+  if (enable && !h->batch.d_spec_stats) HIP_TRY(hipMalloc((void**)&h->batch.d_spec_stats, sizeof(SpecStats)));
+  if (h->batch.d_spec_stats) HIP_TRY(hipMemset(h->batch.d_spec_stats, 0, sizeof(SpecStats)));
+  if (!enable && h->batch.d_spec_stats) {
+    HIP_TRY(hipFree(h->batch.d_spec_stats));
+    h->batch.d_spec_stats = nullptr;
   }
   return HSM_OK;
 }
@@ -307,7 +307,7 @@ int hsm_debug_spec_stats(hsm_ctx* h, int enable, unsigned long long out[4]) {
 int hsm_debug_coop_fallbacks(hsm_ctx* h) {
   if (!h) return 0;
   std::lock_guard<std::mutex> lk(h->mu);
-  return (int)h->coop_fallbacks;
+  return (int)h->single.coop_fallbacks;
 }
 
 int hsm_debug_marks_nonzero(hsm_ctx* h, int level, unsigned long long out[2]) {

@@ -47,7 +47,7 @@ RayGrid level_ray_grid(const Level& L) {
 constexpr int kCastLaneMinBeams = 32;
 
 bool cast_lane_per_beam(const hsm_ctx* h, int n) {
-  if (h->cast_form >= 0) return h->cast_form == 1;
+  if (h->cfg.forms.cast_form >= 0) return h->cfg.forms.cast_form == 1;
   return n >= kCastLaneMinBeams;
 }
 
@@ -65,11 +65,11 @@ int cast_scans_launch(hsm_ctx* h, int level, int batch, const float* d_poses, co
   if (cast_lane_per_beam(h, n)) {
     const long long waves = (long long)batch * ((n + 63) / 64);
     hipLaunchKernelGGL(cast_scans_lane_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, P);
-    h->last_kernel = "cast_scans_lane_kernel";
+    h->last.last_kernel = "cast_scans_lane_kernel";
   } else {
     const long long waves = (long long)batch * n;
     hipLaunchKernelGGL(cast_scans_wave_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, P);
-    h->last_kernel = "cast_scans_wave_kernel";
+    h->last.last_kernel = "cast_scans_wave_kernel";
   }
   HIP_TRY(hipGetLastError());
   return HSM_OK;
@@ -138,7 +138,7 @@ int hsm_ray_distances_device(hsm_ctx* h, int level, float origin_x, float origin
   hipLaunchKernelGGL(ray_distance_kernel<true>, dim3((n + 3) / 4), dim3(256), 0, s, P);
   HIP_TRY(hipGetLastError());
   if (fs) fs->pending = true;
-  h->last_kernel = "ray_distance_kernel";
+  h->last.last_kernel = "ray_distance_kernel";
   return HSM_OK;
 }
 

@@ -29,7 +29,7 @@ namespace {
 constexpr long long kWindowLaneMin = 1ll << 16;
 
 bool window_lane_form(const hsm_ctx* h, long long W) {
-  if (h->window_form >= 0) return h->window_form == 1;
+  if (h->cfg.forms.window_form >= 0) return h->cfg.forms.window_form == 1;
   return W >= kWindowLaneMin;
 }
 
@@ -72,7 +72,7 @@ int score_window_launch(hsm_ctx* h, int level, const float* d_center, const Wind
   P.out_residual = d_out_res;
   const bool lane = window_lane_form(h, W);
   const unsigned grid = lane ? (unsigned)(((long long)W + 255) / 256) : (unsigned)(((long long)W + 3) / 4);
-  if (h->layout == kLayoutPlane) {
+  if (h->cfg.layout == kLayoutPlane) {
     if (lane) hipLaunchKernelGGL((score_window_lane_kernel<kLayoutPlane>), dim3(grid), dim3(256), 0, s, v, P);
     else hipLaunchKernelGGL((score_window_wave_kernel<kLayoutPlane>), dim3(grid), dim3(256), 0, s, v, P);
   } else {
@@ -81,8 +81,8 @@ int score_window_launch(hsm_ctx* h, int level, const float* d_center, const Wind
   }
   HIP_TRY(hipGetLastError());
   if (fs) fs->pending = true;
-  h->last_kernel = lane ? "score_window_lane_kernel" : "score_window_wave_kernel";
-  h->last_parity = HSM_PARITY_EXACT;  // a lane (or lane 0) owns the whole chain: the reference's order in every mode
+  h->last.last_kernel = lane ? "score_window_lane_kernel" : "score_window_wave_kernel";
+  h->last.last_parity = HSM_PARITY_EXACT;  // a lane (or lane 0) owns the whole chain: the reference's order in every mode
   return HSM_OK;
 }
 
