@@ -109,6 +109,10 @@ SIGNATURES = {
     "hsm_score_batch_device": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "hsm_select_best_device": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "hsm_match_score_batch_device": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    "hsm_covariance_batch_device": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "hsm_match_cov_batch_device": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp,
+                                        _vp]),
+    "hsm_covariance_batch": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "hsm_score_window_device": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "hsm_score_window": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "hsm_window_poses_device": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
@@ -684,6 +688,38 @@ class MapRepMultiMap:
             self._h, batch, d_begin or None, d_pts or None, d_offsets or None, shared_n, d_out_pose or None, d_out_cov or None,
             score_level, d_out_likelihood or None, d_out_residual or None, groups, d_group_offsets or None, group_size,
             d_out_index or None, d_out_score or None, d_out_best_pose or None, stream or None), "hsm_match_score_batch_device")
+
+    def covariance_batch_device(self, level, batch, d_poses_world, d_pts, d_offsets, shared_n, d_out_cov_world=0, d_out_cov_map=0,
+                                d_out_lh7=0, d_out_likelihood=0, stream=0):
+        """Raw device pointers (ints), asynchronous on ``stream``: the sigma-point covariance (world [B,9] / map [B,9], column major),
+        the seven sigma-point likelihoods [B,7] and the pose's own likelihood [B] of ``batch`` WORLD poses on ``level``."""
+        _check(self._lib.hsm_covariance_batch_device(self._h, level, batch, d_poses_world or None, d_pts or None, d_offsets or None,
+                                                     shared_n, d_out_cov_world or None, d_out_cov_map or None, d_out_lh7 or None,
+                                                     d_out_likelihood or None, stream or None), "hsm_covariance_batch_device")
+
+    def match_cov_batch_device(self, batch, d_begin, d_pts, d_offsets, shared_n, d_out_pose, d_out_cov, cov_level, d_out_cov_world=0,
+                               d_out_cov_map=0, d_out_lh7=0, d_out_likelihood=0, groups=0, d_group_offsets=0, group_size=0,
+                               d_out_index=0, d_out_score=0, d_out_best_pose=0, stream=0):
+        """match_batch_device -> covariance_batch_device -> (groups > 0) select_best_device as one call on ``stream``."""
+        _check(self._lib.hsm_match_cov_batch_device(
+            self._h, batch, d_begin or None, d_pts or None, d_offsets or None, shared_n, d_out_pose or None, d_out_cov or None,
+            cov_level, d_out_cov_world or None, d_out_cov_map or None, d_out_lh7 or None, d_out_likelihood or None, groups,
+            d_group_offsets or None, group_size, d_out_index or None, d_out_score or None, d_out_best_pose or None, stream or None),
+            "hsm_match_cov_batch_device")
+
+    def covariance_batch(self, level, poses_world, pts, offsets=None):
+        """hsm_covariance_batch: host arrays in and out; ``offsets`` None = every pose against the one scan ``pts``.
+        -> (cov_world [B,9], cov_map [B,9], likelihoods [B,7], likelihood [B]); matrices column major"""
+        w = np.ascontiguousarray(poses_world, np.float32).reshape(-1, 3)
+        a, p, n = _pts(pts)
+        offs = None if offsets is None else np.ascontiguousarray(offsets, np.int32)
+        B = w.shape[0]
+        cw, cm, l7, lh = (np.zeros((B, 9), np.float32), np.zeros((B, 9), np.float32), np.zeros((B, 7), np.float32),
+                          np.zeros(B, np.float32))
+        _check(self._lib.hsm_covariance_batch(self._h, level, B, w.ctypes.data, p, None if offs is None else offs.ctypes.data,
+                                              n if offs is None else 0, cw.ctypes.data, cm.ctypes.data, l7.ctypes.data,
+                                              lh.ctypes.data), "hsm_covariance_batch")
+        return cw, cm, l7, lh
 
     def update_by_scans_device(self, count, d_poses_world, d_pts, d_offsets, shared_n, max_beams=0, origo=None, stream=0):
         """Raw device pointers (ints): integrate ``count`` posed scans in order, queued on the context's stream behind what

@@ -1,6 +1,6 @@
 // gn_step.h -- what every form of the matcher builds a Gauss-Newton step from, on top of the sampler (beam_sample.h): the nine
 // per-beam products and their accumulators, the two summation orders (the reference's chains through LDS; wavefront and team
-// all-reduces), the 3x3 solve, the residual chain and the (score, index) order of the scoring kernels, and how a launch says it
+// all-reduces), the 3x3 solve, the residual chain, the sigma-point statistics and the (score, index) order of the scoring kernels, and how a launch says it
 // is done or takes part in the pose exchange.  Included by the matcher kernel headers (gn_match_teams.h, gn_match_cached.h,
 // gn_match_dense.h, gn_match_exact.h, gn_match_spec.h) and by score_kernels.h, window_kernels.h and probe_kernels.h.  No kernel
 // is defined here.
@@ -370,6 +370,55 @@ __device__ __forceinline__ float exact_residual_round(float funval, float* __res
     }
   }
   return run;
+}
+
+// ---- the sigma-point covariance estimate (OccGridMapUtil::getCovarianceForPose, OccGridMapUtil.h:106-160) ----------------------
+// the seven sigma points around a MAP-frame pose, in the source's order (:119-125): x +- 1.5 cells, y +- 1.5 cells, angle +- 0.05,
+// the pose itself.  (Host-callable as well: tests/cpp/sigma_stats_check.cpp holds both functions to the numpy restatement.)
+__host__ __device__ __forceinline__ void sigma_points(float x, float y, float ang, float sp[7][3]) {
+  const float deltaTransX = 1.5f, deltaTransY = 1.5f, deltaAng = 0.05f;
+  const float s[7][3] = {{x + deltaTransX, y, ang}, {x - deltaTransX, y, ang}, {x, y + deltaTransY, ang},
+                         {x, y - deltaTransY, ang}, {x, y, ang + deltaAng},    {x, y, ang - deltaAng}, {x, y, ang}};
+  for (int i = 0; i < 7; ++i)
+    for (int r = 0; r < 3; ++r) sp[i][r] = s[i][r];
+}
+
+// The 7-term statistics in the source's order (:138-154) and getCovMatrixWorldCoords (:162-188): the seven likelihoods `lh`
+// weight a sample mean and a 3x3 sample covariance of the sigma points.  One thread; the three outputs are one pose's rows
+// (7, 9 and 9 floats, the matrices column major), each may be null.
+__host__ __device__ __forceinline__ void sigma_point_statistics(const float sp[7][3], const float* lh, float cell_length,
+                                                                float* out_lh7, float* out_cov_map, float* out_cov_world) {
+  // likelihoods.sum(): fixed-size 7-vector, unrolled halves (0..2) + (3..6)
+  const float sum = ((lh[0] + (lh[1] + lh[2])) + ((lh[3] + lh[4]) + (lh[5] + lh[6])));
+  const float invLhNormalizer = 1 / sum;
+  float mean[3] = {0.0f, 0.0f, 0.0f};
+  for (int i = 0; i < 7; ++i)
+    for (int r = 0; r < 3; ++r) mean[r] += sp[i][r] * lh[i];
+  for (int r = 0; r < 3; ++r) mean[r] *= invLhNormalizer;
+  float cov[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // column major
+  for (int i = 0; i < 7; ++i) {
+    const float d[3] = {sp[i][0] - mean[0], sp[i][1] - mean[1], sp[i][2] - mean[2]};
+    const float wgt = lh[i] * invLhNormalizer;
+    for (int c = 0; c < 3; ++c)
+      for (int r = 0; r < 3; ++r) cov[c * 3 + r] += wgt * (d[r] * d[c]);
+  }
+  if (out_lh7)
+    for (int i = 0; i < 7; ++i) out_lh7[i] = lh[i];
+  if (out_cov_map)
+    for (int i = 0; i < 9; ++i) out_cov_map[i] = cov[i];
+  if (out_cov_world) {
+    const float scaleTrans = cell_length, scaleTransSq = scaleTrans * scaleTrans;
+    float* W = out_cov_world;  // (r,c) at c*3+r
+    W[0] = cov[0] * scaleTransSq;
+    W[4] = cov[4] * scaleTransSq;
+    W[1] = cov[1] * scaleTransSq;  // (1,0)
+    W[3] = W[1];
+    W[2] = cov[2] * scaleTrans;  // (2,0)
+    W[6] = W[2];
+    W[5] = cov[5] * scaleTrans;  // (2,1)
+    W[7] = W[5];
+    W[8] = cov[8];
+  }
 }
 
 // ---- ranking inside groups of hypotheses ------------------------------------------------------------------------------------

@@ -3,7 +3,8 @@
 // The units, and behind "=>" the members of hsm_ctx each one owns (tests/test_ctx_ownership.py has who else reaches into them):
 //   hector_mi355.hip        the core: the context's life cycle and settings, the error text, the views of a level and the stream
 //                           hand-over around map updates: host code only, no kernel in its include closure  => cfg, order
-//   match.hip               the matcher's front door: every match, score and select entry, the plan of a launch and its record,
+//   match.hip               the matcher's front door: every match, score, batch-covariance (hsm_covariance_batch*,
+//                           hsm_match_cov_batch_device) and select entry, the plan of a launch and its record,
 //                           the single-scan path, and the one-workgroup-per-scan and multi-workgroup matcher forms
 //                           (gn_match_dense.h, gn_match_spec.h, score_kernels.h); the other forms it dispatches to the two
 //                           match_* units below  => single, batch, last, retained

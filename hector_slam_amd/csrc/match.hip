@@ -1,4 +1,4 @@
-// match.hip -- the matcher's front door: every hsm_match* entry, the score, select and match-score entries, the plan of a launch
+// match.hip -- the matcher's front door: every hsm_match* entry, the score, covariance, select and match-score entries, the plan of a launch
 // (match_plan.h) and its record, and the single-scan path with its staging.  Kernels launched here: the one-workgroup-per-scan and
 // multi-workgroup forms of gn_match_dense.h and gn_match_spec.h, and score_kernels.h; the batch / team forms are dispatched to
 // match_exact_cached.hip and match_teams.hip through the launch entries hsm_ctx.h declares, whose kernels this unit does not see.
@@ -279,6 +279,58 @@ int hsm_score_batch_device(hsm_ctx* h, int level, int batch, const float* d_pose
                                    d_out_residual, stream);
 }
 
+// The covariance estimate behind a batched match: B (world pose, scan) pairs on `level` in one launch of covariance_batch_kernel
+// (score_kernels.h).  Built like the score: a reader of the map (order_map_reader), no workspace, no state.  `who`: the entry the
+// caller used, for the error text.
+static int covariance_batch_check(const hsm_ctx* h, int level, int batch, const float* d_poses_world, const float* d_pts_xy,
+                                  const int* d_scan_offsets, int shared_n, const float* d_out_cov_world, const float* d_out_cov_map,
+                                  const float* d_out_lh7, const float* d_out_likelihood, const char* who) {
+  if (!h) return fail_at(HSM_ERR_INVALID, who, ": null context");
+  if (level < 0 || level >= (int)h->levels.size()) return fail_at(HSM_ERR_INVALID, who, ": level out of range");
+  if (batch < 0 || (!d_out_cov_world && !d_out_cov_map && !d_out_lh7 && !d_out_likelihood) || (!d_scan_offsets && shared_n < 0) ||
+      (batch > 0 && (!d_poses_world || (!d_pts_xy && !d_scan_offsets && shared_n > 0))))
+    return fail_at(HSM_ERR_INVALID, who, ": bad argument");
+  return HSM_OK;
+}
+
+static int covariance_batch_device_nolock(hsm_ctx* h, int level, int batch, const float* d_poses_world, const float* d_pts_xy,
+                                          const int* d_scan_offsets, int shared_n, float* d_out_cov_world, float* d_out_cov_map,
+                                          float* d_out_lh7, float* d_out_likelihood, void* stream,
+                                          const char* who = "hsm_covariance_batch_device") {
+  if (int rc = covariance_batch_check(h, level, batch, d_poses_world, d_pts_xy, d_scan_offsets, shared_n, d_out_cov_world,
+                                      d_out_cov_map, d_out_lh7, d_out_likelihood, who))
+    return rc;
+  if (batch == 0) return HSM_OK;
+  if (int rc = select_device(h)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  hsm_ctx::ForeignStream* fs = nullptr;
+  if (int rc = order_map_reader(h, s, who, &fs)) return rc;
+  const float factor = (float)(1.0 / pow(2.0, (double)level));
+  const Level& Lv = h->levels[level];
+  const LevelView v = level_view(Lv, factor, 1);
+  const bool exact = wants_exact(h);
+  const int grid = (batch + 3) / 4;
+  with_sampler_form(h, [&](auto lay, auto ex) {
+    hipLaunchKernelGGL((covariance_batch_kernel<lay(), ex()>), dim3(grid), dim3(256), 0, s, v, d_poses_world, batch,
+                       reinterpret_cast<const float2*>(d_pts_xy), d_scan_offsets, d_scan_offsets ? 0 : shared_n, Lv.cell_length,
+                       d_out_cov_world, d_out_cov_map, d_out_lh7, d_out_likelihood);
+  });
+  HIP_TRY(hipGetLastError());
+  if (fs) fs->pending = true;
+  h->last.last_kernel = "covariance_batch_kernel";
+  h->last.last_parity = exact ? HSM_PARITY_EXACT : (h->cfg.parity.relaxed ? HSM_PARITY_RELAXED : HSM_PARITY_FAST);
+  return HSM_OK;
+}
+
+int hsm_covariance_batch_device(hsm_ctx* h, int level, int batch, const float* d_poses_world, const float* d_pts_xy,
+                                const int* d_scan_offsets, int shared_n, float* d_out_cov_world, float* d_out_cov_map,
+                                float* d_out_lh7, float* d_out_likelihood, void* stream) {
+  if (!h) return fail(HSM_ERR_INVALID, "hsm_covariance_batch_device: null context");
+  std::lock_guard<std::mutex> lk(h->mu);
+  return covariance_batch_device_nolock(h, level, batch, d_poses_world, d_pts_xy, d_scan_offsets, shared_n, d_out_cov_world,
+                                        d_out_cov_map, d_out_lh7, d_out_likelihood, stream);
+}
+
 // Groups of at most this many entries (or, with CSR groups whose sizes only the device knows, launches of at least this many
 // groups) take one wavefront per group, the others one workgroup per group.  Either shape gives the same result.
 constexpr int kSelectWaveGroupMax = 1024;
@@ -359,6 +411,66 @@ int hsm_match_score_batch_device(hsm_ctx* h, int batch, const float* d_begin_wor
   return match_score_batch_device_nolock(h, batch, d_begin_world, d_pts_xy, d_scan_offsets, shared_n, d_out_pose, d_out_cov,
                                          score_level, d_out_likelihood, d_out_residual, groups, d_group_offsets, group_size,
                                          d_out_index, d_out_score, d_out_best_pose, stream);
+}
+
+// match -> covariance estimate at the matched poses -> (groups > 0) the winner of every group by the pose's own likelihood, queued
+// on `stream` under one lock.  Every argument is checked before the first launch (the group rules are match_score's).
+int hsm_match_cov_batch_device(hsm_ctx* h, int batch, const float* d_begin_world, const float* d_pts_xy, const int* d_scan_offsets,
+                               int shared_n, float* d_out_pose, float* d_out_cov, int cov_level, float* d_out_cov_world,
+                               float* d_out_cov_map, float* d_out_lh7, float* d_out_likelihood, int groups,
+                               const int* d_group_offsets, int group_size, int* d_out_index, float* d_out_score,
+                               float* d_out_best_pose, void* stream) {
+  static const char* const who = "hsm_match_cov_batch_device";
+  if (!h) return fail_at(HSM_ERR_INVALID, who, ": null context");
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (cov_level < 0 || cov_level >= (int)h->levels.size()) return fail_at(HSM_ERR_INVALID, who, ": level out of range");
+  if (batch < 0 || !d_begin_world || !d_out_pose || (!d_scan_offsets && shared_n < 0) ||
+      (!d_out_cov_world && !d_out_cov_map && !d_out_lh7 && !d_out_likelihood) ||
+      (batch > 0 && !d_pts_xy && !d_scan_offsets && shared_n > 0) || groups < 0 ||
+      (groups > 0 && (!d_out_likelihood || !d_out_index || (!d_group_offsets && (group_size < 0 || (long long)groups * group_size > batch)))))
+    return fail_at(HSM_ERR_INVALID, who, ": bad argument");
+  if (int rc = match_batch_device_nolock(h, batch, d_begin_world, d_pts_xy, d_scan_offsets, shared_n, d_out_pose, d_out_cov, stream))
+    return rc;
+  // the sizing hint of a CSR match means nothing to the covariance kernel: it reads every scan's length from the offsets
+  if (int rc = covariance_batch_device_nolock(h, cov_level, batch, d_out_pose, d_pts_xy, d_scan_offsets, d_scan_offsets ? 0 : shared_n,
+                                              d_out_cov_world, d_out_cov_map, d_out_lh7, d_out_likelihood, stream, who))
+    return rc;
+  if (groups == 0) return HSM_OK;
+  return select_best_device_nolock(h, groups, d_group_offsets, group_size, d_out_likelihood, d_out_pose, d_out_index, d_out_score,
+                                   d_out_best_pose, stream);
+}
+
+// host arrays in, covariance_batch_kernel on the context's stream, results out; synchronous
+int hsm_covariance_batch(hsm_ctx* h, int level, int batch, const float* poses_world, const float* pts_xy, const int* scan_offsets,
+                         int shared_n, float* out_cov_world, float* out_cov_map, float* out_lh7, float* out_likelihood) {
+  static const char* const who = "hsm_covariance_batch";
+  if (int rc = covariance_batch_check(h, level, batch, poses_world, pts_xy, scan_offsets, shared_n, out_cov_world, out_cov_map,
+                                      out_lh7, out_likelihood, who))
+    return rc;
+  if (batch == 0) return HSM_OK;
+  if (scan_offsets) {
+    if (scan_offsets[0] != 0) return fail_at(HSM_ERR_INVALID, who, ": bad argument");
+    for (int i = 0; i < batch; ++i)
+      if (scan_offsets[i + 1] < scan_offsets[i]) return fail_at(HSM_ERR_INVALID, who, ": bad argument");
+  }
+  const size_t total = scan_offsets ? (size_t)scan_offsets[batch] : (size_t)shared_n;
+  if (total > 0 && !pts_xy) return fail_at(HSM_ERR_INVALID, who, ": bad argument");
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (int rc = select_device(h)) return rc;
+  const CovarianceBatchStage st = covariance_batch_stage(batch, total, poses_world, pts_xy, scan_offsets, out_cov_world, out_cov_map,
+                                                         out_lh7, out_likelihood);
+  if (int rc = h->d_batch.reserve(st.plan.total())) return rc;
+  char* base = h->d_batch;
+  if (int rc = stage_copy_in(st.plan, base, h->stream)) return rc;
+  if (int rc = covariance_batch_device_nolock(h, level, batch, staged<float>(base, st.poses), staged<float>(base, st.pts),
+                                              staged<int>(base, st.offs, scan_offsets), scan_offsets ? 0 : shared_n,
+                                              staged<float>(base, st.cov_world, out_cov_world), staged<float>(base, st.cov_map, out_cov_map),
+                                              staged<float>(base, st.lh7, out_lh7), staged<float>(base, st.lh, out_likelihood),
+                                              h->stream, who))
+    return rc;
+  if (int rc = stage_copy_out(st.plan, base, h->stream)) return rc;
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return HSM_OK;
 }
 
 // what hsm_match_score_batch asks for on top of hsm_match_batch (host pointers)

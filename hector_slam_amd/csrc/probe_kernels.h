@@ -196,10 +196,9 @@ __global__ void __launch_bounds__(448) pose_covariance_kernel(const LevelView L,
   __shared__ float rows[EXACT ? 7 : 1][EXACT ? 64 : 1];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int b = blockIdx.x;
-  const float deltaTransX = 1.5f, deltaTransY = 1.5f, deltaAng = 0.05f;
   const float x = poses[3 * b], y = poses[3 * b + 1], ang = poses[3 * b + 2];
-  float sp[7][3] = {{x + deltaTransX, y, ang}, {x - deltaTransX, y, ang}, {x, y + deltaTransY, ang},
-                    {x, y - deltaTransY, ang}, {x, y, ang + deltaAng},    {x, y, ang - deltaAng}, {x, y, ang}};
+  float sp[7][3];
+  sigma_points(x, y, ang, sp);
   {
     float ex = sp[0][0], ey = sp[0][1], ea = sp[0][2];
 #pragma unroll
@@ -237,37 +236,9 @@ __global__ void __launch_bounds__(448) pose_covariance_kernel(const LevelView L,
   }
   __syncthreads();
   if (threadIdx.x != 0) return;
-  // likelihoods.sum(): fixed-size 7-vector, unrolled halves (0..2) + (3..6)
-  const float sum = ((lh[0] + (lh[1] + lh[2])) + ((lh[3] + lh[4]) + (lh[5] + lh[6])));
-  const float invLhNormalizer = 1 / sum;
-  float mean[3] = {0.0f, 0.0f, 0.0f};
-  for (int i = 0; i < 7; ++i)
-    for (int r = 0; r < 3; ++r) mean[r] += sp[i][r] * lh[i];
-  for (int r = 0; r < 3; ++r) mean[r] *= invLhNormalizer;
-  float cov[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // column major
-  for (int i = 0; i < 7; ++i) {
-    const float d[3] = {sp[i][0] - mean[0], sp[i][1] - mean[1], sp[i][2] - mean[2]};
-    const float wgt = lh[i] * invLhNormalizer;
-    for (int c = 0; c < 3; ++c)
-      for (int r = 0; r < 3; ++r) cov[c * 3 + r] += wgt * (d[r] * d[c]);
-  }
-  if (out_lh7)
-    for (int i = 0; i < 7; ++i) out_lh7[7 * b + i] = lh[i];
-  if (out_cov_map)
-    for (int i = 0; i < 9; ++i) out_cov_map[9 * b + i] = cov[i];
-  if (out_cov_world) {
-    const float scaleTrans = cell_length, scaleTransSq = scaleTrans * scaleTrans;
-    float* W = out_cov_world + 9 * b;  // (r,c) at c*3+r
-    W[0] = cov[0] * scaleTransSq;
-    W[4] = cov[4] * scaleTransSq;
-    W[1] = cov[1] * scaleTransSq;  // (1,0)
-    W[3] = W[1];
-    W[2] = cov[2] * scaleTrans;  // (2,0)
-    W[6] = W[2];
-    W[5] = cov[5] * scaleTrans;  // (2,1)
-    W[7] = W[5];
-    W[8] = cov[8];
-  }
+  // the 7-term statistics in the source's order (gn_step.h)
+  sigma_point_statistics(sp, lh, cell_length, out_lh7 ? out_lh7 + 7 * b : nullptr, out_cov_map ? out_cov_map + 9 * b : nullptr,
+                         out_cov_world ? out_cov_world + 9 * b : nullptr);
 }
 
 }  // namespace hsm

@@ -1,5 +1,6 @@
-// score_kernels.h -- the weighting and ranking of batches of pose hypotheses (score_batch_kernel, select_best_kernel), launched
-// by match.hip only.  Sampler: beam_sample.h; the residual chain and the (score, index) order: gn_step.h.
+// score_kernels.h -- the weighting, the covariance estimate and the ranking of batches of pose hypotheses (score_batch_kernel,
+// covariance_batch_kernel, select_best_kernel), launched by match.hip only.  Sampler: beam_sample.h; the residual chain, the
+// sigma-point statistics and the (score, index) order: gn_step.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -67,6 +68,117 @@ __global__ void __launch_bounds__(256) score_batch_kernel(const LevelView L, con
     if (out_lh) out_lh[b] = 1 - (residual / (float)n);  // getLikelihoodForState (:184-203)
     if (out_residual) out_residual[b] = residual;       // getResidualForState (:205-221)
   }
+}
+
+// ---- the covariance estimate of a batch of pose hypotheses: pose_covariance_kernel for what hsm_match_batch_device returns ------
+// getCovarianceForPose (OccGridMapUtil.h:106-160) + getCovMatrixWorldCoords (:162-188) for B (WORLD pose, scan) pairs in one
+// launch, on score_batch_kernel's conventions (CSR or shared scan, getMapCoordsPose and pt_scale applied here, one wavefront per
+// hypothesis, four per workgroup, pose and offsets read once per wavefront through the scalar unit).  A wavefront scores all
+// seven sigma points of its hypothesis: a round of 64 beams loads and scales an end point once, the five sigma points that
+// differ from the pose by a translation share one sincos_f32 and one rotated end point, the two angle sigma points have their own.
+//
+// Sharing the rotated end point leaves every bit as it was: the reference applies Translation * Rotation to the point, which is
+// t + (R p) with R p evaluated first (beam_sample.h BeamRot), so R p does not depend on t; beam_fetch forms e + r from the same two
+// operations.  Sigma point 6 is the pose: its likelihood is score_batch_kernel's, bit for bit.
+//
+// EXACT: the seven residuals are summed in the reference's beam order.  A round writes seven LDS rows of 64 funvals and lanes
+// 0 .. 6 each add their own row left to right, so one pass of 64 dependent additions advances all seven chains.  Row k is stored
+// rotated by 4 k floats, which keeps its float4s whole and puts the seven lanes' reads of one step into distinct banks.  Padding
+// beyond the scan contributes +0 (likelihood_kernel).  Else: lane-strided partial sums and a wave_allreduce per sigma point, the
+// summation shape of pose_covariance_kernel<_, false>.  LDS: 7 x 64 x 4 B per wavefront (EXACT), none otherwise; no scratch.
+// A scan of 0 beams: every likelihood 1 - 0/0 = NaN and with them every covariance, as the reference computes it.
+// Lane 0 does the 7-term statistics (gn_step.h sigma_point_statistics, the probe's).  out_lh [B] = sigma point 6, contiguous.
+template <int LAYOUT>
+__device__ __forceinline__ float sigma_funval(const LevelRegs& R, f2 e, f2 r) {
+  const BeamSample s = sample_fetch<LAYOUT>(R, f2{e.x + r.x, e.y + r.y});
+  const float M = ((s.lo.x * s.X.x + s.lo.y * s.X.y) * (s.Y.x)) + ((s.hi.x * s.X.x + s.hi.y * s.X.y) * (s.Y.y));
+  return 1.0f - M;
+}
+
+template <int LAYOUT, bool EXACT>
+__global__ void __launch_bounds__(256) covariance_batch_kernel(const LevelView L, const float* __restrict__ poses_world, int batch,
+                                                               const float2* __restrict__ pts_all,
+                                                               const int* __restrict__ offsets, int shared_n, float cell_length,
+                                                               float* __restrict__ out_cov_world, float* __restrict__ out_cov_map,
+                                                               float* __restrict__ out_lh7, float* __restrict__ out_lh) {
+  __shared__ __attribute__((aligned(16))) float rows[EXACT ? 4 : 1][EXACT ? 7 : 1][EXACT ? 64 : 1];
+  const int lane = threadIdx.x & 63;
+  const int b = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)));  // wave-uniform
+  if (b >= batch) return;
+  int beg = 0, n = shared_n;
+  if (offsets) {
+    beg = offsets[b];
+    n = offsets[b + 1] - beg;
+  }
+  const float2* __restrict__ pts = pts_all + beg;
+  float x, y;
+  affine_apply(L.mapTworld, poses_world[3 * b], poses_world[3 * b + 1], x, y);  // getMapCoordsPose
+  float sp[7][3];
+  sigma_points(x, y, poses_world[3 * b + 2], sp);
+  // sigma points 0 .. 3 and 6 share the pose's angle, 4 and 5 the pose's origin
+  float sinRot, cosRot, sinP, cosP, sinM, cosM;
+  sincos_f32(sp[6][2], sinRot, cosRot);
+  sincos_f32(sp[4][2], sinP, cosP);
+  sincos_f32(sp[5][2], sinM, cosM);
+  const float pt_scale = L.pt_scale;
+  const LevelRegs R = level_regs<LAYOUT>(L);
+  const f2 e0 = step_origin(sp[0][0], sp[0][1]), e1 = step_origin(sp[1][0], sp[1][1]), e2 = step_origin(sp[2][0], sp[2][1]),
+           e3 = step_origin(sp[3][0], sp[3][1]), e6 = step_origin(sp[6][0], sp[6][1]);
+  // the seven funvals of one beam; r = R(angle) p as beam_fetch forms it
+  auto funvals = [&](float2 q, float fv[7]) {
+    const f2 p = f2{q.x * pt_scale, q.y * pt_scale};
+    const f2 r = f2{cosRot * p.x - sinRot * p.y, sinRot * p.x + cosRot * p.y};
+    const f2 rp = f2{cosP * p.x - sinP * p.y, sinP * p.x + cosP * p.y};
+    const f2 rm = f2{cosM * p.x - sinM * p.y, sinM * p.x + cosM * p.y};
+    fv[0] = sigma_funval<LAYOUT>(R, e0, r);
+    fv[1] = sigma_funval<LAYOUT>(R, e1, r);
+    fv[2] = sigma_funval<LAYOUT>(R, e2, r);
+    fv[3] = sigma_funval<LAYOUT>(R, e3, r);
+    fv[4] = sigma_funval<LAYOUT>(R, e6, rp);
+    fv[5] = sigma_funval<LAYOUT>(R, e6, rm);
+    fv[6] = sigma_funval<LAYOUT>(R, e6, r);
+  };
+  float lh[7];
+  if (EXACT) {
+    float(*row)[EXACT ? 64 : 1] = rows[(threadIdx.x >> 6) & 3];
+    const float* mine = row[lane < 7 ? lane : 6];  // lanes 0 .. 6: the chain of sigma point `lane`
+    float run = 0.0f;
+    for (int base = 0; base < n; base += 64) {  // wave-uniform trip count
+      const int i = base + lane;
+      float fv[7] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};  // padding beyond the scan: +0 changes no sum
+      if (i < n) funvals(pts[i], fv);
+#pragma unroll
+      for (int k = 0; k < 7; ++k) row[k][(lane + 4 * k) & 63] = fv[k];
+      // (one wavefront: its LDS operations execute in program order, no barrier)
+      if (lane < 7) {
+#pragma unroll 4
+        for (int q = 0; q < 64; q += 4) {
+          const float4 v = *reinterpret_cast<const float4*>(mine + ((q + 4 * lane) & 63));
+          run += v.x;
+          run += v.y;
+          run += v.z;
+          run += v.w;
+        }
+      }
+    }
+    const float mine_lh = 1 - (run / (float)n);  // getLikelihoodForState (:184-203), in lane k for sigma point k
+#pragma unroll
+    for (int k = 0; k < 7; ++k) lh[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine_lh), k));
+  } else {
+    float res[7] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    for (int i = lane; i < n; i += 64) {
+      float fv[7];
+      funvals(pts[i], fv);
+#pragma unroll
+      for (int k = 0; k < 7; ++k) res[k] += fv[k];
+    }
+#pragma unroll
+    for (int k = 0; k < 7; ++k) lh[k] = 1 - (wave_allreduce(res[k]) / (float)n);
+  }
+  if (lane != 0) return;
+  sigma_point_statistics(sp, lh, cell_length, out_lh7 ? out_lh7 + 7 * (size_t)b : nullptr,
+                         out_cov_map ? out_cov_map + 9 * (size_t)b : nullptr, out_cov_world ? out_cov_world + 9 * (size_t)b : nullptr);
+  if (out_lh) out_lh[b] = lh[6];
 }
 
 // WAVE_PER_GROUP: four groups per workgroup, one wavefront each (many small groups); else the whole workgroup takes one group.

@@ -191,6 +191,29 @@ inline PoseCovarianceStage pose_covariance_stage(int batch, int n, const float* 
   return s;
 }
 
+// hsm_covariance_batch (d_batch): world poses[batch * 3] | end points[total_pts] | offsets[batch + 1] (a CSR batch; not carved
+// for a shared scan) | world-frame covariances[batch * 9] | map-frame covariances[batch * 9] | the seven sigma-point
+// likelihoods[batch * 7] | the pose's likelihood[batch].  An output the caller does not ask for is not carved: the kernel gets none.
+struct CovarianceBatchStage {
+  StagePlan plan;
+  size_t poses, pts, offs, cov_world, cov_map, lh7, lh;
+};
+
+inline CovarianceBatchStage covariance_batch_stage(int batch, size_t total_pts, const float* poses, const float* pts,
+                                                   const int* offsets, float* out_cov_world, float* out_cov_map, float* out_lh7,
+                                                   float* out_lh) {
+  const size_t b = (size_t)batch * sizeof(float);
+  CovarianceBatchStage s;
+  s.poses = s.plan.add(3 * b, poses);
+  s.pts = s.plan.add(total_pts * 2 * sizeof(float), pts);
+  s.offs = s.plan.add(offsets ? ((size_t)batch + 1) * sizeof(int) : 0, offsets);
+  s.cov_world = s.plan.add(out_cov_world ? 9 * b : 0, nullptr, out_cov_world);
+  s.cov_map = s.plan.add(out_cov_map ? 9 * b : 0, nullptr, out_cov_map);
+  s.lh7 = s.plan.add(out_lh7 ? 7 * b : 0, nullptr, out_lh7);
+  s.lh = s.plan.add(out_lh ? b : 0, nullptr, out_lh);
+  return s;
+}
+
 // hsm_ray_distances (d_batch): ray begins[n * 2] | ray ends[n * 2] | distances[n] | hit points[n * 2].  The hit points go in and
 // out: a ray without a hit leaves the caller's values.
 struct RayDistancesStage {

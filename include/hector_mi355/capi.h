@@ -776,6 +776,45 @@ int hsm_match_score_batch(hsm_ctx* h, int batch, const float* begin_world, const
                           int shared_n, float* out_pose, float* out_cov, int score_level, float* out_likelihood,
                           float* out_residual, int groups, const int* group_offsets, int group_size, int* out_index,
                           float* out_score, float* out_best_pose);
+/* ---- sigma-point covariances of a batch of pose hypotheses on the device (extension: the reference estimates one per call) ----
+ * replaces: OccGridMapUtil::getCovarianceForPose (HSL/map/OccGridMapUtil.h:106-160) followed by getCovMatrixWorldCoords
+ *           (:162-188) -- the block commented out at ScanMatcher.h:134-147 -- at GridMapBase::getMapCoordsPose(pose)
+ *           (HSL/map/GridMapBase.h:235-239), for B (pose, scan) pairs at once: the uncertainty behind hsm_match_batch_device,
+ *           whose own d_out_cov is the Gauss-Newton Hessian.  DEVICE pointers:
+ *   d_poses_world, d_pts_xy, d_scan_offsets, shared_n   as in hsm_score_batch_device (WORLD poses, converted to the map frame of
+ *                  `level` in the kernel; CSR offsets in points or one shared scan; level-0 units, scaled in the kernel)
+ *   d_out_cov_world [B*9], d_out_cov_map [B*9]   column major      d_out_lh7 [B*7]   the likelihoods of the seven sigma points of
+ *                  :119-125 around the map-frame pose, in that order: x +- 1.5 cells, y +- 1.5 cells, angle +- 0.05 rad, the pose
+ *   d_out_likelihood [B]   sigma point 6 again, contiguous: the same bits as hsm_score_batch_device's likelihood of the same
+ *                  batch, so that it can go straight into hsm_select_best_device
+ *   Any of the four may be NULL, not all.  A scan of 0 beams: every likelihood and every covariance entry NaN (1 - 0/0, as the
+ *   reference computes it).  (The reference prints the likelihoods to stdout on every call, :136; this entry does not.)
+ * HSM_PARITY_AUTO / _EXACT: every residual is summed in the reference's beam order, all outputs are bit-identical to the reference
+ * for every hypothesis.  HSM_PARITY_FAST / _RELAXED: lane-strided partial sums + tree, the bits of hsm_covariance_for_poses in that
+ * mode.  hsm_last_launch_parity / hsm_last_launch_kernel ("covariance_batch_kernel") report the launch.
+ * Ordering, capture, locking and batch == 0: the contract of hsm_score_batch_device, through the same bookkeeping -- reads the map
+ * only, needs no workspace, keeps no per-stream or per-context state, one kernel node under capture.
+ * HSM_ERR_INVALID (nothing launched, hsm_last_error() names the entry): NULL context, level out of range, batch < 0, all four
+ * outputs NULL, shared_n < 0 without offsets, NULL poses, NULL points for a shared scan of shared_n > 0.
+ * Not built: replay through hsm_group_*, a covariance inside hsm_relocalize_device or the scan-log loop. */
+int hsm_covariance_batch_device(hsm_ctx* h, int level, int batch, const float* d_poses_world, const float* d_pts_xy,
+                                const int* d_scan_offsets, int shared_n, float* d_out_cov_world, float* d_out_cov_map,
+                                float* d_out_lh7, float* d_out_likelihood, void* stream);
+/* replaces: MapRepMultiMap::matchData followed by the covariance estimate above at every matched pose.
+ * hsm_match_batch_device, then hsm_covariance_batch_device of its d_out_pose on cov_level, then -- groups > 0 --
+ * hsm_select_best_device over d_out_likelihood and d_out_pose into d_out_index / d_out_score / d_out_best_pose: queued on `stream`
+ * under ONE lock of the context, no host wait in between; the same bits as the three calls.  d_out_cov (the match's Hessian) stays
+ * a separate, optional output.  All arguments are checked before the first launch (groups > 0 needs d_out_likelihood and
+ * d_out_index, and groups * group_size <= batch without group offsets). */
+int hsm_match_cov_batch_device(hsm_ctx* h, int batch, const float* d_begin_world, const float* d_pts_xy, const int* d_scan_offsets,
+                               int shared_n, float* d_out_pose, float* d_out_cov, int cov_level, float* d_out_cov_world,
+                               float* d_out_cov_map, float* d_out_lh7, float* d_out_likelihood, int groups,
+                               const int* d_group_offsets, int group_size, int* d_out_index, float* d_out_score,
+                               float* d_out_best_pose, void* stream);
+/* replaces: getCovarianceForPose + getCovMatrixWorldCoords as above -- hsm_covariance_batch_device with HOST pointers: copies in,
+ * the kernel on the context's stream, copies out; synchronous.  scan_offsets (host) must start at 0 and not decrease. */
+int hsm_covariance_batch(hsm_ctx* h, int level, int batch, const float* poses_world, const float* pts_xy, const int* scan_offsets,
+                         int shared_n, float* out_cov_world, float* out_cov_map, float* out_lh7, float* out_likelihood);
 /* ---- relocalisation: one scan against a WINDOW of poses on the device map (extension: hector_mapping has no recovery once
  * the matcher has left its basin) ----
  * A window is a DEVICE centre d_center_world[3] (so that it can be the d_out_pose of a match or of hsm_slam_* without a host

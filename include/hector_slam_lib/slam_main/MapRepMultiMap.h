@@ -215,6 +215,52 @@ public:
     matchBatchImpl(beginEstimatesWorld, scans, posesOut, covOut, scoreLevel, &likelihoodsOut, groupSize, bestIndexOut);
   }
 
+  // ---- extension: OccGridMapUtil::getCovarianceForPose followed by getCovMatrixWorldCoords (the estimate commented out at
+  // ScanMatcher.h:134-147) for B (WORLD pose, scan) pairs on `level` in one device call (hsm_covariance_batch).  covWorldOut[i]:
+  // the world-frame sigma-point covariance of pose i; likelihoodsOut[i]: getLikelihoodForState at pose i.  An empty scan gives NaN
+  // in both.  scans[i] may all be the same container.
+  void getCovarianceForPosesBatch(const std::vector<Eigen::Vector3f>& posesWorld, const std::vector<const DataContainer*>& scans,
+                                  std::vector<Eigen::Matrix3f>& covWorldOut, std::vector<float>* likelihoodsOut = 0, int level = 0)
+  {
+    const int B = static_cast<int>(posesWorld.size());
+    covWorldOut.resize(B);
+    if (likelihoodsOut) {
+      likelihoodsOut->assign(static_cast<size_t>(B), 0.0f);
+    }
+    if (B == 0) {
+      return;
+    }
+    std::vector<float> poses(3 * static_cast<size_t>(B)), cov(9 * static_cast<size_t>(B), 0.0f);
+    std::vector<int> offsets(static_cast<size_t>(B) + 1, 0);
+    bool shared = true;
+    for (int i = 0; i < B; ++i) {
+      shared = shared && scans[i] == scans[0];
+      offsets[i + 1] = offsets[i] + scans[i]->getSize();
+      for (int k = 0; k < 3; ++k) {
+        poses[3 * i + k] = posesWorld[i][k];
+      }
+    }
+    const int count = shared ? 1 : B;  // containers that travel
+    std::vector<float> pts(2 * static_cast<size_t>(offsets[count]));
+    for (int i = 0; i < count; ++i) {
+      const int n = scans[i]->getSize();
+      for (int j = 0; j < n; ++j) {
+        const Eigen::Vector2f& p = scans[i]->getVecEntry(j);
+        pts[2 * (static_cast<size_t>(offsets[i]) + j)] = p[0];
+        pts[2 * (static_cast<size_t>(offsets[i]) + j) + 1] = p[1];
+      }
+    }
+    hsm_covariance_batch(ctx, level, B, &poses[0], pts.empty() ? 0 : &pts[0], shared ? 0 : &offsets[0], shared ? offsets[1] : 0,
+                         &cov[0], 0, 0, likelihoodsOut ? &(*likelihoodsOut)[0] : 0);
+    for (int i = 0; i < B; ++i) {
+      for (int c = 0; c < 3; ++c) {
+        for (int r = 0; r < 3; ++r) {
+          covWorldOut[i](r, c) = cov[9 * i + 3 * c + r];
+        }
+      }
+    }
+  }
+
   hsm_ctx* getDeviceContext() { return ctx; }
 
 protected:
