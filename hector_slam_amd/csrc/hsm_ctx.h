@@ -9,7 +9,8 @@
 //                           (gn_match_dense.h, gn_match_spec.h, score_kernels.h); the other forms it dispatches to the two
 //                           match_* units below  => single, batch, last, retained
 //   map_update.hip          every writer of the map by scans: the update entries, the movement gate, the device SLAM scan loop and
-//                           the level maintenance the other units reach through this header (map_update.h, update_gate.h)  => upd
+//                           the level maintenance the other units reach through this header (map_update.h, map_update_scans.h;
+//                           behind them update_types.h, update_cell_rule.h, update_gate.h)  => upd
 //   ingest.hip              raw sensor data: the LaserScan / point-cloud conversions of one scan and of batches, in front of
 //                           the match, the update and the SLAM loop (ingest_kernels.h)  => ingest
 //   occupancy.hip           a level as the node's occupancy grid, whole or its changed cells only (occupancy_kernels.h)  => occ
@@ -48,11 +49,11 @@
 #include "stage_layout.h"
 
 namespace hsm {
-struct BeamRec;  // map_update.h.  Its kernels are not templates, so map_update.hip includes that header (and update_gate.h behind
-                 // it) and no other unit does: whatever launches one of its kernels lives there
+struct BeamRec;  // update_types.h.  The update kernels (map_update.h, map_update_scans.h) are not templates, so map_update.hip
+                 // includes the update headers and no other unit does: whatever launches one of their kernels lives there
 struct LevelRW;  // map_cells.h
-struct UpdateBatch;
-struct GateState;
+struct UpdateBatch;  // update_types.h
+struct GateState;    // map_update_scans.h
 }
 
 namespace hsm_host {
@@ -333,13 +334,13 @@ struct hsm_ctx {
   // ---- map_update.hip -----------------------------------------------------------------------------------------------------------
   struct Update {
     Bufs* bufs;
-    Buf<BeamRec> d_beam_recs{bufs};  // dense scans: per-beam records of all levels (map_update.h BeamRec), [HSM_MAX_LEVELS][count() / HSM_MAX_LEVELS]
+    Buf<BeamRec> d_beam_recs{bufs};  // dense scans: per-beam records of all levels (update_types.h BeamRec), [HSM_MAX_LEVELS][count() / HSM_MAX_LEVELS]
     // hsm_update_by_scans_device: one UpdateBatch and one cell box per level for every scan of a call, filled on the device
-    // (map_update.h update_prep_kernel); grown outside capture.  boxes: slot 0 the levels' running dirty boxes, slot 1 the last scan's
+    // (map_update_scans.h update_prep_kernel); grown outside capture.  boxes: slot 0 the levels' running dirty boxes, slot 1 the last scan's
     Buf<UpdateBatch> d_upd_batches{bufs};
     Buf<int> d_upd_boxes{bufs};  // allocated last: non-null = both blocks serve d_upd_batches.count() scans
     bool upd_boxes_outstanding = false;  // device-side updates since the host last merged their boxes into Level::bbox / dirty
-    // the movement gate of HectorSlamProcessor::update (update_gate.h; map_update.h update_gate_prep_kernel): its state and the
+    // the movement gate of HectorSlamProcessor::update (update_gate.h; map_update_scans.h update_gate_prep_kernel): its state and the
     // count of updates it let through live on the device -- the host never learns a gated call's decisions.  Whoever needs
     // Level's update counters on the host first waits for the stream and folds that count in (fold_gate_counters), like the boxes
     hsm::GateState* d_gate = nullptr;
@@ -417,7 +418,7 @@ namespace hsm_host {
 
 using hsm_plan::MatchPlan;
 
-// What a gated update adds to an update call (update_by_scans_device_nolock of map_update.hip; map_update.h UpdateGateParams)
+// What a gated update adds to an update call (update_by_scans_device_nolock of map_update.hip; map_update_scans.h UpdateGateParams)
 struct GateCall {
   const unsigned char* d_force = nullptr;
   int* d_out_applied = nullptr;

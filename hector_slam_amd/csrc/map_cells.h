@@ -1,6 +1,6 @@
 // map_cells.h -- what every kernel that walks a level's cells shares: the read-write view of a level, the tilings of its key and
 // mark planes, the cell probability, the empty cell box, and the closed form of a Bresenham line.  No kernel is defined here:
-// map_update.h (map_update.hip), probe_kernels.h (probes.hip), ray_kernels.h (rays.hip) and occupancy_kernels.h (occupancy.hip)
+// update_types.h (map_update.hip), probe_kernels.h (probes.hip), ray_kernels.h (rays.hip) and occupancy_kernels.h (occupancy.hip)
 // all include it.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,5 +1,5 @@
-// map_update.hip -- everything that launches a kernel of map_update.h, the one unit that includes it (hsm_ctx.h has the rule): the
-// map-update entries of the C ABI (include/hector_mi355/capi.h: hsm_update_by_scan*, hsm_update_by_scans*, hsm_update_by_ingested,
+// map_update.hip -- everything that launches a kernel of map_update.h or map_update_scans.h, the one unit that includes them and
+// the update headers behind them (hsm_ctx.h has the rule): the map-update entries of the C ABI (include/hector_mi355/capi.h: hsm_update_by_scan*, hsm_update_by_scans*, hsm_update_by_ingested,
 // the movement gate), the device SLAM scan loop (hsm_slam_scans_device*), and the level maintenance that create, reset, upload,
 // copy and shift reach through hsm_ctx.h.  What these need of the core runtime (hector_mi355.hip) is declared there too.
 #include <hip/hip_runtime.h>
@@ -12,9 +12,14 @@
 #include "hector_mi355/capi.h"
 #include "hsm_ctx.h"
 #include "map_update.h"
+#include "map_update_scans.h"
 
 using namespace hsm;
 using namespace hsm_host;
+
+// the <SCATTER_TEXELS, STAMPED> instantiation of an apply kernel template; a macro of this file only (a function template is no template argument)
+#define APPLY_FORM(kernel, scatter, stamped) \
+  ((scatter) ? ((stamped) ? kernel<true, true> : kernel<true, false>) : ((stamped) ? kernel<false, true> : kernel<false, false>))
 
 // acc = the hull of acc and b ({x0, y0, x1, y1} inclusive, empty where x1 < x0); b is not empty
 static void box_widen(int acc[4], const int b[4]) {
@@ -26,6 +31,14 @@ static void box_widen(int acc[4], const int b[4]) {
   if (b[1] < acc[1]) acc[1] = b[1];
   if (b[2] > acc[2]) acc[2] = b[2];
   if (b[3] > acc[3]) acc[3] = b[3];
+}
+
+// `applied` more updates of a level (an empty container counts, too): OccGridMapBase.h:123-124, :167, setUpdated() (GridMapBase.h:343)
+static void advance_update_counters(Level& L, int applied) {
+  L.curr_mark_free = L.curr_update_index + 3 * (applied - 1) + 1;
+  L.curr_mark_occ = L.curr_update_index + 3 * (applied - 1) + 2;
+  L.curr_update_index += 3 * applied;
+  L.last_update_index += applied;
 }
 
 int hsm_host::fill_level(hsm_ctx* h, Level& L) {  // GridMapBase::clear + LogOddsCell::resetGridCell
@@ -116,12 +129,7 @@ int hsm_host::fold_gate_counters(hsm_ctx* h, GateState* state) {
   const int applied = host.pending;
   if (applied > 0) {
     HIP_TRY(hipMemsetAsync(&h->upd.d_gate->pending, 0, sizeof(int), h->stream));  // ahead of every later gated call
-    for (Level& L : h->levels) {
-      L.curr_mark_free = L.curr_update_index + 3 * (applied - 1) + 1;
-      L.curr_mark_occ = L.curr_update_index + 3 * (applied - 1) + 2;
-      L.curr_update_index += 3 * applied;
-      L.last_update_index += applied;
-    }
+    for (Level& L : h->levels) advance_update_counters(L, applied);
     h->upd.gate_applied_total += applied;
     if (state) state->pending = 0;
   }
@@ -339,29 +347,22 @@ int launch_update_apply(hsm_ctx* h, const UpdateBatch& batch) {
   }
   if (max_box == 0) return HSM_OK;
   const unsigned ny = (unsigned)batch.nlev;
+  const bool quad = h->cfg.layout == kLayoutQuad;
   int max_n = 0;
   for (int i = 0; i < batch.nlev; ++i)
     if (batch.lv[i].n > max_n) max_n = batch.lv[i].n;
   if (use_dense_bits(h, batch, max_n)) {
     // one wavefront per block of 256 cells of the widened box (32 x 8 cells: two 16 x 8 mark tiles; map_update.h)
     const int g = grid_for(max_box / 4 + 4096);
-    auto dense = h->cfg.layout == kLayoutQuad ? (batch.stamped ? update_apply_dense_kernel<true, true> : update_apply_dense_kernel<true, false>)
-                                          : (batch.stamped ? update_apply_dense_kernel<false, true> : update_apply_dense_kernel<false, false>);
-    hipLaunchKernelGGL(dense, dim3(g, ny), dim3(256), 0, h->stream, batch);
+    hipLaunchKernelGGL(APPLY_FORM(update_apply_dense_kernel, quad, batch.stamped), dim3(g, ny), dim3(256), 0, h->stream, batch);
     HIP_TRY(hipGetLastError());
     return HSM_OK;
   }
-  if (h->cfg.layout == kLayoutQuad && max_n < h->cfg.upd.scatter_texels_max) {
-    // the apply pass writes the texels itself: one dependent launch less for the launch-bound small scans (1081 beams,
-    // 3 levels: complete 39 -> 34.5 us) and one dense pass less for the big ones (16 k beams on 8192^2: 0.51 -> 0.45 ms)
-    auto apply = batch.stamped ? update_apply_kernel<true, true> : update_apply_kernel<true, false>;
-    hipLaunchKernelGGL(apply, dim3(grid_for(max_box), ny), dim3(256), 0, h->stream, batch);
-  } else {
-    auto apply = batch.stamped ? update_apply_kernel<false, true> : update_apply_kernel<false, false>;
-    hipLaunchKernelGGL(apply, dim3(grid_for(max_box), ny), dim3(256), 0, h->stream, batch);
-    if (h->cfg.layout == kLayoutQuad)
-      hipLaunchKernelGGL(update_texels_kernel, dim3(grid_for(max_box), ny), dim3(256), 0, h->stream, batch);
-  }
+  // the apply pass writes the texels itself: one dependent launch less for the launch-bound small scans (1081 beams,
+  // 3 levels: complete 39 -> 34.5 us) and one dense pass less for the big ones (16 k beams on 8192^2: 0.51 -> 0.45 ms)
+  const bool scatter = quad && max_n < h->cfg.upd.scatter_texels_max;
+  hipLaunchKernelGGL(APPLY_FORM(update_apply_kernel, scatter, batch.stamped), dim3(grid_for(max_box), ny), dim3(256), 0, h->stream, batch);
+  if (quad && !scatter) hipLaunchKernelGGL(update_texels_kernel, dim3(grid_for(max_box), ny), dim3(256), 0, h->stream, batch);
   HIP_TRY(hipGetLastError());
   return HSM_OK;
 }
@@ -453,8 +454,7 @@ int update_impl(hsm_ctx* h, const float pose_world[3], const float* pts_xy, int 
     d_level0 = h->d_scan;
   }
   UpdateBatch batch;
-  batch.nlev = 0;
-  batch.stamped = 0;
+  batch.nlev = batch.stamped = 0;
   LevelPrep prep[HSM_MAX_LEVELS];
   if (int rc = prepare_level(h, batch, prep[0], 0, pose_world, d_level0, pts_xy, n, 1.0f, o)) return rc;
   // coarse levels: the containers retained by the last matchData (MapRepMultiMap.h:143)
@@ -506,7 +506,7 @@ int ensure_update_scans(hsm_ctx* h, size_t count) {
 }
 
 // `count` posed scans that are on the device, integrated in order by stream-ordered launches only: one update_prep_kernel, then
-// a mark and an apply launch per scan (map_update.h "posed scans that are already on the device").  The host supplies what it can
+// a mark and an apply launch per scan (map_update_scans.h).  The host supplies what it can
 // compute without the poses: per level the counters and the key generation before the call, from which scan k's follow.
 // `gate`: the gated entries.  update_gate_prep_kernel takes update_prep_kernel's place: it decides on the device which scans are
 // integrated and numbers them behind the updates earlier gated calls applied, so the levels' counters are not advanced here
@@ -588,8 +588,7 @@ int update_by_scans_device_nolock(hsm_ctx* h, const PosedScans& S, hipStream_t s
   // whose predecessors' counts are still on the device sees a counter that lags: the test errs towards the stamp-aware form.)
   bool stamped = false;
   for (int l = 0; l < nlev; ++l) stamped |= h->levels[l].stamps_ahead();
-  auto apply_scan = scatter ? (stamped ? update_apply_scan_kernel<true, true> : update_apply_scan_kernel<true, false>)
-                            : (stamped ? update_apply_scan_kernel<false, true> : update_apply_scan_kernel<false, false>);
+  auto apply_scan = APPLY_FORM(update_apply_scan_kernel, scatter, stamped);
   for (int l = 0; l < nlev; ++l) h->levels[l].marks_pending = true;  // until every apply pass is queued (scrub_pending_marks)
   for (int k = 0; k < count; ++k) {
     for (int l = 0; l < nlev; ++l) {
@@ -612,13 +611,7 @@ int update_by_scans_device_nolock(hsm_ctx* h, const PosedScans& S, hipStream_t s
   for (int l = 0; l < nlev; ++l) {
     Level& L = h->levels[l];
     L.marks_pending = false;
-    if (!gate) {
-      // OccGridMapBase.h:123-124, :167 and setUpdated() (GridMapBase.h:343), `count` times: an empty container counts, too
-      L.curr_mark_free = L.curr_update_index + 3 * (count - 1) + 1;
-      L.curr_mark_occ = L.curr_update_index + 3 * (count - 1) + 2;
-      L.curr_update_index += 3 * count;
-      L.last_update_index += count;
-    }
+    if (!gate) advance_update_counters(L, count);  // (a gated call's count stays on the device: fold_gate_counters)
     L.key_rows[0] = 0;  // which rows carry keys of this generation is known on the device only: the next wrap of a host-side
     L.key_rows[1] = L.sy - 1;  // update clears the whole level
   }
@@ -720,8 +713,7 @@ int hsm_update_by_scan_level(hsm_ctx* h, int level, const float pose_world[3], c
   if (n > 0)
     HIP_TRY(hipMemcpyAsync(h->d_scan, pts_level_xy, (size_t)n * sizeof(float2), hipMemcpyHostToDevice, h->stream));
   UpdateBatch batch;
-  batch.nlev = 0;
-  batch.stamped = 0;
+  batch.nlev = batch.stamped = 0;
   LevelPrep prep;
   if (int rc = prepare_level(h, batch, prep, level, pose_world, h->d_scan, pts_level_xy, n, 1.0f,
                              origo_level ? origo_level : zero))

@@ -1,7 +1,7 @@
 // update_gate.h -- the movement gate of HectorSlamProcessor::update (HSL/slam_main/HectorSlamProcessor.h:71-95): a scan is
 // integrated into the map only when its pose differs from the pose of the last integrated scan by more than a distance or an
 // angle, util::poseDifferenceLargerThan (HSL/util/UtilFunctions.h:73-92), or when the caller forces it (map_without_matching).
-// Plain C++ (no HIP header): the device's gate kernel (map_update.h) and the host compile the same text, and
+// Plain C++ (no HIP header): the device's gate kernel (map_update_scans.h) and the host compile the same text, and
 // tests/cpp/update_gate_model.cpp holds it to the CPU checkers with the host compiler alone (tests/test_update_gate_model.py).
 #pragma once
 #include <float.h>

@@ -1,4 +1,4 @@
-// CPU check for the device-side update preparation (map_update.h update_prep_kernel): the host path of updateByScan calls
+// CPU check for the device-side update preparation (map_update_scans.h update_prep_kernel): the host path of updateByScan calls
 // glibc's sinf and cosf SEPARATELY (prepare_level), the device evaluates libm_exact.h's sincosf_glibc once.  Both must be the
 // same pair of floats for every argument.  Swept: every `stride`-th float bit pattern (all exponents, both signs, denormals,
 // inf / NaN), and every bit pattern within 4096 of the boundaries of sincosf_glibc's argument ranges (2^-12, pi/4, 120, inf)

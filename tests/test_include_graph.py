@@ -23,6 +23,11 @@ OWNERS = {
     "probe_kernels.h": {"probes.hip"},
     "gn_match_exact.h": {"match_exact_cached.hip"},
     "gn_match_spec.h": {"match.hip"},
+    "map_update.h": {"map_update.hip"},
+    "map_update_scans.h": {"map_update.hip"},
+    "update_types.h": {"map_update.hip"},
+    "update_cell_rule.h": {"map_update.hip"},
+    "update_gate.h": {"map_update.hip"},
 }
 # the kernel-free headers of the matcher: what the table says of them, as sets of units as well
 ALL_BUT_EXCHANGE = set(build.UNITS) - {"pose_exchange.hip"}
@@ -93,6 +98,13 @@ def test_context_header_sees_types_only():
     # the matcher's types come with no device function at all
     assert "__device__" not in open(os.path.join(CSRC, "match_types.h")).read()
     assert not _names(closure) & {"beam_sample.h", "gn_step.h", "texel_cache.h"}
+
+
+def test_cell_rule_header_is_plain_cpp():
+    """both apply passes and the host's model test compile it: no HIP, nothing else of csrc/"""
+    assert _names(_closure_of("update_cell_rule.h")) == {"update_cell_rule.h"}
+    text = open(os.path.join(CSRC, "update_cell_rule.h")).read()
+    assert "__global__" not in text and "hip_runtime" not in text
 
 
 def test_exact_cached_unit_is_not_rebuilt_by_the_fast_kernels():

@@ -30,8 +30,9 @@ def test_update_by_scans_entries_are_declared_bound_and_exported():
         assert hasattr(lib, name), name
     for name in ("update_by_scans_device", "update_by_scans"):
         assert callable(getattr(capi.MapRepMultiMap, name, None)), name
-    # the update kernels are not templates: one unit includes their header (and the gate's behind it), and no other
-    own = {"map_update.h", "update_gate.h"}
+    # the update kernels are not templates: one unit includes their headers (and the gate's and the cell rule's behind them), and
+    # no other
+    own = {"map_update.h", "map_update_scans.h", "update_types.h", "update_cell_rule.h", "update_gate.h"}
     assert own <= {os.path.basename(d) for d in build.UNITS["map_update.hip"]}
     for unit, deps in build.UNITS.items():
         assert unit == "map_update.hip" or not own & {os.path.basename(d) for d in deps}, unit
