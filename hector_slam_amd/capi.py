@@ -165,6 +165,8 @@ SIGNATURES = {
     "hsm_take_dirty_bbox": (_i, [_vp, _i, _i32p]),
     "hsm_copy_map": (_i, [_vp, _vp]),
     "hsm_copy_map_boxes": (_i, [_vp, _vp, _vp]),
+    "hsm_merge_map": (_i, [_vp, _vp, _vp]),
+    "hsm_merge_map_box": (_i, [_vp, _vp, _vp, _i, _vp]),
     "hsm_group_sync_maps": (_i, [_vp, _i, _vp]),
     "hsm_shift_map": (_i, [_vp, _f, _f, _vp]),
     "hsm_map_start": (_i, [_vp, _f32p]),
@@ -240,6 +242,26 @@ def match_batch_ranges_workspace(batch: int, n: int) -> int:
 def _check(rc: int, what: str):
     if rc != HSM_OK:
         raise HsmError(f"{what} failed ({rc}): {load_library().hsm_last_error().decode()}")
+
+
+def merge_map(dst, src, src_in_dst):
+    """`src`'s pyramid merged into `dst`'s on the device (hsm_merge_map): src_in_dst = (tx, ty, theta), the pose of src's world
+    frame in dst's, metres and radians; queued on dst's stream, no host wait"""
+    t = np.ascontiguousarray(src_in_dst, np.float32).reshape(-1)
+    if t.size != 3:
+        raise ValueError("src_in_dst must hold tx, ty, theta")
+    _check(dst._lib.hsm_merge_map(dst._h, src._h, t.ctypes.data), "hsm_merge_map")
+
+
+def merge_map_box(dst, src, src_in_dst, level):
+    """the cells of dst's `level` that merge_map(dst, src, src_in_dst) visits (hsm_merge_map_box) -> int32 [x0, y0, x1, y1],
+    inclusive, x1 < x0 where src misses the level; host arithmetic only"""
+    t = np.ascontiguousarray(src_in_dst, np.float32).reshape(-1)
+    if t.size != 3:
+        raise ValueError("src_in_dst must hold tx, ty, theta")
+    bb = np.empty(4, np.int32)
+    _check(dst._lib.hsm_merge_map_box(dst._h, src._h, t.ctypes.data, int(level), bb.ctypes.data), "hsm_merge_map_box")
+    return bb
 
 
 def _addr(a) -> int:

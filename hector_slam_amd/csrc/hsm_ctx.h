@@ -19,7 +19,8 @@
 //   rays.hip                what a laser would see on a level: ray distances of arrays of rays (host or device pointers) and
 //                           expected scans cast from batches of poses (ray_kernels.h)
 //   map_copy.hip            a pyramid, or one cell box per level, copied from another context's planes on the device
-//                           (map_copy_kernels.h; the box arithmetic: map_copy_box.h)  => copy
+//                           (map_copy_kernels.h; the box arithmetic: map_copy_box.h), and another context's pyramid merged into
+//                           this one under a rigid transform (map_merge_kernels.h; its host arithmetic: map_merge_box.h)  => copy
 //   map_shift.hip           the window moved under the robot: every level's contents shifted by whole cells inside their own
 //                           planes, the geometry re-derived for other start coordinates (map_shift_kernels.h; the plan:
 //                           map_shift_plan.h)
@@ -403,8 +404,8 @@ struct hsm_ctx {
   // ---- map_copy.hip, map_shift.hip ----------------------------------------------------------------------------------------------
   struct Copy {
     Bufs* bufs;
-    // hsm_copy_map* (map_copy.hip).  As the destination: the staging patch of the cross-device route (4-byte elements, laid out by
-    // map_copy_box.h copy_patch_at), and the event on the own stream behind the last read of the source, which the source's
+    // hsm_copy_map*, hsm_merge_map (map_copy.hip).  As the destination: the staging patch of the cross-device route (4-byte elements,
+    // laid out by map_copy_box.h copy_patch_at; a merge stages log-odds only, one padded box per level), and the event on the own stream behind the last read of the source, which the source's
     // stream waits for.  As the source: the event on the own stream the destination's stream waits for.
     Buf<float> d_copy_patch{bufs};
     hipEvent_t evt_copy_read = nullptr, evt_copy_src = nullptr;

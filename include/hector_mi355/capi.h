@@ -517,6 +517,58 @@ int hsm_take_dirty_bbox(hsm_ctx* h, int level, int bbox[4]);
 int hsm_copy_map(hsm_ctx* dst, hsm_ctx* src);
 int hsm_copy_map_boxes(hsm_ctx* dst, hsm_ctx* src, const int* boxes);
 
+/* ---- two maps into one: another context's pyramid merged into this one under a rigid transform, on the device ----------------
+ * No counterpart in the reference (GridMapBase can only be copied, GridMapBase.h:173-205): an extension, like the window move and
+ * relocalisation, pinned by the rule below.  Two robots' pyramids, two replicas fed different scans, a stored map and a live one.
+ *
+ * src_in_dst = (tx, ty, theta) in HOST memory, metres and radians: the pose of `src`'s world frame in `dst`'s world frame,
+ * p_dst = R(theta) p_src + t.  The contexts must agree in level count, resolution and layout; they MAY differ in size and in
+ * start coordinates (a 512 x 512 local map into a 4096 x 4096 global one).  `src` is only read.
+ *
+ * Cell rule, per level l, for every cell (x, y) of `dst`'s box (below); cells sit AT integer map coordinates.
+ *   host, in double: c = cos(theta), s = sin(theta), b_l = scale_l * (R(-theta) (-off_dst - t) + off_src), with off the fp32
+ *     offsets (resolution * size) * start of hsm_create widened to double and scale_l what hsm_level_info reports; c, s and
+ *     b_l are then rounded to fp32.
+ *   device, in fp32, every operation rounded, nothing fused: mx = (c x + s y) + b_l.x, my = ((-s) x + c y) + b_l.y,
+ *     ix = (int)floorf(mx + 0.5f), iy likewise.
+ *   v = `src`'s log-odds at (ix, iy) on level l if the cell exists, else 0; a NaN or an infinite log-odds counts as 0.  Nearest
+ *     neighbour: stamps are not read.
+ *   d = `dst`'s log-odds of (x, y):  v == 0: the cell is not written.  v < 0: d' = d + v.
+ *     v > 0: d' = d < 50.0f ? fminf(d + v, 50.0f) : d -- the reference's gate on positive evidence (GridMapLogOdds.h:135-140)
+ *     and a cap at 50: two saturated cells would otherwise sum past the range of expf and put NaN into the probabilities.
+ * `dst`'s stamps, update counters, mark indices and restored-stamp state do not change: frozen cells stay frozen and later scans
+ * integrate under the same cell rules as before.  hsm_update_index(dst, l) advances by one on every level, as after an update.
+ * The update gate, the retained and the ingested scan and all settings are untouched.  The probabilities (and, in the quad
+ * layout, the texels of each box grown by one cell towards lower x and y) are bit for bit what a rebuild from the new log-odds
+ * gives.
+ *
+ * Box, per level: the four corners of `src`'s level rectangle [-0.5, sx_src - 0.5] x [-0.5, sy_src - 0.5] through the inverse
+ * affine (in double) into `dst`'s map coordinates; their bounding box, from floor of the least to ceil of the greatest
+ * coordinate, grown by one cell on every side and clamped to the level; {0, 0, -1, -1} where it misses the level.  The kernel
+ * visits exactly this box, and `dst`'s dirty box (hsm_take_dirty_bbox) and publish box (hsm_occupancy_changes*) widen by it;
+ * hsm_last_update_bbox is left alone.  hsm_merge_map_box returns the box of `level`: a pure host function, for sizing a mirror
+ * refresh.  If every level's box is empty, hsm_merge_map returns HSM_OK, queues nothing, and the update index does not advance.
+ *
+ * Ordering: as hsm_copy_map.  QUEUED on `dst`'s stream; reads `src` behind every update queued on `src` so far, writes `dst`
+ * behind the batched matches callers' streams may still be running on it; `src`'s next update is ordered behind the read.  The
+ * call waits for `dst`'s stream only to fetch the boxes and gated-update counts device-side updates left there.  The contexts'
+ * locks are taken in address order.
+ *
+ * HSM_ERR_INVALID, nothing queued, nothing changed: a NULL context or transform (hsm_merge_map_box: or bbox, or a level out of
+ * range); dst == src; a transform component that is not finite; contexts that differ in level count, resolution or layout; a
+ * caller's stream that either context has matched on being captured into a graph (hsm_merge_map).
+ *
+ * Contexts on the same device: the kernel reads `src`'s planes directly.  On different devices the rows of the `src` box that
+ * `dst`'s box maps back to (the same corner construction the other way round, grown by one, clamped) are first copied
+ * (hipMemcpy2DAsync on `dst`'s stream, log-odds only) into `dst`'s staging patch, and the same kernel reads the patch.
+ * HSM_COPY_STAGE=1 in the environment at `dst`'s hsm_create forces that route on one device as well, and that is the only way it
+ * has been exercised: the cross-device merge itself has not been run.
+ *
+ * Not covered: a transform in device memory, a group-wide merge, the C++ facade, weighted or bilinear resampling, merging
+ * stamps, graph capture of the call. */
+int hsm_merge_map(hsm_ctx* dst, hsm_ctx* src, const float src_in_dst[3]);
+int hsm_merge_map_box(const hsm_ctx* dst, const hsm_ctx* src, const float src_in_dst[3], int level, int bbox[4]);
+
 /* ---- the map window moved under the robot, on the device -------------------------------------------------------------------
  * The reference fixes a map's window at construction (MapRepMultiMap.h:48-72); a robot that reaches its edge loses its beams.
  * hsm_shift_map moves the window so that the context's geometry becomes that of hsm_create(..., new_start_x, new_start_y): the

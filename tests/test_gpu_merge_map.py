@@ -1,0 +1,394 @@
+"""Another context's pyramid merged into this one under a rigid transform (hsm_merge_map, hsm_merge_map_box) on the MI355X, against
+the numpy model of tests/merge_cases.py bit for bit over ALL cells: no tolerance and no exclusion anywhere in this file.
+
+The maps are 3-level pyramids of 70 x 52 (dst) and 48 x 44 cells (src, its own start coordinates), and a pair of the same geometry,
+built by the product's own updates from hector_slam_amd.synth scans; both layouts.  Every case runs on the direct route; the
+cases run again in a child process with HSM_COPY_STAGE=1, which sends every merge through the staging patch of the cross-device
+route (on one device).
+
+At the parent commit every test of this file fails: the entries do not exist."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import merge_cases as mc
+from conftest import bits
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HSM_ERR_INVALID = -1
+F = np.float32
+LAYOUTS = pytest.mark.parametrize("layout", ("quad", "plane"))
+FACTORS = (0.4, 0.9)
+EMPTY = [0, 0, -1, -1]
+
+
+@pytest.fixture(scope="module")
+def capi():
+    import torch
+    assert torch.cuda.is_available(), "gpu-marked tests need a HIP device"
+    from hector_slam_amd import capi as m
+    m.load_library()
+    return m
+
+
+def new_ctx(capi, geom, layout):
+    g = capi.MapRepMultiMap(geom[0], geom[1], geom[2], geom[3], startCoords=geom[4],
+                            layout=capi.LAYOUT_QUAD if layout == "quad" else capi.LAYOUT_PLANE)
+    g.setUpdateFactorFree(FACTORS[0])
+    g.setUpdateFactorOccupied(FACTORS[1])
+    return g
+
+
+def single_update(capi, g, pose, pts):
+    """hsm_retain_scan (what matchData leaves for the coarse levels) + hsm_update_by_scan, which returns when it is queued"""
+    a = np.ascontiguousarray(pts, F).reshape(-1, 2)
+    capi._check(g._lib.hsm_retain_scan(g._h, a.ctypes.data, a.shape[0], np.zeros(2, F)), "hsm_retain_scan")
+    g.updateByScan(a, pose)
+
+
+def integrate(capi, g, scans):
+    for pose, pts in scans:
+        single_update(capi, g, pose, pts)
+
+
+def planes(g):
+    """[(log-odds, stamps)] per level"""
+    return [g.download_level(lvl) for lvl in range(g.getMapLevels())]
+
+
+def grid_probability(capi, g, logodds):
+    """grid_probability of map_cells.h for an array of log-odds, from the library's own expf (hsm_debug_expf)"""
+    lo = np.ascontiguousarray(logodds, F).reshape(-1)
+    e, p = np.empty_like(lo), np.empty_like(lo)
+    capi._check(g._lib.hsm_debug_expf(g._h, lo.size, lo, e, p), "hsm_debug_expf")
+    return p.reshape(np.shape(logodds))
+
+
+SRC_SCANS, DST_SCANS = mc.build_scans(31), mc.build_scans(77, n_scans=5)
+
+
+@pytest.fixture(scope="module")
+def maps(capi):
+    """maps(pair, layout) -> (dst as built, src, dst's planes, src's planes): built once per pair and layout, never changed
+    afterwards (a test clones dst with hsm_copy_map, which brings the counters along)"""
+    made = {}
+
+    def get(pair, layout):
+        if (pair, layout) not in made:
+            gd, gs = mc.PAIRS[pair]
+            dst, src = new_ctx(capi, gd, layout), new_ctx(capi, gs, layout)
+            integrate(capi, dst, DST_SCANS)
+            integrate(capi, src, SRC_SCANS)
+            made[pair, layout] = (dst, src, planes(dst), planes(src))
+        return made[pair, layout]
+    yield get
+    for dst, src, _, _ in made.values():
+        dst.close()
+        src.close()
+
+
+def clone(capi, g, geom, layout):
+    c = new_ctx(capi, geom, layout)
+    c.copy_map_from(g)
+    return c
+
+
+def expected_context(capi, geom, layout, want, stamps):
+    """a fresh context into which the model's planes were uploaded"""
+    exp = new_ctx(capi, geom, layout)
+    for lvl, (lo, st) in enumerate(zip(want, stamps)):
+        exp.upload_level(lvl, lo, st)
+    return exp
+
+
+def assert_reads_alike(dst, exp, what):
+    """a match, a score and a cast on both: stale texels or probabilities show here"""
+    pose0, pts = SRC_SCANS[2]
+    rng = np.random.default_rng(9)
+    starts = (pose0[None, :].astype(np.float64) + rng.uniform(-1, 1, (6, 3)) * [0.08, 0.08, 0.04]).astype(F)
+    a, b = dst.match_batch(starts, pts), exp.match_batch(starts, pts)
+    assert np.array_equal(bits(a[0]), bits(b[0])) and np.array_equal(bits(a[1]), bits(b[1])), (what, "match", a[0], b[0])
+    angles = np.linspace(-3.1, 3.1, 48).astype(F)
+    for lvl in range(mc.LEVELS):
+        sa, sb = dst.score_batch(lvl, starts, pts), exp.score_batch(lvl, starts, pts)
+        assert np.array_equal(bits(sa[0]), bits(sb[0])) and np.array_equal(bits(sa[1]), bits(sb[1])), (what, "score", lvl)
+        ca, cb = dst.cast_scans(lvl, starts[:3], angles, 8.0), exp.cast_scans(lvl, starts[:3], angles, 8.0)
+        assert np.array_equal(bits(ca[0]), bits(cb[0])) and np.array_equal(bits(ca[1]), bits(cb[1])), (what, "cast", lvl)
+
+
+# ---- 1. the cases ----------------------------------------------------------------------------------------------------------------------
+@LAYOUTS
+@pytest.mark.parametrize("pair,name,t", mc.CASES, ids=mc.CASE_IDS)
+def test_merged_state_is_the_models(capi, maps, layout, pair, name, t):
+    gd, gs = mc.PAIRS[pair]
+    built, src, dst_planes, src_planes = maps(pair, layout)
+    dst = clone(capi, built, gd, layout)
+    index = [dst.getUpdateIndex(lvl) for lvl in range(mc.LEVELS)]
+    for lvl in range(mc.LEVELS):
+        dst.take_dirty_bbox(lvl)
+    model = mc.merge_pyramid([p[0] for p in dst_planes], [p[0] for p in src_planes], gd, gs, t)
+    for lvl in range(mc.LEVELS):
+        assert capi.merge_map_box(dst, src, t, lvl).tolist() == list(model[lvl][1]), (lvl, "hsm_merge_map_box")
+    capi.merge_map(dst, src, t)   # queued: nothing has waited
+    nothing = all(box == mc.EMPTY for _, box in model)
+    assert nothing == (name == "misses")
+    changed = 0
+    for lvl, (lo, st) in enumerate(planes(dst)):
+        want, box = model[lvl]
+        print(pair, name, layout, "level", lvl, "box", box, "cells that differ from the model", int((bits(lo) != bits(want)).sum()),
+              "cells the merge changed", int((bits(want) != bits(dst_planes[lvl][0])).sum()))
+        assert np.array_equal(bits(lo), bits(want)), (lvl, "log odds", int((bits(lo) != bits(want)).sum()))
+        assert np.array_equal(st, dst_planes[lvl][1]), (lvl, "stamps")
+        assert np.array_equal(bits(dst.download_prob(lvl)), bits(grid_probability(capi, dst, want))), (lvl, "probabilities")
+        assert dst.getUpdateIndex(lvl) == index[lvl] + (0 if nothing else 1), (lvl, "update index")
+        assert dst.take_dirty_bbox(lvl).tolist() == list(box), (lvl, "dirty box")
+        changed += int((bits(want) != bits(dst_planes[lvl][0])).sum())
+    assert (changed > 0) == (not nothing), "the case merges something"
+    for lvl, (lo, st) in enumerate(planes(src)):   # src is only read
+        assert np.array_equal(bits(lo), bits(src_planes[lvl][0])) and np.array_equal(st, src_planes[lvl][1]), (lvl, "src")
+    exp = expected_context(capi, gd, layout, [m[0] for m in model], [p[1] for p in dst_planes])
+    assert_reads_alike(dst, exp, (pair, name, layout))
+    dst.close()
+    exp.close()
+
+
+def test_staged_route_gives_the_same_bits():
+    """the cases, the saturation and the ordering tests again with HSM_COPY_STAGE=1: every merge goes through the staging patch"""
+    if os.environ.get("HSM_COPY_STAGE") == "1":
+        pytest.fail("the child run must not select this test")
+    env = dict(os.environ, HSM_COPY_STAGE="1")
+    r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider", os.path.abspath(__file__),
+                        "-k", "merged_state or saturated or queued_on_src"], cwd=ROOT, env=env, capture_output=True, text=True,
+                       timeout=300)
+    assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-2000:]
+    assert "%d passed" % (2 * len(mc.CASES) + 2 + 2) in r.stdout, r.stdout[-2000:]
+
+
+# ---- 2. saturation -----------------------------------------------------------------------------------------------------------------------
+@LAYOUTS
+def test_saturated_cells_follow_the_rule_and_leave_no_nan(capi, layout):
+    geom = (mc.RES, 38, 25, 1, (0.5, 0.5))
+    values = F([49.5, 50.5, -60.0, 0.0, 1.25, -0.75, 50.0, -0.0])
+    rng = np.random.default_rng(4)
+    d_lo, s_lo = (rng.choice(values, (25, 38)).astype(F) for _ in range(2))
+    for k, dv in enumerate(values[:3]):       # every pairing of the three saturated values occurs
+        for j, sv in enumerate(values[:3]):
+            d_lo[1 + k, 1 + j], s_lo[1 + k, 1 + j] = dv, sv
+    s_lo[5, 5:9] = F([np.nan, np.inf, -np.inf, 3.0])   # not log-odds a map produces: they count as 0
+    stamps = np.full((25, 38), -1, np.int32)
+    dst, src = new_ctx(capi, geom, layout), new_ctx(capi, geom, layout)
+    dst.upload_level(0, d_lo, stamps)
+    src.upload_level(0, s_lo, stamps)
+    t = F([0, 0, 0])
+    capi.merge_map(dst, src, t)
+    want, box = mc.merge_model(d_lo, s_lo, geom, geom, 0, t)
+    assert box == (0, 0, 37, 24)
+    assert want[1, 1] == F(50.0) and want[2, 1] == F(50.5) and want[2, 2] == F(50.5) and want[3, 3] == F(-120.0)
+    assert want[1, 2] == F(50.0) and want[3, 1] == F(-10.5) and want[1, 3] == F(-10.5)
+    assert np.array_equal(bits(want[5, 5:8]), bits(d_lo[5, 5:8])), "NaN and the infinities count as 0"
+    lo, st = dst.download_level(0)
+    assert np.array_equal(bits(lo), bits(want)), int((bits(lo) != bits(want)).sum())
+    assert np.array_equal(st, stamps)
+    prob = dst.download_prob(0)
+    assert np.isfinite(prob).all() and np.array_equal(bits(prob), bits(grid_probability(capi, dst, want)))
+    exp = expected_context(capi, geom, layout, [want], [stamps])
+    cells = np.ascontiguousarray([(x + 0.25, y + 0.5) for y in range(24) for x in range(37)], F)
+    assert np.array_equal(bits(dst.eval_beams(0, np.zeros(3, F), cells)), bits(exp.eval_beams(0, np.zeros(3, F), cells)))
+    for g in (dst, src, exp):
+        g.close()
+
+
+# ---- 3. frozen cells -----------------------------------------------------------------------------------------------------------------------
+@LAYOUTS
+def test_frozen_cells_stay_frozen_under_a_later_update(capi, maps, layout):
+    gd, gs = mc.PAIRS["local"]
+    _, src, _, src_planes = maps("local", layout)
+    dst_lo = mc.synthetic_planes(gd, 3)
+    rng = np.random.default_rng(8)
+    stamps = [np.where(rng.random(lo.shape) < 0.4, 10 ** 6, -1).astype(np.int32) for lo in dst_lo]   # restored far ahead of the counter
+    t = F(dict(mc.TRANSFORMS)["theta_0.3"])
+    model = mc.merge_pyramid(dst_lo, [p[0] for p in src_planes], gd, gs, t)
+    dst, exp, live = (new_ctx(capi, gd, layout) for _ in range(3))
+    for lvl in range(mc.LEVELS):
+        dst.upload_level(lvl, dst_lo[lvl], stamps[lvl])
+        exp.upload_level(lvl, model[lvl][0], stamps[lvl])
+        live.upload_level(lvl, model[lvl][0], np.full_like(stamps[lvl], -1))
+    capi.merge_map(dst, src, t)
+    for g in (dst, exp, live):
+        single_update(capi, g, *DST_SCANS[1])
+    touched = 0
+    for lvl in range(mc.LEVELS):
+        lo, st = dst.download_level(lvl)
+        lo_e, st_e = exp.download_level(lvl)
+        assert np.array_equal(bits(lo), bits(lo_e)) and np.array_equal(st, st_e), (lvl, "the update after the merge")
+        assert np.array_equal(bits(dst.download_prob(lvl)), bits(exp.download_prob(lvl))), (lvl, "probabilities")
+        frozen = stamps[lvl] == 10 ** 6
+        assert np.array_equal(bits(lo[frozen]), bits(model[lvl][0][frozen])) and (st[frozen] == 10 ** 6).all(), (lvl, "frozen cells")
+        touched += int((bits(live.download_level(lvl)[0])[frozen] != bits(model[lvl][0])[frozen]).sum())
+    assert touched > 0, "the scan crosses cells that are frozen"
+    for g in (dst, exp, live):
+        g.close()
+
+
+# ---- 4. boxes and the published grid -----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("form", ("host", "device"))
+def test_dirty_and_publish_boxes_cover_the_merge(capi, maps, form):
+    import torch
+    gd, gs = mc.PAIRS["local"]
+    built, src, dst_planes, src_planes = maps("local", "quad")
+    dst = clone(capi, built, gd, "quad")
+    t = F(dict(mc.TRANSFORMS)["theta_-2.1"])
+    model = mc.merge_pyramid([p[0] for p in dst_planes], [p[0] for p in src_planes], gd, gs, t)
+    stream = torch.cuda.current_stream().cuda_stream
+    grids, d_boxes = [], []
+    for lvl in range(mc.LEVELS):   # a grid that is current, and empty boxes
+        sx, sy = mc.level_size(gd, lvl)
+        if form == "host":
+            grids.append(np.full((sy, sx), 55, np.int8))
+            dst.occupancy_changes(lvl, grids[lvl])
+        else:
+            grids.append(torch.full((sy, sx), 55, dtype=torch.int8, device="cuda:0"))
+            d_boxes.append(torch.full((4,), -9, dtype=torch.int32, device="cuda:0"))
+            dst.occupancy_changes_device(lvl, grids[lvl].data_ptr(), d_boxes[lvl].data_ptr(), stream)
+        dst.take_dirty_bbox(lvl)
+        last = dst.last_update_bbox(lvl).tolist()
+    capi.merge_map(dst, src, t)
+    for lvl in range(mc.LEVELS):
+        box = list(model[lvl][1])
+        assert box != EMPTY
+        assert dst.take_dirty_bbox(lvl).tolist() == box, (lvl, "dirty box")
+        if form == "host":
+            got, grid = dst.occupancy_changes(lvl, grids[lvl]).tolist(), grids[lvl]
+        else:
+            dst.occupancy_changes_device(lvl, grids[lvl].data_ptr(), d_boxes[lvl].data_ptr(), stream)
+            got, grid = d_boxes[lvl].cpu().numpy().tolist(), grids[lvl].cpu().numpy()
+        assert got[0] <= box[0] and got[1] <= box[1] and got[2] >= box[2] and got[3] >= box[3], (lvl, "publish box", got, box)
+        assert np.array_equal(grid, dst.occupancy_grid(lvl)), (lvl, "the grid kept current")
+        want = np.where(model[lvl][0] < 0, 0, np.where(model[lvl][0] > 0, 100, -1)).astype(np.int8)
+        assert np.array_equal(grid, want), (lvl, "the model's grid")
+    assert dst.last_update_bbox(mc.LEVELS - 1).tolist() == last, "hsm_last_update_bbox is left alone"
+    dst.close()
+
+
+# ---- 5. ordering -----------------------------------------------------------------------------------------------------------------------------
+@LAYOUTS
+def test_updates_queued_on_src_before_the_merge_are_seen_and_later_ones_are_not(capi, maps, layout):
+    gd, gs = mc.PAIRS["local"]
+    built, _, dst_planes, _ = maps("local", layout)
+    dst = clone(capi, built, gd, layout)
+    src, twin = new_ctx(capi, gs, layout), new_ctx(capi, gs, layout)
+    t = F(dict(mc.TRANSFORMS)["quarter_turn"])
+    integrate(capi, twin, SRC_SCANS[:4])      # what src holds where the merge is queued
+    at_merge = planes(twin)
+    integrate(capi, src, SRC_SCANS[:4])       # queued, not waited for
+    capi.merge_map(dst, src, t)
+    integrate(capi, src, SRC_SCANS[4:])       # queued behind the merge's read
+    integrate(capi, twin, SRC_SCANS[4:])
+    model = mc.merge_pyramid([p[0] for p in dst_planes], [p[0] for p in at_merge], gd, gs, t)
+    differs = 0
+    for lvl, (lo, _) in enumerate(planes(dst)):
+        assert np.array_equal(bits(lo), bits(model[lvl][0])), (lvl, int((bits(lo) != bits(model[lvl][0])).sum()))
+    after = planes(twin)
+    for lvl, (lo, st) in enumerate(planes(src)):
+        assert np.array_equal(bits(lo), bits(after[lvl][0])) and np.array_equal(st, after[lvl][1]), (lvl, "src's later updates")
+        late = mc.merge_model(dst_planes[lvl][0], after[lvl][0], gd, gs, lvl, t)[0]
+        differs += int((bits(late) != bits(model[lvl][0])).sum())
+    assert differs > 0, "the later updates would have shown in the merge"
+    for g in (dst, src, twin):
+        g.close()
+
+
+# ---- 6. the update index and the refusals ---------------------------------------------------------------------------------------------------
+def test_update_index_advances_by_one_per_level_and_not_on_a_miss(capi, maps):
+    gd, gs = mc.PAIRS["local"]
+    built, src, _, _ = maps("local", "quad")
+    dst = clone(capi, built, gd, "quad")
+    tr = dict(mc.TRANSFORMS)
+    index = [dst.getUpdateIndex(lvl) for lvl in range(mc.LEVELS)]
+    capi.merge_map(dst, src, F(tr["misses"]))
+    assert [dst.getUpdateIndex(lvl) for lvl in range(mc.LEVELS)] == index
+    capi.merge_map(dst, src, F(tr["identity"]))
+    assert [dst.getUpdateIndex(lvl) for lvl in range(mc.LEVELS)] == [i + 1 for i in index]
+    capi.merge_map(dst, src, F(tr["half_outside"]))
+    assert [dst.getUpdateIndex(lvl) for lvl in range(mc.LEVELS)] == [i + 2 for i in index]
+    single_update(capi, dst, *DST_SCANS[0])   # ... and an update counts on from there
+    assert [dst.getUpdateIndex(lvl) for lvl in range(mc.LEVELS)] == [i + 3 for i in index]
+    dst.close()
+
+
+def test_refusals_queue_nothing_and_change_nothing(capi, maps):
+    import torch
+    gd, gs = mc.PAIRS["local"]
+    built, src, _, src_planes = maps("local", "quad")
+    dst = clone(capi, built, gd, "quad")
+    others = {"a different level count": new_ctx(capi, (mc.RES, 48, 44, 2, (0.5, 0.5)), "quad"),
+              "a different layout": new_ctx(capi, gs, "plane"),
+              "a different resolution": new_ctx(capi, (0.05, 48, 44, 3, (0.5, 0.5)), "quad")}
+    grids = []
+    for lvl in range(mc.LEVELS):
+        dst.take_dirty_bbox(lvl)
+        sx, sy = mc.level_size(gd, lvl)
+        grids.append(np.full((sy, sx), 55, np.int8))
+        dst.occupancy_changes(lvl, grids[lvl])
+    before = planes(dst)
+    index = [dst.getUpdateIndex(lvl) for lvl in range(mc.LEVELS)]
+    lib, ok, box = dst._lib, F([0.1, 0.2, 0.3]), np.full(4, 7, np.int32)
+
+    def refused(rc, text):
+        msg = lib.hsm_last_error().decode()
+        assert rc == HSM_ERR_INVALID and text in msg, (rc, msg, text)
+
+    refused(lib.hsm_merge_map(None, src._h, ok.ctypes.data), "null context")
+    refused(lib.hsm_merge_map(dst._h, None, ok.ctypes.data), "null context")
+    refused(lib.hsm_merge_map(dst._h, src._h, None), "src_in_dst is null")
+    refused(lib.hsm_merge_map(dst._h, dst._h, ok.ctypes.data), "same context")
+    refused(lib.hsm_merge_map_box(dst._h, dst._h, ok.ctypes.data, 0, box.ctypes.data), "same context")
+    for k in range(3):
+        for bad in (np.nan, np.inf):
+            t = ok.copy()
+            t[k] = bad
+            refused(lib.hsm_merge_map(dst._h, src._h, t.ctypes.data), "not finite")
+            refused(lib.hsm_merge_map_box(dst._h, src._h, t.ctypes.data, 0, box.ctypes.data), "not finite")
+    for name, g in others.items():
+        refused(lib.hsm_merge_map(dst._h, g._h, ok.ctypes.data), "differ")
+        refused(lib.hsm_merge_map(g._h, dst._h, ok.ctypes.data), "differ")
+        refused(lib.hsm_merge_map_box(dst._h, g._h, ok.ctypes.data, 0, box.ctypes.data), "differ")
+    refused(lib.hsm_merge_map_box(dst._h, src._h, ok.ctypes.data, 0, None), "bbox is null")
+    refused(lib.hsm_merge_map_box(dst._h, src._h, ok.ctypes.data, -1, box.ctypes.data), "level out of range")
+    refused(lib.hsm_merge_map_box(dst._h, src._h, ok.ctypes.data, mc.LEVELS, box.ctypes.data), "level out of range")
+    assert box.tolist() == [7, 7, 7, 7]
+    # a capture in progress on a stream dst has matched on
+    pose0, pts = SRC_SCANS[2]
+    d = [torch.from_numpy(np.tile(pose0, (4, 1))).to("cuda:0"), torch.from_numpy(np.ascontiguousarray(pts, F)).to("cuda:0"),
+         torch.zeros((4, 3), device="cuda:0")]
+    s = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    launch = lambda: dst.match_batch_device(4, d[0].data_ptr(), d[1].data_ptr(), 0, len(pts), d[2].data_ptr(), 0, s.cuda_stream)
+    launch()
+    s.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, stream=s):
+        launch()
+        rcs = [lib.hsm_merge_map(dst._h, src._h, ok.ctypes.data), lib.hsm_merge_map(src._h, dst._h, ok.ctypes.data)]
+        msg = lib.hsm_last_error().decode()
+    assert rcs == [HSM_ERR_INVALID] * 2 and "captured" in msg, (rcs, msg)
+    torch.cuda.synchronize()
+    for lvl, (lo, st) in enumerate(planes(dst)):
+        assert np.array_equal(bits(lo), bits(before[lvl][0])) and np.array_equal(st, before[lvl][1]), (lvl, "dst after the refusals")
+        assert dst.getUpdateIndex(lvl) == index[lvl]
+        bb = dst.take_dirty_bbox(lvl)
+        assert bb[2] < bb[0], (lvl, "dirty box", bb)
+        bb = dst.occupancy_changes(lvl, grids[lvl])
+        assert bb[2] < bb[0], (lvl, "publish box", bb)
+    for lvl, (lo, st) in enumerate(planes(src)):
+        assert np.array_equal(bits(lo), bits(src_planes[lvl][0])) and np.array_equal(st, src_planes[lvl][1]), (lvl, "src")
+    capi.merge_map(dst, src, ok)   # ... and the capture over, the merge goes through
+    want = mc.merge_model(before[0][0], src_planes[0][0], gd, gs, 0, ok)[0]
+    assert np.array_equal(bits(dst.download_level(0)[0]), bits(want))
+    for g in [dst] + list(others.values()):
+        g.close()
