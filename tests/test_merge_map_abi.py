@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 
 import merge_cases as mc
+import newer_entry_cases as nc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ("hsm_merge_map", "hsm_merge_map_box")
@@ -84,9 +85,13 @@ def _exact(v):
     return repr(float(F(v)))
 
 
-@pytest.mark.parametrize("pair,name,t", mc.CASES, ids=mc.CASE_IDS)
-def test_host_arithmetic_gives_the_models_box_and_constants(box_check, pair, name, t):
-    gd, gs = mc.PAIRS[pair]
+# merge_cases' pairs and those of tests/newer_entry_cases.py: a start outside [0, 1], the far frame, 6 and 8 levels, the strip
+HOST_CASES = [mc.PAIRS[pair] + (t,) for pair, _, t in mc.CASES] + [nc.PAIRS[pair] + (nc.transform(pair, name),) for pair, name in nc.MERGE_CASES]
+HOST_IDS = mc.CASE_IDS + nc.MERGE_IDS
+
+
+@pytest.mark.parametrize("gd,gs,t", HOST_CASES, ids=HOST_IDS)
+def test_host_arithmetic_gives_the_models_box_and_constants(box_check, gd, gs, t):
     assert gd[0] == gs[0] and gd[3] == gs[3]
     args = [_exact(gd[0]), str(gd[1]), str(gd[2]), _exact(gd[4][0]), _exact(gd[4][1]), str(gs[1]), str(gs[2]), _exact(gs[4][0]),
             _exact(gs[4][1]), str(gd[3])] + [_exact(v) for v in t]
