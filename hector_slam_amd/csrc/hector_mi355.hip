@@ -448,11 +448,12 @@ int hsm_reset(hsm_ctx* h) {
   if (!h) return fail(HSM_ERR_INVALID, "null context");
   std::lock_guard<std::mutex> lk(h->mu);
   if (int rc = select_device(h)) return rc;
+  // first: it refuses a reset while a caller's stream is being captured; the folds below wait, which would invalidate that capture
+  if (int rc = order_after_foreign_match(h)) return rc;
   if (h->upd.upd_boxes_outstanding)
     if (int rc = merge_device_boxes(h)) return rc;
   if (h->upd.gate_outstanding)
     if (int rc = fold_gate_counters(h)) return rc;
-  if (int rc = order_after_foreign_match(h)) return rc;
   if (int rc = reset_update_gate(h)) return rc;
   for (Level& L : h->levels) {
     if (int rc = fill_level(h, L)) return rc;

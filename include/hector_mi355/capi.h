@@ -93,7 +93,22 @@ int hsm_create(float map_resolution, int size_x, int size_y, unsigned levels, fl
  * the runtime's per-thread error state is cleared (it is not left for the next hipGetLastError() of an unrelated call). */
 void hsm_destroy(hsm_ctx* h);
 
-/* replaces: MapRepMultiMap::reset -> MapProcContainer::reset  MapRepMultiMap.h:83-90, MapProcContainer.h:67-71 */
+/* replaces: MapRepMultiMap::reset -> MapProcContainer::reset  MapRepMultiMap.h:83-90, MapProcContainer.h:67-71
+ * Clears the cells, nothing else (GridMapBase::reset), on every level:
+ *   cleared  log-odds 0 and stamps -1, the probability / texel planes with them (0.5); the gate's pose back to FLT_MAX three
+ *            times (HectorSlamProcessor::reset); the largest restored stamp (the stamp-aware update form is deselected); the
+ *            last-update box empty; the dirty box and the publish box the whole level, so the first hsm_take_dirty_bbox and the
+ *            first export after it cover all of it.
+ *   stays    the update counters of the maps and the gate's count of applied scans (the reference does not rewind
+ *            currUpdateIndex: the first update afterwards stamps with counter + 1 / + 2), the key generation, the window start
+ *            an hsm_shift_map left (reset clears cells, not geometry), the update factors, gate thresholds, parity and
+ *            batch-order settings, the retained containers of the coarse levels (MapRepMultiMap::dataContainers survive: an
+ *            hsm_update_by_scan with no match in between marks the coarse levels with the scan matched before the reset), the
+ *            cached sensor geometries and every grown buffer.
+ * What gated and device-side calls left on the device (the count of applied scans, the update boxes) is folded in first, so no
+ * host query is needed in front of it.  It is a map update for ordering and capture purposes: stream-ordered behind every
+ * match queued on a caller's stream, refused with HSM_ERR_INVALID while such a stream is being captured; it returns when
+ * the cleared map is in place. */
 int hsm_reset(hsm_ctx* h);
 /* replaces: getMapLevels / getScaleToMap                      MapRepMultiMap.h:92-94 */
 int hsm_levels(const hsm_ctx* h);
