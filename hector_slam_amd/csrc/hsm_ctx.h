@@ -36,6 +36,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <string.h>
 
 #include <mutex>
 #include <string>
@@ -199,6 +200,16 @@ inline int stage_copy_out(const StagePlan& st, char* base, hipStream_t s) {
     if (st.r[i].dst && st.r[i].bytes)
       HIP_TRY(hipMemcpyAsync(st.r[i].dst, base + st.r[i].off, st.r[i].bytes, hipMemcpyDeviceToHost, s));
   return HSM_OK;
+}
+// The same two walks for a block in pinned, device-mapped host memory, which the kernels read and write where it lies: host copies,
+// the second one once the caller has waited for the stream
+inline void stage_fill_host(const StagePlan& st, char* base) {
+  for (int i = 0; i < st.n; ++i)
+    if (st.r[i].src && st.r[i].bytes) memcpy(base + st.r[i].off, st.r[i].src, st.r[i].bytes);
+}
+inline void stage_drain_host(const StagePlan& st, const char* base) {
+  for (int i = 0; i < st.n; ++i)
+    if (st.r[i].dst && st.r[i].bytes) memcpy(st.r[i].dst, base + st.r[i].off, st.r[i].bytes);
 }
 // the device address of a region; the three-argument form: null where the host array it stands for is absent
 template <class T>

@@ -63,6 +63,17 @@ void record_launch(hsm_ctx* h, const MatchPlan& plan) {
   h->last.last_kernel = plan.name;
   h->last.last_parity = plan.parity;
 }
+// ... and behind a sampler kernel (with_sampler_form): its name and the summation order the context ran it in
+void record_sampler_launch(hsm_ctx* h, const char* kernel) {
+  h->last.last_kernel = kernel;
+  h->last.last_parity = wants_exact(h) ? HSM_PARITY_EXACT : (h->cfg.parity.relaxed ? HSM_PARITY_RELAXED : HSM_PARITY_FAST);
+}
+
+// the ranking arguments that every match -> score -> winner entry refuses, device or host arrays alike: `lh` the scores it ranks by
+bool bad_ranking(int batch, int groups, const void* lh, const void* out_index, const void* group_offsets, int group_size) {
+  return groups < 0 ||
+         (groups > 0 && (!lh || !out_index || (!group_offsets && (group_size < 0 || (long long)groups * group_size > batch))));
+}
 
 // the one-workgroup-per-scan forms of this unit: Family::kExactDense, kSpec (gn_match_dense.h, gn_match_spec.h: `batch` workgroups) and
 // kSpec1 (one scan)
@@ -256,7 +267,6 @@ static int score_batch_device_nolock(hsm_ctx* h, int level, int batch, const flo
   if (int rc = order_map_reader(h, s, "hsm_score_batch_device", &fs)) return rc;
   const float factor = (float)(1.0 / pow(2.0, (double)level));
   const LevelView v = level_view(h->levels[level], factor, 1);
-  const bool exact = wants_exact(h);
   const int grid = (batch + 3) / 4;
   with_sampler_form(h, [&](auto lay, auto ex) {
     hipLaunchKernelGGL((score_batch_kernel<lay(), ex()>), dim3(grid), dim3(256), 0, s, v, d_poses_world, batch,
@@ -265,8 +275,7 @@ static int score_batch_device_nolock(hsm_ctx* h, int level, int batch, const flo
   });
   HIP_TRY(hipGetLastError());
   if (fs) fs->pending = true;
-  h->last.last_kernel = "score_batch_kernel";
-  h->last.last_parity = exact ? HSM_PARITY_EXACT : (h->cfg.parity.relaxed ? HSM_PARITY_RELAXED : HSM_PARITY_FAST);
+  record_sampler_launch(h, "score_batch_kernel");
   return HSM_OK;
 }
 
@@ -308,7 +317,6 @@ static int covariance_batch_device_nolock(hsm_ctx* h, int level, int batch, cons
   const float factor = (float)(1.0 / pow(2.0, (double)level));
   const Level& Lv = h->levels[level];
   const LevelView v = level_view(Lv, factor, 1);
-  const bool exact = wants_exact(h);
   const int grid = (batch + 3) / 4;
   with_sampler_form(h, [&](auto lay, auto ex) {
     hipLaunchKernelGGL((covariance_batch_kernel<lay(), ex()>), dim3(grid), dim3(256), 0, s, v, d_poses_world, batch,
@@ -317,8 +325,7 @@ static int covariance_batch_device_nolock(hsm_ctx* h, int level, int batch, cons
   });
   HIP_TRY(hipGetLastError());
   if (fs) fs->pending = true;
-  h->last.last_kernel = "covariance_batch_kernel";
-  h->last.last_parity = exact ? HSM_PARITY_EXACT : (h->cfg.parity.relaxed ? HSM_PARITY_RELAXED : HSM_PARITY_FAST);
+  record_sampler_launch(h, "covariance_batch_kernel");
   return HSM_OK;
 }
 
@@ -375,8 +382,8 @@ static int match_score_batch_device_nolock(hsm_ctx* h, int batch, const float* d
                                            float* d_out_best_pose, void* stream, int n_bound = 0) {
   if (int rc = valid_level(h, score_level)) return rc;
   if (batch < 0 || !d_begin_world || !d_out_pose || (!d_scan_offsets && shared_n < 0) || (!d_out_likelihood && !d_out_residual) ||
-      (batch > 0 && !d_pts_xy && !d_scan_offsets && shared_n > 0) || groups < 0 ||
-      (groups > 0 && (!d_out_likelihood || !d_out_index || (!d_group_offsets && (group_size < 0 || (long long)groups * group_size > batch)))))
+      (batch > 0 && !d_pts_xy && !d_scan_offsets && shared_n > 0) ||
+      bad_ranking(batch, groups, d_out_likelihood, d_out_index, d_group_offsets, group_size))
     return fail(HSM_ERR_INVALID, "hsm_match_score_batch_device: bad argument");
   if (int rc = match_batch_device_nolock(h, batch, d_begin_world, d_pts_xy, d_scan_offsets, shared_n, d_out_pose, d_out_cov, stream, n_bound))
     return rc;
@@ -426,8 +433,8 @@ int hsm_match_cov_batch_device(hsm_ctx* h, int batch, const float* d_begin_world
   if (cov_level < 0 || cov_level >= (int)h->levels.size()) return fail_at(HSM_ERR_INVALID, who, ": level out of range");
   if (batch < 0 || !d_begin_world || !d_out_pose || (!d_scan_offsets && shared_n < 0) ||
       (!d_out_cov_world && !d_out_cov_map && !d_out_lh7 && !d_out_likelihood) ||
-      (batch > 0 && !d_pts_xy && !d_scan_offsets && shared_n > 0) || groups < 0 ||
-      (groups > 0 && (!d_out_likelihood || !d_out_index || (!d_group_offsets && (group_size < 0 || (long long)groups * group_size > batch)))))
+      (batch > 0 && !d_pts_xy && !d_scan_offsets && shared_n > 0) ||
+      bad_ranking(batch, groups, d_out_likelihood, d_out_index, d_group_offsets, group_size))
     return fail_at(HSM_ERR_INVALID, who, ": bad argument");
   if (int rc = match_batch_device_nolock(h, batch, d_begin_world, d_pts_xy, d_scan_offsets, shared_n, d_out_pose, d_out_cov, stream))
     return rc;
@@ -491,39 +498,33 @@ static int match_batch_host(hsm_ctx* h, int batch, const float* begin_world, con
                             int shared_n, float* out_pose, float* out_cov, const BatchScoreReq* sr, const char* who) {
   if (!h) return fail(HSM_ERR_INVALID, "null context");
   if (batch < 0 || !begin_world || !out_pose) return fail(HSM_ERR_INVALID, who);
-  const int G = sr ? sr->groups : 0;
+  static const BatchScoreReq kNoScore = {};
+  const BatchScoreReq& r = sr ? *sr : kNoScore;
+  const int G = r.groups;
   if (sr) {
-    if (int rc = valid_level(h, sr->level)) return rc;
-    if (!sr->out_lh || G < 0 || (G > 0 && (!sr->out_index || (!sr->group_offsets && (sr->group_size < 0 || (long long)G * sr->group_size > batch)))))
-      return fail(HSM_ERR_INVALID, who);
-    if (G > 0 && sr->group_offsets)
+    if (int rc = valid_level(h, r.level)) return rc;
+    if (!r.out_lh || bad_ranking(batch, G, r.out_lh, r.out_index, r.group_offsets, r.group_size)) return fail(HSM_ERR_INVALID, who);
+    if (G > 0 && r.group_offsets)
       for (int g = 0; g < G; ++g)
-        if (sr->group_offsets[g] < 0 || sr->group_offsets[g] > sr->group_offsets[g + 1] || sr->group_offsets[g + 1] > batch)
+        if (r.group_offsets[g] < 0 || r.group_offsets[g] > r.group_offsets[g + 1] || r.group_offsets[g + 1] > batch)
           return fail(HSM_ERR_INVALID, who);
   }
   if (batch == 0) return HSM_OK;
   const size_t total = scan_offsets ? (size_t)scan_offsets[batch] : (size_t)(shared_n > 0 ? shared_n : 0);
   if (total > 0 && !pts_xy) return fail(HSM_ERR_INVALID, who);
-  BatchBytes b = {};  // (stage_layout.h: the match's own arrays, and behind them the score's and the ranking's)
-  b.begin = (size_t)batch * 3 * sizeof(float);
-  b.pts = total * 2 * sizeof(float);
-  b.offs = scan_offsets ? ((size_t)batch + 1) * sizeof(int) : 0;
-  b.cov = (size_t)batch * 9 * sizeof(float);
-  b.lh = sr ? (size_t)batch * sizeof(float) : 0, b.res = sr && sr->out_res ? b.lh : 0;
-  b.goffs = G > 0 && sr->group_offsets ? ((size_t)G + 1) * sizeof(int) : 0;
-  b.idx = (size_t)G * sizeof(int), b.bscore = G > 0 && sr->out_score ? (size_t)G * sizeof(float) : 0;
-  b.bpose = G > 0 && sr->out_best_pose ? (size_t)G * 3 * sizeof(float) : 0;
-  const BatchLayout L = batch_layout(b, !scan_offsets);
-  // the launches behind the copies in: x = the device address of the block
-  auto launch = [&](char* x, const float* d_pts, const int* d_offs, int n_or_hint, int n_bound) {
-    float* d_pose = (float*)(x + L.pose);
-    float* d_cov = out_cov ? (float*)(x + L.cov) : nullptr;
-    if (!sr) return match_batch_device_nolock(h, batch, (const float*)x, d_pts, d_offs, n_or_hint, d_pose, d_cov, h->stream, n_bound);
-    return match_score_batch_device_nolock(h, batch, (const float*)x, d_pts, d_offs, n_or_hint, d_pose, d_cov, sr->level,
-                                           (float*)(x + L.lh), b.res ? (float*)(x + L.res) : nullptr, G,
-                                           b.goffs ? (const int*)(x + L.goffs) : nullptr, sr->group_size, (int*)(x + L.idx),
-                                           b.bscore ? (float*)(x + L.bscore) : nullptr,
-                                           b.bpose ? (float*)(x + L.bpose) : nullptr, h->stream, n_bound);
+  const MatchBatchStage st = match_batch_stage(batch, total, G, !scan_offsets, begin_world, pts_xy, scan_offsets, out_pose, out_cov,
+                                               r.out_lh, r.out_res, r.group_offsets, r.out_index, r.out_score, r.out_best_pose);
+  // the launches behind the copies in: x = the device address of the block, d_pts = that of the end points
+  auto launch = [&](char* x, const float* d_pts, int n_or_hint, int n_bound) {
+    const float* d_begin = staged<float>(x, st.begin);
+    const int* d_offs = staged<int>(x, st.offs, scan_offsets);
+    float* d_pose = staged<float>(x, st.pose);
+    float* d_cov = staged<float>(x, st.cov, out_cov);
+    if (!sr) return match_batch_device_nolock(h, batch, d_begin, d_pts, d_offs, n_or_hint, d_pose, d_cov, h->stream, n_bound);
+    return match_score_batch_device_nolock(h, batch, d_begin, d_pts, d_offs, n_or_hint, d_pose, d_cov, r.level, staged<float>(x, st.lh),
+                                           staged<float>(x, st.res, r.out_res), G, staged<int>(x, st.goffs, r.group_offsets),
+                                           r.group_size, staged<int>(x, st.idx), staged<float>(x, st.bscore, r.out_score),
+                                           staged<float>(x, st.bpose, r.out_best_pose), h->stream, n_bound);
   };
   std::lock_guard<std::mutex> lk(h->mu);
   if (int rc = select_device(h)) return rc;
@@ -535,56 +536,29 @@ static int match_batch_host(hsm_ctx* h, int batch, const float* begin_world, con
     // one 8.6 KB copy + the launch, against three copies, the launch and two more copies of the general path below.
     // (With a score behind the match, its wavefront reads the matched pose back once and writes 4 or 8 bytes; the ranking reads
     // every likelihood once.)
-    if (!h->batch.h_hyp_pinned.holds(L.total)) HIP_TRY(hipStreamSynchronize(h->stream));
-    if (int rc = h->batch.h_hyp_pinned.reserve(L.total, kHalfMore)) return rc;
-    char* hp = h->batch.h_hyp_pinned;
-    memcpy(hp, begin_world, b.begin);
-    if (out_cov) memcpy(hp + L.cov, out_cov, b.cov);  // in/out: an empty scan leaves the caller's matrices untouched (ScanMatcher.h:68,189)
-    if (b.pts) memcpy(hp + L.pts, pts_xy, b.pts);
-    if (b.goffs) memcpy(hp + L.goffs, sr->group_offsets, b.goffs);
-    if (b.bpose) memcpy(hp + L.bpose, sr->out_best_pose, b.bpose);
+    Buf<char>& hyp = h->batch.h_hyp_pinned;
+    if (!hyp.holds(st.plan.total())) HIP_TRY(hipStreamSynchronize(h->stream));
+    if (int rc = hyp.reserve(st.plan.total(), kHalfMore)) return rc;
+    stage_fill_host(st.plan, hyp);
     char* dp = nullptr;
-    HIP_TRY(hipHostGetDevicePointer((void**)&dp, hp, 0));
+    HIP_TRY(hipHostGetDevicePointer((void**)&dp, hyp, 0));
     if (int rc = h->d_scan.reserve(total, kScanGrowth)) return rc;
-    if (b.pts) HIP_TRY(hipMemcpyAsync(h->d_scan, hp + L.pts, b.pts, hipMemcpyHostToDevice, h->stream));
-    if (int rc = launch(dp, (const float*)h->d_scan.p, nullptr, shared_n > 0 ? shared_n : 0, 0)) return rc;
+    if (total) HIP_TRY(hipMemcpyAsync(h->d_scan, hyp + st.pts, total * sizeof(float2), hipMemcpyHostToDevice, h->stream));
+    if (int rc = launch(dp, (const float*)h->d_scan.p, shared_n > 0 ? shared_n : 0, 0)) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));
-    memcpy(out_pose, hp + L.pose, b.begin);
-    if (out_cov) memcpy(out_cov, hp + L.cov, b.cov);
-    if (sr) {
-      memcpy(sr->out_lh, hp + L.lh, b.lh);
-      if (b.res) memcpy(sr->out_res, hp + L.res, b.res);
-      if (b.idx) memcpy(sr->out_index, hp + L.idx, b.idx);
-      if (b.bscore) memcpy(sr->out_score, hp + L.bscore, b.bscore);
-      if (b.bpose) memcpy(sr->out_best_pose, hp + L.bpose, b.bpose);
-    }
+    stage_drain_host(st.plan, hyp);
     return HSM_OK;
   }
-  if (int rc = h->d_batch.reserve(L.total)) return rc;
+  if (int rc = h->d_batch.reserve(st.plan.total())) return rc;
   char* base = h->d_batch;
-  const float* d_pts = (const float*)(base + L.pts);
-  const int* d_offs = (const int*)(base + L.offs);  // (scan_offsets is not null here)
-  HIP_TRY(hipMemcpyAsync(base, begin_world, b.begin, hipMemcpyHostToDevice, h->stream));
-  if (b.pts) HIP_TRY(hipMemcpyAsync(base + L.pts, pts_xy, b.pts, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(base + L.offs, scan_offsets, b.offs, hipMemcpyHostToDevice, h->stream));
-  if (out_cov) HIP_TRY(hipMemcpyAsync(base + L.cov, out_cov, b.cov, hipMemcpyHostToDevice, h->stream));  // in/out
-  if (b.goffs) HIP_TRY(hipMemcpyAsync(base + L.goffs, sr->group_offsets, b.goffs, hipMemcpyHostToDevice, h->stream));
-  if (b.bpose) HIP_TRY(hipMemcpyAsync(base + L.bpose, sr->out_best_pose, b.bpose, hipMemcpyHostToDevice, h->stream));  // in/out
+  if (int rc = stage_copy_in(st.plan, base, h->stream)) return rc;
   int hint = 0;
   for (int i = 0; i < batch; ++i) {
     const int ni = scan_offsets[i + 1] - scan_offsets[i];
     if (ni > hint) hint = ni;
   }
-  if (int rc = launch(base, d_pts, d_offs, hint, hint)) return rc;
-  HIP_TRY(hipMemcpyAsync(out_pose, base + L.pose, b.begin, hipMemcpyDeviceToHost, h->stream));
-  if (out_cov) HIP_TRY(hipMemcpyAsync(out_cov, base + L.cov, b.cov, hipMemcpyDeviceToHost, h->stream));
-  if (sr) {
-    HIP_TRY(hipMemcpyAsync(sr->out_lh, base + L.lh, b.lh, hipMemcpyDeviceToHost, h->stream));
-    if (b.res) HIP_TRY(hipMemcpyAsync(sr->out_res, base + L.res, b.res, hipMemcpyDeviceToHost, h->stream));
-    if (b.idx) HIP_TRY(hipMemcpyAsync(sr->out_index, base + L.idx, b.idx, hipMemcpyDeviceToHost, h->stream));
-    if (b.bscore) HIP_TRY(hipMemcpyAsync(sr->out_score, base + L.bscore, b.bscore, hipMemcpyDeviceToHost, h->stream));
-    if (b.bpose) HIP_TRY(hipMemcpyAsync(sr->out_best_pose, base + L.bpose, b.bpose, hipMemcpyDeviceToHost, h->stream));
-  }
+  if (int rc = launch(base, staged<float>(base, st.pts), hint, hint)) return rc;
+  if (int rc = stage_copy_out(st.plan, base, h->stream)) return rc;
   HIP_TRY(hipStreamSynchronize(h->stream));
   return HSM_OK;
 }

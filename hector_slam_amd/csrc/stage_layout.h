@@ -69,35 +69,6 @@ inline bool slam_ranges_tf_layout(int count, int n, SlamRangesTfLayout* L) {
   return true;
 }
 
-// staging block of hsm_match_batch / hsm_match_score_batch.  Sizes in bytes, 0 for an array the call does not have (pose = begin).
-struct BatchBytes {
-  size_t begin, pts, offs, cov;
-  size_t lh, res, goffs, idx, bscore, bpose;  // the score's and the ranking's arrays
-};
-// byte offsets; the start poses are at 0.  device block: begin | pts | offs | pose | cov, pinned block of the shared-scan form:
-// begin | pose | cov | pts; behind either: likelihood | residual | group offsets | winner index | winner score | winner pose
-struct BatchLayout {
-  size_t pts, offs, pose, cov, lh, res, goffs, idx, bscore, bpose, total;
-};
-
-inline BatchLayout batch_layout(const BatchBytes& b, bool pinned) {
-  Carver c;
-  BatchLayout L;
-  c.take(b.begin);
-  if (!pinned) L.pts = c.take(b.pts), L.offs = c.take(b.offs);
-  L.pose = c.take(b.begin);
-  L.cov = c.take(b.cov);
-  if (pinned) L.pts = c.take(b.pts), L.offs = c.take(b.offs);
-  L.lh = c.take(b.lh);
-  L.res = c.take(b.res);
-  L.goffs = c.take(b.goffs);
-  L.idx = c.take(b.idx);
-  L.bscore = c.take(b.bscore);
-  L.bpose = c.take(b.bpose);
-  L.total = c.total();
-  return L;
-}
-
 // The staging block of a host-array entry: its regions in the order they are carved, each with the host array that is copied
 // into it before the launches (src), the host array that receives it after them (dst), both (an in/out array) or neither (device
 // scratch).  A null array or an empty region is not copied; the copies are queued in the order of the list (hsm_ctx.h stage_copy_in /
@@ -134,6 +105,39 @@ inline UpdateScansStage update_scans_stage(int count, size_t total_pts, const fl
   s.pts = s.plan.add(total_pts * 2 * sizeof(float), pts);
   s.poses = s.plan.add((size_t)count * 3 * sizeof(float), poses);
   s.offs = s.plan.add(((size_t)count + 1) * sizeof(int), offsets);
+  return s;
+}
+
+// hsm_match_batch / hsm_match_score_batch.  A CSR batch (d_batch): start poses | end points | offsets | poses | covariances; the
+// pinned, device-mapped block of the shared-scan form (h_hyp_pinned), whose end points alone are copied on: start poses | poses |
+// covariances | end points; behind either: likelihood | residual | group offsets | winner index | winner score | winner pose.
+// The covariances (carved with or without the caller's array) and the winner poses go in and out: an empty scan and a group
+// without a winner leave the caller's.  The score's and the ranking's arrays the call does not have are not carved.
+struct MatchBatchStage {
+  StagePlan plan;
+  size_t begin, pts, offs, pose, cov, lh, res, goffs, idx, bscore, bpose;
+};
+
+inline MatchBatchStage match_batch_stage(int batch, size_t total_pts, int groups, bool pinned, const float* begin, const float* pts,
+                                         const int* offsets, float* out_pose, float* out_cov, float* out_lh, float* out_res,
+                                         const int* group_offsets, int* out_index, float* out_score, float* out_best_pose) {
+  const size_t b = (size_t)batch * sizeof(float), g = (size_t)groups;
+  MatchBatchStage s;
+  const auto scan = [&] {
+    s.pts = s.plan.add(total_pts * 2 * sizeof(float), pts);
+    s.offs = s.plan.add(offsets ? ((size_t)batch + 1) * sizeof(int) : 0, offsets);
+  };
+  s.begin = s.plan.add(3 * b, begin);
+  if (!pinned) scan();
+  s.pose = s.plan.add(3 * b, nullptr, out_pose);
+  s.cov = s.plan.add(9 * b, out_cov, out_cov);
+  if (pinned) scan();
+  s.lh = s.plan.add(out_lh ? b : 0, nullptr, out_lh);
+  s.res = s.plan.add(out_res ? b : 0, nullptr, out_res);
+  s.goffs = s.plan.add(g && group_offsets ? (g + 1) * sizeof(int) : 0, group_offsets);
+  s.idx = s.plan.add(g * sizeof(int), nullptr, out_index);
+  s.bscore = s.plan.add(out_score ? g * sizeof(float) : 0, nullptr, out_score);
+  s.bpose = s.plan.add(out_best_pose ? g * 3 * sizeof(float) : 0, out_best_pose, out_best_pose);
   return s;
 }
 
@@ -297,6 +301,47 @@ inline SlamRangesTfStage slam_ranges_tf_stage(int count, int n, bool shared_tf, 
   s.ws = s.plan.add(L.total);
   s.plan.view(s.cov, (size_t)count * 9 * sizeof(float), out_cov, nullptr);  // (in as well, behind the other copies in)
   s.plan.view(s.ws + L.origos, (size_t)count * 2 * sizeof(float), nullptr, out_origo);
+  return s;
+}
+
+// hsm_score_window (d_batch): centre pose | end points[n] | likelihoods[window] | residuals[window].  An output the caller does
+// not ask for is not carved: the kernel gets none.
+struct ScoreWindowStage {
+  StagePlan plan;
+  size_t center, pts, lh, res;
+};
+
+inline ScoreWindowStage score_window_stage(size_t window, int n, const float* center, const float* pts, float* out_lh, float* out_res) {
+  ScoreWindowStage s;
+  s.center = s.plan.add(3 * sizeof(float), center);
+  s.pts = s.plan.add((size_t)n * 2 * sizeof(float), pts);
+  s.lh = s.plan.add(out_lh ? window * sizeof(float) : 0, nullptr, out_lh);
+  s.res = s.plan.add(out_res ? window * sizeof(float) : 0, nullptr, out_res);
+  return s;
+}
+
+// hsm_relocalize (d_batch): centre pose | end points[n] | the device call's workspace | candidate poses[k * 3] | candidate
+// covariances[k * 9] | candidate likelihoods[k] | best pose | best score | best index.  The covariances and the best pose go in
+// and out: an empty scan leaves the caller's matrices, a search without a winner the caller's pose.
+struct RelocalizeStage {
+  StagePlan plan;
+  size_t center, pts, ws, pose, cov, lh, bpose, bscore, bidx;
+};
+
+inline RelocalizeStage relocalize_stage(int k, int n, size_t ws_bytes, const float* center, const float* pts, float* out_cand_pose,
+                                        float* out_cand_cov, float* out_cand_lh, float* out_best_pose, float* out_best_score,
+                                        int* out_best_index) {
+  const size_t kf = (size_t)k * sizeof(float);
+  RelocalizeStage s;
+  s.center = s.plan.add(3 * sizeof(float), center);
+  s.pts = s.plan.add((size_t)n * 2 * sizeof(float), pts);
+  s.ws = s.plan.add(ws_bytes);
+  s.pose = s.plan.add(3 * kf, nullptr, out_cand_pose);
+  s.cov = s.plan.add(out_cand_cov ? 9 * kf : 0, out_cand_cov, out_cand_cov);
+  s.lh = s.plan.add(kf, nullptr, out_cand_lh);
+  s.bpose = s.plan.add(3 * sizeof(float), out_best_pose, out_best_pose);
+  s.bscore = s.plan.add(out_best_score ? sizeof(float) : 0, nullptr, out_best_score);
+  s.bidx = s.plan.add(sizeof(int), nullptr, out_best_index);
   return s;
 }
 

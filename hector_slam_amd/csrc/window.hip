@@ -173,18 +173,15 @@ int hsm_score_window(hsm_ctx* h, int level, const float center_world[3], const f
     return rc;
   std::lock_guard<std::mutex> lk(h->mu);
   if (int rc = select_device(h)) return rc;
-  StagePlan st;
-  const size_t c = st.add(3 * sizeof(float), center_world);
-  const size_t p = st.add((size_t)n * 2 * sizeof(float), pts_xy);
-  const size_t lh = st.add(out_likelihood ? (size_t)W * sizeof(float) : 0, nullptr, out_likelihood);
-  const size_t res = st.add(out_residual ? (size_t)W * sizeof(float) : 0, nullptr, out_residual);
-  if (int rc = h->d_batch.reserve(st.total())) return rc;
+  const ScoreWindowStage st = score_window_stage((size_t)W, n, center_world, pts_xy, out_likelihood, out_residual);
+  if (int rc = h->d_batch.reserve(st.plan.total())) return rc;
   char* base = h->d_batch;
-  if (int rc = stage_copy_in(st, base, h->stream)) return rc;
-  if (int rc = score_window_launch(h, level, staged<float>(base, c), window_grid(step, half), (int)W, staged<float>(base, p), n,
-                                   staged<float>(base, lh, out_likelihood), staged<float>(base, res, out_residual), h->stream))
+  if (int rc = stage_copy_in(st.plan, base, h->stream)) return rc;
+  if (int rc = score_window_launch(h, level, staged<float>(base, st.center), window_grid(step, half), (int)W,
+                                   staged<float>(base, st.pts), n, staged<float>(base, st.lh, out_likelihood),
+                                   staged<float>(base, st.res, out_residual), h->stream))
     return rc;
-  if (int rc = stage_copy_out(st, base, h->stream)) return rc;
+  if (int rc = stage_copy_out(st.plan, base, h->stream)) return rc;
   HIP_TRY(hipStreamSynchronize(h->stream));
   return HSM_OK;
 }
@@ -240,26 +237,17 @@ int hsm_relocalize(hsm_ctx* h, int search_level, const float center_world[3], co
     return rc;
   std::lock_guard<std::mutex> lk(h->mu);
   if (int rc = select_device(h)) return rc;
-  StagePlan st;
-  const size_t k3 = (size_t)k * 3 * sizeof(float), k9 = (size_t)k * 9 * sizeof(float);
-  const size_t c = st.add(3 * sizeof(float), center_world);
-  const size_t p = st.add((size_t)n * 2 * sizeof(float), pts_xy);
-  const size_t ws = st.add(relocalize_layout(W, k).total);
-  const size_t pose = st.add(k3, nullptr, out_cand_pose);
-  const size_t cov = st.add(out_cand_cov ? k9 : 0, out_cand_cov, out_cand_cov);  // in/out: an empty scan leaves the caller's matrices
-  const size_t lh = st.add((size_t)k * sizeof(float), nullptr, out_cand_likelihood);
-  const size_t bpose = st.add(3 * sizeof(float), out_best_pose, out_best_pose);  // in/out: no winner keeps the caller's values
-  const size_t bscore = st.add(out_best_score ? sizeof(float) : 0, nullptr, out_best_score);
-  const size_t bidx = st.add(sizeof(int), nullptr, out_best_index);
-  if (int rc = h->d_batch.reserve(st.total())) return rc;
+  const RelocalizeStage st = relocalize_stage(k, n, relocalize_layout(W, k).total, center_world, pts_xy, out_cand_pose, out_cand_cov,
+                                              out_cand_likelihood, out_best_pose, out_best_score, out_best_index);
+  if (int rc = h->d_batch.reserve(st.plan.total())) return rc;
   char* base = h->d_batch;
-  if (int rc = stage_copy_in(st, base, h->stream)) return rc;
-  if (int rc = relocalize_queue(h, search_level, staged<float>(base, c), window_grid(step, half), (int)W, k, staged<float>(base, p),
-                                n, base + ws, staged<float>(base, pose), staged<float>(base, cov, out_cand_cov),
-                                staged<float>(base, lh), staged<float>(base, bpose), staged<float>(base, bscore, out_best_score),
-                                staged<int>(base, bidx), h->stream))
+  if (int rc = stage_copy_in(st.plan, base, h->stream)) return rc;
+  if (int rc = relocalize_queue(h, search_level, staged<float>(base, st.center), window_grid(step, half), (int)W, k,
+                                staged<float>(base, st.pts), n, base + st.ws, staged<float>(base, st.pose),
+                                staged<float>(base, st.cov, out_cand_cov), staged<float>(base, st.lh), staged<float>(base, st.bpose),
+                                staged<float>(base, st.bscore, out_best_score), staged<int>(base, st.bidx), h->stream))
     return rc;
-  if (int rc = stage_copy_out(st, base, h->stream)) return rc;
+  if (int rc = stage_copy_out(st.plan, base, h->stream)) return rc;
   HIP_TRY(hipStreamSynchronize(h->stream));
   return HSM_OK;
 }

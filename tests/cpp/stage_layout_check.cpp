@@ -2,9 +2,10 @@
 // the header existed: the workspace of hsm_match_batch_ranges_device, the staging blocks of hsm_match_batch /
 // hsm_match_score_batch (device and pinned form; with and without score, residual, ranking and its optional arrays) and the
 // growth rule of every grow-on-demand buffer; and the staging plans of the host-array entries built on StagePlan
-// (hsm_update_by_scans, hsm_match_batch_ranges, hsm_match_batch_ranges_tf, hsm_slam_ranges_tf, and the probes hsm_likelihood_states /
-// hsm_residual_states, hsm_covariance_for_poses, hsm_ray_distances) against each entry's layout written out term by term, with the
-// copies a plan asks for.  Every case is compared exactly; prints one JSON line, exits 1 on a mismatch.
+// (hsm_match_batch / hsm_match_score_batch themselves, hsm_update_by_scans, hsm_match_batch_ranges, hsm_match_batch_ranges_tf,
+// hsm_slam_ranges_tf, the probes hsm_likelihood_states / hsm_residual_states, hsm_covariance_for_poses, hsm_ray_distances, and the
+// window entries hsm_score_window, hsm_relocalize) against each entry's layout written out term by term, with the copies a plan
+// asks for.  Every case is compared exactly; prints one JSON line, exits 1 on a mismatch.
 #include <stdio.h>
 
 #include <utility>
@@ -21,6 +22,36 @@ static void same(size_t got, size_t want, const char* what, long long a, long lo
   ++cases;
   if (got == want) return;
   if (++mismatches <= 20) fprintf(stderr, "%s (%lld, %lld, %lld): %zu, written out %zu\n", what, a, b, c, got, want);
+}
+
+static const float kF[1] = {0};  // any non-null host array
+static const double kD[1] = {0};
+static const int kI[1] = {0};
+static const unsigned char kU[1] = {0};
+
+// the copies of a plan: region `off` is copied in from `src` / out to `dst` over `bytes`, and nothing else is
+struct WantCopy {
+  size_t off, bytes;
+  const void* src;
+  const void* dst;
+};
+static void check_copies(const StagePlan& p, const std::vector<WantCopy>& want, const char* what, long long a, long long b, long long c) {
+  size_t in = 0, out = 0, want_in = 0, want_out = 0;
+  for (const WantCopy& w : want) {
+    const bool does_in = w.src && w.bytes, does_out = w.dst && w.bytes;
+    want_in += does_in;
+    want_out += does_out;
+    bool found_in = !does_in, found_out = !does_out;
+    for (int i = 0; i < p.n; ++i) {
+      const StageRegion& r = p.r[i];
+      if (does_in && r.src == w.src && r.off == w.off && r.bytes == w.bytes) found_in = true;
+      if (does_out && r.dst == w.dst && r.off == w.off && r.bytes == w.bytes) found_out = true;
+    }
+    same(found_in && found_out, true, what, a, b, c);
+  }
+  for (int i = 0; i < p.n; ++i) in += p.r[i].src && p.r[i].bytes, out += p.r[i].dst && p.r[i].bytes;
+  same(in, want_in, what, a, b, c);
+  same(out, want_out, what, a, b, c);
 }
 
 static void check_ranges(int batch, int n) {
@@ -72,9 +103,20 @@ static void check_batch(size_t batch, size_t total_pts, size_t G, int flags, boo
     x = al(b_begin) + al(b_pts) + al(b_offs) + al(b_pose) + al(b_cov);
     total = al(b_begin) + al(b_pts) + al(b_offs) + al(b_pose) + al(b_cov) + b_extra;
   }
-  BatchBytes b = {b_begin, b_pts, b_offs, b_cov, b_lh, b_res, b_goffs, b_idx, b_bscore, b_bpose};
-  const BatchLayout L = batch_layout(b, pinned);
+  // the arrays of the call the flags describe (hsm_match_score_batch wants the likelihoods, and the winner index of a ranking)
+  float pose_out[1], cov_io[1], lh[1], res[1], bscore[1], bpose_io[1];
+  int idx[1];
+  const int* offsets = b_offs ? kI : nullptr;
+  float* out_lh = sr ? lh : nullptr;
+  float* out_res = sr && (flags & 2) ? res : nullptr;
+  const int* group_offsets = sr && (flags & 8) ? kI + 0 : nullptr;
+  int* out_index = G > 0 ? idx : nullptr;
+  float* out_score = sr && (flags & 16) ? bscore : nullptr;
+  float* out_best_pose = sr && (flags & 32) ? bpose_io : nullptr;
+  const MatchBatchStage L = match_batch_stage((int)batch, total_pts, (int)G, pinned, kF, kF + 0, offsets, pose_out, cov_io, out_lh,
+                                              out_res, group_offsets, out_index, out_score, out_best_pose);
   const long long key = flags + (pinned ? 1000 : 0);
+  same(L.begin, 0, "batch begin", batch, total_pts, key);
   same(L.pts, pts, "batch pts", batch, total_pts, key);
   if (!pinned) same(L.offs, offs, "batch offs", batch, total_pts, key);
   same(L.pose, pose, "batch pose", batch, total_pts, key);
@@ -85,7 +127,27 @@ static void check_batch(size_t batch, size_t total_pts, size_t G, int flags, boo
   same(L.idx, x + o_idx, "batch winner index", batch, total_pts, key);
   same(L.bscore, x + o_bscore, "batch winner score", batch, total_pts, key);
   same(L.bpose, x + o_bpose, "batch winner pose", batch, total_pts, key);
-  same(L.total, total, "batch total", batch, total_pts, key);
+  same(L.plan.total(), total, "batch total", batch, total_pts, key);
+  // start poses, end points, offsets and group offsets in; poses, likelihood, residual, winner index and score out; covariances
+  // and winner poses both ways; an array the call does not have, neither
+  check_copies(L.plan, {{0, b_begin, kF, nullptr}, {pts, b_pts, kF, nullptr}, {offs, b_offs, offsets, nullptr},
+                        {pose, b_pose, nullptr, pose_out}, {cov, b_cov, cov_io, cov_io}, {x, b_lh, nullptr, out_lh},
+                        {x + o_res, b_res, nullptr, out_res}, {x + o_goffs, b_goffs, group_offsets, nullptr},
+                        {x + o_idx, b_idx, nullptr, out_index}, {x + o_bscore, b_bscore, nullptr, out_score},
+                        {x + o_bpose, b_bpose, out_best_pose, out_best_pose}},
+               "batch copies", batch, total_pts, key);
+  // the copies are queued in the order of the list: that of the block, so begin, pts, offs, cov, group offsets, winner pose go in
+  for (int i = 0; i + 1 < L.plan.n; ++i) same(L.plan.r[i].off <= L.plan.r[i + 1].off, true, "batch copy order", batch, total_pts, key);
+  // ... and without the caller's covariances the region keeps its room and is copied neither way
+  const MatchBatchStage N = match_batch_stage((int)batch, total_pts, (int)G, pinned, kF, kF + 0, offsets, pose_out, nullptr, out_lh,
+                                              out_res, group_offsets, out_index, out_score, out_best_pose);
+  same(N.cov, cov, "batch cov, not asked for", batch, total_pts, key);
+  same(N.plan.total(), total, "batch total, cov not asked for", batch, total_pts, key);
+  check_copies(N.plan, {{0, b_begin, kF, nullptr}, {pts, b_pts, kF, nullptr}, {offs, b_offs, offsets, nullptr},
+                        {pose, b_pose, nullptr, pose_out}, {x, b_lh, nullptr, out_lh}, {x + o_res, b_res, nullptr, out_res},
+                        {x + o_goffs, b_goffs, group_offsets, nullptr}, {x + o_idx, b_idx, nullptr, out_index},
+                        {x + o_bscore, b_bscore, nullptr, out_score}, {x + o_bpose, b_bpose, out_best_pose, out_best_pose}},
+               "batch copies, cov not asked for", batch, total_pts, key);
 }
 
 static void check_growth(size_t n) {
@@ -104,36 +166,6 @@ static void check_growth(size_t n) {
 
 // ---- the staging plans of the host-array entries: offsets and totals written out term by term, as the entries carved them by hand
 // before StagePlan; and which regions are copied in and out (null array or empty region: no copy) ----
-static const float kF[1] = {0};  // any non-null host array
-static const double kD[1] = {0};
-static const int kI[1] = {0};
-static const unsigned char kU[1] = {0};
-
-// the copies of a plan: region `off` is copied in from `src` / out to `dst` over `bytes`, and nothing else is
-struct WantCopy {
-  size_t off, bytes;
-  const void* src;
-  const void* dst;
-};
-static void check_copies(const StagePlan& p, const std::vector<WantCopy>& want, const char* what, long long a, long long b, long long c) {
-  size_t in = 0, out = 0, want_in = 0, want_out = 0;
-  for (const WantCopy& w : want) {
-    const bool does_in = w.src && w.bytes, does_out = w.dst && w.bytes;
-    want_in += does_in;
-    want_out += does_out;
-    bool found_in = !does_in, found_out = !does_out;
-    for (int i = 0; i < p.n; ++i) {
-      const StageRegion& r = p.r[i];
-      if (does_in && r.src == w.src && r.off == w.off && r.bytes == w.bytes) found_in = true;
-      if (does_out && r.dst == w.dst && r.off == w.off && r.bytes == w.bytes) found_out = true;
-    }
-    same(found_in && found_out, true, what, a, b, c);
-  }
-  for (int i = 0; i < p.n; ++i) in += p.r[i].src && p.r[i].bytes, out += p.r[i].dst && p.r[i].bytes;
-  same(in, want_in, what, a, b, c);
-  same(out, want_out, what, a, b, c);
-}
-
 // flags: 1 pts, 2 offsets
 static void check_update_scans_stage(int count, size_t total, int flags) {
   const float* pts = flags & 1 ? kF : nullptr;
@@ -316,6 +348,59 @@ static void check_ray_distances_stage(int n, int flags) {
                "ray stage copies", n, flags, 0);
 }
 
+// flags: 1 out_lh, 2 out_residual, 4 pts
+static void check_score_window_stage(size_t window, int n, int flags) {
+  float lh[1], res[1];
+  float* out_lh = flags & 1 ? lh : nullptr;
+  float* out_res = flags & 2 ? res : nullptr;
+  const float* pts = flags & 4 ? kF + 0 : nullptr;
+  const size_t b_center = 3 * sizeof(float), b_pts = (size_t)n * 2 * sizeof(float);
+  const size_t b_lh = out_lh ? window * sizeof(float) : 0, b_res = out_res ? window * sizeof(float) : 0;
+  const ScoreWindowStage s = score_window_stage(window, n, kF, pts, out_lh, out_res);
+  same(s.center, 0, "window stage centre", window, n, flags);
+  same(s.pts, al(b_center), "window stage pts", window, n, flags);
+  same(s.lh, al(b_center) + al(b_pts), "window stage likelihood", window, n, flags);
+  same(s.res, al(b_center) + al(b_pts) + al(b_lh), "window stage residual", window, n, flags);
+  same(s.plan.total(), al(b_center) + al(b_pts) + al(b_lh) + al(b_res), "window stage total", window, n, flags);
+  check_copies(s.plan, {{0, b_center, kF, nullptr}, {al(b_center), b_pts, pts, nullptr}, {al(b_center) + al(b_pts), b_lh, nullptr, out_lh},
+                        {al(b_center) + al(b_pts) + al(b_lh), b_res, nullptr, out_res}},
+               "window stage copies", window, n, flags);
+}
+
+// flags: 1 out_cand_cov (in and out), 2 out_best_score, 4 pts
+static void check_relocalize_stage(int k, int n, size_t ws_bytes, int flags) {
+  float pose[1], cov[1], lh[1], bpose[1], bscore[1];
+  int bidx[1];
+  float* out_cov = flags & 1 ? cov : nullptr;
+  float* out_bscore = flags & 2 ? bscore : nullptr;
+  const float* pts = flags & 4 ? kF + 0 : nullptr;
+  const size_t b_center = 3 * sizeof(float), b_pts = (size_t)n * 2 * sizeof(float), b_pose = (size_t)k * 3 * sizeof(float);
+  const size_t b_cov = out_cov ? (size_t)k * 9 * sizeof(float) : 0, b_lh = (size_t)k * sizeof(float), b_bpose = 3 * sizeof(float);
+  const size_t b_bscore = out_bscore ? sizeof(float) : 0, b_bidx = sizeof(int);
+  const size_t o_pts = al(b_center), o_ws = al(b_center) + al(b_pts), o_pose = al(b_center) + al(b_pts) + al(ws_bytes);
+  const size_t o_cov = al(b_center) + al(b_pts) + al(ws_bytes) + al(b_pose);
+  const size_t o_lh = al(b_center) + al(b_pts) + al(ws_bytes) + al(b_pose) + al(b_cov);
+  const size_t o_bpose = al(b_center) + al(b_pts) + al(ws_bytes) + al(b_pose) + al(b_cov) + al(b_lh);
+  const size_t o_bscore = al(b_center) + al(b_pts) + al(ws_bytes) + al(b_pose) + al(b_cov) + al(b_lh) + al(b_bpose);
+  const size_t o_bidx = al(b_center) + al(b_pts) + al(ws_bytes) + al(b_pose) + al(b_cov) + al(b_lh) + al(b_bpose) + al(b_bscore);
+  const RelocalizeStage s = relocalize_stage(k, n, ws_bytes, kF, pts, pose, out_cov, lh, bpose, out_bscore, bidx);
+  const long long key = flags + 1000 * (long long)ws_bytes;
+  same(s.center, 0, "relocalize stage centre", k, n, key);
+  same(s.pts, o_pts, "relocalize stage pts", k, n, key);
+  same(s.ws, o_ws, "relocalize stage workspace", k, n, key);
+  same(s.pose, o_pose, "relocalize stage poses", k, n, key);
+  same(s.cov, o_cov, "relocalize stage covariances", k, n, key);
+  same(s.lh, o_lh, "relocalize stage likelihoods", k, n, key);
+  same(s.bpose, o_bpose, "relocalize stage best pose", k, n, key);
+  same(s.bscore, o_bscore, "relocalize stage best score", k, n, key);
+  same(s.bidx, o_bidx, "relocalize stage best index", k, n, key);
+  same(s.plan.total(), o_bidx + al(b_bidx), "relocalize stage total", k, n, key);
+  check_copies(s.plan, {{0, b_center, kF, nullptr}, {o_pts, b_pts, pts, nullptr}, {o_pose, b_pose, nullptr, pose},
+                        {o_cov, b_cov, out_cov, out_cov}, {o_lh, b_lh, nullptr, lh}, {o_bpose, b_bpose, bpose, bpose},
+                        {o_bscore, b_bscore, nullptr, out_bscore}, {o_bidx, b_bidx, nullptr, bidx}},
+               "relocalize stage copies", k, n, key);
+}
+
 int main() {
   // sizes around the 256-byte multiples of every element size in play (4, 8, 12, 36 bytes), and the ends of the ranges
   std::vector<long long> sizes = {0, 1, 2, 3, 5, 7, 21, 22, 31, 32, 33, 63, 64, 65, 85, 86, 127, 128, 129, 255, 256, 257, 1023, 1024,
@@ -376,6 +461,16 @@ int main() {
   }
   for (int n : {0, 1, 65})
     for (int flags = 0; flags < 2; ++flags) check_ray_distances_stage(n, flags);
+  // the window entries' plans: windows of one pose, either side of a 256-byte multiple and of the lane form's 65536; k from 1 to
+  // HSM_MAX_TOPK either side of the multiples 12-, 36- and 4-byte elements reach; a workspace of any size, aligned or not
+  for (int n : {0, 1, 32, 33, 1081})
+    for (int flags = 0; flags < 8; ++flags) {
+      for (size_t window : {(size_t)1, (size_t)63, (size_t)64, (size_t)65, (size_t)1089, (size_t)65536, (size_t)INT_MAX})
+        check_score_window_stage(window, n, flags);
+      for (int k : {1, 7, 8, 21, 22, 63, HSM_MAX_TOPK})
+        for (size_t ws : {(size_t)0, (size_t)8, (size_t)255, (size_t)256, (size_t)257, (size_t)4356 + 1024, (size_t)INT_MAX * 4 + 4096})
+          check_relocalize_stage(k, n, ws, flags);
+    }
   printf("{\"cases\": %lld, \"mismatches\": %lld}\n", cases, mismatches);
   return mismatches ? 1 : 0;
 }

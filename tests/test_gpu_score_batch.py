@@ -317,6 +317,94 @@ def test_match_score_select_chain_on_one_stream(capi, pyramid_scene, chain_case)
     g.close()
 
 
+def test_host_entry_gives_the_device_entrys_bits_with_every_optional_array(capi, oracle_mod, small_scene):
+    """hsm_match_batch and hsm_match_score_batch stage their arrays through one plan (stage_layout.h match_batch_stage): a CSR
+    batch through device memory, hypotheses of one scan through pinned memory.  With every combination of the optional arrays
+    either route gives the bits of the _device entry called on the same inputs uploaded by hand, and an in/out array the call
+    must leave alone -- the covariance of the empty scan, the winner pose of a group without a finite score -- keeps the
+    caller's values, as does every array of a ranking that was not asked for."""
+    import itertools
+    import torch
+    from hector_slam_amd import synth
+    sc = small_scene
+    g = gpu_for(capi, sc, make_oracle(oracle_mod, "ho", sc))
+    lib = capi.load_library()
+    rng = np.random.default_rng(31)
+    B, lens = 8, (0, 1, 63, 64, 65, 181, 200, 200)
+    sfac = float(np.float32(1.0) / np.float32(sc.resolution))
+    scan = np.ascontiguousarray(synth.make_scan(sc.world, sc.query_truth[0], 200, sfac, rng, pad_to_full=True), np.float32)
+    assert scan.shape == (200, 2)
+    init = (sc.query_truth[0][None, :] + rng.uniform(-1, 1, (B, 3)) * [0.1, 0.1, 0.03]).astype(np.float32)
+    routes = {"csr": pack([scan[:n] for n in lens]), "shared": (scan, None)}
+    # (groups, group offsets, group size): eight groups of one -- on the CSR route the first holds the empty scan alone, whose score
+    # is NaN -- and four ragged groups, the first the same and the third empty
+    rankings = {"none": (0, None, 0), "group_size": (B, None, 1), "group_offsets": (4, np.array([0, 1, 4, 4, 8], np.int32), 0)}
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def fresh(G):
+        f = lambda *shape: np.full(shape, SENTINEL, np.float32)  # noqa: E731
+        return dict(pose=f(B, 3), cov=f(B, 9), lh=f(B), res=f(B), idx=np.full(max(G, 1), 99, np.int32), best=f(max(G, 1)),
+                    best_pose=f(max(G, 1), 3))
+
+    def run(route, scored, want, rank):
+        """the host entry on numpy arrays and the _device entry on their uploads -> both sets of arrays, every one of them
+        pre-filled with the sentinel and handed over only where `want` says so"""
+        pts, offs = routes[route]
+        G, goffs, gsize = rankings[rank]
+        host, up = fresh(G), {k: dev(v) for k, v in fresh(G).items()}
+        d_init, d_pts = dev(init), dev(pts)
+        d_offs, d_goffs = (None if a is None else dev(a) for a in (offs, goffs))
+        hp = lambda a, on=True: a.ctypes.data if on and a is not None else None  # noqa: E731
+        dp = lambda t, on=True: t.data_ptr() if on and t is not None else None  # noqa: E731
+        n_host, n_dev = (len(pts), len(pts)) if offs is None else (0, max(lens))  # (a CSR device call: the sizing hint)
+        if not scored:
+            rc = lib.hsm_match_batch(g._h, B, init.reshape(-1), hp(pts), hp(offs), n_host, host["pose"].reshape(-1),
+                                     hp(host["cov"], want["cov"]))
+            rd = lib.hsm_match_batch_device(g._h, B, dp(d_init), dp(d_pts), dp(d_offs), n_dev, dp(up["pose"]),
+                                            dp(up["cov"], want["cov"]), stream or None)
+        else:
+            rc = lib.hsm_match_score_batch(g._h, B, hp(init), hp(pts), hp(offs), n_host, hp(host["pose"]), hp(host["cov"], want["cov"]),
+                                           0, hp(host["lh"]), hp(host["res"], want["res"]), G, hp(goffs), gsize, hp(host["idx"]),
+                                           hp(host["best"], want["best"]), hp(host["best_pose"], want["best_pose"]))
+            rd = lib.hsm_match_score_batch_device(g._h, B, dp(d_init), dp(d_pts), dp(d_offs), n_dev, dp(up["pose"]),
+                                                  dp(up["cov"], want["cov"]), 0, dp(up["lh"]), dp(up["res"], want["res"]), G,
+                                                  dp(d_goffs), gsize, dp(up["idx"]), dp(up["best"], want["best"]),
+                                                  dp(up["best_pose"], want["best_pose"]), stream or None)
+        assert rc == 0 and rd == 0, (route, scored, want, rank, rc, rd, lib.hsm_last_error())
+        return host, {k: v.cpu().numpy() for k, v in up.items()}
+
+    def check(route, scored, want, rank):
+        what = (route, scored, want, rank)
+        G = rankings[rank][0]
+        host, device = run(route, scored, want, rank)
+        assert_same_results(what, host, device)
+        untouched = lambda a: (a == (99 if a.dtype == np.int32 else SENTINEL)).all()  # noqa: E731
+        assert not (host["pose"] == SENTINEL).any(), what
+        empty_scans = [b for b, n in enumerate(lens) if n == 0] if route == "csr" else []
+        for b in range(B):  # in/out: the matcher leaves an empty scan's covariance as the caller had it
+            assert untouched(host["cov"][b]) == (not want["cov"] or b in empty_scans), (what, b)
+        assert untouched(host["lh"]) == (not scored) and untouched(host["res"]) == (not (scored and want["res"])), what
+        if not G:
+            assert untouched(host["idx"]) and untouched(host["best"]) and untouched(host["best_pose"]), what
+            return
+        _, goffs, gsize = rankings[rank]
+        want_idx, _ = select_rule.select_best(host["lh"], **(dict(groups=G, group_size=gsize) if goffs is None else dict(group_offsets=goffs)))
+        assert np.array_equal(host["idx"], want_idx), what
+        no_winner = want_idx < 0
+        # (the cases do hold such groups: the empty scan alone, whose score is NaN, and the empty group)
+        assert all(no_winner[k] for k in {"group_size": empty_scans, "group_offsets": [2] + [0] * (route == "csr")}[rank]), what
+        for k in range(G):  # in/out: a group without a finite score keeps the caller's winner pose
+            assert untouched(host["best_pose"][k]) == (not want["best_pose"] or no_winner[k]), (what, k)
+        assert untouched(host["best"]) == (not want["best"]), what
+
+    for route in routes:
+        for cov in (True, False):
+            check(route, False, dict(cov=cov, res=False, best=False, best_pose=False), "none")
+        for cov, res, rank, best, best_pose in itertools.product((True, False), (True, False), rankings, (True, False), (True, False)):
+            check(route, True, dict(cov=cov, res=res, best=best, best_pose=best_pose), rank)
+    g.close()
+
+
 # ---- 5: selection alone -----------------------------------------------------------------------------------------------------
 def run_select(g, scores, poses=None, groups=None, group_size=None, group_offsets=None):
     import torch
