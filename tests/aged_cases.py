@@ -15,6 +15,7 @@ bit for bit.
 import numpy as np
 
 import border_cases as bc
+from support import upload_planes
 
 RES, START = bc.RES, bc.START
 GEOMETRIES = [bc.GEOMETRIES[0], bc.GEOMETRIES[1]]  # (64, 64, 2), (90, 24, 2)
@@ -73,9 +74,7 @@ def planes(family, geom, seed=0):
 
 def upload(m, family, geom, seed=0):
     """the family's planes into a checker (pyoracle.Oracle) or a device context (capi.MapRepMultiMap)"""
-    for lvl, (lo, ui) in enumerate(planes(family, geom, seed)):
-        m.upload_level(lvl, lo, ui)
-    return m
+    return upload_planes(m, planes(family, geom, seed))
 
 
 def prob_plane(pyoracle, family, geom, lvl, kind="ho"):

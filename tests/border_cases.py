@@ -17,6 +17,8 @@ poses (0, 0, 0) and (-0.0, -0.0, +-0.0) of ZERO_POSES, which only the entries th
 """
 import numpy as np
 
+from support import upload_planes
+
 RES = 0.125
 START = (0.5, 0.5)
 LEVELS = 2
@@ -66,9 +68,7 @@ def map_planes(geom):
 
 def upload(m, geom):
     """the same planes into a checker (pyoracle.Oracle) or a device context (capi.MapRepMultiMap): both have upload_level"""
-    for lvl, (lo, ui) in enumerate(map_planes(geom)):
-        m.upload_level(lvl, lo, ui)
-    return m
+    return upload_planes(m, map_planes(geom))
 
 
 def new_oracle(pyoracle, kind, geom):

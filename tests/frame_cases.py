@@ -16,6 +16,7 @@ pose conversions (GridMapBase.h:226-239, :265-280, MapRepMultiMap.h:48-69), writ
 import numpy as np
 
 import border_cases as bc
+from support import upload_planes
 
 _F = np.float32
 CONTROL = (0.125, (0.5, 0.5))
@@ -141,9 +142,7 @@ def map_planes(geom):
 
 def upload(m, geom):
     """the same planes into a checker or a device context: both have upload_level"""
-    for lvl, (lo, ui) in enumerate(map_planes(geom)):
-        m.upload_level(lvl, lo, ui)
-    return m
+    return upload_planes(m, map_planes(geom))
 
 
 def new_oracle(pyoracle, kind, frame, geom, factors=None):

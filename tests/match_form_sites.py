@@ -17,6 +17,8 @@ Every launch is a few milliseconds on an empty map: the form depends on the call
 """
 import os
 
+from support import layout_of
+
 KNOBS = ("HSM_EXACT_CHAIN_WAVE", "HSM_EXACT_SPLIT_TAIL", "HSM_EXACT_CACHED", "HSM_EXACT_DENSE", "HSM_EXACT_DENSE_MIN",
          "HSM_TEXEL_CACHE", "HSM_BPL", "HSM_SPB_LARGE", "HSM_EXACT_SPEC", "HSM_EXACT_SPEC1", "HSM_COOP_MIN", "HSM_WPS")
 # ... and what else of the environment would change a form: cleared while a context is created
@@ -192,7 +194,7 @@ class Runner:
                 for k, v in site["env"].items():
                     os.environ[k] = str(v)
                 self.ctx = self.capi.MapRepMultiMap(0.05, sx, sy, levels, device=0,
-                                                    layout=self.capi.LAYOUT_QUAD if site["layout"] == "quad" else self.capi.LAYOUT_PLANE)
+                                                    layout=layout_of(self.capi, site["layout"]))
             finally:
                 for k, v in saved.items():
                     os.environ.pop(k, None)

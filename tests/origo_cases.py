@@ -10,6 +10,8 @@ import functools
 
 import numpy as np
 
+import support
+
 RES = 0.05
 LEVELS = 3
 N = 24
@@ -43,15 +45,8 @@ def force_mask():
 
 
 def new_refs(oracle_mod, geom="square", kinds=None):
-    from conftest import oracle_kinds
     sx, sy = GEOMS[geom]
-    refs = {}
-    for kind in (kinds or oracle_kinds()):
-        o = oracle_mod.Oracle(kind, RES, sx, sy, LEVELS)
-        o.set_update_factor_free(0.4)
-        o.set_update_factor_occupied(0.9)
-        refs[kind] = o
-    return refs
+    return support.new_refs(oracle_mod, RES, sx, sy, LEVELS, kinds=kinds)
 
 
 def ref_update(o, pose, pts, origo):

@@ -32,6 +32,7 @@ import numpy as np
 import border_cases as bc
 import order_cases as oc
 from edge_cases import world_pose_of_cell
+from support import upload_planes
 
 RES = oc.RES
 FACTOR_FREE, FACTOR_OCC = oc.FACTOR_FREE, oc.FACTOR_OCC
@@ -232,9 +233,7 @@ def planes(geom, U):
 
 def upload(m, geom, U):
     """the planes into a checker (pyoracle.Oracle) or a device context (capi.MapRepMultiMap)"""
-    for lvl, (lo, ui) in enumerate(planes(geom, U)):
-        m.upload_level(lvl, lo, ui)
-    return m
+    return upload_planes(m, planes(geom, U))
 
 
 # ---- the checkers -------------------------------------------------------------------------------------------------------------------

@@ -12,14 +12,11 @@ import pytest
 import aged_cases as ac
 import gn_f64
 from conftest import bits
+from support import same
 
 GEOMS = pytest.mark.parametrize("geom", ac.GEOMETRIES, ids=ac.gid)
 F = np.float32
 MAX_UNDEFINED = 0.10   # of a family's cases, `tiny` excepted
-
-
-def same(a, b):
-    return np.array_equal(bits(a), bits(b))
 
 
 def same_or_nan(a, b):

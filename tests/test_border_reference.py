@@ -7,12 +7,9 @@ import pytest
 
 import border_cases as bc
 from conftest import bits, oracle_kinds
+from support import same
 
 GEOMS = pytest.mark.parametrize("geom", bc.GEOMETRIES, ids=bc.gid)
-
-
-def same(a, b):
-    return np.array_equal(bits(a), bits(b))
 
 
 def interp_numpy(oracle_mod, geom, lvl, coords):

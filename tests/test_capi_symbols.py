@@ -5,13 +5,13 @@ import re
 
 import pytest
 
+from support import compile_c99, header_code
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def declared_symbols():
-    src = open(os.path.join(ROOT, "include", "hector_mi355", "capi.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(hsm_[a-z0-9_]+)\s*\(", src)))
+    return sorted(set(re.findall(r"\b(hsm_[a-z0-9_]+)\s*\(", header_code())))
 
 
 def test_header_and_binding_agree():
@@ -58,13 +58,9 @@ def test_product_never_references_the_oracle():
 
 def test_header_is_plain_c99(tmp_path):
     """the boundary is a C ABI: the header must compile as C (what cgo / JNI / ctypes-style bindings consume)"""
-    import subprocess
-    src = tmp_path / "use.c"
-    src.write_text('#include "hector_mi355/capi.h"\n'
-                   'int main(void) { hsm_ctx* h = 0; hsm_opts o = {-1, HSM_LAYOUT_AUTO, 0}; (void)o;\n'
-                   '  return hsm_create(0.05f, 64, 64, 1u, 0.5f, 0.5f, &o, &h) == HSM_OK ? 0 : 1; }\n')
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-c", str(src), "-I",
-                    os.path.join(ROOT, "include"), "-o", str(tmp_path / "use.o")], check=True)
+    compile_c99(tmp_path,
+                'int main(void) { hsm_ctx* h = 0; hsm_opts o = {-1, HSM_LAYOUT_AUTO, 0}; (void)o;\n'
+                '  return hsm_create(0.05f, 64, 64, 1u, 0.5f, 0.5f, &o, &h) == HSM_OK ? 0 : 1; }\n')
 
 
 def test_rccl_is_loaded_on_demand_not_linked():

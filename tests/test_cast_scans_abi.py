@@ -8,35 +8,20 @@ be checked without a GPU.
   states.
 """
 import ctypes as C
-import os
-import re
-import subprocess
 
 import numpy as np
 
 import cast_cases
+from support import check_symbols, compile_c99, header_text
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ("hsm_ray_distances_device", "hsm_cast_scans_device", "hsm_cast_scans")
 HSM_ERR_INVALID = -1
 
 
-def _header():
-    return open(os.path.join(ROOT, "include", "hector_mi355", "capi.h")).read()
-
-
 def test_new_symbols_declared_bound_and_exported():
     from hector_slam_amd import build, capi
-    code = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-    build.build_native()
-    lib = capi.load_library()
-    for name in NEW_SYMBOLS:
-        assert re.search(r"\bint\s+" + name + r"\s*\(", code), name
-        assert name in capi.SIGNATURES, name
-        assert hasattr(lib, name), name
-        decl = re.search(r"\b" + name + r"\s*\((.*?)\)\s*;", code, re.S).group(1)
-        assert len(capi.SIGNATURES[name][1]) == decl.count(",") + 1, (name, decl)
-    head = _header()
+    check_symbols(NEW_SYMBOLS)
+    head = header_text()
     assert "5000 steps" in head and "either end point outside the level" in head and "non-finite" in head
     for meth in ("cast_scans", "cast_scans_device", "ray_distances_device"):
         assert callable(getattr(capi.MapRepMultiMap, meth)), meth
@@ -44,15 +29,12 @@ def test_new_symbols_declared_bound_and_exported():
 
 
 def test_header_with_the_new_entries_is_plain_c99(tmp_path):
-    src = tmp_path / "use.c"
-    src.write_text('#include "hector_mi355/capi.h"\n'
-                   "int main(void) { hsm_ctx* h = 0; float f[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};\n"
-                   "  int rc = hsm_ray_distances_device(h, 0, 0.0f, 0.0f, 0.05f, 1, f, f, f, 0, 0);\n"
-                   "  rc += hsm_cast_scans_device(h, 0, 1, f, f, 1, 30.0f, f, 0, 0);\n"
-                   "  rc += hsm_cast_scans(h, 0, 1, f, f, 1, 30.0f, f, f);\n"
-                   "  return rc; }\n")
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-c", str(src), "-I",
-                    os.path.join(ROOT, "include"), "-o", str(tmp_path / "use.o")], check=True)
+    compile_c99(tmp_path,
+                "int main(void) { hsm_ctx* h = 0; float f[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};\n"
+                "  int rc = hsm_ray_distances_device(h, 0, 0.0f, 0.0f, 0.05f, 1, f, f, f, 0, 0);\n"
+                "  rc += hsm_cast_scans_device(h, 0, 1, f, f, 1, 30.0f, f, 0, 0);\n"
+                "  rc += hsm_cast_scans(h, 0, 1, f, f, 1, 30.0f, f, f);\n"
+                "  return rc; }\n")
 
 
 def test_null_context_is_invalid_for_every_new_entry():

@@ -3,20 +3,16 @@ the texel box, the staging patch) on the CPU: tests/cpp/copy_box_check.cpp compi
 holds it to a cell-by-cell restatement for every box of three row ranges on levels 25, 38 and 40 cells wide -- an odd width, an
 even one that is no multiple of 4, and a multiple of 4, so every phase of a run's first cell against the 4-cell alignment
 occurs, boxes that touch x = 0 and y = 0 included, and whole-width boxes, which are one run.  Equality of planes: no tolerance."""
-import os
 import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from support import build_check
 
 
 @pytest.fixture(scope="module")
 def model(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("copy_box") / "copy_box_check"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "hector_slam_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "cpp", "copy_box_check.cpp"), "-o", str(exe)], check=True)
-    return exe
+    return build_check(tmp_path_factory.mktemp("copy_box"), "copy_box_check.cpp")
 
 
 @pytest.mark.parametrize("width", [25, 38, 40])

@@ -7,31 +7,17 @@ checked without a GPU.
 * the new unit is part of the build.
 """
 import ctypes as C
-import os
-import re
-import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from support import check_symbols, compile_c99, header_text
+
 NEW_SYMBOLS = ("hsm_copy_map", "hsm_copy_map_boxes", "hsm_group_sync_maps")
 HSM_ERR_INVALID = -1
 
 
-def _header():
-    return open(os.path.join(ROOT, "include", "hector_mi355", "capi.h")).read()
-
-
 def test_new_symbols_declared_bound_and_exported():
     from hector_slam_amd import build, capi
-    code = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-    build.build_native()
-    lib = capi.load_library()
-    for name in NEW_SYMBOLS:
-        assert re.search(r"\bint\s+" + name + r"\s*\(", code), name
-        assert name in capi.SIGNATURES, name
-        assert hasattr(lib, name), name
-        decl = re.search(r"\b" + name + r"\s*\((.*?)\)\s*;", code, re.S).group(1)
-        assert len(capi.SIGNATURES[name][1]) == decl.count(",") + 1, (name, decl)
-    head = _header()
+    check_symbols(NEW_SYMBOLS)
+    head = header_text()
     assert "equalled `src` outside the boxes" in head and "HSM_COPY_STAGE=1" in head
     assert "the cross-device copy itself has not been run" in head and "address order" in head
     assert callable(capi.MapRepMultiMap.copy_map_from) and callable(capi.MapRepGroup.sync_maps)
@@ -40,15 +26,12 @@ def test_new_symbols_declared_bound_and_exported():
 
 
 def test_header_with_the_new_entries_is_plain_c99(tmp_path):
-    src = tmp_path / "use.c"
-    src.write_text('#include "hector_mi355/capi.h"\n'
-                   "int main(void) { hsm_ctx* a = 0; hsm_ctx* b = 0; hsm_group* g = 0; int boxes[4] = {0, 0, -1, -1};\n"
-                   "  int rc = hsm_copy_map(a, b);\n"
-                   "  rc += hsm_copy_map_boxes(a, b, boxes);\n"
-                   "  rc += hsm_group_sync_maps(g, 0, boxes);\n"
-                   "  return rc; }\n")
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-c", str(src), "-I",
-                    os.path.join(ROOT, "include"), "-o", str(tmp_path / "use.o")], check=True)
+    compile_c99(tmp_path,
+                "int main(void) { hsm_ctx* a = 0; hsm_ctx* b = 0; hsm_group* g = 0; int boxes[4] = {0, 0, -1, -1};\n"
+                "  int rc = hsm_copy_map(a, b);\n"
+                "  rc += hsm_copy_map_boxes(a, b, boxes);\n"
+                "  rc += hsm_group_sync_maps(g, 0, boxes);\n"
+                "  return rc; }\n")
 
 
 def test_null_context_is_invalid_for_every_new_entry():

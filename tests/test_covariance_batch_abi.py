@@ -20,6 +20,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from support import build_check,check_symbols, compile_c99, header_text
 from test_node_rows import sigma_statistics_f32
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -28,22 +29,11 @@ NEW_SYMBOLS = ("hsm_covariance_batch_device", "hsm_match_cov_batch_device", "hsm
 HSM_ERR_INVALID = -1
 
 
-def _header():
-    return open(os.path.join(ROOT, "include", "hector_mi355", "capi.h")).read()
-
-
 def test_new_symbols_declared_bound_and_exported():
-    from hector_slam_amd import build, capi
-    head = _header()
-    code = re.sub(r"/\*.*?\*/", "", head, flags=re.S)
-    build.build_native()
-    lib = capi.load_library()
+    from hector_slam_amd import capi
+    head = header_text()
+    check_symbols(NEW_SYMBOLS)
     for name in NEW_SYMBOLS:
-        assert re.search(r"\bint\s+" + name + r"\s*\(", code), name
-        assert name in capi.SIGNATURES, name
-        assert hasattr(lib, name), name
-        decl = re.search(r"\b" + name + r"\s*\((.*?)\)\s*;", code, re.S).group(1)
-        assert len(capi.SIGNATURES[name][1]) == decl.count(",") + 1, (name, decl)
         # each declaration carries its citation: the comment right in front of it has a "replaces:" line
         comment = re.findall(r"/\*(.*?)\*/\s*int\s+" + name + r"\s*\(", head, re.S)[-1].rsplit("/*", 1)[-1]
         assert "replaces:" in comment, name
@@ -53,15 +43,12 @@ def test_new_symbols_declared_bound_and_exported():
 
 
 def test_header_with_the_new_entries_is_plain_c99(tmp_path):
-    src = tmp_path / "use.c"
-    src.write_text('#include "hector_mi355/capi.h"\n'
-                   "int main(void) { hsm_ctx* h = 0; int idx[1] = {0}; float f[9] = {0.0f};\n"
-                   "  int rc = hsm_covariance_batch_device(h, 0, 1, f, f, 0, 1, f, f, f, f, 0);\n"
-                   "  rc += hsm_match_cov_batch_device(h, 1, f, f, 0, 1, f, 0, 0, f, f, f, f, 1, 0, 1, idx, f, f, 0);\n"
-                   "  rc += hsm_covariance_batch(h, 0, 1, f, f, 0, 1, f, f, f, f);\n"
-                   "  return rc; }\n")
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-c", str(src), "-I",
-                    os.path.join(ROOT, "include"), "-o", str(tmp_path / "use.o")], check=True)
+    compile_c99(tmp_path,
+                "int main(void) { hsm_ctx* h = 0; int idx[1] = {0}; float f[9] = {0.0f};\n"
+                "  int rc = hsm_covariance_batch_device(h, 0, 1, f, f, 0, 1, f, f, f, f, 0);\n"
+                "  rc += hsm_match_cov_batch_device(h, 1, f, f, 0, 1, f, 0, 0, f, f, f, f, 1, 0, 1, idx, f, f, 0);\n"
+                "  rc += hsm_covariance_batch(h, 0, 1, f, f, 0, 1, f, f, f, f);\n"
+                "  return rc; }\n")
 
 
 def test_null_context_is_invalid_for_every_new_entry():
@@ -120,9 +107,7 @@ def test_facade_covariance_batch_compiles():
 
 
 def test_staging_plan_gives_the_written_out_sums(tmp_path):
-    exe = tmp_path / "covariance_stage_check"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-I", CSRC, "-I", os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "tests", "cpp", "covariance_stage_check.cpp"), "-o", str(exe)], check=True)
+    exe = build_check(tmp_path, "covariance_stage_check.cpp", "-I", os.path.join(ROOT, "include"))
     r = subprocess.run([str(exe)], capture_output=True, text=True)
     rec = json.loads(r.stdout.strip().splitlines()[-1])
     assert r.returncode == 0 and rec["mismatches"] == 0, (rec, r.stderr[-2000:])

@@ -26,12 +26,9 @@ import entry_geometry_cases as eg
 import frame_cases as fc
 import window_cases
 from conftest import bits, oracle_kinds
+from support import same
 
 MAPS = pytest.mark.parametrize("m", eg.MAPS, ids=eg.MAP_IDS)
-
-
-def same(a, b):
-    return np.array_equal(bits(a), bits(b))
 
 
 def same_rays(got, want):

@@ -7,14 +7,11 @@ import pytest
 
 import frame_cases as fc
 from conftest import bits, oracle_kinds
+from support import same
 
 FRAMES = pytest.mark.parametrize("frame", fc.FRAMES, ids=fc.fid)
 GEOMS = pytest.mark.parametrize("geom", fc.GEOMETRIES, ids=fc.gid)
 SQUARE = fc.GEOMETRIES[0]
-
-
-def same(a, b):
-    return np.array_equal(bits(a), bits(b))
 
 
 def test_the_frames_are_what_they_say():

@@ -19,8 +19,9 @@ import pytest
 
 import aged_cases as ac
 import gn_f64
-from conftest import bits, oracle_kinds
-from test_gpu_border_sampling import BATCH_FORMS, BATCH_PARAMS, WPS, pack
+from conftest import bits
+from support import capi, kind, new_context, pack, same
+from test_gpu_border_sampling import BATCH_FORMS, BATCH_PARAMS, WPS
 
 pytestmark = pytest.mark.gpu
 GEOMS = pytest.mark.parametrize("geom", ac.GEOMETRIES, ids=ac.gid)
@@ -29,24 +30,6 @@ DEFINED = pytest.mark.parametrize("family", ac.DEFINED)
 FAMILIES = pytest.mark.parametrize("family", ac.FAMILIES)
 F = np.float32
 _REF = {}
-
-
-@pytest.fixture(scope="module")
-def capi():
-    import torch
-    assert torch.cuda.is_available(), "gpu-marked tests need a HIP device"
-    from hector_slam_amd import capi as m
-    m.load_library()
-    return m
-
-
-@pytest.fixture(scope="module", params=oracle_kinds())
-def kind(request):
-    return request.param
-
-
-def same(a, b):
-    return np.array_equal(bits(a), bits(b))
 
 
 def agrees(got, want):
@@ -60,8 +43,7 @@ def agrees(got, want):
 
 
 def new_ctx(capi, family, geom, layout="quad", **kw):
-    g = capi.MapRepMultiMap(ac.RES, geom[0], geom[1], geom[2], ac.START,
-                            layout=capi.LAYOUT_QUAD if layout == "quad" else capi.LAYOUT_PLANE, **kw)
+    g = new_context(capi, ac.RES, geom[0], geom[1], geom[2], ac.START, layout, factors=None, **kw)
     ac.upload(g, family, geom)
     g.synchronize()
     return g

@@ -13,7 +13,8 @@ import pytest
 
 import border_cases as bc
 import gn_f64
-from conftest import bits, oracle_kinds
+from conftest import bits
+from support import capi, kind, new_context, pack, same
 
 pytestmark = pytest.mark.gpu
 GEOMS = pytest.mark.parametrize("geom", bc.GEOMETRIES, ids=bc.gid)
@@ -22,28 +23,9 @@ F = np.float32
 _REF = {}
 
 
-@pytest.fixture(scope="module")
-def capi():
-    import torch
-    assert torch.cuda.is_available(), "gpu-marked tests need a HIP device"
-    from hector_slam_amd import capi as m
-    m.load_library()
-    return m
-
-
-@pytest.fixture(scope="module", params=oracle_kinds())
-def kind(request):
-    return request.param
-
-
-def same(a, b):
-    return np.array_equal(bits(a), bits(b))
-
-
 def new_ctx(capi, geom, layout="quad", **kw):
     """a context in the library's default mode that holds the case's map"""
-    g = capi.MapRepMultiMap(bc.RES, geom[0], geom[1], geom[2], bc.START,
-                            layout=capi.LAYOUT_QUAD if layout == "quad" else capi.LAYOUT_PLANE, **kw)
+    g = new_context(capi, bc.RES, geom[0], geom[1], geom[2], bc.START, layout, factors=None, **kw)
     bc.upload(g, geom)
     g.synchronize()
     return g
@@ -55,13 +37,6 @@ def ref(oracle_mod, kind, geom, key, op):
     if k not in _REF:
         _REF[k] = bc.run_checked(oracle_mod, kind, geom, op)
     return _REF[k]
-
-
-def pack(scans):
-    offs = np.zeros(len(scans) + 1, np.int32)
-    offs[1:] = np.cumsum([len(s) for s in scans])
-    pts = np.concatenate([np.asarray(s, F).reshape(-1, 2) for s in scans])
-    return np.ascontiguousarray(pts, F), offs
 
 
 def eval_cases(geom, lvl):

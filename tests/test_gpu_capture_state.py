@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from conftest import bits, make_oracle, oracle_kinds
+from support import capi
 
 pytestmark = pytest.mark.gpu
 
@@ -20,15 +21,6 @@ KIND = oracle_kinds()[-1]  # "hr" (reference-compiled) where available
 B = 4096
 RANGE_MIN, RANGE_MAX = 0.4, 30.0
 HSM_ERR_INVALID = -1
-
-
-@pytest.fixture(scope="module")
-def capi():
-    import torch
-    assert torch.cuda.is_available()
-    from hector_slam_amd import capi as m
-    m.load_library()
-    return m
 
 
 def oracle_poses(oracle_mod, sc, init, pts, offs, threads=16):

@@ -10,22 +10,14 @@ import pytest
 
 import cast_cases
 from conftest import bits, make_oracle
-from test_gpu_score_batch import dev, gpu_for, oracle_update
+from support import capi, dev, layout_of, stream_ptr
+from test_gpu_score_batch import gpu_for, oracle_update
 
 pytestmark = pytest.mark.gpu
 
 HSM_ERR_INVALID = -1
 SENTINEL = -777.0
 FORMS = {"wave": b"cast_scans_wave_kernel", "lane": b"cast_scans_lane_kernel"}
-
-
-@pytest.fixture(scope="module")
-def capi():
-    import torch
-    assert torch.cuda.is_available()
-    from hector_slam_amd import capi as m
-    m.load_library()
-    return m
 
 
 @pytest.fixture(scope="module")
@@ -50,7 +42,7 @@ def context(capi, monkeypatch, sc, o, form=None, layout="quad", **kw):
         monkeypatch.delenv("HSM_CAST_FORM", raising=False)
     else:
         monkeypatch.setenv("HSM_CAST_FORM", form)
-    return gpu_for(capi, sc, o, layout=capi.LAYOUT_QUAD if layout == "quad" else capi.LAYOUT_PLANE, **kw)
+    return gpu_for(capi, sc, o, layout=layout_of(capi, layout), **kw)
 
 
 def assert_rays(what, got, want):
@@ -92,7 +84,7 @@ def test_device_ray_entry_equals_the_host_entry_and_the_checker(capi, monkeypatc
         dist = torch.full((2000,), SENTINEL, dtype=torch.float32, device="cuda:0")
         hit = torch.full((2000, 2), float("nan"), dtype=torch.float32, device="cuda:0")
         g.ray_distances_device(lvl, 2000, d_b.data_ptr(), d_e.data_ptr(), dist.data_ptr(), hit.data_ptr(),
-                               stream=torch.cuda.current_stream().cuda_stream)
+                               stream=stream_ptr())
         got = dist.cpu().numpy(), hit.cpu().numpy()
         assert capi.load_library().hsm_last_launch_kernel(g._h) == b"ray_distance_kernel"
         assert_rays(f"level {lvl}, device entry", got, want)
@@ -102,7 +94,7 @@ def test_device_ray_entry_equals_the_host_entry_and_the_checker(capi, monkeypatc
         dist.fill_(SENTINEL)
         d_b, d_e = dev(begin), dev(end)
         g.ray_distances_device(lvl, 2000, d_b.data_ptr(), d_e.data_ptr(), dist.data_ptr(), 0,
-                               stream=torch.cuda.current_stream().cuda_stream)
+                               stream=stream_ptr())
         want2 = cast_cases.expected_rays("ho", c["grid"], meta, begin, end)[0]
         got2 = dist.cpu().numpy()
         assert np.array_equal(bits(got2), bits(want2)), (lvl, np.flatnonzero(bits(got2) != bits(want2))[:8])

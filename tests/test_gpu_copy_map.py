@@ -19,6 +19,7 @@ import pytest
 
 import stamp_cases as sc
 from conftest import bits, oracle_kinds
+from support import capi, dev, new_context, pack, single_update, stream_ptr
 
 pytestmark = pytest.mark.gpu
 
@@ -28,15 +29,6 @@ LAYOUTS = pytest.mark.parametrize("layout", ("quad", "plane"))
 RES, SIZE, LEVELS = 0.1, 128, 3
 N_SRC, N_MORE, N_BOX, N_HYP = 12, 4, 3, 16
 ZERO3 = np.zeros(3, np.float32)
-
-
-@pytest.fixture(scope="module")
-def capi():
-    import torch
-    assert torch.cuda.is_available(), "gpu-marked tests need a HIP device"
-    from hector_slam_amd import capi as m
-    m.load_library()
-    return m
 
 
 @pytest.fixture(scope="module")
@@ -64,29 +56,8 @@ def stages(scene, oracle_mod):
         o.close()
 
 
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
-
-
-def pack(scans):
-    offs = np.zeros(len(scans) + 1, np.int32)
-    offs[1:] = np.cumsum([len(s) for s in scans])
-    return np.ascontiguousarray(np.concatenate(scans), np.float32), offs
-
-
 def new_ctx(capi, layout, sx=SIZE, sy=SIZE, levels=LEVELS, res=RES, free=0.4, occ=0.9):
-    g = capi.MapRepMultiMap(res, sx, sy, levels, layout=capi.LAYOUT_QUAD if layout == "quad" else capi.LAYOUT_PLANE)
-    g.setUpdateFactorFree(free)
-    g.setUpdateFactorOccupied(occ)
-    return g
-
-
-def single_update(capi, g, pose, pts):
-    """hsm_retain_scan (what matchData leaves for the coarse levels) + hsm_update_by_scan, which returns when it is queued"""
-    a = np.ascontiguousarray(pts, np.float32).reshape(-1, 2)
-    capi._check(g._lib.hsm_retain_scan(g._h, a.ctypes.data, a.shape[0], np.zeros(2, np.float32)), "hsm_retain_scan")
-    g.updateByScan(a, pose)
+    return new_context(capi, res, sx, sy, levels, layout=layout, factors=(free, occ))
 
 
 def integrate(capi, g, scene, first, last):
@@ -423,7 +394,7 @@ def test_group_replicas_alike_after_a_device_resident_update(capi, oracle_mod, s
     d = [dev(scene.build_poses[:n]), dev(pts), dev(offs)]
     torch.cuda.synchronize()
     m0.update_by_scans_device(n, d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), 0, max(len(x) for x in scene.build_scans[:n]), None,
-                              torch.cuda.current_stream().cuda_stream)
+                              stream_ptr())
     with pytest.raises(capi.HsmError):
         grp.sync_maps(2)
     with pytest.raises(capi.HsmError):

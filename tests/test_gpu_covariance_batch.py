@@ -12,7 +12,8 @@ import pytest
 
 import select_rule
 from conftest import bits, make_oracle, oracle_kinds
-from test_gpu_score_batch import SENTINEL, dev, gpu_for, oracle_update, pack, score
+from support import capi, dev, layout_of, pack
+from test_gpu_score_batch import SENTINEL, gpu_for, oracle_update, score
 
 pytestmark = pytest.mark.gpu
 
@@ -20,19 +21,6 @@ HSM_ERR_INVALID = -1
 CSR_LENS = (0, 1, 63, 64, 65, 128, 129, 0, 181)  # the round boundaries of the chain; an empty scan first and one inside
 SHARED_BATCHES = (1, 3, 4, 5)                    # the wavefront and workgroup boundaries
 KEYS = ("cw", "cm", "l7", "lh")
-
-
-@pytest.fixture(scope="module")
-def capi():
-    import torch
-    assert torch.cuda.is_available()
-    from hector_slam_amd import capi as m
-    m.load_library()
-    return m
-
-
-def layout_of(capi, name):
-    return capi.LAYOUT_QUAD if name == "quad" else capi.LAYOUT_PLANE
 
 
 def fan(sc, q, n=181):

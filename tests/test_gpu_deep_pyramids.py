@@ -18,7 +18,8 @@ import pytest
 import deep_cases
 import gn_f64
 import select_rule
-from conftest import bits, oracle_kinds
+from conftest import bits
+from support import capi, dev, kind, new_context, same
 
 pytestmark = pytest.mark.gpu
 
@@ -28,29 +29,6 @@ HSM_ERR_INVALID = -1
 SENTINEL = -777.0
 LAYOUTS = ["quad", "plane"]
 BIG = [(2048, 2048, 6), deep_cases.LARGE]  # the batch sizes of the benchmark (4096) run on these two
-
-
-@pytest.fixture(scope="module")
-def capi():
-    import torch
-    assert torch.cuda.is_available(), "gpu-marked tests need a HIP device"
-    from hector_slam_amd import capi as m
-    m.load_library()
-    return m
-
-
-@pytest.fixture(scope="module", params=oracle_kinds())
-def kind(request):
-    return request.param
-
-
-def same(a, b):
-    return np.array_equal(bits(a), bits(b))
-
-
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
 
 
 _CASES: dict = {}
@@ -138,10 +116,8 @@ class Ref:
 
 def new_ctx(capi, geom, layout="quad", **kw):
     sx, sy, levels = geom
-    g = capi.MapRepMultiMap(RES, sx, sy, levels, layout=capi.LAYOUT_QUAD if layout == "quad" else capi.LAYOUT_PLANE, **kw)
+    g = new_context(capi, RES, sx, sy, levels, layout=layout, **kw)
     assert g.parity() == capi.PARITY_AUTO and g.getMapLevels() == levels
-    g.setUpdateFactorFree(0.4)
-    g.setUpdateFactorOccupied(0.9)
     assert [g.level_info(l)[:2] for l in range(levels)] == deep_cases.level_sizes(sx, sy, levels)
     return g
 

@@ -15,23 +15,10 @@ the crossed-cell byte map and the end-cell bitmap -- all zero again (hsm_debug_m
 import numpy as np
 import pytest
 
-from conftest import bits, oracle_kinds
+from conftest import bits
+from support import capi, kind, layout_of
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def capi():
-    import torch
-    assert torch.cuda.is_available(), "gpu-marked tests need a HIP device"
-    from hector_slam_amd import capi as m
-    m.load_library()
-    return m
-
-
-@pytest.fixture(scope="module", params=oracle_kinds())
-def kind(request):
-    return request.param
 
 
 from edge_cases import GEOMETRIES, begin_cells, border_fan, probe_coords, world_pose_of_cell  # noqa: E402
@@ -42,7 +29,7 @@ from edge_cases import GEOMETRIES, begin_cells, border_fan, probe_coords, world_
 def test_dense_update_on_and_beyond_the_four_borders_is_bit_exact(capi, oracle_mod, kind, geom, layout):
     sx, sy, levels, n = geom
     res = 0.05
-    g = capi.MapRepMultiMap(res, sx, sy, levels, layout=capi.LAYOUT_QUAD if layout == "quad" else capi.LAYOUT_PLANE)
+    g = capi.MapRepMultiMap(res, sx, sy, levels, layout=layout_of(capi, layout))
     o = oracle_mod.Oracle(kind, res, sx, sy, levels)
     for m_ in (g.setUpdateFactorFree, o.set_update_factor_free):
         m_(0.4)

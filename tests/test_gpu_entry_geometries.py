@@ -42,6 +42,7 @@ import test_gpu_window as tw
 import topk_rule
 import window_cases
 from conftest import bits, oracle_kinds
+from support import capi, dev, new_context, same, single_update, stream_ptr
 
 pytestmark = pytest.mark.gpu
 
@@ -58,26 +59,10 @@ def ids(cases):
     return [f"{m.id}-{layout}" for m, layout in cases]
 
 
-@pytest.fixture(scope="module")
-def capi():
-    import torch
-    assert torch.cuda.is_available(), "gpu-marked tests need a HIP device"
-    from hector_slam_amd import capi as m
-    m.load_library()
-    return m
-
-
-def same(a, b):
-    return np.array_equal(bits(a), bits(b))
-
-
 def new_ctx(capi, oracle_mod, m, layout="quad", upload=True, frame=None):
     """a context in the library's default mode on the map's geometry (or in another frame), with the map"""
     res, start = (m.resolution, m.start) if frame is None else frame
-    g = capi.MapRepMultiMap(res, m.geom[0], m.geom[1], m.geom[2], startCoords=start,
-                            layout=capi.LAYOUT_QUAD if layout == "quad" else capi.LAYOUT_PLANE)
-    g.setUpdateFactorFree(fc.FACTORS[0])
-    g.setUpdateFactorOccupied(fc.FACTORS[1])
+    g = new_context(capi, res, m.geom[0], m.geom[1], m.geom[2], start, layout, fc.FACTORS)
     if upload:
         m.upload(oracle_mod, g)
     g.synchronize()
@@ -104,11 +89,11 @@ def test_casts_and_rays_on_every_level(capi, oracle_mod, monkeypatch, m, layout)
             if form != "lane":
                 continue
             assert g.map_metadata(lvl) == c["meta"], (lvl, g.map_metadata(lvl), c["meta"])
-            d_b, d_e = tcast.dev(c["begin"]), tcast.dev(c["end"])
+            d_b, d_e = dev(c["begin"]), dev(c["end"])
             dist = torch.full((eg.N_RAYS,), SENTINEL, dtype=torch.float32, device="cuda:0")
             hit = torch.full((eg.N_RAYS, 2), float("nan"), dtype=torch.float32, device="cuda:0")
             g.ray_distances_device(lvl, eg.N_RAYS, d_b.data_ptr(), d_e.data_ptr(), dist.data_ptr(), hit.data_ptr(),
-                                   origin_xy=c["meta"][:2], resolution=c["meta"][2], stream=torch.cuda.current_stream().cuda_stream)
+                                   origin_xy=c["meta"][:2], resolution=c["meta"][2], stream=stream_ptr())
             got = dist.cpu().numpy(), hit.cpu().numpy()
             assert lib.hsm_last_launch_kernel(g._h) == b"ray_distance_kernel"
             tcast.assert_rays(f"level {lvl}, device rays", got, want["rays"])
@@ -218,8 +203,8 @@ def test_whole_copy_is_the_source_and_stays_it(capi, oracle_mod, m, layout):
     frame_map = m.kind == "frame"
     src, dst = new_ctx(capi, oracle_mod, m, layout, upload=frame_map), new_ctx(capi, oracle_mod, m, layout, upload=False)
     for k in range(N_SRC):
-        tcopy.single_update(capi, src, poses[k], scans[k])
-    tcopy.single_update(capi, dst, poses[-1], scans[-1])   # other contents, another counter
+        single_update(capi, src, poses[k], scans[k])
+    single_update(capi, dst, poses[-1], scans[-1])   # other contents, another counter
     assert dst.getUpdateIndex(0) != src.getUpdateIndex(0)
     dst.copy_map_from(src)
     s_dst = at_copy = tcopy.state(dst)
@@ -227,7 +212,7 @@ def test_whole_copy_is_the_source_and_stays_it(capi, oracle_mod, m, layout):
     tcopy.assert_state_is_checkers(oracle_mod, s_dst, updated_checkers(oracle_mod, m, N_SRC), N_SRC, "copy")
     for g in (src, dst):
         for k in range(N_SRC, N_SRC + N_MORE):
-            tcopy.single_update(capi, g, poses[k], scans[k])
+            single_update(capi, g, poses[k], scans[k])
     s_dst, s_src = tcopy.state(dst), tcopy.state(src)
     tcopy.assert_same_state(s_dst, s_src, "copy + 2 updates")
     after = updated_checkers(oracle_mod, m, N_SRC + N_MORE)
@@ -245,7 +230,7 @@ def test_box_copies_on_odd_widths_leave_the_rest_alone(capi, oracle_mod, layout)
     src, dst, exp = (new_ctx(capi, oracle_mod, m, layout, upload=(k == 0)) for k in range(3))
     tiny = np.float32([[3.0, 0.2], [0.1, 3.0], [-3.0, 0.3]])
     for _ in range(2):  # src's counters move; an upload leaves them where they are
-        tcopy.single_update(capi, src, m.case().build_poses[0], tiny)
+        single_update(capi, src, m.case().build_poses[0], tiny)
     m.upload(oracle_mod, src)
     s_src = tcopy.state(src)
     prior = [eg.prior_planes(m.geom, lvl) for lvl in range(L)]

@@ -12,27 +12,10 @@ unmodified reference headers).
 import numpy as np
 import pytest
 
-from conftest import bits, make_oracle, oracle_kinds
+from conftest import bits, make_oracle
+from support import capi, kind, layout_of, same
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def capi():
-    import torch
-    assert torch.cuda.is_available(), "gpu-marked tests need a HIP device"
-    from hector_slam_amd import capi as m
-    m.load_library()
-    return m
-
-
-@pytest.fixture(scope="module", params=oracle_kinds())
-def kind(request):
-    return request.param
-
-
-def same(a, b):
-    return np.array_equal(bits(a), bits(b))
 
 
 def exact_gpu(capi, sc, o=None, **kw):
@@ -74,7 +57,7 @@ def test_single_scan_match_bit_identical_for_every_team_width(capi, oracle_mod, 
     beams are dealt to lanes, not the order of the nine sums)"""
     sc = pyramid_scene
     o = make_oracle(oracle_mod, kind, sc)
-    g = exact_gpu(capi, sc, o, waves_per_scan=wps, layout=capi.LAYOUT_QUAD if layout == "quad" else capi.LAYOUT_PLANE)
+    g = exact_gpu(capi, sc, o, waves_per_scan=wps, layout=layout_of(capi, layout))
     for q in range(len(sc.query_scans)):
         pg, cg = g.matchData(sc.query_init[q], sc.query_scans[q])
         po, co = o.match(sc.query_init[q], sc.query_scans[q])
@@ -273,7 +256,7 @@ def test_dense_scan_forms_are_bit_identical(capi, oracle_mod, pyramid_scene, kin
     from hector_slam_amd import synth
     sc = pyramid_scene
     o = make_oracle(oracle_mod, kind, sc)
-    lay = capi.LAYOUT_QUAD if layout == "quad" else capi.LAYOUT_PLANE
+    lay = layout_of(capi, layout)
     monkeypatch.setenv("HSM_EXACT_DENSE_MIN", "1920")
     monkeypatch.setenv("HSM_EXACT_SPEC", "1")
     g = exact_gpu(capi, sc, o, layout=lay)
@@ -393,7 +376,7 @@ def test_single_scan_on_chip_speculative_form(capi, oracle_mod, pyramid_scene, k
     from hector_slam_amd import synth
     sc = pyramid_scene
     o = make_oracle(oracle_mod, kind, sc)
-    lay = capi.LAYOUT_QUAD if layout == "quad" else capi.LAYOUT_PLANE
+    lay = layout_of(capi, layout)
     team = exact_gpu(capi, sc, o, layout=lay)
     monkeypatch.setenv("HSM_EXACT_SPEC1", "1")
     g = exact_gpu(capi, sc, o, layout=lay)
@@ -559,7 +542,7 @@ def test_likelihood_residual_and_sigma_point_covariance_bit_identical(capi, orac
     residuals, likelihoods, the seven sigma-point likelihoods and both covariance matrices bit for bit"""
     sc = pyramid_scene
     o = make_oracle(oracle_mod, kind, sc)
-    g = exact_gpu(capi, sc, o, layout=capi.LAYOUT_QUAD if layout == "quad" else capi.LAYOUT_PLANE)
+    g = exact_gpu(capi, sc, o, layout=layout_of(capi, layout))
     rng = np.random.default_rng(9)
     for lvl in range(sc.levels):
         f = np.float32(1.0 / 2 ** lvl)

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 from conftest import ang_diff, bits, make_oracle, oracle_kinds
+from support import capi
 
 pytestmark = pytest.mark.gpu
 TOL_M, TOL_RAD = 1e-4, 1e-4
@@ -24,15 +25,6 @@ def pose_err(p, q):
     p = np.asarray(p, np.float64).reshape(-1, 3)
     q = np.asarray(q, np.float64).reshape(-1, 3)
     return np.abs(p[:, :2] - q[:, :2]).max(), ang_diff(p[:, 2], q[:, 2]).max()
-
-
-@pytest.fixture(scope="module")
-def capi():
-    import torch
-    assert torch.cuda.is_available()
-    from hector_slam_amd import capi as m
-    m.load_library()
-    return m
 
 
 KIND = oracle_kinds()[-1]  # "hr" (reference-compiled) where available

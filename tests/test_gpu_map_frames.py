@@ -23,7 +23,8 @@ import pytest
 import frame_cases as fc
 import gn_f64
 from conftest import bits, oracle_kinds
-from test_gpu_border_sampling import BATCH_FORMS, BATCH_PARAMS, WPS, check_one_step, pack
+from support import capi, dev, new_context, pack, same
+from test_gpu_border_sampling import BATCH_FORMS, BATCH_PARAMS, WPS, check_one_step
 
 pytestmark = pytest.mark.gpu
 FRAMES = pytest.mark.parametrize("frame", fc.FRAMES, ids=fc.fid)
@@ -35,30 +36,9 @@ ZERO2 = np.zeros(2, F)
 _REF = {}
 
 
-@pytest.fixture(scope="module")
-def capi():
-    import torch
-    assert torch.cuda.is_available(), "gpu-marked tests need a HIP device"
-    from hector_slam_amd import capi as m
-    m.load_library()
-    return m
-
-
-def same(a, b):
-    return np.array_equal(bits(a), bits(b))
-
-
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
-
-
 def new_ctx(capi, frame, geom, layout="quad", upload=True, **kw):
     """a context in the library's default mode, in the frame, that holds the case's map"""
-    g = capi.MapRepMultiMap(frame[0], geom[0], geom[1], geom[2], startCoords=frame[1],
-                            layout=capi.LAYOUT_QUAD if layout == "quad" else capi.LAYOUT_PLANE, **kw)
-    g.setUpdateFactorFree(fc.FACTORS[0])
-    g.setUpdateFactorOccupied(fc.FACTORS[1])
+    g = new_context(capi, frame[0], geom[0], geom[1], geom[2], frame[1], layout, fc.FACTORS, **kw)
     if upload:
         fc.upload(g, geom)
     g.synchronize()

@@ -14,19 +14,11 @@ import numpy as np
 import pytest
 
 import match_form_sites as mfs
+from support import capi
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def capi():
-    import torch
-    assert torch.cuda.is_available(), "gpu-marked tests need a HIP device"
-    from hector_slam_amd import capi as m
-    m.load_library()
-    return m
 
 
 @pytest.fixture(scope="module")

@@ -16,6 +16,7 @@ import pytest
 
 import merge_cases as mc
 from conftest import bits
+from support import capi, new_context, single_update, stream_ptr
 
 pytestmark = pytest.mark.gpu
 
@@ -27,28 +28,8 @@ FACTORS = (0.4, 0.9)
 EMPTY = [0, 0, -1, -1]
 
 
-@pytest.fixture(scope="module")
-def capi():
-    import torch
-    assert torch.cuda.is_available(), "gpu-marked tests need a HIP device"
-    from hector_slam_amd import capi as m
-    m.load_library()
-    return m
-
-
 def new_ctx(capi, geom, layout):
-    g = capi.MapRepMultiMap(geom[0], geom[1], geom[2], geom[3], startCoords=geom[4],
-                            layout=capi.LAYOUT_QUAD if layout == "quad" else capi.LAYOUT_PLANE)
-    g.setUpdateFactorFree(FACTORS[0])
-    g.setUpdateFactorOccupied(FACTORS[1])
-    return g
-
-
-def single_update(capi, g, pose, pts):
-    """hsm_retain_scan (what matchData leaves for the coarse levels) + hsm_update_by_scan, which returns when it is queued"""
-    a = np.ascontiguousarray(pts, F).reshape(-1, 2)
-    capi._check(g._lib.hsm_retain_scan(g._h, a.ctypes.data, a.shape[0], np.zeros(2, F)), "hsm_retain_scan")
-    g.updateByScan(a, pose)
+    return new_context(capi, geom[0], geom[1], geom[2], geom[3], geom[4], layout, FACTORS)
 
 
 def integrate(capi, g, scans):
@@ -244,7 +225,7 @@ def test_dirty_and_publish_boxes_cover_the_merge(capi, maps, form):
     dst = clone(capi, built, gd, "quad")
     t = F(dict(mc.TRANSFORMS)["theta_-2.1"])
     model = mc.merge_pyramid([p[0] for p in dst_planes], [p[0] for p in src_planes], gd, gs, t)
-    stream = torch.cuda.current_stream().cuda_stream
+    stream = stream_ptr()
     grids, d_boxes = [], []
     for lvl in range(mc.LEVELS):   # a grid that is current, and empty boxes
         sx, sy = mc.level_size(gd, lvl)

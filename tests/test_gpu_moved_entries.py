@@ -30,6 +30,7 @@ import test_gpu_shift_map as tshift
 import test_gpu_window as tw
 import window_cases
 from conftest import bits, oracle_kinds
+from support import capi, dev, pack, same, stream_ptr
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -48,23 +49,7 @@ def moved_cases(map_layouts):
     cases = [(m, layout, name) for m, layout in map_layouts for name in mc.moves_of(m)]
     return pytest.mark.parametrize("m,layout,name", cases, ids=["%s-%s-%s" % (m.id, layout, name) for m, layout, name in cases])
 
-same, dev, new_ctx, load, levels_of, assert_planes, whole = (tshift.same, tshift.dev, tshift.new_ctx, tshift.load, tshift.levels_of,
-                                                             tshift.assert_planes, tshift.whole)
-pack = tsb.pack
-
-
-@pytest.fixture(scope="module")
-def capi():
-    import torch
-    assert torch.cuda.is_available(), "gpu-marked tests need a HIP device"
-    from hector_slam_amd import capi as m
-    m.load_library()
-    return m
-
-
-def stream():
-    import torch
-    return torch.cuda.current_stream().cuda_stream
+new_ctx, load, levels_of, assert_planes, whole = tshift.new_ctx, tshift.load, tshift.levels_of, tshift.assert_planes, tshift.whole
 
 
 def box(b):
@@ -84,18 +69,18 @@ def posed_update(g, poses, scans, origos=None, gated=False):
             torch.full((len(scans),), -7, dtype=torch.int32, device="cuda:0")]
     if gated:
         g.update_by_scans_device_gated(len(scans), keep[0].data_ptr(), keep[1].data_ptr(), keep[2].data_ptr(), 0, mc.MAX_BEAMS, None, 0,
-                                       keep[4].data_ptr(), stream())
+                                       keep[4].data_ptr(), stream_ptr())
     elif origos is None:
-        g.update_by_scans_device(len(scans), keep[0].data_ptr(), keep[1].data_ptr(), keep[2].data_ptr(), 0, mc.MAX_BEAMS, None, stream())
+        g.update_by_scans_device(len(scans), keep[0].data_ptr(), keep[1].data_ptr(), keep[2].data_ptr(), 0, mc.MAX_BEAMS, None, stream_ptr())
     else:
         g.update_by_scans_device_origos(len(scans), keep[0].data_ptr(), keep[1].data_ptr(), keep[2].data_ptr(), 0, mc.MAX_BEAMS,
-                                        keep[3].data_ptr(), stream())
+                                        keep[3].data_ptr(), stream_ptr())
     return keep
 
 
 def export_device(g, lvl, grid, d_box):
     import torch
-    g.occupancy_changes_device(lvl, grid.data_ptr(), d_box.data_ptr(), stream())
+    g.occupancy_changes_device(lvl, grid.data_ptr(), d_box.data_ptr(), stream_ptr())
     g.synchronize()
     torch.cuda.synchronize()
     return box(d_box.cpu())
@@ -345,7 +330,7 @@ def check_ranges(capi, g, q, want):
     d = [dev(q["starts"]), dev(q["ranges"]), torch.full((B, 3), -777.0, device="cuda:0"), torch.full((B, 9), -777.0, device="cuda:0"),
          torch.full((B,), -7, dtype=torch.int32, device="cuda:0"), torch.zeros(max(ws_bytes // 4, 1), dtype=torch.int32, device="cuda:0")]
     g.match_batch_ranges_device(B, d[0].data_ptr(), d[1].data_ptr(), n, a0, inc, rmin, rmax, g.getScaleToMap(), d[2].data_ptr(),
-                                d[3].data_ptr(), d[4].data_ptr(), d[5].data_ptr(), ws_bytes, stream())
+                                d[3].data_ptr(), d[4].data_ptr(), d[5].data_ptr(), ws_bytes, stream_ptr())
     torch.cuda.synchronize()
     assert np.array_equal(d[4].cpu().numpy(), want["counts"]), "counts"
     assert same(d[2].cpu().numpy(), np.stack([p for p, _ in want["ranges_match"]])), "poses of the raw batch"

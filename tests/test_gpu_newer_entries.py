@@ -33,6 +33,7 @@ import test_gpu_merge_map as tgm
 import test_gpu_score_batch as tsb
 import test_gpu_shift_map as tshift
 from conftest import bits, oracle_kinds
+from support import capi, dev, pack, single_update
 
 pytestmark = pytest.mark.gpu
 
@@ -40,17 +41,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KIND = oracle_kinds()[-1]
 F = np.float32
 SENTINEL, KEYS = tcb.SENTINEL, tcb.KEYS
-cov_dev, reference, pack = tcb.cov_dev, tcb.reference, tcb.pack
+cov_dev, reference = tcb.cov_dev, tcb.reference
 MOVE = "x3_y-2"
-
-
-@pytest.fixture(scope="module")
-def capi():
-    import torch
-    assert torch.cuda.is_available(), "gpu-marked tests need a HIP device"
-    from hector_slam_amd import capi as m
-    m.load_library()
-    return m
 
 
 def assert_rows(what, got, ref, lens, keys=KEYS):
@@ -155,7 +147,7 @@ class ChainBuffers(tcb.ChainBuffers):
         self.h_init = np.ascontiguousarray(starts, F)
         self.h_pts, self.h_offs = pack(scans)
         self.B = len(self.h_init)
-        self.init, self.pts, self.offs = tsb.dev(self.h_init), tsb.dev(self.h_pts), tsb.dev(self.h_offs)
+        self.init, self.pts, self.offs = dev(self.h_init), dev(self.h_pts), dev(self.h_offs)
         f = lambda *shape: torch.full(shape, SENTINEL, dtype=torch.float32, device="cuda:0")  # noqa: E731
         B, G = self.B, self.G
         self.pose, self.hess, self.cw, self.cm, self.l7, self.lh = f(B, 3), f(B, 9), f(B, 9), f(B, 9), f(B, 7), f(B)
@@ -330,7 +322,7 @@ def test_an_update_after_the_merge_leaves_the_same_planes_on_all_levels(capi, pa
     capi.merge_map(dst, src, case["t"])
     starts, pts = probe_scan(gd)
     for g in (dst, exp):
-        tgm.single_update(capi, g, starts[0], pts)
+        single_update(capi, g, starts[0], pts)
     touched = 0
     for lvl in range(gd[3]):
         (lo, st), (lo_e, st_e) = dst.download_level(lvl), exp.download_level(lvl)

@@ -22,7 +22,8 @@ import numpy as np
 import pytest
 
 import occupancy_cases as oc
-from conftest import oracle_kinds
+import support
+from support import capi, dev, pack, stream_ptr
 
 pytestmark = pytest.mark.gpu
 
@@ -30,26 +31,6 @@ HSM_ERR_INVALID = -1
 LEVELS = oc.LEVELS
 ZERO2 = np.zeros(2, np.float32)
 EMPTY = [0, 0, -1, -1]
-
-
-@pytest.fixture(scope="module")
-def capi():
-    import torch
-    assert torch.cuda.is_available(), "gpu-marked tests need a HIP device"
-    from hector_slam_amd import capi as m
-    m.load_library()
-    return m
-
-
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
-
-
-def pack(scans):
-    offs = np.zeros(len(scans) + 1, np.int32)
-    offs[1:] = np.cumsum([len(s) for s in scans])
-    return np.ascontiguousarray(np.concatenate([np.asarray(s, np.float32).reshape(-1, 2) for s in scans]), np.float32), offs
 
 
 def new_ctx(capi, free=0.4, occ=0.9):
@@ -60,13 +41,7 @@ def new_ctx(capi, free=0.4, occ=0.9):
 
 
 def new_refs(oracle_mod, free=0.4, occ=0.9):
-    refs = {}
-    for kind in oracle_kinds():
-        o = oracle_mod.Oracle(kind, oc.RES, oc.GEOM[0], oc.GEOM[1], LEVELS, oc.START)
-        o.set_update_factor_free(free)
-        o.set_update_factor_occupied(occ)
-        refs[kind] = o
-    return refs
+    return support.new_refs(oracle_mod, oc.RES, oc.GEOM[0], oc.GEOM[1], LEVELS, oc.START, (free, occ))
 
 
 def host_update(capi, g, pose, scan):
@@ -102,7 +77,7 @@ def export(g, lvl, grid, form):
         box = g.occupancy_changes(lvl, work)
     else:
         d, d_box = dev(work), torch.full((4,), -9, dtype=torch.int32, device="cuda:0")
-        g.occupancy_changes_device(lvl, d.data_ptr(), d_box.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        g.occupancy_changes_device(lvl, d.data_ptr(), d_box.data_ptr(), stream_ptr())
         work, box = d.cpu().numpy(), d_box.cpu().numpy()  # (the caller's stream waits behind the export)
     box = [int(v) for v in box]
     sx, sy = oc.dims(lvl)
@@ -387,7 +362,7 @@ def test_grid_device_equals_the_host_export_and_leaves_the_box(capi, oracle_mod)
         sx, sy = oc.dims(lvl)
         for shift in (0, 1):  # a grid that starts on a 4-byte boundary, and one that does not
             buf = torch.full((sx * sy + 8,), oc.POISON, dtype=torch.int8, device="cuda:0")
-            g.occupancy_grid_device(lvl, buf.data_ptr() + shift, torch.cuda.current_stream().cuda_stream)
+            g.occupancy_grid_device(lvl, buf.data_ptr() + shift, stream_ptr())
             got = buf.cpu().numpy()
             assert (got[:shift] == oc.POISON).all() and (got[shift + sx * sy:] == oc.POISON).all(), (lvl, shift)
             assert np.array_equal(got[shift:shift + sx * sy].reshape(sy, sx), g.occupancy_grid(lvl)), (lvl, shift)
@@ -400,7 +375,7 @@ def test_grid_device_equals_the_host_export_and_leaves_the_box(capi, oracle_mod)
     sx, sy = oc.dims(0)
     buf = torch.full((sx * sy + 8,), oc.POISON, dtype=torch.int8, device="cuda:0")
     d_box = torch.full((4,), -9, dtype=torch.int32, device="cuda:0")
-    g.occupancy_changes_device(0, buf.data_ptr() + 3, d_box.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    g.occupancy_changes_device(0, buf.data_ptr() + 3, d_box.data_ptr(), stream_ptr())
     got, m = buf.cpu().numpy(), box_mask((sy, sx), d_box.cpu().numpy())
     assert (got[:3] == oc.POISON).all() and (got[3 + sx * sy:] == oc.POISON).all()
     assert np.array_equal(got[3:3 + sx * sy].reshape(sy, sx), np.where(m, g.occupancy_grid(0), oc.POISON))

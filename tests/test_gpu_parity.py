@@ -19,7 +19,8 @@ import os
 import numpy as np
 import pytest
 
-from conftest import ang_diff, bits, make_oracle, oracle_kinds, ulp_diff
+from conftest import ang_diff, bits, make_oracle, ulp_diff
+from support import capi, kind, layout_of
 
 pytestmark = pytest.mark.gpu
 
@@ -51,15 +52,6 @@ def assert_dtr_close(d, dr, H, n):
     assert (np.abs(d - dr) <= tol).all(), (d, dr, tol)
 
 
-@pytest.fixture(scope="module")
-def capi():
-    import torch
-    assert torch.cuda.is_available(), "gpu-marked tests need a HIP device"
-    from hector_slam_amd import capi as m
-    m.load_library()  # raises if the native library is missing: no silent fallback
-    return m
-
-
 @pytest.fixture(autouse=True)
 def fast_tree_by_default(monkeypatch):
     """contexts created in this file start in HSM_PARITY_FAST (see make_gpu), also those constructed directly"""
@@ -77,12 +69,6 @@ def make_gpu(capi, scene, free=0.4, occ=0.9, build=True, **kw):
     if build:
         g.build_map(scene.build_poses, scene.build_scans)
     return g
-
-
-@pytest.fixture(scope="module", params=oracle_kinds())
-def kind(request):
-    """which CPU checker: "ho" = restatement, "hr" = the reference's own headers"""
-    return request.param
 
 
 @pytest.fixture(scope="module")
@@ -191,7 +177,7 @@ def test_device_sincos_equals_host_libm(sml, oracle_mod):
 def test_per_beam_terms_bit_exact(capi, oracle_mod, pyramid_scene, layout, kind):
     sc = pyramid_scene
     o = make_oracle(oracle_mod, kind, sc)
-    g = make_gpu(capi, sc, build=False, layout=capi.LAYOUT_QUAD if layout == "quad" else capi.LAYOUT_PLANE)
+    g = make_gpu(capi, sc, build=False, layout=layout_of(capi, layout))
     for lvl in range(sc.levels):
         g.upload_level(lvl, *o.download_level(lvl))
     checked = 0
@@ -1584,7 +1570,7 @@ def test_fast_batch_form_one_step_against_float64(capi, case, monkeypatch):
     if case.get("order"):
         monkeypatch.setenv("HSM_BATCH_ORDER_MIN", "1")
     w, init, scans, evs = gn_cases.batch_inputs(case)
-    lay = capi.LAYOUT_QUAD if case["layout"] == "quad" else capi.LAYOUT_PLANE
+    lay = layout_of(capi, case["layout"])
     g = w.gpu(capi, layout=lay, waves_per_scan=case["wps"])
     relaxed = case.get("parity") == "relaxed"
     if relaxed:

@@ -21,7 +21,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from conftest import bits
+from support import layout_of, same
 from test_node_rows import sigma_statistics_f32
 
 pytestmark = pytest.mark.gpu
@@ -39,10 +39,6 @@ def RES_TOL(n, residual):
 
 def LH_TOL(n, residual):
     return RES_TOL(n, residual) / n + 4.0 * U
-
-
-def same(a, b):
-    return np.array_equal(bits(a), bits(b))
 
 
 def scan_and_poses():
@@ -86,7 +82,7 @@ def test_probes_return_the_oracles_values_from_their_aligned_regions(oracle_mod,
     assert torch.cuda.is_available(), "gpu-marked tests need a HIP device"
     from hector_slam_amd import capi
     exact = parity == "exact"
-    g = capi.MapRepMultiMap(RES, SIZE, SIZE, LEVELS, layout=capi.LAYOUT_QUAD if layout == "quad" else capi.LAYOUT_PLANE,
+    g = capi.MapRepMultiMap(RES, SIZE, SIZE, LEVELS, layout=layout_of(capi, layout),
                             parity=capi.PARITY_EXACT if exact else capi.PARITY_FAST)
     for p in want["poses"]:
         g.updateByScan(want["scan"], p)

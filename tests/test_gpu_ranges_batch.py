@@ -6,21 +6,13 @@ import numpy as np
 import pytest
 
 from conftest import ang_diff, bits, make_oracle, oracle_kinds
+from support import capi, stream_ptr
 
 pytestmark = pytest.mark.gpu
 
 KIND = oracle_kinds()[-1]  # "hr" where oracle/_ref is present
 RANGE_MIN, RANGE_MAX = 0.4, 30.0
 HSM_ERR_INVALID, HSM_ERR_TOO_LARGE = -1, -4
-
-
-@pytest.fixture(scope="module")
-def capi():
-    import torch
-    assert torch.cuda.is_available()
-    from hector_slam_amd import capi as m
-    m.load_library()
-    return m
 
 
 def geometry(n):
@@ -330,11 +322,10 @@ def test_capture_and_replay(capi, pyr):
 
 
 def test_validation_leaves_outputs_untouched(capi, pyr):
-    import torch
     sc, r, g, _ = pyr
     geom = geometry(1081)
     d = Dev(capi, sc.query_init[:4], r[:4], cov_fill=6.0)
-    lib, s = g._lib, torch.cuda.current_stream().cuda_stream
+    lib, s = g._lib, stream_ptr()
 
     def call(batch, n, ws_bytes, begin=None):
         return lib.hsm_match_batch_ranges_device(g._h, batch, d.begin.data_ptr() if begin is None else begin, d.ranges.data_ptr(),

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from conftest import bits, make_oracle
+from support import capi, dev, stream_ptr
 import ranges_tf_cases as tc
 from test_node_rows import laser_scan_messages
 
@@ -15,24 +16,10 @@ HSM_OK, HSM_ERR_INVALID, HSM_ERR_TOO_LARGE = 0, -1, -4
 
 
 @pytest.fixture(scope="module")
-def capi():
-    import torch
-    assert torch.cuda.is_available()
-    from hector_slam_amd import capi as m
-    m.load_library()
-    return m
-
-
-@pytest.fixture(scope="module")
 def ctx(capi):
     g = capi.MapRepMultiMap(0.05, 256, 256, 2)
     yield g
     g.close()
-
-
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 class Conv:
@@ -188,7 +175,7 @@ def test_match_of_the_converted_batch_equals_the_reference(capi, oracle_mod, pyr
     d_origo = torch.empty((B, 2), dtype=torch.float32, device="cuda")
     d_pose = torch.full((B, 3), -9.0, dtype=torch.float32, device="cuda")
     d_cov = torch.full((B, 9), 7.0, dtype=torch.float32, device="cuda")
-    s = torch.cuda.current_stream().cuda_stream
+    s = stream_ptr()
     g.ingest_batch_ranges_tf_device(B, d_r.data_ptr(), n, a0, inc, 0.4, 30.0, 30.0, d_T.data_ptr(), False, *ga, scale,
                                     d_pts.data_ptr(), d_offs.data_ptr(), d_counts.data_ptr(), d_origo.data_ptr(), s)
     g.match_batch_device(B, d_init.data_ptr(), d_pts.data_ptr(), d_offs.data_ptr(), n, d_pose.data_ptr(), d_cov.data_ptr(), s)
@@ -299,13 +286,12 @@ def test_capture_replays_and_refuses_an_unseen_geometry(capi, ctx):
 
 
 def test_validation_leaves_outputs_untouched(capi, ctx):
-    import torch
     scale = ctx.getScaleToMap()
     rng = np.random.default_rng(78)
     ga = tc.gate_args(tc.NODE_GATES[0])
     r, T = tc.batch(rng, 4, 181)
     d = Conv(r, T)
-    lib, s = ctx._lib, torch.cuda.current_stream().cuda_stream
+    lib, s = ctx._lib, stream_ptr()
     null = object()
 
     def call(batch=4, n=181, h=ctx._h, ranges=None, tf=None, pts=None, offs=None, counts=None):

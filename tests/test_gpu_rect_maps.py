@@ -14,6 +14,7 @@ from hypothesis import HealthCheck, given, seed, settings
 
 import rect_cases
 from conftest import bits, oracle_kinds
+from support import capi, kind, new_context, same
 from edge_cases import begin_cells, border_fan, probe_coords, world_pose_of_cell
 
 pytestmark = pytest.mark.gpu
@@ -21,24 +22,6 @@ pytestmark = pytest.mark.gpu
 RES = rect_cases.RES
 ZERO2 = np.zeros(2, np.float32)
 RANGE_MIN, RANGE_MAX = 0.4, 30.0
-
-
-@pytest.fixture(scope="module")
-def capi():
-    import torch
-    assert torch.cuda.is_available(), "gpu-marked tests need a HIP device"
-    from hector_slam_amd import capi as m
-    m.load_library()
-    return m
-
-
-@pytest.fixture(scope="module", params=oracle_kinds())
-def kind(request):
-    return request.param
-
-
-def same(a, b):
-    return np.array_equal(bits(a), bits(b))
 
 
 class Ref:
@@ -85,10 +68,8 @@ def assert_match(pg, cg, po, co, what):
 
 
 def new_ctx(capi, sx, sy, levels, layout="quad", start=(0.5, 0.5), free=0.4, occ=0.9, **kw):
-    g = capi.MapRepMultiMap(RES, sx, sy, levels, start, layout=capi.LAYOUT_QUAD if layout == "quad" else capi.LAYOUT_PLANE, **kw)
+    g = new_context(capi, RES, sx, sy, levels, start, layout, (free, occ), **kw)
     assert g.parity() == capi.PARITY_AUTO
-    g.setUpdateFactorFree(free)
-    g.setUpdateFactorOccupied(occ)
     assert [g.level_info(l)[:2] for l in range(levels)] == [(sx >> l, sy >> l) for l in range(levels)]
     return g
 

@@ -32,6 +32,7 @@ import test_gpu_shift_map as tshift
 import test_gpu_window as tw
 import topk_rule
 from conftest import bits, oracle_kinds
+from support import capi, dev, pack, same, stream_ptr
 
 pytestmark = pytest.mark.gpu
 KIND = oracle_kinds()[-1]
@@ -39,17 +40,8 @@ F = np.float32
 EMPTY = [0, 0, -1, -1]
 HSM_ERR_INVALID = -1
 SORTED_BATCH = 1024
-same, dev, new_ctx, levels_of, assert_planes, whole = tshift.same, tshift.dev, tshift.new_ctx, tshift.levels_of, tshift.assert_planes, tshift.whole
-pack, box, posed_update, export_device, stream = tsb.pack, tmoved.box, tmoved.posed_update, tmoved.export_device, tmoved.stream
-
-
-@pytest.fixture(scope="module")
-def capi():
-    import torch
-    assert torch.cuda.is_available(), "gpu-marked tests need a HIP device"
-    from hector_slam_amd import capi as m
-    m.load_library()
-    return m
+new_ctx, levels_of, assert_planes, whole = tshift.new_ctx, tshift.levels_of, tshift.assert_planes, tshift.whole
+box, posed_update, export_device = tmoved.box, tmoved.posed_update, tmoved.export_device
 
 
 class Device:
@@ -80,7 +72,7 @@ class Device:
             self.batches()
         elif name == "export":
             for lvl in range(m.levels):
-                g.occupancy_changes_device(lvl, self.grids[lvl].data_ptr(), self.d_box.data_ptr(), stream())
+                g.occupancy_changes_device(lvl, self.grids[lvl].data_ptr(), self.d_box.data_ptr(), stream_ptr())
         elif name == "serial":
             g.synchronize()
             for lvl in range(m.levels):
@@ -179,7 +171,7 @@ def check_readers(capi, g, m, q, want, what, blank):
         if blank:   # no ray hits anything
             assert (ranges < 0).all() and np.isnan(hit).all() and (dist < 0).all(), (what, lvl)
         d_s, idx = dev(got_scores[lvl]), torch.full((2,), 99, dtype=torch.int32, device="cuda:0")
-        g.select_best_device(2, 0, len(rc.CSR_LENS) // 2, d_s.data_ptr(), 0, idx.data_ptr(), 0, 0, stream())
+        g.select_best_device(2, 0, len(rc.CSR_LENS) // 2, d_s.data_ptr(), 0, idx.data_ptr(), 0, 0, stream_ptr())
         assert np.array_equal(idx.cpu().numpy(), want["best"][lvl][0]), (what, lvl, "select best", idx, want["best"][lvl][0])
     tmoved.check_ranges(capi, g, q, want)
     a0, inc, rmin, rmax = q["laser"]
@@ -209,7 +201,7 @@ def chains(g, m, q, rows):
     idx = torch.full((1,), 99, dtype=torch.int32, device="cuda:0")
     g.match_cov_batch_device(B, d_b.data_ptr(), d_pts.data_ptr(), d_offs.data_ptr(), rc.CSR_LENS[-1], out["pose"].data_ptr(),
                              out["cov"].data_ptr(), 0, out["cw"].data_ptr(), out["cm"].data_ptr(), out["l7"].data_ptr(),
-                             out["lh"].data_ptr(), 1, 0, B, idx.data_ptr(), 0, 0, stream())
+                             out["lh"].data_ptr(), 1, 0, B, idx.data_ptr(), 0, 0, stream_ptr())
     torch.cuda.synchronize()
     cv = {k: v.cpu().numpy() for k, v in out.items()}
     cv["best_index"] = idx.cpu().numpy()

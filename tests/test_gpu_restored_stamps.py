@@ -23,6 +23,7 @@ import pytest
 
 import stamp_cases as sc
 from conftest import bits, oracle_kinds
+from support import capi, dev, layout_of, pack, single_update
 
 pytestmark = pytest.mark.gpu
 
@@ -31,40 +32,12 @@ PARAMS = [(g, U, layout, order) for g in sc.GEOMETRIES for U in sc.COUNTERS for 
 IDS = ["%s-U%d-%s-%s" % (sc.gid(g), U, layout, order) for g, U, layout, order in PARAMS]
 
 
-@pytest.fixture(scope="module")
-def capi():
-    import torch
-    assert torch.cuda.is_available(), "gpu-marked tests need a HIP device"
-    from hector_slam_amd import capi as m
-    m.load_library()
-    return m
-
-
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
-
-
-def pack(scans):
-    offs = np.zeros(len(scans) + 1, np.int32)
-    offs[1:] = np.cumsum([len(s) for s in scans])
-    return np.ascontiguousarray(np.concatenate(scans), np.float32), offs
-
-
-def single_update(capi, g, pose, pts, origo=(0.0, 0.0)):
-    """hsm_retain_scan (what matchData leaves for the coarse levels) + hsm_update_by_scan"""
-    a = np.ascontiguousarray(pts, np.float32).reshape(-1, 2)
-    o = np.ascontiguousarray(origo, np.float32)
-    capi._check(g._lib.hsm_retain_scan(g._h, a.ctypes.data, a.shape[0], o), "hsm_retain_scan")
-    g.updateByScan(a, pose, o)
-
-
 class Restored:
     """a device context and the checkers, both warmed to counter U and restored from stamp_cases' planes"""
 
     def __init__(self, capi, oracle_mod, geom, U, layout, upload=True):
         self.capi, self.om, self.geom, self.U = capi, oracle_mod, geom, U
-        self.g = capi.MapRepMultiMap(sc.RES, geom[0], geom[1], geom[2], layout=capi.LAYOUT_QUAD if layout == "quad" else capi.LAYOUT_PLANE)
+        self.g = capi.MapRepMultiMap(sc.RES, geom[0], geom[1], geom[2], layout=layout_of(capi, layout))
         self.g.setUpdateFactorFree(sc.FACTOR_FREE)
         self.g.setUpdateFactorOccupied(sc.FACTOR_OCC)
         self.refs = {kind: sc.new_checker(oracle_mod, kind, geom) for kind in oracle_kinds()}

@@ -11,6 +11,7 @@ import pytest
 
 import select_rule
 from conftest import bits, make_oracle, oracle_kinds
+from support import capi, dev, layout_of, pack, stream_ptr
 from test_score_batch_abi import selection_cases, wide_start_hypotheses
 
 pytestmark = pytest.mark.gpu
@@ -19,27 +20,6 @@ HSM_ERR_INVALID = -1
 SENTINEL = -777.0
 LENS = (0, 1, 63, 64, 65, 700, 1081)
 FAR_MAP = np.array([[-50.0, 3.0, 0.1], [1e6, 1e6, 0.0]], np.float32)  # (almost) every beam leaves the map
-
-
-@pytest.fixture(scope="module")
-def capi():
-    import torch
-    assert torch.cuda.is_available()
-    from hector_slam_amd import capi as m
-    m.load_library()
-    return m
-
-
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
-
-
-def pack(scans):
-    offs = np.zeros(len(scans) + 1, np.int32)
-    offs[1:] = np.cumsum([len(s) for s in scans])
-    pts = np.concatenate([np.asarray(s, np.float32).reshape(-1, 2) for s in scans]) if offs[-1] else np.zeros((0, 2), np.float32)
-    return np.ascontiguousarray(pts, np.float32), offs
 
 
 def gpu_for(capi, sc, o, sx=None, sy=None, stamps=True, **kw):
@@ -116,7 +96,7 @@ def hypotheses(o, sc, level, rng, lens=LENS, cloud=12):
 def test_csr_batch_is_bit_identical_on_every_level(capi, oracle_mod, pyramid_scene, kind, layout):
     sc = pyramid_scene
     o = make_oracle(oracle_mod, kind, sc)
-    g = gpu_for(capi, sc, o, layout=capi.LAYOUT_QUAD if layout == "quad" else capi.LAYOUT_PLANE)
+    g = gpu_for(capi, sc, o, layout=layout_of(capi, layout))
     rng = np.random.default_rng(17)
     for lvl in range(sc.levels):
         poses, scans = hypotheses(o, sc, lvl, rng)
@@ -140,7 +120,7 @@ def test_csr_batch_is_bit_identical_on_every_level(capi, oracle_mod, pyramid_sce
 def test_shared_scan_gives_the_csr_bits_and_the_old_entry_points_bits(capi, oracle_mod, pyramid_scene, kind, layout):
     sc = pyramid_scene
     o = make_oracle(oracle_mod, kind, sc)
-    g = gpu_for(capi, sc, o, layout=capi.LAYOUT_QUAD if layout == "quad" else capi.LAYOUT_PLANE)
+    g = gpu_for(capi, sc, o, layout=layout_of(capi, layout))
     rng = np.random.default_rng(18)
     for lvl in range(sc.levels):
         for n in LENS:
@@ -324,7 +304,6 @@ def test_host_entry_gives_the_device_entrys_bits_with_every_optional_array(capi,
     must leave alone -- the covariance of the empty scan, the winner pose of a group without a finite score -- keeps the
     caller's values, as does every array of a ranking that was not asked for."""
     import itertools
-    import torch
     from hector_slam_amd import synth
     sc = small_scene
     g = gpu_for(capi, sc, make_oracle(oracle_mod, "ho", sc))
@@ -339,7 +318,7 @@ def test_host_entry_gives_the_device_entrys_bits_with_every_optional_array(capi,
     # (groups, group offsets, group size): eight groups of one -- on the CSR route the first holds the empty scan alone, whose score
     # is NaN -- and four ragged groups, the first the same and the third empty
     rankings = {"none": (0, None, 0), "group_size": (B, None, 1), "group_offsets": (4, np.array([0, 1, 4, 4, 8], np.int32), 0)}
-    stream = torch.cuda.current_stream().cuda_stream
+    stream = stream_ptr()
 
     def fresh(G):
         f = lambda *shape: np.full(shape, SENTINEL, np.float32)  # noqa: E731
@@ -418,7 +397,7 @@ def run_select(g, scores, poses=None, groups=None, group_size=None, group_offset
     bp = torch.full((G, 3), SENTINEL, dtype=torch.float32, device="cuda:0")
     g.select_best_device(G, 0 if d_offs is None else d_offs.data_ptr(), group_size or 0, d_s.data_ptr(),
                          0 if d_p is None else d_p.data_ptr(), idx.data_ptr(), best.data_ptr(), 0 if d_p is None else bp.data_ptr(),
-                         torch.cuda.current_stream().cuda_stream)
+                         stream_ptr())
     return idx.cpu().numpy(), best.cpu().numpy(), bp.cpu().numpy()
 
 

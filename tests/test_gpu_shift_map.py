@@ -16,6 +16,7 @@ import cast_cases
 import frame_cases as fc
 import shift_cases as sc
 from conftest import bits, oracle_kinds
+from support import capi, dev, new_context, same, stream_ptr
 
 pytestmark = pytest.mark.gpu
 KIND = oracle_kinds()[-1]
@@ -30,31 +31,9 @@ DEEP_QUAD = (sc.MAPS[-1], "quad")
 BUILD_BEAMS = 100
 
 
-@pytest.fixture(scope="module")
-def capi():
-    import torch
-    assert torch.cuda.is_available(), "gpu-marked tests need a HIP device"
-    from hector_slam_amd import capi as m
-    m.load_library()
-    return m
-
-
-def same(a, b):
-    return np.array_equal(bits(a), bits(b))
-
-
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
-
-
 def new_ctx(capi, m, layout, start=None):
     """a cleared context in the map's frame (or at `start`) with the update factors of the cases"""
-    g = capi.MapRepMultiMap(m.resolution, m.geom[0], m.geom[1], m.geom[2], startCoords=m.start if start is None else start,
-                            layout=capi.LAYOUT_QUAD if layout == "quad" else capi.LAYOUT_PLANE)
-    g.setUpdateFactorFree(fc.FACTORS[0])
-    g.setUpdateFactorOccupied(fc.FACTORS[1])
-    return g
+    return new_context(capi, m.resolution, m.geom[0], m.geom[1], m.geom[2], m.start if start is None else start, layout, fc.FACTORS)
 
 
 def load(g, planes):
@@ -142,7 +121,7 @@ def test_geometry_planes_matches_and_casts_after_a_move(capi, oracle_mod, m, lay
     d_in, d_pts = dev(starts), dev(pts)
     d_pose, d_cov = torch.zeros((65, 3), device="cuda:0"), torch.zeros((65, 9), device="cuda:0")
     g.match_batch_device(65, d_in.data_ptr(), d_pts.data_ptr(), 0, len(pts), d_pose.data_ptr(), d_cov.data_ptr(),
-                         torch.cuda.current_stream().cuda_stream)
+                         stream_ptr())
     torch.cuda.synchronize()
     want = [o.match(s, pts) for s in starts]
     assert same(d_pose.cpu().numpy(), np.stack([p for p, _ in want])), "batch poses"
@@ -245,7 +224,7 @@ def test_publish_state_after_a_move(capi, oracle_mod, m, layout, device_side):
 
     def export(lvl):
         if device_side:
-            g.occupancy_changes_device(lvl, grids[lvl].data_ptr(), d_box.data_ptr(), torch.cuda.current_stream().cuda_stream)
+            g.occupancy_changes_device(lvl, grids[lvl].data_ptr(), d_box.data_ptr(), stream_ptr())
             g.synchronize()
             torch.cuda.synchronize()
             return [int(v) for v in d_box.cpu()], grids[lvl].cpu().numpy()

@@ -14,23 +14,15 @@ import numpy as np
 import pytest
 
 from conftest import bits, oracle_kinds
+from support import capi, dev, stream_ptr
 import origo_cases as oc
-from test_gpu_update_scans_origos import assert_same_as_ctx, assert_same_as_refs, dev, new_ctx, pack, planes
+from test_gpu_update_scans_origos import assert_same_as_ctx, assert_same_as_refs, new_ctx, pack, planes
 
 pytestmark = pytest.mark.gpu
 
 LEVELS, N = oc.LEVELS, oc.N
 HSM_OK, HSM_ERR_INVALID, HSM_ERR_TOO_LARGE = 0, -1, -4
 COV0 = -777.0
-
-
-@pytest.fixture(scope="module")
-def capi():
-    import torch
-    assert torch.cuda.is_available(), "gpu-marked tests need a HIP device"
-    from hector_slam_amd import capi as m
-    m.load_library()
-    return m
 
 
 @pytest.fixture(scope="module")
@@ -138,7 +130,7 @@ def test_equal_origos_give_the_gated_and_slam_parents_bit_for_bit(capi, traj, en
         m.set_update_gate(*t)
         for lvl in range(LEVELS):
             m.take_dirty_bbox(lvl)
-    s = torch.cuda.current_stream().cuda_stream
+    s = stream_ptr()
     pts, offs = pack(sc.scans)
     d = {"poses": dev(sc.poses), "start": dev(sc.poses[0]), "deltas": dev(sc.deltas), "pts": dev(pts), "offs": dev(offs), "force": dev(force),
          "origos": None if origo is None else dev(np.tile(np.float32(origo), (N, 1)))}
@@ -369,7 +361,7 @@ def test_validation_leaves_outputs_and_map_untouched(capi, traj):
     lib, n = g._lib, r.shape[1]
     need = g.slam_ranges_tf_workspace(4, n)
     d = {"ranges": dev(r[:4]), "T": dev(T[:4]), "ws": torch.full((need + 8,), 0x5A, dtype=torch.uint8, device="cuda:0"), **outputs(4)}
-    s = torch.cuda.current_stream().cuda_stream
+    s = stream_ptr()
     null = object()
 
     def call(count=4, n=n, h=g._h, ranges=None, tf=None, pose=None, ws=None, ws_bytes=need):

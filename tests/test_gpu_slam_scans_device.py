@@ -17,7 +17,9 @@ Nothing here provokes a device fault."""
 import numpy as np
 import pytest
 
-from conftest import bits, oracle_kinds
+from conftest import bits
+import support
+from support import capi, dev, new_context, pack, stream_ptr
 
 pytestmark = pytest.mark.gpu
 
@@ -32,15 +34,6 @@ FLT_MAX = np.finfo(np.float32).max
 
 
 @pytest.fixture(scope="module")
-def capi():
-    import torch
-    assert torch.cuda.is_available(), "gpu-marked tests need a HIP device"
-    from hector_slam_amd import capi as m
-    m.load_library()
-    return m
-
-
-@pytest.fixture(scope="module")
 def traj():
     from hector_slam_amd import synth
     sc = synth.make_scene(n_beams=1081, map_size=512, levels=LEVELS, resolution=RES, n_build=64, n_query=8, room=(16.0, 12.0), seed=2024)
@@ -51,35 +44,14 @@ def traj():
     return sc
 
 
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
-
-
-def pack(scans):
-    offs = np.zeros(len(scans) + 1, np.int32)
-    offs[1:] = np.cumsum([len(s) for s in scans])
-    pts = np.concatenate([np.asarray(s, np.float32).reshape(-1, 2) for s in scans]) if offs[-1] else np.zeros((0, 2), np.float32)
-    return np.ascontiguousarray(pts, np.float32), offs
-
-
 def new_ctx(capi, geom="square", layout="quad"):
     sx, sy = GEOMS[geom]
-    g = capi.MapRepMultiMap(RES, sx, sy, LEVELS, layout=capi.LAYOUT_QUAD if layout == "quad" else capi.LAYOUT_PLANE)
-    g.setUpdateFactorFree(0.4)
-    g.setUpdateFactorOccupied(0.9)
-    return g
+    return new_context(capi, RES, sx, sy, LEVELS, layout=layout)
 
 
 def new_refs(oracle_mod, geom="square"):
     sx, sy = GEOMS[geom]
-    refs = {}
-    for kind in oracle_kinds():
-        o = oracle_mod.Oracle(kind, RES, sx, sy, LEVELS)
-        o.set_update_factor_free(0.4)
-        o.set_update_factor_occupied(0.9)
-        refs[kind] = o
-    return refs
+    return support.new_refs(oracle_mod, RES, sx, sy, LEVELS)
 
 
 def host_path(capi, g, poses, scans, origo=ZERO2):
@@ -213,7 +185,6 @@ def test_state_persists_and_folds(capi, oracle_mod, traj):
     assert np.array_equal(bits(pose), bits(gate.last)) and total == gate.count == int(flags.sum())
 
     # gated -> host updateByScan -> ungated device update -> gated, queued back to back; the same sequence on the checkers
-    import torch
     t = THRESHOLDS["wide"]
     gates = {kind: Gate(o, t) for kind, o in refs.items()}
     want = []
@@ -231,7 +202,7 @@ def test_state_persists_and_folds(capi, oracle_mod, traj):
     host_path(capi, mix, sc.poses[8:9], sc.scans[8:9])
     pts, offs = pack(sc.scans[9:12])
     d = [dev(sc.poses[9:12]), dev(pts), dev(offs)]
-    mix.update_by_scans_device(3, d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), 0, 1081, None, torch.cuda.current_stream().cuda_stream)
+    mix.update_by_scans_device(3, d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), 0, 1081, None, stream_ptr())
     k2 = gated(mix, sc.poses[12:], sc.scans[12:])
     mix.synchronize()
     assert np.array_equal(np.concatenate([k1[1].cpu().numpy(), k2[1].cpu().numpy()]), want.astype(np.int32))

@@ -22,19 +22,11 @@ import pytest
 
 import order_cases as oc
 from conftest import bits, oracle_kinds
+from support import capi, dev, new_context, single_update
 
 pytestmark = pytest.mark.gpu
 
 MIN_CELLS = 100
-
-
-@pytest.fixture(scope="module")
-def capi():
-    import torch
-    assert torch.cuda.is_available(), "gpu-marked tests need a HIP device"
-    from hector_slam_amd import capi as m
-    m.load_library()
-    return m
 
 
 @pytest.fixture(scope="module")
@@ -55,23 +47,9 @@ def reference(oracle_mod):
 
 def new_ctx(capi, map_name, layout="quad"):
     sx, sy = oc.MAPS[map_name]
-    g = capi.MapRepMultiMap(oc.RES, sx, sy, oc.LEVELS, layout=capi.LAYOUT_QUAD if layout == "quad" else capi.LAYOUT_PLANE)
-    g.setUpdateFactorFree(oc.FACTOR_FREE)
-    g.setUpdateFactorOccupied(oc.FACTOR_OCC)
+    g = new_context(capi, oc.RES, sx, sy, oc.LEVELS, layout=layout, factors=(oc.FACTOR_FREE, oc.FACTOR_OCC))
     g.map_name = map_name
     return g
-
-
-def single_update(capi, g, pose, pts):
-    """the single-scan form: hsm_retain_scan (what matchData leaves for the coarse levels) + hsm_update_by_scan"""
-    a = np.ascontiguousarray(pts, np.float32).reshape(-1, 2)
-    capi._check(g._lib.hsm_retain_scan(g._h, a.ctypes.data, a.shape[0], np.zeros(2, np.float32)), "hsm_retain_scan")
-    g.updateByScan(a, pose)
-
-
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
 
 
 def device_update(g, pose, scans, shared=False, gated=False):

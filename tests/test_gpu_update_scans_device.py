@@ -14,7 +14,9 @@ The only input on which the reference is undefined is the NaN pose: (int)NaN is 
 import numpy as np
 import pytest
 
-from conftest import bits, oracle_kinds
+from conftest import bits
+import support
+from support import capi, dev, new_context, pack
 
 pytestmark = pytest.mark.gpu
 
@@ -23,15 +25,6 @@ HSM_ERR_INVALID = -1
 ZERO2 = np.zeros(2, np.float32)
 LEVELS = 3
 GEOMS = {"square": (512, 512), "rect": (500, 360)}  # rect: rows that are no multiple of 64 cells, sx != sy on every level
-
-
-@pytest.fixture(scope="module")
-def capi():
-    import torch
-    assert torch.cuda.is_available(), "gpu-marked tests need a HIP device"
-    from hector_slam_amd import capi as m
-    m.load_library()
-    return m
 
 
 @pytest.fixture(scope="module")
@@ -44,35 +37,14 @@ def traj():
     return sc
 
 
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
-
-
-def pack(scans):
-    offs = np.zeros(len(scans) + 1, np.int32)
-    offs[1:] = np.cumsum([len(s) for s in scans])
-    pts = np.concatenate([np.asarray(s, np.float32).reshape(-1, 2) for s in scans]) if offs[-1] else np.zeros((0, 2), np.float32)
-    return np.ascontiguousarray(pts, np.float32), offs
-
-
 def new_ctx(capi, geom, layout="quad"):
     sx, sy = GEOMS[geom]
-    g = capi.MapRepMultiMap(RES, sx, sy, LEVELS, layout=capi.LAYOUT_QUAD if layout == "quad" else capi.LAYOUT_PLANE)
-    g.setUpdateFactorFree(0.4)
-    g.setUpdateFactorOccupied(0.9)
-    return g
+    return new_context(capi, RES, sx, sy, LEVELS, layout=layout)
 
 
 def new_refs(oracle_mod, geom):
     sx, sy = GEOMS[geom]
-    refs = {}
-    for kind in oracle_kinds():
-        o = oracle_mod.Oracle(kind, RES, sx, sy, LEVELS)
-        o.set_update_factor_free(0.4)
-        o.set_update_factor_occupied(0.9)
-        refs[kind] = o
-    return refs
+    return support.new_refs(oracle_mod, RES, sx, sy, LEVELS)
 
 
 def ref_update(refs, poses, scans, origo=ZERO2):

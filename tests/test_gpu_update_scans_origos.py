@@ -12,20 +12,13 @@ import numpy as np
 import pytest
 
 from conftest import bits, oracle_kinds
+import support
+from support import capi, dev, new_context, stream_ptr
 import origo_cases as oc
 
 pytestmark = pytest.mark.gpu
 
 LEVELS, N = oc.LEVELS, oc.N
-
-
-@pytest.fixture(scope="module")
-def capi():
-    import torch
-    assert torch.cuda.is_available(), "gpu-marked tests need a HIP device"
-    from hector_slam_amd import capi as m
-    m.load_library()
-    return m
 
 
 @pytest.fixture(scope="module")
@@ -39,24 +32,15 @@ def guard(oracle_mod):
         oc.assert_the_reference_depends_on_the_origo(kind)
 
 
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
-
-
 def pack(scans):
-    offs = np.zeros(len(scans) + 1, np.int32)
-    offs[1:] = np.cumsum([len(s) for s in scans])
-    pts = np.concatenate([np.asarray(s, np.float32).reshape(-1, 2) for s in scans]) if offs[-1] else np.zeros((1, 2), np.float32)
-    return np.ascontiguousarray(pts, np.float32), offs
+    """support.pack, with an empty log padded to one row so that the device pointer is not null"""
+    pts, offs = support.pack(scans)
+    return (pts if offs[-1] else np.zeros((1, 2), np.float32)), offs
 
 
 def new_ctx(capi, geom="square", layout="quad"):
     sx, sy = oc.GEOMS[geom]
-    g = capi.MapRepMultiMap(oc.RES, sx, sy, LEVELS, layout=capi.LAYOUT_QUAD if layout == "quad" else capi.LAYOUT_PLANE)
-    g.setUpdateFactorFree(0.4)
-    g.setUpdateFactorOccupied(0.9)
-    return g
+    return new_context(capi, oc.RES, sx, sy, LEVELS, layout=layout)
 
 
 def planes(g):
@@ -138,7 +122,6 @@ def test_one_shared_scan_at_24_poses_and_24_origos(capi, oracle_mod, traj, geom)
 # ---- 5: no behaviour change ----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("origo", [(3.25, -4.5), None], ids=["one pair", "null"])
 def test_equal_origos_give_the_parent_entry_bit_for_bit(capi, traj, origo):
-    import torch
     sc = traj
     g, h = new_ctx(capi, "rect"), new_ctx(capi, "rect")
     for m in (g, h):
@@ -148,7 +131,7 @@ def test_equal_origos_give_the_parent_entry_bit_for_bit(capi, traj, origo):
     pts, offs = pack(sc.scans)
     d = [dev(sc.poses), dev(pts), dev(offs)]
     h.update_by_scans_device(N, d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), 0, 1081, None if origo is None else np.float32(origo),
-                             torch.cuda.current_stream().cuda_stream)
+                             stream_ptr())
     assert g.last_launch_config() == h.last_launch_config()
     for lvl in range(LEVELS):
         assert np.array_equal(g.last_update_bbox(lvl), h.last_update_bbox(lvl)), lvl
@@ -197,7 +180,7 @@ def test_gated_update_with_an_origo_per_scan(capi, oracle_mod, traj, thr, forced
     d = [dev(sc.poses), dev(pts), dev(offs), dev(sc.origos), None if force is None else dev(force),
          torch.full((N,), -7, dtype=torch.int32, device="cuda:0")]
     g.update_by_scans_device_gated_origos(N, d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), 0, 1081, d[3].data_ptr(),
-                                          0 if force is None else d[4].data_ptr(), d[5].data_ptr(), torch.cuda.current_stream().cuda_stream)
+                                          0 if force is None else d[4].data_ptr(), d[5].data_ptr(), stream_ptr())
     g.synchronize()
     assert np.array_equal(d[5].cpu().numpy(), flags.astype(np.int32)), (d[5].cpu().numpy(), flags.astype(int))
     pose, total = g.update_gate_state()

@@ -14,6 +14,7 @@ import select_rule
 import topk_rule
 import window_cases
 from conftest import bits, make_oracle, oracle_kinds
+from support import capi, dev, layout_of, stream_ptr
 from test_window_model import reference_relocalize
 
 pytestmark = pytest.mark.gpu
@@ -23,25 +24,6 @@ SENTINEL = -777.0
 LENS = (0, 1, 63, 64, 65, 200)
 FORMS = ("lane", "wave")
 KERNEL = {"lane": b"score_window_lane_kernel", "wave": b"score_window_wave_kernel"}
-
-
-@pytest.fixture(scope="module")
-def capi():
-    import torch
-    assert torch.cuda.is_available()
-    from hector_slam_amd import capi as m
-    m.load_library()
-    return m
-
-
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
-
-
-def stream_ptr():
-    import torch
-    return torch.cuda.current_stream().cuda_stream
 
 
 def gpu_for(capi, sc, o, sx=None, sy=None, stamps=True, **kw):
@@ -132,7 +114,7 @@ def test_window_scores_are_bit_identical_in_both_forms(capi, oracle_mod, pyramid
     sc = pyramid_scene
     o = make_oracle(oracle_mod, kind, sc)
     forced(monkeypatch, form)
-    g = gpu_for(capi, sc, o, layout=capi.LAYOUT_QUAD if layout == "quad" else capi.LAYOUT_PLANE)
+    g = gpu_for(capi, sc, o, layout=layout_of(capi, layout))
     lib = capi.load_library()
     truth = sc.query_truth[1].astype(np.float32)
     centre = (truth + np.float32([0.03, -0.02, 0.01])).astype(np.float32)

@@ -12,6 +12,7 @@ import subprocess
 import pytest
 
 import match_form_sites as mfs
+from support import build_check
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "match_forms.json")
@@ -32,10 +33,7 @@ def golden():
 
 @pytest.fixture(scope="module")
 def check(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("match_plan") / "match_plan_check"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "hector_slam_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "cpp", "match_plan_check.cpp"), "-o", str(exe)], check=True)
-    return str(exe)
+    return str(build_check(tmp_path_factory.mktemp("match_plan"), "match_plan_check.cpp"))
 
 
 def flat(site, cu):

@@ -13,7 +13,6 @@ At the parent commit the symbol test fails: the entries do not exist.
 """
 import ctypes as C
 import os
-import re
 import subprocess
 
 import numpy as np
@@ -21,6 +20,7 @@ import pytest
 
 import merge_cases as mc
 import newer_entry_cases as nc
+from support import check_symbols, compile_c99, header_text
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ("hsm_merge_map", "hsm_merge_map_box")
@@ -28,22 +28,10 @@ HSM_ERR_INVALID = -1
 F = np.float32
 
 
-def _header():
-    return open(os.path.join(ROOT, "include", "hector_mi355", "capi.h")).read()
-
-
 def test_new_symbols_declared_bound_and_exported():
     from hector_slam_amd import build, capi
-    code = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-    build.build_native()
-    lib = capi.load_library()
-    for name in NEW_SYMBOLS:
-        assert re.search(r"\bint\s+" + name + r"\s*\(", code), name
-        assert name in capi.SIGNATURES, name
-        assert hasattr(lib, name), name
-        decl = re.search(r"\b" + name + r"\s*\((.*?)\)\s*;", code, re.S).group(1)
-        assert len(capi.SIGNATURES[name][1]) == decl.count(",") + 1, (name, decl)
-    head = _header()
+    check_symbols(NEW_SYMBOLS)
+    head = header_text()
     assert "fminf(d + v, 50.0f)" in head and "HSM_COPY_STAGE=1" in head
     assert "the cross-device merge itself has not been run" in head
     assert callable(capi.merge_map) and callable(capi.merge_map_box)
@@ -54,14 +42,11 @@ def test_new_symbols_declared_bound_and_exported():
 
 
 def test_header_with_the_new_entries_is_plain_c99(tmp_path):
-    src = tmp_path / "use.c"
-    src.write_text('#include "hector_mi355/capi.h"\n'
-                   "int main(void) { hsm_ctx* a = 0; hsm_ctx* b = 0; const float t[3] = {0.0f, 0.0f, 0.0f}; int box[4];\n"
-                   "  int rc = hsm_merge_map(a, b, t);\n"
-                   "  rc += hsm_merge_map_box(a, b, t, 0, box);\n"
-                   "  return rc; }\n")
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-c", str(src), "-I",
-                    os.path.join(ROOT, "include"), "-o", str(tmp_path / "use.o")], check=True)
+    compile_c99(tmp_path,
+                "int main(void) { hsm_ctx* a = 0; hsm_ctx* b = 0; const float t[3] = {0.0f, 0.0f, 0.0f}; int box[4];\n"
+                "  int rc = hsm_merge_map(a, b, t);\n"
+                "  rc += hsm_merge_map_box(a, b, t, 0, box);\n"
+                "  return rc; }\n")
 
 
 def test_box_header_is_plain_cpp():

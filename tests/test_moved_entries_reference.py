@@ -16,15 +16,12 @@ import pytest
 
 import moved_entry_cases as mc
 from conftest import bits, oracle_kinds
+from support import same
 from test_gpu_slam_scans_device import Gate
 
 F = np.float32
 KINDS = oracle_kinds()
 MAPS = pytest.mark.parametrize("m", mc.MAPS, ids=[m.id for m in mc.MAPS])
-
-
-def same(a, b):
-    return np.array_equal(bits(a), bits(b))
 
 
 def same_planes(a, b):

@@ -24,15 +24,12 @@ import pytest
 import entry_geometry_cases as egc
 import merge_cases as mc
 import newer_entry_cases as nc
-from conftest import bits, oracle_kinds
+from conftest import oracle_kinds
+from support import same
 
 F = np.float32
 COV = pytest.mark.parametrize("m", nc.COV_MAPS, ids=[m.id for m in nc.COV_MAPS])
 ULPS = 8
-
-
-def same(a, b):
-    return np.array_equal(bits(a), bits(b))
 
 
 def test_the_lists_are_the_issues():

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from conftest import bits, make_oracle
+from support import capi
 
 
 def synthetic_ranges(rng, n, lo=0.0, hi=35.0):
@@ -216,15 +217,6 @@ def test_node_scan_callback_equals_the_processor_loop(oracle_mod):
         po, co = o.proc_last_pose()
         assert np.array_equal(bits(pn), bits(po)) and np.array_equal(bits(cn), bits(co)), ("tf path", t)
         last = po
-
-
-@pytest.fixture(scope="module")
-def capi():
-    import torch
-    assert torch.cuda.is_available()
-    from hector_slam_amd import capi as m
-    m.load_library()
-    return m
 
 
 @pytest.mark.gpu

@@ -3,20 +3,16 @@ on the GRID, a ragged tail) on the CPU: tests/cpp/occupancy_rows_check.cpp compi
 holds it to a byte-by-byte restatement for every box row 0 <= x0 <= x1 < 40 (clipped to the width) on 8 rows of grids 25, 38 and
 40 cells wide -- an odd width, an even one that is no multiple of 4, and a multiple of 4, so every phase of a row's first cell
 against the 4-cell alignment occurs.  Equality of byte grids: no tolerance."""
-import os
 import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from support import build_check
 
 
 @pytest.fixture(scope="module")
 def model(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("occ_rows") / "occupancy_rows_check"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "hector_slam_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "cpp", "occupancy_rows_check.cpp"), "-o", str(exe)], check=True)
-    return exe
+    return build_check(tmp_path_factory.mktemp("occ_rows"), "occupancy_rows_check.cpp")
 
 
 @pytest.mark.parametrize("width", [25, 38, 40])

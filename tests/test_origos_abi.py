@@ -11,6 +11,8 @@ import subprocess
 
 import numpy as np
 
+from support import build_check, header_code, header_text
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HSM_OK, HSM_ERR_INVALID = 0, -1
 HSM_MAX_UPDATE_BEAMS = 1048575
@@ -23,9 +25,7 @@ METHODS = ("update_by_scans_device_origos", "update_by_scans_device_gated_origos
 
 
 def declarations():
-    src = open(os.path.join(ROOT, "include", "hector_mi355", "capi.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return {m.group(1): m.group(2) for m in re.finditer(r"\b(hsm_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;", src, re.S)}
+    return {m.group(1): m.group(2) for m in re.finditer(r"\b(hsm_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;", header_code(), re.S)}
 
 
 def test_entries_are_declared_bound_and_exported():
@@ -46,7 +46,7 @@ def test_entries_are_declared_bound_and_exported():
 
 
 def test_header_says_what_is_left():
-    src = open(os.path.join(ROOT, "include", "hector_mi355", "capi.h")).read()
+    src = header_text()
     assert "Not built: per-scan origos" not in src and "splits the log" not in src
     for word in ("capture into graphs", "hsm_group_*", "byte-map (dense) form", "non-tf conversion", "facade"):
         assert word in src[src.index("hsm_slam_scans_device_origos on what it wrote"):src.index("int hsm_slam_ranges_tf_device(")], word
@@ -79,10 +79,7 @@ def test_refusals_without_a_device_leave_the_outputs_untouched():
 def test_workspace_is_the_sum_of_its_parts(tmp_path):
     from hector_slam_amd import capi
     lib = capi.load_library()
-    exe = tmp_path / "slam_ranges_tf_layout_check"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "hector_slam_amd", "csrc"), "-I",
-                    os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "slam_ranges_tf_layout_check.cpp"), "-o", str(exe)],
-                   check=True)
+    exe = build_check(tmp_path, "slam_ranges_tf_layout_check.cpp", "-I", os.path.join(ROOT, "include"))
     sizes = [(1, 1), (24, 1081), (256, 1081), (63, 64), (64, 63), (65, 65), (7, 0), (0, 181), (0, 0), (1, HSM_MAX_UPDATE_BEAMS),
              (2048, HSM_MAX_UPDATE_BEAMS), (-1, 181), (4, -1), (1, HSM_MAX_UPDATE_BEAMS + 1), (4096, HSM_MAX_UPDATE_BEAMS)]
     out = subprocess.run([str(exe)] + [str(v) for s in sizes for v in s], capture_output=True, text=True, check=True).stdout.split("\n")

@@ -1,14 +1,11 @@
 """B raw LaserScans in, B poses out (hsm_match_batch_ranges*): the C ABI, the workspace arithmetic and the numpy statement of
 the batched conversion the GPU tests hold the device to.  No compute calls on a device: runs without a GPU."""
-import os
-import re
-
 import numpy as np
 import pytest
 
 from conftest import bits
+from support import check_symbols
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("hsm_match_batch_ranges_device", "hsm_match_batch_ranges_workspace", "hsm_match_batch_ranges")
 INT_MAX = 2**31 - 1
 GEOM = (np.float32(-2.35619449), np.float32(0.00436332), np.float32(0.4), np.float32(30.0))  # angle_min, increment, range gate
@@ -28,14 +25,7 @@ def synthetic_batch(rng, B, n, lo=0.0, hi=35.0):
 
 
 def test_names_are_declared_bound_and_exported():
-    from hector_slam_amd import build, capi
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "hector_mi355", "capi.h")).read(), flags=re.S)
-    build.build_native()
-    lib = capi.load_library()
-    for name in NAMES:
-        assert re.search(r"\b" + name + r"\s*\(", src), name
-        assert name in capi.SIGNATURES, name
-        assert hasattr(lib, name), name
+    check_symbols(NAMES, restype=r"(int|size_t)")  # the workspace size is a size_t
 
 
 def test_workspace_covers_the_csr_container_and_grows_with_the_batch():

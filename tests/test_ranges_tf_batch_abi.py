@@ -1,29 +1,20 @@
 """B raw LaserScans and a transform per scan through the node's default tf path (hsm_ingest_batch_ranges_tf_device,
 hsm_match_batch_ranges_tf): the C ABI and the numpy statement of the batched conversion (synth.ranges_tf_to_csr) the GPU tests
 fall back to.  No compute calls on a device: runs without a GPU."""
-import os
-import re
-
 import numpy as np
 import pytest
 
 from conftest import bits
+from support import check_symbols
 import ranges_tf_cases as tc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("hsm_ingest_batch_ranges_tf_device", "hsm_match_batch_ranges_tf")
 SHAPES = ((1, 1, 20.0), (7, 181, 20.0), (33, 1081, 20.0), (5, 1440, 10.0), (3, 0, 20.0))  # B, n, scale_to_map
 
 
 def test_names_are_declared_bound_and_exported():
-    from hector_slam_amd import build, capi
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "hector_mi355", "capi.h")).read(), flags=re.S)
-    build.build_native()
-    lib = capi.load_library()
-    for name in NAMES:
-        assert re.search(r"\b" + name + r"\s*\(", src), name
-        assert name in capi.SIGNATURES, name
-        assert hasattr(lib, name), name
+    from hector_slam_amd import capi
+    check_symbols(NAMES)
     for method in ("ingest_batch_ranges_tf_device", "match_batch_ranges_tf"):
         assert callable(getattr(capi.MapRepMultiMap, method))
 

@@ -10,7 +10,6 @@ forms): what can be checked without a GPU.
 """
 import ctypes as C
 import os
-import re
 import subprocess
 
 import numpy as np
@@ -18,45 +17,30 @@ import pytest
 
 import select_rule
 from conftest import make_oracle, oracle_kinds
+from support import check_symbols, compile_c99, header_text
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ("hsm_score_batch_device", "hsm_select_best_device", "hsm_match_score_batch_device", "hsm_match_score_batch")
 HSM_ERR_INVALID = -1
 
 
-def _header():
-    return open(os.path.join(ROOT, "include", "hector_mi355", "capi.h")).read()
-
-
 def test_new_symbols_declared_bound_and_exported():
-    from hector_slam_amd import build, capi
-    code = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-    build.build_native()
-    lib = capi.load_library()
-    for name in NEW_SYMBOLS:
-        assert re.search(r"\bint\s+" + name + r"\s*\(", code), name
-        assert name in capi.SIGNATURES, name
-        assert hasattr(lib, name), name
-        # the binding passes as many arguments as the header declares
-        decl = re.search(r"\b" + name + r"\s*\((.*?)\)\s*;", code, re.S).group(1)
-        assert len(capi.SIGNATURES[name][1]) == decl.count(",") + 1, (name, decl)
-    head = _header()
+    from hector_slam_amd import capi
+    check_symbols(NEW_SYMBOLS)
+    head = header_text()
     assert "OccGridMapUtil.h:184-221" in head and "getMapCoordsPose" in head  # the "replaces:" line of the new block
     for meth in ("score_batch_device", "select_best_device", "match_score_batch_device", "score_batch", "match_score_batch"):
         assert callable(getattr(capi.MapRepMultiMap, meth)), meth
 
 
 def test_header_with_the_new_entries_is_plain_c99(tmp_path):
-    src = tmp_path / "use.c"
-    src.write_text('#include "hector_mi355/capi.h"\n'
-                   "int main(void) { hsm_ctx* h = 0; int idx[1] = {0}; float f[3] = {0.0f, 0.0f, 0.0f};\n"
-                   "  int rc = hsm_score_batch_device(h, 0, 1, f, f, 0, 1, f, 0, 0);\n"
-                   "  rc += hsm_select_best_device(h, 1, 0, 1, f, f, idx, f, f, 0);\n"
-                   "  rc += hsm_match_score_batch_device(h, 1, f, f, 0, 1, f, 0, 0, f, 0, 1, 0, 1, idx, f, f, 0);\n"
-                   "  rc += hsm_match_score_batch(h, 1, f, f, 0, 1, f, 0, 0, f, 0, 1, 0, 1, idx, f, f);\n"
-                   "  return rc; }\n")
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-c", str(src), "-I",
-                    os.path.join(ROOT, "include"), "-o", str(tmp_path / "use.o")], check=True)
+    compile_c99(tmp_path,
+                "int main(void) { hsm_ctx* h = 0; int idx[1] = {0}; float f[3] = {0.0f, 0.0f, 0.0f};\n"
+                "  int rc = hsm_score_batch_device(h, 0, 1, f, f, 0, 1, f, 0, 0);\n"
+                "  rc += hsm_select_best_device(h, 1, 0, 1, f, f, idx, f, f, 0);\n"
+                "  rc += hsm_match_score_batch_device(h, 1, f, f, 0, 1, f, 0, 0, f, 0, 1, 0, 1, idx, f, f, 0);\n"
+                "  rc += hsm_match_score_batch(h, 1, f, f, 0, 1, f, 0, 0, f, 0, 1, 0, 1, idx, f, f);\n"
+                "  return rc; }\n")
 
 
 def test_null_context_is_invalid_for_every_new_entry():

@@ -11,16 +11,15 @@ import subprocess
 
 import pytest
 
+from support import build_check
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "hector_slam_amd", "csrc")
 
 
 @pytest.fixture(scope="module")
 def check(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("settings") / "settings_check"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-I", CSRC, "-I", os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "tests", "cpp", "settings_check.cpp"), "-o", str(exe)], check=True)
-    return str(exe)
+    return str(build_check(tmp_path_factory.mktemp("settings"), "settings_check.cpp", "-I", os.path.join(ROOT, "include")))
 
 
 def test_parser_is_the_chain_it_replaced(check):

@@ -6,31 +6,17 @@
 * the new unit is part of the build, with its kernels and its plan.
 """
 import ctypes as C
-import os
-import re
-import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from support import check_symbols, compile_c99, header_text
+
 NEW_SYMBOLS = ("hsm_shift_map", "hsm_map_start")
 HSM_ERR_INVALID = -1
 
 
-def _header():
-    return open(os.path.join(ROOT, "include", "hector_mi355", "capi.h")).read()
-
-
 def test_new_symbols_declared_bound_and_exported():
     from hector_slam_amd import build, capi
-    code = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-    build.build_native()
-    lib = capi.load_library()
-    for name in NEW_SYMBOLS:
-        assert re.search(r"\bint\s+" + name + r"\s*\(", code), name
-        assert name in capi.SIGNATURES, name
-        assert hasattr(lib, name), name
-        decl = re.search(r"\b" + name + r"\s*\((.*?)\)\s*;", code, re.S).group(1)
-        assert len(capi.SIGNATURES[name][1]) == decl.count(",") + 1, (name, decl)
-    head = _header()
+    check_symbols(NEW_SYMBOLS)
+    head = header_text()
     assert "carries the old transforms in its kernel arguments" in head and "capture it again after the move" in head
     assert "1/64 cell" in head and "2^(levels - 1)" in head and "never accumulated" in head
     assert "group-wide move" in head and "C++ facade" in head and "hsm_slam_scans_device" in head
@@ -42,15 +28,12 @@ def test_new_symbols_declared_bound_and_exported():
 
 
 def test_header_with_the_new_entries_is_plain_c99(tmp_path):
-    src = tmp_path / "use.c"
-    src.write_text('#include "hector_mi355/capi.h"\n'
-                   "int main(void) { hsm_ctx* a = 0; int d[2] = {0, 0}; float s[2] = {0.0f, 0.0f};\n"
-                   "  int rc = hsm_shift_map(a, 0.5f, 0.5f, d);\n"
-                   "  rc += hsm_shift_map(a, 0.5f, 0.5f, 0);\n"
-                   "  rc += hsm_map_start(a, s);\n"
-                   "  return rc; }\n")
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-c", str(src), "-I",
-                    os.path.join(ROOT, "include"), "-o", str(tmp_path / "use.o")], check=True)
+    compile_c99(tmp_path,
+                "int main(void) { hsm_ctx* a = 0; int d[2] = {0, 0}; float s[2] = {0.0f, 0.0f};\n"
+                "  int rc = hsm_shift_map(a, 0.5f, 0.5f, d);\n"
+                "  rc += hsm_shift_map(a, 0.5f, 0.5f, 0);\n"
+                "  rc += hsm_map_start(a, s);\n"
+                "  return rc; }\n")
 
 
 def test_null_context_is_invalid_for_both_entries():

@@ -2,24 +2,20 @@
 that survive in old and in new coordinates, the refusals) on the CPU: tests/cpp/shift_plan_check.cpp compiles the header with
 the host compiler alone, and every plan it prints is held to the numpy model of tests/shift_cases.py -- for every move of every
 map of the suite, for 2000 seeded random (size, levels, start, start') draws, and for the refusals.  Integers and bits: no tolerance."""
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
 import shift_cases as sc
+from support import build_check
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
 
 
 @pytest.fixture(scope="module")
 def checker(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("shift_plan") / "shift_plan_check"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "hector_slam_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "cpp", "shift_plan_check.cpp"), "-o", str(exe)], check=True)
-    return exe
+    return build_check(tmp_path_factory.mktemp("shift_plan"), "shift_plan_check.cpp")
 
 
 def fbits(x):

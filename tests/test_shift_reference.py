@@ -17,15 +17,12 @@ import pytest
 import frame_cases as fc
 import shift_cases as sc
 from conftest import bits, oracle_kinds
+from support import same
 
 F = np.float32
 KINDS = oracle_kinds()
 MAPS = pytest.mark.parametrize("m", sc.MAPS, ids=[m.id for m in sc.MAPS])
 NAMES = pytest.mark.parametrize("name", sc.SHIFT_NAMES)
-
-
-def same(a, b):
-    return np.array_equal(bits(a), bits(b))
 
 
 @MAPS

@@ -5,17 +5,13 @@ tests/cpp/stage_layout_check.cpp restates them literally and compares every offs
 batch or n of 0 and 1, sizes one byte either side of a 256-byte multiple, n = HSM_MAX_UPDATE_BEAMS, refused batch * n > INT_MAX.
 Exact comparison, no tolerance."""
 import json
-import os
 import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from support import INCLUDE, build_check
 
 
 def test_header_gives_the_written_out_sums(tmp_path):
-    exe = tmp_path / "stage_layout_check"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "hector_slam_amd", "csrc"),
-                    "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "stage_layout_check.cpp"),
-                    "-o", str(exe)], check=True)
+    exe = build_check(tmp_path, "stage_layout_check.cpp", "-I", INCLUDE)
     r = subprocess.run([str(exe)], capture_output=True, text=True)
     rec = json.loads(r.stdout.strip().splitlines()[-1])
     assert r.returncode == 0 and rec["mismatches"] == 0, (rec, r.stderr[-2000:])

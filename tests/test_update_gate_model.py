@@ -3,25 +3,21 @@ reference's fp32 / fp64 mix, and the sequential walk over a log of poses that th
 CPU: tests/cpp/update_gate_model.cpp compiles the header with the host compiler alone, and every decision is compared with
 `Oracle.pose_difference_larger_than` of both checker kinds ("hr": the unmodified UtilFunctions.h, where its library is present).
 Decisions are booleans: equal or not, no tolerance."""
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import oracle_kinds
+from support import build_check
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FLT_MAX = np.finfo(np.float32).max
 DEFAULTS = (0.4, 0.13)  # HectorSlamProcessor.h:62-63
 
 
 @pytest.fixture(scope="module")
 def model(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("gate") / "update_gate_model"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "hector_slam_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "cpp", "update_gate_model.cpp"), "-o", str(exe)], check=True)
-    return exe
+    return build_check(tmp_path_factory.mktemp("gate"), "update_gate_model.cpp")
 
 
 @pytest.fixture(scope="module")

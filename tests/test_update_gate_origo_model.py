@@ -5,13 +5,13 @@ the (first point, length, origo) of level 0 and of the coarse levels must equal 
 matchData copies the scan into dataContainers[l-1] -- points and origo, DataContainer::setFrom -- for every scan that is
 matched (MapRepMultiMap.h:127), a forced scan skips matchData (HectorSlamProcessor.h:75-80), and updateByScan gives level 0 the
 scan's own container and level l >= 1 dataContainers[l-1] (MapRepMultiMap.h:143).  Integers and copied floats: no tolerance."""
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from support import build_check
+
 FLT_MAX = np.finfo(np.float32).max
 REC = np.dtype([("pose", np.float32, 3), ("force", np.int32), ("first", np.int32), ("n", np.int32), ("origo", np.float32, 2)])
 SRC = [("first", np.int32), ("n", np.int32), ("origo", np.float32, 2)]
@@ -20,10 +20,7 @@ OUT = np.dtype([("applied", np.int32), ("rank", np.int32), ("fine", SRC), ("coar
 
 @pytest.fixture(scope="module")
 def model(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("gate_origo") / "update_gate_origo_model"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "hector_slam_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "cpp", "update_gate_origo_model.cpp"), "-o", str(exe)], check=True)
-    return exe
+    return build_check(tmp_path_factory.mktemp("gate_origo"), "update_gate_origo_model.cpp")
 
 
 def run(model, tmp_path, thresholds, slam, rec):

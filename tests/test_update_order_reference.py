@@ -12,15 +12,11 @@ import numpy as np
 import pytest
 
 import order_cases as oc
-from conftest import bits, oracle_kinds
+from conftest import bits
+from support import kind
 
 ALL_CASES = oc.DENSE_CASES + oc.KEYED_CASES
 MIN_CELLS = 100
-
-
-@pytest.fixture(scope="module", params=oracle_kinds())
-def kind(request):
-    return request.param
 
 
 def same_snapshots(a, b, what):

@@ -7,16 +7,15 @@ import os
 import re
 import subprocess
 
+from support import header_code
+
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 NEW = ("hsm_update_by_scans_device", "hsm_update_by_scans")
 
 
 def test_update_by_scans_entries_are_declared_bound_and_exported():
     from hector_slam_amd import build, capi
-    src = open(os.path.join(ROOT, "include", "hector_mi355", "capi.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    decl = {m.group(1): m.group(2) for m in re.finditer(r"\b(hsm_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;", src, re.S)}
+    decl = {m.group(1): m.group(2) for m in re.finditer(r"\b(hsm_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;", header_code(), re.S)}
     for name in NEW:
         assert name in decl, f"{name} is not declared in capi.h"
         assert name in capi.SIGNATURES, f"{name} is not bound in capi.py"

@@ -8,31 +8,18 @@ without a GPU.
 """
 import ctypes as C
 import os
-import re
-import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from support import check_symbols, compile_c99, header_text
+
 NEW_SYMBOLS = ("hsm_score_window_device", "hsm_score_window", "hsm_window_poses_device", "hsm_select_topk_device",
                "hsm_select_topk_workspace", "hsm_relocalize_device", "hsm_relocalize_workspace", "hsm_relocalize")
 HSM_ERR_INVALID = -1
 
 
-def _header():
-    return open(os.path.join(ROOT, "include", "hector_mi355", "capi.h")).read()
-
-
 def test_new_symbols_declared_bound_and_exported():
     from hector_slam_amd import build, capi
-    code = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-    build.build_native()
-    lib = capi.load_library()
-    for name in NEW_SYMBOLS:
-        assert re.search(r"\b(int|size_t)\s+" + name + r"\s*\(", code), name
-        assert name in capi.SIGNATURES, name
-        assert hasattr(lib, name), name
-        decl = re.search(r"\b" + name + r"\s*\((.*?)\)\s*;", code, re.S).group(1)
-        assert len(capi.SIGNATURES[name][1]) == decl.count(",") + 1, (name, decl)
-    head = _header()
+    check_symbols(NEW_SYMBOLS, restype=r"(int|size_t)")
+    head = header_text()
     assert "#define HSM_MAX_TOPK 64" in head and "HSM_WINDOW_FORM" in head and "non-maximum suppression" in head
     for meth in ("score_window_device", "score_window", "window_poses_device", "select_topk_device", "select_topk_workspace",
                  "relocalize_device", "relocalize_workspace", "relocalize"):
@@ -42,19 +29,16 @@ def test_new_symbols_declared_bound_and_exported():
 
 
 def test_header_with_the_new_entries_is_plain_c99(tmp_path):
-    src = tmp_path / "use.c"
-    src.write_text('#include "hector_mi355/capi.h"\n'
-                   "int main(void) { hsm_ctx* h = 0; float f[9] = {0.0f}; float st[3] = {0.1f, 0.1f, 0.1f}; int hf[3] = {1, 1, 1};\n"
-                   "  int idx[HSM_MAX_TOPK]; char ws[64];\n"
-                   "  int rc = hsm_score_window_device(h, 0, f, st, hf, f, 1, f, 0, 0);\n"
-                   "  rc += hsm_score_window(h, 0, f, st, hf, f, 1, f, f);\n"
-                   "  rc += hsm_window_poses_device(h, f, st, hf, idx, 1, f, 0);\n"
-                   "  rc += hsm_select_topk_device(h, 1, f, 1, idx, f, ws, hsm_select_topk_workspace(1, 1), 0);\n"
-                   "  rc += hsm_relocalize_device(h, 0, f, st, hf, 1, f, 1, ws, hsm_relocalize_workspace(27, 1), f, f, f, f, f, idx, 0);\n"
-                   "  rc += hsm_relocalize(h, 0, f, st, hf, 1, f, 1, f, f, f, f, f, idx);\n"
-                   "  return rc; }\n")
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-c", str(src), "-I",
-                    os.path.join(ROOT, "include"), "-o", str(tmp_path / "use.o")], check=True)
+    compile_c99(tmp_path,
+                "int main(void) { hsm_ctx* h = 0; float f[9] = {0.0f}; float st[3] = {0.1f, 0.1f, 0.1f}; int hf[3] = {1, 1, 1};\n"
+                "  int idx[HSM_MAX_TOPK]; char ws[64];\n"
+                "  int rc = hsm_score_window_device(h, 0, f, st, hf, f, 1, f, 0, 0);\n"
+                "  rc += hsm_score_window(h, 0, f, st, hf, f, 1, f, f);\n"
+                "  rc += hsm_window_poses_device(h, f, st, hf, idx, 1, f, 0);\n"
+                "  rc += hsm_select_topk_device(h, 1, f, 1, idx, f, ws, hsm_select_topk_workspace(1, 1), 0);\n"
+                "  rc += hsm_relocalize_device(h, 0, f, st, hf, 1, f, 1, ws, hsm_relocalize_workspace(27, 1), f, f, f, f, f, idx, 0);\n"
+                "  rc += hsm_relocalize(h, 0, f, st, hf, 1, f, 1, f, f, f, f, f, idx);\n"
+                "  return rc; }\n")
 
 
 def test_null_context_is_invalid_for_every_new_entry():
