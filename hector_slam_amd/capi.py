@@ -31,6 +31,8 @@ PARITY_FAST, PARITY_EXACT, PARITY_RELAXED, PARITY_AUTO = 0, 1, 2, 3
 GATHER_AUTO, GATHER_PEER, GATHER_RCCL, GATHER_DIRECT = 0, 1, 2, 3
 ORDER_GIVEN, ORDER_MORTON, ORDER_AUTO = 0, 1, 2
 EXCHANGE_HANDLE_BYTES = 64
+MAX_ALIGN_POINTS = 16384  # HSM_MAX_ALIGN_POINTS
+POINTS_TILE = 4096        # kPointsTile of csrc/map_points_kernels.h: cells of a box a workgroup of the extraction takes at a time
 
 _f32p = np.ctypeslib.ndpointer(dtype=np.float32, flags="C_CONTIGUOUS")
 _i32p = np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS")
@@ -122,6 +124,11 @@ SIGNATURES = {
     "hsm_relocalize_workspace": (C.c_size_t, [_i, _i]),
     "hsm_relocalize": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "hsm_match_score_batch": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp]),
+    "hsm_occupied_points_workspace": (C.c_size_t, [_i]),
+    "hsm_occupied_points_device": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "hsm_occupied_points": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp]),
+    "hsm_align_map_workspace": (C.c_size_t, [_i, _i, _i, _i]),
+    "hsm_align_map": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "hsm_likelihood_states": (_i, [_vp, _i, _i, _f32p, _vp, _i, _f32p]),
     "hsm_residual_states": (_i, [_vp, _i, _i, _f32p, _vp, _i, _f32p]),
     "hsm_covariance_for_poses": (_i, [_vp, _i, _i, _f32p, _vp, _i, _f32p, _f32p, _f32p]),
@@ -474,6 +481,21 @@ class MapRepMultiMap:
         if bx.size != 4 * self.getMapLevels():
             raise ValueError("boxes must hold x0, y0, x1, y1 for every level")
         _check(self._lib.hsm_copy_map_boxes(self._h, src._h, bx.ctypes.data), "hsm_copy_map_boxes")
+
+    def align_map_from(self, src, src_level, src_bbox, every, max_points, search_level, guess, step, half, k):
+        """`src`'s map aligned to this one on the device (hsm_align_map): the occupied cells of src_bbox (None: the whole level) of
+        `src_level`, every `every`-th of them and max_points at most, relocalised on this context in the window (step, half) around
+        `guess`.  Synchronous -> (src_in_dst float32 [3], cov float32 [9], likelihood, counts int32 [2], window_index); without a
+        winner src_in_dst is the guess, the likelihood NaN, the index -1 and cov zeros."""
+        g = np.ascontiguousarray(guess, np.float32).reshape(3)
+        st, hf = self._window(step, half)
+        bb = None if src_bbox is None else (C.c_int * 4)(*[int(v) for v in src_bbox])
+        out, cov = np.empty(3, np.float32), np.zeros(9, np.float32)
+        lh, cnt, idx = np.empty(1, np.float32), np.empty(2, np.int32), np.empty(1, np.int32)
+        _check(self._lib.hsm_align_map(self._h, src._h, int(src_level), bb, int(every), int(max_points), int(search_level),
+                                       g.ctypes.data, st, hf, int(k), out.ctypes.data, cov.ctypes.data, lh.ctypes.data,
+                                       cnt.ctypes.data, idx.ctypes.data), "hsm_align_map")
+        return out, cov, lh[0], cnt, int(idx[0])
 
     def map_start(self):
         """the start coordinates the geometry currently derives from (hsm_map_start) -> float32 [2]"""
@@ -894,6 +916,34 @@ class MapRepMultiMap:
     @staticmethod
     def relocalize_workspace(window_count, k) -> int:
         return int(load_library().hsm_relocalize_workspace(int(window_count), int(k)))
+
+    @staticmethod
+    def align_map_workspace(cells, window_count, k, max_points) -> int:
+        return int(load_library().hsm_align_map_workspace(int(cells), int(window_count), int(k), int(max_points)))
+
+    # ---- a level's occupied cells as a point set in level-0 units (capi.h "another context's map aligned to this one") ----
+    @staticmethod
+    def occupied_points_workspace(cells) -> int:
+        return int(load_library().hsm_occupied_points_workspace(int(cells)))
+
+    def occupied_points_device(self, level, bbox, every, max_points, d_out_pts, d_out_count, d_workspace, workspace_bytes, stream=0):
+        """device pointers as ints; bbox = (x0, y0, x1, y1) inclusive or None for the whole level; asynchronous on ``stream``"""
+        bb = None if bbox is None else (C.c_int * 4)(*[int(v) for v in bbox])
+        _check(self._lib.hsm_occupied_points_device(self._h, int(level), bb, int(every), int(max_points), d_out_pts or None,
+                                                    d_out_count or None, d_workspace or None, workspace_bytes, stream or None),
+               "hsm_occupied_points_device")
+
+    def occupied_points(self, level, bbox=None, every=1, max_points=None):
+        """host arrays -> (points float32 [count[0], 2], counts int32 [2] = written, kept before the cap); max_points None: the
+        level's cell count, which never truncates"""
+        if max_points is None:
+            sx, sy, _, _ = self.level_info(level)
+            max_points = sx * sy
+        bb = None if bbox is None else (C.c_int * 4)(*[int(v) for v in bbox])
+        pts, cnt = np.empty((max(int(max_points), 0), 2), np.float32), np.zeros(2, np.int32)
+        _check(self._lib.hsm_occupied_points(self._h, int(level), bb, int(every), int(max_points),
+                                             pts.ctypes.data if pts.size else None, cnt.ctypes.data), "hsm_occupied_points")
+        return pts[:cnt[0]], cnt
 
     def score_window_device(self, level, d_center, step, half, d_pts, n, d_out_likelihood, d_out_residual=0, stream=0):
         """likelihood / residual of the scan at every pose of the window (device pointers as ints; asynchronous on ``stream``)."""

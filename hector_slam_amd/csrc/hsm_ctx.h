@@ -25,7 +25,8 @@
 //                           planes, the geometry re-derived for other start coordinates (map_shift_kernels.h; the plan:
 //                           map_shift_plan.h)
 //   window.hip              a window of poses around a centre scored on the device map, its K best, and the relocalisation chain
-//                           behind them (window_kernels.h; the window's arithmetic: window_grid.h)
+//                           behind them (window_kernels.h; the window's arithmetic: window_grid.h); a level's occupied cells as
+//                           a point set (map_points_kernels.h) and, with both, another context's map aligned to this one
 //   group.hip               the multi-GPU group (hsm_group_*, hsm_shard_bounds): host code only, librccl opened on demand
 //   match_exact_cached.hip  the exact-order texel-cache batch forms (gn_match_exact.h: the headline kernel and its chain-wavefront forms)
 //   match_teams.hip         the team forms (gn_match_kernel, 1..16 wavefronts per scan: gn_match_teams.h) and the fast texel-cache
@@ -503,6 +504,9 @@ int match_batch_device_nolock(hsm_ctx* h, int batch, const float* d_begin_world,
 int match_score_batch_chain_nolock(hsm_ctx* h, int batch, const float* d_begin_world, const float* d_pts_xy, int shared_n,
                                    float* d_out_pose, float* d_out_cov, int score_level, float* d_out_likelihood, int groups,
                                    int group_size, int* d_out_index, float* d_out_score, float* d_out_best_pose, void* stream);
+// map_copy.hip, for window.hip: what two contexts must share for one's map to be merged into, or aligned to, the other's (level
+// count, resolution of every level, layout); both locks held
+bool merge_compatible(const hsm_ctx* a, const hsm_ctx* b);
 // map_update.hip, for the other units: the level maintenance that launches map_update.h's kernels, what an entry does before it
 // reads or rewrites a level's boxes and counters on the host, and the device SLAM loop over a scan log
 int create_update_state(hsm_ctx* h);

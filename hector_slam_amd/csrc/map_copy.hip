@@ -29,6 +29,14 @@
 using namespace hsm;
 using namespace hsm_host;
 
+// (declared in hsm_ctx.h: hsm_align_map of window.hip refuses the pairs a merge refuses)
+bool hsm_host::merge_compatible(const hsm_ctx* a, const hsm_ctx* b) {
+  if (a->levels.size() != b->levels.size() || a->cfg.layout != b->cfg.layout) return false;
+  for (size_t l = 0; l < a->levels.size(); ++l)
+    if (a->levels[l].cell_length != b->levels[l].cell_length) return false;
+  return true;
+}
+
 namespace {
 
 void widen(int acc[4], const CopyBox& b) {
@@ -186,13 +194,6 @@ MergeAffine merge_affine(const hsm_ctx* dst, const hsm_ctx* src, const float T[3
     off[1] = merge_map_offset(L0.cell_length, L0.sy, of[k]->start[1]);
   }
   return hsm::merge_affine(od, os, dst->levels[level].scale_to_map, T);
-}
-
-bool merge_compatible(const hsm_ctx* a, const hsm_ctx* b) {
-  if (a->levels.size() != b->levels.size() || a->cfg.layout != b->cfg.layout) return false;
-  for (size_t l = 0; l < a->levels.size(); ++l)
-    if (a->levels[l].cell_length != b->levels[l].cell_length) return false;
-  return true;
 }
 
 // the refusals both entries share that need no lock

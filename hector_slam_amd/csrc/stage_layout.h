@@ -345,4 +345,48 @@ inline RelocalizeStage relocalize_stage(int k, int n, size_t ws_bytes, const flo
   return s;
 }
 
+// hsm_occupied_points (d_batch): points[max_points] | counts[2] | the device call's workspace.  Only the counts are copied out
+// by the plan: the entry copies the points the counts name once it has them, so that the caller's array is touched no further.
+struct OccupiedPointsStage {
+  StagePlan plan;
+  size_t pts, counts, ws;
+};
+
+inline OccupiedPointsStage occupied_points_stage(int max_points, size_t ws_bytes, int* out_count) {
+  OccupiedPointsStage s;
+  s.pts = s.plan.add((size_t)max_points * 2 * sizeof(float));
+  s.counts = s.plan.add(2 * sizeof(int), nullptr, out_count);
+  s.ws = s.plan.add(ws_bytes);
+  return s;
+}
+
+// hsm_align_map (the destination's d_batch): the guess as the window's centre | points[max_points] | counts[2] | the
+// extraction's workspace | the relocalisation's workspace, whose k window indices are copied out where they lie (`kindex_at`
+// inside it) | candidate poses[k * 3] | candidate covariances[k * 9] | candidate likelihoods[k] | best pose, seeded with the guess
+// | best score | best index.  The counts come down in the middle of the chain, not with the plan.
+struct AlignMapStage {
+  StagePlan plan;
+  size_t center, pts, counts, xws, ws, pose, cov, lh, bpose, bscore, bidx;
+};
+
+inline AlignMapStage align_map_stage(int k, int max_points, size_t xws_bytes, size_t ws_bytes, size_t kindex_at, const float* guess,
+                                     int* out_kindex, float* out_cand_cov, float* out_best_pose, float* out_best_score,
+                                     int* out_best_index) {
+  const size_t kf = (size_t)k * sizeof(float);
+  AlignMapStage s;
+  s.center = s.plan.add(3 * sizeof(float), guess);
+  s.pts = s.plan.add((size_t)max_points * 2 * sizeof(float));
+  s.counts = s.plan.add(2 * sizeof(int));
+  s.xws = s.plan.add(xws_bytes);
+  s.ws = s.plan.add(ws_bytes);
+  s.pose = s.plan.add(3 * kf);
+  s.cov = s.plan.add(9 * kf, nullptr, out_cand_cov);
+  s.lh = s.plan.add(kf);
+  s.bpose = s.plan.add(3 * sizeof(float), guess, out_best_pose);
+  s.bscore = s.plan.add(sizeof(float), nullptr, out_best_score);
+  s.bidx = s.plan.add(sizeof(int), nullptr, out_best_index);
+  s.plan.view(s.ws + kindex_at, (size_t)k * sizeof(int), nullptr, out_kindex);
+  return s;
+}
+
 }  // namespace hsm_host

@@ -4,6 +4,9 @@
 // window score -> top K -> poses -> match -> score on level 0 -> winner (hsm_relocalize_device, hsm_relocalize).  The kernels are
 // in window_kernels.h, the window's arithmetic and the workspace sizes in window_grid.h.  The scoring entries read the map like a
 // batched score and are ordered like one (order_map_reader of the core runtime, hector_mi355.hip).
+// Also here, because the chain ends in the relocalisation: a level's occupied cells as a point set (hsm_occupied_points*, the
+// kernels in map_points_kernels.h) and another context's map aligned to this one (hsm_align_map): extraction from the other
+// context, the counts fetched, the relocalisation of those points on this one.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <math.h>
@@ -12,12 +15,14 @@
 
 #include "hector_mi355/capi.h"
 #include "hsm_ctx.h"
+#include "map_points_kernels.h"
 #include "window_kernels.h"
 
 using namespace hsm;
 using namespace hsm_host;
 
 static_assert(HSM_MAX_TOPK == kMaxTopK, "capi.h and window_grid.h disagree on K");
+static_assert(HSM_MAX_ALIGN_POINTS <= HSM_MAX_UPDATE_BEAMS, "an aligned point set is a scan the matcher takes");
 
 namespace {
 
@@ -143,6 +148,54 @@ int relocalize_queue(hsm_ctx* h, int search_level, const float* d_center, const 
   return HSM_OK;
 }
 
+// ---- occupied cells as points (map_points_kernels.h) ---------------------------------------------------------------------------------
+// the refusals the three entries share; the workspace is the device entry's own
+int occupied_points_refusals(const hsm_ctx* h, int level, int every, int max_points, const void* pts, const void* count,
+                             const char* who) {
+  if (int rc = valid_level(h, level)) return rc;
+  if (every < 1) return fail_at(HSM_ERR_INVALID, who, ": every < 1");
+  if (max_points < 0) return fail_at(HSM_ERR_INVALID, who, ": max_points < 0");
+  if (!count || (max_points > 0 && !pts)) return fail_at(HSM_ERR_INVALID, who, ": null counts or points");
+  return HSM_OK;
+}
+
+// the three launches on `s`, ordered as a reader of `src`; arguments checked, device selected, lock held.  *mark: as
+// order_map_reader's, and already marked pending -- before the first launch, so that a call that fails half way leaves `src`'s
+// next writer behind whatever it did queue.  A caller that has waited for `s` under the lock may clear the mark again
+int occupied_points_launch(hsm_ctx* src, int level, const PointsBox& B, int every, int max_points, float* d_pts, int* d_count,
+                           void* d_ws, hipStream_t s, const char* who, hsm_ctx::ForeignStream** mark) {
+  if (int rc = order_map_reader(src, s, who, mark)) return rc;
+  if (*mark) (*mark)->pending = true;
+  const Level& L = src->levels[level];
+  MapPointsParams P;
+  P.logodds = L.d_logodds;
+  P.sx = L.sx;
+  P.x0 = B.x0, P.y0 = B.y0, P.w = B.w;
+  P.cells = B.w * B.h;
+  P.tiles = points_tiles(P.cells);
+  P.every = every, P.max_points = max_points;
+  P.worldTmap = L.worldTmap;
+  P.scale = src->levels[0].scale_to_map;  // hsm_scale_to_map
+  P.out = reinterpret_cast<float2*>(d_pts);
+  P.out_count = d_count;
+  P.tile_counts = static_cast<int*>(d_ws);
+  const bool whole = B.w == L.sx;
+  const dim3 grid((unsigned)(P.tiles < 2048 ? P.tiles : 2048));
+  if (P.tiles > 0) {
+    if (whole) hipLaunchKernelGGL(map_points_count_kernel<true>, grid, dim3(256), 0, s, P);
+    else hipLaunchKernelGGL(map_points_count_kernel<false>, grid, dim3(256), 0, s, P);
+    HIP_TRY(hipGetLastError());
+  }
+  hipLaunchKernelGGL(map_points_scan_kernel, dim3(1), dim3(kPointsScanThreads), 0, s, P);  // (an empty box: the counts alone)
+  HIP_TRY(hipGetLastError());
+  if (P.tiles > 0 && max_points > 0) {
+    if (whole) hipLaunchKernelGGL(map_points_scatter_kernel<true>, grid, dim3(256), 0, s, P);
+    else hipLaunchKernelGGL(map_points_scatter_kernel<false>, grid, dim3(256), 0, s, P);
+    HIP_TRY(hipGetLastError());
+  }
+  return HSM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -249,6 +302,112 @@ int hsm_relocalize(hsm_ctx* h, int search_level, const float center_world[3], co
     return rc;
   if (int rc = stage_copy_out(st.plan, base, h->stream)) return rc;
   HIP_TRY(hipStreamSynchronize(h->stream));
+  return HSM_OK;
+}
+
+size_t hsm_occupied_points_workspace(int cells) { return points_workspace_bytes(cells); }
+
+int hsm_occupied_points_device(hsm_ctx* src, int level, const int bbox[4], int every, int max_points, float* d_out_pts_xy,
+                               int* d_out_count, void* d_workspace, size_t workspace_bytes, void* stream) {
+  const char* who = "hsm_occupied_points_device";
+  if (!src) return fail(HSM_ERR_INVALID, "null context");
+  if (int rc = occupied_points_refusals(src, level, every, max_points, d_out_pts_xy, d_out_count, who)) return rc;
+  std::lock_guard<std::mutex> lk(src->mu);  // (hsm_shift_map rewrites the geometry)
+  const PointsBox B = points_clamp_box(bbox, src->levels[level].sx, src->levels[level].sy);
+  if (!d_workspace || ((size_t)d_workspace & 7) || workspace_bytes < points_workspace_bytes((long long)B.w * B.h))
+    return fail_at(HSM_ERR_INVALID, who, ": workspace missing, misaligned or too small");
+  if (int rc = select_device(src)) return rc;
+  hsm_ctx::ForeignStream* fs = nullptr;
+  return occupied_points_launch(src, level, B, every, max_points, d_out_pts_xy, d_out_count, d_workspace,
+                                static_cast<hipStream_t>(stream), who, &fs);
+}
+
+int hsm_occupied_points(hsm_ctx* src, int level, const int bbox[4], int every, int max_points, float* out_pts_xy, int count[2]) {
+  const char* who = "hsm_occupied_points";
+  if (!src) return fail(HSM_ERR_INVALID, "null context");
+  if (int rc = occupied_points_refusals(src, level, every, max_points, out_pts_xy, count, who)) return rc;
+  std::lock_guard<std::mutex> lk(src->mu);
+  if (int rc = select_device(src)) return rc;
+  const PointsBox B = points_clamp_box(bbox, src->levels[level].sx, src->levels[level].sy);
+  const OccupiedPointsStage st = occupied_points_stage(max_points, points_workspace_bytes((long long)B.w * B.h), count);
+  if (int rc = src->d_batch.reserve(st.plan.total())) return rc;
+  char* base = src->d_batch;
+  hsm_ctx::ForeignStream* fs = nullptr;
+  if (int rc = occupied_points_launch(src, level, B, every, max_points, staged<float>(base, st.pts), staged<int>(base, st.counts),
+                                      base + st.ws, src->stream, who, &fs))
+    return rc;
+  if (int rc = stage_copy_out(st.plan, base, src->stream)) return rc;
+  HIP_TRY(hipStreamSynchronize(src->stream));
+  if (count[0] > 0) {  // the points the counts name and no float behind them
+    HIP_TRY(hipMemcpyAsync(out_pts_xy, base + st.pts, (size_t)count[0] * 2 * sizeof(float), hipMemcpyDeviceToHost, src->stream));
+    HIP_TRY(hipStreamSynchronize(src->stream));
+  }
+  return HSM_OK;
+}
+
+size_t hsm_align_map_workspace(int cells, int window_count, int k, int max_points) {
+  const size_t ws = relocalize_layout(window_count, k).total;
+  if (cells < 0 || ws == 0 || max_points < 0 || max_points > HSM_MAX_ALIGN_POINTS) return 0;
+  return align_map_stage(k, max_points, points_workspace_bytes(cells), ws, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr)
+      .plan.total();
+}
+
+int hsm_align_map(hsm_ctx* dst, hsm_ctx* src, int src_level, const int src_bbox[4], int every, int max_points, int search_level,
+                  const float guess_src_in_dst[3], const float step[3], const int half[3], int k, float out_src_in_dst[3],
+                  float out_cov[9], float* out_likelihood, int out_counts[2], int* out_window_index) {
+  const char* who = "hsm_align_map";
+  if (!dst || !src) return fail(HSM_ERR_INVALID, "null context");
+  if (dst == src) return fail_at(HSM_ERR_INVALID, who, ": dst and src are the same context");
+  if (max_points > HSM_MAX_ALIGN_POINTS) return fail_at(HSM_ERR_INVALID, who, ": max_points above HSM_MAX_ALIGN_POINTS");
+  if (!out_src_in_dst) return fail_at(HSM_ERR_INVALID, who, ": out_src_in_dst is null");
+  std::unique_lock<std::mutex> lk_a(dst < src ? dst->mu : src->mu);  // (as hsm_merge_map: two calls in opposite directions)
+  std::unique_lock<std::mutex> lk_b(dst < src ? src->mu : dst->mu);
+  if (!merge_compatible(dst, src)) return fail_at(HSM_ERR_INVALID, who, ": the contexts differ in level count, resolution or layout");
+  if (dst->device != src->device) return fail_at(HSM_ERR_INVALID, who, ": the contexts are on different devices");
+  int cnt[2] = {0, 0}, kindex[HSM_MAX_TOPK], best_index = -1;
+  float cand_cov[HSM_MAX_TOPK * 9], best_score = 0.0f;
+  // (the points and the counts are device regions here: any address that is not null passes the shared refusals)
+  if (int rc = occupied_points_refusals(src, src_level, every, max_points, cnt, cnt, who)) return rc;
+  long long W = 0;
+  if (int rc = relocalize_refusals(dst, search_level, guess_src_in_dst, step, half, k, cnt, max_points, cand_cov, cand_cov,
+                                   out_src_in_dst, &best_index, who, &W))
+    return rc;
+  if (int rc = select_device(dst)) return rc;
+  const Level& S = src->levels[src_level];
+  const PointsBox B = points_clamp_box(src_bbox, S.sx, S.sy);
+  const RelocalizeLayout RL = relocalize_layout(W, k);
+  const AlignMapStage st = align_map_stage(k, max_points, points_workspace_bytes((long long)B.w * B.h), RL.total, RL.index,
+                                           guess_src_in_dst, kindex, cand_cov, out_src_in_dst, &best_score, &best_index);
+  if (int rc = dst->d_batch.reserve(st.plan.total())) return rc;
+  char* base = dst->d_batch;
+  if (int rc = stage_copy_in(st.plan, base, dst->stream)) return rc;
+  // (a) `src`'s cells on `dst`'s stream, behind every update queued on `src`, marked for `src`'s next writer
+  hsm_ctx::ForeignStream* fs = nullptr;
+  if (int rc = occupied_points_launch(src, src_level, B, every, max_points, staged<float>(base, st.pts), staged<int>(base, st.counts),
+                                      base + st.xws, dst->stream, who, &fs))
+    return rc;
+  // (b) the chain's one host wait: every entry behind this point takes the number of points from the host
+  HIP_TRY(hipMemcpyAsync(cnt, base + st.counts, sizeof cnt, hipMemcpyDeviceToHost, dst->stream));
+  HIP_TRY(hipStreamSynchronize(dst->stream));
+  if (fs) fs->pending = false;  // the read of `src` is over, under `src`'s lock: its next writer has nothing to wait for
+  // (c) the points are a scan in `src`'s world frame, so the pose the matcher refines is src_in_dst
+  if (int rc = relocalize_queue(dst, search_level, staged<float>(base, st.center), window_grid(step, half), (int)W, k,
+                                staged<float>(base, st.pts), cnt[0], base + st.ws, staged<float>(base, st.pose),
+                                staged<float>(base, st.cov), staged<float>(base, st.lh), staged<float>(base, st.bpose),
+                                staged<float>(base, st.bscore), staged<int>(base, st.bidx), dst->stream))
+    return rc;
+  // (d) the winner
+  if (int rc = stage_copy_out(st.plan, base, dst->stream)) return rc;
+  HIP_TRY(hipStreamSynchronize(dst->stream));
+  if (out_cov && best_index >= 0)
+    for (int j = 0; j < k; ++j)
+      if (kindex[j] == best_index) {  // (the k window indices are distinct: the place the winner's start took)
+        memcpy(out_cov, cand_cov + 9 * j, 9 * sizeof(float));
+        break;
+      }
+  if (out_likelihood) *out_likelihood = best_score;
+  if (out_counts) out_counts[0] = cnt[0], out_counts[1] = cnt[1];
+  if (out_window_index) *out_window_index = best_index;
   return HSM_OK;
 }
 

@@ -959,6 +959,69 @@ size_t hsm_relocalize_workspace(int window_count, int k);
 int hsm_relocalize(hsm_ctx* h, int search_level, const float center_world[3], const float step[3], const int half[3], int k,
                    const float* pts_xy, int n, float* out_cand_pose, float* out_cand_cov, float* out_cand_likelihood,
                    float* out_best_pose, float* out_best_score, int* out_best_index);
+
+/* ---- another context's map aligned to this one, ready to merge: occupied cells as a point set, then the relocalisation --------
+ * No counterpart in the reference: an extension, like hsm_merge_map, whose src_in_dst this produces.  Two entries.
+ *
+ * hsm_occupied_points_device: the occupied cells of a cell box of `level` of `src`, thinned, as points in level-0 units.
+ * Which cells count: a cell (x, y) of `level` inside the inclusive bbox {x0, y0, x1, y1} (NULL: the whole level) is OCCUPIED when
+ *   its log-odds is > 0.0f: isOccupied of GridMapLogOdds.h:76-84, the cells hsm_occupancy_grid reports as 100.  NaN and +-0 are
+ *   not occupied.  The box is clamped to the level; {0, 0, -1, -1} or a box that misses the level gives no cells.
+ * Order and thinning: occupied cells are ranked in row-major order of the box, y outer and x inner, rank 0 first.  The cell of
+ *   rank r is KEPT when r % every == 0, every >= 1 (by rank, not by lattice: an axis-aligned wall does not vanish).
+ * Output: kept cell number j, in rank order, goes to d_out_pts_xy[2j .. 2j+1] if j < max_points; nothing beyond
+ *   2 * min(kept, max_points) floats is touched.  The order depends on the map alone: no atomics on the output index, no
+ *   dependence on the launch shape.
+ * The point of a cell: (wx, wy) = the level's world-from-map transform applied to ((float)x, (float)y), t0 + (l00 * x + l01 * y)
+ *   in fp32, every operation rounded, nothing fused, then each coordinate times hsm_scale_to_map(src) in fp32: the bits of the
+ *   host's hsm_world_coords_pose(src, level, {x, y, 0}) followed by that multiplication.  (The device's and the host's form of
+ *   the transform agree in operation order.)
+ * Counts: d_out_count[0] the points written, d_out_count[1] the cells kept before the max_points cap: truncation shows.
+ * Form: a counting pass per tile of the box, a scan of the tile counts, a scatter pass.  The tile counts live in the
+ *   caller-owned d_workspace of at least hsm_occupied_points_workspace(cells of the clamped box) bytes, 8-byte aligned (the
+ *   level's cell count always suffices).  Nothing is allocated: capturable, as a reader of the map.
+ * Ordering and locking: the contract of hsm_score_window_device -- queued on `stream` behind every update queued on `src`, `src`'s
+ *   next writer behind the read, no host wait; under capture the launches go into the graph and the caller orders replays.
+ * HSM_ERR_INVALID, nothing queued, outputs untouched: NULL context, level out of range, every < 1, max_points < 0, NULL counts,
+ *   NULL points where max_points > 0, a workspace that is NULL, misaligned or too small.
+ *
+ * hsm_occupied_points: the same with HOST pointers, on the context's stream, its device arrays and workspace staged in the
+ * context's batch staging block; synchronous.  out_pts_xy receives 2 * count[0] floats and is touched no further.
+ *
+ * hsm_align_map: guess -> src_in_dst as hsm_merge_map defines it (p_dst = R(theta) p_src + t).  The points of `src`'s box are a
+ * scan given in `src`'s world frame, and the matcher's "sensor pose" of such a scan on `dst` is src_in_dst.  Synchronous, HOST
+ * pointers, one chain on `dst`'s stream:
+ *   (a) hsm_occupied_points of (src, src_level, src_bbox, every, max_points) into `dst`'s staging block, ordered as a reader of
+ *       `src`;
+ *   (b) the 8 bytes of counts come down: THE ONE HOST WAIT of the chain, because every later entry takes n from the host;
+ *   (c) hsm_relocalize on `dst` with the window (step, half) centred on the guess, k starts, n = count[0] points;
+ *   (d) the winner comes down: out_src_in_dst its refined pose, out_cov[9] (or NULL) the matcher covariance of the place it took
+ *       among the k, out_likelihood (or NULL) its level-0 likelihood, out_window_index (or NULL) the window index its start came
+ *       from, out_counts[2] (or NULL) the counts of (a).
+ * Bit for bit what hsm_occupied_points followed by hsm_relocalize with center_world = guess and out_best_pose seeded with the
+ * guess give.  No winner -- no occupied cell, or every window score NaN: HSM_OK, out_src_in_dst = the guess, likelihood NaN,
+ * window index -1, out_cov untouched.  Neither map is written; stamps, counters and boxes of both stay.
+ * HSM_MAX_ALIGN_POINTS is the densest scan the benchmark's configurations send through the matcher; a larger max_points is
+ * refused: thin with `every`.  hsm_align_map_workspace(cells, window_count, k, max_points): the bytes of `dst`'s staging block
+ * the call carves (grown on demand, kept), host arithmetic, a multiple of 8, 0 for refused sizes.
+ * The contexts' locks are taken in address order, as hsm_merge_map does.
+ * HSM_ERR_INVALID, nothing queued: the refusals of hsm_merge_map on the pair (a NULL context, dst == src, contexts that differ in
+ * level count, resolution or layout), those of hsm_relocalize, those of hsm_occupied_points, max_points > HSM_MAX_ALIGN_POINTS,
+ * a NULL out_src_in_dst, contexts on different devices (hsm_merge_map's cross-device route has itself never been run).
+ *
+ * Not built: a device-resident count (it would free the chain of its host wait and make it capturable, and needs n in device
+ * memory throughout the matcher); hsm_merge_map with the transform in device memory; alignment across devices or through
+ * hsm_group_*; points weighted by log-odds; free cells as points; the C++ facade. */
+#define HSM_MAX_ALIGN_POINTS 16384
+/* host arithmetic, callable without a device; a multiple of 8; 0 for cells < 0 */
+size_t hsm_occupied_points_workspace(int cells);
+int hsm_occupied_points_device(hsm_ctx* src, int level, const int bbox[4], int every, int max_points, float* d_out_pts_xy,
+                               int* d_out_count, void* d_workspace, size_t workspace_bytes, void* stream);
+int hsm_occupied_points(hsm_ctx* src, int level, const int bbox[4], int every, int max_points, float* out_pts_xy, int count[2]);
+size_t hsm_align_map_workspace(int cells, int window_count, int k, int max_points);
+int hsm_align_map(hsm_ctx* dst, hsm_ctx* src, int src_level, const int src_bbox[4], int every, int max_points, int search_level,
+                  const float guess_src_in_dst[3], const float step[3], const int half[3], int k, float out_src_in_dst[3],
+                  float out_cov[9], float* out_likelihood, int out_counts[2], int* out_window_index);
 /* replaces: OccGridMapUtil::getCovarianceForPose (HSL/map/OccGridMapUtil.h:106-160) and
  * getCovMatrixWorldCoords (:162-188) for `batch` MAP-frame poses of `level`: seven sigma points per pose
  * (x +- 1.5 cells, y +- 1.5 cells, angle +- 0.05 rad, the pose), likelihood-weighted sample covariance.
