@@ -447,9 +447,8 @@ int hsm_group_match_batch_device(hsm_group* g, const int* counts, const float* c
       if (int rc2 = reserve_pair(g->d_all_pose[(size_t)r], g->d_all_cov[(size_t)r], total)) return rc2;
     if (n > 0) {
       if (int rc2 = reserve_pair(g->d_pose[(size_t)r], g->d_cov[(size_t)r], n)) return rc2;
-      if (int rc2 = match_batch_device_nolock(h, (int)n, d_begin_world[r], d_pts_xy[r],
-                                              d_scan_offsets ? d_scan_offsets[r] : nullptr, shared_n, g->d_pose[(size_t)r],
-                                              d_out_cov_all ? g->d_cov[(size_t)r] : nullptr, h->stream))
+      const ScanBatch shard{(int)n, d_begin_world[r], d_pts_xy[r], d_scan_offsets ? d_scan_offsets[r] : nullptr, shared_n};
+      if (int rc2 = match_batch_device_nolock(h, shard, {g->d_pose[(size_t)r], d_out_cov_all ? g->d_cov[(size_t)r] : nullptr}, h->stream))
         return rc2;
       if (direct) {
         // (below, also for a replica without scans: every replica posts every epoch)

@@ -456,6 +456,61 @@ struct PosedScans {
   const char* who = "hsm_update_by_scans_device";  // the entry the caller used, for the error texts
 };
 
+// A batch of (pose, scan) pairs on the device, filled once by the entry and passed down: CSR scans (`d_offsets`) or one scan of
+// `shared_n` beams at every pose.  The fields of this and the next bundles are in the order of the C ABI: an entry initialises
+// them with braces.
+struct ScanBatch {
+  int batch = 0;
+  const float* d_poses = nullptr;  // the start poses of a match, the poses to score otherwise
+  const float* d_pts = nullptr;
+  const int* d_offsets = nullptr;
+  int shared_n = 0;  // without offsets: the beams of the one scan; with them: the matcher's sizing hint, nothing to the other kernels
+  bool bad_shape() const { return batch < 0 || (!d_offsets && shared_n < 0); }
+  bool points_missing() const { return batch > 0 && !d_pts && !d_offsets && shared_n > 0; }  // a scan that has beams, and no points
+  int kernel_shared_n() const { return d_offsets ? 0 : shared_n; }                            // what a kernel that takes no hint receives
+  ScanBatch at(const float* d_other) const { return {batch, d_other, d_pts, d_offsets, kernel_shared_n()}; }  // ... behind the match
+};
+// what a batched match adds to its ScanBatch
+struct MatchOut {
+  float* d_out_pose = nullptr;        // [batch * 3]
+  float* d_out_cov = nullptr;         // [batch * 9] or null
+  int n_bound = 0;                    // CSR scans: a true bound of every scan's length where the caller has one, else 0
+  const ExchangeFused* xp = nullptr;  // hsm_match_batch_device_gather: the exchange step the launch may carry
+};
+// the outputs of a scoring step; each may be null, not all of them
+struct ScoreOut {
+  float *d_likelihood = nullptr, *d_residual = nullptr;
+  bool none() const { return !d_likelihood && !d_residual; }
+};
+struct CovOut {
+  float *d_cov_world = nullptr, *d_cov_map = nullptr, *d_lh7 = nullptr, *d_likelihood = nullptr;
+  bool none() const { return !d_cov_world && !d_cov_map && !d_lh7 && !d_likelihood; }
+};
+// A scoring step, alone or as the middle of a match chain: the score, or with `covariance` the covariance estimate, of a
+// ScanBatch on `level`.  `who`: the entry the caller used, for the error texts
+struct ScoringStep {
+  int level = 0;
+  ScoreOut score;
+  CovOut cov;
+  bool covariance = false;
+  const char* who = "hsm_match_score_batch_device";
+  float* likelihood() const { return covariance ? cov.d_likelihood : score.d_likelihood; }  // what a ranking behind it ranks by
+  bool no_output() const { return covariance ? cov.none() : score.none(); }
+};
+// The ranking request behind a scoring step: `groups` groups (0: none) of `group_size` consecutive entries, or CSR
+// `group_offsets`.  Device pointers for the device entries, host pointers in match_batch_host of match.hip
+struct Ranking {
+  int groups = 0;
+  const int* group_offsets = nullptr;
+  int group_size = 0;
+  int* out_index = nullptr;
+  float *out_score = nullptr, *out_best_pose = nullptr;  // may be null; the pose in/out (a group without a winner keeps the caller's)
+  bool bad_ranking(int batch, const void* lh) const {    // what every match -> scoring step -> winner entry refuses; `lh`: the scores
+    return groups < 0 ||
+           (groups > 0 && (!lh || !out_index || (!group_offsets && (group_size < 0 || (long long)groups * group_size > batch))));
+  }
+};
+
 // The scan log of a SLAM call, all on the device: what steers the loop and where its results go.  Scan k's share of every array
 // is sliced here and nowhere else.  (Fields in the order the entries initialise them with braces.)
 struct ScanLog {
@@ -496,14 +551,25 @@ int order_map_reader(hsm_ctx* h, hipStream_t s, const char* who, hsm_ctx::Foreig
 int slam_refuse_capture(hsm_ctx* h, hipStream_t s, const char* who);
 int wait_for_caller_inputs(hsm_ctx* h, hipStream_t s);
 int slam_caller_waits(hsm_ctx* h, hipStream_t s);
+
+// The bracket of a launch on `s` that reads the map: begin() orders it behind the map updates queued so far and can fail;
+// queued(), once the launch is on the stream, leaves the mark the next update waits for -- without it that update runs under the
+// reader.  `mark_now`: marked in begin() already, so that a call of several launches that fails half way leaves the next writer
+// behind what it did queue.  `mark`: null where nothing is to be remembered (the context's own stream; a capture)
+struct MapReader {
+  hsm_ctx::ForeignStream* mark = nullptr;
+  int begin(hsm_ctx* h, hipStream_t s, const char* who, bool mark_now = false) {
+    const int rc = order_map_reader(h, s, who, &mark);
+    if (rc == HSM_OK && mark_now) queued();
+    return rc;
+  }
+  void queued() { if (mark) mark->pending = true; }
+};
 // match.hip, for the other units: the batched match behind the raw-scan, group and scan-loop entries ...
-int match_batch_device_nolock(hsm_ctx* h, int batch, const float* d_begin_world, const float* d_pts_xy, const int* d_scan_offsets,
-                              int shared_n, float* d_out_pose, float* d_out_cov, void* stream, int n_bound = 0,
-                              const ExchangeFused* xp = nullptr);
-// ... and the chain behind hsm_match_score_batch_device (match -> score -> winners), for hsm_relocalize_device of window.hip
-int match_score_batch_chain_nolock(hsm_ctx* h, int batch, const float* d_begin_world, const float* d_pts_xy, int shared_n,
-                                   float* d_out_pose, float* d_out_cov, int score_level, float* d_out_likelihood, int groups,
-                                   int group_size, int* d_out_index, float* d_out_score, float* d_out_best_pose, void* stream);
+int match_batch_device_nolock(hsm_ctx* h, const ScanBatch& B, const MatchOut& M, void* stream);
+// ... and the chain match -> `step` at the matched poses -> winners where R.groups > 0, which hsm_relocalize_device of window.hip
+// ends in too.  Every argument is checked before the first launch
+int match_chain_nolock(hsm_ctx* h, const ScanBatch& B, const MatchOut& M, const ScoringStep& step, const Ranking& R, void* stream);
 // map_copy.hip, for window.hip: what two contexts must share for one's map to be merged into, or aligned to, the other's (level
 // count, resolution of every level, layout); both locks held
 bool merge_compatible(const hsm_ctx* a, const hsm_ctx* b);

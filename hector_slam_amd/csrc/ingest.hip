@@ -264,8 +264,8 @@ static int match_batch_ranges_nolock(hsm_ctx* h, int batch, const float* d_begin
     HIP_TRY(hipGetLastError());
   }
   // n is a true bound of every scan's length after the gate
-  return match_batch_device_nolock(h, batch, d_begin_world, reinterpret_cast<const float*>(pts), offsets, n, d_out_pose,
-                                   d_out_cov, stream, n);
+  return match_batch_device_nolock(h, {batch, d_begin_world, reinterpret_cast<const float*>(pts), offsets, n},
+                                   {d_out_pose, d_out_cov, n}, stream);
 }
 
 int hsm_match_batch_ranges_device(hsm_ctx* h, int batch, const float* d_begin_world, const float* d_ranges, int n,
@@ -410,8 +410,8 @@ int hsm_match_batch_ranges_tf(hsm_ctx* h, int batch, const float* begin_world, c
                                              h->stream))
     return rc;
   // n is a true bound of every scan's length after the gates
-  if (int rc = match_batch_device_nolock(h, batch, staged<float>(base, st.begin), d_pts, d_offs, n, staged<float>(base, st.pose),
-                                         staged<float>(base, st.cov, out_cov), h->stream, n))
+  if (int rc = match_batch_device_nolock(h, {batch, staged<float>(base, st.begin), d_pts, d_offs, n},
+                                         {staged<float>(base, st.pose), staged<float>(base, st.cov, out_cov), n}, h->stream))
     return rc;
   if (int rc = stage_copy_out(st.plan, base, h->stream)) return rc;
   HIP_TRY(hipStreamSynchronize(h->stream));

@@ -651,9 +651,9 @@ int hsm_host::slam_scans_queue(hsm_ctx* h, const ScanLog& log, const PosedScans&
   one.shared_n = 0;
   one.gate = &gate;
   for (int k = 0; k < log.count; ++k) {
-    if (int rc = match_batch_device_nolock(h, 1, h->upd.d_gate->hint, scans.d_pts, scans.d_offsets + k, scans.max_beams, log.pose(k),
-                                           log.cov(k), h->stream))
-      return rc;
+    // scan k as a batch of one for the matcher: its start from the gate's device block, its slice of the CSR, the log's beam hint
+    const ScanBatch scan{1, h->upd.d_gate->hint, scans.d_pts, scans.d_offsets + k, scans.max_beams};
+    if (int rc = match_batch_device_nolock(h, scan, {log.pose(k), log.cov(k)}, h->stream)) return rc;
     gate = log.gate(k);
     one.d_poses = gate.pose_io;
     one.d_offsets = scans.d_offsets + k;

@@ -3,7 +3,9 @@
 // multi-workgroup forms of gn_match_dense.h and gn_match_spec.h, and score_kernels.h; the batch / team forms are dispatched to
 // match_exact_cached.hip and match_teams.hip through the launch entries hsm_ctx.h declares, whose kernels this unit does not see.
 // What it needs of the core runtime (hector_mi355.hip: the context, the level views, the stream ordering, the error text) is
-// declared in hsm_ctx.h and hsm_host.h.
+// declared in hsm_ctx.h and hsm_host.h, and so are the bundles a batched call travels as, filled once by its extern "C" entry:
+// ScanBatch, MatchOut, ScoringStep, Ranking.  match_batch_device_nolock is the match, match_chain_nolock the one chain match ->
+// scoring step -> winners behind the match-score, match-covariance, host and relocalisation entries.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <limits.h>
@@ -67,12 +69,6 @@ void record_launch(hsm_ctx* h, const MatchPlan& plan) {
 void record_sampler_launch(hsm_ctx* h, const char* kernel) {
   h->last.last_kernel = kernel;
   h->last.last_parity = wants_exact(h) ? HSM_PARITY_EXACT : (h->cfg.parity.relaxed ? HSM_PARITY_RELAXED : HSM_PARITY_FAST);
-}
-
-// the ranking arguments that every match -> score -> winner entry refuses, device or host arrays alike: `lh` the scores it ranks by
-bool bad_ranking(int batch, int groups, const void* lh, const void* out_index, const void* group_offsets, int group_size) {
-  return groups < 0 ||
-         (groups > 0 && (!lh || !out_index || (!group_offsets && (group_size < 0 || (long long)groups * group_size > batch))));
 }
 
 // the one-workgroup-per-scan forms of this unit: Family::kExactDense, kSpec (gn_match_dense.h, gn_match_spec.h: `batch` workgroups) and
@@ -179,28 +175,96 @@ void fill_schedule(const hsm_ctx* h, MatchParams& P, bool batched = false) {
   }
 }
 
+// The refusals of a scoring step on its own (a chain has its combined check): the level first.  The covariance entries name
+// themselves in every text, the level's and the null context's too; the score's answer those as valid_level does
+int scoring_level_check(const hsm_ctx* h, const ScoringStep& S) {
+  if (!S.covariance) return valid_level(h, S.level);
+  if (!h) return fail_at(HSM_ERR_INVALID, S.who, ": null context");
+  if (S.level < 0 || S.level >= (int)h->levels.size()) return fail_at(HSM_ERR_INVALID, S.who, ": level out of range");
+  return HSM_OK;
+}
+int scoring_step_check(const hsm_ctx* h, const ScoringStep& S, const ScanBatch& B) {
+  if (int rc = scoring_level_check(h, S)) return rc;
+  if (B.bad_shape() || S.no_output() || (B.batch > 0 && !B.d_poses) || B.points_missing())
+    return fail_at(HSM_ERR_INVALID, S.who, ": bad argument");
+  return HSM_OK;
+}
+
+// The weighting step behind a batched match, or the covariance estimate: B (world pose, scan) pairs on S.level in one launch of
+// score_batch_kernel or covariance_batch_kernel (score_kernels.h), a wavefront per pair.  A reader of the map like the batched
+// match and bracketed like it; no workspace, no state.  Arguments checked
+int scoring_step_launch(hsm_ctx* h, const ScoringStep& S, const ScanBatch& B, void* stream) {
+  if (B.batch == 0) return HSM_OK;
+  if (int rc = select_device(h)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  MapReader reader;
+  if (int rc = reader.begin(h, s, S.covariance ? S.who : "hsm_score_batch_device")) return rc;
+  const Level& Lv = h->levels[S.level];
+  const LevelView v = level_view(Lv, level_factor(S.level), 1);
+  const float2* pts = reinterpret_cast<const float2*>(B.d_pts);
+  const int grid = (B.batch + 3) / 4, n = B.kernel_shared_n();
+  if (!S.covariance)
+    with_sampler_form(h, [&](auto lay, auto ex) {
+      hipLaunchKernelGGL((score_batch_kernel<lay(), ex()>), dim3(grid), dim3(256), 0, s, v, B.d_poses, B.batch, pts, B.d_offsets, n,
+                         S.score.d_likelihood, S.score.d_residual);
+    });
+  else
+    with_sampler_form(h, [&](auto lay, auto ex) {
+      hipLaunchKernelGGL((covariance_batch_kernel<lay(), ex()>), dim3(grid), dim3(256), 0, s, v, B.d_poses, B.batch, pts, B.d_offsets, n,
+                         Lv.cell_length, S.cov.d_cov_world, S.cov.d_cov_map, S.cov.d_lh7, S.cov.d_likelihood);
+    });
+  HIP_TRY(hipGetLastError());
+  reader.queued();
+  record_sampler_launch(h, S.covariance ? "covariance_batch_kernel" : "score_batch_kernel");
+  return HSM_OK;
+}
+
+// Groups of at most this many entries (or, with CSR groups whose sizes only the device knows, launches of at least this many
+// groups) take one wavefront per group, the others one workgroup per group.  Either shape gives the same result.
+constexpr int kSelectWaveGroupMax = 1024;
+
+// the winner of every group of R by `d_scores`, its pose out of `d_poses_world`; reads no map: stream order is all it needs
+int select_best_device_nolock(hsm_ctx* h, const Ranking& R, const float* d_scores, const float* d_poses_world, void* stream) {
+  if (R.groups < 0 || (!R.group_offsets && R.group_size < 0) || !R.out_index || (R.out_best_pose && !d_poses_world) ||
+      (!d_scores && R.groups > 0 && (R.group_offsets || R.group_size > 0)) ||
+      (!R.group_offsets && R.groups > 0 && (long long)R.groups * R.group_size > INT_MAX))
+    return fail(HSM_ERR_INVALID, "hsm_select_best_device: bad argument");
+  if (R.groups == 0) return HSM_OK;
+  if (int rc = select_device(h)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const bool wave_per_group = R.group_offsets ? R.groups >= kSelectWaveGroupMax : R.group_size <= kSelectWaveGroupMax;
+  if (wave_per_group)
+    hipLaunchKernelGGL((select_best_kernel<true>), dim3((R.groups + 3) / 4), dim3(256), 0, s, R.groups, R.group_offsets, R.group_size,
+                       d_scores, d_poses_world, R.out_index, R.out_score, R.out_best_pose);
+  else
+    hipLaunchKernelGGL((select_best_kernel<false>), dim3(R.groups), dim3(256), 0, s, R.groups, R.group_offsets, R.group_size,
+                       d_scores, d_poses_world, R.out_index, R.out_score, R.out_best_pose);
+  HIP_TRY(hipGetLastError());
+  return HSM_OK;
+}
+
 }  // namespace
 
-int hsm_host::match_batch_device_nolock(hsm_ctx* h, int batch, const float* d_begin_world, const float* d_pts_xy,
-                                        const int* d_scan_offsets, int shared_n, float* d_out_pose,
-                                        float* d_out_cov, void* stream, int n_bound, const ExchangeFused* xp) {
-  if (batch < 0 || !d_begin_world || !d_out_pose || (!d_scan_offsets && shared_n < 0))
-    return fail(HSM_ERR_INVALID, "hsm_match_batch_device: bad argument");
-  if (batch == 0) return HSM_OK;
+// The batched match.  B.shared_n doubles as the sizing HINT for CSR input, whose per-scan lengths only the device knows (callers
+// pass the typical beams per scan, 0 = unknown).  It only picks the kernel form: every form handles scans longer than the hint
+// (the beams beyond the register/LDS-resident ones stream from memory).
+int hsm_host::match_batch_device_nolock(hsm_ctx* h, const ScanBatch& B, const MatchOut& M, void* stream) {
+  if (B.bad_shape() || !B.d_poses || !M.d_out_pose) return fail(HSM_ERR_INVALID, "hsm_match_batch_device: bad argument");
+  if (B.batch == 0) return HSM_OK;
   if (int rc = select_device(h)) return rc;
   MatchParams P;
   memset(&P, 0, sizeof P);
   fill_schedule(h, P, true);
-  P.batch = batch;
-  P.begin_world = d_begin_world;
-  P.pts = reinterpret_cast<const float2*>(d_pts_xy);
-  P.offsets = d_scan_offsets;
-  P.shared_n = shared_n;
-  P.out_pose = d_out_pose;
-  P.out_cov = d_out_cov;
+  P.batch = B.batch;
+  P.begin_world = B.d_poses;
+  P.pts = reinterpret_cast<const float2*>(B.d_pts);
+  P.offsets = B.d_offsets;
+  P.shared_n = B.shared_n;
+  P.out_pose = M.d_out_pose;
+  P.out_cov = M.d_out_cov;
   // a true bound of the scan lengths, where the host has one: a shared scan's length, or what the caller computed from host offsets
-  P.n_bound = d_scan_offsets ? n_bound : shared_n;
-  if (xp) P.xp = *xp;
+  P.n_bound = B.d_offsets ? M.n_bound : B.shared_n;
+  if (M.xp) P.xp = *M.xp;
   h->batch.fused_exchange_done = false;
   // workgroup -> XCD mapping (beam_sample.h, xcd_block): chunks dealt to the XCDs in turn balance the data-dependent
   // per-scan time; maps whose touched region outgrows the L2s keep one contiguous eighth of the batch per XCD
@@ -208,323 +272,74 @@ int hsm_host::match_batch_device_nolock(hsm_ctx* h, int batch, const float* d_be
   P.xcd_chunk = outgrows ? 0 : h->cfg.batch.xcd_chunk;
   P.wg_sync = h->cfg.batch.wg_sync >= 0 ? h->cfg.batch.wg_sync : (outgrows ? 1 : 0);
   P.clock_probe = h->batch.clock_probe;
-  // per-scan length is only known on the device for CSR input; shared_n doubles as the sizing HINT there
-  // (callers pass the typical beams per scan, 0 = unknown).  It only picks the kernel form: every form handles
-  // scans longer than the hint (the beams beyond the register/LDS-resident ones stream from memory).
-  const int hint = shared_n > 0 ? shared_n : 1081;
+  const int hint = B.shared_n > 0 ? B.shared_n : 1081;
   hipStream_t s = (hipStream_t)stream;
-  hsm_ctx::ForeignStream* fs = nullptr;
-  if (int rc = order_map_reader(h, s, "hsm_match_batch_device", &fs)) return rc;
+  MapReader reader;
+  if (int rc = reader.begin(h, s, "hsm_match_batch_device")) return rc;
   if (int rc = launch_match(h, P, hint, s)) return rc;
-  if (fs) fs->pending = true;
+  reader.queued();
   return HSM_OK;
+}
+
+// match -> `step` (the score or the covariance estimate) at the matched poses -> (R.groups > 0) the winner of every group by the
+// pose's own likelihood, queued on `stream` under one lock.  Every argument is checked before the first launch, so a bad one
+// queues nothing.
+int hsm_host::match_chain_nolock(hsm_ctx* h, const ScanBatch& B, const MatchOut& M, const ScoringStep& step, const Ranking& R,
+                                 void* stream) {
+  if (int rc = scoring_level_check(h, step)) return rc;
+  if (B.bad_shape() || !B.d_poses || !M.d_out_pose || step.no_output() || B.points_missing() ||
+      R.bad_ranking(B.batch, step.likelihood()))
+    return fail_at(HSM_ERR_INVALID, step.who, ": bad argument");
+  if (int rc = match_batch_device_nolock(h, B, M, stream)) return rc;
+  // the sizing hint of a CSR match means nothing to the scoring step: its kernel reads every scan's length from the offsets
+  if (int rc = scoring_step_launch(h, step, B.at(M.d_out_pose), stream)) return rc;
+  if (R.groups == 0) return HSM_OK;
+  return select_best_device_nolock(h, R, step.likelihood(), M.d_out_pose, stream);
 }
 
 extern "C" {
-
-int hsm_match_batch_device(hsm_ctx* h, int batch, const float* d_begin_world, const float* d_pts_xy,
-                           const int* d_scan_offsets, int shared_n, float* d_out_pose, float* d_out_cov,
-                           void* stream) {
-  if (!h) return fail(HSM_ERR_INVALID, "null context");
-  std::lock_guard<std::mutex> lk(h->mu);
-  return match_batch_device_nolock(h, batch, d_begin_world, d_pts_xy, d_scan_offsets, shared_n, d_out_pose,
-                                   d_out_cov, stream);
-}
-
-int hsm_match_batch_device_gather(hsm_ctx* h, int batch, const float* d_begin_world, const float* d_pts_xy,
-                                  const int* d_scan_offsets, int shared_n, float* d_out_pose, float* d_out_cov,
-                                  hsm_exchange* x, int first_row, int lag, float* d_out_all, void* stream) {
-  if (!h || !x) return fail(HSM_ERR_INVALID, "null context / exchange");
-  if (batch <= 0) return fail(HSM_ERR_INVALID, "hsm_match_batch_device_gather: every rank posts a non-empty shard");
-  std::lock_guard<std::mutex> lk(h->mu);
-  // The exchange step of this match: carried by the matcher launch itself where the form can (the exact-order batch forms: every
-  // wavefront posts its pose from the kernel's epilogue, extra workgroups at the end of the grid unpack the epoch `lag` matches
-  // back -- no launch of its own, nothing between two matcher launches), else one launch of the stand-alone exchange kernel behind it.
-  ExchangeFused f;
-  if (int rc = hsm_host::exchange_fused_begin(x, first_row, batch, lag, d_out_all, &f)) return rc;
-  if (int rc = match_batch_device_nolock(h, batch, d_begin_world, d_pts_xy, d_scan_offsets, shared_n, d_out_pose, d_out_cov, stream, 0, &f))
-    return rc;
-  if (h->batch.fused_exchange_done) {
-    hsm_host::exchange_fused_commit(x, f);
-    return HSM_OK;
-  }
-  return hsm_exchange_post_wait(x, d_out_pose, first_row, batch, lag, d_out_all, stream);
-}
-
-// The weighting step behind a batched match: B (world pose, scan) pairs scored on `level` in one launch of score_batch_kernel
-// (score_kernels.h).  A reader of the map like the batched match, so ordered like it (order_map_reader); no workspace, no state.
-static int score_batch_device_nolock(hsm_ctx* h, int level, int batch, const float* d_poses_world, const float* d_pts_xy,
-                                     const int* d_scan_offsets, int shared_n, float* d_out_likelihood,
-                                     float* d_out_residual, void* stream) {
-  if (int rc = valid_level(h, level)) return rc;
-  if (batch < 0 || (!d_out_likelihood && !d_out_residual) || (!d_scan_offsets && shared_n < 0) ||
-      (batch > 0 && (!d_poses_world || (!d_pts_xy && !d_scan_offsets && shared_n > 0))))
-    return fail(HSM_ERR_INVALID, "hsm_score_batch_device: bad argument");
-  if (batch == 0) return HSM_OK;
-  if (int rc = select_device(h)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  hsm_ctx::ForeignStream* fs = nullptr;
-  if (int rc = order_map_reader(h, s, "hsm_score_batch_device", &fs)) return rc;
-  const float factor = (float)(1.0 / pow(2.0, (double)level));
-  const LevelView v = level_view(h->levels[level], factor, 1);
-  const int grid = (batch + 3) / 4;
-  with_sampler_form(h, [&](auto lay, auto ex) {
-    hipLaunchKernelGGL((score_batch_kernel<lay(), ex()>), dim3(grid), dim3(256), 0, s, v, d_poses_world, batch,
-                       reinterpret_cast<const float2*>(d_pts_xy), d_scan_offsets, d_scan_offsets ? 0 : shared_n,
-                       d_out_likelihood, d_out_residual);
-  });
-  HIP_TRY(hipGetLastError());
-  if (fs) fs->pending = true;
-  record_sampler_launch(h, "score_batch_kernel");
-  return HSM_OK;
-}
-
-int hsm_score_batch_device(hsm_ctx* h, int level, int batch, const float* d_poses_world, const float* d_pts_xy,
-                           const int* d_scan_offsets, int shared_n, float* d_out_likelihood, float* d_out_residual,
-                           void* stream) {
-  if (!h) return fail(HSM_ERR_INVALID, "null context");
-  std::lock_guard<std::mutex> lk(h->mu);
-  return score_batch_device_nolock(h, level, batch, d_poses_world, d_pts_xy, d_scan_offsets, shared_n, d_out_likelihood,
-                                   d_out_residual, stream);
-}
-
-// The covariance estimate behind a batched match: B (world pose, scan) pairs on `level` in one launch of covariance_batch_kernel
-// (score_kernels.h).  Built like the score: a reader of the map (order_map_reader), no workspace, no state.  `who`: the entry the
-// caller used, for the error text.
-static int covariance_batch_check(const hsm_ctx* h, int level, int batch, const float* d_poses_world, const float* d_pts_xy,
-                                  const int* d_scan_offsets, int shared_n, const float* d_out_cov_world, const float* d_out_cov_map,
-                                  const float* d_out_lh7, const float* d_out_likelihood, const char* who) {
-  if (!h) return fail_at(HSM_ERR_INVALID, who, ": null context");
-  if (level < 0 || level >= (int)h->levels.size()) return fail_at(HSM_ERR_INVALID, who, ": level out of range");
-  if (batch < 0 || (!d_out_cov_world && !d_out_cov_map && !d_out_lh7 && !d_out_likelihood) || (!d_scan_offsets && shared_n < 0) ||
-      (batch > 0 && (!d_poses_world || (!d_pts_xy && !d_scan_offsets && shared_n > 0))))
-    return fail_at(HSM_ERR_INVALID, who, ": bad argument");
-  return HSM_OK;
-}
-
-static int covariance_batch_device_nolock(hsm_ctx* h, int level, int batch, const float* d_poses_world, const float* d_pts_xy,
-                                          const int* d_scan_offsets, int shared_n, float* d_out_cov_world, float* d_out_cov_map,
-                                          float* d_out_lh7, float* d_out_likelihood, void* stream,
-                                          const char* who = "hsm_covariance_batch_device") {
-  if (int rc = covariance_batch_check(h, level, batch, d_poses_world, d_pts_xy, d_scan_offsets, shared_n, d_out_cov_world,
-                                      d_out_cov_map, d_out_lh7, d_out_likelihood, who))
-    return rc;
-  if (batch == 0) return HSM_OK;
-  if (int rc = select_device(h)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  hsm_ctx::ForeignStream* fs = nullptr;
-  if (int rc = order_map_reader(h, s, who, &fs)) return rc;
-  const float factor = (float)(1.0 / pow(2.0, (double)level));
-  const Level& Lv = h->levels[level];
-  const LevelView v = level_view(Lv, factor, 1);
-  const int grid = (batch + 3) / 4;
-  with_sampler_form(h, [&](auto lay, auto ex) {
-    hipLaunchKernelGGL((covariance_batch_kernel<lay(), ex()>), dim3(grid), dim3(256), 0, s, v, d_poses_world, batch,
-                       reinterpret_cast<const float2*>(d_pts_xy), d_scan_offsets, d_scan_offsets ? 0 : shared_n, Lv.cell_length,
-                       d_out_cov_world, d_out_cov_map, d_out_lh7, d_out_likelihood);
-  });
-  HIP_TRY(hipGetLastError());
-  if (fs) fs->pending = true;
-  record_sampler_launch(h, "covariance_batch_kernel");
-  return HSM_OK;
-}
-
-int hsm_covariance_batch_device(hsm_ctx* h, int level, int batch, const float* d_poses_world, const float* d_pts_xy,
-                                const int* d_scan_offsets, int shared_n, float* d_out_cov_world, float* d_out_cov_map,
-                                float* d_out_lh7, float* d_out_likelihood, void* stream) {
-  if (!h) return fail(HSM_ERR_INVALID, "hsm_covariance_batch_device: null context");
-  std::lock_guard<std::mutex> lk(h->mu);
-  return covariance_batch_device_nolock(h, level, batch, d_poses_world, d_pts_xy, d_scan_offsets, shared_n, d_out_cov_world,
-                                        d_out_cov_map, d_out_lh7, d_out_likelihood, stream);
-}
-
-// Groups of at most this many entries (or, with CSR groups whose sizes only the device knows, launches of at least this many
-// groups) take one wavefront per group, the others one workgroup per group.  Either shape gives the same result.
-constexpr int kSelectWaveGroupMax = 1024;
-
-// reads no map: stream order is all it needs
-static int select_best_device_nolock(hsm_ctx* h, int groups, const int* d_group_offsets, int group_size, const float* d_scores,
-                                     const float* d_poses_world, int* d_out_index, float* d_out_score,
-                                     float* d_out_pose_world, void* stream) {
-  if (groups < 0 || (!d_group_offsets && group_size < 0) || !d_out_index || (d_out_pose_world && !d_poses_world) ||
-      (!d_scores && groups > 0 && (d_group_offsets || group_size > 0)) ||
-      (!d_group_offsets && groups > 0 && (long long)groups * group_size > INT_MAX))
-    return fail(HSM_ERR_INVALID, "hsm_select_best_device: bad argument");
-  if (groups == 0) return HSM_OK;
-  if (int rc = select_device(h)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  const bool wave_per_group = d_group_offsets ? groups >= kSelectWaveGroupMax : group_size <= kSelectWaveGroupMax;
-  if (wave_per_group)
-    hipLaunchKernelGGL((select_best_kernel<true>), dim3((groups + 3) / 4), dim3(256), 0, s, groups, d_group_offsets, group_size,
-                       d_scores, d_poses_world, d_out_index, d_out_score, d_out_pose_world);
-  else
-    hipLaunchKernelGGL((select_best_kernel<false>), dim3(groups), dim3(256), 0, s, groups, d_group_offsets, group_size,
-                       d_scores, d_poses_world, d_out_index, d_out_score, d_out_pose_world);
-  HIP_TRY(hipGetLastError());
-  return HSM_OK;
-}
-
-int hsm_select_best_device(hsm_ctx* h, int groups, const int* d_group_offsets, int group_size, const float* d_scores,
-                           const float* d_poses_world, int* d_out_index, float* d_out_score, float* d_out_pose_world,
-                           void* stream) {
-  if (!h) return fail(HSM_ERR_INVALID, "null context");
-  std::lock_guard<std::mutex> lk(h->mu);
-  return select_best_device_nolock(h, groups, d_group_offsets, group_size, d_scores, d_poses_world, d_out_index, d_out_score,
-                                   d_out_pose_world, stream);
-}
-
-// match -> score at the matched poses -> (groups > 0) the winner of every group, queued on `stream` under one lock.  Every
-// argument is checked before the first launch, so a bad one queues nothing.
-static int match_score_batch_device_nolock(hsm_ctx* h, int batch, const float* d_begin_world, const float* d_pts_xy,
-                                           const int* d_scan_offsets, int shared_n, float* d_out_pose, float* d_out_cov,
-                                           int score_level, float* d_out_likelihood, float* d_out_residual, int groups,
-                                           const int* d_group_offsets, int group_size, int* d_out_index, float* d_out_score,
-                                           float* d_out_best_pose, void* stream, int n_bound = 0) {
-  if (int rc = valid_level(h, score_level)) return rc;
-  if (batch < 0 || !d_begin_world || !d_out_pose || (!d_scan_offsets && shared_n < 0) || (!d_out_likelihood && !d_out_residual) ||
-      (batch > 0 && !d_pts_xy && !d_scan_offsets && shared_n > 0) ||
-      bad_ranking(batch, groups, d_out_likelihood, d_out_index, d_group_offsets, group_size))
-    return fail(HSM_ERR_INVALID, "hsm_match_score_batch_device: bad argument");
-  if (int rc = match_batch_device_nolock(h, batch, d_begin_world, d_pts_xy, d_scan_offsets, shared_n, d_out_pose, d_out_cov, stream, n_bound))
-    return rc;
-  // the sizing hint of a CSR match means nothing to the score: its kernel reads every scan's length from the offsets
-  if (int rc = score_batch_device_nolock(h, score_level, batch, d_out_pose, d_pts_xy, d_scan_offsets, d_scan_offsets ? 0 : shared_n,
-                                         d_out_likelihood, d_out_residual, stream))
-    return rc;
-  if (groups == 0) return HSM_OK;
-  return select_best_device_nolock(h, groups, d_group_offsets, group_size, d_out_likelihood, d_out_pose, d_out_index, d_out_score,
-                                   d_out_best_pose, stream);
-}
-
-}  // extern "C"
-
-int hsm_host::match_score_batch_chain_nolock(hsm_ctx* h, int batch, const float* d_begin_world, const float* d_pts_xy, int shared_n,
-                                             float* d_out_pose, float* d_out_cov, int score_level, float* d_out_likelihood,
-                                             int groups, int group_size, int* d_out_index, float* d_out_score,
-                                             float* d_out_best_pose, void* stream) {
-  return match_score_batch_device_nolock(h, batch, d_begin_world, d_pts_xy, nullptr, shared_n, d_out_pose, d_out_cov, score_level,
-                                         d_out_likelihood, nullptr, groups, nullptr, group_size, d_out_index, d_out_score,
-                                         d_out_best_pose, stream);
-}
-
-extern "C" {
-
-int hsm_match_score_batch_device(hsm_ctx* h, int batch, const float* d_begin_world, const float* d_pts_xy,
-                                 const int* d_scan_offsets, int shared_n, float* d_out_pose, float* d_out_cov, int score_level,
-                                 float* d_out_likelihood, float* d_out_residual, int groups, const int* d_group_offsets,
-                                 int group_size, int* d_out_index, float* d_out_score, float* d_out_best_pose, void* stream) {
-  if (!h) return fail(HSM_ERR_INVALID, "null context");
-  std::lock_guard<std::mutex> lk(h->mu);
-  return match_score_batch_device_nolock(h, batch, d_begin_world, d_pts_xy, d_scan_offsets, shared_n, d_out_pose, d_out_cov,
-                                         score_level, d_out_likelihood, d_out_residual, groups, d_group_offsets, group_size,
-                                         d_out_index, d_out_score, d_out_best_pose, stream);
-}
-
-// match -> covariance estimate at the matched poses -> (groups > 0) the winner of every group by the pose's own likelihood, queued
-// on `stream` under one lock.  Every argument is checked before the first launch (the group rules are match_score's).
-int hsm_match_cov_batch_device(hsm_ctx* h, int batch, const float* d_begin_world, const float* d_pts_xy, const int* d_scan_offsets,
-                               int shared_n, float* d_out_pose, float* d_out_cov, int cov_level, float* d_out_cov_world,
-                               float* d_out_cov_map, float* d_out_lh7, float* d_out_likelihood, int groups,
-                               const int* d_group_offsets, int group_size, int* d_out_index, float* d_out_score,
-                               float* d_out_best_pose, void* stream) {
-  static const char* const who = "hsm_match_cov_batch_device";
-  if (!h) return fail_at(HSM_ERR_INVALID, who, ": null context");
-  std::lock_guard<std::mutex> lk(h->mu);
-  if (cov_level < 0 || cov_level >= (int)h->levels.size()) return fail_at(HSM_ERR_INVALID, who, ": level out of range");
-  if (batch < 0 || !d_begin_world || !d_out_pose || (!d_scan_offsets && shared_n < 0) ||
-      (!d_out_cov_world && !d_out_cov_map && !d_out_lh7 && !d_out_likelihood) ||
-      (batch > 0 && !d_pts_xy && !d_scan_offsets && shared_n > 0) ||
-      bad_ranking(batch, groups, d_out_likelihood, d_out_index, d_group_offsets, group_size))
-    return fail_at(HSM_ERR_INVALID, who, ": bad argument");
-  if (int rc = match_batch_device_nolock(h, batch, d_begin_world, d_pts_xy, d_scan_offsets, shared_n, d_out_pose, d_out_cov, stream))
-    return rc;
-  // the sizing hint of a CSR match means nothing to the covariance kernel: it reads every scan's length from the offsets
-  if (int rc = covariance_batch_device_nolock(h, cov_level, batch, d_out_pose, d_pts_xy, d_scan_offsets, d_scan_offsets ? 0 : shared_n,
-                                              d_out_cov_world, d_out_cov_map, d_out_lh7, d_out_likelihood, stream, who))
-    return rc;
-  if (groups == 0) return HSM_OK;
-  return select_best_device_nolock(h, groups, d_group_offsets, group_size, d_out_likelihood, d_out_pose, d_out_index, d_out_score,
-                                   d_out_best_pose, stream);
-}
-
-// host arrays in, covariance_batch_kernel on the context's stream, results out; synchronous
-int hsm_covariance_batch(hsm_ctx* h, int level, int batch, const float* poses_world, const float* pts_xy, const int* scan_offsets,
-                         int shared_n, float* out_cov_world, float* out_cov_map, float* out_lh7, float* out_likelihood) {
-  static const char* const who = "hsm_covariance_batch";
-  if (int rc = covariance_batch_check(h, level, batch, poses_world, pts_xy, scan_offsets, shared_n, out_cov_world, out_cov_map,
-                                      out_lh7, out_likelihood, who))
-    return rc;
-  if (batch == 0) return HSM_OK;
-  if (scan_offsets) {
-    if (scan_offsets[0] != 0) return fail_at(HSM_ERR_INVALID, who, ": bad argument");
-    for (int i = 0; i < batch; ++i)
-      if (scan_offsets[i + 1] < scan_offsets[i]) return fail_at(HSM_ERR_INVALID, who, ": bad argument");
-  }
-  const size_t total = scan_offsets ? (size_t)scan_offsets[batch] : (size_t)shared_n;
-  if (total > 0 && !pts_xy) return fail_at(HSM_ERR_INVALID, who, ": bad argument");
-  std::lock_guard<std::mutex> lk(h->mu);
-  if (int rc = select_device(h)) return rc;
-  const CovarianceBatchStage st = covariance_batch_stage(batch, total, poses_world, pts_xy, scan_offsets, out_cov_world, out_cov_map,
-                                                         out_lh7, out_likelihood);
-  if (int rc = h->d_batch.reserve(st.plan.total())) return rc;
-  char* base = h->d_batch;
-  if (int rc = stage_copy_in(st.plan, base, h->stream)) return rc;
-  if (int rc = covariance_batch_device_nolock(h, level, batch, staged<float>(base, st.poses), staged<float>(base, st.pts),
-                                              staged<int>(base, st.offs, scan_offsets), scan_offsets ? 0 : shared_n,
-                                              staged<float>(base, st.cov_world, out_cov_world), staged<float>(base, st.cov_map, out_cov_map),
-                                              staged<float>(base, st.lh7, out_lh7), staged<float>(base, st.lh, out_likelihood),
-                                              h->stream, who))
-    return rc;
-  if (int rc = stage_copy_out(st.plan, base, h->stream)) return rc;
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  return HSM_OK;
-}
 
 // what hsm_match_score_batch asks for on top of hsm_match_batch (host pointers)
 struct BatchScoreReq {
   int level;
-  float* out_lh;
-  float* out_res;  // may be null
-  int groups;      // 0: no ranking
-  const int* group_offsets;
-  int group_size;
-  int* out_index;
-  float* out_score;      // may be null
-  float* out_best_pose;  // may be null; in/out (a group without a winner keeps the caller's values)
+  ScoreOut out;  // the residuals may be null
+  Ranking rank;
 };
 
-// hsm_match_batch, and with `sr` hsm_match_score_batch: host arrays in, one device call on the context's stream, results out
-static int match_batch_host(hsm_ctx* h, int batch, const float* begin_world, const float* pts_xy, const int* scan_offsets,
-                            int shared_n, float* out_pose, float* out_cov, const BatchScoreReq* sr, const char* who) {
+// hsm_match_batch, and with `sr` hsm_match_score_batch: host arrays in (`B`, `M`: host pointers), one device call on the context's
+// stream, results out
+static int match_batch_host(hsm_ctx* h, const ScanBatch& B, const MatchOut& M, const BatchScoreReq* sr, const char* who) {
   if (!h) return fail(HSM_ERR_INVALID, "null context");
-  if (batch < 0 || !begin_world || !out_pose) return fail(HSM_ERR_INVALID, who);
+  if (B.batch < 0 || !B.d_poses || !M.d_out_pose) return fail(HSM_ERR_INVALID, who);
   static const BatchScoreReq kNoScore = {};
   const BatchScoreReq& r = sr ? *sr : kNoScore;
-  const int G = r.groups;
+  const Ranking& R = r.rank;
+  const int batch = B.batch, G = R.groups;
+  const int* scan_offsets = B.d_offsets;
   if (sr) {
     if (int rc = valid_level(h, r.level)) return rc;
-    if (!r.out_lh || bad_ranking(batch, G, r.out_lh, r.out_index, r.group_offsets, r.group_size)) return fail(HSM_ERR_INVALID, who);
-    if (G > 0 && r.group_offsets)
+    if (!r.out.d_likelihood || R.bad_ranking(batch, r.out.d_likelihood)) return fail(HSM_ERR_INVALID, who);
+    if (G > 0 && R.group_offsets)
       for (int g = 0; g < G; ++g)
-        if (r.group_offsets[g] < 0 || r.group_offsets[g] > r.group_offsets[g + 1] || r.group_offsets[g + 1] > batch)
+        if (R.group_offsets[g] < 0 || R.group_offsets[g] > R.group_offsets[g + 1] || R.group_offsets[g + 1] > batch)
           return fail(HSM_ERR_INVALID, who);
   }
   if (batch == 0) return HSM_OK;
-  const size_t total = scan_offsets ? (size_t)scan_offsets[batch] : (size_t)(shared_n > 0 ? shared_n : 0);
-  if (total > 0 && !pts_xy) return fail(HSM_ERR_INVALID, who);
-  const MatchBatchStage st = match_batch_stage(batch, total, G, !scan_offsets, begin_world, pts_xy, scan_offsets, out_pose, out_cov,
-                                               r.out_lh, r.out_res, r.group_offsets, r.out_index, r.out_score, r.out_best_pose);
+  const int shared_n = B.shared_n > 0 ? B.shared_n : 0;
+  const size_t total = scan_offsets ? (size_t)scan_offsets[batch] : (size_t)shared_n;
+  if (total > 0 && !B.d_pts) return fail(HSM_ERR_INVALID, who);
+  const MatchBatchStage st = match_batch_stage(batch, total, G, !scan_offsets, B.d_poses, B.d_pts, scan_offsets, M.d_out_pose, M.d_out_cov,
+                                               r.out.d_likelihood, r.out.d_residual, R.group_offsets, R.out_index, R.out_score,
+                                               R.out_best_pose);
   // the launches behind the copies in: x = the device address of the block, d_pts = that of the end points
   auto launch = [&](char* x, const float* d_pts, int n_or_hint, int n_bound) {
-    const float* d_begin = staged<float>(x, st.begin);
-    const int* d_offs = staged<int>(x, st.offs, scan_offsets);
-    float* d_pose = staged<float>(x, st.pose);
-    float* d_cov = staged<float>(x, st.cov, out_cov);
-    if (!sr) return match_batch_device_nolock(h, batch, d_begin, d_pts, d_offs, n_or_hint, d_pose, d_cov, h->stream, n_bound);
-    return match_score_batch_device_nolock(h, batch, d_begin, d_pts, d_offs, n_or_hint, d_pose, d_cov, r.level, staged<float>(x, st.lh),
-                                           staged<float>(x, st.res, r.out_res), G, staged<int>(x, st.goffs, r.group_offsets),
-                                           r.group_size, staged<int>(x, st.idx), staged<float>(x, st.bscore, r.out_score),
-                                           staged<float>(x, st.bpose, r.out_best_pose), h->stream, n_bound);
+    const ScanBatch D{batch, staged<float>(x, st.begin), d_pts, staged<int>(x, st.offs, scan_offsets), n_or_hint};
+    const MatchOut O{staged<float>(x, st.pose), staged<float>(x, st.cov, M.d_out_cov), n_bound};
+    if (!sr) return match_batch_device_nolock(h, D, O, h->stream);
+    const ScoringStep step{r.level, {staged<float>(x, st.lh), staged<float>(x, st.res, r.out.d_residual)}};
+    const Ranking DR{G, staged<int>(x, st.goffs, R.group_offsets), R.group_size, staged<int>(x, st.idx),
+                     staged<float>(x, st.bscore, R.out_score), staged<float>(x, st.bpose, R.out_best_pose)};
+    return match_chain_nolock(h, D, O, step, DR, h->stream);
   };
   std::lock_guard<std::mutex> lk(h->mu);
   if (int rc = select_device(h)) return rc;
@@ -544,7 +359,7 @@ static int match_batch_host(hsm_ctx* h, int batch, const float* begin_world, con
     HIP_TRY(hipHostGetDevicePointer((void**)&dp, hyp, 0));
     if (int rc = h->d_scan.reserve(total, kScanGrowth)) return rc;
     if (total) HIP_TRY(hipMemcpyAsync(h->d_scan, hyp + st.pts, total * sizeof(float2), hipMemcpyHostToDevice, h->stream));
-    if (int rc = launch(dp, (const float*)h->d_scan.p, shared_n > 0 ? shared_n : 0, 0)) return rc;
+    if (int rc = launch(dp, (const float*)h->d_scan.p, shared_n, 0)) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));
     stage_drain_host(st.plan, hyp);
     return HSM_OK;
@@ -563,9 +378,124 @@ static int match_batch_host(hsm_ctx* h, int batch, const float* begin_world, con
   return HSM_OK;
 }
 
+int hsm_match_batch_device(hsm_ctx* h, int batch, const float* d_begin_world, const float* d_pts_xy,
+                           const int* d_scan_offsets, int shared_n, float* d_out_pose, float* d_out_cov,
+                           void* stream) {
+  if (!h) return fail(HSM_ERR_INVALID, "null context");
+  std::lock_guard<std::mutex> lk(h->mu);
+  return match_batch_device_nolock(h, {batch, d_begin_world, d_pts_xy, d_scan_offsets, shared_n}, {d_out_pose, d_out_cov}, stream);
+}
+
+int hsm_match_batch_device_gather(hsm_ctx* h, int batch, const float* d_begin_world, const float* d_pts_xy,
+                                  const int* d_scan_offsets, int shared_n, float* d_out_pose, float* d_out_cov,
+                                  hsm_exchange* x, int first_row, int lag, float* d_out_all, void* stream) {
+  if (!h || !x) return fail(HSM_ERR_INVALID, "null context / exchange");
+  if (batch <= 0) return fail(HSM_ERR_INVALID, "hsm_match_batch_device_gather: every rank posts a non-empty shard");
+  std::lock_guard<std::mutex> lk(h->mu);
+  // The exchange step of this match: carried by the matcher launch itself where the form can (the exact-order batch forms: every
+  // wavefront posts its pose from the kernel's epilogue, extra workgroups at the end of the grid unpack the epoch `lag` matches
+  // back -- no launch of its own, nothing between two matcher launches), else one launch of the stand-alone exchange kernel behind it.
+  ExchangeFused f;
+  if (int rc = hsm_host::exchange_fused_begin(x, first_row, batch, lag, d_out_all, &f)) return rc;
+  if (int rc = match_batch_device_nolock(h, {batch, d_begin_world, d_pts_xy, d_scan_offsets, shared_n}, {d_out_pose, d_out_cov, 0, &f},
+                                         stream))
+    return rc;
+  if (h->batch.fused_exchange_done) {
+    hsm_host::exchange_fused_commit(x, f);
+    return HSM_OK;
+  }
+  return hsm_exchange_post_wait(x, d_out_pose, first_row, batch, lag, d_out_all, stream);
+}
+
+int hsm_score_batch_device(hsm_ctx* h, int level, int batch, const float* d_poses_world, const float* d_pts_xy,
+                           const int* d_scan_offsets, int shared_n, float* d_out_likelihood, float* d_out_residual,
+                           void* stream) {
+  if (!h) return fail(HSM_ERR_INVALID, "null context");
+  std::lock_guard<std::mutex> lk(h->mu);
+  const ScanBatch B{batch, d_poses_world, d_pts_xy, d_scan_offsets, shared_n};
+  const ScoringStep step{level, {d_out_likelihood, d_out_residual}, {}, false, "hsm_score_batch_device"};
+  if (int rc = scoring_step_check(h, step, B)) return rc;
+  return scoring_step_launch(h, step, B, stream);
+}
+
+int hsm_covariance_batch_device(hsm_ctx* h, int level, int batch, const float* d_poses_world, const float* d_pts_xy,
+                                const int* d_scan_offsets, int shared_n, float* d_out_cov_world, float* d_out_cov_map,
+                                float* d_out_lh7, float* d_out_likelihood, void* stream) {
+  if (!h) return fail(HSM_ERR_INVALID, "hsm_covariance_batch_device: null context");
+  std::lock_guard<std::mutex> lk(h->mu);
+  const ScanBatch B{batch, d_poses_world, d_pts_xy, d_scan_offsets, shared_n};
+  const ScoringStep step{level, {}, {d_out_cov_world, d_out_cov_map, d_out_lh7, d_out_likelihood}, true, "hsm_covariance_batch_device"};
+  if (int rc = scoring_step_check(h, step, B)) return rc;
+  return scoring_step_launch(h, step, B, stream);
+}
+
+int hsm_select_best_device(hsm_ctx* h, int groups, const int* d_group_offsets, int group_size, const float* d_scores,
+                           const float* d_poses_world, int* d_out_index, float* d_out_score, float* d_out_pose_world,
+                           void* stream) {
+  if (!h) return fail(HSM_ERR_INVALID, "null context");
+  std::lock_guard<std::mutex> lk(h->mu);
+  return select_best_device_nolock(h, {groups, d_group_offsets, group_size, d_out_index, d_out_score, d_out_pose_world}, d_scores,
+                                   d_poses_world, stream);
+}
+
+int hsm_match_score_batch_device(hsm_ctx* h, int batch, const float* d_begin_world, const float* d_pts_xy,
+                                 const int* d_scan_offsets, int shared_n, float* d_out_pose, float* d_out_cov, int score_level,
+                                 float* d_out_likelihood, float* d_out_residual, int groups, const int* d_group_offsets,
+                                 int group_size, int* d_out_index, float* d_out_score, float* d_out_best_pose, void* stream) {
+  if (!h) return fail(HSM_ERR_INVALID, "null context");
+  std::lock_guard<std::mutex> lk(h->mu);
+  return match_chain_nolock(h, {batch, d_begin_world, d_pts_xy, d_scan_offsets, shared_n}, {d_out_pose, d_out_cov},
+                            {score_level, {d_out_likelihood, d_out_residual}},
+                            {groups, d_group_offsets, group_size, d_out_index, d_out_score, d_out_best_pose}, stream);
+}
+
+int hsm_match_cov_batch_device(hsm_ctx* h, int batch, const float* d_begin_world, const float* d_pts_xy, const int* d_scan_offsets,
+                               int shared_n, float* d_out_pose, float* d_out_cov, int cov_level, float* d_out_cov_world,
+                               float* d_out_cov_map, float* d_out_lh7, float* d_out_likelihood, int groups,
+                               const int* d_group_offsets, int group_size, int* d_out_index, float* d_out_score,
+                               float* d_out_best_pose, void* stream) {
+  static const char* const who = "hsm_match_cov_batch_device";
+  if (!h) return fail_at(HSM_ERR_INVALID, who, ": null context");
+  std::lock_guard<std::mutex> lk(h->mu);
+  return match_chain_nolock(h, {batch, d_begin_world, d_pts_xy, d_scan_offsets, shared_n}, {d_out_pose, d_out_cov},
+                            {cov_level, {}, {d_out_cov_world, d_out_cov_map, d_out_lh7, d_out_likelihood}, true, who},
+                            {groups, d_group_offsets, group_size, d_out_index, d_out_score, d_out_best_pose}, stream);
+}
+
+// host arrays in, covariance_batch_kernel on the context's stream, results out; synchronous
+int hsm_covariance_batch(hsm_ctx* h, int level, int batch, const float* poses_world, const float* pts_xy, const int* scan_offsets,
+                         int shared_n, float* out_cov_world, float* out_cov_map, float* out_lh7, float* out_likelihood) {
+  static const char* const who = "hsm_covariance_batch";
+  const ScanBatch B{batch, poses_world, pts_xy, scan_offsets, shared_n};
+  if (int rc = scoring_step_check(h, {level, {}, {out_cov_world, out_cov_map, out_lh7, out_likelihood}, true, who}, B)) return rc;
+  if (batch == 0) return HSM_OK;
+  if (scan_offsets) {
+    if (scan_offsets[0] != 0) return fail_at(HSM_ERR_INVALID, who, ": bad argument");
+    for (int i = 0; i < batch; ++i)
+      if (scan_offsets[i + 1] < scan_offsets[i]) return fail_at(HSM_ERR_INVALID, who, ": bad argument");
+  }
+  const size_t total = scan_offsets ? (size_t)scan_offsets[batch] : (size_t)shared_n;
+  if (total > 0 && !pts_xy) return fail_at(HSM_ERR_INVALID, who, ": bad argument");
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (int rc = select_device(h)) return rc;
+  const CovarianceBatchStage st = covariance_batch_stage(batch, total, poses_world, pts_xy, scan_offsets, out_cov_world, out_cov_map,
+                                                         out_lh7, out_likelihood);
+  if (int rc = h->d_batch.reserve(st.plan.total())) return rc;
+  char* base = h->d_batch;
+  if (int rc = stage_copy_in(st.plan, base, h->stream)) return rc;
+  const ScanBatch D{batch, staged<float>(base, st.poses), staged<float>(base, st.pts), staged<int>(base, st.offs, scan_offsets),
+                    B.kernel_shared_n()};
+  const CovOut d_out{staged<float>(base, st.cov_world, out_cov_world), staged<float>(base, st.cov_map, out_cov_map),
+                     staged<float>(base, st.lh7, out_lh7), staged<float>(base, st.lh, out_likelihood)};
+  if (int rc = scoring_step_launch(h, {level, {}, d_out, true, who}, D, h->stream)) return rc;
+  if (int rc = stage_copy_out(st.plan, base, h->stream)) return rc;
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return HSM_OK;
+}
+
 int hsm_match_batch(hsm_ctx* h, int batch, const float* begin_world, const float* pts_xy,
                     const int* scan_offsets, int shared_n, float* out_pose, float* out_cov) {
-  return match_batch_host(h, batch, begin_world, pts_xy, scan_offsets, shared_n, out_pose, out_cov, nullptr,
+  return match_batch_host(h, {batch, begin_world, pts_xy, scan_offsets, shared_n}, {out_pose, out_cov}, nullptr,
                           "hsm_match_batch: bad argument");
 }
 
@@ -573,9 +503,9 @@ int hsm_match_score_batch(hsm_ctx* h, int batch, const float* begin_world, const
                           int shared_n, float* out_pose, float* out_cov, int score_level, float* out_likelihood,
                           float* out_residual, int groups, const int* group_offsets, int group_size, int* out_index,
                           float* out_score, float* out_best_pose) {
-  const BatchScoreReq sr = {score_level, out_likelihood, out_residual, groups, group_offsets, group_size, out_index, out_score,
-                            out_best_pose};
-  return match_batch_host(h, batch, begin_world, pts_xy, scan_offsets, shared_n, out_pose, out_cov, &sr,
+  const BatchScoreReq sr = {score_level, {out_likelihood, out_residual},
+                            {groups, group_offsets, group_size, out_index, out_score, out_best_pose}};
+  return match_batch_host(h, {batch, begin_world, pts_xy, scan_offsets, shared_n}, {out_pose, out_cov}, &sr,
                           "hsm_match_score_batch: bad argument");
 }
 

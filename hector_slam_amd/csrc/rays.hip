@@ -1,8 +1,8 @@
 // rays.hip -- the entries of the C ABI (include/hector_mi355/capi.h) that ask a level "what would a laser see from here?":
 // DistanceMeasurementProvider::getDist for arrays of rays (hsm_ray_distances, hsm_ray_distances_device) and for whole scan fans
 // cast from batches of sensor poses (hsm_cast_scans_device, hsm_cast_scans).  The kernels are in ray_kernels.h.  The device
-// entries read the map like a batched score and are ordered like one (order_map_reader of the core runtime, hector_mi355.hip,
-// which declares what these entries need of it in hsm_ctx.h).
+// entries read the map like a batched score and are ordered like one (the MapReader bracket of hsm_ctx.h, around
+// order_map_reader of the core runtime, hector_mi355.hip, which declares what these entries need of it in hsm_ctx.h).
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <math.h>
@@ -126,8 +126,8 @@ int hsm_ray_distances_device(hsm_ctx* h, int level, float origin_x, float origin
   std::lock_guard<std::mutex> lk(h->mu);
   if (int rc = select_device(h)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  hsm_ctx::ForeignStream* fs = nullptr;
-  if (int rc = order_map_reader(h, s, "hsm_ray_distances_device", &fs)) return rc;
+  MapReader reader;
+  if (int rc = reader.begin(h, s, "hsm_ray_distances_device")) return rc;
   RayQueryParams P;
   P.grid = ray_grid(h->levels[level], origin_x, origin_y, resolution);
   P.begin_world = reinterpret_cast<const float2*>(d_begin_world_xy);
@@ -137,7 +137,7 @@ int hsm_ray_distances_device(hsm_ctx* h, int level, float origin_x, float origin
   P.n = n;
   hipLaunchKernelGGL(ray_distance_kernel<true>, dim3((n + 3) / 4), dim3(256), 0, s, P);
   HIP_TRY(hipGetLastError());
-  if (fs) fs->pending = true;
+  reader.queued();
   h->last.last_kernel = "ray_distance_kernel";
   return HSM_OK;
 }
@@ -152,11 +152,11 @@ int hsm_cast_scans_device(hsm_ctx* h, int level, int batch, const float* d_poses
   std::lock_guard<std::mutex> lk(h->mu);
   if (int rc = select_device(h)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  hsm_ctx::ForeignStream* fs = nullptr;
-  if (int rc = order_map_reader(h, s, "hsm_cast_scans_device", &fs)) return rc;
+  MapReader reader;
+  if (int rc = reader.begin(h, s, "hsm_cast_scans_device")) return rc;
   if (int rc = cast_scans_launch(h, level, batch, d_poses_world, d_beam_angles, n, range_max, d_out_ranges, d_out_hit_xy, s))
     return rc;
-  if (fs) fs->pending = true;
+  reader.queued();
   return HSM_OK;
 }
 

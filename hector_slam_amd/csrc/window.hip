@@ -3,7 +3,7 @@
 // indices as poses (hsm_window_poses_device), the K best of an array of scores (hsm_select_topk_device) and the chain
 // window score -> top K -> poses -> match -> score on level 0 -> winner (hsm_relocalize_device, hsm_relocalize).  The kernels are
 // in window_kernels.h, the window's arithmetic and the workspace sizes in window_grid.h.  The scoring entries read the map like a
-// batched score and are ordered like one (order_map_reader of the core runtime, hector_mi355.hip).
+// batched score and are ordered like one (MapReader of hsm_ctx.h); the chain's tail is match_chain_nolock of match.hip.
 // Also here, because the chain ends in the relocalisation: a level's occupied cells as a point set (hsm_occupied_points*, the
 // kernels in map_points_kernels.h) and another context's map aligned to this one (hsm_align_map): extraction from the other
 // context, the counts fetched, the relocalisation of those points on this one.
@@ -63,10 +63,9 @@ int score_window_refusals(const hsm_ctx* h, int level, const float* d_center, co
 // one kernel on `s`; arguments checked, device selected, lock held
 int score_window_launch(hsm_ctx* h, int level, const float* d_center, const WindowGrid& G, int W, const float* d_pts, int n,
                         float* d_out_lh, float* d_out_res, hipStream_t s) {
-  hsm_ctx::ForeignStream* fs = nullptr;
-  if (int rc = order_map_reader(h, s, "hsm_score_window_device", &fs)) return rc;
-  const float factor = (float)(1.0 / pow(2.0, (double)level));
-  const LevelView v = level_view(h->levels[level], factor, 1);
+  MapReader reader;
+  if (int rc = reader.begin(h, s, "hsm_score_window_device")) return rc;
+  const LevelView v = level_view(h->levels[level], level_factor(level), 1);
   WindowParams P;
   P.grid = G;
   P.center = d_center;
@@ -85,7 +84,7 @@ int score_window_launch(hsm_ctx* h, int level, const float* d_center, const Wind
     else hipLaunchKernelGGL((score_window_wave_kernel<kLayoutQuad>), dim3(grid), dim3(256), 0, s, v, P);
   }
   HIP_TRY(hipGetLastError());
-  if (fs) fs->pending = true;
+  reader.queued();
   h->last.last_kernel = lane ? "score_window_lane_kernel" : "score_window_wave_kernel";
   h->last.last_parity = HSM_PARITY_EXACT;  // a lane (or lane 0) owns the whole chain: the reference's order in every mode
   return HSM_OK;
@@ -140,8 +139,9 @@ int relocalize_queue(hsm_ctx* h, int search_level, const float* d_center, const 
   if (int rc = score_window_launch(h, search_level, d_center, G, W, d_pts, n, scores, nullptr, s)) return rc;
   if (int rc = select_topk_launch(W, scores, k, kindex, kscore, ws + L.topk, s)) return rc;
   if (int rc = window_poses_launch(G, W, d_center, kindex, k, kpose, s)) return rc;
-  if (int rc = match_score_batch_chain_nolock(h, k, kpose, d_pts, n, d_cand_pose, d_cand_cov, 0, d_cand_lh, 1, k, d_best_index,
-                                              d_best_score, d_best_pose, s))
+  // the k starts against the one scan: match, the likelihood on level 0, the winner of the one group of k
+  if (int rc = match_chain_nolock(h, {k, kpose, d_pts, nullptr, n}, {d_cand_pose, d_cand_cov}, {0, {d_cand_lh}},
+                                  {1, nullptr, k, d_best_index, d_best_score, d_best_pose}, s))
     return rc;
   hipLaunchKernelGGL(window_best_index_kernel, dim3(1), dim3(64), 0, s, kindex, k, d_best_index);
   HIP_TRY(hipGetLastError());
@@ -159,13 +159,12 @@ int occupied_points_refusals(const hsm_ctx* h, int level, int every, int max_poi
   return HSM_OK;
 }
 
-// the three launches on `s`, ordered as a reader of `src`; arguments checked, device selected, lock held.  *mark: as
-// order_map_reader's, and already marked pending -- before the first launch, so that a call that fails half way leaves `src`'s
+// the three launches on `s`, ordered as a reader of `src`; arguments checked, device selected, lock held.  `reader`: the caller's
+// bracket, marked pending here already -- before the first launch, so that a call that fails half way leaves `src`'s
 // next writer behind whatever it did queue.  A caller that has waited for `s` under the lock may clear the mark again
 int occupied_points_launch(hsm_ctx* src, int level, const PointsBox& B, int every, int max_points, float* d_pts, int* d_count,
-                           void* d_ws, hipStream_t s, const char* who, hsm_ctx::ForeignStream** mark) {
-  if (int rc = order_map_reader(src, s, who, mark)) return rc;
-  if (*mark) (*mark)->pending = true;
+                           void* d_ws, hipStream_t s, const char* who, MapReader& reader) {
+  if (int rc = reader.begin(src, s, who, /*mark_now=*/true)) return rc;
   const Level& L = src->levels[level];
   MapPointsParams P;
   P.logodds = L.d_logodds;
@@ -317,9 +316,9 @@ int hsm_occupied_points_device(hsm_ctx* src, int level, const int bbox[4], int e
   if (!d_workspace || ((size_t)d_workspace & 7) || workspace_bytes < points_workspace_bytes((long long)B.w * B.h))
     return fail_at(HSM_ERR_INVALID, who, ": workspace missing, misaligned or too small");
   if (int rc = select_device(src)) return rc;
-  hsm_ctx::ForeignStream* fs = nullptr;
+  MapReader reader;
   return occupied_points_launch(src, level, B, every, max_points, d_out_pts_xy, d_out_count, d_workspace,
-                                static_cast<hipStream_t>(stream), who, &fs);
+                                static_cast<hipStream_t>(stream), who, reader);
 }
 
 int hsm_occupied_points(hsm_ctx* src, int level, const int bbox[4], int every, int max_points, float* out_pts_xy, int count[2]) {
@@ -332,9 +331,9 @@ int hsm_occupied_points(hsm_ctx* src, int level, const int bbox[4], int every, i
   const OccupiedPointsStage st = occupied_points_stage(max_points, points_workspace_bytes((long long)B.w * B.h), count);
   if (int rc = src->d_batch.reserve(st.plan.total())) return rc;
   char* base = src->d_batch;
-  hsm_ctx::ForeignStream* fs = nullptr;
+  MapReader reader;
   if (int rc = occupied_points_launch(src, level, B, every, max_points, staged<float>(base, st.pts), staged<int>(base, st.counts),
-                                      base + st.ws, src->stream, who, &fs))
+                                      base + st.ws, src->stream, who, reader))
     return rc;
   if (int rc = stage_copy_out(st.plan, base, src->stream)) return rc;
   HIP_TRY(hipStreamSynchronize(src->stream));
@@ -382,14 +381,14 @@ int hsm_align_map(hsm_ctx* dst, hsm_ctx* src, int src_level, const int src_bbox[
   char* base = dst->d_batch;
   if (int rc = stage_copy_in(st.plan, base, dst->stream)) return rc;
   // (a) `src`'s cells on `dst`'s stream, behind every update queued on `src`, marked for `src`'s next writer
-  hsm_ctx::ForeignStream* fs = nullptr;
+  MapReader reader;
   if (int rc = occupied_points_launch(src, src_level, B, every, max_points, staged<float>(base, st.pts), staged<int>(base, st.counts),
-                                      base + st.xws, dst->stream, who, &fs))
+                                      base + st.xws, dst->stream, who, reader))
     return rc;
   // (b) the chain's one host wait: every entry behind this point takes the number of points from the host
   HIP_TRY(hipMemcpyAsync(cnt, base + st.counts, sizeof cnt, hipMemcpyDeviceToHost, dst->stream));
   HIP_TRY(hipStreamSynchronize(dst->stream));
-  if (fs) fs->pending = false;  // the read of `src` is over, under `src`'s lock: its next writer has nothing to wait for
+  if (reader.mark) reader.mark->pending = false;  // the read of `src` is over, under `src`'s lock: its next writer has nothing to wait for
   // (c) the points are a scan in `src`'s world frame, so the pose the matcher refines is src_in_dst
   if (int rc = relocalize_queue(dst, search_level, staged<float>(base, st.center), window_grid(step, half), (int)W, k,
                                 staged<float>(base, st.pts), cnt[0], base + st.ws, staged<float>(base, st.pose),

@@ -14,6 +14,11 @@ again, all cases, from the commit before that move).  Their first argument is th
 
 The single-scan conversions (INGEST) and one failing HIP status check joined it before raw-scan conversion and the occupancy
 exports moved to ingest.hip and occupancy.hip (recorded again, all cases, from the commit before that move).
+
+The batched match, score, covariance, select and chain entries, the window and relocalisation entries and the device readers of
+rays.hip (MATCHER) joined it before the matcher's front door was rewritten onto argument bundles and every map reader onto one
+bracket (recorded again, all cases, from the commit before that rewrite).  Like the MOVED entries they are called through bare
+addresses.  The steps and half-extents of a window are host arrays the entry reads: "H_STEP", "H_HALF" and their bad variants.
 """
 INT_MAX = 2**31 - 1
 MAX_BEAMS = 1048575  # HSM_MAX_UPDATE_BEAMS
@@ -111,6 +116,42 @@ INGEST = {
     "hsm_ingest_laser_scan_tf": [("ranges", "H"), ("n", N)] + _TF + [("tf_rows", "H")] + _GATES + [("out_pts", None), ("out_n", None),
                                                                                                  ("out_origo", None)],
 }
+# the matcher's front door (match.hip), the window entries (window.hip) and the device readers of rays.hip
+_SCANS = [("pts", "D"), ("offsets", None), ("shared_n", N)]
+_MATCH = [("batch", COUNT), ("begin", "D")] + _SCANS + [("out_pose", "D"), ("out_cov", None)]
+_RANKING = [("groups", 0), ("group_offsets", None), ("group_size", 0), ("out_index", None), ("out_score", None), ("out_best_pose", None)]
+_COV_OUT = [("out_cov_world", "D"), ("out_cov_map", None), ("out_lh7", None), ("out_likelihood", "D")]
+_WINDOW = [("center", "D"), ("step", "H_STEP"), ("half", "H_HALF")]
+_HOST = lambda params: [(k, "H" if v == "D" else v) for k, v in params]  # noqa: E731
+MATCHER = {
+    "hsm_match_batch_device": _MATCH + [("stream", "S")],
+    "hsm_match_batch_device_gather": _MATCH + [("exchange", "D"), ("first_row", 0), ("lag", 0), ("out_all", None), ("stream", "S")],
+    "hsm_score_batch_device": [("level", 0), ("batch", COUNT), ("poses", "D")] + _SCANS + [("out_likelihood", "D"), ("out_residual", None),
+                                                                                           ("stream", "S")],
+    "hsm_covariance_batch_device": [("level", 0), ("batch", COUNT), ("poses", "D")] + _SCANS + _COV_OUT + [("stream", "S")],
+    "hsm_select_best_device": [("groups", 1), ("group_offsets", None), ("group_size", COUNT), ("scores", "D"), ("poses", "D"),
+                               ("out_index", "D"), ("out_score", None), ("out_pose", None), ("stream", "S")],
+    "hsm_match_score_batch_device": _MATCH + [("level", 0), ("out_likelihood", "D"), ("out_residual", None)] + _RANKING + [("stream", "S")],
+    "hsm_match_cov_batch_device": _MATCH + [("level", 0)] + _COV_OUT + _RANKING + [("stream", "S")],
+    "hsm_match_batch": _HOST(_MATCH),
+    "hsm_match_score_batch": _HOST(_MATCH) + [("level", 0), ("out_likelihood", "H"), ("out_residual", None)] + _RANKING,
+    "hsm_covariance_batch": [("level", 0), ("batch", COUNT), ("poses", "H")] + _HOST(_SCANS) + _HOST(_COV_OUT),
+    "hsm_score_window_device": [("level", 0)] + _WINDOW + [("pts", "D"), ("n", N), ("out_likelihood", "D"), ("out_residual", None),
+                                                           ("stream", "S")],
+    "hsm_relocalize_device": [("level", 0)] + _WINDOW + [("k", 2), ("pts", "D"), ("n", N), ("workspace", "D"),
+                                                         ("workspace_bytes", "WS_RELOC"), ("cand_pose", "D"), ("cand_cov", None),
+                                                         ("cand_likelihood", "D"), ("best_pose", "D"), ("best_score", None),
+                                                         ("best_index", "D"), ("stream", "S")],
+    "hsm_ray_distances_device": [("level", 0), ("origin_x", 0.0), ("origin_y", 0.0), ("resolution", 0.05), ("n", N), ("begin", "D"),
+                                 ("end", "D"), ("out_dist", "D"), ("out_hit", None), ("stream", "S")],
+    "hsm_cast_scans_device": [("level", 0), ("batch", COUNT), ("poses", "D"), ("angles", "D"), ("n", N), ("range_max", 30.0),
+                              ("out_ranges", "D"), ("out_hit", None), ("stream", "S")],
+    "hsm_occupied_points_device": [("level", 0), ("bbox", None), ("every", 1), ("max_points", N), ("out_pts", "D"), ("out_count", "D"),
+                                   ("workspace", "D"), ("workspace_bytes", "WS_POINTS"), ("stream", "S")],
+}
+_CHAINS = ["hsm_match_score_batch_device", "hsm_match_cov_batch_device"]
+_BATCH_READERS = ["hsm_score_batch_device", "hsm_covariance_batch_device", "hsm_covariance_batch"]
+_WINDOWS = ["hsm_score_window_device", "hsm_relocalize_device"]
 # what goes in front of an entry's parameters: the context (every entry not listed), the runner's one-device group, or nothing
 FIRST = {e: "group" for e in MOVED if e.startswith("hsm_group_")}
 FIRST.update({"hsm_group_create": None, "hsm_shard_bounds": None})
@@ -136,7 +177,7 @@ def cases():
         out.append((f"{entry}:{what}", entry, over, capture))
 
     for e in ENTRIES:
-        if e not in MOVED and e not in INGEST:
+        if e not in MOVED and e not in INGEST and e not in MATCHER:
             add("negative count", e, **{_count_name(e): -1})
     for e in _UPDATES + _SLAM_SCANS:
         add("negative max_beams", e, max_beams=-5)
@@ -183,6 +224,7 @@ def cases():
     add("too many beams under capture", "hsm_update_by_scans_device", capture=True, offsets=None, shared_n=MAX_BEAMS + 1)
     add("short workspace under capture", "hsm_slam_ranges_tf_device", capture=True, workspace_bytes="WS_SLAM-1")
     moved_cases(add)
+    matcher_cases(add)
     for e in INGEST:
         add("null context", e, ctx=None)
         add("negative n", e, n=-1)
@@ -272,8 +314,108 @@ def moved_cases(add):
     add("null end", "hsm_shard_bounds", end=None)
 
 
+def matcher_cases(add):
+    """the refusals of the entries in MATCHER"""
+    no_out = lambda e: {k: None for k, _ in MATCHER[e] if k.startswith("out_") and k not in ("out_pose", "out_cov")}  # noqa: E731
+    for e in MATCHER:
+        add("null context", e, ctx=None)
+        if MATCHER[e][0][0] == "level" or e in _CHAINS + ["hsm_match_score_batch"]:
+            add("level below zero", e, level=-1)
+            add("level past the pyramid", e, level=2)
+    # the batch of (pose, scan) pairs
+    for e in MATCHER:
+        if any(k == "batch" for k, _ in MATCHER[e]):
+            add("negative batch", e, batch=-1)
+    for e in ["hsm_match_batch_device", "hsm_match_batch", "hsm_match_score_batch"] + _CHAINS:
+        add("null start poses", e, begin=None)
+        add("null output pose", e, out_pose=None)
+    for e in _BATCH_READERS:
+        add("null poses", e, poses=None)
+    for e in ["hsm_match_batch_device"] + _CHAINS + _BATCH_READERS:
+        add("negative shared_n without offsets", e, shared_n=-1)
+    for e in ["hsm_match_batch", "hsm_match_score_batch"] + _CHAINS + _BATCH_READERS:
+        add("null pts for a shared scan", e, pts=None, shared_n=100)
+    for e in _CHAINS + _BATCH_READERS:
+        add("no output", e, **no_out(e))
+    add("no likelihood output", "hsm_match_score_batch", out_likelihood=None, out_residual="H")
+    add("null exchange", "hsm_match_batch_device_gather", exchange=None)
+    add("empty batch", "hsm_match_batch_device_gather", batch=0)
+    add("null exchange and a negative batch", "hsm_match_batch_device_gather", exchange=None, batch=-1)
+    add("offsets that do not start at zero", "hsm_covariance_batch", offsets="H_NEGATIVE", shared_n=0)
+    add("offsets that decrease", "hsm_covariance_batch", offsets="H_DECREASING", shared_n=0)
+    # the ranking
+    for e in _CHAINS + ["hsm_match_score_batch"]:
+        d = "H" if e == "hsm_match_score_batch" else "D"
+        add("negative groups", e, groups=-1, group_size=1, out_index=d)
+        add("groups without out_index", e, groups=1, group_size=COUNT)
+        add("groups times group_size above the batch", e, groups=1, group_size=COUNT + 1, out_index=d)
+        add("negative group_size", e, groups=1, group_size=-1, out_index=d)
+        add("bad ranking and a null start pose", e, groups=1, group_size=COUNT + 1, out_index=d, begin=None)
+        add("level out of range and a negative batch", e, level=7, batch=-1)
+    add("groups without likelihood output", "hsm_match_score_batch_device", groups=1, group_size=COUNT, out_index="D",
+        out_likelihood=None, out_residual="D")
+    add("groups without likelihood output", "hsm_match_cov_batch_device", groups=1, group_size=COUNT, out_index="D", out_likelihood=None)
+    add("group offsets that decrease", "hsm_match_score_batch", groups=2, group_offsets="H_GROUPS_DECREASING", out_index="H")
+    add("group offsets that pass the batch", "hsm_match_score_batch", groups=2, group_offsets="H_GROUPS_PAST", out_index="H")
+    add("group offsets that start below zero", "hsm_match_score_batch", groups=2, group_offsets="H_NEGATIVE", out_index="H")
+    for e in _BATCH_READERS + ["hsm_cast_scans_device"]:
+        add("level out of range and a negative batch", e, level=7, batch=-1)
+    add("negative groups", "hsm_select_best_device", groups=-1)
+    add("negative group_size", "hsm_select_best_device", group_size=-1)
+    add("null out_index", "hsm_select_best_device", out_index=None)
+    add("null scores", "hsm_select_best_device", scores=None)
+    add("winner poses without poses", "hsm_select_best_device", poses=None, out_pose="D")
+    add("groups times group_size above INT_MAX", "hsm_select_best_device", groups=65536, group_size=65536)
+    # the windows
+    for e in _WINDOWS:
+        add("null centre", e, center=None)
+        add("null steps", e, step=None)
+        add("null half-extents", e, half=None)
+        add("negative half-extent", e, half="H_HALF_NEGATIVE")
+        add("non-finite step", e, step="H_STEP_NAN")
+        add("more than INT_MAX hypotheses", e, half="H_HALF_HUGE")
+        add("negative n", e, n=-1)
+        add("null pts", e, pts=None)
+        add("negative half-extent and a level out of range", e, half="H_HALF_NEGATIVE", level=7)
+        add("negative half-extent and a negative n", e, half="H_HALF_NEGATIVE", n=-1)
+    add("no output", "hsm_score_window_device", out_likelihood=None)
+    add("k below one", "hsm_relocalize_device", k=0)
+    add("k above HSM_MAX_TOPK", "hsm_relocalize_device", k=65)
+    for k in ("cand_pose", "cand_likelihood", "best_pose", "best_index"):
+        add(f"null {k}", "hsm_relocalize_device", **{k: None})
+    for e, ws in (("hsm_relocalize_device", "WS_RELOC"), ("hsm_occupied_points_device", "WS_POINTS")):
+        add("null workspace", e, workspace=None)
+        add("workspace one byte short", e, workspace_bytes=ws + "-1")
+        add("workspace at 4 mod 8", e, workspace="D+4")
+    add("null best_index and a null workspace", "hsm_relocalize_device", best_index=None, workspace=None)
+    # the readers of rays.hip
+    add("negative n", "hsm_ray_distances_device", n=-1)
+    add("null begin", "hsm_ray_distances_device", begin=None)
+    add("null end", "hsm_ray_distances_device", end=None)
+    add("null out_dist", "hsm_ray_distances_device", out_dist=None)
+    add("resolution zero", "hsm_ray_distances_device", resolution=0.0)
+    add("resolution NaN", "hsm_ray_distances_device", resolution=float("nan"))
+    add("level out of range and a negative n", "hsm_ray_distances_device", level=7, n=-1)
+    add("negative n", "hsm_cast_scans_device", n=-1)
+    add("negative range_max", "hsm_cast_scans_device", range_max=-1.0)
+    add("range_max NaN", "hsm_cast_scans_device", range_max=float("nan"))
+    add("batch times n above INT_MAX", "hsm_cast_scans_device", batch=65536, n=65536)
+    add("null poses", "hsm_cast_scans_device", poses=None)
+    add("null angles", "hsm_cast_scans_device", angles=None)
+    add("null ranges", "hsm_cast_scans_device", out_ranges=None)
+    add("negative batch and null poses", "hsm_cast_scans_device", batch=-1, poses=None)
+    # a level's occupied cells
+    add("every below one", "hsm_occupied_points_device", every=0)
+    add("negative max_points", "hsm_occupied_points_device", max_points=-1)
+    add("null counts", "hsm_occupied_points_device", out_count=None)
+    add("null points", "hsm_occupied_points_device", out_pts=None)
+    add("every below one and a level out of range", "hsm_occupied_points_device", every=0, level=7)
+    add("negative max_points and a null workspace", "hsm_occupied_points_device", max_points=-1, workspace=None)
+
+
 ENTRIES.update(MOVED)
 ENTRIES.update(INGEST)
+ENTRIES.update(MATCHER)
 
 
 class Runner:
@@ -294,12 +436,15 @@ class Runner:
         # the moved entries: every array argument as a bare address (the binding's array types take no null), and a group of one device
         import ctypes as C
         self.raw = C.CDLL(self.lib._name)
-        for entry in MOVED:
+        for entry in list(MOVED) + list(MATCHER):
             restype, argtypes = capi.SIGNATURES[entry]
             fn = getattr(self.raw, entry)
-            fn.restype, fn.argtypes = restype, [a if a in (C.c_int, C.c_uint, C.c_float) else C.c_void_p for a in argtypes]
+            fn.restype, fn.argtypes = restype, [a if a in (C.c_int, C.c_uint, C.c_float, C.c_size_t) else C.c_void_p for a in argtypes]
         self.zero_int, self.one_int = np.int32([0]), np.int32([1])
         self.ptr_d, self.ptr_null = np.uint64([self.dev.data_ptr()]), np.uint64([0])
+        self.step, self.step_nan = np.float32([0.05, 0.05, 0.01]), np.float32([0.05, np.nan, 0.01])
+        self.half, self.half_negative, self.half_huge = np.int32([1, 1, 0]), np.int32([1, -1, 0]), np.int32([1000, 1000, 1000])
+        self.groups_decreasing, self.groups_past = np.int32([0, 2, 1]), np.int32([0, 1, 3])
         self.group = C.c_void_p()
         assert self.lib.hsm_group_create(0.05, 64, 64, 1, 0.5, 0.5, self.zero_int, 1, C.byref(self.group)) == 0
         self.values = {
@@ -309,9 +454,17 @@ class Runner:
             "WS_SLAM": int(self.lib.hsm_slam_ranges_tf_workspace(COUNT, N)),
             "H_ZERO_INT": self.zero_int.ctypes.data, "H_ONE_INT": self.one_int.ctypes.data, "H_PTR_D": self.ptr_d.ctypes.data,
             "H_PTR_NULL": self.ptr_null.ctypes.data,
+            "H_STEP": self.step.ctypes.data, "H_STEP_NAN": self.step_nan.ctypes.data, "H_HALF": self.half.ctypes.data,
+            "H_HALF_NEGATIVE": self.half_negative.ctypes.data, "H_HALF_HUGE": self.half_huge.ctypes.data,
+            "H_GROUPS_DECREASING": self.groups_decreasing.ctypes.data, "H_GROUPS_PAST": self.groups_past.ctypes.data,
+            "WS_RELOC": int(self.lib.hsm_relocalize_workspace(9, 2)),      # the 3 x 3 x 1 window of H_HALF, k = 2
+            "WS_POINTS": int(self.lib.hsm_occupied_points_workspace(256 * 256)),  # level 0, whole
         }
         self.values["WS_RANGES-1"] = self.values["WS_RANGES"] - 1
         self.values["WS_SLAM-1"] = self.values["WS_SLAM"] - 1
+        self.values["WS_RELOC-1"] = self.values["WS_RELOC"] - 1
+        self.values["WS_POINTS-1"] = self.values["WS_POINTS"] - 1
+        assert 0 < self.values["WS_RELOC"] <= self.dev.numel() and 0 < self.values["WS_POINTS"] <= self.dev.numel()
         assert 0 < self.values["WS_SLAM"] <= self.dev.numel() and 0 < self.values["WS_RANGES"] <= self.dev.numel()
 
     def call(self, entry, over):
@@ -323,7 +476,7 @@ class Runner:
             args.insert(0, over.get("ctx", self.g._h if first == "ctx" else self.group))
         if over.get("failed_hip_call_first"):  # (the library's own HIP runtime, on this thread)
             assert self.raw.hipSetDevice(1 << 20) != 0
-        rc = getattr(self.raw if entry in MOVED else self.lib, entry)(*args)
+        rc = getattr(self.raw if entry in MOVED or entry in MATCHER else self.lib, entry)(*args)
         if over.get("failed_hip_call_first"):
             self.raw.hipGetLastError()  # (nothing of it is left for the next launch check of this thread)
         return {"code": int(rc), "text": self.lib.hsm_last_error().decode() if rc != 0 else ""}

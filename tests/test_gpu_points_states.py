@@ -18,7 +18,7 @@ tests/test_points_states_reference.py.
               on a busy caller's stream; and src after dst is closed.
               After an alignment src takes its next update without waiting on anything: hsm_align_map reads src on dst's
               stream, marks that stream pending in src's list (occupied_points_launch), waits for it on the host under src's
-              lock and clears the mark again (window.hip: fs->pending = false), so order_after_foreign_match finds nothing to
+              lock and clears the mark again (window.hip: reader.mark->pending = false), so order_after_foreign_match finds nothing to
               record an event for.  The extraction on a caller's stream leaves its mark set, and the next writer waits for it.
 
 Durations on the MI355X: the suite without this file 185 s, this file 4.4 s (69 ids, the longest 0.2 s).

@@ -2,7 +2,8 @@
 hsm_last_error() text the library answers with.
 
 The file pins the refusals of the scan-log, update and raw-scan entries across their rewrite onto argument bundles, and those of the
-probes, test hooks and group entries across their move out of the core translation unit (tests/test_gpu_host_refusals.py replays
+probes, test hooks and group entries across their move out of the core translation unit, and those of the batched match, score,
+covariance, window and ray entries across the matcher's rewrite onto bundles (tests/test_gpu_host_refusals.py replays
 the cases against the library under test).  It is recorded on the device from the commit BEFORE such a change, all cases at once
 -- the cases of an earlier recording come out again and must come out unchanged (`recorded_from` keeps the earlier revisions) --
 and never regenerated from the code under test: to record it again, check that commit out (or build its library and name it in
