@@ -104,6 +104,12 @@ SIGNATURES = {
     "hsm_occupancy_changes_device": (_i, [_vp, _i, _vp, _vp, _vp]),
     "hsm_occupancy_changes": (_i, [_vp, _i, _vp, _i32p]),
     "hsm_occupancy_restart": (_i, [_vp, _i]),
+    "hsm_map_extents_device": (_i, [_vp, _i, _vp, _vp]),
+    "hsm_map_extents": (_i, [_vp, _i, _i32p]),
+    "hsm_map_image_device": (_i, [_vp, _i, _vp, _vp, _vp]),
+    "hsm_map_image": (_i, [_vp, _i, _vp, _vp]),
+    "hsm_map_tiles_device": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp]),
+    "hsm_map_tiles": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _vp]),
     "hsm_ray_distances": (_i, [_vp, _i, _f, _f, _f, _i, _f32p, _f32p, _f32p, _f32p]),
     "hsm_ray_distances_device": (_i, [_vp, _i, _f, _f, _f, _i, _vp, _vp, _vp, _vp, _vp]),
     "hsm_cast_scans_device": (_i, [_vp, _i, _i, _vp, _vp, _i, _f, _vp, _vp, _vp]),
@@ -689,6 +695,63 @@ class MapRepMultiMap:
     def occupancy_restart(self, level=-1):
         """the next occupancy_changes* of ``level`` (-1: every level) exports the whole level"""
         _check(self._lib.hsm_occupancy_restart(self._h, level), "hsm_occupancy_restart")
+
+    # ---- known extents, the map image, pose tiles -------------------------------------------
+    def map_extents_device(self, level, d_out_box, stream=0):
+        """Raw device pointer (int): the inclusive hull x0,y0,x1,y1 of ``level``'s known cells into int32 [4] on the device,
+        0,0,-1,-1 without one.  No host wait."""
+        _check(self._lib.hsm_map_extents_device(self._h, level, d_out_box or None, stream or None), "hsm_map_extents_device")
+
+    def map_extents(self, level=0, half_open=False):
+        """GridMapBase::getMapExtends: int32 [4] x0,y0,x1,y1 inclusive, 0,0,-1,-1 without a known cell.  ``half_open``:
+        HectorMapTools::getMapExtends's topLeft / bottomRight, x0,y0,x1+1,y1+1, or None where it returns false."""
+        bb = np.empty(4, np.int32)
+        _check(self._lib.hsm_map_extents(self._h, level, bb), "hsm_map_extents")
+        if not half_open:
+            return bb
+        return None if bb[2] < bb[0] else bb + np.int32([0, 0, 1, 1])
+
+    def crop_box(self, level, crop=None):
+        """``crop`` (x0,y0,x1,y1 inclusive; None: the whole level) clamped to ``level`` as map_image* clamps it, or None where
+        it misses the level"""
+        sx, sy, _, _ = self.level_info(level)
+        if crop is None:
+            return 0, 0, sx - 1, sy - 1
+        x0, y0, x1, y1 = max(int(crop[0]), 0), max(int(crop[1]), 0), min(int(crop[2]), sx - 1), min(int(crop[3]), sy - 1)
+        return None if x1 < x0 or y1 < y0 else (x0, y0, x1, y1)
+
+    def map_image_device(self, level, crop, d_out, stream=0):
+        """Raw device pointer (int): the y-flipped byte image (free 255, occupied 0, unknown 127) of ``crop`` clamped to
+        ``level`` (``crop_box`` says how large it is) into device memory, queued on the context's stream."""
+        c = None if crop is None else np.ascontiguousarray(crop, np.int32).reshape(4)
+        _check(self._lib.hsm_map_image_device(self._h, level, None if c is None else c.ctypes.data, d_out or None, stream or None),
+               "hsm_map_image_device")
+
+    def map_image(self, level=0, crop=None):
+        """map_to_image_node's full image, or that of a cell box: uint8 [hgt, w], row 0 the box's top map row; (0, 0) where the
+        crop misses the level"""
+        box = self.crop_box(level, crop)
+        if box is None:
+            return np.zeros((0, 0), np.uint8)
+        out = np.empty((box[3] - box[1] + 1, box[2] - box[0] + 1), np.uint8)
+        c = np.asarray(box, np.int32)
+        _check(self._lib.hsm_map_image(self._h, level, c.ctypes.data, out.ctypes.data), "hsm_map_image")
+        return out
+
+    def map_tiles_device(self, level, batch, d_poses_world, tile_w, tile_h, d_out_tiles, d_out_boxes=0, stream=0):
+        """Raw device pointers (ints): one ``tile_w`` x ``tile_h`` window of the map image clamped around each of ``batch``
+        world poses [batch, 3]; ``d_out_boxes`` (int32 [batch, 4]) receives the windows' inclusive cell boxes.  No host wait."""
+        _check(self._lib.hsm_map_tiles_device(self._h, level, batch, d_poses_world or None, tile_w, tile_h, d_out_tiles or None,
+                                              d_out_boxes or None, stream or None), "hsm_map_tiles_device")
+
+    def map_tiles(self, level, poses_world, tile_w=64, tile_h=64):
+        """Host arrays: -> (tiles uint8 [B, tile_h, tile_w], boxes int32 [B, 4])"""
+        p = np.ascontiguousarray(poses_world, np.float32).reshape(-1, 3)
+        tiles = np.empty((p.shape[0], tile_h, tile_w), np.uint8)
+        boxes = np.empty((p.shape[0], 4), np.int32)
+        _check(self._lib.hsm_map_tiles(self._h, level, p.shape[0], _addr(p), tile_w, tile_h, _addr(tiles), _addr(boxes)),
+               "hsm_map_tiles")
+        return tiles, boxes
 
     # ---- batched extension ---------------------------------------------------------------
     def match_batch(self, begin_world, pts, offsets=None, want_cov=True):

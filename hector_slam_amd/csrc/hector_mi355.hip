@@ -358,6 +358,9 @@ int hsm_create(float map_resolution, int size_x, int size_y, unsigned levels, fl
     return HSM_ERR_HIP;
   }
 
+  CREATE_TRY(hipMalloc((void**)&h->occ.d_extents, 8 * sizeof(int)));  // (hsm_map_extents*: map_image_kernels.h kExtentsNone)
+  CREATE_TRY(hipMemsetAsync(h->occ.d_extents, 0x7f, 8 * sizeof(int), h->stream));
+
   // MapRepMultiMap ctor (MapRepMultiMap.h:48-72)
   int rx = size_x, ry = size_y;
   const float total_x = map_resolution * (float)size_x;
@@ -431,6 +434,7 @@ void hsm_destroy(hsm_ctx* h) {
   TEARDOWN(log, hipFree(h->single.d_partials));
   TEARDOWN(log, hipFree(h->upd.d_gate));
   TEARDOWN(log, hipFree(h->occ.d_pub_boxes));
+  TEARDOWN(log, hipFree(h->occ.d_extents));
   if (h->single.h_small) TEARDOWN(log, hipHostFree(h->single.h_small));
   for (hipEvent_t e : {h->single.copy_evt, h->order.evt_updates, h->order.evt_foreign, h->order.evt_inputs, h->order.evt_slam_done, h->upd.upd_evt[0], h->upd.upd_evt[1],
                        h->copy.evt_copy_read, h->copy.evt_copy_src})

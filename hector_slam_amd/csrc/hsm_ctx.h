@@ -13,7 +13,9 @@
 //                           behind them update_types.h, update_cell_rule.h, update_gate.h)  => upd
 //   ingest.hip              raw sensor data: the LaserScan / point-cloud conversions of one scan and of batches, in front of
 //                           the match, the update and the SLAM loop (ingest_kernels.h)  => ingest
-//   occupancy.hip           a level as the node's occupancy grid, whole or its changed cells only (occupancy_kernels.h)  => occ
+//   occupancy.hip           a level as the node's occupancy grid, whole or its changed cells only (occupancy_kernels.h), and as
+//                           what the map's consumers draw from: the hull of its known cells, a cell box as a y-flipped byte
+//                           image and windows of that image around batches of poses (map_image_kernels.h)  => occ
 //   probes.hip              the host-array probes (likelihood, covariance, Hessian), level downloads and uploads,
 //                           the hsm_debug_* test hooks, and the kernels only these launch (probe_kernels.h)  => d_cells
 //   rays.hip                what a laser would see on a level: ray distances of arrays of rays (host or device pointers) and
@@ -110,6 +112,19 @@ inline float level_factor(int l) { return (float)(1.0 / pow(2.0, (double)l)); }
 inline void affine_apply_host(const Affine2& a, float x, float y, float& ox, float& oy) {
   ox = a.t0 + (a.l00 * x + a.l01 * y);
   oy = a.t1 + (a.l10 * x + a.l11 * y);
+}
+
+// the level's own OccupancyGrid metadata, as the node publishes it (HectorMappingRos.cpp:546-553), in fp32: origin =
+// getWorldCoords(Vector2f::Zero()) - cell / 2 per axis, resolution = the cell length.  From the level's CURRENT transform: a
+// window move (hsm_shift_map) moves the origin.  What hsm_cast_scans* (rays.hip) and hsm_map_tiles* (occupancy.hip) locate poses by
+struct GridMetadata {
+  float origin_x, origin_y, resolution;
+};
+inline GridMetadata level_grid_metadata(const Level& L) {
+  float wx, wy;
+  affine_apply_host(L.worldTmap, 0.0f, 0.0f, wx, wy);
+  const float half = L.cell_length * 0.5f;
+  return {wx - half, wy - half, L.cell_length};
 }
 
 // Teardown never stops at a failing call (everything else still has to be released), but it must not swallow one either: HIP
@@ -411,6 +426,9 @@ struct hsm_ctx {
     // growing buffer replaces: the levels' publish boxes as device-side updates widen them (never fetched), the box of the export
     // that was queued last on each level (its convert launch reads it), and the whole level as a box (written by hsm_create)
     int* d_pub_boxes = nullptr;
+    // hsm_map_extents* (map_image_kernels.h): the four accumulators of the reduction, which every call leaves as it found them
+    // (filled by hsm_create), and behind them the four ints the host form fetches its box from
+    int* d_extents = nullptr;
   } occ{&bufs};
 
   // ---- map_copy.hip, map_shift.hip ----------------------------------------------------------------------------------------------

@@ -30,13 +30,10 @@ RayGrid ray_grid(const Level& L, float origin_x, float origin_y, float resolutio
   return G;
 }
 
-// the level's own OccupancyGrid metadata, as the node publishes it (HectorMappingRos.cpp:546-553): origin =
-// getWorldCoords(Vector2f::Zero()) - cell / 2 per axis, resolution = the cell length
+// ... on the level's own OccupancyGrid metadata (hsm_ctx.h level_grid_metadata)
 RayGrid level_ray_grid(const Level& L) {
-  float wx, wy;
-  affine_apply_host(L.worldTmap, 0.0f, 0.0f, wx, wy);
-  const float half = L.cell_length * 0.5f;
-  return ray_grid(L, wx - half, wy - half, L.cell_length);
+  const GridMetadata m = level_grid_metadata(L);
+  return ray_grid(L, m.origin_x, m.origin_y, m.resolution);
 }
 
 // Which walk a cast takes (ray_kernels.h): a lane per beam from 32 beams, a wavefront per beam for the shorter fans, which leave

@@ -360,6 +360,21 @@ inline OccupiedPointsStage occupied_points_stage(int max_points, size_t ws_bytes
   return s;
 }
 
+// hsm_map_tiles (d_batch): poses[batch * 3] | tiles[batch * tile bytes] | boxes[batch * 4].  Without the caller's array the boxes
+// are not carved and the kernel gets none.
+struct MapTilesStage {
+  StagePlan plan;
+  size_t poses, tiles, boxes;
+};
+
+inline MapTilesStage map_tiles_stage(int batch, size_t tile_bytes, const float* poses, unsigned char* out_tiles, int* out_boxes) {
+  MapTilesStage s;
+  s.poses = s.plan.add((size_t)batch * 3 * sizeof(float), poses);
+  s.tiles = s.plan.add((size_t)batch * tile_bytes, nullptr, out_tiles);
+  s.boxes = s.plan.add(out_boxes ? (size_t)batch * 4 * sizeof(int) : 0, nullptr, out_boxes);
+  return s;
+}
+
 // hsm_align_map (the destination's d_batch): the guess as the window's centre | points[max_points] | counts[2] | the
 // extraction's workspace | the relocalisation's workspace, whose k window indices are copied out where they lie (`kindex_at`
 // inside it) | candidate poses[k * 3] | candidate covariances[k * 9] | candidate likelihoods[k] | best pose, seeded with the guess

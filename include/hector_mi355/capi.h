@@ -1119,6 +1119,68 @@ int hsm_occupancy_changes(hsm_ctx* h, int level, signed char* grid, int bbox[4])
  * replaced its grid.  Host bookkeeping only, nothing is queued. */
 int hsm_occupancy_restart(hsm_ctx* h, int level);
 
+/* ---- what the map's other consumers draw from: known extents, the map image, pose tiles ------------------------------------
+ * One cell rule for the six entries below, publishMap's: a log-odds < 0 is free, > 0 occupied, anything else (+0, -0, NaN)
+ * unknown.  Image bytes are map_to_image_node's: free 255, occupied 0, unknown 127.  A cell is KNOWN when it is free or
+ * occupied.  On every plane without a NaN that is GridMapBase::getMapExtends's `getValue() != 0.0f`; a NaN cell is unknown here
+ * because the published grid says -1 for it (the reference's float test would call it known).  Everything is integer and
+ * comparison work: equal to the reference loops byte for byte and box for box.
+ * The three device entries follow hsm_occupancy_grid_device: the work runs on the context's stream, behind every update queued
+ * so far and in front of every later one; `stream` (the caller's, NULL = default stream) is waited for once in front and waits
+ * once behind; the host waits for nothing.  HSM_ERR_INVALID, nothing queued and no output touched: a NULL context, a level
+ * out of range, a NULL output where there is something to write, or `stream` / a stream this context has matched on is being
+ * captured into a graph.  None of the six touches the map, its stamps, the publish box of hsm_occupancy_changes* or the
+ * mirror's dirty box.
+ * Not built: capture into graphs, replay through hsm_group_*, a C++ facade entry, a crop box in device memory (extents ->
+ * image without the host learning the size), the GeoTIFF writer's Qt drawing, rotated tiles. */
+/* replaces: GridMapBase::getMapExtends (GridMapBase.h:334-383) and HectorMapTools::getMapExtends
+ *           (hector_map_tools/HectorMapTools.h:241-290; hector_geotiff's setupTransforms, geotiff_writer.cpp:129, crops
+ *           everything it draws to it): the bounding box of every known cell of `level`.
+ *   d_out_box  DEVICE, 4 ints: x0, y0, x1, y1, the INCLUSIVE hull -- GridMapBase's (xMin, yMin, xMax, yMax) -- or 0, 0, -1, -1
+ *              without a known cell, where the reference returns false.  HectorMapTools's topLeft / bottomRight are
+ *              (x0, y0) / (x1 + 1, y1 + 1).
+ * One pass over the plane (16-byte loads, minima and maxima folded per wavefront and workgroup, then integer atomic minima,
+ * which commute: the box does not depend on the launch shape) and one finishing launch of one thread, the only writer of
+ * d_out_box. */
+int hsm_map_extents_device(hsm_ctx* h, int level, int* d_out_box, void* stream);
+/* the same into HOST memory; synchronous: waits for the context's stream */
+int hsm_map_extents(hsm_ctx* h, int level, int box[4]);
+/* replaces: map_to_image_node's full image (hector_compressed_map_transport/src/map_to_image_node.cpp:98-140) with crop ==
+ *           NULL; with a crop to the extents, the cells the GeoTIFF writer draws from.
+ *   crop   HOST, 4 ints, an inclusive cell box x0, y0, x1, y1, or NULL = the whole level.  It is clamped to the level; with
+ *          the clamped box w = x1 - x0 + 1 and hgt = y1 - y0 + 1.  A crop that misses the level: HSM_OK, nothing written.
+ *   d_out  DEVICE, w * hgt bytes, any alignment: d_out[r * w + c] = byte(logodds[(y1 - r) * sx + x0 + c]) -- image row 0 is
+ *          the box's TOP map row.  No byte beyond w * hgt is touched. */
+int hsm_map_image_device(hsm_ctx* h, int level, const int crop[4], unsigned char* d_out, void* stream);
+/* the same into HOST memory (converted into the context's staging grid and copied); synchronous */
+int hsm_map_image(hsm_ctx* h, int level, const int crop[4], unsigned char* out);
+/* replaces: map_to_image_node's tile image (map_to_image_node.cpp:143-235; there one 64 x 64 window around the robot's pose)
+ *           for a batch of poses: local occupancy patches around matched poses or hypotheses.
+ *   d_poses_world  DEVICE [batch * 3] x, y, theta: the layout every batched entry writes.  theta is not read (the reference's
+ *                  tile is not rotated).
+ *   d_out_tiles    DEVICE [batch * tile_w * tile_h] bytes, any alignment, tiles contiguous:
+ *                  tile b, [r * tile_w + c] = byte(logodds[(hi_y - 1 - r) * sx + lo_x + c])
+ *   d_out_boxes    DEVICE [batch * 4] ints or NULL: lo_x, lo_y, hi_x - 1, hi_y - 1 of every tile
+ * Per pose and axis, the reference's arithmetic in its order (:147-193), on the level's OWN OccupancyGrid metadata computed once
+ * on the host in fp32 as for hsm_cast_scans_device, from the current map start (after hsm_shift_map too): origin =
+ * getWorldCoords(0,0) - cell * 0.5f, inv = 1.0f / cell length;
+ *   m = (int)((p - origin) * inv)  (fp32, un-fused, truncation toward zero);  lo = max(m - tile / 2, 0);  hi = lo + tile;
+ *   where hi > size: lo -= hi - size, hi = size;  lo = max(lo, 0).
+ * Where the reference is undefined: the map coordinate (p - origin) * inv of a finite p is clamped in float to +-2^30 in front
+ * of the conversion (the clamps then give the window on the level's edge); a non-finite x or y gives a tile of 127 throughout and
+ * the box 0, 0, -1, -1.
+ * One launch for the whole batch, straight from the log-odds plane (no grid of the level in between): a tile's row is a
+ * contiguous run of floats, read by 16-byte loads and written by packed 4-byte stores where the caller's memory is aligned, byte
+ * stores for the ragged ends; narrow tiles share a wavefront by rows, a large tile is shared by several wavefronts.
+ * HSM_ERR_INVALID besides the common refusals: batch < 0, tile_w < 1, tile_h < 1, tile_w > sx or tile_h > sy (the reference's
+ * shrunken tile on a map smaller than the window is not built), batch * tile_w * tile_h > INT_MAX, NULL poses or tiles where
+ * batch > 0.  batch == 0: HSM_OK, nothing queued. */
+int hsm_map_tiles_device(hsm_ctx* h, int level, int batch, const float* d_poses_world, int tile_w, int tile_h,
+                         unsigned char* d_out_tiles, int* d_out_boxes, void* stream);
+/* the same with HOST pointers: poses in, the kernel on the context's stream, tiles and boxes out; synchronous */
+int hsm_map_tiles(hsm_ctx* h, int level, int batch, const float* poses_world, int tile_w, int tile_h, unsigned char* out_tiles,
+                  int* out_boxes);
+
 /* ---- parity / debug entry points (used by tests, not by the facade) ------------ */
 /* device probability plane p = e^l/(e^l+1) (GridMapLogOdds.h:163-166) */
 int hsm_download_prob(hsm_ctx* h, int level, float* prob);
