@@ -129,6 +129,13 @@ SIGNATURES = {
     "hsm_relocalize_device": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "hsm_relocalize_workspace": (C.c_size_t, [_i, _i]),
     "hsm_relocalize": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "hsm_score_windows_batch_device": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "hsm_select_topk_groups_device": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "hsm_select_topk_groups_workspace": (C.c_size_t, [_i, _i, _i]),
+    "hsm_relocalize_batch_device": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp,
+                                         _vp, _vp, _vp]),
+    "hsm_relocalize_batch_workspace": (C.c_size_t, [_i, _i, _i, _i]),
+    "hsm_relocalize_batch": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "hsm_match_score_batch": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp]),
     "hsm_occupied_points_workspace": (C.c_size_t, [_i]),
     "hsm_occupied_points_device": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, C.c_size_t, _vp]),
@@ -1057,6 +1064,75 @@ class MapRepMultiMap:
                                         r["cand_cov"].ctypes.data if want_cov else None, r["cand_likelihood"].ctypes.data,
                                         r["best_pose"].ctypes.data, bs.ctypes.data, bi.ctypes.data), "hsm_relocalize")
         r.update(best_score=bs[0], best_index=int(bi[0]))
+        return r
+
+    # ---- a batch of scans, each in its own window of one shared shape (capi.h "relocalisation of a BATCH of scans") ----
+    @staticmethod
+    def select_topk_groups_workspace(groups, group_size, k) -> int:
+        return int(load_library().hsm_select_topk_groups_workspace(int(groups), int(group_size), int(k)))
+
+    @staticmethod
+    def relocalize_batch_workspace(batch, window_count, k, total_points) -> int:
+        return int(load_library().hsm_relocalize_batch_workspace(int(batch), int(window_count), int(k), int(total_points)))
+
+    def score_windows_batch_device(self, level, batch, d_centers, step, half, d_pts, d_offsets, shared_n, d_out_likelihood,
+                                   d_out_residual=0, stream=0):
+        """window b around centre b against scan b (CSR ``d_offsets``, or 0 and one scan of ``shared_n`` beams), one launch (device
+        pointers as ints; asynchronous on ``stream``)."""
+        st, hf = self._window(step, half)
+        _check(self._lib.hsm_score_windows_batch_device(self._h, level, batch, d_centers or None, st, hf, d_pts or None,
+                                                        d_offsets or None, shared_n, d_out_likelihood or None,
+                                                        d_out_residual or None, stream or None), "hsm_score_windows_batch_device")
+
+    def score_windows_batch(self, level, centers_world, step, half, pts, offsets=None):
+        """(likelihood [B, W], residual [B, W]); ``offsets`` None: one scan for every window.  Host arrays in and out, through
+        torch device buffers on the current stream, like score_batch."""
+        c = torch.as_tensor(np.ascontiguousarray(centers_world, np.float32).reshape(-1, 3)).cuda()
+        a, _, n = _pts(pts)
+        B, W = c.shape[0], self.window_count(half)
+        d_pts = torch.as_tensor(a).cuda()
+        d_offs = None if offsets is None else torch.as_tensor(np.ascontiguousarray(offsets, np.int32)).cuda()
+        out = torch.empty((2, B, max(W, 0)), dtype=torch.float32, device="cuda")
+        self.score_windows_batch_device(level, B, c.data_ptr() if B else 0, step, half, d_pts.data_ptr() if n else 0,
+                                        0 if d_offs is None else d_offs.data_ptr(), n if d_offs is None else 0, out[0].data_ptr(),
+                                        out[1].data_ptr(), torch.cuda.current_stream().cuda_stream)
+        lh, res = out.cpu().numpy()
+        return lh.copy(), res.copy()
+
+    def select_topk_groups_device(self, groups, group_size, d_scores, k, d_out_index, d_out_score, d_workspace, workspace_bytes,
+                                  stream=0):
+        _check(self._lib.hsm_select_topk_groups_device(self._h, groups, group_size, d_scores or None, k, d_out_index or None,
+                                                       d_out_score or None, d_workspace or None, workspace_bytes, stream or None),
+               "hsm_select_topk_groups_device")
+
+    def relocalize_batch_device(self, search_level, batch, d_centers, step, half, k, d_pts, d_offsets, shared_n, total_points,
+                                d_workspace, workspace_bytes, d_out_cand_pose, d_out_cand_cov, d_out_cand_likelihood,
+                                d_out_cand_index, d_out_best_pose, d_out_best_score, d_out_best_index, stream=0):
+        """hsm_relocalize_device for ``batch`` scans, scan b in the window around centre b, one call on ``stream`` (capi.h)."""
+        st, hf = self._window(step, half)
+        _check(self._lib.hsm_relocalize_batch_device(
+            self._h, search_level, batch, d_centers or None, st, hf, k, d_pts or None, d_offsets or None, shared_n, total_points,
+            d_workspace or None, workspace_bytes, d_out_cand_pose or None, d_out_cand_cov or None, d_out_cand_likelihood or None,
+            d_out_cand_index or None, d_out_best_pose or None, d_out_best_score or None, d_out_best_index or None,
+            stream or None), "hsm_relocalize_batch_device")
+
+    def relocalize_batch(self, search_level, centers_world, step, half, k, pts, offsets=None, want_cov=True):
+        """hsm_relocalize_batch: host arrays.  Returns a dict: cand_pose [B,k,3], cand_cov [B,k,9] or None, cand_likelihood [B,k],
+        cand_index [B,k], best_pose [B,3] (NaN without a winner), best_score [B], best_index [B] (window indices, -1 if none)."""
+        c = np.ascontiguousarray(centers_world, np.float32).reshape(-1, 3)
+        B = c.shape[0]
+        a, p, n = _pts(pts)
+        offs = None if offsets is None else np.ascontiguousarray(offsets, np.int32)
+        st, hf = self._window(step, half)
+        r = {"cand_pose": np.empty((B, k, 3), np.float32), "cand_cov": np.zeros((B, k, 9), np.float32) if want_cov else None,
+             "cand_likelihood": np.empty((B, k), np.float32), "cand_index": np.empty((B, k), np.int32),
+             "best_pose": np.full((B, 3), np.nan, np.float32), "best_score": np.empty(B, np.float32),
+             "best_index": np.empty(B, np.int32)}
+        _check(self._lib.hsm_relocalize_batch(
+            self._h, search_level, B, c.ctypes.data if B else None, st, hf, k, p, None if offs is None else offs.ctypes.data,
+            n if offs is None else 0, r["cand_pose"].ctypes.data, r["cand_cov"].ctypes.data if want_cov else None,
+            r["cand_likelihood"].ctypes.data, r["cand_index"].ctypes.data, r["best_pose"].ctypes.data,
+            r["best_score"].ctypes.data, r["best_index"].ctypes.data), "hsm_relocalize_batch")
         return r
 
     def match_score_batch(self, begin_world, pts, offsets=None, score_level=0, group_size=None, group_offsets=None, want_cov=True):

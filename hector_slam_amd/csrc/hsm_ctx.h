@@ -27,7 +27,8 @@
 //                           planes, the geometry re-derived for other start coordinates (map_shift_kernels.h; the plan:
 //                           map_shift_plan.h)
 //   window.hip              a window of poses around a centre scored on the device map, its K best, and the relocalisation chain
-//                           behind them (window_kernels.h; the window's arithmetic: window_grid.h); a level's occupied cells as
+//                           behind them, for one scan and for a batch of scans in a window each (window_kernels.h; the
+//                           window's arithmetic and the workspace layouts: window_grid.h); a level's occupied cells as
 //                           a point set (map_points_kernels.h) and, with both, another context's map aligned to this one
 //   group.hip               the multi-GPU group (hsm_group_*, hsm_shard_bounds): host code only, librccl opened on demand
 //   match_exact_cached.hip  the exact-order texel-cache batch forms (gn_match_exact.h: the headline kernel and its chain-wavefront forms)

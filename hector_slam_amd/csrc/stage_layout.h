@@ -345,6 +345,36 @@ inline RelocalizeStage relocalize_stage(int k, int n, size_t ws_bytes, const flo
   return s;
 }
 
+// hsm_relocalize_batch (d_batch): centre poses[batch * 3] | end points[total_pts] | offsets[batch + 1] (a CSR batch; not carved
+// for a shared scan) | the device call's workspace | candidate poses[batch * k * 3] | candidate covariances[batch * k * 9] |
+// candidate likelihoods[batch * k] | candidates' window indices[batch * k] | best poses[batch * 3] | best scores[batch] | best
+// indices[batch].  The covariances and the best poses go in and out, as hsm_relocalize's; the arrays the caller does not ask for
+// are not carved.
+struct RelocalizeBatchStage {
+  StagePlan plan;
+  size_t centers, pts, offs, ws, pose, cov, lh, cidx, bpose, bscore, bidx;
+};
+
+inline RelocalizeBatchStage relocalize_batch_stage(int batch, int k, size_t total_pts, size_t ws_bytes, const float* centers,
+                                                   const float* pts, const int* offsets, float* out_cand_pose, float* out_cand_cov,
+                                                   float* out_cand_lh, int* out_cand_index, float* out_best_pose,
+                                                   float* out_best_score, int* out_best_index) {
+  const size_t b = (size_t)batch * sizeof(float), bk = b * (size_t)k;
+  RelocalizeBatchStage s;
+  s.centers = s.plan.add(3 * b, centers);
+  s.pts = s.plan.add(total_pts * 2 * sizeof(float), pts);
+  s.offs = s.plan.add(offsets ? ((size_t)batch + 1) * sizeof(int) : 0, offsets);
+  s.ws = s.plan.add(ws_bytes);
+  s.pose = s.plan.add(3 * bk, nullptr, out_cand_pose);
+  s.cov = s.plan.add(out_cand_cov ? 9 * bk : 0, out_cand_cov, out_cand_cov);
+  s.lh = s.plan.add(bk, nullptr, out_cand_lh);
+  s.cidx = s.plan.add(out_cand_index ? bk : 0, nullptr, out_cand_index);
+  s.bpose = s.plan.add(3 * b, out_best_pose, out_best_pose);
+  s.bscore = s.plan.add(out_best_score ? b : 0, nullptr, out_best_score);
+  s.bidx = s.plan.add(b, nullptr, out_best_index);
+  return s;
+}
+
 // hsm_occupied_points (d_batch): points[max_points] | counts[2] | the device call's workspace.  Only the counts are copied out
 // by the plan: the entry copies the points the counts name once it has them, so that the caller's array is touched no further.
 struct OccupiedPointsStage {

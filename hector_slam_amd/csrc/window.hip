@@ -1,7 +1,9 @@
 // window.hip -- the entries of the C ABI (include/hector_mi355/capi.h) that search a window of poses around a centre on the
 // device-resident map: the likelihood of one scan at every pose of the window (hsm_score_window_device, hsm_score_window), window
 // indices as poses (hsm_window_poses_device), the K best of an array of scores (hsm_select_topk_device) and the chain
-// window score -> top K -> poses -> match -> score on level 0 -> winner (hsm_relocalize_device, hsm_relocalize).  The kernels are
+// window score -> top K -> poses -> match -> score on level 0 -> winner (hsm_relocalize_device, hsm_relocalize); and the same for
+// a batch of scans, each in its own window of one shared shape (hsm_score_windows_batch_device, hsm_select_topk_groups_device,
+// hsm_relocalize_batch_device, hsm_relocalize_batch): one launch per stage whatever the batch.  The kernels are
 // in window_kernels.h, the window's arithmetic and the workspace sizes in window_grid.h.  The scoring entries read the map like a
 // batched score and are ordered like one (MapReader of hsm_ctx.h); the chain's tail is match_chain_nolock of match.hip.
 // Also here, because the chain ends in the relocalisation: a level's occupied cells as a point set (hsm_occupied_points*, the
@@ -50,6 +52,19 @@ int window_refusals(const hsm_ctx* h, const float* d_center, const float step[3]
   return HSM_OK;
 }
 
+// A batch of B windows of W hypotheses each: the lane form's floor is still one lane's walk over one scan, the wave form grows
+// with B * W -- so the rule is the single window's, on B * W.  Measured (profiles/r30/, 1081-beam scans, level 2 of the 2048^2
+// pyramid, lane against wave, B * W hypotheses): 1 089: 137 against 18 us, 8 712: 139 against 31, 33 800: 140 against 82, 69 696:
+// 145 against 150, 270 400: 247 against 536, 557 568: 434 against 1 118, 2 163 200: 1 277 against 4 225.  The wave form grows by
+// 1.9 us per 1000 hypotheses from 17 us and meets the lane form's floor (137-145 us) near 65 000: the single window's constant
+// is the batch's too.
+constexpr long long kWindowBatchLaneMin = kWindowLaneMin;
+
+bool window_batch_lane_form(const hsm_ctx* h, long long BW) {
+  if (h->cfg.forms.window_form >= 0) return h->cfg.forms.window_form == 1;
+  return BW >= kWindowBatchLaneMin;
+}
+
 WindowGrid window_grid(const float step[3], const int half[3]) { return WindowGrid{half[0], half[1], half[2], step[0], step[1], step[2]}; }
 
 int score_window_refusals(const hsm_ctx* h, int level, const float* d_center, const float step[3], const int half[3],
@@ -90,22 +105,80 @@ int score_window_launch(hsm_ctx* h, int level, const float* d_center, const Wind
   return HSM_OK;
 }
 
-int window_poses_launch(const WindowGrid& G, int W, const float* d_center, const int* d_index, int count, float* d_out_pose,
-                        hipStream_t s) {
-  hipLaunchKernelGGL(window_poses_kernel, dim3((unsigned)(((long long)count + 255) / 256)), dim3(256), 0, s, G, W, d_center, d_index,
-                     count, d_out_pose);
+// the scans of a batched window entry: ScanBatch without poses
+struct WindowScans {
+  const float* d_pts;
+  const int* d_offsets;
+  int shared_n;
+  ScanBatch of(int batch) const { return {batch, nullptr, d_pts, d_offsets, shared_n}; }
+};
+
+// what the batched entries refuse on top of window_refusals: the batch's own shape.  *BW: batch * W
+int window_batch_refusals(int batch, long long W, const float* d_centers, const WindowScans& S, const char* who, long long* BW) {
+  if (batch < 0) return fail_at(HSM_ERR_INVALID, who, ": batch < 0");
+  *BW = (long long)batch * W;
+  if (*BW > (long long)INT_MAX) return fail_at(HSM_ERR_INVALID, who, ": more than INT_MAX hypotheses in all");
+  if (batch > 0 && !d_centers) return fail_at(HSM_ERR_INVALID, who, ": null centres");
+  if (S.of(batch).bad_shape() || S.of(batch).points_missing()) return fail_at(HSM_ERR_INVALID, who, ": bad scans");
+  return HSM_OK;
+}
+
+// one kernel on `s` for `batch` >= 1 windows of W hypotheses; arguments checked, device selected, lock held
+int score_windows_batch_launch(hsm_ctx* h, int level, int batch, const float* d_centers, const WindowGrid& G, int W,
+                               const WindowScans& S, float* d_out_lh, float* d_out_res, hipStream_t s) {
+  MapReader reader;
+  if (int rc = reader.begin(h, s, "hsm_score_windows_batch_device")) return rc;
+  const LevelView v = level_view(h->levels[level], level_factor(level), 1);
+  WindowBatchParams P;
+  P.grid = G;
+  P.centers = d_centers;
+  P.batch = batch;
+  P.count = W;
+  P.pts = reinterpret_cast<const float2*>(S.d_pts);
+  P.offsets = S.d_offsets;
+  P.shared_n = S.d_offsets ? 0 : S.shared_n;
+  P.out_lh = d_out_lh;
+  P.out_residual = d_out_res;
+  const bool lane = window_batch_lane_form(h, (long long)batch * W);
+  // lane form: every window padded to whole wavefronts; either form: four wavefronts per workgroup
+  const long long waves = lane ? (long long)batch * (((long long)W + 63) / 64) : (long long)batch * W;
+  const unsigned grid = (unsigned)((waves + 3) / 4);
+  if (h->cfg.layout == kLayoutPlane) {
+    if (lane) hipLaunchKernelGGL((score_windows_batch_lane_kernel<kLayoutPlane>), dim3(grid), dim3(256), 0, s, v, P);
+    else hipLaunchKernelGGL((score_windows_batch_wave_kernel<kLayoutPlane>), dim3(grid), dim3(256), 0, s, v, P);
+  } else {
+    if (lane) hipLaunchKernelGGL((score_windows_batch_lane_kernel<kLayoutQuad>), dim3(grid), dim3(256), 0, s, v, P);
+    else hipLaunchKernelGGL((score_windows_batch_wave_kernel<kLayoutQuad>), dim3(grid), dim3(256), 0, s, v, P);
+  }
+  HIP_TRY(hipGetLastError());
+  reader.queued();
+  h->last.last_kernel = lane ? "score_windows_batch_lane_kernel" : "score_windows_batch_wave_kernel";
+  h->last.last_parity = HSM_PARITY_EXACT;
+  return HSM_OK;
+}
+
+// `count` indices of windows of W hypotheses, `per_window` of them in a row for each centre
+int window_poses_launch(const WindowGrid& G, int W, const float* d_centers, const int* d_index, int count, int per_window,
+                        float* d_out_pose, hipStream_t s) {
+  hipLaunchKernelGGL(window_poses_kernel, dim3((unsigned)(((long long)count + 255) / 256)), dim3(256), 0, s, G, W, d_centers, d_index,
+                     count, per_window, d_out_pose);
   HIP_TRY(hipGetLastError());
   return HSM_OK;
 }
 
-int select_topk_launch(int count, const float* d_scores, int k, int* d_out_index, float* d_out_score, void* d_workspace,
+// the K best of each of `groups` >= 1 runs of `count` scores: two launches; one group: hsm_select_topk_device
+int select_topk_launch(int groups, int count, const float* d_scores, int k, int* d_out_index, float* d_out_score, void* d_workspace,
                        hipStream_t s) {
   const int slices = topk_slices(count);
-  float* cand_score = static_cast<float*>(d_workspace);
-  int* cand_index = reinterpret_cast<int*>(cand_score + (size_t)slices * k);
-  hipLaunchKernelGGL(topk_slice_kernel, dim3((slices + 3) / 4), dim3(256), 0, s, d_scores, count, k, slices, cand_score, cand_index);
+  const TopKGroupsLayout L = topk_groups_layout(groups, count, k);
+  float* cand_score = reinterpret_cast<float*>(static_cast<char*>(d_workspace) + L.cand_score);
+  int* cand_index = reinterpret_cast<int*>(static_cast<char*>(d_workspace) + L.cand_index);
+  const long long waves = (long long)groups * slices;
+  hipLaunchKernelGGL(topk_slice_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, d_scores, count, k, slices, groups,
+                     cand_score, cand_index);
   HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(topk_merge_kernel, dim3(1), dim3(256), 0, s, cand_score, cand_index, slices * k, k, d_out_index, d_out_score);
+  hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)groups), dim3(256), 0, s, cand_score, cand_index, slices * k, k, d_out_index,
+                     d_out_score);
   HIP_TRY(hipGetLastError());
   return HSM_OK;
 }
@@ -114,6 +187,20 @@ int select_topk_refusals(int count, const void* scores, int k, const void* out_i
   if (count < 0 || k < 1 || k > HSM_MAX_TOPK || !out_index || (count > 0 && !scores) || !ws ||
       ws_bytes < topk_workspace_bytes(count, k) || ((size_t)ws & 3))
     return fail(HSM_ERR_INVALID, "hsm_select_topk_device: bad argument");
+  return HSM_OK;
+}
+
+// (no groups: nothing to select, and nothing but the counts and k is looked at)
+int select_topk_groups_refusals(int groups, int group_size, const void* scores, int k, const void* out_index, const void* ws,
+                                size_t ws_bytes) {
+  const char* who = "hsm_select_topk_groups_device";
+  if (groups < 0 || group_size < 0 || k < 1 || k > HSM_MAX_TOPK) return fail_at(HSM_ERR_INVALID, who, ": bad counts or k");
+  if ((long long)groups * group_size > (long long)INT_MAX || (long long)groups * k > (long long)INT_MAX)
+    return fail_at(HSM_ERR_INVALID, who, ": more than INT_MAX scores or places");
+  if (groups == 0) return HSM_OK;
+  if (!out_index || (group_size > 0 && !scores)) return fail_at(HSM_ERR_INVALID, who, ": null scores or indices");
+  if (!ws || ((size_t)ws & 3) || ws_bytes < topk_groups_workspace_bytes(groups, group_size, k))
+    return fail_at(HSM_ERR_INVALID, who, ": workspace missing, misaligned or too small");
   return HSM_OK;
 }
 
@@ -137,13 +224,70 @@ int relocalize_queue(hsm_ctx* h, int search_level, const float* d_center, const 
   float* kscore = reinterpret_cast<float*>(ws + L.kscore);
   float* kpose = reinterpret_cast<float*>(ws + L.pose);
   if (int rc = score_window_launch(h, search_level, d_center, G, W, d_pts, n, scores, nullptr, s)) return rc;
-  if (int rc = select_topk_launch(W, scores, k, kindex, kscore, ws + L.topk, s)) return rc;
-  if (int rc = window_poses_launch(G, W, d_center, kindex, k, kpose, s)) return rc;
+  if (int rc = select_topk_launch(1, W, scores, k, kindex, kscore, ws + L.topk, s)) return rc;
+  if (int rc = window_poses_launch(G, W, d_center, kindex, k, k, kpose, s)) return rc;
   // the k starts against the one scan: match, the likelihood on level 0, the winner of the one group of k
   if (int rc = match_chain_nolock(h, {k, kpose, d_pts, nullptr, n}, {d_cand_pose, d_cand_cov}, {0, {d_cand_lh}},
                                   {1, nullptr, k, d_best_index, d_best_score, d_best_pose}, s))
     return rc;
-  hipLaunchKernelGGL(window_best_index_kernel, dim3(1), dim3(64), 0, s, kindex, k, d_best_index);
+  hipLaunchKernelGGL(window_best_index_kernel, dim3(1), dim3(256), 0, s, kindex, k, 1, d_best_index);
+  HIP_TRY(hipGetLastError());
+  return HSM_OK;
+}
+
+// ---- the chain for a batch of scans, each in its own window -----------------------------------------------------------------
+// the outputs of hsm_relocalize_batch*: device pointers for the device entry, host pointers in the host entry's refusals
+struct RelocalizeBatchOut {
+  float *cand_pose, *cand_cov, *cand_lh;
+  int* cand_index;
+  float *best_pose, *best_score;
+  int* best_index;
+};
+
+int relocalize_batch_refusals(const hsm_ctx* h, int search_level, int batch, const float* d_centers, const float step[3],
+                              const int half[3], int k, const WindowScans& S, long long total_points, const RelocalizeBatchOut& O,
+                              const char* who, long long* W) {
+  if (int rc = valid_level(h, search_level)) return rc;
+  static const float kAnyCentre[3] = {0.0f, 0.0f, 0.0f};  // (a batch of none may come without centres)
+  if (int rc = window_refusals(h, batch > 0 ? d_centers : kAnyCentre, step, half, who, W)) return rc;
+  long long BW = 0;
+  if (int rc = window_batch_refusals(batch, *W, d_centers, S, who, &BW)) return rc;
+  if (k < 1 || k > HSM_MAX_TOPK || (long long)batch * k > (long long)(INT_MAX / 9))
+    return fail_at(HSM_ERR_INVALID, who, ": k out of range, or more than INT_MAX / 9 candidates");
+  if (!O.cand_pose || !O.cand_lh || !O.best_pose || !O.best_index) return fail_at(HSM_ERR_INVALID, who, ": null output");
+  if (S.d_offsets && (total_points < 0 || total_points * k > (long long)INT_MAX))
+    return fail_at(HSM_ERR_INVALID, who, ": total_points negative, or k copies of the scans hold more than INT_MAX points");
+  return HSM_OK;
+}
+
+// the chain on `s` for batch >= 1; arguments checked, device selected, lock held
+int relocalize_batch_queue(hsm_ctx* h, int search_level, int batch, const float* d_centers, const WindowGrid& G, int W, int k,
+                           const WindowScans& S, int total_points, char* ws, const RelocalizeBatchOut& O, hipStream_t s) {
+  const RelocalizeBatchLayout L = relocalize_batch_layout(batch, W, k, S.d_offsets ? total_points : 0);
+  const int cands = batch * k;
+  float* scores = reinterpret_cast<float*>(ws + L.scores);
+  int* kindex = O.cand_index ? O.cand_index : reinterpret_cast<int*>(ws + L.index);
+  float* kscore = reinterpret_cast<float*>(ws + L.kscore);
+  float* kpose = reinterpret_cast<float*>(ws + L.pose);
+  if (int rc = score_windows_batch_launch(h, search_level, batch, d_centers, G, W, S, scores, nullptr, s)) return rc;
+  if (int rc = select_topk_launch(batch, W, scores, k, kindex, kscore, ws + L.topk, s)) return rc;
+  if (int rc = window_poses_launch(G, W, d_centers, kindex, cands, k, kpose, s)) return rc;
+  // the batch * k starts, candidate (b, r) against scan b: a shared scan as it is; CSR scans laid out k times, since the matcher
+  // takes one scan per pair.  Its sizing hint: the mean length
+  ScanBatch pairs{cands, kpose, S.d_pts, nullptr, S.shared_n};
+  if (S.d_offsets) {
+    int* koffsets = reinterpret_cast<int*>(ws + L.offsets);
+    float2* kpts = reinterpret_cast<float2*>(ws + L.pts);
+    hipLaunchKernelGGL(replicate_scans_kernel, dim3((unsigned)cands), dim3(256), 0, s, reinterpret_cast<const float2*>(S.d_pts),
+                       S.d_offsets, batch, k, total_points, kpts, koffsets);
+    HIP_TRY(hipGetLastError());
+    pairs = ScanBatch{cands, kpose, reinterpret_cast<const float*>(kpts), koffsets, (total_points + batch - 1) / batch};
+  }
+  if (int rc = match_chain_nolock(h, pairs, {O.cand_pose, O.cand_cov}, {0, {O.cand_lh}},
+                                  {batch, nullptr, k, O.best_index, O.best_score, O.best_pose}, s))
+    return rc;
+  hipLaunchKernelGGL(window_best_index_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, s, kindex, cands, batch,
+                     O.best_index);
   HIP_TRY(hipGetLastError());
   return HSM_OK;
 }
@@ -248,7 +392,7 @@ int hsm_window_poses_device(hsm_ctx* h, const float* d_center_world, const float
   if (count == 0) return HSM_OK;
   std::lock_guard<std::mutex> lk(h->mu);
   if (int rc = select_device(h)) return rc;
-  return window_poses_launch(window_grid(step, half), (int)W, d_center_world, d_index, count, d_out_pose,
+  return window_poses_launch(window_grid(step, half), (int)W, d_center_world, d_index, count, count, d_out_pose,
                              static_cast<hipStream_t>(stream));
 }
 
@@ -258,7 +402,40 @@ int hsm_select_topk_device(hsm_ctx* h, int count, const float* d_scores, int k, 
   if (int rc = select_topk_refusals(count, d_scores, k, d_out_index, d_workspace, workspace_bytes)) return rc;
   std::lock_guard<std::mutex> lk(h->mu);
   if (int rc = select_device(h)) return rc;
-  return select_topk_launch(count, d_scores, k, d_out_index, d_out_score, d_workspace, static_cast<hipStream_t>(stream));
+  return select_topk_launch(1, count, d_scores, k, d_out_index, d_out_score, d_workspace, static_cast<hipStream_t>(stream));
+}
+
+size_t hsm_select_topk_groups_workspace(int groups, int group_size, int k) {
+  return topk_groups_workspace_bytes(groups, group_size, k);
+}
+
+int hsm_select_topk_groups_device(hsm_ctx* h, int groups, int group_size, const float* d_scores, int k, int* d_out_index,
+                                  float* d_out_score, void* d_workspace, size_t workspace_bytes, void* stream) {
+  if (!h) return fail(HSM_ERR_INVALID, "null context");
+  if (int rc = select_topk_groups_refusals(groups, group_size, d_scores, k, d_out_index, d_workspace, workspace_bytes)) return rc;
+  if (groups == 0) return HSM_OK;
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (int rc = select_device(h)) return rc;
+  return select_topk_launch(groups, group_size, d_scores, k, d_out_index, d_out_score, d_workspace, static_cast<hipStream_t>(stream));
+}
+
+int hsm_score_windows_batch_device(hsm_ctx* h, int level, int batch, const float* d_centers_world, const float step[3],
+                                   const int half[3], const float* d_pts_xy, const int* d_scan_offsets, int shared_n,
+                                   float* d_out_likelihood, float* d_out_residual, void* stream) {
+  const char* who = "hsm_score_windows_batch_device";
+  if (!h) return fail(HSM_ERR_INVALID, "null context");
+  if (int rc = valid_level(h, level)) return rc;
+  static const float kAnyCentre[3] = {0.0f, 0.0f, 0.0f};  // (a batch of none may come without centres)
+  long long W = 0, BW = 0;
+  if (int rc = window_refusals(h, batch > 0 ? d_centers_world : kAnyCentre, step, half, who, &W)) return rc;
+  const WindowScans S{d_pts_xy, d_scan_offsets, shared_n};
+  if (int rc = window_batch_refusals(batch, W, d_centers_world, S, who, &BW)) return rc;
+  if (!d_out_likelihood && !d_out_residual) return fail_at(HSM_ERR_INVALID, who, ": both outputs are null");
+  if (batch == 0) return HSM_OK;
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (int rc = select_device(h)) return rc;
+  return score_windows_batch_launch(h, level, batch, d_centers_world, window_grid(step, half), (int)W, S, d_out_likelihood,
+                                    d_out_residual, static_cast<hipStream_t>(stream));
 }
 
 int hsm_relocalize_device(hsm_ctx* h, int search_level, const float* d_center_world, const float step[3], const int half[3], int k,
@@ -298,6 +475,74 @@ int hsm_relocalize(hsm_ctx* h, int search_level, const float center_world[3], co
                                 staged<float>(base, st.pts), n, base + st.ws, staged<float>(base, st.pose),
                                 staged<float>(base, st.cov, out_cand_cov), staged<float>(base, st.lh), staged<float>(base, st.bpose),
                                 staged<float>(base, st.bscore, out_best_score), staged<int>(base, st.bidx), h->stream))
+    return rc;
+  if (int rc = stage_copy_out(st.plan, base, h->stream)) return rc;
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return HSM_OK;
+}
+
+size_t hsm_relocalize_batch_workspace(int batch, int window_count, int k, int total_points) {
+  return relocalize_batch_layout(batch, window_count, k, total_points).total;
+}
+
+int hsm_relocalize_batch_device(hsm_ctx* h, int search_level, int batch, const float* d_centers_world, const float step[3],
+                                const int half[3], int k, const float* d_pts_xy, const int* d_scan_offsets, int shared_n,
+                                int total_points, void* d_workspace, size_t workspace_bytes, float* d_out_cand_pose,
+                                float* d_out_cand_cov, float* d_out_cand_likelihood, int* d_out_cand_index, float* d_out_best_pose,
+                                float* d_out_best_score, int* d_out_best_index, void* stream) {
+  const char* who = "hsm_relocalize_batch_device";
+  if (!h) return fail(HSM_ERR_INVALID, "null context");
+  const WindowScans S{d_pts_xy, d_scan_offsets, shared_n};
+  const RelocalizeBatchOut O{d_out_cand_pose, d_out_cand_cov, d_out_cand_likelihood, d_out_cand_index,
+                             d_out_best_pose, d_out_best_score,  d_out_best_index};
+  long long W = 0;
+  if (int rc = relocalize_batch_refusals(h, search_level, batch, d_centers_world, step, half, k, S, total_points, O, who, &W)) return rc;
+  const size_t need = relocalize_batch_layout(batch, W, k, d_scan_offsets ? total_points : 0).total;
+  if (!d_workspace || ((size_t)d_workspace & 7) || need == 0 || workspace_bytes < need)
+    return fail_at(HSM_ERR_INVALID, who, ": workspace missing, misaligned or too small");
+  if (batch == 0) return HSM_OK;
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (int rc = select_device(h)) return rc;
+  return relocalize_batch_queue(h, search_level, batch, d_centers_world, window_grid(step, half), (int)W, k, S, total_points,
+                                static_cast<char*>(d_workspace), O, static_cast<hipStream_t>(stream));
+}
+
+int hsm_relocalize_batch(hsm_ctx* h, int search_level, int batch, const float* centers_world, const float step[3], const int half[3],
+                         int k, const float* pts_xy, const int* scan_offsets, int shared_n, float* out_cand_pose,
+                         float* out_cand_cov, float* out_cand_likelihood, int* out_cand_index, float* out_best_pose,
+                         float* out_best_score, int* out_best_index) {
+  const char* who = "hsm_relocalize_batch";
+  if (!h) return fail(HSM_ERR_INVALID, "null context");
+  // (host offsets: they start at 0 and do not decrease, and their last entry is the number of points)
+  long long total = 0;
+  if (scan_offsets && batch > 0) {
+    if (scan_offsets[0] != 0) return fail_at(HSM_ERR_INVALID, who, ": scan_offsets[0] != 0");
+    for (int b = 0; b < batch; ++b)
+      if (scan_offsets[b + 1] < scan_offsets[b]) return fail_at(HSM_ERR_INVALID, who, ": scan_offsets decrease");
+    total = scan_offsets[batch];
+  }
+  if (total > 0 && !pts_xy) return fail_at(HSM_ERR_INVALID, who, ": null points");
+  const WindowScans S{pts_xy, scan_offsets, shared_n};
+  const RelocalizeBatchOut O{out_cand_pose, out_cand_cov, out_cand_likelihood, out_cand_index, out_best_pose, out_best_score, out_best_index};
+  long long W = 0;
+  if (int rc = relocalize_batch_refusals(h, search_level, batch, centers_world, step, half, k, S, total, O, who, &W)) return rc;
+  if (batch == 0) return HSM_OK;
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (int rc = select_device(h)) return rc;
+  const size_t points = scan_offsets ? (size_t)total : (size_t)shared_n;
+  const RelocalizeBatchStage st =
+      relocalize_batch_stage(batch, k, points, relocalize_batch_layout(batch, W, k, total).total, centers_world, pts_xy, scan_offsets,
+                             out_cand_pose, out_cand_cov, out_cand_likelihood, out_cand_index, out_best_pose, out_best_score,
+                             out_best_index);
+  if (int rc = h->d_batch.reserve(st.plan.total())) return rc;
+  char* base = h->d_batch;
+  if (int rc = stage_copy_in(st.plan, base, h->stream)) return rc;
+  const WindowScans DS{staged<float>(base, st.pts), staged<int>(base, st.offs, scan_offsets), shared_n};
+  const RelocalizeBatchOut DO{staged<float>(base, st.pose), staged<float>(base, st.cov, out_cand_cov), staged<float>(base, st.lh),
+                              staged<int>(base, st.cidx, out_cand_index), staged<float>(base, st.bpose),
+                              staged<float>(base, st.bscore, out_best_score), staged<int>(base, st.bidx)};
+  if (int rc = relocalize_batch_queue(h, search_level, batch, staged<float>(base, st.centers), window_grid(step, half), (int)W, k, DS,
+                                      (int)total, base + st.ws, DO, h->stream))
     return rc;
   if (int rc = stage_copy_out(st.plan, base, h->stream)) return rc;
   HIP_TRY(hipStreamSynchronize(h->stream));

@@ -1,8 +1,8 @@
 // window_grid.h -- a window of pose hypotheses around a centre (window.hip, window_kernels.h), stated once: how many hypotheses a
 // window holds, which (i, j, k) a window index stands for, and the fp32 pose of a hypothesis; and the bytes of the caller-owned
-// workspaces of the top-K selection and of hsm_relocalize_device.
-// Plain C++ (no HIP header): the kernels and the host compile the same text, and tests/cpp/window_grid_check.cpp prints it with
-// the host compiler alone (tests/test_window_model.py).
+// workspaces of the top-K selection and of hsm_relocalize_device, single and batched.
+// Plain C++ (no HIP header): the kernels and the host compile the same text, and tests/cpp/window_grid_check.cpp and
+// relocalize_batch_check.cpp print it with the host compiler alone (tests/test_window_model.py, test_relocalize_batch_abi.py).
 #pragma once
 #include <limits.h>
 #include <stddef.h>
@@ -76,6 +76,28 @@ inline size_t topk_workspace_bytes(int count, int k) {
   return round_up8((size_t)topk_slices(count) * (size_t)k * (sizeof(float) + sizeof(int)));
 }
 
+// hsm_select_topk_groups_device: the K best of each of `groups` runs of `group_size` scores.  Every group is sliced like a single
+// array of group_size scores; the candidates lie group after group, all the scores, then all the indices.  One group: the bytes
+// and the layout of topk_workspace_bytes.  0 for refused sizes (a negative count, k out of range, more than INT_MAX scores or
+// places in all) and for no groups
+struct TopKGroupsLayout {
+  size_t cand_score, cand_index, total;
+};
+inline TopKGroupsLayout topk_groups_layout(long long groups, long long group_size, int k) {
+  TopKGroupsLayout L = {0, 0, 0};
+  if (groups < 0 || group_size < 0 || k < 1 || k > kMaxTopK) return L;
+  if (groups > (long long)INT_MAX || group_size > (long long)INT_MAX || groups * group_size > (long long)INT_MAX ||
+      groups * k > (long long)INT_MAX)
+    return L;
+  const size_t cands = (size_t)groups * (size_t)topk_slices((int)group_size) * (size_t)k;
+  L.cand_index = cands * sizeof(float);
+  L.total = round_up8(cands * (sizeof(float) + sizeof(int)));
+  return L;
+}
+inline size_t topk_groups_workspace_bytes(long long groups, long long group_size, int k) {
+  return topk_groups_layout(groups, group_size, k).total;
+}
+
 // hsm_relocalize_device: the W scores, the top-K candidates, K indices, K scores and K start poses, each region 8-byte aligned
 struct RelocalizeLayout {
   size_t scores, topk, index, kscore, pose, total;
@@ -89,6 +111,32 @@ inline RelocalizeLayout relocalize_layout(long long W, int k) {
   L.kscore = L.index + round_up8((size_t)k * sizeof(int));
   L.pose = L.kscore + round_up8((size_t)k * sizeof(float));
   L.total = L.pose + round_up8((size_t)k * 3 * sizeof(float));
+  return L;
+}
+
+// hsm_relocalize_batch_device, B scans with a window of W hypotheses each: the B*W scores, the grouped top-K candidates, B*K
+// indices, B*K scores, B*K start poses, and -- CSR scans -- every scan laid out K times for the matcher, which takes one scan per
+// pair: B*K + 1 offsets and max(K * total_points, 1) end points (one element at least: the matcher clamps an empty scan's loads to
+// element 0).  A shared scan is not copied: its caller passes total_points = 0.  Each region 8-byte aligned.  A total of 0: sizes
+// the entry refuses (B < 0, W < 1, k out of range, total_points < 0, B*W or K*total_points above INT_MAX, B*K above INT_MAX / 9)
+struct RelocalizeBatchLayout {
+  size_t scores, topk, index, kscore, pose, offsets, pts, total;
+};
+inline RelocalizeBatchLayout relocalize_batch_layout(long long B, long long W, int k, long long total_points) {
+  RelocalizeBatchLayout L = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (B < 0 || W < 1 || W > (long long)INT_MAX || k < 1 || k > kMaxTopK || total_points < 0) return L;
+  if (B > (long long)INT_MAX || B * W > (long long)INT_MAX || B * k > (long long)(INT_MAX / 9) ||
+      total_points > (long long)INT_MAX || total_points * k > (long long)INT_MAX)
+    return L;
+  const size_t bk = (size_t)B * (size_t)k, copied = (size_t)total_points * (size_t)k;
+  L.scores = 0;
+  L.topk = round_up8((size_t)B * (size_t)W * sizeof(float));
+  L.index = L.topk + topk_groups_workspace_bytes(B, W, k);
+  L.kscore = L.index + round_up8(bk * sizeof(int));
+  L.pose = L.kscore + round_up8(bk * sizeof(float));
+  L.offsets = L.pose + round_up8(bk * 3 * sizeof(float));
+  L.pts = L.offsets + round_up8((bk + 1) * sizeof(int));
+  L.total = L.pts + (copied > 0 ? copied : 1) * 2 * sizeof(float);
   return L;
 }
 

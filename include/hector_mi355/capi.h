@@ -906,8 +906,8 @@ int hsm_covariance_batch(hsm_ctx* h, int level, int batch, const float* poses_wo
  * needs no workspace, keeps no state, one kernel node under capture.
  * HSM_ERR_INVALID (nothing launched): NULL context, level out of range, a negative half-extent, W > INT_MAX, a non-finite step,
  * n < 0, both outputs NULL, NULL centre, steps or half-extents, NULL points where n > 0.
- * Not built: replay through hsm_group_*, a C++ facade entry, non-maximum suppression among candidates, a window per scan of a
- * batch of different scans. */
+ * Not built: replay through hsm_group_*, a C++ facade entry, non-maximum suppression among candidates.  (A window per scan of a
+ * batch of different scans: hsm_score_windows_batch_device below.) */
 #define HSM_MAX_TOPK 64
 int hsm_score_window_device(hsm_ctx* h, int level, const float* d_center_world, const float step[3], const int half[3],
                             const float* d_pts_xy, int n, float* d_out_likelihood, float* d_out_residual, void* stream);
@@ -959,6 +959,84 @@ size_t hsm_relocalize_workspace(int window_count, int k);
 int hsm_relocalize(hsm_ctx* h, int search_level, const float center_world[3], const float step[3], const int half[3], int k,
                    const float* pts_xy, int n, float* out_cand_pose, float* out_cand_cov, float* out_cand_likelihood,
                    float* out_best_pose, float* out_best_score, int* out_best_index);
+
+/* ---- relocalisation of a BATCH of scans, each in its own window of one shared shape (extension, as above: several matches that
+ * left their basin at once, or a loop-closure search over old scans, against one map) ----
+ * The windows share the HOST steps step[3] and half-extents half[3], so each holds the same W hypotheses; window b lies around
+ * the DEVICE centre d_centers_world[3b ..] and is scored against scan b.  The scans are the pair the other batched entries take:
+ * d_pts_xy with d_scan_offsets [batch + 1] (CSR, in points; they start at 0 and do not decrease), or d_scan_offsets == NULL and
+ * ONE scan of shared_n beams for every window (with offsets shared_n is the matcher's sizing hint in hsm_match_batch_device and
+ * is not looked at here).
+ *
+ * hsm_score_windows_batch_device
+ * replaces: batch calls of hsm_score_window_device, window b and scan b, in ONE kernel launch.  d_out_likelihood [batch * W] /
+ *           d_out_residual [batch * W], window b at [b * W, (b + 1) * W): either may be NULL, not both; the same bits as the
+ *           batch calls.  A scan of 0 beams: residual +0, likelihood NaN.
+ * Two forms that give the same bits -- a wavefront per hypothesis b * W + w, or a lane per hypothesis with every window padded to
+ * whole wavefronts, so that the 64 lanes of a wavefront walk one scan; the entry chooses by batch * W, env HSM_WINDOW_FORM=lane|wave
+ * forces one, hsm_last_launch_kernel names the one that ran ("score_windows_batch_lane_kernel" / "score_windows_batch_wave_kernel").
+ * The reference's beam order in every parity mode: hsm_last_launch_parity reports HSM_PARITY_EXACT.
+ * Ordering, capture and locking: the contract of hsm_score_window_device -- reads the map only, needs no workspace, keeps no
+ * state, one kernel node under capture.  batch == 0: HSM_OK, nothing launched.
+ * HSM_ERR_INVALID (nothing launched): the refusals of hsm_score_window_device, batch < 0, batch * W > INT_MAX, NULL centres where
+ * batch > 0, shared_n < 0 without offsets, NULL points for a shared scan of shared_n > 0.
+ * Not built: replay through hsm_group_*, a C++ facade entry, a window shape per scan, non-maximum suppression among candidates. */
+int hsm_score_windows_batch_device(hsm_ctx* h, int level, int batch, const float* d_centers_world, const float step[3],
+                                   const int half[3], const float* d_pts_xy, const int* d_scan_offsets, int shared_n,
+                                   float* d_out_likelihood, float* d_out_residual, void* stream);
+/* the K best of each of `groups` runs of group_size scores, d_scores[g * group_size ..]: hsm_select_topk_device's rule (a NaN
+ * never takes part, the higher score first, equal scores the lower index first) for every group on its own.  d_out_index
+ * [groups * k], indices RELATIVE to the group, in rank order; d_out_score [groups * k] or NULL; unfilled places -1 and NaN.  Two
+ * launches however many groups: every group's slices reduced to k candidates each in the caller-owned d_workspace of at least
+ * hsm_select_topk_groups_workspace(groups, group_size, k) bytes (4-byte aligned), then one workgroup per group merges them.  No
+ * float atomics; a function of the scores alone; capturable; ordered by `stream` alone.  groups == 1: bit for bit
+ * hsm_select_topk_device, which is this launch.  groups == 0: HSM_OK, nothing launched.
+ * HSM_ERR_INVALID: NULL context, groups < 0, group_size < 0, k out of range, groups * group_size or groups * k above INT_MAX,
+ * NULL indices, NULL scores where group_size > 0, a workspace that is NULL, misaligned or too small. */
+int hsm_select_topk_groups_device(hsm_ctx* h, int groups, int group_size, const float* d_scores, int k, int* d_out_index,
+                                  float* d_out_score, void* d_workspace, size_t workspace_bytes, void* stream);
+/* host arithmetic, callable without a device; a multiple of 8; hsm_select_topk_workspace(group_size, k) for one group; 0 for
+ * refused sizes and for groups == 0 */
+size_t hsm_select_topk_groups_workspace(int groups, int group_size, int k);
+/* One call, everything queued on `stream` under one lock of the context, no host wait:
+ *   1. hsm_score_windows_batch_device on search_level (likelihoods into the workspace)
+ *   2. hsm_select_topk_groups_device, groups = batch, group_size = W
+ *   3. the start poses of the batch * k indices, index (b, r) around centre b (-1: three quiet NaNs)
+ *   4. hsm_match_score_batch_device on the batch * k pairs, candidate (b, r) against scan b, with score_level 0 and batch groups
+ *      of k;  then d_out_best_index[b] is replaced by the WINDOW index the winner's start came from (-1 if none).
+ * Per scan the outputs of hsm_relocalize_device: d_out_cand_pose [batch*k*3], d_out_cand_cov [batch*k*9] or NULL,
+ * d_out_cand_likelihood [batch*k], d_out_cand_index [batch*k] or NULL (the window indices of the starts, -1 for an unfilled
+ * place), d_out_best_pose [batch*3] (a scan without a winner leaves its three as they are), d_out_best_score [batch] or NULL,
+ * d_out_best_index [batch].  In the reference's summation order (the default) the same bits as batch calls of
+ * hsm_relocalize_device; in HSM_PARITY_FAST / _RELAXED the matcher's sums are those of ONE launch of batch * k pairs, whose form
+ * follows batch * k and the mean scan length -- the bits of the single calls where these plan the same form (DESIGN.md "which form
+ * runs when").
+ * The batch matcher takes one scan per pair, so CSR scans are first laid out k times in the workspace by a copy kernel.  The host
+ * must know the bytes: total_points is the caller's statement of d_scan_offsets[batch].  The copy clamps every scan into
+ * [0, total_points] and never writes beyond its region whatever the offsets hold (offsets that break the rule above give
+ * meaningless candidates, nothing else).  A shared scan is not copied, and total_points is not looked at.
+ * d_workspace: at least hsm_relocalize_batch_workspace(batch, W, k, total_points) bytes (total_points = 0 for a shared scan),
+ * 8-byte aligned.  Every argument is checked before the first launch.  Ordering is hsm_match_batch_device's; capturable (a replay
+ * with new centres or scans written into the same buffers gives the new answer).  batch == 0: HSM_OK, nothing launched.
+ * HSM_ERR_INVALID (nothing launched, outputs untouched): the refusals of hsm_score_windows_batch_device and of
+ * hsm_relocalize_device, batch * k > INT_MAX / 9, with offsets total_points < 0 or k * total_points > INT_MAX, a NULL required
+ * output, a workspace that is NULL, misaligned or too small.
+ * Not built: replay through hsm_group_*, a C++ facade entry, a window shape per scan, non-maximum suppression among candidates. */
+int hsm_relocalize_batch_device(hsm_ctx* h, int search_level, int batch, const float* d_centers_world, const float step[3],
+                                const int half[3], int k, const float* d_pts_xy, const int* d_scan_offsets, int shared_n,
+                                int total_points, void* d_workspace, size_t workspace_bytes, float* d_out_cand_pose,
+                                float* d_out_cand_cov, float* d_out_cand_likelihood, int* d_out_cand_index, float* d_out_best_pose,
+                                float* d_out_best_score, int* d_out_best_index, void* stream);
+/* host arithmetic, callable without a device; a multiple of 8; 0 for refused sizes (batch < 0, window_count < 1, k out of range,
+ * total_points < 0, batch * window_count or k * total_points above INT_MAX, batch * k above INT_MAX / 9) */
+size_t hsm_relocalize_batch_workspace(int batch, int window_count, int k, int total_points);
+/* the same with HOST pointers, built like hsm_relocalize (copies in, the chain on the context's stream, copies out; synchronous).
+ * scan_offsets (host) must start at 0 and not decrease; their last entry is the number of points.  out_cand_cov, out_cand_index
+ * and out_best_score may be NULL; out_best_pose is in/out. */
+int hsm_relocalize_batch(hsm_ctx* h, int search_level, int batch, const float* centers_world, const float step[3], const int half[3],
+                         int k, const float* pts_xy, const int* scan_offsets, int shared_n, float* out_cand_pose,
+                         float* out_cand_cov, float* out_cand_likelihood, int* out_cand_index, float* out_best_pose,
+                         float* out_best_score, int* out_best_index);
 
 /* ---- another context's map aligned to this one, ready to merge: occupied cells as a point set, then the relocalisation --------
  * No counterpart in the reference: an extension, like hsm_merge_map, whose src_in_dst this produces.  Two entries.
