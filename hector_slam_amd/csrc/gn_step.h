@@ -2,7 +2,7 @@
 // per-beam products and their accumulators, the two summation orders (the reference's chains through LDS; wavefront and team
 // all-reduces), the 3x3 solve, the residual chain, the sigma-point statistics and the (score, index) order of the scoring kernels, and how a launch says it
 // is done or takes part in the pose exchange.  Included by the matcher kernel headers (gn_match_teams.h, gn_match_cached.h,
-// gn_match_dense.h, gn_match_exact.h, gn_match_spec.h) and by score_kernels.h, window_kernels.h and probe_kernels.h.  No kernel
+// gn_match_dense.h, gn_match_exact.h, gn_match_spec.h), by pose_score.h for the scoring kernels and by probe_kernels.h.  No kernel
 // is defined here.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,6 +1,6 @@
 // probe_kernels.h -- the kernels that only the probes and test hooks launch (probes.hip): the test hooks of the map planes and of
-// libm_exact.h, one evaluation of the matcher's sums at a given pose, and the likelihood and covariance of map-frame poses.  Some
-// are not templates, so exactly one translation unit may include this header.
+// libm_exact.h, one evaluation of the matcher's sums at a given pose, and the likelihood and covariance of map-frame poses (the
+// likelihood itself: pose_score.h).  Some are not templates, so exactly one translation unit may include this header.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -9,6 +9,7 @@
 #include "libm_exact.h"
 #include "map_cells.h"
 #include "match_types.h"
+#include "pose_score.h"
 
 namespace hsm {
 
@@ -129,11 +130,8 @@ __global__ void gn_beam_terms_kernel(const LevelView L, const float2* __restrict
 }
 
 // ---- f3: pose likelihood for a batch of map-frame states against ONE scan --------
-// OccGridMapUtil::getLikelihoodForState (OccGridMapUtil.h:184-214): residual = sum_i (1 - M_i),
-// likelihood = 1 - residual / size, with M from interpMapValue (:233-285) -- the same bilinear sample
-// as the matcher without the gradient.  One wavefront per state, beams strided over the lanes, the
-// texel gather and the zero-texel treatment of out-of-map beams shared with the matcher (an
-// out-of-map beam reads M = 0, i.e. funval = 1, exactly the reference's `return 0.0f`).
+// OccGridMapUtil::getLikelihoodForState (OccGridMapUtil.h:184-214): residual = sum_i (1 - M_i), likelihood = 1 - residual / size.
+// One wavefront per state; sampler, padding and the two summation orders (EXACT: the reference's) are pose_score.h's.
 
 template <int LAYOUT, bool EXACT = false>
 __global__ void __launch_bounds__(256) likelihood_kernel(const LevelView L, const float* __restrict__ states,
@@ -144,39 +142,12 @@ __global__ void __launch_bounds__(256) likelihood_kernel(const LevelView L, cons
   const int lane = threadIdx.x & 63;
   const int b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (b >= batch) return;
-  const float ex = states[3 * b], ey = states[3 * b + 1];
-  float sinRot, cosRot;
-  sincos_f32(states[3 * b + 2], sinRot, cosRot);
-  const LevelRegs R = level_regs<LAYOUT>(L);
-  const f2 e2 = step_origin(ex, ey), cs = f2{cosRot, sinRot}, sc = f2{sinRot, cosRot};
-  float residual = 0.0f;
-  if (EXACT) {
-    float* row = rows[(threadIdx.x >> 6) & 3];
-    for (int base = 0; base < n; base += 64) {  // wave-uniform trip count
-      const int i = base + lane;
-      // padding beyond the scan: funval = +0 (M is only ever 0 .. 1, so no sum is -0 and +0 changes nothing)
-      float funval = 0.0f;
-      if (i < n) {
-        const float2 p = pts[i];
-        BeamRot r;
-        const BeamSample s = beam_fetch<LAYOUT>(R, e2, cs, sc, f2{p.x * pt_scale, p.y * pt_scale}, r);
-        const float M = ((s.lo.x * s.X.x + s.lo.y * s.X.y) * (s.Y.x)) + ((s.hi.x * s.X.x + s.hi.y * s.X.y) * (s.Y.y));
-        funval = 1.0f - M;
-      }
-      residual = exact_residual_round(funval, row, lane, residual);
-    }
-  } else {
-    for (int i = lane; i < n; i += 64) {
-      const float2 p = pts[i];
-      BeamRot r;
-      const BeamSample s = beam_fetch<LAYOUT>(R, e2, cs, sc, f2{p.x * pt_scale, p.y * pt_scale}, r);
-      const float M = ((s.lo.x * s.X.x + s.lo.y * s.X.y) * (s.Y.x)) + ((s.hi.x * s.X.x + s.hi.y * s.X.y) * (s.Y.y));
-      residual += 1.0f - M;
-    }
-    residual = wave_allreduce(residual);
-  }
+  const PoseFrame F = pose_frame_map<LAYOUT>(L, states[3 * b], states[3 * b + 1], states[3 * b + 2], pt_scale);
+  float residual;
+  if (EXACT) residual = residual_reference_order<LAYOUT>(F, pts, n, rows[(threadIdx.x >> 6) & 3], lane);
+  else residual = residual_tree_order<LAYOUT>(F, pts, n, lane);
   if (lane == 0) {
-    if (out_lh) out_lh[b] = 1 - (residual / (float)n);
+    if (out_lh) out_lh[b] = scan_likelihood(residual, n);
     if (out_residual) out_residual[b] = residual;  // getResidualForState (:205-221)
   }
 }
@@ -204,35 +175,11 @@ __global__ void __launch_bounds__(448) pose_covariance_kernel(const LevelView L,
 #pragma unroll
     for (int k = 1; k < 7; ++k)
       if (w == k) ex = sp[k][0], ey = sp[k][1], ea = sp[k][2];
-    float sinRot, cosRot;
-    sincos_f32(ea, sinRot, cosRot);
-    const LevelRegs R = level_regs<LAYOUT>(L);
-    const f2 e2 = step_origin(ex, ey), cs = f2{cosRot, sinRot}, sc = f2{sinRot, cosRot};
-    float residual = 0.0f;
-    if (EXACT) {
-      for (int base = 0; base < n; base += 64) {
-        const int i = base + lane;
-        float funval = 0.0f;
-        if (i < n) {
-          const float2 p = pts[i];
-          BeamRot r;
-          const BeamSample s = beam_fetch<LAYOUT>(R, e2, cs, sc, f2{p.x * pt_scale, p.y * pt_scale}, r);
-          const float M = ((s.lo.x * s.X.x + s.lo.y * s.X.y) * (s.Y.x)) + ((s.hi.x * s.X.x + s.hi.y * s.X.y) * (s.Y.y));
-          funval = 1.0f - M;
-        }
-        residual = exact_residual_round(funval, rows[w], lane, residual);
-      }
-    } else {
-      for (int i = lane; i < n; i += 64) {
-        const float2 p = pts[i];
-        BeamRot r;
-        const BeamSample s = beam_fetch<LAYOUT>(R, e2, cs, sc, f2{p.x * pt_scale, p.y * pt_scale}, r);
-        const float M = ((s.lo.x * s.X.x + s.lo.y * s.X.y) * (s.Y.x)) + ((s.hi.x * s.X.x + s.hi.y * s.X.y) * (s.Y.y));
-        residual += 1.0f - M;
-      }
-      residual = wave_allreduce(residual);
-    }
-    if (lane == 0) lh[w] = 1 - (residual / (float)n);
+    const PoseFrame F = pose_frame_map<LAYOUT>(L, ex, ey, ea, pt_scale);
+    float residual;
+    if (EXACT) residual = residual_reference_order<LAYOUT>(F, pts, n, rows[w], lane);
+    else residual = residual_tree_order<LAYOUT>(F, pts, n, lane);
+    if (lane == 0) lh[w] = scan_likelihood(residual, n);
   }
   __syncthreads();
   if (threadIdx.x != 0) return;

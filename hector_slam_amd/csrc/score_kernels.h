@@ -1,22 +1,20 @@
 // score_kernels.h -- the weighting, the covariance estimate and the ranking of batches of pose hypotheses (score_batch_kernel,
-// covariance_batch_kernel, select_best_kernel), launched by match.hip only.  Sampler: beam_sample.h; the residual chain, the
-// sigma-point statistics and the (score, index) order: gn_step.h.
+// covariance_batch_kernel, select_best_kernel), launched by match.hip only.  The likelihood of a scan at a pose -- frame, funval,
+// the two summation orders, scan b of a batch: pose_score.h; the sigma-point statistics and the (score, index) order: gn_step.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "beam_sample.h"
-#include "gn_step.h"
 #include "match_types.h"
+#include "pose_score.h"
 
 namespace hsm {
 
-// ---- the weighting step of a batch of pose hypotheses: likelihood_kernel for what hsm_match_batch_device returns --------------
+// ---- the weighting step of a batch of pose hypotheses, for what hsm_match_batch_device returns ---------------------------------
 // B (WORLD pose, scan) pairs in one launch: the scans a CSR batch (offsets in points) or one shared scan, the poses converted to
-// the level's map frame here (getMapCoordsPose, GridMapBase.h:235-239 -- the matchers' own first step), the endpoints scaled by
-// the level's 2^-level (DataContainer::setFrom).  One wavefront per hypothesis, four per workgroup; pose and CSR offsets are
-// read once per wavefront through the scalar unit.  Sampler, zero-texel treatment of out-of-map beams and the two summation
-// orders are likelihood_kernel's.  A scan of 0 beams: residual +0, likelihood 1 - 0/0 = NaN, as the reference computes it.
-// Reads the map, the poses and the scans; writes its two outputs; keeps no other state.
+// the level's map frame and the endpoints scaled by the level's 2^-level in the frame (pose_score.h pose_frame_world).  One
+// wavefront per hypothesis, four per workgroup; pose and CSR offsets are read once per wavefront through the scalar unit.  EXACT:
+// the reference's summation order, else the tree order.  A scan of 0 beams: residual +0, likelihood 1 - 0/0 = NaN, as the
+// reference computes it.  Reads the map, the poses and the scans; writes its two outputs; keeps no other state.
 template <int LAYOUT, bool EXACT>
 __global__ void __launch_bounds__(256) score_batch_kernel(const LevelView L, const float* __restrict__ poses_world, int batch,
                                                           const float2* __restrict__ pts_all,
@@ -26,46 +24,14 @@ __global__ void __launch_bounds__(256) score_batch_kernel(const LevelView L, con
   const int lane = threadIdx.x & 63;
   const int b = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)));  // wave-uniform
   if (b >= batch) return;
-  int beg = 0, n = shared_n;
-  if (offsets) {
-    beg = offsets[b];
-    n = offsets[b + 1] - beg;
-  }
-  const float2* __restrict__ pts = pts_all + beg;
-  float ex, ey;
-  affine_apply(L.mapTworld, poses_world[3 * b], poses_world[3 * b + 1], ex, ey);  // getMapCoordsPose
-  float sinRot, cosRot;
-  sincos_f32(poses_world[3 * b + 2], sinRot, cosRot);
-  const float pt_scale = L.pt_scale;
-  const LevelRegs R = level_regs<LAYOUT>(L);
-  const f2 e2 = step_origin(ex, ey), cs = f2{cosRot, sinRot}, sc = f2{sinRot, cosRot};
-  float residual = 0.0f;
-  if (EXACT) {
-    float* row = rows[(threadIdx.x >> 6) & 3];
-    for (int base = 0; base < n; base += 64) {  // wave-uniform trip count
-      const int i = base + lane;
-      float funval = 0.0f;  // padding beyond the scan: +0 changes no sum (see likelihood_kernel)
-      if (i < n) {
-        const float2 p = pts[i];
-        BeamRot r;
-        const BeamSample s = beam_fetch<LAYOUT>(R, e2, cs, sc, f2{p.x * pt_scale, p.y * pt_scale}, r);
-        const float M = ((s.lo.x * s.X.x + s.lo.y * s.X.y) * (s.Y.x)) + ((s.hi.x * s.X.x + s.hi.y * s.X.y) * (s.Y.y));
-        funval = 1.0f - M;
-      }
-      residual = exact_residual_round(funval, row, lane, residual);
-    }
-  } else {
-    for (int i = lane; i < n; i += 64) {
-      const float2 p = pts[i];
-      BeamRot r;
-      const BeamSample s = beam_fetch<LAYOUT>(R, e2, cs, sc, f2{p.x * pt_scale, p.y * pt_scale}, r);
-      const float M = ((s.lo.x * s.X.x + s.lo.y * s.X.y) * (s.Y.x)) + ((s.hi.x * s.X.x + s.hi.y * s.X.y) * (s.Y.y));
-      residual += 1.0f - M;
-    }
-    residual = wave_allreduce(residual);
-  }
+  int n;
+  const float2* __restrict__ pts = batch_scan(pts_all, offsets, shared_n, b, n);
+  const PoseFrame F = pose_frame_world<LAYOUT>(L, poses_world[3 * b], poses_world[3 * b + 1], poses_world[3 * b + 2]);
+  float residual;
+  if (EXACT) residual = residual_reference_order<LAYOUT>(F, pts, n, rows[(threadIdx.x >> 6) & 3], lane);
+  else residual = residual_tree_order<LAYOUT>(F, pts, n, lane);
   if (lane == 0) {
-    if (out_lh) out_lh[b] = 1 - (residual / (float)n);  // getLikelihoodForState (:184-203)
+    if (out_lh) out_lh[b] = scan_likelihood(residual, n);
     if (out_residual) out_residual[b] = residual;       // getResidualForState (:205-221)
   }
 }
@@ -79,20 +45,19 @@ __global__ void __launch_bounds__(256) score_batch_kernel(const LevelView L, con
 //
 // Sharing the rotated end point leaves every bit as it was: the reference applies Translation * Rotation to the point, which is
 // t + (R p) with R p evaluated first (beam_sample.h BeamRot), so R p does not depend on t; beam_fetch forms e + r from the same two
-// operations.  Sigma point 6 is the pose: its likelihood is score_batch_kernel's, bit for bit.
+// operations, and the funval of the sample is pose_score.h's beam_funval.  Sigma point 6 is the pose: its likelihood is
+// score_batch_kernel's, bit for bit.
 //
 // EXACT: the seven residuals are summed in the reference's beam order.  A round writes seven LDS rows of 64 funvals and lanes
 // 0 .. 6 each add their own row left to right, so one pass of 64 dependent additions advances all seven chains.  Row k is stored
 // rotated by 4 k floats, which keeps its float4s whole and puts the seven lanes' reads of one step into distinct banks.  Padding
-// beyond the scan contributes +0 (likelihood_kernel).  Else: lane-strided partial sums and a wave_allreduce per sigma point, the
+// beyond the scan contributes +0 (pose_score.h residual_reference_order).  Else: lane-strided partial sums and a wave_allreduce per sigma point, the
 // summation shape of pose_covariance_kernel<_, false>.  LDS: 7 x 64 x 4 B per wavefront (EXACT), none otherwise; no scratch.
 // A scan of 0 beams: every likelihood 1 - 0/0 = NaN and with them every covariance, as the reference computes it.
 // Lane 0 does the 7-term statistics (gn_step.h sigma_point_statistics, the probe's).  out_lh [B] = sigma point 6, contiguous.
 template <int LAYOUT>
 __device__ __forceinline__ float sigma_funval(const LevelRegs& R, f2 e, f2 r) {
-  const BeamSample s = sample_fetch<LAYOUT>(R, f2{e.x + r.x, e.y + r.y});
-  const float M = ((s.lo.x * s.X.x + s.lo.y * s.X.y) * (s.Y.x)) + ((s.hi.x * s.X.x + s.hi.y * s.X.y) * (s.Y.y));
-  return 1.0f - M;
+  return beam_funval(sample_fetch<LAYOUT>(R, f2{e.x + r.x, e.y + r.y}));
 }
 
 template <int LAYOUT, bool EXACT>
@@ -105,12 +70,8 @@ __global__ void __launch_bounds__(256) covariance_batch_kernel(const LevelView L
   const int lane = threadIdx.x & 63;
   const int b = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)));  // wave-uniform
   if (b >= batch) return;
-  int beg = 0, n = shared_n;
-  if (offsets) {
-    beg = offsets[b];
-    n = offsets[b + 1] - beg;
-  }
-  const float2* __restrict__ pts = pts_all + beg;
+  int n;
+  const float2* __restrict__ pts = batch_scan(pts_all, offsets, shared_n, b, n);
   float x, y;
   affine_apply(L.mapTworld, poses_world[3 * b], poses_world[3 * b + 1], x, y);  // getMapCoordsPose
   float sp[7][3];
@@ -161,7 +122,7 @@ __global__ void __launch_bounds__(256) covariance_batch_kernel(const LevelView L
         }
       }
     }
-    const float mine_lh = 1 - (run / (float)n);  // getLikelihoodForState (:184-203), in lane k for sigma point k
+    const float mine_lh = scan_likelihood(run, n);  // in lane k for sigma point k
 #pragma unroll
     for (int k = 0; k < 7; ++k) lh[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mine_lh), k));
   } else {
@@ -173,7 +134,7 @@ __global__ void __launch_bounds__(256) covariance_batch_kernel(const LevelView L
       for (int k = 0; k < 7; ++k) res[k] += fv[k];
     }
 #pragma unroll
-    for (int k = 0; k < 7; ++k) lh[k] = 1 - (wave_allreduce(res[k]) / (float)n);
+    for (int k = 0; k < 7; ++k) lh[k] = scan_likelihood(wave_allreduce(res[k]), n);
   }
   if (lane != 0) return;
   sigma_point_statistics(sp, lh, cell_length, out_lh7 ? out_lh7 + 7 * (size_t)b : nullptr,

@@ -4,8 +4,11 @@
 // window score -> top K -> poses -> match -> score on level 0 -> winner (hsm_relocalize_device, hsm_relocalize); and the same for
 // a batch of scans, each in its own window of one shared shape (hsm_score_windows_batch_device, hsm_select_topk_groups_device,
 // hsm_relocalize_batch_device, hsm_relocalize_batch): one launch per stage whatever the batch.  The kernels are
-// in window_kernels.h, the window's arithmetic and the workspace sizes in window_grid.h.  The scoring entries read the map like a
-// batched score and are ordered like one (MapReader of hsm_ctx.h); the chain's tail is match_chain_nolock of match.hip.
+// in window_kernels.h (the score of one hypothesis: pose_score.h), the window's arithmetic and the workspace sizes in
+// window_grid.h.  Single and batched entries differ in the score kernels they launch and in nothing else: one form rule on the
+// number of hypotheses, one launch helper (window_score_launch), one chain behind the score (relocalize_after_score, one group
+// or `batch` groups), one workspace layout.  The scoring entries read the map like a batched score and are ordered like one
+// (MapReader of hsm_ctx.h); the chain's tail is match_chain_nolock of match.hip.
 // Also here, because the chain ends in the relocalisation: a level's occupied cells as a point set (hsm_occupied_points*, the
 // kernels in map_points_kernels.h) and another context's map aligned to this one (hsm_align_map): extraction from the other
 // context, the counts fetched, the relocalisation of those points on this one.
@@ -28,16 +31,19 @@ static_assert(HSM_MAX_ALIGN_POINTS <= HSM_MAX_UPDATE_BEAMS, "an aligned point se
 
 namespace {
 
-// Windows of at least this many hypotheses take a lane per hypothesis, smaller ones a wavefront per hypothesis (either gives the
-// same bits).  Measured (profiles/r20/, 1081 beams, level 0 of the 2048^2 pyramid, lane against wave): 1 089 hypotheses 119
-// against 21 us, 4 225: 119 against 23, 35 301: 120 against 93, 269 001: 234 against 585 -- a lane-per-hypothesis launch is never
-// shorter than one lane's walk over the whole scan (119 us), the wave form grows by 1.9 us per 1000 hypotheses; they meet near
-// 52 000, and this is the nearest power of two.
+// Launches of at least this many hypotheses -- W of a single window, B * W of a batch of B -- take a lane per hypothesis, smaller
+// ones a wavefront per hypothesis (either gives the same bits).  A lane-per-hypothesis launch is never shorter than one lane's
+// walk over one whole scan, whatever the batch; the wave form grows by 1.9 us per 1000 hypotheses.  Measured, 1081-beam scans of
+// the 2048^2 pyramid, lane against wave.  One window on level 0 (profiles/r20/): 1 089 hypotheses 119 against 21 us, 4 225: 119
+// against 23, 35 301: 120 against 93, 269 001: 234 against 585; they meet near 52 000.  Batches on level 2 (profiles/r30/), B * W
+// hypotheses: 1 089: 137 against 18 us, 8 712: 139 against 31, 33 800: 140 against 82, 69 696: 145 against 150, 270 400: 247
+// against 536, 557 568: 434 against 1 118, 2 163 200: 1 277 against 4 225; they meet near 65 000.  This is the nearest power of
+// two to both.
 constexpr long long kWindowLaneMin = 1ll << 16;
 
-bool window_lane_form(const hsm_ctx* h, long long W) {
+bool window_lane_form(const hsm_ctx* h, long long hypotheses) {
   if (h->cfg.forms.window_form >= 0) return h->cfg.forms.window_form == 1;
-  return W >= kWindowLaneMin;
+  return hypotheses >= kWindowLaneMin;
 }
 
 // the refusals every window entry shares; *W: the window's size
@@ -52,17 +58,10 @@ int window_refusals(const hsm_ctx* h, const float* d_center, const float step[3]
   return HSM_OK;
 }
 
-// A batch of B windows of W hypotheses each: the lane form's floor is still one lane's walk over one scan, the wave form grows
-// with B * W -- so the rule is the single window's, on B * W.  Measured (profiles/r30/, 1081-beam scans, level 2 of the 2048^2
-// pyramid, lane against wave, B * W hypotheses): 1 089: 137 against 18 us, 8 712: 139 against 31, 33 800: 140 against 82, 69 696:
-// 145 against 150, 270 400: 247 against 536, 557 568: 434 against 1 118, 2 163 200: 1 277 against 4 225.  The wave form grows by
-// 1.9 us per 1000 hypotheses from 17 us and meets the lane form's floor (137-145 us) near 65 000: the single window's constant
-// is the batch's too.
-constexpr long long kWindowBatchLaneMin = kWindowLaneMin;
-
-bool window_batch_lane_form(const hsm_ctx* h, long long BW) {
-  if (h->cfg.forms.window_form >= 0) return h->cfg.forms.window_form == 1;
-  return BW >= kWindowBatchLaneMin;
+// a batch of none may come without centres: what window_refusals looks at in their place
+const float* centres_or_stand_in(int batch, const float* d_centers) {
+  static const float kAnyCentre[3] = {0.0f, 0.0f, 0.0f};
+  return batch > 0 ? d_centers : kAnyCentre;
 }
 
 WindowGrid window_grid(const float step[3], const int half[3]) { return WindowGrid{half[0], half[1], half[2], step[0], step[1], step[2]}; }
@@ -75,12 +74,40 @@ int score_window_refusals(const hsm_ctx* h, int level, const float* d_center, co
   return HSM_OK;
 }
 
-// one kernel on `s`; arguments checked, device selected, lock held
+// the kernels of one window entry, single or batched: [layout is quad][lane form], and the two names hsm_last_launch_kernel gives
+template <typename Params>
+struct WindowKernels {
+  void (*kernel[2][2])(LevelView, Params);
+  const char* name[2];
+};
+const WindowKernels<WindowParams> kSingleKernels = {
+    {{score_window_wave_kernel<kLayoutPlane>, score_window_lane_kernel<kLayoutPlane>},
+     {score_window_wave_kernel<kLayoutQuad>, score_window_lane_kernel<kLayoutQuad>}},
+    {"score_window_wave_kernel", "score_window_lane_kernel"}};
+const WindowKernels<WindowBatchParams> kBatchKernels = {
+    {{score_windows_batch_wave_kernel<kLayoutPlane>, score_windows_batch_lane_kernel<kLayoutPlane>},
+     {score_windows_batch_wave_kernel<kLayoutQuad>, score_windows_batch_lane_kernel<kLayoutQuad>}},
+    {"score_windows_batch_wave_kernel", "score_windows_batch_lane_kernel"}};
+
+// one kernel on `s`, as a reader of the map: the 2 x 2 choice over layout and form, `waves` wavefronts in workgroups of four
+template <typename Params>
+int window_score_launch(hsm_ctx* h, int level, const WindowKernels<Params>& K, bool lane, long long waves, const Params& P,
+                        const char* who, hipStream_t s) {
+  MapReader reader;
+  if (int rc = reader.begin(h, s, who)) return rc;
+  const LevelView v = level_view(h->levels[level], level_factor(level), 1);
+  hipLaunchKernelGGL(K.kernel[h->cfg.layout == kLayoutPlane ? 0 : 1][lane ? 1 : 0], dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s,
+                     v, P);
+  HIP_TRY(hipGetLastError());
+  reader.queued();
+  h->last.last_kernel = K.name[lane ? 1 : 0];
+  h->last.last_parity = HSM_PARITY_EXACT;  // a lane (or lane 0) owns the whole chain: the reference's order in every mode
+  return HSM_OK;
+}
+
+// the single kernels for one window; arguments checked, device selected, lock held
 int score_window_launch(hsm_ctx* h, int level, const float* d_center, const WindowGrid& G, int W, const float* d_pts, int n,
                         float* d_out_lh, float* d_out_res, hipStream_t s) {
-  MapReader reader;
-  if (int rc = reader.begin(h, s, "hsm_score_window_device")) return rc;
-  const LevelView v = level_view(h->levels[level], level_factor(level), 1);
   WindowParams P;
   P.grid = G;
   P.center = d_center;
@@ -90,19 +117,8 @@ int score_window_launch(hsm_ctx* h, int level, const float* d_center, const Wind
   P.out_lh = d_out_lh;
   P.out_residual = d_out_res;
   const bool lane = window_lane_form(h, W);
-  const unsigned grid = lane ? (unsigned)(((long long)W + 255) / 256) : (unsigned)(((long long)W + 3) / 4);
-  if (h->cfg.layout == kLayoutPlane) {
-    if (lane) hipLaunchKernelGGL((score_window_lane_kernel<kLayoutPlane>), dim3(grid), dim3(256), 0, s, v, P);
-    else hipLaunchKernelGGL((score_window_wave_kernel<kLayoutPlane>), dim3(grid), dim3(256), 0, s, v, P);
-  } else {
-    if (lane) hipLaunchKernelGGL((score_window_lane_kernel<kLayoutQuad>), dim3(grid), dim3(256), 0, s, v, P);
-    else hipLaunchKernelGGL((score_window_wave_kernel<kLayoutQuad>), dim3(grid), dim3(256), 0, s, v, P);
-  }
-  HIP_TRY(hipGetLastError());
-  reader.queued();
-  h->last.last_kernel = lane ? "score_window_lane_kernel" : "score_window_wave_kernel";
-  h->last.last_parity = HSM_PARITY_EXACT;  // a lane (or lane 0) owns the whole chain: the reference's order in every mode
-  return HSM_OK;
+  return window_score_launch(h, level, kSingleKernels, lane, lane ? ((long long)W + 63) / 64 : (long long)W, P,
+                             "hsm_score_window_device", s);
 }
 
 // the scans of a batched window entry: ScanBatch without poses
@@ -123,12 +139,9 @@ int window_batch_refusals(int batch, long long W, const float* d_centers, const 
   return HSM_OK;
 }
 
-// one kernel on `s` for `batch` >= 1 windows of W hypotheses; arguments checked, device selected, lock held
+// the batched kernels for `batch` >= 1 windows of W hypotheses; arguments checked, device selected, lock held
 int score_windows_batch_launch(hsm_ctx* h, int level, int batch, const float* d_centers, const WindowGrid& G, int W,
                                const WindowScans& S, float* d_out_lh, float* d_out_res, hipStream_t s) {
-  MapReader reader;
-  if (int rc = reader.begin(h, s, "hsm_score_windows_batch_device")) return rc;
-  const LevelView v = level_view(h->levels[level], level_factor(level), 1);
   WindowBatchParams P;
   P.grid = G;
   P.centers = d_centers;
@@ -139,22 +152,10 @@ int score_windows_batch_launch(hsm_ctx* h, int level, int batch, const float* d_
   P.shared_n = S.d_offsets ? 0 : S.shared_n;
   P.out_lh = d_out_lh;
   P.out_residual = d_out_res;
-  const bool lane = window_batch_lane_form(h, (long long)batch * W);
-  // lane form: every window padded to whole wavefronts; either form: four wavefronts per workgroup
-  const long long waves = lane ? (long long)batch * (((long long)W + 63) / 64) : (long long)batch * W;
-  const unsigned grid = (unsigned)((waves + 3) / 4);
-  if (h->cfg.layout == kLayoutPlane) {
-    if (lane) hipLaunchKernelGGL((score_windows_batch_lane_kernel<kLayoutPlane>), dim3(grid), dim3(256), 0, s, v, P);
-    else hipLaunchKernelGGL((score_windows_batch_wave_kernel<kLayoutPlane>), dim3(grid), dim3(256), 0, s, v, P);
-  } else {
-    if (lane) hipLaunchKernelGGL((score_windows_batch_lane_kernel<kLayoutQuad>), dim3(grid), dim3(256), 0, s, v, P);
-    else hipLaunchKernelGGL((score_windows_batch_wave_kernel<kLayoutQuad>), dim3(grid), dim3(256), 0, s, v, P);
-  }
-  HIP_TRY(hipGetLastError());
-  reader.queued();
-  h->last.last_kernel = lane ? "score_windows_batch_lane_kernel" : "score_windows_batch_wave_kernel";
-  h->last.last_parity = HSM_PARITY_EXACT;
-  return HSM_OK;
+  const bool lane = window_lane_form(h, (long long)batch * W);
+  // (lane form: every window padded to whole wavefronts)
+  return window_score_launch(h, level, kBatchKernels, lane, (long long)batch * (lane ? ((long long)W + 63) / 64 : (long long)W), P,
+                             "hsm_score_windows_batch_device", s);
 }
 
 // `count` indices of windows of W hypotheses, `per_window` of them in a row for each centre
@@ -214,42 +215,63 @@ int relocalize_refusals(const hsm_ctx* h, int search_level, const float* d_cente
   return HSM_OK;
 }
 
-// the chain on `s`; arguments checked, device selected, lock held
-int relocalize_queue(hsm_ctx* h, int search_level, const float* d_center, const WindowGrid& G, int W, int k, const float* d_pts,
-                     int n, char* ws, float* d_cand_pose, float* d_cand_cov, float* d_cand_lh, float* d_best_pose,
-                     float* d_best_score, int* d_best_index, hipStream_t s) {
-  const RelocalizeLayout L = relocalize_layout(W, k);
-  float* scores = reinterpret_cast<float*>(ws + L.scores);
-  int* kindex = reinterpret_cast<int*>(ws + L.index);
-  float* kscore = reinterpret_cast<float*>(ws + L.kscore);
-  float* kpose = reinterpret_cast<float*>(ws + L.pose);
-  if (int rc = score_window_launch(h, search_level, d_center, G, W, d_pts, n, scores, nullptr, s)) return rc;
-  if (int rc = select_topk_launch(1, W, scores, k, kindex, kscore, ws + L.topk, s)) return rc;
-  if (int rc = window_poses_launch(G, W, d_center, kindex, k, k, kpose, s)) return rc;
-  // the k starts against the one scan: match, the likelihood on level 0, the winner of the one group of k
-  if (int rc = match_chain_nolock(h, {k, kpose, d_pts, nullptr, n}, {d_cand_pose, d_cand_cov}, {0, {d_cand_lh}},
-                                  {1, nullptr, k, d_best_index, d_best_score, d_best_pose}, s))
-    return rc;
-  hipLaunchKernelGGL(window_best_index_kernel, dim3(1), dim3(256), 0, s, kindex, k, 1, d_best_index);
-  HIP_TRY(hipGetLastError());
-  return HSM_OK;
-}
-
-// ---- the chain for a batch of scans, each in its own window -----------------------------------------------------------------
-// the outputs of hsm_relocalize_batch*: device pointers for the device entry, host pointers in the host entry's refusals
-struct RelocalizeBatchOut {
+// the outputs of a relocalisation, `groups` * k candidates and `groups` winners: device pointers where it is queued, host pointers
+// in the batched host entry's refusals.  cand_index: the batched entries' alone
+struct RelocalizeOut {
   float *cand_pose, *cand_cov, *cand_lh;
   int* cand_index;
   float *best_pose, *best_score;
   int* best_index;
 };
 
+// The chain behind the window score on `s`, for `groups` >= 1 runs of W scores at ws + L.scores, run g around centre g against
+// scan g: the k best of every run, their poses, and the groups * k starts through match, likelihood on level 0 and the winner of
+// every group of k (match_chain_nolock), named by its window index.  Candidate (g, r) is matched against scan g: a shared scan
+// as it is; CSR scans laid out k times, since the matcher takes one scan per pair (its sizing hint: the mean length).  One
+// group with a shared scan is the single relocalisation: no copy, every grid 1.
+int relocalize_after_score(hsm_ctx* h, int groups, const float* d_centers, const WindowGrid& G, int W, int k, const WindowScans& S,
+                           int total_points, char* ws, const RelocalizeLayout& L, const RelocalizeOut& O, hipStream_t s) {
+  const int cands = groups * k;
+  const float* scores = reinterpret_cast<const float*>(ws + L.scores);
+  int* kindex = O.cand_index ? O.cand_index : reinterpret_cast<int*>(ws + L.index);
+  float* kscore = reinterpret_cast<float*>(ws + L.kscore);
+  float* kpose = reinterpret_cast<float*>(ws + L.pose);
+  if (int rc = select_topk_launch(groups, W, scores, k, kindex, kscore, ws + L.topk, s)) return rc;
+  if (int rc = window_poses_launch(G, W, d_centers, kindex, cands, k, kpose, s)) return rc;
+  ScanBatch pairs{cands, kpose, S.d_pts, nullptr, S.shared_n};
+  if (S.d_offsets) {
+    int* koffsets = reinterpret_cast<int*>(ws + L.offsets);
+    float2* kpts = reinterpret_cast<float2*>(ws + L.pts);
+    hipLaunchKernelGGL(replicate_scans_kernel, dim3((unsigned)cands), dim3(256), 0, s, reinterpret_cast<const float2*>(S.d_pts),
+                       S.d_offsets, groups, k, total_points, kpts, koffsets);
+    HIP_TRY(hipGetLastError());
+    pairs = ScanBatch{cands, kpose, reinterpret_cast<const float*>(kpts), koffsets, (total_points + groups - 1) / groups};
+  }
+  if (int rc = match_chain_nolock(h, pairs, {O.cand_pose, O.cand_cov}, {0, {O.cand_lh}},
+                                  {groups, nullptr, k, O.best_index, O.best_score, O.best_pose}, s))
+    return rc;
+  hipLaunchKernelGGL(window_best_index_kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, s, kindex, cands, groups,
+                     O.best_index);
+  HIP_TRY(hipGetLastError());
+  return HSM_OK;
+}
+
+// the single chain on `s`: the single window score, then one group against the one scan; arguments checked, device selected,
+// lock held
+int relocalize_queue(hsm_ctx* h, int search_level, const float* d_center, const WindowGrid& G, int W, int k, const float* d_pts,
+                     int n, char* ws, const RelocalizeOut& O, hipStream_t s) {
+  const RelocalizeLayout L = relocalize_layout(W, k);
+  if (int rc = score_window_launch(h, search_level, d_center, G, W, d_pts, n, reinterpret_cast<float*>(ws + L.scores), nullptr, s))
+    return rc;
+  return relocalize_after_score(h, 1, d_center, G, W, k, {d_pts, nullptr, n}, 0, ws, L, O, s);
+}
+
+// ---- the chain for a batch of scans, each in its own window -----------------------------------------------------------------
 int relocalize_batch_refusals(const hsm_ctx* h, int search_level, int batch, const float* d_centers, const float step[3],
-                              const int half[3], int k, const WindowScans& S, long long total_points, const RelocalizeBatchOut& O,
+                              const int half[3], int k, const WindowScans& S, long long total_points, const RelocalizeOut& O,
                               const char* who, long long* W) {
   if (int rc = valid_level(h, search_level)) return rc;
-  static const float kAnyCentre[3] = {0.0f, 0.0f, 0.0f};  // (a batch of none may come without centres)
-  if (int rc = window_refusals(h, batch > 0 ? d_centers : kAnyCentre, step, half, who, W)) return rc;
+  if (int rc = window_refusals(h, centres_or_stand_in(batch, d_centers), step, half, who, W)) return rc;
   long long BW = 0;
   if (int rc = window_batch_refusals(batch, *W, d_centers, S, who, &BW)) return rc;
   if (k < 1 || k > HSM_MAX_TOPK || (long long)batch * k > (long long)(INT_MAX / 9))
@@ -260,36 +282,15 @@ int relocalize_batch_refusals(const hsm_ctx* h, int search_level, int batch, con
   return HSM_OK;
 }
 
-// the chain on `s` for batch >= 1; arguments checked, device selected, lock held
+// the batched chain on `s` for batch >= 1: the batched window score, then `batch` groups; arguments checked, device selected,
+// lock held
 int relocalize_batch_queue(hsm_ctx* h, int search_level, int batch, const float* d_centers, const WindowGrid& G, int W, int k,
-                           const WindowScans& S, int total_points, char* ws, const RelocalizeBatchOut& O, hipStream_t s) {
-  const RelocalizeBatchLayout L = relocalize_batch_layout(batch, W, k, S.d_offsets ? total_points : 0);
-  const int cands = batch * k;
-  float* scores = reinterpret_cast<float*>(ws + L.scores);
-  int* kindex = O.cand_index ? O.cand_index : reinterpret_cast<int*>(ws + L.index);
-  float* kscore = reinterpret_cast<float*>(ws + L.kscore);
-  float* kpose = reinterpret_cast<float*>(ws + L.pose);
-  if (int rc = score_windows_batch_launch(h, search_level, batch, d_centers, G, W, S, scores, nullptr, s)) return rc;
-  if (int rc = select_topk_launch(batch, W, scores, k, kindex, kscore, ws + L.topk, s)) return rc;
-  if (int rc = window_poses_launch(G, W, d_centers, kindex, cands, k, kpose, s)) return rc;
-  // the batch * k starts, candidate (b, r) against scan b: a shared scan as it is; CSR scans laid out k times, since the matcher
-  // takes one scan per pair.  Its sizing hint: the mean length
-  ScanBatch pairs{cands, kpose, S.d_pts, nullptr, S.shared_n};
-  if (S.d_offsets) {
-    int* koffsets = reinterpret_cast<int*>(ws + L.offsets);
-    float2* kpts = reinterpret_cast<float2*>(ws + L.pts);
-    hipLaunchKernelGGL(replicate_scans_kernel, dim3((unsigned)cands), dim3(256), 0, s, reinterpret_cast<const float2*>(S.d_pts),
-                       S.d_offsets, batch, k, total_points, kpts, koffsets);
-    HIP_TRY(hipGetLastError());
-    pairs = ScanBatch{cands, kpose, reinterpret_cast<const float*>(kpts), koffsets, (total_points + batch - 1) / batch};
-  }
-  if (int rc = match_chain_nolock(h, pairs, {O.cand_pose, O.cand_cov}, {0, {O.cand_lh}},
-                                  {batch, nullptr, k, O.best_index, O.best_score, O.best_pose}, s))
+                           const WindowScans& S, int total_points, char* ws, const RelocalizeOut& O, hipStream_t s) {
+  const RelocalizeLayout L = relocalize_batch_layout(batch, W, k, S.d_offsets ? total_points : 0);
+  if (int rc = score_windows_batch_launch(h, search_level, batch, d_centers, G, W, S, reinterpret_cast<float*>(ws + L.scores),
+                                          nullptr, s))
     return rc;
-  hipLaunchKernelGGL(window_best_index_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, s, kindex, cands, batch,
-                     O.best_index);
-  HIP_TRY(hipGetLastError());
-  return HSM_OK;
+  return relocalize_after_score(h, batch, d_centers, G, W, k, S, total_points, ws, L, O, s);
 }
 
 // ---- occupied cells as points (map_points_kernels.h) ---------------------------------------------------------------------------------
@@ -425,9 +426,8 @@ int hsm_score_windows_batch_device(hsm_ctx* h, int level, int batch, const float
   const char* who = "hsm_score_windows_batch_device";
   if (!h) return fail(HSM_ERR_INVALID, "null context");
   if (int rc = valid_level(h, level)) return rc;
-  static const float kAnyCentre[3] = {0.0f, 0.0f, 0.0f};  // (a batch of none may come without centres)
   long long W = 0, BW = 0;
-  if (int rc = window_refusals(h, batch > 0 ? d_centers_world : kAnyCentre, step, half, who, &W)) return rc;
+  if (int rc = window_refusals(h, centres_or_stand_in(batch, d_centers_world), step, half, who, &W)) return rc;
   const WindowScans S{d_pts_xy, d_scan_offsets, shared_n};
   if (int rc = window_batch_refusals(batch, W, d_centers_world, S, who, &BW)) return rc;
   if (!d_out_likelihood && !d_out_residual) return fail_at(HSM_ERR_INVALID, who, ": both outputs are null");
@@ -452,8 +452,10 @@ int hsm_relocalize_device(hsm_ctx* h, int search_level, const float* d_center_wo
   std::lock_guard<std::mutex> lk(h->mu);
   if (int rc = select_device(h)) return rc;
   return relocalize_queue(h, search_level, d_center_world, window_grid(step, half), (int)W, k, d_pts_xy, n,
-                          static_cast<char*>(d_workspace), d_out_cand_pose, d_out_cand_cov, d_out_cand_likelihood, d_out_best_pose,
-                          d_out_best_score, d_out_best_index, static_cast<hipStream_t>(stream));
+                          static_cast<char*>(d_workspace),
+                          {d_out_cand_pose, d_out_cand_cov, d_out_cand_likelihood, nullptr, d_out_best_pose, d_out_best_score,
+                           d_out_best_index},
+                          static_cast<hipStream_t>(stream));
 }
 
 int hsm_relocalize(hsm_ctx* h, int search_level, const float center_world[3], const float step[3], const int half[3], int k,
@@ -472,9 +474,11 @@ int hsm_relocalize(hsm_ctx* h, int search_level, const float center_world[3], co
   char* base = h->d_batch;
   if (int rc = stage_copy_in(st.plan, base, h->stream)) return rc;
   if (int rc = relocalize_queue(h, search_level, staged<float>(base, st.center), window_grid(step, half), (int)W, k,
-                                staged<float>(base, st.pts), n, base + st.ws, staged<float>(base, st.pose),
-                                staged<float>(base, st.cov, out_cand_cov), staged<float>(base, st.lh), staged<float>(base, st.bpose),
-                                staged<float>(base, st.bscore, out_best_score), staged<int>(base, st.bidx), h->stream))
+                                staged<float>(base, st.pts), n, base + st.ws,
+                                {staged<float>(base, st.pose), staged<float>(base, st.cov, out_cand_cov), staged<float>(base, st.lh),
+                                 nullptr, staged<float>(base, st.bpose), staged<float>(base, st.bscore, out_best_score),
+                                 staged<int>(base, st.bidx)},
+                                h->stream))
     return rc;
   if (int rc = stage_copy_out(st.plan, base, h->stream)) return rc;
   HIP_TRY(hipStreamSynchronize(h->stream));
@@ -493,7 +497,7 @@ int hsm_relocalize_batch_device(hsm_ctx* h, int search_level, int batch, const f
   const char* who = "hsm_relocalize_batch_device";
   if (!h) return fail(HSM_ERR_INVALID, "null context");
   const WindowScans S{d_pts_xy, d_scan_offsets, shared_n};
-  const RelocalizeBatchOut O{d_out_cand_pose, d_out_cand_cov, d_out_cand_likelihood, d_out_cand_index,
+  const RelocalizeOut O{d_out_cand_pose, d_out_cand_cov, d_out_cand_likelihood, d_out_cand_index,
                              d_out_best_pose, d_out_best_score,  d_out_best_index};
   long long W = 0;
   if (int rc = relocalize_batch_refusals(h, search_level, batch, d_centers_world, step, half, k, S, total_points, O, who, &W)) return rc;
@@ -523,7 +527,7 @@ int hsm_relocalize_batch(hsm_ctx* h, int search_level, int batch, const float* c
   }
   if (total > 0 && !pts_xy) return fail_at(HSM_ERR_INVALID, who, ": null points");
   const WindowScans S{pts_xy, scan_offsets, shared_n};
-  const RelocalizeBatchOut O{out_cand_pose, out_cand_cov, out_cand_likelihood, out_cand_index, out_best_pose, out_best_score, out_best_index};
+  const RelocalizeOut O{out_cand_pose, out_cand_cov, out_cand_likelihood, out_cand_index, out_best_pose, out_best_score, out_best_index};
   long long W = 0;
   if (int rc = relocalize_batch_refusals(h, search_level, batch, centers_world, step, half, k, S, total, O, who, &W)) return rc;
   if (batch == 0) return HSM_OK;
@@ -538,7 +542,7 @@ int hsm_relocalize_batch(hsm_ctx* h, int search_level, int batch, const float* c
   char* base = h->d_batch;
   if (int rc = stage_copy_in(st.plan, base, h->stream)) return rc;
   const WindowScans DS{staged<float>(base, st.pts), staged<int>(base, st.offs, scan_offsets), shared_n};
-  const RelocalizeBatchOut DO{staged<float>(base, st.pose), staged<float>(base, st.cov, out_cand_cov), staged<float>(base, st.lh),
+  const RelocalizeOut DO{staged<float>(base, st.pose), staged<float>(base, st.cov, out_cand_cov), staged<float>(base, st.lh),
                               staged<int>(base, st.cidx, out_cand_index), staged<float>(base, st.bpose),
                               staged<float>(base, st.bscore, out_best_score), staged<int>(base, st.bidx)};
   if (int rc = relocalize_batch_queue(h, search_level, batch, staged<float>(base, st.centers), window_grid(step, half), (int)W, k, DS,
@@ -636,9 +640,10 @@ int hsm_align_map(hsm_ctx* dst, hsm_ctx* src, int src_level, const int src_bbox[
   if (reader.mark) reader.mark->pending = false;  // the read of `src` is over, under `src`'s lock: its next writer has nothing to wait for
   // (c) the points are a scan in `src`'s world frame, so the pose the matcher refines is src_in_dst
   if (int rc = relocalize_queue(dst, search_level, staged<float>(base, st.center), window_grid(step, half), (int)W, k,
-                                staged<float>(base, st.pts), cnt[0], base + st.ws, staged<float>(base, st.pose),
-                                staged<float>(base, st.cov), staged<float>(base, st.lh), staged<float>(base, st.bpose),
-                                staged<float>(base, st.bscore), staged<int>(base, st.bidx), dst->stream))
+                                staged<float>(base, st.pts), cnt[0], base + st.ws,
+                                {staged<float>(base, st.pose), staged<float>(base, st.cov), staged<float>(base, st.lh), nullptr,
+                                 staged<float>(base, st.bpose), staged<float>(base, st.bscore), staged<int>(base, st.bidx)},
+                                dst->stream))
     return rc;
   // (d) the winner
   if (int rc = stage_copy_out(st.plan, base, dst->stream)) return rc;

@@ -98,32 +98,18 @@ inline size_t topk_groups_workspace_bytes(long long groups, long long group_size
   return topk_groups_layout(groups, group_size, k).total;
 }
 
-// hsm_relocalize_device: the W scores, the top-K candidates, K indices, K scores and K start poses, each region 8-byte aligned
-struct RelocalizeLayout {
-  size_t scores, topk, index, kscore, pose, total;
-};
-inline RelocalizeLayout relocalize_layout(long long W, int k) {
-  RelocalizeLayout L = {0, 0, 0, 0, 0, 0};
-  if (W < 1 || W > (long long)INT_MAX || k < 1 || k > kMaxTopK) return L;
-  L.scores = 0;
-  L.topk = round_up8((size_t)W * sizeof(float));
-  L.index = L.topk + topk_workspace_bytes((int)W, k);
-  L.kscore = L.index + round_up8((size_t)k * sizeof(int));
-  L.pose = L.kscore + round_up8((size_t)k * sizeof(float));
-  L.total = L.pose + round_up8((size_t)k * 3 * sizeof(float));
-  return L;
-}
-
+// The relocalisation's workspace, single and batched: one layout, each region 8-byte aligned.
 // hsm_relocalize_batch_device, B scans with a window of W hypotheses each: the B*W scores, the grouped top-K candidates, B*K
 // indices, B*K scores, B*K start poses, and -- CSR scans -- every scan laid out K times for the matcher, which takes one scan per
 // pair: B*K + 1 offsets and max(K * total_points, 1) end points (one element at least: the matcher clamps an empty scan's loads to
-// element 0).  A shared scan is not copied: its caller passes total_points = 0.  Each region 8-byte aligned.  A total of 0: sizes
-// the entry refuses (B < 0, W < 1, k out of range, total_points < 0, B*W or K*total_points above INT_MAX, B*K above INT_MAX / 9)
-struct RelocalizeBatchLayout {
+// element 0).  A shared scan is not copied: its caller passes total_points = 0.  A total of 0: sizes the entry refuses (B < 0,
+// W < 1, k out of range, total_points < 0, B*W or K*total_points above INT_MAX, B*K above INT_MAX / 9)
+struct RelocalizeLayout {
   size_t scores, topk, index, kscore, pose, offsets, pts, total;
 };
-inline RelocalizeBatchLayout relocalize_batch_layout(long long B, long long W, int k, long long total_points) {
-  RelocalizeBatchLayout L = {0, 0, 0, 0, 0, 0, 0, 0};
+using RelocalizeBatchLayout = RelocalizeLayout;
+inline RelocalizeLayout relocalize_batch_layout(long long B, long long W, int k, long long total_points) {
+  RelocalizeLayout L = {0, 0, 0, 0, 0, 0, 0, 0};
   if (B < 0 || W < 1 || W > (long long)INT_MAX || k < 1 || k > kMaxTopK || total_points < 0) return L;
   if (B > (long long)INT_MAX || B * W > (long long)INT_MAX || B * k > (long long)(INT_MAX / 9) ||
       total_points > (long long)INT_MAX || total_points * k > (long long)INT_MAX)
@@ -137,6 +123,14 @@ inline RelocalizeBatchLayout relocalize_batch_layout(long long B, long long W, i
   L.offsets = L.pose + round_up8(bk * 3 * sizeof(float));
   L.pts = L.offsets + round_up8((bk + 1) * sizeof(int));
   L.total = L.pts + (copied > 0 ? copied : 1) * 2 * sizeof(float);
+  return L;
+}
+
+// hsm_relocalize_device: one scan in one window, never copied -- the batched layout's front (one group's W scores, top-K
+// candidates, K indices, K scores, K start poses), which ends behind the start poses.  0 for refused sizes
+inline RelocalizeLayout relocalize_layout(long long W, int k) {
+  RelocalizeLayout L = relocalize_batch_layout(1, W, k, 0);
+  L.total = L.pts = L.offsets;
   return L;
 }
 

@@ -1,13 +1,13 @@
 // window_kernels.h -- the kernels of window.hip: the likelihood of ONE scan at every pose of a window that never exists in memory
 // (two forms with the same bits), window indices turned into poses, and the K best of an array of scores; each with a batch
 // dimension too -- B scans in B windows of one shape, the K best of every group -- and the copy that lays a CSR batch of scans out
-// K times for the matcher.
+// K times for the matcher.  The score of one hypothesis is pose_score.h's: a window kernel only says which hypothesis a lane or
+// a wavefront is and where its centre, its scan and its output slot are.
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "beam_sample.h"
-#include "gn_step.h"
 #include "match_types.h"
+#include "pose_score.h"
 #include "window_grid.h"
 
 namespace hsm {
@@ -22,99 +22,9 @@ struct WindowParams {
   float* out_residual;  // [W] or null
 };
 
-__device__ __forceinline__ float window_beam_funval(const BeamSample& s) {
-  const float M = ((s.lo.x * s.X.x + s.lo.y * s.X.y) * (s.Y.x)) + ((s.hi.x * s.X.x + s.hi.y * s.X.y) * (s.Y.y));
-  return 1.0f - M;
-}
-
-// ---- one LANE per hypothesis ------------------------------------------------------------------------------------------------
-// Every lane walks beams 0 .. n-1 itself, so its running sum IS getResidualForState's chain: no LDS hand-over, no idle lanes.
-// The beam index is wave-uniform, so an end point is one scalar load that all 64 hypotheses share (no LDS copy of the scan: the
-// scalar cache serves it, and the workgroup needs no barrier).  kWindowUnroll texel gathers are issued before the first is used.
-// Lanes that are neighbours in x sample neighbouring texels.  The lanes behind the last hypothesis redo the last one (no
-// divergent exit; they write nothing).  Sampler, bounds and zero-texel treatment are beam_fetch's.
-constexpr int kWindowUnroll = 4;
-
-template <int LAYOUT>
-__global__ void __launch_bounds__(256) score_window_lane_kernel(const LevelView L, const WindowParams P) {
-  const long long wl = (long long)blockIdx.x * 256 + threadIdx.x;
-  const bool live = wl < P.count;
-  const int w = live ? (int)wl : P.count - 1;
-  float x, y, th;
-  window_pose(P.grid, P.center[0], P.center[1], P.center[2], w, x, y, th);
-  float ex, ey;
-  affine_apply(L.mapTworld, x, y, ex, ey);  // getMapCoordsPose
-  float sinRot, cosRot;
-  sincos_f32(th, sinRot, cosRot);
-  const float pt_scale = L.pt_scale;
-  const LevelRegs R = level_regs<LAYOUT>(L);
-  const f2 e2 = step_origin(ex, ey), cs = f2{cosRot, sinRot}, sc = f2{sinRot, cosRot};
-  const float2* __restrict__ pts = P.pts;
-  const int n = P.n;
-  float residual = 0.0f;
-  int i = 0;
-  for (; i + kWindowUnroll <= n; i += kWindowUnroll) {
-    BeamSample s[kWindowUnroll];
-#pragma unroll
-    for (int u = 0; u < kWindowUnroll; ++u) {
-      const float2 p = pts[i + u];
-      BeamRot r;
-      s[u] = beam_fetch<LAYOUT>(R, e2, cs, sc, f2{p.x * pt_scale, p.y * pt_scale}, r);
-    }
-#pragma unroll
-    for (int u = 0; u < kWindowUnroll; ++u) residual += window_beam_funval(s[u]);
-  }
-  for (; i < n; ++i) {
-    const float2 p = pts[i];
-    BeamRot r;
-    const BeamSample s = beam_fetch<LAYOUT>(R, e2, cs, sc, f2{p.x * pt_scale, p.y * pt_scale}, r);
-    residual += window_beam_funval(s);
-  }
-  if (!live) return;
-  if (P.out_lh) P.out_lh[w] = 1 - (residual / (float)n);  // getLikelihoodForState (:184-203); n == 0: NaN
-  if (P.out_residual) P.out_residual[w] = residual;       // getResidualForState (:205-221)
-}
-
-// ---- one WAVEFRONT per hypothesis: score_batch_kernel<LAYOUT, true> with the pose generated from w ----------------------------
-template <int LAYOUT>
-__global__ void __launch_bounds__(256) score_window_wave_kernel(const LevelView L, const WindowParams P) {
-  __shared__ float rows[4][64];
-  const int lane = threadIdx.x & 63;
-  const long long wl = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (wl >= P.count) return;  // (a whole wavefront)
-  const int w = __builtin_amdgcn_readfirstlane((int)wl);
-  float x, y, th;
-  window_pose(P.grid, P.center[0], P.center[1], P.center[2], w, x, y, th);
-  float ex, ey;
-  affine_apply(L.mapTworld, x, y, ex, ey);
-  float sinRot, cosRot;
-  sincos_f32(th, sinRot, cosRot);
-  const float pt_scale = L.pt_scale;
-  const LevelRegs R = level_regs<LAYOUT>(L);
-  const f2 e2 = step_origin(ex, ey), cs = f2{cosRot, sinRot}, sc = f2{sinRot, cosRot};
-  const float2* __restrict__ pts = P.pts;
-  const int n = P.n;
-  float residual = 0.0f;
-  float* row = rows[(threadIdx.x >> 6) & 3];
-  for (int base = 0; base < n; base += 64) {  // wave-uniform trip count
-    const int i = base + lane;
-    float funval = 0.0f;  // padding beyond the scan: +0 changes no sum (see likelihood_kernel)
-    if (i < n) {
-      const float2 p = pts[i];
-      BeamRot r;
-      funval = window_beam_funval(beam_fetch<LAYOUT>(R, e2, cs, sc, f2{p.x * pt_scale, p.y * pt_scale}, r));
-    }
-    residual = exact_residual_round(funval, row, lane, residual);
-  }
-  if (lane == 0) {
-    if (P.out_lh) P.out_lh[w] = 1 - (residual / (float)n);
-    if (P.out_residual) P.out_residual[w] = residual;
-  }
-}
-
-// ---- B windows of one shape, window b around centre b against scan b, in ONE launch -------------------------------------------
-// The two forms above with a batch dimension, and the same bits as B launches of them: a hypothesis' chain is its own whatever
-// else the launch holds.  The scans are a CSR batch or (offsets == nullptr) one scan of shared_n beams for every window.
+// B windows of one shape, window b around centre b against scan b, in ONE launch: the same bits as B launches of the single
+// kernels -- a hypothesis' chain is its own whatever else the launch holds.  The scans are a CSR batch or (offsets == nullptr) one
+// scan of shared_n beams for every window.
 struct WindowBatchParams {
   WindowGrid grid;
   const float* centers;  // [batch * 3] world poses, DEVICE memory
@@ -126,20 +36,43 @@ struct WindowBatchParams {
   float* out_residual;  // [batch * W] or null
 };
 
-// scan b of the batch; b wave-uniform, so the two offsets are scalar loads
-__device__ __forceinline__ const float2* window_batch_scan(const WindowBatchParams& P, int b, int& n) {
-  int beg = 0;
-  n = P.shared_n;
-  if (P.offsets) {
-    beg = P.offsets[b];
-    n = P.offsets[b + 1] - beg;
-  }
-  return P.pts + beg;
+// hypothesis w of the window around `center`, as a frame
+template <int LAYOUT>
+__device__ __forceinline__ PoseFrame window_frame(const LevelView& L, const WindowGrid& grid, const float* center, int w) {
+  float x, y, th;
+  window_pose(grid, center[0], center[1], center[2], w, x, y, th);
+  return pose_frame_world<LAYOUT>(L, x, y, th);
 }
 
-// A LANE per hypothesis.  Every window is padded to whole wavefronts, so a wavefront's 64 lanes walk ONE scan: the beam index and
-// the scan's base stay wave-uniform and an end point stays a scalar load.  The lanes behind a window's last hypothesis redo it and
-// write nothing.  A workgroup's four wavefronts may belong to different scans (no LDS, no barrier).
+// likelihood and residual of one hypothesis into slot `o` of the outputs that exist
+__device__ __forceinline__ void window_store(float* out_lh, float* out_residual, size_t o, float residual, int n) {
+  if (out_lh) out_lh[o] = scan_likelihood(residual, n);
+  if (out_residual) out_residual[o] = residual;       // getResidualForState (:205-221)
+}
+
+// ---- one LANE per hypothesis (pose_score.h residual_lane_chain) -----------------------------------------------------------------
+// Lane wl of a window's wavefronts takes hypothesis wl; the lanes behind the last hypothesis redo the last one (no divergent
+// exit; they write nothing).  Lanes that are neighbours in x sample neighbouring texels.  `slot`: where the window's scores begin.
+template <int LAYOUT>
+__device__ __forceinline__ void score_window_lane(const LevelView& L, const WindowGrid& grid, const float* center, int count,
+                                                  long long wl, const float2* __restrict__ pts, int n, float* out_lh,
+                                                  float* out_residual, size_t slot) {
+  const bool live = wl < count;
+  const int w = live ? (int)wl : count - 1;
+  const PoseFrame F = window_frame<LAYOUT>(L, grid, center, w);
+  const float residual = residual_lane_chain<LAYOUT>(F, pts, n);
+  if (live) window_store(out_lh, out_residual, slot + (size_t)w, residual, n);
+}
+
+template <int LAYOUT>
+__global__ void __launch_bounds__(256) score_window_lane_kernel(const LevelView L, const WindowParams P) {
+  score_window_lane<LAYOUT>(L, P.grid, P.center, P.count, (long long)blockIdx.x * 256 + threadIdx.x, P.pts, P.n, P.out_lh,
+                            P.out_residual, 0);
+}
+
+// Every window is padded to whole wavefronts, so a wavefront's 64 lanes walk ONE scan: the beam index and the scan's base stay
+// wave-uniform and an end point stays a scalar load.  A workgroup's four wavefronts may belong to different scans (no LDS, no
+// barrier).
 template <int LAYOUT>
 __global__ void __launch_bounds__(256) score_windows_batch_lane_kernel(const LevelView L, const WindowBatchParams P) {
   const int waves_per_window = (P.count + 63) >> 6;
@@ -147,83 +80,45 @@ __global__ void __launch_bounds__(256) score_windows_batch_lane_kernel(const Lev
   if (gw >= (long long)P.batch * waves_per_window) return;  // (a whole wavefront)
   const int b = __builtin_amdgcn_readfirstlane((int)(gw / waves_per_window));
   const int wv = __builtin_amdgcn_readfirstlane((int)(gw - (long long)b * waves_per_window));
-  const int wl = wv * 64 + (int)(threadIdx.x & 63);
-  const bool live = wl < P.count;
-  const int w = live ? wl : P.count - 1;
-  const float* __restrict__ center = P.centers + 3 * (size_t)b;
-  float x, y, th;
-  window_pose(P.grid, center[0], center[1], center[2], w, x, y, th);
-  float ex, ey;
-  affine_apply(L.mapTworld, x, y, ex, ey);  // getMapCoordsPose
-  float sinRot, cosRot;
-  sincos_f32(th, sinRot, cosRot);
-  const float pt_scale = L.pt_scale;
-  const LevelRegs R = level_regs<LAYOUT>(L);
-  const f2 e2 = step_origin(ex, ey), cs = f2{cosRot, sinRot}, sc = f2{sinRot, cosRot};
   int n;
-  const float2* __restrict__ pts = window_batch_scan(P, b, n);
-  float residual = 0.0f;
-  int i = 0;
-  for (; i + kWindowUnroll <= n; i += kWindowUnroll) {
-    BeamSample s[kWindowUnroll];
-#pragma unroll
-    for (int u = 0; u < kWindowUnroll; ++u) {
-      const float2 p = pts[i + u];
-      BeamRot r;
-      s[u] = beam_fetch<LAYOUT>(R, e2, cs, sc, f2{p.x * pt_scale, p.y * pt_scale}, r);
-    }
-#pragma unroll
-    for (int u = 0; u < kWindowUnroll; ++u) residual += window_beam_funval(s[u]);
-  }
-  for (; i < n; ++i) {
-    const float2 p = pts[i];
-    BeamRot r;
-    const BeamSample s = beam_fetch<LAYOUT>(R, e2, cs, sc, f2{p.x * pt_scale, p.y * pt_scale}, r);
-    residual += window_beam_funval(s);
-  }
-  if (!live) return;
-  const size_t o = (size_t)b * (size_t)P.count + (size_t)w;
-  if (P.out_lh) P.out_lh[o] = 1 - (residual / (float)n);  // n == 0: NaN
-  if (P.out_residual) P.out_residual[o] = residual;
+  const float2* pts = batch_scan(P.pts, P.offsets, P.shared_n, b, n);
+  score_window_lane<LAYOUT>(L, P.grid, P.centers + 3 * (size_t)b, P.count, wv * 64 + (int)(threadIdx.x & 63), pts, n, P.out_lh,
+                            P.out_residual, (size_t)b * (size_t)P.count);
 }
 
-// A WAVEFRONT per hypothesis g = b * W + w; a workgroup's four wavefronts may belong to different scans.
+// ---- one WAVEFRONT per hypothesis (pose_score.h residual_reference_order): score_batch_kernel<LAYOUT, true> with the pose
+// generated from w; lane 0 stores ----------------------------------------------------------------------------------------------
+template <int LAYOUT>
+__device__ __forceinline__ void score_window_wave(const LevelView& L, const WindowGrid& grid, const float* center, int w,
+                                                  const float2* __restrict__ pts, int n, float* __restrict__ row, float* out_lh,
+                                                  float* out_residual, size_t o) {
+  const int lane = threadIdx.x & 63;
+  const PoseFrame F = window_frame<LAYOUT>(L, grid, center, w);
+  const float residual = residual_reference_order<LAYOUT>(F, pts, n, row, lane);
+  if (lane == 0) window_store(out_lh, out_residual, o, residual, n);
+}
+
+template <int LAYOUT>
+__global__ void __launch_bounds__(256) score_window_wave_kernel(const LevelView L, const WindowParams P) {
+  __shared__ float rows[4][64];
+  const long long wl = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (wl >= P.count) return;  // (a whole wavefront)
+  const int w = __builtin_amdgcn_readfirstlane((int)wl);
+  score_window_wave<LAYOUT>(L, P.grid, P.center, w, P.pts, P.n, rows[(threadIdx.x >> 6) & 3], P.out_lh, P.out_residual, (size_t)w);
+}
+
+// hypothesis g = b * W + w; a workgroup's four wavefronts may belong to different scans
 template <int LAYOUT>
 __global__ void __launch_bounds__(256) score_windows_batch_wave_kernel(const LevelView L, const WindowBatchParams P) {
   __shared__ float rows[4][64];
-  const int lane = threadIdx.x & 63;
   const long long gl = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (gl >= (long long)P.batch * P.count) return;  // (a whole wavefront)
   const int g = __builtin_amdgcn_readfirstlane((int)gl);
   const int b = g / P.count, w = g - b * P.count;
-  const float* __restrict__ center = P.centers + 3 * (size_t)b;
-  float x, y, th;
-  window_pose(P.grid, center[0], center[1], center[2], w, x, y, th);
-  float ex, ey;
-  affine_apply(L.mapTworld, x, y, ex, ey);
-  float sinRot, cosRot;
-  sincos_f32(th, sinRot, cosRot);
-  const float pt_scale = L.pt_scale;
-  const LevelRegs R = level_regs<LAYOUT>(L);
-  const f2 e2 = step_origin(ex, ey), cs = f2{cosRot, sinRot}, sc = f2{sinRot, cosRot};
   int n;
-  const float2* __restrict__ pts = window_batch_scan(P, b, n);
-  float residual = 0.0f;
-  float* row = rows[(threadIdx.x >> 6) & 3];
-  for (int base = 0; base < n; base += 64) {  // wave-uniform trip count
-    const int i = base + lane;
-    float funval = 0.0f;  // padding beyond the scan: +0 changes no sum (see likelihood_kernel)
-    if (i < n) {
-      const float2 p = pts[i];
-      BeamRot r;
-      funval = window_beam_funval(beam_fetch<LAYOUT>(R, e2, cs, sc, f2{p.x * pt_scale, p.y * pt_scale}, r));
-    }
-    residual = exact_residual_round(funval, row, lane, residual);
-  }
-  if (lane == 0) {
-    if (P.out_lh) P.out_lh[g] = 1 - (residual / (float)n);
-    if (P.out_residual) P.out_residual[g] = residual;
-  }
+  const float2* pts = batch_scan(P.pts, P.offsets, P.shared_n, b, n);
+  score_window_wave<LAYOUT>(L, P.grid, P.centers + 3 * (size_t)b, w, pts, n, rows[(threadIdx.x >> 6) & 3], P.out_lh, P.out_residual,
+                            (size_t)g);
 }
 
 // ---- window indices -> poses ------------------------------------------------------------------------------------------------

@@ -34,6 +34,7 @@ ALL_BUT_EXCHANGE = set(build.UNITS) - {"pose_exchange.hip"}
 SHARED = {
     "texel_cache.h": {"match_teams.hip", "match_exact_cached.hip"},
     "gn_step.h": {"match_teams.hip", "match_exact_cached.hip", "match.hip", "window.hip", "probes.hip"},
+    "pose_score.h": {"match.hip", "window.hip", "probes.hip"},
     "match_types.h": ALL_BUT_EXCHANGE,
     "pose_exchange.h": set(build.UNITS),
 }

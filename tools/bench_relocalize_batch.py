@@ -28,7 +28,7 @@ LEVELS = 3
 SEARCH_LEVEL = 2
 WINDOWS = ((16, 16, 0), (32, 32, 0))  # 33 * 33, 65 * 65
 STEP = (0.05, 0.05, 0.0125)
-LANE_MIN = 1 << 16  # kWindowBatchLaneMin of csrc/window.hip: which form the one call picks
+LANE_MIN = 1 << 16  # kWindowLaneMin of csrc/window.hip: which form the one call picks
 
 
 def stats(us):
