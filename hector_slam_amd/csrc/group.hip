@@ -123,9 +123,11 @@ struct hsm_group {
   std::vector<ncclComm_t> comms;
   std::vector<Buf<float>> d_all_pose, d_all_cov;  // all-gather receive blocks of the replicas other than the root (likewise)
   std::string gather_note;                    // why AUTO settled on peer copies, if it did
-  // HSM_GATHER_DIRECT: one mailbox exchange per replica (pose_exchange.hip), re-made when the gathered row count changes
+  // HSM_GATHER_DIRECT: one mailbox exchange per replica (pose_exchange.hip), re-made when the gathered row count changes (x_rows
+  // = 0: at the next direct gather, whatever its row count)
   std::vector<hsm_exchange*> xpose, xcov;
   size_t x_rows = 0;
+  bool shares_device = false;  // a device is listed more than once: the direct gather posts and waits in two rounds
   std::mutex mu;  // one group call at a time
 };
 
@@ -264,6 +266,8 @@ int hsm_group_create(float map_resolution, int size_x, int size_y, unsigned leve
   }
   for (std::vector<Buf<float>>* v : {&g->d_pose, &g->d_cov, &g->d_all_pose, &g->d_all_cov}) v->resize((size_t)n_devices);
   g->evt.assign((size_t)n_devices, nullptr);
+  for (int a = 0; a < n_devices; ++a)
+    for (int b = a + 1; b < n_devices; ++b) g->shares_device = g->shares_device || g->members[(size_t)a]->device == g->members[(size_t)b]->device;
   if (const char* env = getenv("HSM_GROUP_GATHER")) {
     if (strcmp(env, "rccl") == 0) g->gather_pref = HSM_GATHER_RCCL;
     else if (strcmp(env, "peer") == 0) g->gather_pref = HSM_GATHER_PEER;
@@ -423,6 +427,11 @@ int hsm_group_match_batch_device(hsm_group* g, const int* counts, const float* c
       g->x_rows = total;
     }
   }
+  // Replicas that share a device may share a hardware queue (a process has a few, and more streams than that): a wait kernel
+  // that polls for rows a later launch in the same queue has yet to post stalls until its timeout.  Such a group posts in one
+  // round and waits in a second one, every wait behind the events of the posts made on its own device -- it polls only for
+  // rows that other devices store.  A group of distinct devices keeps the one launch per replica.
+  const bool split = direct && g->shares_device;
   bool equal = counts[0] > 0;  // ncclAllGather wants the same count from every rank
   for (int r = 1; r < R; ++r) equal = equal && counts[r] == counts[0];
   const bool self_send = rccl && g->force_p2p;  // test hook: the send / receive form for every shard, the root's own included
@@ -447,6 +456,11 @@ int hsm_group_match_batch_device(hsm_group* g, const int* counts, const float* c
       if (int rc2 = reserve_pair(g->d_all_pose[(size_t)r], g->d_all_cov[(size_t)r], total)) return rc2;
     if (n > 0) {
       if (int rc2 = reserve_pair(g->d_pose[(size_t)r], g->d_cov[(size_t)r], n)) return rc2;
+      // the Hessians are in/out: a scan without beams leaves its row as the caller gave it (ScanMatcher.h:68,189), so the
+      // shard's block starts from the caller's rows -- not from what an earlier call, or nobody, left in it
+      if (d_out_cov_all)
+        HIP_TRY(hipMemcpyPeerAsync(g->d_cov[(size_t)r], h->device, d_out_cov_all + 9 * first[(size_t)r], root_dev, n * 9 * sizeof(float),
+                                   h->stream));
       const ScanBatch shard{(int)n, d_begin_world[r], d_pts_xy[r], d_scan_offsets ? d_scan_offsets[r] : nullptr, shared_n};
       if (int rc2 = match_batch_device_nolock(h, shard, {g->d_pose[(size_t)r], d_out_cov_all ? g->d_cov[(size_t)r] : nullptr}, h->stream))
         return rc2;
@@ -461,6 +475,14 @@ int hsm_group_match_batch_device(hsm_group* g, const int* counts, const float* c
       }
     }
     if (direct && total > 0) {
+      if (split) {
+        // post only; the waits follow in a round of their own, behind this event
+        if (int rc2 = hsm_exchange_post(g->xpose[(size_t)r], g->d_pose[(size_t)r], (int)first[(size_t)r], (int)n, h->stream)) return rc2;
+        if (d_out_cov_all)
+          if (int rc2 = hsm_exchange_post(g->xcov[(size_t)r], g->d_cov[(size_t)r], (int)first[(size_t)r], (int)n, h->stream)) return rc2;
+        HIP_TRY(hipEventRecord(g->evt[(size_t)r], h->stream));
+        return HSM_OK;
+      }
       // ONE launch on this replica's stream, behind its match: store the shard's rows into every replica's mailbox and
       // unpack all shards' rows as they arrive -- the root into the caller's arrays, the others into blocks the group
       // keeps (every replica holds all poses afterwards: hsm_group_gathered).  No collective, no event, no host wait.
@@ -476,7 +498,26 @@ int hsm_group_match_batch_device(hsm_group* g, const int* counts, const float* c
     if (!rccl) HIP_TRY(hipEventRecord(g->evt[(size_t)r], h->stream));
     return HSM_OK;
   });
-  if (rc != HSM_OK) return rc;
+  if (rc == HSM_OK && direct && split && total > 0) {
+    // the second round: every post of this epoch has been queued and its event recorded.  Each replica's stream waits for the
+    // posts made on its own device, then ONE launch unpacks all shards' rows -- the root into the caller's arrays, the others
+    // into blocks the group keeps -- polling only for the rows that replicas on other devices store
+    rc = group_parallel(g, [&](int r) -> int {
+      hsm_ctx* h = g->members[(size_t)r];
+      std::lock_guard<std::mutex> lk(h->mu);
+      if (int rc2 = select_device(h)) return rc2;
+      for (int p = 0; p < R; ++p)
+        if (p != r && g->members[(size_t)p]->device == h->device) HIP_TRY(hipStreamWaitEvent(h->stream, g->evt[(size_t)p], 0));
+      if (int rc2 = hsm_exchange_wait(g->xpose[(size_t)r], r == root ? d_out_pose_all : g->d_all_pose[(size_t)r], h->stream)) return rc2;
+      if (d_out_cov_all)
+        if (int rc2 = hsm_exchange_wait(g->xcov[(size_t)r], r == root ? d_out_cov_all : g->d_all_cov[(size_t)r], h->stream)) return rc2;
+      return HSM_OK;
+    });
+  }
+  if (rc != HSM_OK) {
+    if (direct) g->x_rows = 0;  // (the replicas' epochs may have parted: the next direct gather makes its exchanges anew)
+    return rc;
+  }
   if (direct) return HSM_OK;
   if (rccl) {
     // ONE grouped collective over the group's communicators, each rank's part on its replica's stream (behind its match):

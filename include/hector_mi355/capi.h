@@ -355,7 +355,9 @@ int hsm_slam_scans_device_origos(hsm_ctx* h, int count, const float* d_start_pos
 typedef struct hsm_group hsm_group;
 /* how hsm_group_match_batch_device gathers.  AUTO (default; env HSM_GROUP_GATHER=auto|direct|rccl|peer at hsm_group_create):
  * DIRECT -- the device-side exchange below (hsm_exchange_*: every replica's kernel stores its rows into every replica's
- * mailbox, one launch per replica behind its match, no collective, no event) -- whenever the replicas' devices can access
+ * mailbox, one launch per replica behind its match, no collective, no event; where replicas share a device, a post and a wait
+ * launch per replica, the wait behind the events of that device's posts, so that no kernel polls for rows a launch queued
+ * behind it has yet to store) -- whenever the replicas' devices can access
  * each other (or are the same device); else RCCL when librccl loads, every replica sits on its own device and
  * ncclCommInitAll succeeds; else peer copies (hsm_group_gather_note says why).  DIRECT or RCCL asked for explicitly fail
  * instead of falling back. */
@@ -391,7 +393,11 @@ int hsm_group_process_scan(hsm_group* g, const float hint_world[3], const float*
  * order, into d_out_pose_all [sum(counts) * 3] on replica `root`'s device (and the Hessians into d_out_cov_all
  * [sum * 9] unless NULL): by the device-side exchange (one launch per replica on its own stream), by a grouped ncclAllGather
  * (equal counts) / ncclSend + ncclRecv (ragged counts) on the replicas' own streams, or by hipMemcpyPeerAsync on each replica's
- * own stream (hsm_group_set_gather).  Asynchronous: returns when
+ * own stream (hsm_group_set_gather).  d_out_cov_all is in/out as hsm_match_batch_device's is: a scan without beams passes its
+ * start estimate through and leaves its Hessian row as the caller gave it (every replica starts from the caller's rows of its
+ * shard: one copy of 36 bytes per scan on the replica's stream).  Like the shards themselves, d_out_cov_all is read on the
+ * replicas' streams, which are not ordered behind any stream of the caller: what the caller writes into it must be complete
+ * before the call.  Asynchronous: returns when
  * everything is queued; root's context stream is ordered behind the gather (hsm_synchronize(hsm_group_member(g, root)) or
  * hsm_group_synchronize wait for it). */
 int hsm_group_match_batch_device(hsm_group* g, const int* counts, const float* const* d_begin_world,

@@ -48,6 +48,31 @@ def stream_ptr():
     return torch.cuda.current_stream().cuda_stream
 
 
+_hip = None
+
+
+def hip_runtime():
+    """the HIP runtime this process has loaded (the one the library and torch are bound to), as a ctypes handle"""
+    global _hip
+    if _hip is None:
+        import ctypes
+        paths = {line.split()[-1] for line in open("/proc/self/maps") if "libamdhip64" in line}
+        assert len(paths) == 1, f"expected one loaded libamdhip64, found {sorted(paths)}"
+        _hip = ctypes.CDLL(paths.pop())
+        _hip.hipMemcpy.restype = ctypes.c_int
+        _hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
+    return _hip
+
+
+def device_to_host(ptr, shape, dtype=np.float32):
+    """what a raw device pointer holds, as a host array of `shape`: a blocking hipMemcpy, device to host"""
+    assert ptr, "null device pointer"
+    out = np.empty(shape, dtype)
+    rc = hip_runtime().hipMemcpy(out.ctypes.data, int(ptr), out.nbytes, 2)  # hipMemcpyDeviceToHost
+    assert rc == 0, f"hipMemcpy failed ({rc})"
+    return out
+
+
 def pack(scans):
     """a scan log as CSR: float32 points [n, 2] and int32 offsets [len(scans) + 1]; an empty log is a (0, 2) array"""
     offs = np.zeros(len(scans) + 1, np.int32)
